@@ -382,7 +382,11 @@ class SdcEngine:
 
     def set_state(self, name: str, value):
         a = self._state_array(name)
-        a[...] = value
+        if (isinstance(value, np.ndarray) and value.dtype == a.dtype and value.shape == a.shape and
+                value.flags.c_contiguous):
+            a = value       # already in the library's layout: no host copy (a batch's rings are GBs)
+        else:
+            a[...] = value
         L.check(self.lib.sdc_set_state(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), a.nbytes))
 
     def state_dict(self) -> dict:

@@ -27,7 +27,7 @@ def test_default_step_kernel_of_large_batches_production_vs_oracle(N):
     """The default kernel of a large batch (debug_flags = 0) -- four envs per wavefront at 6 144 envs, ONE LANE PER ENV (sdc_wide.hip)
     from 7 680 -- at the sizes rates are quoted for up to 32 768 envs: 330 single steps over two auto-resets, the first / last
     wavefronts and both sides of every occupancy round sampled, every reward-state path."""
-    rig = ProductionRig(N, debug_flags=0, episode_steps=120, seed=1000 + N, envs_per_wave=4)
+    rig = ProductionRig(N, "quad" if N < 7680 else "wide", debug_flags=0, episode_steps=120, seed=1000 + N)
     assert len(rig.sample) >= 72
     obs, _ = rig.eng.reset()
     rig.begin_all(obs)
@@ -49,8 +49,8 @@ def test_lane_per_env_kernel_equals_four_per_wavefront_for_every_env(N):
     other kernel from the ring --, 260 single steps over two auto-resets under the full load of deferred re-centrings -- every output
     of every env the same bits (the diagnostics column aside: it says which path served the reward state), and at the end the rings."""
     import torch
-    a = ProductionRig(N, debug_flags=0, episode_steps=120, seed=515, envs_per_wave=4, n_random=0)
-    b = ProductionRig(N, debug_flags=4096, episode_steps=120, seed=515, envs_per_wave=4, n_random=0)
+    a = ProductionRig(N, "wide", debug_flags=0, episode_steps=120, seed=515, n_random=0, oracles=False)
+    b = ProductionRig(N, "quad", debug_flags=4096, episode_steps=120, seed=515, n_random=0, oracles=False)
     a.eng.reset()
     b.eng.reset()
     g = torch.Generator(device="cpu").manual_seed(515)
@@ -77,7 +77,7 @@ def test_lane_per_env_kernel_equals_four_per_wavefront_for_every_env(N):
 def test_quad_step_kernel_32768_envs_vs_oracle():
     """... and the four-envs-per-wavefront kernel at 32 768 envs (debug_flags bit 12 keeps the lane-per-env kernel off): the mapping
     the closed loop (and `sdc_rollout` with `actions_out` / unaligned outputs) still runs at that size."""
-    rig = ProductionRig(32768, debug_flags=4096, episode_steps=120, seed=33768, envs_per_wave=4)
+    rig = ProductionRig(32768, "quad", debug_flags=4096, episode_steps=120, seed=33768)
     obs, _ = rig.eng.reset()
     rig.begin_all(obs)
     rig.single_steps(150)
@@ -89,8 +89,9 @@ def test_quad_step_kernel_32768_envs_vs_oracle():
 def test_65536_envs_production_vs_oracle():
     """The largest batch a rate is quoted for (`secondary.batch_scan`): 65 536 envs on the lane-per-env kernel, production
     configuration, 150 single steps over an auto-reset; first / last wavefronts, both sides of every occupancy round and a random
-    spread sampled against the oracle."""
-    rig = ProductionRig(65536, debug_flags=0, episode_steps=120, seed=65536, envs_per_wave=4, n_random=40)
+    spread sampled against the oracle.  env_index_base 2^20: the device's reset draws, keyed on the GLOBAL env index, are held to
+    their NumPy restatement (tests/production_rig.py check_draws)."""
+    rig = ProductionRig(65536, "wide", debug_flags=0, episode_steps=120, seed=65536, n_random=40, env_index_base=1 << 20)
     obs, _ = rig.eng.reset()
     rig.begin_all(obs)
     rig.single_steps(150)
@@ -105,7 +106,7 @@ def test_config3_mixed_racks_32768_production():
     """BASELINE configs[3] at the size of configs[4]: 32 768 envs, rack count 20 / 16 / 25 by env_id % 3, three locations -- nine
     configs in every wavefront -- on the lane-per-env kernel's general form (what `secondary.mixed_racks_32768` times), full rings,
     debug_flags = 0, 330 steps over two auto-resets vs the oracle."""
-    rig = ProductionRig(32768, debug_flags=0, mixed=True, episode_steps=120, seed=3303, envs_per_wave=4)
+    rig = ProductionRig(32768, "wide_gen", debug_flags=0, mixed=True, episode_steps=120, seed=3303)
     combos = {(int(rig.loc_id[i]), int(rig.cfg_id[i])) for i in rig.sample}
     assert len(combos) == 9, combos
     obs, _ = rig.eng.reset()
@@ -127,7 +128,7 @@ def test_policy_and_tou_rollouts_16384_on_the_general_form_vs_oracle():
     utils/trim_and_respond.py:28-38 on the room temperature the previous step reported)."""
     import torch
     N, limit = 16384, 34.9
-    rig = ProductionRig(N, debug_flags=0, mixed=True, episode_steps=120, seed=1616, envs_per_wave=4, reward_method=(0, 3, 6),
+    rig = ProductionRig(N, "wide_gen", debug_flags=0, mixed=True, episode_steps=120, seed=1616, reward_method=(0, 3, 6),
                         policy=(1, 3, 2), trim_and_respond_limit=limit)
     eng = rig.eng
     obs, _ = eng.reset()
@@ -171,7 +172,7 @@ def test_policy_and_tou_rollouts_16384_on_the_general_form_vs_oracle():
 def test_config3_mixed_racks_4096_production():
     """BASELINE configs[3]: 4096 envs, rack count 20 / 16 / 25 by env_id % 3, three locations, debug_flags = 0 (what the bench's
     `secondary.mixed_racks` times), full rings, 330 steps over two auto-resets vs the oracle."""
-    rig = ProductionRig(4096, debug_flags=0, mixed=True, episode_steps=120, seed=303, envs_per_wave=2)
+    rig = ProductionRig(4096, "pair", debug_flags=0, mixed=True, episode_steps=120, seed=303)
     # every (location, rack count) combination is in the sample
     combos = {(int(rig.loc_id[i]), int(rig.cfg_id[i])) for i in rig.sample}
     assert len(combos) == 9, combos
@@ -193,7 +194,7 @@ def test_rollout_16384_envs_full_rings_vs_oracle(flags, kernel):
     kernel off: ONE launch of `sdc_rollout_quad_kernel` per call (still what serves unaligned outputs / `actions_out`)."""
     import torch
     N = 16384
-    rig = ProductionRig(N, debug_flags=flags, episode_steps=120, seed=555, envs_per_wave=4)
+    rig = ProductionRig(N, "wide" if flags == 0 else "quad", debug_flags=flags, episode_steps=120, seed=555)
     eng = rig.eng
     obs, _ = eng.reset()
     rig.begin_all(obs)
@@ -221,7 +222,7 @@ def test_rollout_actor_16384_envs_full_rings_vs_oracle():
     the oracle steps the sampled envs under the actions the in-kernel actors chose (`actions_out`)."""
     from tests.test_gpu_actor import _torch_actor
     N = 16384
-    rig = ProductionRig(N, debug_flags=0, episode_steps=120, seed=556, envs_per_wave=4)
+    rig = ProductionRig(N, "wide", debug_flags=0, episode_steps=120, seed=556)
     eng = rig.eng
     for a in range(3):
         eng.set_actor(a, _torch_actor(60 + a, "tanh").state_dict())
@@ -247,7 +248,7 @@ def test_real_episode_length_4096_production_vs_oracle():
     """The bench's own episode shape -- 4096 envs, 672-step (7-day) episodes, debug_flags 0, rings full -- over two whole
     episodes and into a third (1400 steps, two auto-resets 672 steps apart): the long horizon the 120-step rigs do not reach
     (a rank window re-centred ~every 600 steps per env: every sampled env goes through several deferred take-overs)."""
-    rig = ProductionRig(4096, debug_flags=0, episode_steps=672, seed=909, envs_per_wave=2, n_random=40)
+    rig = ProductionRig(4096, "pair", debug_flags=0, episode_steps=672, seed=909, n_random=40)
     obs, _ = rig.eng.reset()
     rig.begin_all(obs)
     rig.single_steps(1400)

@@ -27,7 +27,7 @@ def test_timed_configuration_4096_envs_vs_oracle():
     (The recipe lives in tests/production_rig.py; tests/test_gpu_production_sizes.py runs it at the other sizes / kernels
     the bench line quotes.)"""
     from tests.production_rig import ProductionRig
-    rig = ProductionRig(4096, debug_flags=0, episode_steps=120, seed=77, envs_per_wave=2)
+    rig = ProductionRig(4096, "pair", debug_flags=0, episode_steps=120, seed=77)
     assert len(rig.sample) >= 64
     obs, _ = rig.eng.reset()
     rig.begin_all(obs)

@@ -97,6 +97,18 @@ def test_no_scratch_and_register_budget(compiled):
     print({k: (usage[k]["VGPRs"], usage[k]["Occupancy"]) for k in STEP_KERNELS + LOOP_KERNELS + ["sdc_dynamics_wide_kernel"]})
 
 
+def test_sampler_residency_matches_the_compiled_kernels(compiled):
+    """tests/production_rig.py samples both sides of every occupancy round of the step kernel under test: the workgroups per CU
+    its GEOMETRY table assumes must be what the compiled kernels allow -- the wavefronts per SIMD the registers leave (the
+    compiler's occupancy) over the workgroup's wavefronts, or the CU's LDS over the workgroup's, whichever is fewer."""
+    from tests.production_rig import GEOMETRY, LDS_PER_CU, SIMDS_PER_CU
+    _, usage = compiled
+    for mapping, g in GEOMETRY.items():
+        u = usage[g.kernel]
+        per_cu = min(SIMDS_PER_CU * u["Occupancy"] // g.waves_per_wg, LDS_PER_CU // max(1, u.get("LDS Size", 0)))
+        assert per_cu == g.wgs_per_cu, (mapping, g, u)
+
+
 def _kernel_body(asm, name):
     lines = asm.split("\n")
     i0 = next(i for i, l in enumerate(lines) if l.startswith(name + ":"))
