@@ -21,6 +21,13 @@ as DIR/<name>.npy (float32; at most 64 MB in all, a fixed seeded sample of env r
 inputs (tables, seeds, action pool, number of steps before the dump) depend only on the arguments, so two builds can
 be compared output for output.  (It refuses --repeats 0: the number of timed steps would come from a wall-clock estimate.)
 
+A plain run does only what the headline needs: set-up, history fill, warm-up, calibration, the timed region, the dump, the
+line.  Its `roofline` is priced from the timed region's own HIP events and in-kernel stamps, with the stored counters of
+profiles/pmc_latest.json.  `--full` adds everything that takes runs of its own, after the timed region: the live PMC passes,
+the episode boundary's cost (`episode_boundary`), `rollout`, `closed_loop`, the `secondary` lines (other shapes, batch
+sizes and rack mixes, with counter passes of their own) and the CPU baseline (`cpu_baseline`); `--no-pmc`,
+`--no-rollout`, `--no-secondary` and `--no-cpu-baseline` leave single parts of it out.
+
 Roofline (`roofline`): SURVEY.md 8(d) bounds the path by HBM (8 TB/s) and prices an env-step at B(H) = 4*H + 1540 bytes, asking
 for the fraction with AND without the history term because an incremental implementation does not move the 4*H bytes.  This
 step is ONE kernel that keeps the reward normalisation's order statistics incrementally, so:
@@ -31,9 +38,9 @@ step is ONE kernel that keeps the reward normalisation's order statistics increm
       time / 8 TB/s (physical), `traffic_over_alg_bytes` = traffic / (1540 x envs): re-reads and layout overhead;
   `valu_busy_frac` = SQ_ACTIVE_INST_VALU x 4 / the SIMD-cycles of the launch: what the kernel is actually bound by (wave-uniform
       fp64 physics issued once per pair / quad of envs), `issue_frac` likewise for every instruction class.
-The PMC counters are collected in this very run (rank 0, N = 1) by short `rocprofv3 --pmc ... --kernel-trace` passes over
-`bench.py --pmc-inner`; if rocprofv3 is not usable the numbers fall back to profiles/pmc_latest.json, which carries the hash of
-the kernel sources it was measured at (`pmc_source`, `pmc_current`).
+With `--full` the PMC counters are collected in this very run (rank 0, N = 1) by short `rocprofv3 --pmc ... --kernel-trace`
+passes over `bench.py --pmc-inner`; without it, or if rocprofv3 is not usable, the numbers come from profiles/pmc_latest.json,
+which carries the hash of the kernel sources it was measured at (`pmc_source`, `pmc_current`).
 
 Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line (rank 0).  For N > 1 it runs one rank
 per GPU over RCCL: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
@@ -578,9 +585,13 @@ def main():
     ap.add_argument("--envs-per-gpu", type=int, default=4096)
     ap.add_argument("--episode-steps", type=int, default=672)
     ap.add_argument("--mixed-racks", action="store_true", help="BASELINE configs[3]: 16/20/25-rack mix")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 counter passes (use profiles/pmc_latest.json)")
-    ap.add_argument("--no-rollout", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure what takes runs of its own: live PMC passes, episode boundary, rollout, "
+                         "closed loop, secondary lines, CPU baseline (a run of one rank)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true",
+                    help="--full without the rocprofv3 counter passes (profiles/pmc_latest.json instead)")
+    ap.add_argument("--no-rollout", action="store_true", help="--full without the rollout and closed-loop lines")
     ap.add_argument("--no-fill", action="store_true", help="skip the history fill (debug only; invalid as a result)")
     ap.add_argument("--repeats", type=int, default=1, help="blocks of --steps in the timed region (0 = until >= 200 ms)")
     ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
@@ -589,7 +600,8 @@ def main():
     ap.add_argument("--pmc-inner", action="store_true", help=argparse.SUPPRESS)   # the run rocprofv3 wraps
     ap.add_argument("--launch-check", action="store_true",
                     help="only launch the ranks, rendezvous, all-reduce once and print the skeleton line (no device needed)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary lines (HARL YAML shape, batch scan, closed loop)")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="--full without the secondary lines (HARL YAML shape, rack mixes, batch scan)")
     ap.add_argument("--single-process", action="store_true",
                     help="--gpus N devices driven from THIS process (one handle + one stream per device, no torch.distributed): "
                          "the form a single-process HARL runner uses (dc_rl_amd.multi_device)")
@@ -787,7 +799,7 @@ def main():
     block_ms = np.array([evs[j].elapsed_time(evs[j + 1]) / nb[j] for j in range(len(evs) - 1)])   # per block of K steps
     ev_ms = float(sum(evs[j].elapsed_time(evs[j + 1]) for j in range(len(evs) - 1)))
     prof = eng.profile_read(reset=True)
-    if prof["steps"] == 0:     # profiling was off in the timed region: sample the kernels in a short extra pass
+    if prof["steps"] == 0 and args.full:     # profiling was off in the timed region: sample the kernels in a short extra pass
         eng.profile(1)
         for i in range(64):
             one_step(i)
@@ -824,7 +836,7 @@ def main():
     # the amortised cost of the episode boundary (device-side reset + the episode's feature rows), measured on its own:
     # it is inside `value` (auto-resets happen in the timed region) but not inside the step kernel's duration
     reset_us = None
-    if world == 1:
+    if world == 1 and args.full:
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -839,8 +851,8 @@ def main():
         total_envs = N * world
         value = total_envs * timed_steps / dt
         b = alg_bytes_per_env_step(hlen)
-        nst = max(1, prof["steps"])
-        k_dyn = prof["dynamics_ms"] / nst * 1e-3     # first wavefront's entry -> last one's exit, in-kernel stamps
+        # first wavefront's entry -> last one's exit, in-kernel stamps (none with --profile-every 0 and no --full)
+        k_dyn = prof["dynamics_ms"] / prof["steps"] * 1e-3 if prof["steps"] else None
         # the step is ONE kernel: HIP-event time over the timed launches / launches = its average launch duration
         # with the dispatch gaps between back-to-back launches (and the ~1/672 auto-resets) included
         k_evt = ev_ms * 1e-3 / timed_steps
@@ -881,7 +893,7 @@ def main():
         pmc, pmc_err, pmc_src = None, None, None
         here = csrc_hash()
         latest = os.path.join(ROOT, "profiles", "pmc_latest.json")
-        if world == 1 and not args.no_pmc:
+        if world == 1 and args.full and not args.no_pmc:
             c, pmc_err = pmc_collect(args)
             if c is not None:
                 pmc, pmc_src = pmc_summary(c), "this run (rocprofv3 --pmc passes over bench.py --pmc-inner)"
@@ -925,7 +937,7 @@ def main():
             "issue_frac": round(issue_frac, 4) if issue_frac else None,
             "wave_issue_frac": pmc.get("wave_issue_frac") if pmc else None,
             "kernel_avg_us": round(k_evt * 1e6, 2),
-            "kernel_first_entry_to_last_exit_us": round(k_dyn * 1e6, 2),
+            "kernel_first_entry_to_last_exit_us": round(k_dyn * 1e6, 2) if k_dyn is not None else None,
             "timed_launches": timed_steps,
             "instructions_per_wavefront": pmc.get("per_wave") if pmc else None,
             "wavefronts_per_launch": pmc.get("waves_per_launch") if pmc else None,
@@ -947,7 +959,7 @@ def main():
         if pmc and pmc_src and pmc_src.startswith("this run") and os.environ.get("SDC_WRITE_PMC"):
             json.dump(pmc, open(latest, "w"), indent=1)
 
-        if world == 1 and not args.no_rollout:
+        if world == 1 and args.full and not args.no_rollout:
             # next to the headline (one launch per step): sdc_rollout, 48 env-steps per launch for action sequences
             # known up front (scripted policies); same work per step, every step's outputs written
             try:
@@ -969,7 +981,7 @@ def main():
                                   "ms_per_step": round(tr / done_steps * 1e3, 5)}
             except Exception as e:
                 out["rollout"] = {"error": repr(e)}
-        if world == 1 and not args.no_rollout:
+        if world == 1 and args.full and not args.no_rollout:
             # the CLOSED loop: sdc_rollout_actor, 48 env-steps per launch with the three agents' actor networks (the
             # reference's StochasticPolicy: LayerNorm(26) -> 64 -> 64 -> 3, fp32, happo.yaml hidden_sizes [64, 64]; random
             # weights) evaluated inside the kernel between the steps -- every env-step includes three network inferences
@@ -996,7 +1008,7 @@ def main():
                                                 "step, actions sampled from their softmax", "actions_last_launch": hist_a}
             except Exception as e:
                 out["closed_loop"] = {"error": repr(e)}
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             # secondary lines (not `value`): the shape the reference's shipped HARL YAML trains on, and how the rate moves
             # with the number of envs per GPU -- so that the driver's record, not only profiles/, shows both
             sec = {}
@@ -1058,7 +1070,7 @@ def main():
                     scan.append({"envs": n, "error": repr(e)})
             sec["batch_scan"] = scan
             out["secondary"] = sec
-        if not args.no_cpu_baseline and world == 1:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(tb, params, args.episode_steps)
             except Exception as e:  # the oracle is only the timed baseline here; never hide the GPU number

@@ -7,17 +7,17 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-# 1. kernel trace + stats of the default bench command (without the PMC sub-passes, which are separate processes)
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --steps 2000 --no-pmc --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.json 2> $O/trace.err
+# 1. kernel trace + stats of the full bench command (without the PMC sub-passes, which are separate processes)
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --steps 2000 --full --no-pmc --no-cpu-baseline --no-secondary > $O/bench_under_rocprof.json 2> $O/trace.err
 cd $R
 python tools/trace_summary.py $O/trace --last 1500 --out $O/kernel_trace_steady_state.json 2>&1 | tail -3
 cp $(find $O/trace -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv
 find $O -name "*kernel_trace.csv" -size +1M -delete; find $O -name "*.db" -delete
 # 2. the bench line itself (with its live PMC passes and the CPU baseline); keeps the counters as profiles/pmc_latest.json
-SDC_WRITE_PMC=1 timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
+SDC_WRITE_PMC=1 timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
 cp profiles/pmc_latest.json $O/pmc.json
-timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_steps20.json 2>> $O/bench.err
-timeout 600 python bench.py --mixed-racks --no-cpu-baseline --no-pmc > $O/bench_mixed_racks.json 2>> $O/bench.err
+timeout 600 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $O/bench_steps20.json 2>> $O/bench.err
+timeout 600 python bench.py --mixed-racks --full --no-cpu-baseline --no-pmc > $O/bench_mixed_racks.json 2>> $O/bench.err
 # 3. side measurements DESIGN.md quotes
 timeout 600 python tools/batch_scan.py > $O/batch_scan.txt 2>&1
 timeout 600 python tools/qb.py > $O/quick_rates.txt 2>&1
