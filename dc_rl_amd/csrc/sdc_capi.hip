@@ -427,6 +427,24 @@ extern "C" {
 const char* sdc_last_error(void) { return g_err.c_str(); }
 int sdc_version(void) { return SDC_ABI_VERSION; }
 
+// FNV-1a over the checkpoint's raw layouts: the record's and the header's dword offsets and the ring's stride.  A re-laid-out
+// record keeps its byte size, so the size check of sdc_set_state cannot tell an old checkpoint from a current one; this can.
+static constexpr unsigned kStateLayout[] = {
+    SDC_REC_DWORDS, SDC_HDR_DWORDS, SDC_HIST_STRIDE,
+    R_CURSOR, R_TREL, R_DAY, R_HOURQ, R_QPOPPED, R_QCUM, R_QCUMT, R_QHEAD, R_QCUM_HM1, R_QCUMT_HM1, R_LAST_DELTA, R_CONSEC,
+    R_SCALE, R_HIST_LEN, R_HIST_POS, R_FAULT, R_F64, R_STPT, R_BAT, R_HIST_REF, R_LAST_ROOM, R_CFG, R_LOC, R_TR_COUNT,
+    R_EPISODE, R_CI_MIN, R_CI_DEN, R_DAY_LO, R_DAY_HI, R_FEAT_OK, R_T_MIN, R_T_DEN, R_END,
+    H_N, H_QS2_LO, H_EOFF, H_QS1, H_RET, H_Q1, H_BU, H_BL, H_QC, H_Q3, H_WFIRST, H_WLAST, H_PEND, H_LAST_XNEW, H_LAST_XOLD,
+    H_LAST_NPREV, H_QS2_HI, H_STICKY, H_KB, H_VALID, H_A1, H_A2,
+    T_R0, T_HI, SDC_TRACK_DWORDS, SDC_WIN};
+static constexpr uint32_t state_layout_hash() {
+  uint32_t x = 2166136261u;
+  for (unsigned v : kStateLayout)
+    for (int b = 0; b < 4; b++) x = (x ^ ((v >> (8 * b)) & 0xFFu)) * 16777619u;
+  return x;
+}
+uint32_t sdc_state_layout(void) { return state_layout_hash(); }
+
 int sdc_create(const sdc_config* cfg, sdc_handle** out) {
   if (!cfg || !out) return fail_msg("sdc_create: null argument");
   if (cfg->n_envs <= 0) return fail_msg("sdc_create: n_envs must be > 0");

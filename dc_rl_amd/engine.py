@@ -27,6 +27,9 @@ _STATE_DTYPES = {
 # a full checkpoint: the raw records + every array the kernels own
 # "hist" first: injecting the ring drops the order-statistic trackers, which "header" then restores
 _CHECKPOINT = ["hist", "record", "header", "qwin", "t_win", "wb_win", "qtab"]
+# what a checkpoint's arrays only make sense with: a load into an engine that differs in any of these is refused
+_META_MUST_MATCH = ("layout", "n_envs", "episode_steps", "hist_cap", "queue_max_len", "max_roll_days", "n_locations",
+                    "n_dc_configs", "env_index_base")
 
 
 def dc_params_struct(p: dict) -> L.SdcDcParams:
@@ -110,6 +113,14 @@ class SdcEngine:
                           env_index_base=int(env_index_base), policy=(C.c_int32 * 3)(*[int(x) for x in policy]),
                           trim_and_respond_limit=float(trim_and_respond_limit))
         self.policy = tuple(int(x) for x in policy)
+        # the sdc_config fields a checkpoint records (all but device and debug_flags: where and how it runs, not what it is)
+        self.config = dict(n_envs=self.n_envs, episode_steps=self.episode_steps, hist_cap=int(hist_cap),
+                           queue_max_len=int(queue_max_len), n_locations=int(n_locations), n_dc_configs=int(n_dc_configs),
+                           auto_reset=bool(auto_reset), weather_noise_std=float(weather_noise_std),
+                           weather_noise_weight=float(weather_noise_weight), max_roll_days=int(max_roll_days),
+                           reward_method=tuple(int(m) for m in reward_method), env_index_base=int(env_index_base),
+                           policy=self.policy, trim_and_respond_limit=float(trim_and_respond_limit))
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
         self._h = C.c_void_p()
         self._pinned_stream = None
         self._pinned_stream_obj = None
@@ -157,7 +168,9 @@ class SdcEngine:
         L.check(self.lib.sdc_assign_envs(self._h, *[a.ctypes.data_as(ip) for a in arrs]))
 
     def set_seed(self, seed: int):
-        L.check(self.lib.sdc_set_seed(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF))
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        L.check(self.lib.sdc_set_seed(self._h, seed))
+        self.seed = seed
 
     # ------------------------------------------------------------------ run
     def _stream(self):
@@ -390,12 +403,31 @@ class SdcEngine:
         L.check(self.lib.sdc_set_state(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), a.nbytes))
 
     def state_dict(self) -> dict:
-        """Full env checkpoint (the reference never checkpoints env state)."""
-        return {n: self.get_state(n) for n in _CHECKPOINT}
+        """Full env checkpoint (the reference never checkpoints env state): the arrays the kernels own
+        and "meta" -- the library's state layout (sdc_state_layout), the engine's configuration and the current RNG seed, which
+        keys every future reset."""
+        sd = {n: self.get_state(n) for n in _CHECKPOINT}
+        sd["meta"] = dict(self.config, layout=int(self.lib.sdc_state_layout()), seed=self.seed)
+        return sd
 
     def load_state_dict(self, sd: dict):
+        """Restore a state_dict().  Refused with a ValueError naming the key: a dict without "meta", or one whose state layout,
+        n_envs, episode_steps, hist_cap, queue_max_len, max_roll_days, n_locations, n_dc_configs or env_index_base differs
+        from this engine's.  The saved seed is applied.  Trace tables, DC parameters and the rest of the constructor's
+        arguments are configuration, not state: the engine keeps its own (set them as for the engine that saved the dict)."""
+        meta = sd.get("meta")
+        if not isinstance(meta, dict):
+            raise ValueError("load_state_dict: the checkpoint has no 'meta' entry (saved by an older build?)")
+        mine = dict(self.config, layout=int(self.lib.sdc_state_layout()))
+        for k in _META_MUST_MATCH:
+            if k not in meta or meta[k] != mine[k]:
+                raise ValueError(f"load_state_dict: checkpoint {k} = {meta.get(k)!r}, this engine's is {mine[k]!r}")
+        if "seed" not in meta:
+            raise ValueError("load_state_dict: checkpoint has no seed")
         for n, v in sd.items():
-            self.set_state(n, v)
+            if n != "meta":
+                self.set_state(n, v)
+        self.set_seed(meta["seed"])
 
     def profile(self, every: int = 1):
         """Per-kernel HIP-event timing on the launch stream (measurement only): every k-th step, 0 = off."""

@@ -212,8 +212,9 @@ const char* sdc_last_error(void);
  *   100  round 1        300  sdc_config: env_index_base, policy[3], trim_and_respond_limit; sdc_reset_override: noise,
  *                            roll_days; sdc_rollout: actions_out; debug_flags bit 6
  *   310  sdc_set_actor, sdc_rollout_actor (closed loop with the actor networks inside the kernel); debug_flags bit 7
- *        (debug_flags bits 9 / 10 came later without a bump: no layout or argument list changed) */
-#define SDC_ABI_VERSION 311
+ *        (debug_flags bits 9 / 10 came later without a bump: no layout or argument list changed)
+ *   312  sdc_state_layout */
+#define SDC_ABI_VERSION 312
 int sdc_version(void);
 
 int sdc_create(const sdc_config* cfg, sdc_handle** out);
@@ -317,6 +318,9 @@ const char* sdc_last_step_kernel(const sdc_handle* h);
  * t_win wb_win (double[N][weather_window_len]);  qtab (uint32[N][queue_stride][2]). */
 int sdc_get_state(sdc_handle* h, const char* field, void* host_buf, size_t bytes);
 int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t bytes);
+/* a hash of the raw layouts a checkpoint holds (the record's and the header's dword offsets, the ring's stride): a checkpoint
+ * is only meaningful to a library that returns the same value -- a re-laid-out record keeps its byte size */
+uint32_t sdc_state_layout(void);
 int sdc_hist_stride(const sdc_handle* h);
 int sdc_queue_stride(const sdc_handle* h);
 

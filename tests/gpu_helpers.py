@@ -86,3 +86,19 @@ def rel_err(got, ref):
 
 def oracle_params_from_dict(p):
     return po.make_params(p["rack_n"], p["rack_full"], p["rack_idle"], p["rack_supply"], p["rack_return"], p)
+
+
+def hdr_offsets():
+    """{name: dword index} of the 256-byte per-env header's fields (csrc/sdc_device.hpp enum SdcHdr)."""
+    import re
+    src = open(os.path.join(os.path.dirname(L.LIB_PATH), "sdc_device.hpp")).read()
+    body = re.search(r"enum SdcHdr \{(.*?)\};", src, re.S)
+    assert body, "enum SdcHdr not found in sdc_device.hpp"
+    return {m.group(1): int(m.group(2)) for m in re.finditer(r"\b(H_\w+)\s*=\s*(\d+)", body.group(1))}
+
+
+def hdr_pend():
+    """dword indices of the four in-flight re-centring stamps in the 256-byte header (csrc/sdc_device.hpp H_PEND): the request
+    step they carry is the engine's launch counter, which a restore moves on (sdc_set_state)."""
+    k = hdr_offsets()["H_PEND"]
+    return [k, k + 1, k + 2, k + 3]

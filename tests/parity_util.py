@@ -101,10 +101,10 @@ class ParityRig:
         obs, _ = self.eng.reset(override=ov)
         return G.raw_obs(obs.cpu().numpy()), oobs
 
-    def reset_some(self, mask):
+    def reset_some(self, mask, also=()):
         """Inject a fresh episode into the masked envs only (sdc_reset with a mask): the others keep stepping where
         they are, so the batch is no longer in lock-step.  Returns (engine raw obs [N,53], oracle raw obs {env: [53]})
-        -- rows of unmasked envs are whatever the engine's obs buffer held."""
+        -- rows of unmasked envs are whatever the engine's obs buffer held.  also: further engines given the same reset."""
         N, lw = self.N, self.eng.lw
         mask = np.asarray(mask, dtype=bool)
         ov = dict(day=np.zeros(N, np.int32), hour=np.zeros(N, np.int32), ci_min=np.zeros(N), ci_max=np.ones(N),
@@ -125,6 +125,8 @@ class ParityRig:
                 oobs[int(i)] = self.oracles[i].begin(tb["W"][lo:hi], tb["C"][lo:hi], NC, dr["T"][lo:hi], dr["WB"][lo:hi],
                                                      NT, lo, dr["day"], dr["hour"], self.steps)
         obs, _ = self.eng.reset(mask=mask.astype(np.uint8), override=ov)
+        for e in also:
+            e.reset(mask=mask.astype(np.uint8), override=ov)
         return G.raw_obs(obs.cpu().numpy()), oobs
 
     def step(self, actions_np):

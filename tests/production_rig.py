@@ -155,21 +155,17 @@ class ProductionRig:
         combos = [(li, f) for li in range(len(locs)) for f in files]
         self.params = [dc_config.size_datacenter(f, 1, traces.max_ambient_for_sizing(traces.obtain_paths(locs[li])[0]))
                        for li, f in combos]
-        eng = self.eng = SdcEngine(N, episode_steps=episode_steps, auto_reset=True, seed=seed, debug_flags=debug_flags,
-                                   n_locations=len(locs), n_dc_configs=len(combos), reward_method=reward_method, policy=policy,
-                                   trim_and_respond_limit=trim_and_respond_limit, env_index_base=env_index_base,
-                                   hist_cap=hist_cap)
-        for li, tb in enumerate(self.tables):
-            eng.set_tables(li, tb["W"], tb["C"], tb["T"], tb["WB"])
-        for ci, p in enumerate(self.params):
-            eng.set_dc_params(ci, p)
+        # (kept: restore() builds a second engine exactly like this one)
+        self.engine_kw = dict(episode_steps=episode_steps, auto_reset=True, seed=seed, debug_flags=debug_flags,
+                              n_locations=len(locs), n_dc_configs=len(combos), reward_method=reward_method, policy=policy,
+                              trim_and_respond_limit=trim_and_respond_limit, env_index_base=env_index_base, hist_cap=hist_cap)
         e = np.arange(N)
         # BASELINE configs[3]: the rack count follows env_id % 3; the location changes every three envs
         self.loc_id = ((e // len(files)) % len(locs)).astype(np.int32)
         self.cfg_id = (self.loc_id * len(files) + e % len(files)).astype(np.int32)
         init_day = traces.get_init_day(6)
         self.day_lo, self.day_hi = init_day - 7, init_day + 7
-        eng.assign(self.loc_id, self.cfg_id, self.day_lo, self.day_hi)
+        eng = self.eng = self.make_engine()
         self.sample = sample_envs(N, self.geom, rng, n_random)
         # steady-state history: every ring full, write positions spread, duplicates included -- generated in place in the buffer
         # set_state hands to the library (no second host copy); only the sampled envs' rings are kept, for their oracles
@@ -197,6 +193,40 @@ class ProductionRig:
         self.draws_checked = 0
         self.kernel_checked = False
         self._idx = None
+        self.twin = None          # restore(keep_twin=True): the engine the checkpoint came from, stepped alongside
+        self.restored = None      # after restore(): "general" until the restored engine's first episode boundary, then "specialised"
+        self.restore_kernels = {"general": set(), "specialised": set()}
+        self.twin_kernels = set()
+
+    def make_engine(self, cfg_id=None, **overrides):
+        """A fresh engine with this rig's constructor arguments, tables, DC parameters and assignment (cfg_id: another
+        assignment of the DC configs) -- and empty rings: nothing is injected."""
+        eng = SdcEngine(self.N, **dict(self.engine_kw, **overrides))
+        for li, tb in enumerate(self.tables):
+            eng.set_tables(li, tb["W"], tb["C"], tb["T"], tb["WB"])
+        for ci, p in enumerate(self.params):
+            eng.set_dc_params(ci, p)
+        eng.assign(self.loc_id, self.cfg_id if cfg_id is None else cfg_id, self.day_lo, self.day_hi)
+        return eng
+
+    def restore(self, keep_twin=True, cfg_id=None, **overrides):
+        """Checkpoint the engine (state_dict), load the checkpoint into a fresh engine (make_engine, then reset(), then
+        load_state_dict) and go on with that one: the oracles are not touched, so they hold the restored engine ("B") to the same
+        trajectory -- including begin_all's check of its next reset draws, which are keyed on the seed, env_index_base and the
+        episode counter the checkpoint carries.  keep_twin: the old engine ("A") stays as `twin`; step() steps it alongside and
+        holds every env of B to it bit for bit.  A restored engine has no feature rows: step() asserts that it runs
+        sdc_dynamics_kernel until its first episode boundary and the kernel of the sample's mapping after it.  -> the checkpoint."""
+        sd = self.eng.state_dict()
+        b = self.make_engine(cfg_id=cfg_id, **overrides)
+        b.reset()
+        b.load_state_dict(sd)
+        if keep_twin:
+            self.twin = self.eng
+        else:
+            self.eng.close()
+        self.eng = b
+        self.restored = "general"
+        return sd
 
     def check_draws(self, st, tw, wb):
         """The device's own reset of every sampled env against tests/reset_ref.py (its Philox draw scheme restated): day, hour,
@@ -277,18 +307,52 @@ class ProductionRig:
         assert got == self.geom.kernel, f"the sample was built for {self.geom.kernel}, the step ran {got}"
         self.kernel_checked = True
 
+    def check_restored_kernel(self, kernel, done):
+        """After restore(): the kernel the restored engine ran for the launch that has just ended (done: it ended an episode)."""
+        self.restore_kernels[self.restored].add(kernel)
+        want = "sdc_dynamics_kernel" if self.restored == "general" else self.geom.kernel
+        assert kernel == want, f"restored engine, {self.restored} phase: expected {want}, ran {kernel}"
+        if done:
+            self.restored = "specialised"
+
+    def twin_equal(self, a_out, b_out, what, final_obs=False):
+        """Every env of the restored engine's outputs (obs, share_obs, rew, done, info[, ...]) against the twin's, bit for bit -- the
+        info diagnostics column aside (it says HOW the reward state was served, which a restore changes); final_obs: also the
+        engines' final_obs buffers."""
+        import torch
+        names = ("obs", "share_obs", "rew", "done", "info")
+        pairs = list(zip(names, a_out[:5], b_out[:5]))
+        if final_obs:
+            pairs.append(("final_obs", self.twin.final_obs, self.eng.final_obs))
+        for nm, u, v in pairs:
+            if u is None and v is None:
+                continue
+            if nm == "info":
+                u, v = u.clone(), v.clone()
+                u[..., L.INFO_IDX["reserved"]] = 0
+                v[..., L.INFO_IDX["reserved"]] = 0
+            if not torch.equal(u, v):
+                bad = (u != v).nonzero()
+                raise AssertionError((what, nm, bad[:6].tolist(), u[tuple(bad[0])].item(), v[tuple(bad[0])].item()))
+
     def step(self, a_dev, want_info=True):
         """One single step under actions a_dev (int32 [N, 3] on the device), the sampled envs against the oracle, the auto-reset
         followed; -> the engine's (obs, share_obs, rew, done, info) views (want_info False: a step without the info rows, which
         is never one of the specialised kernels: sdc_capi.hip lockstep_case)."""
         eng, idx = self.eng, self.sample_index()
         out = eng.step(a_dev, want_info=want_info)
-        if not self.kernel_checked:
+        if self.restored is None and not self.kernel_checked:
             self.check_kernel()
         obs, share, rew, done, info = out
         info = info if want_info else None
         n_done = self._device_checks(info, done)
         assert n_done in (0, self.N), n_done
+        if self.restored is not None:
+            self.check_restored_kernel(eng.last_step_kernel(), n_done > 0)
+        if self.twin is not None:
+            a_out = self.twin.step(a_dev, want_info=want_info)
+            self.twin_kernels.add(self.twin.last_step_kernel())
+            self.twin_equal(a_out, out, "single step", final_obs=n_done > 0)
         fo = G.raw_obs(eng.final_obs[idx].cpu().numpy()) if n_done else None
         self.check_step(a_dev[idx].cpu().numpy(), G.raw_obs(obs[idx].cpu().numpy()), rew[idx].cpu().numpy(),
                         done[idx].cpu().numpy(), None if info is None else info[idx].cpu().numpy(), fo)

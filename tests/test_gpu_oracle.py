@@ -9,6 +9,7 @@ from dc_rl_amd.engine import SdcEngine
 from oracle import pyoracle as po
 from tests import gpu_helpers as G
 from tests import parity_util as P
+from tests.gpu_helpers import hdr_pend as _hdr_pend
 
 pytestmark = pytest.mark.gpu
 
@@ -289,8 +290,9 @@ def test_grid_shapes_with_sweep_workgroups_inside_the_grid_vs_oracle():
 def test_checkpoint_rollback_on_the_same_engine_4096():
     """state_dict(), one step, load_state_dict() on the SAME engine, the same step again: bit-identical outputs, verify
     mode on (debug_flags bit 0), 4096 envs with full rings so that deferred window re-centrings are in flight at every
-    checkpoint (a restored header must not take over a window swept for the state it replaced: sdc_set_state moves the
-    launch counter past every request stamp)."""
+    checkpoint.  (Replaying TWO steps leaves every restored request stamp at least three steps old, stale with or without
+    sdc_set_state's move of the launch counter; the one-step rewind, where that move is what keeps a restored header from taking
+    over a window swept for the state it replaced, is tests/test_gpu_checkpoint.py::test_one_step_rewind_takes_over_no_stale_window.)"""
     import torch
     N, steps, cap = 4096, 672, 10000
     tb = traces.synthetic_tables("ny", 0)
@@ -335,13 +337,3 @@ def test_checkpoint_rollback_on_the_same_engine_4096():
     print("envs with a re-centring request in flight at the checkpoints:", taken)
     assert taken > 0
     eng.close()
-
-
-def _hdr_pend():
-    """dword indices of the four in-flight re-centring stamps in the 256-byte header (csrc/sdc_device.hpp H_PEND)."""
-    import re, os
-    src = open(os.path.join(os.path.dirname(L.LIB_PATH), "sdc_device.hpp")).read()
-    m = re.search(r"H_PEND\s*=\s*(\d+)", src)
-    assert m, "H_PEND not found in sdc_device.hpp"
-    k = int(m.group(1))
-    return [k, k + 1, k + 2, k + 3]
