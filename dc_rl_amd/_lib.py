@@ -18,11 +18,11 @@ INFO_DIM = 44
 TABLE_LEN = 35040
 HDR_DWORDS = 64    # csrc/sdc_device.hpp SdcHdr: 256-byte per-env header
 QWIN = 64          # csrc/sdc_device.hpp SDC_WIN: keys per rank window (4 windows per env: Q1, Q3, upper / lower clip bound)
-ABI_VERSION = 312  # include/sustaindc_hip.h SDC_ABI_VERSION: the struct layouts and argument lists this binding was written for
+ABI_VERSION = 313  # include/sustaindc_hip.h SDC_ABI_VERSION: the struct layouts and argument lists this binding was written for
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
-SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip"]
+SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip"]
 # (-amdgpu-sched-strategy=max-ilp: the machine scheduler orders for instruction-level parallelism instead of minimal register
 #  pressure -- the step kernels' occupancy is pinned by amdgpu_waves_per_eu anyway, and their time is dependent-issue latency:
 #  measured 12.09 -> 11.78 us per step of 4096 envs, the large-batch kernels +1-2 %)
@@ -133,7 +133,7 @@ EXPORTS = [
     "sdc_last_done", "sdc_last_step_kernel",
     "sdc_get_state", "sdc_set_state", "sdc_state_layout",
     "sdc_hist_stride", "sdc_queue_stride", "sdc_profile_enable", "sdc_profile_read",
-    "sdc_set_actor", "sdc_rollout_actor",
+    "sdc_set_actor", "sdc_rollout_actor", "sdc_clone_envs",
 ]
 
 
@@ -281,6 +281,7 @@ def load():
     L.sdc_profile_read.argtypes = [vp, dp, C.c_int]
     L.sdc_set_actor.argtypes = [vp, C.c_int, C.POINTER(SdcActorParams)]
     L.sdc_rollout_actor.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, vp, fp, fp, vp, fp, vp]
+    L.sdc_clone_envs.argtypes = [vp, ip, ip, C.c_int, fp, fp, vp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

@@ -17,6 +17,7 @@
 
 #include "sdc_device.hpp"
 #include "sdc_actor.hpp"
+#include "sdc_clone.hpp"
 
 extern "C" __global__ void sdc_dynamics_kernel(SdcDev S, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
                                                unsigned char* done, float* info, float* final_obs, float* rew);
@@ -46,6 +47,8 @@ extern "C" __global__ void sdc_reward_verify_kernel(SdcDev S, float* info);
 extern "C" __global__ void sdc_features_kernel(SdcDev S, int use_sma);
 extern "C" __global__ void sdc_rollout_kernel(SdcDev S, int K, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
                                               unsigned char* done, float* info, float* final_obs, float* rew);
+
+hipError_t sdc_clone_launch(const SdcClonePlan& P, hipStream_t st);     // sdc_clone.hip
 
 extern "C" __global__ void sdc_reset_kernel(SdcDev S, int use_override, const int* ovr_day, const int* ovr_hour,
                                             const double* ovr_ci_min, const double* ovr_ci_max, const double* ovr_t_min,
@@ -136,6 +139,15 @@ struct sdc_handle {
   std::vector<unsigned char> prof_has_reset;
   double wall_clock_khz = 100000.0;
   double acc_ms[5] = {0, 0, 0, 0, 0};      // dynamics, reward, reset, steps, resets
+  // sdc_clone_envs: the (src, dst) pairs staged through pinned host memory into a device buffer -- two slots of each, used in turn
+  // (allocated together on the first clone: clone_ready).  A slot's event marks the launch that last read it; a clone waits for it
+  // only before it overwrites that slot, i.e. for the clone two calls back
+  int2* clone_pairs_dev = nullptr;        // [2][N]
+  int2* clone_pairs_pin = nullptr;        // [2][N]
+  hipEvent_t clone_done[2] = {nullptr, nullptr};
+  bool clone_in_flight[2] = {false, false};
+  bool clone_ready = false;
+  int clone_slot = 0;
 };
 
 namespace {
@@ -621,6 +633,11 @@ int sdc_create(const sdc_config* cfg, sdc_handle** out) {
 int sdc_destroy(sdc_handle* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
+  for (int i = 0; i < 2; i++) {
+    if (h->clone_in_flight[i]) (void)hipEventSynchronize(h->clone_done[i]);
+    if (h->clone_done[i]) (void)hipEventDestroy(h->clone_done[i]);
+  }
+  if (h->clone_pairs_pin) (void)hipHostFree(h->clone_pairs_pin);
   for (void* p : h->allocs) (void)hipFree(p);
   delete h;
   return 0;
@@ -1317,6 +1334,127 @@ int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t
     h->host_t_rel = tr;
     recompute_steps_to_terminal(h);
   }
+  return 0;
+}
+
+// Env dst[k] becomes a copy of env src[k], on the device and ordered on `stream` like a step (sdc_clone.hip).  What is copied and
+// what is not, and why the deferred re-centring stamps are cleared rather than the launch counter moved: include/sustaindc_hip.h.
+int sdc_clone_envs(sdc_handle* h, const int32_t* src, const int32_t* dst, int n, float* obs, float* share_obs, void* stream) {
+  if (!h) return fail_msg("sdc_clone_envs: null handle");
+  if (n <= 0) return fail_msg("sdc_clone_envs: n must be positive");
+  if (!src || !dst) return fail_msg("sdc_clone_envs: null index array");
+  if (!h->started) return fail_msg("sdc_clone_envs: sdc_reset must be called first");
+  const int N = h->cfg.n_envs;
+  // every refusal before anything reaches the device
+  for (int k = 0; k < n; k++)
+    if (src[k] < 0 || src[k] >= N || dst[k] < 0 || dst[k] >= N)
+      return fail_msg("sdc_clone_envs: pair " + std::to_string(k) + " (" + std::to_string(src[k]) + " -> " + std::to_string(dst[k]) +
+                      ") has an env index outside [0, " + std::to_string(N) + ")");
+  std::vector<int> src_of((size_t)N, -1);      // dst -> its src
+  for (int k = 0; k < n; k++) {
+    if (src_of[(size_t)dst[k]] >= 0) return fail_msg("sdc_clone_envs: dst " + std::to_string(dst[k]) + " appears twice");
+    src_of[(size_t)dst[k]] = src[k];
+  }
+  for (int k = 0; k < n; k++)
+    if (src_of[(size_t)src[k]] >= 0) return fail_msg("sdc_clone_envs: env " + std::to_string(src[k]) + " is both a src and a dst");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const SdcDev& d = h->d;
+  SdcClonePlan P;
+  std::memset(&P, 0, sizeof(P));
+  P.n = n;
+  P.n_envs = N;
+  bool fits = true;
+  const auto add = [&P, &fits](void* base, size_t pitch, int is_hdr) {
+    const bool wide = pitch % 16 == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0;
+    if (wide ? P.n_wide == SDC_CLONE_MAX_WIDE : P.n_narrow == SDC_CLONE_MAX_NARROW) {
+      fits = false;
+      return;
+    }
+    if (is_hdr) P.hdr_wide = wide ? P.n_wide : -1;
+    SdcCloneSeg& g = wide ? P.wide[P.n_wide++] : P.narrow[P.n_narrow++];
+    g.base = static_cast<unsigned char*>(base);
+    g.pitch = (unsigned)pitch;
+    g.first = wide ? P.wide_units : P.narrow_units;
+    (wide ? P.wide_units : P.narrow_units) += (unsigned)(pitch / (wide ? 16 : 4));
+  };
+  add(d.rec, sizeof(unsigned) * SDC_REC_DWORDS, 0);
+  add(d.hdr, sizeof(unsigned) * SDC_HDR_DWORDS, 1);
+  add(d.hist, sizeof(unsigned) * SDC_HIST_STRIDE, 0);
+  add(d.qwin, sizeof(unsigned) * 4 * SDC_WIN, 0);
+  add(d.qtab, sizeof(uint2) * (size_t)d.qstride, 0);
+  add(d.t_win, sizeof(double) * (size_t)d.lw, 0);
+  add(d.wb_win, sizeof(double) * (size_t)d.lw, 0);
+  if (d.prm_env) add(const_cast<double*>(d.prm_env), sizeof(double) * 32, 0);
+  if (h->obs_latch) add(h->obs_latch, sizeof(float) * SDC_OBS_OUT, 0);
+  if (obs) add(obs, sizeof(float) * SDC_OBS_OUT, 0);
+  if (share_obs) add(share_obs, sizeof(float) * SDC_SHARE_OBS_DIM, 0);
+  if (!fits || P.hdr_wide < 0) return fail_msg("sdc_clone_envs: internal: the copy plan's segment table is too small");
+  constexpr int per_block = SDC_CLONE_BLOCK * SDC_CLONE_UNROLL;
+  P.bpp = std::max(1, (int)((P.wide_units + per_block - 1) / per_block));
+  P.blocks_a = n * P.bpp;
+  if (d.feat) {
+    P.feat = d.feat;
+    P.feat_rows = d.episode_steps + 1;
+    P.feat_pair_groups = (n + SDC_CLONE_BLOCK / 8 - 1) / (SDC_CLONE_BLOCK / 8);
+    P.blocks_b = P.feat_pair_groups * ((P.feat_rows + SDC_CLONE_FEAT_ROWS - 1) / SDC_CLONE_FEAT_ROWS);
+  }
+  if (d.qcum_t) {     // (the ring's mirror, where there is one, lies behind the queue table's in the same [row][N] array)
+    P.mirror = d.qcum_t;
+    P.mirror_rows = d.qstride + (d.hist_t ? d.hist_cap : 0);
+    P.mirror_pair_groups = (n + SDC_CLONE_BLOCK - 1) / SDC_CLONE_BLOCK;
+  }
+  if (!h->clone_ready) {
+    // all staging resources or none: a failure part way leaves clone_ready false, and the next call starts over from what is set
+    if (!h->clone_pairs_dev && dev_alloc(h, &h->clone_pairs_dev, 2 * (size_t)N, false) != 0) return -1;
+    if (!h->clone_pairs_pin) {
+      void* q = nullptr;
+      HIP_TRY(hipHostMalloc(&q, sizeof(int2) * 2 * (size_t)N, hipHostMallocDefault));
+      h->clone_pairs_pin = static_cast<int2*>(q);
+    }
+    for (int i = 0; i < 2; i++)
+      if (!h->clone_done[i]) {
+        hipEvent_t ev = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        h->clone_done[i] = ev;
+      }
+    h->clone_ready = true;
+  }
+  const int slot = h->clone_slot;
+  h->clone_slot ^= 1;
+  if (h->clone_in_flight[slot]) {      // (the clone two calls back may still be reading this slot)
+    HIP_TRY(hipEventSynchronize(h->clone_done[slot]));
+    h->clone_in_flight[slot] = false;
+  }
+  int2* pin = h->clone_pairs_pin + (size_t)slot * N;
+  int2* pairs_dev = h->clone_pairs_dev + (size_t)slot * N;
+  // the pairs sorted by dst: range C's lanes then write consecutive mirror dwords for a contiguous dst range
+  int m = 0;
+  for (int e = 0; e < N; e++)
+    if (src_of[(size_t)e] >= 0) pin[m++] = make_int2(src_of[(size_t)e], e);
+  HIP_TRY(hipMemcpyAsync(pairs_dev, pin, sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, st));
+  P.pairs = pairs_dev;
+  HIP_TRY(sdc_clone_launch(P, st));
+  HIP_TRY(hipEventRecord(h->clone_done[slot], st));
+  h->clone_in_flight[slot] = true;
+
+  // the host mirrors follow: episode step, feature rows, config; rel_hint comes back if the batch is in lock-step afterwards
+  sync_mirror(h);
+  const bool cfgs = (int)h->cfg_host.size() == N;
+  for (int k = 0; k < n; k++) {
+    const int s = src[k], t = dst[k];
+    h->host_t_rel[(size_t)t] = h->host_t_rel[(size_t)s];
+    if (h->feat_host[(size_t)t] != h->feat_host[(size_t)s]) {
+      h->n_feat_host += h->feat_host[(size_t)s] ? 1 : -1;
+      h->feat_host[(size_t)t] = h->feat_host[(size_t)s];
+    }
+    if (cfgs) h->cfg_host[(size_t)t] = h->cfg_host[(size_t)s];
+  }
+  if (cfgs && h->prm_env_ok) {       // (the largest rack count in use: what fast_case asks of a batch of several configs)
+    h->racks_max = 0;
+    for (int e = 0; e < N; e++) h->racks_max = std::max(h->racks_max, h->dc_host[(size_t)h->cfg_host[(size_t)e]].p.n_racks);
+  }
+  recompute_steps_to_terminal(h);
   return 0;
 }
 

@@ -429,6 +429,43 @@ class SdcEngine:
                 self.set_state(n, v)
         self.set_seed(meta["seed"])
 
+    def clone_envs(self, src, dst):
+        """Env dst[k] becomes an exact copy of env src[k] (copy.deepcopy of the reference's SustainDC, for envs of this batch), on
+        the device, ordered after the work already queued like a step (sdc_clone_envs).  src / dst: int sequences or arrays of the
+        same length; a scalar src is broadcast.  The engine's obs / share_obs rows follow, so eng.obs[dst] == eng.obs[src]
+        afterwards; the rest of the state is the library's.  dst finishes src's current episode exactly; its reset draws stay keyed
+        on its own index (env_index_base + dst), so from its next reset on it runs episodes of its own.  A lock-step batch stays on
+        the specialised kernels when every src is at the same episode step.  ValueError for what the library refuses: an empty
+        dst, an index outside [0, n_envs), a repeated dst, a dst that is also a src, no reset() yet.  -> (obs, share_obs) views."""
+        s, d = self.clone_pairs(src, dst)
+        ip = C.POINTER(C.c_int32)
+        with self.torch.cuda.device(self.device):
+            rc = self.lib.sdc_clone_envs(self._h, s.ctypes.data_as(ip), d.ctypes.data_as(ip), int(d.shape[0]),
+                                         C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.share_obs.data_ptr()), self._stream())
+        if rc == -2:        # (a refusal: fail_msg, before anything reached the device)
+            raise ValueError(self.lib.sdc_last_error().decode())
+        L.check(rc)
+        return self.obs, self.share_obs
+
+    def clone_pairs(self, src, dst):
+        """clone_envs' arguments as two int32 arrays of one length (a scalar src broadcast); ValueError for a malformed pair list
+        (the library checks the rest)."""
+        def ints(x, name):
+            a = np.asarray(x.cpu() if hasattr(x, "cpu") else x)
+            if a.dtype.kind not in "iu" and not (a.size == 0 and a.dtype.kind == "f"):
+                raise ValueError(f"clone_envs: {name} must hold integers, got {a.dtype}")
+            if a.ndim > 1:
+                raise ValueError(f"clone_envs: {name} must be one-dimensional, got shape {a.shape}")
+            if a.size and (a.min() < 0 or a.max() >= self.n_envs):
+                raise ValueError(f"clone_envs: {name} holds an env index outside [0, {self.n_envs})")
+            return a.astype(np.int32)
+        d = np.ascontiguousarray(ints(dst, "dst").reshape(-1))
+        s = ints(src, "src")
+        s = np.ascontiguousarray(np.broadcast_to(s, d.shape) if s.ndim == 0 else s)
+        if s.shape != d.shape:
+            raise ValueError(f"clone_envs: {s.shape[0]} sources for {d.shape[0]} destinations")
+        return s, d
+
     def profile(self, every: int = 1):
         """Per-kernel HIP-event timing on the launch stream (measurement only): every k-th step, 0 = off."""
         L.check(self.lib.sdc_profile_enable(self._h, int(every)))

@@ -412,6 +412,24 @@ class SustainDCVecEnv(ShareVecEnv):
         self._need_reset = False
         return self._out(self._sel_obs(obs)), self._out(self._share3(share, obs)), (self._avail if self.return_torch else self._avail_np)
 
+    def clone_envs(self, src, dst):
+        """Env dst[k] becomes an exact copy of env src[k] (copy.deepcopy of the reference's SustainDC, on the device: SdcEngine.clone_envs;
+        a scalar src is broadcast).  dst finishes src's current episode exactly and draws episodes of its own from its next reset on.
+        Returns (obs, share_obs, available_actions) for ALL envs in reset()'s layout -- the trained agents, either shared-observation
+        layout -- so a rollout loop can overwrite its observation buffers with them.  The host's per-env entries follow as well: the
+        constant info entries of dst's `infos` (its data-centre config is now src's), its config and month.  ValueError for what the
+        engine refuses."""
+        if self._need_reset:
+            raise ValueError("clone_envs: call reset() first")
+        s, d = self.engine.clone_pairs(src, dst)
+        obs, share = self.engine.clone_envs(s, d)
+        # new lists, not writes into the old ones: the `infos` of earlier steps keep theirs (they describe those steps)
+        const, cfg_id, months = list(self._const), list(self._cfg_id), list(self.months)
+        for a, b in zip(s.tolist(), d.tolist()):
+            const[b], cfg_id[b], months[b] = self._const[a], self._cfg_id[a], self.months[a]
+        self._const, self._cfg_id, self.months = const, cfg_id, months
+        return self._out(self._sel_obs(obs)), self._out(self._share3(share, obs)), (self._avail if self.return_torch else self._avail_np)
+
     def step_async(self, actions):
         t = self._torch
         if not isinstance(actions, t.Tensor):

@@ -213,8 +213,9 @@ const char* sdc_last_error(void);
  *                            roll_days; sdc_rollout: actions_out; debug_flags bit 6
  *   310  sdc_set_actor, sdc_rollout_actor (closed loop with the actor networks inside the kernel); debug_flags bit 7
  *        (debug_flags bits 9 / 10 came later without a bump: no layout or argument list changed)
- *   312  sdc_state_layout */
-#define SDC_ABI_VERSION 312
+ *   312  sdc_state_layout
+ *   313  sdc_clone_envs */
+#define SDC_ABI_VERSION 313
 int sdc_version(void);
 
 int sdc_create(const sdc_config* cfg, sdc_handle** out);
@@ -323,6 +324,27 @@ int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t
 uint32_t sdc_state_layout(void);
 int sdc_hist_stride(const sdc_handle* h);
 int sdc_queue_stride(const sdc_handle* h);
+
+/* replaces: copy.deepcopy(env) of the reference's SustainDC (a plain Python object: what lookahead / MPC controllers, same-episode
+ * policy comparisons and what-if studies branch an env with) for envs of one batch, on the device.  For each k, env dst[k] becomes an
+ * exact copy of env src[k] as it stands after the work already queued on `stream`; the copy is ordered on `stream` like a step, and the
+ * call does not synchronise the device.  The host waits in one case only: the index arrays are staged through two pinned buffers used
+ * in turn, so a clone waits for the launch of the clone two calls back if that one has not finished yet.  src / dst: HOST arrays of n env indices.  Refused (nothing reaches the device): a null handle
+ * or index array, n <= 0, an index outside [0, n_envs), a dst that appears twice, a dst that is also a src, no sdc_reset yet.
+ * Copied: every per-env array the step, rollout, reset and verify kernels read -- the state record (assignment, day range and episode
+ * counter included), the header (episode returns included), the history ring, the rank windows, the queue table, the weather windows,
+ * the episode's feature rows, the queue table's and the ring's mirrors where the batch has them, the per-env config scalars (several
+ * configs), the closed loop's copy of the latest observations (sdc_set_actor) -- and the caller's obs [N][3][26] / share_obs [N][29]
+ * rows (device; either may be NULL), so that the buffer the next actions are chosen from is coherent.  A batch in lock-step before the
+ * clone stays in lock-step when every src is at the same episode step: the next sdc_step / sdc_rollout runs the kernel it would have
+ * run without the clone.
+ * NOT copied: the env's global index (env_index_base + env), which keys its reset draws: dst finishes src's current episode exactly,
+ * and from its next reset on it draws episodes of its own.
+ * Deferred window re-centrings in flight: the copy clears the re-centring stamps of dst AND src (a result swept for src carries src's
+ * index, so dst could never take it over, and the two would part in window placement; dst's own former request describes a state
+ * that no longer exists) -- it does not move the launch counter as sdc_set_state does, which would drop the requests of every env of
+ * the batch.  The windows concerned are re-requested by the step that needs them. */
+int sdc_clone_envs(sdc_handle* h, const int32_t* src, const int32_t* dst, int n, float* obs, float* share_obs, void* stream);
 
 /* Per-kernel timing (measurement only; off by default).  enable = k > 0 samples every k-th sdc_step, 0 switches it
  * off.  In a sampled step one lane per workgroup of each kernel stamps the device's constant-rate wall clock at
