@@ -22,7 +22,9 @@ ABI_VERSION = 313  # include/sustaindc_hip.h SDC_ABI_VERSION: the struct layouts
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
-SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip"]
+SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
+           "sdc_snapshot.hip"]
+SNAPSHOT_MANIFEST = 9   # include/sustaindc_hip.h SDC_SNAPSHOT_MANIFEST: int32 entries per snapshot row's manifest (enum sdc_snapshot_manifest)
 # (-amdgpu-sched-strategy=max-ilp: the machine scheduler orders for instruction-level parallelism instead of minimal register
 #  pressure -- the step kernels' occupancy is pinned by amdgpu_waves_per_eu anyway, and their time is dependent-issue latency:
 #  measured 12.09 -> 11.78 us per step of 4096 envs, the large-batch kernels +1-2 %)
@@ -134,6 +136,7 @@ EXPORTS = [
     "sdc_get_state", "sdc_set_state", "sdc_state_layout",
     "sdc_hist_stride", "sdc_queue_stride", "sdc_profile_enable", "sdc_profile_read",
     "sdc_set_actor", "sdc_rollout_actor", "sdc_clone_envs",
+    "sdc_snapshot_row_bytes", "sdc_snapshot_envs", "sdc_restore_envs",
 ]
 
 
@@ -282,6 +285,10 @@ def load():
     L.sdc_set_actor.argtypes = [vp, C.c_int, C.POINTER(SdcActorParams)]
     L.sdc_rollout_actor.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, vp, fp, fp, vp, fp, vp]
     L.sdc_clone_envs.argtypes = [vp, ip, ip, C.c_int, fp, fp, vp]
+    L.sdc_snapshot_row_bytes.argtypes = [vp]
+    L.sdc_snapshot_row_bytes.restype = C.c_size_t
+    L.sdc_snapshot_envs.argtypes = [vp, ip, C.c_int, vp, ip, fp, fp, vp]
+    L.sdc_restore_envs.argtypes = [vp, ip, ip, C.c_int, vp, C.c_int, ip, fp, fp, vp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

@@ -18,6 +18,7 @@
 #include "sdc_device.hpp"
 #include "sdc_actor.hpp"
 #include "sdc_clone.hpp"
+#include "sdc_snapshot.hpp"
 
 extern "C" __global__ void sdc_dynamics_kernel(SdcDev S, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
                                                unsigned char* done, float* info, float* final_obs, float* rew);
@@ -49,6 +50,7 @@ extern "C" __global__ void sdc_rollout_kernel(SdcDev S, int K, int rel_hint, con
                                               unsigned char* done, float* info, float* final_obs, float* rew);
 
 hipError_t sdc_clone_launch(const SdcClonePlan& P, hipStream_t st);     // sdc_clone.hip
+hipError_t sdc_snapshot_launch(const SdcSnapPlan& P, bool save, hipStream_t st);     // sdc_snapshot.hip
 
 extern "C" __global__ void sdc_reset_kernel(SdcDev S, int use_override, const int* ovr_day, const int* ovr_hour,
                                             const double* ovr_ci_min, const double* ovr_ci_max, const double* ovr_t_min,
@@ -121,8 +123,10 @@ struct sdc_handle {
   // config's scalars is built (SdcDev::prm_env) -- the common-case kernels then serve the batch as they serve one config
   std::vector<SdcDcDev> dc_host;
   std::vector<int> cfg_host;
+  std::vector<int> loc_host;              // ... and of every env's trace set (what a snapshot's manifest records)
   std::vector<unsigned char> dc_set;
   double* prm_env_dev = nullptr;
+  double* prm_cfg_dev = nullptr;          // [n_dc_configs][32] each config's scalars: what a restore copies into prm_env
   bool prm_env_ok = false;
   int racks_max = 0;
   // the lane-per-env kernel's general form (sdc_wide.hip GEN): one SdcWideCfg per config, when the batch's configs qualify
@@ -148,6 +152,13 @@ struct sdc_handle {
   bool clone_in_flight[2] = {false, false};
   bool clone_ready = false;
   int clone_slot = 0;
+  // sdc_snapshot_envs / sdc_restore_envs: {env, row, cfg_id, loc_id} staged the same way (snap_ready: all or none allocated)
+  int4* snap_idx_dev = nullptr;           // [2][N]
+  int4* snap_idx_pin = nullptr;           // [2][N]
+  hipEvent_t snap_done[2] = {nullptr, nullptr};
+  bool snap_in_flight[2] = {false, false};
+  bool snap_ready = false;
+  int snap_slot = 0;
 };
 
 namespace {
@@ -332,6 +343,10 @@ int rebuild_prm_env(sdc_handle* h) {
   }
   if (!h->prm_env_dev && dev_alloc(h, &h->prm_env_dev, (size_t)N * 32) != 0) return -1;
   HIP_TRY(hipMemcpy(h->prm_env_dev, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+  std::vector<double> per_cfg((size_t)C * 32, 0.0);      // (the same rows by config: what sdc_restore_envs copies from)
+  for (int c = 0; c < C; c++) std::memcpy(&per_cfg[(size_t)c * 32], &h->dc_host[c].p.m_cpu, sizeof(double) * P_COUNT_HOST);
+  if (!h->prm_cfg_dev && dev_alloc(h, &h->prm_cfg_dev, (size_t)C * 32) != 0) return -1;
+  HIP_TRY(hipMemcpy(h->prm_cfg_dev, per_cfg.data(), sizeof(double) * per_cfg.size(), hipMemcpyHostToDevice));
   h->d.prm_env = h->prm_env_dev;
   h->prm_env_ok = true;
   return 0;
@@ -638,6 +653,11 @@ int sdc_destroy(sdc_handle* h) {
     if (h->clone_done[i]) (void)hipEventDestroy(h->clone_done[i]);
   }
   if (h->clone_pairs_pin) (void)hipHostFree(h->clone_pairs_pin);
+  for (int i = 0; i < 2; i++) {
+    if (h->snap_in_flight[i]) (void)hipEventSynchronize(h->snap_done[i]);
+    if (h->snap_done[i]) (void)hipEventDestroy(h->snap_done[i]);
+  }
+  if (h->snap_idx_pin) (void)hipHostFree(h->snap_idx_pin);
   for (void* p : h->allocs) (void)hipFree(p);
   delete h;
   return 0;
@@ -778,6 +798,7 @@ int sdc_assign_envs(sdc_handle* h, const int32_t* loc_id, const int32_t* cfg_id,
   }
   h->assigned = true;
   h->cfg_host.assign(cfg_id, cfg_id + N);
+  h->loc_host.assign(loc_id, loc_id + N);
   h->dc_set.resize((size_t)h->cfg.n_dc_configs, 0);
   if (rebuild_prm_env(h)) return -1;
   return rebuild_wide_cfg(h);
@@ -1308,6 +1329,14 @@ int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t
       if (rebuild_prm_env(h)) return -1;
     }
   }
+  if (std::strcmp(field, "loc_id") == 0) {
+    const int* l = static_cast<const int*>(host_buf);
+    h->loc_host.assign(l, l + h->cfg.n_envs);
+  } else if (is_record) {
+    const unsigned* r = static_cast<const unsigned*>(host_buf);
+    h->loc_host.resize((size_t)h->cfg.n_envs);
+    for (int e = 0; e < h->cfg.n_envs; e++) h->loc_host[e] = (int)r[(size_t)e * SDC_REC_DWORDS + R_LOC];
+  }
   if (h->d.qcum_t && std::strcmp(field, "qtab") == 0) {
     hipLaunchKernelGGL(sdc_qcum_mirror_kernel, dim3(h->d.qstride, (h->cfg.n_envs + 255) / 256), dim3(256), 0, 0, h->d);
     HIP_TRY(hipGetLastError());
@@ -1449,6 +1478,277 @@ int sdc_clone_envs(sdc_handle* h, const int32_t* src, const int32_t* dst, int n,
       h->feat_host[(size_t)t] = h->feat_host[(size_t)s];
     }
     if (cfgs) h->cfg_host[(size_t)t] = h->cfg_host[(size_t)s];
+    if ((int)h->loc_host.size() == N) h->loc_host[(size_t)t] = h->loc_host[(size_t)s];
+  }
+  if (cfgs && h->prm_env_ok) {       // (the largest rack count in use: what fast_case asks of a batch of several configs)
+    h->racks_max = 0;
+    for (int e = 0; e < N; e++) h->racks_max = std::max(h->racks_max, h->dc_host[(size_t)h->cfg_host[(size_t)e]].p.n_racks);
+  }
+  recompute_steps_to_terminal(h);
+  return 0;
+}
+
+// ---- snapshots (sdc_snapshot.hip) ----------------------------------------------------------------------------------------------
+// The row layout (sdc_snapshot.hpp) and the segment table of both directions, from this engine's arrays: the wide segments in unit
+// order (record, header first), the narrow ones behind them (the caller's obs first), then the feature rows.  Which array is wide
+// follows from its pitch alone (every engine array is a hipMalloc allocation, 256-byte aligned; the caller's obs / share_obs rows are
+// never wide) and every pitch from episode_steps, so every engine of the same state layout and episode length lays a row out the same
+// way.  -> false if a table is too small or a segment is not where the kernels expect it
+static bool snap_plan(const sdc_handle* h, SdcSnapPlan& P, size_t& row_bytes, float* obs, float* share_obs) {
+  const SdcDev& d = h->d;
+  std::memset(&P, 0, sizeof(P));
+  P.n_envs = h->cfg.n_envs;
+  bool fits = true;
+  const auto add = [&P, &fits](void* base, size_t pitch) -> unsigned {
+    const bool wide = pitch % 16 == 0;
+    if ((wide ? P.n_wide == SDC_SNAP_MAX_WIDE : P.n_narrow == SDC_SNAP_MAX_NARROW) ||
+        (wide && (reinterpret_cast<uintptr_t>(base) & 15u) != 0) || (reinterpret_cast<uintptr_t>(base) & 3u) != 0) {
+      fits = false;
+      return 0;
+    }
+    SdcSnapSeg& g = wide ? P.wide[P.n_wide++] : P.narrow[P.n_narrow++];
+    g.base = static_cast<unsigned char*>(base);
+    g.pitch = (unsigned)pitch;
+    g.first = wide ? P.wide_units : P.narrow_units;
+    (wide ? P.wide_units : P.narrow_units) += (unsigned)(pitch / (wide ? 16 : 4));
+    return g.first;
+  };
+  add(d.rec, sizeof(unsigned) * SDC_REC_DWORDS);                 // wide segment SDC_SNAP_SEG_REC
+  add(d.hdr, sizeof(unsigned) * SDC_HDR_DWORDS);                 // wide segment SDC_SNAP_SEG_HDR
+  add(d.qwin, sizeof(unsigned) * 4 * SDC_WIN);
+  const unsigned q_first = add(d.qtab, sizeof(uint2) * (size_t)d.qstride);
+  add(obs, sizeof(float) * SDC_OBS_OUT);                         // narrow segment SDC_SNAP_SEG_OBS
+  add(share_obs, sizeof(float) * SDC_SHARE_OBS_DIM);
+  add(d.t_win, sizeof(double) * (size_t)d.lw);
+  add(d.wb_win, sizeof(double) * (size_t)d.lw);
+  const unsigned h_first = add(d.hist, sizeof(unsigned) * SDC_HIST_STRIDE);
+  static_assert(sizeof(unsigned) * SDC_REC_DWORDS % 16 == 0 && sizeof(unsigned) * SDC_HDR_DWORDS % 16 == 0 &&
+                sizeof(float) * SDC_OBS_OUT % 16 != 0 && sizeof(float) * SDC_SHARE_OBS_DIM % 16 != 0,
+                "record and header wide, the observation rows narrow: the segment indices the kernels name");
+  P.qtab_off = 16u * q_first;      // (wide units: 16-byte aligned in the row, as range C's loads need)
+  P.hist_off = 16u * h_first;
+  P.feat_off = (16u * P.wide_units + 4u * P.narrow_units + 15u) / 16u * 16u;
+  size_t bytes = P.feat_off;
+  if (d.feat) {
+    P.feat = d.feat;
+    P.feat_rows = d.episode_steps + 1;
+    bytes += sizeof(float) * SDC_FEAT_ROW * (size_t)P.feat_rows;
+  }
+  row_bytes = (bytes + 255) / 256 * 256;
+  P.row_bytes = (unsigned)row_bytes;
+  return fits && P.n_wide > SDC_SNAP_SEG_HDR && P.n_narrow > SDC_SNAP_SEG_OBS && d.qstride % 64 == 0 &&
+         d.hist_cap <= SDC_HIST_STRIDE;
+}
+
+// the grid of ranges A and B for n envs (C and D: the restore's)
+static void snap_grid(SdcSnapPlan& P, const int n) {
+  constexpr int per_block = SDC_SNAP_BLOCK * SDC_SNAP_UNROLL;
+  P.n = n;
+  P.bpe = std::max(1, (int)((P.wide_units + per_block - 1) / per_block));
+  P.blocks_a = n * P.bpe;
+  if (P.feat) {
+    P.feat_groups = (n + SDC_SNAP_BLOCK / 8 - 1) / (SDC_SNAP_BLOCK / 8);
+    P.blocks_b = P.feat_groups * ((P.feat_rows + SDC_SNAP_FEAT_ROWS - 1) / SDC_SNAP_FEAT_ROWS);
+  }
+}
+
+// the launch's {env, row, cfg_id, loc_id} through pinned host memory into a device buffer -- two slots used in turn, as sdc_clone_envs
+// stages its pairs: a call waits only for the launch two calls back, and only if that one has not finished
+static int snap_stage(sdc_handle* h, const std::vector<int4>& ix, hipStream_t st, int* slot_out) {
+  const int N = h->cfg.n_envs;
+  if (!h->snap_ready) {
+    // all staging resources or none: a failure part way leaves snap_ready false, and the next call starts over from what is set
+    if (!h->snap_idx_dev && dev_alloc(h, &h->snap_idx_dev, 2 * (size_t)N, false) != 0) return -1;
+    if (!h->snap_idx_pin) {
+      void* q = nullptr;
+      HIP_TRY(hipHostMalloc(&q, sizeof(int4) * 2 * (size_t)N, hipHostMallocDefault));
+      h->snap_idx_pin = static_cast<int4*>(q);
+    }
+    for (int i = 0; i < 2; i++)
+      if (!h->snap_done[i]) {
+        hipEvent_t ev = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        h->snap_done[i] = ev;
+      }
+    h->snap_ready = true;
+  }
+  const int slot = h->snap_slot;
+  h->snap_slot ^= 1;
+  if (h->snap_in_flight[slot]) {      // (the call two back may still be reading this slot)
+    HIP_TRY(hipEventSynchronize(h->snap_done[slot]));
+    h->snap_in_flight[slot] = false;
+  }
+  int4* pin = h->snap_idx_pin + (size_t)slot * N;
+  std::memcpy(pin, ix.data(), sizeof(int4) * ix.size());
+  HIP_TRY(hipMemcpyAsync(h->snap_idx_dev + (size_t)slot * N, pin, sizeof(int4) * ix.size(), hipMemcpyHostToDevice, st));
+  *slot_out = slot;
+  return 0;
+}
+
+static int snap_launch(sdc_handle* h, SdcSnapPlan& P, const bool save, const int slot, hipStream_t st) {
+  P.idx = h->snap_idx_dev + (size_t)slot * h->cfg.n_envs;
+  HIP_TRY(sdc_snapshot_launch(P, save, st));
+  HIP_TRY(hipEventRecord(h->snap_done[slot], st));
+  h->snap_in_flight[slot] = true;
+  return 0;
+}
+
+// why a manifest row cannot be restored into this engine ("" if it can)
+static std::string snap_manifest_error(const sdc_handle* h, const int32_t* m) {
+  const int32_t want[5] = {(int32_t)state_layout_hash(), h->cfg.episode_steps, h->cfg.hist_cap, h->d.qstride, h->d.lw};
+  static const char* what[5] = {"state layout", "episode_steps", "hist_cap", "queue stride", "weather window length"};
+  static_assert(SDC_SNAP_LAYOUT == 0 && SDC_SNAP_EPISODE_STEPS == 1 && SDC_SNAP_HIST_CAP == 2 && SDC_SNAP_QUEUE_STRIDE == 3 &&
+                SDC_SNAP_WINDOW_LEN == 4, "the manifest's shape entries come first");
+  for (int i = 0; i < 5; i++)
+    if (m[i] != want[i])
+      return std::string(what[i]) + " " + std::to_string(m[i]) + ", this engine's is " + std::to_string(want[i]);
+  if (m[SDC_SNAP_T_REL] < 0 || m[SDC_SNAP_T_REL] > h->cfg.episode_steps)
+    return "episode step " + std::to_string(m[SDC_SNAP_T_REL]) + " outside [0, episode_steps]";
+  if (m[SDC_SNAP_FEAT_OK] != 0 && m[SDC_SNAP_FEAT_OK] != 1) return "feature-rows flag " + std::to_string(m[SDC_SNAP_FEAT_OK]);
+  if (m[SDC_SNAP_CFG_ID] < 0 || m[SDC_SNAP_CFG_ID] >= h->cfg.n_dc_configs)
+    return "cfg_id " + std::to_string(m[SDC_SNAP_CFG_ID]) + ", this engine has " + std::to_string(h->cfg.n_dc_configs) + " dc configs";
+  if (m[SDC_SNAP_LOC_ID] < 0 || m[SDC_SNAP_LOC_ID] >= h->cfg.n_locations)
+    return "loc_id " + std::to_string(m[SDC_SNAP_LOC_ID]) + ", this engine has " + std::to_string(h->cfg.n_locations) + " locations";
+  return "";
+}
+
+size_t sdc_snapshot_row_bytes(const sdc_handle* h) {
+  if (!h) return 0;
+  SdcSnapPlan P;
+  size_t bytes = 0;
+  (void)snap_plan(h, P, bytes, nullptr, nullptr);
+  return bytes;
+}
+
+// Env envs[k] -> snapshot row k, ordered on `stream` like a step, read-only on the engine (sdc_snapshot.hip).  What a row holds and
+// what the manifest records: include/sustaindc_hip.h.
+int sdc_snapshot_envs(sdc_handle* h, const int32_t* envs, int n, void* rows, int32_t* manifest, const float* obs,
+                      const float* share_obs, void* stream) {
+  if (!h) return fail_msg("sdc_snapshot_envs: null handle");
+  if (n <= 0) return fail_msg("sdc_snapshot_envs: n must be positive");
+  if (!envs || !rows || !manifest || !obs || !share_obs) return fail_msg("sdc_snapshot_envs: null array");
+  if (!h->started) return fail_msg("sdc_snapshot_envs: sdc_reset must be called first");
+  const int N = h->cfg.n_envs;
+  if (n > N) return fail_msg("sdc_snapshot_envs: n = " + std::to_string(n) + " is more than the batch's " + std::to_string(N) + " envs");
+  for (int k = 0; k < n; k++)
+    if (envs[k] < 0 || envs[k] >= N)
+      return fail_msg("sdc_snapshot_envs: env " + std::to_string(envs[k]) + " (entry " + std::to_string(k) + ") outside [0, " +
+                      std::to_string(N) + ")");
+  if ((reinterpret_cast<uintptr_t>(rows) & 255u) != 0) return fail_msg("sdc_snapshot_envs: rows must be 256-byte aligned");
+  SdcSnapPlan P;
+  size_t row_bytes = 0;
+  if (!snap_plan(h, P, row_bytes, const_cast<float*>(obs), const_cast<float*>(share_obs)))
+    return fail_msg("sdc_snapshot_envs: obs / share_obs rows not dword-aligned, or a layout the snapshot plan does not know");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  sync_mirror(h);
+  const bool cfgs = (int)h->cfg_host.size() == N, locs = (int)h->loc_host.size() == N;
+  std::vector<int4> ix((size_t)n);
+  for (int k = 0; k < n; k++) {
+    const int e = envs[k];
+    const int cfg = cfgs ? h->cfg_host[(size_t)e] : 0, loc = locs ? h->loc_host[(size_t)e] : 0;
+    ix[(size_t)k] = make_int4(e, k, cfg, loc);
+    int32_t* m = manifest + (size_t)k * SDC_SNAPSHOT_MANIFEST;
+    m[SDC_SNAP_LAYOUT] = (int32_t)state_layout_hash();
+    m[SDC_SNAP_EPISODE_STEPS] = h->cfg.episode_steps;
+    m[SDC_SNAP_HIST_CAP] = h->cfg.hist_cap;
+    m[SDC_SNAP_QUEUE_STRIDE] = h->d.qstride;
+    m[SDC_SNAP_WINDOW_LEN] = h->d.lw;
+    m[SDC_SNAP_T_REL] = h->host_t_rel[(size_t)e];
+    m[SDC_SNAP_FEAT_OK] = h->feat_host[(size_t)e] ? 1 : 0;
+    m[SDC_SNAP_CFG_ID] = cfg;
+    m[SDC_SNAP_LOC_ID] = loc;
+  }
+  P.rows = static_cast<unsigned char*>(rows);
+  snap_grid(P, n);
+  int slot = 0;
+  if (snap_stage(h, ix, st, &slot)) return -1;
+  return snap_launch(h, P, true, slot, st);
+}
+
+// Env envs[k] becomes snapshot row rows_idx[k] (sdc_snapshot.hip), ordered on `stream` like a step; the host mirrors follow the
+// manifest, so a restore that leaves the batch in lock-step keeps rel_hint and the specialised kernels
+int sdc_restore_envs(sdc_handle* h, const int32_t* rows_idx, const int32_t* envs, int n, const void* rows, int n_rows,
+                     const int32_t* manifest, float* obs, float* share_obs, void* stream) {
+  if (!h) return fail_msg("sdc_restore_envs: null handle");
+  if (n <= 0) return fail_msg("sdc_restore_envs: n must be positive");
+  if (n_rows <= 0) return fail_msg("sdc_restore_envs: n_rows must be positive");
+  if (!rows_idx || !envs || !rows || !manifest || !obs || !share_obs) return fail_msg("sdc_restore_envs: null array");
+  if (!h->started) return fail_msg("sdc_restore_envs: sdc_reset must be called first");
+  const int N = h->cfg.n_envs;
+  // every refusal before anything reaches the device
+  for (int k = 0; k < n; k++) {
+    if (envs[k] < 0 || envs[k] >= N)
+      return fail_msg("sdc_restore_envs: env " + std::to_string(envs[k]) + " (entry " + std::to_string(k) + ") outside [0, " +
+                      std::to_string(N) + ")");
+    if (rows_idx[k] < 0 || rows_idx[k] >= n_rows)
+      return fail_msg("sdc_restore_envs: row " + std::to_string(rows_idx[k]) + " (entry " + std::to_string(k) + ") outside [0, " +
+                      std::to_string(n_rows) + ")");
+  }
+  std::vector<int> row_of((size_t)N, -1);      // dst -> its row
+  for (int k = 0; k < n; k++) {
+    if (row_of[(size_t)envs[k]] >= 0) return fail_msg("sdc_restore_envs: dst " + std::to_string(envs[k]) + " appears twice");
+    row_of[(size_t)envs[k]] = rows_idx[k];
+  }
+  for (int k = 0; k < n; k++) {
+    const std::string why = snap_manifest_error(h, manifest + (size_t)rows_idx[k] * SDC_SNAPSHOT_MANIFEST);
+    if (!why.empty()) return fail_msg("sdc_restore_envs: row " + std::to_string(rows_idx[k]) + ": " + why);
+  }
+  if ((reinterpret_cast<uintptr_t>(rows) & 255u) != 0) return fail_msg("sdc_restore_envs: rows must be 256-byte aligned");
+  SdcSnapPlan P;
+  size_t row_bytes = 0;
+  if (!snap_plan(h, P, row_bytes, obs, share_obs))
+    return fail_msg("sdc_restore_envs: obs / share_obs rows not dword-aligned, or a layout the snapshot plan does not know");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const SdcDev& d = h->d;
+  P.rows = static_cast<unsigned char*>(const_cast<void*>(rows));
+  P.obs_latch = h->obs_latch;
+  snap_grid(P, n);
+  if (d.qcum_t) {      // C: the mirrors, in tiles of 64 dst envs (qstride is a multiple of 64: whole tiles of 16 queue-table slots)
+    P.qcum_t = d.qcum_t;
+    P.qstride = d.qstride;
+    P.q_tiles = d.qstride / (SDC_SNAP_TILE_BYTES / 8);
+    if (d.hist_t) {    // (the row holds SDC_HIST_STRIDE >= hist_cap ring slots: the last tile's reads stay inside it)
+      P.hist_t = d.hist_t;
+      P.hist_cap = d.hist_cap;
+      P.h_tiles = (d.hist_cap + SDC_SNAP_TILE_BYTES / 4 - 1) / (SDC_SNAP_TILE_BYTES / 4);
+    }
+    P.tile_groups = (n + SDC_SNAP_TILE_ENVS - 1) / SDC_SNAP_TILE_ENVS;
+    P.blocks_c = P.tile_groups * (P.q_tiles + P.h_tiles);
+  }
+  if (d.prm_env && h->prm_cfg_dev) {      // D: the per-env config scalars (several configs)
+    P.prm_env = const_cast<double*>(d.prm_env);
+    P.prm_cfg = h->prm_cfg_dev;
+    P.blocks_d = (n + SDC_SNAP_BLOCK / 16 - 1) / (SDC_SNAP_BLOCK / 16);
+  }
+  // sorted by dst: range C's wavefronts then write consecutive mirror dwords for a contiguous dst range
+  std::vector<int4> ix;
+  ix.reserve((size_t)n);
+  for (int e = 0; e < N; e++)
+    if (row_of[(size_t)e] >= 0) {
+      const int32_t* m = manifest + (size_t)row_of[(size_t)e] * SDC_SNAPSHOT_MANIFEST;
+      ix.push_back(make_int4(e, row_of[(size_t)e], m[SDC_SNAP_CFG_ID], m[SDC_SNAP_LOC_ID]));
+    }
+  int slot = 0;
+  if (snap_stage(h, ix, st, &slot)) return -1;
+  if (snap_launch(h, P, false, slot, st)) return -1;
+
+  // the host mirrors follow the manifest: episode step, feature rows, config, trace set; rel_hint comes back if the batch is in
+  // lock-step afterwards
+  sync_mirror(h);
+  const bool cfgs = (int)h->cfg_host.size() == N, locs = (int)h->loc_host.size() == N;
+  for (const int4& x : ix) {
+    const int32_t* m = manifest + (size_t)x.y * SDC_SNAPSHOT_MANIFEST;
+    const size_t e = (size_t)x.x;
+    h->host_t_rel[e] = m[SDC_SNAP_T_REL];
+    const unsigned char f = (d.feat && m[SDC_SNAP_FEAT_OK]) ? 1 : 0;
+    if (h->feat_host[e] != f) {
+      h->n_feat_host += f ? 1 : -1;
+      h->feat_host[e] = f;
+    }
+    if (cfgs) h->cfg_host[e] = m[SDC_SNAP_CFG_ID];
+    if (locs) h->loc_host[e] = m[SDC_SNAP_LOC_ID];
   }
   if (cfgs && h->prm_env_ok) {       // (the largest rack count in use: what fast_case asks of a batch of several configs)
     h->racks_max = 0;

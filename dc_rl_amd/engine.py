@@ -30,6 +30,43 @@ _CHECKPOINT = ["hist", "record", "header", "qwin", "t_win", "wb_win", "qtab"]
 # what a checkpoint's arrays only make sense with: a load into an engine that differs in any of these is refused
 _META_MUST_MATCH = ("layout", "n_envs", "episode_steps", "hist_cap", "queue_max_len", "max_roll_days", "n_locations",
                     "n_dc_configs", "env_index_base")
+# ... and a snapshot's rows: the same, but they may go to an engine of another size, and to any slot of it
+_SNAPSHOT_MUST_MATCH = tuple(k for k in _META_MUST_MATCH if k not in ("n_envs", "env_index_base"))
+
+
+def _int_ids(x, what):
+    """an int32 array of env / row indices (a scalar stays 0-d); ValueError for anything else"""
+    a = np.asarray(x.cpu() if hasattr(x, "cpu") else x)
+    if a.dtype.kind not in "iu" and not (a.size == 0 and a.dtype.kind == "f"):
+        raise ValueError(f"{what} must hold integers, got {a.dtype}")
+    if a.ndim > 1:
+        raise ValueError(f"{what} must be one-dimensional, got shape {a.shape}")
+    if a.size and (int(a.min()) < -2 ** 31 or int(a.max()) >= 2 ** 31):
+        raise ValueError(f"{what} holds a value outside int32")
+    a = a.astype(np.int32)
+    return a if a.ndim == 0 else np.ascontiguousarray(a)      # (np.ascontiguousarray would make a scalar one-dimensional)
+
+
+class EnvSnapshot:
+    """Env states in a device buffer (SdcEngine.snapshot): `rows` uint8 [n, row_bytes] -- row k is env `envs[k]`'s complete state in
+    the library's engine-independent layout (include/sustaindc_hip.h sdc_snapshot_envs) --, `manifest` int32 [n, SNAPSHOT_MANIFEST]
+    (host: what the library checks a restore against), `meta` (the state layout and the configuration the rows only make sense with)
+    and `envs`, the source env ids.  `extra`: host-side per-row entries a wrapper keeps with the rows (SustainDCVecEnv)."""
+
+    def __init__(self, rows, manifest, meta, envs, extra=None):
+        self.rows, self.manifest, self.meta, self.envs = rows, manifest, meta, envs
+        self.extra = extra if extra is not None else {}
+
+    def __len__(self):
+        return int(self.envs.shape[0])
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.rows.numel())
+
+    def to(self, device):
+        """The same snapshot with its rows on another device (restore into an engine on another GPU)."""
+        return EnvSnapshot(self.rows.to(device), self.manifest, self.meta, self.envs, self.extra)
 
 
 def dc_params_struct(p: dict) -> L.SdcDcParams:
@@ -465,6 +502,80 @@ class SdcEngine:
         if s.shape != d.shape:
             raise ValueError(f"clone_envs: {s.shape[0]} sources for {d.shape[0]} destinations")
         return s, d
+
+    def _refused(self, rc):
+        if rc == -2:        # (a refusal: fail_msg, before anything reached the device)
+            raise ValueError(self.lib.sdc_last_error().decode())
+        L.check(rc)
+
+    def snapshot(self, envs=None) -> EnvSnapshot:
+        """The complete state of envs (default: all) in a device buffer of their own (sdc_snapshot_envs), ordered after the work already
+        queued like a step, without a device synchronisation.  Read-only on the engine: taking snapshots does not change the run.  The
+        rows can be restored into any envs of this engine or of another with the same state layout, episode_steps, hist_cap,
+        queue_max_len, max_roll_days, locations and dc configs (`restore`), on another GPU after `.to(device)`.  ValueError for what the
+        library refuses: no env, an index outside [0, n_envs), more envs than the batch, no reset() yet."""
+        t = self.torch
+        e = np.arange(self.n_envs, dtype=np.int32) if envs is None else _int_ids(envs, "snapshot: envs").reshape(-1)
+        n = int(e.shape[0])
+        rb = int(self.lib.sdc_snapshot_row_bytes(self._h))
+        manifest = np.zeros((max(n, 1), L.SNAPSHOT_MANIFEST), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        with t.cuda.device(self.device):
+            rows = t.empty((n, rb), dtype=t.uint8, device=self.device)
+            rc = self.lib.sdc_snapshot_envs(self._h, e.ctypes.data_as(ip), n, C.c_void_p(rows.data_ptr()), manifest.ctypes.data_as(ip),
+                                            C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.share_obs.data_ptr()), self._stream())
+        self._refused(rc)
+        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse it before)
+            rows.record_stream(self._pinned_stream_obj)
+        mine = dict(self.config, layout=int(self.lib.sdc_state_layout()))
+        return EnvSnapshot(rows, manifest[:n], {k: mine[k] for k in _SNAPSHOT_MUST_MATCH}, e)
+
+    def restore_pairs(self, snap: EnvSnapshot, envs=None, rows=None):
+        """restore's arguments as (rows, envs), two int32 arrays of one length: envs default to snap.envs, rows to 0 .. len(snap) - 1 (a
+        scalar broadcast); ValueError for a malformed list (the library checks the rest)."""
+        d = snap.envs if envs is None else _int_ids(envs, "restore: envs").reshape(-1)
+        if rows is None:
+            if envs is not None and d.shape[0] != len(snap):
+                raise ValueError(f"restore: {d.shape[0]} envs for {len(snap)} snapshot rows: say which rows go where (rows=)")
+            r = np.arange(len(snap), dtype=np.int32)
+        else:
+            r = _int_ids(rows, "restore: rows")
+            r = np.ascontiguousarray(np.broadcast_to(r, d.shape) if r.ndim == 0 else r)
+        if r.shape != d.shape:
+            raise ValueError(f"restore: {r.shape[0]} rows for {d.shape[0]} envs")
+        return r, np.ascontiguousarray(d)
+
+    def restore(self, snap: EnvSnapshot, envs=None, rows=None):
+        """Env envs[k] becomes snapshot row rows[k] (sdc_restore_envs): by default row k goes back into env snap.envs[k]; a scalar
+        `rows` is broadcast (one state into several envs).  One launch ordered like a step, no device synchronisation; the engine's
+        obs / share_obs rows follow.  A restore that leaves the batch in lock-step (a whole-batch rewind) keeps the specialised
+        kernels.  A restored env finishes the saved episode exactly; its later episodes are keyed on its own global index and this
+        engine's seed.  ValueError for a snapshot of another state layout or configuration, rows on another device, and what the
+        library refuses (an index out of range, a repeated env, no reset() yet).  -> (obs, share_obs) views."""
+        t = self.torch
+        mine = dict(self.config, layout=int(self.lib.sdc_state_layout()))
+        for k in _SNAPSHOT_MUST_MATCH:
+            if snap.meta.get(k) != mine[k]:
+                raise ValueError(f"restore: snapshot {k} = {snap.meta.get(k)!r}, this engine's is {mine[k]!r}")
+        if snap.rows.device != self.device:
+            raise ValueError(f"restore: the snapshot's rows are on {snap.rows.device}, this engine runs on {self.device} "
+                             "(snapshot.to(device))")
+        rb = int(self.lib.sdc_snapshot_row_bytes(self._h))
+        if snap.rows.dtype != t.uint8 or snap.rows.dim() != 2 or snap.rows.shape[1] != rb or not snap.rows.is_contiguous():
+            raise ValueError(f"restore: rows must be a contiguous uint8 tensor [n, {rb}], got {tuple(snap.rows.shape)}")
+        m = np.ascontiguousarray(snap.manifest, dtype=np.int32)
+        if m.shape != (snap.rows.shape[0], L.SNAPSHOT_MANIFEST):
+            raise ValueError(f"restore: manifest of shape {m.shape} for {snap.rows.shape[0]} rows")
+        r, d = self.restore_pairs(snap, envs, rows)
+        ip = C.POINTER(C.c_int32)
+        with t.cuda.device(self.device):
+            rc = self.lib.sdc_restore_envs(self._h, r.ctypes.data_as(ip), d.ctypes.data_as(ip), int(d.shape[0]),
+                                           C.c_void_p(snap.rows.data_ptr()), int(snap.rows.shape[0]), m.ctypes.data_as(ip),
+                                           C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.share_obs.data_ptr()), self._stream())
+        self._refused(rc)
+        if self._pinned_stream_obj is not None:
+            snap.rows.record_stream(self._pinned_stream_obj)
+        return self.obs, self.share_obs
 
     def profile(self, every: int = 1):
         """Per-kernel HIP-event timing on the launch stream (measurement only): every k-th step, 0 = off."""

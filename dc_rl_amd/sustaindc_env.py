@@ -26,6 +26,7 @@ class EnvConfig(dict):
 class SustainDC(Env):
     def __init__(self, env_config, device: int = 0, seed: int = 1):
         env_config = EnvConfig(env_config)
+        self._ctor = (dict(env_config), device, seed)     # (what __deepcopy__ builds the copy from)
         self.env_config = env_config
         self.agents = list(env_config["agents"])
         self.location = env_config["location"]
@@ -84,6 +85,21 @@ class SustainDC(Env):
         info["__common__"] = common
         self.infos = {**{k: common for k in self.agents}, "__common__": {"states": o}}
         return o, r, terminateds, truncateds, info
+
+    def __deepcopy__(self, memo):
+        """copy.deepcopy (the reference's way to branch an env: lookahead / MPC, same-episode policy comparisons, what-if studies): a
+        fresh SustainDC from the same constructor arguments whose env is restored from a snapshot of this one
+        (SustainDCVecEnv.__deepcopy__), with the host-side state -- base agents, the last infos -- copied.  The copy keeps this env's
+        global index and seed: under the same actions it follows this env exactly, across resets."""
+        import copy
+        cfg, device, seed = self._ctor
+        new = type(self)(copy.deepcopy(cfg, memo), device=device, seed=seed)
+        memo[id(self)] = new
+        new._vec._take_state(self._vec)
+        new.base_agents = copy.deepcopy(self.base_agents, memo)
+        new.infos = copy.deepcopy(self.infos, memo)
+        new.init_day = self.init_day
+        return new
 
     def render(self, *a, **k):
         return None

@@ -271,6 +271,9 @@ class SustainDCVecEnv(ShareVecEnv):
                  months: Optional[Sequence[int]] = None, device: int = 0, return_torch: bool = False,
                  auto_reset: bool = True, data_root: Optional[str] = None, env_index_base: int = 0,
                  snapshot_infos: bool = False):
+        # (what __deepcopy__ builds the copy from)
+        self._init_args = dict(env_args=env_args, n_envs=n_envs, seed=seed, months=months, device=device, return_torch=return_torch,
+                               auto_reset=auto_reset, data_root=data_root, env_index_base=env_index_base, snapshot_infos=snapshot_infos)
         per_env = [_merge_args(a) for a in env_args] if isinstance(env_args, (list, tuple)) else [_merge_args(env_args)] * n_envs
         if len(per_env) != n_envs:
             raise ValueError("env_args list must have n_envs entries")
@@ -337,6 +340,7 @@ class SustainDCVecEnv(ShareVecEnv):
         init_day = np.array([traces.get_init_day(m) for m in self.months])
         self.engine.assign(np.array(loc_id), np.array(cfg_id), np.maximum(0, init_day - 7), np.minimum(364, init_day + 7))
         self._cfg_id = cfg_id
+        self._loc_keys, self._cfg_keys = loc_keys, cfg_keys
         # per-env constant info entries (envs/dc_gym.py:224-227, envs/bat_env_fwd_view.py:118-121, carbon_ls.py:294-297)
         self._const = []
         for i in range(n_envs):
@@ -429,6 +433,63 @@ class SustainDCVecEnv(ShareVecEnv):
             const[b], cfg_id[b], months[b] = self._const[a], self._cfg_id[a], self.months[a]
         self._const, self._cfg_id, self.months = const, cfg_id, months
         return self._out(self._sel_obs(obs)), self._out(self._share3(share, obs)), (self._avail if self.return_torch else self._avail_np)
+
+    def snapshot(self, envs=None):
+        """The complete state of envs (default: all) in a device buffer (SdcEngine.snapshot), with the rows' host-side entries: their
+        constant info entries, data-centre config and month.  Read-only: the run goes on as without it."""
+        if self._need_reset:
+            raise ValueError("snapshot: call reset() first")
+        snap = self.engine.snapshot(envs)
+        ids = snap.envs.tolist()
+        snap.extra = {"const": [self._const[i] for i in ids], "cfg_id": [self._cfg_id[i] for i in ids],
+                      "months": [self.months[i] for i in ids], "cfg_keys": self._cfg_keys, "loc_keys": self._loc_keys}
+        return snap
+
+    def restore(self, snap, envs=None, rows=None):
+        """Env envs[k] becomes snapshot row rows[k] (SdcEngine.restore: by default every row goes back to the env it was taken from; a
+        scalar `rows` is broadcast).  The host's per-env entries follow: dst's constant info entries, config and month are the row's.
+        Returns (obs, share_obs, available_actions) for ALL envs in reset()'s layout.  The device-side logger accumulator
+        (accumulate_logger_sums) is a sum over the batch, not env state: a restore leaves it alone.  ValueError for a snapshot of a vector
+        env with other data-centre configs or trace sets, and for what the engine refuses."""
+        if self._need_reset:
+            raise ValueError("restore: call reset() first")
+        x = snap.extra
+        if x.get("cfg_keys") != self._cfg_keys or x.get("loc_keys") != self._loc_keys:
+            raise ValueError("restore: the snapshot was not taken from a vector env with these data-centre configs and trace sets")
+        r, d = self.engine.restore_pairs(snap, envs, rows)
+        obs, share = self.engine.restore(snap, d, r)
+        # new lists, not writes into the old ones: the `infos` of earlier steps keep theirs (they describe those steps)
+        const, cfg_id, months = list(self._const), list(self._cfg_id), list(self.months)
+        for a, b in zip(r.tolist(), d.tolist()):
+            const[b], cfg_id[b], months[b] = x["const"][a], x["cfg_id"][a], x["months"][a]
+        self._const, self._cfg_id, self.months = const, cfg_id, months
+        return self._out(self._sel_obs(obs)), self._out(self._share3(share, obs)), (self._avail if self.return_torch else self._avail_np)
+
+    def _take_state(self, src):
+        """This env (built from src's constructor arguments, never stepped) becomes a copy of src: every env restored from a snapshot
+        of src's, the seed and the host-side state copied.  src not reset yet: nothing to restore."""
+        self.engine.set_seed(src.engine.seed)
+        self.months, self._cfg_id, self._const = list(src.months), list(src._cfg_id), list(src._const)
+        if not src._need_reset:
+            self.engine.reset()            # (the library restores into envs that have been reset once; every env is overwritten)
+            self._need_reset = False
+            self.restore(src.snapshot().to(self.engine.device))
+            self.engine.out_flat.copy_(src.engine.out_flat)      # (the last step's outputs as well)
+            self.engine.final_obs.copy_(src.engine.final_obs)
+        if src._logger_acc is not None:
+            self._logger_keys, self._logger_idx = list(src._logger_keys), list(src._logger_idx)
+            self._logger_acc = src._logger_acc.to(self.engine.device, copy=True)
+            self._logger_steps = src._logger_steps
+
+    def __deepcopy__(self, memo):
+        """copy.deepcopy: a fresh vector env from the same constructor arguments, every env restored from a snapshot of this one --
+        same global indices and seed, so the copy follows this env exactly, across resets, until the two are given different
+        actions.  Before reset() a copy is just a fresh env."""
+        import copy
+        new = type(self)(**copy.deepcopy(self._init_args, memo))
+        memo[id(self)] = new
+        new._take_state(self)
+        return new
 
     def step_async(self, actions):
         t = self._torch

@@ -214,7 +214,9 @@ const char* sdc_last_error(void);
  *   310  sdc_set_actor, sdc_rollout_actor (closed loop with the actor networks inside the kernel); debug_flags bit 7
  *        (debug_flags bits 9 / 10 came later without a bump: no layout or argument list changed)
  *   312  sdc_state_layout
- *   313  sdc_clone_envs */
+ *   313  sdc_clone_envs
+ *        (sdc_snapshot_row_bytes, sdc_snapshot_envs, sdc_restore_envs came later without a bump: new entry points, no layout or
+ *        existing argument list changed) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -345,6 +347,50 @@ int sdc_queue_stride(const sdc_handle* h);
  * that no longer exists) -- it does not move the launch counter as sdc_set_state does, which would drop the requests of every env of
  * the batch.  The windows concerned are re-requested by the step that needs them. */
 int sdc_clone_envs(sdc_handle* h, const int32_t* src, const int32_t* dst, int n, float* obs, float* share_obs, void* stream);
+
+/* replaces: copy.deepcopy(env) of the reference's SustainDC where the copy must outlive the batch or leave it -- rewinding an env
+ * (lookahead / MPC: save at t, roll out candidate A, rewind, roll out candidate B), branching several policies from one state, moving
+ * env states to an engine of another size, mapping or GPU.  An env's state goes to a row of a CALLER-OWNED device buffer and back.
+ * A row is the env's complete state in a layout that depends on the state layout (sdc_state_layout) and on episode_steps alone --
+ * never on n_envs, the mapping or the device: the state record (assignment, day range and episode counter included), the header
+ * (episode returns included; its four deferred re-centring stamps are stored as zeros), the history ring, the rank windows, the
+ * queue table, the weather windows, the episode's feature rows and the caller's obs [3][26] / share_obs [29] rows.  Not stored: the
+ * queue table's and the ring's mirrors and the per-env config scalars -- derived data, rebuilt by the restore from the row.
+ * sdc_snapshot_row_bytes: a row's size (a multiple of 256; ~145 KB at 672-step episodes), 0 for a null handle.
+ * sdc_snapshot_envs: env envs[k] -> row k of rows [n][row_bytes] (device, 256-byte aligned); manifest [n][SDC_SNAPSHOT_MANIFEST] (HOST
+ * int32) is filled at enqueue time from the host's mirrors.  READ-ONLY on the engine: the live env keeps its stamps and the launch
+ * counter does not move, so taking snapshots does not change the run they are taken from.  envs may repeat; n <= n_envs.
+ * sdc_restore_envs: env envs[k] becomes row rows_idx[k] of rows [n_rows][row_bytes] (this engine's or another's of the same state
+ * layout, episode_steps, hist_cap, queue stride and weather window length); manifest [n_rows][SDC_SNAPSHOT_MANIFEST] as the snapshot
+ * filled it.  One row may go to several envs; a dst must not appear twice.  The dst's stamps are cleared (as sdc_clone_envs does),
+ * the feature rows go back into step-major order, the mirrors are rebuilt where this engine has them, the obs / share_obs rows go to
+ * the caller's buffers and to the closed loop's copy.  The host's mirrors (episode step, feature rows, config, trace set) follow the
+ * manifest: a restore that leaves every env of the batch at one episode step (a whole-batch rewind) keeps the specialised kernels,
+ * one that leaves envs at different steps falls to the general kernel, as a masked reset does.
+ * Both calls are ordered on `stream` like a step and do not synchronise the device (the index arrays are staged as sdc_clone_envs
+ * stages its pairs); obs [N][3][26] / share_obs [N][29] are the caller's device buffers (required).  Refused (-2, nothing reaches the
+ * device): a null handle or array, n <= 0 (n_rows <= 0), an env index outside [0, n_envs), a row index outside [0, n_rows), a repeated
+ * dst, no sdc_reset yet, rows not 256-byte aligned, a manifest whose layout, episode_steps, hist_cap, queue stride or window length
+ * differs from this engine's, a cfg_id / loc_id this engine does not have.
+ * NOT part of an env's state: its global index (env_index_base + env) and the engine's seed.  A restored env finishes the saved episode
+ * exactly; its later episodes are keyed on its own slot and the engine's seed -- so a rewind in place reproduces future episodes too. */
+#define SDC_SNAPSHOT_MANIFEST 9
+enum sdc_snapshot_manifest {
+  SDC_SNAP_LAYOUT = 0,     /* sdc_state_layout() */
+  SDC_SNAP_EPISODE_STEPS,
+  SDC_SNAP_HIST_CAP,
+  SDC_SNAP_QUEUE_STRIDE,   /* sdc_queue_stride() */
+  SDC_SNAP_WINDOW_LEN,     /* sdc_weather_window_len() */
+  SDC_SNAP_T_REL,          /* the env's episode step */
+  SDC_SNAP_FEAT_OK,        /* 1: the row holds valid feature rows of the episode */
+  SDC_SNAP_CFG_ID,
+  SDC_SNAP_LOC_ID
+};
+size_t sdc_snapshot_row_bytes(const sdc_handle* h);
+int sdc_snapshot_envs(sdc_handle* h, const int32_t* envs, int n, void* rows, int32_t* manifest, const float* obs,
+                      const float* share_obs, void* stream);
+int sdc_restore_envs(sdc_handle* h, const int32_t* rows_idx, const int32_t* envs, int n, const void* rows, int n_rows,
+                     const int32_t* manifest, float* obs, float* share_obs, void* stream);
 
 /* Per-kernel timing (measurement only; off by default).  enable = k > 0 samples every k-th sdc_step, 0 switches it
  * off.  In a sampled step one lane per workgroup of each kernel stamps the device's constant-rate wall clock at

@@ -1,0 +1,436 @@
+"""Env snapshots in caller-owned device buffers (SdcEngine.snapshot / restore over sdc_snapshot_envs / sdc_restore_envs) and
+copy.deepcopy of the surfaces built on them.
+
+1. Rewind in place on every step mapping (pair, quad, wide, wide_gen mixed, the general kernel of a staggered batch, and the ring
+   mirror at 49 152 envs): snapshot at t with requests in flight, K steps through the auto-reset, restore, the same actions again --
+   every output row the same bits on every step, the kernel right after the restore the one before it, the state equal at the end.
+2. Snapshots are read-only: the state bit for bit before / after one, and a run taking one every few steps equals a run without.
+3. Subset restore and replication under the fp64 oracle (verify mode): sampled rows into several dst each, different actions after.
+4. Across engines: 4096 envs (pair kernel) -> 49 152 (wide kernel, mirrors rebuilt), slots whose global index matches the source and
+   slots whose index does not; rollout() right after a restore; rollout_actor() after a whole-batch restore.
+5. The vector env's restore (reset layout, info constants across configs) and copy.deepcopy of SustainDC.
+6. The refusals, each of which leaves the state untouched."""
+import copy
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from dc_rl_amd import _lib as L
+from dc_rl_amd import SustainDC, SustainDCVecEnv, dc_config, traces
+from dc_rl_amd.engine import SdcEngine, _CHECKPOINT
+from tests.production_rig import ProductionRig, sample_parts
+from tests.test_gpu_checkpoint import assert_same_state
+from tests.test_gpu_clone import _acts, _actor, _bits, _oracle_copy, _pending_envs, _stagger
+
+pytestmark = pytest.mark.gpu
+
+EP = 48
+SNAP_AT = 20
+RSV = L.INFO_IDX["reserved"]
+
+
+def _small(n=64, steps=16, reset=True, **kw):
+    tb = traces.synthetic_tables("ny", 0)
+    p = dc_config.size_datacenter("dc_config.json", 1, 30.0)
+    e = SdcEngine(n, episode_steps=steps, auto_reset=True, seed=5, **kw)
+    e.set_tables(0, tb["W"], tb["C"], tb["T"], tb["WB"])
+    e.set_dc_params(0, p)
+    e.assign(0, 0, 174, 188)
+    if reset:
+        e.reset()
+    return e
+
+
+class _Frozen:
+    """a state_dict() taken earlier, where assert_same_state wants an engine"""
+
+    def __init__(self, sd, config):
+        self._sd, self.config = sd, config
+
+    def state_dict(self):
+        return self._sd
+
+
+def _outputs_equal(a, b, what):
+    """(obs, share_obs, rew, done, info, final_obs) of two passes, bit for bit -- info's diagnostics column aside, final_obs in the rows
+    of the envs that finished (the others keep whatever an earlier step wrote there)"""
+    import torch
+    for nm, u, v in zip(("obs", "share_obs", "rew", "done", "info", "final_obs"), a, b):
+        if nm == "info":
+            u, v = u.clone(), v.clone()
+            u[:, RSV] = 0
+            v[:, RSV] = 0
+        if nm == "final_obs":
+            fin = a[3].bool()
+            u, v = u[fin], v[fin]
+        if not torch.equal(u, v):
+            bad = (u != v).nonzero()
+            raise AssertionError((what, nm, bad[:4].tolist()))
+
+
+def _to_pending(eng, N, g, need=2):
+    while len(_pending_envs(eng)) < need:      # (a step where re-centring requests of several envs are in flight)
+        eng.step(_acts(N, g))
+        assert eng.steps_to_episode_end() > 8
+
+
+# (mapping, envs, mixed, staggered, hist_cap)
+REWINDS = [
+    ("pair", 4096, False, False, 10000),
+    ("quad", 6144, False, False, 10000),
+    ("wide", 8192, False, False, 10000),
+    ("wide_gen", 8192, True, False, 10000),
+    ("general", 2570, False, True, 10000),
+    ("wide", 49152, False, False, 2048),      # the ring's slot-major mirror
+]
+
+
+@pytest.mark.parametrize("mapping,N,mixed,stagger,cap", REWINDS, ids=[f"{r[0]}-{r[1]}" for r in REWINDS])
+def test_rewind_in_place_replays_bit_for_bit(mapping, N, mixed, stagger, cap):
+    import torch
+    rig = ProductionRig(N, mapping, mixed=mixed, episode_steps=EP, seed=300 + N, n_random=0, oracles=False, hist_cap=cap)
+    eng = rig.eng
+    eng.reset()
+    g = torch.Generator(device="cpu").manual_seed(N)
+    if stagger:
+        _stagger(rig, g)
+    for _ in range(SNAP_AT):
+        eng.step(_acts(N, g))
+    _to_pending(eng, N, g)
+    kernel = eng.last_step_kernel()
+    if not stagger:
+        assert kernel == rig.geom.kernel, (kernel, rig.geom.kernel)
+    obs0, share0 = eng.obs.clone(), eng.share_obs.clone()
+    snap = eng.snapshot()
+    assert len(snap) == N and snap.nbytes == N * snap.rows.shape[1]
+    K = eng.steps_to_episode_end() + (14 if stagger else 6)      # (through the auto-reset: both halves' when staggered)
+    acts = [_acts(N, g) for _ in range(K)]
+    first, ends = [], 0
+    for t in range(K):
+        out = eng.step(acts[t])
+        first.append([x.clone() for x in out] + [eng.final_obs.clone()])
+        ends += int(out[3].any())
+    assert ends >= (2 if stagger else 1)
+    sd_first = eng.state_dict()
+    obs, share = eng.restore(snap)
+    assert torch.equal(obs, obs0) and torch.equal(share, share0)
+    for t in range(K):
+        out = eng.step(acts[t])
+        if t == 0:      # (load_state_dict would run the general kernel until the next boundary)
+            assert eng.last_step_kernel() == kernel, (eng.last_step_kernel(), kernel)
+        _outputs_equal(first[t], [x for x in out] + [eng.final_obs], f"{mapping} {N} replay step {t}")
+    moved = assert_same_state(_Frozen(sd_first, eng.config), eng, f"{mapping} {N} after the replay")
+    assert not bool((eng.info[:, L.INFO_IDX["fault"]] != 0).any())
+    print(f"rewind {mapping} {N}: {K} steps replayed, kernel {kernel}, rank windows placed differently {moved}")
+    eng.close()
+
+
+def test_snapshots_are_read_only():
+    import torch
+    N = 4096
+    a = ProductionRig(N, "pair", episode_steps=EP, seed=41, n_random=0, oracles=False)
+    a.eng.reset()
+    g = torch.Generator(device="cpu").manual_seed(5)
+    for _ in range(SNAP_AT):
+        a.eng.step(_acts(N, g))
+    _to_pending(a.eng, N, g)
+    # one snapshot with requests in flight: every array of the engine the same bits before and after, the stamps included
+    before = {k: _bits(a.eng.get_state(k)) for k in _CHECKPOINT}
+    obs0, left = a.eng.obs.clone(), a.eng.steps_to_episode_end()
+    assert len(_pending_envs(a.eng)) >= 2
+    snaps = [a.eng.snapshot()]
+    for k in _CHECKPOINT:
+        np.testing.assert_array_equal(_bits(a.eng.get_state(k)), before[k], err_msg=k)
+    assert torch.equal(a.eng.obs, obs0) and a.eng.steps_to_episode_end() == left
+    a.eng.close()
+    # b with snapshots every third step against a twin without, from the reset through the boundary
+    b = ProductionRig(N, "pair", episode_steps=EP, seed=41, n_random=0, oracles=False)
+    c = ProductionRig(N, "pair", episode_steps=EP, seed=41, n_random=0, oracles=False)
+    b.eng.reset()
+    c.eng.reset()
+    g = torch.Generator(device="cpu").manual_seed(7)
+    for t in range(EP):
+        x = _acts(N, g)
+        if t % 3 == 1:
+            snaps.append(b.eng.snapshot(np.arange(0, N, 5)))
+        ob = [v.clone() for v in b.eng.step(x)]
+        oc = c.eng.step(x)
+        _outputs_equal(ob + [b.eng.final_obs], list(oc) + [c.eng.final_obs], f"step {t}")
+    assert b.eng.last_step_kernel() == c.eng.last_step_kernel() == "sdc_dynamics_fast_kernel"
+    assert_same_state(b.eng, c.eng, "snapshots every third step")
+    b.eng.close()
+    c.eng.close()
+
+
+def test_subset_restore_and_replication_against_the_oracle_verify_mode():
+    """64 sampled rows -- the first and last workgroups, envs with requests in flight, envs with tasks queued -- each restored into
+    two OTHER sampled envs (their oracles copied from the source's), then every env driven by its own random actions: every sampled
+    env against the fp64 oracle every step through the boundary, whose draws begin_all holds to each dst's OWN global index; verify
+    mode checks every env's reward state."""
+    N = 4096
+    rig = ProductionRig(N, "pair", debug_flags=1, episode_steps=EP, seed=5150, n_random=260)
+    eng = rig.eng
+    obs, _ = eng.reset()
+    rig.begin_all(obs)
+    rig.single_steps(SNAP_AT, seed=5)
+    s = np.array(sorted(rig.orcs))
+    t = 0
+    while len(np.intersect1d(_pending_envs(eng), s)) < 3:
+        rig.single_steps(1, seed=100 + t)
+        t += 1
+        assert eng.steps_to_episode_end() > 8
+    parts = sample_parts(N, rig.geom)
+    pend = np.intersect1d(_pending_envs(eng), s)
+    queued = np.intersect1d(np.nonzero(eng.info[:, L.INFO_IDX["ls_tasks_in_queue"]].cpu().numpy() > 0)[0], s)
+    rng = np.random.default_rng(3)
+    first = [e for e in list(parts["first"][:2]) + list(parts["last"][:2]) + list(pend[:2]) + list(queued[:2])]
+    src = [int(e) for e in dict.fromkeys(first)]
+    rest = [int(e) for e in rng.permutation(s) if int(e) not in src]
+    src, rest = src + rest[:64 - len(src)], rest[64 - len(src):]
+    assert len(src) == 64 and len(rest) >= 128, (len(src), len(rest))
+    src, dst = np.array(src), np.array(rest[:128])
+    snap = eng.snapshot(src)
+    rows = np.r_[np.arange(64), np.arange(64)]
+    eng.restore(snap, envs=dst, rows=rows)
+    for r, d in zip(rows, dst):
+        rig.orcs[int(d)] = _oracle_copy(rig.orcs[int(src[r])])
+    resets = rig.resets
+    rig.single_steps(EP - SNAP_AT - t + 6, seed=9)        # (independent actions per env: the copies diverge from their sources)
+    assert rig.resets == resets + 1
+    print(f"subset restore: 64 rows -> 128 dst, {len(pend)} sampled envs pending, worst {rig.worst}")
+    rig.assert_ok()
+    assert (eng.get_state("order_stat_sticky") == 0).all()
+    eng.close()
+
+
+def test_across_engines_4096_pair_to_49152_wide():
+    import torch
+    BASE, cap = 40000, 2048
+    a = ProductionRig(4096, "pair", episode_steps=EP, seed=77, n_random=0, oracles=False, hist_cap=cap, env_index_base=BASE)
+    b = ProductionRig(49152, "wide", episode_steps=EP, seed=77, n_random=0, oracles=False, hist_cap=cap)
+    ea, eb = a.eng, b.eng
+    ea.reset()
+    eb.reset()
+    g = torch.Generator(device="cpu").manual_seed(11)
+    for _ in range(SNAP_AT):
+        ea.step(_acts(4096, g))
+        eb.step(_acts(49152, g))
+    _to_pending(ea, 4096, g)
+    while eb.steps_to_episode_end() > ea.steps_to_episode_end():      # (the two batches at one episode step)
+        eb.step(_acts(49152, g))
+    kernel = eb.last_step_kernel()
+    assert kernel == "sdc_dynamics_wide_kernel"
+    snap = ea.snapshot()
+    same = BASE + np.arange(4096)        # global index = the source's
+    other = np.arange(4096)              # another global index
+    eb.restore(snap, envs=np.r_[same, other], rows=np.r_[np.arange(4096), np.arange(4096)])
+    src = np.arange(4096)
+    live = np.ones(4096, bool)
+    for t in range(ea.steps_to_episode_end() + 6):
+        x = _acts(4096, g)
+        y = _acts(49152, g)
+        y[torch.as_tensor(same)] = x
+        y[torch.as_tensor(other)] = x
+        oa = [v.clone() for v in ea.step(x)]
+        ob = eb.step(y)
+        if t == 0:
+            assert eb.last_step_kernel() == kernel
+        done = bool(oa[3].any())
+        for nm, u, v in zip(("obs", "share_obs", "rew", "done", "info"), oa, ob):
+            if nm == "info":
+                u, v = u.clone(), v.clone()
+                u[:, RSV] = 0
+                v[:, RSV] = 0
+            assert torch.equal(u, v[torch.as_tensor(same)]), (t, nm, "matching index")
+            if live.all() and not (done and nm == "obs" or done and nm == "share_obs"):
+                assert torch.equal(u, v[torch.as_tensor(other)]), (t, nm, "other index")
+        if done:
+            live[:] = False
+            assert not torch.equal(oa[0], ob[0][torch.as_tensor(other)])      # (their own next episodes)
+    assert not live.any()
+    # rollout() right after a restore: the same bits as the source's
+    snap = ea.snapshot()
+    eb.restore(snap, envs=same)
+    K = min(8, ea.steps_to_episode_end())
+    xs = torch.randint(0, 3, (K, 4096, 3), dtype=torch.int32, generator=g).cuda()
+    ys = torch.randint(0, 3, (K, 49152, 3), dtype=torch.int32, generator=g).cuda()
+    ys[:, torch.as_tensor(same)] = xs
+    ra = [v.clone() for v in ea.rollout(xs)]
+    rb = eb.rollout(ys)
+    for k in range(K):
+        for nm, u, v in zip(("obs", "share_obs", "rew", "done", "info"), [w[k] for w in ra], [w[k] for w in rb]):
+            if nm == "info":
+                u, v = u.clone(), v.clone()
+                u[:, RSV] = 0
+                v[:, RSV] = 0
+            assert torch.equal(u, v[torch.as_tensor(same)]), ("rollout", k, nm)
+    # rollout_actor() after a WHOLE-batch restore (the closed loop refuses staggered batches): every slot j is source env j % 4096
+    for e in (ea, eb):
+        for s_ in range(3):
+            e.set_actor(s_, _actor(10 + s_))
+    ea.step(_acts(4096, g))          # (latch the observations on both; then the whole of b from a)
+    eb.step(_acts(49152, g))
+    snap = ea.snapshot()
+    eb.restore(snap, envs=np.arange(49152), rows=np.arange(49152) % 4096)
+    K = min(6, ea.steps_to_episode_end())
+    oa = ea.rollout_actor(K, sample=False, want_logits=True)
+    ob = eb.rollout_actor(K, sample=False, want_logits=True)
+    idx = torch.as_tensor(np.arange(49152) % 4096, device=ob[0].device)
+    for nm, u, v in zip(("obs", "share_obs", "rew", "done", "info", "actions", "logits"), oa, ob):
+        if nm == "info":
+            u, v = u.clone(), v.clone()
+            u[..., RSV] = 0
+            v[..., RSV] = 0
+        assert torch.equal(u[:, idx], v), ("closed loop", nm)
+    print(f"across engines: 4096 -> 49152, kernels {kernel} / {eb.last_step_kernel()}, row {snap.rows.shape[1]} bytes")
+    ea.close()
+    eb.close()
+
+
+def _info_dict(row):
+    return {k: row[k] for k in row.keys()}
+
+
+def test_vec_env_restore_returns_reset_layout_and_carries_the_info_constants():
+    args = [{"location": "ny", "month": 6, "days_per_episode": 1, "partial_obs": True, "nonoverlapping_shared_obs_space": True,
+             "dc_config_file": ("dc_config.json", "dc_config_r16.json")[i % 2]} for i in range(16)]
+    env = SustainDCVecEnv(args, n_envs=16, seed=3, months=[6] * 16)
+    o0, s0, a0 = env.reset()
+    env.step(np.ones((16, 3), np.int32))
+    assert _info_dict(env.step(np.ones((16, 3), np.int32))[4][3][0])["dc_power_ub_kW"] != \
+        _info_dict(env.step(np.ones((16, 3), np.int32))[4][0][0])["dc_power_ub_kW"]
+    snap = env.snapshot([0])
+    o, s, a = env.restore(snap, envs=[3, 5], rows=0)
+    assert o.shape == o0.shape and s.shape == s0.shape and a.shape == a0.shape
+    np.testing.assert_array_equal(o[[3, 5]], o[[0, 0]])
+    assert env._cfg_id[3] == env._cfg_id[5] == env._cfg_id[0]
+    rng = np.random.default_rng(1)
+    for t in range(3):
+        x = rng.integers(0, 3, (16, 3)).astype(np.int32)
+        x[[3, 5]] = x[0]
+        infos = env.step(x)[4]
+        for e in (3, 5):
+            for ag in range(3):
+                p, q = _info_dict(infos[0][ag]), _info_dict(infos[e][ag])
+                assert p.keys() == q.keys()
+                for k in p:
+                    if k != "reserved":
+                        assert np.array_equal(np.asarray(p[k]), np.asarray(q[k])), (t, e, ag, k)
+    with pytest.raises(ValueError):
+        env.restore(snap, envs=[1, 1], rows=0)
+    env.close()
+
+
+def _step_dicts_equal(r1, r2, what):
+    o1, rew1, te1, tr1, i1 = r1
+    o2, rew2, te2, tr2, i2 = r2
+    assert o1.keys() == o2.keys() and rew1 == rew2 and te1 == te2 and tr1 == tr2, what
+    for k in o1:
+        assert np.array_equal(o1[k], o2[k]), (what, k)
+    for k in i1["__common__"]:
+        if k != "reserved":
+            assert np.array_equal(np.asarray(i1["__common__"][k]), np.asarray(i2["__common__"][k])), (what, k)
+
+
+def test_deepcopy_of_sustaindc_follows_the_original_past_a_reset():
+    """copy.deepcopy(SustainDC(...)) after some steps -- the reference's branching idiom, which raised ValueError from the engine's
+    ctypes handle before -- gives an env whose step() dicts equal the original's under the same actions, across a reset; under other
+    actions the two part, and the original still equals a third env that was never copied."""
+    cfg = {"location": "ny", "month": 6, "days_per_episode": 1}
+    fresh = copy.deepcopy(SustainDC(cfg, seed=4))       # (before reset(): just a fresh env)
+    env, third = SustainDC(cfg, seed=4), SustainDC(cfg, seed=4)
+    env.reset()
+    third.reset()
+    rng = np.random.default_rng(2)
+    agents = env.agents
+    acts = lambda: {a: int(rng.integers(0, 3)) for a in agents}
+    for _ in range(30):
+        x = acts()
+        env.step(x)
+        third.step(x)
+    cp = copy.deepcopy(env)
+    resets = 0
+    for t in range(120):
+        x = acts()
+        r1, r2, r3 = env.step(x), cp.step(x), third.step(x)
+        _step_dicts_equal(r1, r2, f"copy step {t}")
+        _step_dicts_equal(r1, r3, f"third step {t}")
+        if r1[3]["__all__"]:
+            for e in (env, cp, third):
+                e.reset()
+            resets += 1
+    assert resets >= 1
+    parted = False
+    for t in range(20):
+        x, y = acts(), acts()
+        r1, r2, r3 = env.step(x), cp.step(y), third.step(x)
+        _step_dicts_equal(r1, r3, f"original vs third, step {t}")
+        parted |= any(not np.array_equal(r1[0][k], r2[0][k]) for k in r1[0]) or r1[1] != r2[1]
+    assert parted
+    fresh.reset()
+    for e in (fresh, env, cp, third):
+        e.close()
+
+
+def test_refusals_change_nothing():
+    import torch
+    e = _small()
+    g = torch.Generator(device="cpu").manual_seed(1)
+    for _ in range(5):
+        e.step(_acts(64, g))
+    snap = e.snapshot([1, 2, 3])
+    before = {k: _bits(e.get_state(k)) for k in _CHECKPOINT}
+    obs0, left = e.obs.clone(), e.steps_to_episode_end()
+    bad = [
+        (lambda: e.snapshot([]), "n must be positive"),
+        (lambda: e.snapshot([64]), "outside"),
+        (lambda: e.snapshot([-1]), "outside"),
+        (lambda: e.snapshot(np.zeros(65, np.int64)), "more than"),
+        (lambda: e.restore(snap, envs=[64], rows=[0]), "outside"),
+        (lambda: e.restore(snap, envs=[4], rows=[3]), "outside"),
+        (lambda: e.restore(snap, envs=[4, 4], rows=[0, 1]), "twice"),
+        (lambda: e.restore(snap, envs=[4, 5]), "rows="),
+    ]
+    for fn, msg in bad:
+        with pytest.raises(ValueError, match=msg):
+            fn()
+    # the library's own manifest checks, without the binding's
+    ip = C.POINTER(C.c_int32)
+    r, d = np.zeros(1, np.int32), np.array([9], np.int32)
+    for col, delta, msg in ((0, 1, b"state layout"), (1, 1, b"episode_steps"), (2, 1, b"hist_cap"), (3, 64, b"queue stride"),
+                            (4, 1, b"window length"), (7, 5, b"cfg_id"), (8, 5, b"loc_id"), (5, 1000, b"episode step")):
+        m = snap.manifest.copy()
+        m[0, col] += delta
+        rc = e.lib.sdc_restore_envs(e._h, r.ctypes.data_as(ip), d.ctypes.data_as(ip), 1, C.c_void_p(snap.rows.data_ptr()), 3,
+                                    m.ctypes.data_as(ip), C.c_void_p(e.obs.data_ptr()), C.c_void_p(e.share_obs.data_ptr()), None)
+        assert rc == -2 and msg in e.lib.sdc_last_error(), (col, rc, e.lib.sdc_last_error())
+    m = snap.manifest.copy()
+    rc = e.lib.sdc_restore_envs(e._h, r.ctypes.data_as(ip), d.ctypes.data_as(ip), 1, C.c_void_p(snap.rows.data_ptr() + 16), 3,
+                                m.ctypes.data_as(ip), C.c_void_p(e.obs.data_ptr()), C.c_void_p(e.share_obs.data_ptr()), None)
+    assert rc == -2 and b"aligned" in e.lib.sdc_last_error()
+    assert e.lib.sdc_restore_envs(e._h, None, None, 1, None, 1, None, None, None, None) == -2
+    assert b"null array" in e.lib.sdc_last_error()
+    # snapshots of engines of another shape
+    for kw, key in ((dict(steps=24), "episode_steps"), (dict(hist_cap=5000), "hist_cap")):
+        other = _small(**kw)
+        with pytest.raises(ValueError, match=key):
+            e.restore(other.snapshot([0]), envs=[4])
+        with pytest.raises(ValueError, match=key):
+            other.restore(snap, envs=[4], rows=0)
+        other.close()
+    for k in _CHECKPOINT:
+        np.testing.assert_array_equal(_bits(e.get_state(k)), before[k], err_msg=k)
+    assert torch.equal(e.obs, obs0) and e.steps_to_episode_end() == left
+    fresh = _small(reset=False)
+    with pytest.raises(ValueError, match="sdc_reset"):
+        fresh.snapshot([0])
+    with pytest.raises(ValueError, match="sdc_reset"):
+        fresh.restore(snap, envs=[0], rows=0)
+    # and a restore that is allowed: one row into several envs
+    e.restore(snap, envs=[10, 11, 12], rows=1)
+    for k in ("record", "hist", "qtab"):
+        v = _bits(e.get_state(k))
+        assert (v[[10, 11, 12]] == v[2]).all(), k
+    fresh.close()
+    e.close()
