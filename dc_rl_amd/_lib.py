@@ -23,7 +23,9 @@ ABI_VERSION = 313  # include/sustaindc_hip.h SDC_ABI_VERSION: the struct layouts
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
-           "sdc_snapshot.hip"]
+           "sdc_snapshot.hip", "sdc_mark.hip"]
+MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
+MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 SNAPSHOT_MANIFEST = 9   # include/sustaindc_hip.h SDC_SNAPSHOT_MANIFEST: int32 entries per snapshot row's manifest (enum sdc_snapshot_manifest)
 # (-amdgpu-sched-strategy=max-ilp: the machine scheduler orders for instruction-level parallelism instead of minimal register
 #  pressure -- the step kernels' occupancy is pinned by amdgpu_waves_per_eu anyway, and their time is dependent-issue latency:
@@ -137,6 +139,7 @@ EXPORTS = [
     "sdc_hist_stride", "sdc_queue_stride", "sdc_profile_enable", "sdc_profile_read",
     "sdc_set_actor", "sdc_rollout_actor", "sdc_clone_envs",
     "sdc_snapshot_row_bytes", "sdc_snapshot_envs", "sdc_restore_envs",
+    "sdc_mark_row_bytes", "sdc_mark_envs", "sdc_rewind_envs",
 ]
 
 
@@ -289,6 +292,10 @@ def load():
     L.sdc_snapshot_row_bytes.restype = C.c_size_t
     L.sdc_snapshot_envs.argtypes = [vp, ip, C.c_int, vp, ip, fp, fp, vp]
     L.sdc_restore_envs.argtypes = [vp, ip, ip, C.c_int, vp, C.c_int, ip, fp, fp, vp]
+    L.sdc_mark_row_bytes.argtypes = [C.c_int]
+    L.sdc_mark_row_bytes.restype = C.c_size_t
+    L.sdc_mark_envs.argtypes = [vp, ip, C.c_int, C.c_int, vp, ip, fp, fp, vp]
+    L.sdc_rewind_envs.argtypes = [vp, ip, C.c_int, vp, ip, fp, fp, vp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -19,6 +20,7 @@
 #include "sdc_actor.hpp"
 #include "sdc_clone.hpp"
 #include "sdc_snapshot.hpp"
+#include "sdc_mark.hpp"
 
 extern "C" __global__ void sdc_dynamics_kernel(SdcDev S, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
                                                unsigned char* done, float* info, float* final_obs, float* rew);
@@ -51,6 +53,7 @@ extern "C" __global__ void sdc_rollout_kernel(SdcDev S, int K, int rel_hint, con
 
 hipError_t sdc_clone_launch(const SdcClonePlan& P, hipStream_t st);     // sdc_clone.hip
 hipError_t sdc_snapshot_launch(const SdcSnapPlan& P, bool save, hipStream_t st);     // sdc_snapshot.hip
+hipError_t sdc_mark_launch(const SdcMarkPlan& P, bool save, hipStream_t st);     // sdc_mark.hip
 
 extern "C" __global__ void sdc_reset_kernel(SdcDev S, int use_override, const int* ovr_day, const int* ovr_hour,
                                             const double* ovr_ci_min, const double* ovr_ci_max, const double* ovr_t_min,
@@ -159,6 +162,11 @@ struct sdc_handle {
   bool snap_in_flight[2] = {false, false};
   bool snap_ready = false;
   int snap_slot = 0;
+  // sdc_mark_envs / sdc_rewind_envs: ONE live mark per env -- the serial of the env's latest mark (0: none alive; sized by the first
+  // mark), cleared by whatever rewrites state a mark row does not hold (mark_kill); the index staging is the snapshot calls'
+  std::vector<int> mark_serial;
+  int mark_next_serial = 0;
+  int mark_engine_id = 0;                 // this handle's id in the manifests it fills (given out by the first mark)
 };
 
 namespace {
@@ -447,6 +455,14 @@ void recompute_steps_to_terminal(sdc_handle* h) {
     if (h->host_t_rel[e] != h->rel_hint) h->rel_hint = -1;
 }
 
+// every mark of env e is dead: its episode, ring, queue table, windows or feature rows are being rewritten as a whole
+inline void mark_kill(sdc_handle* h, const int e) {
+  if (!h->mark_serial.empty()) h->mark_serial[(size_t)e] = 0;
+}
+inline void mark_kill_all(sdc_handle* h) {
+  if (!h->mark_serial.empty()) std::fill(h->mark_serial.begin(), h->mark_serial.end(), 0);
+}
+
 }  // namespace
 
 extern "C" {
@@ -632,6 +648,9 @@ int sdc_create(const sdc_config* cfg, sdc_handle** out) {
       {"t_win", (void**)&d.t_win, sizeof(double) * (size_t)d.lw, 0, 0},
       {"wb_win", (void**)&d.wb_win, sizeof(double) * (size_t)d.lw, 0, 0},
       {"qtab", (void**)&d.qtab, sizeof(uint2) * (size_t)d.qstride, 0, 0},
+      // READ-ONLY (sdc_get_state alone; refused where the batch has none): the slot-major mirrors, [qstride][N] / [hist_cap][N] raw dwords
+      {"qcum_t", (void**)&d.qcum_t, sizeof(unsigned) * (size_t)d.qstride, 0, 0},
+      {"hist_t", (void**)&d.hist_t, sizeof(unsigned) * (size_t)d.hist_cap, 0, 0},
   };
   // scale starts at 1, last_delta = None (envs/dc_gym.py:81-83)
   {
@@ -906,6 +925,7 @@ int sdc_reset(sdc_handle* h, const uint8_t* mask_host, const sdc_reset_override*
     if (!mask_host || mask_host[e]) {
       h->host_t_rel[e] = 0;
       note_features(h, e);
+      mark_kill(h, e);
     }
   recompute_steps_to_terminal(h);
   h->started = true;
@@ -977,6 +997,7 @@ int sdc_step(sdc_handle* h, const int32_t* actions, float* obs, float* share_obs
         if (h->host_t_rel[e] >= h->cfg.episode_steps) {
           h->host_t_rel[e] = 0;
           note_features(h, e);
+          mark_kill(h, e);
         }
       recompute_steps_to_terminal(h);
     }
@@ -1072,6 +1093,7 @@ int sdc_rollout(sdc_handle* h, int n_steps, const int32_t* actions, float* obs, 
         if (h->host_t_rel[e] >= h->cfg.episode_steps) {
           h->host_t_rel[e] = 0;
           note_features(h, e);
+          mark_kill(h, e);
         }
       recompute_steps_to_terminal(h);
     }
@@ -1182,6 +1204,7 @@ int sdc_rollout_actor(sdc_handle* h, int n_steps, int sample, float* obs, float*
         if (h->host_t_rel[e] >= h->cfg.episode_steps) {
           h->host_t_rel[e] = 0;
           note_features(h, e);
+          mark_kill(h, e);
         }
       recompute_steps_to_terminal(h);
       if (latch_obs(h, obs + last * SDC_OBS_OUT, st)) return -1;     // the next launch starts from the reset observations
@@ -1263,6 +1286,7 @@ int sdc_get_state(sdc_handle* h, const char* field, void* host_buf, size_t bytes
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());
   if (!f->ptr) return rec_get(h, f->rec_idx, f->rec_dwords, host_buf, f->in_hdr);
+  if (!*f->ptr) return fail_msg(std::string("sdc_get_state: this batch has no ") + field);
   HIP_TRY(hipMemcpy(host_buf, *f->ptr, need, hipMemcpyDeviceToHost));
   if (std::strcmp(field, "hist") == 0) {  // device keys -> fp32 offsets (empty slot -> NaN)
     unsigned* u = static_cast<unsigned*>(host_buf);
@@ -1287,6 +1311,8 @@ int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t
   if (!h || !field || !host_buf) return fail_msg("sdc_set_state: null argument");
   const Field* f = find_field(h, field);
   if (!f) return fail_msg(std::string("sdc_set_state: unknown field ") + field);
+  if (std::strcmp(field, "qcum_t") == 0 || std::strcmp(field, "hist_t") == 0)
+    return fail_msg(std::string("sdc_set_state: ") + field + " is derived from " + (field[0] == 'q' ? "qtab" : "hist") + ": write that");
   const size_t need = f->elem * (size_t)h->cfg.n_envs;
   if (bytes != need) return fail_msg(std::string("sdc_set_state: size mismatch for ") + field);
   // what the kernels index with is validated BEFORE anything reaches the device: a config id out of range would index
@@ -1348,6 +1374,7 @@ int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t
     HIP_TRY(hipDeviceSynchronize());
   }
   h->latch_valid = false;                  // (closed loop: the library's copy of the latest observations describes the state before this write)
+  mark_kill_all(h);                        // (a mark row holds only what steps change: whatever was written, it may not be that)
   if (invalidate_features(h)) return -1;   // whatever was written, the precomputed observation rows may no longer match it
   // Deferred window re-centrings in flight belong to the state that has just been overwritten: a restored header may
   // carry request stamps (H_PEND) that the NEXT step would find "two steps old" again and take a swept window over --
@@ -1473,6 +1500,7 @@ int sdc_clone_envs(sdc_handle* h, const int32_t* src, const int32_t* dst, int n,
   for (int k = 0; k < n; k++) {
     const int s = src[k], t = dst[k];
     h->host_t_rel[(size_t)t] = h->host_t_rel[(size_t)s];
+    mark_kill(h, t);
     if (h->feat_host[(size_t)t] != h->feat_host[(size_t)s]) {
       h->n_feat_host += h->feat_host[(size_t)s] ? 1 : -1;
       h->feat_host[(size_t)t] = h->feat_host[(size_t)s];
@@ -1742,6 +1770,7 @@ int sdc_restore_envs(sdc_handle* h, const int32_t* rows_idx, const int32_t* envs
     const int32_t* m = manifest + (size_t)x.y * SDC_SNAPSHOT_MANIFEST;
     const size_t e = (size_t)x.x;
     h->host_t_rel[e] = m[SDC_SNAP_T_REL];
+    mark_kill(h, x.x);
     const unsigned char f = (d.feat && m[SDC_SNAP_FEAT_OK]) ? 1 : 0;
     if (h->feat_host[e] != f) {
       h->n_feat_host += f ? 1 : -1;
@@ -1754,6 +1783,197 @@ int sdc_restore_envs(sdc_handle* h, const int32_t* rows_idx, const int32_t* envs
     h->racks_max = 0;
     for (int e = 0; e < N; e++) h->racks_max = std::max(h->racks_max, h->dc_host[(size_t)h->cfg_host[(size_t)e]].p.n_racks);
   }
+  recompute_steps_to_terminal(h);
+  return 0;
+}
+
+// ---- marks (sdc_mark.hip) --------------------------------------------------------------------------------------------------------
+// What a mark row holds and why that is enough: include/sustaindc_hip.h; the row layout: sdc_mark.hpp.
+size_t sdc_mark_row_bytes(int max_steps) {
+  if (max_steps < 1 || max_steps > SDC_MARK_MAX_STEPS) return 0;
+  return ((size_t)SDC_MARK_FIXED_BYTES + 12u * (size_t)max_steps + 255u) / 256u * 256u;
+}
+
+// the part of the plan both directions share.  -> false: observation rows that are not dword-aligned
+static bool mark_plan(const sdc_handle* h, SdcMarkPlan& P, const int n, const int max_steps, const void* rows, const float* obs,
+                      const float* share_obs) {
+  const SdcDev& d = h->d;
+  std::memset(&P, 0, sizeof(P));
+  P.n = n;
+  P.n_envs = h->cfg.n_envs;
+  P.max_steps = max_steps;
+  P.hist_cap = d.hist_cap;
+  P.qstride = d.qstride;
+  P.rows = static_cast<unsigned char*>(const_cast<void*>(rows));
+  P.row_bytes = (unsigned)sdc_mark_row_bytes(max_steps);
+  P.rec = d.rec;
+  P.hdr = d.hdr;
+  P.qwin = d.qwin;
+  P.hist = d.hist;
+  P.qtab = reinterpret_cast<unsigned*>(d.qtab);
+  P.obs = const_cast<float*>(obs);
+  P.share_obs = const_cast<float*>(share_obs);
+  P.blocks_a = (n + SDC_MARK_ENVS_PER_BLOCK - 1) / SDC_MARK_ENVS_PER_BLOCK;
+  return ((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(share_obs)) & 3u) == 0 && d.hist_cap >= 1 &&
+         d.hist_cap <= SDC_HIST_STRIDE && d.qstride >= 1;
+}
+
+// the arguments both calls refuse alike ("" if they pass)
+static std::string mark_args_error(const sdc_handle* h, const int32_t* envs, const int n, const void* rows, const void* manifest,
+                                   const void* obs, const void* share_obs) {
+  if (n <= 0) return "n must be positive";
+  if (!rows || !manifest || !obs || !share_obs) return "null array";
+  if (!h->started) return "sdc_reset must be called first";
+  const int N = h->cfg.n_envs;
+  if (n > N) return "n = " + std::to_string(n) + " is more than the batch's " + std::to_string(N) + " envs";
+  if (!envs && n != N) return "envs == NULL means the whole batch: n must be " + std::to_string(N) + ", not " + std::to_string(n);
+  if (envs)
+    for (int k = 0; k < n; k++)
+      if (envs[k] < 0 || envs[k] >= N)
+        return "env " + std::to_string(envs[k]) + " (entry " + std::to_string(k) + ") outside [0, " + std::to_string(N) + ")";
+  if ((reinterpret_cast<uintptr_t>(rows) & 255u) != 0) return "rows must be 256-byte aligned";
+  return "";
+}
+
+// the launch's {env, row} pairs (sorted by env: range M's lanes are then consecutive envs) through the snapshot calls' staging slots;
+// envs == NULL: nothing to stage.  row_of: env -> its row, -1 for the others
+static int mark_launch(sdc_handle* h, SdcMarkPlan& P, const bool save, const std::vector<int>& row_of, const bool whole,
+                       hipStream_t st) {
+  if (whole) {
+    HIP_TRY(sdc_mark_launch(P, save, st));
+    return 0;
+  }
+  std::vector<int4> ix;
+  ix.reserve((size_t)P.n);
+  for (int e = 0; e < P.n_envs; e++)
+    if (row_of[(size_t)e] >= 0) ix.push_back(make_int4(e, row_of[(size_t)e], 0, 0));
+  int slot = 0;
+  if (snap_stage(h, ix, st, &slot)) return -1;
+  P.idx = h->snap_idx_dev + (size_t)slot * h->cfg.n_envs;
+  HIP_TRY(sdc_mark_launch(P, save, st));
+  HIP_TRY(hipEventRecord(h->snap_done[slot], st));
+  h->snap_in_flight[slot] = true;
+  return 0;
+}
+
+// What the next max_steps steps can change in env envs[k] -> mark row k, ordered on `stream` like a step, read-only on the engine.  The
+// env's earlier mark is dead from here on.
+int sdc_mark_envs(sdc_handle* h, const int32_t* envs, int n, int max_steps, void* rows, int32_t* manifest, const float* obs,
+                  const float* share_obs, void* stream) {
+  if (!h) return fail_msg("sdc_mark_envs: null handle");
+  if (max_steps < 1 || max_steps > SDC_MARK_MAX_STEPS)
+    return fail_msg("sdc_mark_envs: max_steps = " + std::to_string(max_steps) + " outside [1, " + std::to_string(SDC_MARK_MAX_STEPS) + "]");
+  const std::string why = mark_args_error(h, envs, n, rows, manifest, obs, share_obs);
+  if (!why.empty()) return fail_msg("sdc_mark_envs: " + why);
+  const int N = h->cfg.n_envs;
+  std::vector<int> row_of;
+  if (envs) {
+    row_of.assign((size_t)N, -1);
+    for (int k = 0; k < n; k++) {
+      if (row_of[(size_t)envs[k]] >= 0) return fail_msg("sdc_mark_envs: env " + std::to_string(envs[k]) + " appears twice");
+      row_of[(size_t)envs[k]] = k;
+    }
+  }
+  SdcMarkPlan P;
+  if (!mark_plan(h, P, n, max_steps, rows, obs, share_obs)) return fail_msg("sdc_mark_envs: obs / share_obs rows not dword-aligned");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (mark_launch(h, P, true, row_of, envs == nullptr, st)) return -1;
+  // the bookkeeping behind the launch: the device is already at work while the host fills the manifest
+  sync_mirror(h);
+  if (h->mark_serial.empty()) h->mark_serial.assign((size_t)N, 0);
+  if (!h->mark_engine_id) {
+    static std::atomic<int> ids{0};
+    h->mark_engine_id = ++ids;
+  }
+  h->mark_next_serial = h->mark_next_serial == 0x7FFFFFFF ? 1 : h->mark_next_serial + 1;
+  const int32_t layout = (int32_t)state_layout_hash();
+  for (int k = 0; k < n; k++) {
+    const int e = envs ? envs[k] : k;
+    h->mark_serial[(size_t)e] = h->mark_next_serial;
+    int32_t* m = manifest + (size_t)k * SDC_MARK_MANIFEST;
+    m[SDC_MARK_M_LAYOUT] = layout;
+    m[SDC_MARK_M_ENGINE] = h->mark_engine_id;
+    m[SDC_MARK_M_STEPS] = max_steps;
+    m[SDC_MARK_M_ENV] = e;
+    m[SDC_MARK_M_SERIAL] = h->mark_next_serial;
+    m[SDC_MARK_M_T_REL] = h->host_t_rel[(size_t)e];
+    m[SDC_MARK_M_HIST_CAP] = h->cfg.hist_cap;
+  }
+  return 0;
+}
+
+// Mark row k -> env envs[k], the slot it was taken from; the host mirrors follow the manifest, so a whole-batch rewind of a lock-step
+// batch keeps rel_hint and the specialised kernels.  The mark stays alive: a rewind may be repeated.
+int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows, const int32_t* manifest, float* obs, float* share_obs,
+                    void* stream) {
+  if (!h) return fail_msg("sdc_rewind_envs: null handle");
+  std::string why = mark_args_error(h, envs, n, rows, manifest, obs, share_obs);
+  if (!why.empty()) return fail_msg("sdc_rewind_envs: " + why);
+  const int N = h->cfg.n_envs;
+  // every refusal before anything reaches the device, from the host's mirrors
+  sync_mirror(h);
+  const int32_t layout = (int32_t)state_layout_hash();
+  const int max_steps = manifest[SDC_MARK_M_STEPS];
+  if (max_steps < 1 || max_steps > SDC_MARK_MAX_STEPS)
+    return fail_msg("sdc_rewind_envs: manifest with max_steps = " + std::to_string(max_steps) + " outside [1, " +
+                    std::to_string(SDC_MARK_MAX_STEPS) + "]");
+  std::vector<int> row_of;
+  if (envs) row_of.assign((size_t)N, -1);
+  // (the scan goes on behind the first refusal: every mark of the call that has been overrun dies; a message is built for the first only)
+  int bad_k = -1, bad_why = 0;
+  for (int k = 0; k < n; k++) {
+    const int e = envs ? envs[k] : k;
+    const int32_t* m = manifest + (size_t)k * SDC_MARK_MANIFEST;
+    int w = 0;
+    if (m[SDC_MARK_M_LAYOUT] != layout) w = 1;
+    else if (h->mark_engine_id == 0 || m[SDC_MARK_M_ENGINE] != h->mark_engine_id) w = 2;
+    else if (m[SDC_MARK_M_ENV] != e) w = 3;
+    else if (m[SDC_MARK_M_STEPS] != max_steps || m[SDC_MARK_M_HIST_CAP] != h->cfg.hist_cap) w = 4;
+    else if (envs && row_of[(size_t)e] >= 0) w = 5;
+    else if (m[SDC_MARK_M_SERIAL] == 0 || h->mark_serial[(size_t)e] != m[SDC_MARK_M_SERIAL]) w = 6;
+    else if (h->host_t_rel[(size_t)e] < m[SDC_MARK_M_T_REL]) w = 7;
+    else if (h->host_t_rel[(size_t)e] - m[SDC_MARK_M_T_REL] > max_steps) {
+      w = 8;
+      h->mark_serial[(size_t)e] = 0;     // slots beyond the row's reach have been overwritten: nothing can bring this mark back
+    }
+    if (envs) row_of[(size_t)e] = k;
+    if (w && bad_k < 0) { bad_k = k; bad_why = w; }
+  }
+  if (bad_k >= 0) {
+    const int e = envs ? envs[bad_k] : bad_k;
+    const int32_t* m = manifest + (size_t)bad_k * SDC_MARK_MANIFEST;
+    const int taken = h->host_t_rel[(size_t)e] - m[SDC_MARK_M_T_REL];
+    switch (bad_why) {
+      case 1: why = "state layout " + std::to_string(m[SDC_MARK_M_LAYOUT]) + ", this library's is " + std::to_string(layout); break;
+      case 2: why = "the mark was taken from another engine (a mark goes back into the engine and the env it came from)"; break;
+      case 3: why = "the mark was taken from env " + std::to_string(m[SDC_MARK_M_ENV]); break;
+      case 4: why = "max_steps / hist_cap differ from the first row's / this engine's (the rows of a call come from one sdc_mark_envs call)"; break;
+      case 5: why = "the env appears twice"; break;
+      case 6: why = "the mark is dead (a later mark of the env, a reset, sdc_set_state, a clone or restore into the env, or an earlier "
+                    "rewind refused beyond its max_steps)"; break;
+      case 7: why = "the env is at episode step " + std::to_string(h->host_t_rel[(size_t)e]) + ", before the mark's " +
+                    std::to_string(m[SDC_MARK_M_T_REL]); break;
+      default: why = std::to_string(taken) + " steps taken since the mark, more than its max_steps = " + std::to_string(max_steps) +
+                     " (the mark is dead for good: slots beyond its reach have been overwritten)";
+    }
+    return fail_msg("sdc_rewind_envs: row " + std::to_string(bad_k) + " (env " + std::to_string(e) + "): " + why);
+  }
+  SdcMarkPlan P;
+  if (!mark_plan(h, P, n, max_steps, rows, obs, share_obs)) return fail_msg("sdc_rewind_envs: obs / share_obs rows not dword-aligned");
+  const SdcDev& d = h->d;
+  P.obs_latch = h->obs_latch;
+  if (d.qcum_t) {      // M: the mirrors' rows of the rewound slots
+    P.qcum_t = d.qcum_t;
+    P.hist_t = d.hist_t;
+    P.m_chunks = (max_steps + SDC_MARK_MIRROR_J - 1) / SDC_MARK_MIRROR_J;
+    P.blocks_m = (n + SDC_MARK_BLOCK - 1) / SDC_MARK_BLOCK * P.m_chunks;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (mark_launch(h, P, false, row_of, envs == nullptr, st)) return -1;
+  // the host mirrors follow the manifest: the episode step (feature rows, config and trace set are the episode's: unchanged)
+  for (int k = 0; k < n; k++) h->host_t_rel[(size_t)(envs ? envs[k] : k)] = manifest[(size_t)k * SDC_MARK_MANIFEST + SDC_MARK_M_T_REL];
   recompute_steps_to_terminal(h);
   return 0;
 }

@@ -69,6 +69,33 @@ class EnvSnapshot:
         return EnvSnapshot(self.rows.to(device), self.manifest, self.meta, self.envs, self.extra)
 
 
+class EnvMark:
+    """What the next `max_steps` steps can change in envs (SdcEngine.mark): `rows` uint8 [n, row_bytes] on the engine's device -- row k
+    belongs to env `envs[k]` (include/sustaindc_hip.h sdc_mark_envs: ~2.3 KB per env for 16 steps, against a snapshot's ~146 KB) --,
+    `manifest` int32 [n, MARK_MANIFEST] (host: what the library checks a rewind against) and `envs`.  A mark goes back into the engine
+    and the envs it was taken from, and only while it is the envs' latest mark and they have not been reset, written or overwritten."""
+
+    def __init__(self, rows, manifest, envs, max_steps, whole):
+        self.rows, self.manifest, self.envs, self.max_steps, self.whole = rows, manifest, envs, int(max_steps), bool(whole)
+        self._pos = None
+
+    def __len__(self):
+        return int(self.envs.shape[0])
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.rows.numel())
+
+    def positions(self, envs):
+        """the rows of `envs` (an int32 array); ValueError for an env the mark does not hold"""
+        if self._pos is None:
+            self._pos = {int(e): k for k, e in enumerate(self.envs.tolist())}
+        try:
+            return np.asarray([self._pos[int(e)] for e in envs.tolist()], dtype=np.int64)
+        except KeyError as ex:
+            raise ValueError(f"rewind: env {ex.args[0]} is not one of the mark's envs") from None
+
+
 def dc_params_struct(p: dict) -> L.SdcDcParams:
     """dict (see dc_config.size_datacenter) -> C struct."""
     s = L.SdcDcParams()
@@ -415,6 +442,10 @@ class SdcEngine:
             return np.zeros((N, self.lw), dtype=np.float64)
         if name == "qtab":
             return np.zeros((N, self.queue_stride, 2), dtype=np.uint32)
+        if name == "qcum_t":        # (get_state only: the slot-major mirrors, where the batch has them)
+            return np.zeros((self.queue_stride, N), dtype=np.uint32)
+        if name == "hist_t":
+            return np.zeros((self.config["hist_cap"], N), dtype=np.uint32)
         if name == "record":
             return np.zeros((N, 64), dtype=np.uint32)
         if name == "ep_return":
@@ -576,6 +607,108 @@ class SdcEngine:
         if self._pinned_stream_obj is not None:
             snap.rows.record_stream(self._pinned_stream_obj)
         return self.obs, self.share_obs
+
+    # ------------------------------------------------------------------ mark / rewind / lookahead
+    def mark(self, envs=None, max_steps: int = 16) -> EnvMark:
+        """Save what the next `max_steps` steps can change in envs (default: the whole batch) into a device buffer (sdc_mark_envs): one
+        launch ordered like a step, no device synchronisation, read-only on the engine.  `rewind(mark)` undoes up to max_steps steps
+        taken since -- inside one episode, into the same envs of this engine.  One live mark per env: a later mark of an env, its reset
+        (auto-reset included), set_state / load_state_dict, a clone or restore INTO it kill the mark.  ValueError for what the library
+        refuses: max_steps outside [1, MARK_MAX_STEPS], no env, an index out of range or repeated, no reset() yet."""
+        t = self.torch
+        K = int(max_steps)
+        rb = int(self.lib.sdc_mark_row_bytes(K))
+        if rb == 0:
+            raise ValueError(f"mark: max_steps = {K} outside [1, {L.MARK_MAX_STEPS}]")
+        whole = envs is None
+        if whole:
+            if getattr(self, "_all_envs", None) is None:
+                self._all_envs = np.arange(self.n_envs, dtype=np.int32)
+            e = self._all_envs
+        else:
+            e = _int_ids(envs, "mark: envs").reshape(-1)
+        n = int(e.shape[0])
+        manifest = np.empty((max(n, 1), L.MARK_MANIFEST), dtype=np.int32)
+        ip = C.POINTER(C.c_int32)
+        with t.cuda.device(self.device):
+            rows = t.empty((n, rb), dtype=t.uint8, device=self.device)
+            rc = self.lib.sdc_mark_envs(self._h, None if whole else e.ctypes.data_as(ip), n, K, C.c_void_p(rows.data_ptr()),
+                                        manifest.ctypes.data_as(ip), C.c_void_p(self.obs.data_ptr()),
+                                        C.c_void_p(self.share_obs.data_ptr()), self._stream())
+        self._refused(rc)
+        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse it before)
+            rows.record_stream(self._pinned_stream_obj)
+        return EnvMark(rows, manifest[:n], e, K, whole)
+
+    def rewind(self, mark: EnvMark, envs=None):
+        """Undo the steps taken since `mark` in its envs (default), or in a subset of them (sdc_rewind_envs): one launch ordered like a
+        step, no device synchronisation; the engine's obs / share_obs rows (and the closed loop's copy) follow.  A whole-batch rewind
+        of a lock-step batch stays on the kernel it was on; a rewind of some envs leaves the batch out of lock-step, as a masked reset
+        does.  The mark stays alive: it may be rewound to again.  ValueError, with the engine untouched, for a mark of another engine,
+        a dead mark (see `mark`), an env that is not in the mark, and more than max_steps steps taken since the mark -- after which
+        the mark is dead for good.  -> (obs, share_obs) views."""
+        t = self.torch
+        if not isinstance(mark, EnvMark):
+            raise ValueError("rewind: not an EnvMark")
+        if mark.rows.device != self.device:
+            raise ValueError(f"rewind: the mark's rows are on {mark.rows.device}, this engine runs on {self.device}")
+        ip = C.POINTER(C.c_int32)
+        with t.cuda.device(self.device):
+            if envs is None:
+                e, rows, m, whole = mark.envs, mark.rows, mark.manifest, mark.whole
+            else:       # some of the mark's envs: their rows gathered into a buffer of their own (row k belongs to envs[k])
+                e = np.ascontiguousarray(_int_ids(envs, "rewind: envs").reshape(-1))
+                pos = mark.positions(e)
+                rows = mark.rows[t.as_tensor(pos, device=self.device)].contiguous() if pos.size else mark.rows[:0]
+                m, whole = np.ascontiguousarray(mark.manifest[pos]), False
+            n = int(e.shape[0])
+            if n == 0:
+                raise ValueError("rewind: no env")
+            rc = self.lib.sdc_rewind_envs(self._h, None if whole else e.ctypes.data_as(ip), n, C.c_void_p(rows.data_ptr()),
+                                          m.ctypes.data_as(ip), C.c_void_p(self.obs.data_ptr()),
+                                          C.c_void_p(self.share_obs.data_ptr()), self._stream())
+        self._refused(rc)
+        if self._pinned_stream_obj is not None:
+            rows.record_stream(self._pinned_stream_obj)
+        return self.obs, self.share_obs
+
+    def lookahead(self, actions):
+        """Score M candidate action sequences of K steps from the current state and come back to it: `actions` int32 device tensor
+        [M, K, N, 3].  The batch is marked (max_steps = K); every candidate is rolled out (`rollout`), its rewards summed over the K
+        steps on the device in fp64, in step order, and the batch rewound.  -> returns [M, N, 3] float64 on the device; the engine --
+        state, output buffers, closed-loop copy -- is where it was, with one difference: a rewind clears the header's re-centring
+        stamps, so deferred re-centrings in flight at the call are dropped and re-requested by the steps that need them (window
+        placement and info[reserved] may differ from a run that never looked ahead; no other output does).  The rollouts ask for
+        the info rows although they are thrown away: without them the batch is not the specialised kernels' case (sdc_capi.hip
+        lockstep_case) and every candidate would run the general kernel.  ValueError for a K that would finish an episode:
+        K >= steps_to_episode_end() with auto_reset (the reset would kill the mark), K > steps_to_episode_end() without; and for
+        K > MARK_MAX_STEPS."""
+        t = self.torch
+        if not (isinstance(actions, t.Tensor) and actions.dtype == t.int32 and actions.is_cuda and actions.is_contiguous() and
+                actions.dim() == 4 and tuple(actions.shape[2:]) == (self.n_envs, 3) and actions.shape[0] >= 1 and actions.shape[1] >= 1):
+            raise ValueError("lookahead: actions must be a contiguous int32 CUDA tensor of shape (M, K, n_envs, 3)")
+        M, K = int(actions.shape[0]), int(actions.shape[1])
+        if K > L.MARK_MAX_STEPS:
+            raise ValueError(f"lookahead: K = {K} is more than a mark holds (MARK_MAX_STEPS = {L.MARK_MAX_STEPS})")
+        left = self.steps_to_episode_end()
+        if self.config["auto_reset"] and K >= left:
+            raise ValueError(f"lookahead: K = {K} steps would finish an episode ({left} steps left): the auto-reset kills the mark")
+        if K > left:
+            raise ValueError(f"lookahead: K = {K} steps would run past the end of an episode ({left} steps left)")
+        with t.cuda.device(self.device):
+            keep, keep_final = self.out_flat.clone(), self.final_obs.clone()     # (the last step's outputs: rollout overwrites them)
+            mk = self.mark(max_steps=K)
+            returns = t.empty((M, self.n_envs, L.N_AGENTS), dtype=t.float64, device=self.device)
+            for c in range(M):
+                rew = self.rollout(actions[c])[2]
+                acc = returns[c]
+                acc.copy_(rew[0])
+                for k in range(1, K):
+                    acc.add_(rew[k])      # (fp32 -> fp64 is exact; one addition per step, in step order)
+                self.rewind(mk)
+            self.out_flat.copy_(keep)
+            self.final_obs.copy_(keep_final)
+        return returns
 
     def profile(self, every: int = 1):
         """Per-kernel HIP-event timing on the launch stream (measurement only): every k-th step, 0 = off."""

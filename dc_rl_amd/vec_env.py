@@ -465,6 +465,27 @@ class SustainDCVecEnv(ShareVecEnv):
         self._const, self._cfg_id, self.months = const, cfg_id, months
         return self._out(self._sel_obs(obs)), self._out(self._share3(share, obs)), (self._avail if self.return_torch else self._avail_np)
 
+    def mark(self, envs=None, max_steps: int = 16):
+        """Save what the next `max_steps` steps can change in envs (default: all) -- SdcEngine.mark: ~2.3 KB per env for 16 steps against
+        a snapshot's ~146 KB.  Read-only: the run goes on as without it.  One live mark per env; a reset of the env (auto-reset
+        included), a clone or restore into it kill the mark."""
+        if self._need_reset:
+            raise ValueError("mark: call reset() first")
+        return self.engine.mark(envs, max_steps)
+
+    def rewind(self, mark, envs=None):
+        """Undo the steps taken since `mark` in its envs, or in a subset of them (SdcEngine.rewind).  Returns (obs, share_obs,
+        available_actions) for ALL envs in reset()'s layout.  Actions handed to step_async and not yet stepped are dropped (they were
+        chosen from observations that no longer stand).  The host's per-env entries (constant info entries, config, month) belong to
+        the episode and do not change inside it; an `infos` object of an earlier step keeps describing that step.  The device-side
+        logger accumulator (accumulate_logger_sums) is NOT rewound: it counts what was stepped, detours included.  ValueError for
+        what the engine refuses."""
+        if self._need_reset:
+            raise ValueError("rewind: call reset() first")
+        obs, share = self.engine.rewind(mark, envs)
+        self._actions = None
+        return self._out(self._sel_obs(obs)), self._out(self._share3(share, obs)), (self._avail if self.return_torch else self._avail_np)
+
     def _take_state(self, src):
         """This env (built from src's constructor arguments, never stepped) becomes a copy of src: every env restored from a snapshot
         of src's, the seed and the host-side state copied.  src not reset yet: nothing to restore."""

@@ -216,7 +216,7 @@ const char* sdc_last_error(void);
  *   312  sdc_state_layout
  *   313  sdc_clone_envs
  *        (sdc_snapshot_row_bytes, sdc_snapshot_envs, sdc_restore_envs came later without a bump: new entry points, no layout or
- *        existing argument list changed) */
+ *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -318,7 +318,10 @@ const char* sdc_last_step_kernel(const sdc_handle* h);
  * qwin (uint32[N][64][4], the reward state's rank windows: per lane the keys of {Q1, Q3, upper bound, lower bound});
  * ep_return (double[N][3]);
  * hist (float[N][hist_stride], energy minus hist_ref, NaN = empty slot: every slot >= hist_len must be NaN);
- * t_win wb_win (double[N][weather_window_len]);  qtab (uint32[N][queue_stride][2]). */
+ * t_win wb_win (double[N][weather_window_len]);  qtab (uint32[N][queue_stride][2]).
+ * sdc_get_state only (diagnostics; refused where the batch has none, and by sdc_set_state always: they are derived from qtab / hist):
+ * qcum_t (uint32[queue_stride][N], the time-major mirror of qtab's cum column), hist_t (uint32[hist_cap][N], the slot-major mirror of the
+ * ring, raw keys). */
 int sdc_get_state(sdc_handle* h, const char* field, void* host_buf, size_t bytes);
 int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t bytes);
 /* a hash of the raw layouts a checkpoint holds (the record's and the header's dword offsets, the ring's stride): a checkpoint
@@ -391,6 +394,58 @@ int sdc_snapshot_envs(sdc_handle* h, const int32_t* envs, int n, void* rows, int
                       const float* share_obs, void* stream);
 int sdc_restore_envs(sdc_handle* h, const int32_t* rows_idx, const int32_t* envs, int n, const void* rows, int n_rows,
                      const int32_t* manifest, float* obs, float* share_obs, void* stream);
+
+/* MARK AND REWIND: undo up to max_steps env-steps of an env in place -- the inner loop of lookahead / MPC ("mark at t, roll out candidate
+ * A, rewind, roll out candidate B") at a fraction of a snapshot's cost.  A snapshot row is the env's complete state (~146 KB at
+ * 672-step episodes); a MARK ROW holds only what max_steps steps INSIDE ONE EPISODE can change: the state record, the header (episode
+ * returns included; its four deferred re-centring stamps stored as zeros), the four rank windows, the caller's obs [3][26] /
+ * share_obs [29] rows, the max_steps history-ring slots the next appends go to (from the record's hist_len / hist_pos on: consecutive
+ * slots, wrapping at hist_cap) and the max_steps queue-table entries from the env's episode step on (clipped at the table's end).
+ * Not in the row because no step writes it: the rest of the ring and of the queue table, the weather windows, the episode's feature
+ * rows, the per-env config scalars.  The mirrors of the queue table and the ring are derived: the rewind patches their rows of the
+ * same slots from the row.
+ * sdc_mark_row_bytes: roundup256(1964 + 12 * max_steps) -- 2 304 bytes for 16 steps, 2 816 for 64; 0 if max_steps is outside
+ * [1, SDC_MARK_MAX_STEPS].  SDC_MARK_MAX_STEPS is 256: 2.7 days of a 15-minute episode, far beyond any lookahead horizon, and it keeps a
+ * row (5 120 bytes) below 1/28 of a snapshot row.
+ * sdc_mark_envs: env envs[k] -> row k of rows [n][row_bytes] (caller-owned device buffer, 256-byte aligned); manifest
+ * [n][SDC_MARK_MANIFEST] (HOST int32) is filled at enqueue time.  envs == NULL: envs 0 .. n - 1 with n == n_envs (the whole batch: no
+ * index staging).  READ-ONLY on the engine, as a snapshot is: the live env keeps its stamps and the launch counter does not move; a run
+ * that takes marks is bit for bit the run without them.
+ * sdc_rewind_envs: row k goes back into env envs[k] -- the SAME slot of the SAME engine it was taken from: record, header (stamps
+ * cleared, as sdc_restore_envs and sdc_clone_envs do), rank windows, the ring slots and queue entries, the mirrors' rows of those where
+ * the engine has mirrors, the caller's obs / share_obs rows and the closed loop's copy of obs.  The launch counter does not move.  The
+ * host's mirror of the episode step follows the manifest: a whole-batch rewind of a lock-step batch stays on the kernel it was on, a
+ * rewind of some envs leaves the batch out of lock-step, as a masked reset does.
+ * ONE LIVE MARK PER ENV.  A row is only meaningful while everything it does not hold is unchanged; the library decides that from its
+ * host mirrors, before anything reaches the device.  It keeps a serial per env: sdc_mark_envs gives the env a new one (its older mark is
+ * dead from then on) and writes it to the manifest.  The serial is cleared -- every mark of the env dead -- by sdc_reset of the env
+ * (masked or not), its auto-reset, sdc_set_state, and being a dst of sdc_clone_envs or sdc_restore_envs; being a clone src or a
+ * snapshot source changes nothing.  A rewind leaves the mark alive: it may be repeated.  (Nested marks -- a stack per env for
+ * depth-first search -- are out of scope: snapshots serve that.)
+ * Both calls are ordered on `stream` like a step and do not synchronise the device; index arrays are staged as sdc_clone_envs stages its
+ * pairs.  obs [N][3][26] / share_obs [N][29]: the caller's device buffers (required).  Refused (-2 and a message naming the reason,
+ * nothing enqueued, all or nothing for the call): a null handle or array (other than envs), n <= 0, n > n_envs, envs == NULL with
+ * n != n_envs, an index out of range or repeated, no sdc_reset yet, rows not 256-byte aligned, max_steps out of range; a rewind
+ * additionally: a manifest of another state layout (sdc_state_layout) or engine, of another env than envs[k], a dead serial, an env
+ * whose episode step is below the mark's, or MORE THAN max_steps STEPS TAKEN SINCE THE MARK -- slots beyond the row's reach have been
+ * overwritten, so with that refusal the mark is dead for good.  This is the one side effect a refused call has: EVERY row of the call
+ * whose mark has been overrun dies with it, also where the refusal names another row. */
+#define SDC_MARK_MAX_STEPS 256
+#define SDC_MARK_MANIFEST 7
+enum sdc_mark_manifest {
+  SDC_MARK_M_LAYOUT = 0,   /* sdc_state_layout() */
+  SDC_MARK_M_ENGINE,       /* the engine's id (unique among the process's engines that have taken marks) */
+  SDC_MARK_M_STEPS,        /* max_steps */
+  SDC_MARK_M_ENV,          /* the env's index */
+  SDC_MARK_M_SERIAL,       /* the env's serial at this mark (never 0) */
+  SDC_MARK_M_T_REL,        /* the env's episode step at the mark */
+  SDC_MARK_M_HIST_CAP
+};
+size_t sdc_mark_row_bytes(int max_steps);
+int sdc_mark_envs(sdc_handle* h, const int32_t* envs, int n, int max_steps, void* rows, int32_t* manifest, const float* obs,
+                  const float* share_obs, void* stream);
+int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows, const int32_t* manifest, float* obs, float* share_obs,
+                    void* stream);
 
 /* Per-kernel timing (measurement only; off by default).  enable = k > 0 samples every k-th sdc_step, 0 switches it
  * off.  In a sampled step one lane per workgroup of each kernel stamps the device's constant-rate wall clock at
