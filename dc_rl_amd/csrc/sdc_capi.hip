@@ -88,6 +88,19 @@ struct Field {
   int in_hdr = 0;  // 0: the 256-byte state record, 1: the 256-byte header
 };
 
+// The index entries of a launch (which envs, which rows) staged through pinned host memory into a device buffer: two slots of [N]
+// entries of each, used in turn and allocated together on first use.  A slot's event marks the launch that last read it; a call waits
+// for it only before it overwrites that slot, i.e. for the call two back on the same stage (stage_acquire / stage_commit)
+struct IdxStage {
+  size_t entry_bytes;
+  unsigned char* dev = nullptr;           // [2][N]
+  unsigned char* pin = nullptr;           // [2][N]
+  hipEvent_t done[2] = {nullptr, nullptr};
+  bool in_flight[2] = {false, false};
+  bool ready = false;                     // all of the above or none
+  int slot = 0;                           // the slot the next call fills
+};
+
 }  // namespace
 
 struct sdc_handle {
@@ -146,24 +159,12 @@ struct sdc_handle {
   std::vector<unsigned char> prof_has_reset;
   double wall_clock_khz = 100000.0;
   double acc_ms[5] = {0, 0, 0, 0, 0};      // dynamics, reward, reset, steps, resets
-  // sdc_clone_envs: the (src, dst) pairs staged through pinned host memory into a device buffer -- two slots of each, used in turn
-  // (allocated together on the first clone: clone_ready).  A slot's event marks the launch that last read it; a clone waits for it
-  // only before it overwrites that slot, i.e. for the clone two calls back
-  int2* clone_pairs_dev = nullptr;        // [2][N]
-  int2* clone_pairs_pin = nullptr;        // [2][N]
-  hipEvent_t clone_done[2] = {nullptr, nullptr};
-  bool clone_in_flight[2] = {false, false};
-  bool clone_ready = false;
-  int clone_slot = 0;
-  // sdc_snapshot_envs / sdc_restore_envs: {env, row, cfg_id, loc_id} staged the same way (snap_ready: all or none allocated)
-  int4* snap_idx_dev = nullptr;           // [2][N]
-  int4* snap_idx_pin = nullptr;           // [2][N]
-  hipEvent_t snap_done[2] = {nullptr, nullptr};
-  bool snap_in_flight[2] = {false, false};
-  bool snap_ready = false;
-  int snap_slot = 0;
+  // two stages, so that a clone never waits for a snapshot two calls back or the other way round: sdc_clone_envs' {src, dst} pairs, and
+  // the {env, row, cfg_id, loc_id} of the snapshot / restore / mark / rewind calls
+  IdxStage clone_stage{sizeof(int2)};
+  IdxStage idx_stage{sizeof(int4)};
   // sdc_mark_envs / sdc_rewind_envs: ONE live mark per env -- the serial of the env's latest mark (0: none alive; sized by the first
-  // mark), cleared by whatever rewrites state a mark row does not hold (mark_kill); the index staging is the snapshot calls'
+  // mark), cleared by whatever rewrites state a mark row does not hold (mark_kill); the index staging is idx_stage
   std::vector<int> mark_serial;
   int mark_next_serial = 0;
   int mark_engine_id = 0;                 // this handle's id in the manifests it fills (given out by the first mark)
@@ -331,6 +332,13 @@ bool wide_gen_case(const sdc_handle* h, const int32_t* actions, const float* obs
          d.reward_method[0] == SDC_REWARD_DEFAULT;
 }
 
+// the largest rack count in use: what fast_case asks of a batch of several configs (every env has a config that is set: prm_env_ok, or
+// rebuild_prm_env on its way there)
+void refresh_racks_max(sdc_handle* h) {
+  h->racks_max = 0;
+  for (int e = 0; e < h->cfg.n_envs; e++) h->racks_max = std::max(h->racks_max, h->dc_host[(size_t)h->cfg_host[(size_t)e]].p.n_racks);
+}
+
 // several configs: (re)build every env's copy of its config's scalars once all configs and the assignment are known
 int rebuild_prm_env(sdc_handle* h) {
   h->prm_env_ok = false;
@@ -343,12 +351,8 @@ int rebuild_prm_env(sdc_handle* h) {
   constexpr size_t P_COUNT_HOST = (offsetof(SdcDcDev, ret_sum) - offsetof(SdcDcDev, p.m_cpu)) / sizeof(double) + 1;
   static_assert(P_COUNT_HOST <= 32, "prm_env rows are 32 doubles");
   std::vector<double> tab((size_t)N * 32, 0.0);
-  h->racks_max = 0;
-  for (int e = 0; e < N; e++) {
-    const SdcDcDev& c = h->dc_host[h->cfg_host[e]];
-    std::memcpy(&tab[(size_t)e * 32], &c.p.m_cpu, sizeof(double) * P_COUNT_HOST);
-    h->racks_max = std::max(h->racks_max, c.p.n_racks);
-  }
+  for (int e = 0; e < N; e++) std::memcpy(&tab[(size_t)e * 32], &h->dc_host[h->cfg_host[e]].p.m_cpu, sizeof(double) * P_COUNT_HOST);
+  refresh_racks_max(h);
   if (!h->prm_env_dev && dev_alloc(h, &h->prm_env_dev, (size_t)N * 32) != 0) return -1;
   HIP_TRY(hipMemcpy(h->prm_env_dev, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
   std::vector<double> per_cfg((size_t)C * 32, 0.0);      // (the same rows by config: what sdc_restore_envs copies from)
@@ -461,6 +465,179 @@ inline void mark_kill(sdc_handle* h, const int e) {
 }
 inline void mark_kill_all(sdc_handle* h) {
   if (!h->mark_serial.empty()) std::fill(h->mark_serial.begin(), h->mark_serial.end(), 0);
+}
+
+// env e has started a new episode (a reset, by the caller or inside a stepping call): whatever a reset invalidates goes here
+void new_episode(sdc_handle* h, const int e) {
+  h->host_t_rel[e] = 0;
+  note_features(h, e);
+  mark_kill(h, e);
+}
+
+// env e's state has been replaced as a whole (a clone or a restore into it): the host mirrors follow what it holds now -- episode step,
+// feature rows, config, trace set.  The caller folds pending steps in first (sync_mirror) and calls recompute_steps_to_terminal behind
+// its last env: rel_hint comes back if the batch is in lock-step afterwards
+void follow_env(sdc_handle* h, const size_t e, const int t_rel, const bool feat_ok, const int cfg, const int loc) {
+  h->host_t_rel[e] = t_rel;
+  mark_kill(h, (int)e);
+  if (h->feat_host[e] != (feat_ok ? 1 : 0)) {
+    h->n_feat_host += feat_ok ? 1 : -1;
+    h->feat_host[e] = feat_ok ? 1 : 0;
+  }
+  if (h->cfg_host.size() == h->host_t_rel.size()) h->cfg_host[e] = cfg;
+  if (h->loc_host.size() == h->host_t_rel.size()) h->loc_host[e] = loc;
+}
+
+// one single-step launch of the lane-per-env kernel (sdc_wide.hip), its common-case form or (`gen`) its general one
+void launch_wide(sdc_handle* h, SdcDev& d, const bool gen, const int rel, const int32_t* actions, float* obs, float* share_obs,
+                 unsigned char* done, float* info, float* final_obs, float* rew, hipStream_t st) {
+  d.sweep_blocks = wide_sweep_blocks(h);
+  h->last_step_kernel = gen ? "sdc_dynamics_wide_gen_kernel" : "sdc_dynamics_wide_kernel";
+  hipLaunchKernelGGL(gen ? sdc_dynamics_wide_gen_kernel : sdc_dynamics_wide_kernel, dim3(d.sweep_blocks + h->cfg.n_envs / SDC_WAVE),
+                     dim3(2 * SDC_WAVE), 0, st, d, rel, actions, obs, share_obs, done, info, final_obs, rew);
+}
+
+// What every stepping call does behind its launch(es) of n_steps steps; obs_last / share_obs_last (may be NULL) are the LAST step's
+// slices.  Episodes have a fixed length and every env advances one step per launched step, so the host knows from its mirror of the
+// step counters when an env has finished -- no device read-back.  With auto_reset the finished envs are reset inside the call
+// (harl/envs/env_wrappers.py:176-190): the last step's obs / share_obs receive the reset observation, final_obs keeps the pre-reset
+// one.  `timed`: the launch was a profiled sdc_step.  The closed loop's copy of the latest observations is taken in every case
+// (`latch_always`) or only after an auto-reset (sdc_rollout_actor: its kernel writes the copy itself)
+int finish_launch(sdc_handle* h, SdcDev& d, const int n_steps, float* obs_last, float* share_obs_last, hipStream_t st, const bool timed,
+                  const bool latch_always) {
+  HIP_TRY(hipGetLastError());
+  const int N = h->cfg.n_envs;
+  h->n_last_done = 0;
+  h->steps_to_terminal -= n_steps;
+  h->pending += n_steps;
+  if (h->rel_hint >= 0) h->rel_hint += n_steps;
+  bool was_reset = false;
+  if (h->steps_to_terminal == 0) {      // at least one env just finished
+    sync_mirror(h);
+    note_done(h);
+    if (h->cfg.auto_reset) {
+      d.reset_mask = nullptr;
+      if (timed) h->prof_has_reset[h->prof_used] = 1;
+      hipLaunchKernelGGL(sdc_reset_kernel, dim3(N), dim3(SDC_WAVE), 0, st, d, 0, h->ovr_day, h->ovr_hour, h->ovr_ci_min,
+                         h->ovr_ci_max, h->ovr_t_min, h->ovr_t_max, 1, obs_last, share_obs_last, nullptr, nullptr);
+      launch_features(h, d, st);
+      HIP_TRY(hipGetLastError());
+      for (int e = 0; e < N; e++)
+        if (h->host_t_rel[e] >= h->cfg.episode_steps) new_episode(h, e);
+      recompute_steps_to_terminal(h);
+      was_reset = true;
+    }
+  }
+  if (timed) h->prof_used += 1;
+  if (latch_always || was_reset) return latch_obs(h, obs_last, st) ? -1 : 0;
+  return 0;
+}
+
+// ---- the env-copy calls' plumbing (clone, snapshot / restore, mark / rewind) ----------------------------------------------------------
+// The pinned side of the slot this call fills.  Allocates on first use -- all staging resources or none: a failure part way leaves
+// `ready` false, and the next call starts over from what is set -- and waits for the call two back if it may still be reading the slot
+int stage_acquire(sdc_handle* h, IdxStage& S, void** pin) {
+  const size_t slot_bytes = S.entry_bytes * (size_t)h->cfg.n_envs;
+  if (!S.ready) {
+    if (!S.dev && dev_alloc(h, &S.dev, 2 * slot_bytes, false) != 0) return -1;
+    if (!S.pin) {
+      void* q = nullptr;
+      HIP_TRY(hipHostMalloc(&q, 2 * slot_bytes, hipHostMallocDefault));
+      S.pin = static_cast<unsigned char*>(q);
+    }
+    for (int i = 0; i < 2; i++)
+      if (!S.done[i]) {
+        hipEvent_t ev = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        S.done[i] = ev;
+      }
+    S.ready = true;
+  }
+  const int slot = S.slot;
+  S.slot ^= 1;
+  if (S.in_flight[slot]) {
+    HIP_TRY(hipEventSynchronize(S.done[slot]));
+    S.in_flight[slot] = false;
+  }
+  *pin = S.pin + (size_t)slot * slot_bytes;
+  return 0;
+}
+// ... and its first n entries on their way: copied to the device, read by launch(the device side of the slot) -> hipError_t, and the
+// slot in flight until that launch is done
+template <typename Launch>
+int stage_commit(sdc_handle* h, IdxStage& S, const size_t n, hipStream_t st, Launch launch) {
+  const int slot = S.slot ^ 1;      // (the slot stage_acquire has just handed out)
+  const size_t off = (size_t)slot * S.entry_bytes * (size_t)h->cfg.n_envs;
+  HIP_TRY(hipMemcpyAsync(S.dev + off, S.pin + off, S.entry_bytes * n, hipMemcpyHostToDevice, st));
+  HIP_TRY(launch(S.dev + off));
+  HIP_TRY(hipEventRecord(S.done[slot], st));
+  S.in_flight[slot] = true;
+  return 0;
+}
+// both, for entries the caller has built elsewhere
+template <typename Launch>
+int stage_send(sdc_handle* h, IdxStage& S, const void* entries, const size_t n, hipStream_t st, Launch launch) {
+  void* pin = nullptr;
+  if (stage_acquire(h, S, &pin)) return -1;
+  std::memcpy(pin, entries, S.entry_bytes * n);
+  return stage_commit(h, S, n, st, launch);
+}
+void stage_destroy(IdxStage& S) {
+  for (int i = 0; i < 2; i++) {
+    if (S.in_flight[i]) (void)hipEventSynchronize(S.done[i]);
+    if (S.done[i]) (void)hipEventDestroy(S.done[i]);
+  }
+  if (S.pin) (void)hipHostFree(S.pin);
+}
+
+// The inverse map of n entries (envs[k], vals ? vals[k] : k) -- map[env] = its value, -1 for the other envs -- or why the entries have
+// none ("" if they have), without the caller's prefix: an env outside [0, N); a value outside [0, n_vals) (n_vals > 0, `val_noun`:
+// checked entry by entry with the env); an env that appears twice (`twice`: the caller's noun for it).  map == nullptr: the ranges only
+std::string unique_index_map(const int32_t* envs, const int32_t* vals, const int n, const int N, const int n_vals, const char* val_noun,
+                             const char* twice, std::vector<int>* map) {
+  const auto outside = [](const char* noun, const int v, const int k, const int bound) {
+    return std::string(noun) + " " + std::to_string(v) + " (entry " + std::to_string(k) + ") outside [0, " + std::to_string(bound) + ")";
+  };
+  for (int k = 0; k < n; k++) {
+    if (envs[k] < 0 || envs[k] >= N) return outside("env", envs[k], k, N);
+    if (n_vals > 0 && (vals[k] < 0 || vals[k] >= n_vals)) return outside(val_noun, vals[k], k, n_vals);
+  }
+  if (!map) return "";
+  map->assign((size_t)N, -1);
+  for (int k = 0; k < n; k++) {
+    if ((*map)[(size_t)envs[k]] >= 0) return std::string(twice) + " " + std::to_string(envs[k]) + " appears twice";
+    (*map)[(size_t)envs[k]] = vals ? vals[k] : k;
+  }
+  return "";
+}
+// the caller's row buffer (snapshot rows, mark rows): nullptr if it may be used, else why not
+const char* rows_error(const void* rows) {
+  return (reinterpret_cast<uintptr_t>(rows) & 255u) != 0 ? "rows must be 256-byte aligned" : nullptr;
+}
+
+// One env-major array joins the segment table of a copy plan (SdcClonePlan, SdcSnapPlan: the same fields) as a wide segment (16-byte
+// units) or a narrow one (dwords).  Which, is the caller's rule:
+//   SEG_DEMOTE (the clone): wide if pitch AND base are 16-byte aligned, else narrow -- any array can be copied;
+//   SEG_BY_PITCH (the snapshot): by the pitch alone, because the row layout must not depend on a pointer; a wide array with a
+//     misaligned base is refused, and so is a base that is not dword-aligned.
+// -> false (and nothing added) if refused or the class's table is full
+enum SegPolicy { SEG_DEMOTE, SEG_BY_PITCH };
+template <typename Plan>
+bool seg_add(Plan& P, const SegPolicy policy, void* base, const size_t pitch) {
+  const uintptr_t b = reinterpret_cast<uintptr_t>(base);
+  const bool wide = pitch % 16 == 0 && (policy == SEG_BY_PITCH || (b & 15u) == 0);
+  if (policy == SEG_BY_PITCH && ((wide && (b & 15u) != 0) || (b & 3u) != 0)) return false;
+  constexpr int max_wide = (int)(sizeof(P.wide) / sizeof(P.wide[0])), max_narrow = (int)(sizeof(P.narrow) / sizeof(P.narrow[0]));
+  if (wide ? P.n_wide == max_wide : P.n_narrow == max_narrow) return false;
+  int& count = wide ? P.n_wide : P.n_narrow;
+  unsigned& units = wide ? P.wide_units : P.narrow_units;
+  SdcSeg& g = wide ? P.wide[count] : P.narrow[count];
+  g.base = static_cast<unsigned char*>(base);
+  g.pitch = (unsigned)pitch;
+  g.first = units;
+  count += 1;
+  units += (unsigned)(pitch / (wide ? 16 : 4));
+  return true;
 }
 
 }  // namespace
@@ -667,16 +844,8 @@ int sdc_create(const sdc_config* cfg, sdc_handle** out) {
 int sdc_destroy(sdc_handle* h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
-  for (int i = 0; i < 2; i++) {
-    if (h->clone_in_flight[i]) (void)hipEventSynchronize(h->clone_done[i]);
-    if (h->clone_done[i]) (void)hipEventDestroy(h->clone_done[i]);
-  }
-  if (h->clone_pairs_pin) (void)hipHostFree(h->clone_pairs_pin);
-  for (int i = 0; i < 2; i++) {
-    if (h->snap_in_flight[i]) (void)hipEventSynchronize(h->snap_done[i]);
-    if (h->snap_done[i]) (void)hipEventDestroy(h->snap_done[i]);
-  }
-  if (h->snap_idx_pin) (void)hipHostFree(h->snap_idx_pin);
+  stage_destroy(h->clone_stage);
+  stage_destroy(h->idx_stage);
   for (void* p : h->allocs) (void)hipFree(p);
   delete h;
   return 0;
@@ -922,11 +1091,7 @@ int sdc_reset(sdc_handle* h, const uint8_t* mask_host, const sdc_reset_override*
   if (mask_host) HIP_TRY(hipStreamSynchronize(st));  // mask staging buffer is reused by the next call
   sync_mirror(h);
   for (int e = 0; e < N; e++)
-    if (!mask_host || mask_host[e]) {
-      h->host_t_rel[e] = 0;
-      note_features(h, e);
-      mark_kill(h, e);
-    }
+    if (!mask_host || mask_host[e]) new_episode(h, e);
   recompute_steps_to_terminal(h);
   h->started = true;
   return 0;
@@ -951,16 +1116,10 @@ int sdc_step(sdc_handle* h, const int32_t* actions, float* obs, float* share_obs
   d.step_no = h->step_no;
   h->step_no = next_step_no(h->step_no, 1);
   if (fast_case(h, actions, share_obs, info, timed) && wide_case(h, obs, share_obs, info, final_obs)) {
-    d.sweep_blocks = wide_sweep_blocks(h);
-    h->last_step_kernel = "sdc_dynamics_wide_kernel";
-    hipLaunchKernelGGL(sdc_dynamics_wide_kernel, dim3(d.sweep_blocks + N / SDC_WAVE), dim3(2 * SDC_WAVE), 0, st, d, h->rel_hint, actions,
-                       obs, share_obs, done, info, final_obs, rew);
+    launch_wide(h, d, false, h->rel_hint, actions, obs, share_obs, done, info, final_obs, rew, st);
   } else if (wide_gen_case(h, actions, obs, share_obs, info, final_obs, timed)) {
     // a large batch of SEVERAL configs, or with rule-based policies / other reward functions: the lane-per-env kernel's general form
-    d.sweep_blocks = wide_sweep_blocks(h);
-    h->last_step_kernel = "sdc_dynamics_wide_gen_kernel";
-    hipLaunchKernelGGL(sdc_dynamics_wide_gen_kernel, dim3(d.sweep_blocks + N / SDC_WAVE), dim3(2 * SDC_WAVE), 0, st, d, h->rel_hint, actions,
-                       obs, share_obs, done, info, final_obs, rew);
+    launch_wide(h, d, true, h->rel_hint, actions, obs, share_obs, done, info, final_obs, rew, st);
   } else if (fast_case(h, actions, share_obs, info, timed) && quad_case(h, false)) {
     h->last_step_kernel = "sdc_dynamics_quad_kernel";
     hipLaunchKernelGGL(sdc_dynamics_quad_kernel, dim3(d.sweep_blocks + quad_blocks(N)), dim3(SDC_WAVE * STEP_WPB), 0, st, d,
@@ -975,36 +1134,7 @@ int sdc_step(sdc_handle* h, const int32_t* actions, float* obs, float* share_obs
                        actions, obs, share_obs, done, info, final_obs, rew);
   }
   if (h->cfg.debug_flags & 1) hipLaunchKernelGGL(sdc_reward_verify_kernel, dim3(N), dim3(SDC_BLOCK), 0, st, d, info);
-  HIP_TRY(hipGetLastError());
-  h->n_last_done = 0;
-  h->steps_to_terminal -= 1;
-  h->pending += 1;
-  if (h->rel_hint >= 0) h->rel_hint += 1;
-  if (h->steps_to_terminal == 0) {
-    // At least one env just finished.  Episodes have a fixed length and every env advances one step per
-    // launch, so the host knows this from its mirror of the step counters -- no device read-back.
-    sync_mirror(h);
-    note_done(h);
-    if (h->cfg.auto_reset) {
-      // harl/envs/env_wrappers.py:176-190: reset inside the same step call and return the reset obs
-      d.reset_mask = nullptr;
-      if (timed) h->prof_has_reset[h->prof_used] = 1;
-      hipLaunchKernelGGL(sdc_reset_kernel, dim3(N), dim3(SDC_WAVE), 0, st, d, 0, h->ovr_day, h->ovr_hour, h->ovr_ci_min,
-                         h->ovr_ci_max, h->ovr_t_min, h->ovr_t_max, 1, obs, share_obs, nullptr, nullptr);
-      launch_features(h, d, st);
-      HIP_TRY(hipGetLastError());
-      for (int e = 0; e < N; e++)
-        if (h->host_t_rel[e] >= h->cfg.episode_steps) {
-          h->host_t_rel[e] = 0;
-          note_features(h, e);
-          mark_kill(h, e);
-        }
-      recompute_steps_to_terminal(h);
-    }
-  }
-  if (timed) h->prof_used += 1;
-  if (latch_obs(h, obs, st)) return -1;
-  return 0;
+  return finish_launch(h, d, 1, obs, share_obs, st, timed, true);
 }
 
 int sdc_rollout(sdc_handle* h, int n_steps, const int32_t* actions, float* obs, float* share_obs, float* rew,
@@ -1035,22 +1165,14 @@ int sdc_rollout(sdc_handle* h, int n_steps, const int32_t* actions, float* obs, 
     // deferred re-centrings running between them as in sdc_step -- faster than one n_steps launch of four envs per wavefront
     // (16 384 envs: 17.7 against 23.4 us per step), the same outputs to the bit.  Its general form likewise: several configs,
     // rule-based policies (a step's policy reads the state the previous launch left), other reward functions.
-    d.sweep_blocks = wide_sweep_blocks(h);
-    h->last_step_kernel = w_common ? "sdc_dynamics_wide_kernel" : "sdc_dynamics_wide_gen_kernel";
     for (int k = 0; k < n_steps; k++) {
       d.step_no = h->step_no;
       h->step_no = next_step_no(h->step_no, 1);
       const size_t o = (size_t)k * N;
       d.actions_out = actions_out ? actions_out + o * 3 : nullptr;
       const int rel_k = h->rel_hint >= 0 ? h->rel_hint + k : h->rel_hint;
-      if (w_common)
-        hipLaunchKernelGGL(sdc_dynamics_wide_kernel, dim3(d.sweep_blocks + N / SDC_WAVE), dim3(2 * SDC_WAVE), 0, st, d, rel_k,
-                           actions + o * 3, obs + o * SDC_OBS_OUT, share_obs + o * SDC_SHARE_OBS_DIM, done + o,
-                           info + o * SDC_INFO_DIM, final_obs, rew + o * 3);
-      else
-        hipLaunchKernelGGL(sdc_dynamics_wide_gen_kernel, dim3(d.sweep_blocks + N / SDC_WAVE), dim3(2 * SDC_WAVE), 0, st, d, rel_k,
-                           actions ? actions + o * 3 : nullptr, obs + o * SDC_OBS_OUT, share_obs + o * SDC_SHARE_OBS_DIM, done + o,
-                           info + o * SDC_INFO_DIM, final_obs, rew + o * 3);
+      launch_wide(h, d, w_gen, rel_k, actions ? actions + o * 3 : nullptr, obs + o * SDC_OBS_OUT, share_obs + o * SDC_SHARE_OBS_DIM,
+                  done + o, info + o * SDC_INFO_DIM, final_obs, rew + o * 3, st);
     }
   } else {
     // (a multi-step launch has no spare wavefronts between its steps: it re-centres inline, and requests left by the
@@ -1059,47 +1181,14 @@ int sdc_rollout(sdc_handle* h, int n_steps, const int32_t* actions, float* obs, 
     d.step_no = h->step_no;
     h->step_no = next_step_no(h->step_no, n_steps + 3);
     HIP_TRY(hipMemsetAsync(d.rq_count, 0, sizeof(int) * 4, st));
-    const bool r_fast = fast_case(h, actions, share_obs, info, false) && !actions_out;
-    h->last_step_kernel = r_fast ? (quad_case(h, true) ? "sdc_rollout_quad_kernel" : "sdc_rollout_fast_kernel") : "sdc_rollout_kernel";
-    if (fast_case(h, actions, share_obs, info, false) && !actions_out && quad_case(h, true))
-      hipLaunchKernelGGL(sdc_rollout_quad_kernel, dim3(quad_blocks(N)), dim3(SDC_WAVE * STEP_WPB), 0, st, d, n_steps, h->rel_hint,
-                         actions, obs, share_obs, done, info, final_obs, rew);
-    else if (fast_case(h, actions, share_obs, info, false) && !actions_out)
-      hipLaunchKernelGGL(sdc_rollout_fast_kernel, dim3(step_blocks(N)), dim3(SDC_WAVE * STEP_WPB), 0, st, d, n_steps, h->rel_hint,
-                         actions, obs, share_obs, done, info, final_obs, rew);
-    else
-      hipLaunchKernelGGL(sdc_rollout_kernel, dim3(step_blocks(N)), dim3(SDC_WAVE * STEP_WPB), 0, st, d, n_steps, h->rel_hint, actions,
-                         obs, share_obs, done, info, final_obs, rew);
+    const bool r_fast = fast_case(h, actions, share_obs, info, false) && !actions_out, r_quad = r_fast && quad_case(h, true);
+    h->last_step_kernel = r_quad ? "sdc_rollout_quad_kernel" : r_fast ? "sdc_rollout_fast_kernel" : "sdc_rollout_kernel";
+    hipLaunchKernelGGL(r_quad ? sdc_rollout_quad_kernel : r_fast ? sdc_rollout_fast_kernel : sdc_rollout_kernel,
+                       dim3(r_quad ? quad_blocks(N) : step_blocks(N)), dim3(SDC_WAVE * STEP_WPB), 0, st, d, n_steps, h->rel_hint, actions, obs,
+                       share_obs, done, info, final_obs, rew);
   }
-  HIP_TRY(hipGetLastError());
-  h->n_last_done = 0;
-  h->steps_to_terminal -= n_steps;
-  h->pending += n_steps;
-  if (h->rel_hint >= 0) h->rel_hint += n_steps;
-  if (h->steps_to_terminal == 0) {
-    sync_mirror(h);
-    note_done(h);
-    if (h->cfg.auto_reset) {
-      // as in sdc_step: the finished envs are reset inside the call; the LAST step's obs / share_obs slices receive
-      // the reset observation, final_obs the pre-reset one
-      d.reset_mask = nullptr;
-      const size_t last = (size_t)(n_steps - 1) * N;
-      hipLaunchKernelGGL(sdc_reset_kernel, dim3(N), dim3(SDC_WAVE), 0, st, d, 0, h->ovr_day, h->ovr_hour, h->ovr_ci_min,
-                         h->ovr_ci_max, h->ovr_t_min, h->ovr_t_max, 1, obs + last * SDC_OBS_OUT,
-                         share_obs ? share_obs + last * SDC_SHARE_OBS_DIM : nullptr, nullptr, nullptr);
-      launch_features(h, d, st);
-      HIP_TRY(hipGetLastError());
-      for (int e = 0; e < N; e++)
-        if (h->host_t_rel[e] >= h->cfg.episode_steps) {
-          h->host_t_rel[e] = 0;
-          note_features(h, e);
-          mark_kill(h, e);
-        }
-      recompute_steps_to_terminal(h);
-    }
-  }
-  if (latch_obs(h, obs + (size_t)(n_steps - 1) * N * SDC_OBS_OUT, st)) return -1;
-  return 0;
+  const size_t last = (size_t)(n_steps - 1) * N;      // the LAST step's slices
+  return finish_launch(h, d, n_steps, obs + last * SDC_OBS_OUT, share_obs ? share_obs + last * SDC_SHARE_OBS_DIM : nullptr, st, false, true);
 }
 
 int sdc_set_actor(sdc_handle* h, int slot, const sdc_actor_params* p) {
@@ -1184,33 +1273,9 @@ int sdc_rollout_actor(sdc_handle* h, int n_steps, int sample, float* obs, float*
                        h->rel_hint, h->actor_dev, h->obs_latch, sample ? 1 : 0, obs, share_obs, done, info, final_obs, rew, actions_out,
                        logits_out, h->obs_latch);
   }
-  HIP_TRY(hipGetLastError());
-  h->n_last_done = 0;
-  h->steps_to_terminal -= n_steps;
-  h->pending += n_steps;
-  if (h->rel_hint >= 0) h->rel_hint += n_steps;
-  if (h->steps_to_terminal == 0) {
-    sync_mirror(h);
-    note_done(h);
-    if (h->cfg.auto_reset) {
-      d.reset_mask = nullptr;
-      const size_t last = (size_t)(n_steps - 1) * N;
-      hipLaunchKernelGGL(sdc_reset_kernel, dim3(N), dim3(SDC_WAVE), 0, st, d, 0, h->ovr_day, h->ovr_hour, h->ovr_ci_min,
-                         h->ovr_ci_max, h->ovr_t_min, h->ovr_t_max, 1, obs + last * SDC_OBS_OUT,
-                         share_obs + last * SDC_SHARE_OBS_DIM, nullptr, nullptr);
-      launch_features(h, d, st);
-      HIP_TRY(hipGetLastError());
-      for (int e = 0; e < N; e++)
-        if (h->host_t_rel[e] >= h->cfg.episode_steps) {
-          h->host_t_rel[e] = 0;
-          note_features(h, e);
-          mark_kill(h, e);
-        }
-      recompute_steps_to_terminal(h);
-      if (latch_obs(h, obs + last * SDC_OBS_OUT, st)) return -1;     // the next launch starts from the reset observations
-    }
-  }
-  return 0;
+  // (after an auto-reset alone: the next launch starts from the reset observations)
+  const size_t last = (size_t)(n_steps - 1) * N;
+  return finish_launch(h, d, n_steps, obs + last * SDC_OBS_OUT, share_obs + last * SDC_SHARE_OBS_DIM, st, false, false);
 }
 
 int sdc_steps_to_episode_end(const sdc_handle* h) { return h ? h->steps_to_terminal : -1; }
@@ -1406,11 +1471,9 @@ int sdc_clone_envs(sdc_handle* h, const int32_t* src, const int32_t* dst, int n,
     if (src[k] < 0 || src[k] >= N || dst[k] < 0 || dst[k] >= N)
       return fail_msg("sdc_clone_envs: pair " + std::to_string(k) + " (" + std::to_string(src[k]) + " -> " + std::to_string(dst[k]) +
                       ") has an env index outside [0, " + std::to_string(N) + ")");
-  std::vector<int> src_of((size_t)N, -1);      // dst -> its src
-  for (int k = 0; k < n; k++) {
-    if (src_of[(size_t)dst[k]] >= 0) return fail_msg("sdc_clone_envs: dst " + std::to_string(dst[k]) + " appears twice");
-    src_of[(size_t)dst[k]] = src[k];
-  }
+  std::vector<int> src_of;      // dst -> its src
+  const std::string why = unique_index_map(dst, src, n, N, 0, nullptr, "dst", &src_of);
+  if (!why.empty()) return fail_msg("sdc_clone_envs: " + why);
   for (int k = 0; k < n; k++)
     if (src_of[(size_t)src[k]] >= 0) return fail_msg("sdc_clone_envs: env " + std::to_string(src[k]) + " is both a src and a dst");
   HIP_TRY(hipSetDevice(h->device));
@@ -1420,32 +1483,18 @@ int sdc_clone_envs(sdc_handle* h, const int32_t* src, const int32_t* dst, int n,
   std::memset(&P, 0, sizeof(P));
   P.n = n;
   P.n_envs = N;
-  bool fits = true;
-  const auto add = [&P, &fits](void* base, size_t pitch, int is_hdr) {
-    const bool wide = pitch % 16 == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0;
-    if (wide ? P.n_wide == SDC_CLONE_MAX_WIDE : P.n_narrow == SDC_CLONE_MAX_NARROW) {
-      fits = false;
-      return;
-    }
-    if (is_hdr) P.hdr_wide = wide ? P.n_wide : -1;
-    SdcCloneSeg& g = wide ? P.wide[P.n_wide++] : P.narrow[P.n_narrow++];
-    g.base = static_cast<unsigned char*>(base);
-    g.pitch = (unsigned)pitch;
-    g.first = wide ? P.wide_units : P.narrow_units;
-    (wide ? P.wide_units : P.narrow_units) += (unsigned)(pitch / (wide ? 16 : 4));
-  };
-  add(d.rec, sizeof(unsigned) * SDC_REC_DWORDS, 0);
-  add(d.hdr, sizeof(unsigned) * SDC_HDR_DWORDS, 1);
-  add(d.hist, sizeof(unsigned) * SDC_HIST_STRIDE, 0);
-  add(d.qwin, sizeof(unsigned) * 4 * SDC_WIN, 0);
-  add(d.qtab, sizeof(uint2) * (size_t)d.qstride, 0);
-  add(d.t_win, sizeof(double) * (size_t)d.lw, 0);
-  add(d.wb_win, sizeof(double) * (size_t)d.lw, 0);
-  if (d.prm_env) add(const_cast<double*>(d.prm_env), sizeof(double) * 32, 0);
-  if (h->obs_latch) add(h->obs_latch, sizeof(float) * SDC_OBS_OUT, 0);
-  if (obs) add(obs, sizeof(float) * SDC_OBS_OUT, 0);
-  if (share_obs) add(share_obs, sizeof(float) * SDC_SHARE_OBS_DIM, 0);
-  if (!fits || P.hdr_wide < 0) return fail_msg("sdc_clone_envs: internal: the copy plan's segment table is too small");
+  const auto add = [&P](void* base, size_t pitch) { return seg_add(P, SEG_DEMOTE, base, pitch); };
+  bool fits = add(d.rec, sizeof(unsigned) * SDC_REC_DWORDS);
+  P.hdr_wide = P.n_wide;      // (the next wide segment, if the header becomes one)
+  fits = fits && add(d.hdr, sizeof(unsigned) * SDC_HDR_DWORDS) && P.n_wide > P.hdr_wide &&
+              add(d.hist, sizeof(unsigned) * SDC_HIST_STRIDE) && add(d.qwin, sizeof(unsigned) * 4 * SDC_WIN) &&
+              add(d.qtab, sizeof(uint2) * (size_t)d.qstride) && add(d.t_win, sizeof(double) * (size_t)d.lw) &&
+              add(d.wb_win, sizeof(double) * (size_t)d.lw);
+  if (d.prm_env) fits = fits && add(const_cast<double*>(d.prm_env), sizeof(double) * 32);
+  if (h->obs_latch) fits = fits && add(h->obs_latch, sizeof(float) * SDC_OBS_OUT);
+  if (obs) fits = fits && add(obs, sizeof(float) * SDC_OBS_OUT);
+  if (share_obs) fits = fits && add(share_obs, sizeof(float) * SDC_SHARE_OBS_DIM);
+  if (!fits) return fail_msg("sdc_clone_envs: internal: the copy plan's segment table is too small");
   constexpr int per_block = SDC_CLONE_BLOCK * SDC_CLONE_UNROLL;
   P.bpp = std::max(1, (int)((P.wide_units + per_block - 1) / per_block));
   P.blocks_a = n * P.bpp;
@@ -1460,58 +1509,27 @@ int sdc_clone_envs(sdc_handle* h, const int32_t* src, const int32_t* dst, int n,
     P.mirror_rows = d.qstride + (d.hist_t ? d.hist_cap : 0);
     P.mirror_pair_groups = (n + SDC_CLONE_BLOCK - 1) / SDC_CLONE_BLOCK;
   }
-  if (!h->clone_ready) {
-    // all staging resources or none: a failure part way leaves clone_ready false, and the next call starts over from what is set
-    if (!h->clone_pairs_dev && dev_alloc(h, &h->clone_pairs_dev, 2 * (size_t)N, false) != 0) return -1;
-    if (!h->clone_pairs_pin) {
-      void* q = nullptr;
-      HIP_TRY(hipHostMalloc(&q, sizeof(int2) * 2 * (size_t)N, hipHostMallocDefault));
-      h->clone_pairs_pin = static_cast<int2*>(q);
-    }
-    for (int i = 0; i < 2; i++)
-      if (!h->clone_done[i]) {
-        hipEvent_t ev = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        h->clone_done[i] = ev;
-      }
-    h->clone_ready = true;
-  }
-  const int slot = h->clone_slot;
-  h->clone_slot ^= 1;
-  if (h->clone_in_flight[slot]) {      // (the clone two calls back may still be reading this slot)
-    HIP_TRY(hipEventSynchronize(h->clone_done[slot]));
-    h->clone_in_flight[slot] = false;
-  }
-  int2* pin = h->clone_pairs_pin + (size_t)slot * N;
-  int2* pairs_dev = h->clone_pairs_dev + (size_t)slot * N;
+  void* pin_slot = nullptr;
+  if (stage_acquire(h, h->clone_stage, &pin_slot)) return -1;
+  int2* pin = static_cast<int2*>(pin_slot);
   // the pairs sorted by dst: range C's lanes then write consecutive mirror dwords for a contiguous dst range
   int m = 0;
   for (int e = 0; e < N; e++)
     if (src_of[(size_t)e] >= 0) pin[m++] = make_int2(src_of[(size_t)e], e);
-  HIP_TRY(hipMemcpyAsync(pairs_dev, pin, sizeof(int2) * (size_t)n, hipMemcpyHostToDevice, st));
-  P.pairs = pairs_dev;
-  HIP_TRY(sdc_clone_launch(P, st));
-  HIP_TRY(hipEventRecord(h->clone_done[slot], st));
-  h->clone_in_flight[slot] = true;
+  if (stage_commit(h, h->clone_stage, (size_t)n, st, [&P, st](const void* pairs_dev) {
+        P.pairs = static_cast<const int2*>(pairs_dev);
+        return sdc_clone_launch(P, st);
+      }))
+    return -1;
 
-  // the host mirrors follow: episode step, feature rows, config; rel_hint comes back if the batch is in lock-step afterwards
+  // the host mirrors follow src's
   sync_mirror(h);
-  const bool cfgs = (int)h->cfg_host.size() == N;
+  const bool cfgs = (int)h->cfg_host.size() == N, locs = (int)h->loc_host.size() == N;
   for (int k = 0; k < n; k++) {
-    const int s = src[k], t = dst[k];
-    h->host_t_rel[(size_t)t] = h->host_t_rel[(size_t)s];
-    mark_kill(h, t);
-    if (h->feat_host[(size_t)t] != h->feat_host[(size_t)s]) {
-      h->n_feat_host += h->feat_host[(size_t)s] ? 1 : -1;
-      h->feat_host[(size_t)t] = h->feat_host[(size_t)s];
-    }
-    if (cfgs) h->cfg_host[(size_t)t] = h->cfg_host[(size_t)s];
-    if ((int)h->loc_host.size() == N) h->loc_host[(size_t)t] = h->loc_host[(size_t)s];
+    const size_t s = (size_t)src[k];
+    follow_env(h, (size_t)dst[k], h->host_t_rel[s], h->feat_host[s] != 0, cfgs ? h->cfg_host[s] : 0, locs ? h->loc_host[s] : 0);
   }
-  if (cfgs && h->prm_env_ok) {       // (the largest rack count in use: what fast_case asks of a batch of several configs)
-    h->racks_max = 0;
-    for (int e = 0; e < N; e++) h->racks_max = std::max(h->racks_max, h->dc_host[(size_t)h->cfg_host[(size_t)e]].p.n_racks);
-  }
+  if (h->prm_env_ok) refresh_racks_max(h);
   recompute_steps_to_terminal(h);
   return 0;
 }
@@ -1527,29 +1545,18 @@ static bool snap_plan(const sdc_handle* h, SdcSnapPlan& P, size_t& row_bytes, fl
   std::memset(&P, 0, sizeof(P));
   P.n_envs = h->cfg.n_envs;
   bool fits = true;
-  const auto add = [&P, &fits](void* base, size_t pitch) -> unsigned {
-    const bool wide = pitch % 16 == 0;
-    if ((wide ? P.n_wide == SDC_SNAP_MAX_WIDE : P.n_narrow == SDC_SNAP_MAX_NARROW) ||
-        (wide && (reinterpret_cast<uintptr_t>(base) & 15u) != 0) || (reinterpret_cast<uintptr_t>(base) & 3u) != 0) {
-      fits = false;
-      return 0;
-    }
-    SdcSnapSeg& g = wide ? P.wide[P.n_wide++] : P.narrow[P.n_narrow++];
-    g.base = static_cast<unsigned char*>(base);
-    g.pitch = (unsigned)pitch;
-    g.first = wide ? P.wide_units : P.narrow_units;
-    (wide ? P.wide_units : P.narrow_units) += (unsigned)(pitch / (wide ? 16 : 4));
-    return g.first;
-  };
+  const auto add = [&P, &fits](void* base, size_t pitch) { fits = seg_add(P, SEG_BY_PITCH, base, pitch) && fits; };
   add(d.rec, sizeof(unsigned) * SDC_REC_DWORDS);                 // wide segment SDC_SNAP_SEG_REC
   add(d.hdr, sizeof(unsigned) * SDC_HDR_DWORDS);                 // wide segment SDC_SNAP_SEG_HDR
   add(d.qwin, sizeof(unsigned) * 4 * SDC_WIN);
-  const unsigned q_first = add(d.qtab, sizeof(uint2) * (size_t)d.qstride);
+  const unsigned q_first = P.wide_units;      // (wide: qstride % 64 == 0 below)
+  add(d.qtab, sizeof(uint2) * (size_t)d.qstride);
   add(obs, sizeof(float) * SDC_OBS_OUT);                         // narrow segment SDC_SNAP_SEG_OBS
   add(share_obs, sizeof(float) * SDC_SHARE_OBS_DIM);
   add(d.t_win, sizeof(double) * (size_t)d.lw);
   add(d.wb_win, sizeof(double) * (size_t)d.lw);
-  const unsigned h_first = add(d.hist, sizeof(unsigned) * SDC_HIST_STRIDE);
+  const unsigned h_first = P.wide_units;
+  add(d.hist, sizeof(unsigned) * SDC_HIST_STRIDE);
   static_assert(sizeof(unsigned) * SDC_REC_DWORDS % 16 == 0 && sizeof(unsigned) * SDC_HDR_DWORDS % 16 == 0 &&
                 sizeof(float) * SDC_OBS_OUT % 16 != 0 && sizeof(float) * SDC_SHARE_OBS_DIM % 16 != 0,
                 "record and header wide, the observation rows narrow: the segment indices the kernels name");
@@ -1580,45 +1587,12 @@ static void snap_grid(SdcSnapPlan& P, const int n) {
   }
 }
 
-// the launch's {env, row, cfg_id, loc_id} through pinned host memory into a device buffer -- two slots used in turn, as sdc_clone_envs
-// stages its pairs: a call waits only for the launch two calls back, and only if that one has not finished
-static int snap_stage(sdc_handle* h, const std::vector<int4>& ix, hipStream_t st, int* slot_out) {
-  const int N = h->cfg.n_envs;
-  if (!h->snap_ready) {
-    // all staging resources or none: a failure part way leaves snap_ready false, and the next call starts over from what is set
-    if (!h->snap_idx_dev && dev_alloc(h, &h->snap_idx_dev, 2 * (size_t)N, false) != 0) return -1;
-    if (!h->snap_idx_pin) {
-      void* q = nullptr;
-      HIP_TRY(hipHostMalloc(&q, sizeof(int4) * 2 * (size_t)N, hipHostMallocDefault));
-      h->snap_idx_pin = static_cast<int4*>(q);
-    }
-    for (int i = 0; i < 2; i++)
-      if (!h->snap_done[i]) {
-        hipEvent_t ev = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        h->snap_done[i] = ev;
-      }
-    h->snap_ready = true;
-  }
-  const int slot = h->snap_slot;
-  h->snap_slot ^= 1;
-  if (h->snap_in_flight[slot]) {      // (the call two back may still be reading this slot)
-    HIP_TRY(hipEventSynchronize(h->snap_done[slot]));
-    h->snap_in_flight[slot] = false;
-  }
-  int4* pin = h->snap_idx_pin + (size_t)slot * N;
-  std::memcpy(pin, ix.data(), sizeof(int4) * ix.size());
-  HIP_TRY(hipMemcpyAsync(h->snap_idx_dev + (size_t)slot * N, pin, sizeof(int4) * ix.size(), hipMemcpyHostToDevice, st));
-  *slot_out = slot;
-  return 0;
-}
-
-static int snap_launch(sdc_handle* h, SdcSnapPlan& P, const bool save, const int slot, hipStream_t st) {
-  P.idx = h->snap_idx_dev + (size_t)slot * h->cfg.n_envs;
-  HIP_TRY(sdc_snapshot_launch(P, save, st));
-  HIP_TRY(hipEventRecord(h->snap_done[slot], st));
-  h->snap_in_flight[slot] = true;
-  return 0;
+// the launch's {env, row, cfg_id, loc_id} through the handle's idx_stage, and the launch
+static int snap_launch(sdc_handle* h, SdcSnapPlan& P, const bool save, const std::vector<int4>& ix, hipStream_t st) {
+  return stage_send(h, h->idx_stage, ix.data(), ix.size(), st, [&P, save, st](const void* idx_dev) {
+    P.idx = static_cast<const int4*>(idx_dev);
+    return sdc_snapshot_launch(P, save, st);
+  });
 }
 
 // why a manifest row cannot be restored into this engine ("" if it can)
@@ -1658,11 +1632,9 @@ int sdc_snapshot_envs(sdc_handle* h, const int32_t* envs, int n, void* rows, int
   if (!h->started) return fail_msg("sdc_snapshot_envs: sdc_reset must be called first");
   const int N = h->cfg.n_envs;
   if (n > N) return fail_msg("sdc_snapshot_envs: n = " + std::to_string(n) + " is more than the batch's " + std::to_string(N) + " envs");
-  for (int k = 0; k < n; k++)
-    if (envs[k] < 0 || envs[k] >= N)
-      return fail_msg("sdc_snapshot_envs: env " + std::to_string(envs[k]) + " (entry " + std::to_string(k) + ") outside [0, " +
-                      std::to_string(N) + ")");
-  if ((reinterpret_cast<uintptr_t>(rows) & 255u) != 0) return fail_msg("sdc_snapshot_envs: rows must be 256-byte aligned");
+  const std::string why = unique_index_map(envs, nullptr, n, N, 0, nullptr, nullptr, nullptr);      // (an env may appear twice)
+  if (!why.empty()) return fail_msg("sdc_snapshot_envs: " + why);
+  if (const char* w = rows_error(rows)) return fail_msg(std::string("sdc_snapshot_envs: ") + w);
   SdcSnapPlan P;
   size_t row_bytes = 0;
   if (!snap_plan(h, P, row_bytes, const_cast<float*>(obs), const_cast<float*>(share_obs)))
@@ -1689,9 +1661,7 @@ int sdc_snapshot_envs(sdc_handle* h, const int32_t* envs, int n, void* rows, int
   }
   P.rows = static_cast<unsigned char*>(rows);
   snap_grid(P, n);
-  int slot = 0;
-  if (snap_stage(h, ix, st, &slot)) return -1;
-  return snap_launch(h, P, true, slot, st);
+  return snap_launch(h, P, true, ix, st);
 }
 
 // Env envs[k] becomes snapshot row rows_idx[k] (sdc_snapshot.hip), ordered on `stream` like a step; the host mirrors follow the
@@ -1705,24 +1675,14 @@ int sdc_restore_envs(sdc_handle* h, const int32_t* rows_idx, const int32_t* envs
   if (!h->started) return fail_msg("sdc_restore_envs: sdc_reset must be called first");
   const int N = h->cfg.n_envs;
   // every refusal before anything reaches the device
-  for (int k = 0; k < n; k++) {
-    if (envs[k] < 0 || envs[k] >= N)
-      return fail_msg("sdc_restore_envs: env " + std::to_string(envs[k]) + " (entry " + std::to_string(k) + ") outside [0, " +
-                      std::to_string(N) + ")");
-    if (rows_idx[k] < 0 || rows_idx[k] >= n_rows)
-      return fail_msg("sdc_restore_envs: row " + std::to_string(rows_idx[k]) + " (entry " + std::to_string(k) + ") outside [0, " +
-                      std::to_string(n_rows) + ")");
-  }
-  std::vector<int> row_of((size_t)N, -1);      // dst -> its row
-  for (int k = 0; k < n; k++) {
-    if (row_of[(size_t)envs[k]] >= 0) return fail_msg("sdc_restore_envs: dst " + std::to_string(envs[k]) + " appears twice");
-    row_of[(size_t)envs[k]] = rows_idx[k];
-  }
+  std::vector<int> row_of;      // dst -> its row
+  const std::string bad = unique_index_map(envs, rows_idx, n, N, n_rows, "row", "dst", &row_of);
+  if (!bad.empty()) return fail_msg("sdc_restore_envs: " + bad);
   for (int k = 0; k < n; k++) {
     const std::string why = snap_manifest_error(h, manifest + (size_t)rows_idx[k] * SDC_SNAPSHOT_MANIFEST);
     if (!why.empty()) return fail_msg("sdc_restore_envs: row " + std::to_string(rows_idx[k]) + ": " + why);
   }
-  if ((reinterpret_cast<uintptr_t>(rows) & 255u) != 0) return fail_msg("sdc_restore_envs: rows must be 256-byte aligned");
+  if (const char* w = rows_error(rows)) return fail_msg(std::string("sdc_restore_envs: ") + w);
   SdcSnapPlan P;
   size_t row_bytes = 0;
   if (!snap_plan(h, P, row_bytes, obs, share_obs))
@@ -1758,31 +1718,15 @@ int sdc_restore_envs(sdc_handle* h, const int32_t* rows_idx, const int32_t* envs
       const int32_t* m = manifest + (size_t)row_of[(size_t)e] * SDC_SNAPSHOT_MANIFEST;
       ix.push_back(make_int4(e, row_of[(size_t)e], m[SDC_SNAP_CFG_ID], m[SDC_SNAP_LOC_ID]));
     }
-  int slot = 0;
-  if (snap_stage(h, ix, st, &slot)) return -1;
-  if (snap_launch(h, P, false, slot, st)) return -1;
+  if (snap_launch(h, P, false, ix, st)) return -1;
 
-  // the host mirrors follow the manifest: episode step, feature rows, config, trace set; rel_hint comes back if the batch is in
-  // lock-step afterwards
+  // the host mirrors follow the manifest
   sync_mirror(h);
-  const bool cfgs = (int)h->cfg_host.size() == N, locs = (int)h->loc_host.size() == N;
   for (const int4& x : ix) {
     const int32_t* m = manifest + (size_t)x.y * SDC_SNAPSHOT_MANIFEST;
-    const size_t e = (size_t)x.x;
-    h->host_t_rel[e] = m[SDC_SNAP_T_REL];
-    mark_kill(h, x.x);
-    const unsigned char f = (d.feat && m[SDC_SNAP_FEAT_OK]) ? 1 : 0;
-    if (h->feat_host[e] != f) {
-      h->n_feat_host += f ? 1 : -1;
-      h->feat_host[e] = f;
-    }
-    if (cfgs) h->cfg_host[e] = m[SDC_SNAP_CFG_ID];
-    if (locs) h->loc_host[e] = m[SDC_SNAP_LOC_ID];
+    follow_env(h, (size_t)x.x, m[SDC_SNAP_T_REL], d.feat && m[SDC_SNAP_FEAT_OK], m[SDC_SNAP_CFG_ID], m[SDC_SNAP_LOC_ID]);
   }
-  if (cfgs && h->prm_env_ok) {       // (the largest rack count in use: what fast_case asks of a batch of several configs)
-    h->racks_max = 0;
-    for (int e = 0; e < N; e++) h->racks_max = std::max(h->racks_max, h->dc_host[(size_t)h->cfg_host[(size_t)e]].p.n_racks);
-  }
+  if (h->prm_env_ok) refresh_racks_max(h);
   recompute_steps_to_terminal(h);
   return 0;
 }
@@ -1827,16 +1771,16 @@ static std::string mark_args_error(const sdc_handle* h, const int32_t* envs, con
   const int N = h->cfg.n_envs;
   if (n > N) return "n = " + std::to_string(n) + " is more than the batch's " + std::to_string(N) + " envs";
   if (!envs && n != N) return "envs == NULL means the whole batch: n must be " + std::to_string(N) + ", not " + std::to_string(n);
-  if (envs)
-    for (int k = 0; k < n; k++)
-      if (envs[k] < 0 || envs[k] >= N)
-        return "env " + std::to_string(envs[k]) + " (entry " + std::to_string(k) + ") outside [0, " + std::to_string(N) + ")";
-  if ((reinterpret_cast<uintptr_t>(rows) & 255u) != 0) return "rows must be 256-byte aligned";
+  if (envs) {
+    const std::string why = unique_index_map(envs, nullptr, n, N, 0, nullptr, nullptr, nullptr);
+    if (!why.empty()) return why;
+  }
+  if (const char* w = rows_error(rows)) return w;
   return "";
 }
 
-// the launch's {env, row} pairs (sorted by env: range M's lanes are then consecutive envs) through the snapshot calls' staging slots;
-// envs == NULL: nothing to stage.  row_of: env -> its row, -1 for the others
+// the launch's {env, row} pairs (sorted by env: range M's lanes are then consecutive envs) through the handle's idx_stage, and the
+// launch; `whole` (envs == NULL): nothing to stage.  row_of: env -> its row, -1 for the others
 static int mark_launch(sdc_handle* h, SdcMarkPlan& P, const bool save, const std::vector<int>& row_of, const bool whole,
                        hipStream_t st) {
   if (whole) {
@@ -1847,13 +1791,10 @@ static int mark_launch(sdc_handle* h, SdcMarkPlan& P, const bool save, const std
   ix.reserve((size_t)P.n);
   for (int e = 0; e < P.n_envs; e++)
     if (row_of[(size_t)e] >= 0) ix.push_back(make_int4(e, row_of[(size_t)e], 0, 0));
-  int slot = 0;
-  if (snap_stage(h, ix, st, &slot)) return -1;
-  P.idx = h->snap_idx_dev + (size_t)slot * h->cfg.n_envs;
-  HIP_TRY(sdc_mark_launch(P, save, st));
-  HIP_TRY(hipEventRecord(h->snap_done[slot], st));
-  h->snap_in_flight[slot] = true;
-  return 0;
+  return stage_send(h, h->idx_stage, ix.data(), ix.size(), st, [&P, save, st](const void* idx_dev) {
+    P.idx = static_cast<const int4*>(idx_dev);
+    return sdc_mark_launch(P, save, st);
+  });
 }
 
 // What the next max_steps steps can change in env envs[k] -> mark row k, ordered on `stream` like a step, read-only on the engine.  The
@@ -1868,11 +1809,8 @@ int sdc_mark_envs(sdc_handle* h, const int32_t* envs, int n, int max_steps, void
   const int N = h->cfg.n_envs;
   std::vector<int> row_of;
   if (envs) {
-    row_of.assign((size_t)N, -1);
-    for (int k = 0; k < n; k++) {
-      if (row_of[(size_t)envs[k]] >= 0) return fail_msg("sdc_mark_envs: env " + std::to_string(envs[k]) + " appears twice");
-      row_of[(size_t)envs[k]] = k;
-    }
+    const std::string twice = unique_index_map(envs, nullptr, n, N, 0, nullptr, "env", &row_of);
+    if (!twice.empty()) return fail_msg("sdc_mark_envs: " + twice);
   }
   SdcMarkPlan P;
   if (!mark_plan(h, P, n, max_steps, rows, obs, share_obs)) return fail_msg("sdc_mark_envs: obs / share_obs rows not dword-aligned");
@@ -1972,7 +1910,8 @@ int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows,
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (mark_launch(h, P, false, row_of, envs == nullptr, st)) return -1;
-  // the host mirrors follow the manifest: the episode step (feature rows, config and trace set are the episode's: unchanged)
+  // the host mirrors follow the manifest: the episode step alone (feature rows, config and trace set are the episode's: unchanged; and
+  // not follow_env: the mark stays alive)
   for (int k = 0; k < n; k++) h->host_t_rel[(size_t)(envs ? envs[k] : k)] = manifest[(size_t)k * SDC_MARK_MANIFEST + SDC_MARK_M_T_REL];
   recompute_steps_to_terminal(h);
   return 0;

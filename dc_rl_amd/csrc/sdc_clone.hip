@@ -13,40 +13,6 @@
 
 namespace {
 
-// (a clang vector, not HIP's uint4: an array of HIP's vector struct is not promoted to registers -- range B's eight loads went
-// through scratch memory)
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// where unit u of a class lies: the last segment whose first unit is <= u.  The scan is unrolled over the table's capacity, so every
-// segment is read at a constant index (a runtime index into the by-value plan would put the plan in scratch memory)
-template <int CAP>
-__device__ __forceinline__ void unit_addr(const SdcCloneSeg (&T)[CAP], const int n_segs, const unsigned u, const size_t src, const size_t dst,
-                                          const unsigned char*& from, unsigned char*& to, unsigned& j, int& seg) {
-  unsigned char* base = T[0].base;
-  unsigned pitch = T[0].pitch, first = 0;
-  seg = 0;
-#pragma unroll
-  for (int i = 1; i < CAP; i++)
-    if (i < n_segs && T[i].first <= u) {
-      base = T[i].base;
-      pitch = T[i].pitch;
-      first = T[i].first;
-      seg = i;
-    }
-  from = base + src * pitch;
-  to = base + dst * pitch;
-  j = u - first;
-}
-
-// header dwords H_PEND .. H_PEND + 3: a dst starts with no deferred re-centring in flight (its windows are src's, valid as they are;
-// a request stamped for src -- or for dst's former state -- carries that env's index in its result, which dst must not take over)
-__device__ __forceinline__ u32x4 clear_pend(u32x4 v, const unsigned unit) {
-  static_assert(H_PEND % 4 == 2, "H_PEND .. H_PEND + 3 are the last two dwords of one 16-byte unit and the first two of the next");
-  if (unit == H_PEND / 4) { v.z = 0u; v.w = 0u; }
-  if (unit == H_PEND / 4 + 1) { v.x = 0u; v.y = 0u; }
-  return v;
-}
-
 __device__ __forceinline__ void range_a(const SdcClonePlan& P, const int b, const int tid) {
   const int k = b / P.bpp, part = b - k * P.bpp;
   const int2 pr = P.pairs[k];
@@ -62,23 +28,28 @@ __device__ __forceinline__ void range_a(const SdcClonePlan& P, const int b, cons
 #pragma unroll
     for (int i = 0; i < SDC_CLONE_UNROLL; i++) {
       const unsigned u = min(u0 + i * stride, P.wide_units - 1);     // (past the end: the last unit again, copied twice)
-      const unsigned char* f;
-      unsigned char* t;
-      unit_addr(P.wide, P.n_wide, u, src, dst, f, t, jj[i], seg[i]);
+      unsigned char* base;
+      unsigned pitch, first;
+      seg_find(P.wide, P.n_wide, u, base, pitch, first, seg[i]);
+      const unsigned char* const f = base + src * pitch;
+      unsigned char* const t = base + dst * pitch;
+      jj[i] = u - first;
       v[i] = reinterpret_cast<const u32x4*>(f)[jj[i]];
       to[i] = reinterpret_cast<u32x4*>(t) + jj[i];
     }
 #pragma unroll
-    for (int i = 0; i < SDC_CLONE_UNROLL; i++) *to[i] = seg[i] == P.hdr_wide ? clear_pend(v[i], jj[i]) : v[i];
+    for (int i = 0; i < SDC_CLONE_UNROLL; i++) *to[i] = seg[i] == P.hdr_wide ? clear_pend(v[i], jj[i]) : v[i];     // (dst's stamps)
   }
   // dword units (rows whose length or alignment is not a multiple of 16 bytes: the observation rows)
 #pragma unroll 1
   for (unsigned u = (unsigned)part * SDC_CLONE_BLOCK + tid; u < P.narrow_units; u += stride) {
-    const unsigned char* f;
-    unsigned char* t;
-    unsigned j;
+    unsigned char* base;
+    unsigned pitch, first;
     int seg;
-    unit_addr(P.narrow, P.n_narrow, u, src, dst, f, t, j, seg);
+    seg_find(P.narrow, P.n_narrow, u, base, pitch, first, seg);
+    const unsigned char* const f = base + src * pitch;
+    unsigned char* const t = base + dst * pitch;
+    const unsigned j = u - first;
     reinterpret_cast<unsigned*>(t)[j] = reinterpret_cast<const unsigned*>(f)[j];
   }
   // ... and src itself: a request in flight for src would be taken over by src alone, and the two would part in window placement
@@ -95,13 +66,7 @@ __device__ __forceinline__ void range_b(const SdcClonePlan& P, const int b, cons
   const size_t rs = (size_t)P.n_envs * Q;  // units per step
   const u32x4* from = reinterpret_cast<const u32x4*>(P.feat) + (size_t)pr.x * Q + q;
   u32x4* to = reinterpret_cast<u32x4*>(P.feat) + (size_t)pr.y * Q + q;
-  // (the last workgroup's rows past the end are clamped to the last row, which its lane then copies more than once: no branches
-  // between the loads and the stores, so the eight loads stay in flight together)
-  u32x4 v[SDC_CLONE_FEAT_ROWS];
-#pragma unroll
-  for (int i = 0; i < SDC_CLONE_FEAT_ROWS; i++) v[i] = from[(size_t)min(rows0 + i, P.feat_rows - 1) * rs];
-#pragma unroll
-  for (int i = 0; i < SDC_CLONE_FEAT_ROWS; i++) to[(size_t)min(rows0 + i, P.feat_rows - 1) * rs] = v[i];
+  move_feat_rows<SDC_CLONE_FEAT_ROWS>(from, rs, to, rs, rows0, P.feat_rows);
 }
 
 __device__ __forceinline__ void range_c(const SdcClonePlan& P, const int b, const int tid) {

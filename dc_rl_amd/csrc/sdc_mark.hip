@@ -2,7 +2,7 @@
 // mark row k -> env envs[k], the same slot it was taken from (sdc_mark_envs / sdc_rewind_envs, sdc_capi.hip; the row layout and the block
 // ranges: sdc_mark.hpp).
 //
-// Bandwidth kernels on the model of sdc_snapshot.hip, for rows of 2-5 KB instead of 146 KB: every byte is read once and written once,
+// Bandwidth kernels like those of sdc_snapshot.hip, for rows of 2-5 KB instead of 146 KB: every byte is read once and written once,
 // every load of a lane is issued before its first store, and reads and writes never meet -- the save reads the engine and writes the
 // caller's rows, the rewind reads the rows and writes the engine, and the host refuses an env that appears twice.  (Where hist_cap is
 // smaller than max_steps the slot sequence passes a ring slot more than once: the save then reads it more than once, and the rewind's
@@ -14,11 +14,9 @@
 
 #include "sdc_device.hpp"
 #include "sdc_mark.hpp"
+#include "sdc_rowcopy.hpp"
 
 namespace {
-
-// (a clang vector, not HIP's uint4: see sdc_snapshot.hip)
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int REC_UNITS = SDC_REC_DWORDS / 4, HDR_UNITS = SDC_HDR_DWORDS / 4, WIN_UNITS = SDC_WIN;
 static_assert(REC_UNITS + HDR_UNITS + WIN_UNITS == SDC_MARK_WIDE_UNITS && SDC_OBS_OUT + SDC_SHARE_OBS_DIM == SDC_MARK_OBS_DWORDS &&
@@ -26,7 +24,6 @@ static_assert(REC_UNITS + HDR_UNITS + WIN_UNITS == SDC_MARK_WIDE_UNITS && SDC_OB
 static_assert(SDC_MARK_WIDE_UNITS <= 96 && SDC_MARK_WIDE_UNITS > 64 && SDC_MARK_OBS_DWORDS <= 128 && SDC_MARK_OBS_DWORDS > 64,
               "a wavefront moves the fixed part in two passes of each kind");
 static_assert(R_TREL == 1 && R_HIST_LEN == 13 && R_HIST_POS == 14, "lane 0 holds t_rel in .y, lane 3 hist_len / hist_pos in .y / .z");
-static_assert(H_PEND % 4 == 2, "H_PEND .. H_PEND + 3 are the last two dwords of one 16-byte unit and the first two of the next");
 
 // the ring slot the j-th append after a record with (hist_len, hist_pos) goes to: what j + 1 calls of hist_append_slot (sdc_physics.hpp)
 // return last -- hist_len + j while the ring is young, then hist_pos, hist_pos + 1, ... modulo hist_cap.  Always below hist_cap
@@ -41,14 +38,6 @@ __device__ __forceinline__ u32x4* wide_ptr(const SdcMarkPlan& P, const size_t en
                 : u < REC_UNITS + HDR_UNITS ? P.hdr + env * SDC_HDR_DWORDS + 4 * (u - REC_UNITS)
                                             : P.qwin + env * (4 * SDC_WIN) + 4 * (u - REC_UNITS - HDR_UNITS);
   return reinterpret_cast<u32x4*>(p);
-}
-
-// header units H_PEND / 4 and the next: no deferred re-centring in flight -- in the row (a request carries the launch counter of the
-// moment it was filed) and in a rewound env (whatever request its later state had filed describes a state that no longer exists)
-__device__ __forceinline__ u32x4 clear_pend(u32x4 v, const unsigned u) {
-  if (u == REC_UNITS + H_PEND / 4) { v.z = 0u; v.w = 0u; }
-  if (u == REC_UNITS + H_PEND / 4 + 1) { v.x = 0u; v.y = 0u; }
-  return v;
 }
 
 __device__ __forceinline__ void env_row(const SdcMarkPlan& P, const int k, size_t& env, unsigned char*& row) {
@@ -87,7 +76,7 @@ __device__ __forceinline__ void range_a(const SdcMarkPlan& P, const int b, const
   // the record's episode step and ring position: lanes 0 and 3 hold them (the live record on a save, the saved one on a rewind)
   const int t_rel = __builtin_amdgcn_readlane((int)w0.y, 0);
   const int hist_len = __builtin_amdgcn_readlane((int)w0.y, 3), hist_pos = __builtin_amdgcn_readlane((int)w0.z, 3);
-  w0 = clear_pend(w0, u0);
+  w0 = clear_pend(w0, u0, REC_UNITS);     // (the header follows the record)
 
   // ---- the variable part: K ring slots, then K queue-table entries of two dwords; SDC_MARK_VAR_UNROLL loads in flight per lane.  The
   // fixed part's stores follow the first pass's loads

@@ -1,7 +1,7 @@
 // sdc_snapshot.hip -- sdc_snapshot_save_kernel: env envs[k] -> snapshot row k; sdc_snapshot_restore_kernel: snapshot row rows[k] ->
 // env envs[k] (sdc_snapshot_envs / sdc_restore_envs, sdc_capi.hip; the plan and the row layout: sdc_snapshot.hpp).
 //
-// Bandwidth kernels on the model of sdc_clone.hip: a row is 145 920 bytes at 672-step episodes (sdc_capi.hip snap_plan: ring 40 960,
+// Bandwidth kernels built from the same parts as sdc_clone.hip (sdc_rowcopy.hpp): a row is 145 920 bytes at 672-step episodes (sdc_capi.hip snap_plan: ring 40 960,
 // feature rows 86 144, weather windows 2 x 5 520, queue table 5 632, record + header + rank windows 1 536, obs rows 428, padding to
 // 256), each byte read once and written once.  Reads and writes never meet: the save
 // reads the engine and writes the caller's rows, the restore reads the rows and writes the engine, and the host refuses a dst that
@@ -14,40 +14,6 @@
 #include "sdc_snapshot.hpp"
 
 namespace {
-
-// (a clang vector, not HIP's uint4: an array of HIP's vector struct is not promoted to registers)
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// where unit u of a class lies, in the engine and in the snapshot row: the last segment whose first unit is <= u.  The scan is
-// unrolled over the table's capacity, so every segment is read at a constant index (a runtime index into the by-value plan would put
-// the plan in scratch memory).  A class's segments lie in the row in unit order from `row0` on: no row offset per segment
-template <int CAP, int UNIT>
-__device__ __forceinline__ void unit_addr(const SdcSnapSeg (&T)[CAP], const int n_segs, const unsigned u, const size_t env,
-                                          unsigned char* row0, unsigned char*& eng, unsigned char*& snap, unsigned& j, int& seg) {
-  unsigned char* base = T[0].base;
-  unsigned pitch = T[0].pitch, first = 0;
-  seg = 0;
-#pragma unroll
-  for (int i = 1; i < CAP; i++)
-    if (i < n_segs && T[i].first <= u) {
-      base = T[i].base;
-      pitch = T[i].pitch;
-      first = T[i].first;
-      seg = i;
-    }
-  j = u - first;
-  eng = base + env * pitch + (size_t)j * UNIT;
-  snap = row0 + (size_t)u * UNIT;
-}
-
-// header dwords H_PEND .. H_PEND + 3: no deferred re-centring in flight -- in the row (a request carries its env's index and the
-// launch counter of the engine that filed it) and in a restored env (whatever request its former state had filed)
-__device__ __forceinline__ u32x4 clear_pend(u32x4 v, const unsigned unit) {
-  static_assert(H_PEND % 4 == 2, "H_PEND .. H_PEND + 3 are the last two dwords of one 16-byte unit and the first two of the next");
-  if (unit == H_PEND / 4) { v.z = 0u; v.w = 0u; }
-  if (unit == H_PEND / 4 + 1) { v.x = 0u; v.y = 0u; }
-  return v;
-}
 
 // record dwords R_CFG / R_LOC of a restored env: the assignment the host checked against this engine's configs and trace sets
 __device__ __forceinline__ u32x4 set_assignment(u32x4 v, const unsigned unit, const int cfg, const int loc) {
@@ -73,8 +39,11 @@ __device__ __forceinline__ void range_a(const SdcSnapPlan& P, const int b, const
 #pragma unroll
     for (int i = 0; i < SDC_SNAP_UNROLL; i++) {
       const unsigned u = min(u0 + i * stride, P.wide_units - 1);     // (past the end: the last unit again, copied twice)
-      unsigned char *e, *s;
-      unit_addr<SDC_SNAP_MAX_WIDE, 16>(P.wide, P.n_wide, u, env, row, e, s, jj[i], seg[i]);
+      unsigned char* base;
+      unsigned pitch, first;
+      seg_find(P.wide, P.n_wide, u, base, pitch, first, seg[i]);
+      jj[i] = u - first;
+      unsigned char *const e = base + env * pitch + (size_t)jj[i] * 16, *const s = row + (size_t)u * 16;
       v[i] = *reinterpret_cast<const u32x4*>(SAVE ? e : s);
       to[i] = reinterpret_cast<u32x4*>(SAVE ? s : e);
     }
@@ -90,10 +59,12 @@ __device__ __forceinline__ void range_a(const SdcSnapPlan& P, const int b, const
   unsigned char* row_n = row + (size_t)P.wide_units * 16;
 #pragma unroll 1
   for (unsigned u = (unsigned)part * SDC_SNAP_BLOCK + tid; u < P.narrow_units; u += stride) {
-    unsigned char *e, *s;
-    unsigned j;
+    unsigned char* base;
+    unsigned pitch, first;
     int seg;
-    unit_addr<SDC_SNAP_MAX_NARROW, 4>(P.narrow, P.n_narrow, u, env, row_n, e, s, j, seg);
+    seg_find(P.narrow, P.n_narrow, u, base, pitch, first, seg);
+    const unsigned j = u - first;
+    unsigned char *const e = base + env * pitch + (size_t)j * 4, *const s = row_n + (size_t)u * 4;
     const unsigned w = *reinterpret_cast<const unsigned*>(SAVE ? e : s);
     *reinterpret_cast<unsigned*>(SAVE ? s : e) = w;
     if (!SAVE && seg == SDC_SNAP_SEG_OBS && P.obs_latch) reinterpret_cast<unsigned*>(P.obs_latch + env * SDC_OBS_OUT)[j] = w;
@@ -111,22 +82,10 @@ __device__ __forceinline__ void range_b(const SdcSnapPlan& P, const int b, const
   const size_t rs = (size_t)P.n_envs * Q;  // units per step
   u32x4* fe = reinterpret_cast<u32x4*>(P.feat) + (size_t)ix.x * Q + q;
   u32x4* sn = reinterpret_cast<u32x4*>(P.rows + (size_t)ix.y * P.row_bytes + P.feat_off) + q;
-  // (the last workgroup's rows past the end are clamped to the last row, which its lane then copies more than once: no branches
-  // between the loads and the stores, so the loads stay in flight together)
-  u32x4 v[SDC_SNAP_FEAT_ROWS];
-#pragma unroll
-  for (int i = 0; i < SDC_SNAP_FEAT_ROWS; i++) {
-    const size_t s = (size_t)min(rows0 + i, P.feat_rows - 1);
-    v[i] = SAVE ? fe[s * rs] : sn[s * Q];
-  }
-#pragma unroll
-  for (int i = 0; i < SDC_SNAP_FEAT_ROWS; i++) {
-    const size_t s = (size_t)min(rows0 + i, P.feat_rows - 1);
-    if (SAVE)
-      sn[s * Q] = v[i];
-    else
-      fe[s * rs] = v[i];
-  }
+  if (SAVE)
+    move_feat_rows<SDC_SNAP_FEAT_ROWS>(fe, rs, sn, Q, rows0, P.feat_rows);
+  else
+    move_feat_rows<SDC_SNAP_FEAT_ROWS>(sn, Q, fe, rs, rows0, P.feat_rows);
 }
 
 constexpr int TILE_DW = SDC_SNAP_TILE_BYTES / 4;     // dwords of one env's row per tile

@@ -6,7 +6,7 @@
 // the engine's n_envs or mapping.  Rows are row_bytes apart (a multiple of 256) in a caller-owned device buffer [n_rows][row_bytes].
 // One launch per direction, in block ranges:
 //   A  the ENV-MAJOR arrays (record, header, rank windows, caller obs / share_obs, queue table, weather windows, ring): `bpe`
-//      workgroups per env, 16 bytes per lane where the engine's row allows it (SdcSnapSeg in `wide`), a dword per lane where it
+//      workgroups per env, 16 bytes per lane where the engine's row allows it (SdcSeg in `wide`, sdc_rowcopy.hpp), a dword per lane where it
 //      does not (`narrow`);
 //   B  the STEP-MAJOR feature rows (SdcDev::feat [episode_steps + 1][N][SDC_FEAT_ROW]) <-> episode_steps + 1 contiguous 128-byte rows
 //      of the snapshot row: eight lanes of 16 bytes per row, 32 envs and SDC_SNAP_FEAT_ROWS steps per workgroup;
@@ -16,7 +16,7 @@
 //   D  (restore, several configs) the per-env copy of the config's scalars (SdcDev::prm_env), from a per-config table.
 #pragma once
 
-#include <stdint.h>
+#include "sdc_rowcopy.hpp"
 
 #define SDC_SNAP_BLOCK 256
 #define SDC_SNAP_MAX_WIDE 7         // segments of 16-byte units (record, header, rank windows, queue table, weather windows, ring)
@@ -29,14 +29,9 @@
 #define SDC_SNAP_SEG_HDR 1          // the second the header (its re-centring stamps H_PEND are written as zeros, both ways)
 #define SDC_SNAP_SEG_OBS 0          // the first narrow segment is the caller's obs (restore: written to the closed loop's copy too)
 
-// one env-major array: env e's unit j lies at base + e * pitch + j * unit (unit: 16 bytes in `wide`, 4 in `narrow`); its units are
-// numbered from `first` on within the segment's class.  In a snapshot row the wide units lie in unit order from byte 0 on, the narrow
-// ones from byte 16 * wide_units on, the feature rows at feat_off
-struct SdcSnapSeg {
-  unsigned char* base;
-  unsigned pitch;
-  unsigned first;
-};
+// env e's unit j of a segment lies at base + e * pitch + j * unit (unit: 16 bytes in `wide`, 4 in `narrow`).  In a snapshot row the
+// wide units lie in unit order from byte 0 on, the narrow ones from byte 16 * wide_units on (a class's segments in unit order: no row
+// offset per segment), the feature rows at feat_off
 
 struct SdcSnapPlan {
   const int4* idx;         // [n] {env, snapshot row, cfg_id, loc_id} (device; restore: sorted by env)
@@ -46,8 +41,8 @@ struct SdcSnapPlan {
   unsigned row_bytes;
   int n_wide, n_narrow;
   unsigned wide_units, narrow_units;   // per env, over all segments of the class
-  SdcSnapSeg wide[SDC_SNAP_MAX_WIDE];
-  SdcSnapSeg narrow[SDC_SNAP_MAX_NARROW];
+  SdcSeg wide[SDC_SNAP_MAX_WIDE];
+  SdcSeg narrow[SDC_SNAP_MAX_NARROW];
   int bpe;                 // range A: workgroups per env
   int blocks_a, blocks_b, blocks_c, blocks_d;   // the grid is A, then B, then C, then D
   float* feat;             // range B (nullptr: none)
