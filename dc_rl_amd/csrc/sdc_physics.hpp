@@ -36,7 +36,8 @@ static_assert(P_COUNT <= HL, "one config scalar per lane of a half");
       /* chiller_power */ 1.0 / 2.778, 0.94483600, -0.05700880, 0.00185486, 2.333, -1.975, 0.6121, 0.03303, 0.6852, 0.2818,   \
       0.05, 1.0 / 0.05, 6.67 - 35.0,                                                                           \
       /* rack model, water, battery, load shifting */ 3.8, 5.3, -14.01, 0.3528, 0.101, 0.044, 0.01, 0.8, 0.2, 1.0 / 100.0,      \
-      1.0 / 20.0, 1.0 / 1e3, 1.0 / 60.0, 1.0 / 1e4, 1.0 / 1e8, 0.04, 0.1, 1e-300, 1e300
+      1.0 / 20.0, 1.0 / 1e3, 1.0 / 60.0, 1.0 / 1e4, 1.0 / 1e8, 0.04, 0.1, 1e-300, 1e300,                                         \
+      /* exp_plain: ln 2 - (double)ln 2 */ 2.3190468138462996e-17
 constexpr double SDC_KVALS[] = {SDC_KVALS_LIST};
 constexpr int SDC_K_COUNT = (int)(sizeof(SDC_KVALS) / sizeof(double));
 constexpr int SDC_K_LDS = 128;     // table entries in LDS (two per lane)
@@ -99,8 +100,10 @@ __device__ __forceinline__ void ktab_store(double* kt, const int lane, const dou
   kt[lane + SDC_WAVE] = k1;
 }
 
-// log2 of a positive, normal, finite double: |error| <= 3e-15 absolute (for the rack model's x^y = exp2(y log2 x), nine
-// orders below what the fp32 outputs resolve) in 29 instructions -- the library's correctly rounded, every-special-case
+// log2 of a positive, normal, finite double: |error| <= 0.5 ulp(result) + 1e-15 for every such x, which on the rack model's range
+// [2^-30, 2^30] is <= 3e-15 absolute -- a bound on THAT range (beyond |log2 x| = 32 half an ulp of the result alone is more), for the
+// rack model's x^y = exp2(y log2 x), nine orders below what the fp32 outputs resolve; both asserted against mpmath on the device
+// (tests/test_gpu_physics_functions.py; measured 8.8e-16 on the rack range).  29 instructions -- the library's correctly rounded, every-special-case
 // log2 is 82.  x = m 2^e with m in [sqrt(1/2), sqrt(2)); log m = 2 atanh(s), s = (m - 1) / (m + 1), |s| <= 0.172: the odd
 // series through s^17 leaves 9e-16 relative.
 template <class KT>
@@ -129,17 +132,9 @@ __device__ __forceinline__ double log2_pos_normal(const double x, const KT kt) {
   return fma(q * p, KC(2.8853900817779268) /* 2 / ln 2 */, (double)e);
 }
 
-// exp(t) for |t| <= 700: 2^(t log2 e) with the fraction's power from a degree-12 Taylor polynomial (<= 2e-16 relative)
-// + the scaling by ldexp; 17 instructions against the library's 45
+// e^f 2^n for |f| <= 0.3466 and an integer n: the degree-12 Taylor polynomial + the scaling by ldexp
 template <class KT>
-__device__ __forceinline__ double exp2_plain(const double y, const KT kt);
-template <class KT>
-__device__ __forceinline__ double exp_plain(const double t, const KT kt) { return exp2_plain(t * KC(1.4426950408889634), kt); }
-// 2^y for |y| <= 1000, same way
-template <class KT>
-__device__ __forceinline__ double exp2_plain(const double y, const KT kt) {
-  const double n = __builtin_rint(y);
-  const double f = (y - n) * KC(0.6931471805599453);     // |f| <= 0.3466
+__device__ __forceinline__ double exp_frac12(const double f, const double n, const KT kt) {
   double p = KC(1.0 / 479001600.0);
   p = fma(p, f, KC(1.0 / 39916800.0));
   p = fma(p, f, KC(1.0 / 3628800.0));
@@ -155,8 +150,26 @@ __device__ __forceinline__ double exp2_plain(const double y, const KT kt) {
   p = fma(p, f, 1.0);
   return __builtin_amdgcn_ldexp(p, (int)n);
 }
+// exp(t) for |t| <= 700: n = rint(t log2 e), f = t - n ln 2 in two fused steps (ln 2 as a double and what it leaves, so that f is good
+// to 5e-17 for every n up to 1010 -- as (t log2 e - n) ln 2 the product's rounding alone cost 4e-14 relative at |t| = 700 and 6e-16 at
+// the sigmoid's |t| = 10), then the polynomial: <= 4 ulp (8.9e-16) relative over the whole range, asserted against mpmath on the device
+// (tests/test_gpu_physics_functions.py; measured 3.5e-16); 17 instructions against the library's 45
+template <class KT>
+__device__ __forceinline__ double exp_plain(const double t, const KT kt) {
+  const double n = __builtin_rint(t * KC(1.4426950408889634));
+  double f = fma(-n, KC(0.6931471805599453), t);
+  f = fma(-n, KC(2.3190468138462996e-17), f);            // ln 2 - (double)ln 2
+  return exp_frac12(f, n, kt);
+}
+// 2^y for |y| <= 1000, same way (y - n is exact): <= 4 ulp relative, asserted the same way (measured 3.4e-16)
+template <class KT>
+__device__ __forceinline__ double exp2_plain(const double y, const KT kt) {
+  const double n = __builtin_rint(y);
+  return exp_frac12((y - n) * KC(0.6931471805599453) /* |f| <= 0.3466 */, n, kt);
+}
 
-// 2^y to <= 3e-10 relative (degree 8): for the rack outlet-temperature rise, whose consumers resolve 1e-7 at best
+// 2^y to <= 3e-10 relative (degree 8; the Taylor remainder at |f| = ln2 / 2 is 2.91e-10 of e^f, measured 2.72e-10): for the rack
+// outlet-temperature rise, whose consumers resolve 1e-7 at best
 template <class KT>
 __device__ __forceinline__ double exp2_short(const double y, const KT kt) {
   const double n = __builtin_rint(y);

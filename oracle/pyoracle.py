@@ -105,6 +105,8 @@ def lib():
                                     C.POINTER(C.c_uint)]
         L.sdco_chiller_power.argtypes = [C.c_double, C.c_double, C.c_double]
         L.sdco_chiller_power.restype = C.c_double
+        L.sdco_battery_step.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, dp]
+        L.sdco_battery_step.restype = C.c_uint
         L.sdco_size_datacenter.argtypes = [C.POINTER(Params), C.c_double, dp]
         L.sdco_run_steps.argtypes = [C.POINTER(Env), C.POINTER(Params), C.POINTER(C.c_int32), C.c_long, C.c_int,
                                      C.c_int, C.c_int, dp]

@@ -401,6 +401,50 @@ void sdco_episode_begin(sdco_env *e, const sdco_params *p, const double *W, cons
 
 static double sigmoid(double x) { return 1 / (1 + exp(-x)); }
 
+/* the battery block of the step: envs/bat_env_fwd_view.py:84-245, envs/battery_model.py:94-132.
+ * out = {bat_load after the step, energy without the battery (kWh), energy with it, CO2, SoC after the step,
+ *        rate * 1e4 before np.round(rate, 4) (charging; 0 otherwise), load * 1e8 before np.round(load, 8) (0 when idle)};
+ * returns the fault bits (SDCO_FAULT_BAT_DISCHARGE). */
+unsigned sdco_battery_step(int action, double bat_load, double cap, double total_kw, double ci, double out[7]) {
+  unsigned fault = 0;
+  const double dcload = total_kw / 1e3; /* MW (sustaindc_env.py:652) */
+  double energy, co2, rate_e4 = 0.0, load_e8 = 0.0;
+  if (action == 0) { /* charge */
+    double soc = (bat_load - 0) / (cap - 0);
+    rate_e4 = (0.5 * (1 - sigmoid(10 * (soc - 0.5)))) * 1e4;
+    double rate = rint(rate_e4) / 1e4; /* np.round(rate, 4) */
+    double tu = rate * 15 / 60;
+    double max_charge = fmin((cap / 1) * 0.1, (1 * cap - bat_load) / ((1 * tu) - (-0.04)));
+    double charging_load = fmin(max_charge, cap) * 1 * tu;
+    load_e8 = (bat_load + charging_load) * 1e8;
+    bat_load = rint(load_e8) / 1e8; /* np.round(load, 8) */
+    energy = dcload * 1e3 * 0.25 + charging_load * 1e3;
+    co2 = energy * ci;
+  } else if (action == 1) { /* discharge */
+    double soc = (bat_load - 0) / (cap - 0);
+    double rate = fmax(0.5, 4 * sigmoid(10 * (soc - 0.25)));
+    double tu = rate * 15 / 60;
+    double max_d = fmin(fmin((cap / 1) * 1, (bat_load - 0 * cap) / (0.01 + (1 * tu))), dcload / 4);
+    load_e8 = (bat_load - (fmin(max_d, cap) * 1 * tu)) * 1e8;
+    bat_load = rint(load_e8) / 1e8;
+    double discharge = max_d < cap ? max_d * tu : cap * tu;
+    if (!(dcload * 1e3 * 0.25 >= discharge * 1e3)) fault |= SDCO_FAULT_BAT_DISCHARGE;
+    energy = dcload * 1e3 * 0.25 - discharge * 1e3;
+    co2 = fmax(energy, 0) * ci;
+  } else { /* idle */
+    energy = dcload * 1e3 * 0.25;
+    co2 = energy * ci;
+  }
+  out[0] = bat_load;
+  out[1] = dcload * 1e3 * 0.25;
+  out[2] = energy;
+  out[3] = co2;
+  out[4] = bat_load / cap;
+  out[5] = rate_e4;
+  out[6] = load_e8;
+  return fault;
+}
+
 int sdco_step(sdco_env *e, const sdco_params *p, const int32_t act[3], float *obs53, double rew[3],
               double info[SDCO_INFO_DIM]) {
   const int i = e->cursor;
@@ -519,39 +563,17 @@ int sdco_step(sdco_env *e, const sdco_params *p, const int32_t act[3], float *ob
   info[SDCO_I_DC_AMBIENT_TEMP] = T[i];
   info[SDCO_I_DC_WATER_USAGE] = dc[5];
 
-  /* ---- battery: envs/bat_env_fwd_view.py:84-245, envs/battery_model.py:94-132 */
-  const double cap = p->bat_capacity;
-  const double dcload = total_kw / 1e3; /* MW (sustaindc_env.py:652) */
+  /* ---- battery: sdco_battery_step */
   const double ci = C[i];
-  double energy, co2;
-  if (act[2] == 0) { /* charge */
-    double soc = (e->bat_load - 0) / (cap - 0);
-    double rate = np_round(0.5 * (1 - sigmoid(10 * (soc - 0.5))), 1e4);
-    double tu = rate * 15 / 60;
-    double max_charge = fmin((cap / 1) * 0.1, (1 * cap - e->bat_load) / ((1 * tu) - (-0.04)));
-    double charging_load = fmin(max_charge, cap) * 1 * tu;
-    e->bat_load = np_round(e->bat_load + charging_load, 1e8);
-    energy = dcload * 1e3 * 0.25 + charging_load * 1e3;
-    co2 = energy * ci;
-  } else if (act[2] == 1) { /* discharge */
-    double soc = (e->bat_load - 0) / (cap - 0);
-    double rate = fmax(0.5, 4 * sigmoid(10 * (soc - 0.25)));
-    double tu = rate * 15 / 60;
-    double max_d = fmin(fmin((cap / 1) * 1, (e->bat_load - 0 * cap) / (0.01 + (1 * tu))), dcload / 4);
-    e->bat_load = np_round(e->bat_load - (fmin(max_d, cap) * 1 * tu), 1e8);
-    double discharge = max_d < cap ? max_d * tu : cap * tu;
-    if (!(dcload * 1e3 * 0.25 >= discharge * 1e3)) fault |= SDCO_FAULT_BAT_DISCHARGE;
-    energy = dcload * 1e3 * 0.25 - discharge * 1e3;
-    co2 = fmax(energy, 0) * ci;
-  } else { /* idle */
-    energy = dcload * 1e3 * 0.25;
-    co2 = energy * ci;
-  }
+  double bat[7];
+  fault |= sdco_battery_step(act[2], e->bat_load, p->bat_capacity, total_kw, ci, bat);
+  e->bat_load = bat[0];
+  const double energy = bat[2];
   info[SDCO_I_BAT_ACTION] = act[2];
-  info[SDCO_I_BAT_SOC] = e->bat_load / cap;
-  info[SDCO_I_BAT_CO2] = co2;
+  info[SDCO_I_BAT_SOC] = bat[4];
+  info[SDCO_I_BAT_CO2] = bat[3];
   info[SDCO_I_BAT_AVG_CI] = ci;
-  info[SDCO_I_BAT_ENERGY_WITHOUT_KWH] = dcload * 1e3 * 0.25;
+  info[SDCO_I_BAT_ENERGY_WITHOUT_KWH] = bat[1];
   info[SDCO_I_BAT_ENERGY_WITH_KWH] = energy;
 
   /* ---- managers step: utils/managers.py:127-147 (+ :285, :452, :633: cursor += 1) */

@@ -121,6 +121,10 @@ void sdco_extract_features(const double *vals, int n, double cur, double out5[5]
 void sdco_dc_model(const sdco_params *p, double stpt, double load_pct, double ambient, double wet_bulb,
                    double out[8], unsigned *fault); /* IT + HVAC + water; see .c */
 double sdco_chiller_power(double max_cooling_cap, double load, double ambient_temp); /* datacenter.py:356-429 */
+/* the battery block of sdco_step (bat_env_fwd_view.py:84-245, battery_model.py:94-132); returns the fault bits.
+ * out = {bat_load after, energy without battery kWh, energy with it, CO2, SoC after, rate * 1e4 and load * 1e8 as they are
+ * before np.round(rate, 4) / np.round(load, 8) (0 where the action does not round)} */
+unsigned sdco_battery_step(int action, double bat_load, double cap, double total_kw, double ci, double out[7]);
 
 /* init-time sizing (utils/make_envs_pyenv.py:139-197, envs/datacenter.py:476-529).  Fills
  * p->ctafr, p->ct_fan_ref_p, p->bat_capacity and the min/max of the 88-point sweep. */
