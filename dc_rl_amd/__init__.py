@@ -8,6 +8,8 @@ Public surface (mirrors the reference's names for this path):
   * `install_into_harl()`                          -- rebinds those factories inside an UNCHANGED HARL tree (zero edits)
   * `SustainDCMultiDeviceVecEnv` / `make_train_env(..., devices=[...])` -- the same ShareVecEnv over several GPUs in one process
   * `SdcEngine`                                    -- thin ctypes wrapper over the C-ABI (include/sustaindc_hip.h)
+  * `RBCBatteryAgent`, `trim_and_respond_ctrl`, `ShootingMPCAgent` -- the rule-based baselines (utils/rbc_agents.py,
+                                                      utils/trim_and_respond.py) and a shooting MPC over `SdcEngine.plan`
 
 The compute path is the HIP extension `csrc/libsustaindc_hip.so` (hand-written gfx950 kernels).  There is
 no CPU fallback: constructing an engine without the extension or without an MI355X raises.
@@ -28,6 +30,9 @@ _LAZY = {
     "make_ls_env": ("make_envs_pyenv", "make_ls_env"),
     "make_dc_pyeplus_env": ("make_envs_pyenv", "make_dc_pyeplus_env"),
     "make_bat_fwd_env": ("make_envs_pyenv", "make_bat_fwd_env"),
+    "ShootingMPCAgent": ("agents", "ShootingMPCAgent"),
+    "RBCBatteryAgent": ("agents", "RBCBatteryAgent"),
+    "trim_and_respond_ctrl": ("agents", "trim_and_respond_ctrl"),
 }
 
 

@@ -107,3 +107,46 @@ class trim_and_respond_ctrl:
 #   trim_and_respond_ctrl(limit)                              -> POLICY_TRIM_AND_RESPOND on the dc slot: fed the
 #                                                               dc_int_temperature the previous step reported
 POLICY_EXTERNAL, POLICY_DO_NOTHING, POLICY_RBC, POLICY_TRIM_AND_RESPOND = 0, 1, 2, 3
+
+
+class ShootingMPCAgent:
+    """Random-shooting model-predictive control with the simulator as its own model: at every decision draw `n_candidates` action
+    sequences of `horizon` steps per env, score them on the device from the env's current state (SdcEngine.plan / SustainDCVecEnv.plan
+    over sdc_plan: mark, roll out, score, rewind) and play the first action of the best.  Candidate 0 is always the do-nothing sequence
+    (ls 1, dc 1, bat 2), so on the model the chosen sequence never scores below doing nothing.  The candidates come from a torch.Generator on
+    the env's device seeded with `seed`: two agents with one seed on twin envs choose the same actions.  reward_weights, gamma,
+    info_weights: the objective, as `plan` takes it.  The horizon is shortened to what the episode has left (the planner does not look
+    across an episode's end); with fewer than two steps left the agent does nothing.  `last`: the latest PlanResult (None after a
+    do-nothing fallback), `last_horizon` the horizon it used."""
+
+    DO_NOTHING = (1, 1, 2)
+
+    def __init__(self, n_candidates: int = 8, horizon: int = 8, seed: int = 0, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0,
+                 info_weights=None):
+        if n_candidates < 1 or horizon < 1:
+            raise ValueError("ShootingMPCAgent: n_candidates and horizon must be positive")
+        self.n_candidates, self.horizon, self.seed = int(n_candidates), int(horizon), int(seed)
+        self.reward_weights, self.gamma, self.info_weights = tuple(reward_weights), float(gamma), info_weights
+        self._gen = None
+        self.last = None
+        self.last_horizon = 0
+
+    def act(self, env):
+        """env: an SdcEngine or a SustainDCVecEnv -> int32 device tensor [N, 3] (the vec env: [N, n_agents], its agents' columns)."""
+        import torch
+        eng = getattr(env, "engine", env)
+        N = eng.n_envs
+        idx = list(getattr(env, "_agent_idx", (0, 1, 2)))
+        nothing = torch.tensor([self.DO_NOTHING[i] for i in idx], dtype=torch.int32, device=eng.device)
+        left = eng.steps_to_episode_end()
+        K = min(self.horizon, left - 1 if eng.config["auto_reset"] else left)
+        if left < 2 or K < 1:
+            self.last, self.last_horizon = None, 0
+            return nothing.expand(N, len(idx)).contiguous()
+        if self._gen is None:
+            self._gen = torch.Generator(device=eng.device)
+            self._gen.manual_seed(self.seed)
+        cand = torch.randint(0, 3, (self.n_candidates, K, N, len(idx)), generator=self._gen, device=eng.device, dtype=torch.int32)
+        cand[0] = nothing
+        self.last, self.last_horizon = env.plan(cand, self.reward_weights, self.gamma, self.info_weights), K
+        return self.last.action

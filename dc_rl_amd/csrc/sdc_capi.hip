@@ -21,6 +21,7 @@
 #include "sdc_clone.hpp"
 #include "sdc_snapshot.hpp"
 #include "sdc_mark.hpp"
+#include "sdc_plan.hpp"
 
 extern "C" __global__ void sdc_dynamics_kernel(SdcDev S, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
                                                unsigned char* done, float* info, float* final_obs, float* rew);
@@ -89,10 +90,11 @@ struct Field {
 };
 
 // The index entries of a launch (which envs, which rows) staged through pinned host memory into a device buffer: two slots of [N]
-// entries of each, used in turn and allocated together on first use.  A slot's event marks the launch that last read it; a call waits
+// entries of each (or of `slot_entries`, for what is not sized by the batch), used in turn and allocated together on first use.  A slot's event marks the launch that last read it; a call waits
 // for it only before it overwrites that slot, i.e. for the call two back on the same stage (stage_acquire / stage_commit)
 struct IdxStage {
   size_t entry_bytes;
+  size_t slot_entries = 0;                // entries per slot (0: n_envs)
   unsigned char* dev = nullptr;           // [2][N]
   unsigned char* pin = nullptr;           // [2][N]
   hipEvent_t done[2] = {nullptr, nullptr};
@@ -168,6 +170,14 @@ struct sdc_handle {
   std::vector<int> mark_serial;
   int mark_next_serial = 0;
   int mark_engine_id = 0;                 // this handle's id in the manifests it fills (given out by the first mark)
+  // sdc_plan: the mark rows and the rollouts' output block (sdc_plan.hpp) are the handle's, grown on demand and freed with it; the
+  // manifest of its mark; the discount table's staging
+  unsigned char* plan_rows = nullptr;
+  size_t plan_rows_bytes = 0;
+  unsigned char* plan_out = nullptr;
+  size_t plan_out_bytes = 0;
+  std::vector<int32_t> plan_manifest;
+  IdxStage plan_stage{sizeof(double), SDC_MARK_MAX_STEPS};
 };
 
 namespace {
@@ -537,7 +547,7 @@ int finish_launch(sdc_handle* h, SdcDev& d, const int n_steps, float* obs_last, 
 // The pinned side of the slot this call fills.  Allocates on first use -- all staging resources or none: a failure part way leaves
 // `ready` false, and the next call starts over from what is set -- and waits for the call two back if it may still be reading the slot
 int stage_acquire(sdc_handle* h, IdxStage& S, void** pin) {
-  const size_t slot_bytes = S.entry_bytes * (size_t)h->cfg.n_envs;
+  const size_t slot_bytes = S.entry_bytes * (S.slot_entries ? S.slot_entries : (size_t)h->cfg.n_envs);
   if (!S.ready) {
     if (!S.dev && dev_alloc(h, &S.dev, 2 * slot_bytes, false) != 0) return -1;
     if (!S.pin) {
@@ -567,7 +577,7 @@ int stage_acquire(sdc_handle* h, IdxStage& S, void** pin) {
 template <typename Launch>
 int stage_commit(sdc_handle* h, IdxStage& S, const size_t n, hipStream_t st, Launch launch) {
   const int slot = S.slot ^ 1;      // (the slot stage_acquire has just handed out)
-  const size_t off = (size_t)slot * S.entry_bytes * (size_t)h->cfg.n_envs;
+  const size_t off = (size_t)slot * S.entry_bytes * (S.slot_entries ? S.slot_entries : (size_t)h->cfg.n_envs);
   HIP_TRY(hipMemcpyAsync(S.dev + off, S.pin + off, S.entry_bytes * n, hipMemcpyHostToDevice, st));
   HIP_TRY(launch(S.dev + off));
   HIP_TRY(hipEventRecord(S.done[slot], st));
@@ -706,7 +716,7 @@ int sdc_create(const sdc_config* cfg, sdc_handle** out) {
   d.lw = cfg->episode_steps + 18;
   d.qstride = (cfg->episode_steps + 63) / 64 * 64;
   d.max_roll_days = cfg->max_roll_days;
-  d.debug_flags = cfg->debug_flags;
+  d.debug_flags = cfg->debug_flags & ~SDC_PLAN_DEBUG_TWO_STEPS;      // (sdc_plan's test hook: read from h->cfg by that call alone)
   d.env_base = cfg->env_index_base;
   for (int a = 0; a < 3; a++) {
     if (cfg->reward_method[a] < 0 || cfg->reward_method[a] > SDC_REWARD_WATER) {
@@ -846,6 +856,9 @@ int sdc_destroy(sdc_handle* h) {
   (void)hipSetDevice(h->device);
   stage_destroy(h->clone_stage);
   stage_destroy(h->idx_stage);
+  stage_destroy(h->plan_stage);
+  if (h->plan_rows) (void)hipFree(h->plan_rows);
+  if (h->plan_out) (void)hipFree(h->plan_out);
   for (void* p : h->allocs) (void)hipFree(p);
   delete h;
   return 0;
@@ -1915,6 +1928,119 @@ int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows,
   for (int k = 0; k < n; k++) h->host_t_rel[(size_t)(envs ? envs[k] : k)] = manifest[(size_t)k * SDC_MARK_MANIFEST + SDC_MARK_M_T_REL];
   recompute_steps_to_terminal(h);
   return 0;
+}
+
+// ---- plan (sdc_plan.hip) ---------------------------------------------------------------------------------------------------------
+// The contract and the arithmetic: include/sustaindc_hip.h; the output block and the kernels' plans: sdc_plan.hpp.
+
+// a buffer of the handle's that only grows (hipFree waits for whatever may still use the old one)
+static int plan_grow(sdc_handle* h, unsigned char** buf, size_t* have, const size_t need) {
+  if (*have >= need) return 0;
+  if (*buf) {
+    HIP_TRY(hipFree(*buf));
+    *buf = nullptr;
+    *have = 0;
+  }
+  void* q = nullptr;
+  HIP_TRY(hipMalloc(&q, need));
+  *buf = static_cast<unsigned char*>(q);
+  *have = need;
+  (void)h;
+  return 0;
+}
+
+// Mark, then per candidate: roll out (in chunks of what the output block holds), score, rewind; then select.  Built from the entry
+// points themselves -- sdc_mark_envs, sdc_rollout, sdc_rewind_envs -- so the rollouts choose their kernel as sdc_rollout does and the
+// host mirrors are kept by the code that keeps them for every other caller.  Whatever those would refuse is refused here first.
+int sdc_plan(sdc_handle* h, int n_cand, int n_steps, const int32_t* actions, const sdc_plan_objective* objective, double* returns,
+             double* score, int32_t* best, int32_t* best_action, float* obs, float* share_obs, void* stream) {
+  if (!h) return fail_msg("sdc_plan: null handle");
+  if (n_cand < 1) return fail_msg("sdc_plan: n_cand = " + std::to_string(n_cand) + " must be positive");
+  if (n_steps < 1 || n_steps > SDC_MARK_MAX_STEPS)
+    return fail_msg("sdc_plan: n_steps = " + std::to_string(n_steps) + " outside [1, " + std::to_string(SDC_MARK_MAX_STEPS) + "]");
+  if (!actions || !score || !best || !best_action || !obs || !share_obs) return fail_msg("sdc_plan: null array");
+  if (((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(share_obs)) & 3u) != 0)
+    return fail_msg("sdc_plan: obs / share_obs rows not dword-aligned");
+  if (!h->started) return fail_msg("sdc_plan: sdc_reset must be called first");
+  if (h->cfg.debug_flags & 1) return fail_msg("sdc_plan: verify mode checks single steps (sdc_rollout refuses it as well)");
+  if (h->cfg.auto_reset && n_steps >= h->steps_to_terminal)
+    return fail_msg("sdc_plan: n_steps = " + std::to_string(n_steps) + " would finish an episode (" + std::to_string(h->steps_to_terminal) +
+                    " steps left): the auto-reset kills the mark");
+  if (n_steps > h->steps_to_terminal)
+    return fail_msg("sdc_plan: n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" +
+                    std::to_string(h->steps_to_terminal) + " steps left)");
+  sdc_plan_objective obj;
+  std::memset(&obj, 0, sizeof(obj));
+  obj.reward_weight[0] = obj.reward_weight[1] = obj.reward_weight[2] = 1.0;
+  obj.gamma = 1.0;
+  if (objective) obj = *objective;
+  if (!(obj.gamma > 0.0 && obj.gamma <= 1.0)) return fail_msg("sdc_plan: gamma = " + std::to_string(obj.gamma) + " outside (0, 1]");
+  if (obj.n_cols < 0 || obj.n_cols > SDC_PLAN_MAX_COLS)
+    return fail_msg("sdc_plan: n_cols = " + std::to_string(obj.n_cols) + " outside [0, " + std::to_string(SDC_PLAN_MAX_COLS) + "]");
+  for (int j = 0; j < obj.n_cols; j++)
+    if (obj.col[j] < 0 || obj.col[j] >= SDC_INFO_DIM)
+      return fail_msg("sdc_plan: info column " + std::to_string(obj.col[j]) + " (entry " + std::to_string(j) + ") outside [0, " +
+                      std::to_string(SDC_INFO_DIM) + ")");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const size_t N = (size_t)h->cfg.n_envs;
+  // the handle's buffers, before anything is enqueued
+  int chunk = sdc_plan_steps_fit(N, n_steps, SDC_PLAN_SCRATCH_BYTES);
+  if (h->cfg.debug_flags & SDC_PLAN_DEBUG_TWO_STEPS) chunk = std::min(chunk, 2);
+  const SdcPlanBlock B = sdc_plan_block(N, (size_t)chunk);
+  if (plan_grow(h, &h->plan_rows, &h->plan_rows_bytes, N * sdc_mark_row_bytes(n_steps))) return -1;
+  if (plan_grow(h, &h->plan_out, &h->plan_out_bytes, B.bytes)) return -1;
+  h->plan_manifest.resize(N * SDC_MARK_MANIFEST);
+  unsigned char* const out = h->plan_out;
+  float* const o_obs = reinterpret_cast<float*>(out + B.obs);
+  float* const o_share = reinterpret_cast<float*>(out + B.share_obs);
+  float* const o_rew = reinterpret_cast<float*>(out + B.rew);
+  float* const o_info = reinterpret_cast<float*>(out + B.info);
+  float* const o_final = reinterpret_cast<float*>(out + B.final_obs);
+  // the discount table g_k = g_{k-1} * gamma, through the plan's stage; the slot stays in flight until the last kernel that reads it
+  void* pin = nullptr;
+  if (stage_acquire(h, h->plan_stage, &pin)) return -1;
+  double* const g = static_cast<double*>(pin);
+  g[0] = 1.0;
+  for (int k = 1; k < n_steps; k++) g[k] = g[k - 1] * obj.gamma;
+  int rc = 0;
+  const int staged = stage_commit(h, h->plan_stage, (size_t)n_steps, st, [&](const void* g_dev) {
+    rc = sdc_mark_envs(h, nullptr, (int)N, n_steps, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
+    SdcPlanScore S;
+    std::memset(&S, 0, sizeof(S));
+    S.n_envs = (int)N;
+    S.n_cols = obj.n_cols;
+    S.g = static_cast<const double*>(g_dev);
+    S.rew = o_rew;
+    S.info = o_info;
+    for (int a = 0; a < 3; a++) S.w[a] = obj.reward_weight[a];
+    for (int j = 0; j < obj.n_cols; j++) {
+      S.col[j] = obj.col[j];
+      S.col_weight[j] = obj.col_weight[j];
+    }
+    for (int c = 0; c < n_cand && rc == 0; c++) {
+      S.returns = returns ? returns + (size_t)c * N * 3 : nullptr;
+      S.score = score + (size_t)c * N;
+      for (int k0 = 0; k0 < n_steps && rc == 0; k0 += chunk) {
+        S.first_step = k0;
+        S.steps = std::min(chunk, n_steps - k0);
+        rc = sdc_rollout(h, S.steps, actions + ((size_t)c * (size_t)n_steps + (size_t)k0) * N * 3, o_obs, o_share, o_rew, out + B.done, o_info,
+                         o_final, nullptr, stream);
+        if (rc == 0) {
+          const hipError_t e = sdc_plan_score_launch(S, st);
+          if (e != hipSuccess) rc = fail("sdc_plan_score_kernel", e);
+        }
+      }
+      if (rc == 0) rc = sdc_rewind_envs(h, nullptr, (int)N, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
+    }
+    if (rc == 0) {
+      const SdcPlanSelect Q{(int)N, n_cand, n_steps, score, actions, best, best_action};
+      const hipError_t e = sdc_plan_select_launch(Q, st);
+      if (e != hipSuccess) rc = fail("sdc_plan_select_kernel", e);
+    }
+    return hipSuccess;
+  });
+  return rc ? rc : staged;
 }
 
 }  // extern "C"

@@ -96,6 +96,36 @@ class EnvMark:
             raise ValueError(f"rewind: env {ex.args[0]} is not one of the mark's envs") from None
 
 
+class PlanResult:
+    """What SdcEngine.plan returns, all on the engine's device: `best` int32 [N] the winning candidate of every env, `action` int32
+    [N, 3] its first action (SustainDCVecEnv.plan: the agent subset's columns), `score` float64 [M, N] and `returns` float64 [M, N, 3]
+    (the three agents' discounted returns of every candidate)."""
+
+    def __init__(self, best, action, score, returns):
+        self.best, self.action, self.score, self.returns = best, action, score, returns
+
+
+def plan_objective(reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None) -> L.SdcPlanObjective:
+    """plan's objective as the library's struct; ValueError for anything but three reward weights, an unknown info key, more than
+    PLAN_MAX_COLS keys (gamma is the library's to refuse)."""
+    w = [float(x) for x in reward_weights]
+    if len(w) != 3:
+        raise ValueError(f"plan: reward_weights must be three numbers (ls, dc, bat), got {len(w)}")
+    cols = dict(info_weights or {})
+    if len(cols) > L.PLAN_MAX_COLS:
+        raise ValueError(f"plan: info_weights names {len(cols)} keys, at most {L.PLAN_MAX_COLS} can be weighed")
+    o = L.SdcPlanObjective()
+    o.reward_weight[:] = w
+    o.gamma = float(gamma)
+    o.n_cols = len(cols)
+    for j, (key, weight) in enumerate(cols.items()):
+        if key not in L.INFO_IDX:
+            raise ValueError(f"plan: info_weights key {key!r} is not an info column (dc_rl_amd._lib.INFO_COLS)")
+        o.col[j] = L.INFO_IDX[key]
+        o.col_weight[j] = float(weight)
+    return o
+
+
 def dc_params_struct(p: dict) -> L.SdcDcParams:
     """dict (see dc_config.size_datacenter) -> C struct."""
     s = L.SdcDcParams()
@@ -709,6 +739,44 @@ class SdcEngine:
             self.out_flat.copy_(keep)
             self.final_obs.copy_(keep_final)
         return returns
+
+    def plan(self, actions, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None) -> PlanResult:
+        """Score M candidate action sequences of K steps from the current state, pick every env's best, and come back (sdc_plan): one
+        library call -- mark, per candidate rollout / score / rewind, select -- with no Python between the launches and no per-step
+        output the caller has to hold; what `lookahead` does in a loop, plus the objective and the selection.  `actions` int32 device
+        tensor [M, K, N, 3].  A candidate's score is the discounted sum over its steps (gamma ** k, built by repeated multiplication) of
+        reward_weights . (r_ls, r_dc, r_bat) + sum of info_weights[key] * info[key] -- `info_weights` a dict of at most PLAN_MAX_COLS
+        info key names (dc_rl_amd._lib.INFO_COLS: bat_CO2_footprint, dc_water_usage, ls_tasks_dropped, ...) -> weight; fp64, in step
+        order (the exact operation order: include/sustaindc_hip.h).  The best candidate is the lowest-numbered one with the highest
+        score.  -> PlanResult(best [N], action [N, 3] = actions[best, 0], score [M, N], returns [M, N, 3]).
+        The engine -- state, output buffers, closed-loop copy -- is where it was, with `lookahead`'s one difference (the rewinds clear
+        the re-centring stamps) and the same price: the call uses up the envs' one live mark, so a mark taken earlier is dead
+        afterwards.  A slot on a built-in policy ignores its action column.  ValueError, with the engine untouched, for malformed
+        actions, an unknown info key or too many, and what the library refuses: K > MARK_MAX_STEPS, K >= steps_to_episode_end() with
+        auto_reset (> without), no reset() yet, gamma outside (0, 1], verify mode (debug_flags bit 0: rollouts have none)."""
+        t = self.torch
+        if not (isinstance(actions, t.Tensor) and actions.dtype == t.int32 and actions.is_cuda and actions.is_contiguous() and
+                actions.dim() == 4 and tuple(actions.shape[2:]) == (self.n_envs, 3) and actions.shape[0] >= 1 and actions.shape[1] >= 1):
+            raise ValueError("plan: actions must be a contiguous int32 CUDA tensor of shape (M, K, n_envs, 3)")
+        if actions.device != self.device:
+            raise ValueError(f"plan: actions are on {actions.device}, this engine runs on {self.device}")
+        M, K, N = int(actions.shape[0]), int(actions.shape[1]), self.n_envs
+        if K > L.MARK_MAX_STEPS:
+            raise ValueError(f"plan: K = {K} is more than a mark holds (MARK_MAX_STEPS = {L.MARK_MAX_STEPS})")
+        obj = plan_objective(reward_weights, gamma, info_weights)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with t.cuda.device(self.device):
+            returns = t.empty((M, N, L.N_AGENTS), dtype=t.float64, device=self.device)
+            score = t.empty((M, N), dtype=t.float64, device=self.device)
+            best = t.empty((N,), dtype=t.int32, device=self.device)
+            action = t.empty((N, 3), dtype=t.int32, device=self.device)
+            rc = self.lib.sdc_plan(self._h, M, K, p(actions), C.byref(obj), p(returns), p(score), p(best), p(action), p(self.obs),
+                                   p(self.share_obs), self._stream())
+        self._refused(rc)
+        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse them before)
+            for x in (returns, score, best, action, actions):
+                x.record_stream(self._pinned_stream_obj)
+        return PlanResult(best, action, score, returns)
 
     def profile(self, every: int = 1):
         """Per-kernel HIP-event timing on the launch stream (measurement only): every k-th step, 0 = off."""

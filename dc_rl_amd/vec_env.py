@@ -486,6 +486,27 @@ class SustainDCVecEnv(ShareVecEnv):
         self._actions = None
         return self._out(self._sel_obs(obs)), self._out(self._share3(share, obs)), (self._avail if self.return_torch else self._avail_np)
 
+    def plan(self, actions, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None):
+        """Score M candidate action sequences of K steps, pick every env's best, and come back (SdcEngine.plan).  `actions`: an int
+        tensor [M, K, num_envs, n_agents] in this env's agent order; with an agent subset the other slots' columns are filled with 1
+        (they are played on the device and never read), as step_async does.  -> PlanResult whose `action` [num_envs, n_agents] holds
+        the subset's columns, ready for step(); `returns` keeps all three slots.  The run goes on as if the call had not happened;
+        actions handed to step_async stay; the envs' live mark is used up.  ValueError for what the engine refuses."""
+        if self._need_reset:
+            raise ValueError("plan: call reset() first")
+        t = self._torch
+        if not (isinstance(actions, t.Tensor) and actions.dim() == 4 and tuple(actions.shape[2:]) == (self.num_envs, self.n_agents)):
+            raise ValueError(f"plan: actions must be a tensor of shape (M, K, {self.num_envs}, {self.n_agents})")
+        a = actions.to(device=self.engine.device, dtype=t.int32)
+        if self.n_agents != 3:
+            full = t.ones(tuple(a.shape[:3]) + (3,), dtype=t.int32, device=self.engine.device)
+            full[..., self._agent_idx] = a
+            a = full
+        res = self.engine.plan(a.contiguous(), reward_weights, gamma, info_weights)
+        if self.n_agents != 3:
+            res.action = res.action[:, self._agent_idx].contiguous()
+        return res
+
     def _take_state(self, src):
         """This env (built from src's constructor arguments, never stepped) becomes a copy of src: every env restored from a snapshot
         of src's, the seed and the host-side state copied.  src not reset yet: nothing to restore."""

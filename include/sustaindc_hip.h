@@ -127,7 +127,9 @@ typedef struct {
                               large: single steps above 5632 envs, the multi-step entry points above 4096; same
                               results to the bit).
                               Bit 13 (8192): TEST HOOK -- every 61st (env + launch) redoes its clip bounds' side from the
-                              history as if a bound had left its window (a path ~4e-8 of the env-steps take by themselves) */
+                              history as if a bound had left its window (a path ~4e-8 of the env-steps take by themselves).
+                              Bit 14 (16384): TEST HOOK -- sdc_plan's output block holds two steps, so that short horizons
+                              run its chunked path; read by sdc_plan alone, the step kernels never see the bit */
   int32_t reward_method[3]; /* reward function per agent slot (ls, dc, bat), utils/reward_creator.py:322-334:
                                SDC_REWARD_DEFAULT the slot's own default_*_reward, SDC_REWARD_FOOTPRINT
                                default_dc_reward = default_bat_reward, SDC_REWARD_CUSTOM custom_agent_reward (0),
@@ -216,7 +218,7 @@ const char* sdc_last_error(void);
  *   312  sdc_state_layout
  *   313  sdc_clone_envs
  *        (sdc_snapshot_row_bytes, sdc_snapshot_envs, sdc_restore_envs came later without a bump: new entry points, no layout or
- *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise) */
+ *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise; sdc_plan likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -446,6 +448,42 @@ int sdc_mark_envs(sdc_handle* h, const int32_t* envs, int n, int max_steps, void
                   const float* share_obs, void* stream);
 int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows, const int32_t* manifest, float* obs, float* share_obs,
                     void* stream);
+
+/* PLAN: score n_cand candidate action sequences of n_steps steps from the current state, pick the best one per env, and come back -- the
+ * closing step of a shooting model-predictive controller that uses the simulator as its own model.  One call, ordered on `stream`, no
+ * device synchronisation: the whole batch is marked (max_steps = n_steps) into a row buffer the handle owns; every candidate is rolled
+ * out through sdc_rollout's own path (the same kernel choice) into an output block the handle owns -- never into a caller's buffer --,
+ * scored by one launch of sdc_plan_score_kernel per rollout and rewound; sdc_plan_select_kernel then picks.  Afterwards the engine is
+ * where a rewind leaves it: state rewound, the header's re-centring stamps cleared, the closed loop's copy of obs restored, the caller's
+ * obs / share_obs rows (required, as for sdc_mark_envs / sdc_rewind_envs) holding what they held.  THE CALL USES UP THE ENVS' ONE LIVE
+ * MARK: a mark the caller took earlier is dead afterwards.
+ * actions [n_cand][n_steps][N][3] int32 (device); a slot on a built-in policy ignores its column, as in sdc_rollout.
+ * objective (host; NULL: weights 1, 1, 1, gamma 1, no columns).  With g_0 = 1, g_k = g_{k-1} * gamma (an fp64 table built on the host),
+ * r_k the step's three fp32 rewards and i_k its info row, all arithmetic in fp64 without fused multiply-adds, k = 0 .. n_steps - 1 in order:
+ *   returns[c][n][a] = 0.0, then += g_k * r_k[a]                                                (may be NULL)
+ *   s_k = (w[0] * r_k[0] + w[1] * r_k[1]) + w[2] * r_k[2], then for j = 0 .. n_cols - 1 in order += col_weight[j] * i_k[col[j]]
+ *   score[c][n] = 0.0, then += g_k * s_k
+ *   best[n] = the lowest c whose score is strictly greater than every earlier candidate's (candidate 0 unless a later one beats it with >)
+ *   best_action[n][:] = actions[best[n]][0][n][:]
+ * The output block is capped at 256 MiB (csrc/sdc_plan.hpp SDC_PLAN_SCRATCH_BYTES): where n_steps steps of outputs do not fit, a candidate is rolled out in chunks
+ * of as many steps as fit (at least one) and the score kernel carries its sums across them -- a rollout of K steps equals K single
+ * steps, so the results do not depend on the chunking.  debug_flags bit 14 (16384, TEST HOOK, read by this call alone): the block holds
+ * two steps.
+ * Refused (-2 and a message, nothing enqueued, the engine untouched): a null handle; n_cand < 1; n_steps outside
+ * [1, SDC_MARK_MAX_STEPS]; n_steps >= sdc_steps_to_episode_end() with auto_reset (the reset would kill the mark), > without; no
+ * sdc_reset yet; gamma outside (0, 1]; n_cols outside [0, SDC_PLAN_MAX_COLS] or a column outside [0, SDC_INFO_DIM); a null actions /
+ * score / best / best_action / obs / share_obs; obs / share_obs rows that are not dword-aligned; verify mode (debug_flags bit 0), which
+ * sdc_rollout refuses as well. */
+#define SDC_PLAN_MAX_COLS 8
+typedef struct {
+  double reward_weight[3];   /* w_ls, w_dc, w_bat */
+  double gamma;              /* discount per step, (0, 1] */
+  int32_t n_cols;            /* 0..SDC_PLAN_MAX_COLS info columns in the objective */
+  int32_t col[SDC_PLAN_MAX_COLS];     /* enum sdc_info_col, each in [0, SDC_INFO_DIM) */
+  double col_weight[SDC_PLAN_MAX_COLS];
+} sdc_plan_objective;
+int sdc_plan(sdc_handle* h, int n_cand, int n_steps, const int32_t* actions, const sdc_plan_objective* objective, double* returns,
+             double* score, int32_t* best, int32_t* best_action, float* obs, float* share_obs, void* stream);
 
 /* Per-kernel timing (measurement only; off by default).  enable = k > 0 samples every k-th sdc_step, 0 switches it
  * off.  In a sampled step one lane per workgroup of each kernel stamps the device's constant-rate wall clock at
