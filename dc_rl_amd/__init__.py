@@ -10,6 +10,7 @@ Public surface (mirrors the reference's names for this path):
   * `SdcEngine`                                    -- thin ctypes wrapper over the C-ABI (include/sustaindc_hip.h)
   * `RBCBatteryAgent`, `trim_and_respond_ctrl`, `ShootingMPCAgent` -- the rule-based baselines (utils/rbc_agents.py,
                                                       utils/trim_and_respond.py) and a shooting MPC over `SdcEngine.plan`
+  * `CEMMPCAgent`, `CEMResult`                     -- the cross-entropy-method MPC over `SdcEngine.plan_cem` and what that call returns
 
 The compute path is the HIP extension `csrc/libsustaindc_hip.so` (hand-written gfx950 kernels).  There is
 no CPU fallback: constructing an engine without the extension or without an MI355X raises.
@@ -31,6 +32,8 @@ _LAZY = {
     "make_dc_pyeplus_env": ("make_envs_pyenv", "make_dc_pyeplus_env"),
     "make_bat_fwd_env": ("make_envs_pyenv", "make_bat_fwd_env"),
     "ShootingMPCAgent": ("agents", "ShootingMPCAgent"),
+    "CEMMPCAgent": ("agents", "CEMMPCAgent"),
+    "CEMResult": ("engine", "CEMResult"),
     "RBCBatteryAgent": ("agents", "RBCBatteryAgent"),
     "trim_and_respond_ctrl": ("agents", "trim_and_respond_ctrl"),
 }

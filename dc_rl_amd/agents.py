@@ -150,3 +150,75 @@ class ShootingMPCAgent:
         cand[0] = nothing
         self.last, self.last_horizon = env.plan(cand, self.reward_weights, self.gamma, self.info_weights), K
         return self.last.action
+
+
+class CEMMPCAgent:
+    """Model-predictive control with the cross-entropy method, the simulator as its own model: at every decision run `n_iters`
+    iterations of "sample `n_candidates` sequences of `horizon` steps per env from a per-step, per-agent categorical distribution, score
+    them, refit the distribution to the `n_elite` best" on the device (SdcEngine.plan_cem / SustainDCVecEnv.plan_cem over sdc_plan_cem:
+    one call, one mark) and play the first action of the best sequence found.  alpha, p_min: the refit's smoothing and probability
+    floor; reward_weights, gamma, info_weights: the objective, as `plan` takes it.  Candidate 0 of every iteration is the incumbent --
+    at first the do-nothing sequence (ls 1, dc 1, bat 2) -- so on the model the chosen sequence never scores below doing nothing.
+    With `warm_start` the next decision starts from this one's result moved up by a step: best_seq[1:] with do-nothing appended, probs[1:]
+    with a uniform last step (torch ops on the device); both start afresh when the episode step goes backwards (a reset) or the horizon
+    grows.  The draws are keyed on (seed, the decision's number `draw`, which goes up by one per planned decision): two agents with one
+    seed on twin envs choose the same actions.  The horizon is shortened to what the episode has left (the planner does not look across
+    an episode's end); with fewer than two steps left the agent does nothing.  `last`: the latest CEMResult (None after a do-nothing
+    fallback), `last_horizon` the horizon it used."""
+
+    DO_NOTHING = (1, 1, 2)
+
+    def __init__(self, n_candidates: int = 8, n_elite: int = 2, n_iters: int = 3, horizon: int = 8, seed: int = 0, alpha: float = 0.0,
+                 p_min: float = 0.0, warm_start: bool = True, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None):
+        if n_candidates < 2 or not 1 <= n_elite <= n_candidates or n_iters < 1 or horizon < 1:
+            raise ValueError("CEMMPCAgent: n_candidates >= 2, 1 <= n_elite <= n_candidates, n_iters and horizon positive")
+        self.n_candidates, self.n_elite, self.n_iters, self.horizon = int(n_candidates), int(n_elite), int(n_iters), int(horizon)
+        self.seed, self.alpha, self.p_min, self.warm_start = int(seed), float(alpha), float(p_min), bool(warm_start)
+        self.reward_weights, self.gamma, self.info_weights = tuple(reward_weights), float(gamma), info_weights
+        self.draw = 0
+        self.last = None
+        self.last_horizon = 0
+        self._probs = self._best_seq = self._step = None
+
+    @classmethod
+    def shifted(cls, probs, best_seq, K):
+        """(probs [k, N, 3, 3], best_seq [k, N, 3]) of one decision -> the next decision's, K <= k steps: moved up by a step, the
+        last step uniform / do-nothing; new tensors on the same device"""
+        import torch
+        p = torch.full((K,) + tuple(probs.shape[1:]), 1.0 / 3.0, dtype=probs.dtype, device=probs.device)
+        b = torch.tensor(cls.DO_NOTHING, dtype=best_seq.dtype, device=best_seq.device).expand((K,) + tuple(best_seq.shape[1:])).contiguous()
+        p[:K - 1] = probs[1:K]
+        b[:K - 1] = best_seq[1:K]
+        return p, b
+
+    def _start(self, step, K):
+        """the (probs, best_seq) this decision starts from: the last decision's shifted, or (None, None) -- uniform and do-nothing --
+        without warm start, on the first decision, after the episode step went backwards, and when the horizon has grown"""
+        prev, self._step = self._step, step
+        if not self.warm_start or self._probs is None or prev is None or step <= prev or K > self._probs.shape[0]:
+            return None, None
+        return self.shifted(self._probs, self._best_seq, K)
+
+    def act(self, env):
+        """env: an SdcEngine or a SustainDCVecEnv -> int32 device tensor [N, 3] (the vec env: [N, n_agents], its agents' columns)."""
+        import torch
+        eng = getattr(env, "engine", env)
+        N = eng.n_envs
+        idx = list(getattr(env, "_agent_idx", (0, 1, 2)))
+        left = eng.steps_to_episode_end()
+        K = min(self.horizon, left - 1 if eng.config["auto_reset"] else left)
+        step = eng.config["episode_steps"] - left
+        if left < 2 or K < 1:
+            self.last, self.last_horizon = None, 0
+            self._probs = self._best_seq = None
+            self._step = step
+            nothing = torch.tensor([self.DO_NOTHING[i] for i in idx], dtype=torch.int32, device=eng.device)
+            return nothing.expand(N, len(idx)).contiguous()
+        probs, best_seq = self._start(step, K)
+        self.last = env.plan_cem(K, self.n_iters, self.n_candidates, self.n_elite, probs=probs, best_seq=best_seq, seed=self.seed,
+                                 draw=self.draw, alpha=self.alpha, p_min=self.p_min, reward_weights=self.reward_weights,
+                                 gamma=self.gamma, info_weights=self.info_weights)
+        self.draw = (self.draw + 1) & 0xFFFFFFFF
+        self.last_horizon = K
+        self._probs, self._best_seq = self.last.probs, self.last.best_seq
+        return self.last.action

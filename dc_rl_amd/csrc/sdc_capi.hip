@@ -21,6 +21,7 @@
 #include "sdc_clone.hpp"
 #include "sdc_snapshot.hpp"
 #include "sdc_mark.hpp"
+#include "sdc_cem.hpp"
 #include "sdc_plan.hpp"
 
 extern "C" __global__ void sdc_dynamics_kernel(SdcDev S, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
@@ -1949,94 +1950,213 @@ static int plan_grow(sdc_handle* h, unsigned char** buf, size_t* have, const siz
   return 0;
 }
 
-// Mark, then per candidate: roll out (in chunks of what the output block holds), score, rewind; then select.  Built from the entry
-// points themselves -- sdc_mark_envs, sdc_rollout, sdc_rewind_envs -- so the rollouts choose their kernel as sdc_rollout does and the
-// host mirrors are kept by the code that keeps them for every other caller.  Whatever those would refuse is refused here first.
-int sdc_plan(sdc_handle* h, int n_cand, int n_steps, const int32_t* actions, const sdc_plan_objective* objective, double* returns,
-             double* score, int32_t* best, int32_t* best_action, float* obs, float* share_obs, void* stream) {
-  if (!h) return fail_msg("sdc_plan: null handle");
-  if (n_cand < 1) return fail_msg("sdc_plan: n_cand = " + std::to_string(n_cand) + " must be positive");
+// What both plan calls refuse about the horizon, the engine and the objective, in sdc_plan's order (`arrays`: the caller's own null
+// check, reported at its place in that order); obj: the objective with the defaults filled in.  -> 0, or -2 with the message set
+static int plan_refused(const char* who, const sdc_handle* h, const int n_steps, const bool arrays, const float* obs, const float* share_obs,
+                        const sdc_plan_objective* objective, sdc_plan_objective& obj) {
+  const std::string w = std::string(who) + ": ";
   if (n_steps < 1 || n_steps > SDC_MARK_MAX_STEPS)
-    return fail_msg("sdc_plan: n_steps = " + std::to_string(n_steps) + " outside [1, " + std::to_string(SDC_MARK_MAX_STEPS) + "]");
-  if (!actions || !score || !best || !best_action || !obs || !share_obs) return fail_msg("sdc_plan: null array");
+    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " outside [1, " + std::to_string(SDC_MARK_MAX_STEPS) + "]");
+  if (!arrays || !obs || !share_obs) return fail_msg(w + "null array");
   if (((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(share_obs)) & 3u) != 0)
-    return fail_msg("sdc_plan: obs / share_obs rows not dword-aligned");
-  if (!h->started) return fail_msg("sdc_plan: sdc_reset must be called first");
-  if (h->cfg.debug_flags & 1) return fail_msg("sdc_plan: verify mode checks single steps (sdc_rollout refuses it as well)");
+    return fail_msg(w + "obs / share_obs rows not dword-aligned");
+  if (!h->started) return fail_msg(w + "sdc_reset must be called first");
+  if (h->cfg.debug_flags & 1) return fail_msg(w + "verify mode checks single steps (sdc_rollout refuses it as well)");
   if (h->cfg.auto_reset && n_steps >= h->steps_to_terminal)
-    return fail_msg("sdc_plan: n_steps = " + std::to_string(n_steps) + " would finish an episode (" + std::to_string(h->steps_to_terminal) +
+    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would finish an episode (" + std::to_string(h->steps_to_terminal) +
                     " steps left): the auto-reset kills the mark");
   if (n_steps > h->steps_to_terminal)
-    return fail_msg("sdc_plan: n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" +
+    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" +
                     std::to_string(h->steps_to_terminal) + " steps left)");
-  sdc_plan_objective obj;
   std::memset(&obj, 0, sizeof(obj));
   obj.reward_weight[0] = obj.reward_weight[1] = obj.reward_weight[2] = 1.0;
   obj.gamma = 1.0;
   if (objective) obj = *objective;
-  if (!(obj.gamma > 0.0 && obj.gamma <= 1.0)) return fail_msg("sdc_plan: gamma = " + std::to_string(obj.gamma) + " outside (0, 1]");
+  if (!(obj.gamma > 0.0 && obj.gamma <= 1.0)) return fail_msg(w + "gamma = " + std::to_string(obj.gamma) + " outside (0, 1]");
   if (obj.n_cols < 0 || obj.n_cols > SDC_PLAN_MAX_COLS)
-    return fail_msg("sdc_plan: n_cols = " + std::to_string(obj.n_cols) + " outside [0, " + std::to_string(SDC_PLAN_MAX_COLS) + "]");
+    return fail_msg(w + "n_cols = " + std::to_string(obj.n_cols) + " outside [0, " + std::to_string(SDC_PLAN_MAX_COLS) + "]");
   for (int j = 0; j < obj.n_cols; j++)
     if (obj.col[j] < 0 || obj.col[j] >= SDC_INFO_DIM)
-      return fail_msg("sdc_plan: info column " + std::to_string(obj.col[j]) + " (entry " + std::to_string(j) + ") outside [0, " +
+      return fail_msg(w + "info column " + std::to_string(obj.col[j]) + " (entry " + std::to_string(j) + ") outside [0, " +
                       std::to_string(SDC_INFO_DIM) + ")");
+  return 0;
+}
+
+// A plan call's horizon, the layout of the handle's output block for it, and the score kernel's plan but for the candidate's own arrays
+struct PlanRun {
+  int n_steps, chunk;
+  SdcPlanBlock B;
+  SdcPlanScore S;
+};
+
+// the handle's buffers, before anything is enqueued
+static int plan_prepare(sdc_handle* h, const int n_steps, const sdc_plan_objective& obj, PlanRun& R) {
+  const size_t N = (size_t)h->cfg.n_envs;
+  R.n_steps = n_steps;
+  R.chunk = sdc_plan_steps_fit(N, n_steps, SDC_PLAN_SCRATCH_BYTES);
+  if (h->cfg.debug_flags & SDC_PLAN_DEBUG_TWO_STEPS) R.chunk = std::min(R.chunk, 2);
+  R.B = sdc_plan_block(N, (size_t)R.chunk);
+  if (plan_grow(h, &h->plan_rows, &h->plan_rows_bytes, N * sdc_mark_row_bytes(n_steps))) return -1;
+  if (plan_grow(h, &h->plan_out, &h->plan_out_bytes, R.B.bytes)) return -1;
+  h->plan_manifest.resize(N * SDC_MARK_MANIFEST);
+  std::memset(&R.S, 0, sizeof(R.S));
+  R.S.n_envs = (int)N;
+  R.S.n_cols = obj.n_cols;
+  R.S.rew = reinterpret_cast<float*>(h->plan_out + R.B.rew);
+  R.S.info = reinterpret_cast<float*>(h->plan_out + R.B.info);
+  for (int a = 0; a < 3; a++) R.S.w[a] = obj.reward_weight[a];
+  for (int j = 0; j < obj.n_cols; j++) {
+    R.S.col[j] = obj.col[j];
+    R.S.col_weight[j] = obj.col_weight[j];
+  }
+  return 0;
+}
+
+// the discount table g_k = g_{k-1} * gamma into the pinned side of the plan's stage
+static void plan_discounts(double* const g, const int n_steps, const double gamma) {
+  g[0] = 1.0;
+  for (int k = 1; k < n_steps; k++) g[k] = g[k - 1] * gamma;
+}
+
+// Per candidate: roll out (in chunks of what the output block holds), score, rewind -- from the mark the caller has taken into
+// h->plan_rows.  Built from the entry points themselves -- sdc_rollout, sdc_rewind_envs -- so the rollouts choose their kernel as
+// sdc_rollout does and the host mirrors are kept by the code that keeps them for every other caller.
+static int plan_candidates(sdc_handle* h, PlanRun& R, const void* g_dev, const int n_cand, const int32_t* actions, double* returns,
+                           double* score, float* obs, float* share_obs, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const size_t N = (size_t)h->cfg.n_envs;
+  unsigned char* const out = h->plan_out;
+  float* const o_obs = reinterpret_cast<float*>(out + R.B.obs);
+  float* const o_share = reinterpret_cast<float*>(out + R.B.share_obs);
+  float* const o_rew = reinterpret_cast<float*>(out + R.B.rew);
+  float* const o_info = reinterpret_cast<float*>(out + R.B.info);
+  float* const o_final = reinterpret_cast<float*>(out + R.B.final_obs);
+  SdcPlanScore& S = R.S;
+  S.g = static_cast<const double*>(g_dev);
+  int rc = 0;
+  for (int c = 0; c < n_cand && rc == 0; c++) {
+    S.returns = returns ? returns + (size_t)c * N * 3 : nullptr;
+    S.score = score + (size_t)c * N;
+    for (int k0 = 0; k0 < R.n_steps && rc == 0; k0 += R.chunk) {
+      S.first_step = k0;
+      S.steps = std::min(R.chunk, R.n_steps - k0);
+      rc = sdc_rollout(h, S.steps, actions + ((size_t)c * (size_t)R.n_steps + (size_t)k0) * N * 3, o_obs, o_share, o_rew, out + R.B.done,
+                       o_info, o_final, nullptr, stream);
+      if (rc == 0) {
+        const hipError_t e = sdc_plan_score_launch(S, st);
+        if (e != hipSuccess) rc = fail("sdc_plan_score_kernel", e);
+      }
+    }
+    if (rc == 0) rc = sdc_rewind_envs(h, nullptr, (int)N, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
+  }
+  return rc;
+}
+
+// Mark, the candidates (plan_candidates), select.  Whatever the entry points underneath would refuse is refused here first.
+int sdc_plan(sdc_handle* h, int n_cand, int n_steps, const int32_t* actions, const sdc_plan_objective* objective, double* returns,
+             double* score, int32_t* best, int32_t* best_action, float* obs, float* share_obs, void* stream) {
+  if (!h) return fail_msg("sdc_plan: null handle");
+  if (n_cand < 1) return fail_msg("sdc_plan: n_cand = " + std::to_string(n_cand) + " must be positive");
+  sdc_plan_objective obj;
+  if (plan_refused("sdc_plan", h, n_steps, actions && score && best && best_action, obs, share_obs, objective, obj)) return -2;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t N = (size_t)h->cfg.n_envs;
-  // the handle's buffers, before anything is enqueued
-  int chunk = sdc_plan_steps_fit(N, n_steps, SDC_PLAN_SCRATCH_BYTES);
-  if (h->cfg.debug_flags & SDC_PLAN_DEBUG_TWO_STEPS) chunk = std::min(chunk, 2);
-  const SdcPlanBlock B = sdc_plan_block(N, (size_t)chunk);
-  if (plan_grow(h, &h->plan_rows, &h->plan_rows_bytes, N * sdc_mark_row_bytes(n_steps))) return -1;
-  if (plan_grow(h, &h->plan_out, &h->plan_out_bytes, B.bytes)) return -1;
-  h->plan_manifest.resize(N * SDC_MARK_MANIFEST);
-  unsigned char* const out = h->plan_out;
-  float* const o_obs = reinterpret_cast<float*>(out + B.obs);
-  float* const o_share = reinterpret_cast<float*>(out + B.share_obs);
-  float* const o_rew = reinterpret_cast<float*>(out + B.rew);
-  float* const o_info = reinterpret_cast<float*>(out + B.info);
-  float* const o_final = reinterpret_cast<float*>(out + B.final_obs);
-  // the discount table g_k = g_{k-1} * gamma, through the plan's stage; the slot stays in flight until the last kernel that reads it
+  PlanRun R;
+  if (plan_prepare(h, n_steps, obj, R)) return -1;
+  // the discount table through the plan's stage; the slot stays in flight until the last kernel that reads it
   void* pin = nullptr;
   if (stage_acquire(h, h->plan_stage, &pin)) return -1;
-  double* const g = static_cast<double*>(pin);
-  g[0] = 1.0;
-  for (int k = 1; k < n_steps; k++) g[k] = g[k - 1] * obj.gamma;
+  plan_discounts(static_cast<double*>(pin), n_steps, obj.gamma);
   int rc = 0;
   const int staged = stage_commit(h, h->plan_stage, (size_t)n_steps, st, [&](const void* g_dev) {
     rc = sdc_mark_envs(h, nullptr, (int)N, n_steps, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
-    SdcPlanScore S;
-    std::memset(&S, 0, sizeof(S));
-    S.n_envs = (int)N;
-    S.n_cols = obj.n_cols;
-    S.g = static_cast<const double*>(g_dev);
-    S.rew = o_rew;
-    S.info = o_info;
-    for (int a = 0; a < 3; a++) S.w[a] = obj.reward_weight[a];
-    for (int j = 0; j < obj.n_cols; j++) {
-      S.col[j] = obj.col[j];
-      S.col_weight[j] = obj.col_weight[j];
-    }
-    for (int c = 0; c < n_cand && rc == 0; c++) {
-      S.returns = returns ? returns + (size_t)c * N * 3 : nullptr;
-      S.score = score + (size_t)c * N;
-      for (int k0 = 0; k0 < n_steps && rc == 0; k0 += chunk) {
-        S.first_step = k0;
-        S.steps = std::min(chunk, n_steps - k0);
-        rc = sdc_rollout(h, S.steps, actions + ((size_t)c * (size_t)n_steps + (size_t)k0) * N * 3, o_obs, o_share, o_rew, out + B.done, o_info,
-                         o_final, nullptr, stream);
-        if (rc == 0) {
-          const hipError_t e = sdc_plan_score_launch(S, st);
-          if (e != hipSuccess) rc = fail("sdc_plan_score_kernel", e);
-        }
-      }
-      if (rc == 0) rc = sdc_rewind_envs(h, nullptr, (int)N, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
-    }
+    if (rc == 0) rc = plan_candidates(h, R, g_dev, n_cand, actions, returns, score, obs, share_obs, stream);
     if (rc == 0) {
       const SdcPlanSelect Q{(int)N, n_cand, n_steps, score, actions, best, best_action};
       const hipError_t e = sdc_plan_select_launch(Q, st);
       if (e != hipSuccess) rc = fail("sdc_plan_select_kernel", e);
+    }
+    return hipSuccess;
+  });
+  return rc ? rc : staged;
+}
+
+// ---- plan with the cross-entropy method (sdc_cem.hip) -------------------------------------------------------------------------------
+// The contract and the arithmetic: include/sustaindc_hip.h; the kernels' plans: sdc_cem.hpp.  One mark serves every rollout of every
+// iteration: a rewind keeps its mark alive.
+int sdc_plan_cem(sdc_handle* h, int n_steps, const sdc_cem_params* cem, const sdc_plan_objective* objective, double* probs,
+                 int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* cand, double* cand_score, float* obs,
+                 float* share_obs, void* stream) {
+  static const char* const who = "sdc_plan_cem";
+  if (!h) return fail_msg("sdc_plan_cem: null handle");
+  if (!cem) return fail_msg("sdc_plan_cem: null cem");
+  const sdc_cem_params c = *cem;
+  if (c.n_iters < 1) return fail_msg("sdc_plan_cem: n_iters = " + std::to_string(c.n_iters) + " must be positive");
+  if (c.iter0 < 0 || (long long)c.iter0 + c.n_iters > 65536)
+    return fail_msg("sdc_plan_cem: iter0 = " + std::to_string(c.iter0) + " with n_iters = " + std::to_string(c.n_iters) +
+                    " outside [0, 65536]");
+  if (c.n_cand < 2 || c.n_cand > SDC_CEM_MAX_CAND)
+    return fail_msg("sdc_plan_cem: n_cand = " + std::to_string(c.n_cand) + " outside [2, " + std::to_string(SDC_CEM_MAX_CAND) + "]");
+  if (c.n_elite < 1 || c.n_elite > c.n_cand)
+    return fail_msg("sdc_plan_cem: n_elite = " + std::to_string(c.n_elite) + " outside [1, n_cand = " + std::to_string(c.n_cand) + "]");
+  for (int a = 0; a < 3; a++)
+    if (c.fixed_action[a] < -1 || c.fixed_action[a] > 2)
+      return fail_msg("sdc_plan_cem: fixed_action[" + std::to_string(a) + "] = " + std::to_string(c.fixed_action[a]) + " outside [-1, 2]");
+  if (!(c.alpha >= 0.0 && c.alpha < 1.0)) return fail_msg("sdc_plan_cem: alpha = " + std::to_string(c.alpha) + " outside [0, 1)");
+  if (!(c.p_min >= 0.0 && c.p_min <= 1.0 / 3.0)) return fail_msg("sdc_plan_cem: p_min = " + std::to_string(c.p_min) + " outside [0, 1/3]");
+  sdc_plan_objective obj;
+  if (plan_refused(who, h, n_steps, probs && best_seq && best_score && best_action && cand && cand_score, obs, share_obs, objective, obj))
+    return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const size_t N = (size_t)h->cfg.n_envs;
+  PlanRun R;
+  if (plan_prepare(h, n_steps, obj, R)) return -1;
+  SdcCemSample Q;
+  std::memset(&Q, 0, sizeof(Q));
+  Q.n_envs = (int)N;
+  Q.n_cand = c.n_cand;
+  Q.n_steps = n_steps;
+  Q.env_base = h->cfg.env_index_base;
+  Q.draw = c.draw;
+  Q.key0 = (unsigned)c.seed;
+  Q.key1 = (unsigned)(c.seed >> 32);
+  Q.probs = probs;
+  Q.best_seq = best_seq;
+  Q.cand = cand;
+  SdcCemRefit F;
+  std::memset(&F, 0, sizeof(F));
+  F.n_envs = (int)N;
+  F.n_cand = c.n_cand;
+  F.n_steps = n_steps;
+  F.n_elite = c.n_elite;
+  F.alpha = c.alpha;
+  F.take = 1.0 - c.alpha;
+  F.p_min = c.p_min;
+  F.score = cand_score;
+  F.cand = cand;
+  F.probs = probs;
+  F.best_seq = best_seq;
+  F.best_action = best_action;
+  for (int a = 0; a < 3; a++) Q.fixed[a] = F.fixed[a] = c.fixed_action[a];
+  void* pin = nullptr;
+  if (stage_acquire(h, h->plan_stage, &pin)) return -1;
+  plan_discounts(static_cast<double*>(pin), n_steps, obj.gamma);
+  int rc = 0;
+  const int staged = stage_commit(h, h->plan_stage, (size_t)n_steps, st, [&](const void* g_dev) {
+    rc = sdc_mark_envs(h, nullptr, (int)N, n_steps, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
+    for (int i = 0; i < c.n_iters && rc == 0; i++) {
+      Q.c3 = ((unsigned)(c.iter0 + i) << 16) | SDC_CEM_STREAM;
+      hipError_t e = sdc_cem_sample_launch(Q, st);
+      if (e != hipSuccess) rc = fail("sdc_cem_sample_kernel", e);
+      if (rc == 0) rc = plan_candidates(h, R, g_dev, c.n_cand, cand, nullptr, cand_score, obs, share_obs, stream);
+      if (rc == 0) {
+        F.last = i == c.n_iters - 1;
+        F.best_score = best_score + (size_t)i * N;
+        e = sdc_cem_refit_launch(F, st);
+        if (e != hipSuccess) rc = fail("sdc_cem_refit_kernel", e);
+      }
     }
     return hipSuccess;
   });

@@ -105,6 +105,16 @@ class PlanResult:
         self.best, self.action, self.score, self.returns = best, action, score, returns
 
 
+class CEMResult:
+    """What SdcEngine.plan_cem returns, all on the engine's device: `action` int32 [N, 3] the first action of every env's best sequence
+    (SustainDCVecEnv.plan_cem: the agent subset's columns), `best_seq` int32 [K, N, 3] that sequence, `best_score` float64 [I, N] its
+    score after each iteration, `probs` float64 [K, N, 3, 3] the refitted distributions, `cand` int32 [M, K, N, 3] and `cand_score`
+    float64 [M, N] the last iteration's candidates and their scores."""
+
+    def __init__(self, action, best_seq, best_score, probs, cand, cand_score):
+        self.action, self.best_seq, self.best_score, self.probs, self.cand, self.cand_score = action, best_seq, best_score, probs, cand, cand_score
+
+
 def plan_objective(reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None) -> L.SdcPlanObjective:
     """plan's objective as the library's struct; ValueError for anything but three reward weights, an unknown info key, more than
     PLAN_MAX_COLS keys (gamma is the library's to refuse)."""
@@ -777,6 +787,80 @@ class SdcEngine:
             for x in (returns, score, best, action, actions):
                 x.record_stream(self._pinned_stream_obj)
         return PlanResult(best, action, score, returns)
+
+    def plan_cem(self, horizon: int, n_iters: int, n_candidates: int, n_elite: int, *, probs=None, best_seq=None, seed: int = 0,
+                 draw: int = 0, iter0: int = 0, alpha: float = 0.0, p_min: float = 0.0, fixed_action=(-1, -1, -1),
+                 reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None) -> CEMResult:
+        """Plan `horizon` = K steps ahead with the cross-entropy method and come back (sdc_plan_cem): one library call -- one mark, then
+        per iteration: sample M = n_candidates sequences on the device from every env's per-step, per-agent categorical distribution,
+        score them as `plan` does (the same objective arguments), refit the distribution to the E = n_elite best, keep the best
+        sequence found so far -- with no Python between the launches.  `probs` float64 device tensor [K, N, 3 agents, 3 actions]
+        (None: uniform) and `best_seq` int32 [K, N, 3], the incumbent (None: do nothing -- 1, 1, 2); tensors passed in are updated in
+        place and returned, and their entries are not checked (they live on the device).  Candidate 0 of every iteration is the
+        incumbent, so its score never falls and it wins ties.  The draws are the project's counter-based generator keyed on (seed, draw,
+        iteration index iter0 + i, candidate, step, the env's GLOBAL index): the same arguments give the same candidates, whatever the
+        batch is split into; a caller numbers its decisions with `draw`, and a call of I iterations equals I calls of one with iter0 =
+        0 .. I-1 that carry probs and best_seq.  Refit: p = normalise(max(alpha * p + (1 - alpha) * elite frequency, p_min)) (the
+        exact operations: include/sustaindc_hip.h).  fixed_action: per agent -1, or the value 0..2 every sampled candidate carries
+        for it (its probs stay as they are).  -> CEMResult(action [N, 3] = best_seq[0], best_seq, best_score [I, N], probs, cand
+        [M, K, N, 3], cand_score [M, N]).  The engine afterwards, and the price (the envs' one live mark), are `plan`'s.  ValueError,
+        with the engine untouched, for malformed tensors or objective and what the library refuses: plan's horizon, auto-reset and
+        verify-mode rules; n_iters < 1, iter0 < 0, iter0 + n_iters > 65536; M outside [2, CEM_MAX_CAND]; E outside [1, M]; a
+        fixed_action outside [-1, 2]; alpha outside [0, 1); p_min outside [0, 1/3]."""
+        t = self.torch
+        K, N, M, n_it = int(horizon), self.n_envs, int(n_candidates), int(n_iters)
+        fixed = [int(x) for x in fixed_action]
+        if len(fixed) != 3:
+            raise ValueError(f"plan_cem: fixed_action must be three integers (ls, dc, bat), got {len(fixed)}")
+        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(draw) < 1 << 32:
+            raise ValueError("plan_cem: seed must fit 64 bits and draw 32, both unsigned")
+
+        def given(x, name, dtype, shape):
+            if not (isinstance(x, t.Tensor) and x.dtype == dtype and x.is_cuda and x.is_contiguous() and tuple(x.shape) == shape):
+                raise ValueError(f"plan_cem: {name} must be a contiguous {str(dtype).split('.')[-1]} CUDA tensor of shape {shape}")
+            if x.device != self.device:
+                raise ValueError(f"plan_cem: {name} is on {x.device}, this engine runs on {self.device}")
+            return x
+
+        if probs is not None:
+            given(probs, "probs", t.float64, (K, N, 3, 3))
+        if best_seq is not None:
+            given(best_seq, "best_seq", t.int32, (K, N, 3))
+        obj = plan_objective(reward_weights, gamma, info_weights)
+        cem = L.SdcCemParams()
+        cem.n_iters, cem.iter0, cem.n_cand, cem.n_elite = n_it, int(iter0), M, int(n_elite)
+        cem.fixed_action[:] = fixed
+        cem.draw, cem.seed, cem.alpha, cem.p_min = int(draw), int(seed), float(alpha), float(p_min)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        sized = 1 <= K <= L.MARK_MAX_STEPS and 2 <= M <= L.CEM_MAX_CAND and n_it >= 1 and 0 <= int(iter0) <= L.CEM_MAX_ITERS - n_it
+        with t.cuda.device(self.device):
+            if sized:
+                if self._pinned_stream_obj is not None:
+                    # (probs and best_seq -- the defaults below, a caller's, CEMMPCAgent's shifted ones -- are filled by torch ops on
+                    #  torch's current stream and read by the sample kernel on the pinned one: order it behind them)
+                    self._pinned_stream_obj.wait_stream(t.cuda.current_stream(self.device))
+                if probs is None:
+                    probs = t.full((K, N, 3, 3), 1.0 / 3.0, dtype=t.float64, device=self.device)
+                if best_seq is None:
+                    best_seq = t.tensor([1, 1, 2], dtype=t.int32, device=self.device).expand(K, N, 3).contiguous()
+                best_score = t.empty((n_it, N), dtype=t.float64, device=self.device)
+                action = t.empty((N, 3), dtype=t.int32, device=self.device)
+                cand = t.empty((M, K, N, 3), dtype=t.int32, device=self.device)
+                cand_score = t.empty((M, N), dtype=t.float64, device=self.device)
+                arrays = (probs, best_seq, best_score, action, cand, cand_score)
+                rc = self.lib.sdc_plan_cem(self._h, K, C.byref(cem), C.byref(obj), *[p(x) for x in arrays], p(self.obs), p(self.share_obs),
+                                           self._stream())
+            else:      # (sizes no array can be given: the library words the refusal, and it looks at the sizes before the arrays)
+                arrays = ()
+                rc = self.lib.sdc_plan_cem(self._h, K, C.byref(cem), C.byref(obj), None, None, None, None, None, None, p(self.obs),
+                                           p(self.share_obs), self._stream())
+                if rc == 0:
+                    raise L.SdcError(f"plan_cem: sdc_plan_cem accepted K = {K}, M = {M}, I = {n_it}, iter0 = {int(iter0)} and no arrays")
+        self._refused(rc)
+        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse them before)
+            for x in arrays:
+                x.record_stream(self._pinned_stream_obj)
+        return CEMResult(action, best_seq, best_score, probs, cand, cand_score)
 
     def profile(self, every: int = 1):
         """Per-kernel HIP-event timing on the launch stream (measurement only): every k-th step, 0 = off."""

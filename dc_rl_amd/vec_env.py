@@ -507,6 +507,23 @@ class SustainDCVecEnv(ShareVecEnv):
             res.action = res.action[:, self._agent_idx].contiguous()
         return res
 
+    def plan_cem(self, horizon, n_iters, n_candidates, n_elite, *, probs=None, best_seq=None, fixed_action=None, **kw):
+        """Plan with the cross-entropy method and come back (SdcEngine.plan_cem, which documents the arguments; `probs` [K, num_envs,
+        3, 3] and `best_seq` [K, num_envs, 3] are the engine's, all three slots).  With an agent subset the other slots are not
+        planned for: every sampled candidate carries 1 in their columns (what `plan` fills them with; they are played on the device
+        and never read) and their probs stay as they are.  -> CEMResult whose `action` [num_envs, n_agents] holds the subset's
+        columns, ready for step().  The run goes on as if the call had not happened; the envs' live mark is used up.  ValueError for
+        what the engine refuses."""
+        if self._need_reset:
+            raise ValueError("plan_cem: call reset() first")
+        fixed = [-1, -1, -1] if fixed_action is None else [int(x) for x in fixed_action]
+        if self.n_agents != 3:
+            fixed = [fixed[i] if i in self._agent_idx else 1 for i in range(3)]
+        res = self.engine.plan_cem(horizon, n_iters, n_candidates, n_elite, probs=probs, best_seq=best_seq, fixed_action=fixed, **kw)
+        if self.n_agents != 3:
+            res.action = res.action[:, self._agent_idx].contiguous()
+        return res
+
     def _take_state(self, src):
         """This env (built from src's constructor arguments, never stepped) becomes a copy of src: every env restored from a snapshot
         of src's, the seed and the host-side state copied.  src not reset yet: nothing to restore."""

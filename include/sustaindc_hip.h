@@ -218,7 +218,7 @@ const char* sdc_last_error(void);
  *   312  sdc_state_layout
  *   313  sdc_clone_envs
  *        (sdc_snapshot_row_bytes, sdc_snapshot_envs, sdc_restore_envs came later without a bump: new entry points, no layout or
- *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise; sdc_plan likewise) */
+ *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise; sdc_plan and sdc_plan_cem likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -484,6 +484,53 @@ typedef struct {
 } sdc_plan_objective;
 int sdc_plan(sdc_handle* h, int n_cand, int n_steps, const int32_t* actions, const sdc_plan_objective* objective, double* returns,
              double* score, int32_t* best, int32_t* best_action, float* obs, float* share_obs, void* stream);
+
+/* PLAN WITH THE CROSS-ENTROPY METHOD: n_iters rounds of "sample n_cand candidate sequences from a per-env, per-step, per-agent
+ * categorical distribution, score them as sdc_plan does, refit the distribution to the n_elite best and keep the best sequence found so
+ * far" -- one call, ordered on `stream`, no device synchronisation, ONE mark of the whole batch (max_steps = n_steps) for all n_iters *
+ * n_cand rollouts.  Per iteration it = iter0 .. iter0 + n_iters - 1: sdc_cem_sample_kernel; sdc_plan's own per-candidate loop (rollout
+ * into the handle's output block, sdc_plan_score_kernel, rewind; the objective, its arithmetic and the chunking are sdc_plan's);
+ * sdc_cem_refit_kernel.  Afterwards the engine is where sdc_plan leaves it (rewound, re-centring stamps cleared, the caller's output
+ * arrays never written), and THE CALL USES UP THE ENVS' ONE LIVE MARK.  All arrays are the device's; K = n_steps, M = n_cand,
+ * E = n_elite, I = n_iters, N the batch:
+ *   probs       in/out [K][N][3 agents][3 actions] fp64     best_seq    in/out [K][N][3] int32: the incumbent on entry, the best
+ *   best_score  out [I][N]: the incumbent's score after each iteration        sequence found on return
+ *   best_action out [N][3] = best_seq[0]                    cand        work/out [M][K][N][3]: the last iteration's candidates
+ *   cand_score  work/out [M][N]: their scores
+ * SAMPLE.  Candidate 0 is a copy of best_seq (elitism: the incumbent's score never falls from one iteration to the next, and it wins
+ * ties).  For m = 1 .. M-1, step k, env n: one philox4x32_10 block with counter (m * K + k, env_index_base + n, draw, (it << 16) |
+ * 0xCE3D) and key (seed's low word, seed's high word); words x, y, z serve agents ls, dc, bat, w is unused.  For agent a with
+ * probabilities p0, p1, p2:  u = (double)word * 2^-32;  action = (u >= p0) + (u >= (p0 + p1)) -- one fp64 addition; p2 is never read.
+ * fixed_action[a] >= 0 replaces the draw of agent a in candidates 1 .. M-1.
+ * REFIT, per env.  rank(c) = the number of c' with score[c'] > score[c], or score[c'] == score[c] and c' < c; c is elite iff rank(c) <
+ * E; best = the candidate of rank 0.  best_seq[:][n] = candidate best's actions (best = 0: unchanged), best_score[it - iter0][n] =
+ * score[best][n], and after the last iteration best_action[n] = best_seq[0][n].  For every step k and agent a without a fixed action,
+ * with cnt[j] the number of elites whose action is j, all fp64, no fused multiply-adds, an IEEE division:
+ *   t_j = (double)cnt[j] / (double)E;  q_j = alpha * p_j + take * t_j  (take = 1.0 - alpha, computed once on the host);
+ *   q_j = max(q_j, p_min);  s = (q0 + q1) + q2;  p_j = q_j / s
+ * An agent with a fixed action keeps its probs.
+ * THE ENTRIES OF probs AND best_seq ARE NOT VALIDATED: they live on the device.  Probabilities that are not a distribution give
+ * whatever the thresholds above give; an action outside 0..2 is played as sdc_rollout plays it.  A NaN score (a non-finite objective) is
+ * outranked by nothing and outranks nothing: every such candidate has rank 0 and is elite, so the elites may then be more than E while
+ * the divisor stays E; best is the lowest-numbered candidate of rank 0, so the result is still the same from run to run.
+ * Refused (-2 and a message, nothing enqueued, the engine untouched): everything sdc_plan refuses, with the same horizon, auto-reset and
+ * verify-mode rules; a null cem; n_iters < 1, iter0 < 0, iter0 + n_iters > 65536; n_cand outside [2, SDC_CEM_MAX_CAND]; n_elite outside
+ * [1, n_cand]; a fixed_action outside [-1, 2]; alpha outside [0, 1); p_min outside [0, 1/3]; a null array. */
+#define SDC_CEM_MAX_CAND 64
+typedef struct {
+  int32_t n_iters;          /* I >= 1 */
+  int32_t iter0;            /* index of this call's first iteration, >= 0, iter0 + I <= 65536 */
+  int32_t n_cand;           /* M in [2, SDC_CEM_MAX_CAND] */
+  int32_t n_elite;          /* E in [1, M] */
+  int32_t fixed_action[3];  /* per agent: -1 = sampled, 0..2 = every sampled candidate carries this value */
+  uint32_t draw;            /* the caller's decision counter: goes into the generator's counter */
+  uint64_t seed;
+  double alpha;             /* [0, 1): weight of the old distribution in the refit */
+  double p_min;             /* [0, 1/3]: floor of every probability before renormalising */
+} sdc_cem_params;
+int sdc_plan_cem(sdc_handle* h, int n_steps, const sdc_cem_params* cem, const sdc_plan_objective* objective, double* probs,
+                 int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* cand, double* cand_score, float* obs,
+                 float* share_obs, void* stream);
 
 /* Per-kernel timing (measurement only; off by default).  enable = k > 0 samples every k-th sdc_step, 0 switches it
  * off.  In a sampled step one lane per workgroup of each kernel stamps the device's constant-rate wall clock at

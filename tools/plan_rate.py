@@ -3,7 +3,12 @@ same rollouts and rewinds driven from Python, the rewards summed with torch ops)
 process, at 4 096 and at 32 768 envs (672-step episodes).  Device events around each call, one warm-up call, then the median, min and
 max of nine calls; also plan with three info columns in the objective (the score kernel's LDS route).  One JSON line per size.  Run it
 under `rocprofv3 --kernel-trace --stats -- python tools/plan_rate.py` for sdc_plan_score_kernel's and sdc_plan_select_kernel's own
-time."""
+time.
+
+--cem: SdcEngine.plan_cem (one sdc_plan_cem call) at I = 3 iterations, M = 8 candidates, E = 2 elites, K = 8 steps beside the same
+planner driven from Python -- per iteration torch sampling from the distributions, `plan`, topk, the refit as torch ops -- and beside
+3 x the time of one `plan` of the same M and K; the same process, sizes and timing.  Under rocprofv3 as above for
+sdc_cem_sample_kernel's and sdc_cem_refit_kernel's own time."""
 import json
 import os
 import sys
@@ -17,10 +22,60 @@ from tools.mark_rate import timed3
 
 REPS = 9
 M, K = 4, 8
+CEM_I, CEM_M, CEM_E, CEM_K = 3, 8, 2, 8
 COLUMNS = {"bat_CO2_footprint": -1e-3, "dc_water_usage": -1.0, "ls_tasks_dropped": -1.0}
 
 
+def cem_in_python(eng, probs, best_seq, I, M, E):
+    """the loop plan_cem replaces: per iteration sample from probs [K, N, 3, 3], score with `plan`, keep the best, refit to the elites"""
+    K, N = probs.shape[0], probs.shape[1]
+    ar = torch.arange(N, device=probs.device)
+    for _ in range(I):
+        draws = torch.multinomial(probs.reshape(-1, 3), M - 1, replacement=True)      # [K N 3, M-1]
+        cand = torch.empty((M, K, N, 3), dtype=torch.int32, device=probs.device)
+        cand[0] = best_seq
+        cand[1:] = draws.reshape(K, N, 3, M - 1).permute(3, 0, 1, 2)
+        score = eng.plan(cand).score
+        elite = score.topk(E, dim=0).indices      # [E, N]
+        best_seq = cand[elite[0], :, ar].permute(1, 0, 2).contiguous()
+        picked = cand[elite, :, ar[None]].long()      # [E, N, K, 3]
+        cnt = torch.zeros((N, K, 3, 3), dtype=torch.float64, device=probs.device)
+        cnt.scatter_add_(3, picked.permute(1, 2, 3, 0), torch.ones((N, K, 3, E), dtype=torch.float64, device=probs.device))
+        probs = (cnt / E).permute(1, 0, 2, 3).contiguous()
+    return probs, best_seq
+
+
+def main_cem():
+    I, M, E, K = CEM_I, CEM_M, CEM_E, CEM_K
+    for N in (4096, 32768):
+        eng, _, _ = bench.build_engine(N, EP, 0, seed=99, debug_flags=0)
+        eng.reset()
+        g = torch.Generator(device="cpu").manual_seed(N)
+        acts = torch.randint(0, 3, (8, N, 3), dtype=torch.int32, generator=g).cuda()
+        for t in range(40):
+            eng.step(acts[t % 8])
+        cand = torch.randint(0, 3, (M, K, N, 3), dtype=torch.int32, generator=g).cuda()
+        uniform = torch.full((K, N, 3, 3), 1.0 / 3.0, dtype=torch.float64, device=cand.device)
+        nothing = torch.tensor([1, 1, 2], dtype=torch.int32, device=cand.device).expand(K, N, 3).contiguous()
+        res = eng.plan_cem(K, I, M, E)      # (warm: the handle's buffers are allocated)
+        eng.plan(cand)
+        cem_in_python(eng, uniform, nothing, I, M, E)
+        torch.cuda.synchronize()
+        improved = int((res.best_score[-1] > res.best_score[0]).sum())
+        cem = timed3(lambda: eng.plan_cem(K, I, M, E), REPS)
+        loop = timed3(lambda: cem_in_python(eng, uniform, nothing, I, M, E), REPS)
+        plan = timed3(lambda: eng.plan(cand), REPS)
+        eng.step(acts[0])
+        print(json.dumps(dict(what="plan_cem", n_envs=N, iterations=I, candidates=M, elites=E, steps=K, plan_cem_ms=cem[0],
+                              plan_cem_ms_range=cem[1:], python_loop_ms=loop[0], python_loop_ms_range=loop[1:],
+                              three_plans_ms=3 * plan[0], three_plans_ms_range=[3 * plan[1], 3 * plan[2]],
+                              envs_improved_after_iteration_0=improved, step_kernel_after=eng.last_step_kernel())))
+        eng.close()
+
+
 def main():
+    if "--cem" in sys.argv[1:]:
+        return main_cem()
     for N in (4096, 32768):
         eng, _, _ = bench.build_engine(N, EP, 0, seed=99, debug_flags=0)
         eng.reset()
