@@ -23,11 +23,12 @@ ABI_VERSION = 313  # include/sustaindc_hip.h SDC_ABI_VERSION: the struct layouts
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
-           "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip"]
+           "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_stats.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
 PLAN_DEBUG_TWO_STEPS = 16384   # sdc_config.debug_flags bit 14 (test hook): sdc_plan's output block holds two steps
+STATS_FIELDS = 4        # include/sustaindc_hip.h SDC_STATS_FIELDS: sum, min, max, count of positive values (enum sdc_stat_field)
 CEM_MAX_CAND = 64       # include/sustaindc_hip.h SDC_CEM_MAX_CAND: candidates per iteration of sdc_plan_cem
 CEM_MAX_ITERS = 65536   # ... and its iteration indices: iter0 + n_iters <= this (the index is 16 bits of the generator's counter)
 SNAPSHOT_MANIFEST = 9   # include/sustaindc_hip.h SDC_SNAPSHOT_MANIFEST: int32 entries per snapshot row's manifest (enum sdc_snapshot_manifest)
@@ -159,7 +160,7 @@ EXPORTS = [
     "sdc_hist_stride", "sdc_queue_stride", "sdc_profile_enable", "sdc_profile_read",
     "sdc_set_actor", "sdc_rollout_actor", "sdc_clone_envs",
     "sdc_snapshot_row_bytes", "sdc_snapshot_envs", "sdc_restore_envs",
-    "sdc_mark_row_bytes", "sdc_mark_envs", "sdc_rewind_envs", "sdc_plan", "sdc_plan_cem",
+    "sdc_mark_row_bytes", "sdc_mark_envs", "sdc_rewind_envs", "sdc_plan", "sdc_plan_cem", "sdc_rollout_stats",
 ]
 
 
@@ -318,6 +319,7 @@ def load():
     L.sdc_rewind_envs.argtypes = [vp, ip, C.c_int, vp, ip, fp, fp, vp]
     L.sdc_plan.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(SdcPlanObjective), vp, vp, vp, vp, fp, fp, vp]
     L.sdc_plan_cem.argtypes = [vp, C.c_int, C.POINTER(SdcCemParams), C.POINTER(SdcPlanObjective), vp, vp, vp, vp, vp, vp, fp, fp, vp]
+    L.sdc_rollout_stats.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

@@ -23,6 +23,7 @@
 #include "sdc_mark.hpp"
 #include "sdc_cem.hpp"
 #include "sdc_plan.hpp"
+#include "sdc_stats.hpp"
 
 extern "C" __global__ void sdc_dynamics_kernel(SdcDev S, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
                                                unsigned char* done, float* info, float* final_obs, float* rew);
@@ -2018,35 +2019,44 @@ static void plan_discounts(double* const g, const int n_steps, const double gamm
   for (int k = 1; k < n_steps; k++) g[k] = g[k - 1] * gamma;
 }
 
-// Per candidate: roll out (in chunks of what the output block holds), score, rewind -- from the mark the caller has taken into
-// h->plan_rows.  Built from the entry points themselves -- sdc_rollout, sdc_rewind_envs -- so the rollouts choose their kernel as
-// sdc_rollout does and the host mirrors are kept by the code that keeps them for every other caller.
+// n_steps steps rolled out into the handle's output block (layout B, of `chunk` steps) in chunks, per_chunk(first step, steps) behind each
+// chunk's rollout.  Built from the entry point itself -- sdc_rollout -- so the rollouts choose their kernel as sdc_rollout does and the
+// host mirrors are kept by the code that keeps them for every other caller.  actions [n_steps][N][3], or nullptr (built-in policies)
+extern "C++" {
+template <class PerChunk>
+static int rollout_chunks(sdc_handle* h, const SdcPlanBlock& B, const int n_steps, const int chunk, const int32_t* actions, void* stream,
+                          PerChunk&& per_chunk) {
+  const size_t N = (size_t)h->cfg.n_envs;
+  unsigned char* const out = h->plan_out;
+  int rc = 0;
+  for (int k0 = 0; k0 < n_steps && rc == 0; k0 += chunk) {
+    const int steps = std::min(chunk, n_steps - k0);
+    rc = sdc_rollout(h, steps, actions ? actions + (size_t)k0 * N * 3 : nullptr, reinterpret_cast<float*>(out + B.obs),
+                     reinterpret_cast<float*>(out + B.share_obs), reinterpret_cast<float*>(out + B.rew), out + B.done,
+                     reinterpret_cast<float*>(out + B.info), reinterpret_cast<float*>(out + B.final_obs), nullptr, stream);
+    if (rc == 0) rc = per_chunk(k0, steps);
+  }
+  return rc;
+}
+}  // extern "C++"
+
+// Per candidate: roll out (rollout_chunks), score each chunk, rewind -- from the mark the caller has taken into h->plan_rows.
 static int plan_candidates(sdc_handle* h, PlanRun& R, const void* g_dev, const int n_cand, const int32_t* actions, double* returns,
                            double* score, float* obs, float* share_obs, void* stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t N = (size_t)h->cfg.n_envs;
-  unsigned char* const out = h->plan_out;
-  float* const o_obs = reinterpret_cast<float*>(out + R.B.obs);
-  float* const o_share = reinterpret_cast<float*>(out + R.B.share_obs);
-  float* const o_rew = reinterpret_cast<float*>(out + R.B.rew);
-  float* const o_info = reinterpret_cast<float*>(out + R.B.info);
-  float* const o_final = reinterpret_cast<float*>(out + R.B.final_obs);
   SdcPlanScore& S = R.S;
   S.g = static_cast<const double*>(g_dev);
   int rc = 0;
   for (int c = 0; c < n_cand && rc == 0; c++) {
     S.returns = returns ? returns + (size_t)c * N * 3 : nullptr;
     S.score = score + (size_t)c * N;
-    for (int k0 = 0; k0 < R.n_steps && rc == 0; k0 += R.chunk) {
+    rc = rollout_chunks(h, R.B, R.n_steps, R.chunk, actions + (size_t)c * (size_t)R.n_steps * N * 3, stream, [&](const int k0, const int steps) {
       S.first_step = k0;
-      S.steps = std::min(R.chunk, R.n_steps - k0);
-      rc = sdc_rollout(h, S.steps, actions + ((size_t)c * (size_t)R.n_steps + (size_t)k0) * N * 3, o_obs, o_share, o_rew, out + R.B.done,
-                       o_info, o_final, nullptr, stream);
-      if (rc == 0) {
-        const hipError_t e = sdc_plan_score_launch(S, st);
-        if (e != hipSuccess) rc = fail("sdc_plan_score_kernel", e);
-      }
-    }
+      S.steps = steps;
+      const hipError_t e = sdc_plan_score_launch(S, st);
+      return e != hipSuccess ? fail("sdc_plan_score_kernel", e) : 0;
+    });
     if (rc == 0) rc = sdc_rewind_envs(h, nullptr, (int)N, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
   }
   return rc;
@@ -2161,6 +2171,71 @@ int sdc_plan_cem(sdc_handle* h, int n_steps, const sdc_cem_params* cem, const sd
     return hipSuccess;
   });
   return rc ? rc : staged;
+}
+
+// ---- episode statistics (sdc_stats.hip) ---------------------------------------------------------------------------------------------
+// The contract and the arithmetic: include/sustaindc_hip.h; the kernels' plans and the lane mapping: sdc_stats.hpp.  The rollouts go
+// into the plan calls' output block (rollout_chunks); nothing is marked or rewound.
+int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int accumulate, double* stats, double* returns,
+                      int32_t* counts, float* obs, float* share_obs, float* rew, uint8_t* done, float* info, float* final_obs,
+                      void* stream) {
+  static const std::string w = "sdc_rollout_stats: ";
+  if (!h) return fail_msg(w + "null handle");
+  if (n_steps < 1) return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " must be positive");
+  if (!stats || !returns || !counts || !obs || !share_obs) return fail_msg(w + "null array (stats, returns, counts, obs and share_obs are required)");
+  const auto addr = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+  if (((addr(stats) | addr(returns)) & 15u) != 0) return fail_msg(w + "stats / returns not 16-byte aligned");
+  if (((addr(counts) | addr(obs) | addr(share_obs) | addr(rew) | addr(info) | addr(final_obs)) & 3u) != 0)
+    return fail_msg(w + "counts / obs / share_obs / rew / info / final_obs rows not dword-aligned");
+  if (accumulate != 0 && accumulate != 1) return fail_msg(w + "accumulate = " + std::to_string(accumulate) + " outside {0, 1}");
+  if (!h->started) return fail_msg(w + "sdc_reset must be called first");
+  if (h->cfg.debug_flags & 1) return fail_msg(w + "verify mode checks single steps (sdc_rollout refuses it as well)");
+  if (!actions && !all_policies(h)) return fail_msg(w + "actions may only be NULL when every agent slot has a policy");
+  if (n_steps > h->steps_to_terminal)
+    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" +
+                    std::to_string(h->steps_to_terminal) + " steps left)");
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const size_t N = (size_t)h->cfg.n_envs;
+  int chunk = sdc_plan_steps_fit(N, n_steps, SDC_PLAN_SCRATCH_BYTES);
+  if (h->cfg.debug_flags & SDC_PLAN_DEBUG_TWO_STEPS) chunk = std::min(chunk, 2);
+  const SdcPlanBlock B = sdc_plan_block(N, (size_t)chunk);
+  if (plan_grow(h, &h->plan_out, &h->plan_out_bytes, B.bytes)) return -1;
+  unsigned char* const out = h->plan_out;
+  SdcStatsReduce S;
+  std::memset(&S, 0, sizeof(S));
+  S.n_envs = (int)N;
+  S.rew = reinterpret_cast<const float*>(out + B.rew);
+  S.info = reinterpret_cast<const float*>(out + B.info);
+  S.stats = stats;
+  S.returns = returns;
+  S.counts = counts;
+  int last_steps = 0;
+  const int rc = rollout_chunks(h, B, n_steps, chunk, actions, stream, [&](const int k0, const int steps) {
+    S.steps = last_steps = steps;
+    S.init = (k0 == 0 && accumulate == 0) ? 1 : 0;
+    const hipError_t e = sdc_stats_reduce_launch(S, st);
+    return e != hipSuccess ? fail("sdc_stats_reduce_kernel", e) : 0;
+  });
+  if (rc) return rc;
+  const size_t last = (size_t)(last_steps - 1) * N;      // the LAST step's slices of the last chunk
+  SdcStatsLast Q;
+  std::memset(&Q, 0, sizeof(Q));
+  Q.n_envs = (int)N;
+  Q.obs = reinterpret_cast<const float*>(out + B.obs) + last * SDC_OBS_OUT;
+  Q.share_obs = reinterpret_cast<const float*>(out + B.share_obs) + last * SDC_SHARE_OBS_DIM;
+  Q.rew = reinterpret_cast<const float*>(out + B.rew) + last * SDC_N_AGENTS;
+  Q.info = reinterpret_cast<const float*>(out + B.info) + last * SDC_INFO_DIM;
+  Q.done = out + B.done + last;
+  Q.final_obs = reinterpret_cast<const float*>(out + B.final_obs);
+  Q.o_obs = obs;
+  Q.o_share_obs = share_obs;
+  Q.o_rew = rew;
+  Q.o_info = info;
+  Q.o_done = done;
+  Q.o_final_obs = final_obs;
+  const hipError_t e = sdc_stats_last_launch(Q, st);
+  return e != hipSuccess ? fail("sdc_stats_last_kernel", e) : 0;
 }
 
 }  // extern "C"

@@ -115,6 +115,75 @@ class CEMResult:
         self.action, self.best_seq, self.best_score, self.probs, self.cand, self.cand_score = action, best_seq, best_score, probs, cand, cand_score
 
 
+# EpisodeStats.summary: the reference logger's quantities (harl/envs/sustaindc/sustaindc_logger.py), name -> (info column, kind)
+_SUMMARY = {
+    "average_net_energy": ("bat_total_energy_with_battery_KWh", "mean"),      # sustaindc_logger.py:87, :131
+    "average_ite_power": ("dc_ITE_total_power_kW", "mean"),                   # :93, :132
+    "average_ct_power": ("dc_CT_total_power_kW", "mean"),                     # :94, :133
+    "average_chiller_power": ("dc_Compressor_total_power_kW", "mean"),        # :95, :134
+    "average_hvac_power": ("dc_HVAC_total_power_kW", "mean"),                 # :96, :135
+    "average_CO2_footprint": ("bat_CO2_footprint", "mean"),                   # :88, :137
+    "total_water_usage": ("dc_water_usage", "total"),                         # :89, :138
+    "total_tasks_in_queue": ("ls_tasks_in_queue", "total"),                   # :91, :140
+    "total_tasks_dropped": ("ls_tasks_dropped", "total"),                     # :92, :141
+    "average_hvac_power_on_use": ("dc_HVAC_total_power_kW", "positive"),      # :98-99, :153
+}
+
+
+class EpisodeStats:
+    """What SdcEngine.rollout_stats / evaluate return: per-env statistics of the steps taken, on the engine's device (sdc_rollout_stats,
+    include/sustaindc_hip.h).  `stats` float64 [4, N, 44] -- `sum`, `min`, `max`, `n_pos` (the number of steps with a positive value) are
+    its [N, 44] views, one row per env and one column per info key (dc_rl_amd._lib.INFO_COLS) --, `returns` float64 [N, 3] the three
+    agents' summed rewards, `counts` int32 [N, 2] with the views `steps` [N] (steps reduced) and `fault` [N] (the OR of the steps'
+    info[fault] bits).  From `evaluate` every tensor has a leading [E] dimension, one entry per episode."""
+
+    def __init__(self, stats, returns, counts):
+        self.stats, self.returns, self.counts = stats, returns, counts
+
+    sum = property(lambda self: self.stats.select(-3, 0))
+    min = property(lambda self: self.stats.select(-3, 1))
+    max = property(lambda self: self.stats.select(-3, 2))
+    n_pos = property(lambda self: self.stats.select(-3, 3))
+    steps = property(lambda self: self.counts[..., 0])
+    fault = property(lambda self: self.counts[..., 1])
+
+    def col(self, name: str, field: str = "sum"):
+        """The [N] column of `field` ("sum", "min", "max", "n_pos") for the reference's info key `name`; ValueError for an unknown one."""
+        if name not in L.INFO_IDX:
+            raise ValueError(f"col: {name!r} is not an info column (dc_rl_amd._lib.INFO_COLS)")
+        if field not in ("sum", "min", "max", "n_pos"):
+            raise ValueError(f"col: field {field!r} is not one of sum, min, max, n_pos")
+        return getattr(self, field)[..., L.INFO_IDX[name]]
+
+    def summary(self) -> dict:
+        """The reference logger's episode quantities (harl/envs/sustaindc/sustaindc_logger.py:126-149) on the host, fp64:
+        {"per_env": {name: array [N] (or [E, N])}, "batch": {name: float (or array [E])}, "steps": ..., "fault": ...}.  Per env the
+        logger's formulas with the env's own sums and step count; over the batch with the sums over the envs and the sum of their step
+        counts, which is what the logger accumulates (:86-101: one `step_count` per env and step).
+          average_net_energy, average_ite_power, average_ct_power, average_chiller_power, average_hvac_power, average_CO2_footprint
+              = sum / steps (:131-137);   total_water_usage, total_tasks_in_queue, total_tasks_dropped = sum (:138-141);
+          average_hvac_power_on_use = sum / n_pos of dc_HVAC_total_power_kW: the mean over the steps where it was positive (:98-99,
+              :153; the power is never negative, so the other steps add nothing to the sum); NaN where it never was.
+        A quantity of an env that took no step is 0, as in the logger (:142-150)."""
+        s, n = self.sum.cpu().numpy(), self.n_pos.cpu().numpy()
+        steps = self.steps.cpu().numpy().astype(np.float64)
+        tot_steps = steps.sum(axis=-1)
+        per_env, batch = {}, {}
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for name, (key, kind) in _SUMMARY.items():
+                c = L.INFO_IDX[key]
+                x, bx = s[..., c], s[..., c].sum(axis=-1)
+                if kind == "mean":
+                    per_env[name] = np.where(steps > 0, x / steps, 0.0)
+                    batch[name] = np.where(tot_steps > 0, bx / tot_steps, 0.0)
+                elif kind == "total":
+                    per_env[name], batch[name] = x, bx
+                else:
+                    per_env[name], batch[name] = x / n[..., c], bx / n[..., c].sum(axis=-1)
+        batch = {k: (float(v) if np.ndim(v) == 0 else np.asarray(v)) for k, v in batch.items()}
+        return {"per_env": per_env, "batch": batch, "steps": self.steps.cpu().numpy(), "fault": self.fault.cpu().numpy()}
+
+
 def plan_objective(reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None) -> L.SdcPlanObjective:
     """plan's objective as the library's struct; ValueError for anything but three reward weights, an unknown info key, more than
     PLAN_MAX_COLS keys (gamma is the library's to refuse)."""
@@ -861,6 +930,78 @@ class SdcEngine:
             for x in arrays:
                 x.record_stream(self._pinned_stream_obj)
         return CEMResult(action, best_seq, best_score, probs, cand, cand_score)
+
+    def rollout_stats(self, actions=None, n_steps: int = None, into: Optional[EpisodeStats] = None) -> EpisodeStats:
+        """K env-steps as `rollout` takes them, reduced on the device to per-env statistics (sdc_rollout_stats): the steps' outputs go
+        into a block the engine's library owns, in chunks, and one small kernel per chunk folds them into an EpisodeStats -- sum, min,
+        max and count of positive values of all 44 info columns, the three agents' returns, the step count, the OR of the fault bits --
+        so an episode of a large batch never materialises its 617 B per env-step.  fp64, in step order (the exact operations:
+        include/sustaindc_hip.h).  actions: int32 device tensor [K, N, 3], or None with n_steps when every slot has a built-in
+        policy; K may reach the episode's end (steps_to_episode_end()), where the auto-reset happens as in `rollout`.  `into`: an
+        EpisodeStats of this engine to continue (its tensors are updated in place and it is returned); calls split anywhere give the
+        bits of one call.  The engine moves; its single-step views (obs, share_obs, rew, done, info, final_obs) follow the last step,
+        as after `rollout`.  ValueError, with the engine untouched, for malformed arguments and what the library refuses: K < 1,
+        K > steps_to_episode_end(), no reset() yet, verify mode (debug_flags bit 0)."""
+        t = self.torch
+        if actions is None:
+            if n_steps is None or any(p == 0 for p in self.policy):
+                raise ValueError("rollout_stats: actions=None needs n_steps and a built-in policy on every agent slot")
+            K = int(n_steps)
+        else:
+            if not (isinstance(actions, t.Tensor) and actions.dtype == t.int32 and actions.is_cuda and
+                    actions.is_contiguous() and actions.dim() == 3 and tuple(actions.shape[1:]) == (self.n_envs, 3)):
+                raise ValueError("rollout_stats: actions must be a contiguous int32 CUDA tensor of shape (K, n_envs, 3)")
+            if actions.device != self.device:
+                raise ValueError(f"rollout_stats: actions are on {actions.device}, this engine runs on {self.device}")
+            K = int(actions.shape[0])
+            if n_steps is not None and int(n_steps) != K:
+                raise ValueError("rollout_stats: n_steps does not match the action sequence")
+        N = self.n_envs
+        if into is not None:
+            want = ((into.stats, t.float64, (L.STATS_FIELDS, N, L.INFO_DIM)), (into.returns, t.float64, (N, L.N_AGENTS)),
+                    (into.counts, t.int32, (N, 2)))
+            if not (isinstance(into, EpisodeStats) and all(isinstance(x, t.Tensor) and x.dtype == d and tuple(x.shape) == sh and
+                                                           x.is_contiguous() and x.device == self.device for x, d, sh in want)):
+                raise ValueError(f"rollout_stats: into must be an EpisodeStats of this engine (contiguous tensors on {self.device}: stats "
+                                 f"float64 {want[0][2]}, returns float64 {want[1][2]}, counts int32 {want[2][2]})")
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with t.cuda.device(self.device):
+            if into is None:
+                res = EpisodeStats(t.empty((L.STATS_FIELDS, N, L.INFO_DIM), dtype=t.float64, device=self.device),
+                                   t.empty((N, L.N_AGENTS), dtype=t.float64, device=self.device),
+                                   t.empty((N, 2), dtype=t.int32, device=self.device))
+            else:
+                res = into
+                if self._pinned_stream_obj is not None:      # (its tensors may have been touched on torch's current stream)
+                    self._pinned_stream_obj.wait_stream(t.cuda.current_stream(self.device))
+            rc = self.lib.sdc_rollout_stats(self._h, K, p(actions) if actions is not None else None, 0 if into is None else 1,
+                                            p(res.stats), p(res.returns), p(res.counts), p(self.obs), p(self.share_obs), p(self.rew),
+                                            p(self.done), p(self.info), p(self.final_obs), self._stream())
+        self._refused(rc)
+        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse them before)
+            for x in (res.stats, res.returns, res.counts) + ((actions,) if actions is not None else ()):
+                x.record_stream(self._pinned_stream_obj)
+        return res
+
+    def evaluate(self, n_episodes: int, actions=None) -> EpisodeStats:
+        """`n_episodes` whole episodes of the batch, one `rollout_stats` of episode_steps steps each -> an EpisodeStats whose tensors
+        carry a leading [E] dimension (stats [E, 4, N, 44], returns [E, N, 3], counts [E, N, 2]).  The batch is reset first; between
+        episodes the auto-reset starts the next one (auto_reset off: reset() is called).  actions: None (every slot on a built-in
+        policy), an int32 device tensor [episode_steps, N, 3] replayed every episode, or a callable episode -> such a tensor."""
+        t = self.torch
+        E = int(n_episodes)
+        if E < 1:
+            raise ValueError(f"evaluate: n_episodes = {n_episodes} must be positive")
+        if actions is None and any(p == 0 for p in self.policy):
+            raise ValueError("evaluate: actions=None needs a built-in policy on every agent slot")
+        self.reset()
+        eps = []
+        for e in range(E):
+            if e > 0 and not self.config["auto_reset"]:
+                self.reset()
+            a = actions(e) if callable(actions) else actions
+            eps.append(self.rollout_stats(a, n_steps=self.episode_steps))
+        return EpisodeStats(t.stack([x.stats for x in eps]), t.stack([x.returns for x in eps]), t.stack([x.counts for x in eps]))
 
     def profile(self, every: int = 1):
         """Per-kernel HIP-event timing on the launch stream (measurement only): every k-th step, 0 = off."""

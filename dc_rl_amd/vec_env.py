@@ -524,6 +524,57 @@ class SustainDCVecEnv(ShareVecEnv):
             res.action = res.action[:, self._agent_idx].contiguous()
         return res
 
+    def _stats_actions(self, actions, K, what):
+        """an action sequence [K, num_envs, n_agents] in this env's agent order -> the engine's [K, num_envs, 3] int32; None: the trained
+        agents play the reference's base do-nothing actions (utils/base_agents.py: ls 1, dc 1, bat 2), as the other slots do on the device"""
+        t = self._torch
+        dev = self.engine.device
+        if actions is None:
+            if K is None:
+                raise ValueError(f"{what}: actions=None needs n_steps")
+            return t.tensor([1, 1, 2], dtype=t.int32, device=dev).expand(int(K), self.num_envs, 3).contiguous()
+        if not (isinstance(actions, t.Tensor) and actions.dim() == 3 and tuple(actions.shape[1:]) == (self.num_envs, self.n_agents)):
+            raise ValueError(f"{what}: actions must be a tensor of shape (K, {self.num_envs}, {self.n_agents})")
+        a = actions.to(device=dev, dtype=t.int32)
+        if self.n_agents != 3:
+            full = t.ones(tuple(a.shape[:2]) + (3,), dtype=t.int32, device=dev)
+            full[..., self._agent_idx] = a
+            a = full
+        return a.contiguous()
+
+    def rollout_stats(self, actions=None, n_steps=None, into=None):
+        """K env-steps reduced on the device to per-env statistics (SdcEngine.rollout_stats, which documents the result).  `actions`: an
+        int tensor [K, num_envs, n_agents] in this env's agent order; with an agent subset the other slots' columns are filled with 1
+        (they are played on the device and never read), as step_async does.  None with n_steps: every trained agent plays the
+        reference's base do-nothing action (ls 1, dc 1, bat 2) -- the baseline the other slots already play.  The envs move as under K
+        calls of step(); actions handed to step_async and not yet stepped are dropped.  THE LOGGER ACCUMULATOR
+        (accumulate_logger_sums) IS LEFT ALONE: it counts what went through step(), and these steps did not.  ValueError for what the
+        engine refuses."""
+        if self._need_reset:
+            raise ValueError("rollout_stats: call reset() first")
+        a = self._stats_actions(actions, n_steps, "rollout_stats")
+        if n_steps is not None and int(n_steps) != int(a.shape[0]):
+            raise ValueError("rollout_stats: n_steps does not match the action sequence")
+        res = self.engine.rollout_stats(a, into=into)
+        self._actions = None
+        self._gen += 1      # (the engine's info buffer now holds another step: `infos` objects that view it say so)
+        return res
+
+    def evaluate(self, n_episodes, actions=None):
+        """`n_episodes` whole episodes of the batch from a reset (SdcEngine.evaluate) -> an EpisodeStats with a leading [E] dimension.
+        `actions`: None (do-nothing baseline, see rollout_stats), an int tensor [episode_steps, num_envs, n_agents] replayed every
+        episode, or a callable episode -> such a tensor.  The logger accumulator (accumulate_logger_sums) is left alone.  Afterwards
+        the envs stand at the start of a fresh episode when auto_reset is on; otherwise call reset()."""
+        steps = self.episode_steps
+        fixed = None if callable(actions) else self._stats_actions(actions, steps, "evaluate")
+        if fixed is not None and int(fixed.shape[0]) != steps:
+            raise ValueError(f"evaluate: actions must hold episode_steps = {steps} steps, got {int(fixed.shape[0])}")
+        res = self.engine.evaluate(n_episodes, (lambda e: self._stats_actions(actions(e), steps, "evaluate")) if fixed is None else fixed)
+        self._actions = None
+        self._gen += 1
+        self._need_reset = not self.engine.config["auto_reset"]
+        return res
+
     def _take_state(self, src):
         """This env (built from src's constructor arguments, never stepped) becomes a copy of src: every env restored from a snapshot
         of src's, the seed and the host-side state copied.  src not reset yet: nothing to restore."""

@@ -128,8 +128,9 @@ typedef struct {
                               results to the bit).
                               Bit 13 (8192): TEST HOOK -- every 61st (env + launch) redoes its clip bounds' side from the
                               history as if a bound had left its window (a path ~4e-8 of the env-steps take by themselves).
-                              Bit 14 (16384): TEST HOOK -- sdc_plan's output block holds two steps, so that short horizons
-                              run its chunked path; read by sdc_plan alone, the step kernels never see the bit */
+                              Bit 14 (16384): TEST HOOK -- the handle's output block holds two steps, so that short horizons
+                              run the chunked path of sdc_plan / sdc_plan_cem / sdc_rollout_stats; read by those calls alone,
+                              the step kernels never see the bit */
   int32_t reward_method[3]; /* reward function per agent slot (ls, dc, bat), utils/reward_creator.py:322-334:
                                SDC_REWARD_DEFAULT the slot's own default_*_reward, SDC_REWARD_FOOTPRINT
                                default_dc_reward = default_bat_reward, SDC_REWARD_CUSTOM custom_agent_reward (0),
@@ -218,7 +219,8 @@ const char* sdc_last_error(void);
  *   312  sdc_state_layout
  *   313  sdc_clone_envs
  *        (sdc_snapshot_row_bytes, sdc_snapshot_envs, sdc_restore_envs came later without a bump: new entry points, no layout or
- *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise; sdc_plan and sdc_plan_cem likewise) */
+ *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise; sdc_plan, sdc_plan_cem and
+ *        sdc_rollout_stats likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -531,6 +533,37 @@ typedef struct {
 int sdc_plan_cem(sdc_handle* h, int n_steps, const sdc_cem_params* cem, const sdc_plan_objective* objective, double* probs,
                  int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* cand, double* cand_score, float* obs,
                  float* share_obs, void* stream);
+
+/* EPISODE STATISTICS: advance the engine by n_steps env-steps exactly as sdc_rollout(h, n_steps, actions, ...) would -- the call is made
+ * of sdc_rollout calls: the same kernel choice, launch counter and host mirrors, the auto-reset at the episode's end -- and hand back
+ * per-env statistics of the steps' outputs instead of the outputs.  No mark, no rewind: the engine moves.  One call, ordered on `stream`,
+ * no device synchronisation (the handle's output block is allocated on first use and when it has to grow).  The rollouts write into the
+ * output block the handle owns (sdc_plan's: capped at 256 MiB, csrc/sdc_plan.hpp) in chunks of as many steps as fit, at least one;
+ * debug_flags bit 14 (TEST HOOK): two steps.  After each chunk one launch of sdc_stats_reduce_kernel (csrc/sdc_stats.hip) folds the
+ * chunk's info and rew rows into stats / returns / counts; after the last chunk sdc_stats_last_kernel copies the last step's obs,
+ * share_obs, rew, done and info rows to the caller's single-step arrays [N]... (obs and share_obs required; rew, done, info, final_obs
+ * may be NULL), and the block's final_obs rows of the envs that finished into final_obs (the other rows keep what they held, as after
+ * sdc_rollout).  n_steps may reach the episode's end -- the statistics cover the n_steps steps taken, the terminal one included, and
+ * obs / share_obs then hold the reset observations as after sdc_rollout -- and is not limited by SDC_MARK_MAX_STEPS.
+ * actions [n_steps][N][3] int32 (device); NULL when every slot has a built-in policy.  All arrays are the device's:
+ *   stats   [SDC_STATS_FIELDS][N][SDC_INFO_DIM] fp64, 16-byte aligned      returns [N][3] fp64, 16-byte aligned
+ *   counts  [N][2] int32: steps reduced, the OR of the steps' info[fault] bits
+ * accumulate == 0:  SUM = 0.0, MIN = +inf, MAX = -inf, NPOS = 0.0, returns = 0.0, counts = 0;  accumulate == 1: continue from what the
+ * arrays hold.  Then for k = 0 .. n_steps - 1 in order, all in fp64 without fused multiply-adds, per env n and info column c with
+ * x = (double)info_k[n][c]:
+ *   SUM += x;   MIN = x < MIN ? x : MIN;   MAX = x > MAX ? x : MAX;   NPOS += (x > 0.0) ? 1.0 : 0.0
+ *   returns[n][a] += (double)rew_k[n][a];   counts[n][0] += 1;   counts[n][1] |= (uint32_t)info_k[n][SDC_INFO_FAULT]
+ * A NaN therefore never enters MIN, MAX or NPOS and propagates through SUM.  All 44 columns are reduced.  The results depend neither on
+ * the chunking nor on splitting one call into several with accumulate == 1.
+ * Refused (-2 and a message, nothing enqueued, the engine untouched): a null handle; n_steps < 1; a null stats / returns / counts / obs /
+ * share_obs; stats or returns not 16-byte aligned, another array not dword-aligned; accumulate outside {0, 1}; no sdc_reset yet; verify
+ * mode (debug_flags bit 0), which sdc_rollout refuses as well; null actions while a slot is on SDC_POLICY_EXTERNAL; n_steps >
+ * sdc_steps_to_episode_end(). */
+#define SDC_STATS_FIELDS 4
+enum sdc_stat_field { SDC_STAT_SUM = 0, SDC_STAT_MIN, SDC_STAT_MAX, SDC_STAT_NPOS };
+int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int accumulate, double* stats, double* returns,
+                      int32_t* counts, float* obs, float* share_obs, float* rew, uint8_t* done, float* info, float* final_obs,
+                      void* stream);
 
 /* Per-kernel timing (measurement only; off by default).  enable = k > 0 samples every k-th sdc_step, 0 switches it
  * off.  In a sampled step one lane per workgroup of each kernel stamps the device's constant-rate wall clock at
