@@ -11,6 +11,8 @@ Public surface (mirrors the reference's names for this path):
   * `RBCBatteryAgent`, `trim_and_respond_ctrl`, `ShootingMPCAgent` -- the rule-based baselines (utils/rbc_agents.py,
                                                       utils/trim_and_respond.py) and a shooting MPC over `SdcEngine.plan`
   * `CEMMPCAgent`, `CEMResult`                     -- the cross-entropy-method MPC over `SdcEngine.plan_cem` and what that call returns
+  * `GroupCEMMPCAgent`, `GroupCEMResult`         -- the same with the samples in env slots: groups of replica envs, one rollout per
+                                                      iteration (`SdcEngine.plan_cem_groups`, `sync_groups`)
   * `EpisodeStats`                                 -- per-env episode statistics reduced on the device (`SdcEngine.rollout_stats` / `evaluate`)
 
 The compute path is the HIP extension `csrc/libsustaindc_hip.so` (hand-written gfx950 kernels).  There is
@@ -35,6 +37,8 @@ _LAZY = {
     "ShootingMPCAgent": ("agents", "ShootingMPCAgent"),
     "CEMMPCAgent": ("agents", "CEMMPCAgent"),
     "CEMResult": ("engine", "CEMResult"),
+    "GroupCEMMPCAgent": ("agents", "GroupCEMMPCAgent"),
+    "GroupCEMResult": ("engine", "GroupCEMResult"),
     "EpisodeStats": ("engine", "EpisodeStats"),
     "RBCBatteryAgent": ("agents", "RBCBatteryAgent"),
     "trim_and_respond_ctrl": ("agents", "trim_and_respond_ctrl"),

@@ -23,13 +23,14 @@ ABI_VERSION = 313  # include/sustaindc_hip.h SDC_ABI_VERSION: the struct layouts
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
-           "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_stats.hip"]
+           "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
 PLAN_DEBUG_TWO_STEPS = 16384   # sdc_config.debug_flags bit 14 (test hook): sdc_plan's output block holds two steps
 STATS_FIELDS = 4        # include/sustaindc_hip.h SDC_STATS_FIELDS: sum, min, max, count of positive values (enum sdc_stat_field)
 CEM_MAX_CAND = 64       # include/sustaindc_hip.h SDC_CEM_MAX_CAND: candidates per iteration of sdc_plan_cem
+CEM_MAX_GROUP = 1024    # include/sustaindc_hip.h SDC_CEM_MAX_GROUP: replicas per group of sdc_plan_cem_groups
 CEM_MAX_ITERS = 65536   # ... and its iteration indices: iter0 + n_iters <= this (the index is 16 bits of the generator's counter)
 SNAPSHOT_MANIFEST = 9   # include/sustaindc_hip.h SDC_SNAPSHOT_MANIFEST: int32 entries per snapshot row's manifest (enum sdc_snapshot_manifest)
 # (-amdgpu-sched-strategy=max-ilp: the machine scheduler orders for instruction-level parallelism instead of minimal register
@@ -152,6 +153,14 @@ class SdcCemParams(C.Structure):
     ]
 
 
+class SdcCemGroupParams(C.Structure):
+    """The cross-entropy method's parameters of one sdc_plan_cem_groups call (include/sustaindc_hip.h sdc_cem_group_params)."""
+    _fields_ = [
+        ("group_size", C.c_int32), ("group_base", C.c_int32), ("n_iters", C.c_int32), ("iter0", C.c_int32), ("n_elite", C.c_int32),
+        ("fixed_action", C.c_int32 * 3), ("draw", C.c_uint32), ("seed", C.c_uint64), ("alpha", C.c_double), ("p_min", C.c_double),
+    ]
+
+
 EXPORTS = [
     "sdc_last_error", "sdc_version", "sdc_create", "sdc_destroy", "sdc_set_seed", "sdc_weather_window_len", "sdc_set_tables",
     "sdc_set_dc_params", "sdc_assign_envs", "sdc_reset", "sdc_step", "sdc_rollout", "sdc_steps_to_episode_end",
@@ -161,6 +170,7 @@ EXPORTS = [
     "sdc_set_actor", "sdc_rollout_actor", "sdc_clone_envs",
     "sdc_snapshot_row_bytes", "sdc_snapshot_envs", "sdc_restore_envs",
     "sdc_mark_row_bytes", "sdc_mark_envs", "sdc_rewind_envs", "sdc_plan", "sdc_plan_cem", "sdc_rollout_stats",
+    "sdc_plan_cem_groups",
 ]
 
 
@@ -319,6 +329,8 @@ def load():
     L.sdc_rewind_envs.argtypes = [vp, ip, C.c_int, vp, ip, fp, fp, vp]
     L.sdc_plan.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(SdcPlanObjective), vp, vp, vp, vp, fp, fp, vp]
     L.sdc_plan_cem.argtypes = [vp, C.c_int, C.POINTER(SdcCemParams), C.POINTER(SdcPlanObjective), vp, vp, vp, vp, vp, vp, fp, fp, vp]
+    L.sdc_plan_cem_groups.argtypes = [vp, C.c_int, C.POINTER(SdcCemGroupParams), C.POINTER(SdcPlanObjective), vp, vp, vp, vp, vp, vp, vp,
+                                      fp, fp, vp]
     L.sdc_rollout_stats.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp]
     for name in EXPORTS:
         getattr(L, name)

@@ -222,3 +222,50 @@ class CEMMPCAgent:
         self.last_horizon = K
         self._probs, self._best_seq = self.last.probs, self.last.best_seq
         return self.last.action
+
+
+class GroupCEMMPCAgent(CEMMPCAgent):
+    """CEMMPCAgent with the samples in env slots: the batch is groups of `group_size` = R consecutive envs that hold one state, every
+    replica plays one sampled sequence per iteration, and the whole iteration is one rollout of the batch (SdcEngine.plan_cem_groups /
+    SustainDCVecEnv.plan_cem_groups over sdc_plan_cem_groups) -- up to 1 024 samples per group and iteration.  The decision counter,
+    the horizon cut at the episode's end and the warm start are CEMMPCAgent's, per group: probs [K, G, 3, 3], best_seq [K, G, 3].
+    `act` returns `step_actions` -- the group's best first action for every replica --, so stepping with it keeps a group identical.
+    Replicas draw their own resets (those are keyed on the global env index), so the agent makes every group a copy of its first env
+    (`sync_groups`) on its first decision and whenever the episode step has gone backwards (a reset or auto-reset), and starts probs
+    and best_seq afresh then.  `last`: the latest GroupCEMResult (None after a do-nothing fallback)."""
+
+    def __init__(self, group_size: int, n_elite: int = 2, n_iters: int = 3, horizon: int = 8, seed: int = 0, alpha: float = 0.0,
+                 p_min: float = 0.0, warm_start: bool = True, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None):
+        if group_size < 2 or not 1 <= n_elite <= group_size or n_iters < 1 or horizon < 1:
+            raise ValueError("GroupCEMMPCAgent: group_size >= 2, 1 <= n_elite <= group_size, n_iters and horizon positive")
+        super().__init__(int(group_size), n_elite, n_iters, horizon, seed, alpha, p_min, warm_start, reward_weights, gamma, info_weights)
+        self.group_size = int(group_size)
+        self.syncs = 0      # how often the groups have been re-synchronised
+
+    def act(self, env):
+        """env: an SdcEngine or a SustainDCVecEnv -> int32 device tensor [N, 3] (the vec env: [N, n_agents], its agents' columns)."""
+        import torch
+        eng = getattr(env, "engine", env)
+        N = eng.n_envs
+        idx = list(getattr(env, "_agent_idx", (0, 1, 2)))
+        left = eng.steps_to_episode_end()
+        K = min(self.horizon, left - 1 if eng.config["auto_reset"] else left)
+        step = eng.config["episode_steps"] - left
+        if self._step is None or step < self._step:      # the first decision, or a new episode: the replicas drew resets of their own
+            env.sync_groups(self.group_size)
+            self.syncs += 1
+            self._probs = self._best_seq = None
+        if left < 2 or K < 1:
+            self.last, self.last_horizon = None, 0
+            self._probs = self._best_seq = None
+            self._step = step
+            nothing = torch.tensor([self.DO_NOTHING[i] for i in idx], dtype=torch.int32, device=eng.device)
+            return nothing.expand(N, len(idx)).contiguous()
+        probs, best_seq = self._start(step, K)
+        self.last = env.plan_cem_groups(self.group_size, K, self.n_iters, self.n_elite, probs=probs, best_seq=best_seq, seed=self.seed,
+                                        draw=self.draw, alpha=self.alpha, p_min=self.p_min, reward_weights=self.reward_weights,
+                                        gamma=self.gamma, info_weights=self.info_weights)
+        self.draw = (self.draw + 1) & 0xFFFFFFFF
+        self.last_horizon = K
+        self._probs, self._best_seq = self.last.probs, self.last.best_seq
+        return self.last.step_actions

@@ -22,6 +22,7 @@
 #include "sdc_snapshot.hpp"
 #include "sdc_mark.hpp"
 #include "sdc_cem.hpp"
+#include "sdc_cem_groups.hpp"
 #include "sdc_plan.hpp"
 #include "sdc_stats.hpp"
 
@@ -2166,6 +2167,111 @@ int sdc_plan_cem(sdc_handle* h, int n_steps, const sdc_cem_params* cem, const sd
         F.best_score = best_score + (size_t)i * N;
         e = sdc_cem_refit_launch(F, st);
         if (e != hipSuccess) rc = fail("sdc_cem_refit_kernel", e);
+      }
+    }
+    return hipSuccess;
+  });
+  return rc ? rc : staged;
+}
+
+// ---- plan with the cross-entropy method over replica groups (sdc_cem_groups.hip) -----------------------------------------------------
+// The contract and the arithmetic: include/sustaindc_hip.h; the kernels' plans: sdc_cem_groups.hpp.  sdc_plan_cem with the candidates
+// in env slots: per iteration ONE rollout of the whole batch (plan_candidates with the single "candidate" cand) between the group
+// sample and the group refit kernel.
+int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* cem, const sdc_plan_objective* objective, double* probs,
+                        int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* step_actions, int32_t* cand,
+                        double* cand_score, float* obs, float* share_obs, void* stream) {
+  static const char* const who = "sdc_plan_cem_groups";
+  const std::string w = std::string(who) + ": ";
+  if (!h) return fail_msg(w + "null handle");
+  if (!cem) return fail_msg(w + "null cem");
+  const sdc_cem_group_params c = *cem;
+  const int N = h->cfg.n_envs;
+  if (c.n_iters < 1) return fail_msg(w + "n_iters = " + std::to_string(c.n_iters) + " must be positive");
+  if (c.iter0 < 0 || (long long)c.iter0 + c.n_iters > 65536)
+    return fail_msg(w + "iter0 = " + std::to_string(c.iter0) + " with n_iters = " + std::to_string(c.n_iters) + " outside [0, 65536]");
+  if (c.group_size < 2 || c.group_size > SDC_CEM_MAX_GROUP)
+    return fail_msg(w + "group_size = " + std::to_string(c.group_size) + " outside [2, " + std::to_string(SDC_CEM_MAX_GROUP) + "]");
+  if (N % c.group_size != 0)
+    return fail_msg(w + "n_envs = " + std::to_string(N) + " is not a multiple of group_size = " + std::to_string(c.group_size));
+  if (c.n_elite < 1 || c.n_elite > c.group_size)
+    return fail_msg(w + "n_elite = " + std::to_string(c.n_elite) + " outside [1, group_size = " + std::to_string(c.group_size) + "]");
+  if (c.group_base < 0) return fail_msg(w + "group_base = " + std::to_string(c.group_base) + " is negative");
+  for (int a = 0; a < 3; a++)
+    if (c.fixed_action[a] < -1 || c.fixed_action[a] > 2)
+      return fail_msg(w + "fixed_action[" + std::to_string(a) + "] = " + std::to_string(c.fixed_action[a]) + " outside [-1, 2]");
+  if (!(c.alpha >= 0.0 && c.alpha < 1.0)) return fail_msg(w + "alpha = " + std::to_string(c.alpha) + " outside [0, 1)");
+  if (!(c.p_min >= 0.0 && c.p_min <= 1.0 / 3.0)) return fail_msg(w + "p_min = " + std::to_string(c.p_min) + " outside [0, 1/3]");
+  sdc_plan_objective obj;
+  if (plan_refused(who, h, n_steps, probs && best_seq && best_score && best_action && step_actions && cand && cand_score, obs, share_obs,
+                   objective, obj))
+    return -2;
+  // what the host mirrors know of a group's replicas: the episode step, the config, the trace set, the feature-row flag
+  const int R = c.group_size, G = N / R;
+  sync_mirror(h);
+  const bool cfgs = (int)h->cfg_host.size() == N, locs = (int)h->loc_host.size() == N;
+  for (int e = 0; e < N; e++) {
+    const int l = e - e % R;      // the group's first env
+    if (e == l) continue;
+    const char* what = h->host_t_rel[(size_t)e] != h->host_t_rel[(size_t)l]                         ? "episode step"
+                       : cfgs && h->cfg_host[(size_t)e] != h->cfg_host[(size_t)l]                  ? "data-centre config"
+                       : locs && h->loc_host[(size_t)e] != h->loc_host[(size_t)l]                  ? "location"
+                       : (h->feat_host[(size_t)e] != 0) != (h->feat_host[(size_t)l] != 0)          ? "feature-row flag"
+                                                                                                   : nullptr;
+    if (what)
+      return fail_msg(w + "group " + std::to_string(e / R) + " is out of step: env " + std::to_string(e) + " and its group's first env " +
+                      std::to_string(l) + " differ in " + what + " (the replicas of a group hold one state: sdc_clone_envs)");
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  PlanRun Rn;
+  if (plan_prepare(h, n_steps, obj, Rn)) return -1;
+  SdcCemGroupSample Q;
+  std::memset(&Q, 0, sizeof(Q));
+  Q.n_envs = N;
+  Q.group_size = R;
+  Q.n_groups = G;
+  Q.n_steps = n_steps;
+  Q.group_base = c.group_base;
+  Q.draw = c.draw;
+  Q.key0 = (unsigned)c.seed;
+  Q.key1 = (unsigned)(c.seed >> 32);
+  Q.probs = probs;
+  Q.best_seq = best_seq;
+  Q.cand = cand;
+  SdcCemGroupRefit F;
+  std::memset(&F, 0, sizeof(F));
+  F.n_envs = N;
+  F.group_size = R;
+  F.n_groups = G;
+  F.n_steps = n_steps;
+  F.n_elite = c.n_elite;
+  F.alpha = c.alpha;
+  F.take = 1.0 - c.alpha;
+  F.p_min = c.p_min;
+  F.score = cand_score;
+  F.cand = cand;
+  F.probs = probs;
+  F.best_seq = best_seq;
+  F.best_action = best_action;
+  F.step_actions = step_actions;
+  for (int a = 0; a < 3; a++) Q.fixed[a] = F.fixed[a] = c.fixed_action[a];
+  void* pin = nullptr;
+  if (stage_acquire(h, h->plan_stage, &pin)) return -1;
+  plan_discounts(static_cast<double*>(pin), n_steps, obj.gamma);
+  int rc = 0;
+  const int staged = stage_commit(h, h->plan_stage, (size_t)n_steps, st, [&](const void* g_dev) {
+    rc = sdc_mark_envs(h, nullptr, N, n_steps, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
+    for (int i = 0; i < c.n_iters && rc == 0; i++) {
+      Q.c3 = ((unsigned)(c.iter0 + i) << 16) | SDC_CEM_STREAM;
+      hipError_t e = sdc_cem_group_sample_launch(Q, st);
+      if (e != hipSuccess) rc = fail("sdc_cem_group_sample_kernel", e);
+      if (rc == 0) rc = plan_candidates(h, Rn, g_dev, 1, cand, nullptr, cand_score, obs, share_obs, stream);
+      if (rc == 0) {
+        F.last = i == c.n_iters - 1;
+        F.best_score = best_score + (size_t)i * (size_t)G;
+        e = sdc_cem_group_refit_launch(F, st);
+        if (e != hipSuccess) rc = fail("sdc_cem_group_refit_kernel", e);
       }
     }
     return hipSuccess;

@@ -115,6 +115,19 @@ class CEMResult:
         self.action, self.best_seq, self.best_score, self.probs, self.cand, self.cand_score = action, best_seq, best_score, probs, cand, cand_score
 
 
+class GroupCEMResult:
+    """What SdcEngine.plan_cem_groups returns, all on the engine's device; G = N / group_size groups: `action` int32 [G, 3] the first
+    action of every group's best sequence (SustainDCVecEnv.plan_cem_groups: the agent subset's columns), `step_actions` int32 [N, 3]
+    (the vec env: [N, n_agents]) the same broadcast to every replica -- what to step with so that a group stays identical --,
+    `best_seq` int32 [K, G, 3] that sequence, `best_score` float64 [I, G] its score after each iteration, `probs` float64
+    [K, G, 3, 3] the refitted distributions, `cand` int32 [K, N, 3] and `cand_score` float64 [N] the last iteration's sequences
+    (replica r of group g played cand[:, g R + r]) and their scores."""
+
+    def __init__(self, action, step_actions, best_seq, best_score, probs, cand, cand_score):
+        self.action, self.step_actions, self.best_seq, self.best_score = action, step_actions, best_seq, best_score
+        self.probs, self.cand, self.cand_score = probs, cand, cand_score
+
+
 # EpisodeStats.summary: the reference logger's quantities (harl/envs/sustaindc/sustaindc_logger.py), name -> (info column, kind)
 _SUMMARY = {
     "average_net_energy": ("bat_total_energy_with_battery_KWh", "mean"),      # sustaindc_logger.py:87, :131
@@ -930,6 +943,103 @@ class SdcEngine:
             for x in arrays:
                 x.record_stream(self._pinned_stream_obj)
         return CEMResult(action, best_seq, best_score, probs, cand, cand_score)
+
+    def sync_groups(self, group_size: int):
+        """Every group of `group_size` consecutive envs becomes a copy of its first env: one clone_envs call with the leaders as sources
+        (the replicas finish the leader's episode exactly; their own resets stay keyed on their own global indices, so call this again
+        after a reset or auto-reset).  What plan_cem_groups asks of the batch.  ValueError for a group_size that is not in [2, n_envs]
+        or does not divide n_envs, and what clone_envs refuses.  -> (obs, share_obs) views."""
+        R = int(group_size)
+        if R < 2 or R > self.n_envs or self.n_envs % R:
+            raise ValueError(f"sync_groups: group_size = {R} must be at least 2 and divide n_envs = {self.n_envs}")
+        e = np.arange(self.n_envs, dtype=np.int32)
+        dst = e[e % R != 0]
+        return self.clone_envs(dst - dst % R, dst)
+
+    def plan_cem_groups(self, group_size: int, horizon: int, n_iters: int, n_elite: int, *, probs=None, best_seq=None, seed: int = 0,
+                        draw: int = 0, iter0: int = 0, alpha: float = 0.0, p_min: float = 0.0, fixed_action=(-1, -1, -1),
+                        group_base: Optional[int] = None, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0,
+                        info_weights=None) -> GroupCEMResult:
+        """`plan_cem` with the candidates in env slots (sdc_plan_cem_groups): the batch is G = N / R groups of R = group_size
+        consecutive envs that hold ONE state (`sync_groups` makes them so; stepping with the result's `step_actions` keeps them so),
+        and in every iteration each replica plays its own sampled sequence in a single K = horizon step rollout of the whole batch --
+        one sample launch, one rollout, one score, one rewind and one refit per iteration whatever R is, up to CEM_MAX_GROUP = 1024
+        samples per group.  The arithmetic is plan_cem's with "candidate m of env n" read as "replica r of group g": for R <= 64 the
+        results equal, bit for bit, plan_cem(n_candidates=R) on an engine of G envs whose env g is group g's state and whose
+        env_index_base is `group_base`.  `probs` float64 device tensor [K, G, 3, 3] (None: uniform) and `best_seq` int32 [K, G, 3]
+        (None: do nothing -- 1, 1, 2) are updated in place and returned; replica 0 of a group carries the incumbent.  `group_base`:
+        the global index of this engine's group 0 in the generator's counter (None: env_index_base // R, refused where R does not
+        divide env_index_base).  The other arguments, the engine afterwards and the price (the envs' one live mark) are plan_cem's.
+        What the host knows of a group's replicas (episode step, config, location, feature-row flag) is checked; bit equality of their
+        states beyond that is the caller's contract.  -> GroupCEMResult(action [G, 3], step_actions [N, 3], best_seq, best_score
+        [I, G], probs, cand [K, N, 3], cand_score [N]).  ValueError, with the engine untouched, for malformed tensors or objective and
+        what the library refuses: plan_cem's rules with n_candidates read as group_size; R outside [2, CEM_MAX_GROUP] or not dividing
+        N; E outside [1, R]; a negative group_base; a group out of step."""
+        t = self.torch
+        K, N, R, n_it = int(horizon), self.n_envs, int(group_size), int(n_iters)
+        fixed = [int(x) for x in fixed_action]
+        if len(fixed) != 3:
+            raise ValueError(f"plan_cem_groups: fixed_action must be three integers (ls, dc, bat), got {len(fixed)}")
+        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(draw) < 1 << 32:
+            raise ValueError("plan_cem_groups: seed must fit 64 bits and draw 32, both unsigned")
+        grouped = 2 <= R <= L.CEM_MAX_GROUP and N % R == 0
+        if group_base is None:
+            base = int(self.config["env_index_base"])
+            if grouped and base % R:
+                raise ValueError(f"plan_cem_groups: group_size = {R} does not divide env_index_base = {base} (pass group_base)")
+            group_base = base // R if grouped else 0
+        if not -(1 << 31) <= int(group_base) < 1 << 31:
+            raise ValueError("plan_cem_groups: group_base must fit 32 bits")
+        G = N // R if grouped else 0
+
+        def given(x, name, dtype, shape):
+            if not (isinstance(x, t.Tensor) and x.dtype == dtype and x.is_cuda and x.is_contiguous() and tuple(x.shape) == shape):
+                raise ValueError(f"plan_cem_groups: {name} must be a contiguous {str(dtype).split('.')[-1]} CUDA tensor of shape {shape}")
+            if x.device != self.device:
+                raise ValueError(f"plan_cem_groups: {name} is on {x.device}, this engine runs on {self.device}")
+            return x
+
+        sized = grouped and 1 <= K <= L.MARK_MAX_STEPS and n_it >= 1 and 0 <= int(iter0) <= L.CEM_MAX_ITERS - n_it
+        if sized and probs is not None:
+            given(probs, "probs", t.float64, (K, G, 3, 3))
+        if sized and best_seq is not None:
+            given(best_seq, "best_seq", t.int32, (K, G, 3))
+        obj = plan_objective(reward_weights, gamma, info_weights)
+        cem = L.SdcCemGroupParams()
+        cem.group_size, cem.group_base, cem.n_iters, cem.iter0, cem.n_elite = R, int(group_base), n_it, int(iter0), int(n_elite)
+        cem.fixed_action[:] = fixed
+        cem.draw, cem.seed, cem.alpha, cem.p_min = int(draw), int(seed), float(alpha), float(p_min)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        with t.cuda.device(self.device):
+            if sized:
+                if self._pinned_stream_obj is not None:
+                    # (probs and best_seq are filled by torch ops on torch's current stream and read by the sample kernel on the
+                    #  pinned one: order it behind them)
+                    self._pinned_stream_obj.wait_stream(t.cuda.current_stream(self.device))
+                if probs is None:
+                    probs = t.full((K, G, 3, 3), 1.0 / 3.0, dtype=t.float64, device=self.device)
+                if best_seq is None:
+                    best_seq = t.tensor([1, 1, 2], dtype=t.int32, device=self.device).expand(K, G, 3).contiguous()
+                best_score = t.empty((n_it, G), dtype=t.float64, device=self.device)
+                action = t.empty((G, 3), dtype=t.int32, device=self.device)
+                step_actions = t.empty((N, 3), dtype=t.int32, device=self.device)
+                cand = t.empty((K, N, 3), dtype=t.int32, device=self.device)
+                cand_score = t.empty((N,), dtype=t.float64, device=self.device)
+                arrays = (probs, best_seq, best_score, action, step_actions, cand, cand_score)
+                rc = self.lib.sdc_plan_cem_groups(self._h, K, C.byref(cem), C.byref(obj), *[p(x) for x in arrays], p(self.obs),
+                                                  p(self.share_obs), self._stream())
+            else:      # (sizes no array can be given: the library words the refusal, and it looks at the sizes before the arrays)
+                arrays = ()
+                rc = self.lib.sdc_plan_cem_groups(self._h, K, C.byref(cem), C.byref(obj), None, None, None, None, None, None, None,
+                                                  p(self.obs), p(self.share_obs), self._stream())
+                if rc == 0:
+                    raise L.SdcError(f"plan_cem_groups: sdc_plan_cem_groups accepted R = {R}, K = {K}, I = {n_it}, iter0 = {int(iter0)} "
+                                     "and no arrays")
+        self._refused(rc)
+        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse them before)
+            for x in arrays:
+                x.record_stream(self._pinned_stream_obj)
+        return GroupCEMResult(action, step_actions, best_seq, best_score, probs, cand, cand_score)
 
     def rollout_stats(self, actions=None, n_steps: int = None, into: Optional[EpisodeStats] = None) -> EpisodeStats:
         """K env-steps as `rollout` takes them, reduced on the device to per-env statistics (sdc_rollout_stats): the steps' outputs go

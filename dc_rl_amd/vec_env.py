@@ -524,6 +524,34 @@ class SustainDCVecEnv(ShareVecEnv):
             res.action = res.action[:, self._agent_idx].contiguous()
         return res
 
+    def sync_groups(self, group_size):
+        """Every group of `group_size` consecutive envs becomes a copy of its first env (SdcEngine.sync_groups, through this env's
+        clone_envs, so the host's per-env entries follow).  Returns what clone_envs returns."""
+        R = int(group_size)
+        if R < 2 or R > self.num_envs or self.num_envs % R:
+            raise ValueError(f"sync_groups: group_size = {R} must be at least 2 and divide num_envs = {self.num_envs}")
+        e = np.arange(self.num_envs, dtype=np.int32)
+        dst = e[e % R != 0]
+        return self.clone_envs(dst - dst % R, dst)
+
+    def plan_cem_groups(self, group_size, horizon, n_iters, n_elite, *, probs=None, best_seq=None, fixed_action=None, **kw):
+        """Plan with the cross-entropy method over replica groups and come back (SdcEngine.plan_cem_groups, which documents the
+        arguments; `probs` [K, G, 3, 3] and `best_seq` [K, G, 3] are the engine's, all three slots).  With an agent subset the other
+        slots are not planned for: every sampled replica carries 1 in their columns and their probs stay as they are, as in plan_cem.
+        -> GroupCEMResult whose `action` [G, n_agents] and `step_actions` [num_envs, n_agents] hold the subset's columns, the latter
+        ready for step().  The run goes on as if the call had not happened; the envs' live mark is used up.  ValueError for what the
+        engine refuses."""
+        if self._need_reset:
+            raise ValueError("plan_cem_groups: call reset() first")
+        fixed = [-1, -1, -1] if fixed_action is None else [int(x) for x in fixed_action]
+        if self.n_agents != 3:
+            fixed = [fixed[i] if i in self._agent_idx else 1 for i in range(3)]
+        res = self.engine.plan_cem_groups(group_size, horizon, n_iters, n_elite, probs=probs, best_seq=best_seq, fixed_action=fixed, **kw)
+        if self.n_agents != 3:
+            res.action = res.action[:, self._agent_idx].contiguous()
+            res.step_actions = res.step_actions[:, self._agent_idx].contiguous()
+        return res
+
     def _stats_actions(self, actions, K, what):
         """an action sequence [K, num_envs, n_agents] in this env's agent order -> the engine's [K, num_envs, 3] int32; None: the trained
         agents play the reference's base do-nothing actions (utils/base_agents.py: ls 1, dc 1, bat 2), as the other slots do on the device"""

@@ -219,8 +219,8 @@ const char* sdc_last_error(void);
  *   312  sdc_state_layout
  *   313  sdc_clone_envs
  *        (sdc_snapshot_row_bytes, sdc_snapshot_envs, sdc_restore_envs came later without a bump: new entry points, no layout or
- *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise; sdc_plan, sdc_plan_cem and
- *        sdc_rollout_stats likewise) */
+ *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise; sdc_plan, sdc_plan_cem,
+ *        sdc_rollout_stats and sdc_plan_cem_groups likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -533,6 +533,63 @@ typedef struct {
 int sdc_plan_cem(sdc_handle* h, int n_steps, const sdc_cem_params* cem, const sdc_plan_objective* objective, double* probs,
                  int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* cand, double* cand_score, float* obs,
                  float* share_obs, void* stream);
+
+/* PLAN WITH THE CROSS-ENTROPY METHOD OVER REPLICA GROUPS: sdc_plan_cem with the candidates in env slots instead of one after another in
+ * time.  The batch of N = G * R envs is G groups of R = group_size consecutive envs (replicas): group g = envs [g R, (g + 1) R).  THE R
+ * REPLICAS OF A GROUP HOLD THE SAME STATE -- the caller's contract (sdc_clone_envs from the group's first env makes it so, and stepping
+ * every replica with step_actions keeps it so).  What the host mirrors know is checked (below); bit equality of the replicas' states
+ * beyond that is NOT validated on the device: replicas that differ are scored from their own states.  In one iteration every replica
+ * plays its own sampled sequence in ONE rollout of the whole batch, and the distribution is refitted per group: per iteration it =
+ * iter0 .. iter0 + n_iters - 1 one sdc_cem_group_sample_kernel, sdc_plan's per-candidate path with the single "candidate" cand (rollout
+ * into the handle's output block in chunks, sdc_plan_score_kernel, rewind; the objective, its arithmetic, the chunking and debug_flags
+ * bit 14 are sdc_plan's), one sdc_cem_group_refit_kernel -- whatever R is.  One call, ordered on `stream`, no device synchronisation,
+ * ONE mark of the whole batch (max_steps = n_steps).  Afterwards the engine is where sdc_plan_cem leaves it (rewound, re-centring stamps
+ * cleared, the caller's output arrays never written), and THE CALL USES UP THE ENVS' ONE LIVE MARK.  All arrays are the device's; K =
+ * n_steps, E = n_elite, I = n_iters:
+ *   probs        in/out [K][G][3 agents][3 actions] fp64    best_seq     in/out [K][G][3] int32: the incumbent on entry, the best
+ *   best_score   out [I][G]: the incumbent's score after each iteration        sequence found on return
+ *   best_action  out [G][3] = best_seq[0]                   step_actions out [N][3] = best_action[n / R]: what to hand to sdc_step so
+ *   cand         work/out [K][N][3], sdc_rollout's `actions` layout: replica r of group g plays         that a group stays identical
+ *   cand[:][g R + r]; the last iteration's                  cand_score   work/out [N]: their scores
+ * The arithmetic is sdc_plan_cem's with "candidate m of env n" read as "replica r of group g":
+ * SAMPLE.  Replica 0 carries a copy of best_seq (the incumbent: its score never falls from one iteration to the next, and it wins
+ * ties).  For r = 1 .. R-1, step k, group g: one philox4x32_10 block with counter (r * K + k, group_base + g, draw, (it << 16) |
+ * 0xCE3D) and key (seed's low word, seed's high word); words x, y, z serve agents ls, dc, bat, w is unused.  For agent a with
+ * probabilities p0, p1, p2:  u = (double)word * 2^-32;  action = (u >= p0) + (u >= (p0 + p1)) -- one fp64 addition; p2 is never read.
+ * fixed_action[a] >= 0 replaces the draw of agent a in replicas 1 .. R-1.
+ * REFIT, per group over its R scores s[r] = cand_score[g R + r].  rank(r) = the number of r' with s[r'] > s[r], or s[r'] == s[r] and
+ * r' < r; r is elite iff rank(r) < E; best = the lowest-numbered replica of rank 0.  best_seq[:][g] = replica best's actions (best = 0:
+ * the bits it had), best_score[it - iter0][g] = s[best], and after the last iteration best_action[g] = best_seq[0][g] and
+ * step_actions[g R + r] = best_action[g] for every r.  For every step k and agent a without a fixed action, with cnt[j] the number of
+ * elites whose action (its low two bits) is j, all fp64, no fused multiply-adds, an IEEE division:
+ *   t_j = (double)cnt[j] / (double)E;  q_j = alpha * p_j + take * t_j  (take = 1.0 - alpha, computed once on the host);
+ *   q_j = max(q_j, p_min);  s = (q0 + q1) + q2;  p_j = q_j / s
+ * An agent with a fixed action keeps its probs.  The entries of probs and best_seq are not validated, and a NaN score is outranked by
+ * nothing and outranks nothing (rank 0, elite; the divisor stays E), both as in sdc_plan_cem.
+ * CONSEQUENCE: an engine of G envs running sdc_plan_cem with n_cand = R <= SDC_CEM_MAX_CAND and env_index_base = group_base, and an
+ * engine of G R envs whose group g holds that engine's env g, return the same probs, best_seq, best_score and best_action bit for
+ * bit, and the latter's cand_score[g R + r] is the former's cand_score[r][g].
+ * Refused (-2 and a message, nothing enqueued, the engine untouched): everything sdc_plan_cem refuses, with n_cand read as group_size
+ * (a null params; n_iters < 1, iter0 < 0, iter0 + n_iters > 65536; a fixed_action outside [-1, 2]; alpha outside [0, 1); p_min outside
+ * [0, 1/3]; sdc_plan's horizon, auto-reset and verify-mode rules; a null array); group_size outside [2, SDC_CEM_MAX_GROUP]; n_envs not
+ * a multiple of group_size; n_elite outside [1, group_size]; group_base < 0; and, from the host mirrors in O(N), a group whose replicas
+ * are not all at the same episode step, data-centre config, location and feature-row flag. */
+#define SDC_CEM_MAX_GROUP 1024
+typedef struct {
+  int32_t group_size;       /* R in [2, SDC_CEM_MAX_GROUP]; N % R == 0; group g = envs [g R, (g+1) R) */
+  int32_t group_base;       /* global index of this engine's group 0, >= 0: goes into the generator's counter */
+  int32_t n_iters;          /* I >= 1 */
+  int32_t iter0;            /* index of this call's first iteration, >= 0, iter0 + I <= 65536 */
+  int32_t n_elite;          /* E in [1, R] */
+  int32_t fixed_action[3];  /* per agent: -1 = sampled, 0..2 = every sampled replica carries this value */
+  uint32_t draw;            /* the caller's decision counter: goes into the generator's counter */
+  uint64_t seed;
+  double alpha;             /* [0, 1): weight of the old distribution in the refit */
+  double p_min;             /* [0, 1/3]: floor of every probability before renormalising */
+} sdc_cem_group_params;
+int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* cem, const sdc_plan_objective* objective, double* probs,
+                        int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* step_actions, int32_t* cand,
+                        double* cand_score, float* obs, float* share_obs, void* stream);
 
 /* EPISODE STATISTICS: advance the engine by n_steps env-steps exactly as sdc_rollout(h, n_steps, actions, ...) would -- the call is made
  * of sdc_rollout calls: the same kernel choice, launch counter and host mirrors, the auto-reset at the episode's end -- and hand back

@@ -8,7 +8,13 @@ time.
 --cem: SdcEngine.plan_cem (one sdc_plan_cem call) at I = 3 iterations, M = 8 candidates, E = 2 elites, K = 8 steps beside the same
 planner driven from Python -- per iteration torch sampling from the distributions, `plan`, topk, the refit as torch ops -- and beside
 3 x the time of one `plan` of the same M and K; the same process, sizes and timing.  Under rocprofv3 as above for
-sdc_cem_sample_kernel's and sdc_cem_refit_kernel's own time."""
+sdc_cem_sample_kernel's and sdc_cem_refit_kernel's own time.
+
+--groups: SdcEngine.plan_cem_groups (one sdc_plan_cem_groups call) at I = 3, K = 8, E = R / 8, G = 64 groups of R = 64 replicas (4 096
+envs) and of R = 512 (32 768 envs), beside SdcEngine.plan_cem on a 64-env engine with M = 64 candidates -- as many samples per data
+centre as the R = 64 case -- and beside three single-candidate `plan` calls at the groups' batch size (three 8-step rollouts, scores
+and rewinds); the same process and timing.  Under rocprofv3 as above for sdc_cem_group_sample_kernel's and
+sdc_cem_group_refit_kernel's own time."""
 import json
 import os
 import sys
@@ -73,9 +79,49 @@ def main_cem():
         eng.close()
 
 
+def _warm_engine(N):
+    eng, _, _ = bench.build_engine(N, EP, 0, seed=99, debug_flags=0)
+    eng.reset()
+    g = torch.Generator(device="cpu").manual_seed(N)
+    acts = torch.randint(0, 3, (8, N, 3), dtype=torch.int32, generator=g).cuda()
+    for t in range(40):
+        eng.step(acts[t % 8])
+    return eng, g
+
+
+def main_groups():
+    I, K, G = 3, 8, 64
+    small, _ = _warm_engine(G)
+    small.plan_cem(K, I, 64, 8)      # (warm: the handle's buffers are allocated)
+    torch.cuda.synchronize()
+    serial = timed3(lambda: small.plan_cem(K, I, 64, 8), REPS)
+    print(json.dumps(dict(what="plan_cem", n_envs=G, iterations=I, candidates=64, elites=8, steps=K, plan_cem_ms=serial[0],
+                          plan_cem_ms_range=serial[1:], step_kernel_after=small.last_step_kernel())))
+    small.close()
+    for R in (64, 512):
+        N, E = G * R, R // 8
+        eng, g = _warm_engine(N)
+        eng.sync_groups(R)
+        one = torch.randint(0, 3, (1, K, N, 3), dtype=torch.int32, generator=g).cuda()
+        res = eng.plan_cem_groups(R, K, I, E)
+        eng.plan(one)
+        torch.cuda.synchronize()
+        improved = int((res.best_score[-1] > res.best_score[0]).sum())
+        grp = timed3(lambda: eng.plan_cem_groups(R, K, I, E), REPS)
+        plan = timed3(lambda: eng.plan(one), REPS)
+        eng.step(res.step_actions)
+        print(json.dumps(dict(what="plan_cem_groups", n_envs=N, groups=G, group_size=R, iterations=I, elites=E, steps=K,
+                              plan_cem_groups_ms=grp[0], plan_cem_groups_ms_range=grp[1:], three_single_candidate_plans_ms=3 * plan[0],
+                              three_single_candidate_plans_ms_range=[3 * plan[1], 3 * plan[2]],
+                              groups_improved_after_iteration_0=improved, step_kernel_after=eng.last_step_kernel())))
+        eng.close()
+
+
 def main():
     if "--cem" in sys.argv[1:]:
         return main_cem()
+    if "--groups" in sys.argv[1:]:
+        return main_groups()
     for N in (4096, 32768):
         eng, _, _ = bench.build_engine(N, EP, 0, seed=99, debug_flags=0)
         eng.reset()
