@@ -109,6 +109,23 @@ class trim_and_respond_ctrl:
 POLICY_EXTERNAL, POLICY_DO_NOTHING, POLICY_RBC, POLICY_TRIM_AND_RESPOND = 0, 1, 2, 3
 
 
+def _mpc_horizon(env, horizon):
+    """What every MPC agent's decision starts from: env an SdcEngine or a SustainDCVecEnv -> (the horizon cut to what the episode has
+    left -- the planner does not look across an episode's end; 0: fewer than two steps left, do nothing --, the episode step)"""
+    eng = getattr(env, "engine", env)
+    left = eng.steps_to_episode_end()
+    K = min(horizon, left - 1 if eng.config["auto_reset"] else left)
+    return (K if left >= 2 and K >= 1 else 0), eng.config["episode_steps"] - left
+
+
+def _do_nothing(env, values):
+    """the do-nothing actions `values` (ls, dc, bat) for every env: int32 [N, the env's agent columns] on the env's device"""
+    import torch
+    eng = getattr(env, "engine", env)
+    idx = list(getattr(env, "_agent_idx", (0, 1, 2)))
+    return torch.tensor([values[i] for i in idx], dtype=torch.int32, device=eng.device).expand(eng.n_envs, len(idx)).contiguous()
+
+
 class ShootingMPCAgent:
     """Random-shooting model-predictive control with the simulator as its own model: at every decision draw `n_candidates` action
     sequences of `horizon` steps per env, score them on the device from the env's current state (SdcEngine.plan / SustainDCVecEnv.plan
@@ -135,18 +152,14 @@ class ShootingMPCAgent:
         """env: an SdcEngine or a SustainDCVecEnv -> int32 device tensor [N, 3] (the vec env: [N, n_agents], its agents' columns)."""
         import torch
         eng = getattr(env, "engine", env)
-        N = eng.n_envs
-        idx = list(getattr(env, "_agent_idx", (0, 1, 2)))
-        nothing = torch.tensor([self.DO_NOTHING[i] for i in idx], dtype=torch.int32, device=eng.device)
-        left = eng.steps_to_episode_end()
-        K = min(self.horizon, left - 1 if eng.config["auto_reset"] else left)
-        if left < 2 or K < 1:
+        K, nothing = _mpc_horizon(env, self.horizon)[0], _do_nothing(env, self.DO_NOTHING)
+        if K == 0:
             self.last, self.last_horizon = None, 0
-            return nothing.expand(N, len(idx)).contiguous()
+            return nothing
         if self._gen is None:
             self._gen = torch.Generator(device=eng.device)
             self._gen.manual_seed(self.seed)
-        cand = torch.randint(0, 3, (self.n_candidates, K, N, len(idx)), generator=self._gen, device=eng.device, dtype=torch.int32)
+        cand = torch.randint(0, 3, (self.n_candidates, K) + tuple(nothing.shape), generator=self._gen, device=eng.device, dtype=torch.int32)
         cand[0] = nothing
         self.last, self.last_horizon = env.plan(cand, self.reward_weights, self.gamma, self.info_weights), K
         return self.last.action
@@ -201,27 +214,30 @@ class CEMMPCAgent:
 
     def act(self, env):
         """env: an SdcEngine or a SustainDCVecEnv -> int32 device tensor [N, 3] (the vec env: [N, n_agents], its agents' columns)."""
-        import torch
-        eng = getattr(env, "engine", env)
-        N = eng.n_envs
-        idx = list(getattr(env, "_agent_idx", (0, 1, 2)))
-        left = eng.steps_to_episode_end()
-        K = min(self.horizon, left - 1 if eng.config["auto_reset"] else left)
-        step = eng.config["episode_steps"] - left
-        if left < 2 or K < 1:
+        K, step = _mpc_horizon(env, self.horizon)
+        self._before(env, step)
+        if K == 0:
             self.last, self.last_horizon = None, 0
             self._probs = self._best_seq = None
             self._step = step
-            nothing = torch.tensor([self.DO_NOTHING[i] for i in idx], dtype=torch.int32, device=eng.device)
-            return nothing.expand(N, len(idx)).contiguous()
+            return _do_nothing(env, self.DO_NOTHING)
         probs, best_seq = self._start(step, K)
-        self.last = env.plan_cem(K, self.n_iters, self.n_candidates, self.n_elite, probs=probs, best_seq=best_seq, seed=self.seed,
-                                 draw=self.draw, alpha=self.alpha, p_min=self.p_min, reward_weights=self.reward_weights,
-                                 gamma=self.gamma, info_weights=self.info_weights)
+        self.last = self._plan(env, K, probs=probs, best_seq=best_seq, seed=self.seed, draw=self.draw, alpha=self.alpha, p_min=self.p_min,
+                               reward_weights=self.reward_weights, gamma=self.gamma, info_weights=self.info_weights)
         self.draw = (self.draw + 1) & 0xFFFFFFFF
         self.last_horizon = K
         self._probs, self._best_seq = self.last.probs, self.last.best_seq
-        return self.last.action
+        return self._chosen(self.last)
+
+    # what GroupCEMMPCAgent does differently
+    def _before(self, env, step):
+        pass
+
+    def _plan(self, env, K, **kw):
+        return env.plan_cem(K, self.n_iters, self.n_candidates, self.n_elite, **kw)
+
+    def _chosen(self, res):
+        return res.action
 
 
 class GroupCEMMPCAgent(CEMMPCAgent):
@@ -242,30 +258,14 @@ class GroupCEMMPCAgent(CEMMPCAgent):
         self.group_size = int(group_size)
         self.syncs = 0      # how often the groups have been re-synchronised
 
-    def act(self, env):
-        """env: an SdcEngine or a SustainDCVecEnv -> int32 device tensor [N, 3] (the vec env: [N, n_agents], its agents' columns)."""
-        import torch
-        eng = getattr(env, "engine", env)
-        N = eng.n_envs
-        idx = list(getattr(env, "_agent_idx", (0, 1, 2)))
-        left = eng.steps_to_episode_end()
-        K = min(self.horizon, left - 1 if eng.config["auto_reset"] else left)
-        step = eng.config["episode_steps"] - left
+    def _before(self, env, step):
         if self._step is None or step < self._step:      # the first decision, or a new episode: the replicas drew resets of their own
             env.sync_groups(self.group_size)
             self.syncs += 1
             self._probs = self._best_seq = None
-        if left < 2 or K < 1:
-            self.last, self.last_horizon = None, 0
-            self._probs = self._best_seq = None
-            self._step = step
-            nothing = torch.tensor([self.DO_NOTHING[i] for i in idx], dtype=torch.int32, device=eng.device)
-            return nothing.expand(N, len(idx)).contiguous()
-        probs, best_seq = self._start(step, K)
-        self.last = env.plan_cem_groups(self.group_size, K, self.n_iters, self.n_elite, probs=probs, best_seq=best_seq, seed=self.seed,
-                                        draw=self.draw, alpha=self.alpha, p_min=self.p_min, reward_weights=self.reward_weights,
-                                        gamma=self.gamma, info_weights=self.info_weights)
-        self.draw = (self.draw + 1) & 0xFFFFFFFF
-        self.last_horizon = K
-        self._probs, self._best_seq = self.last.probs, self.last.best_seq
-        return self.last.step_actions
+
+    def _plan(self, env, K, **kw):
+        return env.plan_cem_groups(self.group_size, K, self.n_iters, self.n_elite, **kw)
+
+    def _chosen(self, res):
+        return res.step_actions

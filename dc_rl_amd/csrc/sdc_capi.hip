@@ -1937,7 +1937,7 @@ int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows,
 // The contract and the arithmetic: include/sustaindc_hip.h; the output block and the kernels' plans: sdc_plan.hpp.
 
 // a buffer of the handle's that only grows (hipFree waits for whatever may still use the old one)
-static int plan_grow(sdc_handle* h, unsigned char** buf, size_t* have, const size_t need) {
+static int plan_grow(unsigned char** buf, size_t* have, const size_t need) {
   if (*have >= need) return 0;
   if (*buf) {
     HIP_TRY(hipFree(*buf));
@@ -1948,11 +1948,13 @@ static int plan_grow(sdc_handle* h, unsigned char** buf, size_t* have, const siz
   HIP_TRY(hipMalloc(&q, need));
   *buf = static_cast<unsigned char*>(q);
   *have = need;
-  (void)h;
   return 0;
 }
 
-// What both plan calls refuse about the horizon, the engine and the objective, in sdc_plan's order (`arrays`: the caller's own null
+// a kernel launch's error -> the call's return code, with the message set
+static int launched(const char* kernel, const hipError_t e) { return e != hipSuccess ? fail(kernel, e) : 0; }
+
+// What every plan call refuses about the horizon, the engine and the objective, in sdc_plan's order (`arrays`: the caller's own null
 // check, reported at its place in that order); obj: the objective with the defaults filled in.  -> 0, or -2 with the message set
 static int plan_refused(const char* who, const sdc_handle* h, const int n_steps, const bool arrays, const float* obs, const float* share_obs,
                         const sdc_plan_objective* objective, sdc_plan_objective& obj) {
@@ -1991,15 +1993,21 @@ struct PlanRun {
   SdcPlanScore S;
 };
 
+// the steps of a call of n_steps that the handle's output block holds at a time, the block's layout for them, and the block grown to it
+static int plan_out_block(sdc_handle* h, const int n_steps, int& chunk, SdcPlanBlock& B) {
+  const size_t N = (size_t)h->cfg.n_envs;
+  chunk = sdc_plan_steps_fit(N, n_steps, SDC_PLAN_SCRATCH_BYTES);
+  if (h->cfg.debug_flags & SDC_PLAN_DEBUG_TWO_STEPS) chunk = std::min(chunk, 2);
+  B = sdc_plan_block(N, (size_t)chunk);
+  return plan_grow(&h->plan_out, &h->plan_out_bytes, B.bytes);
+}
+
 // the handle's buffers, before anything is enqueued
 static int plan_prepare(sdc_handle* h, const int n_steps, const sdc_plan_objective& obj, PlanRun& R) {
   const size_t N = (size_t)h->cfg.n_envs;
   R.n_steps = n_steps;
-  R.chunk = sdc_plan_steps_fit(N, n_steps, SDC_PLAN_SCRATCH_BYTES);
-  if (h->cfg.debug_flags & SDC_PLAN_DEBUG_TWO_STEPS) R.chunk = std::min(R.chunk, 2);
-  R.B = sdc_plan_block(N, (size_t)R.chunk);
-  if (plan_grow(h, &h->plan_rows, &h->plan_rows_bytes, N * sdc_mark_row_bytes(n_steps))) return -1;
-  if (plan_grow(h, &h->plan_out, &h->plan_out_bytes, R.B.bytes)) return -1;
+  if (plan_grow(&h->plan_rows, &h->plan_rows_bytes, N * sdc_mark_row_bytes(n_steps))) return -1;
+  if (plan_out_block(h, n_steps, R.chunk, R.B)) return -1;
   h->plan_manifest.resize(N * SDC_MARK_MANIFEST);
   std::memset(&R.S, 0, sizeof(R.S));
   R.S.n_envs = (int)N;
@@ -2012,12 +2020,6 @@ static int plan_prepare(sdc_handle* h, const int n_steps, const sdc_plan_objecti
     R.S.col_weight[j] = obj.col_weight[j];
   }
   return 0;
-}
-
-// the discount table g_k = g_{k-1} * gamma into the pinned side of the plan's stage
-static void plan_discounts(double* const g, const int n_steps, const double gamma) {
-  g[0] = 1.0;
-  for (int k = 1; k < n_steps; k++) g[k] = g[k - 1] * gamma;
 }
 
 // n_steps steps rolled out into the handle's output block (layout B, of `chunk` steps) in chunks, per_chunk(first step, steps) behind each
@@ -2041,27 +2043,64 @@ static int rollout_chunks(sdc_handle* h, const SdcPlanBlock& B, const int n_step
 }
 }  // extern "C++"
 
-// Per candidate: roll out (rollout_chunks), score each chunk, rewind -- from the mark the caller has taken into h->plan_rows.
-static int plan_candidates(sdc_handle* h, PlanRun& R, const void* g_dev, const int n_cand, const int32_t* actions, double* returns,
-                           double* score, float* obs, float* share_obs, void* stream) {
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+// What a plan call works with once it has been let through: the run, the device side of its discount table, the caller's obs /
+// share_obs rows (every rewind refreshes them) and stream
+struct PlanSession {
+  sdc_handle* h;
+  PlanRun R;
+  const void* g_dev;
+  float *obs, *share_obs;
+  void* stream;
+  hipStream_t st() const { return reinterpret_cast<hipStream_t>(stream); }
+};
+
+// Per candidate: roll out (rollout_chunks), score each chunk, rewind -- from the mark the session has taken into h->plan_rows.
+static int plan_candidates(PlanSession& P, const int n_cand, const int32_t* actions, double* returns, double* score) {
+  sdc_handle* const h = P.h;
   const size_t N = (size_t)h->cfg.n_envs;
-  SdcPlanScore& S = R.S;
-  S.g = static_cast<const double*>(g_dev);
+  SdcPlanScore& S = P.R.S;
+  S.g = static_cast<const double*>(P.g_dev);
   int rc = 0;
   for (int c = 0; c < n_cand && rc == 0; c++) {
     S.returns = returns ? returns + (size_t)c * N * 3 : nullptr;
     S.score = score + (size_t)c * N;
-    rc = rollout_chunks(h, R.B, R.n_steps, R.chunk, actions + (size_t)c * (size_t)R.n_steps * N * 3, stream, [&](const int k0, const int steps) {
-      S.first_step = k0;
-      S.steps = steps;
-      const hipError_t e = sdc_plan_score_launch(S, st);
-      return e != hipSuccess ? fail("sdc_plan_score_kernel", e) : 0;
-    });
-    if (rc == 0) rc = sdc_rewind_envs(h, nullptr, (int)N, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
+    rc = rollout_chunks(h, P.R.B, P.R.n_steps, P.R.chunk, actions + (size_t)c * (size_t)P.R.n_steps * N * 3, P.stream,
+                        [&](const int k0, const int steps) {
+                          S.first_step = k0;
+                          S.steps = steps;
+                          return launched("sdc_plan_score_kernel", sdc_plan_score_launch(S, P.st()));
+                        });
+    if (rc == 0) rc = sdc_rewind_envs(h, nullptr, (int)N, h->plan_rows, h->plan_manifest.data(), P.obs, P.share_obs, P.stream);
   }
   return rc;
 }
+
+// What the three plan calls do alike once their arguments have passed (plan_refused and their own checks): the handle's buffers, the
+// discount table g_k = g_{k-1} * gamma through the plan's stage -- the slot stays in flight until the last kernel that reads it --, the
+// mark of the whole batch, and then body(session) -> rc, which enqueues the call's own work.  One mark serves every rollout of the
+// call: a rewind keeps its mark alive.
+extern "C++" {
+template <class Body>
+static int plan_session(sdc_handle* h, const int n_steps, const sdc_plan_objective& obj, float* obs, float* share_obs, void* stream,
+                        Body&& body) {
+  HIP_TRY(hipSetDevice(h->device));
+  PlanSession P{h, {}, nullptr, obs, share_obs, stream};
+  if (plan_prepare(h, n_steps, obj, P.R)) return -1;
+  void* pin = nullptr;
+  if (stage_acquire(h, h->plan_stage, &pin)) return -1;
+  double* const g = static_cast<double*>(pin);
+  g[0] = 1.0;
+  for (int k = 1; k < n_steps; k++) g[k] = g[k - 1] * obj.gamma;
+  int rc = 0;
+  const int staged = stage_commit(h, h->plan_stage, (size_t)n_steps, P.st(), [&](const void* g_dev) {
+    P.g_dev = g_dev;
+    rc = sdc_mark_envs(h, nullptr, h->cfg.n_envs, n_steps, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
+    if (rc == 0) rc = body(P);
+    return hipSuccess;
+  });
+  return rc ? rc : staged;
+}
+}  // extern "C++"
 
 // Mark, the candidates (plan_candidates), select.  Whatever the entry points underneath would refuse is refused here first.
 int sdc_plan(sdc_handle* h, int n_cand, int n_steps, const int32_t* actions, const sdc_plan_objective* objective, double* returns,
@@ -2070,141 +2109,145 @@ int sdc_plan(sdc_handle* h, int n_cand, int n_steps, const int32_t* actions, con
   if (n_cand < 1) return fail_msg("sdc_plan: n_cand = " + std::to_string(n_cand) + " must be positive");
   sdc_plan_objective obj;
   if (plan_refused("sdc_plan", h, n_steps, actions && score && best && best_action, obs, share_obs, objective, obj)) return -2;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const size_t N = (size_t)h->cfg.n_envs;
-  PlanRun R;
-  if (plan_prepare(h, n_steps, obj, R)) return -1;
-  // the discount table through the plan's stage; the slot stays in flight until the last kernel that reads it
-  void* pin = nullptr;
-  if (stage_acquire(h, h->plan_stage, &pin)) return -1;
-  plan_discounts(static_cast<double*>(pin), n_steps, obj.gamma);
-  int rc = 0;
-  const int staged = stage_commit(h, h->plan_stage, (size_t)n_steps, st, [&](const void* g_dev) {
-    rc = sdc_mark_envs(h, nullptr, (int)N, n_steps, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
-    if (rc == 0) rc = plan_candidates(h, R, g_dev, n_cand, actions, returns, score, obs, share_obs, stream);
-    if (rc == 0) {
-      const SdcPlanSelect Q{(int)N, n_cand, n_steps, score, actions, best, best_action};
-      const hipError_t e = sdc_plan_select_launch(Q, st);
-      if (e != hipSuccess) rc = fail("sdc_plan_select_kernel", e);
-    }
-    return hipSuccess;
+  const SdcPlanSelect Q{h->cfg.n_envs, n_cand, n_steps, score, actions, best, best_action};
+  return plan_session(h, n_steps, obj, obs, share_obs, stream, [&](PlanSession& P) {
+    const int rc = plan_candidates(P, n_cand, actions, returns, score);
+    return rc ? rc : launched("sdc_plan_select_kernel", sdc_plan_select_launch(Q, P.st()));
   });
-  return rc ? rc : staged;
 }
 
-// ---- plan with the cross-entropy method (sdc_cem.hip) -------------------------------------------------------------------------------
-// The contract and the arithmetic: include/sustaindc_hip.h; the kernels' plans: sdc_cem.hpp.  One mark serves every rollout of every
-// iteration: a rewind keeps its mark alive.
-int sdc_plan_cem(sdc_handle* h, int n_steps, const sdc_cem_params* cem, const sdc_plan_objective* objective, double* probs,
-                 int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* cand, double* cand_score, float* obs,
-                 float* share_obs, void* stream) {
-  static const char* const who = "sdc_plan_cem";
-  if (!h) return fail_msg("sdc_plan_cem: null handle");
-  if (!cem) return fail_msg("sdc_plan_cem: null cem");
-  const sdc_cem_params c = *cem;
-  if (c.n_iters < 1) return fail_msg("sdc_plan_cem: n_iters = " + std::to_string(c.n_iters) + " must be positive");
-  if (c.iter0 < 0 || (long long)c.iter0 + c.n_iters > 65536)
-    return fail_msg("sdc_plan_cem: iter0 = " + std::to_string(c.iter0) + " with n_iters = " + std::to_string(c.n_iters) +
-                    " outside [0, 65536]");
-  if (c.n_cand < 2 || c.n_cand > SDC_CEM_MAX_CAND)
-    return fail_msg("sdc_plan_cem: n_cand = " + std::to_string(c.n_cand) + " outside [2, " + std::to_string(SDC_CEM_MAX_CAND) + "]");
-  if (c.n_elite < 1 || c.n_elite > c.n_cand)
-    return fail_msg("sdc_plan_cem: n_elite = " + std::to_string(c.n_elite) + " outside [1, n_cand = " + std::to_string(c.n_cand) + "]");
+// ---- plan with the cross-entropy method (sdc_cem.hip, sdc_cem_groups.hip) -----------------------------------------------------------
+// The contract and the arithmetic: include/sustaindc_hip.h; the kernels' plans: sdc_cem.hpp, sdc_cem_groups.hpp.
+
+// The parameter ranges sdc_plan_cem and sdc_plan_cem_groups refuse alike (w: the caller's "who: "), each -> 0, or -2 with the message
+// set.  The callers run them in their own order, with their own checks in between.
+static int cem_iters_refused(const std::string& w, const int n_iters, const int iter0) {
+  if (n_iters < 1) return fail_msg(w + "n_iters = " + std::to_string(n_iters) + " must be positive");
+  if (iter0 < 0 || (long long)iter0 + n_iters > 65536)
+    return fail_msg(w + "iter0 = " + std::to_string(iter0) + " with n_iters = " + std::to_string(n_iters) + " outside [0, 65536]");
+  return 0;
+}
+// (the population the elites are taken from: its name and size)
+static int cem_elite_refused(const std::string& w, const int n_elite, const char* pop, const int size) {
+  if (n_elite < 1 || n_elite > size)
+    return fail_msg(w + "n_elite = " + std::to_string(n_elite) + " outside [1, " + pop + " = " + std::to_string(size) + "]");
+  return 0;
+}
+static int cem_refit_refused(const std::string& w, const int32_t* fixed_action, const double alpha, const double p_min) {
   for (int a = 0; a < 3; a++)
-    if (c.fixed_action[a] < -1 || c.fixed_action[a] > 2)
-      return fail_msg("sdc_plan_cem: fixed_action[" + std::to_string(a) + "] = " + std::to_string(c.fixed_action[a]) + " outside [-1, 2]");
-  if (!(c.alpha >= 0.0 && c.alpha < 1.0)) return fail_msg("sdc_plan_cem: alpha = " + std::to_string(c.alpha) + " outside [0, 1)");
-  if (!(c.p_min >= 0.0 && c.p_min <= 1.0 / 3.0)) return fail_msg("sdc_plan_cem: p_min = " + std::to_string(c.p_min) + " outside [0, 1/3]");
-  sdc_plan_objective obj;
-  if (plan_refused(who, h, n_steps, probs && best_seq && best_score && best_action && cand && cand_score, obs, share_obs, objective, obj))
-    return -2;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const size_t N = (size_t)h->cfg.n_envs;
-  PlanRun R;
-  if (plan_prepare(h, n_steps, obj, R)) return -1;
-  SdcCemSample Q;
+    if (fixed_action[a] < -1 || fixed_action[a] > 2)
+      return fail_msg(w + "fixed_action[" + std::to_string(a) + "] = " + std::to_string(fixed_action[a]) + " outside [-1, 2]");
+  if (!(alpha >= 0.0 && alpha < 1.0)) return fail_msg(w + "alpha = " + std::to_string(alpha) + " outside [0, 1)");
+  if (!(p_min >= 0.0 && p_min <= 1.0 / 3.0)) return fail_msg(w + "p_min = " + std::to_string(p_min) + " outside [0, 1/3]");
+  return 0;
+}
+
+extern "C++" {
+// the fields the per-env and the group kernels' plans share, from the fields the two parameter structs share
+template <class Sample, class Params>
+static Sample cem_sample_plan(const int n_envs, const int n_steps, const Params& c, const double* probs, const int32_t* best_seq, int32_t* cand) {
+  Sample Q;
   std::memset(&Q, 0, sizeof(Q));
-  Q.n_envs = (int)N;
-  Q.n_cand = c.n_cand;
+  Q.n_envs = n_envs;
   Q.n_steps = n_steps;
-  Q.env_base = h->cfg.env_index_base;
   Q.draw = c.draw;
   Q.key0 = (unsigned)c.seed;
   Q.key1 = (unsigned)(c.seed >> 32);
   Q.probs = probs;
   Q.best_seq = best_seq;
   Q.cand = cand;
-  SdcCemRefit F;
+  for (int a = 0; a < 3; a++) Q.fixed[a] = c.fixed_action[a];
+  return Q;
+}
+template <class Refit, class Params>
+static Refit cem_refit_plan(const int n_envs, const int n_steps, const Params& c, const double* score, const int32_t* cand, double* probs,
+                            int32_t* best_seq, int32_t* best_action) {
+  Refit F;
   std::memset(&F, 0, sizeof(F));
-  F.n_envs = (int)N;
-  F.n_cand = c.n_cand;
+  F.n_envs = n_envs;
   F.n_steps = n_steps;
   F.n_elite = c.n_elite;
   F.alpha = c.alpha;
   F.take = 1.0 - c.alpha;
   F.p_min = c.p_min;
-  F.score = cand_score;
+  F.score = score;
   F.cand = cand;
   F.probs = probs;
   F.best_seq = best_seq;
   F.best_action = best_action;
-  for (int a = 0; a < 3; a++) Q.fixed[a] = F.fixed[a] = c.fixed_action[a];
-  void* pin = nullptr;
-  if (stage_acquire(h, h->plan_stage, &pin)) return -1;
-  plan_discounts(static_cast<double*>(pin), n_steps, obj.gamma);
-  int rc = 0;
-  const int staged = stage_commit(h, h->plan_stage, (size_t)n_steps, st, [&](const void* g_dev) {
-    rc = sdc_mark_envs(h, nullptr, (int)N, n_steps, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
-    for (int i = 0; i < c.n_iters && rc == 0; i++) {
-      Q.c3 = ((unsigned)(c.iter0 + i) << 16) | SDC_CEM_STREAM;
-      hipError_t e = sdc_cem_sample_launch(Q, st);
-      if (e != hipSuccess) rc = fail("sdc_cem_sample_kernel", e);
-      if (rc == 0) rc = plan_candidates(h, R, g_dev, c.n_cand, cand, nullptr, cand_score, obs, share_obs, stream);
-      if (rc == 0) {
-        F.last = i == c.n_iters - 1;
-        F.best_score = best_score + (size_t)i * N;
-        e = sdc_cem_refit_launch(F, st);
-        if (e != hipSuccess) rc = fail("sdc_cem_refit_kernel", e);
-      }
-    }
-    return hipSuccess;
-  });
-  return rc ? rc : staged;
+  for (int a = 0; a < 3; a++) F.fixed[a] = c.fixed_action[a];
+  return F;
 }
 
-// ---- plan with the cross-entropy method over replica groups (sdc_cem_groups.hip) -----------------------------------------------------
-// The contract and the arithmetic: include/sustaindc_hip.h; the kernels' plans: sdc_cem_groups.hpp.  sdc_plan_cem with the candidates
-// in env slots: per iteration ONE rollout of the whole batch (plan_candidates with the single "candidate" cand) between the group
-// sample and the group refit kernel.
+// The iterations of a CEM call: the sample launch of plan Q with the iteration's counter word, the rollouts of the n_cand candidate
+// arrays in `cand` (plan_candidates), the refit launch of plan F with the iteration's row of best_score, `stride` entries long
+template <class Sample, class Refit>
+static int cem_iterations(PlanSession& P, const int n_iters, const int iter0, const int n_cand, const int32_t* cand, double* cand_score,
+                          double* best_score, const size_t stride, Sample& Q, hipError_t (*sample)(const Sample&, hipStream_t),
+                          const char* sample_kernel, Refit& F, hipError_t (*refit)(const Refit&, hipStream_t), const char* refit_kernel) {
+  int rc = 0;
+  for (int i = 0; i < n_iters && rc == 0; i++) {
+    Q.c3 = ((unsigned)(iter0 + i) << 16) | SDC_CEM_STREAM;
+    rc = launched(sample_kernel, sample(Q, P.st()));
+    if (rc == 0) rc = plan_candidates(P, n_cand, cand, nullptr, cand_score);
+    if (rc == 0) {
+      F.last = i == n_iters - 1;
+      F.best_score = best_score + (size_t)i * stride;
+      rc = launched(refit_kernel, refit(F, P.st()));
+    }
+  }
+  return rc;
+}
+}  // extern "C++"
+
+int sdc_plan_cem(sdc_handle* h, int n_steps, const sdc_cem_params* cem, const sdc_plan_objective* objective, double* probs,
+                 int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* cand, double* cand_score, float* obs,
+                 float* share_obs, void* stream) {
+  static const std::string w = "sdc_plan_cem: ";
+  if (!h) return fail_msg(w + "null handle");
+  if (!cem) return fail_msg(w + "null cem");
+  const sdc_cem_params c = *cem;
+  if (cem_iters_refused(w, c.n_iters, c.iter0)) return -2;
+  if (c.n_cand < 2 || c.n_cand > SDC_CEM_MAX_CAND)
+    return fail_msg(w + "n_cand = " + std::to_string(c.n_cand) + " outside [2, " + std::to_string(SDC_CEM_MAX_CAND) + "]");
+  if (cem_elite_refused(w, c.n_elite, "n_cand", c.n_cand) || cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min)) return -2;
+  sdc_plan_objective obj;
+  if (plan_refused("sdc_plan_cem", h, n_steps, probs && best_seq && best_score && best_action && cand && cand_score, obs, share_obs,
+                   objective, obj))
+    return -2;
+  const int N = h->cfg.n_envs;
+  SdcCemSample Q = cem_sample_plan<SdcCemSample>(N, n_steps, c, probs, best_seq, cand);
+  Q.n_cand = c.n_cand;
+  Q.env_base = h->cfg.env_index_base;
+  SdcCemRefit F = cem_refit_plan<SdcCemRefit>(N, n_steps, c, cand_score, cand, probs, best_seq, best_action);
+  F.n_cand = c.n_cand;
+  return plan_session(h, n_steps, obj, obs, share_obs, stream, [&](PlanSession& P) {
+    return cem_iterations(P, c.n_iters, c.iter0, c.n_cand, cand, cand_score, best_score, (size_t)N, Q, sdc_cem_sample_launch,
+                          "sdc_cem_sample_kernel", F, sdc_cem_refit_launch, "sdc_cem_refit_kernel");
+  });
+}
+
+// sdc_plan_cem with the candidates in env slots: per iteration ONE rollout of the whole batch (plan_candidates with the single
+// "candidate" cand) between the group sample and the group refit kernel.
 int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* cem, const sdc_plan_objective* objective, double* probs,
                         int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* step_actions, int32_t* cand,
                         double* cand_score, float* obs, float* share_obs, void* stream) {
-  static const char* const who = "sdc_plan_cem_groups";
-  const std::string w = std::string(who) + ": ";
+  static const std::string w = "sdc_plan_cem_groups: ";
   if (!h) return fail_msg(w + "null handle");
   if (!cem) return fail_msg(w + "null cem");
   const sdc_cem_group_params c = *cem;
   const int N = h->cfg.n_envs;
-  if (c.n_iters < 1) return fail_msg(w + "n_iters = " + std::to_string(c.n_iters) + " must be positive");
-  if (c.iter0 < 0 || (long long)c.iter0 + c.n_iters > 65536)
-    return fail_msg(w + "iter0 = " + std::to_string(c.iter0) + " with n_iters = " + std::to_string(c.n_iters) + " outside [0, 65536]");
+  if (cem_iters_refused(w, c.n_iters, c.iter0)) return -2;
   if (c.group_size < 2 || c.group_size > SDC_CEM_MAX_GROUP)
     return fail_msg(w + "group_size = " + std::to_string(c.group_size) + " outside [2, " + std::to_string(SDC_CEM_MAX_GROUP) + "]");
   if (N % c.group_size != 0)
     return fail_msg(w + "n_envs = " + std::to_string(N) + " is not a multiple of group_size = " + std::to_string(c.group_size));
-  if (c.n_elite < 1 || c.n_elite > c.group_size)
-    return fail_msg(w + "n_elite = " + std::to_string(c.n_elite) + " outside [1, group_size = " + std::to_string(c.group_size) + "]");
+  if (cem_elite_refused(w, c.n_elite, "group_size", c.group_size)) return -2;
   if (c.group_base < 0) return fail_msg(w + "group_base = " + std::to_string(c.group_base) + " is negative");
-  for (int a = 0; a < 3; a++)
-    if (c.fixed_action[a] < -1 || c.fixed_action[a] > 2)
-      return fail_msg(w + "fixed_action[" + std::to_string(a) + "] = " + std::to_string(c.fixed_action[a]) + " outside [-1, 2]");
-  if (!(c.alpha >= 0.0 && c.alpha < 1.0)) return fail_msg(w + "alpha = " + std::to_string(c.alpha) + " outside [0, 1)");
-  if (!(c.p_min >= 0.0 && c.p_min <= 1.0 / 3.0)) return fail_msg(w + "p_min = " + std::to_string(c.p_min) + " outside [0, 1/3]");
+  if (cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min)) return -2;
   sdc_plan_objective obj;
-  if (plan_refused(who, h, n_steps, probs && best_seq && best_score && best_action && step_actions && cand && cand_score, obs, share_obs,
-                   objective, obj))
+  if (plan_refused("sdc_plan_cem_groups", h, n_steps, probs && best_seq && best_score && best_action && step_actions && cand && cand_score,
+                   obs, share_obs, objective, obj))
     return -2;
   // what the host mirrors know of a group's replicas: the episode step, the config, the trace set, the feature-row flag
   const int R = c.group_size, G = N / R;
@@ -2222,66 +2265,21 @@ int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* 
       return fail_msg(w + "group " + std::to_string(e / R) + " is out of step: env " + std::to_string(e) + " and its group's first env " +
                       std::to_string(l) + " differ in " + what + " (the replicas of a group hold one state: sdc_clone_envs)");
   }
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  PlanRun Rn;
-  if (plan_prepare(h, n_steps, obj, Rn)) return -1;
-  SdcCemGroupSample Q;
-  std::memset(&Q, 0, sizeof(Q));
-  Q.n_envs = N;
-  Q.group_size = R;
-  Q.n_groups = G;
-  Q.n_steps = n_steps;
+  SdcCemGroupSample Q = cem_sample_plan<SdcCemGroupSample>(N, n_steps, c, probs, best_seq, cand);
+  SdcCemGroupRefit F = cem_refit_plan<SdcCemGroupRefit>(N, n_steps, c, cand_score, cand, probs, best_seq, best_action);
+  Q.group_size = F.group_size = R;
+  Q.n_groups = F.n_groups = G;
   Q.group_base = c.group_base;
-  Q.draw = c.draw;
-  Q.key0 = (unsigned)c.seed;
-  Q.key1 = (unsigned)(c.seed >> 32);
-  Q.probs = probs;
-  Q.best_seq = best_seq;
-  Q.cand = cand;
-  SdcCemGroupRefit F;
-  std::memset(&F, 0, sizeof(F));
-  F.n_envs = N;
-  F.group_size = R;
-  F.n_groups = G;
-  F.n_steps = n_steps;
-  F.n_elite = c.n_elite;
-  F.alpha = c.alpha;
-  F.take = 1.0 - c.alpha;
-  F.p_min = c.p_min;
-  F.score = cand_score;
-  F.cand = cand;
-  F.probs = probs;
-  F.best_seq = best_seq;
-  F.best_action = best_action;
   F.step_actions = step_actions;
-  for (int a = 0; a < 3; a++) Q.fixed[a] = F.fixed[a] = c.fixed_action[a];
-  void* pin = nullptr;
-  if (stage_acquire(h, h->plan_stage, &pin)) return -1;
-  plan_discounts(static_cast<double*>(pin), n_steps, obj.gamma);
-  int rc = 0;
-  const int staged = stage_commit(h, h->plan_stage, (size_t)n_steps, st, [&](const void* g_dev) {
-    rc = sdc_mark_envs(h, nullptr, N, n_steps, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
-    for (int i = 0; i < c.n_iters && rc == 0; i++) {
-      Q.c3 = ((unsigned)(c.iter0 + i) << 16) | SDC_CEM_STREAM;
-      hipError_t e = sdc_cem_group_sample_launch(Q, st);
-      if (e != hipSuccess) rc = fail("sdc_cem_group_sample_kernel", e);
-      if (rc == 0) rc = plan_candidates(h, Rn, g_dev, 1, cand, nullptr, cand_score, obs, share_obs, stream);
-      if (rc == 0) {
-        F.last = i == c.n_iters - 1;
-        F.best_score = best_score + (size_t)i * (size_t)G;
-        e = sdc_cem_group_refit_launch(F, st);
-        if (e != hipSuccess) rc = fail("sdc_cem_group_refit_kernel", e);
-      }
-    }
-    return hipSuccess;
+  return plan_session(h, n_steps, obj, obs, share_obs, stream, [&](PlanSession& P) {
+    return cem_iterations(P, c.n_iters, c.iter0, 1, cand, cand_score, best_score, (size_t)G, Q, sdc_cem_group_sample_launch,
+                          "sdc_cem_group_sample_kernel", F, sdc_cem_group_refit_launch, "sdc_cem_group_refit_kernel");
   });
-  return rc ? rc : staged;
 }
 
 // ---- episode statistics (sdc_stats.hip) ---------------------------------------------------------------------------------------------
 // The contract and the arithmetic: include/sustaindc_hip.h; the kernels' plans and the lane mapping: sdc_stats.hpp.  The rollouts go
-// into the plan calls' output block (rollout_chunks); nothing is marked or rewound.
+// into the plan calls' output block (plan_out_block, rollout_chunks); nothing is marked or rewound.
 int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int accumulate, double* stats, double* returns,
                       int32_t* counts, float* obs, float* share_obs, float* rew, uint8_t* done, float* info, float* final_obs,
                       void* stream) {
@@ -2303,10 +2301,9 @@ int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int ac
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t N = (size_t)h->cfg.n_envs;
-  int chunk = sdc_plan_steps_fit(N, n_steps, SDC_PLAN_SCRATCH_BYTES);
-  if (h->cfg.debug_flags & SDC_PLAN_DEBUG_TWO_STEPS) chunk = std::min(chunk, 2);
-  const SdcPlanBlock B = sdc_plan_block(N, (size_t)chunk);
-  if (plan_grow(h, &h->plan_out, &h->plan_out_bytes, B.bytes)) return -1;
+  int chunk;
+  SdcPlanBlock B;
+  if (plan_out_block(h, n_steps, chunk, B)) return -1;
   unsigned char* const out = h->plan_out;
   SdcStatsReduce S;
   std::memset(&S, 0, sizeof(S));
@@ -2320,8 +2317,7 @@ int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int ac
   const int rc = rollout_chunks(h, B, n_steps, chunk, actions, stream, [&](const int k0, const int steps) {
     S.steps = last_steps = steps;
     S.init = (k0 == 0 && accumulate == 0) ? 1 : 0;
-    const hipError_t e = sdc_stats_reduce_launch(S, st);
-    return e != hipSuccess ? fail("sdc_stats_reduce_kernel", e) : 0;
+    return launched("sdc_stats_reduce_kernel", sdc_stats_reduce_launch(S, st));
   });
   if (rc) return rc;
   const size_t last = (size_t)(last_steps - 1) * N;      // the LAST step's slices of the last chunk
@@ -2340,8 +2336,7 @@ int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int ac
   Q.o_info = info;
   Q.o_done = done;
   Q.o_final_obs = final_obs;
-  const hipError_t e = sdc_stats_last_launch(Q, st);
-  return e != hipSuccess ? fail("sdc_stats_last_kernel", e) : 0;
+  return launched("sdc_stats_last_kernel", sdc_stats_last_launch(Q, st));
 }
 
 }  // extern "C"

@@ -197,6 +197,21 @@ class EpisodeStats:
         return {"per_env": per_env, "batch": batch, "steps": self.steps.cpu().numpy(), "fault": self.fault.cpu().numpy()}
 
 
+def group_sync_pairs(group_size, n, n_name):
+    """sync_groups' clone pairs for `n` envs in groups of `group_size`: (src, dst), every env but a group's first and that first env;
+    ValueError in sync_groups' words, with the caller's name `n_name` for its env count"""
+    R = int(group_size)
+    if R < 2 or R > n or n % R:
+        raise ValueError(f"sync_groups: group_size = {R} must be at least 2 and divide {n_name} = {n}")
+    e = np.arange(n, dtype=np.int32)
+    dst = e[e % R != 0]
+    return dst - dst % R, dst
+
+
+def _p(x):
+    return C.c_void_p(x.data_ptr())
+
+
 def plan_objective(reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None) -> L.SdcPlanObjective:
     """plan's objective as the library's struct; ValueError for anything but three reward weights, an unknown info key, more than
     PLAN_MAX_COLS keys (gamma is the library's to refuse)."""
@@ -856,19 +871,77 @@ class SdcEngine:
         if K > L.MARK_MAX_STEPS:
             raise ValueError(f"plan: K = {K} is more than a mark holds (MARK_MAX_STEPS = {L.MARK_MAX_STEPS})")
         obj = plan_objective(reward_weights, gamma, info_weights)
-        p = lambda x: C.c_void_p(x.data_ptr())
         with t.cuda.device(self.device):
             returns = t.empty((M, N, L.N_AGENTS), dtype=t.float64, device=self.device)
             score = t.empty((M, N), dtype=t.float64, device=self.device)
             best = t.empty((N,), dtype=t.int32, device=self.device)
             action = t.empty((N, 3), dtype=t.int32, device=self.device)
-            rc = self.lib.sdc_plan(self._h, M, K, p(actions), C.byref(obj), p(returns), p(score), p(best), p(action), p(self.obs),
-                                   p(self.share_obs), self._stream())
+            rc = self.lib.sdc_plan(self._h, M, K, _p(actions), C.byref(obj), _p(returns), _p(score), _p(best), _p(action), _p(self.obs),
+                                   _p(self.share_obs), self._stream())
         self._refused(rc)
-        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse them before)
-            for x in (returns, score, best, action, actions):
-                x.record_stream(self._pinned_stream_obj)
+        self._written_on_pinned_stream(returns, score, best, action, actions)
         return PlanResult(best, action, score, returns)
+
+    def _written_on_pinned_stream(self, *arrays):
+        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse them before)
+            for x in arrays:
+                x.record_stream(self._pinned_stream_obj)
+
+    def _behind_torch_stream(self):
+        """tensors filled by torch ops on torch's current stream are about to be read by a kernel on the pinned one: order it behind them"""
+        if self._pinned_stream_obj is not None:
+            self._pinned_stream_obj.wait_stream(self.torch.cuda.current_stream(self.device))
+
+    def _cem_fixed(self, who, fixed_action, seed, draw):
+        """fixed_action as three ints; the ValueErrors both CEM calls raise first"""
+        fixed = [int(x) for x in fixed_action]
+        if len(fixed) != 3:
+            raise ValueError(f"{who}: fixed_action must be three integers (ls, dc, bat), got {len(fixed)}")
+        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(draw) < 1 << 32:
+            raise ValueError(f"{who}: seed must fit 64 bits and draw 32, both unsigned")
+        return fixed
+
+    def _cem(self, who, fn, cem, fixed, K, lead, outputs, result, sized, check, sizes, n_iters, n_elite, probs, best_seq, seed, draw, iter0,
+             alpha, p_min, reward_weights, gamma, info_weights):
+        """The CEM call of plan_cem and plan_cem_groups: library function `fn` with `cem`, its params struct with the caller's own
+        fields set (the shared ones are filled here), probs [K, lead, 3, 3] / best_seq [K, lead, 3] -- a caller's are validated if
+        `check` -- and, behind them, new tensors of `outputs`' (shape, dtype); -> result(*the arrays in the library's order).  Not
+        `sized` (sizes no array can be given): the library is called with null arrays and words the refusal; it looks at the sizes
+        before the arrays."""
+        t = self.torch
+
+        def given(x, name, dtype, shape):
+            if not (isinstance(x, t.Tensor) and x.dtype == dtype and x.is_cuda and x.is_contiguous() and tuple(x.shape) == shape):
+                raise ValueError(f"{who}: {name} must be a contiguous {str(dtype).split('.')[-1]} CUDA tensor of shape {shape}")
+            if x.device != self.device:
+                raise ValueError(f"{who}: {name} is on {x.device}, this engine runs on {self.device}")
+
+        if check and probs is not None:
+            given(probs, "probs", t.float64, (K, lead, 3, 3))
+        if check and best_seq is not None:
+            given(best_seq, "best_seq", t.int32, (K, lead, 3))
+        obj = plan_objective(reward_weights, gamma, info_weights)
+        cem.n_iters, cem.iter0, cem.n_elite = int(n_iters), int(iter0), int(n_elite)
+        cem.fixed_action[:] = fixed
+        cem.draw, cem.seed, cem.alpha, cem.p_min = int(draw), int(seed), float(alpha), float(p_min)
+        with t.cuda.device(self.device):
+            if sized:
+                # (probs and best_seq -- the defaults below, a caller's, CEMMPCAgent's shifted ones -- are read by the sample kernel)
+                self._behind_torch_stream()
+                if probs is None:
+                    probs = t.full((K, lead, 3, 3), 1.0 / 3.0, dtype=t.float64, device=self.device)
+                if best_seq is None:
+                    best_seq = t.tensor([1, 1, 2], dtype=t.int32, device=self.device).expand(K, lead, 3).contiguous()
+                arrays = [probs, best_seq] + [t.empty(shape, dtype=dtype, device=self.device) for shape, dtype in outputs]
+                ptrs = [_p(x) for x in arrays]
+            else:
+                arrays, ptrs = [], [None] * (2 + len(outputs))
+            rc = fn(self._h, K, C.byref(cem), C.byref(obj), *ptrs, _p(self.obs), _p(self.share_obs), self._stream())
+            if not sized and rc == 0:
+                raise L.SdcError(f"{who}: {fn.__name__} accepted {sizes} and no arrays")
+        self._refused(rc)
+        self._written_on_pinned_stream(*arrays)
+        return result(*arrays)
 
     def plan_cem(self, horizon: int, n_iters: int, n_candidates: int, n_elite: int, *, probs=None, best_seq=None, seed: int = 0,
                  draw: int = 0, iter0: int = 0, alpha: float = 0.0, p_min: float = 0.0, fixed_action=(-1, -1, -1),
@@ -891,70 +964,23 @@ class SdcEngine:
         fixed_action outside [-1, 2]; alpha outside [0, 1); p_min outside [0, 1/3]."""
         t = self.torch
         K, N, M, n_it = int(horizon), self.n_envs, int(n_candidates), int(n_iters)
-        fixed = [int(x) for x in fixed_action]
-        if len(fixed) != 3:
-            raise ValueError(f"plan_cem: fixed_action must be three integers (ls, dc, bat), got {len(fixed)}")
-        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(draw) < 1 << 32:
-            raise ValueError("plan_cem: seed must fit 64 bits and draw 32, both unsigned")
-
-        def given(x, name, dtype, shape):
-            if not (isinstance(x, t.Tensor) and x.dtype == dtype and x.is_cuda and x.is_contiguous() and tuple(x.shape) == shape):
-                raise ValueError(f"plan_cem: {name} must be a contiguous {str(dtype).split('.')[-1]} CUDA tensor of shape {shape}")
-            if x.device != self.device:
-                raise ValueError(f"plan_cem: {name} is on {x.device}, this engine runs on {self.device}")
-            return x
-
-        if probs is not None:
-            given(probs, "probs", t.float64, (K, N, 3, 3))
-        if best_seq is not None:
-            given(best_seq, "best_seq", t.int32, (K, N, 3))
-        obj = plan_objective(reward_weights, gamma, info_weights)
+        fixed = self._cem_fixed("plan_cem", fixed_action, seed, draw)
         cem = L.SdcCemParams()
-        cem.n_iters, cem.iter0, cem.n_cand, cem.n_elite = n_it, int(iter0), M, int(n_elite)
-        cem.fixed_action[:] = fixed
-        cem.draw, cem.seed, cem.alpha, cem.p_min = int(draw), int(seed), float(alpha), float(p_min)
-        p = lambda x: C.c_void_p(x.data_ptr())
+        cem.n_cand = M
         sized = 1 <= K <= L.MARK_MAX_STEPS and 2 <= M <= L.CEM_MAX_CAND and n_it >= 1 and 0 <= int(iter0) <= L.CEM_MAX_ITERS - n_it
-        with t.cuda.device(self.device):
-            if sized:
-                if self._pinned_stream_obj is not None:
-                    # (probs and best_seq -- the defaults below, a caller's, CEMMPCAgent's shifted ones -- are filled by torch ops on
-                    #  torch's current stream and read by the sample kernel on the pinned one: order it behind them)
-                    self._pinned_stream_obj.wait_stream(t.cuda.current_stream(self.device))
-                if probs is None:
-                    probs = t.full((K, N, 3, 3), 1.0 / 3.0, dtype=t.float64, device=self.device)
-                if best_seq is None:
-                    best_seq = t.tensor([1, 1, 2], dtype=t.int32, device=self.device).expand(K, N, 3).contiguous()
-                best_score = t.empty((n_it, N), dtype=t.float64, device=self.device)
-                action = t.empty((N, 3), dtype=t.int32, device=self.device)
-                cand = t.empty((M, K, N, 3), dtype=t.int32, device=self.device)
-                cand_score = t.empty((M, N), dtype=t.float64, device=self.device)
-                arrays = (probs, best_seq, best_score, action, cand, cand_score)
-                rc = self.lib.sdc_plan_cem(self._h, K, C.byref(cem), C.byref(obj), *[p(x) for x in arrays], p(self.obs), p(self.share_obs),
-                                           self._stream())
-            else:      # (sizes no array can be given: the library words the refusal, and it looks at the sizes before the arrays)
-                arrays = ()
-                rc = self.lib.sdc_plan_cem(self._h, K, C.byref(cem), C.byref(obj), None, None, None, None, None, None, p(self.obs),
-                                           p(self.share_obs), self._stream())
-                if rc == 0:
-                    raise L.SdcError(f"plan_cem: sdc_plan_cem accepted K = {K}, M = {M}, I = {n_it}, iter0 = {int(iter0)} and no arrays")
-        self._refused(rc)
-        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse them before)
-            for x in arrays:
-                x.record_stream(self._pinned_stream_obj)
-        return CEMResult(action, best_seq, best_score, probs, cand, cand_score)
+        outputs = [((n_it, N), t.float64), ((N, 3), t.int32), ((M, K, N, 3), t.int32), ((M, N), t.float64)]
+        return self._cem("plan_cem", self.lib.sdc_plan_cem, cem, fixed, K, N, outputs,
+                         lambda probs, best_seq, best_score, action, cand, cand_score:
+                         CEMResult(action, best_seq, best_score, probs, cand, cand_score),
+                         sized, True, f"K = {K}, M = {M}, I = {n_it}, iter0 = {int(iter0)}", n_it, n_elite, probs, best_seq, seed, draw,
+                         iter0, alpha, p_min, reward_weights, gamma, info_weights)
 
     def sync_groups(self, group_size: int):
         """Every group of `group_size` consecutive envs becomes a copy of its first env: one clone_envs call with the leaders as sources
         (the replicas finish the leader's episode exactly; their own resets stay keyed on their own global indices, so call this again
         after a reset or auto-reset).  What plan_cem_groups asks of the batch.  ValueError for a group_size that is not in [2, n_envs]
         or does not divide n_envs, and what clone_envs refuses.  -> (obs, share_obs) views."""
-        R = int(group_size)
-        if R < 2 or R > self.n_envs or self.n_envs % R:
-            raise ValueError(f"sync_groups: group_size = {R} must be at least 2 and divide n_envs = {self.n_envs}")
-        e = np.arange(self.n_envs, dtype=np.int32)
-        dst = e[e % R != 0]
-        return self.clone_envs(dst - dst % R, dst)
+        return self.clone_envs(*group_sync_pairs(group_size, self.n_envs, "n_envs"))
 
     def plan_cem_groups(self, group_size: int, horizon: int, n_iters: int, n_elite: int, *, probs=None, best_seq=None, seed: int = 0,
                         draw: int = 0, iter0: int = 0, alpha: float = 0.0, p_min: float = 0.0, fixed_action=(-1, -1, -1),
@@ -977,11 +1003,7 @@ class SdcEngine:
         N; E outside [1, R]; a negative group_base; a group out of step."""
         t = self.torch
         K, N, R, n_it = int(horizon), self.n_envs, int(group_size), int(n_iters)
-        fixed = [int(x) for x in fixed_action]
-        if len(fixed) != 3:
-            raise ValueError(f"plan_cem_groups: fixed_action must be three integers (ls, dc, bat), got {len(fixed)}")
-        if not 0 <= int(seed) < 1 << 64 or not 0 <= int(draw) < 1 << 32:
-            raise ValueError("plan_cem_groups: seed must fit 64 bits and draw 32, both unsigned")
+        fixed = self._cem_fixed("plan_cem_groups", fixed_action, seed, draw)
         grouped = 2 <= R <= L.CEM_MAX_GROUP and N % R == 0
         if group_base is None:
             base = int(self.config["env_index_base"])
@@ -991,55 +1013,15 @@ class SdcEngine:
         if not -(1 << 31) <= int(group_base) < 1 << 31:
             raise ValueError("plan_cem_groups: group_base must fit 32 bits")
         G = N // R if grouped else 0
-
-        def given(x, name, dtype, shape):
-            if not (isinstance(x, t.Tensor) and x.dtype == dtype and x.is_cuda and x.is_contiguous() and tuple(x.shape) == shape):
-                raise ValueError(f"plan_cem_groups: {name} must be a contiguous {str(dtype).split('.')[-1]} CUDA tensor of shape {shape}")
-            if x.device != self.device:
-                raise ValueError(f"plan_cem_groups: {name} is on {x.device}, this engine runs on {self.device}")
-            return x
-
-        sized = grouped and 1 <= K <= L.MARK_MAX_STEPS and n_it >= 1 and 0 <= int(iter0) <= L.CEM_MAX_ITERS - n_it
-        if sized and probs is not None:
-            given(probs, "probs", t.float64, (K, G, 3, 3))
-        if sized and best_seq is not None:
-            given(best_seq, "best_seq", t.int32, (K, G, 3))
-        obj = plan_objective(reward_weights, gamma, info_weights)
         cem = L.SdcCemGroupParams()
-        cem.group_size, cem.group_base, cem.n_iters, cem.iter0, cem.n_elite = R, int(group_base), n_it, int(iter0), int(n_elite)
-        cem.fixed_action[:] = fixed
-        cem.draw, cem.seed, cem.alpha, cem.p_min = int(draw), int(seed), float(alpha), float(p_min)
-        p = lambda x: C.c_void_p(x.data_ptr())
-        with t.cuda.device(self.device):
-            if sized:
-                if self._pinned_stream_obj is not None:
-                    # (probs and best_seq are filled by torch ops on torch's current stream and read by the sample kernel on the
-                    #  pinned one: order it behind them)
-                    self._pinned_stream_obj.wait_stream(t.cuda.current_stream(self.device))
-                if probs is None:
-                    probs = t.full((K, G, 3, 3), 1.0 / 3.0, dtype=t.float64, device=self.device)
-                if best_seq is None:
-                    best_seq = t.tensor([1, 1, 2], dtype=t.int32, device=self.device).expand(K, G, 3).contiguous()
-                best_score = t.empty((n_it, G), dtype=t.float64, device=self.device)
-                action = t.empty((G, 3), dtype=t.int32, device=self.device)
-                step_actions = t.empty((N, 3), dtype=t.int32, device=self.device)
-                cand = t.empty((K, N, 3), dtype=t.int32, device=self.device)
-                cand_score = t.empty((N,), dtype=t.float64, device=self.device)
-                arrays = (probs, best_seq, best_score, action, step_actions, cand, cand_score)
-                rc = self.lib.sdc_plan_cem_groups(self._h, K, C.byref(cem), C.byref(obj), *[p(x) for x in arrays], p(self.obs),
-                                                  p(self.share_obs), self._stream())
-            else:      # (sizes no array can be given: the library words the refusal, and it looks at the sizes before the arrays)
-                arrays = ()
-                rc = self.lib.sdc_plan_cem_groups(self._h, K, C.byref(cem), C.byref(obj), None, None, None, None, None, None, None,
-                                                  p(self.obs), p(self.share_obs), self._stream())
-                if rc == 0:
-                    raise L.SdcError(f"plan_cem_groups: sdc_plan_cem_groups accepted R = {R}, K = {K}, I = {n_it}, iter0 = {int(iter0)} "
-                                     "and no arrays")
-        self._refused(rc)
-        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse them before)
-            for x in arrays:
-                x.record_stream(self._pinned_stream_obj)
-        return GroupCEMResult(action, step_actions, best_seq, best_score, probs, cand, cand_score)
+        cem.group_size, cem.group_base = R, int(group_base)
+        sized = grouped and 1 <= K <= L.MARK_MAX_STEPS and n_it >= 1 and 0 <= int(iter0) <= L.CEM_MAX_ITERS - n_it
+        outputs = [((n_it, G), t.float64), ((G, 3), t.int32), ((N, 3), t.int32), ((K, N, 3), t.int32), ((N,), t.float64)]
+        return self._cem("plan_cem_groups", self.lib.sdc_plan_cem_groups, cem, fixed, K, G, outputs,
+                         lambda probs, best_seq, best_score, action, step_actions, cand, cand_score:
+                         GroupCEMResult(action, step_actions, best_seq, best_score, probs, cand, cand_score),
+                         sized, sized, f"R = {R}, K = {K}, I = {n_it}, iter0 = {int(iter0)}", n_it, n_elite, probs, best_seq, seed, draw,
+                         iter0, alpha, p_min, reward_weights, gamma, info_weights)
 
     def rollout_stats(self, actions=None, n_steps: int = None, into: Optional[EpisodeStats] = None) -> EpisodeStats:
         """K env-steps as `rollout` takes them, reduced on the device to per-env statistics (sdc_rollout_stats): the steps' outputs go
@@ -1074,7 +1056,7 @@ class SdcEngine:
                                                            x.is_contiguous() and x.device == self.device for x, d, sh in want)):
                 raise ValueError(f"rollout_stats: into must be an EpisodeStats of this engine (contiguous tensors on {self.device}: stats "
                                  f"float64 {want[0][2]}, returns float64 {want[1][2]}, counts int32 {want[2][2]})")
-        p = lambda x: C.c_void_p(x.data_ptr())
+        p = lambda x: _p(x) if x is not None else None
         with t.cuda.device(self.device):
             if into is None:
                 res = EpisodeStats(t.empty((L.STATS_FIELDS, N, L.INFO_DIM), dtype=t.float64, device=self.device),
@@ -1082,15 +1064,12 @@ class SdcEngine:
                                    t.empty((N, 2), dtype=t.int32, device=self.device))
             else:
                 res = into
-                if self._pinned_stream_obj is not None:      # (its tensors may have been touched on torch's current stream)
-                    self._pinned_stream_obj.wait_stream(t.cuda.current_stream(self.device))
-            rc = self.lib.sdc_rollout_stats(self._h, K, p(actions) if actions is not None else None, 0 if into is None else 1,
+                self._behind_torch_stream()      # (its tensors may have been touched on torch's current stream)
+            rc = self.lib.sdc_rollout_stats(self._h, K, p(actions), 0 if into is None else 1,
                                             p(res.stats), p(res.returns), p(res.counts), p(self.obs), p(self.share_obs), p(self.rew),
                                             p(self.done), p(self.info), p(self.final_obs), self._stream())
         self._refused(rc)
-        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse them before)
-            for x in (res.stats, res.returns, res.counts) + ((actions,) if actions is not None else ()):
-                x.record_stream(self._pinned_stream_obj)
+        self._written_on_pinned_stream(res.stats, res.returns, res.counts, *(() if actions is None else (actions,)))
         return res
 
     def evaluate(self, n_episodes: int, actions=None) -> EpisodeStats:

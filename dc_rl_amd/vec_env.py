@@ -27,7 +27,7 @@ import numpy as np
 
 from . import _lib as L
 from . import dc_config, traces
-from .engine import SdcEngine
+from .engine import SdcEngine, group_sync_pairs
 from .make_envs_pyenv import make_bat_fwd_env, make_dc_pyeplus_env, make_ls_env
 from .spaces import Box, Discrete
 
@@ -497,15 +497,31 @@ class SustainDCVecEnv(ShareVecEnv):
         t = self._torch
         if not (isinstance(actions, t.Tensor) and actions.dim() == 4 and tuple(actions.shape[2:]) == (self.num_envs, self.n_agents)):
             raise ValueError(f"plan: actions must be a tensor of shape (M, K, {self.num_envs}, {self.n_agents})")
+        res = self.engine.plan(self._three_columns(actions), reward_weights, gamma, info_weights)
+        return self._subset_columns(res, "action")
+
+    def _three_columns(self, actions):
+        """actions [..., n_agents] in this env's agent order -> the engine's contiguous int32 [..., 3] on its device; with an agent
+        subset the other slots' columns are filled with 1"""
+        t = self._torch
         a = actions.to(device=self.engine.device, dtype=t.int32)
         if self.n_agents != 3:
-            full = t.ones(tuple(a.shape[:3]) + (3,), dtype=t.int32, device=self.engine.device)
+            full = t.ones(tuple(a.shape[:-1]) + (3,), dtype=t.int32, device=self.engine.device)
             full[..., self._agent_idx] = a
             a = full
-        res = self.engine.plan(a.contiguous(), reward_weights, gamma, info_weights)
+        return a.contiguous()
+
+    def _subset_columns(self, res, *fields):
+        """a plan result whose `fields` [..., 3] are narrowed to this env's agent columns"""
         if self.n_agents != 3:
-            res.action = res.action[:, self._agent_idx].contiguous()
+            for f in fields:
+                setattr(res, f, getattr(res, f)[:, self._agent_idx].contiguous())
         return res
+
+    def _subset_fixed(self, fixed_action):
+        """fixed_action of a CEM call under this env's agent subset: the other slots carry 1 in every sampled candidate"""
+        fixed = [-1, -1, -1] if fixed_action is None else [int(x) for x in fixed_action]
+        return fixed if self.n_agents == 3 else [fixed[i] if i in self._agent_idx else 1 for i in range(3)]
 
     def plan_cem(self, horizon, n_iters, n_candidates, n_elite, *, probs=None, best_seq=None, fixed_action=None, **kw):
         """Plan with the cross-entropy method and come back (SdcEngine.plan_cem, which documents the arguments; `probs` [K, num_envs,
@@ -516,23 +532,14 @@ class SustainDCVecEnv(ShareVecEnv):
         what the engine refuses."""
         if self._need_reset:
             raise ValueError("plan_cem: call reset() first")
-        fixed = [-1, -1, -1] if fixed_action is None else [int(x) for x in fixed_action]
-        if self.n_agents != 3:
-            fixed = [fixed[i] if i in self._agent_idx else 1 for i in range(3)]
-        res = self.engine.plan_cem(horizon, n_iters, n_candidates, n_elite, probs=probs, best_seq=best_seq, fixed_action=fixed, **kw)
-        if self.n_agents != 3:
-            res.action = res.action[:, self._agent_idx].contiguous()
-        return res
+        res = self.engine.plan_cem(horizon, n_iters, n_candidates, n_elite, probs=probs, best_seq=best_seq,
+                                   fixed_action=self._subset_fixed(fixed_action), **kw)
+        return self._subset_columns(res, "action")
 
     def sync_groups(self, group_size):
         """Every group of `group_size` consecutive envs becomes a copy of its first env (SdcEngine.sync_groups, through this env's
         clone_envs, so the host's per-env entries follow).  Returns what clone_envs returns."""
-        R = int(group_size)
-        if R < 2 or R > self.num_envs or self.num_envs % R:
-            raise ValueError(f"sync_groups: group_size = {R} must be at least 2 and divide num_envs = {self.num_envs}")
-        e = np.arange(self.num_envs, dtype=np.int32)
-        dst = e[e % R != 0]
-        return self.clone_envs(dst - dst % R, dst)
+        return self.clone_envs(*group_sync_pairs(group_size, self.num_envs, "num_envs"))
 
     def plan_cem_groups(self, group_size, horizon, n_iters, n_elite, *, probs=None, best_seq=None, fixed_action=None, **kw):
         """Plan with the cross-entropy method over replica groups and come back (SdcEngine.plan_cem_groups, which documents the
@@ -543,14 +550,9 @@ class SustainDCVecEnv(ShareVecEnv):
         engine refuses."""
         if self._need_reset:
             raise ValueError("plan_cem_groups: call reset() first")
-        fixed = [-1, -1, -1] if fixed_action is None else [int(x) for x in fixed_action]
-        if self.n_agents != 3:
-            fixed = [fixed[i] if i in self._agent_idx else 1 for i in range(3)]
-        res = self.engine.plan_cem_groups(group_size, horizon, n_iters, n_elite, probs=probs, best_seq=best_seq, fixed_action=fixed, **kw)
-        if self.n_agents != 3:
-            res.action = res.action[:, self._agent_idx].contiguous()
-            res.step_actions = res.step_actions[:, self._agent_idx].contiguous()
-        return res
+        res = self.engine.plan_cem_groups(group_size, horizon, n_iters, n_elite, probs=probs, best_seq=best_seq,
+                                          fixed_action=self._subset_fixed(fixed_action), **kw)
+        return self._subset_columns(res, "action", "step_actions")
 
     def _stats_actions(self, actions, K, what):
         """an action sequence [K, num_envs, n_agents] in this env's agent order -> the engine's [K, num_envs, 3] int32; None: the trained
@@ -563,12 +565,7 @@ class SustainDCVecEnv(ShareVecEnv):
             return t.tensor([1, 1, 2], dtype=t.int32, device=dev).expand(int(K), self.num_envs, 3).contiguous()
         if not (isinstance(actions, t.Tensor) and actions.dim() == 3 and tuple(actions.shape[1:]) == (self.num_envs, self.n_agents)):
             raise ValueError(f"{what}: actions must be a tensor of shape (K, {self.num_envs}, {self.n_agents})")
-        a = actions.to(device=dev, dtype=t.int32)
-        if self.n_agents != 3:
-            full = t.ones(tuple(a.shape[:2]) + (3,), dtype=t.int32, device=dev)
-            full[..., self._agent_idx] = a
-            a = full
-        return a.contiguous()
+        return self._three_columns(actions)
 
     def rollout_stats(self, actions=None, n_steps=None, into=None):
         """K env-steps reduced on the device to per-env statistics (SdcEngine.rollout_stats, which documents the result).  `actions`: an

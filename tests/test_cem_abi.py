@@ -3,35 +3,21 @@ mirror has the C compiler's size and offsets; the library refuses a null handle 
 cross-compiles for gfx950 with no scratch, no spills and an occupancy of at least 4 for exactly its two kernels; CEMMPCAgent's warm
 start (the shift of best_seq and probs by a step, the fresh start when the episode step goes backwards) on CPU tensors, against an
 engine stub that records what the agent hands to plan_cem."""
-import ctypes as C
-import os
 import re
-import subprocess
-import tempfile
 
 from dc_rl_amd import _lib as L
+from tests.plan_util import AgentStub as _Stub
+from tests.plan_util import assert_c_layout, assert_no_scratch_or_spills, entry_point_header, kernel_resources
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-HEADER = os.path.join(ROOT, "include", "sustaindc_hip.h")
 ARGS = ["h", "n_steps", "cem", "objective", "probs", "best_seq", "best_score", "best_action", "cand", "cand_score", "obs", "share_obs",
         "stream"]
 MEMBERS = ["n_iters", "iter0", "n_cand", "n_elite", "fixed_action", "draw", "seed", "alpha", "p_min"]
 
 
 def test_cem_entry_point_is_declared_exported_and_bound_at_abi_313():
-    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert re.search(r"#define SDC_ABI_VERSION 313\b", hdr)
+    hdr = entry_point_header("sdc_plan_cem", ARGS, "sdc_cem.hip")
     m = re.search(r"#define SDC_CEM_MAX_CAND (\d+)", hdr)
     assert m and int(m.group(1)) == L.CEM_MAX_CAND == 64
-    decl = re.search(r"\bint sdc_plan_cem\(([^)]*)\);", hdr)
-    assert decl and [a.split()[-1].lstrip("*") for a in decl.group(1).split(",")] == ARGS, decl
-    assert "sdc_plan_cem" in L.EXPORTS
-    assert L.ABI_VERSION == 313 and "sdc_cem.hip" in L.SOURCES
-    L.build()
-    lib = C.CDLL(L.LIB_PATH)
-    assert lib.sdc_version() == 313
-    assert hasattr(lib, "sdc_plan_cem")
-    assert len(L.load().sdc_plan_cem.argtypes) == len(ARGS)
     import dc_rl_amd
     from dc_rl_amd.agents import CEMMPCAgent
     from dc_rl_amd.engine import CEMResult
@@ -39,19 +25,7 @@ def test_cem_entry_point_is_declared_exported_and_bound_at_abi_313():
 
 
 def test_params_mirror_has_the_c_layout(tmp_path):
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void) {",
-           '  printf("sizeof %zu\\n", sizeof(sdc_cem_params));']
-    src += [f'  printf("{m} %zu\\n", offsetof(sdc_cem_params, {m}));' for m in MEMBERS]
-    src += ["  return 0;", "}"]
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = str(tmp_path / "layout")
-    subprocess.run(["gcc", "-o", exe, str(c)], check=True)
-    out = dict(ln.split() for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["sizeof"]) == C.sizeof(L.SdcCemParams)
-    for m in MEMBERS:
-        assert int(out[m]) == getattr(L.SdcCemParams, m).offset, m
-    assert [f[0] for f in L.SdcCemParams._fields_] == MEMBERS
+    assert_c_layout(tmp_path, "sdc_cem_params", L.SdcCemParams, MEMBERS)
     assert L.SdcCemParams.fixed_action.size == 12 and L.SdcCemParams.seed.size == 8 and L.SdcCemParams.draw.size == 4
 
 
@@ -62,55 +36,12 @@ def test_null_handle_is_refused_before_any_device_work():
 
 
 def test_cem_kernels_compile_for_gfx950_without_scratch_or_spills():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = [f for f in L.HIPCC_FLAGS if f != "-shared"]
-    with tempfile.TemporaryDirectory() as td:
-        r = subprocess.run([hipcc] + flags + ["-c", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "sdc_cem.hip",
-                            "-o", os.path.join(td, "o.o")], cwd=L.CSRC, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    per, cur = {}, None
-    for line in r.stderr.splitlines():
-        f = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if f:
-            cur = per.setdefault(f.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    assert set(per) == {"sdc_cem_sample_kernel", "sdc_cem_refit_kernel"}, sorted(per)
+    per = kernel_resources("sdc_cem.hip")
+    assert_no_scratch_or_spills(per, {"sdc_cem_sample_kernel", "sdc_cem_refit_kernel"})
     for k, u in per.items():
-        assert u["ScratchSize"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (k, u)
         assert u["Occupancy"] >= 4, (k, u)
     # the refit kernel's LDS: four workgroups of four wavefronts fit a CU's 160 KiB, as its header says
     assert 4 * per["sdc_cem_refit_kernel"]["LDS Size"] <= 160 * 1024, per["sdc_cem_refit_kernel"]
-
-
-class _Stub:
-    """What CEMMPCAgent.act asks of an engine, on the CPU: plan_cem records its arguments and answers with tensors that tell the step
-    and the decision apart (best_seq[k] = 100 d + 10 k + agent, probs[k] = d + k / 16 + (agent, action) / 256)."""
-
-    def __init__(self, n_envs=2, episode_steps=12):
-        import torch
-        self.n_envs, self.device = n_envs, torch.device("cpu")
-        self.config = dict(auto_reset=True, episode_steps=episode_steps)
-        self.t, self.calls = 0, []
-
-    def steps_to_episode_end(self):
-        return self.config["episode_steps"] - self.t
-
-    def step(self):
-        self.t = (self.t + 1) % self.config["episode_steps"]
-
-    def plan_cem(self, K, n_iters, M, E, *, probs, best_seq, draw, **kw):
-        import torch
-        from dc_rl_amd.engine import CEMResult
-        self.calls.append(dict(K=K, probs=None if probs is None else probs.clone(), best_seq=None if best_seq is None else best_seq.clone(),
-                               draw=draw, n_iters=n_iters, M=M, E=E, **kw))
-        d, N = len(self.calls), self.n_envs
-        k = torch.arange(K).view(K, 1, 1)
-        seq = (100 * d + 10 * k + torch.arange(3).view(1, 1, 3)).expand(K, N, 3).to(torch.int32).contiguous()
-        p = (d + k.view(K, 1, 1, 1) / 16.0 + torch.arange(9).view(1, 1, 3, 3) / 256.0).expand(K, N, 3, 3).to(torch.float64).contiguous()
-        return CEMResult(seq[0].clone(), seq, torch.zeros((n_iters, N), dtype=torch.float64), p, None, None)
 
 
 def test_warm_start_shifts_by_a_step_and_starts_afresh_when_the_episode_step_goes_backwards():

@@ -4,16 +4,13 @@ device; the translation unit cross-compiles for gfx950 with no scratch and no sp
 LDS and occupancy figures DESIGN section 4.14 states; GroupCEMMPCAgent's host logic (the warm start's shift by a step, the
 re-synchronisation and the fresh start when the episode step goes backwards) on CPU tensors, against an engine stub that records what
 the agent asks of it."""
-import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 from dc_rl_amd import _lib as L
+from tests.plan_util import ROOT, assert_c_layout, assert_no_scratch_or_spills, entry_point_header, kernel_resources
+from tests.plan_util import AgentStub as _Stub
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-HEADER = os.path.join(ROOT, "include", "sustaindc_hip.h")
 ARGS = ["h", "n_steps", "cem", "objective", "probs", "best_seq", "best_score", "best_action", "step_actions", "cand", "cand_score", "obs",
         "share_obs", "stream"]
 MEMBERS = ["group_size", "group_base", "n_iters", "iter0", "n_elite", "fixed_action", "draw", "seed", "alpha", "p_min"]
@@ -22,19 +19,9 @@ FIGURES = {"sdc_cem_group_sample_kernel": (36, 3552, 8), "sdc_cem_group_refit_ke
 
 
 def test_entry_point_is_declared_exported_and_bound_at_abi_313():
-    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert re.search(r"#define SDC_ABI_VERSION 313\b", hdr)
+    hdr = entry_point_header("sdc_plan_cem_groups", ARGS, "sdc_cem_groups.hip")
     m = re.search(r"#define SDC_CEM_MAX_GROUP (\d+)", hdr)
     assert m and int(m.group(1)) == L.CEM_MAX_GROUP == 1024
-    decl = re.search(r"\bint sdc_plan_cem_groups\(([^)]*)\);", hdr)
-    assert decl and [a.split()[-1].lstrip("*") for a in decl.group(1).split(",")] == ARGS, decl
-    assert "sdc_plan_cem_groups" in L.EXPORTS
-    assert L.ABI_VERSION == 313 and "sdc_cem_groups.hip" in L.SOURCES
-    L.build()
-    lib = C.CDLL(L.LIB_PATH)
-    assert lib.sdc_version() == 313
-    assert hasattr(lib, "sdc_plan_cem_groups")
-    assert len(L.load().sdc_plan_cem_groups.argtypes) == len(ARGS)
     import dc_rl_amd
     from dc_rl_amd.agents import GroupCEMMPCAgent
     from dc_rl_amd.engine import GroupCEMResult, SdcEngine
@@ -47,19 +34,7 @@ def test_entry_point_is_declared_exported_and_bound_at_abi_313():
 
 
 def test_params_mirror_has_the_c_layout(tmp_path):
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void) {",
-           '  printf("sizeof %zu\\n", sizeof(sdc_cem_group_params));']
-    src += [f'  printf("{m} %zu\\n", offsetof(sdc_cem_group_params, {m}));' for m in MEMBERS]
-    src += ["  return 0;", "}"]
-    c = tmp_path / "layout.c"
-    c.write_text("\n".join(src))
-    exe = str(tmp_path / "layout")
-    subprocess.run(["gcc", "-o", exe, str(c)], check=True)
-    out = dict(ln.split() for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines())
-    assert int(out["sizeof"]) == C.sizeof(L.SdcCemGroupParams)
-    for m in MEMBERS:
-        assert int(out[m]) == getattr(L.SdcCemGroupParams, m).offset, m
-    assert [f[0] for f in L.SdcCemGroupParams._fields_] == MEMBERS
+    assert_c_layout(tmp_path, "sdc_cem_group_params", L.SdcCemGroupParams, MEMBERS)
     assert L.SdcCemGroupParams.fixed_action.size == 12 and L.SdcCemGroupParams.seed.size == 8 and L.SdcCemGroupParams.draw.size == 4
 
 
@@ -70,24 +45,9 @@ def test_null_handle_is_refused_before_any_device_work():
 
 
 def test_group_kernels_compile_for_gfx950_without_scratch_or_spills_at_the_documented_figures():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = [f for f in L.HIPCC_FLAGS if f != "-shared"]
-    with tempfile.TemporaryDirectory() as td:
-        r = subprocess.run([hipcc] + flags + ["-c", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "sdc_cem_groups.hip",
-                            "-o", os.path.join(td, "o.o")], cwd=L.CSRC, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    per, cur = {}, None
-    for line in r.stderr.splitlines():
-        f = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if f:
-            cur = per.setdefault(f.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    assert set(per) == set(FIGURES), sorted(per)
+    per = kernel_resources("sdc_cem_groups.hip")
+    assert_no_scratch_or_spills(per, FIGURES)
     for k, u in per.items():
-        assert u["ScratchSize"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (k, u)
         assert (u["VGPRs"], u["LDS Size"], u["Occupancy"]) == FIGURES[k], (k, u)
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     sec = design[design.index("### 4.14"):]
@@ -98,39 +58,6 @@ def test_group_kernels_compile_for_gfx950_without_scratch_or_spills_at_the_docum
     # the refit kernel's scores [1024] fp64 are 8 KiB of its LDS; a sample wavefront's LDS leaves the register file as the limit
     assert per["sdc_cem_group_refit_kernel"]["LDS Size"] >= 8 * L.CEM_MAX_GROUP
     assert 32 * per["sdc_cem_group_sample_kernel"]["LDS Size"] <= 160 * 1024
-
-
-class _Stub:
-    """What GroupCEMMPCAgent.act asks of an engine, on the CPU: sync_groups and plan_cem_groups record their arguments; the latter
-    answers with tensors that tell the step and the decision apart (best_seq[k] = 100 d + 10 k + agent, probs[k] = d + k / 16 +
-    (agent, action) / 256, step_actions = best_seq[0] of the env's group)."""
-
-    def __init__(self, n_envs=6, episode_steps=12):
-        import torch
-        self.n_envs, self.device = n_envs, torch.device("cpu")
-        self.config = dict(auto_reset=True, episode_steps=episode_steps)
-        self.t, self.calls, self.syncs = 0, [], []
-
-    def steps_to_episode_end(self):
-        return self.config["episode_steps"] - self.t
-
-    def step(self):
-        self.t = (self.t + 1) % self.config["episode_steps"]
-
-    def sync_groups(self, R):
-        self.syncs.append((len(self.calls), R))
-
-    def plan_cem_groups(self, R, K, n_iters, E, *, probs, best_seq, draw, **kw):
-        import torch
-        from dc_rl_amd.engine import GroupCEMResult
-        self.calls.append(dict(R=R, K=K, probs=None if probs is None else probs.clone(), best_seq=None if best_seq is None else best_seq.clone(),
-                               draw=draw, n_iters=n_iters, E=E, **kw))
-        d, G = len(self.calls), self.n_envs // R
-        k = torch.arange(K).view(K, 1, 1)
-        seq = (100 * d + 10 * k + torch.arange(3).view(1, 1, 3)).expand(K, G, 3).to(torch.int32).contiguous()
-        p = (d + k.view(K, 1, 1, 1) / 16.0 + torch.arange(9).view(1, 1, 3, 3) / 256.0).expand(K, G, 3, 3).to(torch.float64).contiguous()
-        return GroupCEMResult(seq[0].clone(), seq[0].repeat_interleave(R, dim=0), seq, torch.zeros((n_iters, G), dtype=torch.float64), p,
-                              None, None)
 
 
 def test_agent_warm_start_shifts_by_a_step_and_resyncs_and_starts_afresh_when_the_episode_step_goes_backwards():

@@ -17,15 +17,15 @@ import pytest
 
 from dc_rl_amd import _lib as L
 from dc_rl_amd import CEMMPCAgent, CEMResult, SustainDCVecEnv
-from tests import reset_ref as RR
-from tests.test_gpu_clone import _acts, _bits
+from tests.plan_util import EP, OBJ, _outputs, _twins, objective, planner_refusals, refusal_engines, refused
+from tests.plan_util import refit_ref as _refit_ref
+from tests.plan_util import sample_ref as _sample_ref
+from tests.test_gpu_clone import _acts
 from tests.test_gpu_mark import _assert_rewound, _grab, _mk, _same_out
-from tests.test_gpu_plan import EP, _outputs, _twins
 
 pytestmark = pytest.mark.gpu
 
 N, M, E, K, I = 70, 5, 2, 3, 3
-OBJ = dict(reward_weights=(0.5, 2.0, -1.0), gamma=0.9, info_weights={"bat_CO2_footprint": -1e-3, "dc_water_usage": -0.5})
 FIELDS = ("action", "best_seq", "best_score", "probs", "cand", "cand_score")
 
 
@@ -48,57 +48,6 @@ def _seq(K_, N_, seed=4):
     import torch
     g = torch.Generator(device="cpu").manual_seed(seed)
     return torch.randint(0, 3, (K_, N_, 3), dtype=torch.int32, generator=g).cuda()
-
-
-def _sample_ref(probs, M_, seed, draw, it, base=0, fixed=(-1, -1, -1)):
-    """candidates 1 .. M-1 [M-1, K, N, 3] by the header's rule: one philox4x32_10 block per (m, k, n), counter (m K + k, base + n, draw,
-    (it << 16) | 0xCE3D), key (seed lo, seed hi); u = word * 2^-32; action = (u >= p0) + (u >= p0 + p1)"""
-    p = probs.cpu().numpy()
-    K_, N_ = p.shape[0], p.shape[1]
-    m = np.arange(1, M_, dtype=np.uint64)[:, None, None]
-    k = np.arange(K_, dtype=np.uint64)[None, :, None]
-    n = np.arange(N_, dtype=np.uint64)[None, None, :]
-    words = RR.philox4x32_10(m * np.uint64(K_) + k, np.uint64(base) + n, draw, (it << 16) | 0xCE3D, seed & 0xFFFFFFFF, seed >> 32)
-    out = np.empty((M_ - 1, K_, N_, 3), dtype=np.int32)
-    for a in range(3):
-        u = np.asarray(words[a]).astype(np.float64) * 2.0 ** -32
-        p0 = p[None, :, :, a, 0]
-        p01 = p0 + p[None, :, :, a, 1]
-        out[..., a] = (u >= p0).astype(np.int32) + (u >= p01).astype(np.int32)
-        if fixed[a] >= 0:
-            out[..., a] = fixed[a]
-    return out
-
-
-def _refit_ref(cand, score, probs, best_seq, E_, alpha, p_min, fixed=(-1, -1, -1)):
-    """the header's REFIT from one iteration's candidates and scores, in torch fp64, one operation per tensor op (no fused
-    multiply-adds): -> (elite [M, N], best [N], best_seq, best_score [N], probs)"""
-    import torch
-    M_, K_, N_, _ = cand.shape
-    dev = cand.device
-    c = torch.arange(M_, device=dev)
-    # [c, c', n]: c' outranks c
-    over = (score[None, :, :] > score[:, None, :]) | ((score[None, :, :] == score[:, None, :]) & (c[None, :, None] < c[:, None, None]))
-    rank = over.sum(1)
-    elite = rank < E_
-    assert bool(((rank == 0).sum(0) == 1).all())
-    best = (rank == 0).int().argmax(0)
-    ar = torch.arange(N_, device=dev)
-    winner = cand[best, :, ar].permute(1, 0, 2)      # [K, N, 3]
-    new_seq = torch.where((best != 0)[None, :, None], winner, best_seq)
-    best_score = score[best, ar]
-    hit = (cand[..., None] == torch.arange(3, device=dev, dtype=cand.dtype)) & elite[:, None, :, None, None]      # [M, K, N, 3, 3]
-    cnt = hit.sum(0).double()
-    t = cnt / float(E_)
-    take = 1.0 - alpha
-    q = probs * alpha + t * take
-    q = torch.maximum(q, torch.tensor(p_min, dtype=torch.float64, device=dev))
-    s = (q[..., 0] + q[..., 1]) + q[..., 2]
-    p = q / s[..., None]
-    for a in range(3):
-        if fixed[a] >= 0:
-            p[:, :, a] = probs[:, :, a]
-    return elite, best, new_seq, best_score, p
 
 
 def _same(ra, rb, what, fields=FIELDS):
@@ -311,37 +260,11 @@ def test_draws_are_keyed_on_the_global_env_index():
 def test_refusals_leave_the_engine_untouched():
     import torch
     n = 8
-    a = _mk(n, ep=48)
-    fresh = _mk(n, ep=48, reset=False)
-    verify = _mk(n, ep=48, debug_flags=1)
-    late = _mk(n, ep=48, auto_reset=False)
-    g = torch.Generator(device="cpu").manual_seed(5)
-    for _ in range(10):
-        a.step(_acts(n, g))
-    for _ in range(46):
-        late.step(_acts(n, g))
-
-    def refused(eng, match, call):
-        before = {k: _bits(eng.get_state(k)).copy() for k in ("record", "header")}
-        left = eng.steps_to_episode_end()
-        with pytest.raises(ValueError, match=match):
-            call()
-        for k, x in before.items():
-            assert np.array_equal(x, _bits(eng.get_state(k))), (match, k)
-        assert eng.steps_to_episode_end() == left
+    a, fresh, verify, late = refusal_engines(n)
 
     # what sdc_plan refuses
-    refused(a, "n_steps", lambda: a.plan_cem(L.MARK_MAX_STEPS + 1, 1, 2, 1))
+    planner_refusals(lambda e, K, **kw: e.plan_cem(K, 1, 2, 1, **kw), "n_steps", a, fresh, verify, late)
     refused(a, "n_steps", lambda: a.plan_cem(0, 1, 2, 1))
-    refused(a, "auto-reset", lambda: a.plan_cem(38, 1, 2, 1))      # (38 steps left: the last one would reset)
-    refused(late, "past the end", lambda: late.plan_cem(3, 1, 2, 1))
-    refused(fresh, "sdc_reset must be called first", lambda: fresh.plan_cem(2, 1, 2, 1))
-    refused(verify, "verify mode", lambda: verify.plan_cem(2, 1, 2, 1))
-    for bad in (0.0, -0.5, 1.5, float("nan")):
-        refused(a, "gamma", lambda: a.plan_cem(3, 1, 2, 1, gamma=bad))
-    refused(a, "not an info column", lambda: a.plan_cem(3, 1, 2, 1, info_weights={"no_such_key": 1.0}))
-    refused(a, "at most 8", lambda: a.plan_cem(3, 1, 2, 1, info_weights={k: 1.0 for k in L.INFO_COLS[:9]}))
-    refused(a, "three numbers", lambda: a.plan_cem(3, 1, 2, 1, reward_weights=(1.0, 1.0)))
     # the parameters' ranges
     refused(a, "n_iters", lambda: a.plan_cem(3, 0, 2, 1))
     refused(a, "iter0", lambda: a.plan_cem(3, 1, 2, 1, iter0=-1))
@@ -383,13 +306,6 @@ def test_refusals_leave_the_engine_untouched():
         rc = a.lib.sdc_plan_cem(a._h, 3, None if no_cem else C.byref(cem), C.byref(obj) if obj is not None else None, *ptrs, p(a.obs),
                                 p(a.share_obs), a._stream())
         a._refused(rc)
-
-    def objective(n_cols, col0):
-        o = L.SdcPlanObjective()
-        o.reward_weight[:] = [1.0, 1.0, 1.0]
-        o.gamma, o.n_cols = 1.0, n_cols
-        o.col[0] = col0
-        return o
 
     for i in range(len(arrays)):
         refused(a, "null array", lambda: raw(null=i))

@@ -4,8 +4,8 @@ has rank 0 and is elite, the divisor stays E, and the incumbent-to-be is the low
 are that file's."""
 import pytest
 
-from tests.test_gpu_cem import E, K, M, N, OBJ, _probs, _same, _seq
-from tests.test_gpu_plan import _twins
+from tests.plan_util import OBJ, _twins
+from tests.test_gpu_cem import E, K, M, N, _probs, _same, _seq
 
 pytestmark = pytest.mark.gpu
 

@@ -20,11 +20,10 @@ import pytest
 
 from dc_rl_amd import _lib as L
 from dc_rl_amd import GroupCEMMPCAgent, GroupCEMResult, SustainDCVecEnv
-from tests import reset_ref as RR
-from tests.test_gpu_cem import OBJ
-from tests.test_gpu_clone import _acts, _bits
+from tests.plan_util import EP, OBJ, RSV, _outputs, _twins, objective, planner_refusals, refusal_engines, refused, sample_ref
+from tests.plan_util import refit_ref as _refit_ref
+from tests.test_gpu_clone import _acts
 from tests.test_gpu_mark import _assert_rewound, _grab, _mk
-from tests.test_gpu_plan import EP, RSV, _outputs, _twins
 
 pytestmark = pytest.mark.gpu
 
@@ -53,61 +52,15 @@ def _gseq(K_, G_, seed=4):
 def _sample_ref(probs, best_seq, R, seed, draw, it, base=0, fixed=(-1, -1, -1)):
     """cand [K, G R, 3] by the header's rule: replica 0 the incumbent; replica r >= 1 one philox4x32_10 block per (r, k, g), counter
     (r K + k, base + g, draw, (it << 16) | 0xCE3D), key (seed lo, seed hi); u = word * 2^-32; action = (u >= p0) + (u >= p0 + p1)"""
-    p = probs.cpu().numpy()
-    K_, G_ = p.shape[0], p.shape[1]
-    k, g, r = np.broadcast_arrays(np.arange(K_, dtype=np.uint64)[:, None, None], np.arange(G_, dtype=np.uint64)[None, :, None],
-                                  np.arange(R, dtype=np.uint64)[None, None, :])
-    words = RR.philox4x32_10(r * np.uint64(K_) + k, np.uint64(base) + g, draw, (it << 16) | 0xCE3D, seed & 0xFFFFFFFF, seed >> 32)
-    out = np.empty((K_, G_, R, 3), dtype=np.int32)
-    for a in range(3):
-        u = np.asarray(words[a]).astype(np.float64) * 2.0 ** -32
-        p0 = p[:, :, None, a, 0]
-        p01 = p0 + p[:, :, None, a, 1]
-        out[..., a] = (u >= p0).astype(np.int32) + (u >= p01).astype(np.int32)
-        if fixed[a] >= 0:
-            out[..., a] = fixed[a]
-    out[:, :, 0, :] = best_seq.cpu().numpy()
-    return out.reshape(K_, G_ * R, 3)
+    sampled = sample_ref(probs, R, seed, draw, it, base, fixed)      # replicas 1 .. R-1 [R-1, K, G, 3]
+    out = np.concatenate([best_seq.cpu().numpy()[None], sampled]).transpose(1, 2, 0, 3)
+    return np.ascontiguousarray(out).reshape(out.shape[0], out.shape[1] * R, 3)
 
 
 def _as_candidates(res, R):
     """a GroupCEMResult's cand [K, G R, 3] / cand_score [G R] in plan_cem's layout: [R, K, G, 3] / [R, G]"""
     K_, N_ = res.cand.shape[0], res.cand.shape[1]
     return res.cand.view(K_, N_ // R, R, 3).permute(2, 0, 1, 3).contiguous(), res.cand_score.view(N_ // R, R).t().contiguous()
-
-
-def _refit_ref(cand, score, probs, best_seq, E_, alpha, p_min, fixed=(-1, -1, -1)):
-    """the header's REFIT from one iteration's replicas [R, K, G, 3] and scores [R, G], in torch fp64, one operation per tensor op (no
-    fused multiply-adds): -> (elite [R, G], best [G], best_seq, best_score [G], probs).  tests/test_gpu_cem._refit_ref with one
-    difference: t_j = cnt_j / E divides by a TENSOR that holds E.  torch divides a CUDA tensor by a Python scalar as a multiplication
-    by the scalar's reciprocal, which is the IEEE quotient for E = 2 and, as it happens, for cnt <= E = 3 (that file's cases), but is
-    an ulp off for e.g. 5 / 21; tensor / tensor is the IEEE division the header states."""
-    import torch
-    M_, K_, N_, _ = cand.shape
-    dev = cand.device
-    c = torch.arange(M_, device=dev)
-    # [c, c', n]: c' outranks c
-    over = (score[None, :, :] > score[:, None, :]) | ((score[None, :, :] == score[:, None, :]) & (c[None, :, None] < c[:, None, None]))
-    rank = over.sum(1)
-    elite = rank < E_
-    assert bool(((rank == 0).sum(0) == 1).all())
-    best = (rank == 0).int().argmax(0)
-    ar = torch.arange(N_, device=dev)
-    winner = cand[best, :, ar].permute(1, 0, 2)      # [K, G, 3]
-    new_seq = torch.where((best != 0)[None, :, None], winner, best_seq)
-    best_score = score[best, ar]
-    hit = (cand[..., None] == torch.arange(3, device=dev, dtype=cand.dtype)) & elite[:, None, :, None, None]      # [R, K, G, 3, 3]
-    cnt = hit.sum(0).double()
-    t = cnt / torch.full_like(cnt, float(E_))
-    take = 1.0 - alpha
-    q = probs * alpha + t * take
-    q = torch.maximum(q, torch.tensor(p_min, dtype=torch.float64, device=dev))
-    s = (q[..., 0] + q[..., 1]) + q[..., 2]
-    p = q / s[..., None]
-    for a in range(3):
-        if fixed[a] >= 0:
-            p[:, :, a] = probs[:, :, a]
-    return elite, best, new_seq, best_score, p
 
 
 def _same(ra, rb, what, fields=FIELDS):
@@ -359,46 +312,14 @@ def test_chunked_output_block_gives_the_unchunked_results():
 def test_refusals_leave_the_engine_untouched():
     import torch
     n, R = 8, 4
-    a = _mk(n, ep=48)
-    fresh = _mk(n, ep=48, reset=False)
-    verify = _mk(n, ep=48, debug_flags=1)
-    late = _mk(n, ep=48, auto_reset=False)
-    split = _mk(n, ep=48)
-    g = torch.Generator(device="cpu").manual_seed(5)
-    for _ in range(10):
-        x = _acts(n, g)
-        a.step(x)
-        split.step(x)
-    for _ in range(46):
-        late.step(_acts(n, g))
+    a, split, fresh, verify, late = refusal_engines(n, alongside=1)
     mask = np.zeros(n, dtype=np.uint8)
     mask[5] = 1
     split.reset(mask=mask)      # env 5 starts a new episode: group 1 is out of step
 
-    def refused(eng, match, call):
-        before = {k: _bits(eng.get_state(k)).copy() for k in ("record", "header")}
-        outs = _outputs(eng)
-        left = eng.steps_to_episode_end()
-        with pytest.raises(ValueError, match=match):
-            call()
-        for k, x in before.items():
-            assert np.array_equal(x, _bits(eng.get_state(k))), (match, k)
-        for nm, x in outs.items():
-            assert torch.equal(getattr(eng, nm).view(torch.uint8), x.view(torch.uint8)), (match, nm)
-        assert eng.steps_to_episode_end() == left
-
     # what sdc_plan / sdc_plan_cem refuse
-    refused(a, "n_steps", lambda: a.plan_cem_groups(R, L.MARK_MAX_STEPS + 1, 1, 1))
+    planner_refusals(lambda e, K, **kw: e.plan_cem_groups(R, K, 1, 1, **kw), "n_steps", a, fresh, verify, late)
     refused(a, "n_steps", lambda: a.plan_cem_groups(R, 0, 1, 1))
-    refused(a, "auto-reset", lambda: a.plan_cem_groups(R, 38, 1, 1))      # (38 steps left: the last one would reset)
-    refused(late, "past the end", lambda: late.plan_cem_groups(R, 3, 1, 1))
-    refused(fresh, "sdc_reset must be called first", lambda: fresh.plan_cem_groups(R, 2, 1, 1))
-    refused(verify, "verify mode", lambda: verify.plan_cem_groups(R, 2, 1, 1))
-    for bad in (0.0, -0.5, 1.5, float("nan")):
-        refused(a, "gamma", lambda: a.plan_cem_groups(R, 3, 1, 1, gamma=bad))
-    refused(a, "not an info column", lambda: a.plan_cem_groups(R, 3, 1, 1, info_weights={"no_such_key": 1.0}))
-    refused(a, "at most 8", lambda: a.plan_cem_groups(R, 3, 1, 1, info_weights={k: 1.0 for k in L.INFO_COLS[:9]}))
-    refused(a, "three numbers", lambda: a.plan_cem_groups(R, 3, 1, 1, reward_weights=(1.0, 1.0)))
     refused(a, "n_iters", lambda: a.plan_cem_groups(R, 3, 0, 1))
     refused(a, "iter0", lambda: a.plan_cem_groups(R, 3, 1, 1, iter0=-1))
     refused(a, "iter0", lambda: a.plan_cem_groups(R, 3, 2, 1, iter0=65535))
@@ -447,13 +368,6 @@ def test_refusals_leave_the_engine_untouched():
         rc = a.lib.sdc_plan_cem_groups(a._h, 3, None if no_cem else C.byref(cem), C.byref(obj) if obj is not None else None, *ptrs,
                                        p(a.obs), p(a.share_obs), a._stream())
         a._refused(rc)
-
-    def objective(n_cols, col0):
-        o = L.SdcPlanObjective()
-        o.reward_weight[:] = [1.0, 1.0, 1.0]
-        o.gamma, o.n_cols = 1.0, n_cols
-        o.col[0] = col0
-        return o
 
     for i in range(len(arrays)):
         refused(a, "null array", lambda: raw(null=i))

@@ -17,34 +17,16 @@ import pytest
 from dc_rl_amd import _lib as L
 from dc_rl_amd import ShootingMPCAgent, SustainDCVecEnv
 from dc_rl_amd.engine import PlanResult
-from tests.test_gpu_clone import _acts, _bits
+from tests.plan_util import RSV, _outputs, _twins, objective, planner_refusals, refusal_engines, refused
+from tests.test_gpu_clone import _acts
 from tests.test_gpu_mark import _assert_rewound, _grab, _mk, _same_out, _same_state
 
 pytestmark = pytest.mark.gpu
-
-EP = 96
-RSV = L.INFO_IDX["reserved"]
-
-
-def _twins(N, n=2, history=20, seed=21, **kw):
-    """n engines with one seed after the same `history` random steps; -> (engines, the generator for what follows)"""
-    import torch
-    engs = [_mk(N, ep=EP, seed=seed, **kw) for _ in range(n)]
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    for _ in range(history):
-        x = _acts(N, g)
-        for e in engs:
-            e.step(x)
-    return engs, g
 
 
 def _cands(M, K, N, g):
     import torch
     return torch.randint(0, 3, (M, K, N, 3), dtype=torch.int32, generator=g).cuda()
-
-
-def _outputs(e):
-    return {nm: getattr(e, nm).clone() for nm in ("obs", "share_obs", "rew", "done", "info", "final_obs")}
 
 
 def _pz(x):
@@ -219,25 +201,8 @@ def test_large_batch_rollout_path_equals_lookahead():
 def test_refusals_leave_the_engine_untouched():
     import torch
     N = 8
-    a = _mk(N, ep=48)
-    fresh = _mk(N, ep=48, reset=False)
-    verify = _mk(N, ep=48, debug_flags=1)
-    late = _mk(N, ep=48, auto_reset=False)
-    g = torch.Generator(device="cpu").manual_seed(5)
-    for _ in range(10):
-        a.step(_acts(N, g))
-    for _ in range(46):
-        late.step(_acts(N, g))
+    a, fresh, verify, late = refusal_engines(N)
     ones = lambda M, K, n=N: torch.ones((M, K, n, 3), dtype=torch.int32, device=a.device)
-
-    def refused(eng, match, call):
-        before = {k: _bits(eng.get_state(k)).copy() for k in ("record", "header")}
-        left = eng.steps_to_episode_end()
-        with pytest.raises(ValueError, match=match):
-            call()
-        for k, x in before.items():
-            assert np.array_equal(x, _bits(eng.get_state(k))), (match, k)
-        assert eng.steps_to_episode_end() == left
 
     refused(a, "actions must be", lambda: a.plan(ones(2, 3, N + 1)))
     refused(a, "actions must be", lambda: a.plan(ones(2, 3).long()))
@@ -245,16 +210,7 @@ def test_refusals_leave_the_engine_untouched():
     refused(a, "actions must be", lambda: a.plan(ones(2, 3).cpu()))
     refused(a, "actions must be", lambda: a.plan(ones(0, 3)))
     refused(a, "actions must be", lambda: a.plan(ones(2, 6)[:, ::2]))
-    refused(a, "MARK_MAX_STEPS", lambda: a.plan(ones(1, L.MARK_MAX_STEPS + 1)))
-    refused(a, "auto-reset", lambda: a.plan(ones(1, 38)))      # (38 steps left: the last one would reset)
-    refused(late, "past the end", lambda: late.plan(ones(1, 3)))
-    refused(fresh, "sdc_reset must be called first", lambda: fresh.plan(ones(1, 2)))
-    refused(verify, "verify mode", lambda: verify.plan(ones(1, 2)))
-    for bad in (0.0, -0.5, 1.5, float("nan")):
-        refused(a, "gamma", lambda: a.plan(ones(2, 3), gamma=bad))
-    refused(a, "not an info column", lambda: a.plan(ones(2, 3), info_weights={"no_such_key": 1.0}))
-    refused(a, "at most 8", lambda: a.plan(ones(2, 3), info_weights={k: 1.0 for k in L.INFO_COLS[:9]}))
-    refused(a, "three numbers", lambda: a.plan(ones(2, 3), reward_weights=(1.0, 1.0)))
+    planner_refusals(lambda e, K, **kw: e.plan(ones(2, K), **kw), "MARK_MAX_STEPS", a, fresh, verify, late)
     # what the Python surface cannot send: straight to the library
     x = ones(2, 3)
     out = [torch.empty(2 * N * 3, dtype=torch.float64, device=a.device) for _ in range(2)]
@@ -265,13 +221,6 @@ def test_refusals_leave_the_engine_untouched():
         rc = a.lib.sdc_plan(a._h, n_cand, n_steps, p(acts) if acts is not None else None, C.byref(obj) if obj is not None else None,
                             p(out[0]), p(score) if score is not None else None, p(ints[0]), p(ints[1]), p(a.obs), p(a.share_obs), a._stream())
         a._refused(rc)
-
-    def objective(n_cols, col0):
-        o = L.SdcPlanObjective()
-        o.reward_weight[:] = [1.0, 1.0, 1.0]
-        o.gamma, o.n_cols = 1.0, n_cols
-        o.col[0] = col0
-        return o
 
     refused(a, "n_cand", lambda: raw(n_cand=0))
     refused(a, "n_steps", lambda: raw(n_steps=0))

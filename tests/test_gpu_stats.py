@@ -23,30 +23,15 @@ import pytest
 
 from dc_rl_amd import _lib as L
 from dc_rl_amd import EpisodeStats, SustainDCVecEnv
-from tests.test_gpu_clone import _acts
-from tests.test_gpu_mark import _grab, _mk, _same_out, _same_state
+from tests.plan_util import EP, RSV, _twins, refusal_engines, refused
+from tests.test_gpu_mark import _mk, _same_out, _same_state
 
 pytestmark = pytest.mark.gpu
 
-EP = 96
 K7 = 7
-RSV, FAULT = L.INFO_IDX["reserved"], L.INFO_IDX["fault"]
+FAULT = L.INFO_IDX["fault"]
 COLS = [c for c in range(L.INFO_DIM) if c != RSV]
 FAULT_ACTION = 64      # include/sustaindc_hip.h SDC_FAULT_ACTION
-
-
-def _twins(N, n=2, history=20, seed=21, policy=None, **kw):
-    """n engines with one seed after the same `history` random steps (built-in policies: steps without actions)"""
-    import torch
-    if policy is not None:
-        kw["policy"] = policy
-    engs = [_mk(N, ep=EP, seed=seed, **kw) for _ in range(n)]
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    for _ in range(history):
-        x = None if policy is not None else _acts(N, g)
-        for e in engs:
-            e.step(x)
-    return engs, g
 
 
 def _seq(K, N, g):
@@ -242,29 +227,9 @@ def test_large_batch_rollout_path_every_env():
 def test_refusals_name_their_reason_and_leave_the_engine_untouched():
     import torch
     N = 8
-    a = _mk(N, ep=48)
-    fresh = _mk(N, ep=48, reset=False)
-    verify = _mk(N, ep=48, debug_flags=1)
-    late = _mk(N, ep=48, auto_reset=False)
+    a, fresh, verify, late = refusal_engines(N)
     pol = _mk(N, ep=48, policy=(1, 3, 2))
-    g = torch.Generator(device="cpu").manual_seed(5)
-    for _ in range(10):
-        a.step(_acts(N, g))
-    for _ in range(46):
-        late.step(_acts(N, g))
     ones = lambda K, n=N: torch.ones((K, n, 3), dtype=torch.int32, device=a.device)
-
-    def refused(eng, match, call):
-        before, left = _grab(eng), eng.steps_to_episode_end()
-        outs = {nm: getattr(eng, nm).clone() for nm in ("obs", "share_obs", "rew", "done", "info", "final_obs")}
-        with pytest.raises(ValueError, match=match):
-            call()
-        after = _grab(eng)
-        for k, x in before.items():
-            assert np.array_equal(x, after[k]), (match, k)
-        assert eng.steps_to_episode_end() == left
-        for nm, x in outs.items():
-            assert torch.equal(getattr(eng, nm), x), (match, nm)
 
     # through the Python surface
     refused(a, "actions must be", lambda: a.rollout_stats(ones(2, N + 1)))

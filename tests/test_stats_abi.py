@@ -2,37 +2,22 @@
 the library's sources; the library refuses a null handle before it touches a device; the translation unit cross-compiles for gfx950 with
 no scratch, no spills and an occupancy of at least 4 for exactly its two kernels; EpisodeStats.summary() on hand-made CPU tensors against
 a NumPy restatement of the reference logger's formulas (harl/envs/sustaindc/sustaindc_logger.py:86-101, :126-149)."""
-import ctypes as C
-import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 
 from dc_rl_amd import _lib as L
+from tests.plan_util import assert_no_scratch_or_spills, entry_point_header, kernel_resources
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-HEADER = os.path.join(ROOT, "include", "sustaindc_hip.h")
 ARGS = ["h", "n_steps", "actions", "accumulate", "stats", "returns", "counts", "obs", "share_obs", "rew", "done", "info", "final_obs",
         "stream"]
 
 
 def test_stats_entry_point_is_declared_exported_and_bound_at_abi_313():
-    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    assert re.search(r"#define SDC_ABI_VERSION 313\b", hdr)
+    hdr = entry_point_header("sdc_rollout_stats", ARGS, "sdc_stats.hip")
     m = re.search(r"#define SDC_STATS_FIELDS (\d+)", hdr)
     assert m and int(m.group(1)) == L.STATS_FIELDS == 4
     assert re.search(r"enum sdc_stat_field \{ SDC_STAT_SUM = 0, SDC_STAT_MIN, SDC_STAT_MAX, SDC_STAT_NPOS \};", hdr)
-    decl = re.search(r"\bint sdc_rollout_stats\(([^)]*)\);", hdr)
-    assert decl and [a.split()[-1].lstrip("*") for a in decl.group(1).split(",")] == ARGS, decl
-    assert "sdc_rollout_stats" in L.EXPORTS
-    assert L.ABI_VERSION == 313 and "sdc_stats.hip" in L.SOURCES
-    L.build()
-    lib = C.CDLL(L.LIB_PATH)
-    assert lib.sdc_version() == 313
-    assert hasattr(lib, "sdc_rollout_stats")
-    assert len(L.load().sdc_rollout_stats.argtypes) == len(ARGS)
     import dc_rl_amd
     from dc_rl_amd.engine import EpisodeStats, SdcEngine
     assert dc_rl_amd.EpisodeStats is EpisodeStats
@@ -48,24 +33,9 @@ def test_null_handle_is_refused_before_any_device_work():
 
 
 def test_stats_kernels_compile_for_gfx950_without_scratch_or_spills():
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = [f for f in L.HIPCC_FLAGS if f != "-shared"]
-    with tempfile.TemporaryDirectory() as td:
-        r = subprocess.run([hipcc] + flags + ["-c", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "sdc_stats.hip",
-                            "-o", os.path.join(td, "o.o")], cwd=L.CSRC, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    per, cur = {}, None
-    for line in r.stderr.splitlines():
-        f = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if f:
-            cur = per.setdefault(f.group(1), {})
-            continue
-        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).strip()] = int(m.group(2))
-    assert set(per) == {"sdc_stats_reduce_kernel", "sdc_stats_last_kernel"}, sorted(per)
+    per = kernel_resources("sdc_stats.hip")
+    assert_no_scratch_or_spills(per, {"sdc_stats_reduce_kernel", "sdc_stats_last_kernel"})
     for k, u in per.items():
-        assert u["ScratchSize"] == 0 and u["VGPRs Spill"] == 0 and u["SGPRs Spill"] == 0, (k, u)
         assert u["Occupancy"] >= 4, (k, u)
         assert u["LDS Size"] == 0, (k, u)      # no LDS, as the kernels' header says
 
