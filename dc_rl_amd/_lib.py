@@ -23,10 +23,12 @@ ABI_VERSION = 313  # include/sustaindc_hip.h SDC_ABI_VERSION: the struct layouts
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
-           "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip"]
+           "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip", "sdc_plan_terms.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
+PLAN_MAX_LIMITS = 8     # include/sustaindc_hip.h SDC_PLAN_MAX_LIMITS: limit entries of sdc_set_plan_terms
+PLAN_MAX_TERMINAL = 8   # include/sustaindc_hip.h SDC_PLAN_MAX_TERMINAL: columns of its terminal term
 PLAN_DEBUG_TWO_STEPS = 16384   # sdc_config.debug_flags bit 14 (test hook): sdc_plan's output block holds two steps
 STATS_FIELDS = 4        # include/sustaindc_hip.h SDC_STATS_FIELDS: sum, min, max, count of positive values (enum sdc_stat_field)
 CEM_MAX_CAND = 64       # include/sustaindc_hip.h SDC_CEM_MAX_CAND: candidates per iteration of sdc_plan_cem
@@ -145,6 +147,15 @@ class SdcPlanObjective(C.Structure):
     ]
 
 
+class SdcPlanTerms(C.Structure):
+    """The limits and the terminal term the plan calls score with next to their objective (include/sustaindc_hip.h sdc_plan_terms)."""
+    _fields_ = [
+        ("n_limits", C.c_int32), ("limit_col", C.c_int32 * PLAN_MAX_LIMITS), ("limit_side", C.c_int32 * PLAN_MAX_LIMITS),
+        ("limit_bound", C.c_double * PLAN_MAX_LIMITS), ("limit_weight", C.c_double * PLAN_MAX_LIMITS),
+        ("n_terminal", C.c_int32), ("terminal_col", C.c_int32 * PLAN_MAX_TERMINAL), ("terminal_weight", C.c_double * PLAN_MAX_TERMINAL),
+    ]
+
+
 class SdcCemParams(C.Structure):
     """The cross-entropy method's parameters of one sdc_plan_cem call (include/sustaindc_hip.h sdc_cem_params)."""
     _fields_ = [
@@ -170,7 +181,7 @@ EXPORTS = [
     "sdc_set_actor", "sdc_rollout_actor", "sdc_clone_envs",
     "sdc_snapshot_row_bytes", "sdc_snapshot_envs", "sdc_restore_envs",
     "sdc_mark_row_bytes", "sdc_mark_envs", "sdc_rewind_envs", "sdc_plan", "sdc_plan_cem", "sdc_rollout_stats",
-    "sdc_plan_cem_groups",
+    "sdc_plan_cem_groups", "sdc_set_plan_terms", "sdc_get_plan_terms",
 ]
 
 
@@ -331,6 +342,8 @@ def load():
     L.sdc_plan_cem.argtypes = [vp, C.c_int, C.POINTER(SdcCemParams), C.POINTER(SdcPlanObjective), vp, vp, vp, vp, vp, vp, fp, fp, vp]
     L.sdc_plan_cem_groups.argtypes = [vp, C.c_int, C.POINTER(SdcCemGroupParams), C.POINTER(SdcPlanObjective), vp, vp, vp, vp, vp, vp, vp,
                                       fp, fp, vp]
+    L.sdc_set_plan_terms.argtypes = [vp, C.POINTER(SdcPlanTerms)]
+    L.sdc_get_plan_terms.argtypes = [vp, C.POINTER(SdcPlanTerms)]
     L.sdc_rollout_stats.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp]
     for name in EXPORTS:
         getattr(L, name)

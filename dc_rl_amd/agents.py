@@ -134,7 +134,8 @@ class ShootingMPCAgent:
     the env's device seeded with `seed`: two agents with one seed on twin envs choose the same actions.  reward_weights, gamma,
     info_weights: the objective, as `plan` takes it.  The horizon is shortened to what the episode has left (the planner does not look
     across an episode's end); with fewer than two steps left the agent does nothing.  `last`: the latest PlanResult (None after a
-    do-nothing fallback), `last_horizon` the horizon it used."""
+    do-nothing fallback), `last_horizon` the horizon it used.  The agent plans through the env, so limits and a terminal term:
+    `env.set_plan_terms`."""
 
     DO_NOTHING = (1, 1, 2)
 
@@ -177,7 +178,8 @@ class CEMMPCAgent:
     grows.  The draws are keyed on (seed, the decision's number `draw`, which goes up by one per planned decision): two agents with one
     seed on twin envs choose the same actions.  The horizon is shortened to what the episode has left (the planner does not look across
     an episode's end); with fewer than two steps left the agent does nothing.  `last`: the latest CEMResult (None after a do-nothing
-    fallback), `last_horizon` the horizon it used."""
+    fallback), `last_horizon` the horizon it used.  The agent plans through the env, so limits and a terminal term:
+    `env.set_plan_terms`."""
 
     DO_NOTHING = (1, 1, 2)
 
@@ -248,7 +250,8 @@ class GroupCEMMPCAgent(CEMMPCAgent):
     `act` returns `step_actions` -- the group's best first action for every replica --, so stepping with it keeps a group identical.
     Replicas draw their own resets (those are keyed on the global env index), so the agent makes every group a copy of its first env
     (`sync_groups`) on its first decision and whenever the episode step has gone backwards (a reset or auto-reset), and starts probs
-    and best_seq afresh then.  `last`: the latest GroupCEMResult (None after a do-nothing fallback)."""
+    and best_seq afresh then.  `last`: the latest GroupCEMResult (None after a do-nothing fallback).  As for CEMMPCAgent, limits and a
+    terminal term: `env.set_plan_terms`."""
 
     def __init__(self, group_size: int, n_elite: int = 2, n_iters: int = 3, horizon: int = 8, seed: int = 0, alpha: float = 0.0,
                  p_min: float = 0.0, warm_start: bool = True, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None):

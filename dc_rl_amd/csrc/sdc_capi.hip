@@ -24,6 +24,7 @@
 #include "sdc_cem.hpp"
 #include "sdc_cem_groups.hpp"
 #include "sdc_plan.hpp"
+#include "sdc_plan_terms.hpp"
 #include "sdc_stats.hpp"
 
 extern "C" __global__ void sdc_dynamics_kernel(SdcDev S, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
@@ -181,6 +182,8 @@ struct sdc_handle {
   size_t plan_out_bytes = 0;
   std::vector<int32_t> plan_manifest;
   IdxStage plan_stage{sizeof(double), SDC_MARK_MAX_STEPS};
+  // sdc_set_plan_terms: what the plan calls score with next to their objective (both counts 0: nothing set, every field 0)
+  sdc_plan_terms plan_terms{};
 };
 
 namespace {
@@ -2043,23 +2046,48 @@ static int rollout_chunks(sdc_handle* h, const SdcPlanBlock& B, const int n_step
 }
 }  // extern "C++"
 
-// What a plan call works with once it has been let through: the run, the device side of its discount table, the caller's obs /
-// share_obs rows (every rewind refreshes them) and stream
+// What a plan call works with once it has been let through: the run, the device side of its discount table, the discount of the
+// handle's terminal term (g[n_steps - 1] * gamma), the caller's obs / share_obs rows (every rewind refreshes them) and stream
 struct PlanSession {
   sdc_handle* h;
   PlanRun R;
   const void* g_dev;
+  double g_terminal;
   float *obs, *share_obs;
   void* stream;
   hipStream_t st() const { return reinterpret_cast<hipStream_t>(stream); }
 };
 
-// Per candidate: roll out (rollout_chunks), score each chunk, rewind -- from the mark the session has taken into h->plan_rows.
+// the score kernel's plan with the handle's plan terms (sdc_plan_terms.hpp); S is read at the launch
+static SdcPlanScoreTerms plan_terms_plan(const PlanSession& P) {
+  const sdc_plan_terms& t = P.h->plan_terms;
+  SdcPlanScoreTerms T;
+  std::memset(&T, 0, sizeof(T));
+  T.n_steps = P.R.n_steps;
+  T.n_limits = t.n_limits;
+  T.n_terminal = t.n_terminal;
+  T.g_terminal = P.g_terminal;
+  T.cols = sdc_plan_pack_cols(P.R.S.col, P.R.S.n_cols);
+  T.limit_cols = sdc_plan_pack_cols(t.limit_col, t.n_limits);
+  T.terminal_cols = sdc_plan_pack_cols(t.terminal_col, t.n_terminal);
+  for (int j = 0; j < t.n_limits; j++) {
+    T.limit_upper |= (t.limit_side[j] > 0 ? 1u : 0u) << j;
+    T.limit_bound[j] = t.limit_bound[j];
+    T.limit_weight[j] = t.limit_weight[j];
+  }
+  for (int j = 0; j < t.n_terminal; j++) T.terminal_weight[j] = t.terminal_weight[j];
+  return T;
+}
+
+// Per candidate: roll out (rollout_chunks), score each chunk, rewind -- from the mark the session has taken into h->plan_rows.  With
+// plan terms on the handle the score is sdc_plan_score_terms_kernel's, without it is sdc_plan_score_kernel's.
 static int plan_candidates(PlanSession& P, const int n_cand, const int32_t* actions, double* returns, double* score) {
   sdc_handle* const h = P.h;
   const size_t N = (size_t)h->cfg.n_envs;
   SdcPlanScore& S = P.R.S;
   S.g = static_cast<const double*>(P.g_dev);
+  const bool terms = h->plan_terms.n_limits > 0 || h->plan_terms.n_terminal > 0;
+  SdcPlanScoreTerms T = plan_terms_plan(P);
   int rc = 0;
   for (int c = 0; c < n_cand && rc == 0; c++) {
     S.returns = returns ? returns + (size_t)c * N * 3 : nullptr;
@@ -2068,7 +2096,9 @@ static int plan_candidates(PlanSession& P, const int n_cand, const int32_t* acti
                         [&](const int k0, const int steps) {
                           S.first_step = k0;
                           S.steps = steps;
-                          return launched("sdc_plan_score_kernel", sdc_plan_score_launch(S, P.st()));
+                          if (!terms) return launched("sdc_plan_score_kernel", sdc_plan_score_launch(S, P.st()));
+                          T.S = S;
+                          return launched("sdc_plan_score_terms_kernel", sdc_plan_score_terms_launch(T, P.st()));
                         });
     if (rc == 0) rc = sdc_rewind_envs(h, nullptr, (int)N, h->plan_rows, h->plan_manifest.data(), P.obs, P.share_obs, P.stream);
   }
@@ -2084,13 +2114,14 @@ template <class Body>
 static int plan_session(sdc_handle* h, const int n_steps, const sdc_plan_objective& obj, float* obs, float* share_obs, void* stream,
                         Body&& body) {
   HIP_TRY(hipSetDevice(h->device));
-  PlanSession P{h, {}, nullptr, obs, share_obs, stream};
+  PlanSession P{h, {}, nullptr, 0.0, obs, share_obs, stream};
   if (plan_prepare(h, n_steps, obj, P.R)) return -1;
   void* pin = nullptr;
   if (stage_acquire(h, h->plan_stage, &pin)) return -1;
   double* const g = static_cast<double*>(pin);
   g[0] = 1.0;
   for (int k = 1; k < n_steps; k++) g[k] = g[k - 1] * obj.gamma;
+  P.g_terminal = g[n_steps - 1] * obj.gamma;
   int rc = 0;
   const int staged = stage_commit(h, h->plan_stage, (size_t)n_steps, P.st(), [&](const void* g_dev) {
     P.g_dev = g_dev;
@@ -2114,6 +2145,57 @@ int sdc_plan(sdc_handle* h, int n_cand, int n_steps, const int32_t* actions, con
     const int rc = plan_candidates(P, n_cand, actions, returns, score);
     return rc ? rc : launched("sdc_plan_select_kernel", sdc_plan_select_launch(Q, P.st()));
   });
+}
+
+// ---- plan terms (sdc_plan_terms.hip) ---------------------------------------------------------------------------------------------------
+// Host state of the handle; plan_candidates reads it.  The contract: include/sustaindc_hip.h.
+int sdc_set_plan_terms(sdc_handle* h, const sdc_plan_terms* terms) {
+  static const std::string w = "sdc_set_plan_terms: ";
+  if (!h) return fail_msg(w + "null handle");
+  sdc_plan_terms t;
+  std::memset(&t, 0, sizeof(t));
+  if (!terms || (terms->n_limits == 0 && terms->n_terminal == 0)) {
+    h->plan_terms = t;
+    return 0;
+  }
+  if (terms->n_limits < 0 || terms->n_limits > SDC_PLAN_MAX_LIMITS)
+    return fail_msg(w + "n_limits = " + std::to_string(terms->n_limits) + " outside [0, " + std::to_string(SDC_PLAN_MAX_LIMITS) + "]");
+  if (terms->n_terminal < 0 || terms->n_terminal > SDC_PLAN_MAX_TERMINAL)
+    return fail_msg(w + "n_terminal = " + std::to_string(terms->n_terminal) + " outside [0, " + std::to_string(SDC_PLAN_MAX_TERMINAL) + "]");
+  const auto entry = [](const char* field, const int j) { return std::string(field) + "[" + std::to_string(j) + "] = "; };
+  t.n_limits = terms->n_limits;
+  t.n_terminal = terms->n_terminal;
+  for (int j = 0; j < t.n_limits; j++) {
+    const int col = terms->limit_col[j], side = terms->limit_side[j];
+    const double bound = terms->limit_bound[j], weight = terms->limit_weight[j];
+    if (col < 0 || col >= SDC_INFO_DIM)
+      return fail_msg(w + entry("limit_col", j) + std::to_string(col) + " outside [0, " + std::to_string(SDC_INFO_DIM) + ")");
+    if (side != 1 && side != -1) return fail_msg(w + entry("limit_side", j) + std::to_string(side) + " is neither +1 (upper) nor -1 (lower)");
+    if (!std::isfinite(bound)) return fail_msg(w + entry("limit_bound", j) + std::to_string(bound) + " is not finite");
+    if (!std::isfinite(weight)) return fail_msg(w + entry("limit_weight", j) + std::to_string(weight) + " is not finite");
+    if (weight < 0.0) return fail_msg(w + entry("limit_weight", j) + std::to_string(weight) + " is negative");
+    t.limit_col[j] = col;
+    t.limit_side[j] = side;
+    t.limit_bound[j] = bound;
+    t.limit_weight[j] = weight;
+  }
+  for (int j = 0; j < t.n_terminal; j++) {
+    const int col = terms->terminal_col[j];
+    const double weight = terms->terminal_weight[j];
+    if (col < 0 || col >= SDC_INFO_DIM)
+      return fail_msg(w + entry("terminal_col", j) + std::to_string(col) + " outside [0, " + std::to_string(SDC_INFO_DIM) + ")");
+    if (!std::isfinite(weight)) return fail_msg(w + entry("terminal_weight", j) + std::to_string(weight) + " is not finite");
+    t.terminal_col[j] = col;
+    t.terminal_weight[j] = weight;
+  }
+  h->plan_terms = t;
+  return 0;
+}
+
+int sdc_get_plan_terms(const sdc_handle* h, sdc_plan_terms* out) {
+  if (!h || !out) return fail_msg("sdc_get_plan_terms: null handle or out");
+  *out = h->plan_terms;
+  return 0;
 }
 
 // ---- plan with the cross-entropy method (sdc_cem.hip, sdc_cem_groups.hip) -----------------------------------------------------------

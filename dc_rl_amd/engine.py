@@ -882,6 +882,73 @@ class SdcEngine:
         self._written_on_pinned_stream(returns, score, best, action, actions)
         return PlanResult(best, action, score, returns)
 
+    def set_plan_terms(self, limits=None, terminal=None):
+        """What a linear objective cannot say, kept on the engine (sdc_set_plan_terms): every later `plan`, `plan_cem` and
+        `plan_cem_groups` scores with it until it is cleared.  `limits`: a dict info key -> (low, high, weight), `low` / `high` each a
+        float or None -- every step the candidate pays weight * max(0, low - info[key]) and weight * max(0, info[key] - high) (each
+        side given is one entry, in dict order, low before high; at most PLAN_MAX_LIMITS entries; weight >= 0).  `terminal`: a dict
+        info key -> weight of at most PLAN_MAX_TERMINAL keys -- the info row the horizon's LAST step leaves, weighed and discounted as
+        one step further (gamma ** K), is added to the score: what a finite horizon otherwise defers for free (ls_tasks_in_queue,
+        ls_oldest_task_age, bat_SOC, ...).  No arguments (or two empty dicts) clears the terms.  `returns` never see them; the exact
+        operation order: include/sustaindc_hip.h.  Whether a plan keeps a limit shows in its rollout: `lookahead` / `rollout` of the
+        chosen sequence gives the info rows.  Host state: nothing is enqueued.  ValueError, with the terms set before still in force,
+        for an unknown info key, too many entries, and what the library refuses (a bound or weight that is not finite, a negative
+        limit weight)."""
+        s = L.SdcPlanTerms()
+        entries = []
+        for key, spec in dict(limits or {}).items():
+            if key not in L.INFO_IDX:
+                raise ValueError(f"set_plan_terms: limits key {key!r} is not an info column (dc_rl_amd._lib.INFO_COLS)")
+            try:
+                low, high, weight = spec
+            except (TypeError, ValueError):
+                raise ValueError(f"set_plan_terms: limits[{key!r}] must be (low, high, weight)") from None
+            entries += [(L.INFO_IDX[key], side, float(b), float(weight)) for side, b in ((-1, low), (1, high)) if b is not None]
+        if len(entries) > L.PLAN_MAX_LIMITS:
+            raise ValueError(f"set_plan_terms: limits make {len(entries)} entries (one per side given), at most {L.PLAN_MAX_LIMITS} can be set")
+        s.n_limits = len(entries)
+        for j, (col, side, bound, weight) in enumerate(entries):
+            s.limit_col[j], s.limit_side[j], s.limit_bound[j], s.limit_weight[j] = col, side, bound, weight
+        term = dict(terminal or {})
+        if len(term) > L.PLAN_MAX_TERMINAL:
+            raise ValueError(f"set_plan_terms: terminal names {len(term)} keys, at most {L.PLAN_MAX_TERMINAL} can be weighed")
+        s.n_terminal = len(term)
+        for j, (key, weight) in enumerate(term.items()):
+            if key not in L.INFO_IDX:
+                raise ValueError(f"set_plan_terms: terminal key {key!r} is not an info column (dc_rl_amd._lib.INFO_COLS)")
+            s.terminal_col[j], s.terminal_weight[j] = L.INFO_IDX[key], float(weight)
+        self._set_plan_terms_struct(s)
+
+    def _set_plan_terms_struct(self, s: L.SdcPlanTerms):
+        self._refused(self.lib.sdc_set_plan_terms(self._h, C.byref(s)))
+
+    def _plan_terms_struct(self) -> L.SdcPlanTerms:
+        """the terms as the library holds them (what a copy of this engine is given: SustainDCVecEnv.__deepcopy__)"""
+        s = L.SdcPlanTerms()
+        self._refused(self.lib.sdc_get_plan_terms(self._h, C.byref(s)))
+        return s
+
+    @property
+    def plan_terms(self):
+        """The terms in force, read back from the library (sdc_get_plan_terms) -> (limits, terminal), the two dicts `set_plan_terms`
+        takes (both empty: none set), so that `set_plan_terms(*e.plan_terms)` sets the same entries in the same order.  ValueError for
+        terms set through the C ABI that the dicts cannot say: a column with two entries on one side, or with two weights."""
+        s = self._plan_terms_struct()
+        limits = {}
+        for j in range(s.n_limits):
+            key, at = L.INFO_COLS[s.limit_col[j]], 0 if s.limit_side[j] < 0 else 1
+            had = limits.setdefault(key, [None, None, s.limit_weight[j]])
+            if had[at] is not None or had[2] != s.limit_weight[j]:
+                raise ValueError(f"plan_terms: the entries on {key!r} do not fit (low, high, weight): read them with sdc_get_plan_terms")
+            had[at] = s.limit_bound[j]
+        terminal = {}
+        for j in range(s.n_terminal):
+            key = L.INFO_COLS[s.terminal_col[j]]
+            if key in terminal:
+                raise ValueError(f"plan_terms: {key!r} is in the terminal term twice: read it with sdc_get_plan_terms")
+            terminal[key] = s.terminal_weight[j]
+        return {k: tuple(v) for k, v in limits.items()}, terminal
+
     def _written_on_pinned_stream(self, *arrays):
         if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse them before)
             for x in arrays:

@@ -500,6 +500,17 @@ class SustainDCVecEnv(ShareVecEnv):
         res = self.engine.plan(self._three_columns(actions), reward_weights, gamma, info_weights)
         return self._subset_columns(res, "action")
 
+    def set_plan_terms(self, limits=None, terminal=None):
+        """Limits on info columns and a terminal term for every later plan / plan_cem / plan_cem_groups of this env
+        (SdcEngine.set_plan_terms, which documents the arguments); no arguments clears them.  They stay across reset() and go to a
+        copy.deepcopy of this env."""
+        self.engine.set_plan_terms(limits, terminal)
+
+    @property
+    def plan_terms(self):
+        """(limits, terminal) in force (SdcEngine.plan_terms)"""
+        return self.engine.plan_terms
+
     def _three_columns(self, actions):
         """actions [..., n_agents] in this env's agent order -> the engine's contiguous int32 [..., 3] on its device; with an agent
         subset the other slots' columns are filled with 1"""
@@ -604,6 +615,7 @@ class SustainDCVecEnv(ShareVecEnv):
         """This env (built from src's constructor arguments, never stepped) becomes a copy of src: every env restored from a snapshot
         of src's, the seed and the host-side state copied.  src not reset yet: nothing to restore."""
         self.engine.set_seed(src.engine.seed)
+        self.engine._set_plan_terms_struct(src.engine._plan_terms_struct())
         self.months, self._cfg_id, self._const = list(src.months), list(src._cfg_id), list(src._const)
         if not src._need_reset:
             self.engine.reset()            # (the library restores into envs that have been reset once; every env is overwritten)

@@ -220,7 +220,7 @@ const char* sdc_last_error(void);
  *   313  sdc_clone_envs
  *        (sdc_snapshot_row_bytes, sdc_snapshot_envs, sdc_restore_envs came later without a bump: new entry points, no layout or
  *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise; sdc_plan, sdc_plan_cem,
- *        sdc_rollout_stats and sdc_plan_cem_groups likewise) */
+ *        sdc_rollout_stats and sdc_plan_cem_groups likewise; sdc_set_plan_terms and sdc_get_plan_terms likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -486,6 +486,43 @@ typedef struct {
 } sdc_plan_objective;
 int sdc_plan(sdc_handle* h, int n_cand, int n_steps, const int32_t* actions, const sdc_plan_objective* objective, double* returns,
              double* score, int32_t* best, int32_t* best_action, float* obs, float* share_obs, void* stream);
+
+/* PLAN TERMS: what a linear objective cannot say -- operating limits ("stay below 27 degrees", "SOC never under 0.2": a hinge on an info
+ * column, charged every step) and a terminal term (weights on the info row the horizon's LAST step leaves: queue length, overdue tasks,
+ * the battery's charge -- what a finite horizon otherwise defers for free).  The terms are host state of the handle: sdc_set_plan_terms
+ * copies them, and every later sdc_plan, sdc_plan_cem and sdc_plan_cem_groups call scores with them until they are cleared (terms NULL,
+ * or both counts 0).  While terms are set those calls score a rollout with sdc_plan_score_terms_kernel (csrc/sdc_plan_terms.hip) in
+ * place of sdc_plan_score_kernel; with none set the launch is sdc_plan_score_kernel, as before the terms existed.  Neither call touches
+ * the device.  sdc_get_plan_terms copies out what is set (cleared: every field 0).
+ * The arithmetic, in sdc_plan's words (fp64, no fused multiply-adds, steps k = 0 .. n_steps - 1 in order; s_k as sdc_plan defines it:
+ * the rewards first, then the objective's own columns), with i_k the step's info row:
+ *   for j = 0 .. n_limits - 1 in order, x = (double) i_k[limit_col[j]]:
+ *     d = limit_side[j] > 0 ? x - limit_bound[j] : limit_bound[j] - x
+ *     e = d > 0.0 ? d : 0.0                (a compare and a select: a NaN x gives e = 0)
+ *     s_k = s_k - limit_weight[j] * e
+ *   score += g_k * s_k                     (as in sdc_plan)
+ *   after the horizon's last step k = n_steps - 1 only:
+ *     t = 0.0, then for j = 0 .. n_terminal - 1 in order += terminal_weight[j] * (double) i_k[terminal_col[j]]
+ *     score += (g_{n_steps-1} * gamma) * t     (the discount one fp64 multiply on the host)
+ * `returns` do not see the terms.  Nothing downstream changes: sdc_plan's selection rule and the CEM calls' ranking, elites and refit
+ * are what they were and see these scores.  A horizon rolled out in chunks applies the terminal term once, in its last chunk.
+ * Refused (-2 and a message; the terms set before stay in force): a null handle; n_limits outside [0, SDC_PLAN_MAX_LIMITS], n_terminal
+ * outside [0, SDC_PLAN_MAX_TERMINAL]; a limit_col or terminal_col outside [0, SDC_INFO_DIM); a limit_side other than +1 / -1; a
+ * limit_bound, limit_weight or terminal_weight that is not finite; a negative limit_weight.  sdc_get_plan_terms: a null handle or out. */
+#define SDC_PLAN_MAX_LIMITS 8
+#define SDC_PLAN_MAX_TERMINAL 8
+typedef struct {
+  int32_t n_limits;                                /* 0..SDC_PLAN_MAX_LIMITS */
+  int32_t limit_col[SDC_PLAN_MAX_LIMITS];          /* enum sdc_info_col */
+  int32_t limit_side[SDC_PLAN_MAX_LIMITS];         /* +1: upper bound, -1: lower bound */
+  double limit_bound[SDC_PLAN_MAX_LIMITS];         /* finite */
+  double limit_weight[SDC_PLAN_MAX_LIMITS];        /* finite, >= 0: penalty per unit of excess per step */
+  int32_t n_terminal;                              /* 0..SDC_PLAN_MAX_TERMINAL */
+  int32_t terminal_col[SDC_PLAN_MAX_TERMINAL];
+  double terminal_weight[SDC_PLAN_MAX_TERMINAL];   /* finite */
+} sdc_plan_terms;
+int sdc_set_plan_terms(sdc_handle* h, const sdc_plan_terms* terms);
+int sdc_get_plan_terms(const sdc_handle* h, sdc_plan_terms* out);
 
 /* PLAN WITH THE CROSS-ENTROPY METHOD: n_iters rounds of "sample n_cand candidate sequences from a per-env, per-step, per-agent
  * categorical distribution, score them as sdc_plan does, refit the distribution to the n_elite best and keep the best sequence found so

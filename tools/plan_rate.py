@@ -14,7 +14,11 @@ sdc_cem_sample_kernel's and sdc_cem_refit_kernel's own time.
 envs) and of R = 512 (32 768 envs), beside SdcEngine.plan_cem on a 64-env engine with M = 64 candidates -- as many samples per data
 centre as the R = 64 case -- and beside three single-candidate `plan` calls at the groups' batch size (three 8-step rollouts, scores
 and rewinds); the same process and timing.  Under rocprofv3 as above for sdc_cem_group_sample_kernel's and
-sdc_cem_group_refit_kernel's own time."""
+sdc_cem_group_refit_kernel's own time.
+
+--terms: one `plan` call at 4 096 envs, M = 8 candidates, K = 8 steps with no plan terms (sdc_plan_score_kernel), with 2 limits + 1
+terminal column and with 8 + 8 (sdc_plan_score_terms_kernel: SdcEngine.set_plan_terms); the same process and timing, the three taken
+in turn three times so that a drift of the machine shows as a spread of each.  On a revision without plan terms: the first alone."""
 import json
 import os
 import sys
@@ -117,7 +121,42 @@ def main_groups():
         eng.close()
 
 
+TERMS_FEW = ({"dc_int_temperature": (None, 27.0, 10.0), "bat_SOC": (0.2, None, 5.0)}, {"ls_tasks_in_queue": -1e-3})
+TERMS_FULL = ({"dc_int_temperature": (18.0, 27.0, 10.0), "bat_SOC": (0.2, 0.9, 5.0), "dc_crac_setpoint": (16.0, 22.0, 1.0),
+               "dc_total_power_kW": (None, 1500.0, 1e-3), "ls_tasks_dropped": (None, 0.0, 2.0)},
+              {"ls_tasks_in_queue": -1e-3, "ls_oldest_task_age": -0.1, "ls_overdue_penalty": -1.0, "bat_SOC": 1.0,
+               "ls_norm_tasks_in_queue": -0.5, "ls_average_task_age": -0.1, "dc_int_temperature": -0.01, "bat_CO2_footprint": -1e-6})
+
+
+def main_terms():
+    N, M_, K_ = 4096, 8, 8
+    eng, g = _warm_engine(N)
+    cand = torch.randint(0, 3, (M_, K_, N, 3), dtype=torch.int32, generator=g).cuda()
+    cases = [("no_terms", None)]
+    if hasattr(eng, "set_plan_terms"):
+        cases += [("limits_2_terminal_1", TERMS_FEW), ("limits_8_terminal_8", TERMS_FULL)]
+    scores = {}
+    for name, terms in cases:      # (warm: the handle's buffers, both score kernels' code)
+        if terms is not None:
+            eng.set_plan_terms(*terms)
+        scores[name] = eng.plan(cand, info_weights=COLUMNS).score
+    torch.cuda.synchronize()
+    out = dict(what="plan_terms", n_envs=N, candidates=M_, steps=K_, objective_columns=len(COLUMNS))
+    for turn in range(3):
+        for name, terms in cases:
+            if hasattr(eng, "set_plan_terms"):
+                eng.set_plan_terms(*(terms or ()))
+            out.setdefault(name + "_ms", []).append(timed3(lambda: eng.plan(cand, info_weights=COLUMNS), REPS))
+    out["scores_differ_from_no_terms"] = {k: bool((v != scores["no_terms"]).any()) for k, v in scores.items() if k != "no_terms"}
+    eng.step(cand[0, 0])
+    out["step_kernel_after"] = eng.last_step_kernel()
+    print(json.dumps(out))
+    eng.close()
+
+
 def main():
+    if "--terms" in sys.argv[1:]:
+        return main_terms()
     if "--cem" in sys.argv[1:]:
         return main_cem()
     if "--groups" in sys.argv[1:]:
