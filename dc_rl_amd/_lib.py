@@ -29,7 +29,22 @@ MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
 PLAN_MAX_LIMITS = 8     # include/sustaindc_hip.h SDC_PLAN_MAX_LIMITS: limit entries of sdc_set_plan_terms
 PLAN_MAX_TERMINAL = 8   # include/sustaindc_hip.h SDC_PLAN_MAX_TERMINAL: columns of its terminal term
-PLAN_DEBUG_TWO_STEPS = 16384   # sdc_config.debug_flags bit 14 (test hook): sdc_plan's output block holds two steps
+# sdc_config.debug_flags: include/sustaindc_hip.h SDC_DEBUG_* (what each bit does is written there; csrc/sdc_dispatch.hpp: which
+# kernel a call lands on under each)
+DEBUG_VERIFY = 1                # public mode: a checking kernel behind every single step
+DEBUG_WHY_REBUILD = 2           # measurement modes (the call goes to the general kernel) ...
+DEBUG_PHASES = 8
+DEBUG_STAMPS = 16
+DEBUG_RECORD_WAIT = 32
+DEBUG_STEP_NO_ENV = 64          # test hook: the launch counter starts at $SDC_TEST_STEP_NO
+DEBUG_GENERAL = 128             # mapping overrides: the general kernels ...
+DEBUG_HW_ID = 256               # ... (a measurement mode)
+DEBUG_PAIR = 512                # ... two envs per wavefront
+DEBUG_QUAD = 1024               # ... four
+DEBUG_WIDE = 2048               # ... one lane per env
+DEBUG_WIDE_OFF = 4096           # ... never one lane per env
+DEBUG_BOUND_REPAIR = 8192       # test hook: every 61st (env + launch) repairs its clip bounds from the history
+PLAN_DEBUG_TWO_STEPS = 16384    # test hook: sdc_plan's output block holds two steps
 STATS_FIELDS = 4        # include/sustaindc_hip.h SDC_STATS_FIELDS: sum, min, max, count of positive values (enum sdc_stat_field)
 CEM_MAX_CAND = 64       # include/sustaindc_hip.h SDC_CEM_MAX_CAND: candidates per iteration of sdc_plan_cem
 CEM_MAX_GROUP = 1024    # include/sustaindc_hip.h SDC_CEM_MAX_GROUP: replicas per group of sdc_plan_cem_groups

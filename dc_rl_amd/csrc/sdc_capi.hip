@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "sdc_device.hpp"
+#include "sdc_dispatch.hpp"
 #include "sdc_actor.hpp"
 #include "sdc_clone.hpp"
 #include "sdc_snapshot.hpp"
@@ -189,11 +190,6 @@ struct sdc_handle {
 namespace {
 
 constexpr int PROF_SLOTS = 256;
-#ifndef SDC_STEP_WPB
-#define SDC_STEP_WPB 4
-#endif
-constexpr int STEP_WPB = SDC_STEP_WPB;   // csrc/sdc_step.hip SDC_STEP_WPB: env pairs (wavefronts) per workgroup of the step kernel
-int step_blocks(int n_envs) { return ((n_envs + 1) / 2 + STEP_WPB - 1) / STEP_WPB; }
 // The step counter that stamps re-centring requests wraps at 3 * 2^22: a multiple of the 3 rotating request sets and of
 // the 2^22 the header stamps are taken modulo, so set rotation and stamp ages stay continuous across the wrap (the one
 // request in flight at the wrap misses its full-width result stamp and falls back to the inline sweep).
@@ -202,9 +198,6 @@ int next_step_no(int s, int by) {
   if (by == 0) return s > STEP_WRAP - 4096 ? s % 3 + 3 : s;     // a multi-step launch must not straddle the wrap
   s += by;
   return s >= STEP_WRAP ? s - STEP_WRAP : s;
-}
-bool all_policies(const sdc_handle* h) {
-  return h->d.policy[0] != SDC_POLICY_EXTERNAL && h->d.policy[1] != SDC_POLICY_EXTERNAL && h->d.policy[2] != SDC_POLICY_EXTERNAL;
 }
 
 template <typename T>
@@ -268,87 +261,42 @@ void note_features(sdc_handle* h, int e) {
     h->n_feat_host += 1;
   }
 }
-// THE COMMON CASE, for which the step / rollout kernels exist in a specialised form (sdc_step.hip, template FAST):
-// every env in lock-step with valid feature rows, one data-centre config, the caller's actions on all three slots, the
-// default reward functions, no diagnostics or profiling, an even number of envs, every output array present.
-// debug_flags bit 0 (the verify kernel, a separate launch) and bit 6 (test hook of sdc_create) do not touch the step;
-// bit 7 forces the general kernel (tests compare the two bit for bit).  The common case runs FOUR envs per wavefront
-// (sdc_*_quad_kernel) when the batch is a multiple of four envs and large enough for that mapping to pay: a SIMD has to hold
-// more than one such wavefront, or nothing overlaps its waits.  Measured (tools/step_scan.py, MI355X: 1024 SIMDs): single
-// steps are faster with four envs per wavefront from ~6 700 envs on (6144: 16.3 us with two, 16.7 with four; 7168: 21.7 /
-// 18.3); the multi-step kernels (sdc_rollout, sdc_rollout_actor), whose two-env form keeps two wavefronts per SIMD and
-// needs a second round above 4096 envs, from any batch above 4096 (5120 envs: rollout 17.7 / 14.0 us per step, closed loop
-// 28.2 / 19.7).  debug_flags bit 9 keeps two envs per wavefront, bit 10 picks four whatever the size (the tests compare
-// all of them bit for bit).
-#ifndef SDC_FAST_DEBUG
-#define SDC_FAST_DEBUG 0
-#endif
-constexpr int FAST_DEBUG_FLAGS = SDC_FAST_DEBUG ? (8 | 16 | 32 | 256) : 0;   // (measurement builds: see sdc_step.hip)
-#ifndef SDC_QUAD_MIN_ENVS_STEP
-// (round 4: 5 632 envs = 704 env-pair workgroups = 2.75 dispatch rounds is the last size at which two envs per wavefront win --
-// 12.6 against 13.1 us per step; 6 144 envs: 16.5 against 13.3, the third round full and the spare sweep wavefronts pushing 128 env
-// wavefronts into a fourth)
-#define SDC_QUAD_MIN_ENVS_STEP 5636
-#endif
-#ifndef SDC_QUAD_MIN_ENVS_LOOP
-#define SDC_QUAD_MIN_ENVS_LOOP 4100
-#endif
-bool quad_case(const sdc_handle* h, const bool multi_step) {
-  return (h->cfg.n_envs & 3) == 0 && h->d.n_cfg == 1 && (h->d.debug_flags & (512 | FAST_DEBUG_FLAGS)) == 0 &&
-         (h->cfg.n_envs >= (multi_step ? SDC_QUAD_MIN_ENVS_LOOP : SDC_QUAD_MIN_ENVS_STEP) || (h->d.debug_flags & 1024));
-}
-int quad_blocks(int n_envs) { return (n_envs / 4 + STEP_WPB - 1) / STEP_WPB; }
-// ONE LANE PER ENV (sdc_wide.hip): single steps of the largest lock-step batches -- a multiple of 64 envs, one config of <= 31
-// racks, 16-byte aligned output rows (whole-line stores through the wavefront's staging block); debug_flags bit 11 forces it
-// for any such batch, bit 12 keeps it off
-#ifndef SDC_WIDE_MIN_ENVS
-// (measured, us per step with the episode boundary inside, lane per env / four per wavefront, round 6 -- after the record's one-line
-// layout and the kernel-argument touch: 6 144 envs 13.74 / 13.40, 7 168: 14.02 / 13.69, 7 680: 14.16 / 14.34, 8 192: 14.25 / 14.47,
-// 8 704: 14.63 / 15.52, 12 288: 15.6 / 21.4, 16 384: 16.5 / 24.8, 32 768: 23.6 / 40.5, 65 536: 42.7 / 73.4; round 5's crossover was 9 216)
-#define SDC_WIDE_MIN_ENVS 7680
-#endif
-#ifndef SDC_WIDE_ROLLOUT_MIN_ENVS
-#define SDC_WIDE_ROLLOUT_MIN_ENVS 12288      // sdc_rollout: K single-step launches of the lane-per-env kernel from here (below: one K-step launch)
-#endif
-// the structural conditions of the lane-per-env kernel (either form): a multiple of 64 envs, the queue table's time-major mirror,
-// whole-line stores through the workgroup's staging block (16-byte aligned output rows)
-bool wide_shape(const sdc_handle* h, const float* obs, const float* share_obs, const float* info, const float* final_obs) {
-  const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
-  return (h->cfg.n_envs & 63) == 0 && h->d.qcum_t != nullptr && (h->d.debug_flags & (512 | 1024 | 4096 | FAST_DEBUG_FLAGS)) == 0 &&
-         (h->cfg.n_envs >= SDC_WIDE_MIN_ENVS || (h->d.debug_flags & 2048)) && al16(obs) && al16(share_obs) && al16(info) && al16(final_obs);
-}
-// ... its common-case form (one config of <= 32 racks in <= 8 classes; fast_case holds as well: the caller checks both)
-bool wide_case(const sdc_handle* h, const float* obs, const float* share_obs, const float* info, const float* final_obs) {
-  return wide_shape(h, obs, share_obs, info, final_obs) && h->d.n_cfg == 1 && h->racks_cfg0 <= 32 && h->rack_cls_cfg0 > 0;
-}
-int wide_sweep_blocks(const sdc_handle* h) { return std::min(h->d.rq_max, 256) / 2; }     // (two wavefronts each, a request per wavefront)
-// what every specialised kernel needs: all envs in lock-step with valid feature rows, every output array present, no profiling
-bool lockstep_case(const sdc_handle* h, const float* share_obs, const float* info, bool timed) {
+// WHICH KERNEL a stepping call lands on is decided in sdc_dispatch.hpp, from these facts about the handle and the call (`some_actions`:
+// the caller's array, or the actors' choices for the closed loop) -- host fields and pointer bits, nothing per env
+SdcStepFacts step_facts(const sdc_handle* h, const bool some_actions, const float* obs, const float* share_obs, const float* info,
+                        const float* final_obs, const int32_t* actions_out, const bool timed) {
+  const auto aligned = [](const void* p, const uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; };
   const SdcDev& d = h->d;
-  return h->rel_hint >= 0 && d.feat != nullptr && h->n_feat_host == h->cfg.n_envs && share_obs && info && !timed &&
-         (h->cfg.n_envs & 1) == 0 && (d.debug_flags & ~(1 | 64 | 512 | 1024 | 2048 | 4096 | FAST_DEBUG_FLAGS)) == 0;
+  SdcStepFacts f;
+  f.n_envs = h->cfg.n_envs;
+  f.n_cfg = d.n_cfg;
+  f.racks_cfg0 = h->racks_cfg0;
+  f.rack_cls_cfg0 = h->rack_cls_cfg0;
+  f.racks_max = h->racks_max;
+  f.prm_env_ok = h->prm_env_ok;
+  f.wide_gen_ok = h->wide_gen_ok;
+  f.has_qcum_t = d.qcum_t != nullptr;
+  f.has_feat = d.feat != nullptr;
+  f.n_feat_host = h->n_feat_host;
+  f.rel_hint = h->rel_hint;
+  for (int a = 0; a < 3; a++) {
+    f.policy[a] = d.policy[a];
+    f.reward_method[a] = d.reward_method[a];
+  }
+  f.debug_flags = d.debug_flags;
+  f.actions = some_actions;
+  f.share_obs = share_obs != nullptr;
+  f.info = info != nullptr;
+  f.actions_out = actions_out != nullptr;
+  f.timed = timed;
+  f.rows_al16 = aligned(obs, 16) && aligned(share_obs, 16) && aligned(info, 16) && aligned(final_obs, 16);
+  f.actions_out_al4 = aligned(actions_out, 4);
+  return f;
 }
-bool fast_case(const sdc_handle* h, const int32_t* actions, const float* share_obs, const float* info, bool timed) {
-  const SdcDev& d = h->d;
-  return lockstep_case(h, share_obs, info, timed) &&
-         (d.n_cfg == 1 ? (h->racks_cfg0 > 0 && h->racks_cfg0 <= 32) : (h->prm_env_ok && h->racks_max <= 32)) && actions &&
-         d.policy[0] == SDC_POLICY_EXTERNAL && d.policy[1] == SDC_POLICY_EXTERNAL && d.policy[2] == SDC_POLICY_EXTERNAL &&
-         d.reward_method[0] == SDC_REWARD_DEFAULT && d.reward_method[1] == SDC_REWARD_DEFAULT &&
-         d.reward_method[2] == SDC_REWARD_DEFAULT;
-}
-// ... and the lane-per-env kernel's GENERAL form (sdc_wide.hip GEN): several configs (SdcWideCfg: rebuild_wide_cfg), rule-based
-// policies on any slot, any reward function for the dc / battery agents.  The ls agent keeps default_ls_reward -- with another one
-// the history is not appended to (utils/reward_creator.py:63), a mode the per-lane reward path does not have.
-bool wide_gen_case(const sdc_handle* h, const int32_t* actions, const float* obs, const float* share_obs, const float* info,
-                   const float* final_obs, bool timed) {
-  const SdcDev& d = h->d;
-  const bool acts = actions != nullptr || (d.policy[0] != SDC_POLICY_EXTERNAL && d.policy[1] != SDC_POLICY_EXTERNAL &&
-                                           d.policy[2] != SDC_POLICY_EXTERNAL);
-  return lockstep_case(h, share_obs, info, timed) && wide_shape(h, obs, share_obs, info, final_obs) && h->wide_gen_ok && acts &&
-         d.reward_method[0] == SDC_REWARD_DEFAULT;
-}
+static_assert(SDC_DISPATCH_HIST_MIRROR_MIN_ENVS == SDC_HIST_MIRROR_MIN_ENVS, "sdc_wide_mirrors and the lane-per-env kernel: one threshold");
+static_assert(sdc_kernel_of(SDC_PATH_WIDE, SDC_LAUNCH_SINGLE).envs_per_block == SDC_WAVE, "the lane-per-env kernel: a wavefront of envs per workgroup");
 
-// the largest rack count in use: what fast_case asks of a batch of several configs (every env has a config that is set: prm_env_ok, or
+// the largest rack count in use: what the common case (sdc_dispatch.hpp) asks of a batch of several configs (every env has a config that is set: prm_env_ok, or
 // rebuild_prm_env on its way there)
 void refresh_racks_max(sdc_handle* h) {
   h->racks_max = 0;
@@ -504,13 +452,29 @@ void follow_env(sdc_handle* h, const size_t e, const int t_rel, const bool feat_
   if (h->loc_host.size() == h->host_t_rel.size()) h->loc_host[e] = loc;
 }
 
-// one single-step launch of the lane-per-env kernel (sdc_wide.hip), its common-case form or (`gen`) its general one
-void launch_wide(sdc_handle* h, SdcDev& d, const bool gen, const int rel, const int32_t* actions, float* obs, float* share_obs,
+// the kernels behind sdc_dispatch.hpp's table, by SdcStepPath
+using StepKernel = void (*)(SdcDev, int, const int32_t*, float*, float*, unsigned char*, float*, float*, float*);
+using RolloutKernel = void (*)(SdcDev, int, int, const int32_t*, float*, float*, unsigned char*, float*, float*, float*);
+constexpr StepKernel STEP_KERNELS[5] = {sdc_dynamics_kernel, sdc_dynamics_fast_kernel, sdc_dynamics_quad_kernel, sdc_dynamics_wide_kernel,
+                                        sdc_dynamics_wide_gen_kernel};
+constexpr RolloutKernel ROLLOUT_KERNELS[3] = {sdc_rollout_kernel, sdc_rollout_fast_kernel, sdc_rollout_quad_kernel};
+
+// one single-step launch of `path`'s kernel: its sweep workgroups at the front of the grid, the env workgroups behind them
+void launch_step(sdc_handle* h, SdcDev& d, const SdcStepPath path, const int rel, const int32_t* actions, float* obs, float* share_obs,
                  unsigned char* done, float* info, float* final_obs, float* rew, hipStream_t st) {
-  d.sweep_blocks = wide_sweep_blocks(h);
-  h->last_step_kernel = gen ? "sdc_dynamics_wide_gen_kernel" : "sdc_dynamics_wide_kernel";
-  hipLaunchKernelGGL(gen ? sdc_dynamics_wide_gen_kernel : sdc_dynamics_wide_kernel, dim3(d.sweep_blocks + h->cfg.n_envs / SDC_WAVE),
-                     dim3(2 * SDC_WAVE), 0, st, d, rel, actions, obs, share_obs, done, info, final_obs, rew);
+  const SdcKernelInfo k = sdc_kernel_of(path, SDC_LAUNCH_SINGLE);
+  if (k.sweep == SDC_SWEEP_WIDE) d.sweep_blocks = std::min(d.rq_max, 256) / 2;     // (two wavefronts each, a request per wavefront)
+  h->last_step_kernel = k.name;
+  hipLaunchKernelGGL(STEP_KERNELS[path], dim3(d.sweep_blocks + sdc_env_blocks(k, h->cfg.n_envs)), dim3(SDC_WAVE * k.waves_per_block), 0, st,
+                     d, rel, actions, obs, share_obs, done, info, final_obs, rew);
+}
+// ... and one launch of its multi-step kernel (no sweep workgroups: it re-centres inline)
+void launch_rollout(sdc_handle* h, const SdcDev& d, const SdcStepPath path, const int n_steps, const int32_t* actions, float* obs,
+                    float* share_obs, unsigned char* done, float* info, float* final_obs, float* rew, hipStream_t st) {
+  const SdcKernelInfo k = sdc_kernel_of(path, SDC_LAUNCH_MULTI);
+  h->last_step_kernel = k.name;
+  hipLaunchKernelGGL(ROLLOUT_KERNELS[path], dim3(sdc_env_blocks(k, h->cfg.n_envs)), dim3(SDC_WAVE * k.waves_per_block), 0, st, d, n_steps,
+                     h->rel_hint, actions, obs, share_obs, done, info, final_obs, rew);
 }
 
 // What every stepping call does behind its launch(es) of n_steps steps; obs_last / share_obs_last (may be NULL) are the LAST step's
@@ -703,7 +667,7 @@ int sdc_create(const sdc_config* cfg, sdc_handle** out) {
 
   sdc_handle* h = new sdc_handle();
   h->cfg = *cfg;
-  if (cfg->debug_flags & 64)   // test hook (tests of the launch counter's wrap): start the counter where the environment says
+  if (cfg->debug_flags & SDC_DEBUG_STEP_NO_ENV)   // test hook (tests of the launch counter's wrap): start the counter where the environment says
     if (const char* t = std::getenv("SDC_TEST_STEP_NO")) h->step_no = std::atoi(t) % STEP_WRAP;
   h->device = cfg->device;
   SdcDev& d = h->d;
@@ -767,10 +731,10 @@ int sdc_create(const sdc_config* cfg, sdc_handle** out) {
   A(d.qtab, (size_t)N * d.qstride);
   d.qcum_t = nullptr;
   d.hist_t = nullptr;
-  if ((N & 63) == 0 && (N >= SDC_WIDE_MIN_ENVS || (cfg->debug_flags & 2048))) {      // (batches the lane-per-env kernel can serve: wide_case)
+  if (const SdcWideMirrors mirrors = sdc_wide_mirrors(N, cfg->debug_flags); mirrors.qcum_t) {      // (batches the lane-per-env kernel can serve)
     // ... and BEHIND it, in the same allocation, the history ring's slot-major mirror for the batches that get one (rows qstride ..
     // qstride + hist_cap of the same [row][N] array: the lane-per-env kernel addresses it from the pointer and the strides it holds anyway)
-    const bool mirror = N >= SDC_HIST_MIRROR_MIN_ENVS;
+    const bool mirror = mirrors.hist_t;
     A(d.qcum_t, (size_t)N * ((size_t)d.qstride + (mirror ? (size_t)d.hist_cap : 0)));      // (zeroed by the allocation)
     if (mirror) {
       d.hist_t = d.qcum_t + (size_t)N * d.qstride;
@@ -1119,7 +1083,7 @@ int sdc_reset(sdc_handle* h, const uint8_t* mask_host, const sdc_reset_override*
 int sdc_step(sdc_handle* h, const int32_t* actions, float* obs, float* share_obs, float* rew, uint8_t* done,
              float* info, float* final_obs, void* stream) {
   if (!h || !obs || !rew || !done) return fail_msg("sdc_step: null argument");
-  if (!actions && !all_policies(h)) return fail_msg("sdc_step: actions may only be NULL when every agent slot has a policy");
+  if (!actions && !sdc_all_policies(h->d.policy)) return fail_msg("sdc_step: actions may only be NULL when every agent slot has a policy");
   if (!h->started) return fail_msg("sdc_step: sdc_reset must be called first");
   if (h->steps_to_terminal <= 0)
     return fail_msg("sdc_step: an environment has finished its episode; call sdc_reset (auto_reset is off)");
@@ -1134,52 +1098,29 @@ int sdc_step(sdc_handle* h, const int32_t* actions, float* obs, float* share_obs
   }
   d.step_no = h->step_no;
   h->step_no = next_step_no(h->step_no, 1);
-  if (fast_case(h, actions, share_obs, info, timed) && wide_case(h, obs, share_obs, info, final_obs)) {
-    launch_wide(h, d, false, h->rel_hint, actions, obs, share_obs, done, info, final_obs, rew, st);
-  } else if (wide_gen_case(h, actions, obs, share_obs, info, final_obs, timed)) {
-    // a large batch of SEVERAL configs, or with rule-based policies / other reward functions: the lane-per-env kernel's general form
-    launch_wide(h, d, true, h->rel_hint, actions, obs, share_obs, done, info, final_obs, rew, st);
-  } else if (fast_case(h, actions, share_obs, info, timed) && quad_case(h, false)) {
-    h->last_step_kernel = "sdc_dynamics_quad_kernel";
-    hipLaunchKernelGGL(sdc_dynamics_quad_kernel, dim3(d.sweep_blocks + quad_blocks(N)), dim3(SDC_WAVE * STEP_WPB), 0, st, d,
-                       h->rel_hint, actions, obs, share_obs, done, info, final_obs, rew);
-  } else if (fast_case(h, actions, share_obs, info, timed)) {
-    h->last_step_kernel = "sdc_dynamics_fast_kernel";
-    hipLaunchKernelGGL(sdc_dynamics_fast_kernel, dim3(d.sweep_blocks + step_blocks(N)), dim3(SDC_WAVE * STEP_WPB), 0, st, d,
-                       h->rel_hint, actions, obs, share_obs, done, info, final_obs, rew);
-  } else {
-    h->last_step_kernel = "sdc_dynamics_kernel";
-    hipLaunchKernelGGL(sdc_dynamics_kernel, dim3(d.sweep_blocks + step_blocks(N)), dim3(SDC_WAVE * STEP_WPB), 0, st, d, h->rel_hint,
-                       actions, obs, share_obs, done, info, final_obs, rew);
-  }
-  if (h->cfg.debug_flags & 1) hipLaunchKernelGGL(sdc_reward_verify_kernel, dim3(N), dim3(SDC_BLOCK), 0, st, d, info);
+  const SdcStepPath path = sdc_single_step_path(step_facts(h, actions != nullptr, obs, share_obs, info, final_obs, nullptr, timed));
+  launch_step(h, d, path, h->rel_hint, actions, obs, share_obs, done, info, final_obs, rew, st);
+  if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) hipLaunchKernelGGL(sdc_reward_verify_kernel, dim3(N), dim3(SDC_BLOCK), 0, st, d, info);
   return finish_launch(h, d, 1, obs, share_obs, st, timed, true);
 }
 
 int sdc_rollout(sdc_handle* h, int n_steps, const int32_t* actions, float* obs, float* share_obs, float* rew,
                 uint8_t* done, float* info, float* final_obs, int32_t* actions_out, void* stream) {
   if (!h || !obs || !rew || !done) return fail_msg("sdc_rollout: null argument");
-  if (!actions && !all_policies(h)) return fail_msg("sdc_rollout: actions may only be NULL when every agent slot has a policy");
+  if (!actions && !sdc_all_policies(h->d.policy)) return fail_msg("sdc_rollout: actions may only be NULL when every agent slot has a policy");
   if (!h->started) return fail_msg("sdc_rollout: sdc_reset must be called first");
   if (n_steps <= 0) return fail_msg("sdc_rollout: n_steps must be positive");
   if (n_steps > h->steps_to_terminal)
     return fail_msg("sdc_rollout: the rollout would run past the end of an episode (" +
                     std::to_string(h->steps_to_terminal) + " steps left); split it there");
-  if (h->cfg.debug_flags & 1) return fail_msg("sdc_rollout: verify mode checks single steps; use sdc_step");
+  if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) return fail_msg("sdc_rollout: verify mode checks single steps; use sdc_step");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N = h->cfg.n_envs;
   SdcDev d = h->d;
   d.actions_out = actions_out;
-  // (a MULTI-STEP launch of four envs per wavefront has no launch boundary between its steps: it stays ahead of K lane-per-env
-  // launches up to SDC_WIDE_ROLLOUT_MIN_ENVS envs -- 8 192 envs: 11.6 against 14.3 us per step, 12 288: 15.4 / 15.6, 16 384: 23.4 / 17.4)
-  const bool roll_wide = N >= SDC_WIDE_ROLLOUT_MIN_ENVS || (h->d.debug_flags & 2048);
-  const bool w_common = roll_wide && actions && !actions_out && fast_case(h, actions, share_obs, info, false) &&
-                        wide_case(h, obs, share_obs, info, final_obs);
-  // (the slices of step k start k * N rows in: aligned like the arrays themselves for the batches this kernel takes, N % 64 == 0)
-  const bool w_gen = roll_wide && !w_common && wide_gen_case(h, actions, obs, share_obs, info, final_obs, false) &&
-                     (!actions_out || (reinterpret_cast<uintptr_t>(actions_out) & 3u) == 0);
-  if (w_common || w_gen) {
+  const SdcRolloutPath rp = sdc_rollout_path(step_facts(h, actions != nullptr, obs, share_obs, info, final_obs, actions_out, false));
+  if (rp.per_step) {
     // A batch the lane-per-env kernel serves (sdc_wide.hip), from SDC_WIDE_ROLLOUT_MIN_ENVS envs: n_steps single-step launches of it, the
     // deferred re-centrings running between them as in sdc_step -- faster than one n_steps launch of four envs per wavefront
     // (16 384 envs: 17.7 against 23.4 us per step), the same outputs to the bit.  Its general form likewise: several configs,
@@ -1190,7 +1131,7 @@ int sdc_rollout(sdc_handle* h, int n_steps, const int32_t* actions, float* obs, 
       const size_t o = (size_t)k * N;
       d.actions_out = actions_out ? actions_out + o * 3 : nullptr;
       const int rel_k = h->rel_hint >= 0 ? h->rel_hint + k : h->rel_hint;
-      launch_wide(h, d, w_gen, rel_k, actions ? actions + o * 3 : nullptr, obs + o * SDC_OBS_OUT, share_obs + o * SDC_SHARE_OBS_DIM,
+      launch_step(h, d, rp.path, rel_k, actions ? actions + o * 3 : nullptr, obs + o * SDC_OBS_OUT, share_obs + o * SDC_SHARE_OBS_DIM,
                   done + o, info + o * SDC_INFO_DIM, final_obs, rew + o * 3, st);
     }
   } else {
@@ -1200,11 +1141,7 @@ int sdc_rollout(sdc_handle* h, int n_steps, const int32_t* actions, float* obs, 
     d.step_no = h->step_no;
     h->step_no = next_step_no(h->step_no, n_steps + 3);
     HIP_TRY(hipMemsetAsync(d.rq_count, 0, sizeof(int) * 4, st));
-    const bool r_fast = fast_case(h, actions, share_obs, info, false) && !actions_out, r_quad = r_fast && quad_case(h, true);
-    h->last_step_kernel = r_quad ? "sdc_rollout_quad_kernel" : r_fast ? "sdc_rollout_fast_kernel" : "sdc_rollout_kernel";
-    hipLaunchKernelGGL(r_quad ? sdc_rollout_quad_kernel : r_fast ? sdc_rollout_fast_kernel : sdc_rollout_kernel,
-                       dim3(r_quad ? quad_blocks(N) : step_blocks(N)), dim3(SDC_WAVE * STEP_WPB), 0, st, d, n_steps, h->rel_hint, actions, obs,
-                       share_obs, done, info, final_obs, rew);
+    launch_rollout(h, d, rp.path, n_steps, actions, obs, share_obs, done, info, final_obs, rew, st);
   }
   const size_t last = (size_t)(n_steps - 1) * N;      // the LAST step's slices
   return finish_launch(h, d, n_steps, obs + last * SDC_OBS_OUT, share_obs ? share_obs + last * SDC_SHARE_OBS_DIM : nullptr, st, false, true);
@@ -1259,9 +1196,9 @@ int sdc_rollout_actor(sdc_handle* h, int n_steps, int sample, float* obs, float*
   if (n_steps > h->steps_to_terminal)
     return fail_msg("sdc_rollout_actor: the rollout would run past the end of an episode (" + std::to_string(h->steps_to_terminal) +
                     " steps left); split it there");
-  // the common case only: what fast_case checks, with the actions coming from the actors instead of the caller
-  static const int32_t some_actions = 0;
-  if (!fast_case(h, &some_actions, share_obs, info, false) || (h->cfg.debug_flags & 1))
+  // the common case only, with the actions coming from the actors instead of the caller
+  const SdcActorPath ap = sdc_actor_path(step_facts(h, true, obs, share_obs, info, final_obs, actions_out, false));
+  if (ap.refused)
     return fail_msg("sdc_rollout_actor: needs the common case (lock-step batch with feature rows, one data-centre config of <= 32 "
                     "racks, external-action slots, default rewards, an even number of envs, no debug flags)");
   HIP_TRY(hipSetDevice(h->device));
@@ -1273,7 +1210,6 @@ int sdc_rollout_actor(sdc_handle* h, int n_steps, int sample, float* obs, float*
   d.step_no = h->step_no;
   h->step_no = next_step_no(h->step_no, n_steps + 3);
   HIP_TRY(hipMemsetAsync(d.rq_count, 0, sizeof(int) * 4, st));
-  constexpr int AWPB = 8;     // sdc_step.hip SDC_ACTOR_WPB
   if (!h->actor_lds_set) {     // (a per-device attribute: once per handle, not once per process)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(sdc_rollout_actor_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)sdc_rollout_actor_lds_bytes()));
@@ -1281,17 +1217,12 @@ int sdc_rollout_actor(sdc_handle* h, int n_steps, int sample, float* obs, float*
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sdc_rollout_actor_quad_lds_bytes()));
     h->actor_lds_set = true;
   }
-  if (quad_case(h, true)) {   // four envs per wavefront (batches above 4096 envs)
-    const int blocks = (N / 4 + AWPB - 1) / AWPB;
-    hipLaunchKernelGGL(sdc_rollout_actor_quad_kernel, dim3(blocks), dim3(SDC_WAVE * AWPB), sdc_rollout_actor_quad_lds_bytes(), st, d,
-                       n_steps, h->rel_hint, h->actor_dev, h->obs_latch, sample ? 1 : 0, obs, share_obs, done, info, final_obs, rew,
-                       actions_out, logits_out, h->obs_latch);
-  } else {
-    const int blocks = ((N + 1) / 2 + AWPB - 1) / AWPB;
-    hipLaunchKernelGGL(sdc_rollout_actor_kernel, dim3(blocks), dim3(SDC_WAVE * AWPB), sdc_rollout_actor_lds_bytes(), st, d, n_steps,
-                       h->rel_hint, h->actor_dev, h->obs_latch, sample ? 1 : 0, obs, share_obs, done, info, final_obs, rew, actions_out,
-                       logits_out, h->obs_latch);
-  }
+  const bool quad = ap.path == SDC_PATH_QUAD;      // four envs per wavefront (batches above 4096 envs)
+  const SdcKernelInfo k = sdc_kernel_of(ap.path, SDC_LAUNCH_ACTOR);
+  hipLaunchKernelGGL(quad ? sdc_rollout_actor_quad_kernel : sdc_rollout_actor_kernel, dim3(sdc_env_blocks(k, N)),
+                     dim3(SDC_WAVE * k.waves_per_block), quad ? sdc_rollout_actor_quad_lds_bytes() : sdc_rollout_actor_lds_bytes(), st, d,
+                     n_steps, h->rel_hint, h->actor_dev, h->obs_latch, sample ? 1 : 0, obs, share_obs, done, info, final_obs, rew,
+                     actions_out, logits_out, h->obs_latch);
   // (after an auto-reset alone: the next launch starts from the reset observations)
   const size_t last = (size_t)(n_steps - 1) * N;
   return finish_launch(h, d, n_steps, obs + last * SDC_OBS_OUT, share_obs + last * SDC_SHARE_OBS_DIM, st, false, false);
@@ -1968,7 +1899,7 @@ static int plan_refused(const char* who, const sdc_handle* h, const int n_steps,
   if (((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(share_obs)) & 3u) != 0)
     return fail_msg(w + "obs / share_obs rows not dword-aligned");
   if (!h->started) return fail_msg(w + "sdc_reset must be called first");
-  if (h->cfg.debug_flags & 1) return fail_msg(w + "verify mode checks single steps (sdc_rollout refuses it as well)");
+  if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) return fail_msg(w + "verify mode checks single steps (sdc_rollout refuses it as well)");
   if (h->cfg.auto_reset && n_steps >= h->steps_to_terminal)
     return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would finish an episode (" + std::to_string(h->steps_to_terminal) +
                     " steps left): the auto-reset kills the mark");
@@ -2375,8 +2306,8 @@ int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int ac
     return fail_msg(w + "counts / obs / share_obs / rew / info / final_obs rows not dword-aligned");
   if (accumulate != 0 && accumulate != 1) return fail_msg(w + "accumulate = " + std::to_string(accumulate) + " outside {0, 1}");
   if (!h->started) return fail_msg(w + "sdc_reset must be called first");
-  if (h->cfg.debug_flags & 1) return fail_msg(w + "verify mode checks single steps (sdc_rollout refuses it as well)");
-  if (!actions && !all_policies(h)) return fail_msg(w + "actions may only be NULL when every agent slot has a policy");
+  if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) return fail_msg(w + "verify mode checks single steps (sdc_rollout refuses it as well)");
+  if (!actions && !sdc_all_policies(h->d.policy)) return fail_msg(w + "actions may only be NULL when every agent slot has a policy");
   if (n_steps > h->steps_to_terminal)
     return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" +
                     std::to_string(h->steps_to_terminal) + " steps left)");

@@ -199,7 +199,7 @@ struct SdcRefillRes {
 struct SdcDev {
   int n_envs, episode_steps, hist_cap, queue_max, table_len, lw, qstride, max_roll_days;
   int env_base;     // global index of env 0 (sdc_config.env_index_base): keys the reset RNG
-  int debug_flags;  // bit 0: cross-check the tracked order statistics against the bisection every step
+  int debug_flags;  // sdc_config.debug_flags (SDC_DEBUG_*) without SDC_PLAN_DEBUG_TWO_STEPS
   int reward_method[3];   // sdc_reward_method per agent slot (ls, dc, bat)
   int policy[3];          // sdc_policy per agent slot: who chooses the action
   double tr_limit;        // trim-and-respond: TandR_monitor_limit
@@ -247,10 +247,10 @@ struct SdcDev {
                      // sweeps and rebuilds read an env's ring as a whole: they keep the ring itself
 };
 
-// TEST HOOK (debug_flags bit 13 = 8192): every 61st (env + launch) takes env_reward's "a clip bound left its window" repair whatever the
+// TEST HOOK (debug_flags SDC_DEBUG_BOUND_REPAIR): every 61st (env + launch) takes env_reward's "a clip bound left its window" repair whatever the
 // windows say -- the path is otherwise taken by ~4e-8 of the env-steps (tests/test_gpu_bound_repair.py runs it in verify mode)
 __device__ __forceinline__ bool bound_repair_forced(const SdcDev& S, const int env) {
-  return (S.debug_flags & 8192) != 0 && (unsigned)(env + S.step_no) % 61u == 0u;
+  return (S.debug_flags & SDC_DEBUG_BOUND_REPAIR) != 0 && (unsigned)(env + S.step_no) % 61u == 0u;
 }
 
 // per-kernel timing without host events: one lane per workgroup stamps the constant-rate wall clock at entry and

@@ -59,7 +59,7 @@ struct PairShared {
   float info[EPW][SDC_INFO_DIM];
   unsigned long long dbg_t[2];
   unsigned long long dbg_s[2];
-  unsigned dbg_bits;                   // (diagnostics, debug_flags bit 3) which rare paths this wavefront's step took
+  unsigned dbg_bits;                   // (diagnostics, SDC_DEBUG_PHASES) which rare paths this wavefront's step took
   sdc_rw::TailLds tl;                  // scratch of the ring paths (window refill, rebuild): one env at a time
 };
 
@@ -138,7 +138,7 @@ __device__ __forceinline__ double lrec_f64(const unsigned* rp, int idx) { return
 // the coupled dynamics at cursor i and the observation at i' = i + 1 of BOTH envs of the wavefront: lane = (half h, l)
 //
 // FAST (here and in pair_reward_fast / pair_step): the launch is the COMMON CASE, which the host checks before it picks
-// the kernel (sdc_capi.hip fast_case) -- every env in lock-step with valid feature rows, one data-centre config, the
+// the kernel (sdc_dispatch.hpp sdc_common_case) -- every env in lock-step with valid feature rows, one data-centre config, the
 // caller's actions on all three slots, the default reward functions, no diagnostics, an even number of envs, all output
 // arrays present.  What the general code decides at run time is then a compile-time constant: the same source, the
 // same arithmetic in the same order (so both kernels give the same bits), minus the tests, the exec-mask bookkeeping
@@ -530,7 +530,7 @@ __device__ __forceinline__ void env_reward(const SdcDev& S, const int env, const
     bool wd1 = false, wd3 = false, wdu = false, wdl = false;   // a window goes back to memory only if its lanes changed
     double A1 = rec_f64(hd0, H_A1), A2 = rec_f64(hd0, H_A2);
     bool ok = n >= SMALL_N && qt_valid(q1) && qt_valid(q3) && qt_valid(bu) && qt_valid(bl) && rec_i32(hd0, H_VALID) == 1;
-    int why = ok ? 0 : 1;                            // diagnostics (debug_flags bit 1): why a rebuild was needed
+    int why = ok ? 0 : 1;                            // diagnostics (SDC_DEBUG_WHY_REBUILD): why a rebuild was needed
     if (__builtin_expect(ok && append, 1)) {
       // O(1) updates: running sums, the four windows
       const double vn = key_f64(x_new), vo = has_old ? key_f64(x_old) : 0.0;
@@ -613,7 +613,7 @@ __device__ __forceinline__ void env_reward(const SdcDev& S, const int env, const
           const double t2 = (qs2_0 - (double)qc0 * (b.ub * b.ub)) + (qs2_1 - (double)qc1 * (b.lb * b.lb));
           clipped_moments(n, b, A1, A2, t1, t2, mean, sd, inv_sd, S.hist_cap, S.rc_hist_cap, S.hist_cap_d);
           done_eval = true;
-          path = 5 + ((S.debug_flags & 2) ? why : 0);      // 5: the clip bounds' tail sums redone from the ring
+          path = 5 + ((S.debug_flags & SDC_DEBUG_WHY_REBUILD) ? why : 0);      // 5: the clip bounds' tail sums redone from the ring
         }
       } else {
         why = 4;
@@ -646,7 +646,7 @@ __device__ __forceinline__ void env_reward(const SdcDev& S, const int env, const
         const double t2 = (qs2_0 - (double)qc0 * (rb.b.ub * rb.b.ub)) + (qs2_1 - (double)qc1 * (rb.b.lb * rb.b.lb));
         clipped_moments(n, rb.b, A1, A2, t1, t2, mean, sd, inv_sd);
       }
-      path = 3 + ((S.debug_flags & 2) ? why : 0);
+      path = 3 + ((S.debug_flags & SDC_DEBUG_WHY_REBUILD) ? why : 0);
     }
     put_u32(o0, H_KB, kb0);
     put_u32(o0, H_KB + 1, kb1);
@@ -764,7 +764,7 @@ __device__ __forceinline__ unsigned long long pair_reward_fast(const SdcDev& S, 
   Win bl = win_from(kw, (int)hp[H_BL + T_R0], (int)hp[H_BL + T_HI]);
   double A1 = lrec_f64(hp, H_A1), A2 = lrec_f64(hp, H_A2);
   bool ok = append & (n >= SMALL_N) & (q1.hi > 0) & (q3.hi > 0) & (bu.hi > 0) & (bl.hi > 0) & ((int)hp[H_VALID] == 1);
-  if constexpr (!FAST) ok = ok & !bound_repair_forced(S, envc);     // (test hook, debug_flags bit 13: env_reward takes the step)
+  if constexpr (!FAST) ok = ok & !bound_repair_forced(S, envc);     // (test hook, SDC_DEBUG_BOUND_REPAIR: env_reward takes the step)
   // ---- deferred re-centrings (SdcRefillReq / SdcRefillRes): a window requested two steps ago arrives now --------------
   unsigned pend0 = hp[H_PEND], pend1 = hp[H_PEND + 1], pend2 = hp[H_PEND + 2], pend3 = hp[H_PEND + 3];
   // cached first / last key of every window (see below)
@@ -1035,7 +1035,7 @@ __device__ __forceinline__ unsigned long long pair_reward_fast(const SdcDev& S, 
       rew[envc * 3 + 2] = (float)r[2];
       float* inf = sh.info[h];
       inf[SDC_INFO_ENERGY_Z] = (float)z;
-      inf[SDC_INFO_RESERVED] = wdc ? 2.0f : (SDC_DBG_OK(FAST) && (S.debug_flags & 8) && filed) ? 4.0f : 0.0f;   // no ring read by this wavefront (2: a deferred re-centred window arrived; 4, with the timing diagnostics on: a request was filed)
+      inf[SDC_INFO_RESERVED] = wdc ? 2.0f : (SDC_DBG_OK(FAST) && (S.debug_flags & SDC_DEBUG_PHASES) && filed) ? 4.0f : 0.0f;   // no ring read by this wavefront (2: a deferred re-centred window arrived; 4, with the timing diagnostics on: a request was filed)
       inf[SDC_INFO_EP_RETURN_LS] = (float)ret[0];
       inf[SDC_INFO_EP_RETURN_DC] = (float)ret[1];
       inf[SDC_INFO_EP_RETURN_BAT] = (float)ret[2];
@@ -1108,8 +1108,8 @@ __device__ __forceinline__ void pair_step(const SdcDev& S, PairShared& sh, const
   if (one_cfg && l < P_COUNT)
     prm_pre = (!FAST || S.n_cfg == 1) ? reinterpret_cast<const double*>(&S.dc[0].p.m_cpu)[l]
                                       : S.prm_env[(size_t)envc * 32 + l];   // (several configs: the env's own copy, see SdcDev)
-  const unsigned long long dbg_entry = (SDC_DBG_OK(FAST) && (S.debug_flags & 16)) ? wall_clock64() : 0ull;
-  if (SDC_DBG_OK(FAST) && (S.debug_flags & 8) && lane == 0) sh.dbg_bits = 0u;
+  const unsigned long long dbg_entry = (SDC_DBG_OK(FAST) && (S.debug_flags & SDC_DEBUG_STAMPS)) ? wall_clock64() : 0ull;
+  if (SDC_DBG_OK(FAST) && (S.debug_flags & SDC_DEBUG_PHASES) && lane == 0) sh.dbg_bits = 0u;
 
   // ---- level 0: the two state records (one dwordx2 per lane, 512 contiguous bytes), headers, actions ----------------
   uint2* recp = reinterpret_cast<uint2*>(S.rec + (size_t)envc * SDC_REC_DWORDS) + l;
@@ -1126,7 +1126,7 @@ __device__ __forceinline__ void pair_step(const SdcDev& S, PairShared& sh, const
   if (FAST || S.policy[1] == SDC_POLICY_EXTERNAL) a_dc = act_v.y;
   if (FAST || S.policy[2] == SDC_POLICY_EXTERNAL) a_bat = act_v.z;
   unsigned long long dbg_rec = 0ull;
-  if (SDC_DBG_OK(FAST) && __builtin_expect((S.debug_flags & 32) != 0, 0)) {
+  if (SDC_DBG_OK(FAST) && __builtin_expect((S.debug_flags & SDC_DEBUG_RECORD_WAIT) != 0, 0)) {
     unsigned tmp = rr.x;
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(tmp)::"memory");
     dbg_rec = wall_clock64() + (tmp & 0u);
@@ -1243,7 +1243,7 @@ __device__ __forceinline__ void pair_step(const SdcDev& S, PairShared& sh, const
   }
 
   unsigned long long dbg_a0 = 0ull;
-  if (SDC_DBG_OK(FAST) && __builtin_expect((S.debug_flags & 8) != 0, 0)) dbg_a0 = wall_clock64();
+  if (SDC_DBG_OK(FAST) && __builtin_expect((S.debug_flags & SDC_DEBUG_PHASES) != 0, 0)) dbg_a0 = wall_clock64();
   // the rank windows of both envs, one key each per lane: wanted at the end of the step, so the loads are issued here --
   // after the start-of-launch burst of every env's record / header / gather loads -- and ride along in 8 registers
   // reward-side state (headers: returns, trackers, sums; the rank windows' keys; the evicted ring key): wanted at the end of
@@ -1282,7 +1282,7 @@ __device__ __forceinline__ void pair_step(const SdcDev& S, PairShared& sh, const
     wave_sync();
   }
   __builtin_amdgcn_s_setprio(SDC_BASE_PRIO);
-  if (SDC_DBG_OK(FAST) && __builtin_expect((S.debug_flags & 8) != 0, 0) && lane == 0) sh.dbg_t[0] = wall_clock64();
+  if (SDC_DBG_OK(FAST) && __builtin_expect((S.debug_flags & SDC_DEBUG_PHASES) != 0, 0) && lane == 0) sh.dbg_t[0] = wall_clock64();
 
   // ---- rewards + reward-state upkeep: both envs at once on the O(1) path; an env that needs its ring (or anything
   // unusual) is redone whole-wavefront from its untouched state ------------------------------------------------------------
@@ -1305,20 +1305,20 @@ __device__ __forceinline__ void pair_step(const SdcDev& S, PairShared& sh, const
                pick_f64(d.norm_ci, e), pick_f64(d.oldest_norm, e), pick_i32(d.overdue, e), pick_i32(d.hourq_n, e),
                pick_f64(d.p_it, e), pick_f64(d.total_kw, e), pick_f64(d.water, e), rew, sh.info[e], sh.tl);
   }
-  if (SDC_DBG_OK(FAST) && __builtin_expect((S.debug_flags & 8) != 0, 0)) {
+  if (SDC_DBG_OK(FAST) && __builtin_expect((S.debug_flags & SDC_DEBUG_PHASES) != 0, 0)) {
     wave_sync();
     if (lane == 0) {
       const unsigned long long dbg_a3 = wall_clock64();
       for (int e = 0; e < n_here; e++) {
         float* inf = sh.info[e];
-        inf[40] = (S.debug_flags & 32) ? (float)(dbg_rec - dbg_entry) : (S.debug_flags & 16) ? (float)(dbg_a0 & 0xFFFFFull) : 0.0f;
-        inf[41] = (S.debug_flags & 16) ? (float)(dbg_a0 - dbg_entry) : (float)(sh.dbg_t[0] - dbg_a0);
+        inf[40] = (S.debug_flags & SDC_DEBUG_RECORD_WAIT) ? (float)(dbg_rec - dbg_entry) : (S.debug_flags & SDC_DEBUG_STAMPS) ? (float)(dbg_a0 & 0xFFFFFull) : 0.0f;
+        inf[41] = (S.debug_flags & SDC_DEBUG_STAMPS) ? (float)(dbg_a0 - dbg_entry) : (float)(sh.dbg_t[0] - dbg_a0);
         inf[42] = (float)(dbg_a3 - sh.dbg_t[0]);
         if (SDC_STAMP_A != 0 && SDC_STAMP_B != 0) inf[42] = (float)(sh.dbg_s[1] - sh.dbg_s[0]);
         inf[SDC_INFO_RESERVED] += (float)(8u * sh.dbg_bits);
-        if (S.debug_flags & 256)     // where the wavefront ran: XCC id << 16 | HW_ID (wave, SIMD, CU, SH, SE)
+        if (S.debug_flags & SDC_DEBUG_HW_ID)     // where the wavefront ran: XCC id << 16 | HW_ID (wave, SIMD, CU, SH, SE)
           inf[40] = (float)(((__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xFu) << 16) | (__builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFFFFu));
-        inf[43] = (S.debug_flags & 16) ? (float)(dbg_a3 & 0xFFFFFull) : (float)(dbg_a3 - dbg_a0);
+        inf[43] = (S.debug_flags & SDC_DEBUG_STAMPS) ? (float)(dbg_a3 & 0xFFFFFull) : (float)(dbg_a3 - dbg_a0);
       }
     }
   }

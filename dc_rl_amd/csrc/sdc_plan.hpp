@@ -2,7 +2,7 @@
 // of the output block its rollouts write into.
 //
 // THE OUTPUT BLOCK belongs to the handle: the arrays sdc_rollout fills for `steps` steps, each on a 256-byte boundary (the lane-per-env
-// step kernel stores whole lines: sdc_capi.hip wide_shape), in this order:
+// step kernel stores whole lines: sdc_dispatch.hpp sdc_wide_structural), in this order:
 //   obs [steps][N][3][26] | share_obs [steps][N][29] | rew [steps][N][3] | info [steps][N][44] | done [steps][N] | final_obs [N][3][26]
 // 617 bytes per env-step, of which the score kernel reads the 12 of rew and, with info columns in the objective, the 176 of info.  The
 // block is capped at SDC_PLAN_SCRATCH_BYTES; a horizon that does not fit is rolled out in chunks of sdc_plan_steps_fit steps.
@@ -23,7 +23,6 @@
 #include "../../include/sustaindc_hip.h"
 
 #define SDC_PLAN_SCRATCH_BYTES ((size_t)256 << 20)   // cap of the output block
-#define SDC_PLAN_DEBUG_TWO_STEPS 16384               // sdc_config.debug_flags bit 14 (test hook): the block holds two steps
 #define SDC_PLAN_SCORE_BLOCK 64                      // score kernel: envs (lanes) per workgroup
 #define SDC_PLAN_TILE_ROWS 32                        // ... info rows per LDS tile fill (half the workgroup's)
 #define SDC_PLAN_TILE_LOADS 6                        // ... 16-byte units a lane loads per fill: ceil(32 * 11 / 64)

@@ -95,8 +95,7 @@ extern "C" __global__ SDC_QUAD_BOUNDS void sdc_rollout_quad_kernel(
 // Workgroup = 8 wavefronts (16 envs) sharing ONE copy of the three networks in LDS (76 KB; with the wavefronts' own
 // 5.5 KB each and the constant table ~122 KB of the CU's 160 KB: one workgroup per CU, two wavefronts per SIMD at 4096
 // envs).  obs_in [N][3][26]: the observations the first actions are chosen from (the engine's latest).  actions_out
-// [K][N][3] receives what the actors chose, logits_out [K][N][3][3] (or null) their logits.
-#define SDC_ACTOR_WPB 8
+// [K][N][3] receives what the actors chose, logits_out [K][N][3][3] (or null) their logits.  (SDC_ACTOR_WPB: sdc_tuning.hpp)
 struct ActorLds {
   PairShared shs[SDC_ACTOR_WPB];
   double ktab[SDC_K_LDS];

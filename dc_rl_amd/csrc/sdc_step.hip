@@ -46,7 +46,7 @@ __device__ __forceinline__ void dynamics_launch(const SdcDev& S, PairShared* shs
   if (!FAST && lane == 0) prof_stamp(S, SDC_PROF_DYNAMICS, env0, 1);
 }
 // (three resident wavefronts per SIMD: two env pairs + room for a spare one, <= 168 VGPRs)
-// the general kernel, and the one for the common case (see pair_dynamics; the host picks: sdc_capi.hip fast_case)
+// the general kernel, and the one for the common case (see pair_dynamics; the host picks: sdc_dispatch.hpp sdc_common_case)
 extern "C" __global__ SDC_STEP_BOUNDS void sdc_dynamics_kernel(
     SdcDev S, const int rel_hint, const int32_t* __restrict__ actions, float* __restrict__ obs, float* __restrict__ share_obs,
     unsigned char* __restrict__ done, float* __restrict__ info, float* __restrict__ final_obs, float* __restrict__ rew) {

@@ -24,7 +24,7 @@
 // env_reward() (sdc_pairstep.hpp).
 //
 // The host picks this kernel for a lock-step batch of a multiple of 64 envs from SDC_WIDE_MIN_ENVS: its COMMON-CASE form (one
-// config, the caller's actions, default rewards: sdc_capi.hip wide_case) or its GENERAL form (template GEN, wide_gen_case): every
+// config, the caller's actions, default rewards: sdc_dispatch.hpp sdc_wide_common) or its GENERAL form (template GEN, sdc_wide_general): every
 // lane carries its own config (SdcWideCfg, staged in LDS: BASELINE configs[3]'s 16 / 20 / 25-rack mixes), the rule-based policies of
 // utils/rbc_agents.py:3-47, utils/trim_and_respond.py:8-38 and utils/base_agents.py choose actions inside the step, the dc / battery
 // agents take any of utils/reward_creator.py:154-334.  Same expressions either way: the same bits as the pair kernels.
@@ -1129,7 +1129,7 @@ __device__ __forceinline__ void wide_rewards(const SdcDev& S, WideSharedT<GEN>& 
     r_a[0] = rls; r_a[1] = foot; r_a[2] = foot;
     if constexpr (GEN) {
       // the dc / battery agents' reward functions (utils/reward_creator.py:154-334: sdc_trackers.hpp agent_reward); the ls agent keeps
-      // default_ls_reward here (wide_gen_case)
+      // default_ls_reward here (sdc_wide_general)
       const WideHandGen& G = *reinterpret_cast<const WideHandGen*>(sh.row + WE * 32);
       const double ite_kw = SDC_DIV_CONST(G.p_it[lane], 1e3), hour = (double)hourq_n * 0.25;
 #pragma unroll
@@ -1297,7 +1297,7 @@ extern "C" __global__ __launch_bounds__(2 * SDC_WAVE) __attribute__((amdgpu_wave
 }
 
 // ... and its GENERAL form: every lane its own config, rule-based policies, any reward function for the dc / battery agents
-// (sdc_capi.hip wide_gen_case).  51 KB of LDS: three workgroups per CU.
+// (sdc_dispatch.hpp sdc_wide_general).  51 KB of LDS: three workgroups per CU.
 extern "C" __global__ __launch_bounds__(2 * SDC_WAVE) __attribute__((amdgpu_waves_per_eu(1, 2))) void sdc_dynamics_wide_gen_kernel(
     SdcDev S, const int rel_hint, const int32_t* __restrict__ actions, float* __restrict__ obs, float* __restrict__ share_obs,
     unsigned char* __restrict__ done, float* __restrict__ info, float* __restrict__ final_obs, float* __restrict__ rew) {

@@ -816,8 +816,8 @@ class SdcEngine:
         state, output buffers, closed-loop copy -- is where it was, with one difference: a rewind clears the header's re-centring
         stamps, so deferred re-centrings in flight at the call are dropped and re-requested by the steps that need them (window
         placement and info[reserved] may differ from a run that never looked ahead; no other output does).  The rollouts ask for
-        the info rows although they are thrown away: without them the batch is not the specialised kernels' case (sdc_capi.hip
-        lockstep_case) and every candidate would run the general kernel.  ValueError for a K that would finish an episode:
+        the info rows although they are thrown away: without them the batch is not the specialised kernels' case (csrc/sdc_dispatch.hpp
+        sdc_specialised_ok) and every candidate would run the general kernel.  ValueError for a K that would finish an episode:
         K >= steps_to_episode_end() with auto_reset (the reset would kill the mark), K > steps_to_episode_end() without; and for
         K > MARK_MAX_STEPS."""
         t = self.torch
@@ -860,7 +860,7 @@ class SdcEngine:
         the re-centring stamps) and the same price: the call uses up the envs' one live mark, so a mark taken earlier is dead
         afterwards.  A slot on a built-in policy ignores its action column.  ValueError, with the engine untouched, for malformed
         actions, an unknown info key or too many, and what the library refuses: K > MARK_MAX_STEPS, K >= steps_to_episode_end() with
-        auto_reset (> without), no reset() yet, gamma outside (0, 1], verify mode (debug_flags bit 0: rollouts have none)."""
+        auto_reset (> without), no reset() yet, gamma outside (0, 1], verify mode (debug_flags DEBUG_VERIFY: rollouts have none)."""
         t = self.torch
         if not (isinstance(actions, t.Tensor) and actions.dtype == t.int32 and actions.is_cuda and actions.is_contiguous() and
                 actions.dim() == 4 and tuple(actions.shape[2:]) == (self.n_envs, 3) and actions.shape[0] >= 1 and actions.shape[1] >= 1):
@@ -1100,7 +1100,7 @@ class SdcEngine:
         EpisodeStats of this engine to continue (its tensors are updated in place and it is returned); calls split anywhere give the
         bits of one call.  The engine moves; its single-step views (obs, share_obs, rew, done, info, final_obs) follow the last step,
         as after `rollout`.  ValueError, with the engine untouched, for malformed arguments and what the library refuses: K < 1,
-        K > steps_to_episode_end(), no reset() yet, verify mode (debug_flags bit 0)."""
+        K > steps_to_episode_end(), no reset() yet, verify mode (debug_flags DEBUG_VERIFY)."""
         t = self.torch
         if actions is None:
             if n_steps is None or any(p == 0 for p in self.policy):

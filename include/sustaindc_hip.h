@@ -98,6 +98,43 @@ enum sdc_info_col {
 
 typedef struct sdc_handle sdc_handle;
 
+/* sdc_config.debug_flags, one name per bit the library reads.  Four kinds:
+ *   PUBLIC MODE       changes what a call does, on any kernel;
+ *   MEASUREMENT MODE  in-kernel diagnostics that only the general kernels carry: the call goes to the general step / rollout kernel
+ *                     (they overwrite info[reserved] / the episode-return columns info[40..43]);
+ *   MAPPING OVERRIDE  picks among the kernels that give the same results to the bit (csrc/sdc_dispatch.hpp: tests compare them);
+ *   TEST HOOK         forces a path the tests could not otherwise reach.
+ * A bit without a name sends the call to the general kernel as well. */
+#define SDC_DEBUG_VERIFY 1           /* bit 0, PUBLIC MODE: after every sdc_step check the incremental reward state (the four rank
+                                        windows, running sums) and the reported z-score against an exact bisection and a direct fp64
+                                        pass over each env's history (slow; a mismatch sets SDC_FAULT_ORDER_STAT).  The multi-step
+                                        entry points refuse it */
+#define SDC_DEBUG_WHY_REBUILD 2      /* bit 1, MEASUREMENT MODE: info[reserved]'s path codes 3 / 5 carry why a rebuild happened */
+#define SDC_DEBUG_PHASES 8           /* bit 3, MEASUREMENT MODE: per-wavefront phase durations in info[40..43], the rare paths the
+                                        wavefront's step took in info[reserved] above bit 3 */
+#define SDC_DEBUG_STAMPS 16          /* bit 4, MEASUREMENT MODE (with bit 3): absolute wavefront start / end stamps instead */
+#define SDC_DEBUG_RECORD_WAIT 32     /* bit 5, MEASUREMENT MODE (with bit 3): info[40] = entry until the state record has arrived */
+#define SDC_DEBUG_STEP_NO_ENV 64     /* bit 6, TEST HOOK: sdc_create reads the environment variable SDC_TEST_STEP_NO and starts the
+                                        launch counter there (tests of the counter's wrap); the step does not see the bit */
+#define SDC_DEBUG_GENERAL 128        /* bit 7, MAPPING OVERRIDE: always the GENERAL step / rollout kernels, never the ones
+                                        specialised for the common case */
+#define SDC_DEBUG_HW_ID 256          /* bit 8, MEASUREMENT MODE (with bit 3): info[40] = where the wavefront ran (XCC, SE, SH, CU,
+                                        SIMD, wave) */
+#define SDC_DEBUG_PAIR 512           /* bit 9, MAPPING OVERRIDE: the common-case kernels with two envs per wavefront whatever the
+                                        batch size (by default four when the batch is a multiple of four and large: single steps
+                                        above 5632 envs, the multi-step entry points above 4096) */
+#define SDC_DEBUG_QUAD 1024          /* bit 10, MAPPING OVERRIDE: ... with four envs per wavefront whatever the size */
+#define SDC_DEBUG_WIDE 2048          /* bit 11, MAPPING OVERRIDE: the lane-per-env kernel for any batch that is a multiple of 64 envs
+                                        (by default from 7680 envs; sdc_rollout from 12288); sdc_create gives the batch the mirror
+                                        the kernel reads.  Not together with bit 9 / 10 / 12: those win */
+#define SDC_DEBUG_WIDE_OFF 4096      /* bit 12, MAPPING OVERRIDE: never the lane-per-env kernel */
+#define SDC_DEBUG_BOUND_REPAIR 8192  /* bit 13, TEST HOOK (general kernel): every 61st (env + launch) redoes its clip bounds' side
+                                        from the history as if a bound had left its window (a path ~4e-8 of the env-steps take by
+                                        themselves) */
+#define SDC_PLAN_DEBUG_TWO_STEPS 16384 /* bit 14, TEST HOOK: the handle's output block holds two steps, so that short horizons run
+                                        the chunked path of sdc_plan / sdc_plan_cem / sdc_plan_cem_groups / sdc_rollout_stats; read by
+                                        those calls alone, the step kernels never see the bit */
+
 /* replaces: EnvConfig / SustainDC.__init__ wiring (sustaindc_env.py:34-160) for N envs */
 typedef struct {
   int32_t n_envs;
@@ -112,25 +149,7 @@ typedef struct {
   double weather_noise_std;   /* 0.75 (utils/managers.py:504) ; 0 disables the noise */
   double weather_noise_weight;/* 0.02 (utils/managers.py:504) */
   int32_t max_roll_days;   /* 14: roll in [0, 14) days (utils/managers.py:601) */
-  int32_t debug_flags;     /* bit 0: VERIFY MODE -- after every step check the incremental reward state (the four rank
-                              windows, running sums) and the reported z-score against an exact bisection
-                              and a direct fp64 pass over each env's history (slow; a mismatch sets
-                              SDC_FAULT_ORDER_STAT).  Bits 1, 3, 4: diagnostics in info[reserved] / info[40..43]
-                              (why a rebuild happened; per-wavefront phase durations; absolute wavefront start /
-                              end stamps) -- measurement only, they overwrite the episode-return columns.
-                              Bit 6 (64): TEST HOOK -- sdc_create reads the environment variable SDC_TEST_STEP_NO and
-                              starts the launch counter there (tests of the counter's wrap); ignored otherwise.
-                              Bit 7 (128): always launch the GENERAL step / rollout kernels, never the ones specialised
-                              for the common case (same results to the bit: tests compare the two).
-                              Bits 9 / 10 (512 / 1024): the common-case kernels with two / four envs per wavefront
-                              whatever the batch size (by default four when the batch is a multiple of four and
-                              large: single steps above 5632 envs, the multi-step entry points above 4096; same
-                              results to the bit).
-                              Bit 13 (8192): TEST HOOK -- every 61st (env + launch) redoes its clip bounds' side from the
-                              history as if a bound had left its window (a path ~4e-8 of the env-steps take by themselves).
-                              Bit 14 (16384): TEST HOOK -- the handle's output block holds two steps, so that short horizons
-                              run the chunked path of sdc_plan / sdc_plan_cem / sdc_rollout_stats; read by those calls alone,
-                              the step kernels never see the bit */
+  int32_t debug_flags;     /* SDC_DEBUG_* below, or'ed; 0 in production */
   int32_t reward_method[3]; /* reward function per agent slot (ls, dc, bat), utils/reward_creator.py:322-334:
                                SDC_REWARD_DEFAULT the slot's own default_*_reward, SDC_REWARD_FOOTPRINT
                                default_dc_reward = default_bat_reward, SDC_REWARD_CUSTOM custom_agent_reward (0),
@@ -310,7 +329,7 @@ int sdc_steps_to_episode_end(const sdc_handle* h);
 int sdc_last_done(const sdc_handle* h, uint8_t* done_host);
 /* name of the kernel the last sdc_step / sdc_rollout launched ("" before the first): the host picks by batch size and configuration
  * between the general kernel, the common-case kernels with two / four envs per wavefront and the lane-per-env kernel of the
- * largest batches (sdc_capi.hip fast_case / quad_case / wide_case) -- all give the same results; tests and benchmarks name
+ * largest batches (csrc/sdc_dispatch.hpp: the whole decision, and the table of kernels) -- all give the same results; tests and benchmarks name
  * what they measured with this. */
 const char* sdc_last_step_kernel(const sdc_handle* h);
 

@@ -43,7 +43,7 @@ class ParityRig:
     """N envs on the engine + N scalar oracle envs fed the same inputs."""
 
     def __init__(self, n_envs, episode_steps=672, seed=0, locations=("ny",), dc_files=("dc_config.json",),
-                 capacity_mw=1.0, months=None, hist_cap=10000, with_oracle=True, oracle_envs=None, debug_flags=1,
+                 capacity_mw=1.0, months=None, hist_cap=10000, with_oracle=True, oracle_envs=None, debug_flags=L.DEBUG_VERIFY,
                  reward_method=(0, 0, 0)):
         self.N = n_envs
         self.steps = episode_steps

@@ -176,7 +176,7 @@ def refusal_engines(N, alongside=0):
     from tests.test_gpu_mark import _mk
     stepped = [_mk(N, ep=48) for _ in range(1 + alongside)]
     fresh = _mk(N, ep=48, reset=False)
-    verify = _mk(N, ep=48, debug_flags=1)
+    verify = _mk(N, ep=48, debug_flags=L.DEBUG_VERIFY)
     late = _mk(N, ep=48, auto_reset=False)
     g = torch.Generator(device="cpu").manual_seed(5)
     for _ in range(10):

@@ -45,10 +45,10 @@ class KernelGeometry:
     sweeps: str            # the spare (re-centring) workgroups FIRST in the grid: "coop", "wide" or "none"
 
     def env_blocks(self, N):
-        return -(-N // self.envs_per_wg)     # sdc_capi.hip step_blocks / quad_blocks / N / SDC_WAVE
+        return -(-N // self.envs_per_wg)     # csrc/sdc_dispatch.hpp sdc_env_blocks
 
     def sweep_blocks(self, N):
-        """sdc_capi.hip: d.sweep_blocks (sdc_create) for the pair / quad / general kernels, wide_sweep_blocks for the lane-per-env
+        """sdc_capi.hip: d.sweep_blocks (sdc_create) for the pair / quad / general kernels, launch_step's for the lane-per-env
         kernel (half the request capacity d.rq_max, at most 128), none in the multi-step kernels."""
         if self.sweeps == "coop":
             return min(128, max(32, N // 128))
@@ -338,7 +338,7 @@ class ProductionRig:
     def step(self, a_dev, want_info=True):
         """One single step under actions a_dev (int32 [N, 3] on the device), the sampled envs against the oracle, the auto-reset
         followed; -> the engine's (obs, share_obs, rew, done, info) views (want_info False: a step without the info rows, which
-        is never one of the specialised kernels: sdc_capi.hip lockstep_case)."""
+        is never one of the specialised kernels: csrc/sdc_dispatch.hpp sdc_specialised_ok)."""
         eng, idx = self.eng, self.sample_index()
         out = eng.step(a_dev, want_info=want_info)
         if self.restored is None and not self.kernel_checked:

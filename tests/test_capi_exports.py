@@ -26,7 +26,7 @@ def test_library_builds_and_exports_all_declared_symbols():
 
 def test_struct_layouts_match_header(tmp_path):
     """The ctypes mirrors of the header's structs against the C compiler's view of include/sustaindc_hip.h: sizes and
-    the offset of every member."""
+    the offset of every member; and the debug_flags names (SDC_DEBUG_*, SDC_PLAN_DEBUG_TWO_STEPS) against _lib's DEBUG_* mirror."""
     import subprocess
     members = {
         "sdc_config": ["n_envs", "device", "episode_steps", "hist_cap", "queue_max_len", "n_locations", "n_dc_configs",
@@ -43,6 +43,9 @@ def test_struct_layouts_match_header(tmp_path):
         src.append(f'  printf("{st} %zu\\n", sizeof({st}));')
         for m in ms:
             src.append(f'  printf("{st}.{m} %zu\\n", offsetof({st}, {m}));')
+    flag_names = re.findall(r"^#define (SDC_DEBUG_\w+|SDC_PLAN_DEBUG_TWO_STEPS)\b", open(os.path.join(ROOT, "include", "sustaindc_hip.h")).read(),
+                            flags=re.M)
+    src += [f'  printf("{n} %d\\n", {n});' for n in flag_names]
     src += ["  return 0;", "}"]
     c = tmp_path / "layout.c"
     c.write_text("\n".join(src))
@@ -55,6 +58,13 @@ def test_struct_layouts_match_header(tmp_path):
             assert int(out[f"{st}.{m}"]) == getattr(mirror[st], m).offset, (st, m)
     assert [f[0] for f in L.SdcConfig._fields_] == members["sdc_config"]     # every member of sdc_config is mirrored
     assert len(L.INFO_COLS) == L.INFO_DIM
+    # every flag name of the header is mirrored with the header's value, every mirrored name is the header's, each is one bit of its own
+    py_names = sorted(n for n in vars(L) if n.startswith("DEBUG_") or n == "PLAN_DEBUG_TWO_STEPS")
+    assert sorted(n[len("SDC_"):] for n in flag_names) == py_names and len(py_names) == 14
+    for n in flag_names:
+        v = int(out[n])
+        assert v == getattr(L, n[len("SDC_"):]) and v > 0 and v & (v - 1) == 0, n
+    assert len({int(out[n]) for n in flag_names}) == len(flag_names)
 
 
 def test_fails_loudly_without_gpu_or_bad_args():

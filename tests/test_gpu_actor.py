@@ -60,8 +60,8 @@ def _engine(N, steps, seed=5, debug_flags=0):
     return e
 
 
-# (40 envs: a partly filled workgroup; debug_flags 1024: four envs per wavefront -- the mapping of large batches -- whatever the size)
-@pytest.mark.parametrize("activation,N,flags", [("tanh", 512, 0), ("relu", 512, 0), ("tanh", 40, 0), ("tanh", 512, 1024),
+# (40 envs: a partly filled workgroup; debug_flags DEBUG_QUAD: four envs per wavefront -- the mapping of large batches -- whatever the size)
+@pytest.mark.parametrize("activation,N,flags", [("tanh", 512, 0), ("relu", 512, 0), ("tanh", 40, 0), ("tanh", 512, L.DEBUG_QUAD),
                                                 ("relu", 40, 1024)])
 def test_in_kernel_actor_matches_torch_and_external_rollout(activation, N, flags):
     import torch
@@ -109,7 +109,7 @@ def test_in_kernel_actor_matches_torch_and_external_rollout(activation, N, flags
     b_eng.close()
 
 
-@pytest.mark.parametrize("flags", [0, 1024])
+@pytest.mark.parametrize("flags", [0, L.DEBUG_QUAD])
 def test_layernorm_of_large_relu_activations(flags):
     """ReLU outputs of ~30 with a spread of ~0.5 (large biases, small weights): the hidden LayerNorms' one-pass variance must not
     lose the spread to cancellation (advisor finding of round 3: E[x^2] - mean^2 in fp32 is ~1e-4 off at this magnitude, ten times

@@ -1,6 +1,6 @@
 """env_reward's repair of "a clip bound left its window" (csrc/sdc_pairstep.hpp: the bounds' tail sums redone from the ring in one
 pass instead of a full rebuild; the window moved by the ahead-of-need refill) -- a path ~4e-8 of the env-steps take by themselves.
-debug_flags bit 13 makes every 61st (env + launch) take it; bit 0 (verify mode) has sdc_reward_verify_kernel check, after every
+debug_flags DEBUG_BOUND_REPAIR makes every 61st (env + launch) take it; DEBUG_VERIFY (verify mode) has sdc_reward_verify_kernel check, after every
 step, every key of all four rank windows against its rank in the ring, the quartiles against an exact bisection and the reported
 z-score against a direct fp64 pass over the env's history."""
 import numpy as np
@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 def test_forced_bound_repairs_verify_and_match_the_unforced_run(hist_cap):
     import torch
     N, ep, steps_total = 256, 288, 1500
-    rigs = [P.ParityRig(N, episode_steps=ep, seed=5, hist_cap=hist_cap, with_oracle=False, debug_flags=f) for f in (1 | 8192, 1)]
+    rigs = [P.ParityRig(N, episode_steps=ep, seed=5, hist_cap=hist_cap, with_oracle=False, debug_flags=f) for f in (L.DEBUG_VERIFY | L.DEBUG_BOUND_REPAIR, L.DEBUG_VERIFY)]
     rng = np.random.default_rng(5)
     n0 = hist_cap - 200          # the ring fills and wraps inside the test
     hist = np.full((N, rigs[0].eng.hist_stride), np.nan, np.float32)

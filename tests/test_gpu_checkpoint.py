@@ -299,10 +299,10 @@ REWINDS = [("wide", 8192, False), ("wide_gen", 16384, True)]
 @pytest.mark.parametrize("mapping,N,mixed", REWINDS, ids=[f"{r[0]}-{r[1]}" for r in REWINDS])
 def test_rewind_on_the_same_engine_across_the_boundary(mapping, N, mixed):
     """state_dict(), 72 single steps (the oracles check them; the episode boundary is among them), load_state_dict() on the SAME
-    engine and the same 72 steps again: every output of every env the same bits, verify mode on (debug_flags bit 0: every step's
+    engine and the same 72 steps again: every output of every env the same bits, verify mode on (debug_flags DEBUG_VERIFY: every step's
     reward state checked against an exact pass over the ring), requests in flight at the checkpoint."""
     import torch
-    rig = ProductionRig(N, mapping, debug_flags=1, mixed=mixed, episode_steps=EP, seed=6000 + N, n_random=24)
+    rig = ProductionRig(N, mapping, debug_flags=L.DEBUG_VERIFY, mixed=mixed, episode_steps=EP, seed=6000 + N, n_random=24)
     eng = rig.eng
     obs, _ = eng.reset()
     rig.begin_all(obs)
@@ -351,11 +351,11 @@ def test_one_step_rewind_takes_over_no_stale_window(mapping, N):
     stamped in the step before the checkpoint would look exactly "two steps old" to the replayed step, whose launch counter is
     one on from the checkpoint's: without sdc_set_state moving the counter on, the replay would take over the window swept for
     the first pass, which already holds the replayed step's own insertion, and replay that insertion a second time.  Verify mode
-    (debug_flags bit 0) checks every window against the ring after every step; the replay must equal the first pass to the bit.
+    (debug_flags DEBUG_VERIFY) checks every window against the ring after every step; the replay must equal the first pass to the bit.
     Four rounds, one per episode, late in the episode where requests are many; the first pass runs the kernel of the mapping
     (the episode boundary between the rounds brings the feature rows back), the replay the general kernel."""
     import torch
-    rig = ProductionRig(N, mapping, debug_flags=1, episode_steps=EP, seed=8000 + N, n_random=24)
+    rig = ProductionRig(N, mapping, debug_flags=L.DEBUG_VERIFY, episode_steps=EP, seed=8000 + N, n_random=24)
     eng = rig.eng
     obs, _ = eng.reset()
     rig.begin_all(obs)
@@ -458,7 +458,7 @@ def test_staggered_envs_and_partial_rings_restore_vs_oracle():
     sd = a.state_dict()
     hl = a.get_state("hist_len").astype(np.int64)
     assert 0 < hl.max() < 10000, hl.max()
-    b = SdcEngine(N, episode_steps=steps, auto_reset=False, seed=seed, debug_flags=1)
+    b = SdcEngine(N, episode_steps=steps, auto_reset=False, seed=seed, debug_flags=L.DEBUG_VERIFY)
     tb = rig.tables[0]
     b.set_tables(0, tb["W"], tb["C"], tb["T"], tb["WB"])
     b.set_dc_params(0, rig.params[0])

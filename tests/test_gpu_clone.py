@@ -202,10 +202,10 @@ def _oracle_copy(o):
 def test_divergent_branches_against_the_oracle_verify_mode():
     """Sampled envs cloned onto other sampled envs (their oracles copied likewise), then driven by DIFFERENT random actions than
     their sources: every sampled env against the fp64 oracle every step, through the auto-reset, where begin_all holds dst's draws
-    to the NumPy restatement keyed on dst's own index.  debug_flags 1: the verify kernel checks every env's reward state."""
+    to the NumPy restatement keyed on dst's own index.  debug_flags DEBUG_VERIFY: the verify kernel checks every env's reward state."""
     import torch
     N = 4096
-    rig = ProductionRig(N, "pair", debug_flags=1, episode_steps=EP, seed=4242, n_random=160)
+    rig = ProductionRig(N, "pair", debug_flags=L.DEBUG_VERIFY, episode_steps=EP, seed=4242, n_random=160)
     eng = rig.eng
     obs, _ = eng.reset()
     rig.begin_all(obs)

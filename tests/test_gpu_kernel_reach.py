@@ -1,15 +1,17 @@
-"""The step kernels at the edges of their reach (csrc/sdc_capi.hip sdc_step and the predicates above it: lockstep_case, fast_case,
-quad_case, wide_shape, wide_case, wide_gen_case):
+"""The step kernels at the edges of their reach (csrc/sdc_dispatch.hpp: sdc_single_step_path / sdc_rollout_path decide which kernel a
+call lands on; tests/test_step_dispatch.py holds those functions to the same tables without a GPU):
 
   * batch sizes either side of every threshold, each in the production configuration (tests/production_rig.py: debug_flags 0, full
     rings, one auto-reset, the kernel's own geometry sampled against the oracle) -- and WHICH kernel each lands on, from a table
-    (KERNEL_OF_BATCH) that must be edited on purpose when a threshold moves;
+    (tests/step_paths.py KERNEL_OF_BATCH) that must be edited on purpose when a threshold moves;
   * rack counts 1 / 17 / 31 / 32 / 33 and configs of exactly 8 / 9 / 12 / 13 rack classes, on every mapping each is eligible for
     (forced by debug_flags), every env the same bits as the general kernel, sampled envs against the oracle, and where each lands;
   * the two mirrors the lane-per-env kernel reads -- the ring's slot-major copy (SdcDev::hist_t, 49 152 envs and up) and the queue
     table's time-major copy (qcum_t, 7 680 envs and up) -- kept coherent by the OTHER kernels: a batch that switches between the
-    general kernel (`step(want_info=False)` fails lockstep_case) and the lane-per-env kernel, held bit for bit to a batch that never
-    leaves the four-envs-per-wavefront kernel."""
+    general kernel (`step(want_info=False)`: no specialised kernel runs without `info`) and the lane-per-env kernel, held bit for bit
+    to a batch that never leaves the four-envs-per-wavefront kernel;
+  * sdc_rollout on every kernel it can land on (forced by debug_flags, by `actions_out`, by the batch's size modulo 2 and 4), every
+    output the same bits as the general multi-step kernel's."""
 import json
 import os
 
@@ -19,29 +21,9 @@ import pytest
 from dc_rl_amd import _lib as L
 from dc_rl_amd import dc_config
 from tests.production_rig import ProductionRig
+from tests.step_paths import GENERAL, KERNEL_OF_BATCH, PAIR, QUAD, RACK_CASES, ROLLOUT_CASES, WIDE, WIDE_OFF, expected_mapping
 
 pytestmark = pytest.mark.gpu
-
-# sdc_capi.hip:232-300 -- odd N: general; N % 4 != 0: two envs per wavefront (pair); N % 4 == 0 from SDC_QUAD_MIN_ENVS_STEP = 5636:
-# four per wavefront (quad); N % 64 == 0 from SDC_WIDE_MIN_ENVS = 7680: lane per env (wide); the ring's mirror from
-# SDC_HIST_MIRROR_MIN_ENVS = 49152
-KERNEL_OF_BATCH = {
-    5632: "pair",        # the last size below the quad threshold
-    5634: "pair",        # N % 4 != 0
-    5636: "quad",        # the threshold itself; the last workgroup a quarter full (4 of 16 envs)
-    7616: "quad",        # 476 workgroups: nb % 8 != 0, no XCD remap
-    7680: "wide",        # the threshold itself
-    7681: "general",     # odd: the last wavefront carries one env
-    7682: "pair",
-    7684: "quad",
-    7744: "wide",        # 121 workgroups: nb % 8 != 0
-    49088: "wide",       # the largest batch without the ring's mirror
-    49216: "wide",       # with the mirror, 769 workgroups: nb % 8 != 0
-}
-
-# debug_flags that force a mapping (sdc_capi.hip): 128 general, 512 two per wavefront, 1024 four, 2048 lane per env, 4096 lane per env off
-GENERAL, PAIR, QUAD, WIDE, WIDE_OFF = 128, 512, 1024, 2048, 4096
-
 
 @pytest.mark.parametrize("N", sorted(KERNEL_OF_BATCH))
 def test_batch_size_thresholds_production_vs_oracle(N):
@@ -80,25 +62,6 @@ def rack_config(tmp_path, n_racks, n_classes=None):
 
 def rack_classes(p):
     return len({(p["rack_n"][r], p["rack_supply"][r], p["rack_full"][r], p["rack_idle"][r]) for r in range(len(p["rack_n"]))})
-
-
-def expected_mapping(flags, racks, classes, two_configs=False):
-    """Where a 256-env batch lands (sdc_capi.hip sdc_step): more than 32 racks -> the general kernel whatever the flags; the lane-per-
-    env kernel's common form for one config of <= 8 classes (SDC_MAX_RACK_CLS), its general form up to 12 (SDC_WIDE_MAX_CLS) or for
-    several configs, else two envs per wavefront; quad_case needs ONE config."""
-    if racks > 32 or flags == GENERAL:
-        return "general"
-    if flags == QUAD and not two_configs:
-        return "quad"
-    if flags == WIDE:
-        if classes <= 8 and not two_configs:
-            return "wide"
-        if classes <= 12:
-            return "wide_gen"
-    return "pair"
-
-
-RACK_CASES = [(1, None), (17, None), (31, None), (32, None), (33, None), (20, 8), (20, 9), (20, 12), (20, 13)]
 
 
 def _same(ref, other, t, what):
@@ -200,3 +163,51 @@ def test_mirrors_stay_coherent_across_kernel_switches(N):
     print(f"{N} envs: {switched} general-kernel steps among 300, auto-resets {a.resets}")
     for r in (a, b):
         r.eng.close()
+
+
+@pytest.mark.parametrize("N", sorted({c[0] for c in ROLLOUT_CASES}))
+def test_rollout_lands_on_each_multi_step_mapping_with_the_general_kernels_bits(N):
+    """sdc_rollout, K = 3, 24-step episodes, nine calls (the eighth ends the episode: an auto-reset inside its last step): under each
+    of tests/step_paths.py ROLLOUT_CASES the call lands on the kernel listed there, and obs, share_obs, rew, done, info (without
+    info[reserved]: which way the step's reward state was served, a diagnostic that differs between a multi-step launch and single-step
+    launches) and final_obs are the same bits as those of an engine held to the general multi-step kernel; `actions_out`, where given,
+    is the actions applied."""
+    import torch
+    from dc_rl_amd import traces
+    from dc_rl_amd.engine import SdcEngine
+    steps, K = 24, 3
+    cases = [c for c in ROLLOUT_CASES if c[0] == N]
+    tb = traces.synthetic_tables("ny", 0)
+    p = dc_config.size_datacenter("dc_config.json", 1, 30.0)
+    engs = []
+    for flags in [GENERAL] + [c[1] for c in cases]:
+        e = SdcEngine(N, episode_steps=steps, auto_reset=True, seed=31, debug_flags=flags)
+        e.set_tables(0, tb["W"], tb["C"], tb["T"], tb["WB"])
+        e.set_dc_params(0, p)
+        e.assign(0, 0, 200, 210)
+        e.reset()
+        engs.append(e)
+    ref = engs[0]
+    g = torch.Generator(device="cpu").manual_seed(N)
+    acts = torch.randint(0, 3, (9 * K, N, 3), dtype=torch.int32, generator=g).cuda()
+    rsv = L.INFO_IDX["reserved"]
+    names = ("obs", "share_obs", "rew", "done", "info")
+    ended = 0
+    for r in range(9):
+        seq = acts[r * K:(r + 1) * K].contiguous()
+        want = ref.rollout(seq)
+        assert ref.last_step_kernel() == "sdc_rollout_kernel"
+        want[4][:, :, rsv] = 0
+        ended += int(bool(want[3][-1].all()))
+        for e, (_, flags, want_actions, kernel) in zip(engs[1:], cases):
+            got = e.rollout(seq, want_actions=want_actions)
+            assert e.last_step_kernel() == kernel, (N, flags, want_actions, r, e.last_step_kernel())
+            got[4][:, :, rsv] = 0
+            for nm, u, v in zip(names + ("final_obs",), tuple(want[:5]) + (ref.final_obs,), tuple(got[:5]) + (e.final_obs,)):
+                assert torch.equal(u, v), (N, flags, want_actions, r, nm)
+            if want_actions:
+                assert torch.equal(got[5], seq), (N, flags, r, "actions_out")
+    assert ended == 1
+    for e in engs:
+        assert (e.info[:, L.INFO_IDX["fault"]] == 0).all()
+        e.close()

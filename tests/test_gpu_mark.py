@@ -341,7 +341,7 @@ def test_requests_in_flight_at_the_mark_and_at_the_rewind_verify_mode_against_th
     detour) to the episode's end and through the auto-reset; no SDC_FAULT_ORDER_STAT (no fault at all) in any step, detour included."""
     import torch
     N = 4096
-    rig = ProductionRig(N, "pair", debug_flags=1, episode_steps=96, seed=6161, n_random=160)
+    rig = ProductionRig(N, "pair", debug_flags=L.DEBUG_VERIFY, episode_steps=96, seed=6161, n_random=160)
     eng = rig.eng
     obs, _ = eng.reset()
     rig.begin_all(obs)
@@ -376,7 +376,7 @@ def test_requests_in_flight_at_the_mark_and_at_the_rewind_verify_mode_against_th
             rig.single_steps(1, seed=300 + 10 * rnd + t2)
             t2 += 1
     # windows re-centred by spare wavefronts were taken over during the detours.  (Code 4, "a request was filed", is only reported
-    # with debug_flags bit 3, a measurement mode that overwrites the episode-return columns the oracle comparison reads: that requests
+    # with debug_flags DEBUG_PHASES, a measurement mode that overwrites the episode-return columns the oracle comparison reads: that requests
     # are in flight at the mark and at the rewind is asserted from the headers' stamps above instead.)
     assert 2 in codes, codes
     resets = rig.resets
@@ -391,10 +391,10 @@ def test_requests_in_flight_at_the_mark_and_at_the_rewind_verify_mode_against_th
 def test_mirrors_after_a_rewind_and_a_switch_to_the_general_kernel_and_back():
     """8 192 envs (the queue table's time-major mirror): after a rewind, three steps of the general kernel (`want_info=False`: it appends
     to the table, the ring and the mirrors), then the lane-per-env kernel again, which reads the mirrors; a third engine runs the
-    general kernel throughout (debug_flags 128) and never looks aside: outputs equal on every step."""
+    general kernel throughout (debug_flags DEBUG_GENERAL) and never looks aside: outputs equal on every step."""
     import torch
     N = 8192
-    a, b, c = _mk(N), _mk(N), _mk(N, debug_flags=128)
+    a, b, c = _mk(N), _mk(N), _mk(N, debug_flags=L.DEBUG_GENERAL)
     g = torch.Generator(device="cpu").manual_seed(8)
     for t in range(CAP + 5):
         x = _acts(N, g)

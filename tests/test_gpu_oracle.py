@@ -60,7 +60,7 @@ def test_full_history_ring_vs_oracle():
 
 
 def test_order_statistic_tracker_stress():
-    """The O(1) order-statistic trackers of the reward normalisation against the exact bisection (debug_flags bit 0) on
+    """The O(1) order-statistic trackers of the reward normalisation against the exact bisection (debug_flags DEBUG_VERIFY) on
     histories built to stress them: heavy duplicates, monotone drifts, constant runs, values straddling zero (sign
     change of the fp32 offsets), a small history capacity so evictions start early."""
     import torch
@@ -289,7 +289,7 @@ def test_grid_shapes_with_sweep_workgroups_inside_the_grid_vs_oracle():
 
 def test_checkpoint_rollback_on_the_same_engine_4096():
     """state_dict(), one step, load_state_dict() on the SAME engine, the same step again: bit-identical outputs, verify
-    mode on (debug_flags bit 0), 4096 envs with full rings so that deferred window re-centrings are in flight at every
+    mode on (debug_flags DEBUG_VERIFY), 4096 envs with full rings so that deferred window re-centrings are in flight at every
     checkpoint.  (Replaying TWO steps leaves every restored request stamp at least three steps old, stale with or without
     sdc_set_state's move of the launch counter; the one-step rewind, where that move is what keeps a restored header from taking
     over a window swept for the state it replaced, is tests/test_gpu_checkpoint.py::test_one_step_rewind_takes_over_no_stale_window.)"""
@@ -297,7 +297,7 @@ def test_checkpoint_rollback_on_the_same_engine_4096():
     N, steps, cap = 4096, 672, 10000
     tb = traces.synthetic_tables("ny", 0)
     p = dc_config.size_datacenter("dc_config.json", 1, 30.0)
-    eng = SdcEngine(N, episode_steps=steps, auto_reset=True, seed=5, debug_flags=1)
+    eng = SdcEngine(N, episode_steps=steps, auto_reset=True, seed=5, debug_flags=L.DEBUG_VERIFY)
     eng.set_tables(0, tb["W"], tb["C"], tb["T"], tb["WB"])
     eng.set_dc_params(0, p)
     eng.assign(0, 0, 174, 188)

@@ -3,10 +3,10 @@ call's stated arithmetic restated in torch fp64 from a twin engine's rollouts.
 
  1. plan with the default objective equals lookahead (returns, score, every state field, the engine's output tensors) at 130 and
     4 096 envs;  2. a discounted, weighted objective with info columns, bit for bit;  3. the selection rule;  4. the chunked output
-    block (debug_flags bit 14) against the unchunked one;  5. the large-batch rollout path (12 288 envs);  6. the refusals, each of
+    block (debug_flags PLAN_DEBUG_TWO_STEPS) against the unchunked one;  5. the large-batch rollout path (12 288 envs);  6. the refusals, each of
     which leaves the engine untouched;  7. the vector env with an agent subset;  8. the shooting MPC agent.
 
-NOT in verify mode (debug_flags bit 0), although the project's parity tests usually are: sdc_rollout refuses verify mode ("verify mode
+NOT in verify mode (debug_flags DEBUG_VERIFY), although the project's parity tests usually are: sdc_rollout refuses verify mode ("verify mode
 checks single steps"), so neither `lookahead` nor `rollout` -- the references here -- nor sdc_plan, which takes sdc_rollout's path, run
 in it; test 6 checks that refusal.  The rings hold 128 keys and the episodes 96 steps, as in tests/test_gpu_mark.py."""
 import ctypes as C
@@ -179,7 +179,7 @@ def test_chunked_output_block_gives_the_unchunked_results():
 
 def test_large_batch_rollout_path_equals_lookahead():
     import torch
-    N, M, K = 12288, 2, 3      # sdc_capi.hip SDC_WIDE_ROLLOUT_MIN_ENVS: a rollout is K launches of the lane-per-env kernel
+    N, M, K = 12288, 2, 3      # csrc/sdc_dispatch.hpp SDC_WIDE_ROLLOUT_MIN_ENVS: a rollout is K launches of the lane-per-env kernel
     (a, b), g = _twins(N, history=4)
     assert a.last_step_kernel() == "sdc_dynamics_wide_kernel"
     cand = _cands(M, K, N, g)

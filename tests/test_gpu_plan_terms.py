@@ -4,7 +4,7 @@ held to the stated arithmetic (include/sustaindc_hip.h) restated in torch fp64 f
  1. sdc_plan's scores bit for bit against the restatement at 164 envs (two full workgroups and one whose second half-tile holds 4
     rows), with 2 limits + 1 terminal column and with all 8 + 8 slots, the bounds the medians of the twin's own rollouts;  2. no terms,
     terms set and cleared, and both counts 0 all give the bits of a plan that never saw terms;  3. the chunked output block (debug_flags
-    bit 14, chunks of 2 + 2 + 1 steps: the terminal step alone in the last) against the unchunked one;  4. the selection follows the
+    PLAN_DEBUG_TWO_STEPS, chunks of 2 + 2 + 1 steps: the terminal step alone in the last) against the unchunked one;  4. the selection follows the
     terms;  5. plan_cem and plan_cem_groups score with them;  6. the refusals, each of which leaves the terms and the engine as they
     were;  7. the vector env, and copy.deepcopy of it and of SustainDC.
 

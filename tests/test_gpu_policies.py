@@ -18,7 +18,7 @@ def _run(d, mode):
     steps, n_ep, N = int(d["meta_steps"]), int(d["meta_episodes"]), 2
     eng = G.make_engine_for_fixture(d, n_envs=N, policy=tuple(int(x) for x in d["meta_device_policy"]),
                                     trim_and_respond_limit=float(d["meta_tr_limit"]),
-                                    debug_flags=1 if mode == "steps" else 0)
+                                    debug_flags=L.DEBUG_VERIFY if mode == "steps" else 0)
     eng.set_state("stpt", np.full(N, float(d["init_stpt"])))
     worst = dict(obs=0.0, rew=0.0, info=0.0)
     for ep in range(n_ep):

@@ -50,7 +50,7 @@ def test_lane_per_env_kernel_equals_four_per_wavefront_for_every_env(N):
     of every env the same bits (the diagnostics column aside: it says which path served the reward state), and at the end the rings."""
     import torch
     a = ProductionRig(N, "wide", debug_flags=0, episode_steps=120, seed=515, n_random=0, oracles=False)
-    b = ProductionRig(N, "quad", debug_flags=4096, episode_steps=120, seed=515, n_random=0, oracles=False)
+    b = ProductionRig(N, "quad", debug_flags=L.DEBUG_WIDE_OFF, episode_steps=120, seed=515, n_random=0, oracles=False)
     a.eng.reset()
     b.eng.reset()
     g = torch.Generator(device="cpu").manual_seed(515)
@@ -75,9 +75,9 @@ def test_lane_per_env_kernel_equals_four_per_wavefront_for_every_env(N):
 
 
 def test_quad_step_kernel_32768_envs_vs_oracle():
-    """... and the four-envs-per-wavefront kernel at 32 768 envs (debug_flags bit 12 keeps the lane-per-env kernel off): the mapping
+    """... and the four-envs-per-wavefront kernel at 32 768 envs (debug_flags DEBUG_WIDE_OFF keeps the lane-per-env kernel off): the mapping
     the closed loop (and `sdc_rollout` with `actions_out` / unaligned outputs) still runs at that size."""
-    rig = ProductionRig(32768, "quad", debug_flags=4096, episode_steps=120, seed=33768)
+    rig = ProductionRig(32768, "quad", debug_flags=L.DEBUG_WIDE_OFF, episode_steps=120, seed=33768)
     obs, _ = rig.eng.reset()
     rig.begin_all(obs)
     rig.single_steps(150)
@@ -186,11 +186,11 @@ def test_config3_mixed_racks_4096_production():
     rig.eng.close()
 
 
-@pytest.mark.parametrize("flags,kernel", [(0, "sdc_dynamics_wide_kernel"), (4096, "sdc_rollout_quad_kernel")])
+@pytest.mark.parametrize("flags,kernel", [(0, "sdc_dynamics_wide_kernel"), (L.DEBUG_WIDE_OFF, "sdc_rollout_quad_kernel")])
 def test_rollout_16384_envs_full_rings_vs_oracle(flags, kernel):
     """`sdc_rollout` at 16 384 envs, rings full: 10 single steps (their deferred requests are still in flight when the multi-step
     call starts), then 48 + 48 + the episode's last 14 steps in three calls, across an auto-reset, vs the oracle.  debug_flags 0:
-    what the call does at this size since round 5 -- K single-step launches of the lane-per-env kernel; bit 12 (4096) keeps that
+    what the call does at this size since round 5 -- K single-step launches of the lane-per-env kernel; DEBUG_WIDE_OFF keeps that
     kernel off: ONE launch of `sdc_rollout_quad_kernel` per call (still what serves unaligned outputs / `actions_out`)."""
     import torch
     N = 16384

@@ -169,7 +169,7 @@ def test_subset_restore_and_replication_against_the_oracle_verify_mode():
     env against the fp64 oracle every step through the boundary, whose draws begin_all holds to each dst's OWN global index; verify
     mode checks every env's reward state."""
     N = 4096
-    rig = ProductionRig(N, "pair", debug_flags=1, episode_steps=EP, seed=5150, n_random=260)
+    rig = ProductionRig(N, "pair", debug_flags=L.DEBUG_VERIFY, episode_steps=EP, seed=5150, n_random=260)
     eng = rig.eng
     obs, _ = eng.reset()
     rig.begin_all(obs)

@@ -2,7 +2,7 @@
 sdc_ringpath.hpp) in verify mode: thousands of steps over many envs, episode boundaries with device-side auto-reset,
 a wrapping history ring, policy switches that change the shape of the energy distribution.  After every step the
 verify kernel recomputes each env's order statistics by exact bisection and its clipped moments by a direct fp64 pass
-over the ring and compares them with the incremental state and with the reported z-score (debug_flags bit 0)."""
+over the ring and compares them with the incremental state and with the reported z-score (debug_flags DEBUG_VERIFY)."""
 import numpy as np
 import pytest
 
@@ -11,13 +11,15 @@ from tests import parity_util as P
 
 pytestmark = pytest.mark.gpu
 
+VERIFY, QUAD = L.DEBUG_VERIFY, L.DEBUG_QUAD
 
-# (flags 1: verify mode; + 1024: the common-case kernel with four envs per wavefront -- the mapping of large batches -- whatever
+
+# (VERIFY: verify mode; + QUAD: the common-case kernel with four envs per wavefront -- the mapping of large batches -- whatever
 # the batch size)
 # (mixed: BASELINE configs[3] -- 16 / 20 / 25 racks x three locations -- on the common-case kernels, every env with its own copy
 # of its config's scalars: round 4)
-@pytest.mark.parametrize("hist_cap,steps_total,flags,mixed", [(10000, 2600, 1, False), (1500, 5200, 1, False),
-                                                              (1500, 5200, 1 | 1024, False), (1500, 2600, 1, True)])
+@pytest.mark.parametrize("hist_cap,steps_total,flags,mixed", [(10000, 2600, VERIFY, False), (1500, 5200, VERIFY, False),
+                                                              (1500, 5200, VERIFY | QUAD, False), (1500, 2600, VERIFY, True)])
 def test_reward_state_soak(hist_cap, steps_total, flags, mixed):
     import torch
     N, ep = 512, 288
@@ -75,7 +77,7 @@ def test_reward_state_soak(hist_cap, steps_total, flags, mixed):
     eng.close()
 
 
-@pytest.mark.parametrize("hist_cap,flags", [(33, 1), (64, 1), (65, 1), (100, 1), (200, 1), (64, 1 | 1024), (100, 1 | 1024)])
+@pytest.mark.parametrize("hist_cap,flags", [(33, VERIFY), (64, VERIFY), (65, VERIFY), (100, VERIFY), (200, VERIFY), (64, VERIFY | QUAD), (100, VERIFY | QUAD)])
 def test_rank_windows_small_histories(hist_cap, flags):
     """Histories about as long as a 64-key window, from empty: the windows list the whole history while it is shorter
     than a window, stay anchored at its ends when it is not much longer, and every eviction hits a window.  Random and
@@ -113,9 +115,9 @@ def test_deferred_recentring_across_the_step_counter_wrap(monkeypatch):
     """The host's step counter (stamps of the re-centring requests) wraps at 3 * 2^22; start just below it and run across
     the wrap in verify mode: requests keep being served and taken over on both sides, nothing mismatches."""
     import torch
-    monkeypatch.setenv("SDC_TEST_STEP_NO", str((3 << 22) - 160))     # (read only with debug_flags bit 6; each set_state below moves the counter on by 3)
+    monkeypatch.setenv("SDC_TEST_STEP_NO", str((3 << 22) - 160))     # (read only with debug_flags DEBUG_STEP_NO_ENV; each set_state below moves the counter on by 3)
     N, ep, cap = 512, 96, 1500
-    rig = P.ParityRig(N, episode_steps=ep, seed=91, hist_cap=cap, with_oracle=False, debug_flags=1 | 64)
+    rig = P.ParityRig(N, episode_steps=ep, seed=91, hist_cap=cap, with_oracle=False, debug_flags=VERIFY | L.DEBUG_STEP_NO_ENV)
     eng = rig.eng
     rng = np.random.default_rng(91)
     hist = np.full((N, eng.hist_stride), np.nan, np.float32)

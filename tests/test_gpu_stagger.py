@@ -70,7 +70,7 @@ def test_auto_reset_of_a_subset_vs_oracle():
     N, steps = 40, 64
     tb = traces.synthetic_tables("ny", 0)
     p = dc_config.size_datacenter("dc_config.json", 1, 30.0)
-    eng = SdcEngine(N, episode_steps=steps, auto_reset=True, seed=19, debug_flags=1)
+    eng = SdcEngine(N, episode_steps=steps, auto_reset=True, seed=19, debug_flags=L.DEBUG_VERIFY)
     eng.set_tables(0, tb["W"], tb["C"], tb["T"], tb["WB"])
     eng.set_dc_params(0, p)
     init_day = traces.get_init_day(4)

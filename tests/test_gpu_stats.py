@@ -4,7 +4,7 @@ through an int64 view.
 
  1. the arithmetic at 3 envs (one partial wavefront of the reduce kernel) and 130 (32 full wavefronts and a partial one): all four fields
     of the info columns, returns, steps, fault; the engine's state and single-step views against the twin's;  2. the chunked output block
-    (debug_flags bit 14: chunks of 2, 2, 2, 1 steps);  3. continuation with `into=`;  4. the episode's end with auto-reset;  5. built-in
+    (debug_flags PLAN_DEBUG_TWO_STEPS: chunks of 2, 2, 2, 1 steps);  3. continuation with `into=`;  4. the episode's end with auto-reset;  5. built-in
     policies on all three slots;  6. fault bits;  7. the large-batch rollout path (12 288 envs);  8. the refusals, each of which leaves
     the engine untouched;  9. `evaluate` through the vector env against a per-step step() loop.
 
@@ -210,7 +210,7 @@ def test_fault_bits_are_the_or_over_the_steps():
 
 
 def test_large_batch_rollout_path_every_env():
-    N, K = 12288, 3      # sdc_capi.hip SDC_WIDE_ROLLOUT_MIN_ENVS: a rollout is K launches of the lane-per-env kernel
+    N, K = 12288, 3      # csrc/sdc_dispatch.hpp SDC_WIDE_ROLLOUT_MIN_ENVS: a rollout is K launches of the lane-per-env kernel
     (a, b), g = _twins(N, history=4)
     assert a.last_step_kernel() == "sdc_dynamics_wide_kernel"
     acts = _seq(K, N, g)

@@ -42,13 +42,13 @@ def test_262144_envs_production_vs_oracle():
 
 
 def test_131072_envs_lane_per_env_equals_four_per_wavefront_for_every_env():
-    """Two engines of 131 072 envs, the same seed, debug_flags 0 (lane per env, the ring's mirror) against 4096 (four envs per
+    """Two engines of 131 072 envs, the same seed, debug_flags 0 (lane per env, the ring's mirror) against DEBUG_WIDE_OFF (four envs per
     wavefront): 150 steps over an auto-reset, every output of every env the same bits (the diagnostics column aside: it says which
     path served the reward state), final observations included, and at the end the rings."""
     import torch
     N = 131072
     a = ProductionRig(N, "wide", debug_flags=0, episode_steps=120, seed=1310, n_random=0, oracles=False)
-    b = ProductionRig(N, "quad", debug_flags=4096, episode_steps=120, seed=1310, n_random=0, oracles=False)
+    b = ProductionRig(N, "quad", debug_flags=L.DEBUG_WIDE_OFF, episode_steps=120, seed=1310, n_random=0, oracles=False)
     a.eng.reset()
     b.eng.reset()
     g = torch.Generator(device="cpu").manual_seed(1310)

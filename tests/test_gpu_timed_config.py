@@ -1,6 +1,6 @@
 """Parity in the configuration bench.py times, and the reference's real-trace fixtures as ONE heterogeneous batch.
 
-Every other oracle / golden parity test builds its engine in verify mode (debug_flags bit 0: a checking kernel after
+Every other oracle / golden parity test builds its engine in verify mode (debug_flags DEBUG_VERIFY: a checking kernel after
 each step).  These two run the PRODUCTION configuration -- debug_flags = 0, and for the first one everything else the
 timed region has too: 4096 envs (BASELINE.json configs[2]), auto-reset with the device's own Philox resets, every history
 ring at its 10 000-entry steady state, i.i.d. uniform actions, deferred window re-centring by the spare wavefronts under
@@ -113,8 +113,8 @@ def test_golden_fixtures_as_one_heterogeneous_batch():
 
 def test_common_case_kernels_equal_the_general_kernels():
     """The step / rollout kernels specialised for the common case (lock-step batch with feature rows, one config, external
-    actions, default rewards, no diagnostics: what bench.py times) -- four envs per wavefront (debug_flags bit 10: the default
-    for large batches) and two (bit 9) -- against the general kernels (debug_flags bit 7 forces them): every
+    actions, default rewards, no diagnostics: what bench.py times) -- four envs per wavefront (debug_flags DEBUG_QUAD: the default
+    for large batches) and two (DEBUG_PAIR) -- against the general kernels (DEBUG_GENERAL forces them): every
     output and the whole state bit for bit, over auto-resets, single steps and rollouts."""
     import torch
     N, steps, cap = 1024, 96, 10000
@@ -125,7 +125,7 @@ def test_common_case_kernels_equal_the_general_kernels():
     hist[:, :cap] = (331 + 70 * rng.standard_normal((N, cap))).clip(150, 650).astype(np.float32)
     pos = rng.integers(0, cap, N).astype(np.int32)
     engs = []
-    for flags in (1024, 512, 128):       # four envs per wavefront, two, the general kernels
+    for flags in (L.DEBUG_QUAD, L.DEBUG_PAIR, L.DEBUG_GENERAL):       # four envs per wavefront, two, the general kernels
         e = SdcEngine(N, episode_steps=steps, auto_reset=True, seed=12, debug_flags=flags)
         e.set_tables(0, tb["W"], tb["C"], tb["T"], tb["WB"])
         e.set_dc_params(0, p)
@@ -165,15 +165,15 @@ def test_common_case_kernels_equal_the_general_kernels():
 
 @pytest.mark.parametrize("N", [7168, 7176])      # (7176: a partly filled last workgroup, a grid that is not a multiple of 8; from 7 680 envs: one lane per env)
 def test_large_batches_take_the_four_env_mapping(N):
-    """Large batches (single steps above 5632 envs and below 7680, the multi-step kernels above 4096) run four envs per wavefront by default (sdc_capi.hip quad_case): same outputs
-    and state, bit for bit, as the two-env mapping (debug_flags bit 9) at those sizes -- steps, a rollout, the closed loop."""
+    """Large batches (single steps above 5632 envs and below 7680, the multi-step kernels above 4096) run four envs per wavefront by default (csrc/sdc_dispatch.hpp sdc_quad_ok): same outputs
+    and state, bit for bit, as the two-env mapping (debug_flags DEBUG_PAIR) at those sizes -- steps, a rollout, the closed loop."""
     import torch
     from tests.test_gpu_actor import _torch_actor
     steps = 96
     tb = traces.synthetic_tables("ny", 0)
     p = dc_config.size_datacenter("dc_config.json", 1, 30.0)
     engs = []
-    for flags in (0, 512):
+    for flags in (0, L.DEBUG_PAIR):
         e = SdcEngine(N, episode_steps=steps, auto_reset=True, seed=21, debug_flags=flags)
         e.set_tables(0, tb["W"], tb["C"], tb["T"], tb["WB"])
         e.set_dc_params(0, p)
@@ -209,7 +209,7 @@ def test_four_env_mapping_other_rack_counts(cfg):
     tb = traces.synthetic_tables("ny", 0)
     p = dc_config.size_datacenter(cfg, 1, 30.0)
     engs = []
-    for flags in (1024, 512):
+    for flags in (L.DEBUG_QUAD, L.DEBUG_PAIR):
         e = SdcEngine(N, episode_steps=steps, auto_reset=True, seed=3, debug_flags=flags)
         e.set_tables(0, tb["W"], tb["C"], tb["T"], tb["WB"])
         e.set_dc_params(0, p)
@@ -242,7 +242,7 @@ def test_four_env_mapping_other_rack_counts(cfg):
 def test_common_case_kernels_serve_several_configs():
     """BASELINE configs[3] (16 / 20 / 25 racks by env_id % 3, three locations) on the kernels specialised for the common case
     (round 4: every env carries its own copy of its config's scalars, SdcDev::prm_env, so that they arrive with the record)
-    against the general kernels (debug_flags bit 7): every output and the whole state bit for bit over single steps, two
+    against the general kernels (debug_flags DEBUG_GENERAL): every output and the whole state bit for bit over single steps, two
     auto-resets and a rollout, rings full -- and after the host re-assigns the configs."""
     import torch
     from tests.production_rig import MIXED_FILES, MIXED_LOCATIONS
@@ -259,7 +259,7 @@ def test_common_case_kernels_serve_several_configs():
     hist[:, :cap] = (331 + 70 * rng.standard_normal((N, cap))).clip(150, 650).astype(np.float32)
     pos = rng.integers(0, cap, N).astype(np.int32)
     engs = []
-    for flags in (0, 128):
+    for flags in (0, L.DEBUG_GENERAL):
         e = SdcEngine(N, episode_steps=steps, auto_reset=True, seed=14, debug_flags=flags, n_locations=3, n_dc_configs=9)
         for li, tb in enumerate(tabs):
             e.set_tables(li, tb["W"], tb["C"], tb["T"], tb["WB"])

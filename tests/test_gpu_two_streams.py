@@ -1,5 +1,5 @@
 """Stress test of SdcEngine.use_stream: two engines pinned to their own streams, 10 000 launches in all,
-verify mode on (debug_flags bit 0: every step's reward state checked against the ring by a second kernel on the same
+verify mode on (debug_flags DEBUG_VERIFY: every step's reward state checked against the ring by a second kernel on the same
 stream), MASKED resets with device draws on one engine while the other keeps stepping, auto-resets on both, deferred
 window re-centrings in flight throughout (small history capacity).  No synchronisation between the groups except at the
 comparison points.  The run must (a) raise no fault / sticky verify flag and (b) equal, bit for bit, the same schedule
@@ -26,7 +26,7 @@ def _run(pinned, n_steps):
     p = dc_config.size_datacenter("dc_config.json", 1, 30.0)
     engs, streams = [], []
     for g in range(2):
-        e = SdcEngine(N, episode_steps=steps, auto_reset=True, seed=900 + g, hist_cap=cap, debug_flags=1)
+        e = SdcEngine(N, episode_steps=steps, auto_reset=True, seed=900 + g, hist_cap=cap, debug_flags=L.DEBUG_VERIFY)
         e.set_tables(0, tb["W"], tb["C"], tb["T"], tb["WB"])
         e.set_dc_params(0, p)
         e.assign(0, 0, 174, 188)

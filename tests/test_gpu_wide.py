@@ -1,5 +1,5 @@
-"""The lane-per-env step kernel (csrc/sdc_wide.hip, the largest batches; forced here by debug_flags bit 11) against the two-envs-per-
-wavefront kernel (bit 9): same arithmetic in the same order, so every output and the state are the same BITS."""
+"""The lane-per-env step kernel (csrc/sdc_wide.hip, the largest batches; forced here by debug_flags DEBUG_WIDE) against the two-envs-per-
+wavefront kernel (DEBUG_PAIR): same arithmetic in the same order, so every output and the state are the same BITS."""
 import numpy as np
 import pytest
 
@@ -9,7 +9,7 @@ from dc_rl_amd.engine import SdcEngine
 
 pytestmark = pytest.mark.gpu
 
-WIDE, PAIR = 2048, 512
+WIDE, PAIR, WIDE_OFF = L.DEBUG_WIDE, L.DEBUG_PAIR, L.DEBUG_WIDE_OFF
 
 
 def _engines(N, steps, cfg="dc_config.json", seed=3, days=(200, 210), flags=(WIDE, PAIR)):
@@ -125,10 +125,10 @@ def test_lane_per_env_kernel_full_rings_whole_state():
 
 def test_the_host_picks_the_kernel_by_batch_size():
     """Single steps of a lock-step, single-config batch: two envs per wavefront up to 5 632 envs, four above, one lane per env from
-    7 680 (sdc_capi.hip fast_case / quad_case / wide_case); debug_flags bit 12 keeps the lane-per-env kernel off."""
+    7 680 (csrc/sdc_dispatch.hpp sdc_single_step_path); debug_flags DEBUG_WIDE_OFF keeps the lane-per-env kernel off."""
     import torch
     for N, flags, want in ((4096, 0, "sdc_dynamics_fast_kernel"), (7616, 0, "sdc_dynamics_quad_kernel"),
-                           (7680, 0, "sdc_dynamics_wide_kernel"), (7680, 4096, "sdc_dynamics_quad_kernel"),
+                           (7680, 0, "sdc_dynamics_wide_kernel"), (7680, WIDE_OFF, "sdc_dynamics_quad_kernel"),
                            (9220, 0, "sdc_dynamics_quad_kernel")):
         (e,) = _engines(N, 96, flags=(flags,))
         e.step(torch.ones((N, 3), dtype=torch.int32, device="cuda"))
@@ -137,12 +137,12 @@ def test_the_host_picks_the_kernel_by_batch_size():
 
 
 def test_rollout_of_a_large_batch_is_single_step_launches_of_the_lane_per_env_kernel():
-    """`sdc_rollout` over a batch the lane-per-env kernel serves (12 288 envs and up: sdc_capi.hip SDC_WIDE_ROLLOUT_MIN_ENVS): K launches of it inside the call, the same bits
-    as K calls of step() on a twin engine and as the multi-step kernel of four envs per wavefront (debug_flags bit 12), across an
+    """`sdc_rollout` over a batch the lane-per-env kernel serves (12 288 envs and up: csrc/sdc_dispatch.hpp SDC_WIDE_ROLLOUT_MIN_ENVS): K launches of it inside the call, the same bits
+    as K calls of step() on a twin engine and as the multi-step kernel of four envs per wavefront (debug_flags DEBUG_WIDE_OFF), across an
     episode end (auto-reset inside the last step)."""
     import torch
     N, steps, K = 12288, 48, 24
-    a, b, c = _engines(N, steps, flags=(0, 0, 4096))
+    a, b, c = _engines(N, steps, flags=(0, 0, WIDE_OFF))
     g = torch.Generator(device="cpu").manual_seed(21)
     acts = torch.randint(0, 3, (2 * K, N, 3), dtype=torch.int32, generator=g).cuda()
     rsv = L.INFO_IDX["reserved"]
@@ -214,12 +214,12 @@ def test_the_queue_tables_time_major_mirror_is_kept_by_every_kernel():
 
 def test_lane_per_env_kernel_in_verify_mode_from_empty_rings():
     """7 680 envs (the smallest batch the host gives to the lane-per-env kernel by itself) from EMPTY rings for 1 300 steps with
-    debug_flags bit 0: after every step sdc_reward_verify_kernel checks every key of all four rank windows against its rank in the
+    debug_flags DEBUG_VERIFY: after every step sdc_reward_verify_kernel checks every key of all four rank windows against its rank in the
     ring, the quartiles against an exact bisection and z against a direct fp64 pass.  Covers the young histories (fallback path for
     all 64 envs of a wavefront), the first rebuilds, the flood of re-centring requests around steps 64-100 and an auto-reset."""
     import torch
     N = 7680
-    (e,) = _engines(N, 672, flags=(1,))
+    (e,) = _engines(N, 672, flags=(L.DEBUG_VERIFY,))
     g = torch.Generator(device="cpu").manual_seed(12)
     pool = torch.randint(0, 3, (64, N, 3), dtype=torch.int32, generator=g).cuda()
     for t in range(1300):

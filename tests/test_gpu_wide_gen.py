@@ -1,7 +1,7 @@
 """The lane-per-env kernel's GENERAL form (csrc/sdc_wide.hip, template GEN -> `sdc_dynamics_wide_gen_kernel`; forced here by
-debug_flags bit 11): every lane its own data-centre config (BASELINE configs[3]: 16 / 20 / 25 racks x three locations in ONE batch),
+debug_flags DEBUG_WIDE): every lane its own data-centre config (BASELINE configs[3]: 16 / 20 / 25 racks x three locations in ONE batch),
 the rule-based policies of utils/rbc_agents.py:3-47, utils/trim_and_respond.py:8-38 and utils/base_agents.py inside the step, the
-dc / battery agents under any of utils/reward_creator.py:154-334 -- against the two-envs-per-wavefront kernels (bit 9), which run the
+dc / battery agents under any of utils/reward_creator.py:154-334 -- against the two-envs-per-wavefront kernels (DEBUG_PAIR), which run the
 same arithmetic in the same order: every output and the state are the same BITS.  (The pair kernels against the oracle and the
 reference's fixtures: tests/test_gpu_golden.py, test_gpu_policies.py, test_gpu_tou.py; this form against the oracle at production
 sizes: tests/test_gpu_production_sizes.py.)"""
@@ -14,7 +14,7 @@ from dc_rl_amd.engine import SdcEngine
 
 pytestmark = pytest.mark.gpu
 
-WIDE, PAIR = 2048, 512
+WIDE, PAIR = L.DEBUG_WIDE, L.DEBUG_PAIR
 FILES = ("dc_config.json", "dc_config_r16.json", "dc_config_r25.json")
 LOCS = ("ny", "az", "wa")
 GEN_KERNEL = "sdc_dynamics_wide_gen_kernel"

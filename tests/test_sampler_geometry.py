@@ -3,7 +3,7 @@ it checks is only worth something if it follows the grid of the kernel under tes
 launches in csrc/sdc_capi.hip sdc_step).  No GPU needed.
 
 Worked by hand:
-  * lane per env (64 envs per workgroup of two wavefronts, four workgroups per CU = 1024 per round; sdc_capi.hip wide_sweep_blocks:
+  * lane per env (64 envs per workgroup of two wavefronts, four workgroups per CU = 1024 per round; sdc_capi.hip launch_step:
     128 sweep workgroups from 4096 envs up): 7 680 envs = 120 workgroups (a multiple of 8: XCD remap b -> (b % 8) * 15 + b // 8,
     the last workgroup stays last), 248 in the grid, one round; 7 744 envs = 121 workgroups (identity); 65 536 envs = 1024
     workgroups + 128 sweeps: dispatch slot 1024 is env workgroup 896, remapped to block 112; 262 144 envs = 4096 workgroups, 4 x 1024

@@ -29,7 +29,7 @@ def _define(name, fname):
 
 def clone_bytes(eng, n_pairs):
     """bytes read + written by one clone of n_pairs pairs (sdc_clone.hpp ranges A, B, C), from the engine's own strides and the
-    library's own thresholds (sdc_capi.hip sdc_create: which arrays a batch has)"""
+    library's own thresholds (sdc_dispatch.hpp sdc_wide_mirrors: which arrays a batch has)"""
     N, E, cap = eng.n_envs, eng.episode_steps, eng.config["hist_cap"]
     per = (4 * L.HDR_DWORDS * 2 + 4 * eng.hist_stride + 4 * 4 * L.QWIN + 8 * eng.queue_stride + 2 * 8 * eng.lw +   # A: record, header,
            4 * L.N_AGENTS * L.OBS_PAD + 4 * L.SHARE_OBS_DIM)                                                        # ring ... obs rows
@@ -37,7 +37,7 @@ def clone_bytes(eng, n_pairs):
         per += 8 * 32                                                                                                # A: config scalars
     if 8 * (E + 25 + eng.lw) <= 50 * 1024:
         per += (E + 1) * 4 * 32                                                                                      # B: feature rows
-    if N % 64 == 0 and N >= _define("SDC_WIDE_MIN_ENVS", "sdc_capi.hip"):                                          # C: the mirrors
+    if N % 64 == 0 and N >= _define("SDC_WIDE_MIN_ENVS", "sdc_dispatch.hpp"):                                          # C: the mirrors
         per += 4 * (eng.queue_stride + (cap if N >= _define("SDC_HIST_MIRROR_MIN_ENVS", "sdc_device.hpp") else 0))
     return 2 * per * n_pairs
 

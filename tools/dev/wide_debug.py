@@ -12,7 +12,7 @@ hist = np.full((N, 10240), np.nan, np.float32)
 hist[:, :cap] = (331 + 70 * rng.standard_normal((N, cap))).clip(150, 650).astype(np.float32)
 pos = rng.integers(0, cap, N).astype(np.int32)
 engs = []
-for flags in (2048, 512):
+for flags in (L.DEBUG_WIDE, L.DEBUG_PAIR):
     e = SdcEngine(N, episode_steps=steps, auto_reset=True, seed=12, debug_flags=flags)
     e.set_tables(0, tb["W"], tb["C"], tb["T"], tb["WB"]); e.set_dc_params(0, p); e.assign(0, 0, 174, 188)
     e.set_state("hist", hist); e.set_state("hist_len", np.full(N, cap, np.int32)); e.set_state("hist_pos", pos)

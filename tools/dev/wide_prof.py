@@ -1,5 +1,5 @@
 """A few hundred steady-state step launches at N envs with full history rings (injected: no 10 000-step fill) for a profiler.
-usage: python tools/dev/wide_prof.py N [steps] ; SDC_DBG = debug_flags (4096: lane-per-env kernel off)"""
+usage: python tools/dev/wide_prof.py N [steps] ; SDC_DBG = debug_flags (DEBUG_WIDE_OFF = 4096: lane-per-env kernel off)"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch

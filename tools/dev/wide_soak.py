@@ -1,4 +1,4 @@
-"""Soak of the lane-per-env kernel in VERIFY mode (debug_flags bit 0: after every step sdc_reward_verify_kernel checks every key of all
+"""Soak of the lane-per-env kernel in VERIFY mode (debug_flags DEBUG_VERIFY: after every step sdc_reward_verify_kernel checks every key of all
 four rank windows against its rank in the ring, the quartiles against an exact bisection, z against a direct fp64 pass): N envs from
 empty rings through the 10 000-step fill (young histories, the first re-centrings, the request flood around step 64-100) and four more
 episodes.   usage: python tools/dev/wide_soak.py [N] [steps]"""
@@ -8,7 +8,7 @@ import numpy as np, torch, bench
 from dc_rl_amd import _lib as L
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 12700
-eng, tb, params = bench.build_engine(N, 672, 0, seed=4321, debug_flags=1)
+eng, tb, params = bench.build_engine(N, 672, 0, seed=4321, debug_flags=L.DEBUG_VERIFY)
 g = torch.Generator(device="cpu").manual_seed(77)
 pool = torch.randint(0, 3, (128, N, 3), dtype=torch.int32, generator=g).to("cuda:0")
 eng.reset()

@@ -4,8 +4,9 @@ the workgroup entered.  usage: python tools/dev/wide_tail.py N"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch, bench
+from dc_rl_amd import _lib as L
 N = int(sys.argv[1])
-e, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=2048)
+e, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=L.DEBUG_WIDE)
 g = torch.Generator(device="cpu").manual_seed(1234)
 acts = torch.randint(0, 3, (64, N, 3), dtype=torch.int32, generator=g).to("cuda:0")
 e.reset()

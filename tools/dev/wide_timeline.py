@@ -2,10 +2,11 @@
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch, bench
+from dc_rl_amd import _lib as L
 N = int(sys.argv[1])
 # steady state as bench.py reaches it: 10 000-step history fill from the synthetic traces (injected rings of i.i.d. values make a step's
 # energy land inside the rank windows far more often than a real history does)
-e, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=2048)
+e, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=L.DEBUG_WIDE)
 g = torch.Generator(device="cpu").manual_seed(1234)
 acts = torch.randint(0, 3, (64, N, 3), dtype=torch.int32, generator=g).to("cuda:0")
 e.reset()

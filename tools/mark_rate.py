@@ -39,7 +39,7 @@ def mark_bytes(eng, K, rewind):
     loop's copy of obs (none here: no actor is set)"""
     N = eng.n_envs
     per = 2 * (1964 + 12 * K)
-    if rewind and N % 64 == 0 and N >= _define("SDC_WIDE_MIN_ENVS", "sdc_capi.hip"):
+    if rewind and N % 64 == 0 and N >= _define("SDC_WIDE_MIN_ENVS", "sdc_dispatch.hpp"):
         mirrors = 2 if N >= _define("SDC_HIST_MIRROR_MIN_ENVS", "sdc_device.hpp") else 1
         per += 12 + 8 * K * mirrors
     return per * N

@@ -1,10 +1,11 @@
-"""Diagnostic: histogram of the reward path codes (info[:, 39]) over steady-state steps (debug_flags bit 1 = miss reasons)."""
+"""Diagnostic: histogram of the reward path codes (info[:, 39]) over steady-state steps (debug_flags DEBUG_WHY_REBUILD = miss reasons)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import bench
+from dc_rl_amd import _lib as L
 N = int(os.environ.get("SDC_N", "4096"))
-eng, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=int(os.environ.get("SDC_DBG","2")))
+eng, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=int(os.environ.get("SDC_DBG", str(L.DEBUG_WHY_REBUILD))))
 g = torch.Generator(device="cpu").manual_seed(1234)
 pool = torch.randint(0, 3, (64, N, 3), dtype=torch.int32, generator=g).to("cuda:0")
 mode = os.environ.get("SDC_MODE", "rand")

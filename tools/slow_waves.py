@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, bench
 from dc_rl_amd import _lib as L
 N = 4096
-eng, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=8)
+eng, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=L.DEBUG_PHASES)
 g = torch.Generator(device="cpu").manual_seed(1234)
 pool = torch.randint(0, 3, (256, N, 3), dtype=torch.int32, generator=g).to("cuda:0")
 eng.reset()

@@ -22,7 +22,7 @@ def call_bytes(eng, restore):
     mirrors (range C: the cum column of the queue table and the ring read again, the mirror rows written) and the closed loop's copy"""
     N, cap = eng.n_envs, eng.config["hist_cap"]
     per = 2 * int(eng.lib.sdc_snapshot_row_bytes(eng._h))
-    if restore and N % 64 == 0 and N >= _define("SDC_WIDE_MIN_ENVS", "sdc_capi.hip"):
+    if restore and N % 64 == 0 and N >= _define("SDC_WIDE_MIN_ENVS", "sdc_dispatch.hpp"):
         rows = eng.queue_stride + (cap if N >= _define("SDC_HIST_MIRROR_MIN_ENVS", "sdc_device.hpp") else 0)
         per += 8 * eng.queue_stride + 4 * rows      # (range C reads whole 16-byte pieces of the queue table: both columns)
     return per * N

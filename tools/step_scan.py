@@ -1,10 +1,11 @@
 """us per sdc_step launch (no episode boundary inside the timed window) by batch size and lane mapping (development aid):
-debug_flags 512 = two envs per wavefront, 1024 = four."""
+debug_flags DEBUG_PAIR = two envs per wavefront, DEBUG_QUAD = four."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, bench
+from dc_rl_amd import _lib as L
 for N in [int(x) for x in os.environ.get("SDC_NS", "4096,8192,12288,16384").split(",")]:
-    for flags in (512, 1024):
+    for flags in (L.DEBUG_PAIR, L.DEBUG_QUAD):
         eng, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=flags)
         g = torch.Generator(device="cuda").manual_seed(1234)
         pool = torch.randint(0, 3, (256, N, 3), dtype=torch.int32, device="cuda", generator=g)
@@ -42,5 +43,5 @@ for N in [int(x) for x in os.environ.get("SDC_NS", "4096,8192,12288,16384").spli
             eng.rollout_actor(kk, sample=True); done += kk
         torch.cuda.synchronize(); tc = (time.perf_counter() - t0) / done * 1e6
         print("N %6d  %s: %.2f us per step = %.1f M env-steps/s;  sdc_rollout (48 per launch) %.2f us = %.1f M;  closed loop (sampled) %.2f us = %.1f M" % (
-            N, "two envs per wavefront " if flags == 512 else "four envs per wavefront", best, N / best, tr, N / tr, tc, N / tc))
+            N, "two envs per wavefront " if flags == L.DEBUG_PAIR else "four envs per wavefront", best, N / best, tr, N / tr, tc, N / tc))
         eng.close()

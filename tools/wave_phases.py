@@ -1,8 +1,9 @@
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, bench
+from dc_rl_amd import _lib as L
 N = int(os.environ.get("SDC_N", "4096"))
-for flags in (8, 24):
+for flags in (L.DEBUG_PHASES, L.DEBUG_PHASES | L.DEBUG_STAMPS):
     eng, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=flags)
     g = torch.Generator(device="cpu").manual_seed(1234)
     pool = torch.randint(0, 3, (256, N, 3), dtype=torch.int32, generator=g).to("cuda:0")
@@ -13,7 +14,7 @@ for flags in (8, 24):
         o, s, r, d, info = eng.step(pool[i & 255])
         rows.append(info[::2, 39:44].cpu().numpy().copy())
     a = np.concatenate(rows)
-    if flags == 8:
+    if flags == L.DEBUG_PHASES:
         x = a[:, 2:] / 100.0
         print("per wave (us): dynamics %.2f  reward(2 envs) %.2f  total-after-gather %.2f | p99 total %.2f max %.2f" % (
             x[:, 0].mean(), x[:, 1].mean(), x[:, 2].mean(), np.percentile(x[:, 2], 99), x[:, 2].max()))

@@ -3,8 +3,9 @@ by rare path taken (info[reserved] bits), by a_ls of the pair, by where they ran
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, bench
+from dc_rl_amd import _lib as L
 N = 4096
-eng, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=8 | 16 | 256)
+eng, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=L.DEBUG_PHASES | L.DEBUG_STAMPS | L.DEBUG_HW_ID)
 g = torch.Generator(device="cpu").manual_seed(1234)
 pool = torch.randint(0, 3, (1024, N, 3), dtype=torch.int32, generator=g).to("cuda:0")
 eng.reset()
@@ -22,7 +23,7 @@ for i in range(300):
 P0 = np.stack([r[0] for r in rows]); P1 = np.stack([r[1] for r in rows]); HW = np.stack([r[2] for r in rows])
 PRE = np.stack([r[3] for r in rows]) / 100.0; END = np.stack([r[4] for r in rows]); REW = np.stack([r[5] for r in rows]) / 100.0
 A0 = np.stack([r[6] for r in rows]); A1 = np.stack([r[7] for r in rows])
-# (flag 16 without 32: inf[40] would be dbg_a0 & 0xFFFFF; with 256 it is the HW id; inf[43] = end & 0xFFFFF, inf[41] = entry -> staged)
+# (STAMPS without RECORD_WAIT: inf[40] would be dbg_a0 & 0xFFFFF; with HW_ID it is the HW id; inf[43] = end & 0xFFFFF, inf[41] = entry -> staged)
 bits = (P0 >> 3) | (P1 >> 3)
 path = np.maximum(P0 & 7, P1 & 7)
 print("waves x launches", P0.shape[1], P0.shape[0])

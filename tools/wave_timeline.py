@@ -1,10 +1,11 @@
-"""Diagnostic: the life of every wavefront of a step launch on one time axis (in-kernel clock stamps, debug_flags 8 + 16):
+"""Diagnostic: the life of every wavefront of a step launch on one time axis (in-kernel clock stamps, debug_flags DEBUG_PHASES + DEBUG_STAMPS):
 entry, inputs staged, end; which wavefronts end last, and what the launch span would be without the slowest ones."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, bench
+from dc_rl_amd import _lib as L
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
-eng, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=24)
+eng, tb, params = bench.build_engine(N, 672, 0, seed=1234, debug_flags=L.DEBUG_PHASES | L.DEBUG_STAMPS)
 g = torch.Generator(device="cpu").manual_seed(1234)
 pool = torch.randint(0, 3, (256, N, 3), dtype=torch.int32, generator=g).to("cuda:0")
 eng.reset()
