@@ -18,6 +18,8 @@
 
 #include "sdc_device.hpp"
 #include "sdc_dispatch.hpp"
+#include "sdc_kernels.hpp"
+#include "sdc_mirror.hpp"
 #include "sdc_actor.hpp"
 #include "sdc_clone.hpp"
 #include "sdc_snapshot.hpp"
@@ -27,44 +29,6 @@
 #include "sdc_plan.hpp"
 #include "sdc_plan_terms.hpp"
 #include "sdc_stats.hpp"
-
-extern "C" __global__ void sdc_dynamics_kernel(SdcDev S, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
-                                               unsigned char* done, float* info, float* final_obs, float* rew);
-extern "C" __global__ void sdc_dynamics_fast_kernel(SdcDev S, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
-                                                    unsigned char* done, float* info, float* final_obs, float* rew);
-extern "C" __global__ void sdc_dynamics_quad_kernel(SdcDev S, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
-                                                    unsigned char* done, float* info, float* final_obs, float* rew);
-extern "C" __global__ void sdc_dynamics_wide_kernel(SdcDev S, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
-                                                    unsigned char* done, float* info, float* final_obs, float* rew);
-extern "C" __global__ void sdc_dynamics_wide_gen_kernel(SdcDev S, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
-                                                        unsigned char* done, float* info, float* final_obs, float* rew);
-extern "C" __global__ void sdc_rollout_quad_kernel(SdcDev S, int K, int rel_hint, const int32_t* actions, float* obs,
-                                                   float* share_obs, unsigned char* done, float* info, float* final_obs, float* rew);
-extern "C" __global__ void sdc_rollout_fast_kernel(SdcDev S, int K, int rel_hint, const int32_t* actions, float* obs,
-                                                   float* share_obs, unsigned char* done, float* info, float* final_obs, float* rew);
-extern "C" __global__ void sdc_rollout_actor_kernel(SdcDev S, int K, int rel_hint, const SdcActorDev* nets, const float* obs_in,
-                                                    int sample, float* obs, float* share_obs, unsigned char* done, float* info,
-                                                    float* final_obs, float* rew, int32_t* actions_out, float* logits_out,
-                                                    float* obs_latch);
-size_t sdc_rollout_actor_lds_bytes();
-extern "C" __global__ void sdc_rollout_actor_quad_kernel(SdcDev S, int K, int rel_hint, const SdcActorDev* nets, const float* obs_in,
-                                                         int sample, float* obs, float* share_obs, unsigned char* done, float* info,
-                                                         float* final_obs, float* rew, int32_t* actions_out, float* logits_out,
-                                                         float* obs_latch);
-size_t sdc_rollout_actor_quad_lds_bytes();
-extern "C" __global__ void sdc_reward_verify_kernel(SdcDev S, float* info);
-extern "C" __global__ void sdc_features_kernel(SdcDev S, int use_sma);
-extern "C" __global__ void sdc_rollout_kernel(SdcDev S, int K, int rel_hint, const int32_t* actions, float* obs, float* share_obs,
-                                              unsigned char* done, float* info, float* final_obs, float* rew);
-
-hipError_t sdc_clone_launch(const SdcClonePlan& P, hipStream_t st);     // sdc_clone.hip
-hipError_t sdc_snapshot_launch(const SdcSnapPlan& P, bool save, hipStream_t st);     // sdc_snapshot.hip
-hipError_t sdc_mark_launch(const SdcMarkPlan& P, bool save, hipStream_t st);     // sdc_mark.hip
-
-extern "C" __global__ void sdc_reset_kernel(SdcDev S, int use_override, const int* ovr_day, const int* ovr_hour,
-                                            const double* ovr_ci_min, const double* ovr_ci_max, const double* ovr_t_min,
-                                            const double* ovr_t_max, int only_done, float* obs, float* share_obs,
-                                            const double* inj_noise, const int* inj_roll);
 
 namespace {
 
@@ -113,7 +77,7 @@ struct IdxStage {
 struct sdc_handle {
   sdc_config cfg;
   SdcDev d;
-  int rel_hint = -1;   // the episode step all envs are at, if they are in lock-step (else -1)
+  SdcHostMirror mirror;      // what the host knows of each env (sdc_mirror.hpp): every decision below is taken from it, none from the device
   int step_no = 3;           // steps launched (stamps the deferred window re-centrings; starts above the stamps of zeroed memory)
   int device;
   std::vector<void*> allocs;
@@ -125,12 +89,6 @@ struct sdc_handle {
   double* ovr_ci_max = nullptr;
   double* ovr_t_min = nullptr;
   double* ovr_t_max = nullptr;
-  // host mirror for auto-reset scheduling: steps left until the earliest env finishes
-  std::vector<int> host_t_rel;  // exact at the last sync point
-  int pending = 0;              // steps launched since then (every env advances by one per step)
-  int steps_to_terminal = 0;
-  std::vector<unsigned char> feat_host;   // host mirror of R_FEAT_OK: the env's episode has valid observation feature rows
-  int n_feat_host = 0;                    // how many envs have
   // closed loop (sdc_set_actor / sdc_rollout_actor): the three actor networks and the library's copy of the latest
   // observations (what the first actions of a launch are chosen from); allocated when the first actor is set
   SdcActorDev* actor_dev = nullptr;
@@ -142,11 +100,9 @@ struct sdc_handle {
   int racks_cfg0 = 0;                     // racks of data-centre config 0 (the specialised kernels take <= 32: one pass)
   const char* last_step_kernel = "";      // sdc_last_step_kernel
   int rack_cls_cfg0 = 0;                  // ... and its rack classes (SdcRackClasses; 0: more than the lane-per-env kernel's tables hold)
-  // several data-centre configs: host copies of the configs and of the assignment, from which every env's own copy of its
+  // several data-centre configs: host copies of the configs, from which (and the mirror's assignment) every env's own copy of its
   // config's scalars is built (SdcDev::prm_env) -- the common-case kernels then serve the batch as they serve one config
   std::vector<SdcDcDev> dc_host;
-  std::vector<int> cfg_host;
-  std::vector<int> loc_host;              // ... and of every env's trace set (what a snapshot's manifest records)
   std::vector<unsigned char> dc_set;
   double* prm_env_dev = nullptr;
   double* prm_cfg_dev = nullptr;          // [n_dc_configs][32] each config's scalars: what a restore copies into prm_env
@@ -155,8 +111,6 @@ struct sdc_handle {
   // the lane-per-env kernel's general form (sdc_wide.hip GEN): one SdcWideCfg per config, when the batch's configs qualify
   SdcWideCfg* wcfg_dev = nullptr;
   bool wide_gen_ok = false;
-  std::vector<unsigned char> last_done;   // which envs finished in the last sdc_step / sdc_rollout call (host mirror)
-  int n_last_done = 0;
   bool tables_set = false, assigned = false, started = false;
   // optional per-kernel timing: the kernels stamp the device wall clock per workgroup into one slot per sampled step
   int prof = 0;       // sample every `prof`-th step (0 = off)
@@ -170,10 +124,7 @@ struct sdc_handle {
   // the {env, row, cfg_id, loc_id} of the snapshot / restore / mark / rewind calls
   IdxStage clone_stage{sizeof(int2)};
   IdxStage idx_stage{sizeof(int4)};
-  // sdc_mark_envs / sdc_rewind_envs: ONE live mark per env -- the serial of the env's latest mark (0: none alive; sized by the first
-  // mark), cleared by whatever rewrites state a mark row does not hold (mark_kill); the index staging is idx_stage
-  std::vector<int> mark_serial;
-  int mark_next_serial = 0;
+  // sdc_mark_envs / sdc_rewind_envs: which marks are alive is the mirror's; the index staging is idx_stage
   int mark_engine_id = 0;                 // this handle's id in the manifests it fills (given out by the first mark)
   // sdc_plan: the mark rows and the rollouts' output block (sdc_plan.hpp) are the handle's, grown on demand and freed with it; the
   // manifest of its mark; the discount table's staging
@@ -210,14 +161,6 @@ int dev_alloc(sdc_handle* h, T** p, size_t count, bool zero = true) {
   return 0;
 }
 
-// fold the steps launched since the last sync point into the per-env mirror
-void sync_mirror(sdc_handle* h) {
-  if (h->pending) {
-    for (int e = 0; e < h->cfg.n_envs; e++) h->host_t_rel[e] += h->pending;
-    h->pending = 0;
-  }
-}
-
 // one field of every env's record (256-byte state record, or 256-byte header) <-> a dense host array
 // the episode's observation feature rows of the envs a reset kernel has just reset (sdc_features.hip); episodes too long
 // for the kernel's LDS windows go without (the step then computes the features itself)
@@ -250,19 +193,11 @@ int rec_get(sdc_handle* h, int idx, int dwords, void* host, int in_hdr = 0) {
 // the episode's precomputed observation rows follow the traces, the env's location and its weather windows
 int invalidate_features(sdc_handle* h) {
   std::vector<unsigned> z((size_t)h->cfg.n_envs, 0u);
-  h->feat_host.assign((size_t)h->cfg.n_envs, 0);
-  h->n_feat_host = 0;
+  h->mirror.features_invalidated();
   return rec_put(h, R_FEAT_OK, 1, z.data());
 }
-// the envs a reset has just given fresh feature rows (launch_features: every env the reset kernel has reset)
-void note_features(sdc_handle* h, int e) {
-  if (h->d.feat && !h->feat_host[e]) {
-    h->feat_host[e] = 1;
-    h->n_feat_host += 1;
-  }
-}
 // WHICH KERNEL a stepping call lands on is decided in sdc_dispatch.hpp, from these facts about the handle and the call (`some_actions`:
-// the caller's array, or the actors' choices for the closed loop) -- host fields and pointer bits, nothing per env
+// the caller's array, or the actors' choices for the closed loop) -- host fields, the mirror's two summaries and pointer bits, nothing per env
 SdcStepFacts step_facts(const sdc_handle* h, const bool some_actions, const float* obs, const float* share_obs, const float* info,
                         const float* final_obs, const int32_t* actions_out, const bool timed) {
   const auto aligned = [](const void* p, const uintptr_t to) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) == 0; };
@@ -277,8 +212,8 @@ SdcStepFacts step_facts(const sdc_handle* h, const bool some_actions, const floa
   f.wide_gen_ok = h->wide_gen_ok;
   f.has_qcum_t = d.qcum_t != nullptr;
   f.has_feat = d.feat != nullptr;
-  f.n_feat_host = h->n_feat_host;
-  f.rel_hint = h->rel_hint;
+  f.n_feat_host = h->mirror.n_feat();
+  f.rel_hint = h->mirror.rel_hint();
   for (int a = 0; a < 3; a++) {
     f.policy[a] = d.policy[a];
     f.reward_method[a] = d.reward_method[a];
@@ -300,7 +235,7 @@ static_assert(sdc_kernel_of(SDC_PATH_WIDE, SDC_LAUNCH_SINGLE).envs_per_block == 
 // rebuild_prm_env on its way there)
 void refresh_racks_max(sdc_handle* h) {
   h->racks_max = 0;
-  for (int e = 0; e < h->cfg.n_envs; e++) h->racks_max = std::max(h->racks_max, h->dc_host[(size_t)h->cfg_host[(size_t)e]].p.n_racks);
+  for (int e = 0; e < h->cfg.n_envs; e++) h->racks_max = std::max(h->racks_max, h->dc_host[(size_t)h->mirror.cfg(e)].p.n_racks);
 }
 
 // several configs: (re)build every env's copy of its config's scalars once all configs and the assignment are known
@@ -308,14 +243,14 @@ int rebuild_prm_env(sdc_handle* h) {
   h->prm_env_ok = false;
   h->d.prm_env = nullptr;
   const int N = h->cfg.n_envs, C = h->cfg.n_dc_configs;
-  if (C <= 1 || (int)h->cfg_host.size() != N) return 0;
+  if (C <= 1 || !h->mirror.cfg_assigned()) return 0;
   for (int c = 0; c < C; c++)
     if (!h->dc_set[c]) return 0;
   // (the config's scalars lie contiguously from sdc_dc_params::m_cpu to SdcDcDev::ret_sum: sdc_step.hip's P_* enum, asserted there)
   constexpr size_t P_COUNT_HOST = (offsetof(SdcDcDev, ret_sum) - offsetof(SdcDcDev, p.m_cpu)) / sizeof(double) + 1;
   static_assert(P_COUNT_HOST <= 32, "prm_env rows are 32 doubles");
   std::vector<double> tab((size_t)N * 32, 0.0);
-  for (int e = 0; e < N; e++) std::memcpy(&tab[(size_t)e * 32], &h->dc_host[h->cfg_host[e]].p.m_cpu, sizeof(double) * P_COUNT_HOST);
+  for (int e = 0; e < N; e++) std::memcpy(&tab[(size_t)e * 32], &h->dc_host[(size_t)h->mirror.cfg(e)].p.m_cpu, sizeof(double) * P_COUNT_HOST);
   refresh_racks_max(h);
   if (!h->prm_env_dev && dev_alloc(h, &h->prm_env_dev, (size_t)N * 32) != 0) return -1;
   HIP_TRY(hipMemcpy(h->prm_env_dev, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
@@ -397,61 +332,6 @@ int latch_obs(sdc_handle* h, const float* obs, hipStream_t st) {
   return 0;
 }
 
-// the envs whose episode ended with the step(s) just launched, from the host mirror of the step counters
-void note_done(sdc_handle* h) {
-  const int N = h->cfg.n_envs;
-  h->last_done.assign((size_t)N, 0);
-  h->n_last_done = 0;
-  for (int e = 0; e < N; e++)
-    if (h->host_t_rel[e] >= h->cfg.episode_steps) {
-      h->last_done[e] = 1;
-      h->n_last_done += 1;
-    }
-}
-
-void recompute_steps_to_terminal(sdc_handle* h) {
-  sync_mirror(h);
-  int m = 1 << 30;
-  for (int e = 0; e < h->cfg.n_envs; e++) {
-    const int left = h->cfg.episode_steps - h->host_t_rel[e];
-    if (left < m) m = left;
-  }
-  h->steps_to_terminal = m;
-  // envs in lock-step: the kernels are told the episode step up front (see env_step)
-  h->rel_hint = h->host_t_rel.empty() ? -1 : h->host_t_rel[0];
-  for (int e = 1; e < h->cfg.n_envs && h->rel_hint >= 0; e++)
-    if (h->host_t_rel[e] != h->rel_hint) h->rel_hint = -1;
-}
-
-// every mark of env e is dead: its episode, ring, queue table, windows or feature rows are being rewritten as a whole
-inline void mark_kill(sdc_handle* h, const int e) {
-  if (!h->mark_serial.empty()) h->mark_serial[(size_t)e] = 0;
-}
-inline void mark_kill_all(sdc_handle* h) {
-  if (!h->mark_serial.empty()) std::fill(h->mark_serial.begin(), h->mark_serial.end(), 0);
-}
-
-// env e has started a new episode (a reset, by the caller or inside a stepping call): whatever a reset invalidates goes here
-void new_episode(sdc_handle* h, const int e) {
-  h->host_t_rel[e] = 0;
-  note_features(h, e);
-  mark_kill(h, e);
-}
-
-// env e's state has been replaced as a whole (a clone or a restore into it): the host mirrors follow what it holds now -- episode step,
-// feature rows, config, trace set.  The caller folds pending steps in first (sync_mirror) and calls recompute_steps_to_terminal behind
-// its last env: rel_hint comes back if the batch is in lock-step afterwards
-void follow_env(sdc_handle* h, const size_t e, const int t_rel, const bool feat_ok, const int cfg, const int loc) {
-  h->host_t_rel[e] = t_rel;
-  mark_kill(h, (int)e);
-  if (h->feat_host[e] != (feat_ok ? 1 : 0)) {
-    h->n_feat_host += feat_ok ? 1 : -1;
-    h->feat_host[e] = feat_ok ? 1 : 0;
-  }
-  if (h->cfg_host.size() == h->host_t_rel.size()) h->cfg_host[e] = cfg;
-  if (h->loc_host.size() == h->host_t_rel.size()) h->loc_host[e] = loc;
-}
-
 // the kernels behind sdc_dispatch.hpp's table, by SdcStepPath
 using StepKernel = void (*)(SdcDev, int, const int32_t*, float*, float*, unsigned char*, float*, float*, float*);
 using RolloutKernel = void (*)(SdcDev, int, int, const int32_t*, float*, float*, unsigned char*, float*, float*, float*);
@@ -474,12 +354,12 @@ void launch_rollout(sdc_handle* h, const SdcDev& d, const SdcStepPath path, cons
   const SdcKernelInfo k = sdc_kernel_of(path, SDC_LAUNCH_MULTI);
   h->last_step_kernel = k.name;
   hipLaunchKernelGGL(ROLLOUT_KERNELS[path], dim3(sdc_env_blocks(k, h->cfg.n_envs)), dim3(SDC_WAVE * k.waves_per_block), 0, st, d, n_steps,
-                     h->rel_hint, actions, obs, share_obs, done, info, final_obs, rew);
+                     h->mirror.rel_hint(), actions, obs, share_obs, done, info, final_obs, rew);
 }
 
 // What every stepping call does behind its launch(es) of n_steps steps; obs_last / share_obs_last (may be NULL) are the LAST step's
-// slices.  Episodes have a fixed length and every env advances one step per launched step, so the host knows from its mirror of the
-// step counters when an env has finished -- no device read-back.  With auto_reset the finished envs are reset inside the call
+// slices.  Episodes have a fixed length and every env advances one step per launched step, so the host knows from its mirror
+// (sdc_mirror.hpp) when an env has finished -- no device read-back.  With auto_reset the finished envs are reset inside the call
 // (harl/envs/env_wrappers.py:176-190): the last step's obs / share_obs receive the reset observation, final_obs keeps the pre-reset
 // one.  `timed`: the launch was a profiled sdc_step.  The closed loop's copy of the latest observations is taken in every case
 // (`latch_always`) or only after an auto-reset (sdc_rollout_actor: its kernel writes the copy itself)
@@ -487,26 +367,16 @@ int finish_launch(sdc_handle* h, SdcDev& d, const int n_steps, float* obs_last, 
                   const bool latch_always) {
   HIP_TRY(hipGetLastError());
   const int N = h->cfg.n_envs;
-  h->n_last_done = 0;
-  h->steps_to_terminal -= n_steps;
-  h->pending += n_steps;
-  if (h->rel_hint >= 0) h->rel_hint += n_steps;
   bool was_reset = false;
-  if (h->steps_to_terminal == 0) {      // at least one env just finished
-    sync_mirror(h);
-    note_done(h);
-    if (h->cfg.auto_reset) {
-      d.reset_mask = nullptr;
-      if (timed) h->prof_has_reset[h->prof_used] = 1;
-      hipLaunchKernelGGL(sdc_reset_kernel, dim3(N), dim3(SDC_WAVE), 0, st, d, 0, h->ovr_day, h->ovr_hour, h->ovr_ci_min,
-                         h->ovr_ci_max, h->ovr_t_min, h->ovr_t_max, 1, obs_last, share_obs_last, nullptr, nullptr);
-      launch_features(h, d, st);
-      HIP_TRY(hipGetLastError());
-      for (int e = 0; e < N; e++)
-        if (h->host_t_rel[e] >= h->cfg.episode_steps) new_episode(h, e);
-      recompute_steps_to_terminal(h);
-      was_reset = true;
-    }
+  if (h->mirror.stepped(n_steps) && h->cfg.auto_reset) {      // at least one env just finished
+    d.reset_mask = nullptr;
+    if (timed) h->prof_has_reset[h->prof_used] = 1;
+    hipLaunchKernelGGL(sdc_reset_kernel, dim3(N), dim3(SDC_WAVE), 0, st, d, 0, h->ovr_day, h->ovr_hour, h->ovr_ci_min, h->ovr_ci_max,
+                       h->ovr_t_min, h->ovr_t_max, 1, obs_last, share_obs_last, nullptr, nullptr);
+    launch_features(h, d, st);
+    HIP_TRY(hipGetLastError());
+    h->mirror.finished_envs_reset();
+    was_reset = true;
   }
   if (timed) h->prof_used += 1;
   if (latch_always || was_reset) return latch_obs(h, obs_last, st) ? -1 : 0;
@@ -782,8 +652,7 @@ int sdc_create(const sdc_config* cfg, sdc_handle** out) {
       return fail_msg("sdc_create: hour LUT upload failed");
     }
   }
-  h->host_t_rel.assign(N, cfg->episode_steps);  // "finished": a reset is required before stepping
-  h->feat_host.assign(N, 0);
+  h->mirror = SdcHostMirror(N, cfg->episode_steps, d.feat != nullptr);      // every env "finished": a reset is required before stepping
   h->fields = {
       {"cursor", nullptr, 4, R_CURSOR, 1}, {"t_rel", nullptr, 4, R_TREL, 1}, {"day", nullptr, 4, R_DAY, 1},
       {"hourq", nullptr, 4, R_HOURQ, 1}, {"q_popped", nullptr, 4, R_QPOPPED, 1}, {"q_cum", nullptr, 4, R_QCUM, 1},
@@ -968,8 +837,8 @@ int sdc_assign_envs(sdc_handle* h, const int32_t* loc_id, const int32_t* cfg_id,
     if (rec_put(h, R_STPT, 2, st.data())) return -1;
   }
   h->assigned = true;
-  h->cfg_host.assign(cfg_id, cfg_id + N);
-  h->loc_host.assign(loc_id, loc_id + N);
+  h->mirror.set_cfg_ids(cfg_id);
+  h->mirror.set_loc_ids(loc_id);
   h->dc_set.resize((size_t)h->cfg.n_dc_configs, 0);
   if (rebuild_prm_env(h)) return -1;
   return rebuild_wide_cfg(h);
@@ -1072,10 +941,7 @@ int sdc_reset(sdc_handle* h, const uint8_t* mask_host, const sdc_reset_override*
     return -1;
   }
   if (mask_host) HIP_TRY(hipStreamSynchronize(st));  // mask staging buffer is reused by the next call
-  sync_mirror(h);
-  for (int e = 0; e < N; e++)
-    if (!mask_host || mask_host[e]) new_episode(h, e);
-  recompute_steps_to_terminal(h);
+  h->mirror.reset(mask_host);
   h->started = true;
   return 0;
 }
@@ -1085,7 +951,7 @@ int sdc_step(sdc_handle* h, const int32_t* actions, float* obs, float* share_obs
   if (!h || !obs || !rew || !done) return fail_msg("sdc_step: null argument");
   if (!actions && !sdc_all_policies(h->d.policy)) return fail_msg("sdc_step: actions may only be NULL when every agent slot has a policy");
   if (!h->started) return fail_msg("sdc_step: sdc_reset must be called first");
-  if (h->steps_to_terminal <= 0)
+  if (h->mirror.steps_to_terminal() <= 0)
     return fail_msg("sdc_step: an environment has finished its episode; call sdc_reset (auto_reset is off)");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1099,7 +965,7 @@ int sdc_step(sdc_handle* h, const int32_t* actions, float* obs, float* share_obs
   d.step_no = h->step_no;
   h->step_no = next_step_no(h->step_no, 1);
   const SdcStepPath path = sdc_single_step_path(step_facts(h, actions != nullptr, obs, share_obs, info, final_obs, nullptr, timed));
-  launch_step(h, d, path, h->rel_hint, actions, obs, share_obs, done, info, final_obs, rew, st);
+  launch_step(h, d, path, h->mirror.rel_hint(), actions, obs, share_obs, done, info, final_obs, rew, st);
   if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) hipLaunchKernelGGL(sdc_reward_verify_kernel, dim3(N), dim3(SDC_BLOCK), 0, st, d, info);
   return finish_launch(h, d, 1, obs, share_obs, st, timed, true);
 }
@@ -1110,9 +976,9 @@ int sdc_rollout(sdc_handle* h, int n_steps, const int32_t* actions, float* obs, 
   if (!actions && !sdc_all_policies(h->d.policy)) return fail_msg("sdc_rollout: actions may only be NULL when every agent slot has a policy");
   if (!h->started) return fail_msg("sdc_rollout: sdc_reset must be called first");
   if (n_steps <= 0) return fail_msg("sdc_rollout: n_steps must be positive");
-  if (n_steps > h->steps_to_terminal)
+  if (n_steps > h->mirror.steps_to_terminal())
     return fail_msg("sdc_rollout: the rollout would run past the end of an episode (" +
-                    std::to_string(h->steps_to_terminal) + " steps left); split it there");
+                    std::to_string(h->mirror.steps_to_terminal()) + " steps left); split it there");
   if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) return fail_msg("sdc_rollout: verify mode checks single steps; use sdc_step");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -1130,7 +996,7 @@ int sdc_rollout(sdc_handle* h, int n_steps, const int32_t* actions, float* obs, 
       h->step_no = next_step_no(h->step_no, 1);
       const size_t o = (size_t)k * N;
       d.actions_out = actions_out ? actions_out + o * 3 : nullptr;
-      const int rel_k = h->rel_hint >= 0 ? h->rel_hint + k : h->rel_hint;
+      const int rel = h->mirror.rel_hint(), rel_k = rel >= 0 ? rel + k : rel;
       launch_step(h, d, rp.path, rel_k, actions ? actions + o * 3 : nullptr, obs + o * SDC_OBS_OUT, share_obs + o * SDC_SHARE_OBS_DIM,
                   done + o, info + o * SDC_INFO_DIM, final_obs, rew + o * 3, st);
     }
@@ -1193,8 +1059,8 @@ int sdc_rollout_actor(sdc_handle* h, int n_steps, int sample, float* obs, float*
   if (!h->started) return fail_msg("sdc_rollout_actor: sdc_reset must be called first");
   if (!h->latch_valid) return fail_msg("sdc_rollout_actor: no observations yet (the actors were set after the last reset / step: reset or step once)");
   if (n_steps <= 0) return fail_msg("sdc_rollout_actor: n_steps must be positive");
-  if (n_steps > h->steps_to_terminal)
-    return fail_msg("sdc_rollout_actor: the rollout would run past the end of an episode (" + std::to_string(h->steps_to_terminal) +
+  if (n_steps > h->mirror.steps_to_terminal())
+    return fail_msg("sdc_rollout_actor: the rollout would run past the end of an episode (" + std::to_string(h->mirror.steps_to_terminal()) +
                     " steps left); split it there");
   // the common case only, with the actions coming from the actors instead of the caller
   const SdcActorPath ap = sdc_actor_path(step_facts(h, true, obs, share_obs, info, final_obs, actions_out, false));
@@ -1221,21 +1087,21 @@ int sdc_rollout_actor(sdc_handle* h, int n_steps, int sample, float* obs, float*
   const SdcKernelInfo k = sdc_kernel_of(ap.path, SDC_LAUNCH_ACTOR);
   hipLaunchKernelGGL(quad ? sdc_rollout_actor_quad_kernel : sdc_rollout_actor_kernel, dim3(sdc_env_blocks(k, N)),
                      dim3(SDC_WAVE * k.waves_per_block), quad ? sdc_rollout_actor_quad_lds_bytes() : sdc_rollout_actor_lds_bytes(), st, d,
-                     n_steps, h->rel_hint, h->actor_dev, h->obs_latch, sample ? 1 : 0, obs, share_obs, done, info, final_obs, rew,
+                     n_steps, h->mirror.rel_hint(), h->actor_dev, h->obs_latch, sample ? 1 : 0, obs, share_obs, done, info, final_obs, rew,
                      actions_out, logits_out, h->obs_latch);
   // (after an auto-reset alone: the next launch starts from the reset observations)
   const size_t last = (size_t)(n_steps - 1) * N;
   return finish_launch(h, d, n_steps, obs + last * SDC_OBS_OUT, share_obs + last * SDC_SHARE_OBS_DIM, st, false, false);
 }
 
-int sdc_steps_to_episode_end(const sdc_handle* h) { return h ? h->steps_to_terminal : -1; }
+int sdc_steps_to_episode_end(const sdc_handle* h) { return h ? h->mirror.steps_to_terminal() : -1; }
 
 const char* sdc_last_step_kernel(const sdc_handle* h) { return h ? h->last_step_kernel : ""; }
 
 int sdc_last_done(const sdc_handle* h, uint8_t* done_host) {
   if (!h) return -1;
-  if (h->n_last_done > 0 && done_host) std::memcpy(done_host, h->last_done.data(), (size_t)h->cfg.n_envs);
-  return h->n_last_done;
+  if (h->mirror.n_last_done() > 0 && done_host) std::memcpy(done_host, h->mirror.last_done(), (size_t)h->cfg.n_envs);
+  return h->mirror.n_last_done();
 }
 
 int sdc_profile_enable(sdc_handle* h, int enable) {
@@ -1358,26 +1224,16 @@ int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t
   } else {
     HIP_TRY(hipMemcpy(*f->ptr, host_buf, need, hipMemcpyHostToDevice));
   }
+  const int* ids = static_cast<const int*>(host_buf);      // (cfg_id, loc_id: [N]; record: the fields of [N][SDC_REC_DWORDS])
   if (h->cfg.n_dc_configs > 1) {             // the envs' own copies of their configs' scalars follow the assignment
-    if (is_cfg) {
-      const int* c = static_cast<const int*>(host_buf);
-      h->cfg_host.assign(c, c + h->cfg.n_envs);
-      if (rebuild_prm_env(h)) return -1;
-    } else if (is_record) {
-      const unsigned* r = static_cast<const unsigned*>(host_buf);
-      h->cfg_host.resize((size_t)h->cfg.n_envs);
-      for (int e = 0; e < h->cfg.n_envs; e++) h->cfg_host[e] = (int)r[(size_t)e * SDC_REC_DWORDS + R_CFG];
+    if (is_cfg || is_record) {
+      if (is_cfg) h->mirror.set_cfg_ids(ids);
+      else h->mirror.set_cfg_ids(ids + R_CFG, SDC_REC_DWORDS);
       if (rebuild_prm_env(h)) return -1;
     }
   }
-  if (std::strcmp(field, "loc_id") == 0) {
-    const int* l = static_cast<const int*>(host_buf);
-    h->loc_host.assign(l, l + h->cfg.n_envs);
-  } else if (is_record) {
-    const unsigned* r = static_cast<const unsigned*>(host_buf);
-    h->loc_host.resize((size_t)h->cfg.n_envs);
-    for (int e = 0; e < h->cfg.n_envs; e++) h->loc_host[e] = (int)r[(size_t)e * SDC_REC_DWORDS + R_LOC];
-  }
+  if (std::strcmp(field, "loc_id") == 0) h->mirror.set_loc_ids(ids);
+  else if (is_record) h->mirror.set_loc_ids(ids + R_LOC, SDC_REC_DWORDS);
   if (h->d.qcum_t && std::strcmp(field, "qtab") == 0) {
     hipLaunchKernelGGL(sdc_qcum_mirror_kernel, dim3(h->d.qstride, (h->cfg.n_envs + 255) / 256), dim3(256), 0, 0, h->d);
     HIP_TRY(hipGetLastError());
@@ -1389,7 +1245,7 @@ int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t
     HIP_TRY(hipDeviceSynchronize());
   }
   h->latch_valid = false;                  // (closed loop: the library's copy of the latest observations describes the state before this write)
-  mark_kill_all(h);                        // (a mark row holds only what steps change: whatever was written, it may not be that)
+  h->mirror.mark_kill_all();               // (a mark row holds only what steps change: whatever was written, it may not be that)
   if (invalidate_features(h)) return -1;   // whatever was written, the precomputed observation rows may no longer match it
   // Deferred window re-centrings in flight belong to the state that has just been overwritten: a restored header may
   // carry request stamps (H_PEND) that the NEXT step would find "two steps old" again and take a swept window over --
@@ -1401,9 +1257,7 @@ int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t
   if (std::strcmp(field, "t_rel") == 0 || std::strcmp(field, "record") == 0) {
     std::vector<int> tr(h->cfg.n_envs);
     if (rec_get(h, R_TREL, 1, tr.data())) return -1;
-    h->pending = 0;
-    h->host_t_rel = tr;
-    recompute_steps_to_terminal(h);
+    h->mirror.reload_t_rel(tr.data());
   }
   return 0;
 }
@@ -1472,15 +1326,8 @@ int sdc_clone_envs(sdc_handle* h, const int32_t* src, const int32_t* dst, int n,
       }))
     return -1;
 
-  // the host mirrors follow src's
-  sync_mirror(h);
-  const bool cfgs = (int)h->cfg_host.size() == N, locs = (int)h->loc_host.size() == N;
-  for (int k = 0; k < n; k++) {
-    const size_t s = (size_t)src[k];
-    follow_env(h, (size_t)dst[k], h->host_t_rel[s], h->feat_host[s] != 0, cfgs ? h->cfg_host[s] : 0, locs ? h->loc_host[s] : 0);
-  }
+  h->mirror.copy_envs(src, dst, n);
   if (h->prm_env_ok) refresh_racks_max(h);
-  recompute_steps_to_terminal(h);
   return 0;
 }
 
@@ -1591,12 +1438,11 @@ int sdc_snapshot_envs(sdc_handle* h, const int32_t* envs, int n, void* rows, int
     return fail_msg("sdc_snapshot_envs: obs / share_obs rows not dword-aligned, or a layout the snapshot plan does not know");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  sync_mirror(h);
-  const bool cfgs = (int)h->cfg_host.size() == N, locs = (int)h->loc_host.size() == N;
+  const SdcHostMirror& mir = h->mirror;
   std::vector<int4> ix((size_t)n);
   for (int k = 0; k < n; k++) {
     const int e = envs[k];
-    const int cfg = cfgs ? h->cfg_host[(size_t)e] : 0, loc = locs ? h->loc_host[(size_t)e] : 0;
+    const int cfg = mir.cfg(e), loc = mir.loc(e);
     ix[(size_t)k] = make_int4(e, k, cfg, loc);
     int32_t* m = manifest + (size_t)k * SDC_SNAPSHOT_MANIFEST;
     m[SDC_SNAP_LAYOUT] = (int32_t)state_layout_hash();
@@ -1604,8 +1450,8 @@ int sdc_snapshot_envs(sdc_handle* h, const int32_t* envs, int n, void* rows, int
     m[SDC_SNAP_HIST_CAP] = h->cfg.hist_cap;
     m[SDC_SNAP_QUEUE_STRIDE] = h->d.qstride;
     m[SDC_SNAP_WINDOW_LEN] = h->d.lw;
-    m[SDC_SNAP_T_REL] = h->host_t_rel[(size_t)e];
-    m[SDC_SNAP_FEAT_OK] = h->feat_host[(size_t)e] ? 1 : 0;
+    m[SDC_SNAP_T_REL] = mir.t_rel(e);
+    m[SDC_SNAP_FEAT_OK] = mir.feat(e) ? 1 : 0;
     m[SDC_SNAP_CFG_ID] = cfg;
     m[SDC_SNAP_LOC_ID] = loc;
   }
@@ -1614,7 +1460,7 @@ int sdc_snapshot_envs(sdc_handle* h, const int32_t* envs, int n, void* rows, int
   return snap_launch(h, P, true, ix, st);
 }
 
-// Env envs[k] becomes snapshot row rows_idx[k] (sdc_snapshot.hip), ordered on `stream` like a step; the host mirrors follow the
+// Env envs[k] becomes snapshot row rows_idx[k] (sdc_snapshot.hip), ordered on `stream` like a step; the host's mirror follows the
 // manifest, so a restore that leaves the batch in lock-step keeps rel_hint and the specialised kernels
 int sdc_restore_envs(sdc_handle* h, const int32_t* rows_idx, const int32_t* envs, int n, const void* rows, int n_rows,
                      const int32_t* manifest, float* obs, float* share_obs, void* stream) {
@@ -1670,14 +1516,15 @@ int sdc_restore_envs(sdc_handle* h, const int32_t* rows_idx, const int32_t* envs
     }
   if (snap_launch(h, P, false, ix, st)) return -1;
 
-  // the host mirrors follow the manifest
-  sync_mirror(h);
+  // the host's copy follows the manifest
+  std::vector<SdcEnvFacts> facts;
+  facts.reserve(ix.size());
   for (const int4& x : ix) {
     const int32_t* m = manifest + (size_t)x.y * SDC_SNAPSHOT_MANIFEST;
-    follow_env(h, (size_t)x.x, m[SDC_SNAP_T_REL], d.feat && m[SDC_SNAP_FEAT_OK], m[SDC_SNAP_CFG_ID], m[SDC_SNAP_LOC_ID]);
+    facts.push_back({x.x, m[SDC_SNAP_T_REL], m[SDC_SNAP_FEAT_OK] != 0, m[SDC_SNAP_CFG_ID], m[SDC_SNAP_LOC_ID]});
   }
+  h->mirror.replace_envs(facts.data(), facts.size());
   if (h->prm_env_ok) refresh_racks_max(h);
-  recompute_steps_to_terminal(h);
   return 0;
 }
 
@@ -1768,30 +1615,27 @@ int sdc_mark_envs(sdc_handle* h, const int32_t* envs, int n, int max_steps, void
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (mark_launch(h, P, true, row_of, envs == nullptr, st)) return -1;
   // the bookkeeping behind the launch: the device is already at work while the host fills the manifest
-  sync_mirror(h);
-  if (h->mark_serial.empty()) h->mark_serial.assign((size_t)N, 0);
   if (!h->mark_engine_id) {
     static std::atomic<int> ids{0};
     h->mark_engine_id = ++ids;
   }
-  h->mark_next_serial = h->mark_next_serial == 0x7FFFFFFF ? 1 : h->mark_next_serial + 1;
+  const int serial = h->mirror.mark(envs, n);
   const int32_t layout = (int32_t)state_layout_hash();
   for (int k = 0; k < n; k++) {
     const int e = envs ? envs[k] : k;
-    h->mark_serial[(size_t)e] = h->mark_next_serial;
     int32_t* m = manifest + (size_t)k * SDC_MARK_MANIFEST;
     m[SDC_MARK_M_LAYOUT] = layout;
     m[SDC_MARK_M_ENGINE] = h->mark_engine_id;
     m[SDC_MARK_M_STEPS] = max_steps;
     m[SDC_MARK_M_ENV] = e;
-    m[SDC_MARK_M_SERIAL] = h->mark_next_serial;
-    m[SDC_MARK_M_T_REL] = h->host_t_rel[(size_t)e];
+    m[SDC_MARK_M_SERIAL] = serial;
+    m[SDC_MARK_M_T_REL] = h->mirror.t_rel(e);
     m[SDC_MARK_M_HIST_CAP] = h->cfg.hist_cap;
   }
   return 0;
 }
 
-// Mark row k -> env envs[k], the slot it was taken from; the host mirrors follow the manifest, so a whole-batch rewind of a lock-step
+// Mark row k -> env envs[k], the slot it was taken from; the host's mirror follows the manifest, so a whole-batch rewind of a lock-step
 // batch keeps rel_hint and the specialised kernels.  The mark stays alive: a rewind may be repeated.
 int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows, const int32_t* manifest, float* obs, float* share_obs,
                     void* stream) {
@@ -1799,8 +1643,8 @@ int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows,
   std::string why = mark_args_error(h, envs, n, rows, manifest, obs, share_obs);
   if (!why.empty()) return fail_msg("sdc_rewind_envs: " + why);
   const int N = h->cfg.n_envs;
-  // every refusal before anything reaches the device, from the host's mirrors
-  sync_mirror(h);
+  // every refusal before anything reaches the device, from the host's mirror
+  SdcHostMirror& mir = h->mirror;
   const int32_t layout = (int32_t)state_layout_hash();
   const int max_steps = manifest[SDC_MARK_M_STEPS];
   if (max_steps < 1 || max_steps > SDC_MARK_MAX_STEPS)
@@ -1819,11 +1663,11 @@ int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows,
     else if (m[SDC_MARK_M_ENV] != e) w = 3;
     else if (m[SDC_MARK_M_STEPS] != max_steps || m[SDC_MARK_M_HIST_CAP] != h->cfg.hist_cap) w = 4;
     else if (envs && row_of[(size_t)e] >= 0) w = 5;
-    else if (m[SDC_MARK_M_SERIAL] == 0 || h->mark_serial[(size_t)e] != m[SDC_MARK_M_SERIAL]) w = 6;
-    else if (h->host_t_rel[(size_t)e] < m[SDC_MARK_M_T_REL]) w = 7;
-    else if (h->host_t_rel[(size_t)e] - m[SDC_MARK_M_T_REL] > max_steps) {
+    else if (!mir.mark_alive(e, m[SDC_MARK_M_SERIAL])) w = 6;
+    else if (mir.steps_since(e, m[SDC_MARK_M_T_REL]) < 0) w = 7;
+    else if (mir.steps_since(e, m[SDC_MARK_M_T_REL]) > max_steps) {
       w = 8;
-      h->mark_serial[(size_t)e] = 0;     // slots beyond the row's reach have been overwritten: nothing can bring this mark back
+      mir.mark_kill(e);     // slots beyond the row's reach have been overwritten: nothing can bring this mark back
     }
     if (envs) row_of[(size_t)e] = k;
     if (w && bad_k < 0) { bad_k = k; bad_why = w; }
@@ -1831,7 +1675,7 @@ int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows,
   if (bad_k >= 0) {
     const int e = envs ? envs[bad_k] : bad_k;
     const int32_t* m = manifest + (size_t)bad_k * SDC_MARK_MANIFEST;
-    const int taken = h->host_t_rel[(size_t)e] - m[SDC_MARK_M_T_REL];
+    const int taken = mir.steps_since(e, m[SDC_MARK_M_T_REL]);
     switch (bad_why) {
       case 1: why = "state layout " + std::to_string(m[SDC_MARK_M_LAYOUT]) + ", this library's is " + std::to_string(layout); break;
       case 2: why = "the mark was taken from another engine (a mark goes back into the engine and the env it came from)"; break;
@@ -1840,7 +1684,7 @@ int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows,
       case 5: why = "the env appears twice"; break;
       case 6: why = "the mark is dead (a later mark of the env, a reset, sdc_set_state, a clone or restore into the env, or an earlier "
                     "rewind refused beyond its max_steps)"; break;
-      case 7: why = "the env is at episode step " + std::to_string(h->host_t_rel[(size_t)e]) + ", before the mark's " +
+      case 7: why = "the env is at episode step " + std::to_string(mir.t_rel(e)) + ", before the mark's " +
                     std::to_string(m[SDC_MARK_M_T_REL]); break;
       default: why = std::to_string(taken) + " steps taken since the mark, more than its max_steps = " + std::to_string(max_steps) +
                      " (the mark is dead for good: slots beyond its reach have been overwritten)";
@@ -1860,10 +1704,8 @@ int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows,
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (mark_launch(h, P, false, row_of, envs == nullptr, st)) return -1;
-  // the host mirrors follow the manifest: the episode step alone (feature rows, config and trace set are the episode's: unchanged; and
-  // not follow_env: the mark stays alive)
-  for (int k = 0; k < n; k++) h->host_t_rel[(size_t)(envs ? envs[k] : k)] = manifest[(size_t)k * SDC_MARK_MANIFEST + SDC_MARK_M_T_REL];
-  recompute_steps_to_terminal(h);
+  // the host's copy follows the manifest: the episode step alone (feature rows, config and trace set are the episode's: unchanged)
+  mir.rewind(envs, n, manifest + SDC_MARK_M_T_REL, SDC_MARK_MANIFEST);
   return 0;
 }
 
@@ -1900,12 +1742,12 @@ static int plan_refused(const char* who, const sdc_handle* h, const int n_steps,
     return fail_msg(w + "obs / share_obs rows not dword-aligned");
   if (!h->started) return fail_msg(w + "sdc_reset must be called first");
   if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) return fail_msg(w + "verify mode checks single steps (sdc_rollout refuses it as well)");
-  if (h->cfg.auto_reset && n_steps >= h->steps_to_terminal)
-    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would finish an episode (" + std::to_string(h->steps_to_terminal) +
+  if (h->cfg.auto_reset && n_steps >= h->mirror.steps_to_terminal())
+    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would finish an episode (" + std::to_string(h->mirror.steps_to_terminal()) +
                     " steps left): the auto-reset kills the mark");
-  if (n_steps > h->steps_to_terminal)
+  if (n_steps > h->mirror.steps_to_terminal())
     return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" +
-                    std::to_string(h->steps_to_terminal) + " steps left)");
+                    std::to_string(h->mirror.steps_to_terminal()) + " steps left)");
   std::memset(&obj, 0, sizeof(obj));
   obj.reward_weight[0] = obj.reward_weight[1] = obj.reward_weight[2] = 1.0;
   obj.gamma = 1.0;
@@ -1958,7 +1800,7 @@ static int plan_prepare(sdc_handle* h, const int n_steps, const sdc_plan_objecti
 
 // n_steps steps rolled out into the handle's output block (layout B, of `chunk` steps) in chunks, per_chunk(first step, steps) behind each
 // chunk's rollout.  Built from the entry point itself -- sdc_rollout -- so the rollouts choose their kernel as sdc_rollout does and the
-// host mirrors are kept by the code that keeps them for every other caller.  actions [n_steps][N][3], or nullptr (built-in policies)
+// host's mirror is kept by the code that keeps it for every other caller.  actions [n_steps][N][3], or nullptr (built-in policies)
 extern "C++" {
 template <class PerChunk>
 static int rollout_chunks(sdc_handle* h, const SdcPlanBlock& B, const int n_steps, const int chunk, const int32_t* actions, void* stream,
@@ -2262,18 +2104,17 @@ int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* 
   if (plan_refused("sdc_plan_cem_groups", h, n_steps, probs && best_seq && best_score && best_action && step_actions && cand && cand_score,
                    obs, share_obs, objective, obj))
     return -2;
-  // what the host mirrors know of a group's replicas: the episode step, the config, the trace set, the feature-row flag
+  // what the host's mirror (sdc_mirror.hpp) knows of a group's replicas: the episode step, the config, the trace set, the feature-row flag
   const int R = c.group_size, G = N / R;
-  sync_mirror(h);
-  const bool cfgs = (int)h->cfg_host.size() == N, locs = (int)h->loc_host.size() == N;
+  const SdcHostMirror& mir = h->mirror;
   for (int e = 0; e < N; e++) {
     const int l = e - e % R;      // the group's first env
     if (e == l) continue;
-    const char* what = h->host_t_rel[(size_t)e] != h->host_t_rel[(size_t)l]                         ? "episode step"
-                       : cfgs && h->cfg_host[(size_t)e] != h->cfg_host[(size_t)l]                  ? "data-centre config"
-                       : locs && h->loc_host[(size_t)e] != h->loc_host[(size_t)l]                  ? "location"
-                       : (h->feat_host[(size_t)e] != 0) != (h->feat_host[(size_t)l] != 0)          ? "feature-row flag"
-                                                                                                   : nullptr;
+    const char* what = mir.t_rel(e) != mir.t_rel(l)   ? "episode step"
+                       : mir.cfg(e) != mir.cfg(l)     ? "data-centre config"
+                       : mir.loc(e) != mir.loc(l)     ? "location"
+                       : mir.feat(e) != mir.feat(l)   ? "feature-row flag"
+                                                      : nullptr;
     if (what)
       return fail_msg(w + "group " + std::to_string(e / R) + " is out of step: env " + std::to_string(e) + " and its group's first env " +
                       std::to_string(l) + " differ in " + what + " (the replicas of a group hold one state: sdc_clone_envs)");
@@ -2308,9 +2149,9 @@ int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int ac
   if (!h->started) return fail_msg(w + "sdc_reset must be called first");
   if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) return fail_msg(w + "verify mode checks single steps (sdc_rollout refuses it as well)");
   if (!actions && !sdc_all_policies(h->d.policy)) return fail_msg(w + "actions may only be NULL when every agent slot has a policy");
-  if (n_steps > h->steps_to_terminal)
+  if (n_steps > h->mirror.steps_to_terminal())
     return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" +
-                    std::to_string(h->steps_to_terminal) + " steps left)");
+                    std::to_string(h->mirror.steps_to_terminal()) + " steps left)");
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t N = (size_t)h->cfg.n_envs;

@@ -38,3 +38,5 @@ struct SdcClonePlan {
   int mirror_rows;
   int mirror_pair_groups;  // ceil(n / 256)
 };
+
+hipError_t sdc_clone_launch(const SdcClonePlan& P, hipStream_t st);

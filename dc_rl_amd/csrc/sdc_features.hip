@@ -12,6 +12,7 @@
 // np.std as NumPy's pairwise add.reduce (for n = 8 / 16: eight accumulators, then ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7))),
 // np.gradient as central differences with one-sided ends, the first sign change of the gradient as a scan.
 #include "sdc_device.hpp"
+#include "sdc_kernels.hpp"
 
 namespace {
 

@@ -24,6 +24,7 @@
 //      per workgroup.
 #pragma once
 
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #define SDC_MARK_BLOCK 256
@@ -56,3 +57,5 @@ struct SdcMarkPlan {
   unsigned* hist_t;        // [hist_cap][N] (nullptr: no ring mirror)
   int m_chunks;            // ceil(K / SDC_MARK_MIRROR_J)
 };
+
+hipError_t sdc_mark_launch(const SdcMarkPlan& P, bool save, hipStream_t st);

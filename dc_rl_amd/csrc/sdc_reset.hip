@@ -14,6 +14,7 @@
 // counters are cleared (carbon_ls.py:85, battery_model.py:90-91, dc_gym.py:114-116); the CRAC set-point
 // and the energy history survive (dc_gym.py:91-140 never touches raw_curr_stpt; reward_creator.py:5).
 #include "sdc_device.hpp"
+#include "sdc_kernels.hpp"
 #include <type_traits>
 
 namespace {

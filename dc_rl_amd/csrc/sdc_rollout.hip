@@ -3,6 +3,7 @@
 #include "sdc_pairstep.hpp"
 #include "sdc_sweep.hpp"
 #include "sdc_actor.hpp"
+#include "sdc_kernels.hpp"
 
 // K env-steps per launch for action sequences that are known up front or chosen by the built-in rule-based policies
 // (scripted evaluation, the reference's RBC / do-nothing baselines): every wavefront advances its own two envs K times

@@ -60,3 +60,5 @@ struct SdcSnapPlan {
   int q_tiles, h_tiles;    // tiles per group of 64 envs: qstride / 16, ceil(hist_cap / 32)
   int tile_groups;         // ceil(n / 64)
 };
+
+hipError_t sdc_snapshot_launch(const SdcSnapPlan& P, bool save, hipStream_t st);

@@ -6,6 +6,7 @@
 // in sdc_wide.hip.
 #include "sdc_pairstep.hpp"
 #include "sdc_sweep.hpp"
+#include "sdc_kernels.hpp"
 
 // One launch of this kernel is one env-step of all N environments.
 template <bool FAST>

@@ -5,6 +5,7 @@
 // z-score that was reported.
 // Measurement / test infrastructure only: never launched when debug_flags is 0.
 #include "sdc_trackers.hpp"
+#include "sdc_kernels.hpp"
 
 namespace {
 

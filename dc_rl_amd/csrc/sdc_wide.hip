@@ -33,6 +33,7 @@
 #include <type_traits>
 #include "sdc_pairstep.hpp"
 #include "sdc_sweep.hpp"
+#include "sdc_kernels.hpp"
 
 namespace {
 
