@@ -1,0 +1,184 @@
+"""Argument work of the Python binding (engine.py, vec_env.py, multi_device.py), each rule written once: index lists and pair
+lists, device-tensor checks, the layout of a step's output block, the shapes of the state arrays, reset overrides, the horizon rules.
+Pure: NumPy, torch and the constants of `_lib`; the library is never loaded and no GPU touched, so tests/test_engine_args.py holds
+every refusal text without one.  The texts are the entry points' own -- callers hand in their name and words.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _lib as L
+
+
+# ---------------------------------------------------------------------- index lists and pair lists
+def int_ids(x, what, n=None):
+    """an int32 array of env / row indices (a scalar stays 0-d); ValueError for anything else.  With `n` the indices are held to
+    [0, n) in place of the int32 bound."""
+    a = np.asarray(x.cpu() if hasattr(x, "cpu") else x)
+    if a.dtype.kind not in "iu" and not (a.size == 0 and a.dtype.kind == "f"):
+        raise ValueError(f"{what} must hold integers, got {a.dtype}")
+    if a.ndim > 1:
+        raise ValueError(f"{what} must be one-dimensional, got shape {a.shape}")
+    if n is not None:
+        if a.size and (a.min() < 0 or a.max() >= n):
+            raise ValueError(f"{what} holds an env index outside [0, {n})")
+    elif a.size and (int(a.min()) < -2 ** 31 or int(a.max()) >= 2 ** 31):
+        raise ValueError(f"{what} holds a value outside int32")
+    a = a.astype(np.int32)
+    return a if a.ndim == 0 else np.ascontiguousarray(a)      # (np.ascontiguousarray would make a scalar one-dimensional)
+
+
+def pairs(first, second, who, first_words, second_words):
+    """two int_ids results as contiguous arrays of one length (a 0-d `first` broadcast); ValueError in the caller's words"""
+    second = np.ascontiguousarray(second.reshape(-1))
+    first = np.ascontiguousarray(np.broadcast_to(first, second.shape) if first.ndim == 0 else first)
+    if first.shape != second.shape:
+        raise ValueError(f"{who}: {first.shape[0]} {first_words} for {second.shape[0]} {second_words}")
+    return first, second
+
+
+def clone_pairs(src, dst, n_envs):
+    """SdcEngine.clone_pairs: (src, dst)"""
+    d = int_ids(dst, "clone_envs: dst", n_envs)
+    return pairs(int_ids(src, "clone_envs: src", n_envs), d, "clone_envs", "sources", "destinations")
+
+
+def restore_pairs(snap_envs, envs=None, rows=None):
+    """SdcEngine.restore_pairs for a snapshot of envs `snap_envs`: (rows, envs)"""
+    n = int(snap_envs.shape[0])
+    d = snap_envs if envs is None else int_ids(envs, "restore: envs").reshape(-1)
+    if rows is None:
+        if envs is not None and d.shape[0] != n:
+            raise ValueError(f"restore: {d.shape[0]} envs for {n} snapshot rows: say which rows go where (rows=)")
+        r = np.arange(n, dtype=np.int32)
+    else:
+        r = int_ids(rows, "restore: rows")
+    return pairs(r, d, "restore", "rows", "envs")
+
+
+def group_sync_pairs(group_size, n, n_name):
+    """sync_groups' clone pairs for `n` envs in groups of `group_size`: (src, dst), every env but a group's first and that first env;
+    ValueError in sync_groups' words, with the caller's name `n_name` for its env count"""
+    R = int(group_size)
+    if R < 2 or R > n or n % R:
+        raise ValueError(f"sync_groups: group_size = {R} must be at least 2 and divide {n_name} = {n}")
+    e = np.arange(n, dtype=np.int32)
+    dst = e[e % R != 0]
+    return dst - dst % R, dst
+
+
+# ---------------------------------------------------------------------- device tensors
+ANY, SOME = None, "some"        # a shape pattern's entries: an int (exactly that), ANY size, SOME (at least 1)
+
+
+def is_tensor(x, dtype, shape, device=None, cuda=True):
+    """x is a contiguous torch tensor of `dtype` whose shape fits the pattern `shape`, on a GPU (`cuda`) and on `device` if given"""
+    import torch
+    return (isinstance(x, torch.Tensor) and x.dtype == dtype and (x.is_cuda or not cuda) and x.is_contiguous() and
+            x.dim() == len(shape) and all(n >= 1 if want is SOME else want is ANY or n == want for n, want in zip(x.shape, shape)) and
+            (device is None or x.device == device))
+
+
+def device_tensor(x, who, name, dtype, shape, text=None, device=None, plural=False):
+    """ValueError unless x is a contiguous CUDA tensor of `dtype` fitting the pattern `shape` (`text`: how the message shows it;
+    default the pattern itself) -- and, where the engine's `device` is given, on it.  `who`: the entry point ("": no prefix)."""
+    pre = f"{who}: " if who else ""
+    if not is_tensor(x, dtype, shape):
+        raise ValueError(f"{pre}{name} must be a contiguous {str(dtype).split('.')[-1]} CUDA tensor of shape {text or tuple(shape)}")
+    if device is not None and x.device != device:
+        raise ValueError(f"{pre}{name} {'are' if plural else 'is'} on {x.device}, this engine runs on {device}")
+
+
+# ---------------------------------------------------------------------- the horizon of lookahead and plan
+def check_horizon(who, K, left=None, auto_reset=False):
+    """ValueError for a horizon a mark cannot hold and -- `left` = steps_to_episode_end() given -- one that would finish an episode"""
+    if K > L.MARK_MAX_STEPS:
+        raise ValueError(f"{who}: K = {K} is more than a mark holds (MARK_MAX_STEPS = {L.MARK_MAX_STEPS})")
+    if left is not None and auto_reset and K >= left:
+        raise ValueError(f"{who}: K = {K} steps would finish an episode ({left} steps left): the auto-reset kills the mark")
+    if left is not None and K > left:
+        raise ValueError(f"{who}: K = {K} steps would run past the end of an episode ({left} steps left)")
+
+
+# ---------------------------------------------------------------------- the step's output block
+# the step's outputs are views of ONE device allocation (obs | share_obs | rew | info as floats, then done as bytes), so that a
+# host-side consumer can fetch a whole step with a single device->host copy (`out_flat`)
+_OUT_FLOATS = (("obs", (L.N_AGENTS, L.OBS_PAD)), ("share", (L.SHARE_OBS_DIM,)), ("rew", (L.N_AGENTS,)), ("info", (L.INFO_DIM,)))
+
+
+def out_layout(n):
+    """the block of `n` envs -> ([(name, dtype name, shape, offset in floats)] in memory order: obs, share, rew, info, done; bytes)"""
+    blocks, o = [], 0
+    for name, per_env in _OUT_FLOATS:
+        blocks.append((name, "float32", (n,) + per_env, o))
+        o += n * int(np.prod(per_env))
+    return blocks + [("done", "uint8", (n,), o)], o * 4 + n
+
+
+def out_views(flat, n):
+    """{name: view} of a flat uint8 tensor (host or device) holding the block of `n` envs"""
+    import torch
+    blocks, _ = out_layout(n)
+    fl = flat[:blocks[-1][3] * 4].view(torch.float32)
+    views = {name: fl[o:o + int(np.prod(shape))].view(shape) for name, _, shape, o in blocks[:-1]}
+    views["done"] = flat[blocks[-1][3] * 4:]
+    return views
+
+
+# ---------------------------------------------------------------------- state arrays (get_state / set_state)
+# an env's scalars, one entry per env: name -> dtype
+STATE_SCALARS = {
+    **dict.fromkeys(("cursor", "t_rel", "day", "hourq", "q_popped", "q_cum", "q_head", "q_cum_hm1", "last_delta", "consecutive", "scale",
+                     "hist_len", "hist_pos", "episode", "loc_id", "cfg_id", "day_lo", "day_hi", "hist_n"), np.int32),
+    **dict.fromkeys(("q_cumT", "q_cumT_hm1", "fault", "order_stat_sticky"), np.uint32),
+    **dict.fromkeys(("stpt", "bat_load", "ci_min", "ci_den", "t_min", "t_den", "hist_ref"), np.float64),
+}
+# name -> (dtype, shape): a string is one of the engine's sizes (n_envs, hist_stride, lw, queue_stride, hist_cap)
+STATE_ARRAYS = {
+    **{name: (dt, ("n_envs",)) for name, dt in STATE_SCALARS.items()},
+    "hist": (np.float32, ("n_envs", "hist_stride")),
+    "t_win": (np.float64, ("n_envs", "lw")), "wb_win": (np.float64, ("n_envs", "lw")),
+    "qtab": (np.uint32, ("n_envs", "queue_stride", 2)),
+    "qcum_t": (np.uint32, ("queue_stride", "n_envs")),      # (get_state only: the slot-major mirrors, where the batch has them)
+    "hist_t": (np.uint32, ("hist_cap", "n_envs")),
+    "record": (np.uint32, ("n_envs", 64)),
+    "ep_return": (np.float64, ("n_envs", 3)),
+    "header": (np.uint32, ("n_envs", L.HDR_DWORDS)),
+    "qwin": (np.uint32, ("n_envs", L.QWIN, 4)),
+}
+
+
+def _shape(shape, sizes):
+    return tuple(sizes[d] if isinstance(d, str) else d for d in shape)
+
+
+def state_array(name, sizes):
+    """a zeroed host array for state `name` of an engine with `sizes`; KeyError for an unknown name"""
+    dt, shape = STATE_ARRAYS[name]
+    return np.zeros(_shape(shape, sizes), dtype=dt)
+
+
+# ---------------------------------------------------------------------- reset overrides
+# kind -> the fields of sdc_reset_override it sets: (field, dtype, shape)
+_PER_ENV_I32 = tuple((f, np.int32, ("n_envs",)) for f in ("day", "hour"))
+RESET_OVERRIDES = {
+    # the reference's own draws (day, hour, roll, the year's coherent-noise array): the device does the rest
+    "noise": _PER_ENV_I32 + (("roll_days", np.int32, ("n_envs",)), ("noise", np.float64, ("n_envs", L.TABLE_LEN))),
+    "windows": _PER_ENV_I32 + tuple((f, np.float64, ("n_envs",)) for f in ("ci_min", "ci_max", "t_min", "t_max")) +
+               tuple((f, np.float64, ("n_envs", "lw")) for f in ("t_win", "wb_win")),
+}
+
+
+def reset_override(override, sizes):
+    """reset's `override` dict -> {field: contiguous host array} (the kind with "noise" if that key is there); ValueError for a shape"""
+    kind = "noise" if "noise" in override else "windows"
+    arrays = {f: np.ascontiguousarray(override[f], dtype=dt) for f, dt, _ in RESET_OVERRIDES[kind]}
+    bad = [len(shape) for f, _, shape in RESET_OVERRIDES[kind] if arrays[f].shape != _shape(shape, sizes)]
+    N = sizes["n_envs"]
+    if bad and kind == "noise":
+        raise ValueError(f"noise injection: noise ({N}, {L.TABLE_LEN}), day / hour / roll_days ({N},)")
+    if 1 in bad:
+        raise ValueError("override scalars must have shape (n_envs,)")
+    if bad:
+        raise ValueError(f"override weather windows must have shape ({N}, {sizes['lw']})")
+    return arrays

@@ -1,8 +1,8 @@
 """SdcEngine: N SustainDC environment instances resident on one MI355X, driven through the C-ABI.
 
 PyTorch is plumbing here: it owns the obs / action / reward / info device buffers and the HIP stream;
-the step runs in the hand-written kernels of csrc/ (sdc_dynamics_kernel = one env-step of all N envs,
-sdc_reset_kernel at episode boundaries).
+every call lands in the hand-written kernels of csrc/ (which step kernel a call launches: csrc/sdc_dispatch.hpp; sdc_reset_kernel at
+episode boundaries).  How the methods below share their plumbing -- `_args.py`'s validators, `_call`, `_p` --: DESIGN.md 4.18.
 """
 from __future__ import annotations
 
@@ -11,19 +11,11 @@ from typing import Optional
 
 import numpy as np
 
+from . import _args as A
 from . import _lib as L
+from ._args import group_sync_pairs       # noqa: F401  (vec_env imports it from here)
 
-_STATE_DTYPES = {
-    "cursor": (np.int32, 1), "t_rel": (np.int32, 1), "day": (np.int32, 1), "hourq": (np.int32, 1),
-    "q_popped": (np.int32, 1), "q_cum": (np.int32, 1), "q_cumT": (np.uint32, 1), "q_head": (np.int32, 1),
-    "q_cum_hm1": (np.int32, 1), "q_cumT_hm1": (np.uint32, 1),
-    "last_delta": (np.int32, 1), "consecutive": (np.int32, 1), "scale": (np.int32, 1),
-    "hist_len": (np.int32, 1), "hist_pos": (np.int32, 1), "episode": (np.int32, 1), "fault": (np.uint32, 1),
-    "loc_id": (np.int32, 1), "cfg_id": (np.int32, 1), "day_lo": (np.int32, 1), "day_hi": (np.int32, 1),
-    "hist_n": (np.int32, 1), "order_stat_sticky": (np.uint32, 1),
-    "stpt": (np.float64, 1), "bat_load": (np.float64, 1), "ci_min": (np.float64, 1), "ci_den": (np.float64, 1),
-    "t_min": (np.float64, 1), "t_den": (np.float64, 1), "hist_ref": (np.float64, 1),
-}
+_STATE_DTYPES = A.STATE_SCALARS     # (an env's scalar states: tests iterate over the names)
 # a full checkpoint: the raw records + every array the kernels own
 # "hist" first: injecting the ring drops the order-statistic trackers, which "header" then restores
 _CHECKPOINT = ["hist", "record", "header", "qwin", "t_win", "wb_win", "qtab"]
@@ -32,19 +24,6 @@ _META_MUST_MATCH = ("layout", "n_envs", "episode_steps", "hist_cap", "queue_max_
                     "n_dc_configs", "env_index_base")
 # ... and a snapshot's rows: the same, but they may go to an engine of another size, and to any slot of it
 _SNAPSHOT_MUST_MATCH = tuple(k for k in _META_MUST_MATCH if k not in ("n_envs", "env_index_base"))
-
-
-def _int_ids(x, what):
-    """an int32 array of env / row indices (a scalar stays 0-d); ValueError for anything else"""
-    a = np.asarray(x.cpu() if hasattr(x, "cpu") else x)
-    if a.dtype.kind not in "iu" and not (a.size == 0 and a.dtype.kind == "f"):
-        raise ValueError(f"{what} must hold integers, got {a.dtype}")
-    if a.ndim > 1:
-        raise ValueError(f"{what} must be one-dimensional, got shape {a.shape}")
-    if a.size and (int(a.min()) < -2 ** 31 or int(a.max()) >= 2 ** 31):
-        raise ValueError(f"{what} holds a value outside int32")
-    a = a.astype(np.int32)
-    return a if a.ndim == 0 else np.ascontiguousarray(a)      # (np.ascontiguousarray would make a scalar one-dimensional)
 
 
 class EnvSnapshot:
@@ -197,19 +176,14 @@ class EpisodeStats:
         return {"per_env": per_env, "batch": batch, "steps": self.steps.cpu().numpy(), "fault": self.fault.cpu().numpy()}
 
 
-def group_sync_pairs(group_size, n, n_name):
-    """sync_groups' clone pairs for `n` envs in groups of `group_size`: (src, dst), every env but a group's first and that first env;
-    ValueError in sync_groups' words, with the caller's name `n_name` for its env count"""
-    R = int(group_size)
-    if R < 2 or R > n or n % R:
-        raise ValueError(f"sync_groups: group_size = {R} must be at least 2 and divide {n_name} = {n}")
-    e = np.arange(n, dtype=np.int32)
-    dst = e[e % R != 0]
-    return dst - dst % R, dst
-
-
 def _p(x):
-    return C.c_void_p(x.data_ptr())
+    """a device tensor's address for the library (None stays a null pointer)"""
+    return None if x is None else C.c_void_p(x.data_ptr())
+
+
+def _ip(a):
+    """... and a host int32 array's"""
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 def plan_objective(reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None) -> L.SdcPlanObjective:
@@ -333,20 +307,44 @@ class SdcEngine:
         self.lw = self.lib.sdc_weather_window_len(self._h)
         self.hist_stride = self.lib.sdc_hist_stride(self._h)
         self.queue_stride = self.lib.sdc_queue_stride(self._h)
-        N = self.n_envs
-        kw = dict(device=self.device)
-        # the step's outputs are views of ONE device allocation (obs | share_obs | rew | info as floats, then done as
-        # bytes), so that a host-side consumer can fetch a whole step with a single device->host copy (`out_flat`)
-        n_f = N * (L.N_AGENTS * L.OBS_PAD + L.SHARE_OBS_DIM + L.N_AGENTS + L.INFO_DIM)
-        self.out_flat = torch.zeros(n_f * 4 + N, dtype=torch.uint8, **kw)
-        fl = self.out_flat[:n_f * 4].view(torch.float32)
-        o = 0
-        self.obs = fl[o:o + N * L.N_AGENTS * L.OBS_PAD].view(N, L.N_AGENTS, L.OBS_PAD); o += N * L.N_AGENTS * L.OBS_PAD
-        self.share_obs = fl[o:o + N * L.SHARE_OBS_DIM].view(N, L.SHARE_OBS_DIM); o += N * L.SHARE_OBS_DIM
-        self.rew = fl[o:o + N * L.N_AGENTS].view(N, L.N_AGENTS); o += N * L.N_AGENTS
-        self.info = fl[o:o + N * L.INFO_DIM].view(N, L.INFO_DIM); o += N * L.INFO_DIM
-        self.done = self.out_flat[n_f * 4:]
-        self.final_obs = torch.zeros((N, L.N_AGENTS, L.OBS_PAD), dtype=torch.float32, **kw)
+        self._sizes = dict(n_envs=self.n_envs, hist_stride=self.hist_stride, lw=self.lw, queue_stride=self.queue_stride,
+                           hist_cap=int(hist_cap))
+        # the step's outputs are views of ONE device allocation (the layout: _args.out_layout)
+        self.out_flat = torch.zeros(A.out_layout(self.n_envs)[1], dtype=torch.uint8, device=self.device)
+        self.obs, self.share_obs, self.rew, self.done, self.info = self.split_out_flat(self.out_flat)
+        self.final_obs = torch.zeros((self.n_envs, L.N_AGENTS, L.OBS_PAD), dtype=torch.float32, device=self.device)
+        self._all_envs = np.arange(self.n_envs, dtype=np.int32)
+        self._obs_ptrs = (_p(self.obs), _p(self.share_obs))      # (the pair most calls end with; the tensors live as long as the engine)
+
+    # ------------------------------------------------------------------ the call into the library (all but step()'s)
+    def _call(self, fn, *args, refuses=False, wrote=()):
+        """fn(handle, *args) on the engine's device.  A return code other than 0 raises what the entry point always raised: SdcError
+        (the older ones), or -- `refuses` -- ValueError for a refusal (rc -2: nothing reached the device) and SdcError for the rest.
+        `wrote`: the tensors (None: skipped) the call wrote or read on the launch stream; they are record_stream'ed when it is pinned."""
+        with self.torch.cuda.device(self.device):
+            rc = fn(self._h, *args)
+        if refuses:
+            self._refused(rc)
+        elif rc != 0:
+            L.check(rc)
+        if self._pinned_stream_obj is not None:      # (used on the pinned stream: the allocator must not reuse them before)
+            for x in wrote:
+                if x is not None:
+                    x.record_stream(self._pinned_stream_obj)
+
+    def _refused(self, rc):
+        if rc == -2:        # (a refusal: fail_msg, before anything reached the device)
+            raise ValueError(self.lib.sdc_last_error().decode())
+        L.check(rc)
+
+    def _behind_torch_stream(self):
+        """tensors filled by torch ops on torch's current stream are about to be read by a kernel on the pinned one: order it behind them"""
+        if self._pinned_stream_obj is not None:
+            self._pinned_stream_obj.wait_stream(self.torch.cuda.current_stream(self.device))
+
+    def _identity(self):
+        """what this engine is: its configuration and the library's state layout (what checkpoints and snapshots are held to)"""
+        return dict(self.config, layout=int(self.lib.sdc_state_layout()))
 
     # ------------------------------------------------------------------ setup
     def set_tables(self, loc_id: int, W, Cc, T, WB):
@@ -355,22 +353,20 @@ class SdcEngine:
             if a.shape != (L.TABLE_LEN,):
                 raise ValueError(f"trace tables must have shape ({L.TABLE_LEN},), got {a.shape}")
         dp = C.POINTER(C.c_double)
-        L.check(self.lib.sdc_set_tables(self._h, int(loc_id), *[a.ctypes.data_as(dp) for a in arrs], L.TABLE_LEN))
+        self._call(self.lib.sdc_set_tables, int(loc_id), *[a.ctypes.data_as(dp) for a in arrs], L.TABLE_LEN)
 
     def set_dc_params(self, cfg_id: int, params: dict):
-        s = dc_params_struct(params)
-        L.check(self.lib.sdc_set_dc_params(self._h, int(cfg_id), C.byref(s)))
+        self._call(self.lib.sdc_set_dc_params, int(cfg_id), C.byref(dc_params_struct(params)))
 
     def assign(self, loc_id, cfg_id, day_lo, day_hi):
         N = self.n_envs
         arrs = [np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.int32), (N,))) for a in
                 (loc_id, cfg_id, day_lo, day_hi)]
-        ip = C.POINTER(C.c_int32)
-        L.check(self.lib.sdc_assign_envs(self._h, *[a.ctypes.data_as(ip) for a in arrs]))
+        self._call(self.lib.sdc_assign_envs, *[_ip(a) for a in arrs])
 
     def set_seed(self, seed: int):
         seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        L.check(self.lib.sdc_set_seed(self._h, seed))
+        self._call(self.lib.sdc_set_seed, seed)
         self.seed = seed
 
     # ------------------------------------------------------------------ run
@@ -396,43 +392,12 @@ class SdcEngine:
             if m.shape != (N,):
                 raise ValueError("mask must have shape (n_envs,)")
             mptr = m.ctypes.data_as(C.POINTER(C.c_uint8))
-        optr = None
-        keep = None
-        if override is not None and "noise" in override:
-            # the reference's own draws (day, hour, roll, the year's coherent-noise array): the device does the rest
-            dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-            day = np.ascontiguousarray(override["day"], dtype=np.int32)
-            hour = np.ascontiguousarray(override["hour"], dtype=np.int32)
-            roll = np.ascontiguousarray(override["roll_days"], dtype=np.int32)
-            noise = np.ascontiguousarray(override["noise"], dtype=np.float64)
-            if noise.shape != (N, L.TABLE_LEN) or any(a.shape != (N,) for a in (day, hour, roll)):
-                raise ValueError(f"noise injection: noise ({N}, {L.TABLE_LEN}), day / hour / roll_days ({N},)")
-            nul = C.POINTER(C.c_double)()
-            o = L.SdcResetOverride(day.ctypes.data_as(ip), hour.ctypes.data_as(ip), nul, nul, nul, nul, nul, nul,
-                                   noise.ctypes.data_as(dp), roll.ctypes.data_as(ip))
-            keep = (day, hour, roll, noise, o)
-            optr = C.byref(o)
-        elif override is not None:
-            dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-            day = np.ascontiguousarray(override["day"], dtype=np.int32)
-            hour = np.ascontiguousarray(override["hour"], dtype=np.int32)
-            sc = [np.ascontiguousarray(override[k], dtype=np.float64) for k in ("ci_min", "ci_max", "t_min", "t_max")]
-            tw = np.ascontiguousarray(override["t_win"], dtype=np.float64)
-            wb = np.ascontiguousarray(override["wb_win"], dtype=np.float64)
-            for a in [day, hour] + sc:
-                if a.shape != (N,):
-                    raise ValueError("override scalars must have shape (n_envs,)")
-            if tw.shape != (N, self.lw) or wb.shape != (N, self.lw):
-                raise ValueError(f"override weather windows must have shape ({N}, {self.lw})")
-            o = L.SdcResetOverride(day.ctypes.data_as(ip), hour.ctypes.data_as(ip), *[a.ctypes.data_as(dp) for a in sc],
-                                   tw.ctypes.data_as(dp), wb.ctypes.data_as(dp), C.POINTER(C.c_double)(),
-                                   C.POINTER(C.c_int32)())
-            keep = (day, hour, sc, tw, wb, o)
-            optr = C.byref(o)
-        with self.torch.cuda.device(self.device):
-            L.check(self.lib.sdc_reset(self._h, mptr, optr, C.c_void_p(self.obs.data_ptr()),
-                                       C.c_void_p(self.share_obs.data_ptr()), self._stream()))
-        del keep
+        o = None
+        if override is not None:
+            arrays = A.reset_override(override, self._sizes)        # (alive until the call returns: the struct holds addresses)
+            o = L.SdcResetOverride(**{f: a.ctypes.data_as(C.POINTER(C.c_int32 if a.dtype == np.int32 else C.c_double))
+                                      for f, a in arrays.items()})
+        self._call(self.lib.sdc_reset, mptr, None if o is None else C.byref(o), *self._obs_ptrs, self._stream())
         return self.obs, self.share_obs
 
     def step(self, actions, want_info: bool = True):
@@ -463,14 +428,8 @@ class SdcEngine:
 
     def split_out_flat(self, flat):
         """Views (obs, share_obs, rew, done, info) over a host / device copy of `out_flat` (a uint8 tensor of the same size)."""
-        t, N = self.torch, self.n_envs
-        n_f = N * (L.N_AGENTS * L.OBS_PAD + L.SHARE_OBS_DIM + L.N_AGENTS + L.INFO_DIM)
-        fl = flat[:n_f * 4].view(t.float32)
-        a = N * L.N_AGENTS * L.OBS_PAD
-        b = a + N * L.SHARE_OBS_DIM
-        c = b + N * L.N_AGENTS
-        return (fl[:a].view(N, L.N_AGENTS, L.OBS_PAD), fl[a:b].view(N, L.SHARE_OBS_DIM), fl[b:c].view(N, L.N_AGENTS),
-                flat[n_f * 4:], fl[c:].view(N, L.INFO_DIM))
+        v = A.out_views(flat, self.n_envs)
+        return v["obs"], v["share"], v["rew"], v["done"], v["info"]
 
     def last_step_kernel(self) -> str:
         """Name of the step kernel the last `step()` launched (the host picks by batch size and configuration; all give the same
@@ -504,36 +463,39 @@ class SdcEngine:
         obs [K,N,3,26], share_obs [K,N,29], rew [K,N,3], done [K,N] (uint8), info [K,N,44] (or None).
         Same results as K calls of step()."""
         t = self.torch
+        K = self._sequence_steps("", actions, n_steps)     # (no device check: DESIGN.md 4.18, kept oddities)
+        out = self._rollout_outputs(K, want_info)
+        aout = t.empty((K, self.n_envs, 3), dtype=t.int32, device=self.device) if want_actions else None
+        self._call(self.lib.sdc_rollout, K, _p(actions), *[_p(x) for x in out], _p(self.final_obs), _p(aout), self._stream(),
+                   wrote=out + (aout,))
+        self._views_follow(*out)
+        return out + (aout,) if want_actions else out
+
+    def _sequence_steps(self, who, actions, n_steps, device=None):
+        """K of rollout's and rollout_stats' arguments: an action sequence [K, N, 3] (on `device`, if given), or None with n_steps when
+        every slot has a built-in policy; ValueError in `who`'s name ("": none) for anything else"""
+        pre = f"{who}: " if who else ""
         if actions is None:
             if n_steps is None or any(p == 0 for p in self.policy):
-                raise ValueError("actions=None needs n_steps and a built-in policy on every agent slot")
-            K = int(n_steps)
-        else:
-            if not (isinstance(actions, t.Tensor) and actions.dtype == t.int32 and actions.is_cuda and
-                    actions.is_contiguous() and actions.dim() == 3 and tuple(actions.shape[1:]) == (self.n_envs, 3)):
-                raise ValueError("actions must be a contiguous int32 CUDA tensor of shape (K, n_envs, 3)")
-            K = int(actions.shape[0])
-            if n_steps is not None and int(n_steps) != K:
-                raise ValueError("n_steps does not match the action sequence")
-        N = self.n_envs
-        kw = dict(device=self.device)
-        obs = t.empty((K, N, L.N_AGENTS, L.OBS_PAD), dtype=t.float32, **kw)
-        share = t.empty((K, N, L.SHARE_OBS_DIM), dtype=t.float32, **kw)
-        rew = t.empty((K, N, L.N_AGENTS), dtype=t.float32, **kw)
-        done = t.empty((K, N), dtype=t.uint8, **kw)
-        info = t.empty((K, N, L.INFO_DIM), dtype=t.float32, **kw) if want_info else None
-        aout = t.empty((K, N, 3), dtype=t.int32, **kw) if want_actions else None
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
-        with t.cuda.device(self.device):
-            L.check(self.lib.sdc_rollout(self._h, K, p(actions), p(obs), p(share), p(rew), p(done), p(info),
-                                         p(self.final_obs), p(aout), self._stream()))
-        # the engine's single-step views follow the last step
-        self.obs.copy_(obs[-1]); self.share_obs.copy_(share[-1]); self.rew.copy_(rew[-1]); self.done.copy_(done[-1])
-        if info is not None:
-            self.info.copy_(info[-1])
-        if want_actions:
-            return obs, share, rew, done, info, aout
-        return obs, share, rew, done, info
+                raise ValueError(f"{pre}actions=None needs n_steps and a built-in policy on every agent slot")
+            return int(n_steps)
+        A.device_tensor(actions, who, "actions", self.torch.int32, (A.ANY, self.n_envs, 3), "(K, n_envs, 3)", device, True)
+        if n_steps is not None and int(n_steps) != int(actions.shape[0]):
+            raise ValueError(f"{pre}n_steps does not match the action sequence")
+        return int(actions.shape[0])
+
+    def _rollout_outputs(self, K, want_info=True):
+        """fresh tensors for K steps' outputs: (obs, share_obs, rew, done, info or None)"""
+        t, N = self.torch, self.n_envs
+        new = lambda shape, dtype=t.float32: t.empty((K, N) + shape, dtype=dtype, device=self.device)
+        return (new((L.N_AGENTS, L.OBS_PAD)), new((L.SHARE_OBS_DIM,)), new((L.N_AGENTS,)), new((), t.uint8),
+                new((L.INFO_DIM,)) if want_info else None)
+
+    def _views_follow(self, *out):
+        """the engine's single-step views follow the last step of a rollout's outputs (_rollout_outputs' order)"""
+        for mine, x in zip((self.obs, self.share_obs, self.rew, self.done, self.info), out):
+            if x is not None:
+                mine.copy_(x[-1])
 
     # ------------------------------------------------------------------ closed loop: the actors inside the kernel
     def set_actor(self, agent_slot: int, params):
@@ -541,7 +503,7 @@ class SdcEngine:
         state_dict of the reference's StochasticPolicy (harl/models/policy_models/stochastic_policy.py: keys
         base.feature_norm.*, base.mlp.fc.{0,2,3,5}.*, act.action_out.linear.*; tensors or arrays) or a dict with the
         fields of sdc_actor_params; `activation`: "tanh" (happo.yaml) or "relu"."""
-        L.check(self.lib.sdc_set_actor(self._h, int(agent_slot), C.byref(actor_params(params))))
+        self._call(self.lib.sdc_set_actor, int(agent_slot), C.byref(actor_params(params)))
 
     def rollout_actor(self, n_steps: int, sample: bool = False, want_logits: bool = False):
         """K env-steps in ONE launch with the three actors (set_actor) choosing every action inside the kernel from the
@@ -551,51 +513,21 @@ class SdcEngine:
         logits [K,N,3,3] or None).  K must not run past the end of the episode (steps_to_episode_end())."""
         t = self.torch
         K, N = int(n_steps), self.n_envs
-        kw = dict(device=self.device)
-        obs = t.empty((K, N, L.N_AGENTS, L.OBS_PAD), dtype=t.float32, **kw)
-        share = t.empty((K, N, L.SHARE_OBS_DIM), dtype=t.float32, **kw)
-        rew = t.empty((K, N, L.N_AGENTS), dtype=t.float32, **kw)
-        done = t.empty((K, N), dtype=t.uint8, **kw)
-        info = t.empty((K, N, L.INFO_DIM), dtype=t.float32, **kw)
-        acts = t.empty((K, N, 3), dtype=t.int32, **kw)
-        logits = t.empty((K, N, 3, 3), dtype=t.float32, **kw) if want_logits else None
-        p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
-        with t.cuda.device(self.device):
-            L.check(self.lib.sdc_rollout_actor(self._h, K, 1 if sample else 0, p(obs), p(share), p(rew), p(done), p(info),
-                                               p(self.final_obs), p(acts), p(logits), self._stream()))
-        self.obs.copy_(obs[-1]); self.share_obs.copy_(share[-1]); self.rew.copy_(rew[-1]); self.done.copy_(done[-1])
-        self.info.copy_(info[-1])
-        return obs, share, rew, done, info, acts, logits
+        out = self._rollout_outputs(K)
+        acts = t.empty((K, N, 3), dtype=t.int32, device=self.device)
+        logits = t.empty((K, N, 3, 3), dtype=t.float32, device=self.device) if want_logits else None
+        self._call(self.lib.sdc_rollout_actor, K, 1 if sample else 0, *[_p(x) for x in out], _p(self.final_obs), _p(acts), _p(logits),
+                   self._stream(), wrote=out + (acts, logits))
+        self._views_follow(*out)
+        return out + (acts, logits)
 
     # ------------------------------------------------------------------ state access (parity injection / checkpoint)
     def _state_array(self, name):
-        N = self.n_envs
-        if name in _STATE_DTYPES:
-            dt, k = _STATE_DTYPES[name]
-            return np.zeros((N,) if k == 1 else (N, k), dtype=dt)
-        if name == "hist":
-            return np.zeros((N, self.hist_stride), dtype=np.float32)
-        if name in ("t_win", "wb_win"):
-            return np.zeros((N, self.lw), dtype=np.float64)
-        if name == "qtab":
-            return np.zeros((N, self.queue_stride, 2), dtype=np.uint32)
-        if name == "qcum_t":        # (get_state only: the slot-major mirrors, where the batch has them)
-            return np.zeros((self.queue_stride, N), dtype=np.uint32)
-        if name == "hist_t":
-            return np.zeros((self.config["hist_cap"], N), dtype=np.uint32)
-        if name == "record":
-            return np.zeros((N, 64), dtype=np.uint32)
-        if name == "ep_return":
-            return np.zeros((N, 3), dtype=np.float64)
-        if name == "header":
-            return np.zeros((N, L.HDR_DWORDS), dtype=np.uint32)
-        if name == "qwin":
-            return np.zeros((N, L.QWIN, 4), dtype=np.uint32)
-        raise KeyError(name)
+        return A.state_array(name, self._sizes)
 
     def get_state(self, name: str) -> np.ndarray:
         a = self._state_array(name)
-        L.check(self.lib.sdc_get_state(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), a.nbytes))
+        self._call(self.lib.sdc_get_state, name.encode(), a.ctypes.data_as(C.c_void_p), a.nbytes)
         return a
 
     def set_state(self, name: str, value):
@@ -605,14 +537,14 @@ class SdcEngine:
             a = value       # already in the library's layout: no host copy (a batch's rings are GBs)
         else:
             a[...] = value
-        L.check(self.lib.sdc_set_state(self._h, name.encode(), a.ctypes.data_as(C.c_void_p), a.nbytes))
+        self._call(self.lib.sdc_set_state, name.encode(), a.ctypes.data_as(C.c_void_p), a.nbytes)
 
     def state_dict(self) -> dict:
         """Full env checkpoint (the reference never checkpoints env state): the arrays the kernels own
         and "meta" -- the library's state layout (sdc_state_layout), the engine's configuration and the current RNG seed, which
         keys every future reset."""
         sd = {n: self.get_state(n) for n in _CHECKPOINT}
-        sd["meta"] = dict(self.config, layout=int(self.lib.sdc_state_layout()), seed=self.seed)
+        sd["meta"] = dict(self._identity(), seed=self.seed)
         return sd
 
     def load_state_dict(self, sd: dict):
@@ -623,7 +555,7 @@ class SdcEngine:
         meta = sd.get("meta")
         if not isinstance(meta, dict):
             raise ValueError("load_state_dict: the checkpoint has no 'meta' entry (saved by an older build?)")
-        mine = dict(self.config, layout=int(self.lib.sdc_state_layout()))
+        mine = self._identity()
         for k in _META_MUST_MATCH:
             if k not in meta or meta[k] != mine[k]:
                 raise ValueError(f"load_state_dict: checkpoint {k} = {meta.get(k)!r}, this engine's is {mine[k]!r}")
@@ -643,38 +575,13 @@ class SdcEngine:
         the specialised kernels when every src is at the same episode step.  ValueError for what the library refuses: an empty
         dst, an index outside [0, n_envs), a repeated dst, a dst that is also a src, no reset() yet.  -> (obs, share_obs) views."""
         s, d = self.clone_pairs(src, dst)
-        ip = C.POINTER(C.c_int32)
-        with self.torch.cuda.device(self.device):
-            rc = self.lib.sdc_clone_envs(self._h, s.ctypes.data_as(ip), d.ctypes.data_as(ip), int(d.shape[0]),
-                                         C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.share_obs.data_ptr()), self._stream())
-        if rc == -2:        # (a refusal: fail_msg, before anything reached the device)
-            raise ValueError(self.lib.sdc_last_error().decode())
-        L.check(rc)
+        self._call(self.lib.sdc_clone_envs, _ip(s), _ip(d), int(d.shape[0]), *self._obs_ptrs, self._stream(), refuses=True)
         return self.obs, self.share_obs
 
     def clone_pairs(self, src, dst):
         """clone_envs' arguments as two int32 arrays of one length (a scalar src broadcast); ValueError for a malformed pair list
         (the library checks the rest)."""
-        def ints(x, name):
-            a = np.asarray(x.cpu() if hasattr(x, "cpu") else x)
-            if a.dtype.kind not in "iu" and not (a.size == 0 and a.dtype.kind == "f"):
-                raise ValueError(f"clone_envs: {name} must hold integers, got {a.dtype}")
-            if a.ndim > 1:
-                raise ValueError(f"clone_envs: {name} must be one-dimensional, got shape {a.shape}")
-            if a.size and (a.min() < 0 or a.max() >= self.n_envs):
-                raise ValueError(f"clone_envs: {name} holds an env index outside [0, {self.n_envs})")
-            return a.astype(np.int32)
-        d = np.ascontiguousarray(ints(dst, "dst").reshape(-1))
-        s = ints(src, "src")
-        s = np.ascontiguousarray(np.broadcast_to(s, d.shape) if s.ndim == 0 else s)
-        if s.shape != d.shape:
-            raise ValueError(f"clone_envs: {s.shape[0]} sources for {d.shape[0]} destinations")
-        return s, d
-
-    def _refused(self, rc):
-        if rc == -2:        # (a refusal: fail_msg, before anything reached the device)
-            raise ValueError(self.lib.sdc_last_error().decode())
-        L.check(rc)
+        return A.clone_pairs(src, dst, self.n_envs)
 
     def snapshot(self, envs=None) -> EnvSnapshot:
         """The complete state of envs (default: all) in a device buffer of their own (sdc_snapshot_envs), ordered after the work already
@@ -683,35 +590,19 @@ class SdcEngine:
         queue_max_len, max_roll_days, locations and dc configs (`restore`), on another GPU after `.to(device)`.  ValueError for what the
         library refuses: no env, an index outside [0, n_envs), more envs than the batch, no reset() yet."""
         t = self.torch
-        e = np.arange(self.n_envs, dtype=np.int32) if envs is None else _int_ids(envs, "snapshot: envs").reshape(-1)
+        e = self._all_envs.copy() if envs is None else A.int_ids(envs, "snapshot: envs").reshape(-1)
         n = int(e.shape[0])
-        rb = int(self.lib.sdc_snapshot_row_bytes(self._h))
         manifest = np.zeros((max(n, 1), L.SNAPSHOT_MANIFEST), dtype=np.int32)
-        ip = C.POINTER(C.c_int32)
-        with t.cuda.device(self.device):
-            rows = t.empty((n, rb), dtype=t.uint8, device=self.device)
-            rc = self.lib.sdc_snapshot_envs(self._h, e.ctypes.data_as(ip), n, C.c_void_p(rows.data_ptr()), manifest.ctypes.data_as(ip),
-                                            C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.share_obs.data_ptr()), self._stream())
-        self._refused(rc)
-        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse it before)
-            rows.record_stream(self._pinned_stream_obj)
-        mine = dict(self.config, layout=int(self.lib.sdc_state_layout()))
+        rows = t.empty((n, int(self.lib.sdc_snapshot_row_bytes(self._h))), dtype=t.uint8, device=self.device)
+        self._call(self.lib.sdc_snapshot_envs, _ip(e), n, _p(rows), _ip(manifest), *self._obs_ptrs, self._stream(),
+                   refuses=True, wrote=(rows,))
+        mine = self._identity()
         return EnvSnapshot(rows, manifest[:n], {k: mine[k] for k in _SNAPSHOT_MUST_MATCH}, e)
 
     def restore_pairs(self, snap: EnvSnapshot, envs=None, rows=None):
         """restore's arguments as (rows, envs), two int32 arrays of one length: envs default to snap.envs, rows to 0 .. len(snap) - 1 (a
         scalar broadcast); ValueError for a malformed list (the library checks the rest)."""
-        d = snap.envs if envs is None else _int_ids(envs, "restore: envs").reshape(-1)
-        if rows is None:
-            if envs is not None and d.shape[0] != len(snap):
-                raise ValueError(f"restore: {d.shape[0]} envs for {len(snap)} snapshot rows: say which rows go where (rows=)")
-            r = np.arange(len(snap), dtype=np.int32)
-        else:
-            r = _int_ids(rows, "restore: rows")
-            r = np.ascontiguousarray(np.broadcast_to(r, d.shape) if r.ndim == 0 else r)
-        if r.shape != d.shape:
-            raise ValueError(f"restore: {r.shape[0]} rows for {d.shape[0]} envs")
-        return r, np.ascontiguousarray(d)
+        return A.restore_pairs(snap.envs, envs, rows)
 
     def restore(self, snap: EnvSnapshot, envs=None, rows=None):
         """Env envs[k] becomes snapshot row rows[k] (sdc_restore_envs): by default row k goes back into env snap.envs[k]; a scalar
@@ -721,7 +612,7 @@ class SdcEngine:
         engine's seed.  ValueError for a snapshot of another state layout or configuration, rows on another device, and what the
         library refuses (an index out of range, a repeated env, no reset() yet).  -> (obs, share_obs) views."""
         t = self.torch
-        mine = dict(self.config, layout=int(self.lib.sdc_state_layout()))
+        mine = self._identity()
         for k in _SNAPSHOT_MUST_MATCH:
             if snap.meta.get(k) != mine[k]:
                 raise ValueError(f"restore: snapshot {k} = {snap.meta.get(k)!r}, this engine's is {mine[k]!r}")
@@ -735,14 +626,8 @@ class SdcEngine:
         if m.shape != (snap.rows.shape[0], L.SNAPSHOT_MANIFEST):
             raise ValueError(f"restore: manifest of shape {m.shape} for {snap.rows.shape[0]} rows")
         r, d = self.restore_pairs(snap, envs, rows)
-        ip = C.POINTER(C.c_int32)
-        with t.cuda.device(self.device):
-            rc = self.lib.sdc_restore_envs(self._h, r.ctypes.data_as(ip), d.ctypes.data_as(ip), int(d.shape[0]),
-                                           C.c_void_p(snap.rows.data_ptr()), int(snap.rows.shape[0]), m.ctypes.data_as(ip),
-                                           C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.share_obs.data_ptr()), self._stream())
-        self._refused(rc)
-        if self._pinned_stream_obj is not None:
-            snap.rows.record_stream(self._pinned_stream_obj)
+        self._call(self.lib.sdc_restore_envs, _ip(r), _ip(d), int(d.shape[0]), _p(snap.rows), int(snap.rows.shape[0]), _ip(m),
+                   *self._obs_ptrs, self._stream(), refuses=True, wrote=(snap.rows,))
         return self.obs, self.share_obs
 
     # ------------------------------------------------------------------ mark / rewind / lookahead
@@ -758,23 +643,12 @@ class SdcEngine:
         if rb == 0:
             raise ValueError(f"mark: max_steps = {K} outside [1, {L.MARK_MAX_STEPS}]")
         whole = envs is None
-        if whole:
-            if getattr(self, "_all_envs", None) is None:
-                self._all_envs = np.arange(self.n_envs, dtype=np.int32)
-            e = self._all_envs
-        else:
-            e = _int_ids(envs, "mark: envs").reshape(-1)
+        e = self._all_envs if whole else A.int_ids(envs, "mark: envs").reshape(-1)
         n = int(e.shape[0])
         manifest = np.empty((max(n, 1), L.MARK_MANIFEST), dtype=np.int32)
-        ip = C.POINTER(C.c_int32)
-        with t.cuda.device(self.device):
-            rows = t.empty((n, rb), dtype=t.uint8, device=self.device)
-            rc = self.lib.sdc_mark_envs(self._h, None if whole else e.ctypes.data_as(ip), n, K, C.c_void_p(rows.data_ptr()),
-                                        manifest.ctypes.data_as(ip), C.c_void_p(self.obs.data_ptr()),
-                                        C.c_void_p(self.share_obs.data_ptr()), self._stream())
-        self._refused(rc)
-        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse it before)
-            rows.record_stream(self._pinned_stream_obj)
+        rows = t.empty((n, rb), dtype=t.uint8, device=self.device)
+        self._call(self.lib.sdc_mark_envs, None if whole else _ip(e), n, K, _p(rows), _ip(manifest), *self._obs_ptrs, self._stream(),
+                   refuses=True, wrote=(rows,))
         return EnvMark(rows, manifest[:n], e, K, whole)
 
     def rewind(self, mark: EnvMark, envs=None):
@@ -789,24 +663,18 @@ class SdcEngine:
             raise ValueError("rewind: not an EnvMark")
         if mark.rows.device != self.device:
             raise ValueError(f"rewind: the mark's rows are on {mark.rows.device}, this engine runs on {self.device}")
-        ip = C.POINTER(C.c_int32)
-        with t.cuda.device(self.device):
-            if envs is None:
-                e, rows, m, whole = mark.envs, mark.rows, mark.manifest, mark.whole
-            else:       # some of the mark's envs: their rows gathered into a buffer of their own (row k belongs to envs[k])
-                e = np.ascontiguousarray(_int_ids(envs, "rewind: envs").reshape(-1))
-                pos = mark.positions(e)
-                rows = mark.rows[t.as_tensor(pos, device=self.device)].contiguous() if pos.size else mark.rows[:0]
-                m, whole = np.ascontiguousarray(mark.manifest[pos]), False
-            n = int(e.shape[0])
-            if n == 0:
-                raise ValueError("rewind: no env")
-            rc = self.lib.sdc_rewind_envs(self._h, None if whole else e.ctypes.data_as(ip), n, C.c_void_p(rows.data_ptr()),
-                                          m.ctypes.data_as(ip), C.c_void_p(self.obs.data_ptr()),
-                                          C.c_void_p(self.share_obs.data_ptr()), self._stream())
-        self._refused(rc)
-        if self._pinned_stream_obj is not None:
-            rows.record_stream(self._pinned_stream_obj)
+        if envs is None:
+            e, rows, m, whole = mark.envs, mark.rows, mark.manifest, mark.whole
+        else:       # some of the mark's envs: their rows gathered into a buffer of their own (row k belongs to envs[k])
+            e = np.ascontiguousarray(A.int_ids(envs, "rewind: envs").reshape(-1))
+            pos = mark.positions(e)
+            rows = mark.rows[t.as_tensor(pos, device=self.device)].contiguous() if pos.size else mark.rows[:0]
+            m, whole = np.ascontiguousarray(mark.manifest[pos]), False
+        n = int(e.shape[0])
+        if n == 0:
+            raise ValueError("rewind: no env")
+        self._call(self.lib.sdc_rewind_envs, None if whole else _ip(e), n, _p(rows), _ip(m), *self._obs_ptrs, self._stream(),
+                   refuses=True, wrote=(rows,))
         return self.obs, self.share_obs
 
     def lookahead(self, actions):
@@ -821,17 +689,9 @@ class SdcEngine:
         K >= steps_to_episode_end() with auto_reset (the reset would kill the mark), K > steps_to_episode_end() without; and for
         K > MARK_MAX_STEPS."""
         t = self.torch
-        if not (isinstance(actions, t.Tensor) and actions.dtype == t.int32 and actions.is_cuda and actions.is_contiguous() and
-                actions.dim() == 4 and tuple(actions.shape[2:]) == (self.n_envs, 3) and actions.shape[0] >= 1 and actions.shape[1] >= 1):
-            raise ValueError("lookahead: actions must be a contiguous int32 CUDA tensor of shape (M, K, n_envs, 3)")
+        A.device_tensor(actions, "lookahead", "actions", t.int32, (A.SOME, A.SOME, self.n_envs, 3), "(M, K, n_envs, 3)")
         M, K = int(actions.shape[0]), int(actions.shape[1])
-        if K > L.MARK_MAX_STEPS:
-            raise ValueError(f"lookahead: K = {K} is more than a mark holds (MARK_MAX_STEPS = {L.MARK_MAX_STEPS})")
-        left = self.steps_to_episode_end()
-        if self.config["auto_reset"] and K >= left:
-            raise ValueError(f"lookahead: K = {K} steps would finish an episode ({left} steps left): the auto-reset kills the mark")
-        if K > left:
-            raise ValueError(f"lookahead: K = {K} steps would run past the end of an episode ({left} steps left)")
+        A.check_horizon("lookahead", K, self.steps_to_episode_end(), self.config["auto_reset"])
         with t.cuda.device(self.device):
             keep, keep_final = self.out_flat.clone(), self.final_obs.clone()     # (the last step's outputs: rollout overwrites them)
             mk = self.mark(max_steps=K)
@@ -862,24 +722,16 @@ class SdcEngine:
         actions, an unknown info key or too many, and what the library refuses: K > MARK_MAX_STEPS, K >= steps_to_episode_end() with
         auto_reset (> without), no reset() yet, gamma outside (0, 1], verify mode (debug_flags DEBUG_VERIFY: rollouts have none)."""
         t = self.torch
-        if not (isinstance(actions, t.Tensor) and actions.dtype == t.int32 and actions.is_cuda and actions.is_contiguous() and
-                actions.dim() == 4 and tuple(actions.shape[2:]) == (self.n_envs, 3) and actions.shape[0] >= 1 and actions.shape[1] >= 1):
-            raise ValueError("plan: actions must be a contiguous int32 CUDA tensor of shape (M, K, n_envs, 3)")
-        if actions.device != self.device:
-            raise ValueError(f"plan: actions are on {actions.device}, this engine runs on {self.device}")
+        A.device_tensor(actions, "plan", "actions", t.int32, (A.SOME, A.SOME, self.n_envs, 3), "(M, K, n_envs, 3)", self.device, True)
         M, K, N = int(actions.shape[0]), int(actions.shape[1]), self.n_envs
-        if K > L.MARK_MAX_STEPS:
-            raise ValueError(f"plan: K = {K} is more than a mark holds (MARK_MAX_STEPS = {L.MARK_MAX_STEPS})")
+        A.check_horizon("plan", K)
         obj = plan_objective(reward_weights, gamma, info_weights)
-        with t.cuda.device(self.device):
-            returns = t.empty((M, N, L.N_AGENTS), dtype=t.float64, device=self.device)
-            score = t.empty((M, N), dtype=t.float64, device=self.device)
-            best = t.empty((N,), dtype=t.int32, device=self.device)
-            action = t.empty((N, 3), dtype=t.int32, device=self.device)
-            rc = self.lib.sdc_plan(self._h, M, K, _p(actions), C.byref(obj), _p(returns), _p(score), _p(best), _p(action), _p(self.obs),
-                                   _p(self.share_obs), self._stream())
-        self._refused(rc)
-        self._written_on_pinned_stream(returns, score, best, action, actions)
+        returns = t.empty((M, N, L.N_AGENTS), dtype=t.float64, device=self.device)
+        score = t.empty((M, N), dtype=t.float64, device=self.device)
+        best = t.empty((N,), dtype=t.int32, device=self.device)
+        action = t.empty((N, 3), dtype=t.int32, device=self.device)
+        self._call(self.lib.sdc_plan, M, K, _p(actions), C.byref(obj), _p(returns), _p(score), _p(best), _p(action), *self._obs_ptrs,
+                   self._stream(), refuses=True, wrote=(returns, score, best, action, actions))
         return PlanResult(best, action, score, returns)
 
     def set_plan_terms(self, limits=None, terminal=None):
@@ -920,12 +772,12 @@ class SdcEngine:
         self._set_plan_terms_struct(s)
 
     def _set_plan_terms_struct(self, s: L.SdcPlanTerms):
-        self._refused(self.lib.sdc_set_plan_terms(self._h, C.byref(s)))
+        self._call(self.lib.sdc_set_plan_terms, C.byref(s), refuses=True)
 
     def _plan_terms_struct(self) -> L.SdcPlanTerms:
         """the terms as the library holds them (what a copy of this engine is given: SustainDCVecEnv.__deepcopy__)"""
         s = L.SdcPlanTerms()
-        self._refused(self.lib.sdc_get_plan_terms(self._h, C.byref(s)))
+        self._call(self.lib.sdc_get_plan_terms, C.byref(s), refuses=True)
         return s
 
     @property
@@ -949,16 +801,6 @@ class SdcEngine:
             terminal[key] = s.terminal_weight[j]
         return {k: tuple(v) for k, v in limits.items()}, terminal
 
-    def _written_on_pinned_stream(self, *arrays):
-        if self._pinned_stream_obj is not None:      # (written on the pinned stream: the allocator must not reuse them before)
-            for x in arrays:
-                x.record_stream(self._pinned_stream_obj)
-
-    def _behind_torch_stream(self):
-        """tensors filled by torch ops on torch's current stream are about to be read by a kernel on the pinned one: order it behind them"""
-        if self._pinned_stream_obj is not None:
-            self._pinned_stream_obj.wait_stream(self.torch.cuda.current_stream(self.device))
-
     def _cem_fixed(self, who, fixed_action, seed, draw):
         """fixed_action as three ints; the ValueErrors both CEM calls raise first"""
         fixed = [int(x) for x in fixed_action]
@@ -976,38 +818,27 @@ class SdcEngine:
         `sized` (sizes no array can be given): the library is called with null arrays and words the refusal; it looks at the sizes
         before the arrays."""
         t = self.torch
-
-        def given(x, name, dtype, shape):
-            if not (isinstance(x, t.Tensor) and x.dtype == dtype and x.is_cuda and x.is_contiguous() and tuple(x.shape) == shape):
-                raise ValueError(f"{who}: {name} must be a contiguous {str(dtype).split('.')[-1]} CUDA tensor of shape {shape}")
-            if x.device != self.device:
-                raise ValueError(f"{who}: {name} is on {x.device}, this engine runs on {self.device}")
-
         if check and probs is not None:
-            given(probs, "probs", t.float64, (K, lead, 3, 3))
+            A.device_tensor(probs, who, "probs", t.float64, (K, lead, 3, 3), device=self.device)
         if check and best_seq is not None:
-            given(best_seq, "best_seq", t.int32, (K, lead, 3))
+            A.device_tensor(best_seq, who, "best_seq", t.int32, (K, lead, 3), device=self.device)
         obj = plan_objective(reward_weights, gamma, info_weights)
         cem.n_iters, cem.iter0, cem.n_elite = int(n_iters), int(iter0), int(n_elite)
         cem.fixed_action[:] = fixed
         cem.draw, cem.seed, cem.alpha, cem.p_min = int(draw), int(seed), float(alpha), float(p_min)
-        with t.cuda.device(self.device):
-            if sized:
-                # (probs and best_seq -- the defaults below, a caller's, CEMMPCAgent's shifted ones -- are read by the sample kernel)
-                self._behind_torch_stream()
-                if probs is None:
-                    probs = t.full((K, lead, 3, 3), 1.0 / 3.0, dtype=t.float64, device=self.device)
-                if best_seq is None:
-                    best_seq = t.tensor([1, 1, 2], dtype=t.int32, device=self.device).expand(K, lead, 3).contiguous()
-                arrays = [probs, best_seq] + [t.empty(shape, dtype=dtype, device=self.device) for shape, dtype in outputs]
-                ptrs = [_p(x) for x in arrays]
-            else:
-                arrays, ptrs = [], [None] * (2 + len(outputs))
-            rc = fn(self._h, K, C.byref(cem), C.byref(obj), *ptrs, _p(self.obs), _p(self.share_obs), self._stream())
-            if not sized and rc == 0:
-                raise L.SdcError(f"{who}: {fn.__name__} accepted {sizes} and no arrays")
-        self._refused(rc)
-        self._written_on_pinned_stream(*arrays)
+        arrays = []
+        if sized:
+            # (probs and best_seq -- the defaults below, a caller's, CEMMPCAgent's shifted ones -- are read by the sample kernel)
+            self._behind_torch_stream()
+            if probs is None:
+                probs = t.full((K, lead, 3, 3), 1.0 / 3.0, dtype=t.float64, device=self.device)
+            if best_seq is None:
+                best_seq = t.tensor([1, 1, 2], dtype=t.int32, device=self.device).expand(K, lead, 3).contiguous()
+            arrays = [probs, best_seq] + [t.empty(shape, dtype=dtype, device=self.device) for shape, dtype in outputs]
+        ptrs = [_p(x) for x in arrays] or [None] * (2 + len(outputs))
+        self._call(fn, K, C.byref(cem), C.byref(obj), *ptrs, *self._obs_ptrs, self._stream(), refuses=True, wrote=arrays)
+        if not sized:
+            raise L.SdcError(f"{who}: {fn.__name__} accepted {sizes} and no arrays")
         return result(*arrays)
 
     def plan_cem(self, horizon: int, n_iters: int, n_candidates: int, n_elite: int, *, probs=None, best_seq=None, seed: int = 0,
@@ -1102,41 +933,20 @@ class SdcEngine:
         as after `rollout`.  ValueError, with the engine untouched, for malformed arguments and what the library refuses: K < 1,
         K > steps_to_episode_end(), no reset() yet, verify mode (debug_flags DEBUG_VERIFY)."""
         t = self.torch
-        if actions is None:
-            if n_steps is None or any(p == 0 for p in self.policy):
-                raise ValueError("rollout_stats: actions=None needs n_steps and a built-in policy on every agent slot")
-            K = int(n_steps)
-        else:
-            if not (isinstance(actions, t.Tensor) and actions.dtype == t.int32 and actions.is_cuda and
-                    actions.is_contiguous() and actions.dim() == 3 and tuple(actions.shape[1:]) == (self.n_envs, 3)):
-                raise ValueError("rollout_stats: actions must be a contiguous int32 CUDA tensor of shape (K, n_envs, 3)")
-            if actions.device != self.device:
-                raise ValueError(f"rollout_stats: actions are on {actions.device}, this engine runs on {self.device}")
-            K = int(actions.shape[0])
-            if n_steps is not None and int(n_steps) != K:
-                raise ValueError("rollout_stats: n_steps does not match the action sequence")
+        K = self._sequence_steps("rollout_stats", actions, n_steps, self.device)
         N = self.n_envs
-        if into is not None:
-            want = ((into.stats, t.float64, (L.STATS_FIELDS, N, L.INFO_DIM)), (into.returns, t.float64, (N, L.N_AGENTS)),
-                    (into.counts, t.int32, (N, 2)))
-            if not (isinstance(into, EpisodeStats) and all(isinstance(x, t.Tensor) and x.dtype == d and tuple(x.shape) == sh and
-                                                           x.is_contiguous() and x.device == self.device for x, d, sh in want)):
+        want = ((t.float64, (L.STATS_FIELDS, N, L.INFO_DIM)), (t.float64, (N, L.N_AGENTS)), (t.int32, (N, 2)))     # stats, returns, counts
+        if into is None:
+            res = EpisodeStats(*[t.empty(sh, dtype=d, device=self.device) for d, sh in want])
+        else:
+            res, mine = into, (into.stats, into.returns, into.counts)
+            if not (isinstance(into, EpisodeStats) and all(A.is_tensor(x, d, sh, self.device, cuda=False) for x, (d, sh) in zip(mine, want))):
                 raise ValueError(f"rollout_stats: into must be an EpisodeStats of this engine (contiguous tensors on {self.device}: stats "
-                                 f"float64 {want[0][2]}, returns float64 {want[1][2]}, counts int32 {want[2][2]})")
-        p = lambda x: _p(x) if x is not None else None
-        with t.cuda.device(self.device):
-            if into is None:
-                res = EpisodeStats(t.empty((L.STATS_FIELDS, N, L.INFO_DIM), dtype=t.float64, device=self.device),
-                                   t.empty((N, L.N_AGENTS), dtype=t.float64, device=self.device),
-                                   t.empty((N, 2), dtype=t.int32, device=self.device))
-            else:
-                res = into
-                self._behind_torch_stream()      # (its tensors may have been touched on torch's current stream)
-            rc = self.lib.sdc_rollout_stats(self._h, K, p(actions), 0 if into is None else 1,
-                                            p(res.stats), p(res.returns), p(res.counts), p(self.obs), p(self.share_obs), p(self.rew),
-                                            p(self.done), p(self.info), p(self.final_obs), self._stream())
-        self._refused(rc)
-        self._written_on_pinned_stream(res.stats, res.returns, res.counts, *(() if actions is None else (actions,)))
+                                 f"float64 {want[0][1]}, returns float64 {want[1][1]}, counts int32 {want[2][1]})")
+            self._behind_torch_stream()      # (its tensors may have been touched on torch's current stream)
+        self._call(self.lib.sdc_rollout_stats, K, _p(actions), 0 if into is None else 1, _p(res.stats), _p(res.returns), _p(res.counts),
+                   *self._obs_ptrs, _p(self.rew), _p(self.done), _p(self.info), _p(self.final_obs), self._stream(),
+                   refuses=True, wrote=(res.stats, res.returns, res.counts, actions))
         return res
 
     def evaluate(self, n_episodes: int, actions=None) -> EpisodeStats:
@@ -1161,11 +971,11 @@ class SdcEngine:
 
     def profile(self, every: int = 1):
         """Per-kernel HIP-event timing on the launch stream (measurement only): every k-th step, 0 = off."""
-        L.check(self.lib.sdc_profile_enable(self._h, int(every)))
+        self._call(self.lib.sdc_profile_enable, int(every))
 
     def profile_read(self, reset: bool = True) -> dict:
         out = (C.c_double * 5)()
-        L.check(self.lib.sdc_profile_read(self._h, out, 1 if reset else 0))
+        self._call(self.lib.sdc_profile_read, out, 1 if reset else 0)
         return {"dynamics_ms": out[0], "reward_ms": out[1], "reset_ms": out[2], "steps": int(out[3]),
                 "resets": int(out[4])}
 

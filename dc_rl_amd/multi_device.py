@@ -18,9 +18,10 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
+from . import _args as A
 from . import _lib as L
 from .distributed import shard_range
-from .vec_env import LOGGER_KEYS, LazyInfos, ShareVecEnv, SustainDCVecEnv, _FinalObs
+from .vec_env import LOGGER_KEYS, LazyInfos, ShareVecEnv, SustainDCVecEnv, final_obs_of, sel, sel_obs, share3_np
 
 
 def shard_ranges(n_envs: int, n_shards: int):
@@ -106,25 +107,19 @@ class SustainDCMultiDeviceVecEnv(ShareVecEnv):
         """Two alternating sets of pinned host arrays for the whole job (a step's arrays stay valid until the step after next)."""
         t = self._torch
         if self._host is None:
-            N = self.num_envs
             self._host = []
-            for _ in range(2):
-                full = {"obs": t.empty((N, L.N_AGENTS, L.OBS_PAD), dtype=t.float32, pin_memory=True),
-                        "share": t.empty((N, L.SHARE_OBS_DIM), dtype=t.float32, pin_memory=True),
-                        "rew": t.empty((N, L.N_AGENTS), dtype=t.float32, pin_memory=True),
-                        "info": t.empty((N, L.INFO_DIM), dtype=t.float32, pin_memory=True),
-                        "done": t.empty((N,), dtype=t.uint8, pin_memory=True)}
+            for _ in range(2):      # (the step's five blocks, each a tensor of its own: a shard copies into its slice of each)
+                full = {name: t.empty(shape, dtype=getattr(t, dtype), pin_memory=True)
+                        for name, dtype, shape, _ in A.out_layout(self.num_envs)[0]}
                 full["slices"] = [{k: v[lo:hi] for k, v in full.items()} for lo, hi in self.ranges]
                 self._host.append(full)
         self._host_flip ^= 1
         return self._host[self._host_flip]
 
-    def _sel(self, x):
-        return x if self.n_agents == 3 else x[:, self._agent_idx]
-
-    def _sel_obs(self, obs):
-        o = self._sel(obs)
-        return o if self.obs_width == L.OBS_PAD else o[:, :, :self.obs_width]
+    def _np_outputs(self, obs, share):
+        """(obs, share_obs) of the whole job in NumPy, as a single SustainDCVecEnv lays them out"""
+        return (sel_obs(obs, self._agent_idx, self.obs_width),
+                share3_np(share, obs, self._agent_idx, self.obs_width, self.share_concat))
 
     def seed(self, seed: int):
         for sh in self.shards:
@@ -142,8 +137,7 @@ class SustainDCMultiDeviceVecEnv(ShareVecEnv):
             res = []
             for d, sh in enumerate(self.shards):
                 with self._on(d):
-                    obs, share = outs[d]
-                    res.append((sh._sel_obs(obs), sh._share3(share, obs), sh._avail))
+                    res.append(sh._reset_layout(*outs[d]))
             self._publish()
             return tuple(r[0] for r in res), tuple(r[1] for r in res), tuple(r[2] for r in res)
         host = []
@@ -152,7 +146,7 @@ class SustainDCMultiDeviceVecEnv(ShareVecEnv):
                 host.append((outs[d][0].cpu().numpy(), outs[d][1].cpu().numpy()))
         obs = np.concatenate([o for o, _ in host], axis=0)
         share = np.concatenate([s for _, s in host], axis=0)
-        return self._sel_obs(obs), self._share3_np(share, obs), self._avail_np
+        return (*self._np_outputs(obs, share), self._avail_np)
 
     def _publish(self):
         """Device-resident outputs are produced on the shards' own streams: make each device's CURRENT stream (where the
@@ -166,11 +160,6 @@ class SustainDCMultiDeviceVecEnv(ShareVecEnv):
         t = self._torch
         for dev, st in zip(self.devices, self.streams):
             st.wait_stream(t.cuda.current_stream(dev))
-
-    def _share3_np(self, share, obs):
-        if self.share_concat:
-            share = self._sel_obs(obs).reshape(self.num_envs, self.share_dim)
-        return np.broadcast_to(share[:, None, :], (self.num_envs, self.n_agents, share.shape[1]))
 
     def step_async(self, actions):
         """actions: ONE [N, n_agents(, 1)] batch (NumPy array, host tensor, nested list: the ShareVecEnv contract), or -- the
@@ -223,17 +212,14 @@ class SustainDCMultiDeviceVecEnv(ShareVecEnv):
             for d, (sh, (lo, hi)) in enumerate(zip(self.shards, self.ranges)):
                 if done_h[lo:hi].any():
                     with self._on(d):
-                        extras[d] = _FinalObs(sh.engine.final_obs.cpu().numpy(), done_h[lo:hi], self._agent_idx, k,
-                                              self.share_concat, self.obs_width)
+                        extras[d] = final_obs_of(sh, sh.engine.final_obs.cpu().numpy(), done_h[lo:hi])
         extra = _ShardedExtra(self.ranges, extras) if any(e is not None for e in extras) else {}
         self._gen += 1
         acts = _ShardedActions(applied)
         infos = LazyInfos(hs["info"], acts, done_h, self._const, extra, self, 1, k, self.shards[0]._info_keys)
         if self.snapshot_infos:
             infos.rows()
-        obs = hs["obs"].numpy()
-        share = hs["share"].numpy()
-        return (self._sel_obs(obs), self._share3_np(share, obs), self._sel(hs["rew"].numpy())[..., None],
+        return (*self._np_outputs(hs["obs"].numpy(), hs["share"].numpy()), sel(hs["rew"].numpy(), self._agent_idx)[..., None],
                 np.repeat(done_h[:, None], k, axis=1), infos, self._avail_np)
 
     # ------------------------------------------------------------------ reductions over the shards

@@ -25,6 +25,7 @@ from typing import List, Optional, Union
 
 import numpy as np
 
+from . import _args as A
 from . import _lib as L
 from . import dc_config, traces
 from .engine import SdcEngine, group_sync_pairs
@@ -118,6 +119,48 @@ class _FinalObs:
                                  "original_state": np.repeat(raw[None, :], self._k, axis=0),
                                  "original_avail_actions": np.ones((self._k, 3), dtype=np.float32)}
         return d
+
+
+def final_obs_of(env, final_obs, done):
+    """the _FinalObs of a step of `env` (a vector env or one shard's): the host copy of its pre-reset observations, who finished"""
+    return _FinalObs(final_obs, done, env._agent_idx, env.n_agents, env.share_concat, env.obs_width)
+
+
+def sel(x, agent_idx):
+    """the trained agents' rows of a [N, 3, ...] array (all of them in the usual three-agent case)"""
+    return x if len(agent_idx) == 3 else x[:, agent_idx]
+
+
+def sel_obs(obs, agent_idx, width):
+    """... of the [N, 3, 26] observation block, cut to the widest trained agent's width"""
+    o = sel(obs, agent_idx)
+    return o if width == L.OBS_PAD else o[:, :, :width]
+
+
+def share3_np(share, obs, agent_idx, width, concat):
+    """NumPy outputs: the same shared vector for every trained agent, [N, n_agents, share_dim] (the layouts: SustainDCVecEnv._share3)"""
+    if concat:
+        share = sel_obs(obs, agent_idx, width).reshape(obs.shape[0], width * len(agent_idx))
+    return np.broadcast_to(share[:, None, :], (share.shape[0], len(agent_idx), share.shape[1]))
+
+
+def three_columns(actions, agent_idx, device):
+    """actions [..., n_agents] in the trained agents' order -> the engine's contiguous int32 [..., 3] on its device; with an agent
+    subset the other slots' columns are filled with 1 (they are played on the device and never read)"""
+    import torch as t
+    a = actions if actions.dtype == t.int32 and actions.device == device else actions.to(device=device, dtype=t.int32)
+    if len(agent_idx) != 3:
+        full = t.ones(tuple(a.shape[:-1]) + (3,), dtype=t.int32, device=device)
+        full[..., agent_idx] = a
+        a = full
+    return a.contiguous()
+
+
+def keyed_sums(keys, values):
+    """{key: sum}: `values` are the sums of the keys that are info columns, in order; the others (constant 0 in the reference too) 0.0"""
+    out = {k: 0.0 for k in keys}
+    out.update({k: float(v) for k, v in zip([k for k in keys if k in L.INFO_IDX], values)})
+    return out
 
 
 _INFOS = L.load_infos()        # csrc/sdc_infos.c: InfoSeq (`infos`), InfoView (`infos[i][a]`) -- C types, see there
@@ -399,13 +442,32 @@ class SustainDCVecEnv(ShareVecEnv):
         return share.unsqueeze(1).expand(-1, self.n_agents, -1)
 
     def _sel(self, x):
-        # the trained agents' rows of a [N, 3, ...] array (all of them in the usual three-agent case)
-        return x if self.n_agents == 3 else x[:, self._agent_idx]
+        return sel(x, self._agent_idx)
 
     def _sel_obs(self, obs):
-        # ... of the [N, 3, 26] observation block, cut to the widest trained agent's width
-        o = self._sel(obs)
-        return o if self.obs_width == L.OBS_PAD else o[:, :, :self.obs_width]
+        return sel_obs(obs, self._agent_idx, self.obs_width)
+
+    def _ready(self, who):
+        if self._need_reset:
+            raise ValueError(f"{who}: call reset() first")
+
+    def _reset_layout(self, obs, share):
+        """(obs, share_obs, available_actions) for ALL envs as reset() returns them: the trained agents, either shared-observation layout"""
+        return self._out(self._sel_obs(obs)), self._out(self._share3(share, obs)), (self._avail if self.return_torch else self._avail_np)
+
+    def _host_entries_follow(self, src_rows, dst, const, cfg_id, months):
+        """The host's per-env entries of envs `dst` become entries `src_rows` of const / cfg_id / months (this env's own lists: a clone;
+        a snapshot's: a restore)."""
+        # new lists, not writes into the old ones: the `infos` of earlier steps keep theirs (they describe those steps)
+        new = list(self._const), list(self._cfg_id), list(self.months)
+        for a, b in zip(src_rows.tolist(), dst.tolist()):
+            new[0][b], new[1][b], new[2][b] = const[a], cfg_id[a], months[a]
+        self._const, self._cfg_id, self.months = new
+
+    def _log_step(self, info):
+        if self._logger_acc is not None:      # device-side logger sums: one small reduction per step, no read-back
+            self._logger_acc.add_(info[:, self._logger_idx].sum(0, dtype=self._torch.float64))
+            self._logger_steps += 1
 
     def seed(self, seed: int):
         self.engine.set_seed(seed)
@@ -414,7 +476,7 @@ class SustainDCVecEnv(ShareVecEnv):
     def reset(self):
         obs, share = self.engine.reset()
         self._need_reset = False
-        return self._out(self._sel_obs(obs)), self._out(self._share3(share, obs)), (self._avail if self.return_torch else self._avail_np)
+        return self._reset_layout(obs, share)
 
     def clone_envs(self, src, dst):
         """Env dst[k] becomes an exact copy of env src[k] (copy.deepcopy of the reference's SustainDC, on the device: SdcEngine.clone_envs;
@@ -423,22 +485,16 @@ class SustainDCVecEnv(ShareVecEnv):
         layout -- so a rollout loop can overwrite its observation buffers with them.  The host's per-env entries follow as well: the
         constant info entries of dst's `infos` (its data-centre config is now src's), its config and month.  ValueError for what the
         engine refuses."""
-        if self._need_reset:
-            raise ValueError("clone_envs: call reset() first")
+        self._ready("clone_envs")
         s, d = self.engine.clone_pairs(src, dst)
         obs, share = self.engine.clone_envs(s, d)
-        # new lists, not writes into the old ones: the `infos` of earlier steps keep theirs (they describe those steps)
-        const, cfg_id, months = list(self._const), list(self._cfg_id), list(self.months)
-        for a, b in zip(s.tolist(), d.tolist()):
-            const[b], cfg_id[b], months[b] = self._const[a], self._cfg_id[a], self.months[a]
-        self._const, self._cfg_id, self.months = const, cfg_id, months
-        return self._out(self._sel_obs(obs)), self._out(self._share3(share, obs)), (self._avail if self.return_torch else self._avail_np)
+        self._host_entries_follow(s, d, self._const, self._cfg_id, self.months)
+        return self._reset_layout(obs, share)
 
     def snapshot(self, envs=None):
         """The complete state of envs (default: all) in a device buffer (SdcEngine.snapshot), with the rows' host-side entries: their
         constant info entries, data-centre config and month.  Read-only: the run goes on as without it."""
-        if self._need_reset:
-            raise ValueError("snapshot: call reset() first")
+        self._ready("snapshot")
         snap = self.engine.snapshot(envs)
         ids = snap.envs.tolist()
         snap.extra = {"const": [self._const[i] for i in ids], "cfg_id": [self._cfg_id[i] for i in ids],
@@ -451,26 +507,20 @@ class SustainDCVecEnv(ShareVecEnv):
         Returns (obs, share_obs, available_actions) for ALL envs in reset()'s layout.  The device-side logger accumulator
         (accumulate_logger_sums) is a sum over the batch, not env state: a restore leaves it alone.  ValueError for a snapshot of a vector
         env with other data-centre configs or trace sets, and for what the engine refuses."""
-        if self._need_reset:
-            raise ValueError("restore: call reset() first")
+        self._ready("restore")
         x = snap.extra
         if x.get("cfg_keys") != self._cfg_keys or x.get("loc_keys") != self._loc_keys:
             raise ValueError("restore: the snapshot was not taken from a vector env with these data-centre configs and trace sets")
         r, d = self.engine.restore_pairs(snap, envs, rows)
         obs, share = self.engine.restore(snap, d, r)
-        # new lists, not writes into the old ones: the `infos` of earlier steps keep theirs (they describe those steps)
-        const, cfg_id, months = list(self._const), list(self._cfg_id), list(self.months)
-        for a, b in zip(r.tolist(), d.tolist()):
-            const[b], cfg_id[b], months[b] = x["const"][a], x["cfg_id"][a], x["months"][a]
-        self._const, self._cfg_id, self.months = const, cfg_id, months
-        return self._out(self._sel_obs(obs)), self._out(self._share3(share, obs)), (self._avail if self.return_torch else self._avail_np)
+        self._host_entries_follow(r, d, x["const"], x["cfg_id"], x["months"])
+        return self._reset_layout(obs, share)
 
     def mark(self, envs=None, max_steps: int = 16):
         """Save what the next `max_steps` steps can change in envs (default: all) -- SdcEngine.mark: ~2.3 KB per env for 16 steps against
         a snapshot's ~146 KB.  Read-only: the run goes on as without it.  One live mark per env; a reset of the env (auto-reset
         included), a clone or restore into it kill the mark."""
-        if self._need_reset:
-            raise ValueError("mark: call reset() first")
+        self._ready("mark")
         return self.engine.mark(envs, max_steps)
 
     def rewind(self, mark, envs=None):
@@ -480,11 +530,10 @@ class SustainDCVecEnv(ShareVecEnv):
         the episode and do not change inside it; an `infos` object of an earlier step keeps describing that step.  The device-side
         logger accumulator (accumulate_logger_sums) is NOT rewound: it counts what was stepped, detours included.  ValueError for
         what the engine refuses."""
-        if self._need_reset:
-            raise ValueError("rewind: call reset() first")
+        self._ready("rewind")
         obs, share = self.engine.rewind(mark, envs)
         self._actions = None
-        return self._out(self._sel_obs(obs)), self._out(self._share3(share, obs)), (self._avail if self.return_torch else self._avail_np)
+        return self._reset_layout(obs, share)
 
     def plan(self, actions, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None):
         """Score M candidate action sequences of K steps, pick every env's best, and come back (SdcEngine.plan).  `actions`: an int
@@ -492,8 +541,7 @@ class SustainDCVecEnv(ShareVecEnv):
         (they are played on the device and never read), as step_async does.  -> PlanResult whose `action` [num_envs, n_agents] holds
         the subset's columns, ready for step(); `returns` keeps all three slots.  The run goes on as if the call had not happened;
         actions handed to step_async stay; the envs' live mark is used up.  ValueError for what the engine refuses."""
-        if self._need_reset:
-            raise ValueError("plan: call reset() first")
+        self._ready("plan")
         t = self._torch
         if not (isinstance(actions, t.Tensor) and actions.dim() == 4 and tuple(actions.shape[2:]) == (self.num_envs, self.n_agents)):
             raise ValueError(f"plan: actions must be a tensor of shape (M, K, {self.num_envs}, {self.n_agents})")
@@ -512,15 +560,8 @@ class SustainDCVecEnv(ShareVecEnv):
         return self.engine.plan_terms
 
     def _three_columns(self, actions):
-        """actions [..., n_agents] in this env's agent order -> the engine's contiguous int32 [..., 3] on its device; with an agent
-        subset the other slots' columns are filled with 1"""
-        t = self._torch
-        a = actions.to(device=self.engine.device, dtype=t.int32)
-        if self.n_agents != 3:
-            full = t.ones(tuple(a.shape[:-1]) + (3,), dtype=t.int32, device=self.engine.device)
-            full[..., self._agent_idx] = a
-            a = full
-        return a.contiguous()
+        """`three_columns` of actions [..., n_agents] in this env's agent order"""
+        return three_columns(actions, self._agent_idx, self.engine.device)
 
     def _subset_columns(self, res, *fields):
         """a plan result whose `fields` [..., 3] are narrowed to this env's agent columns"""
@@ -541,8 +582,7 @@ class SustainDCVecEnv(ShareVecEnv):
         and never read) and their probs stay as they are.  -> CEMResult whose `action` [num_envs, n_agents] holds the subset's
         columns, ready for step().  The run goes on as if the call had not happened; the envs' live mark is used up.  ValueError for
         what the engine refuses."""
-        if self._need_reset:
-            raise ValueError("plan_cem: call reset() first")
+        self._ready("plan_cem")
         res = self.engine.plan_cem(horizon, n_iters, n_candidates, n_elite, probs=probs, best_seq=best_seq,
                                    fixed_action=self._subset_fixed(fixed_action), **kw)
         return self._subset_columns(res, "action")
@@ -559,8 +599,7 @@ class SustainDCVecEnv(ShareVecEnv):
         -> GroupCEMResult whose `action` [G, n_agents] and `step_actions` [num_envs, n_agents] hold the subset's columns, the latter
         ready for step().  The run goes on as if the call had not happened; the envs' live mark is used up.  ValueError for what the
         engine refuses."""
-        if self._need_reset:
-            raise ValueError("plan_cem_groups: call reset() first")
+        self._ready("plan_cem_groups")
         res = self.engine.plan_cem_groups(group_size, horizon, n_iters, n_elite, probs=probs, best_seq=best_seq,
                                           fixed_action=self._subset_fixed(fixed_action), **kw)
         return self._subset_columns(res, "action", "step_actions")
@@ -586,8 +625,7 @@ class SustainDCVecEnv(ShareVecEnv):
         calls of step(); actions handed to step_async and not yet stepped are dropped.  THE LOGGER ACCUMULATOR
         (accumulate_logger_sums) IS LEFT ALONE: it counts what went through step(), and these steps did not.  ValueError for what the
         engine refuses."""
-        if self._need_reset:
-            raise ValueError("rollout_stats: call reset() first")
+        self._ready("rollout_stats")
         a = self._stats_actions(actions, n_steps, "rollout_stats")
         if n_steps is not None and int(n_steps) != int(a.shape[0]):
             raise ValueError("rollout_stats: n_steps does not match the action sequence")
@@ -658,14 +696,7 @@ class SustainDCVecEnv(ShareVecEnv):
             actions = pin.to(self.engine.device, non_blocking=True)
             self._act_evt[k].record(t.cuda.current_stream(self.engine.device))
             self._act_rec[k] = True
-        a = actions.reshape(self.num_envs, self.n_agents)
-        if a.dtype != t.int32 or a.device != self.engine.device:
-            a = a.to(device=self.engine.device, dtype=t.int32)
-        if self.n_agents != 3:      # the other slots are played on the device; their columns are never read
-            full = t.ones((self.num_envs, 3), dtype=t.int32, device=self.engine.device)
-            full[:, self._agent_idx] = a
-            a = full
-        self._actions = a.contiguous()
+        self._actions = self._three_columns(actions.reshape(self.num_envs, self.n_agents))
 
     def step_wait(self):
         if self._need_reset:
@@ -688,8 +719,7 @@ class SustainDCVecEnv(ShareVecEnv):
             done_h = hb["done"].numpy().astype(bool)
         extra = {}
         if done_h.any():    # ONE host copy of the pre-reset observations; the per-env entries are built when read
-            extra = _FinalObs(self.engine.final_obs.cpu().numpy(), done_h, self._agent_idx, self.n_agents, self.share_concat,
-                              self.obs_width)
+            extra = final_obs_of(self, self.engine.final_obs.cpu().numpy(), done_h)
         # `infos` (lazy): reads the step's [N, 44] info block on first access -- from the pinned host copy made with the
         # other outputs (NumPy mode: valid for one more step), from the device otherwise.  An access after the block has
         # been overwritten RAISES instead of returning a later step's values; `snapshot_infos=True` makes every infos
@@ -705,9 +735,7 @@ class SustainDCVecEnv(ShareVecEnv):
             infos = LazyInfos(hb["info"], a, done_h, self._const, extra, self, 1, self.n_agents, self._info_keys)   # pinned double buffer: one more step
             if self.snapshot_infos:
                 infos.rows()
-        if self._logger_acc is not None:      # device-side logger sums: one small reduction per step, no read-back
-            self._logger_acc.add_(info[:, self._logger_idx].sum(0, dtype=t.float64))
-            self._logger_steps += 1
+        self._log_step(info)
         k = self.n_agents
         if self.return_torch:
             # the engine's output tensors are persistent, so the shaped views are too (uint8 0/1 -> bool is a reinterpret)
@@ -722,12 +750,9 @@ class SustainDCVecEnv(ShareVecEnv):
             o, r = v[2] if v[2] is not None else (self._sel_obs(obs), self._sel(rew).unsqueeze(-1))
             sh = v[0] if v[0] is not None else self._share3(share, obs)
             return o, sh, r, v[1], infos, self._avail
-        if self.share_concat:
-            sh = self._sel_obs(hb["obs"].numpy()).reshape(self.num_envs, self.share_dim)
-        else:
-            sh = hb["share"].numpy()
-        share3 = np.broadcast_to(sh[:, None, :], (self.num_envs, k, sh.shape[1]))
-        return (self._sel_obs(hb["obs"].numpy()), share3, self._sel(hb["rew"].numpy())[..., None],
+        obs_h = hb["obs"].numpy()
+        share3 = share3_np(hb["share"].numpy(), obs_h, self._agent_idx, self.obs_width, self.share_concat)
+        return (self._sel_obs(obs_h), share3, self._sel(hb["rew"].numpy())[..., None],
                 np.repeat(done_h[:, None], k, axis=1), infos, self._avail_np)
 
     def _launch_into(self, host):
@@ -740,14 +765,9 @@ class SustainDCVecEnv(ShareVecEnv):
         self._actions = None
         e = self.engine
         e.step(a)
-        host["obs"].copy_(e.obs, non_blocking=True)
-        host["share"].copy_(e.share_obs, non_blocking=True)
-        host["rew"].copy_(e.rew, non_blocking=True)
-        host["info"].copy_(e.info, non_blocking=True)
-        host["done"].copy_(e.done, non_blocking=True)
-        if self._logger_acc is not None:
-            self._logger_acc.add_(e.info[:, self._logger_idx].sum(0, dtype=self._torch.float64))
-            self._logger_steps += 1
+        for name, x in (("obs", e.obs), ("share", e.share_obs), ("rew", e.rew), ("info", e.info), ("done", e.done)):
+            host[name].copy_(x, non_blocking=True)
+        self._log_step(e.info)
         return a
 
     def _host_buffers(self):
@@ -757,8 +777,7 @@ class SustainDCVecEnv(ShareVecEnv):
             self._host = []
             for _ in range(2):
                 flat = t.empty(e.out_flat.shape, dtype=t.uint8, pin_memory=True)
-                o, sh, r, d, i = e.split_out_flat(flat)
-                self._host.append({"flat": flat, "obs": o, "share": sh, "rew": r, "done": d, "info": i})
+                self._host.append(dict(A.out_views(flat, e.n_envs), flat=flat))
         self._host_flip ^= 1
         return self._host[self._host_flip]
 
@@ -776,9 +795,7 @@ class SustainDCVecEnv(ShareVecEnv):
         """-> ({key: sum over envs and steps since the last read}, steps accumulated).  ONE device->host copy."""
         if self._logger_acc is None:
             raise RuntimeError("call accumulate_logger_sums() first")
-        vals = self._logger_acc.cpu().numpy()
-        out = {k: 0.0 for k in self._logger_keys}       # keys the env does not track (constant 0 in the reference too)
-        out.update({k: float(v) for k, v in zip([k for k in self._logger_keys if k in L.INFO_IDX], vals)})
+        out = keyed_sums(self._logger_keys, self._logger_acc.cpu().numpy())
         n = self._logger_steps
         if reset:
             self._logger_acc.zero_()
@@ -788,10 +805,7 @@ class SustainDCVecEnv(ShareVecEnv):
     def info_sums(self, keys: Sequence[str] = LOGGER_KEYS):
         """Sum over envs of the given info columns for the last step, computed on the device."""
         idx = [L.INFO_IDX[k] for k in keys if k in L.INFO_IDX]
-        s = self.engine.info[:, idx].sum(0).cpu().numpy()
-        out = {k: 0.0 for k in keys}
-        out.update({k: float(v) for k, v in zip([k for k in keys if k in L.INFO_IDX], s)})
-        return out
+        return keyed_sums(keys, self.engine.info[:, idx].sum(0).cpu().numpy())
 
     def close_extras(self):
         self.engine.close()
