@@ -100,6 +100,44 @@ def check_horizon(who, K, left=None, auto_reset=False):
         raise ValueError(f"{who}: K = {K} steps would run past the end of an episode ({left} steps left)")
 
 
+# ---------------------------------------------------------------------- the plan forecast
+def forecast_modes(who, **channels):
+    """set_plan_forecast's channel arguments (L.FORECAST_CHANNELS: a mode's name, its code, or None = "perfect") -> the four codes in
+    the library's order; ValueError in the caller's name for an unknown channel, name or code"""
+    unknown = sorted(set(channels) - set(L.FORECAST_CHANNELS))
+    if unknown:
+        raise ValueError(f"{who}: {unknown[0]!r} is not a forecast channel {L.FORECAST_CHANNELS}")
+    modes = []
+    for ch in L.FORECAST_CHANNELS:
+        m = channels.get(ch)
+        if m is None:
+            m = L.FORECAST_PERFECT
+        elif isinstance(m, str):
+            if m not in L.FORECAST_MODES:
+                raise ValueError(f"{who}: {ch} = {m!r} is not a forecast mode {tuple(L.FORECAST_MODES)}")
+            m = L.FORECAST_MODES[m]
+        elif isinstance(m, (int, np.integer)) and not isinstance(m, bool):
+            m = int(m)        # (a code outside 0..3 is the library's to refuse)
+        else:
+            raise ValueError(f"{who}: {ch} must be a forecast mode's name {tuple(L.FORECAST_MODES)} or code, got {type(m).__name__}")
+        modes.append(m)
+    return modes
+
+
+def forecast_mode_names(modes):
+    """the four codes -> {channel: mode name}"""
+    names = {v: k for k, v in L.FORECAST_MODES.items()}
+    return {ch: names[int(m)] for ch, m in zip(L.FORECAST_CHANNELS, modes)}
+
+
+def forecast_entries(who, n, left):
+    """ValueError for a count of forecast entries the library would refuse (`left` = steps_to_episode_end())"""
+    if not 1 <= n <= L.MARK_MAX_STEPS + 2:
+        raise ValueError(f"{who}: n = {n} outside [1, MARK_MAX_STEPS + 2 = {L.MARK_MAX_STEPS + 2}]")
+    if n > left + 2:
+        raise ValueError(f"{who}: n = {n} entries reach past the end of an episode ({left} steps left: at most that + 2)")
+
+
 # ---------------------------------------------------------------------- the step's output block
 # the step's outputs are views of ONE device allocation (obs | share_obs | rew | info as floats, then done as bytes), so that a
 # host-side consumer can fetch a whole step with a single device->host copy (`out_flat`)

@@ -23,12 +23,17 @@ ABI_VERSION = 313  # include/sustaindc_hip.h SDC_ABI_VERSION: the struct layouts
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
-           "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip", "sdc_plan_terms.hip"]
+           "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip", "sdc_plan_terms.hip",
+           "sdc_forecast.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
 PLAN_MAX_LIMITS = 8     # include/sustaindc_hip.h SDC_PLAN_MAX_LIMITS: limit entries of sdc_set_plan_terms
 PLAN_MAX_TERMINAL = 8   # include/sustaindc_hip.h SDC_PLAN_MAX_TERMINAL: columns of its terminal term
+# include/sustaindc_hip.h SDC_FORECAST_*: a channel's mode in sdc_set_plan_forecast; the channels in the order of sdc_plan_forecast.mode
+FORECAST_PERFECT, FORECAST_PERSISTENCE, FORECAST_DAILY, FORECAST_VALUES = 0, 1, 2, 3
+FORECAST_MODES = {"perfect": FORECAST_PERFECT, "persistence": FORECAST_PERSISTENCE, "daily": FORECAST_DAILY, "values": FORECAST_VALUES}
+FORECAST_CHANNELS = ("workload", "carbon", "temperature", "wet_bulb")
 # sdc_config.debug_flags: include/sustaindc_hip.h SDC_DEBUG_* (what each bit does is written there; csrc/sdc_dispatch.hpp: which
 # kernel a call lands on under each)
 DEBUG_VERIFY = 1                # public mode: a checking kernel behind every single step
@@ -171,6 +176,11 @@ class SdcPlanTerms(C.Structure):
     ]
 
 
+class SdcPlanForecast(C.Structure):
+    """What the plan calls' rollouts believe the traces ahead are (include/sustaindc_hip.h sdc_plan_forecast)."""
+    _fields_ = [("mode", C.c_int32 * 4), ("values_entries", C.c_int32), ("values", C.c_void_p)]
+
+
 class SdcCemParams(C.Structure):
     """The cross-entropy method's parameters of one sdc_plan_cem call (include/sustaindc_hip.h sdc_cem_params)."""
     _fields_ = [
@@ -197,6 +207,7 @@ EXPORTS = [
     "sdc_snapshot_row_bytes", "sdc_snapshot_envs", "sdc_restore_envs",
     "sdc_mark_row_bytes", "sdc_mark_envs", "sdc_rewind_envs", "sdc_plan", "sdc_plan_cem", "sdc_rollout_stats",
     "sdc_plan_cem_groups", "sdc_set_plan_terms", "sdc_get_plan_terms",
+    "sdc_set_plan_forecast", "sdc_get_plan_forecast", "sdc_forecast_traces",
 ]
 
 
@@ -359,6 +370,9 @@ def load():
                                       fp, fp, vp]
     L.sdc_set_plan_terms.argtypes = [vp, C.POINTER(SdcPlanTerms)]
     L.sdc_get_plan_terms.argtypes = [vp, C.POINTER(SdcPlanTerms)]
+    L.sdc_set_plan_forecast.argtypes = [vp, C.POINTER(SdcPlanForecast)]
+    L.sdc_get_plan_forecast.argtypes = [vp, C.POINTER(SdcPlanForecast)]
+    L.sdc_forecast_traces.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     L.sdc_rollout_stats.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp]
     for name in EXPORTS:
         getattr(L, name)

@@ -118,6 +118,13 @@ def _mpc_horizon(env, horizon):
     return (K if left >= 2 and K >= 1 else 0), eng.config["episode_steps"] - left
 
 
+def _set_forecast(env, forecast):
+    """an MPC agent's `forecast` onto the env's engine: a mode's name for all four channels, or the dict of set_plan_forecast's arguments"""
+    if isinstance(forecast, str):
+        forecast = dict(workload=forecast, carbon=forecast, temperature=forecast, wet_bulb=forecast)
+    env.set_plan_forecast(**forecast)
+
+
 def _do_nothing(env, values):
     """the do-nothing actions `values` (ls, dc, bat) for every env: int32 [N, the env's agent columns] on the env's device"""
     import torch
@@ -135,16 +142,19 @@ class ShootingMPCAgent:
     info_weights: the objective, as `plan` takes it.  The horizon is shortened to what the episode has left (the planner does not look
     across an episode's end); with fewer than two steps left the agent does nothing.  `last`: the latest PlanResult (None after a
     do-nothing fallback), `last_horizon` the horizon it used.  The agent plans through the env, so limits and a terminal term:
-    `env.set_plan_terms`."""
+    `env.set_plan_terms`.  `forecast`: None -- the env's plan forecast is left as it is (none set: perfect foresight, an oracle
+    bound) --, or a mode's name for all four traces ("persistence", "daily"), or a dict of `set_plan_forecast`'s arguments; it is set
+    on the env before the first decision."""
 
     DO_NOTHING = (1, 1, 2)
 
     def __init__(self, n_candidates: int = 8, horizon: int = 8, seed: int = 0, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0,
-                 info_weights=None):
+                 info_weights=None, forecast=None):
         if n_candidates < 1 or horizon < 1:
             raise ValueError("ShootingMPCAgent: n_candidates and horizon must be positive")
         self.n_candidates, self.horizon, self.seed = int(n_candidates), int(horizon), int(seed)
         self.reward_weights, self.gamma, self.info_weights = tuple(reward_weights), float(gamma), info_weights
+        self.forecast = forecast
         self._gen = None
         self.last = None
         self.last_horizon = 0
@@ -158,6 +168,8 @@ class ShootingMPCAgent:
             self.last, self.last_horizon = None, 0
             return nothing
         if self._gen is None:
+            if self.forecast is not None:
+                _set_forecast(env, self.forecast)
             self._gen = torch.Generator(device=eng.device)
             self._gen.manual_seed(self.seed)
         cand = torch.randint(0, 3, (self.n_candidates, K) + tuple(nothing.shape), generator=self._gen, device=eng.device, dtype=torch.int32)
@@ -179,17 +191,20 @@ class CEMMPCAgent:
     seed on twin envs choose the same actions.  The horizon is shortened to what the episode has left (the planner does not look across
     an episode's end); with fewer than two steps left the agent does nothing.  `last`: the latest CEMResult (None after a do-nothing
     fallback), `last_horizon` the horizon it used.  The agent plans through the env, so limits and a terminal term:
-    `env.set_plan_terms`."""
+    `env.set_plan_terms`; `forecast` as ShootingMPCAgent's: set on the env before the first decision."""
 
     DO_NOTHING = (1, 1, 2)
 
     def __init__(self, n_candidates: int = 8, n_elite: int = 2, n_iters: int = 3, horizon: int = 8, seed: int = 0, alpha: float = 0.0,
-                 p_min: float = 0.0, warm_start: bool = True, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None):
+                 p_min: float = 0.0, warm_start: bool = True, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None,
+                 forecast=None):
         if n_candidates < 2 or not 1 <= n_elite <= n_candidates or n_iters < 1 or horizon < 1:
             raise ValueError("CEMMPCAgent: n_candidates >= 2, 1 <= n_elite <= n_candidates, n_iters and horizon positive")
         self.n_candidates, self.n_elite, self.n_iters, self.horizon = int(n_candidates), int(n_elite), int(n_iters), int(horizon)
         self.seed, self.alpha, self.p_min, self.warm_start = int(seed), float(alpha), float(p_min), bool(warm_start)
         self.reward_weights, self.gamma, self.info_weights = tuple(reward_weights), float(gamma), info_weights
+        self.forecast = forecast
+        self._forecast_set = forecast is None
         self.draw = 0
         self.last = None
         self.last_horizon = 0
@@ -217,6 +232,9 @@ class CEMMPCAgent:
     def act(self, env):
         """env: an SdcEngine or a SustainDCVecEnv -> int32 device tensor [N, 3] (the vec env: [N, n_agents], its agents' columns)."""
         K, step = _mpc_horizon(env, self.horizon)
+        if not self._forecast_set:
+            _set_forecast(env, self.forecast)
+            self._forecast_set = True
         self._before(env, step)
         if K == 0:
             self.last, self.last_horizon = None, 0
@@ -251,13 +269,15 @@ class GroupCEMMPCAgent(CEMMPCAgent):
     Replicas draw their own resets (those are keyed on the global env index), so the agent makes every group a copy of its first env
     (`sync_groups`) on its first decision and whenever the episode step has gone backwards (a reset or auto-reset), and starts probs
     and best_seq afresh then.  `last`: the latest GroupCEMResult (None after a do-nothing fallback).  As for CEMMPCAgent, limits and a
-    terminal term: `env.set_plan_terms`."""
+    terminal term: `env.set_plan_terms`, and `forecast` (a "values" forecast must be identical within a group)."""
 
     def __init__(self, group_size: int, n_elite: int = 2, n_iters: int = 3, horizon: int = 8, seed: int = 0, alpha: float = 0.0,
-                 p_min: float = 0.0, warm_start: bool = True, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None):
+                 p_min: float = 0.0, warm_start: bool = True, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None,
+                 forecast=None):
         if group_size < 2 or not 1 <= n_elite <= group_size or n_iters < 1 or horizon < 1:
             raise ValueError("GroupCEMMPCAgent: group_size >= 2, 1 <= n_elite <= group_size, n_iters and horizon positive")
-        super().__init__(int(group_size), n_elite, n_iters, horizon, seed, alpha, p_min, warm_start, reward_weights, gamma, info_weights)
+        super().__init__(int(group_size), n_elite, n_iters, horizon, seed, alpha, p_min, warm_start, reward_weights, gamma, info_weights,
+                         forecast)
         self.group_size = int(group_size)
         self.syncs = 0      # how often the groups have been re-synchronised
 

@@ -28,6 +28,7 @@
 #include "sdc_cem_groups.hpp"
 #include "sdc_plan.hpp"
 #include "sdc_plan_terms.hpp"
+#include "sdc_forecast.hpp"
 #include "sdc_stats.hpp"
 
 namespace {
@@ -136,6 +137,13 @@ struct sdc_handle {
   IdxStage plan_stage{sizeof(double), SDC_MARK_MAX_STEPS};
   // sdc_set_plan_terms: what the plan calls score with next to their objective (both counts 0: nothing set, every field 0)
   sdc_plan_terms plan_terms{};
+  // sdc_set_plan_forecast: what the plan calls' rollouts believe the traces ahead are (every field 0: nothing set); the forecast
+  // [n_steps + 2][N][4] of a plan call and the row bits its overlay replaces (sdc_forecast.hpp), grown on demand and freed with the handle
+  sdc_plan_forecast plan_forecast{};
+  unsigned char* plan_fc = nullptr;
+  size_t plan_fc_bytes = 0;
+  unsigned char* plan_saved = nullptr;
+  size_t plan_saved_bytes = 0;
 };
 
 namespace {
@@ -698,6 +706,8 @@ int sdc_destroy(sdc_handle* h) {
   stage_destroy(h->plan_stage);
   if (h->plan_rows) (void)hipFree(h->plan_rows);
   if (h->plan_out) (void)hipFree(h->plan_out);
+  if (h->plan_fc) (void)hipFree(h->plan_fc);
+  if (h->plan_saved) (void)hipFree(h->plan_saved);
   for (void* p : h->allocs) (void)hipFree(p);
   delete h;
   return 0;
@@ -1730,6 +1740,105 @@ static int plan_grow(unsigned char** buf, size_t* have, const size_t need) {
 // a kernel launch's error -> the call's return code, with the message set
 static int launched(const char* kernel, const hipError_t e) { return e != hipSuccess ? fail(kernel, e) : 0; }
 
+// ---- plan forecast (sdc_forecast.hip) --------------------------------------------------------------------------------------------------
+// Host state of the handle; plan_session overlays it.  The contract: include/sustaindc_hip.h.
+
+// bit c: channel c of the handle's forecast is not PERFECT (0: the plan calls launch what they launch without a forecast)
+static unsigned forecast_channels(const sdc_handle* h) {
+  unsigned m = 0;
+  for (int c = 0; c < SDC_FC_CHANNELS; c++)
+    if (h->plan_forecast.mode[c] != SDC_FORECAST_PERFECT) m |= 1u << c;
+  return m;
+}
+// a VALUES channel of the handle's forecast without n_entries entries to read -> -2 with the message set
+static int forecast_values_refused(const std::string& w, const sdc_handle* h, const int n_entries) {
+  const sdc_plan_forecast& f = h->plan_forecast;
+  for (int c = 0; c < SDC_FC_CHANNELS; c++) {
+    if (f.mode[c] != SDC_FORECAST_VALUES) continue;
+    if (!f.values) return fail_msg(w + "forecast channel " + std::to_string(c) + " is SDC_FORECAST_VALUES and values is null");
+    if (f.values_entries < n_entries)
+      return fail_msg(w + "the forecast's values hold " + std::to_string(f.values_entries) + " entries, " + std::to_string(n_entries) +
+                      " are needed (n_steps + 2 at a plan call)");
+  }
+  return 0;
+}
+// what a plan call of n_steps refuses while a forecast is set
+static int forecast_refused(const std::string& w, const sdc_handle* h, const int n_steps) {
+  if (forecast_channels(h) == 0) return 0;
+  if (!h->d.feat) return fail_msg(w + "this engine has no feature rows (episodes too long for them): the forecast lives in the feature rows");
+  for (int e = 0; e < h->cfg.n_envs && h->mirror.n_feat() != h->cfg.n_envs; e++)      // (the count: no walk while every env's rows are valid)
+    if (!h->mirror.feat(e))
+      return fail_msg(w + "env " + std::to_string(e) +
+                      "'s feature rows are not valid (a host write to its state since its reset): the forecast lives in the feature rows");
+  return forecast_values_refused(w, h, n_steps + 2);
+}
+// the fill kernel's plan for n_entries entries into fc, with the handle's modes or -- truth -- every channel PERFECT
+static SdcForecastFill forecast_fill_plan(const sdc_handle* h, const int n_entries, const bool truth, double* fc) {
+  const sdc_plan_forecast& f = h->plan_forecast;
+  SdcForecastFill F;
+  std::memset(&F, 0, sizeof(F));
+  F.n_envs = h->cfg.n_envs;
+  F.n_entries = n_entries;
+  F.table_len = h->d.table_len;
+  F.lw = h->d.lw;
+  if (!truth) {
+    F.mode_w = f.mode[SDC_FC_W];
+    F.mode_c = f.mode[SDC_FC_C];
+    F.mode_t = f.mode[SDC_FC_T];
+    F.mode_wb = f.mode[SDC_FC_WB];
+    F.values = f.values;
+  }
+  F.rec = h->d.rec;
+  F.tabW = h->d.tabW;
+  F.tabC = h->d.tabC;
+  F.t_win = h->d.t_win;
+  F.wb_win = h->d.wb_win;
+  F.fc = fc;
+  return F;
+}
+
+int sdc_set_plan_forecast(sdc_handle* h, const sdc_plan_forecast* fc) {
+  static const std::string w = "sdc_set_plan_forecast: ";
+  if (!h) return fail_msg(w + "null handle");
+  sdc_plan_forecast f;
+  std::memset(&f, 0, sizeof(f));
+  if (fc) {
+    for (int c = 0; c < SDC_FC_CHANNELS; c++) {
+      if (fc->mode[c] < SDC_FORECAST_PERFECT || fc->mode[c] > SDC_FORECAST_VALUES)
+        return fail_msg(w + "mode[" + std::to_string(c) + "] = " + std::to_string(fc->mode[c]) + " outside [0, 3]");
+      f.mode[c] = fc->mode[c];
+    }
+    if (fc->values_entries < 0) return fail_msg(w + "values_entries = " + std::to_string(fc->values_entries) + " is negative");
+    f.values_entries = fc->values_entries;
+    f.values = fc->values;
+  }
+  h->plan_forecast = f;
+  return 0;
+}
+
+int sdc_get_plan_forecast(const sdc_handle* h, sdc_plan_forecast* out) {
+  if (!h || !out) return fail_msg("sdc_get_plan_forecast: null handle or out");
+  *out = h->plan_forecast;
+  return 0;
+}
+
+int sdc_forecast_traces(sdc_handle* h, int n_entries, int truth, double* out, void* stream) {
+  static const std::string w = "sdc_forecast_traces: ";
+  if (!h) return fail_msg(w + "null handle");
+  if (n_entries < 1 || n_entries > SDC_MARK_MAX_STEPS + 2)
+    return fail_msg(w + "n_entries = " + std::to_string(n_entries) + " outside [1, " + std::to_string(SDC_MARK_MAX_STEPS + 2) + "]");
+  if (!out) return fail_msg(w + "null out");
+  if ((reinterpret_cast<uintptr_t>(out) & 7u) != 0) return fail_msg(w + "out not 8-byte aligned");
+  if (!h->started) return fail_msg(w + "sdc_reset must be called first");
+  if (n_entries > h->mirror.steps_to_terminal() + 2)
+    return fail_msg(w + "n_entries = " + std::to_string(n_entries) + " reaches past the end of an episode (" +
+                    std::to_string(h->mirror.steps_to_terminal()) + " steps left: at most that + 2 entries)");
+  if (!truth && forecast_values_refused(w, h, n_entries)) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  return launched("sdc_forecast_fill_kernel",
+                  sdc_forecast_fill_launch(forecast_fill_plan(h, n_entries, truth != 0, out), reinterpret_cast<hipStream_t>(stream)));
+}
+
 // What every plan call refuses about the horizon, the engine and the objective, in sdc_plan's order (`arrays`: the caller's own null
 // check, reported at its place in that order); obj: the objective with the defaults filled in.  -> 0, or -2 with the message set
 static int plan_refused(const char* who, const sdc_handle* h, const int n_steps, const bool arrays, const float* obs, const float* share_obs,
@@ -1759,7 +1868,7 @@ static int plan_refused(const char* who, const sdc_handle* h, const int n_steps,
     if (obj.col[j] < 0 || obj.col[j] >= SDC_INFO_DIM)
       return fail_msg(w + "info column " + std::to_string(obj.col[j]) + " (entry " + std::to_string(j) + ") outside [0, " +
                       std::to_string(SDC_INFO_DIM) + ")");
-  return 0;
+  return forecast_refused(w, h, n_steps);
 }
 
 // A plan call's horizon, the layout of the handle's output block for it, and the score kernel's plan but for the candidate's own arrays
@@ -1889,6 +1998,24 @@ static int plan_session(sdc_handle* h, const int n_steps, const sdc_plan_objecti
   HIP_TRY(hipSetDevice(h->device));
   PlanSession P{h, {}, nullptr, 0.0, obs, share_obs, stream};
   if (plan_prepare(h, n_steps, obj, P.R)) return -1;
+  // the handle's forecast (sdc_forecast.hpp): behind the mark one fill and one overlay of the rows the rollouts will read, behind the
+  // body -- whatever it returns -- the saved bits back.  Nothing of it with every channel PERFECT
+  const size_t N = (size_t)h->cfg.n_envs;
+  SdcForecastSwap W;
+  std::memset(&W, 0, sizeof(W));
+  W.channels = forecast_channels(h);
+  if (W.channels) {
+    if (plan_grow(&h->plan_fc, &h->plan_fc_bytes, (size_t)(n_steps + 2) * N * SDC_FC_CHANNELS * sizeof(double))) return -1;
+    if (plan_grow(&h->plan_saved, &h->plan_saved_bytes, (size_t)n_steps * N * SDC_FORECAST_SAVED_DWORDS * sizeof(unsigned))) return -1;
+    W.n_envs = (int)N;
+    W.n_steps = n_steps;
+    W.n_rows = h->d.episode_steps + 1;
+    W.units = sdc_forecast_units(W.channels);
+    W.rec = h->d.rec;
+    W.fc = reinterpret_cast<const double*>(h->plan_fc);
+    W.feat = h->d.feat;
+    W.saved = reinterpret_cast<unsigned*>(h->plan_saved);
+  }
   void* pin = nullptr;
   if (stage_acquire(h, h->plan_stage, &pin)) return -1;
   double* const g = static_cast<double*>(pin);
@@ -1899,7 +2026,19 @@ static int plan_session(sdc_handle* h, const int n_steps, const sdc_plan_objecti
   const int staged = stage_commit(h, h->plan_stage, (size_t)n_steps, P.st(), [&](const void* g_dev) {
     P.g_dev = g_dev;
     rc = sdc_mark_envs(h, nullptr, h->cfg.n_envs, n_steps, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
+    bool overlaid = false;
+    if (rc == 0 && W.channels) {
+      rc = launched("sdc_forecast_fill_kernel",
+                    sdc_forecast_fill_launch(forecast_fill_plan(h, n_steps + 2, false, reinterpret_cast<double*>(h->plan_fc)), P.st()));
+      if (rc == 0) rc = launched("sdc_forecast_swap_kernel", sdc_forecast_swap_launch(W, P.st()));
+      overlaid = rc == 0;
+    }
     if (rc == 0) rc = body(P);
+    if (overlaid) {
+      W.back = 1;
+      const int back = launched("sdc_forecast_swap_kernel", sdc_forecast_swap_launch(W, P.st()));
+      if (rc == 0) rc = back;
+    }
     return hipSuccess;
   });
   return rc ? rc : staged;

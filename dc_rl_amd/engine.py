@@ -301,6 +301,7 @@ class SdcEngine:
         self._pinned_stream_obj = None
         self._out_ptrs = None
         self._done_buf = None
+        self._forecast_values = None      # set_plan_forecast's `values`, kept alive while the library holds its address
         with torch.cuda.device(self.device):
             torch.cuda.init()
             L.check(self.lib.sdc_create(C.byref(cfg), C.byref(self._h)))
@@ -718,7 +719,8 @@ class SdcEngine:
         score.  -> PlanResult(best [N], action [N, 3] = actions[best, 0], score [M, N], returns [M, N, 3]).
         The engine -- state, output buffers, closed-loop copy -- is where it was, with `lookahead`'s one difference (the rewinds clear
         the re-centring stamps) and the same price: the call uses up the envs' one live mark, so a mark taken earlier is dead
-        afterwards.  A slot on a built-in policy ignores its action column.  ValueError, with the engine untouched, for malformed
+        afterwards.  A slot on a built-in policy ignores its action column.  The rollouts read the traces of the steps ahead as the
+        episode holds them (perfect foresight) unless a forecast is set: `set_plan_forecast`.  ValueError, with the engine untouched, for malformed
         actions, an unknown info key or too many, and what the library refuses: K > MARK_MAX_STEPS, K >= steps_to_episode_end() with
         auto_reset (> without), no reset() yet, gamma outside (0, 1], verify mode (debug_flags DEBUG_VERIFY: rollouts have none)."""
         t = self.torch
@@ -800,6 +802,79 @@ class SdcEngine:
                 raise ValueError(f"plan_terms: {key!r} is in the terminal term twice: read it with sdc_get_plan_terms")
             terminal[key] = s.terminal_weight[j]
         return {k: tuple(v) for k, v in limits.items()}, terminal
+
+    # ------------------------------------------------------------------ plan forecast
+    def set_plan_forecast(self, workload=None, carbon=None, temperature=None, wet_bulb=None, values=None):
+        """What the rollouts of every later `plan`, `plan_cem` and `plan_cem_groups` believe the traces of the steps ahead are, kept on
+        the engine (sdc_set_plan_forecast) until it is cleared.  Without one the planners have perfect foresight: their rollouts read
+        the real workload, carbon intensity, dry bulb (with the weather noise the episode drew) and wet bulb of the next K steps --
+        an oracle bound, not a controller.  Per channel a mode, by name or code (dc_rl_amd._lib.FORECAST_MODES):
+          "perfect" (or None)  the truth, the channel is left alone;
+          "persistence"        the value at the current step, for the whole horizon;
+          "daily"              the value 96 steps (a day) earlier; the current value now -- and, for temperature / wet_bulb, wherever
+                               a day earlier lies before the episode's start;
+          "values"             `values`: a float64 device tensor [J, n_envs, 4], J >= K + 2, columns (workload, carbon, temperature,
+                               wet_bulb), entry j what the trace is believed to be j steps ahead (j = 0: now).  The engine keeps the
+                               tensor and reads it at every plan call: refresh its contents in place between decisions
+                               (`future_traces(J)` gives the truth to put an error model on).  Not clipped: a workload outside
+                               [0, 1] raises the workload fault in the rollouts, as a step does.
+        `set_plan_forecast(None)` / no arguments / every channel "perfect": cleared, the plan calls launch what they launch without.
+        A plan call overlays the step inputs in the envs' feature rows of the next K steps behind its mark and puts the saved bits
+        back before it returns (three more launches per call); the rows' observation entries stay the truth, so a slot on a built-in
+        rule-based policy keeps reading the true observation features.  Replicas of a group (`plan_cem_groups`) must be given
+        identical `values`.  Host state: nothing is enqueued.  While a forecast is set the plan calls also refuse (ValueError) envs
+        whose feature rows are stale (a set_state since their reset) and `values` with fewer than K + 2 entries.  ValueError, with the
+        forecast set before still in force, for an unknown mode, and "values" without a fitting tensor."""
+        modes = A.forecast_modes("set_plan_forecast", workload=workload, carbon=carbon, temperature=temperature, wet_bulb=wet_bulb)
+        if values is not None:
+            A.device_tensor(values, "set_plan_forecast", "values", self.torch.float64, (A.SOME, self.n_envs, 4), "(J, n_envs, 4)", self.device)
+        self._set_plan_forecast_state(modes, values)
+
+    def _set_plan_forecast_state(self, modes, values):
+        """(the four codes, the values tensor or None) -> the library; the tensor is kept alive for as long as it is set"""
+        s = L.SdcPlanForecast()
+        s.mode[:] = modes
+        if values is not None:
+            s.values_entries, s.values = int(values.shape[0]), values.data_ptr()
+        clear = values is None and not any(modes)
+        self._call(self.lib.sdc_set_plan_forecast, None if clear else C.byref(s), refuses=True)
+        self._forecast_values = values
+
+    def _plan_forecast_state(self):
+        """(codes, values) as the library holds them (what a copy of this engine is given, with `values` cloned)"""
+        s = L.SdcPlanForecast()
+        self._call(self.lib.sdc_get_plan_forecast, C.byref(s), refuses=True)
+        kept = self._forecast_values
+        if (s.values or 0) != (0 if kept is None else kept.data_ptr()):
+            raise ValueError("plan_forecast: the values array was set through the C ABI: read it with sdc_get_plan_forecast")
+        return list(s.mode), kept
+
+    @property
+    def plan_forecast(self):
+        """The forecast in force, read back from the library (sdc_get_plan_forecast) -> the dict of `set_plan_forecast`'s arguments
+        (mode names; `values` the tensor the engine keeps, or None), so that `set_plan_forecast(**e.plan_forecast)` sets the same."""
+        modes, values = self._plan_forecast_state()
+        return dict(A.forecast_mode_names(modes), values=values)
+
+    def _traces(self, who, n, truth):
+        n = int(n)
+        A.forecast_entries(who, n, self.steps_to_episode_end())
+        out = self.torch.empty((n, self.n_envs, 4), dtype=self.torch.float64, device=self.device)
+        self._behind_torch_stream()      # (a "values" tensor the caller has just refreshed with torch ops)
+        self._call(self.lib.sdc_forecast_traces, n, 1 if truth else 0, _p(out), self._stream(), refuses=True,
+                   wrote=(out, self._forecast_values))
+        return out
+
+    def future_traces(self, n: int):
+        """The true traces of the next steps -> float64 device tensor [n, n_envs, 4], columns (workload, carbon, temperature, wet_bulb),
+        entry j the value j steps ahead (j = 0: what the next step reads): what a perfect forecast is, and what a caller's own error
+        model for `set_plan_forecast(values=)` starts from.  n <= steps_to_episode_end() + 2 and MARK_MAX_STEPS + 2 (ValueError)."""
+        return self._traces("future_traces", n, True)
+
+    def forecast_traces(self, n: int):
+        """What the forecast in force (`set_plan_forecast`) gives from the current state: `future_traces`' layout; the same tensor
+        where every channel is "perfect".  A plan call of K steps plans against forecast_traces(K + 2)."""
+        return self._traces("forecast_traces", n, False)
 
     def _cem_fixed(self, who, fixed_action, seed, draw):
         """fixed_action as three ints; the ValueErrors both CEM calls raise first"""

@@ -559,6 +559,27 @@ class SustainDCVecEnv(ShareVecEnv):
         """(limits, terminal) in force (SdcEngine.plan_terms)"""
         return self.engine.plan_terms
 
+    def set_plan_forecast(self, workload=None, carbon=None, temperature=None, wet_bulb=None, values=None):
+        """What every later plan / plan_cem / plan_cem_groups of this env believes the traces ahead are (SdcEngine.set_plan_forecast,
+        which documents the arguments); `set_plan_forecast(None)` or no arguments clears it.  It stays across reset() and goes to a
+        copy.deepcopy of this env, `values` cloned."""
+        self.engine.set_plan_forecast(workload, carbon, temperature, wet_bulb, values)
+
+    @property
+    def plan_forecast(self):
+        """the forecast in force (SdcEngine.plan_forecast)"""
+        return self.engine.plan_forecast
+
+    def future_traces(self, n):
+        """the true traces of the next steps, float64 [n, num_envs, 4] (SdcEngine.future_traces)"""
+        self._ready("future_traces")
+        return self.engine.future_traces(n)
+
+    def forecast_traces(self, n):
+        """what the forecast in force gives from the current state, float64 [n, num_envs, 4] (SdcEngine.forecast_traces)"""
+        self._ready("forecast_traces")
+        return self.engine.forecast_traces(n)
+
     def _three_columns(self, actions):
         """`three_columns` of actions [..., n_agents] in this env's agent order"""
         return three_columns(actions, self._agent_idx, self.engine.device)
@@ -654,6 +675,8 @@ class SustainDCVecEnv(ShareVecEnv):
         of src's, the seed and the host-side state copied.  src not reset yet: nothing to restore."""
         self.engine.set_seed(src.engine.seed)
         self.engine._set_plan_terms_struct(src.engine._plan_terms_struct())
+        modes, values = src.engine._plan_forecast_state()
+        self.engine._set_plan_forecast_state(modes, None if values is None else values.to(self.engine.device, copy=True))
         self.months, self._cfg_id, self._const = list(src.months), list(src._cfg_id), list(src._const)
         if not src._need_reset:
             self.engine.reset()            # (the library restores into envs that have been reset once; every env is overwritten)

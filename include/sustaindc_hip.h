@@ -239,7 +239,8 @@ const char* sdc_last_error(void);
  *   313  sdc_clone_envs
  *        (sdc_snapshot_row_bytes, sdc_snapshot_envs, sdc_restore_envs came later without a bump: new entry points, no layout or
  *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise; sdc_plan, sdc_plan_cem,
- *        sdc_rollout_stats and sdc_plan_cem_groups likewise; sdc_set_plan_terms and sdc_get_plan_terms likewise) */
+ *        sdc_rollout_stats and sdc_plan_cem_groups likewise; sdc_set_plan_terms and sdc_get_plan_terms likewise;
+ *        sdc_set_plan_forecast, sdc_get_plan_forecast and sdc_forecast_traces likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -542,6 +543,50 @@ typedef struct {
 } sdc_plan_terms;
 int sdc_set_plan_terms(sdc_handle* h, const sdc_plan_terms* terms);
 int sdc_get_plan_terms(const sdc_handle* h, sdc_plan_terms* out);
+
+/* PLAN FORECAST: what the plan calls' rollouts believe the traces of the next n_steps steps are.  Without one a plan call's rollouts
+ * read the episode's own feature rows -- the real workload, carbon intensity, dry bulb (with the weather noise the episode drew) and wet
+ * bulb of the steps ahead: perfect foresight, an oracle bound.  A forecast is host state of the handle: sdc_set_plan_forecast copies the
+ * struct (not the array `values` points to), and every later sdc_plan, sdc_plan_cem and sdc_plan_cem_groups call plans against it until it
+ * is cleared (fc NULL); neither call touches the device.  sdc_get_plan_forecast copies out what is set (cleared: every field 0).
+ * With i an env's trace-table index and rel its episode step when the plan call starts, K = n_steps and J = K + 2, the forecast is
+ * fc[j][n][c], fp64, j = 0 .. J - 1, c in (W, C, T, WB) = (workload, carbon intensity, dry bulb, wet bulb): what the planner believes
+ * trace c is at table index i + j.  Each channel has a mode:
+ *   SDC_FORECAST_PERFECT      the truth: W, C = table[loc][clamp(i + j, 0, SDC_TABLE_LEN - 1)]; T, WB = t_win / wb_win[n][rel + j].  The
+ *                             channel's slots are NOT WRITTEN.
+ *   SDC_FORECAST_PERSISTENCE  the truth at j = 0, for every j
+ *   SDC_FORECAST_DAILY        j = 0: the truth; j >= 1: the truth 96 indices earlier (table[clamp(i + j - 96)]; win[rel + j - 96]) --
+ *                             where rel + j < 96, T and WB fall back to persistence (the windows start at the episode's first index)
+ *   SDC_FORECAST_VALUES       values[j][n][c] (device, fp64, [values_entries][N][4]), as given: not clipped (a workload outside [0, 1]
+ *                             raises SDC_FAULT_WORKLOAD in the rollouts, as a step does).  Read at every plan call: the caller
+ *                             refreshes the contents between decisions
+ * Between its mark and its return a plan call OVERLAYS the step inputs in the feature rows rel + 1 .. rel + K of every env (row
+ * rel + 1 + k holds the inputs of the step from episode step rel + k): W, C, T, WB = fc[k]; T1 = (float) fc[k + 1].T;
+ * NCNEXT = (fc[k + 2].C - ci_min) / ci_den from the env's record (an IEEE subtraction, then an IEEE division) -- only the slots of
+ * channels that are not PERFECT -- and puts the saved bits back before it returns, whatever its return code: three more launches per call
+ * (sdc_forecast_fill_kernel, sdc_forecast_swap_kernel twice; csrc/sdc_forecast.hip), none with every channel PERFECT or no forecast
+ * set.  The rows' observation entries stay the truth: a slot on a built-in rule-based policy keeps reading the true observation
+ * features.  Replicas of a group (sdc_plan_cem_groups) get identical rows from the built-in modes by construction; VALUES must be
+ * identical within a group, which is the caller's duty.
+ * sdc_forecast_traces: one launch of the fill kernel alone -> out[j][n][c], j < n_entries: what the handle's forecast gives from the
+ * current state, or the true traces when truth != 0 (how a caller builds VALUES: truth plus its own error model).
+ * Refused (-2 and a message; the forecast set before stays in force): sdc_set_plan_forecast: a null handle, a mode outside 0..3, a
+ * negative values_entries.  sdc_forecast_traces: a null handle or out, n_entries outside [1, SDC_MARK_MAX_STEPS + 2] or above
+ * sdc_steps_to_episode_end() + 2, no reset yet, a VALUES channel (truth == 0) with null values or values_entries < n_entries.  The plan
+ * calls, while a channel is not PERFECT: an engine without feature rows or an env whose rows are not valid (after a host write to its
+ * state), a VALUES channel with null values or values_entries < n_steps + 2. */
+#define SDC_FORECAST_PERFECT 0
+#define SDC_FORECAST_PERSISTENCE 1
+#define SDC_FORECAST_DAILY 2
+#define SDC_FORECAST_VALUES 3
+typedef struct {
+  int32_t mode[4];          /* SDC_FORECAST_* of W, C, T, WB */
+  int32_t values_entries;   /* entries j of `values` (VALUES channels: >= n_steps + 2 at a plan call) */
+  const double* values;     /* [values_entries][N][4] device, or NULL */
+} sdc_plan_forecast;
+int sdc_set_plan_forecast(sdc_handle* h, const sdc_plan_forecast* fc);
+int sdc_get_plan_forecast(const sdc_handle* h, sdc_plan_forecast* out);
+int sdc_forecast_traces(sdc_handle* h, int n_entries, int truth, double* out, void* stream);
 
 /* PLAN WITH THE CROSS-ENTROPY METHOD: n_iters rounds of "sample n_cand candidate sequences from a per-env, per-step, per-agent
  * categorical distribution, score them as sdc_plan does, refit the distribution to the n_elite best and keep the best sequence found so
