@@ -14,6 +14,8 @@ Public surface (mirrors the reference's names for this path):
   * `GroupCEMMPCAgent`, `GroupCEMResult`         -- the same with the samples in env slots: groups of replica envs, one rollout per
                                                       iteration (`SdcEngine.plan_cem_groups`, `sync_groups`)
   * `EpisodeStats`                                 -- per-env episode statistics reduced on the device (`SdcEngine.rollout_stats` / `evaluate`)
+  * `PolicyStats`                                  -- what the in-kernel actors did over those steps: action counts, switches, entropy,
+                                                      log-probability (`SdcEngine.rollout_actor_stats` / `evaluate(actors=True)`)
 
 The compute path is the HIP extension `csrc/libsustaindc_hip.so` (hand-written gfx950 kernels).  There is
 no CPU fallback: constructing an engine without the extension or without an MI355X raises.
@@ -40,6 +42,7 @@ _LAZY = {
     "GroupCEMMPCAgent": ("agents", "GroupCEMMPCAgent"),
     "GroupCEMResult": ("engine", "GroupCEMResult"),
     "EpisodeStats": ("engine", "EpisodeStats"),
+    "PolicyStats": ("engine", "PolicyStats"),
     "RBCBatteryAgent": ("agents", "RBCBatteryAgent"),
     "trim_and_respond_ctrl": ("agents", "trim_and_respond_ctrl"),
 }

@@ -24,7 +24,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
            "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip", "sdc_plan_terms.hip",
-           "sdc_forecast.hip"]
+           "sdc_forecast.hip", "sdc_policy_stats.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
@@ -51,6 +51,10 @@ DEBUG_WIDE_OFF = 4096           # ... never one lane per env
 DEBUG_BOUND_REPAIR = 8192       # test hook: every 61st (env + launch) repairs its clip bounds from the history
 PLAN_DEBUG_TWO_STEPS = 16384    # test hook: sdc_plan's output block holds two steps
 STATS_FIELDS = 4        # include/sustaindc_hip.h SDC_STATS_FIELDS: sum, min, max, count of positive values (enum sdc_stat_field)
+POLICY_COUNTS = 5       # include/sustaindc_hip.h SDC_POLICY_COUNTS: n0, n1, n2, switches, last action (enum sdc_policy_count)
+POLICY_SUMS = 2         # include/sustaindc_hip.h SDC_POLICY_SUMS: log-probability, entropy (enum sdc_policy_sum)
+POLICY_N0, POLICY_N1, POLICY_N2, POLICY_SWITCHES, POLICY_LAST = range(POLICY_COUNTS)
+POLICY_LOGP, POLICY_ENTROPY = range(POLICY_SUMS)
 CEM_MAX_CAND = 64       # include/sustaindc_hip.h SDC_CEM_MAX_CAND: candidates per iteration of sdc_plan_cem
 CEM_MAX_GROUP = 1024    # include/sustaindc_hip.h SDC_CEM_MAX_GROUP: replicas per group of sdc_plan_cem_groups
 CEM_MAX_ITERS = 65536   # ... and its iteration indices: iter0 + n_iters <= this (the index is 16 bits of the generator's counter)
@@ -207,7 +211,7 @@ EXPORTS = [
     "sdc_snapshot_row_bytes", "sdc_snapshot_envs", "sdc_restore_envs",
     "sdc_mark_row_bytes", "sdc_mark_envs", "sdc_rewind_envs", "sdc_plan", "sdc_plan_cem", "sdc_rollout_stats",
     "sdc_plan_cem_groups", "sdc_set_plan_terms", "sdc_get_plan_terms",
-    "sdc_set_plan_forecast", "sdc_get_plan_forecast", "sdc_forecast_traces",
+    "sdc_set_plan_forecast", "sdc_get_plan_forecast", "sdc_forecast_traces", "sdc_rollout_actor_stats",
 ]
 
 
@@ -374,6 +378,7 @@ def load():
     L.sdc_get_plan_forecast.argtypes = [vp, C.POINTER(SdcPlanForecast)]
     L.sdc_forecast_traces.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     L.sdc_rollout_stats.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp]
+    L.sdc_rollout_actor_stats.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

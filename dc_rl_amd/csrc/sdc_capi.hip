@@ -30,6 +30,7 @@
 #include "sdc_plan_terms.hpp"
 #include "sdc_forecast.hpp"
 #include "sdc_stats.hpp"
+#include "sdc_policy_stats.hpp"
 
 namespace {
 
@@ -144,6 +145,9 @@ struct sdc_handle {
   size_t plan_fc_bytes = 0;
   unsigned char* plan_saved = nullptr;
   size_t plan_saved_bytes = 0;
+  // sdc_rollout_actor_stats: a chunk's actions and logits (sdc_policy_stats.hpp), grown on demand and freed with the handle
+  unsigned char* policy_out = nullptr;
+  size_t policy_out_bytes = 0;
 };
 
 namespace {
@@ -708,6 +712,7 @@ int sdc_destroy(sdc_handle* h) {
   if (h->plan_out) (void)hipFree(h->plan_out);
   if (h->plan_fc) (void)hipFree(h->plan_fc);
   if (h->plan_saved) (void)hipFree(h->plan_saved);
+  if (h->policy_out) (void)hipFree(h->policy_out);
   for (void* p : h->allocs) (void)hipFree(p);
   delete h;
   return 0;
@@ -1095,6 +1100,7 @@ int sdc_rollout_actor(sdc_handle* h, int n_steps, int sample, float* obs, float*
   }
   const bool quad = ap.path == SDC_PATH_QUAD;      // four envs per wavefront (batches above 4096 envs)
   const SdcKernelInfo k = sdc_kernel_of(ap.path, SDC_LAUNCH_ACTOR);
+  h->last_step_kernel = k.name;
   hipLaunchKernelGGL(quad ? sdc_rollout_actor_quad_kernel : sdc_rollout_actor_kernel, dim3(sdc_env_blocks(k, N)),
                      dim3(SDC_WAVE * k.waves_per_block), quad ? sdc_rollout_actor_quad_lds_bytes() : sdc_rollout_actor_lds_bytes(), st, d,
                      n_steps, h->mirror.rel_hint(), h->actor_dev, h->obs_latch, sample ? 1 : 0, obs, share_obs, done, info, final_obs, rew,
@@ -1907,24 +1913,31 @@ static int plan_prepare(sdc_handle* h, const int n_steps, const sdc_plan_objecti
   return 0;
 }
 
-// n_steps steps rolled out into the handle's output block (layout B, of `chunk` steps) in chunks, per_chunk(first step, steps) behind each
-// chunk's rollout.  Built from the entry point itself -- sdc_rollout -- so the rollouts choose their kernel as sdc_rollout does and the
-// host's mirror is kept by the code that keeps it for every other caller.  actions [n_steps][N][3], or nullptr (built-in policies)
+// n_steps steps rolled out into the handle's output block (layout B, of `chunk` steps) in chunks: rollout(first step, steps, the block's
+// obs, share_obs, rew, done, info, final_obs) -> rc, then per_chunk(first step, steps) behind it.  The rollout is an entry point itself --
+// sdc_rollout (rollout_of), sdc_rollout_actor (sdc_rollout_actor_stats) -- so the rollouts choose their kernel as that entry point does
+// and the host's mirror is kept by the code that keeps it for every other caller.
 extern "C++" {
-template <class PerChunk>
-static int rollout_chunks(sdc_handle* h, const SdcPlanBlock& B, const int n_steps, const int chunk, const int32_t* actions, void* stream,
-                          PerChunk&& per_chunk) {
-  const size_t N = (size_t)h->cfg.n_envs;
+template <class Rollout, class PerChunk>
+static int rollout_chunks(sdc_handle* h, const SdcPlanBlock& B, const int n_steps, const int chunk, Rollout&& rollout, PerChunk&& per_chunk) {
   unsigned char* const out = h->plan_out;
   int rc = 0;
   for (int k0 = 0; k0 < n_steps && rc == 0; k0 += chunk) {
     const int steps = std::min(chunk, n_steps - k0);
-    rc = sdc_rollout(h, steps, actions ? actions + (size_t)k0 * N * 3 : nullptr, reinterpret_cast<float*>(out + B.obs),
-                     reinterpret_cast<float*>(out + B.share_obs), reinterpret_cast<float*>(out + B.rew), out + B.done,
-                     reinterpret_cast<float*>(out + B.info), reinterpret_cast<float*>(out + B.final_obs), nullptr, stream);
+    rc = rollout(k0, steps, reinterpret_cast<float*>(out + B.obs), reinterpret_cast<float*>(out + B.share_obs),
+                 reinterpret_cast<float*>(out + B.rew), out + B.done, reinterpret_cast<float*>(out + B.info),
+                 reinterpret_cast<float*>(out + B.final_obs));
     if (rc == 0) rc = per_chunk(k0, steps);
   }
   return rc;
+}
+
+// rollout_chunks' rollout for an action sequence: sdc_rollout of actions [n_steps][N][3], or nullptr (built-in policies)
+static auto rollout_of(sdc_handle* h, const int32_t* actions, void* stream) {
+  return [=](const int k0, const int steps, float* obs, float* share_obs, float* rew, uint8_t* done, float* info, float* final_obs) {
+    return sdc_rollout(h, steps, actions ? actions + (size_t)k0 * (size_t)h->cfg.n_envs * 3 : nullptr, obs, share_obs, rew, done, info,
+                       final_obs, nullptr, stream);
+  };
 }
 }  // extern "C++"
 
@@ -1974,7 +1987,7 @@ static int plan_candidates(PlanSession& P, const int n_cand, const int32_t* acti
   for (int c = 0; c < n_cand && rc == 0; c++) {
     S.returns = returns ? returns + (size_t)c * N * 3 : nullptr;
     S.score = score + (size_t)c * N;
-    rc = rollout_chunks(h, P.R.B, P.R.n_steps, P.R.chunk, actions + (size_t)c * (size_t)P.R.n_steps * N * 3, P.stream,
+    rc = rollout_chunks(h, P.R.B, P.R.n_steps, P.R.chunk, rollout_of(h, actions + (size_t)c * (size_t)P.R.n_steps * N * 3, P.stream),
                         [&](const int k0, const int steps) {
                           S.first_step = k0;
                           S.steps = steps;
@@ -2270,47 +2283,64 @@ int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* 
   });
 }
 
-// ---- episode statistics (sdc_stats.hip) ---------------------------------------------------------------------------------------------
-// The contract and the arithmetic: include/sustaindc_hip.h; the kernels' plans and the lane mapping: sdc_stats.hpp.  The rollouts go
-// into the plan calls' output block (plan_out_block, rollout_chunks); nothing is marked or rewound.
-int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int accumulate, double* stats, double* returns,
-                      int32_t* counts, float* obs, float* share_obs, float* rew, uint8_t* done, float* info, float* final_obs,
-                      void* stream) {
-  static const std::string w = "sdc_rollout_stats: ";
+// ---- episode statistics (sdc_stats.hip, sdc_policy_stats.hip) ---------------------------------------------------------------------
+// The contracts and the arithmetic: include/sustaindc_hip.h; the kernels' plans and the lane mappings: sdc_stats.hpp,
+// sdc_policy_stats.hpp.  The rollouts go into the plan calls' output block (plan_out_block, rollout_chunks); nothing is marked or rewound.
+
+// the caller's arrays of sdc_rollout_stats and sdc_rollout_actor_stats
+struct StatsArrays {
+  double *stats, *returns;
+  int32_t* counts;
+  float *obs, *share_obs, *rew;
+  uint8_t* done;
+  float *info, *final_obs;
+};
+
+// What both calls refuse about their arrays and the engine, in sdc_rollout_stats' order, up to verify mode.  -> 0, or -2 with the message set
+static int stats_refused(const std::string& w, const sdc_handle* h, const int n_steps, const int accumulate, const StatsArrays& a) {
   if (!h) return fail_msg(w + "null handle");
   if (n_steps < 1) return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " must be positive");
-  if (!stats || !returns || !counts || !obs || !share_obs) return fail_msg(w + "null array (stats, returns, counts, obs and share_obs are required)");
+  if (!a.stats || !a.returns || !a.counts || !a.obs || !a.share_obs)
+    return fail_msg(w + "null array (stats, returns, counts, obs and share_obs are required)");
   const auto addr = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
-  if (((addr(stats) | addr(returns)) & 15u) != 0) return fail_msg(w + "stats / returns not 16-byte aligned");
-  if (((addr(counts) | addr(obs) | addr(share_obs) | addr(rew) | addr(info) | addr(final_obs)) & 3u) != 0)
+  if (((addr(a.stats) | addr(a.returns)) & 15u) != 0) return fail_msg(w + "stats / returns not 16-byte aligned");
+  if (((addr(a.counts) | addr(a.obs) | addr(a.share_obs) | addr(a.rew) | addr(a.info) | addr(a.final_obs)) & 3u) != 0)
     return fail_msg(w + "counts / obs / share_obs / rew / info / final_obs rows not dword-aligned");
   if (accumulate != 0 && accumulate != 1) return fail_msg(w + "accumulate = " + std::to_string(accumulate) + " outside {0, 1}");
   if (!h->started) return fail_msg(w + "sdc_reset must be called first");
   if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) return fail_msg(w + "verify mode checks single steps (sdc_rollout refuses it as well)");
-  if (!actions && !sdc_all_policies(h->d.policy)) return fail_msg(w + "actions may only be NULL when every agent slot has a policy");
+  return 0;
+}
+// ... and about the episode's end
+static int stats_past_end_refused(const std::string& w, const sdc_handle* h, const int n_steps) {
   if (n_steps > h->mirror.steps_to_terminal())
     return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" +
                     std::to_string(h->mirror.steps_to_terminal()) + " steps left)");
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return 0;
+}
+
+// The chunks of a statistics call, the block (layout B, of `chunk` steps) grown already: rollout (rollout_chunks'), behind each chunk
+// sdc_stats_reduce_kernel and extra(first step, steps, init) -> rc; behind the last chunk sdc_stats_last_kernel
+extern "C++" {
+template <class Rollout, class Extra>
+static int stats_chunks(sdc_handle* h, const SdcPlanBlock& B, const int n_steps, const int chunk, const int accumulate, const StatsArrays& a,
+                        hipStream_t st, Rollout&& rollout, Extra&& extra) {
   const size_t N = (size_t)h->cfg.n_envs;
-  int chunk;
-  SdcPlanBlock B;
-  if (plan_out_block(h, n_steps, chunk, B)) return -1;
   unsigned char* const out = h->plan_out;
   SdcStatsReduce S;
   std::memset(&S, 0, sizeof(S));
   S.n_envs = (int)N;
   S.rew = reinterpret_cast<const float*>(out + B.rew);
   S.info = reinterpret_cast<const float*>(out + B.info);
-  S.stats = stats;
-  S.returns = returns;
-  S.counts = counts;
+  S.stats = a.stats;
+  S.returns = a.returns;
+  S.counts = a.counts;
   int last_steps = 0;
-  const int rc = rollout_chunks(h, B, n_steps, chunk, actions, stream, [&](const int k0, const int steps) {
+  const int rc = rollout_chunks(h, B, n_steps, chunk, rollout, [&](const int k0, const int steps) {
     S.steps = last_steps = steps;
     S.init = (k0 == 0 && accumulate == 0) ? 1 : 0;
-    return launched("sdc_stats_reduce_kernel", sdc_stats_reduce_launch(S, st));
+    const int r = launched("sdc_stats_reduce_kernel", sdc_stats_reduce_launch(S, st));
+    return r ? r : extra(k0, steps, S.init);
   });
   if (rc) return rc;
   const size_t last = (size_t)(last_steps - 1) * N;      // the LAST step's slices of the last chunk
@@ -2323,13 +2353,90 @@ int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int ac
   Q.info = reinterpret_cast<const float*>(out + B.info) + last * SDC_INFO_DIM;
   Q.done = out + B.done + last;
   Q.final_obs = reinterpret_cast<const float*>(out + B.final_obs);
-  Q.o_obs = obs;
-  Q.o_share_obs = share_obs;
-  Q.o_rew = rew;
-  Q.o_info = info;
-  Q.o_done = done;
-  Q.o_final_obs = final_obs;
+  Q.o_obs = a.obs;
+  Q.o_share_obs = a.share_obs;
+  Q.o_rew = a.rew;
+  Q.o_info = a.info;
+  Q.o_done = a.done;
+  Q.o_final_obs = a.final_obs;
   return launched("sdc_stats_last_kernel", sdc_stats_last_launch(Q, st));
+}
+}  // extern "C++"
+
+int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int accumulate, double* stats, double* returns,
+                      int32_t* counts, float* obs, float* share_obs, float* rew, uint8_t* done, float* info, float* final_obs,
+                      void* stream) {
+  static const std::string w = "sdc_rollout_stats: ";
+  const StatsArrays a = {stats, returns, counts, obs, share_obs, rew, done, info, final_obs};
+  if (stats_refused(w, h, n_steps, accumulate, a)) return -2;
+  if (!actions && !sdc_all_policies(h->d.policy)) return fail_msg(w + "actions may only be NULL when every agent slot has a policy");
+  if (stats_past_end_refused(w, h, n_steps)) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  int chunk;
+  SdcPlanBlock B;
+  if (plan_out_block(h, n_steps, chunk, B)) return -1;
+  return stats_chunks(h, B, n_steps, chunk, accumulate, a, reinterpret_cast<hipStream_t>(stream), rollout_of(h, actions, stream),
+                      [](int, int, int) { return 0; });
+}
+
+// What sdc_rollout_actor would refuse about the actors and the batch, asked before anything is enqueued (its own checks stay where they
+// are: every chunk passes them again).  The output arrays are the handle's block's: all there, 256-byte aligned
+static int actor_refused(const std::string& w, const sdc_handle* h) {
+  if (!h->actor_set[0] || !h->actor_set[1] || !h->actor_set[2]) return fail_msg(w + "sdc_set_actor all three agents first");
+  if (h->actor_activation[0] != h->actor_activation[1] || h->actor_activation[0] != h->actor_activation[2])
+    return fail_msg(w + "the three actors must share one activation (the reference builds them from one model config: happo.yaml "
+                        "activation_func)");
+  if (!h->latch_valid)
+    return fail_msg(w + "no observations yet (the actors were set after the last reset / step: reset or step once)");
+  SdcStepFacts f = step_facts(h, true, nullptr, nullptr, nullptr, nullptr, nullptr, false);
+  f.share_obs = f.info = f.actions_out = true;
+  if (sdc_actor_path(f).refused)
+    return fail_msg(w + "needs the common case (lock-step batch with feature rows, one data-centre config of <= 32 racks, "
+                        "external-action slots, default rewards, an even number of envs, no debug flags)");
+  return 0;
+}
+
+int sdc_rollout_actor_stats(sdc_handle* h, int n_steps, int sample, int accumulate, double* stats, double* returns, int32_t* counts,
+                            int32_t* policy_counts, double* policy_sums, float* obs, float* share_obs, float* rew, uint8_t* done,
+                            float* info, float* final_obs, void* stream) {
+  static const std::string w = "sdc_rollout_actor_stats: ";
+  const StatsArrays a = {stats, returns, counts, obs, share_obs, rew, done, info, final_obs};
+  if (stats_refused(w, h, n_steps, accumulate, a)) return -2;
+  if (sample != 0 && sample != 1) return fail_msg(w + "sample = " + std::to_string(sample) + " outside {0, 1}");
+  if ((policy_counts == nullptr) != (policy_sums == nullptr)) return fail_msg(w + "policy_counts and policy_sums are given together or not at all");
+  if ((reinterpret_cast<uintptr_t>(policy_sums) & 15u) != 0) return fail_msg(w + "policy_sums not 16-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(policy_counts) & 3u) != 0) return fail_msg(w + "policy_counts not dword-aligned");
+  if (actor_refused(w, h)) return -2;
+  if (stats_past_end_refused(w, h, n_steps)) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const size_t N = (size_t)h->cfg.n_envs;
+  int chunk;
+  SdcPlanBlock B;
+  if (plan_out_block(h, n_steps, chunk, B)) return -1;
+  const SdcPolicyBlock PB = sdc_policy_block(N, (size_t)chunk);
+  if (plan_grow(&h->policy_out, &h->policy_out_bytes, PB.bytes)) return -1;
+  SdcPolicyStats P;
+  std::memset(&P, 0, sizeof(P));
+  P.n_envs = (int)N;
+  P.actions = reinterpret_cast<const int32_t*>(h->policy_out + PB.actions);
+  P.logits = reinterpret_cast<const float*>(h->policy_out + PB.logits);
+  P.counts = policy_counts;
+  P.sums = policy_sums;
+  int32_t* const actions_out = reinterpret_cast<int32_t*>(h->policy_out + PB.actions);
+  float* const logits_out = reinterpret_cast<float*>(h->policy_out + PB.logits);
+  return stats_chunks(
+      h, B, n_steps, chunk, accumulate, a, st,
+      [=](int, const int steps, float* b_obs, float* b_share_obs, float* b_rew, uint8_t* b_done, float* b_info, float* b_final_obs) {
+        return sdc_rollout_actor(h, steps, sample, b_obs, b_share_obs, b_rew, b_done, b_info, b_final_obs, actions_out,
+                                 policy_counts ? logits_out : nullptr, stream);
+      },
+      [&](int, const int steps, const int init) {
+        if (!policy_counts) return 0;
+        P.steps = steps;
+        P.init = init;
+        return launched("sdc_policy_stats_kernel", sdc_policy_stats_launch(P, st));
+      });
 }
 
 }  // extern "C"

@@ -127,10 +127,11 @@ class EpisodeStats:
     include/sustaindc_hip.h).  `stats` float64 [4, N, 44] -- `sum`, `min`, `max`, `n_pos` (the number of steps with a positive value) are
     its [N, 44] views, one row per env and one column per info key (dc_rl_amd._lib.INFO_COLS) --, `returns` float64 [N, 3] the three
     agents' summed rewards, `counts` int32 [N, 2] with the views `steps` [N] (steps reduced) and `fault` [N] (the OR of the steps'
-    info[fault] bits).  From `evaluate` every tensor has a leading [E] dimension, one entry per episode."""
+    info[fault] bits).  `policy`: the PolicyStats of the same steps from `rollout_actor_stats` / `evaluate(actors=True)`, None from
+    `rollout_stats`.  From `evaluate` every tensor has a leading [E] dimension, one entry per episode."""
 
-    def __init__(self, stats, returns, counts):
-        self.stats, self.returns, self.counts = stats, returns, counts
+    def __init__(self, stats, returns, counts, policy=None):
+        self.stats, self.returns, self.counts, self.policy = stats, returns, counts, policy
 
     sum = property(lambda self: self.stats.select(-3, 0))
     min = property(lambda self: self.stats.select(-3, 1))
@@ -174,6 +175,48 @@ class EpisodeStats:
                     per_env[name], batch[name] = x / n[..., c], bx / n[..., c].sum(axis=-1)
         batch = {k: (float(v) if np.ndim(v) == 0 else np.asarray(v)) for k, v in batch.items()}
         return {"per_env": per_env, "batch": batch, "steps": self.steps.cpu().numpy(), "fault": self.fault.cpu().numpy()}
+
+
+class PolicyStats:
+    """What the three actors did over the steps of an EpisodeStats (sdc_rollout_actor_stats, include/sustaindc_hip.h), per env and agent
+    (ls, dc, bat), on the engine's device: `counts` int32 [N, 3, 5] with the views `action_counts` [N, 3, 3] (steps on which action
+    0 / 1 / 2 was played), `switches` [N, 3] (steps whose action differs from the step before) and `last_action` [N, 3] (-1: no step
+    yet); `sums` float64 [N, 3, 2] with the views `logp` (the summed log-probability of the actions played) and `entropy` (the summed
+    entropy of the distributions they were chosen from).  From `evaluate` every tensor has a leading [E] dimension."""
+
+    def __init__(self, counts, sums):
+        self.counts, self.sums = counts, sums
+
+    action_counts = property(lambda self: self.counts[..., :3])
+    switches = property(lambda self: self.counts[..., L.POLICY_SWITCHES])
+    last_action = property(lambda self: self.counts[..., L.POLICY_LAST])
+    logp = property(lambda self: self.sums[..., L.POLICY_LOGP])
+    entropy = property(lambda self: self.sums[..., L.POLICY_ENTROPY])
+
+    def summary(self) -> dict:
+        """Per-step quantities on the host, fp64: {"per_env": {name: array [N, 3] (or [E, N, 3])}, "batch": {name: array [3] (or
+        [E, 3])}, "steps": array [N, 3]}, the last axis the agents (ls, dc, bat).  With steps = the three action counts' sum:
+          action_frequency  [..., 3 agents, 3 actions] = action_counts / steps;
+          mean_entropy = entropy / steps;   mean_logp = logp / steps;
+          switch_rate = switches / max(steps - 1, 1): the share of step-to-step transitions on which the agent changed its action.
+        Over the batch the same formulas with the sums over the envs (the transitions: the sum of the envs' max(steps - 1, 1)).  A
+        quantity of an (env, agent) that took no step is 0."""
+        n = self.action_counts.cpu().numpy().astype(np.float64)
+        sw = self.switches.cpu().numpy().astype(np.float64)
+        lp, ent = self.logp.cpu().numpy(), self.entropy.cpu().numpy()
+        steps = n.sum(axis=-1)
+        trans = np.maximum(steps - 1.0, 1.0)
+        per_env, batch = {}, {}
+        with np.errstate(divide="ignore", invalid="ignore"):
+            def ratio(x, d):
+                return np.where(d > 0, x / d, 0.0)
+            bsteps = steps.sum(axis=-2)
+            per_env["action_frequency"] = ratio(n, steps[..., None])
+            batch["action_frequency"] = ratio(n.sum(axis=-3), bsteps[..., None])
+            for name, x in (("mean_entropy", ent), ("mean_logp", lp)):
+                per_env[name], batch[name] = ratio(x, steps), ratio(x.sum(axis=-2), bsteps)
+            per_env["switch_rate"], batch["switch_rate"] = sw / trans, sw.sum(axis=-2) / trans.sum(axis=-2)
+        return {"per_env": per_env, "batch": batch, "steps": steps.astype(np.int64)}
 
 
 def _p(x):
@@ -302,6 +345,7 @@ class SdcEngine:
         self._out_ptrs = None
         self._done_buf = None
         self._forecast_values = None      # set_plan_forecast's `values`, kept alive while the library holds its address
+        self._actors = {}                 # set_actor's structs by slot
         with torch.cuda.device(self.device):
             torch.cuda.init()
             L.check(self.lib.sdc_create(C.byref(cfg), C.byref(self._h)))
@@ -504,7 +548,11 @@ class SdcEngine:
         state_dict of the reference's StochasticPolicy (harl/models/policy_models/stochastic_policy.py: keys
         base.feature_norm.*, base.mlp.fc.{0,2,3,5}.*, act.action_out.linear.*; tensors or arrays) or a dict with the
         fields of sdc_actor_params; `activation`: "tanh" (happo.yaml) or "relu"."""
-        self._call(self.lib.sdc_set_actor, int(agent_slot), C.byref(actor_params(params)))
+        self._set_actor_struct(int(agent_slot), actor_params(params))
+
+    def _set_actor_struct(self, slot: int, p: L.SdcActorParams):
+        self._call(self.lib.sdc_set_actor, slot, C.byref(p))
+        self._actors[slot] = p      # (the host copy: what a copy of this engine is given, SustainDCVecEnv._take_state)
 
     def rollout_actor(self, n_steps: int, sample: bool = False, want_logits: bool = False):
         """K env-steps in ONE launch with the three actors (set_actor) choosing every action inside the kernel from the
@@ -996,6 +1044,30 @@ class SdcEngine:
                          sized, sized, f"R = {R}, K = {K}, I = {n_it}, iter0 = {int(iter0)}", n_it, n_elite, probs, best_seq, seed, draw,
                          iter0, alpha, p_min, reward_weights, gamma, info_weights)
 
+    def _stats_into(self, who, into, policy_stats=None):
+        """the EpisodeStats a statistics call fills: a new one, or the caller's `into` checked (ValueError in `who`'s name) -- tensors of
+        this engine's shapes on its device, and a PolicyStats exactly when `policy_stats` (None: rollout_stats, which has none)"""
+        t, N = self.torch, self.n_envs
+        want = ((t.float64, (L.STATS_FIELDS, N, L.INFO_DIM)), (t.float64, (N, L.N_AGENTS)), (t.int32, (N, 2)))     # stats, returns, counts
+        pwant = ((t.int32, (N, L.N_AGENTS, L.POLICY_COUNTS)), (t.float64, (N, L.N_AGENTS, L.POLICY_SUMS)))        # counts, sums
+        new = lambda shapes: [t.empty(sh, dtype=d, device=self.device) for d, sh in shapes]
+        if into is None:
+            return EpisodeStats(*new(want), PolicyStats(*new(pwant)) if policy_stats else None)
+        fits = lambda xs, shapes: all(A.is_tensor(x, d, sh, self.device, cuda=False) for x, (d, sh) in zip(xs, shapes))
+        if not (isinstance(into, EpisodeStats) and fits((into.stats, into.returns, into.counts), want)):
+            raise ValueError(f"{who}: into must be an EpisodeStats of this engine (contiguous tensors on {self.device}: stats "
+                             f"float64 {want[0][1]}, returns float64 {want[1][1]}, counts int32 {want[2][1]})")
+        if policy_stats is not None:
+            pol = into.policy
+            if policy_stats != (pol is not None):
+                raise ValueError(f"{who}: into must carry a PolicyStats exactly when policy_stats is set (policy_stats = "
+                                 f"{bool(policy_stats)}, into.policy is {'given' if pol is not None else 'None'})")
+            if pol is not None and not (isinstance(pol, PolicyStats) and fits((pol.counts, pol.sums), pwant)):
+                raise ValueError(f"{who}: into.policy must be a PolicyStats of this engine (contiguous tensors on {self.device}: counts "
+                                 f"int32 {pwant[0][1]}, sums float64 {pwant[1][1]})")
+        self._behind_torch_stream()      # (its tensors may have been touched on torch's current stream)
+        return into
+
     def rollout_stats(self, actions=None, n_steps: int = None, into: Optional[EpisodeStats] = None) -> EpisodeStats:
         """K env-steps as `rollout` takes them, reduced on the device to per-env statistics (sdc_rollout_stats): the steps' outputs go
         into a block the engine's library owns, in chunks, and one small kernel per chunk folds them into an EpisodeStats -- sum, min,
@@ -1007,42 +1079,62 @@ class SdcEngine:
         bits of one call.  The engine moves; its single-step views (obs, share_obs, rew, done, info, final_obs) follow the last step,
         as after `rollout`.  ValueError, with the engine untouched, for malformed arguments and what the library refuses: K < 1,
         K > steps_to_episode_end(), no reset() yet, verify mode (debug_flags DEBUG_VERIFY)."""
-        t = self.torch
         K = self._sequence_steps("rollout_stats", actions, n_steps, self.device)
-        N = self.n_envs
-        want = ((t.float64, (L.STATS_FIELDS, N, L.INFO_DIM)), (t.float64, (N, L.N_AGENTS)), (t.int32, (N, 2)))     # stats, returns, counts
-        if into is None:
-            res = EpisodeStats(*[t.empty(sh, dtype=d, device=self.device) for d, sh in want])
-        else:
-            res, mine = into, (into.stats, into.returns, into.counts)
-            if not (isinstance(into, EpisodeStats) and all(A.is_tensor(x, d, sh, self.device, cuda=False) for x, (d, sh) in zip(mine, want))):
-                raise ValueError(f"rollout_stats: into must be an EpisodeStats of this engine (contiguous tensors on {self.device}: stats "
-                                 f"float64 {want[0][1]}, returns float64 {want[1][1]}, counts int32 {want[2][1]})")
-            self._behind_torch_stream()      # (its tensors may have been touched on torch's current stream)
+        res = self._stats_into("rollout_stats", into)
         self._call(self.lib.sdc_rollout_stats, K, _p(actions), 0 if into is None else 1, _p(res.stats), _p(res.returns), _p(res.counts),
                    *self._obs_ptrs, _p(self.rew), _p(self.done), _p(self.info), _p(self.final_obs), self._stream(),
                    refuses=True, wrote=(res.stats, res.returns, res.counts, actions))
         return res
 
-    def evaluate(self, n_episodes: int, actions=None) -> EpisodeStats:
+    def rollout_actor_stats(self, n_steps: int, sample: bool = False, into: Optional[EpisodeStats] = None,
+                            policy_stats: bool = True) -> EpisodeStats:
+        """K env-steps as `rollout_actor` takes them -- the three actors (set_actor) choosing every action inside the kernel --, reduced
+        on the device (sdc_rollout_actor_stats): `rollout_stats`' EpisodeStats of the environment's outputs and, in its `policy`, a
+        PolicyStats of what the actors did -- per env and agent how often each action was played, how often it changed from one step to
+        the next, the summed log-probability of the actions played and the summed entropy of the distributions (fp64, in step order; the
+        exact operations: include/sustaindc_hip.h) -- so an evaluation of a trained policy never materialises its 617 + 48 B per
+        env-step.  sample=False: the distributions' mode, True: a draw (the same draws as `rollout_actor`, however the steps are split
+        into calls).  `policy_stats=False` leaves the PolicyStats out (`policy` is None; the logits are not written).  `into`: an
+        EpisodeStats of this engine to continue, carrying a PolicyStats exactly when `policy_stats` is set; calls split anywhere give the
+        bits of one call.  The engine moves; its single-step views follow the last step.  ValueError, with the engine untouched, for
+        malformed arguments and what the library refuses: what `rollout_stats` refuses, an actor not set, actors of different
+        activations, actors set after the last reset / step, a batch `rollout_actor` does not serve."""
+        pol = bool(policy_stats)
+        res = self._stats_into("rollout_actor_stats", into, pol)
+        pc, ps = (res.policy.counts, res.policy.sums) if pol else (None, None)
+        self._call(self.lib.sdc_rollout_actor_stats, int(n_steps), 1 if sample else 0, 0 if into is None else 1, _p(res.stats),
+                   _p(res.returns), _p(res.counts), _p(pc), _p(ps), *self._obs_ptrs, _p(self.rew), _p(self.done), _p(self.info),
+                   _p(self.final_obs), self._stream(), refuses=True, wrote=(res.stats, res.returns, res.counts, pc, ps))
+        return res
+
+    def evaluate(self, n_episodes: int, actions=None, *, actors: bool = False, sample: bool = False) -> EpisodeStats:
         """`n_episodes` whole episodes of the batch, one `rollout_stats` of episode_steps steps each -> an EpisodeStats whose tensors
         carry a leading [E] dimension (stats [E, 4, N, 44], returns [E, N, 3], counts [E, N, 2]).  The batch is reset first; between
         episodes the auto-reset starts the next one (auto_reset off: reset() is called).  actions: None (every slot on a built-in
-        policy), an int32 device tensor [episode_steps, N, 3] replayed every episode, or a callable episode -> such a tensor."""
+        policy), an int32 device tensor [episode_steps, N, 3] replayed every episode, or a callable episode -> such a tensor.
+        `actors=True`: the three actors (set_actor) play instead -- one `rollout_actor_stats` per episode, `sample` as there -- and
+        the result's `policy` is a PolicyStats with the same leading dimension; ValueError together with `actions`."""
         t = self.torch
         E = int(n_episodes)
         if E < 1:
             raise ValueError(f"evaluate: n_episodes = {n_episodes} must be positive")
-        if actions is None and any(p == 0 for p in self.policy):
+        if actors and actions is not None:
+            raise ValueError("evaluate: actors=True plays the actors' own actions: give no actions")
+        if not actors and actions is None and any(p == 0 for p in self.policy):
             raise ValueError("evaluate: actions=None needs a built-in policy on every agent slot")
         self.reset()
         eps = []
         for e in range(E):
             if e > 0 and not self.config["auto_reset"]:
                 self.reset()
-            a = actions(e) if callable(actions) else actions
-            eps.append(self.rollout_stats(a, n_steps=self.episode_steps))
-        return EpisodeStats(t.stack([x.stats for x in eps]), t.stack([x.returns for x in eps]), t.stack([x.counts for x in eps]))
+            if actors:
+                eps.append(self.rollout_actor_stats(self.episode_steps, sample=sample))
+            else:
+                a = actions(e) if callable(actions) else actions
+                eps.append(self.rollout_stats(a, n_steps=self.episode_steps))
+        stack = lambda get: t.stack([get(x) for x in eps])
+        pol = PolicyStats(stack(lambda x: x.policy.counts), stack(lambda x: x.policy.sums)) if actors else None
+        return EpisodeStats(stack(lambda x: x.stats), stack(lambda x: x.returns), stack(lambda x: x.counts), pol)
 
     def profile(self, every: int = 1):
         """Per-kernel HIP-event timing on the launch stream (measurement only): every k-th step, 0 = off."""

@@ -650,25 +650,55 @@ class SustainDCVecEnv(ShareVecEnv):
         a = self._stats_actions(actions, n_steps, "rollout_stats")
         if n_steps is not None and int(n_steps) != int(a.shape[0]):
             raise ValueError("rollout_stats: n_steps does not match the action sequence")
-        res = self.engine.rollout_stats(a, into=into)
+        return self._stats_done(self.engine.rollout_stats(a, into=into))
+
+    def set_actor(self, agent, params):
+        """One agent's actor network for rollout_actor_stats / evaluate(actors=True) (SdcEngine.set_actor, which documents `params`).
+        `agent`: a name ("agent_ls", "agent_dc", "agent_bat") or a slot 0..2.  The actors stay across reset() and go to a copy.deepcopy
+        of this env.  ValueError when this env trains an agent subset: the closed-loop kernel needs all three actors."""
+        if self.n_agents != 3:
+            raise ValueError(f"set_actor: this env trains {self.agents}; the actors run inside the kernel for all three agents only")
+        if isinstance(agent, str):
+            if agent not in AGENTS:
+                raise ValueError(f"set_actor: unknown agent {agent!r}; the environment has {AGENTS}")
+            agent = AGENTS.index(agent)
+        if int(agent) not in (0, 1, 2):
+            raise ValueError(f"set_actor: agent slot {agent} outside 0 (agent_ls), 1 (agent_dc), 2 (agent_bat)")
+        self.engine.set_actor(int(agent), params)
+
+    def _stats_done(self, res):
+        """what every statistics call leaves behind on the host: pending actions dropped, the info buffer holds another step"""
         self._actions = None
         self._gen += 1      # (the engine's info buffer now holds another step: `infos` objects that view it say so)
         return res
 
-    def evaluate(self, n_episodes, actions=None):
+    def rollout_actor_stats(self, n_steps, sample=False, into=None, policy_stats=True):
+        """K env-steps played by the three actors (set_actor) inside the kernel, reduced on the device to an EpisodeStats with a
+        PolicyStats (SdcEngine.rollout_actor_stats, which documents the arguments and the result).  The envs move as under K calls of
+        step(); actions handed to step_async and not yet stepped are dropped; the logger accumulator (accumulate_logger_sums) is left
+        alone, as by rollout_stats.  ValueError for what the engine refuses."""
+        self._ready("rollout_actor_stats")
+        return self._stats_done(self.engine.rollout_actor_stats(n_steps, sample=sample, into=into, policy_stats=policy_stats))
+
+    def evaluate(self, n_episodes, actions=None, *, actors=False, sample=False):
         """`n_episodes` whole episodes of the batch from a reset (SdcEngine.evaluate) -> an EpisodeStats with a leading [E] dimension.
         `actions`: None (do-nothing baseline, see rollout_stats), an int tensor [episode_steps, num_envs, n_agents] replayed every
-        episode, or a callable episode -> such a tensor.  The logger accumulator (accumulate_logger_sums) is left alone.  Afterwards
-        the envs stand at the start of a fresh episode when auto_reset is on; otherwise call reset()."""
+        episode, or a callable episode -> such a tensor.  `actors=True`: the three actors (set_actor) play, by their distributions'
+        mode or -- `sample` -- a draw, and the result carries a PolicyStats; ValueError together with `actions`.  The logger accumulator
+        (accumulate_logger_sums) is left alone.  Afterwards the envs stand at the start of a fresh episode when auto_reset is on;
+        otherwise call reset()."""
         steps = self.episode_steps
-        fixed = None if callable(actions) else self._stats_actions(actions, steps, "evaluate")
-        if fixed is not None and int(fixed.shape[0]) != steps:
-            raise ValueError(f"evaluate: actions must hold episode_steps = {steps} steps, got {int(fixed.shape[0])}")
-        res = self.engine.evaluate(n_episodes, (lambda e: self._stats_actions(actions(e), steps, "evaluate")) if fixed is None else fixed)
-        self._actions = None
-        self._gen += 1
+        if actors:
+            if actions is not None:
+                raise ValueError("evaluate: actors=True plays the actors' own actions: give no actions")
+            res = self.engine.evaluate(n_episodes, actors=True, sample=sample)
+        else:
+            fixed = None if callable(actions) else self._stats_actions(actions, steps, "evaluate")
+            if fixed is not None and int(fixed.shape[0]) != steps:
+                raise ValueError(f"evaluate: actions must hold episode_steps = {steps} steps, got {int(fixed.shape[0])}")
+            res = self.engine.evaluate(n_episodes, (lambda e: self._stats_actions(actions(e), steps, "evaluate")) if fixed is None else fixed)
         self._need_reset = not self.engine.config["auto_reset"]
-        return res
+        return self._stats_done(res)
 
     def _take_state(self, src):
         """This env (built from src's constructor arguments, never stepped) becomes a copy of src: every env restored from a snapshot
@@ -677,6 +707,8 @@ class SustainDCVecEnv(ShareVecEnv):
         self.engine._set_plan_terms_struct(src.engine._plan_terms_struct())
         modes, values = src.engine._plan_forecast_state()
         self.engine._set_plan_forecast_state(modes, None if values is None else values.to(self.engine.device, copy=True))
+        for slot, p in sorted(src.engine._actors.items()):      # (before the reset below: it fills the closed loop's observation copy)
+            self.engine._set_actor_struct(slot, p)
         self.months, self._cfg_id, self._const = list(src.months), list(src._cfg_id), list(src._const)
         if not src._need_reset:
             self.engine.reset()            # (the library restores into envs that have been reset once; every env is overwritten)

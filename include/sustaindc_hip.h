@@ -240,7 +240,7 @@ const char* sdc_last_error(void);
  *        (sdc_snapshot_row_bytes, sdc_snapshot_envs, sdc_restore_envs came later without a bump: new entry points, no layout or
  *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise; sdc_plan, sdc_plan_cem,
  *        sdc_rollout_stats and sdc_plan_cem_groups likewise; sdc_set_plan_terms and sdc_get_plan_terms likewise;
- *        sdc_set_plan_forecast, sdc_get_plan_forecast and sdc_forecast_traces likewise) */
+ *        sdc_set_plan_forecast, sdc_get_plan_forecast and sdc_forecast_traces likewise; sdc_rollout_actor_stats likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -328,7 +328,7 @@ int sdc_steps_to_episode_end(const sdc_handle* h);
  * about episode boundaries (harl/envs/env_wrappers.py:176-190: "original_obs" bookkeeping) without a device->host
  * read.  Returns the number of finished envs; done_host [N] (host, may be NULL) is filled only when it is > 0. */
 int sdc_last_done(const sdc_handle* h, uint8_t* done_host);
-/* name of the kernel the last sdc_step / sdc_rollout launched ("" before the first): the host picks by batch size and configuration
+/* name of the kernel the last sdc_step / sdc_rollout / sdc_rollout_actor launched ("" before the first): the host picks by batch size and configuration
  * between the general kernel, the common-case kernels with two / four envs per wavefront and the lane-per-env kernel of the
  * largest batches (csrc/sdc_dispatch.hpp: the whole decision, and the table of kernels) -- all give the same results; tests and benchmarks name
  * what they measured with this. */
@@ -722,6 +722,45 @@ enum sdc_stat_field { SDC_STAT_SUM = 0, SDC_STAT_MIN, SDC_STAT_MAX, SDC_STAT_NPO
 int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int accumulate, double* stats, double* returns,
                       int32_t* counts, float* obs, float* share_obs, float* rew, uint8_t* done, float* info, float* final_obs,
                       void* stream);
+
+/* POLICY EVALUATION: advance the engine by n_steps env-steps exactly as sdc_rollout_actor(h, n_steps, sample, ...) would -- the call is
+ * made of sdc_rollout_actor calls: the same kernel choice, launch counter, host mirror and observation latch, the same draws for
+ * sample = 1, the auto-reset at the episode's end -- and hand back statistics instead of outputs: sdc_rollout_stats' per-env statistics
+ * of the environment's outputs, and per env and agent what the actors did.  No mark, no rewind: the engine moves.  One call, ordered on
+ * `stream`, no device synchronisation (the handle's buffers are allocated on first use and when they have to grow).  The rollouts write
+ * into the output block the handle owns (sdc_plan's, as for sdc_rollout_stats) in chunks of as many steps as fit, at least one;
+ * debug_flags bit 14 (TEST HOOK): two steps; the chunk's actions and logits go into a second buffer of the handle's, chunk x N x 48
+ * bytes.  After each chunk one launch of sdc_stats_reduce_kernel folds the chunk's info and rew rows into stats / returns / counts and,
+ * when the policy arrays are given, one launch of sdc_policy_stats_kernel (csrc/sdc_policy_stats.hip) folds its actions and logits into
+ * them; after the last chunk sdc_stats_last_kernel fills the caller's single-step arrays as for sdc_rollout_stats.
+ * stats, returns, counts, accumulate and the single-step arrays: sdc_rollout_stats' contract and arithmetic, word for word.
+ * The policy arrays are the device's, and either both or neither is given:
+ *   policy_counts [N][3][SDC_POLICY_COUNTS] int32: per env and agent N0, N1, N2 (steps on which action 0 / 1 / 2 was played), SWITCHES
+ *                 (steps whose action differs from the step before), LAST (the last action; -1: none yet)
+ *   policy_sums   [N][3][SDC_POLICY_SUMS] fp64, 16-byte aligned: LOGP (the summed log-probability of the actions played), ENTROPY (the
+ *                 summed entropy of the distributions they were chosen from)
+ * accumulate == 0:  N0 = N1 = N2 = SWITCHES = 0, LAST = -1, LOGP = ENTROPY = 0.0;  accumulate == 1: continue from what the arrays hold.
+ * Then for k = 0 .. n_steps - 1 in order, per env n and agent a, with j the action and l0, l1, l2 the fp32 logits of that step:
+ *   N_j += 1;   SWITCHES += (LAST >= 0 && j != LAST) ? 1 : 0;   LAST = j
+ *   m = max(l0, l1, l2) in fp32;   z_i = (double)l_i - (double)m;   e_i = exp(z_i);   s = (e0 + e1) + e2;   lse = log(s)
+ *   lp_i = z_i - lse;   p_i = e_i / s
+ *   LOGP += lp_j;   ENTROPY += -((p0 * lp0 + p1 * lp1) + p2 * lp2)
+ * all in fp64 without fused multiply-adds.  Nothing special happens at an episode boundary: a caller who wants per-episode numbers
+ * starts each episode with accumulate == 0.  The results depend neither on the chunking nor on splitting one call into several with
+ * accumulate == 1.
+ * Refused (-2 and a message, nothing enqueued, the engine untouched), all before the first chunk's launch: what sdc_rollout_stats refuses
+ * except what concerns `actions` (a null handle; n_steps < 1; a null stats / returns / counts / obs / share_obs; stats or returns not
+ * 16-byte aligned, another array not dword-aligned; accumulate outside {0, 1}; no sdc_reset yet; verify mode; n_steps >
+ * sdc_steps_to_episode_end()); what sdc_rollout_actor refuses (an actor not set; the three activations not equal; no observations yet;
+ * a batch that is not the common case); sample outside {0, 1}; one policy array without the other; policy_sums not 16-byte aligned;
+ * policy_counts not dword-aligned. */
+#define SDC_POLICY_COUNTS 5
+enum sdc_policy_count { SDC_POLICY_N0 = 0, SDC_POLICY_N1, SDC_POLICY_N2, SDC_POLICY_SWITCHES, SDC_POLICY_LAST };
+#define SDC_POLICY_SUMS 2
+enum sdc_policy_sum { SDC_POLICY_LOGP = 0, SDC_POLICY_ENTROPY };
+int sdc_rollout_actor_stats(sdc_handle* h, int n_steps, int sample, int accumulate, double* stats, double* returns, int32_t* counts,
+                            int32_t* policy_counts, double* policy_sums, float* obs, float* share_obs, float* rew, uint8_t* done,
+                            float* info, float* final_obs, void* stream);
 
 /* Per-kernel timing (measurement only; off by default).  enable = k > 0 samples every k-th sdc_step, 0 switches it
  * off.  In a sampled step one lane per workgroup of each kernel stamps the device's constant-rate wall clock at
