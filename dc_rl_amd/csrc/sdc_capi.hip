@@ -18,6 +18,7 @@
 
 #include "sdc_device.hpp"
 #include "sdc_dispatch.hpp"
+#include "sdc_setup.hpp"
 #include "sdc_kernels.hpp"
 #include "sdc_mirror.hpp"
 #include "sdc_actor.hpp"
@@ -99,20 +100,16 @@ struct sdc_handle {
   bool actor_lds_set = false;   // the closed-loop kernels' dynamic-LDS limit has been raised on this handle's device
   float* obs_latch = nullptr;
   bool latch_valid = false;
-  int racks_cfg0 = 0;                     // racks of data-centre config 0 (the specialised kernels take <= 32: one pass)
   const char* last_step_kernel = "";      // sdc_last_step_kernel
-  int rack_cls_cfg0 = 0;                  // ... and its rack classes (SdcRackClasses; 0: more than the lane-per-env kernel's tables hold)
-  // several data-centre configs: host copies of the configs, from which (and the mirror's assignment) every env's own copy of its
-  // config's scalars is built (SdcDev::prm_env) -- the common-case kernels then serve the batch as they serve one config
+  // what sdc_setup.hpp derives: the sizes of sdc_create; host copies of the configs ([n_dc_configs]; zeros where dc_set is 0) and the
+  // facts about them that sdc_dispatch.hpp asks for, behind the device's copies of their tables (rebuild_config_tables)
+  SdcGeometry geo{};
   std::vector<SdcDcDev> dc_host;
   std::vector<unsigned char> dc_set;
-  double* prm_env_dev = nullptr;
+  SdcConfigFacts facts;
+  double* prm_env_dev = nullptr;          // [N][32] every env's own copy of its config's scalars (several configs: SdcDev::prm_env)
   double* prm_cfg_dev = nullptr;          // [n_dc_configs][32] each config's scalars: what a restore copies into prm_env
-  bool prm_env_ok = false;
-  int racks_max = 0;
-  // the lane-per-env kernel's general form (sdc_wide.hip GEN): one SdcWideCfg per config, when the batch's configs qualify
-  SdcWideCfg* wcfg_dev = nullptr;
-  bool wide_gen_ok = false;
+  SdcWideCfg* wcfg_dev = nullptr;         // [SDC_WIDE_MAX_CFG] the lane-per-env kernel's general form (sdc_wide.hip GEN): one per config
   bool tables_set = false, assigned = false, started = false;
   // optional per-kernel timing: the kernels stamp the device wall clock per workgroup into one slot per sampled step
   int prof = 0;       // sample every `prof`-th step (0 = off)
@@ -173,20 +170,15 @@ int dev_alloc(sdc_handle* h, T** p, size_t count, bool zero = true) {
   return 0;
 }
 
-// one field of every env's record (256-byte state record, or 256-byte header) <-> a dense host array
 // the episode's observation feature rows of the envs a reset kernel has just reset (sdc_features.hip); episodes too long
-// for the kernel's LDS windows go without (the step then computes the features itself)
+// for the kernel's LDS windows go without (the step then computes the features itself); the launch shape is sdc_geometry's
 void launch_features(sdc_handle* h, const SdcDev& d, hipStream_t st) {
-  if (!d.feat) return;
-  const size_t win = sizeof(double) * (size_t)(d.episode_steps + 25 + d.lw), sma = sizeof(double) * (size_t)(d.episode_steps + 22);
-  const size_t tile = sizeof(float) * SDC_WAVE * (SDC_FEAT_ROW + 1), cap = 64 * 1024;
-  // four wavefronts share an env's windows (and the window's moving averages, computed once) where four tiles fit beside them
-  const int waves = win + sma + 4 * tile <= cap ? 4 : 1;
-  const int use_sma = win + sma + waves * tile <= cap ? 1 : 0;
-  hipLaunchKernelGGL(sdc_features_kernel, dim3(d.n_envs), dim3(SDC_WAVE * waves), win + (use_sma ? sma : 0) + waves * tile, st, d, use_sma);
-  (void)h;
+  const SdcGeometry& g = h->geo;
+  if (!g.has_feat) return;
+  hipLaunchKernelGGL(sdc_features_kernel, dim3(d.n_envs), dim3(SDC_WAVE * g.feat_waves), g.feat_lds_bytes, st, d, g.feat_use_sma);
 }
 
+// one field of every env's record (256-byte state record, or 256-byte header) <-> a dense host array
 int rec_put(sdc_handle* h, int idx, int dwords, const void* host, int in_hdr = 0) {
   unsigned* base = in_hdr ? h->d.hdr : h->d.rec;
   const size_t pitch = sizeof(unsigned) * (in_hdr ? SDC_HDR_DWORDS : SDC_REC_DWORDS);
@@ -217,13 +209,13 @@ SdcStepFacts step_facts(const sdc_handle* h, const bool some_actions, const floa
   SdcStepFacts f;
   f.n_envs = h->cfg.n_envs;
   f.n_cfg = d.n_cfg;
-  f.racks_cfg0 = h->racks_cfg0;
-  f.rack_cls_cfg0 = h->rack_cls_cfg0;
-  f.racks_max = h->racks_max;
-  f.prm_env_ok = h->prm_env_ok;
-  f.wide_gen_ok = h->wide_gen_ok;
-  f.has_qcum_t = d.qcum_t != nullptr;
-  f.has_feat = d.feat != nullptr;
+  f.racks_cfg0 = h->facts.racks_cfg0;
+  f.rack_cls_cfg0 = h->facts.rack_cls_cfg0;
+  f.racks_max = h->facts.racks_max;
+  f.prm_env_ok = h->facts.prm_env_ok;
+  f.wide_gen_ok = h->facts.wide_gen_ok;
+  f.has_qcum_t = h->geo.mirrors.qcum_t;
+  f.has_feat = h->geo.has_feat;
   f.n_feat_host = h->mirror.n_feat();
   f.rel_hint = h->mirror.rel_hint();
   for (int a = 0; a < 3; a++) {
@@ -243,89 +235,37 @@ SdcStepFacts step_facts(const sdc_handle* h, const bool some_actions, const floa
 static_assert(SDC_DISPATCH_HIST_MIRROR_MIN_ENVS == SDC_HIST_MIRROR_MIN_ENVS, "sdc_wide_mirrors and the lane-per-env kernel: one threshold");
 static_assert(sdc_kernel_of(SDC_PATH_WIDE, SDC_LAUNCH_SINGLE).envs_per_block == SDC_WAVE, "the lane-per-env kernel: a wavefront of envs per workgroup");
 
-// the largest rack count in use: what the common case (sdc_dispatch.hpp) asks of a batch of several configs (every env has a config that is set: prm_env_ok, or
-// rebuild_prm_env on its way there)
+// a clone or a restore has moved assignments: the largest rack count in use, which the common case (sdc_dispatch.hpp) asks of a batch
+// of several configs
 void refresh_racks_max(sdc_handle* h) {
-  h->racks_max = 0;
-  for (int e = 0; e < h->cfg.n_envs; e++) h->racks_max = std::max(h->racks_max, h->dc_host[(size_t)h->mirror.cfg(e)].p.n_racks);
+  if (h->facts.prm_env_ok) h->facts.racks_max = sdc_racks_max(h->dc_host.data(), h->mirror.cfg_ids(), h->cfg.n_envs);
 }
 
-// several configs: (re)build every env's copy of its config's scalars once all configs and the assignment are known
-int rebuild_prm_env(sdc_handle* h) {
-  h->prm_env_ok = false;
-  h->d.prm_env = nullptr;
+// the configs or the assignment have changed: derive the batch's tables and facts again (sdc_setup.hpp) and upload the tables.  A fact
+// that rests on a table holds once the table is on the device
+int rebuild_config_tables(sdc_handle* h) {
+  SdcDev& d = h->d;
   const int N = h->cfg.n_envs, C = h->cfg.n_dc_configs;
-  if (C <= 1 || !h->mirror.cfg_assigned()) return 0;
-  for (int c = 0; c < C; c++)
-    if (!h->dc_set[c]) return 0;
-  // (the config's scalars lie contiguously from sdc_dc_params::m_cpu to SdcDcDev::ret_sum: sdc_step.hip's P_* enum, asserted there)
-  constexpr size_t P_COUNT_HOST = (offsetof(SdcDcDev, ret_sum) - offsetof(SdcDcDev, p.m_cpu)) / sizeof(double) + 1;
-  static_assert(P_COUNT_HOST <= 32, "prm_env rows are 32 doubles");
-  std::vector<double> tab((size_t)N * 32, 0.0);
-  for (int e = 0; e < N; e++) std::memcpy(&tab[(size_t)e * 32], &h->dc_host[(size_t)h->mirror.cfg(e)].p.m_cpu, sizeof(double) * P_COUNT_HOST);
-  refresh_racks_max(h);
-  if (!h->prm_env_dev && dev_alloc(h, &h->prm_env_dev, (size_t)N * 32) != 0) return -1;
-  HIP_TRY(hipMemcpy(h->prm_env_dev, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
-  std::vector<double> per_cfg((size_t)C * 32, 0.0);      // (the same rows by config: what sdc_restore_envs copies from)
-  for (int c = 0; c < C; c++) std::memcpy(&per_cfg[(size_t)c * 32], &h->dc_host[c].p.m_cpu, sizeof(double) * P_COUNT_HOST);
-  if (!h->prm_cfg_dev && dev_alloc(h, &h->prm_cfg_dev, (size_t)C * 32) != 0) return -1;
-  HIP_TRY(hipMemcpy(h->prm_cfg_dev, per_cfg.data(), sizeof(double) * per_cfg.size(), hipMemcpyHostToDevice));
-  h->d.prm_env = h->prm_env_dev;
-  h->prm_env_ok = true;
-  return 0;
-}
-
-// the lane-per-env kernel's general form: one SdcWideCfg per config, if every config is set, has <= 32 racks in <= SDC_WIDE_MAX_CLS
-// classes, and the scalars the kernel keeps wave-uniform are the same bits in all of them
-int rebuild_wide_cfg(sdc_handle* h) {
-  h->wide_gen_ok = false;
-  h->d.wcfg = nullptr;
-  const int C = h->cfg.n_dc_configs;
-  if (C > SDC_WIDE_MAX_CFG || (int)h->dc_set.size() != C || (int)h->dc_host.size() != C) return 0;
-  for (int c = 0; c < C; c++)
-    if (!h->dc_set[c]) return 0;
-  std::vector<SdcWideCfg> tab((size_t)C);
-  std::memset(tab.data(), 0, sizeof(SdcWideCfg) * tab.size());
-  int max_cls = 0, max_racks = 0;
-  for (int c = 0; c < C; c++) {
-    const SdcDcDev& e = h->dc_host[c];
-    const sdc_dc_params& p = e.p;
-    const SdcDcDev& e0 = h->dc_host[0];
-    // wave-uniform in the kernel (read from config 0): must not differ
-    const double shared_c[] = {p.m_cpu, p.c_cpu, p.rs_cpu, p.m_fan, p.c_fan, p.rs_fan, p.itfan_ref_p, p.itfan_ref_v_ratio, p.it_fan_full_load_v,
-                               p.c_air, p.rho_air, p.crac_supply_pu, p.min_temp, p.max_temp, e.rc_itfan_ref_v_ratio, e.rc_rho_air, e.k_outlet};
-    const sdc_dc_params& p0 = e0.p;
-    const double shared_0[] = {p0.m_cpu, p0.c_cpu, p0.rs_cpu, p0.m_fan, p0.c_fan, p0.rs_fan, p0.itfan_ref_p, p0.itfan_ref_v_ratio, p0.it_fan_full_load_v,
-                               p0.c_air, p0.rho_air, p0.crac_supply_pu, p0.min_temp, p0.max_temp, e0.rc_itfan_ref_v_ratio, e0.rc_rho_air, e0.k_outlet};
-    if (std::memcmp(shared_c, shared_0, sizeof(shared_c)) != 0) return 0;
-    if (p.n_racks > 32) return 0;
-    SdcWideCfg& w = tab[(size_t)c];
-    int n = 0;
-    for (int r = 0; r < p.n_racks; r++) {
-      int k = -1;
-      for (int j = 0; j < n; j++)
-        if (w.cls[j][0] == p.rack_n[r] && w.cls[j][1] == p.rack_supply[r] && w.cls[j][2] == p.rack_full[r] && w.cls[j][3] == p.rack_idle[r]) k = j;
-      if (k < 0) {
-        if (n == SDC_WIDE_MAX_CLS) return 0;
-        k = n++;
-        w.cls[k][0] = p.rack_n[r]; w.cls[k][1] = p.rack_supply[r]; w.cls[k][2] = p.rack_full[r]; w.cls[k][3] = p.rack_idle[r];
-      }
-      w.map[r >> 3] |= (unsigned)k << (4 * (r & 7));
-    }
-    w.n_cls = n;
-    w.n_racks = p.n_racks;
-    w.scal[WC_RET_SUM] = e.ret_sum; w.scal[WC_RC_N_RACKS] = e.rc_n_racks; w.scal[WC_CT_FAN_REF_P] = p.ct_fan_ref_p;
-    w.scal[WC_RC_CTAFR] = e.rc_ctafr; w.scal[WC_BAT_CAP] = p.bat_capacity_mwh; w.scal[WC_RC_BAT_CAP] = e.rc_bat_capacity;
-    max_cls = std::max(max_cls, n);
-    max_racks = std::max(max_racks, p.n_racks);
+  const SdcConfigTables t = sdc_config_tables(h->dc_host.data(), h->dc_set.data(), C, h->mirror.cfg_ids(), N);
+  h->facts = SdcConfigFacts{};
+  d.prm_env = nullptr;
+  d.wcfg = nullptr;
+  if (t.facts.prm_env_ok) {
+    if (!h->prm_env_dev && dev_alloc(h, &h->prm_env_dev, (size_t)N * SDC_PRM_ROW) != 0) return -1;
+    HIP_TRY(hipMemcpy(h->prm_env_dev, t.prm_env.data(), sizeof(double) * t.prm_env.size(), hipMemcpyHostToDevice));
+    if (!h->prm_cfg_dev && dev_alloc(h, &h->prm_cfg_dev, (size_t)C * SDC_PRM_ROW) != 0) return -1;
+    HIP_TRY(hipMemcpy(h->prm_cfg_dev, t.prm_cfg.data(), sizeof(double) * t.prm_cfg.size(), hipMemcpyHostToDevice));
+    d.prm_env = h->prm_env_dev;
   }
-  if (!h->wcfg_dev && dev_alloc(h, &h->wcfg_dev, (size_t)SDC_WIDE_MAX_CFG) != 0) return -1;
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->wcfg_dev, tab.data(), sizeof(SdcWideCfg) * tab.size(), hipMemcpyHostToDevice));
-  h->d.wcfg = h->wcfg_dev;
-  h->d.wide_max_cls = max_cls;
-  h->d.wide_max_racks4 = (max_racks + 3) / 4 * 4;
-  h->wide_gen_ok = true;
+  if (t.facts.wide_gen_ok) {
+    if (!h->wcfg_dev && dev_alloc(h, &h->wcfg_dev, (size_t)SDC_WIDE_MAX_CFG) != 0) return -1;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(h->wcfg_dev, t.wide.data(), sizeof(SdcWideCfg) * t.wide.size(), hipMemcpyHostToDevice));
+    d.wcfg = h->wcfg_dev;
+    d.wide_max_cls = t.wide_max_cls;
+    d.wide_max_racks4 = t.wide_max_racks4;
+  }
+  h->facts = t.facts;
   return 0;
 }
 
@@ -529,15 +469,8 @@ uint32_t sdc_state_layout(void) { return state_layout_hash(); }
 
 int sdc_create(const sdc_config* cfg, sdc_handle** out) {
   if (!cfg || !out) return fail_msg("sdc_create: null argument");
-  if (cfg->n_envs <= 0) return fail_msg("sdc_create: n_envs must be > 0");
-  if (cfg->episode_steps <= 0) return fail_msg("sdc_create: episode_steps must be > 0");
-  if (cfg->hist_cap < 2 || cfg->hist_cap > SDC_HIST_STRIDE)
-    return fail_msg("sdc_create: hist_cap must be in [2, 10240]");
-  if (cfg->n_locations <= 0 || cfg->n_dc_configs <= 0) return fail_msg("sdc_create: need >= 1 location and dc config");
-  if (cfg->env_index_base < 0) return fail_msg("sdc_create: env_index_base must be >= 0");
-  if (cfg->queue_max_len <= 0 || cfg->queue_max_len > 65535) return fail_msg("sdc_create: bad queue_max_len");
-  if ((long long)cfg->episode_steps * 20 > 0x7FFFFFFFLL / cfg->episode_steps)
-    return fail_msg("sdc_create: episode too long for the 32-bit queue prefix sums");
+  const SdcRefusal refusal = sdc_check_config(*cfg);      // (sdc_setup.hpp: every check that needs no device)
+  if (refusal.msg && !refusal.after_device) return fail_msg(refusal.msg);
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (cfg->device < 0 || cfg->device >= ndev) return fail_msg("sdc_create: no such HIP device");
@@ -546,9 +479,13 @@ int sdc_create(const sdc_config* cfg, sdc_handle** out) {
   HIP_TRY(hipGetDeviceProperties(&prop, cfg->device));
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail_msg(std::string("sdc_create: built for gfx950 (MI355X) only, device is ") + prop.gcnArchName);
+  if (refusal.msg) return fail_msg(refusal.msg);
 
   sdc_handle* h = new sdc_handle();
   h->cfg = *cfg;
+  const SdcGeometry& g = h->geo = sdc_geometry(*cfg);
+  h->dc_host.assign((size_t)cfg->n_dc_configs, SdcDcDev{});      // (a config that is never set: zeros, like the device's copy)
+  h->dc_set.assign((size_t)cfg->n_dc_configs, 0);
   if (cfg->debug_flags & SDC_DEBUG_STEP_NO_ENV)   // test hook (tests of the launch counter's wrap): start the counter where the environment says
     if (const char* t = std::getenv("SDC_TEST_STEP_NO")) h->step_no = std::atoi(t) % STEP_WRAP;
   h->device = cfg->device;
@@ -565,27 +502,14 @@ int sdc_create(const sdc_config* cfg, sdc_handle** out) {
   d.hist_cap_d = (double)cfg->hist_cap;
   d.table_len = SDC_TABLE_LEN;
   static_assert(SDC_TABLE_LEN % 8 == 0, "sdc_reset_kernel: a lane's 8 samples of the year's walk are all inside the table or all outside");
-  d.lw = cfg->episode_steps + 18;
-  d.qstride = (cfg->episode_steps + 63) / 64 * 64;
+  d.lw = g.lw;
+  d.qstride = g.qstride;
   d.max_roll_days = cfg->max_roll_days;
   d.debug_flags = cfg->debug_flags & ~SDC_PLAN_DEBUG_TWO_STEPS;      // (sdc_plan's test hook: read from h->cfg by that call alone)
   d.env_base = cfg->env_index_base;
   for (int a = 0; a < 3; a++) {
-    if (cfg->reward_method[a] < 0 || cfg->reward_method[a] > SDC_REWARD_WATER) {
-      sdc_destroy(h);
-      return fail_msg("sdc_create: unknown reward_method");
-    }
     d.reward_method[a] = cfg->reward_method[a];
-  }
-  for (int a = 0; a < 3; a++) {
-    const int pol = cfg->policy[a];
-    const bool ok = pol == SDC_POLICY_EXTERNAL || pol == SDC_POLICY_DO_NOTHING || (a == 2 && pol == SDC_POLICY_RBC) ||
-                    (a == 1 && pol == SDC_POLICY_TRIM_AND_RESPOND);
-    if (!ok) {
-      sdc_destroy(h);
-      return fail_msg("sdc_create: policy must be EXTERNAL or DO_NOTHING, RBC for the battery slot, TRIM_AND_RESPOND for the dc slot");
-    }
-    d.policy[a] = pol;
+    d.policy[a] = cfg->policy[a];
   }
   d.tr_limit = cfg->trim_and_respond_limit;
   d.actions_out = nullptr;
@@ -613,10 +537,10 @@ int sdc_create(const sdc_config* cfg, sdc_handle** out) {
   A(d.qtab, (size_t)N * d.qstride);
   d.qcum_t = nullptr;
   d.hist_t = nullptr;
-  if (const SdcWideMirrors mirrors = sdc_wide_mirrors(N, cfg->debug_flags); mirrors.qcum_t) {      // (batches the lane-per-env kernel can serve)
+  if (g.mirrors.qcum_t) {      // (batches the lane-per-env kernel can serve)
     // ... and BEHIND it, in the same allocation, the history ring's slot-major mirror for the batches that get one (rows qstride ..
     // qstride + hist_cap of the same [row][N] array: the lane-per-env kernel addresses it from the pointer and the strides it holds anyway)
-    const bool mirror = mirrors.hist_t;
+    const bool mirror = g.mirrors.hist_t;
     A(d.qcum_t, (size_t)N * ((size_t)d.qstride + (mirror ? (size_t)d.hist_cap : 0)));      // (zeroed by the allocation)
     if (mirror) {
       d.hist_t = d.qcum_t + (size_t)N * d.qstride;
@@ -636,12 +560,10 @@ int sdc_create(const sdc_config* cfg, sdc_handle** out) {
   A(d.hdr, (size_t)N * SDC_HDR_DWORDS);
   A(d.qwin, (size_t)N * (4 * SDC_WIN));
   d.feat = nullptr;
-  if (sizeof(double) * (size_t)(cfg->episode_steps + 25 + d.lw) <= 50 * 1024)   // the features kernel's LDS windows (+ 8.4 KB tile per wavefront)
-    A(d.feat, (size_t)N * (size_t)(cfg->episode_steps + 1) * SDC_FEAT_ROW);
+  if (g.has_feat) A(d.feat, (size_t)N * (size_t)(cfg->episode_steps + 1) * SDC_FEAT_ROW);
   A(d.rq_count, 4);
-  // deferred re-centring capacity by batch size (sdc_device.hpp): ~26 requests per step and 4096 envs on average
-  d.rq_max = std::min((int)SDC_RQ_LIMIT, std::max((int)SDC_RQ_MIN, (N / 32 + 127) / 128 * 128));
-  d.sweep_blocks = std::min(128, std::max(32, N / 128));   // four wavefronts each; a workgroup serves requests b, b + sweep_blocks, ...
+  d.rq_max = g.rq_max;      // deferred re-centring capacity by batch size
+  d.sweep_blocks = g.sweep_blocks;
   A(d.rq, 3 * (size_t)d.rq_max);
   A(d.rs, 3 * (size_t)d.rq_max);
   A(d.reset_mask, N);
@@ -664,7 +586,7 @@ int sdc_create(const sdc_config* cfg, sdc_handle** out) {
       return fail_msg("sdc_create: hour LUT upload failed");
     }
   }
-  h->mirror = SdcHostMirror(N, cfg->episode_steps, d.feat != nullptr);      // every env "finished": a reset is required before stepping
+  h->mirror = SdcHostMirror(N, cfg->episode_steps, g.has_feat);      // every env "finished": a reset is required before stepping
   h->fields = {
       {"cursor", nullptr, 4, R_CURSOR, 1}, {"t_rel", nullptr, 4, R_TREL, 1}, {"day", nullptr, 4, R_DAY, 1},
       {"hourq", nullptr, 4, R_HOURQ, 1}, {"q_popped", nullptr, 4, R_QPOPPED, 1}, {"q_cum", nullptr, 4, R_QCUM, 1},
@@ -748,85 +670,14 @@ int sdc_set_tables(sdc_handle* h, int loc_id, const double* W, const double* C, 
 int sdc_set_dc_params(sdc_handle* h, int cfg_id, const sdc_dc_params* p) {
   if (!h || !p) return fail_msg("sdc_set_dc_params: null argument");
   if (cfg_id < 0 || cfg_id >= h->cfg.n_dc_configs) return fail_msg("sdc_set_dc_params: cfg_id out of range");
-  if (p->n_racks <= 0 || p->n_racks > SDC_MAX_RACKS) return fail_msg("sdc_set_dc_params: n_racks must be in [1, 64]");
-  HIP_TRY(hipSetDevice(h->device));
-  // reciprocals for the kernels' 3-instruction divisions: exact unless a divisor's significand is all ones
   SdcDcDev e;
-  e.p = *p;
-  const double divisors[5] = {(double)p->n_racks, p->itfan_ref_v_ratio, p->rho_air, p->ctafr, p->bat_capacity_mwh};
-  double* rcs[5] = {&e.rc_n_racks, &e.rc_itfan_ref_v_ratio, &e.rc_rho_air, &e.rc_ctafr, &e.rc_bat_capacity};
-  for (int i = 0; i < 5; i++) {
-    unsigned long long bits;
-    std::memcpy(&bits, &divisors[i], 8);
-    if (!(divisors[i] > 0) || !std::isfinite(divisors[i]) || (bits & 0xFFFFFFFFFFFFFull) == 0xFFFFFFFFFFFFFull)
-      return fail_msg("sdc_set_dc_params: n_racks, itfan_ref_v_ratio, rho_air, ctafr and bat_capacity_mwh must be "
-                      "positive, finite, and not have an all-ones significand");
-    *rcs[i] = 1.0 / divisors[i];
-  }
-  e.k_outlet = 1.918 / (p->c_air * p->rho_air * 0.526);
-  e.n_racks_f = (double)p->n_racks;
-  e.ret_sum = 0.0;
-  for (int r = 0; r < p->n_racks; r++) e.ret_sum += p->rack_return[r];
-  // rack classes: distinct (cpus, full, idle, supply) tuples in order of first appearance, grouped by (cpus, supply)
-  {
-    SdcRackClasses& rc = e.rc;
-    std::memset(&rc, 0, sizeof(rc));
-    struct Cls { double n, full, idle, supply; int grp; };
-    std::vector<Cls> cls;
-    std::vector<std::pair<double, double>> grp;
-    std::vector<int> of_rack((size_t)p->n_racks, 0);
-    bool fits = p->n_racks <= 32;
-    for (int r = 0; r < p->n_racks && fits; r++) {
-      const Cls c = {p->rack_n[r], p->rack_full[r], p->rack_idle[r], p->rack_supply[r], 0};
-      int k = -1;
-      for (size_t j = 0; j < cls.size(); j++)
-        if (cls[j].n == c.n && cls[j].full == c.full && cls[j].idle == c.idle && cls[j].supply == c.supply) k = (int)j;
-      if (k < 0) {
-        int g = -1;
-        for (size_t j = 0; j < grp.size(); j++)
-          if (grp[j].first == c.n && grp[j].second == c.supply) g = (int)j;
-        if (g < 0) { g = (int)grp.size(); grp.push_back({c.n, c.supply}); }
-        k = (int)cls.size();
-        cls.push_back(c);
-        cls.back().grp = g;
-      }
-      of_rack[(size_t)r] = k;
-      if (cls.size() > SDC_MAX_RACK_CLS) fits = false;
-    }
-    if (fits) {
-      // renumber the classes group by group
-      std::vector<int> renum(cls.size(), 0);
-      int next = 0;
-      rc.n_grp = (int)grp.size();
-      for (int g = 0; g < rc.n_grp; g++) {
-        rc.grp_begin[g] = next;
-        rc.grp_n[g] = grp[(size_t)g].first;
-        rc.grp_supply[g] = grp[(size_t)g].second;
-        for (size_t j = 0; j < cls.size(); j++)
-          if (cls[j].grp == g) {
-            renum[j] = next;
-            rc.cls_full[next] = cls[j].full;
-            rc.cls_idle[next] = cls[j].idle;
-            next++;
-          }
-      }
-      rc.grp_begin[rc.n_grp] = next;
-      rc.n_cls = next;
-      for (int r = 0; r < p->n_racks; r++) rc.cls_of_rack[r] = renum[(size_t)of_rack[(size_t)r]];
-    }
-  }
+  if (const char* refused = sdc_derive_dc(*p, e)) return fail_msg(refused);      // (sdc_setup.hpp: reciprocals, rack classes)
+  HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(const_cast<SdcDcDev*>(h->d.dc) + cfg_id, &e, sizeof(e), hipMemcpyHostToDevice));
-  if (cfg_id == 0) {
-    h->racks_cfg0 = p->n_racks;
-    h->rack_cls_cfg0 = e.rc.n_cls;
-  }
-  h->dc_host.resize((size_t)h->cfg.n_dc_configs);
-  h->dc_set.resize((size_t)h->cfg.n_dc_configs, 0);
   h->dc_host[cfg_id] = e;
   h->dc_set[cfg_id] = 1;
-  if (rebuild_prm_env(h)) return -1;
-  return rebuild_wide_cfg(h);
+  return rebuild_config_tables(h);
 }
 
 int sdc_assign_envs(sdc_handle* h, const int32_t* loc_id, const int32_t* cfg_id, const int32_t* day_lo,
@@ -845,18 +696,14 @@ int sdc_assign_envs(sdc_handle* h, const int32_t* loc_id, const int32_t* cfg_id,
     return -1;
   // the CRAC set-point starts at the config's initial value (make_envs_pyenv.py:124) and is never reset
   if (!h->started) {
-    std::vector<SdcDcDev> ps(h->cfg.n_dc_configs);
-    HIP_TRY(hipMemcpy(ps.data(), h->d.dc, sizeof(SdcDcDev) * ps.size(), hipMemcpyDeviceToHost));
     std::vector<double> st(N);
-    for (int e = 0; e < N; e++) st[e] = ps[cfg_id[e]].p.init_setpoint;
+    for (int e = 0; e < N; e++) st[e] = h->dc_host[(size_t)cfg_id[e]].p.init_setpoint;      // (a config not set yet: 0.0)
     if (rec_put(h, R_STPT, 2, st.data())) return -1;
   }
   h->assigned = true;
   h->mirror.set_cfg_ids(cfg_id);
   h->mirror.set_loc_ids(loc_id);
-  h->dc_set.resize((size_t)h->cfg.n_dc_configs, 0);
-  if (rebuild_prm_env(h)) return -1;
-  return rebuild_wide_cfg(h);
+  return rebuild_config_tables(h);
 }
 
 int sdc_reset(sdc_handle* h, const uint8_t* mask_host, const sdc_reset_override* ovr, float* obs, float* share_obs,
@@ -1245,7 +1092,7 @@ int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t
     if (is_cfg || is_record) {
       if (is_cfg) h->mirror.set_cfg_ids(ids);
       else h->mirror.set_cfg_ids(ids + R_CFG, SDC_REC_DWORDS);
-      if (rebuild_prm_env(h)) return -1;
+      if (rebuild_config_tables(h)) return -1;
     }
   }
   if (std::strcmp(field, "loc_id") == 0) h->mirror.set_loc_ids(ids);
@@ -1343,7 +1190,7 @@ int sdc_clone_envs(sdc_handle* h, const int32_t* src, const int32_t* dst, int n,
     return -1;
 
   h->mirror.copy_envs(src, dst, n);
-  if (h->prm_env_ok) refresh_racks_max(h);
+  refresh_racks_max(h);
   return 0;
 }
 
@@ -1540,7 +1387,7 @@ int sdc_restore_envs(sdc_handle* h, const int32_t* rows_idx, const int32_t* envs
     facts.push_back({x.x, m[SDC_SNAP_T_REL], m[SDC_SNAP_FEAT_OK] != 0, m[SDC_SNAP_CFG_ID], m[SDC_SNAP_LOC_ID]});
   }
   h->mirror.replace_envs(facts.data(), facts.size());
-  if (h->prm_env_ok) refresh_racks_max(h);
+  refresh_racks_max(h);
   return 0;
 }
 

@@ -19,11 +19,8 @@
 #include <stdint.h>
 
 #include "../../include/sustaindc_hip.h"
+#include "sdc_setup.hpp"   // SdcDcDev, SdcRackClasses, SdcWideCfg and the sizes the host derives: defined HIP-free, next to their derivation
 
-#define SDC_BLOCK 256
-#define SDC_WAVE 64
-#define SDC_HIST_PER_THREAD 40  // 10 x float4 per thread -> 10240 ring slots per env
-#define SDC_HIST_STRIDE (SDC_BLOCK * SDC_HIST_PER_THREAD)
 #define SDC_NORM_WINDOW 2880    // 30 days x 96 (utils/managers.py:435, :606)
 #define SDC_OBS_RAW 53
 #define SDC_OBS_OUT (SDC_N_AGENTS * SDC_OBS_PAD)
@@ -123,55 +120,6 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-#define SDC_MAX_RACK_CLS 8     // rack classes (and groups) the lane-per-env kernel keeps tables for
-// (128 dwords: a wavefront holds the table in two registers, dword j in lane j % 64, and reads entries with v_readlane; the
-// doubles fill the first 64 dwords, the integers the second)
-struct SdcRackClasses {
-  double grp_n[SDC_MAX_RACK_CLS], grp_supply[SDC_MAX_RACK_CLS];     // group g: racks of grp_n cpus with supply approach grp_supply
-  double cls_full[SDC_MAX_RACK_CLS], cls_idle[SDC_MAX_RACK_CLS];    // class c (of group g: grp_begin[g] <= c < grp_begin[g + 1])
-  int n_grp, n_cls;
-  int grp_begin[SDC_MAX_RACK_CLS + 1];
-  int cls_of_rack[32];                                               // rack slot -> class
-  int pad[21];
-};
-static_assert(sizeof(SdcRackClasses) == 512 && SDC_MAX_RACK_CLS == 8, "two registers of a wavefront hold the table");
-
-// A data-centre parameter set as the kernels see it: the caller's struct plus correctly rounded reciprocals of the
-// parameters the step divides by (computed on the host by sdc_set_dc_params), so that those divisions take the
-// 3-instruction form of sdc_div_const.
-struct SdcDcDev {
-  sdc_dc_params p;
-  double rc_n_racks, rc_itfan_ref_v_ratio, rc_rho_air, rc_ctafr, rc_bat_capacity;
-  double k_outlet;   // 1.918 / (c_air rho_air 0.526): the constant factor of the rack outlet-temperature rise
-  double n_racks_f;  // p.n_racks as a double (the step kernel hands the scalars from p.m_cpu to here round as doubles)
-  double ret_sum;    // sum of rack_return over the config's racks (the CRAC return temperature is (this + sum of outlets) / racks)
-  // RACK CLASSES (the lane-per-env kernel, sdc_wide.hip: its rack model is a per-lane LOOP, and a rack's power / outlet temperature
-  // depend on its four parameters only): the config's DISTINCT (cpus, full load, idle, supply approach) tuples, grouped by their
-  // (cpus, supply approach) pair -- what the fan / airflow / inlet part depends on.  The shipped 20-rack config has 7 classes in 2
-  // groups.  n_cls == 0: too many classes for the kernel's tables (sdc_set_dc_params).
-  SdcRackClasses rc;
-};
-
-// THE LANE-PER-ENV KERNEL'S GENERAL FORM (sdc_wide.hip, template GEN: several configs in one batch, rule-based policies, alternate
-// reward functions of the dc / battery agents): every LANE carries its own config.  What differs between the configs of a batch the
-// kernel serves -- the rack table and the quantities sized from it and from the location (utils/make_envs_pyenv.py:139-218) -- is one
-// SdcWideCfg per config, staged into LDS by every workgroup (LDS-DMA) and read per lane; the scalars of the server / HVAC
-// characteristics (CPU and fan curves, air constants, set-point limits) must be the same bits in every config (the reference's
-// dc_config_dc{1,2,3}.json differ in their rack lists only) and stay wave-uniform.  59 doubles per config: an ODD number of 8-byte
-// words, so lanes of different configs read different LDS banks.
-#define SDC_WIDE_MAX_CLS 12    // rack classes per config (the shipped 16 / 20 / 25-rack configs: 8 / 7 / 11)
-#define SDC_WIDE_MAX_CFG 16
-enum { WC_RET_SUM = 0, WC_RC_N_RACKS, WC_CT_FAN_REF_P, WC_RC_CTAFR, WC_BAT_CAP, WC_RC_BAT_CAP, WC_SCAL_COUNT };
-struct SdcWideCfg {
-  double cls[SDC_WIDE_MAX_CLS][4];     // class c: {cpus, supply approach, full load, idle} (unused classes: zeros)
-  double scal[WC_SCAL_COUNT];          // the per-config scalars, WC_*
-  unsigned map[4];                     // rack slot r -> class: 4 bits each, slot r in bits 4 (r % 8) of map[r / 8]
-  int n_cls, n_racks;
-  double pad[2];
-};
-static_assert(sizeof(SdcWideCfg) == 59 * 8, "an odd number of 8-byte words per config");
-#define SDC_WIDE_CFG_DOUBLES 59
-
 // DEFERRED WINDOW RE-CENTRING.  A rank window that the next step could exhaust has to be re-centred with one sweep over
 // the env's 40 KB ring (sdc_ringpath.hpp qt_refill, ~5 us) -- done inline that sweep made its wavefront the straggler of
 // nearly every launch.  Instead the step that sees the need (step t) files a REQUEST with a snapshot of the window;
@@ -183,8 +131,7 @@ static_assert(sizeof(SdcWideCfg) == 59 * 8, "an odd number of 8-byte words per c
 // Requests per set: S.rq_max (and S.sweep_blocks four-wavefront sweep workgroups per launch), sized by the host with the batch --
 // ~26 windows per 4096 envs ask per step, and a request that finds no room is re-centred INLINE by its env's wavefront (a 5 us
 // straggler).  Rounds 2-3 had 128 / 32 whatever the batch: at 16 384 envs 42 % of the re-centrings ran inline.
-#define SDC_RQ_MIN 128        // (4096 envs and below)
-#define SDC_RQ_LIMIT 2047     // (the request index + 1 has 11 bits in the header's stamp)
+// (SDC_RQ_MIN / SDC_RQ_LIMIT: sdc_setup.hpp)
 struct SdcRefillReq {
   int env, win, dir, kt, n, r0, hi, patch_slot;
   unsigned patch_x;
@@ -361,7 +308,7 @@ __device__ __forceinline__ double sdc_div_fast(const double a, const double b) {
 enum { SDC_P_COS = 0, SDC_P_SIN, SDC_P_NC, SDC_P_CI7 = 3, SDC_P_OLDEST = 10, SDC_P_AVG, SDC_P_NORMQ, SDC_P_W, SDC_P_NT,
        SDC_P_TSLOPE = 15, SDC_P_T5 = 16, SDC_P_HIST = 21, SDC_P_WNEXT = 26, SDC_P_NTNEXT, SDC_P_SOC, SDC_POOL_DIM };
 
-#define SDC_FEAT_ROW 32      // floats per feature row (128 bytes)
+// (SDC_FEAT_ROW floats per feature row, 128 bytes: sdc_setup.hpp)
 // feature rows are kept step-major: the rows all envs read in one launch (envs in lock-step) are adjacent -- 512 KB at
 // 4096 envs, a handful of pages -- instead of one row per 86 KB
 // the time-major mirror of the queue table's `cum` column (SdcDev::qcum_t), kept by whoever appends to the table

@@ -46,7 +46,7 @@ class SdcHostMirror {
   bool feat(const int e) const { return feat_[(size_t)e] != 0; }
   int cfg(const int e) const { return cfg_.empty() ? 0 : cfg_[(size_t)e]; }
   int loc(const int e) const { return loc_.empty() ? 0 : loc_[(size_t)e]; }
-  bool cfg_assigned() const { return !cfg_.empty(); }
+  const int* cfg_ids() const { return cfg_.empty() ? nullptr : cfg_.data(); }      // [N], or nullptr: unassigned
   int rel_hint() const { return rel_hint_; }
   int steps_to_terminal() const { return steps_to_terminal_; }
   int n_feat() const { return n_feat_; }
