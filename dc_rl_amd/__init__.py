@@ -16,6 +16,8 @@ Public surface (mirrors the reference's names for this path):
   * `EpisodeStats`                                 -- per-env episode statistics reduced on the device (`SdcEngine.rollout_stats` / `evaluate`)
   * `PolicyStats`                                  -- what the in-kernel actors did over those steps: action counts, switches, entropy,
                                                       log-probability (`SdcEngine.rollout_actor_stats` / `evaluate(actors=True)`)
+  * `PlanStats`                                    -- what the CEM planner did over those steps: action counts, switches, predicted
+                                                      score, gain (`SdcEngine.rollout_cem_stats` / `evaluate(mpc=agent)`)
 
 The compute path is the HIP extension `csrc/libsustaindc_hip.so` (hand-written gfx950 kernels).  There is
 no CPU fallback: constructing an engine without the extension or without an MI355X raises.
@@ -43,6 +45,7 @@ _LAZY = {
     "GroupCEMResult": ("engine", "GroupCEMResult"),
     "EpisodeStats": ("engine", "EpisodeStats"),
     "PolicyStats": ("engine", "PolicyStats"),
+    "PlanStats": ("engine", "PlanStats"),
     "RBCBatteryAgent": ("agents", "RBCBatteryAgent"),
     "trim_and_respond_ctrl": ("agents", "trim_and_respond_ctrl"),
 }

@@ -249,6 +249,39 @@ class CEMMPCAgent:
         self._probs, self._best_seq = self.last.probs, self.last.best_seq
         return self._chosen(self.last)
 
+    def rollout_stats(self, env, n_steps, into=None):
+        """n_steps decisions and steps in ONE library call (SdcEngine.rollout_cem_stats / SustainDCVecEnv.rollout_cem_stats) with this
+        agent's parameters and carried state -> the call's EpisodeStats, its `plan` a PlanStats.  What n_steps rounds of `act(env)` and
+        a step with its actions do, bit for bit; afterwards `draw`, the carried distribution, `last_horizon` and the step it was made
+        at are what those rounds would have left, so `act()` may follow (`last` is None: the call keeps the last decision's arrays in
+        the result's `mpc`, not a CEMResult).  `into`: an EpisodeStats of the env's to continue.  The engine's arguments are checked
+        first: a refused call leaves the agent as it was, but for a `forecast`, which is set on the env before the first decision."""
+        import torch
+        eng = getattr(env, "engine", env)
+        n_steps = int(n_steps)
+        step = _mpc_horizon(env, self.horizon)[1]
+        if not self._forecast_set:
+            _set_forecast(env, self.forecast)
+            self._forecast_set = True
+        H, N = self.horizon, eng.n_envs
+        # the carried result, if the first decision may start from it (_start's rule but for the horizon, which the library checks)
+        carried = self.warm_start and self._probs is not None and self._step is not None and step > self._step
+        probs = torch.empty((H, N, 3, 3), dtype=torch.float64, device=eng.device)
+        best_seq = torch.empty((H, N, 3), dtype=torch.int32, device=eng.device)
+        k = int(self._probs.shape[0]) if carried else 0
+        if k:
+            probs[:k], best_seq[:k] = self._probs, self._best_seq
+        res = env.rollout_cem_stats(n_steps, H, self.n_iters, self.n_candidates, self.n_elite, probs=probs, best_seq=best_seq,
+                                    resume_steps=k, warm_start=self.warm_start, seed=self.seed, draw=self.draw, alpha=self.alpha,
+                                    p_min=self.p_min, idle_action=self.DO_NOTHING, reward_weights=self.reward_weights, gamma=self.gamma,
+                                    info_weights=self.info_weights, into=into)
+        c = res.mpc
+        self.draw = (self.draw + c.planned) & 0xFFFFFFFF
+        self.last, self.last_horizon = None, c.steps
+        self._probs, self._best_seq = (c.probs[:c.steps], c.best_seq[:c.steps]) if c.steps else (None, None)
+        self._step = step + n_steps - 1
+        return res
+
     # what GroupCEMMPCAgent does differently
     def _before(self, env, step):
         pass
@@ -292,3 +325,7 @@ class GroupCEMMPCAgent(CEMMPCAgent):
 
     def _chosen(self, res):
         return res.step_actions
+
+    def rollout_stats(self, env, n_steps, into=None):
+        raise NotImplementedError("GroupCEMMPCAgent.rollout_stats: the closed loop in the library plans per env (CEMMPCAgent); the "
+                                  "replica-group form needs sync_groups after every reset and is not built")

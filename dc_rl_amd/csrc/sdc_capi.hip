@@ -32,6 +32,8 @@
 #include "sdc_forecast.hpp"
 #include "sdc_stats.hpp"
 #include "sdc_policy_stats.hpp"
+#include "sdc_mpc.hpp"
+#include "sdc_mpc_schedule.hpp"
 
 namespace {
 
@@ -1692,6 +1694,22 @@ int sdc_forecast_traces(sdc_handle* h, int n_entries, int truth, double* out, vo
                   sdc_forecast_fill_launch(forecast_fill_plan(h, n_entries, truth != 0, out), reinterpret_cast<hipStream_t>(stream)));
 }
 
+// What every plan call refuses about its objective; obj: the objective with the defaults filled in.  -> 0, or -2 with the message set
+static int plan_objective_refused(const std::string& w, const sdc_plan_objective* objective, sdc_plan_objective& obj) {
+  std::memset(&obj, 0, sizeof(obj));
+  obj.reward_weight[0] = obj.reward_weight[1] = obj.reward_weight[2] = 1.0;
+  obj.gamma = 1.0;
+  if (objective) obj = *objective;
+  if (!(obj.gamma > 0.0 && obj.gamma <= 1.0)) return fail_msg(w + "gamma = " + std::to_string(obj.gamma) + " outside (0, 1]");
+  if (obj.n_cols < 0 || obj.n_cols > SDC_PLAN_MAX_COLS)
+    return fail_msg(w + "n_cols = " + std::to_string(obj.n_cols) + " outside [0, " + std::to_string(SDC_PLAN_MAX_COLS) + "]");
+  for (int j = 0; j < obj.n_cols; j++)
+    if (obj.col[j] < 0 || obj.col[j] >= SDC_INFO_DIM)
+      return fail_msg(w + "info column " + std::to_string(obj.col[j]) + " (entry " + std::to_string(j) + ") outside [0, " +
+                      std::to_string(SDC_INFO_DIM) + ")");
+  return 0;
+}
+
 // What every plan call refuses about the horizon, the engine and the objective, in sdc_plan's order (`arrays`: the caller's own null
 // check, reported at its place in that order); obj: the objective with the defaults filled in.  -> 0, or -2 with the message set
 static int plan_refused(const char* who, const sdc_handle* h, const int n_steps, const bool arrays, const float* obs, const float* share_obs,
@@ -1710,17 +1728,7 @@ static int plan_refused(const char* who, const sdc_handle* h, const int n_steps,
   if (n_steps > h->mirror.steps_to_terminal())
     return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" +
                     std::to_string(h->mirror.steps_to_terminal()) + " steps left)");
-  std::memset(&obj, 0, sizeof(obj));
-  obj.reward_weight[0] = obj.reward_weight[1] = obj.reward_weight[2] = 1.0;
-  obj.gamma = 1.0;
-  if (objective) obj = *objective;
-  if (!(obj.gamma > 0.0 && obj.gamma <= 1.0)) return fail_msg(w + "gamma = " + std::to_string(obj.gamma) + " outside (0, 1]");
-  if (obj.n_cols < 0 || obj.n_cols > SDC_PLAN_MAX_COLS)
-    return fail_msg(w + "n_cols = " + std::to_string(obj.n_cols) + " outside [0, " + std::to_string(SDC_PLAN_MAX_COLS) + "]");
-  for (int j = 0; j < obj.n_cols; j++)
-    if (obj.col[j] < 0 || obj.col[j] >= SDC_INFO_DIM)
-      return fail_msg(w + "info column " + std::to_string(obj.col[j]) + " (entry " + std::to_string(j) + ") outside [0, " +
-                      std::to_string(SDC_INFO_DIM) + ")");
+  if (plan_objective_refused(w, objective, obj)) return -2;
   return forecast_refused(w, h, n_steps);
 }
 
@@ -1847,35 +1855,63 @@ static int plan_candidates(PlanSession& P, const int n_cand, const int32_t* acti
   return rc;
 }
 
-// What the three plan calls do alike once their arguments have passed (plan_refused and their own checks): the handle's buffers, the
-// discount table g_k = g_{k-1} * gamma through the plan's stage -- the slot stays in flight until the last kernel that reads it --, the
-// mark of the whole batch, and then body(session) -> rc, which enqueues the call's own work.  One mark serves every rollout of the
-// call: a rewind keeps its mark alive.
+// The overlay's plan of the handle's forecast (sdc_forecast.hpp) for a plan of n_steps, the handle's two buffers grown to it;
+// W.channels == 0: every channel PERFECT, nothing to launch
+static int plan_forecast_swap(sdc_handle* h, const int n_steps, SdcForecastSwap& W) {
+  const size_t N = (size_t)h->cfg.n_envs;
+  std::memset(&W, 0, sizeof(W));
+  W.channels = forecast_channels(h);
+  if (!W.channels) return 0;
+  if (plan_grow(&h->plan_fc, &h->plan_fc_bytes, (size_t)(n_steps + 2) * N * SDC_FC_CHANNELS * sizeof(double))) return -1;
+  if (plan_grow(&h->plan_saved, &h->plan_saved_bytes, (size_t)n_steps * N * SDC_FORECAST_SAVED_DWORDS * sizeof(unsigned))) return -1;
+  W.n_envs = (int)N;
+  W.n_steps = n_steps;
+  W.n_rows = h->d.episode_steps + 1;
+  W.units = sdc_forecast_units(W.channels);
+  W.rec = h->d.rec;
+  W.fc = reinterpret_cast<const double*>(h->plan_fc);
+  W.feat = h->d.feat;
+  W.saved = reinterpret_cast<unsigned*>(h->plan_saved);
+  return 0;
+}
+
 extern "C++" {
+// A plan of P.R.n_steps steps once its buffers are there and its discount table is on the device (P.g_dev, P.g_terminal): the mark of
+// the whole batch; the handle's forecast -- behind the mark one fill and one overlay of the rows the rollouts will read, behind the body,
+// whatever it returns, the saved bits back; nothing of it with every channel PERFECT --; and body(session) -> rc, which enqueues the
+// call's own work.  One mark serves every rollout of the plan: a rewind keeps its mark alive.
+template <class Body>
+static int plan_marked(PlanSession& P, SdcForecastSwap& W, Body&& body) {
+  sdc_handle* const h = P.h;
+  const int n_steps = P.R.n_steps;
+  int rc = sdc_mark_envs(h, nullptr, h->cfg.n_envs, n_steps, h->plan_rows, h->plan_manifest.data(), P.obs, P.share_obs, P.stream);
+  bool overlaid = false;
+  if (rc == 0 && W.channels) {
+    rc = launched("sdc_forecast_fill_kernel",
+                  sdc_forecast_fill_launch(forecast_fill_plan(h, n_steps + 2, false, reinterpret_cast<double*>(h->plan_fc)), P.st()));
+    if (rc == 0) rc = launched("sdc_forecast_swap_kernel", sdc_forecast_swap_launch(W, P.st()));
+    overlaid = rc == 0;
+  }
+  if (rc == 0) rc = body(P);
+  if (overlaid) {
+    W.back = 1;
+    const int back = launched("sdc_forecast_swap_kernel", sdc_forecast_swap_launch(W, P.st()));
+    if (rc == 0) rc = back;
+  }
+  return rc;
+}
+
+// What the three plan calls do alike once their arguments have passed (plan_refused and their own checks): the handle's buffers, the
+// discount table g_k = g_{k-1} * gamma through the plan's stage -- the slot stays in flight until the last kernel that reads it --, and
+// behind it the marked plan (plan_marked) with the call's body.
 template <class Body>
 static int plan_session(sdc_handle* h, const int n_steps, const sdc_plan_objective& obj, float* obs, float* share_obs, void* stream,
                         Body&& body) {
   HIP_TRY(hipSetDevice(h->device));
   PlanSession P{h, {}, nullptr, 0.0, obs, share_obs, stream};
   if (plan_prepare(h, n_steps, obj, P.R)) return -1;
-  // the handle's forecast (sdc_forecast.hpp): behind the mark one fill and one overlay of the rows the rollouts will read, behind the
-  // body -- whatever it returns -- the saved bits back.  Nothing of it with every channel PERFECT
-  const size_t N = (size_t)h->cfg.n_envs;
   SdcForecastSwap W;
-  std::memset(&W, 0, sizeof(W));
-  W.channels = forecast_channels(h);
-  if (W.channels) {
-    if (plan_grow(&h->plan_fc, &h->plan_fc_bytes, (size_t)(n_steps + 2) * N * SDC_FC_CHANNELS * sizeof(double))) return -1;
-    if (plan_grow(&h->plan_saved, &h->plan_saved_bytes, (size_t)n_steps * N * SDC_FORECAST_SAVED_DWORDS * sizeof(unsigned))) return -1;
-    W.n_envs = (int)N;
-    W.n_steps = n_steps;
-    W.n_rows = h->d.episode_steps + 1;
-    W.units = sdc_forecast_units(W.channels);
-    W.rec = h->d.rec;
-    W.fc = reinterpret_cast<const double*>(h->plan_fc);
-    W.feat = h->d.feat;
-    W.saved = reinterpret_cast<unsigned*>(h->plan_saved);
-  }
+  if (plan_forecast_swap(h, n_steps, W)) return -1;
   void* pin = nullptr;
   if (stage_acquire(h, h->plan_stage, &pin)) return -1;
   double* const g = static_cast<double*>(pin);
@@ -1885,20 +1921,7 @@ static int plan_session(sdc_handle* h, const int n_steps, const sdc_plan_objecti
   int rc = 0;
   const int staged = stage_commit(h, h->plan_stage, (size_t)n_steps, P.st(), [&](const void* g_dev) {
     P.g_dev = g_dev;
-    rc = sdc_mark_envs(h, nullptr, h->cfg.n_envs, n_steps, h->plan_rows, h->plan_manifest.data(), obs, share_obs, stream);
-    bool overlaid = false;
-    if (rc == 0 && W.channels) {
-      rc = launched("sdc_forecast_fill_kernel",
-                    sdc_forecast_fill_launch(forecast_fill_plan(h, n_steps + 2, false, reinterpret_cast<double*>(h->plan_fc)), P.st()));
-      if (rc == 0) rc = launched("sdc_forecast_swap_kernel", sdc_forecast_swap_launch(W, P.st()));
-      overlaid = rc == 0;
-    }
-    if (rc == 0) rc = body(P);
-    if (overlaid) {
-      W.back = 1;
-      const int back = launched("sdc_forecast_swap_kernel", sdc_forecast_swap_launch(W, P.st()));
-      if (rc == 0) rc = back;
-    }
+    rc = plan_marked(P, W, body);
     return hipSuccess;
   });
   return rc ? rc : staged;
@@ -2166,31 +2189,26 @@ static int stats_past_end_refused(const std::string& w, const sdc_handle* h, con
   return 0;
 }
 
-// The chunks of a statistics call, the block (layout B, of `chunk` steps) grown already: rollout (rollout_chunks'), behind each chunk
-// sdc_stats_reduce_kernel and extra(first step, steps, init) -> rc; behind the last chunk sdc_stats_last_kernel
-extern "C++" {
-template <class Rollout, class Extra>
-static int stats_chunks(sdc_handle* h, const SdcPlanBlock& B, const int n_steps, const int chunk, const int accumulate, const StatsArrays& a,
-                        hipStream_t st, Rollout&& rollout, Extra&& extra) {
-  const size_t N = (size_t)h->cfg.n_envs;
+// sdc_stats_reduce_kernel's plan over the block (layout B) into the caller's arrays, but for the chunk's steps and init
+static SdcStatsReduce stats_reduce_plan(const sdc_handle* h, const SdcPlanBlock& B, const StatsArrays& a) {
   unsigned char* const out = h->plan_out;
   SdcStatsReduce S;
   std::memset(&S, 0, sizeof(S));
-  S.n_envs = (int)N;
+  S.n_envs = h->cfg.n_envs;
   S.rew = reinterpret_cast<const float*>(out + B.rew);
   S.info = reinterpret_cast<const float*>(out + B.info);
   S.stats = a.stats;
   S.returns = a.returns;
   S.counts = a.counts;
-  int last_steps = 0;
-  const int rc = rollout_chunks(h, B, n_steps, chunk, rollout, [&](const int k0, const int steps) {
-    S.steps = last_steps = steps;
-    S.init = (k0 == 0 && accumulate == 0) ? 1 : 0;
-    const int r = launched("sdc_stats_reduce_kernel", sdc_stats_reduce_launch(S, st));
-    return r ? r : extra(k0, steps, S.init);
-  });
-  if (rc) return rc;
-  const size_t last = (size_t)(last_steps - 1) * N;      // the LAST step's slices of the last chunk
+  return S;
+}
+
+// sdc_stats_last_kernel behind a call's last chunk of last_steps steps in the block (layout B): its LAST step's slices -> the caller's
+// single-step arrays
+static int stats_last(const sdc_handle* h, const SdcPlanBlock& B, const int last_steps, const StatsArrays& a, hipStream_t st) {
+  const size_t N = (size_t)h->cfg.n_envs;
+  unsigned char* const out = h->plan_out;
+  const size_t last = (size_t)(last_steps - 1) * N;
   SdcStatsLast Q;
   std::memset(&Q, 0, sizeof(Q));
   Q.n_envs = (int)N;
@@ -2207,6 +2225,23 @@ static int stats_chunks(sdc_handle* h, const SdcPlanBlock& B, const int n_steps,
   Q.o_done = a.done;
   Q.o_final_obs = a.final_obs;
   return launched("sdc_stats_last_kernel", sdc_stats_last_launch(Q, st));
+}
+
+// The chunks of a statistics call, the block (layout B, of `chunk` steps) grown already: rollout (rollout_chunks'), behind each chunk
+// sdc_stats_reduce_kernel and extra(first step, steps, init) -> rc; behind the last chunk sdc_stats_last_kernel
+extern "C++" {
+template <class Rollout, class Extra>
+static int stats_chunks(sdc_handle* h, const SdcPlanBlock& B, const int n_steps, const int chunk, const int accumulate, const StatsArrays& a,
+                        hipStream_t st, Rollout&& rollout, Extra&& extra) {
+  SdcStatsReduce S = stats_reduce_plan(h, B, a);
+  int last_steps = 0;
+  const int rc = rollout_chunks(h, B, n_steps, chunk, rollout, [&](const int k0, const int steps) {
+    S.steps = last_steps = steps;
+    S.init = (k0 == 0 && accumulate == 0) ? 1 : 0;
+    const int r = launched("sdc_stats_reduce_kernel", sdc_stats_reduce_launch(S, st));
+    return r ? r : extra(k0, steps, S.init);
+  });
+  return rc ? rc : stats_last(h, B, last_steps, a, st);
 }
 }  // extern "C++"
 
@@ -2284,6 +2319,134 @@ int sdc_rollout_actor_stats(sdc_handle* h, int n_steps, int sample, int accumula
         P.init = init;
         return launched("sdc_policy_stats_kernel", sdc_policy_stats_launch(P, st));
       });
+}
+
+// ---- planner evaluation (sdc_mpc.hip) -----------------------------------------------------------------------------------------------
+// The contract: include/sustaindc_hip.h; the decision schedule: sdc_mpc_schedule.hpp; the two kernels' plans: sdc_mpc.hpp.  A planned
+// decision is sdc_plan_cem's own body (plan_marked around cem_iterations), the step sdc_rollout_stats' with a one-step chunk; the
+// discount table of the longest horizon is staged once, and every decision reads its prefix.
+int sdc_rollout_cem_stats(sdc_handle* h, int n_steps, const sdc_mpc_params* mpc, const sdc_plan_objective* objective, int accumulate,
+                          double* stats, double* returns, int32_t* counts, int32_t* plan_counts, double* plan_sums, double* probs,
+                          int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* cand, double* cand_score, float* obs,
+                          float* share_obs, float* rew, uint8_t* done, float* info, float* final_obs, void* stream) {
+  static const std::string w = "sdc_rollout_cem_stats: ";
+  const StatsArrays a = {stats, returns, counts, obs, share_obs, rew, done, info, final_obs};
+  if (stats_refused(w, h, n_steps, accumulate, a)) return -2;
+  if (!mpc) return fail_msg(w + "null mpc");
+  const sdc_mpc_params m = *mpc;
+  const sdc_cem_params c = m.cem;
+  const int H = m.horizon;
+  if (H < 1 || H > SDC_MARK_MAX_STEPS)
+    return fail_msg(w + "horizon = " + std::to_string(H) + " outside [1, " + std::to_string(SDC_MARK_MAX_STEPS) + "]");
+  if (m.warm_start != 0 && m.warm_start != 1) return fail_msg(w + "warm_start = " + std::to_string(m.warm_start) + " outside {0, 1}");
+  if (m.resume != 0 && m.resume != 1) return fail_msg(w + "resume = " + std::to_string(m.resume) + " outside {0, 1}");
+  if (m.resume && (m.resume_steps < 1 || m.resume_steps > H))
+    return fail_msg(w + "resume_steps = " + std::to_string(m.resume_steps) + " outside [1, horizon = " + std::to_string(H) + "]");
+  for (int k = 0; k < 3; k++)
+    if (m.idle_action[k] < 0 || m.idle_action[k] > 2)
+      return fail_msg(w + "idle_action[" + std::to_string(k) + "] = " + std::to_string(m.idle_action[k]) + " outside [0, 2]");
+  if (cem_iters_refused(w, c.n_iters, c.iter0)) return -2;
+  if (c.n_cand < 2 || c.n_cand > SDC_CEM_MAX_CAND)
+    return fail_msg(w + "n_cand = " + std::to_string(c.n_cand) + " outside [2, " + std::to_string(SDC_CEM_MAX_CAND) + "]");
+  if (cem_elite_refused(w, c.n_elite, "n_cand", c.n_cand) || cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min)) return -2;
+  if (!probs || !best_seq || !best_score || !best_action || !cand || !cand_score)
+    return fail_msg(w + "null array (probs, best_seq, best_score, best_action, cand and cand_score are required)");
+  const auto addr = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+  if (((addr(probs) | addr(best_score) | addr(cand_score)) & 7u) != 0) return fail_msg(w + "probs / best_score / cand_score not 8-byte aligned");
+  if (((addr(best_seq) | addr(best_action) | addr(cand)) & 3u) != 0) return fail_msg(w + "best_seq / best_action / cand not dword-aligned");
+  if ((plan_counts == nullptr) != (plan_sums == nullptr)) return fail_msg(w + "plan_counts and plan_sums are given together or not at all");
+  if ((addr(plan_sums) & 15u) != 0) return fail_msg(w + "plan_sums not 16-byte aligned");
+  if ((addr(plan_counts) & 3u) != 0) return fail_msg(w + "plan_counts not dword-aligned");
+  sdc_plan_objective obj;
+  if (plan_objective_refused(w, objective, obj)) return -2;
+  if (stats_past_end_refused(w, h, n_steps)) return -2;
+  // the longest planned decision: the first one (the horizon only shrinks towards the episode's end); 0: every decision idles
+  const int left0 = h->mirror.steps_to_terminal(), auto_reset = h->cfg.auto_reset ? 1 : 0;
+  int k_max = 0;
+  {
+    SdcMpcSchedule S(H, m.warm_start, auto_reset, m.resume ? m.resume_steps : 0);
+    for (int t = 0; t < n_steps; t++) k_max = std::max(k_max, S.next(left0 - t).steps);
+  }
+  if (k_max > 0 && forecast_refused(w, h, k_max)) return -2;
+
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int N = h->cfg.n_envs;
+  // every buffer at its largest before anything is enqueued: the step's one-step block, the longest decision's rows, block and forecast
+  int chunk1;
+  SdcPlanBlock B1;
+  if (plan_out_block(h, 1, chunk1, B1)) return -1;
+  SdcForecastSwap W;
+  std::memset(&W, 0, sizeof(W));
+  if (k_max > 0) {
+    PlanRun R;
+    if (plan_prepare(h, k_max, obj, R) || plan_forecast_swap(h, k_max, W)) return -1;
+  }
+  SdcMpcStart A;
+  std::memset(&A, 0, sizeof(A));
+  A.n_envs = N;
+  A.probs = probs;
+  A.best_seq = best_seq;
+  SdcMpcFold F;
+  std::memset(&F, 0, sizeof(F));
+  F.n_envs = N;
+  F.best_action = best_action;
+  F.counts = plan_counts;
+  F.sums = plan_sums;
+  F.score_first = best_score;
+  F.score_last = best_score + (size_t)(c.n_iters - 1) * (size_t)N;
+  for (int k = 0; k < 3; k++) A.idle[k] = F.idle[k] = m.idle_action[k];
+
+  void* pin = nullptr;
+  if (stage_acquire(h, h->plan_stage, &pin)) return -1;
+  double* const g = static_cast<double*>(pin);
+  g[0] = 1.0;
+  for (int k = 1; k < H; k++) g[k] = g[k - 1] * obj.gamma;
+  int rc = 0;
+  const int staged = stage_commit(h, h->plan_stage, (size_t)H, st, [&](const void* g_dev) {
+    SdcMpcSchedule S(H, m.warm_start, auto_reset, m.resume ? m.resume_steps : 0);
+    SdcStatsReduce R1 = stats_reduce_plan(h, B1, a);
+    R1.steps = 1;
+    for (int t = 0; t < n_steps && rc == 0; t++) {
+      const SdcMpcDecision d = S.next(h->mirror.steps_to_terminal());
+      const int init = (t == 0 && accumulate == 0) ? 1 : 0;
+      if (d.planned) {
+        const int K = d.steps;
+        A.steps = K;
+        A.fresh = d.fresh;
+        rc = launched("sdc_mpc_start_kernel", sdc_mpc_start_launch(A, st));
+        PlanSession P{h, {}, g_dev, g[K - 1] * obj.gamma, obs, share_obs, stream};
+        if (rc == 0 && (plan_prepare(h, K, obj, P.R) || plan_forecast_swap(h, K, W))) rc = -1;
+        if (rc == 0) {
+          sdc_cem_params ck = c;
+          ck.draw = c.draw + d.draw_index;
+          SdcCemSample Q = cem_sample_plan<SdcCemSample>(N, K, ck, probs, best_seq, cand);
+          Q.n_cand = c.n_cand;
+          Q.env_base = h->cfg.env_index_base;
+          SdcCemRefit T = cem_refit_plan<SdcCemRefit>(N, K, ck, cand_score, cand, probs, best_seq, best_action);
+          T.n_cand = c.n_cand;
+          rc = plan_marked(P, W, [&](PlanSession& P_) {
+            return cem_iterations(P_, c.n_iters, c.iter0, c.n_cand, cand, cand_score, best_score, (size_t)N, Q, sdc_cem_sample_launch,
+                                  "sdc_cem_sample_kernel", T, sdc_cem_refit_launch, "sdc_cem_refit_kernel");
+          });
+        }
+      }
+      if (rc == 0 && (!d.planned || plan_counts)) {
+        F.planned = d.planned;
+        F.init = init;
+        rc = launched("sdc_mpc_fold_kernel", sdc_mpc_fold_launch(F, st));
+      }
+      // the step: sdc_rollout_stats' path with a one-step chunk and best_action as its actions
+      if (rc == 0)
+        rc = rollout_chunks(h, B1, 1, 1, rollout_of(h, best_action, stream), [&](int, int) {
+          R1.init = init;
+          return launched("sdc_stats_reduce_kernel", sdc_stats_reduce_launch(R1, st));
+        });
+    }
+    if (rc == 0) rc = stats_last(h, B1, 1, a, st);
+    return hipSuccess;
+  });
+  return rc ? rc : staged;
 }
 
 }  // extern "C"

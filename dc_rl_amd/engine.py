@@ -128,10 +128,13 @@ class EpisodeStats:
     its [N, 44] views, one row per env and one column per info key (dc_rl_amd._lib.INFO_COLS) --, `returns` float64 [N, 3] the three
     agents' summed rewards, `counts` int32 [N, 2] with the views `steps` [N] (steps reduced) and `fault` [N] (the OR of the steps'
     info[fault] bits).  `policy`: the PolicyStats of the same steps from `rollout_actor_stats` / `evaluate(actors=True)`, None from
-    `rollout_stats`.  From `evaluate` every tensor has a leading [E] dimension, one entry per episode."""
+    `rollout_stats`.  `plan`: the PlanStats of the same steps from `rollout_cem_stats` / `evaluate(mpc=)`, None from the others; `mpc`:
+    the MPCCarry `rollout_cem_stats` leaves (what a later call resumes from), None from the others.  From `evaluate` every tensor has a
+    leading [E] dimension, one entry per episode."""
 
-    def __init__(self, stats, returns, counts, policy=None):
-        self.stats, self.returns, self.counts, self.policy = stats, returns, counts, policy
+    def __init__(self, stats, returns, counts, policy=None, *, plan=None):
+        self.stats, self.returns, self.counts, self.policy, self.plan = stats, returns, counts, policy, plan
+        self.mpc = None
 
     sum = property(lambda self: self.stats.select(-3, 0))
     min = property(lambda self: self.stats.select(-3, 1))
@@ -217,6 +220,83 @@ class PolicyStats:
                 per_env[name], batch[name] = ratio(x, steps), ratio(x.sum(axis=-2), bsteps)
             per_env["switch_rate"], batch["switch_rate"] = sw / trans, sw.sum(axis=-2) / trans.sum(axis=-2)
         return {"per_env": per_env, "batch": batch, "steps": steps.astype(np.int64)}
+
+
+class PlanStats:
+    """What the planner did over the steps of an EpisodeStats (sdc_rollout_cem_stats, include/sustaindc_hip.h), on the engine's device:
+    `counts` int32 [N, 3, 5] per env and agent (ls, dc, bat) with the views `action_counts` [N, 3, 3] (steps on which action 0 / 1 / 2
+    was played, idle decisions included), `switches` [N, 3] (steps whose action differs from the step before) and `last_action` [N, 3]
+    (-1: no step yet); `sums` float64 [N, 4] per env with the views `score` (the summed score the planner predicted for the sequence
+    it chose, over the planned decisions), `gain` (the summed improvement of that score over the CEM iterations: last minus first),
+    `planned` and `idle` (the number of decisions of either kind, as doubles).  From `evaluate` every tensor has a leading [E]
+    dimension."""
+
+    def __init__(self, counts, sums):
+        self.counts, self.sums = counts, sums
+
+    action_counts = property(lambda self: self.counts[..., :3])
+    switches = property(lambda self: self.counts[..., L.POLICY_SWITCHES])
+    last_action = property(lambda self: self.counts[..., L.POLICY_LAST])
+    score = property(lambda self: self.sums[..., L.PLAN_SCORE])
+    gain = property(lambda self: self.sums[..., L.PLAN_GAIN])
+    planned = property(lambda self: self.sums[..., L.PLAN_PLANNED])
+    idle = property(lambda self: self.sums[..., L.PLAN_IDLE])
+
+    def summary(self) -> dict:
+        """Per-decision quantities on the host, fp64: {"per_env": {...}, "batch": {...}, "steps": array [N, 3] (or [E, N, 3]),
+        "planned": array [N], "idle": array [N]}.  With steps = the three action counts' sum, per env and agent (last axis: ls, dc, bat):
+          action_frequency  [..., 3 agents, 3 actions] = action_counts / steps;
+          switch_rate = switches / max(steps - 1, 1);
+        and per env:  mean_score = score / planned;   mean_gain = gain / planned -- per planned decision.
+        Over the batch the same formulas with the sums over the envs (the transitions: the sum of the envs' max(steps - 1, 1)).  A
+        quantity of an env that took no step, or planned no decision, is 0, never NaN."""
+        n = self.action_counts.cpu().numpy().astype(np.float64)
+        sw = self.switches.cpu().numpy().astype(np.float64)
+        score, gain = self.score.cpu().numpy(), self.gain.cpu().numpy()
+        planned, idle = self.planned.cpu().numpy(), self.idle.cpu().numpy()
+        steps = n.sum(axis=-1)
+        trans = np.maximum(steps - 1.0, 1.0)
+        per_env, batch = {}, {}
+        with np.errstate(divide="ignore", invalid="ignore"):
+            def ratio(x, d):
+                return np.where(d > 0, x / d, 0.0)
+            bsteps, bplanned = steps.sum(axis=-2), planned.sum(axis=-1)
+            per_env["action_frequency"] = ratio(n, steps[..., None])
+            batch["action_frequency"] = ratio(n.sum(axis=-3), bsteps[..., None])
+            per_env["switch_rate"], batch["switch_rate"] = sw / trans, sw.sum(axis=-2) / trans.sum(axis=-2)
+            for name, x in (("mean_score", score), ("mean_gain", gain)):
+                per_env[name], batch[name] = ratio(x, planned), ratio(x.sum(axis=-1), bplanned)
+        batch = {k: (float(v) if np.ndim(v) == 0 else np.asarray(v)) for k, v in batch.items()}
+        return {"per_env": per_env, "batch": batch, "steps": steps.astype(np.int64), "planned": planned.astype(np.int64),
+                "idle": idle.astype(np.int64)}
+
+
+class MPCCarry:
+    """What `rollout_cem_stats` leaves of the planner's state, on the engine's device: `probs` float64 [H, N, 3, 3] and `best_seq` int32
+    [H, N, 3], the arrays of the call (a caller's own are the same tensors), whose first `steps` steps hold the last planned decision's
+    result, unshifted -- `steps` is 0 when no decision of the call was planned or its last one was idle: nothing to resume from --;
+    `planned`: the number of planned decisions of the call (what the draw counter advances by); `best_action` int32 [N, 3] the last
+    action played; `best_score` float64 [I, N] the last planned decision's scores."""
+
+    def __init__(self, probs, best_seq, steps, planned, best_action, best_score):
+        self.probs, self.best_seq, self.steps, self.planned = probs, best_seq, int(steps), int(planned)
+        self.best_action, self.best_score = best_action, best_score
+
+
+def mpc_schedule(left, n_steps, horizon, auto_reset, warm_start=True, resume_steps=0):
+    """The decisions of a `rollout_cem_stats` call of n_steps that starts `left` steps before the episode's end, by the library's rule
+    (csrc/sdc_mpc_schedule.hpp; agents._mpc_horizon and CEMMPCAgent._start) -> a list of (K, planned, fresh, draw index) per step."""
+    out, carried, j = [], int(resume_steps), 0
+    for t in range(int(n_steps)):
+        lt = left - t
+        K = min(horizon, lt - 1 if auto_reset else lt)
+        if not (lt >= 2 and K >= 1):
+            out.append((0, False, False, 0))
+            carried = 0
+            continue
+        out.append((K, True, (not warm_start) or carried == 0 or K > carried, j))
+        carried, j = K, j + 1
+    return out
 
 
 def _p(x):
@@ -1044,15 +1124,18 @@ class SdcEngine:
                          sized, sized, f"R = {R}, K = {K}, I = {n_it}, iter0 = {int(iter0)}", n_it, n_elite, probs, best_seq, seed, draw,
                          iter0, alpha, p_min, reward_weights, gamma, info_weights)
 
-    def _stats_into(self, who, into, policy_stats=None):
+    def _stats_into(self, who, into, policy_stats=None, plan_stats=None):
         """the EpisodeStats a statistics call fills: a new one, or the caller's `into` checked (ValueError in `who`'s name) -- tensors of
-        this engine's shapes on its device, and a PolicyStats exactly when `policy_stats` (None: rollout_stats, which has none)"""
+        this engine's shapes on its device, a PolicyStats exactly when `policy_stats` (None: the call has none) and a PlanStats exactly
+        when `plan_stats` (the same)"""
         t, N = self.torch, self.n_envs
         want = ((t.float64, (L.STATS_FIELDS, N, L.INFO_DIM)), (t.float64, (N, L.N_AGENTS)), (t.int32, (N, 2)))     # stats, returns, counts
         pwant = ((t.int32, (N, L.N_AGENTS, L.POLICY_COUNTS)), (t.float64, (N, L.N_AGENTS, L.POLICY_SUMS)))        # counts, sums
+        mwant = ((t.int32, (N, L.N_AGENTS, L.POLICY_COUNTS)), (t.float64, (N, L.PLAN_SUMS)))                      # the plan's counts, sums
         new = lambda shapes: [t.empty(sh, dtype=d, device=self.device) for d, sh in shapes]
         if into is None:
-            return EpisodeStats(*new(want), PolicyStats(*new(pwant)) if policy_stats else None)
+            return EpisodeStats(*new(want), PolicyStats(*new(pwant)) if policy_stats else None,
+                                plan=PlanStats(*new(mwant)) if plan_stats else None)
         fits = lambda xs, shapes: all(A.is_tensor(x, d, sh, self.device, cuda=False) for x, (d, sh) in zip(xs, shapes))
         if not (isinstance(into, EpisodeStats) and fits((into.stats, into.returns, into.counts), want)):
             raise ValueError(f"{who}: into must be an EpisodeStats of this engine (contiguous tensors on {self.device}: stats "
@@ -1065,6 +1148,14 @@ class SdcEngine:
             if pol is not None and not (isinstance(pol, PolicyStats) and fits((pol.counts, pol.sums), pwant)):
                 raise ValueError(f"{who}: into.policy must be a PolicyStats of this engine (contiguous tensors on {self.device}: counts "
                                  f"int32 {pwant[0][1]}, sums float64 {pwant[1][1]})")
+        if plan_stats is not None:
+            pl = into.plan
+            if plan_stats != (pl is not None):
+                raise ValueError(f"{who}: into must carry a PlanStats exactly when plan_stats is set (plan_stats = "
+                                 f"{bool(plan_stats)}, into.plan is {'given' if pl is not None else 'None'})")
+            if pl is not None and not (isinstance(pl, PlanStats) and fits((pl.counts, pl.sums), mwant)):
+                raise ValueError(f"{who}: into.plan must be a PlanStats of this engine (contiguous tensors on {self.device}: counts "
+                                 f"int32 {mwant[0][1]}, sums float64 {mwant[1][1]})")
         self._behind_torch_stream()      # (its tensors may have been touched on torch's current stream)
         return into
 
@@ -1107,34 +1198,109 @@ class SdcEngine:
                    _p(self.final_obs), self._stream(), refuses=True, wrote=(res.stats, res.returns, res.counts, pc, ps))
         return res
 
-    def evaluate(self, n_episodes: int, actions=None, *, actors: bool = False, sample: bool = False) -> EpisodeStats:
+    def rollout_cem_stats(self, n_steps: int, horizon: int, n_iters: int, n_candidates: int, n_elite: int, *, probs=None, best_seq=None,
+                          resume_steps: int = 0, warm_start: bool = True, seed: int = 0, draw: int = 0, alpha: float = 0.0,
+                          p_min: float = 0.0, fixed_action=(-1, -1, -1), idle_action=(1, 1, 2), reward_weights=(1.0, 1.0, 1.0),
+                          gamma: float = 1.0, info_weights=None, into: Optional[EpisodeStats] = None,
+                          plan_stats: bool = True) -> EpisodeStats:
+        """n_steps env-steps under receding-horizon control with the cross-entropy method, reduced on the device
+        (sdc_rollout_cem_stats): before every step the library plans as `plan_cem(K, n_iters, n_candidates, n_elite, ...)` does -- K =
+        `horizon` cut to what the episode has left, as CEMMPCAgent cuts it --, plays the best sequence's first action, and folds the
+        step into `rollout_stats`' EpisodeStats; one library call with no Python between the decisions.  What CEMMPCAgent does in a
+        loop of act() and step(), bit for bit: the decision schedule (planned or idle, fresh or warm-started from the last result moved
+        up by a step, draw + j for the j-th planned decision) is written out in include/sustaindc_hip.h.  The result's `plan` is a
+        PlanStats -- per env and agent the actions played, per env the predicted score, its gain over the iterations and the number of
+        planned / idle decisions (`plan_stats=False`: None) --, its `mpc` an MPCCarry.  `probs` float64 [horizon, N, 3, 3] and
+        `best_seq` int32 [horizon, N, 3]: the planner's arrays (None: new ones); with `resume_steps` = k > 0 they hold an earlier
+        decision's unshifted result of k steps (an earlier call's `mpc`), and the first planned decision continues from it.
+        `idle_action`: what an idle decision plays and a fresh incumbent holds.  seed, alpha, p_min, fixed_action and the objective:
+        `plan_cem`'s; plan terms and a plan forecast set on the engine apply to every decision.  `into`: an EpisodeStats of this
+        engine to continue, carrying a PlanStats exactly when `plan_stats` is set.  The engine moves; its single-step views follow the
+        last step; the envs' live mark is used up.  n_steps may reach the episode's end, where the auto-reset happens.  ValueError,
+        with the engine untouched, for malformed arguments and what the library refuses: what `rollout_stats` and `plan_cem` refuse
+        (the latter's horizon rules replaced by the schedule), horizon outside [1, MARK_MAX_STEPS], resume_steps outside [0, horizon]
+        or without the arrays, an idle_action outside 0..2."""
+        t = self.torch
+        who = "rollout_cem_stats"
+        H, N, M, n_it = int(horizon), self.n_envs, int(n_candidates), int(n_iters)
+        fixed = self._cem_fixed(who, fixed_action, seed, draw)
+        idle = [int(x) for x in idle_action]
+        if len(idle) != 3:
+            raise ValueError(f"{who}: idle_action must be three integers (ls, dc, bat), got {len(idle)}")
+        k_res = int(resume_steps)
+        if k_res < 0 or (k_res > 0 and (probs is None or best_seq is None)):
+            raise ValueError(f"{who}: resume_steps = {k_res} must not be negative, and resuming needs probs and best_seq")
+        obj = plan_objective(reward_weights, gamma, info_weights)
+        sized = 1 <= H <= L.MARK_MAX_STEPS and 2 <= M <= L.CEM_MAX_CAND and 1 <= n_it <= L.CEM_MAX_ITERS
+        if sized and probs is not None:
+            A.device_tensor(probs, who, "probs", t.float64, (H, N, 3, 3), device=self.device)
+        if sized and best_seq is not None:
+            A.device_tensor(best_seq, who, "best_seq", t.int32, (H, N, 3), device=self.device)
+        pl = bool(plan_stats)
+        res = self._stats_into(who, into, None, pl)
+        mpc = L.SdcMpcParams()
+        mpc.horizon, mpc.warm_start, mpc.resume, mpc.resume_steps = H, 1 if warm_start else 0, 1 if k_res > 0 else 0, k_res
+        mpc.idle_action[:] = idle
+        cem = mpc.cem
+        cem.n_iters, cem.iter0, cem.n_cand, cem.n_elite = n_it, 0, M, int(n_elite)
+        cem.fixed_action[:] = fixed
+        cem.draw, cem.seed, cem.alpha, cem.p_min = int(draw), int(seed), float(alpha), float(p_min)
+        arrays = [None] * 6
+        if sized:
+            self._behind_torch_stream()      # (a caller's probs / best_seq may have been filled by torch ops)
+            new = lambda shape, dtype: t.empty(shape, dtype=dtype, device=self.device)
+            arrays = [new((H, N, 3, 3), t.float64) if probs is None else probs, new((H, N, 3), t.int32) if best_seq is None else best_seq,
+                      new((n_it, N), t.float64), new((N, 3), t.int32), new((M, H, N, 3), t.int32), new((M, N), t.float64)]
+        pc, ps = (res.plan.counts, res.plan.sums) if pl else (None, None)
+        left = self.steps_to_episode_end()
+        self._call(self.lib.sdc_rollout_cem_stats, int(n_steps), C.byref(mpc), C.byref(obj), 0 if into is None else 1, _p(res.stats),
+                   _p(res.returns), _p(res.counts), _p(pc), _p(ps), *[_p(x) for x in arrays], *self._obs_ptrs, _p(self.rew),
+                   _p(self.done), _p(self.info), _p(self.final_obs), self._stream(), refuses=True,
+                   wrote=[res.stats, res.returns, res.counts, pc, ps] + arrays)
+        if not sized:
+            raise L.SdcError(f"{who}: sdc_rollout_cem_stats accepted H = {H}, M = {M}, I = {n_it} and no arrays")
+        plan = mpc_schedule(left, int(n_steps), H, self.config["auto_reset"], bool(warm_start), k_res)
+        res.mpc = MPCCarry(arrays[0], arrays[1], plan[-1][0], sum(1 for d in plan if d[1]), arrays[3], arrays[2])
+        return res
+
+    def evaluate(self, n_episodes: int, actions=None, *, actors: bool = False, sample: bool = False, mpc=None) -> EpisodeStats:
         """`n_episodes` whole episodes of the batch, one `rollout_stats` of episode_steps steps each -> an EpisodeStats whose tensors
         carry a leading [E] dimension (stats [E, 4, N, 44], returns [E, N, 3], counts [E, N, 2]).  The batch is reset first; between
         episodes the auto-reset starts the next one (auto_reset off: reset() is called).  actions: None (every slot on a built-in
         policy), an int32 device tensor [episode_steps, N, 3] replayed every episode, or a callable episode -> such a tensor.
         `actors=True`: the three actors (set_actor) play instead -- one `rollout_actor_stats` per episode, `sample` as there -- and
-        the result's `policy` is a PolicyStats with the same leading dimension; ValueError together with `actions`."""
+        the result's `policy` is a PolicyStats with the same leading dimension; ValueError together with `actions`.  `mpc=agent`: a
+        CEMMPCAgent plans every step -- one `agent.rollout_stats` (`rollout_cem_stats`) per episode, the agent's draw counter running
+        on from episode to episode -- and the result's `plan` is a PlanStats with the same leading dimension; ValueError together with
+        `actions` or `actors`."""
         t = self.torch
         E = int(n_episodes)
         if E < 1:
             raise ValueError(f"evaluate: n_episodes = {n_episodes} must be positive")
         if actors and actions is not None:
             raise ValueError("evaluate: actors=True plays the actors' own actions: give no actions")
-        if not actors and actions is None and any(p == 0 for p in self.policy):
+        if mpc is not None and (actors or actions is not None):
+            raise ValueError("evaluate: mpc= plays the planner's own actions: give neither actions nor actors")
+        if mpc is not None and not callable(getattr(mpc, "rollout_stats", None)):
+            raise ValueError("evaluate: mpc must be an agent with rollout_stats(env, n_steps) (dc_rl_amd.agents.CEMMPCAgent)")
+        if mpc is None and not actors and actions is None and any(p == 0 for p in self.policy):
             raise ValueError("evaluate: actions=None needs a built-in policy on every agent slot")
         self.reset()
         eps = []
         for e in range(E):
             if e > 0 and not self.config["auto_reset"]:
                 self.reset()
-            if actors:
+            if mpc is not None:
+                eps.append(mpc.rollout_stats(self, self.episode_steps))
+            elif actors:
                 eps.append(self.rollout_actor_stats(self.episode_steps, sample=sample))
             else:
                 a = actions(e) if callable(actions) else actions
                 eps.append(self.rollout_stats(a, n_steps=self.episode_steps))
         stack = lambda get: t.stack([get(x) for x in eps])
         pol = PolicyStats(stack(lambda x: x.policy.counts), stack(lambda x: x.policy.sums)) if actors else None
-        return EpisodeStats(stack(lambda x: x.stats), stack(lambda x: x.returns), stack(lambda x: x.counts), pol)
+        pln = PlanStats(stack(lambda x: x.plan.counts), stack(lambda x: x.plan.sums)) if mpc is not None else None
+        return EpisodeStats(stack(lambda x: x.stats), stack(lambda x: x.returns), stack(lambda x: x.counts), pol, plan=pln)
 
     def profile(self, every: int = 1):
         """Per-kernel HIP-event timing on the launch stream (measurement only): every k-th step, 0 = off."""

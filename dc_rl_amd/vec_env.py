@@ -680,15 +680,36 @@ class SustainDCVecEnv(ShareVecEnv):
         self._ready("rollout_actor_stats")
         return self._stats_done(self.engine.rollout_actor_stats(n_steps, sample=sample, into=into, policy_stats=policy_stats))
 
-    def evaluate(self, n_episodes, actions=None, *, actors=False, sample=False):
+    def rollout_cem_stats(self, n_steps, horizon, n_iters, n_candidates, n_elite, **kw):
+        """n_steps env-steps planned by the cross-entropy method inside the library, reduced on the device to an EpisodeStats with a
+        PlanStats (SdcEngine.rollout_cem_stats, which documents the arguments and the result; `probs` / `best_seq` are the engine's,
+        all three slots).  The envs move as under n_steps rounds of plan_cem() and step(); actions handed to step_async and not yet
+        stepped are dropped; the logger accumulator (accumulate_logger_sums) is left alone, as by rollout_stats.  ValueError when
+        this env trains an agent subset -- plan_cem + step() would play 1 in the other slots' columns, the library steps with the
+        planner's best_action of all three: the two would differ --, and for what the engine refuses."""
+        if self.n_agents != 3:
+            raise ValueError(f"rollout_cem_stats: this env trains {self.agents}; the library steps with the planner's best_action for all "
+                             "three agents, which is not what step() plays in the other slots' columns")
+        self._ready("rollout_cem_stats")
+        return self._stats_done(self.engine.rollout_cem_stats(n_steps, horizon, n_iters, n_candidates, n_elite, **kw))
+
+    def evaluate(self, n_episodes, actions=None, *, actors=False, sample=False, mpc=None):
         """`n_episodes` whole episodes of the batch from a reset (SdcEngine.evaluate) -> an EpisodeStats with a leading [E] dimension.
         `actions`: None (do-nothing baseline, see rollout_stats), an int tensor [episode_steps, num_envs, n_agents] replayed every
         episode, or a callable episode -> such a tensor.  `actors=True`: the three actors (set_actor) play, by their distributions'
-        mode or -- `sample` -- a draw, and the result carries a PolicyStats; ValueError together with `actions`.  The logger accumulator
+        mode or -- `sample` -- a draw, and the result carries a PolicyStats; ValueError together with `actions`.  `mpc=agent`: a
+        CEMMPCAgent plans every step inside the library (rollout_cem_stats), and the result carries a PlanStats; ValueError together
+        with `actions` or `actors`, and when this env trains an agent subset.  The logger accumulator
         (accumulate_logger_sums) is left alone.  Afterwards the envs stand at the start of a fresh episode when auto_reset is on;
         otherwise call reset()."""
         steps = self.episode_steps
-        if actors:
+        if mpc is not None:
+            if actors or actions is not None:
+                raise ValueError("evaluate: mpc= plays the planner's own actions: give neither actions nor actors")
+            if self.n_agents != 3:
+                raise ValueError(f"evaluate: this env trains {self.agents}; mpc= needs all three agents (rollout_cem_stats)")
+            res = self.engine.evaluate(n_episodes, mpc=mpc)
+        elif actors:
             if actions is not None:
                 raise ValueError("evaluate: actors=True plays the actors' own actions: give no actions")
             res = self.engine.evaluate(n_episodes, actors=True, sample=sample)

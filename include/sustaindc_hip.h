@@ -762,6 +762,62 @@ int sdc_rollout_actor_stats(sdc_handle* h, int n_steps, int sample, int accumula
                             int32_t* policy_counts, double* policy_sums, float* obs, float* share_obs, float* rew, uint8_t* done,
                             float* info, float* final_obs, void* stream);
 
+/* PLANNER EVALUATION: advance the engine by n_steps env-steps under receding-horizon control with the cross-entropy method -- before
+ * every step the library plans exactly as sdc_plan_cem does and then plays the first action of the best sequence found -- and hand back
+ * sdc_rollout_stats' per-env statistics of the steps taken, per env and agent what the planner played, and per env what it predicted.
+ * One call, ordered on `stream`, no device synchronisation (the handle's buffers are allocated on first use and when they have to grow)
+ * and no host wait between the decisions: the discount table of the whole call is staged once.  The engine ends where n_steps rounds of sdc_plan_cem followed
+ * by a one-step sdc_rollout_stats of best_action would leave it, the auto-reset at the episode's end included, and THE CALL USES UP THE
+ * ENVS' ONE LIVE MARK, as every plan call does.  The handle's plan terms and plan forecast apply to every decision.
+ * THE DECISION SCHEDULE (csrc/sdc_mpc_schedule.hpp).  H = mpc->horizon; for step t of the call let `left` be
+ * sdc_steps_to_episode_end() before that step and K_t = min(H, auto_reset ? left - 1 : left).  The decision is PLANNED iff left >= 2 and
+ * K_t >= 1; otherwise it is IDLE: idle_action is played, no draw is consumed and the carried distribution is dropped.  A planned
+ * decision starts FRESH -- probs = 1.0 / 3.0 (the double) everywhere, best_seq = idle_action -- when warm_start == 0; when it is the
+ * call's first planned decision and resume == 0; when the decision before it was idle; and when K_t exceeds the number of steps the
+ * carried result has.  Otherwise it starts from the carried result SHIFTED: steps 0 .. K_t - 2 take steps 1 .. K_t - 1, step K_t - 1 is
+ * uniform / idle_action.  resume == 1: probs / best_seq hold an earlier decision's unshifted result of resume_steps steps.  The j-th
+ * planned decision of the call (j = 0, 1, ...) is sdc_plan_cem with n_steps = K_t, the embedded cem parameters and draw = cem.draw + j
+ * (mod 2^32).  After the call probs[0:K] and best_seq[0:K] hold the last planned decision's result, unshifted, K its horizon; after a
+ * call whose last decision was idle they hold nothing a later call may resume from.
+ * PER STEP, in stream order: a planned decision is one sdc_mpc_start_kernel (csrc/sdc_mpc.hip: the fresh fill or the in-place shift),
+ * sdc_plan_cem's own launches (mark, I x (sample, M x (rollout, score, rewind), refit), the forecast's overlay) and one
+ * sdc_mpc_fold_kernel; an idle decision is one sdc_mpc_fold_kernel, which writes idle_action into best_action.  Then the step:
+ * sdc_rollout of one step with best_action into the handle's output block, and sdc_stats_reduce_kernel behind it; behind the call's
+ * last step sdc_stats_last_kernel fills the single-step arrays as for sdc_rollout_stats.  The planner's rollouts share the block with the
+ * step: the stream orders them.
+ * stats, returns, counts, accumulate and the single-step arrays: sdc_rollout_stats' contract and arithmetic, word for word.  The
+ * planner's arrays are sdc_plan_cem's with K read as H -- probs [H][N][3][3], best_seq [H][N][3], best_score [I][N], best_action [N][3],
+ * cand [M][H][N][3], cand_score [M][N] --; a decision with K < H uses the contiguous [K]... prefix of each, so best_score, cand and
+ * cand_score hold the last planned decision's and best_action the last action played.  The plan statistics are the device's, and
+ * either both or neither is given:
+ *   plan_counts [N][3][SDC_POLICY_COUNTS] int32, sdc_policy_count's entries of the actions PLAYED, idle decisions included: with j the
+ *               action,  N_j += 1;  SWITCHES += (LAST >= 0 && j != LAST) ? 1 : 0;  LAST = j
+ *   plan_sums   [N][SDC_PLAN_SUMS] fp64, 16-byte aligned: on a planned decision  SCORE += best_score[I-1][n];  GAIN +=
+ *               best_score[I-1][n] - best_score[0][n];  PLANNED += 1.0;  on an idle one  IDLE += 1.0  and nothing else.  fp64, in
+ *               step order, no fused operation
+ * accumulate == 0:  N0 = N1 = N2 = SWITCHES = 0, LAST = -1, the sums 0.0;  accumulate == 1: continue from what the arrays hold.
+ * Refused (-2 and a message, nothing enqueued, the engine untouched), all before the first launch: what sdc_rollout_stats refuses except
+ * what concerns `actions` (n_steps > sdc_steps_to_episode_end() among it); what sdc_plan_cem refuses about its parameters, objective and
+ * arrays (its horizon and auto-reset rules are replaced by the schedule above; a forecast's needs are asked for the longest decision);
+ * a null mpc; horizon outside [1, SDC_MARK_MAX_STEPS]; warm_start or resume outside {0, 1}; resume_steps outside [1, horizon] while
+ * resuming; an idle_action outside 0..2; one of plan_counts / plan_sums without the other; plan_sums not 16-byte aligned; probs or
+ * best_score or cand_score not 8-byte aligned, plan_counts or another int32 array not dword-aligned. */
+#define SDC_PLAN_SUMS 4
+enum sdc_plan_sum { SDC_PLAN_SCORE = 0, SDC_PLAN_GAIN, SDC_PLAN_PLANNED, SDC_PLAN_IDLE };
+typedef struct {
+  int32_t horizon;         /* H in [1, SDC_MARK_MAX_STEPS] */
+  int32_t warm_start;      /* 0: every planned decision starts fresh; 1: from the carried result shifted where the schedule allows */
+  int32_t resume;          /* 1: probs / best_seq hold an earlier decision's unshifted result */
+  int32_t resume_steps;    /* ... of this many steps, in [1, H] (read only while resuming) */
+  int32_t idle_action[3];  /* each 0..2: what an idle decision plays, and a fresh best_seq */
+  int32_t reserved;
+  sdc_cem_params cem;      /* sdc_plan_cem's parameters; draw: the first planned decision's */
+} sdc_mpc_params;
+int sdc_rollout_cem_stats(sdc_handle* h, int n_steps, const sdc_mpc_params* mpc, const sdc_plan_objective* objective, int accumulate,
+                          double* stats, double* returns, int32_t* counts, int32_t* plan_counts, double* plan_sums, double* probs,
+                          int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* cand, double* cand_score, float* obs,
+                          float* share_obs, float* rew, uint8_t* done, float* info, float* final_obs, void* stream);
+
 /* Per-kernel timing (measurement only; off by default).  enable = k > 0 samples every k-th sdc_step, 0 switches it
  * off.  In a sampled step one lane per workgroup of each kernel stamps the device's constant-rate wall clock at
  * entry and exit; sdc_profile_read synchronises the device and accumulates, per sampled launch,

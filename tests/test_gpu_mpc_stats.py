@@ -1,0 +1,427 @@
+"""Planner evaluation on the device (SdcEngine.rollout_cem_stats / evaluate(mpc=), CEMMPCAgent.rollout_stats, SustainDCVecEnv.rollout_cem_stats
+/ evaluate over sdc_rollout_cem_stats) held to the Python loop it replaces.
+
+THE REFERENCE throughout is a twin engine with the same seed, driven by that loop: `a = CEMMPCAgent(...).act(twin)`, then
+`twin.rollout_stats(a[None], into=ref)`; its plan arrays are restated in torch in step order from the agent's `last.action` /
+`last.best_score` (`_loop`).
+
+THE BAR is every bit: stats, returns, counts; plan_counts and plan_sums (fp64 additions and one subtraction in step order, no fused
+operation possible); the final probs / best_seq prefix and best_action; the engines' states and single-step views (tests/test_gpu_mark.py
+_same_state / _same_out).  info[reserved] is left out between two engines, as in tests/test_gpu_stats.py.  No case is excluded from any
+comparison.
+
+ 1. 10 steps from a reset at 6 envs (18 lanes: one partial wavefront of the two kernels) and 130 (390 lanes: full wavefronts and a partial
+    one), warm start on and off;  2. the chunked output block (debug_flags bit 14: every horizon of 4 is rolled out 2 + 2);  3. continuation:
+    5 steps, then 5 more with `into=`, `resume_steps` and the returned arrays, and `agent.act()` behind `agent.rollout_stats`;  4. the
+    episode's end: the horizon shrinks 4, 4, 4, 3, 2, 1, the last step idles and auto-resets, and the call after it starts fresh;  5. a
+    persistence forecast, a limit and a terminal term;  6. a fixed action, alpha and p_min;  7. the refusals, each of which leaves the
+    engine, the launch counter and the caller's arrays untouched;  8. through the vector env: evaluate(mpc=), the agent-subset ValueError,
+    copy.deepcopy.
+
+96-step episodes, rings of 128 keys, auto-reset on, H = 4, M = 4, E = 2, I = 2."""
+import copy
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+from dc_rl_amd import _lib as L
+from dc_rl_amd import CEMMPCAgent, EpisodeStats, PlanStats, SustainDCVecEnv
+from tests.plan_util import refused
+from tests.test_gpu_actor_stats import _engine as _actor_engine
+from tests.test_gpu_mark import _same_out, _same_state
+from tests.test_gpu_stats import _bits
+
+pytestmark = pytest.mark.gpu
+
+EP, H, M, E, I = 96, 4, 4, 2, 2
+RSV = L.INFO_IDX["reserved"]
+COLS = [c for c in range(L.INFO_DIM) if c != RSV]
+CEM = dict(n_candidates=M, n_elite=E, n_iters=I, horizon=H, seed=77)
+
+
+def _engine(N, **kw):
+    return _actor_engine(N, actors=None, **kw)
+
+
+def _agent(cls=CEMMPCAgent, **kw):
+    return cls(**dict(CEM, **kw))
+
+
+def _loop(twin, agent, n, ref=None, plan=None):
+    """n rounds of the loop that exists today on `twin` -> (the EpisodeStats, (plan counts [N, 3, 5], plan sums [N, 4]) restated in step
+    order, the last actions); `ref` / `plan`: an earlier call's, to continue"""
+    import torch
+    N, dev = twin.n_envs, twin.device
+    if plan is None:
+        counts = torch.zeros((N, 3, 5), dtype=torch.int32, device=dev)
+        counts[..., L.POLICY_LAST] = -1
+        sums = torch.zeros((N, 4), dtype=torch.float64, device=dev)
+    else:
+        counts, sums = plan[0].clone(), plan[1].clone()
+    which = torch.arange(3, dtype=torch.int32, device=dev)
+    a = None
+    for _ in range(n):
+        a = agent.act(twin)
+        ref = twin.rollout_stats(a[None], into=ref)
+        last = counts[..., L.POLICY_LAST]
+        counts[..., :3] += (a[..., None] == which).to(torch.int32)
+        counts[..., L.POLICY_SWITCHES] += ((last >= 0) & (a != last)).to(torch.int32)
+        counts[..., L.POLICY_LAST] = a
+        if agent.last is not None:
+            s = agent.last.best_score
+            sums[:, L.PLAN_SCORE] = sums[:, L.PLAN_SCORE] + s[-1]
+            sums[:, L.PLAN_GAIN] = sums[:, L.PLAN_GAIN] + (s[-1] - s[0])
+            sums[:, L.PLAN_PLANNED] = sums[:, L.PLAN_PLANNED] + 1.0
+        else:
+            sums[:, L.PLAN_IDLE] = sums[:, L.PLAN_IDLE] + 1.0
+    return ref, (counts, sums), a.clone()
+
+
+def _assert_call(got, ref, plan, action, agent, what):
+    """a rollout_cem_stats result against the loop's: every bit of the statistics, the plan arrays, the carried prefix, the last action"""
+    import torch
+    assert isinstance(got, EpisodeStats) and isinstance(got.plan, PlanStats) and got.policy is None
+    N = ref.counts.shape[0]
+    assert got.plan.counts.shape == (N, 3, L.POLICY_COUNTS) and got.plan.counts.dtype == torch.int32 and got.plan.counts.is_cuda
+    assert got.plan.sums.shape == (N, L.PLAN_SUMS) and got.plan.sums.dtype == torch.float64
+    assert torch.equal(_bits(got.stats[..., COLS]), _bits(ref.stats[..., COLS])), (what, "stats")
+    assert torch.equal(_bits(got.returns), _bits(ref.returns)), (what, "returns")
+    assert torch.equal(got.counts, ref.counts), (what, "counts")
+    if not torch.equal(got.plan.counts, plan[0]):
+        bad = (got.plan.counts != plan[0]).nonzero()
+        raise AssertionError((what, "plan_counts", len(bad), bad[:4].tolist()))
+    if not torch.equal(_bits(got.plan.sums), _bits(plan[1])):
+        bad = (_bits(got.plan.sums) != _bits(plan[1])).nonzero()
+        raise AssertionError((what, "plan_sums", len(bad), bad[:4].tolist(), got.plan.sums[:2].tolist(), plan[1][:2].tolist()))
+    c = got.mpc
+    assert c.steps == agent.last_horizon, (what, c.steps, agent.last_horizon)
+    if c.steps:
+        assert torch.equal(_bits(c.probs[:c.steps]), _bits(agent._probs)), (what, "probs")
+        assert torch.equal(c.best_seq[:c.steps], agent._best_seq), (what, "best_seq")
+        assert torch.equal(_bits(c.best_score), _bits(agent.last.best_score)), (what, "best_score")
+    assert torch.equal(c.best_action, action), (what, "best_action")
+
+
+def _assert_engines(e, twin, what):
+    _same_state(e, twin, what)
+    _same_out(e, twin, what)
+
+
+def _call(e, n, agent_kw=None, **kw):
+    """rollout_cem_stats on e with the shared CEM parameters"""
+    p = dict(CEM, **(agent_kw or {}))
+    return e.rollout_cem_stats(n, p["horizon"], p["n_iters"], p["n_candidates"], p["n_elite"], seed=p["seed"],
+                               **{k: v for k, v in p.items() if k in ("alpha", "p_min", "warm_start")}, **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(N, warm):
+    """the 10-step run from a reset that cases 1 to 3 share at N envs: the twin, its agent and the loop's results -- computed once, never
+    changed afterwards"""
+    twin, agent = _engine(N), _agent(warm_start=warm)
+    return (twin, agent) + _loop(twin, agent, 10)
+
+
+@pytest.mark.parametrize("N", [6, 130])
+@pytest.mark.parametrize("warm", [True, False])
+def test_ten_steps_from_a_reset_equal_the_python_loop(N, warm):
+    twin, agent, ref, plan, action = _reference(N, warm)
+    e = _engine(N)
+    got = _call(e, 10, dict(warm_start=warm))
+    _assert_call(got, ref, plan, action, agent, f"N = {N}, warm_start = {warm}")
+    _assert_engines(e, twin, f"N = {N}, warm_start = {warm}")
+    assert got.mpc.planned == 10 == agent.draw
+    assert bool((got.plan.planned == 10.0).all()) and bool((got.plan.idle == 0.0).all()) and bool((got.steps == 10).all())
+    s = got.plan.summary()
+    assert np.allclose(s["per_env"]["action_frequency"].sum(-1), 1.0) and np.array_equal(s["planned"], np.full(N, 10))
+    assert bool((got.plan.gain >= 0.0).all())      # the incumbent's score never falls from one iteration to the next
+
+
+def test_the_chunked_output_block_changes_nothing():
+    N = 6
+    twin, agent, ref, plan, action = _reference(N, True)
+    e = _engine(N, debug_flags=L.PLAN_DEBUG_TWO_STEPS)
+    got = _call(e, 10)
+    _assert_call(got, ref, plan, action, agent, "two-step block")
+    _assert_engines(e, twin, "two-step block")
+    nostats = _call(_engine(N), 10, plan_stats=False)
+    import torch
+    assert nostats.plan is None and torch.equal(_bits(nostats.returns), _bits(ref.returns)) and nostats.mpc.planned == 10
+
+
+def test_continuation_with_into_and_the_returned_arrays_and_act_behind_rollout_stats():
+    import torch
+    N = 6
+    twin, agent, ref, plan, action = _reference(N, True)
+    e = _engine(N)
+    first = _call(e, 5)
+    assert first.mpc.steps == H and first.mpc.planned == 5
+    got = _call(e, 5, into=first, probs=first.mpc.probs, best_seq=first.mpc.best_seq, resume_steps=first.mpc.steps, draw=first.mpc.planned)
+    assert got is first
+    _assert_call(got, ref, plan, action, agent, "5 + 5")
+    _assert_engines(e, twin, "5 + 5")
+    # the agent's own call, split 3 + 4 + 3, and then act() on both sides
+    e2, mine = _engine(N), _agent()
+    st = mine.rollout_stats(e2, 3)
+    st = mine.rollout_stats(e2, 4, into=st)
+    st = mine.rollout_stats(e2, 3, into=st)
+    _assert_call(st, ref, plan, action, agent, "agent 3 + 4 + 3")
+    assert (mine.draw, mine.last_horizon, mine._step) == (agent.draw, agent.last_horizon, agent._step) and mine.last is None
+    twin2, theirs = _engine(N), _agent()
+    _loop(twin2, theirs, 10)
+    a, b = mine.act(e2), theirs.act(twin2)
+    assert torch.equal(a, b) and mine.draw == theirs.draw == 11
+    assert torch.equal(_bits(mine.last.probs), _bits(theirs.last.probs)) and torch.equal(mine.last.best_seq, theirs.last.best_seq)
+    assert torch.equal(_bits(mine.last.best_score), _bits(theirs.last.best_score))
+    e2.step(a), twin2.step(b)
+    _assert_engines(e2, twin2, "the step behind act()")
+
+
+def test_the_episodes_end_inside_the_call_and_the_call_after_it():
+    import torch
+    N = 6
+    e, twin = _engine(N), _engine(N)
+    g = torch.Generator(device="cpu").manual_seed(9)
+    acts = torch.randint(0, 3, (EP - 7, N, 3), generator=g, dtype=torch.int32).to(e.device)
+    e.rollout_stats(acts), twin.rollout_stats(acts)
+    assert e.steps_to_episode_end() == 7
+    agent, mine = _agent(), _agent()
+    ref, plan, action = _loop(twin, agent, 7)
+    got = mine.rollout_stats(e, 7)
+    _assert_call(got, ref, plan, action, agent, "to the episode's end")
+    _assert_engines(e, twin, "to the episode's end")
+    assert e.steps_to_episode_end() == EP and bool(e.done.bool().all())      # the auto-reset is inside the call
+    assert bool((got.plan.idle == 1.0).all()) and bool((got.plan.planned == 6.0).all())
+    assert got.mpc.planned == 6 and got.mpc.steps == 0 and mine.draw == agent.draw == 6
+    assert torch.equal(action, torch.tensor([1, 1, 2], dtype=torch.int32, device=e.device).expand(N, 3))
+    assert mine._probs is None and mine.last_horizon == 0
+    # the next call starts fresh, in the new episode
+    ref, plan, action = _loop(twin, agent, 3)
+    got = mine.rollout_stats(e, 3)
+    _assert_call(got, ref, plan, action, agent, "the call after the reset")
+    _assert_engines(e, twin, "the call after the reset")
+    assert mine.draw == 9 and bool((got.plan.idle == 0.0).all())
+
+
+def test_a_forecast_a_limit_and_a_terminal_term_apply_to_every_decision():
+    N = 6
+    e, twin = _engine(N), _engine(N)
+    for x in (e, twin):
+        x.set_plan_terms(limits={"dc_int_temperature": (None, 24.0, 1.5)}, terminal={"ls_tasks_in_queue": -0.002})
+    kw = dict(forecast="persistence", gamma=0.95, reward_weights=(1.0, 0.5, 2.0), info_weights={"bat_CO2_footprint": -1e-3})
+    agent, mine = _agent(**kw), _agent(**kw)
+    ref, plan, action = _loop(twin, agent, 6)
+    got = mine.rollout_stats(e, 6)
+    assert e.plan_forecast["carbon"] == "persistence"
+    _assert_call(got, ref, plan, action, agent, "forecast and terms")
+    _assert_engines(e, twin, "forecast and terms")
+    # ... and they matter: the same steps without them are planned differently
+    import torch
+    plain = _call(_engine(N), 6)
+    assert not torch.equal(_bits(plain.plan.sums), _bits(got.plan.sums))
+
+
+class _FixedDc(CEMMPCAgent):
+    """the agent with agent_dc's action fixed to 1 in every sampled candidate"""
+
+    def _plan(self, env, K, **kw):
+        return super()._plan(env, K, fixed_action=(-1, 1, -1), **kw)
+
+
+def test_a_fixed_action_alpha_and_p_min():
+    N = 6
+    e, twin = _engine(N), _engine(N)
+    agent = _agent(_FixedDc, alpha=0.3, p_min=0.05)
+    ref, plan, action = _loop(twin, agent, 6)
+    got = _call(e, 6, dict(alpha=0.3, p_min=0.05), fixed_action=(-1, 1, -1))
+    _assert_call(got, ref, plan, action, agent, "fixed action")
+    _assert_engines(e, twin, "fixed action")
+    assert bool((got.plan.action_counts[:, 1, 1] == 6).all())      # agent_dc held its set-point throughout
+
+
+# ---- refusals ---------------------------------------------------------------------------------------------------------------------
+def _raw(e, keep, n_steps=2, accumulate=0, null_mpc=False, mpc=None, null=(), offset=None, objective=None):
+    """sdc_rollout_cem_stats on e through ctypes: valid arguments but for what is asked for -- `mpc`: fields of sdc_mpc_params, `null`:
+    arrays passed as NULL, `offset`: array -> bytes its address is moved by; ValueError(the message) on -2.  `keep`: the caller's dict
+    the arrays are put into (they hold 7s)"""
+    import torch
+    N, dev = e.n_envs, e.device
+    shapes = dict(stats=((4, N, L.INFO_DIM), torch.float64), returns=((N, 3), torch.float64), counts=((N, 2), torch.int32),
+                  plan_counts=((N, 3, 5), torch.int32), plan_sums=((N, 4), torch.float64), probs=((H, N, 3, 3), torch.float64),
+                  best_seq=((H, N, 3), torch.int32), best_score=((I, N), torch.float64), best_action=((N, 3), torch.int32),
+                  cand=((M, H, N, 3), torch.int32), cand_score=((M, N), torch.float64))
+    for nm, (shape, dtype) in shapes.items():
+        keep[nm] = torch.full((int(np.prod(shape)) + 4,), 7, dtype=dtype, device=dev)      # (room for a moved address)
+    p = L.SdcMpcParams()
+    p.horizon, p.warm_start, p.resume, p.resume_steps = H, 1, 0, 0
+    p.idle_action[:] = [1, 1, 2]
+    p.cem.n_iters, p.cem.n_cand, p.cem.n_elite, p.cem.seed = I, M, E, 77
+    p.cem.fixed_action[:] = [-1, -1, -1]
+    for k, v in (mpc or {}).items():
+        if k == "idle_action":
+            p.idle_action[:] = v
+        else:
+            setattr(p, k, v)
+    ptr = lambda nm: None if nm in null else C.c_void_p(keep[nm].data_ptr() + (offset or {}).get(nm, 0))
+    outs = dict(obs=e.obs, share_obs=e.share_obs, rew=e.rew, done=e.done, info=e.info, final_obs=e.final_obs)
+    optr = lambda nm: None if nm in null else C.c_void_p(outs[nm].data_ptr() + (offset or {}).get(nm, 0))
+    torch.cuda.synchronize()
+    rc = e.lib.sdc_rollout_cem_stats(e._h, n_steps, None if null_mpc else C.byref(p), objective, accumulate, *[ptr(nm) for nm in shapes],
+                                     *[optr(nm) for nm in outs], e._stream())
+    assert rc == -2, rc
+    torch.cuda.synchronize()
+    for nm in shapes:
+        assert bool((keep[nm] == 7).all()), nm      # the caller's arrays: untouched
+    raise ValueError(e.lib.sdc_last_error().decode())
+
+
+def test_refusals_leave_the_engine_the_launch_counter_and_the_arrays_untouched():
+    import torch
+    from tests.plan_util import objective, refusal_engines
+    N = 6
+    a, b, fresh, verify, late = refusal_engines(N, alongside=1)      # a, b: 38 steps left of 48; late: 2 left, no auto-reset
+    keep = {}
+    raw = lambda match, eng=a, **kw: refused(eng, match, lambda: _raw(eng, keep, **kw))
+    # sdc_rollout_stats' own, but for `actions`
+    raw("n_steps = 0 must be positive", n_steps=0)
+    raw("null array", null=("stats",))
+    raw("null array", null=("share_obs",))
+    raw("stats / returns not 16-byte aligned", offset={"returns": 8})
+    raw("not dword-aligned", offset={"counts": 2})
+    raw("accumulate = 2", accumulate=2)
+    raw("sdc_reset must be called first", eng=fresh)
+    raw("verify mode", eng=verify)
+    raw("past the end of an episode", n_steps=39)
+    raw("past the end of an episode", eng=late, n_steps=3)
+    # the parameter struct
+    raw("null mpc", null_mpc=True)
+    raw("horizon = 0 outside", mpc=dict(horizon=0))
+    raw("horizon = 257 outside", mpc=dict(horizon=L.MARK_MAX_STEPS + 1))
+    raw("warm_start = 2", mpc=dict(warm_start=2))
+    raw("resume = -1", mpc=dict(resume=-1))
+    raw("resume_steps = 0 outside", mpc=dict(resume=1, resume_steps=0))
+    raw("resume_steps = 5 outside", mpc=dict(resume=1, resume_steps=H + 1))
+    raw(r"idle_action\[2\] = 3", mpc=dict(idle_action=[1, 1, 3]))
+    raw(r"idle_action\[0\] = -1", mpc=dict(idle_action=[-1, 1, 2]))
+    # sdc_plan_cem's parameters, objective and arrays
+    for field, bad, match in (("n_iters", 0, "n_iters"), ("iter0", -1, "iter0"), ("iter0", 65535, "iter0"), ("n_cand", 1, "n_cand"),
+                              ("n_cand", L.CEM_MAX_CAND + 1, "n_cand"), ("n_elite", 0, "n_elite"), ("n_elite", M + 1, "n_elite"),
+                              ("alpha", 1.0, "alpha"), ("alpha", -0.1, "alpha"), ("p_min", 0.5, "p_min"), ("p_min", float("nan"), "p_min")):
+        raw(match, mpc={"cem": _cem(**{field: bad})})
+    raw(r"fixed_action\[1\] = 3", mpc={"cem": _cem(fixed_action=(-1, 3, -1))})
+    for nm in ("probs", "best_seq", "best_score", "best_action", "cand", "cand_score"):
+        raw("null array", null=(nm,))
+    raw("gamma", objective=C.byref(_objective(gamma=0.0)))
+    raw("gamma", objective=C.byref(_objective(gamma=1.5)))
+    raw("n_cols", objective=C.byref(objective(L.PLAN_MAX_COLS + 1, 0)))
+    raw("info column", objective=C.byref(objective(1, L.INFO_DIM)))
+    # the plan statistics and the alignments
+    raw("given together or not at all", null=("plan_counts",))
+    raw("given together or not at all", null=("plan_sums",))
+    raw("plan_sums not 16-byte aligned", offset={"plan_sums": 8})
+    raw("plan_counts not dword-aligned", offset={"plan_counts": 2})
+    raw("not 8-byte aligned", offset={"probs": 4})
+    raw("not 8-byte aligned", offset={"cand_score": 4})
+    raw("not dword-aligned", offset={"best_seq": 2})
+    raw("not dword-aligned", offset={"obs": 2})
+    # a forecast whose values are too short for the longest decision
+    a.set_plan_forecast(carbon="values", values=torch.zeros((H + 1, N, 4), dtype=torch.float64, device=a.device))
+    raw("entries")
+    a.set_plan_forecast()
+    # through the binding: ValueError before the library is asked, or from it
+    call = lambda **kw: (lambda: _call(a, kw.pop("n", 2), **kw))
+    refused(a, "three integers", call(idle_action=(1, 1)))
+    refused(a, "three integers", call(fixed_action=(1, 1)))
+    refused(a, "resuming needs probs and best_seq", call(resume_steps=2))
+    refused(a, "must not be negative", call(resume_steps=-1))
+    refused(a, "probs", call(probs=torch.zeros((H - 1, N, 3, 3), dtype=torch.float64, device=a.device)))
+    refused(a, "at most 8", call(info_weights={k: 1.0 for k in L.INFO_COLS[:9]}))
+    refused(a, "horizon = 300", lambda: a.rollout_cem_stats(2, 300, I, M, E))
+    refused(a, "n_cand = 65", lambda: a.rollout_cem_stats(2, H, I, L.CEM_MAX_CAND + 1, E))
+    refused(a, "exactly when plan_stats", call(into=a.rollout_stats(torch.ones((1, N, 3), dtype=torch.int32, device=a.device))))
+    b.rollout_stats(torch.ones((1, N, 3), dtype=torch.int32, device=a.device))
+    # the launch counter: the twin that was refused nothing runs the loop, the refused engine the call -- the same bits
+    agent = _agent()
+    ref, plan, action = _loop(b, agent, 3)
+    got = _call(a, 3)
+    _assert_call(got, ref, plan, action, agent, "behind the refusals")
+    _assert_engines(a, b, "behind the refusals")
+
+
+def _cem(**kw):
+    c = L.SdcCemParams()
+    c.n_iters, c.n_cand, c.n_elite, c.seed = I, M, E, 77
+    c.fixed_action[:] = [-1, -1, -1]
+    for k, v in kw.items():
+        if k == "fixed_action":
+            c.fixed_action[:] = v
+        else:
+            setattr(c, k, v)
+    return c
+
+
+def _objective(gamma):
+    o = L.SdcPlanObjective()
+    o.reward_weight[:] = [1.0, 1.0, 1.0]
+    o.gamma = gamma
+    return o
+
+
+# ---- the vector env ---------------------------------------------------------------------------------------------------------------
+ARGS = {"location": "ny", "month": 6, "days_per_episode": 1, "partial_obs": True, "nonoverlapping_shared_obs_space": True}
+
+
+def _vec(N, **extra):
+    return SustainDCVecEnv(dict(ARGS, **extra), n_envs=N, seed=3, months=[6] * N, return_torch=True)
+
+
+def _same_bits(x, y, what):
+    import torch
+    assert torch.equal(_bits(x.stats[..., COLS]), _bits(y.stats[..., COLS])), (what, "stats")
+    assert torch.equal(_bits(x.returns), _bits(y.returns)) and torch.equal(x.counts, y.counts), (what, "returns / counts")
+    assert torch.equal(x.plan.counts, y.plan.counts) and torch.equal(_bits(x.plan.sums), _bits(y.plan.sums)), (what, "plan")
+
+
+def test_vec_env_evaluate_with_the_planner_the_subset_refusal_and_a_deepcopy():
+    import torch
+    N, EPS = 6, 2
+    a, b = _vec(N), _vec(N)
+    assert a.episode_steps == EP
+    with pytest.raises(ValueError, match="call reset"):
+        a.rollout_cem_stats(2, H, I, M, E)
+    got = a.evaluate(EPS, mpc=_agent())
+    assert got.stats.shape == (EPS, 4, N, L.INFO_DIM) and got.returns.shape == (EPS, N, 3) and got.counts.shape == (EPS, N, 2)
+    assert isinstance(got.plan, PlanStats) and got.plan.counts.shape == (EPS, N, 3, 5) and got.plan.sums.shape == (EPS, N, 4)
+    assert got.policy is None and bool((got.steps == EP).all())
+    assert bool((got.plan.planned == EP - 1.0).all()) and bool((got.plan.idle == 1.0).all())
+    s = got.plan.summary()
+    assert s["per_env"]["mean_score"].shape == (EPS, N) and s["batch"]["action_frequency"].shape == (EPS, 3, 3)
+    # ... equals two single calls from a reset, the agent's draw counter running on
+    b.reset()
+    theirs = _agent()
+    for ep in range(EPS):
+        one = theirs.rollout_stats(b, EP)
+        _same_bits(EpisodeStats(got.stats[ep], got.returns[ep], got.counts[ep], plan=PlanStats(got.plan.counts[ep], got.plan.sums[ep])), one,
+                   f"episode {ep}")
+    assert theirs.draw == EPS * (EP - 1)
+    _same_state(a.engine, b.engine, "evaluate against two calls")
+    _same_out(a.engine, b.engine, "evaluate against two calls")
+    for bad in (dict(actors=True), dict(actions=torch.ones((EP, N, 3), dtype=torch.int32))):
+        with pytest.raises(ValueError, match="neither actions nor actors"):
+            a.evaluate(1, mpc=_agent(), **bad)
+    # an agent subset: the other slots' stepped actions would differ from the planner's best_action
+    sub = _vec(4, agents=["agent_dc", "agent_bat"])
+    sub.reset()
+    with pytest.raises(ValueError, match="best_action"):
+        sub.rollout_cem_stats(2, H, I, M, E)
+    with pytest.raises(ValueError, match="all three agents"):
+        sub.evaluate(1, mpc=_agent())
+    sub.close()
+    # a copy of the env afterwards evaluates identically
+    c = copy.deepcopy(a)
+    x, y = a.evaluate(1, mpc=_agent(seed=5)), c.evaluate(1, mpc=_agent(seed=5))
+    _same_bits(x, y, "the copy's evaluate")
+    for v in (a, b, c):
+        v.close()
