@@ -17,7 +17,9 @@ Public surface (mirrors the reference's names for this path):
   * `PolicyStats`                                  -- what the in-kernel actors did over those steps: action counts, switches, entropy,
                                                       log-probability (`SdcEngine.rollout_actor_stats` / `evaluate(actors=True)`)
   * `PlanStats`                                    -- what the CEM planner did over those steps: action counts, switches, predicted
-                                                      score, gain (`SdcEngine.rollout_cem_stats` / `evaluate(mpc=agent)`)
+                                                      score, gain (`SdcEngine.rollout_cem_stats` / `evaluate(mpc=agent)`); per
+                                                      replica group, with the count of replicas that diverged, from
+                                                      `SdcEngine.rollout_cem_groups_stats` / `evaluate(mpc=group_agent)`
 
 The compute path is the HIP extension `csrc/libsustaindc_hip.so` (hand-written gfx950 kernels).  There is
 no CPU fallback: constructing an engine without the extension or without an MI355X raises.

@@ -24,7 +24,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
            "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip", "sdc_plan_terms.hip",
-           "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip"]
+           "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip", "sdc_mpc_groups.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
@@ -211,6 +211,14 @@ class SdcMpcParams(C.Structure):
     ]
 
 
+class SdcMpcGroupParams(C.Structure):
+    """The receding-horizon loop's parameters of one sdc_rollout_cem_groups_stats call (include/sustaindc_hip.h sdc_mpc_group_params)."""
+    _fields_ = [
+        ("horizon", C.c_int32), ("warm_start", C.c_int32), ("resume", C.c_int32), ("resume_steps", C.c_int32),
+        ("idle_action", C.c_int32 * 3), ("sync_first", C.c_int32), ("cem", SdcCemGroupParams),
+    ]
+
+
 EXPORTS = [
     "sdc_last_error", "sdc_version", "sdc_create", "sdc_destroy", "sdc_set_seed", "sdc_weather_window_len", "sdc_set_tables",
     "sdc_set_dc_params", "sdc_assign_envs", "sdc_reset", "sdc_step", "sdc_rollout", "sdc_steps_to_episode_end",
@@ -222,7 +230,7 @@ EXPORTS = [
     "sdc_mark_row_bytes", "sdc_mark_envs", "sdc_rewind_envs", "sdc_plan", "sdc_plan_cem", "sdc_rollout_stats",
     "sdc_plan_cem_groups", "sdc_set_plan_terms", "sdc_get_plan_terms",
     "sdc_set_plan_forecast", "sdc_get_plan_forecast", "sdc_forecast_traces", "sdc_rollout_actor_stats",
-    "sdc_rollout_cem_stats",
+    "sdc_rollout_cem_stats", "sdc_rollout_cem_groups_stats",
 ]
 
 
@@ -392,6 +400,8 @@ def load():
     L.sdc_rollout_actor_stats.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp]
     L.sdc_rollout_cem_stats.argtypes = [vp, C.c_int, C.POINTER(SdcMpcParams), C.POINTER(SdcPlanObjective), C.c_int, vp, vp, vp, vp, vp, vp,
                                         vp, vp, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp]
+    L.sdc_rollout_cem_groups_stats.argtypes = [vp, C.c_int, C.POINTER(SdcMpcGroupParams), C.POINTER(SdcPlanObjective), C.c_int] + [vp] * 13 + [
+        fp, fp, fp, vp, fp, fp, vp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

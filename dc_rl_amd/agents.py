@@ -327,5 +327,39 @@ class GroupCEMMPCAgent(CEMMPCAgent):
         return res.step_actions
 
     def rollout_stats(self, env, n_steps, into=None):
-        raise NotImplementedError("GroupCEMMPCAgent.rollout_stats: the closed loop in the library plans per env (CEMMPCAgent); the "
-                                  "replica-group form needs sync_groups after every reset and is not built")
+        """n_steps decisions and steps in ONE library call (SdcEngine.rollout_cem_groups_stats / SustainDCVecEnv.rollout_cem_groups_stats)
+        with this agent's parameters and carried state -> the call's EpisodeStats, its `plan` a PlanStats per group with `diverged`.
+        What n_steps rounds of `act(env)` and a step with its actions do, bit for bit: the call syncs the groups inside the library
+        exactly when `act` would call `sync_groups` -- on the first decision, and when the episode step has gone backwards --, counts it
+        in `syncs` and drops the carried result.  n_steps may reach the episode's end, not cross it: one call per episode.  Afterwards
+        `draw`, the carried distribution, `last_horizon` and the step it was made at are what those rounds would have left, so `act()`
+        may follow (`last` is None).  `into`: an EpisodeStats of the env's to continue.  The engine's arguments are checked first: a
+        refused call leaves the agent as it was, but for a `forecast`, which is set on the env before the first decision."""
+        import torch
+        eng = getattr(env, "engine", env)
+        n_steps = int(n_steps)
+        step = _mpc_horizon(env, self.horizon)[1]
+        if not self._forecast_set:
+            _set_forecast(env, self.forecast)
+            self._forecast_set = True
+        H, R = self.horizon, self.group_size
+        G = eng.n_envs // R
+        sync = self._step is None or step < self._step      # (_before's rule)
+        carried = not sync and self.warm_start and self._probs is not None and step > self._step
+        probs = torch.empty((H, G, 3, 3), dtype=torch.float64, device=eng.device)
+        best_seq = torch.empty((H, G, 3), dtype=torch.int32, device=eng.device)
+        k = int(self._probs.shape[0]) if carried else 0
+        if k:
+            probs[:k], best_seq[:k] = self._probs, self._best_seq
+        res = env.rollout_cem_groups_stats(n_steps, R, H, self.n_iters, self.n_elite, sync=sync, probs=probs, best_seq=best_seq,
+                                           resume_steps=k, warm_start=self.warm_start, seed=self.seed, draw=self.draw, alpha=self.alpha,
+                                           p_min=self.p_min, idle_action=self.DO_NOTHING, reward_weights=self.reward_weights,
+                                           gamma=self.gamma, info_weights=self.info_weights, into=into)
+        if sync:
+            self.syncs += 1
+        c = res.mpc
+        self.draw = (self.draw + c.planned) & 0xFFFFFFFF
+        self.last, self.last_horizon = None, c.steps
+        self._probs, self._best_seq = (c.probs[:c.steps], c.best_seq[:c.steps]) if c.steps else (None, None)
+        self._step = step + n_steps - 1
+        return res

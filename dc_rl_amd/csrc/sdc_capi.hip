@@ -33,6 +33,7 @@
 #include "sdc_stats.hpp"
 #include "sdc_policy_stats.hpp"
 #include "sdc_mpc.hpp"
+#include "sdc_mpc_groups.hpp"
 #include "sdc_mpc_schedule.hpp"
 
 namespace {
@@ -2104,32 +2105,21 @@ int sdc_plan_cem(sdc_handle* h, int n_steps, const sdc_cem_params* cem, const sd
   });
 }
 
-// sdc_plan_cem with the candidates in env slots: per iteration ONE rollout of the whole batch (plan_candidates with the single
-// "candidate" cand) between the group sample and the group refit kernel.
-int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* cem, const sdc_plan_objective* objective, double* probs,
-                        int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* step_actions, int32_t* cand,
-                        double* cand_score, float* obs, float* share_obs, void* stream) {
-  static const std::string w = "sdc_plan_cem_groups: ";
-  if (!h) return fail_msg(w + "null handle");
-  if (!cem) return fail_msg(w + "null cem");
-  const sdc_cem_group_params c = *cem;
-  const int N = h->cfg.n_envs;
-  if (cem_iters_refused(w, c.n_iters, c.iter0)) return -2;
+// What sdc_plan_cem_groups and sdc_rollout_cem_groups_stats refuse alike about the groups of a batch of N envs, in the former's order
+static int cem_groups_refused(const std::string& w, const int N, const sdc_cem_group_params& c) {
   if (c.group_size < 2 || c.group_size > SDC_CEM_MAX_GROUP)
     return fail_msg(w + "group_size = " + std::to_string(c.group_size) + " outside [2, " + std::to_string(SDC_CEM_MAX_GROUP) + "]");
   if (N % c.group_size != 0)
     return fail_msg(w + "n_envs = " + std::to_string(N) + " is not a multiple of group_size = " + std::to_string(c.group_size));
   if (cem_elite_refused(w, c.n_elite, "group_size", c.group_size)) return -2;
   if (c.group_base < 0) return fail_msg(w + "group_base = " + std::to_string(c.group_base) + " is negative");
-  if (cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min)) return -2;
-  sdc_plan_objective obj;
-  if (plan_refused("sdc_plan_cem_groups", h, n_steps, probs && best_seq && best_score && best_action && step_actions && cand && cand_score,
-                   obs, share_obs, objective, obj))
-    return -2;
-  // what the host's mirror (sdc_mirror.hpp) knows of a group's replicas: the episode step, the config, the trace set, the feature-row flag
-  const int R = c.group_size, G = N / R;
+  return 0;
+}
+// ... and, from what the host's mirror (sdc_mirror.hpp) knows of a group's replicas in O(N): the episode step, the config, the trace
+// set, the feature-row flag
+static int groups_out_of_step_refused(const std::string& w, const sdc_handle* h, const int R) {
   const SdcHostMirror& mir = h->mirror;
-  for (int e = 0; e < N; e++) {
+  for (int e = 0; e < h->cfg.n_envs; e++) {
     const int l = e - e % R;      // the group's first env
     if (e == l) continue;
     const char* what = mir.t_rel(e) != mir.t_rel(l)   ? "episode step"
@@ -2141,6 +2131,27 @@ int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* 
       return fail_msg(w + "group " + std::to_string(e / R) + " is out of step: env " + std::to_string(e) + " and its group's first env " +
                       std::to_string(l) + " differ in " + what + " (the replicas of a group hold one state: sdc_clone_envs)");
   }
+  return 0;
+}
+
+// sdc_plan_cem with the candidates in env slots: per iteration ONE rollout of the whole batch (plan_candidates with the single
+// "candidate" cand) between the group sample and the group refit kernel.
+int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* cem, const sdc_plan_objective* objective, double* probs,
+                        int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* step_actions, int32_t* cand,
+                        double* cand_score, float* obs, float* share_obs, void* stream) {
+  static const std::string w = "sdc_plan_cem_groups: ";
+  if (!h) return fail_msg(w + "null handle");
+  if (!cem) return fail_msg(w + "null cem");
+  const sdc_cem_group_params c = *cem;
+  const int N = h->cfg.n_envs;
+  if (cem_iters_refused(w, c.n_iters, c.iter0) || cem_groups_refused(w, N, c) || cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min))
+    return -2;
+  sdc_plan_objective obj;
+  if (plan_refused("sdc_plan_cem_groups", h, n_steps, probs && best_seq && best_score && best_action && step_actions && cand && cand_score,
+                   obs, share_obs, objective, obj))
+    return -2;
+  if (groups_out_of_step_refused(w, h, c.group_size)) return -2;
+  const int R = c.group_size, G = N / R;
   SdcCemGroupSample Q = cem_sample_plan<SdcCemGroupSample>(N, n_steps, c, probs, best_seq, cand);
   SdcCemGroupRefit F = cem_refit_plan<SdcCemGroupRefit>(N, n_steps, c, cand_score, cand, probs, best_seq, best_action);
   Q.group_size = F.group_size = R;
@@ -2324,7 +2335,92 @@ int sdc_rollout_actor_stats(sdc_handle* h, int n_steps, int sample, int accumula
 // ---- planner evaluation (sdc_mpc.hip) -----------------------------------------------------------------------------------------------
 // The contract: include/sustaindc_hip.h; the decision schedule: sdc_mpc_schedule.hpp; the two kernels' plans: sdc_mpc.hpp.  A planned
 // decision is sdc_plan_cem's own body (plan_marked around cem_iterations), the step sdc_rollout_stats' with a one-step chunk; the
-// discount table of the longest horizon is staged once, and every decision reads its prefix.
+// discount table of the longest horizon is staged once, and every decision reads its prefix.  sdc_rollout_cem_groups_stats
+// (sdc_mpc_groups.hip) is the same loop (mpc_steps) with sdc_plan_cem_groups' body, a sync in front and the agreement check behind the step.
+
+// What both calls refuse about the loop's own parameters (the leading fields of sdc_mpc_params and sdc_mpc_group_params)
+static int mpc_loop_refused(const std::string& w, const int H, const int warm_start, const int resume, const int resume_steps,
+                            const int32_t* idle_action) {
+  if (H < 1 || H > SDC_MARK_MAX_STEPS)
+    return fail_msg(w + "horizon = " + std::to_string(H) + " outside [1, " + std::to_string(SDC_MARK_MAX_STEPS) + "]");
+  if (warm_start != 0 && warm_start != 1) return fail_msg(w + "warm_start = " + std::to_string(warm_start) + " outside {0, 1}");
+  if (resume != 0 && resume != 1) return fail_msg(w + "resume = " + std::to_string(resume) + " outside {0, 1}");
+  if (resume && (resume_steps < 1 || resume_steps > H))
+    return fail_msg(w + "resume_steps = " + std::to_string(resume_steps) + " outside [1, horizon = " + std::to_string(H) + "]");
+  for (int k = 0; k < 3; k++)
+    if (idle_action[k] < 0 || idle_action[k] > 2)
+      return fail_msg(w + "idle_action[" + std::to_string(k) + "] = " + std::to_string(idle_action[k]) + " outside [0, 2]");
+  return 0;
+}
+
+// the longest planned decision of a call of n_steps that starts `left` steps before the episode's end: the first one (the horizon only
+// shrinks towards the episode's end); 0: every decision idles
+static int mpc_longest(const int H, const int warm_start, const int auto_reset, const int resume_steps, const int left, const int n_steps) {
+  int k_max = 0;
+  SdcMpcSchedule S(H, warm_start, auto_reset, resume_steps);
+  for (int t = 0; t < n_steps; t++) k_max = std::max(k_max, S.next(left - t).steps);
+  return k_max;
+}
+
+extern "C++" {
+// The steps of a planner evaluation once its arguments have passed.  Every buffer at its largest before anything is enqueued: the step's
+// one-step block, the longest decision's (k_max steps) rows, block and forecast; then first() -> rc (the groups' sync); the discount table
+// of H steps staged once; then per step the schedule's decision d -- planned: start(d) -> rc and plan_marked around body(session, d)
+// -> rc, which enqueues the planner's iterations --, fold(d, init) -> rc, and the step: sdc_rollout_stats' path with a one-step chunk and
+// `actions` [N][3], behind its reduce kernel behind(B1, init) -> rc.  Behind the last step sdc_stats_last_kernel.
+template <class First, class Start, class Body, class Fold, class Behind>
+static int mpc_steps(sdc_handle* h, const int n_steps, const int H, const int warm_start, const int resume_steps, const int k_max,
+                     const int accumulate, const sdc_plan_objective& obj, const StatsArrays& a, const int32_t* actions, void* stream,
+                     First&& first, Start&& start, Body&& body, Fold&& fold, Behind&& behind) {
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int auto_reset = h->cfg.auto_reset ? 1 : 0;
+  int chunk1;
+  SdcPlanBlock B1;
+  if (plan_out_block(h, 1, chunk1, B1)) return -1;
+  SdcForecastSwap W;
+  std::memset(&W, 0, sizeof(W));
+  if (k_max > 0) {
+    PlanRun R;
+    if (plan_prepare(h, k_max, obj, R) || plan_forecast_swap(h, k_max, W)) return -1;
+  }
+  if (const int rc = first()) return rc;
+
+  void* pin = nullptr;
+  if (stage_acquire(h, h->plan_stage, &pin)) return -1;
+  double* const g = static_cast<double*>(pin);
+  g[0] = 1.0;
+  for (int k = 1; k < H; k++) g[k] = g[k - 1] * obj.gamma;
+  int rc = 0;
+  const int staged = stage_commit(h, h->plan_stage, (size_t)H, st, [&](const void* g_dev) {
+    SdcMpcSchedule S(H, warm_start, auto_reset, resume_steps);
+    SdcStatsReduce R1 = stats_reduce_plan(h, B1, a);
+    R1.steps = 1;
+    for (int t = 0; t < n_steps && rc == 0; t++) {
+      const SdcMpcDecision d = S.next(h->mirror.steps_to_terminal());
+      const int init = (t == 0 && accumulate == 0) ? 1 : 0;
+      if (d.planned) {
+        const int K = d.steps;
+        rc = start(d);
+        PlanSession P{h, {}, g_dev, g[K - 1] * obj.gamma, a.obs, a.share_obs, stream};
+        if (rc == 0 && (plan_prepare(h, K, obj, P.R) || plan_forecast_swap(h, K, W))) rc = -1;
+        if (rc == 0) rc = plan_marked(P, W, [&](PlanSession& P_) { return body(P_, d); });
+      }
+      if (rc == 0) rc = fold(d, init);
+      if (rc == 0)
+        rc = rollout_chunks(h, B1, 1, 1, rollout_of(h, actions, stream), [&](int, int) {
+          R1.init = init;
+          const int r = launched("sdc_stats_reduce_kernel", sdc_stats_reduce_launch(R1, st));
+          return r ? r : behind(B1, init);
+        });
+    }
+    if (rc == 0) rc = stats_last(h, B1, 1, a, st);
+    return hipSuccess;
+  });
+  return rc ? rc : staged;
+}
+}  // extern "C++"
+
 int sdc_rollout_cem_stats(sdc_handle* h, int n_steps, const sdc_mpc_params* mpc, const sdc_plan_objective* objective, int accumulate,
                           double* stats, double* returns, int32_t* counts, int32_t* plan_counts, double* plan_sums, double* probs,
                           int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* cand, double* cand_score, float* obs,
@@ -2336,15 +2432,7 @@ int sdc_rollout_cem_stats(sdc_handle* h, int n_steps, const sdc_mpc_params* mpc,
   const sdc_mpc_params m = *mpc;
   const sdc_cem_params c = m.cem;
   const int H = m.horizon;
-  if (H < 1 || H > SDC_MARK_MAX_STEPS)
-    return fail_msg(w + "horizon = " + std::to_string(H) + " outside [1, " + std::to_string(SDC_MARK_MAX_STEPS) + "]");
-  if (m.warm_start != 0 && m.warm_start != 1) return fail_msg(w + "warm_start = " + std::to_string(m.warm_start) + " outside {0, 1}");
-  if (m.resume != 0 && m.resume != 1) return fail_msg(w + "resume = " + std::to_string(m.resume) + " outside {0, 1}");
-  if (m.resume && (m.resume_steps < 1 || m.resume_steps > H))
-    return fail_msg(w + "resume_steps = " + std::to_string(m.resume_steps) + " outside [1, horizon = " + std::to_string(H) + "]");
-  for (int k = 0; k < 3; k++)
-    if (m.idle_action[k] < 0 || m.idle_action[k] > 2)
-      return fail_msg(w + "idle_action[" + std::to_string(k) + "] = " + std::to_string(m.idle_action[k]) + " outside [0, 2]");
+  if (mpc_loop_refused(w, H, m.warm_start, m.resume, m.resume_steps, m.idle_action)) return -2;
   if (cem_iters_refused(w, c.n_iters, c.iter0)) return -2;
   if (c.n_cand < 2 || c.n_cand > SDC_CEM_MAX_CAND)
     return fail_msg(w + "n_cand = " + std::to_string(c.n_cand) + " outside [2, " + std::to_string(SDC_CEM_MAX_CAND) + "]");
@@ -2360,28 +2448,12 @@ int sdc_rollout_cem_stats(sdc_handle* h, int n_steps, const sdc_mpc_params* mpc,
   sdc_plan_objective obj;
   if (plan_objective_refused(w, objective, obj)) return -2;
   if (stats_past_end_refused(w, h, n_steps)) return -2;
-  // the longest planned decision: the first one (the horizon only shrinks towards the episode's end); 0: every decision idles
-  const int left0 = h->mirror.steps_to_terminal(), auto_reset = h->cfg.auto_reset ? 1 : 0;
-  int k_max = 0;
-  {
-    SdcMpcSchedule S(H, m.warm_start, auto_reset, m.resume ? m.resume_steps : 0);
-    for (int t = 0; t < n_steps; t++) k_max = std::max(k_max, S.next(left0 - t).steps);
-  }
+  const int resume_steps = m.resume ? m.resume_steps : 0;
+  const int k_max = mpc_longest(H, m.warm_start, h->cfg.auto_reset ? 1 : 0, resume_steps, h->mirror.steps_to_terminal(), n_steps);
   if (k_max > 0 && forecast_refused(w, h, k_max)) return -2;
 
-  HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N = h->cfg.n_envs;
-  // every buffer at its largest before anything is enqueued: the step's one-step block, the longest decision's rows, block and forecast
-  int chunk1;
-  SdcPlanBlock B1;
-  if (plan_out_block(h, 1, chunk1, B1)) return -1;
-  SdcForecastSwap W;
-  std::memset(&W, 0, sizeof(W));
-  if (k_max > 0) {
-    PlanRun R;
-    if (plan_prepare(h, k_max, obj, R) || plan_forecast_swap(h, k_max, W)) return -1;
-  }
   SdcMpcStart A;
   std::memset(&A, 0, sizeof(A));
   A.n_envs = N;
@@ -2397,56 +2469,153 @@ int sdc_rollout_cem_stats(sdc_handle* h, int n_steps, const sdc_mpc_params* mpc,
   F.score_last = best_score + (size_t)(c.n_iters - 1) * (size_t)N;
   for (int k = 0; k < 3; k++) A.idle[k] = F.idle[k] = m.idle_action[k];
 
-  void* pin = nullptr;
-  if (stage_acquire(h, h->plan_stage, &pin)) return -1;
-  double* const g = static_cast<double*>(pin);
-  g[0] = 1.0;
-  for (int k = 1; k < H; k++) g[k] = g[k - 1] * obj.gamma;
-  int rc = 0;
-  const int staged = stage_commit(h, h->plan_stage, (size_t)H, st, [&](const void* g_dev) {
-    SdcMpcSchedule S(H, m.warm_start, auto_reset, m.resume ? m.resume_steps : 0);
-    SdcStatsReduce R1 = stats_reduce_plan(h, B1, a);
-    R1.steps = 1;
-    for (int t = 0; t < n_steps && rc == 0; t++) {
-      const SdcMpcDecision d = S.next(h->mirror.steps_to_terminal());
-      const int init = (t == 0 && accumulate == 0) ? 1 : 0;
-      if (d.planned) {
-        const int K = d.steps;
-        A.steps = K;
+  return mpc_steps(
+      h, n_steps, H, m.warm_start, resume_steps, k_max, accumulate, obj, a, best_action, stream, [] { return 0; },
+      [&](const SdcMpcDecision& d) {
+        A.steps = d.steps;
         A.fresh = d.fresh;
-        rc = launched("sdc_mpc_start_kernel", sdc_mpc_start_launch(A, st));
-        PlanSession P{h, {}, g_dev, g[K - 1] * obj.gamma, obs, share_obs, stream};
-        if (rc == 0 && (plan_prepare(h, K, obj, P.R) || plan_forecast_swap(h, K, W))) rc = -1;
-        if (rc == 0) {
-          sdc_cem_params ck = c;
-          ck.draw = c.draw + d.draw_index;
-          SdcCemSample Q = cem_sample_plan<SdcCemSample>(N, K, ck, probs, best_seq, cand);
-          Q.n_cand = c.n_cand;
-          Q.env_base = h->cfg.env_index_base;
-          SdcCemRefit T = cem_refit_plan<SdcCemRefit>(N, K, ck, cand_score, cand, probs, best_seq, best_action);
-          T.n_cand = c.n_cand;
-          rc = plan_marked(P, W, [&](PlanSession& P_) {
-            return cem_iterations(P_, c.n_iters, c.iter0, c.n_cand, cand, cand_score, best_score, (size_t)N, Q, sdc_cem_sample_launch,
-                                  "sdc_cem_sample_kernel", T, sdc_cem_refit_launch, "sdc_cem_refit_kernel");
-          });
-        }
-      }
-      if (rc == 0 && (!d.planned || plan_counts)) {
+        return launched("sdc_mpc_start_kernel", sdc_mpc_start_launch(A, st));
+      },
+      [&](PlanSession& P, const SdcMpcDecision& d) {
+        const int K = d.steps;
+        sdc_cem_params ck = c;
+        ck.draw = c.draw + d.draw_index;
+        SdcCemSample Q = cem_sample_plan<SdcCemSample>(N, K, ck, probs, best_seq, cand);
+        Q.n_cand = c.n_cand;
+        Q.env_base = h->cfg.env_index_base;
+        SdcCemRefit T = cem_refit_plan<SdcCemRefit>(N, K, ck, cand_score, cand, probs, best_seq, best_action);
+        T.n_cand = c.n_cand;
+        return cem_iterations(P, c.n_iters, c.iter0, c.n_cand, cand, cand_score, best_score, (size_t)N, Q, sdc_cem_sample_launch,
+                              "sdc_cem_sample_kernel", T, sdc_cem_refit_launch, "sdc_cem_refit_kernel");
+      },
+      [&](const SdcMpcDecision& d, const int init) {
+        if (d.planned && !plan_counts) return 0;
         F.planned = d.planned;
         F.init = init;
-        rc = launched("sdc_mpc_fold_kernel", sdc_mpc_fold_launch(F, st));
-      }
-      // the step: sdc_rollout_stats' path with a one-step chunk and best_action as its actions
-      if (rc == 0)
-        rc = rollout_chunks(h, B1, 1, 1, rollout_of(h, best_action, stream), [&](int, int) {
-          R1.init = init;
-          return launched("sdc_stats_reduce_kernel", sdc_stats_reduce_launch(R1, st));
-        });
-    }
-    if (rc == 0) rc = stats_last(h, B1, 1, a, st);
-    return hipSuccess;
-  });
-  return rc ? rc : staged;
+        return launched("sdc_mpc_fold_kernel", sdc_mpc_fold_launch(F, st));
+      },
+      [](const SdcPlanBlock&, int) { return 0; });
+}
+
+// sdc_rollout_cem_stats over replica groups: the loop above with sdc_plan_cem_groups' body (the group sample and group refit kernels, one
+// rollout of the batch per iteration), sdc_mpc_start_kernel over the G groups, sdc_mpc_group_fold_kernel, the step played with
+// step_actions, and sdc_group_agree_kernel behind the step's reduce.  sync_first: one sdc_clone_envs in front, the groups' first envs ->
+// their replicas; the episode's end is then the first envs' (what the mirror says once the clone has been made).
+int sdc_rollout_cem_groups_stats(sdc_handle* h, int n_steps, const sdc_mpc_group_params* mpc, const sdc_plan_objective* objective,
+                                 int accumulate, double* stats, double* returns, int32_t* counts, int32_t* plan_counts, double* plan_sums,
+                                 int32_t* diverged, double* probs, int32_t* best_seq, double* best_score, int32_t* best_action,
+                                 int32_t* step_actions, int32_t* cand, double* cand_score, float* obs, float* share_obs, float* rew,
+                                 uint8_t* done, float* info, float* final_obs, void* stream) {
+  static const std::string w = "sdc_rollout_cem_groups_stats: ";
+  const StatsArrays a = {stats, returns, counts, obs, share_obs, rew, done, info, final_obs};
+  if (stats_refused(w, h, n_steps, accumulate, a)) return -2;
+  if (!mpc) return fail_msg(w + "null mpc");
+  const sdc_mpc_group_params m = *mpc;
+  const sdc_cem_group_params c = m.cem;
+  const int H = m.horizon, N = h->cfg.n_envs;
+  if (mpc_loop_refused(w, H, m.warm_start, m.resume, m.resume_steps, m.idle_action)) return -2;
+  if (m.sync_first != 0 && m.sync_first != 1) return fail_msg(w + "sync_first = " + std::to_string(m.sync_first) + " outside {0, 1}");
+  if (m.sync_first && m.resume)
+    return fail_msg(w + "sync_first with resume (behind the sync the first planned decision starts fresh: nothing can be resumed)");
+  if (cem_iters_refused(w, c.n_iters, c.iter0) || cem_groups_refused(w, N, c) || cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min))
+    return -2;
+  if (!probs || !best_seq || !best_score || !best_action || !step_actions || !cand || !cand_score)
+    return fail_msg(w + "null array (probs, best_seq, best_score, best_action, step_actions, cand and cand_score are required)");
+  const auto addr = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
+  if (((addr(probs) | addr(best_score) | addr(cand_score)) & 7u) != 0) return fail_msg(w + "probs / best_score / cand_score not 8-byte aligned");
+  if (((addr(best_seq) | addr(best_action) | addr(step_actions) | addr(cand)) & 3u) != 0)
+    return fail_msg(w + "best_seq / best_action / step_actions / cand not dword-aligned");
+  if ((plan_counts == nullptr) != (plan_sums == nullptr) || (plan_counts == nullptr) != (diverged == nullptr))
+    return fail_msg(w + "plan_counts, plan_sums and diverged are given together or not at all");
+  if ((addr(plan_sums) & 15u) != 0) return fail_msg(w + "plan_sums not 16-byte aligned");
+  if (((addr(plan_counts) | addr(diverged)) & 3u) != 0) return fail_msg(w + "plan_counts / diverged not dword-aligned");
+  sdc_plan_objective obj;
+  if (plan_objective_refused(w, objective, obj)) return -2;
+  // the steps the episode has left: behind a sync every replica stands where its group's first env stands
+  const int R = c.group_size, G = N / R;
+  int left0 = h->mirror.steps_to_terminal();
+  if (m.sync_first) {
+    int most = 0;
+    for (int e = 0; e < N; e += R) most = std::max(most, h->mirror.t_rel(e));
+    left0 = h->d.episode_steps - most;
+  }
+  if (n_steps > left0)
+    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" + std::to_string(left0) +
+                    " steps left)");
+  if (!m.sync_first && groups_out_of_step_refused(w, h, R)) return -2;
+  const int resume_steps = m.resume ? m.resume_steps : 0;
+  const int k_max = mpc_longest(H, m.warm_start, h->cfg.auto_reset ? 1 : 0, resume_steps, left0, n_steps);
+  if (k_max > 0 && forecast_refused(w, h, k_max)) return -2;
+
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  SdcMpcStart A;
+  std::memset(&A, 0, sizeof(A));
+  A.n_envs = G;
+  A.probs = probs;
+  A.best_seq = best_seq;
+  SdcMpcGroupFold F;
+  std::memset(&F, 0, sizeof(F));
+  F.n_envs = N;
+  F.n_groups = G;
+  F.best_action = best_action;
+  F.step_actions = step_actions;
+  F.counts = plan_counts;
+  F.sums = plan_sums;
+  F.diverged = diverged;
+  F.score_first = best_score;
+  F.score_last = best_score + (size_t)(c.n_iters - 1) * (size_t)G;
+  for (int k = 0; k < 3; k++) A.idle[k] = F.idle[k] = m.idle_action[k];
+  SdcGroupAgree Y;
+  std::memset(&Y, 0, sizeof(Y));
+  Y.n_envs = N;
+  Y.group_size = R;
+  Y.diverged = diverged;
+
+  return mpc_steps(
+      h, n_steps, H, m.warm_start, resume_steps, k_max, accumulate, obj, a, step_actions, stream,
+      [&] {
+        if (!m.sync_first) return 0;
+        std::vector<int32_t> src((size_t)(N - G)), dst((size_t)(N - G));
+        size_t k = 0;
+        for (int e = 0; e < N; e++)
+          if (e % R != 0) {
+            src[k] = e - e % R;
+            dst[k++] = e;
+          }
+        return sdc_clone_envs(h, src.data(), dst.data(), N - G, obs, share_obs, stream);
+      },
+      [&](const SdcMpcDecision& d) {
+        A.steps = d.steps;
+        A.fresh = d.fresh;
+        return launched("sdc_mpc_start_kernel", sdc_mpc_start_launch(A, st));
+      },
+      [&](PlanSession& P, const SdcMpcDecision& d) {
+        const int K = d.steps;
+        sdc_cem_group_params ck = c;
+        ck.draw = c.draw + d.draw_index;
+        SdcCemGroupSample Q = cem_sample_plan<SdcCemGroupSample>(N, K, ck, probs, best_seq, cand);
+        SdcCemGroupRefit T = cem_refit_plan<SdcCemGroupRefit>(N, K, ck, cand_score, cand, probs, best_seq, best_action);
+        Q.group_size = T.group_size = R;
+        Q.n_groups = T.n_groups = G;
+        Q.group_base = c.group_base;
+        T.step_actions = step_actions;
+        return cem_iterations(P, c.n_iters, c.iter0, 1, cand, cand_score, best_score, (size_t)G, Q, sdc_cem_group_sample_launch,
+                              "sdc_cem_group_sample_kernel", T, sdc_cem_group_refit_launch, "sdc_cem_group_refit_kernel");
+      },
+      [&](const SdcMpcDecision& d, const int init) {
+        if (d.planned && !plan_counts) return 0;
+        F.planned = d.planned;
+        F.init = init;
+        return launched("sdc_mpc_group_fold_kernel", sdc_mpc_group_fold_launch(F, st));
+      },
+      [&](const SdcPlanBlock& B1, int) {
+        if (!diverged) return 0;
+        // (the one-step block: step 0's slices)
+        Y.rew = reinterpret_cast<const float*>(h->plan_out + B1.rew);
+        Y.info = reinterpret_cast<const float*>(h->plan_out + B1.info);
+        Y.done = h->plan_out + B1.done;
+        return launched("sdc_group_agree_kernel", sdc_group_agree_launch(Y, st));
+      });
 }
 
 }  // extern "C"

@@ -229,10 +229,12 @@ class PlanStats:
     (-1: no step yet); `sums` float64 [N, 4] per env with the views `score` (the summed score the planner predicted for the sequence
     it chose, over the planned decisions), `gain` (the summed improvement of that score over the CEM iterations: last minus first),
     `planned` and `idle` (the number of decisions of either kind, as doubles).  From `evaluate` every tensor has a leading [E]
-    dimension."""
+    dimension.  From `rollout_cem_groups_stats` (sdc_rollout_cem_groups_stats) the leading dimension N is the number of groups G, and
+    `diverged` is an int32 [G] tensor: per group the number of (step, replica) pairs at which a replica's rew, done or info row (without
+    info[reserved]) differed from its group's first env's in any bit -- 0 while the group holds one state; None from the per-env call."""
 
-    def __init__(self, counts, sums):
-        self.counts, self.sums = counts, sums
+    def __init__(self, counts, sums, diverged=None):
+        self.counts, self.sums, self.diverged = counts, sums, diverged
 
     action_counts = property(lambda self: self.counts[..., :3])
     switches = property(lambda self: self.counts[..., L.POLICY_SWITCHES])
@@ -249,7 +251,8 @@ class PlanStats:
           switch_rate = switches / max(steps - 1, 1);
         and per env:  mean_score = score / planned;   mean_gain = gain / planned -- per planned decision.
         Over the batch the same formulas with the sums over the envs (the transitions: the sum of the envs' max(steps - 1, 1)).  A
-        quantity of an env that took no step, or planned no decision, is 0, never NaN."""
+        quantity of an env that took no step, or planned no decision, is 0, never NaN.  With `diverged` (replica groups: read "env" as
+        "group") the dict also carries "diverged": array [G] (or [E, G])."""
         n = self.action_counts.cpu().numpy().astype(np.float64)
         sw = self.switches.cpu().numpy().astype(np.float64)
         score, gain = self.score.cpu().numpy(), self.gain.cpu().numpy()
@@ -267,8 +270,11 @@ class PlanStats:
             for name, x in (("mean_score", score), ("mean_gain", gain)):
                 per_env[name], batch[name] = ratio(x, planned), ratio(x.sum(axis=-1), bplanned)
         batch = {k: (float(v) if np.ndim(v) == 0 else np.asarray(v)) for k, v in batch.items()}
-        return {"per_env": per_env, "batch": batch, "steps": steps.astype(np.int64), "planned": planned.astype(np.int64),
-                "idle": idle.astype(np.int64)}
+        out = {"per_env": per_env, "batch": batch, "steps": steps.astype(np.int64), "planned": planned.astype(np.int64),
+               "idle": idle.astype(np.int64)}
+        if self.diverged is not None:
+            out["diverged"] = self.diverged.cpu().numpy().astype(np.int64)
+        return out
 
 
 class MPCCarry:
@@ -276,11 +282,13 @@ class MPCCarry:
     [H, N, 3], the arrays of the call (a caller's own are the same tensors), whose first `steps` steps hold the last planned decision's
     result, unshifted -- `steps` is 0 when no decision of the call was planned or its last one was idle: nothing to resume from --;
     `planned`: the number of planned decisions of the call (what the draw counter advances by); `best_action` int32 [N, 3] the last
-    action played; `best_score` float64 [I, N] the last planned decision's scores."""
+    action played; `best_score` float64 [I, N] the last planned decision's scores.  From `rollout_cem_groups_stats` the arrays are per
+    group -- probs [H, G, 3, 3], best_seq [H, G, 3], best_action [G, 3], best_score [I, G] -- and `step_actions` int32 [N, 3] is the last
+    action played, per env (None from the per-env call)."""
 
-    def __init__(self, probs, best_seq, steps, planned, best_action, best_score):
+    def __init__(self, probs, best_seq, steps, planned, best_action, best_score, step_actions=None):
         self.probs, self.best_seq, self.steps, self.planned = probs, best_seq, int(steps), int(planned)
-        self.best_action, self.best_score = best_action, best_score
+        self.best_action, self.best_score, self.step_actions = best_action, best_score, step_actions
 
 
 def mpc_schedule(left, n_steps, horizon, auto_reset, warm_start=True, resume_steps=0):
@@ -1124,14 +1132,16 @@ class SdcEngine:
                          sized, sized, f"R = {R}, K = {K}, I = {n_it}, iter0 = {int(iter0)}", n_it, n_elite, probs, best_seq, seed, draw,
                          iter0, alpha, p_min, reward_weights, gamma, info_weights)
 
-    def _stats_into(self, who, into, policy_stats=None, plan_stats=None):
+    def _stats_into(self, who, into, policy_stats=None, plan_stats=None, groups=None):
         """the EpisodeStats a statistics call fills: a new one, or the caller's `into` checked (ValueError in `who`'s name) -- tensors of
         this engine's shapes on its device, a PolicyStats exactly when `policy_stats` (None: the call has none) and a PlanStats exactly
-        when `plan_stats` (the same)"""
+        when `plan_stats` (the same); `groups` = G: the PlanStats is per group and carries `diverged`"""
         t, N = self.torch, self.n_envs
         want = ((t.float64, (L.STATS_FIELDS, N, L.INFO_DIM)), (t.float64, (N, L.N_AGENTS)), (t.int32, (N, 2)))     # stats, returns, counts
         pwant = ((t.int32, (N, L.N_AGENTS, L.POLICY_COUNTS)), (t.float64, (N, L.N_AGENTS, L.POLICY_SUMS)))        # counts, sums
         mwant = ((t.int32, (N, L.N_AGENTS, L.POLICY_COUNTS)), (t.float64, (N, L.PLAN_SUMS)))                      # the plan's counts, sums
+        if groups is not None:                                                                                    # ... per group, and diverged
+            mwant = ((t.int32, (groups, L.N_AGENTS, L.POLICY_COUNTS)), (t.float64, (groups, L.PLAN_SUMS)), (t.int32, (groups,)))
         new = lambda shapes: [t.empty(sh, dtype=d, device=self.device) for d, sh in shapes]
         if into is None:
             return EpisodeStats(*new(want), PolicyStats(*new(pwant)) if policy_stats else None,
@@ -1153,9 +1163,10 @@ class SdcEngine:
             if plan_stats != (pl is not None):
                 raise ValueError(f"{who}: into must carry a PlanStats exactly when plan_stats is set (plan_stats = "
                                  f"{bool(plan_stats)}, into.plan is {'given' if pl is not None else 'None'})")
-            if pl is not None and not (isinstance(pl, PlanStats) and fits((pl.counts, pl.sums), mwant)):
+            if pl is not None and not (isinstance(pl, PlanStats) and fits((pl.counts, pl.sums, pl.diverged), mwant)):
                 raise ValueError(f"{who}: into.plan must be a PlanStats of this engine (contiguous tensors on {self.device}: counts "
-                                 f"int32 {mwant[0][1]}, sums float64 {mwant[1][1]})")
+                                 f"int32 {mwant[0][1]}, sums float64 {mwant[1][1]}" +
+                                 (f", diverged int32 {mwant[2][1]})" if groups is not None else ")"))
         self._behind_torch_stream()      # (its tensors may have been touched on torch's current stream)
         return into
 
@@ -1263,6 +1274,80 @@ class SdcEngine:
         res.mpc = MPCCarry(arrays[0], arrays[1], plan[-1][0], sum(1 for d in plan if d[1]), arrays[3], arrays[2])
         return res
 
+    def rollout_cem_groups_stats(self, n_steps: int, group_size: int, horizon: int, n_iters: int, n_elite: int, *, sync: bool = False,
+                                 probs=None, best_seq=None, resume_steps: int = 0, warm_start: bool = True, seed: int = 0, draw: int = 0,
+                                 alpha: float = 0.0, p_min: float = 0.0, fixed_action=(-1, -1, -1), idle_action=(1, 1, 2),
+                                 group_base: Optional[int] = None, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None,
+                                 into: Optional[EpisodeStats] = None, plan_stats: bool = True) -> EpisodeStats:
+        """`rollout_cem_stats` over replica groups (sdc_rollout_cem_groups_stats): before every step the library plans as
+        `plan_cem_groups(group_size, K, n_iters, n_elite, ...)` does -- G = N / R groups of R = group_size consecutive envs that hold
+        one state, one rollout of the batch per iteration --, plays the result's `step_actions`, folds the step into the EpisodeStats
+        and checks on the device that every replica's rew, done and info rows (without info[reserved]) still equal its group's first
+        env's, bit for bit; one library call with no Python between the decisions.  What GroupCEMMPCAgent does in a loop of act() and
+        step(), bit for bit.  `sync=True`: the call begins with `sync_groups(group_size)` inside the library, and its first planned
+        decision starts fresh (ValueError together with `resume_steps`); without it the groups must be in step, as for
+        `plan_cem_groups`.  n_steps <= steps_to_episode_end() puts an auto-reset at the call's last step at most -- the replicas
+        draw resets of their own there --, so a call per episode with `sync=True` is all an evaluation needs.  The statistics stay per
+        env [N] (a group's replicas carry equal rows: read every R-th); the result's `plan` is a PlanStats PER GROUP -- counts
+        [G, 3, 5], sums [G, 4] and `diverged` int32 [G], the (step, replica) pairs that differed from their group's first env
+        (`plan_stats=False`: None, and nothing is checked) --, its `mpc` an MPCCarry per group with `step_actions` [N, 3].  `probs`
+        float64 [horizon, G, 3, 3], `best_seq` int32 [horizon, G, 3], `resume_steps`, `idle_action`, `into` and the other arguments:
+        `rollout_cem_stats`' and `plan_cem_groups`'.  ValueError, with the engine untouched, for malformed arguments and what the
+        library refuses: what `rollout_cem_stats` refuses, what `plan_cem_groups` refuses about the groups."""
+        t = self.torch
+        who = "rollout_cem_groups_stats"
+        H, N, R, n_it = int(horizon), self.n_envs, int(group_size), int(n_iters)
+        fixed = self._cem_fixed(who, fixed_action, seed, draw)
+        idle = [int(x) for x in idle_action]
+        if len(idle) != 3:
+            raise ValueError(f"{who}: idle_action must be three integers (ls, dc, bat), got {len(idle)}")
+        k_res = int(resume_steps)
+        if k_res < 0 or (k_res > 0 and (probs is None or best_seq is None)):
+            raise ValueError(f"{who}: resume_steps = {k_res} must not be negative, and resuming needs probs and best_seq")
+        grouped = 2 <= R <= L.CEM_MAX_GROUP and N % R == 0
+        if group_base is None:
+            base = int(self.config["env_index_base"])
+            if grouped and base % R:
+                raise ValueError(f"{who}: group_size = {R} does not divide env_index_base = {base} (pass group_base)")
+            group_base = base // R if grouped else 0
+        if not -(1 << 31) <= int(group_base) < 1 << 31:
+            raise ValueError(f"{who}: group_base must fit 32 bits")
+        G = N // R if grouped else 0
+        obj = plan_objective(reward_weights, gamma, info_weights)
+        sized = grouped and 1 <= H <= L.MARK_MAX_STEPS and 1 <= n_it <= L.CEM_MAX_ITERS
+        if sized and probs is not None:
+            A.device_tensor(probs, who, "probs", t.float64, (H, G, 3, 3), device=self.device)
+        if sized and best_seq is not None:
+            A.device_tensor(best_seq, who, "best_seq", t.int32, (H, G, 3), device=self.device)
+        pl = bool(plan_stats)
+        res = self._stats_into(who, into, None, pl, G if sized else None)
+        mpc = L.SdcMpcGroupParams()
+        mpc.horizon, mpc.warm_start, mpc.resume, mpc.resume_steps = H, 1 if warm_start else 0, 1 if k_res > 0 else 0, k_res
+        mpc.idle_action[:] = idle
+        mpc.sync_first = 1 if sync else 0
+        cem = mpc.cem
+        cem.group_size, cem.group_base, cem.n_iters, cem.iter0, cem.n_elite = R, int(group_base), n_it, 0, int(n_elite)
+        cem.fixed_action[:] = fixed
+        cem.draw, cem.seed, cem.alpha, cem.p_min = int(draw), int(seed), float(alpha), float(p_min)
+        arrays = [None] * 7
+        if sized:
+            self._behind_torch_stream()      # (a caller's probs / best_seq may have been filled by torch ops)
+            new = lambda shape, dtype: t.empty(shape, dtype=dtype, device=self.device)
+            arrays = [new((H, G, 3, 3), t.float64) if probs is None else probs, new((H, G, 3), t.int32) if best_seq is None else best_seq,
+                      new((n_it, G), t.float64), new((G, 3), t.int32), new((N, 3), t.int32), new((H, N, 3), t.int32), new((N,), t.float64)]
+        pc, ps, pd = (res.plan.counts, res.plan.sums, res.plan.diverged) if pl else (None, None, None)
+        self._call(self.lib.sdc_rollout_cem_groups_stats, int(n_steps), C.byref(mpc), C.byref(obj), 0 if into is None else 1, _p(res.stats),
+                   _p(res.returns), _p(res.counts), _p(pc), _p(ps), _p(pd), *[_p(x) for x in arrays], *self._obs_ptrs, _p(self.rew),
+                   _p(self.done), _p(self.info), _p(self.final_obs), self._stream(), refuses=True,
+                   wrote=[res.stats, res.returns, res.counts, pc, ps, pd] + arrays)
+        if not sized:
+            raise L.SdcError(f"{who}: sdc_rollout_cem_groups_stats accepted R = {R}, H = {H}, I = {n_it} and no arrays")
+        # the steps the episode had left behind the sync, from where the call has left the batch (no env finished: it moved n_steps)
+        left = int(n_steps) if self.last_done() is not None else self.steps_to_episode_end() + int(n_steps)
+        plan = mpc_schedule(left, int(n_steps), H, self.config["auto_reset"], bool(warm_start), k_res)
+        res.mpc = MPCCarry(arrays[0], arrays[1], plan[-1][0], sum(1 for d in plan if d[1]), arrays[3], arrays[2], arrays[4])
+        return res
+
     def evaluate(self, n_episodes: int, actions=None, *, actors: bool = False, sample: bool = False, mpc=None) -> EpisodeStats:
         """`n_episodes` whole episodes of the batch, one `rollout_stats` of episode_steps steps each -> an EpisodeStats whose tensors
         carry a leading [E] dimension (stats [E, 4, N, 44], returns [E, N, 3], counts [E, N, 2]).  The batch is reset first; between
@@ -1272,7 +1357,8 @@ class SdcEngine:
         the result's `policy` is a PolicyStats with the same leading dimension; ValueError together with `actions`.  `mpc=agent`: a
         CEMMPCAgent plans every step -- one `agent.rollout_stats` (`rollout_cem_stats`) per episode, the agent's draw counter running
         on from episode to episode -- and the result's `plan` is a PlanStats with the same leading dimension; ValueError together with
-        `actions` or `actors`."""
+        `actions` or `actors`.  A GroupCEMMPCAgent plans over replica groups (`rollout_cem_groups_stats`, one call per episode, each
+        with `sync=True`: the replicas drew resets of their own); the PlanStats is then per group and carries `diverged`."""
         t = self.torch
         E = int(n_episodes)
         if E < 1:
@@ -1299,7 +1385,10 @@ class SdcEngine:
                 eps.append(self.rollout_stats(a, n_steps=self.episode_steps))
         stack = lambda get: t.stack([get(x) for x in eps])
         pol = PolicyStats(stack(lambda x: x.policy.counts), stack(lambda x: x.policy.sums)) if actors else None
-        pln = PlanStats(stack(lambda x: x.plan.counts), stack(lambda x: x.plan.sums)) if mpc is not None else None
+        pln = None
+        if mpc is not None:
+            pln = PlanStats(stack(lambda x: x.plan.counts), stack(lambda x: x.plan.sums),
+                            stack(lambda x: x.plan.diverged) if eps[0].plan.diverged is not None else None)
         return EpisodeStats(stack(lambda x: x.stats), stack(lambda x: x.returns), stack(lambda x: x.counts), pol, plan=pln)
 
     def profile(self, every: int = 1):

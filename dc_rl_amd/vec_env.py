@@ -693,13 +693,31 @@ class SustainDCVecEnv(ShareVecEnv):
         self._ready("rollout_cem_stats")
         return self._stats_done(self.engine.rollout_cem_stats(n_steps, horizon, n_iters, n_candidates, n_elite, **kw))
 
+    def rollout_cem_groups_stats(self, n_steps, group_size, horizon, n_iters, n_elite, *, sync=False, **kw):
+        """n_steps env-steps planned by the cross-entropy method over replica groups inside the library, reduced on the device to an
+        EpisodeStats with a PlanStats per group (SdcEngine.rollout_cem_groups_stats, which documents the arguments and the result;
+        `probs` / `best_seq` are the engine's, all three slots).  The envs move as under n_steps rounds of plan_cem_groups() and
+        step(); with `sync` the call begins as sync_groups(group_size) does, and the host's per-env entries follow as after it.  Actions
+        handed to step_async and not yet stepped are dropped; the logger accumulator (accumulate_logger_sums) is left alone, as by
+        rollout_stats.  ValueError when this env trains an agent subset, as for rollout_cem_stats, and for what the engine refuses."""
+        if self.n_agents != 3:
+            raise ValueError(f"rollout_cem_groups_stats: this env trains {self.agents}; the library steps with the planner's best_action "
+                             "for all three agents, which is not what step() plays in the other slots' columns")
+        self._ready("rollout_cem_groups_stats")
+        res = self.engine.rollout_cem_groups_stats(n_steps, group_size, horizon, n_iters, n_elite, sync=sync, **kw)
+        if sync:
+            self._host_entries_follow(*group_sync_pairs(group_size, self.num_envs, "num_envs"), self._const, self._cfg_id, self.months)
+        return self._stats_done(res)
+
     def evaluate(self, n_episodes, actions=None, *, actors=False, sample=False, mpc=None):
         """`n_episodes` whole episodes of the batch from a reset (SdcEngine.evaluate) -> an EpisodeStats with a leading [E] dimension.
         `actions`: None (do-nothing baseline, see rollout_stats), an int tensor [episode_steps, num_envs, n_agents] replayed every
         episode, or a callable episode -> such a tensor.  `actors=True`: the three actors (set_actor) play, by their distributions'
         mode or -- `sample` -- a draw, and the result carries a PolicyStats; ValueError together with `actions`.  `mpc=agent`: a
         CEMMPCAgent plans every step inside the library (rollout_cem_stats), and the result carries a PlanStats; ValueError together
-        with `actions` or `actors`, and when this env trains an agent subset.  The logger accumulator
+        with `actions` or `actors`, and when this env trains an agent subset.  A GroupCEMMPCAgent plans over replica groups
+        (rollout_cem_groups_stats, one call per episode that syncs the groups first; the host's per-env entries follow as after
+        sync_groups), and the PlanStats is per group with `diverged`.  The logger accumulator
         (accumulate_logger_sums) is left alone.  Afterwards the envs stand at the start of a fresh episode when auto_reset is on;
         otherwise call reset()."""
         steps = self.episode_steps
@@ -708,7 +726,11 @@ class SustainDCVecEnv(ShareVecEnv):
                 raise ValueError("evaluate: mpc= plays the planner's own actions: give neither actions nor actors")
             if self.n_agents != 3:
                 raise ValueError(f"evaluate: this env trains {self.agents}; mpc= needs all three agents (rollout_cem_stats)")
+            synced = getattr(mpc, "syncs", 0)
             res = self.engine.evaluate(n_episodes, mpc=mpc)
+            if getattr(mpc, "syncs", 0) != synced:      # a GroupCEMMPCAgent's calls synced the groups: the host's entries follow once
+                self._host_entries_follow(*group_sync_pairs(mpc.group_size, self.num_envs, "num_envs"), self._const, self._cfg_id,
+                                          self.months)
         elif actors:
             if actions is not None:
                 raise ValueError("evaluate: actors=True plays the actors' own actions: give no actions")

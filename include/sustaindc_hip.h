@@ -240,7 +240,8 @@ const char* sdc_last_error(void);
  *        (sdc_snapshot_row_bytes, sdc_snapshot_envs, sdc_restore_envs came later without a bump: new entry points, no layout or
  *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise; sdc_plan, sdc_plan_cem,
  *        sdc_rollout_stats and sdc_plan_cem_groups likewise; sdc_set_plan_terms and sdc_get_plan_terms likewise;
- *        sdc_set_plan_forecast, sdc_get_plan_forecast and sdc_forecast_traces likewise; sdc_rollout_actor_stats likewise) */
+ *        sdc_set_plan_forecast, sdc_get_plan_forecast and sdc_forecast_traces likewise; sdc_rollout_actor_stats, sdc_rollout_cem_stats
+ *        and sdc_rollout_cem_groups_stats likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -817,6 +818,56 @@ int sdc_rollout_cem_stats(sdc_handle* h, int n_steps, const sdc_mpc_params* mpc,
                           double* stats, double* returns, int32_t* counts, int32_t* plan_counts, double* plan_sums, double* probs,
                           int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* cand, double* cand_score, float* obs,
                           float* share_obs, float* rew, uint8_t* done, float* info, float* final_obs, void* stream);
+
+/* PLANNER EVALUATION OVER REPLICA GROUPS: sdc_rollout_cem_stats with every planned decision replaced by sdc_plan_cem_groups' own body --
+ * the batch is G = N / R groups of R = cem.group_size consecutive envs that hold one state, one iteration is ONE rollout of the batch --
+ * and, behind every step, a check on the device that a group's replicas still agree.  One call, ordered on `stream`, no device
+ * synchronisation and no host wait between the decisions; the discount table of the whole call is staged once; the handle's plan terms
+ * and plan forecast apply to every decision; THE CALL USES UP THE ENVS' ONE LIVE MARK.  The engine ends where -- after the sync below --
+ * n_steps rounds of sdc_plan_cem_groups followed by a one-step sdc_rollout_stats of step_actions would leave it.
+ * sync_first == 1: the call begins with one sdc_clone_envs of the batch, the groups' first envs g R as sources and the envs g R + 1 ..
+ * g R + R - 1 as destinations (the caller's obs / share_obs rows follow), and the first planned decision starts fresh; the O(N) check
+ * of the host mirrors that sdc_plan_cem_groups makes ("group out of step") is skipped, the clone establishes it, and the episode's end
+ * is the groups' first envs'.  sync_first == 0: the check is made as sdc_plan_cem_groups makes it.  n_steps <=
+ * sdc_steps_to_episode_end() lets an auto-reset happen at the call's last step only -- the replicas draw resets of their own there --,
+ * so one sync at the front of a call is all a whole episode needs; the next call syncs again.
+ * THE DECISION SCHEDULE is sdc_rollout_cem_stats' (csrc/sdc_mpc_schedule.hpp), unchanged; the j-th planned decision of the call is
+ * sdc_plan_cem_groups with n_steps = K_t, the embedded cem parameters and draw = cem.draw + j (mod 2^32).
+ * PER STEP, in stream order: a planned decision is one sdc_mpc_start_kernel over the G groups, sdc_plan_cem_groups' own launches (mark,
+ * I x (group sample, rollout, score, rewind, group refit), the forecast's overlay) and -- with the plan statistics -- one
+ * sdc_mpc_group_fold_kernel (csrc/sdc_mpc_groups.hip); an idle decision is one sdc_mpc_group_fold_kernel, which writes idle_action into
+ * best_action and into every row of step_actions.  Then the step: sdc_rollout of one step with step_actions into the handle's output
+ * block, sdc_stats_reduce_kernel behind it and -- with the plan statistics -- sdc_group_agree_kernel over the same rows; behind the
+ * call's last step sdc_stats_last_kernel fills the single-step arrays as for sdc_rollout_stats.
+ * stats, returns, counts [N]..., accumulate and the single-step arrays: sdc_rollout_stats' contract and arithmetic, word for word, per
+ * env: a group's replicas carry equal rows, and the caller reads every R-th.  The planner's arrays are sdc_plan_cem_groups' with K read
+ * as H -- probs [H][G][3][3], best_seq [H][G][3], best_score [I][G], best_action [G][3], step_actions [N][3], cand [H][N][3], cand_score
+ * [N] --; a decision with K < H uses the contiguous [K]... prefix of each.  The plan statistics are the device's, and all three or none
+ * are given:
+ *   plan_counts [G][3][SDC_POLICY_COUNTS], plan_sums [G][SDC_PLAN_SUMS] (16-byte aligned): sdc_rollout_cem_stats' entries and
+ *               arithmetic with "env n" read as "group g" (the action played is best_action[g], the scores best_score[.][g])
+ *   diverged    [G] int32: the number of (step, replica) pairs of the call at which replica n = g R + r, r >= 1, differed from its
+ *               group's first env in ANY BIT of the step's three rew dwords, its done byte or its info row without info[reserved]
+ *               (scheduling-dependent by definition).  obs is not compared: after the terminal step it holds the replicas' own reset
+ *               observations.  accumulate == 0: from 0; accumulate == 1: from what it holds.
+ * Refused (-2 and a message, nothing enqueued, the engine untouched), all before the first launch: what sdc_rollout_cem_stats refuses
+ * (with sdc_plan_cem's n_cand rules replaced by the following); what sdc_plan_cem_groups refuses about group_size, n_elite and
+ * group_base, and -- sync_first == 0 -- a group out of step; sync_first outside {0, 1}; sync_first together with resume; one of
+ * plan_counts / plan_sums / diverged without the others; step_actions null or, like diverged, not dword-aligned. */
+typedef struct {
+  int32_t horizon;           /* as sdc_mpc_params */
+  int32_t warm_start;
+  int32_t resume;
+  int32_t resume_steps;
+  int32_t idle_action[3];
+  int32_t sync_first;        /* 1: before the first decision every group becomes a copy of its first env */
+  sdc_cem_group_params cem;  /* sdc_plan_cem_groups' own; draw: the first planned decision's */
+} sdc_mpc_group_params;
+int sdc_rollout_cem_groups_stats(sdc_handle* h, int n_steps, const sdc_mpc_group_params* mpc, const sdc_plan_objective* objective,
+                                 int accumulate, double* stats, double* returns, int32_t* counts, int32_t* plan_counts, double* plan_sums,
+                                 int32_t* diverged, double* probs, int32_t* best_seq, double* best_score, int32_t* best_action,
+                                 int32_t* step_actions, int32_t* cand, double* cand_score, float* obs, float* share_obs, float* rew,
+                                 uint8_t* done, float* info, float* final_obs, void* stream);
 
 /* Per-kernel timing (measurement only; off by default).  enable = k > 0 samples every k-th sdc_step, 0 switches it
  * off.  In a sampled step one lane per workgroup of each kernel stamps the device's constant-rate wall clock at
