@@ -315,11 +315,29 @@ int sdc_set_actor(sdc_handle* h, int agent_slot, const sdc_actor_params* p);
  * step's own observations (the first from the observations the last sdc_reset / sdc_step / sdc_rollout* call returned,
  * of which the library keeps a copy once an actor is set): observation -> actor -> action -> step without a launch or a
  * host round trip per step.  sample = 0: the distributions' mode (deterministic = True in the reference), 1: a draw
- * (counter-based RNG keyed on seed, global env index, episode step, agent).  Outputs as sdc_rollout (all required but
+ * (counter-based RNG keyed on seed, global env index, the env's episode number, episode step and a stream constant, one word per
+ * agent: THE POLICY HEAD below).  Outputs as sdc_rollout (all required but
  * final_obs); actions_out [n_steps][N][3] receives the actions, logits_out [n_steps][N][3][3] (may be NULL) the actors'
  * logits.  Only for the common case the specialised kernels serve (lock-step batch with feature rows, one data-centre
  * config of <= 32 racks, default rewards, an even number of envs) and three actors with the same activation; anything
- * else is refused. */
+ * else is refused.
+ * THE POLICY HEAD: from an agent's three fp32 logits l0, l1, l2 -- the values logits_out receives -- to the action its env step is
+ * given.  Both actor kernels (two and four envs per wavefront) do the same, and nothing but env state and configuration enters:
+ * the same steps asked for in launches of other lengths, or by a shard of a larger job, choose the same actions.
+ * MODE (sample = 0).  The first maximum: 1 if l1 > l0 and l1 >= l2, else 2 if l2 > l0 and l2 > l1, else 0 -- torch.argmax's rule,
+ * ties towards the lower action.
+ * DRAW (sample = 1).  One philox4x32_10 block per (env n, episode step) with counter (episode step, env_index_base + n, the env's
+ * episode number, 0xAC70) and key (seed's low word, seed's high word).  The episode step counts from 0 at the env's reset (the batch
+ * is in lock-step: one value per launched step); the episode number is the env's own -- 1 after its first reset, one more with every
+ * reset or auto-reset, the "episode" state array -- so envs of one batch may differ in it; a launch never crosses an episode's end.
+ * Words x, y, z serve agents ls, dc, bat, w is unused:  u = (float)(word >> 8) * 2^-24, in [0, 1) on a 24-bit grid.  Then, all fp32,
+ * exp2 the hardware's (v_exp_f32, ~1 ulp), every other operation rounded once (there is no multiply-add pair to fuse):
+ *   m = max(l0, l1, l2);  e_i = exp2((l_i - m) * log2 e), log2 e = 1.4426950408889634f;  t = u * ((e0 + e1) + e2);
+ *   action = (t >= e0) + (t >= e0 + e1)
+ * -- the inverse CDF of softmax(l); e2 enters the sum only.  An e_i that underflows to 0 is never drawn except by its place: l =
+ * (-200, 0, -200) draws 1 for every u, u = 0 included.
+ * NaN or infinite logits are not specified (torch's Categorical refuses them); finite weights and observations do not produce them:
+ * a hidden layer whose activations are all equal (a dead ReLU layer) leaves its LayerNorm's beta, not a NaN. */
 int sdc_rollout_actor(sdc_handle* h, int n_steps, int sample, float* obs, float* share_obs, float* rew, uint8_t* done,
                       float* info, float* final_obs, int32_t* actions_out, float* logits_out, void* stream);
 /* steps until the first env finishes its episode (0: a reset is due) */
