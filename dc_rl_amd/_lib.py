@@ -24,7 +24,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
            "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip", "sdc_plan_terms.hip",
-           "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip", "sdc_mpc_groups.hip"]
+           "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip", "sdc_mpc_groups.hip", "sdc_critic.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
@@ -165,6 +165,16 @@ class SdcActorParams(C.Structure):
     ]
 
 
+class SdcCriticParams(C.Structure):
+    """The V critic in torch's layout, with a ValueNorm folded into scale / shift (include/sustaindc_hip.h sdc_critic_params)."""
+    _fields_ = [
+        ("ln0_g", C.c_float * 29), ("ln0_b", C.c_float * 29),
+        ("w1", C.c_float * (64 * 29)), ("b1", C.c_float * 64), ("ln1_g", C.c_float * 64), ("ln1_b", C.c_float * 64),
+        ("w2", C.c_float * (64 * 64)), ("b2", C.c_float * 64), ("ln2_g", C.c_float * 64), ("ln2_b", C.c_float * 64),
+        ("w3", C.c_float * 64), ("b3", C.c_float), ("scale", C.c_float), ("shift", C.c_float), ("flags", C.c_int32),
+    ]
+
+
 class SdcPlanObjective(C.Structure):
     """What sdc_plan scores a candidate by (include/sustaindc_hip.h sdc_plan_objective)."""
     _fields_ = [
@@ -231,6 +241,7 @@ EXPORTS = [
     "sdc_plan_cem_groups", "sdc_set_plan_terms", "sdc_get_plan_terms",
     "sdc_set_plan_forecast", "sdc_get_plan_forecast", "sdc_forecast_traces", "sdc_rollout_actor_stats",
     "sdc_rollout_cem_stats", "sdc_rollout_cem_groups_stats",
+    "sdc_set_critic", "sdc_critic_values", "sdc_set_plan_critic", "sdc_get_plan_critic",
 ]
 
 
@@ -402,6 +413,10 @@ def load():
                                         vp, vp, vp, vp, vp, fp, fp, fp, vp, fp, fp, vp]
     L.sdc_rollout_cem_groups_stats.argtypes = [vp, C.c_int, C.POINTER(SdcMpcGroupParams), C.POINTER(SdcPlanObjective), C.c_int] + [vp] * 13 + [
         fp, fp, fp, vp, fp, fp, vp]
+    L.sdc_set_critic.argtypes = [vp, C.POINTER(SdcCriticParams)]
+    L.sdc_critic_values.argtypes = [vp, fp, C.c_longlong, fp, vp]
+    L.sdc_set_plan_critic.argtypes = [vp, C.c_double]
+    L.sdc_get_plan_critic.argtypes = [vp, dp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

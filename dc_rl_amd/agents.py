@@ -142,7 +142,8 @@ class ShootingMPCAgent:
     info_weights: the objective, as `plan` takes it.  The horizon is shortened to what the episode has left (the planner does not look
     across an episode's end); with fewer than two steps left the agent does nothing.  `last`: the latest PlanResult (None after a
     do-nothing fallback), `last_horizon` the horizon it used.  The agent plans through the env, so limits and a terminal term:
-    `env.set_plan_terms`.  `forecast`: None -- the env's plan forecast is left as it is (none set: perfect foresight, an oracle
+    `env.set_plan_terms`, and a learned value at the horizon's end: `env.set_critic` + `env.set_plan_critic` (no argument here: the term
+    lives on the engine, as the plan terms do).  `forecast`: None -- the env's plan forecast is left as it is (none set: perfect foresight, an oracle
     bound) --, or a mode's name for all four traces ("persistence", "daily"), or a dict of `set_plan_forecast`'s arguments; it is set
     on the env before the first decision."""
 
@@ -191,7 +192,8 @@ class CEMMPCAgent:
     seed on twin envs choose the same actions.  The horizon is shortened to what the episode has left (the planner does not look across
     an episode's end); with fewer than two steps left the agent does nothing.  `last`: the latest CEMResult (None after a do-nothing
     fallback), `last_horizon` the horizon it used.  The agent plans through the env, so limits and a terminal term:
-    `env.set_plan_terms`; `forecast` as ShootingMPCAgent's: set on the env before the first decision."""
+    `env.set_plan_terms`, a critic as the terminal value: `env.set_critic` + `env.set_plan_critic` (on the engine, like the terms: no
+    argument here); `forecast` as ShootingMPCAgent's: set on the env before the first decision."""
 
     DO_NOTHING = (1, 1, 2)
 
@@ -302,7 +304,8 @@ class GroupCEMMPCAgent(CEMMPCAgent):
     Replicas draw their own resets (those are keyed on the global env index), so the agent makes every group a copy of its first env
     (`sync_groups`) on its first decision and whenever the episode step has gone backwards (a reset or auto-reset), and starts probs
     and best_seq afresh then.  `last`: the latest GroupCEMResult (None after a do-nothing fallback).  As for CEMMPCAgent, limits and a
-    terminal term: `env.set_plan_terms`, and `forecast` (a "values" forecast must be identical within a group)."""
+    terminal term: `env.set_plan_terms`, a critic as the terminal value: `env.set_critic` + `env.set_plan_critic` (on the engine: no
+    argument here), and `forecast` (a "values" forecast must be identical within a group)."""
 
     def __init__(self, group_size: int, n_elite: int = 2, n_iters: int = 3, horizon: int = 8, seed: int = 0, alpha: float = 0.0,
                  p_min: float = 0.0, warm_start: bool = True, reward_weights=(1.0, 1.0, 1.0), gamma: float = 1.0, info_weights=None,

@@ -29,6 +29,7 @@
 #include "sdc_cem_groups.hpp"
 #include "sdc_plan.hpp"
 #include "sdc_plan_terms.hpp"
+#include "sdc_critic.hpp"
 #include "sdc_forecast.hpp"
 #include "sdc_stats.hpp"
 #include "sdc_policy_stats.hpp"
@@ -138,6 +139,11 @@ struct sdc_handle {
   IdxStage plan_stage{sizeof(double), SDC_MARK_MAX_STEPS};
   // sdc_set_plan_terms: what the plan calls score with next to their objective (both counts 0: nothing set, every field 0)
   sdc_plan_terms plan_terms{};
+  // sdc_set_critic: the critic in the kernels' layout (sdc_critic_pack.hpp), allocated when the first one is set; sdc_set_plan_critic:
+  // the weight the plan calls give its value of the horizon's last share_obs rows (0: off, nothing launched)
+  SdcCriticDev* critic_dev = nullptr;
+  bool critic_set = false;
+  double plan_critic_weight = 0.0;
   // sdc_set_plan_forecast: what the plan calls' rollouts believe the traces ahead are (every field 0: nothing set); the forecast
   // [n_steps + 2][N][4] of a plan call and the row bits its overlay replaces (sdc_forecast.hpp), grown on demand and freed with the handle
   sdc_plan_forecast plan_forecast{};
@@ -1831,7 +1837,8 @@ static SdcPlanScoreTerms plan_terms_plan(const PlanSession& P) {
 }
 
 // Per candidate: roll out (rollout_chunks), score each chunk, rewind -- from the mark the session has taken into h->plan_rows.  With
-// plan terms on the handle the score is sdc_plan_score_terms_kernel's, without it is sdc_plan_score_kernel's.
+// plan terms on the handle the score is sdc_plan_score_terms_kernel's, without it is sdc_plan_score_kernel's; with a plan critic weight
+// sdc_critic_terminal_kernel adds the critic's terminal value behind the last chunk's score.
 static int plan_candidates(PlanSession& P, const int n_cand, const int32_t* actions, double* returns, double* score) {
   sdc_handle* const h = P.h;
   const size_t N = (size_t)h->cfg.n_envs;
@@ -1839,6 +1846,10 @@ static int plan_candidates(PlanSession& P, const int n_cand, const int32_t* acti
   S.g = static_cast<const double*>(P.g_dev);
   const bool terms = h->plan_terms.n_limits > 0 || h->plan_terms.n_terminal > 0;
   SdcPlanScoreTerms T = plan_terms_plan(P);
+  // the plan critic (sdc_set_plan_critic): behind the score launch of the chunk that holds the horizon's last step, the critic's value
+  // of that step's share_obs rows in the block, added into the candidate's score (sdc_critic.hip)
+  const double critic_weight = h->plan_critic_weight;
+  SdcCriticTerminal V{h->critic_dev, nullptr, nullptr, (int)N, P.g_terminal * critic_weight, nullptr};
   int rc = 0;
   for (int c = 0; c < n_cand && rc == 0; c++) {
     S.returns = returns ? returns + (size_t)c * N * 3 : nullptr;
@@ -1847,9 +1858,16 @@ static int plan_candidates(PlanSession& P, const int n_cand, const int32_t* acti
                         [&](const int k0, const int steps) {
                           S.first_step = k0;
                           S.steps = steps;
-                          if (!terms) return launched("sdc_plan_score_kernel", sdc_plan_score_launch(S, P.st()));
-                          T.S = S;
-                          return launched("sdc_plan_score_terms_kernel", sdc_plan_score_terms_launch(T, P.st()));
+                          if (terms) T.S = S;
+                          const int scored = terms ? launched("sdc_plan_score_terms_kernel", sdc_plan_score_terms_launch(T, P.st()))
+                                                   : launched("sdc_plan_score_kernel", sdc_plan_score_launch(S, P.st()));
+                          if (scored || critic_weight == 0.0 || k0 + steps != P.R.n_steps) return scored;
+                          const size_t last = (size_t)(steps - 1) * N;      // the chunk's last step is the horizon's
+                          V.rows = reinterpret_cast<const float*>(h->plan_out + P.R.B.share_obs) + last * SDC_SHARE_OBS_DIM;
+                          V.done = h->plan_out + P.R.B.done + last;
+                          V.score = S.score;
+                          h->last_step_kernel = "sdc_critic_terminal_kernel";
+                          return launched("sdc_critic_terminal_kernel", sdc_critic_terminal_launch(V, P.st()));
                         });
     if (rc == 0) rc = sdc_rewind_envs(h, nullptr, (int)N, h->plan_rows, h->plan_manifest.data(), P.obs, P.share_obs, P.stream);
   }
@@ -1991,6 +2009,51 @@ int sdc_set_plan_terms(sdc_handle* h, const sdc_plan_terms* terms) {
 int sdc_get_plan_terms(const sdc_handle* h, sdc_plan_terms* out) {
   if (!h || !out) return fail_msg("sdc_get_plan_terms: null handle or out");
   *out = h->plan_terms;
+  return 0;
+}
+
+// ---- the critic (sdc_critic.hip) -------------------------------------------------------------------------------------------------------
+// The contract: include/sustaindc_hip.h THE CRITIC; the pack and what is refused about the parameters: sdc_critic_pack.hpp.
+int sdc_set_critic(sdc_handle* h, const sdc_critic_params* p) {
+  static const std::string w = "sdc_set_critic: ";
+  if (!h || !p) return fail_msg(w + "null handle or params");
+  if (const char* why = sdc_critic_params_error(p)) return fail_msg(w + why);
+  HIP_TRY(hipSetDevice(h->device));
+  if (!h->critic_dev && dev_alloc(h, &h->critic_dev, 1) != 0) return -1;
+  std::unique_ptr<SdcCriticDev> packed(new SdcCriticDev);      // (26 KB: on the heap, per call -- see sdc_set_actor)
+  sdc_critic_pack(p, packed.get());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h->critic_dev, packed.get(), sizeof(SdcCriticDev), hipMemcpyHostToDevice));
+  h->critic_set = true;
+  return 0;
+}
+
+int sdc_critic_values(sdc_handle* h, const float* share_obs, long long n_rows, float* values, void* stream) {
+  static const std::string w = "sdc_critic_values: ";
+  if (!h) return fail_msg(w + "null handle");
+  if (!h->critic_set) return fail_msg(w + "sdc_set_critic first");
+  if (n_rows < 1) return fail_msg(w + "n_rows = " + std::to_string(n_rows) + " must be positive");
+  if (!share_obs || !values) return fail_msg(w + "null array");
+  if (((reinterpret_cast<uintptr_t>(share_obs) | reinterpret_cast<uintptr_t>(values)) & 3u) != 0)
+    return fail_msg(w + "share_obs / values not dword-aligned");
+  HIP_TRY(hipSetDevice(h->device));
+  h->last_step_kernel = "sdc_critic_values_kernel";
+  return launched("sdc_critic_values_kernel",
+                  sdc_critic_values_launch(SdcCriticValues{h->critic_dev, share_obs, n_rows, values}, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int sdc_set_plan_critic(sdc_handle* h, double weight) {
+  static const std::string w = "sdc_set_plan_critic: ";
+  if (!h) return fail_msg(w + "null handle");
+  if (!std::isfinite(weight)) return fail_msg(w + "weight = " + std::to_string(weight) + " is not finite");
+  if (weight != 0.0 && !h->critic_set) return fail_msg(w + "weight = " + std::to_string(weight) + " while no critic is set (sdc_set_critic first)");
+  h->plan_critic_weight = weight;
+  return 0;
+}
+
+int sdc_get_plan_critic(const sdc_handle* h, double* weight) {
+  if (!h || !weight) return fail_msg("sdc_get_plan_critic: null handle or out");
+  *weight = h->plan_critic_weight;
   return 0;
 }
 

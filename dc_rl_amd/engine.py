@@ -394,6 +394,76 @@ def actor_params(params) -> L.SdcActorParams:
     return p
 
 
+_CRITIC_SD_KEYS = {   # the reference's VNet state_dict -> sdc_critic_params fields
+    "ln0_g": "base.feature_norm.weight", "ln0_b": "base.feature_norm.bias",
+    "w1": "base.mlp.fc.0.weight", "b1": "base.mlp.fc.0.bias", "ln1_g": "base.mlp.fc.2.weight", "ln1_b": "base.mlp.fc.2.bias",
+    "w2": "base.mlp.fc.3.weight", "b2": "base.mlp.fc.3.bias", "ln2_g": "base.mlp.fc.5.weight", "ln2_b": "base.mlp.fc.5.bias",
+    "w3": "v_out.weight", "b3": "v_out.bias",
+}
+_CRITIC_SHAPES = {"ln0_g": (29,), "ln0_b": (29,), "w1": (64, 29), "b1": (64,), "ln1_g": (64,), "ln1_b": (64,),
+                  "w2": (64, 64), "b2": (64,), "ln2_g": (64,), "ln2_b": (64,), "w3": (64,), "b3": ()}
+
+
+def value_norm_scale_shift(value_norm):
+    """A ValueNorm folded into (scale, shift) of `value * scale + shift`, in fp32 as harl/common/valuenorm.py running_mean_var and
+    denormalize do it: None -> (1, 0); a (mean, var) pair -> (sqrt(var), mean); an object or dict with running_mean, running_mean_sq
+    and debiasing_term -> the debiased mean and variance first (the debiasing term clamped at 1e-5, the variance at 1e-2)."""
+    f = np.float32
+    if value_norm is None:
+        return 1.0, 0.0
+    get = (lambda k: value_norm[k]) if isinstance(value_norm, dict) else (lambda k: getattr(value_norm, k))
+    num = lambda v: f(np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32).reshape(-1)[0])
+    if isinstance(value_norm, (tuple, list)):
+        if len(value_norm) != 2:
+            raise ValueError("critic_params: value_norm must be None, a (mean, var) pair, or hold running_mean, running_mean_sq and debiasing_term")
+        mean, var = num(value_norm[0]), num(value_norm[1])
+    else:
+        try:
+            rm, rsq, deb = num(get("running_mean")), num(get("running_mean_sq")), num(get("debiasing_term"))
+        except (KeyError, AttributeError):
+            raise KeyError("critic_params: value_norm holds no running_mean / running_mean_sq / debiasing_term (a ValueNorm moved across "
+                           "devices drops them from its state_dict: pass the object)") from None
+        deb = np.maximum(deb, f(1e-5))
+        mean, mean_sq = f(rm / deb), f(rsq / deb)
+        var = np.maximum(f(mean_sq - f(mean * mean)), f(1e-2))
+    return float(np.sqrt(f(var))), float(mean)
+
+
+def critic_params(params, value_norm=None, activation="tanh") -> L.SdcCriticParams:
+    """The V critic as the library's struct.  `params`: a state_dict of the reference's VNet (harl/models/value_function_models/v_net.py:
+    keys base.feature_norm.* -- absent: use_feature_normalization off --, base.mlp.fc.{0,2,3,5}.*, v_out.*; tensors or arrays), or a dict
+    of the fields of sdc_critic_params (w3 [64] or [1, 64]; optionally "scale", "shift", "flags" or "activation" /
+    "use_feature_normalization").  `value_norm`: see value_norm_scale_shift.  `activation`: "tanh" or "relu".  KeyError for a missing
+    parameter, ValueError for a wrong shape, NotImplementedError for another activation."""
+    p = L.SdcCriticParams()
+    feature_norm = True
+    for field, shape in _CRITIC_SHAPES.items():
+        v = params.get(field, params.get(_CRITIC_SD_KEYS[field]))
+        if v is None:
+            if field in ("ln0_g", "ln0_b"):      # use_feature_normalization False: no feature_norm in the state_dict
+                feature_norm = False
+                continue
+            raise KeyError(f"critic parameters: neither {field!r} nor {_CRITIC_SD_KEYS[field]!r} given")
+        a = np.ascontiguousarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+        if field in ("w3", "b3") and a.size == int(np.prod(shape, dtype=np.int64)):
+            a = a.reshape(shape)                 # (v_out: Linear(64, 1) stores [1, 64] and [1])
+        if a.shape != shape:
+            raise ValueError(f"critic parameter {field}: shape {a.shape}, expected {shape} (hidden_sizes [64, 64], 29 inputs, one value)")
+        if field == "b3":
+            p.b3 = float(a)
+        else:
+            C.memmove(getattr(p, field), a.ctypes.data, a.nbytes)
+    act = params.get("activation", activation)
+    if act not in ("tanh", "relu", 0, 1):
+        raise NotImplementedError(f"critic activation {act!r}: the kernel runs tanh and relu")
+    p.flags = (1 if params.get("use_feature_normalization", feature_norm) else 0) | ({"tanh": 0, "relu": 1}.get(act, act) << 1)
+    if "flags" in params:
+        p.flags = int(params["flags"])
+    scale, shift = value_norm_scale_shift(value_norm)
+    p.scale, p.shift = float(params.get("scale", scale)), float(params.get("shift", shift))
+    return p
+
+
 class SdcEngine:
     def __init__(self, n_envs: int, episode_steps: int = 672, device: int = 0, n_locations: int = 1,
                  n_dc_configs: int = 1, auto_reset: bool = True, seed: int = 0, hist_cap: int = 10000,
@@ -434,6 +504,7 @@ class SdcEngine:
         self._done_buf = None
         self._forecast_values = None      # set_plan_forecast's `values`, kept alive while the library holds its address
         self._actors = {}                 # set_actor's structs by slot
+        self._critic = None               # set_critic's struct
         with torch.cuda.device(self.device):
             torch.cuda.init()
             L.check(self.lib.sdc_create(C.byref(cfg), C.byref(self._h)))
@@ -642,12 +713,14 @@ class SdcEngine:
         self._call(self.lib.sdc_set_actor, slot, C.byref(p))
         self._actors[slot] = p      # (the host copy: what a copy of this engine is given, SustainDCVecEnv._take_state)
 
-    def rollout_actor(self, n_steps: int, sample: bool = False, want_logits: bool = False):
+    def rollout_actor(self, n_steps: int, sample: bool = False, want_logits: bool = False, want_values: bool = False):
         """K env-steps in ONE launch with the three actors (set_actor) choosing every action inside the kernel from the
         step's own observations -- the closed loop observation -> actor -> action -> step without a launch per step.
         sample=False: the distributions' mode (the reference's deterministic=True), True: a draw.
         Returns (obs [K,N,3,26], share_obs [K,N,29], rew [K,N,3], done [K,N], info [K,N,44], actions [K,N,3] int32,
-        logits [K,N,3,3] or None).  K must not run past the end of the episode (steps_to_episode_end())."""
+        logits [K,N,3,3] or None).  K must not run past the end of the episode (steps_to_episode_end()).
+        want_values=True appends values [K,N]: the critic's (set_critic) value of every returned share_obs row, one
+        `critic_values` launch behind the rollout -- what a policy-gradient batch needs next to the rest."""
         t = self.torch
         K, N = int(n_steps), self.n_envs
         out = self._rollout_outputs(K)
@@ -656,7 +729,55 @@ class SdcEngine:
         self._call(self.lib.sdc_rollout_actor, K, 1 if sample else 0, *[_p(x) for x in out], _p(self.final_obs), _p(acts), _p(logits),
                    self._stream(), wrote=out + (acts, logits))
         self._views_follow(*out)
+        if want_values:
+            return out + (acts, logits, self.critic_values(out[1]))
         return out + (acts, logits)
+
+    # ------------------------------------------------------------------ the critic: values, and the planners' terminal value
+    def set_critic(self, params, value_norm=None, activation="tanh"):
+        """The V critic for critic_values(), rollout_actor(want_values=True) and the planners' terminal value (set_plan_critic):
+        `params`, `value_norm` and `activation` as `critic_params` takes them (a VNet state_dict or the fields of sdc_critic_params;
+        None, a (mean, var) pair or a ValueNorm; "tanh" or "relu").  The call waits for the device (a launch in flight may read the
+        critic set before).  ValueError, with the critic set before still in force, for what the library refuses: an entry that is not
+        finite, scale <= 0, unknown flag bits."""
+        self._set_critic_struct(critic_params(params, value_norm, activation))
+
+    def _set_critic_struct(self, p: L.SdcCriticParams):
+        self._call(self.lib.sdc_set_critic, C.byref(p), refuses=True)
+        self._critic = p      # (the host copy: what a copy of this engine is given, SustainDCVecEnv._take_state)
+
+    def critic_values(self, share_obs):
+        """The critic's value of every row of `share_obs`, a contiguous fp32 tensor [..., 29] on this engine's device -> fp32 [...]
+        (sdc_critic_values: one launch, stream-ordered; a row's value depends on that row alone).  ValueError for another tensor, an
+        empty one, and before set_critic."""
+        t = self.torch
+        if not (isinstance(share_obs, t.Tensor) and share_obs.dtype == t.float32 and share_obs.is_cuda and share_obs.is_contiguous() and
+                share_obs.dim() >= 1 and share_obs.shape[-1] == L.SHARE_OBS_DIM):
+            raise ValueError(f"critic_values: share_obs must be a contiguous float32 CUDA tensor of shape (..., {L.SHARE_OBS_DIM})")
+        if share_obs.device != self.device:
+            raise ValueError(f"critic_values: share_obs is on {share_obs.device}, this engine runs on {self.device}")
+        values = t.empty(share_obs.shape[:-1], dtype=t.float32, device=self.device)
+        self._behind_torch_stream()
+        self._call(self.lib.sdc_critic_values, _p(share_obs), values.numel(), _p(values), self._stream(), refuses=True,
+                   wrote=(share_obs, values))
+        return values
+
+    def set_plan_critic(self, weight: float):
+        """The critic (set_critic) as the planners' terminal value, kept on the engine next to the plan terms (sdc_set_plan_critic):
+        while `weight` is not 0, every later `plan`, `plan_cem` and `plan_cem_groups` -- and `rollout_cem_stats` /
+        `rollout_cem_groups_stats`, whose predicted score then includes it -- adds gamma ** K * weight * V(share_obs after the horizon's
+        last step) to a candidate's score, 0 where that step ended the episode; `returns` never see it (the exact operation order:
+        include/sustaindc_hip.h).  One more launch per candidate.  0 (the default) turns it off: nothing is launched and every
+        result is what it is without a critic.  Host state: nothing is enqueued.  ValueError for a weight that is not finite, and for
+        a weight other than 0 before set_critic."""
+        self._call(self.lib.sdc_set_plan_critic, float(weight), refuses=True)
+
+    @property
+    def plan_critic(self) -> float:
+        """The plan critic's weight in force, read back from the library (0.0: off)"""
+        w = C.c_double()
+        self._call(self.lib.sdc_get_plan_critic, C.byref(w), refuses=True)
+        return w.value
 
     # ------------------------------------------------------------------ state access (parity injection / checkpoint)
     def _state_array(self, name):

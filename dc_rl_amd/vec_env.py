@@ -559,6 +559,29 @@ class SustainDCVecEnv(ShareVecEnv):
         """(limits, terminal) in force (SdcEngine.plan_terms)"""
         return self.engine.plan_terms
 
+    def set_critic(self, params, value_norm=None, activation="tanh"):
+        """The V critic for critic_values() and the planners' terminal value (SdcEngine.set_critic, which documents the arguments).
+        It stays across reset() and goes to a copy.deepcopy of this env.  NotImplementedError in the concatenated shared-observation
+        layout: a critic trained there sees the agents' observations side by side (78 inputs), not the engine's 29-entry share_obs."""
+        if self.share_concat:
+            raise NotImplementedError("set_critic: this env hands out the concatenated shared observation (78 inputs); the critic "
+                                      "kernel runs over the engine's 29-entry share_obs rows")
+        self.engine.set_critic(params, value_norm, activation)
+
+    def critic_values(self, share_obs):
+        """The critic's value of every row of a contiguous float32 device tensor [..., 29] -> [...] (SdcEngine.critic_values)"""
+        return self.engine.critic_values(share_obs)
+
+    def set_plan_critic(self, weight):
+        """The critic as the terminal value of every later plan / plan_cem / plan_cem_groups of this env (SdcEngine.set_plan_critic);
+        0 turns it off.  The weight stays across reset() and goes to a copy.deepcopy of this env."""
+        self.engine.set_plan_critic(weight)
+
+    @property
+    def plan_critic(self):
+        """the plan critic's weight in force (SdcEngine.plan_critic)"""
+        return self.engine.plan_critic
+
     def set_plan_forecast(self, workload=None, carbon=None, temperature=None, wet_bulb=None, values=None):
         """What every later plan / plan_cem / plan_cem_groups of this env believes the traces ahead are (SdcEngine.set_plan_forecast,
         which documents the arguments); `set_plan_forecast(None)` or no arguments clears it.  It stays across reset() and goes to a
@@ -752,6 +775,9 @@ class SustainDCVecEnv(ShareVecEnv):
         self.engine._set_plan_forecast_state(modes, None if values is None else values.to(self.engine.device, copy=True))
         for slot, p in sorted(src.engine._actors.items()):      # (before the reset below: it fills the closed loop's observation copy)
             self.engine._set_actor_struct(slot, p)
+        if src.engine._critic is not None:
+            self.engine._set_critic_struct(src.engine._critic)
+            self.engine.set_plan_critic(src.engine.plan_critic)
         self.months, self._cfg_id, self._const = list(src.months), list(src._cfg_id), list(src._const)
         if not src._need_reset:
             self.engine.reset()            # (the library restores into envs that have been reset once; every env is overwritten)

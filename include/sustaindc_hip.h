@@ -241,7 +241,8 @@ const char* sdc_last_error(void);
  *        existing argument list changed; sdc_mark_row_bytes, sdc_mark_envs, sdc_rewind_envs likewise; sdc_plan, sdc_plan_cem,
  *        sdc_rollout_stats and sdc_plan_cem_groups likewise; sdc_set_plan_terms and sdc_get_plan_terms likewise;
  *        sdc_set_plan_forecast, sdc_get_plan_forecast and sdc_forecast_traces likewise; sdc_rollout_actor_stats, sdc_rollout_cem_stats
- *        and sdc_rollout_cem_groups_stats likewise) */
+ *        and sdc_rollout_cem_groups_stats likewise; sdc_set_critic, sdc_critic_values, sdc_set_plan_critic and sdc_get_plan_critic
+ *        likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -350,7 +351,8 @@ int sdc_last_done(const sdc_handle* h, uint8_t* done_host);
 /* name of the kernel the last sdc_step / sdc_rollout / sdc_rollout_actor launched ("" before the first): the host picks by batch size and configuration
  * between the general kernel, the common-case kernels with two / four envs per wavefront and the lane-per-env kernel of the
  * largest batches (csrc/sdc_dispatch.hpp: the whole decision, and the table of kernels) -- all give the same results; tests and benchmarks name
- * what they measured with this. */
+ * what they measured with this.  The critic's two kernels (sdc_critic_values, THE PLAN CRITIC) are named here as well when they were
+ * the last launch. */
 const char* sdc_last_step_kernel(const sdc_handle* h);
 
 /* parity injection + env checkpoint: copy one named state field to / from HOST memory, dense per env.
@@ -562,6 +564,47 @@ typedef struct {
 } sdc_plan_terms;
 int sdc_set_plan_terms(sdc_handle* h, const sdc_plan_terms* terms);
 int sdc_get_plan_terms(const sdc_handle* h, sdc_plan_terms* out);
+
+/* THE CRITIC.  replaces: the V critic's forward pass (harl/models/value_function_models/v_net.py VNet over harl/models/base/mlp.py
+ * MLPBase, hidden_sizes [64, 64], no recurrence) and harl/common/valuenorm.py ValueNorm.denormalize, over rows of share_obs:
+ *     LayerNorm(29) -> Linear(29, 64) -> act -> LayerNorm(64) -> Linear(64, 64) -> act -> LayerNorm(64) -> Linear(64, 1);  v * scale + shift
+ * fp32 throughout (LayerNorm: biased variance, eps 1e-5), the two hidden layers on fp32-input matrix instructions, 16 rows per wavefront
+ * (csrc/sdc_critic.hpp).  sdc_critic_params is torch's layout ([out][in], row-major), as sdc_actor_params is; flags bit 0: the feature
+ * LayerNorm is on (off: ln0_g / ln0_b are not used, but must be finite), bits 1-2: the activation, 0 tanh, 1 relu.  scale and shift fold a
+ * ValueNorm (sqrt of its debiased variance, its debiased mean); 1 and 0 without one.
+ * sdc_set_critic packs the parameters into the kernels' layout and copies them to the handle's device (host pointer; it waits for the
+ * device first: a launch in flight may still read the critic set before).  Refused (-2 and a message; the critic set before stays in
+ * force): a null handle or params; an entry that is not finite; scale <= 0; flag bits above bit 2 or an activation code above 1.
+ * sdc_critic_values: values[r] = the critic's value of share_obs row r, r < n_rows -- rows [n_rows][29] fp32, 116 bytes apart, device
+ * memory, dword-aligned; one launch of sdc_critic_values_kernel on `stream`, no synchronisation; a row's value does not depend on which
+ * other rows the call holds or on their order.  Refused: a null handle; no critic set; a null or not dword-aligned share_obs or values;
+ * n_rows < 1.  sdc_last_step_kernel names the kernel afterwards.
+ * THE PLAN CRITIC: the critic as the planners' terminal value -- MPC with a learned value at the horizon's end.  The weight is host state
+ * of the handle, next to the plan terms: sdc_set_plan_critic stores it, and while it is not 0 every later sdc_plan, sdc_plan_cem and
+ * sdc_plan_cem_groups call (and through them sdc_rollout_cem_stats and sdc_rollout_cem_groups_stats, whose predicted score then includes
+ * the term) launches, per candidate, one sdc_critic_terminal_kernel behind the score launch of the chunk that holds the horizon's last
+ * step and in front of the rewind.  With s_n the share_obs row env n (a replica is an env row) has after step n_steps - 1 of the
+ * candidate's rollout and done_n that step's done flag:
+ *     V_n = the value sdc_critic_values gives for s_n, bit for bit
+ *     score[n] = score[n] + ((g_{n_steps-1} * gamma) * weight) * (done_n ? 0.0 : (double) V_n)
+ * fp64, no fused multiply-add; the two factors in front are multiplied on the host, in that order.  An episode that ends with the horizon
+ * has no value behind it: the term is 0 there.  `returns` do not see the term; the plan terms, the selection rule and the CEM calls'
+ * ranking, elites and refit are what they were and see these scores.  With weight 0 (the default) nothing is launched and every result
+ * is bit for bit what it is without a critic.  sdc_last_step_kernel names sdc_critic_terminal_kernel after a plan call that launched it
+ * (the rewind behind it launches no step kernel).
+ * Refused: a null handle (or out); a weight that is not finite; a weight other than 0 while no critic is set. */
+typedef struct {
+  float ln0_g[29], ln0_b[29];                        /* base.feature_norm */
+  float w1[64 * 29], b1[64], ln1_g[64], ln1_b[64];   /* base.mlp.fc.0, fc.2 */
+  float w2[64 * 64], b2[64], ln2_g[64], ln2_b[64];   /* base.mlp.fc.3, fc.5 */
+  float w3[64], b3;                                  /* v_out */
+  float scale, shift;                                /* > 0, finite */
+  int32_t flags;
+} sdc_critic_params;
+int sdc_set_critic(sdc_handle* h, const sdc_critic_params* p);
+int sdc_critic_values(sdc_handle* h, const float* share_obs, long long n_rows, float* values, void* stream);
+int sdc_set_plan_critic(sdc_handle* h, double weight);
+int sdc_get_plan_critic(const sdc_handle* h, double* weight);
 
 /* PLAN FORECAST: what the plan calls' rollouts believe the traces of the next n_steps steps are.  Without one a plan call's rollouts
  * read the episode's own feature rows -- the real workload, carbon intensity, dry bulb (with the weather noise the episode drew) and wet
