@@ -265,18 +265,20 @@ class CEMMPCAgent:
         if not self._forecast_set:
             _set_forecast(env, self.forecast)
             self._forecast_set = True
-        H, N = self.horizon, eng.n_envs
+        H, lead = self.horizon, self._lead(eng)
+        sync = self._sync_due(step)
         # the carried result, if the first decision may start from it (_start's rule but for the horizon, which the library checks)
-        carried = self.warm_start and self._probs is not None and self._step is not None and step > self._step
-        probs = torch.empty((H, N, 3, 3), dtype=torch.float64, device=eng.device)
-        best_seq = torch.empty((H, N, 3), dtype=torch.int32, device=eng.device)
+        carried = not sync and self.warm_start and self._probs is not None and self._step is not None and step > self._step
+        probs = torch.empty((H, lead, 3, 3), dtype=torch.float64, device=eng.device)
+        best_seq = torch.empty((H, lead, 3), dtype=torch.int32, device=eng.device)
         k = int(self._probs.shape[0]) if carried else 0
         if k:
             probs[:k], best_seq[:k] = self._probs, self._best_seq
-        res = env.rollout_cem_stats(n_steps, H, self.n_iters, self.n_candidates, self.n_elite, probs=probs, best_seq=best_seq,
-                                    resume_steps=k, warm_start=self.warm_start, seed=self.seed, draw=self.draw, alpha=self.alpha,
-                                    p_min=self.p_min, idle_action=self.DO_NOTHING, reward_weights=self.reward_weights, gamma=self.gamma,
-                                    info_weights=self.info_weights, into=into)
+        res = self._rollout(env, n_steps, sync, probs=probs, best_seq=best_seq, resume_steps=k, warm_start=self.warm_start, seed=self.seed,
+                            draw=self.draw, alpha=self.alpha, p_min=self.p_min, idle_action=self.DO_NOTHING,
+                            reward_weights=self.reward_weights, gamma=self.gamma, info_weights=self.info_weights, into=into)
+        if sync:
+            self._synced()
         c = res.mpc
         self.draw = (self.draw + c.planned) & 0xFFFFFFFF
         self.last, self.last_horizon = None, c.steps
@@ -284,7 +286,7 @@ class CEMMPCAgent:
         self._step = step + n_steps - 1
         return res
 
-    # what GroupCEMMPCAgent does differently
+    # what GroupCEMMPCAgent does differently: in act(), then in rollout_stats()
     def _before(self, env, step):
         pass
 
@@ -293,6 +295,18 @@ class CEMMPCAgent:
 
     def _chosen(self, res):
         return res.action
+
+    def _lead(self, eng):      # the carried arrays' leading dimension: a distribution per env
+        return eng.n_envs
+
+    def _sync_due(self, step):
+        return False
+
+    def _synced(self):
+        pass
+
+    def _rollout(self, env, n_steps, sync, **kw):
+        return env.rollout_cem_stats(n_steps, self.horizon, self.n_iters, self.n_candidates, self.n_elite, **kw)
 
 
 class GroupCEMMPCAgent(CEMMPCAgent):
@@ -318,10 +332,9 @@ class GroupCEMMPCAgent(CEMMPCAgent):
         self.syncs = 0      # how often the groups have been re-synchronised
 
     def _before(self, env, step):
-        if self._step is None or step < self._step:      # the first decision, or a new episode: the replicas drew resets of their own
+        if self._sync_due(step):
             env.sync_groups(self.group_size)
-            self.syncs += 1
-            self._probs = self._best_seq = None
+            self._synced()
 
     def _plan(self, env, K, **kw):
         return env.plan_cem_groups(self.group_size, K, self.n_iters, self.n_elite, **kw)
@@ -338,31 +351,17 @@ class GroupCEMMPCAgent(CEMMPCAgent):
         `draw`, the carried distribution, `last_horizon` and the step it was made at are what those rounds would have left, so `act()`
         may follow (`last` is None).  `into`: an EpisodeStats of the env's to continue.  The engine's arguments are checked first: a
         refused call leaves the agent as it was, but for a `forecast`, which is set on the env before the first decision."""
-        import torch
-        eng = getattr(env, "engine", env)
-        n_steps = int(n_steps)
-        step = _mpc_horizon(env, self.horizon)[1]
-        if not self._forecast_set:
-            _set_forecast(env, self.forecast)
-            self._forecast_set = True
-        H, R = self.horizon, self.group_size
-        G = eng.n_envs // R
-        sync = self._step is None or step < self._step      # (_before's rule)
-        carried = not sync and self.warm_start and self._probs is not None and step > self._step
-        probs = torch.empty((H, G, 3, 3), dtype=torch.float64, device=eng.device)
-        best_seq = torch.empty((H, G, 3), dtype=torch.int32, device=eng.device)
-        k = int(self._probs.shape[0]) if carried else 0
-        if k:
-            probs[:k], best_seq[:k] = self._probs, self._best_seq
-        res = env.rollout_cem_groups_stats(n_steps, R, H, self.n_iters, self.n_elite, sync=sync, probs=probs, best_seq=best_seq,
-                                           resume_steps=k, warm_start=self.warm_start, seed=self.seed, draw=self.draw, alpha=self.alpha,
-                                           p_min=self.p_min, idle_action=self.DO_NOTHING, reward_weights=self.reward_weights,
-                                           gamma=self.gamma, info_weights=self.info_weights, into=into)
-        if sync:
-            self.syncs += 1
-        c = res.mpc
-        self.draw = (self.draw + c.planned) & 0xFFFFFFFF
-        self.last, self.last_horizon = None, c.steps
-        self._probs, self._best_seq = (c.probs[:c.steps], c.best_seq[:c.steps]) if c.steps else (None, None)
-        self._step = step + n_steps - 1
-        return res
+        return super().rollout_stats(env, n_steps, into)
+
+    def _lead(self, eng):
+        return eng.n_envs // self.group_size
+
+    def _sync_due(self, step):      # the first decision, or a new episode: the replicas drew resets of their own
+        return self._step is None or step < self._step
+
+    def _synced(self):
+        self.syncs += 1
+        self._probs = self._best_seq = None
+
+    def _rollout(self, env, n_steps, sync, **kw):
+        return env.rollout_cem_groups_stats(n_steps, self.group_size, self.horizon, self.n_iters, self.n_elite, sync=sync, **kw)

@@ -2082,6 +2082,13 @@ static int cem_refit_refused(const std::string& w, const int32_t* fixed_action, 
   if (!(p_min >= 0.0 && p_min <= 1.0 / 3.0)) return fail_msg(w + "p_min = " + std::to_string(p_min) + " outside [0, 1/3]");
   return 0;
 }
+// What sdc_plan_cem and sdc_rollout_cem_stats refuse alike about the per-env planner's parameters, in the former's order
+static int cem_params_refused(const std::string& w, const sdc_cem_params& c) {
+  if (cem_iters_refused(w, c.n_iters, c.iter0)) return -2;
+  if (c.n_cand < 2 || c.n_cand > SDC_CEM_MAX_CAND)
+    return fail_msg(w + "n_cand = " + std::to_string(c.n_cand) + " outside [2, " + std::to_string(SDC_CEM_MAX_CAND) + "]");
+  return cem_elite_refused(w, c.n_elite, "n_cand", c.n_cand) || cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min) ? -2 : 0;
+}
 
 extern "C++" {
 // the fields the per-env and the group kernels' plans share, from the fields the two parameter structs share
@@ -2139,6 +2146,39 @@ static int cem_iterations(PlanSession& P, const int n_iters, const int iter0, co
   }
   return rc;
 }
+
+// The per-env planner's body for a plan of K steps, as plan_marked takes it: (session) -> rc, which enqueues the iterations of c over
+// the caller's arrays.  sdc_plan_cem runs it once, sdc_rollout_cem_stats per planned decision with that decision's draw in c.
+static auto cem_body(const sdc_handle* h, const sdc_cem_params& c, const int K, double* probs, int32_t* best_seq, double* best_score,
+                     int32_t* best_action, int32_t* cand, double* cand_score) {
+  const int N = h->cfg.n_envs, n_iters = c.n_iters, iter0 = c.iter0, n_cand = c.n_cand;
+  SdcCemSample Q = cem_sample_plan<SdcCemSample>(N, K, c, probs, best_seq, cand);
+  Q.n_cand = n_cand;
+  Q.env_base = h->cfg.env_index_base;
+  SdcCemRefit T = cem_refit_plan<SdcCemRefit>(N, K, c, cand_score, cand, probs, best_seq, best_action);
+  T.n_cand = n_cand;
+  return [=](PlanSession& P) mutable {
+    return cem_iterations(P, n_iters, iter0, n_cand, cand, cand_score, best_score, (size_t)N, Q, sdc_cem_sample_launch,
+                          "sdc_cem_sample_kernel", T, sdc_cem_refit_launch, "sdc_cem_refit_kernel");
+  };
+}
+
+// ... and the groups planner's, the candidates in env slots: per iteration ONE rollout of the whole batch (plan_candidates with the
+// single "candidate" cand) between the group sample and the group refit kernel.  sdc_plan_cem_groups, sdc_rollout_cem_groups_stats.
+static auto cem_groups_body(const sdc_handle* h, const sdc_cem_group_params& c, const int K, double* probs, int32_t* best_seq,
+                            double* best_score, int32_t* best_action, int32_t* step_actions, int32_t* cand, double* cand_score) {
+  const int N = h->cfg.n_envs, G = N / c.group_size, n_iters = c.n_iters, iter0 = c.iter0;
+  SdcCemGroupSample Q = cem_sample_plan<SdcCemGroupSample>(N, K, c, probs, best_seq, cand);
+  SdcCemGroupRefit T = cem_refit_plan<SdcCemGroupRefit>(N, K, c, cand_score, cand, probs, best_seq, best_action);
+  Q.group_size = T.group_size = c.group_size;
+  Q.n_groups = T.n_groups = G;
+  Q.group_base = c.group_base;
+  T.step_actions = step_actions;
+  return [=](PlanSession& P) mutable {
+    return cem_iterations(P, n_iters, iter0, 1, cand, cand_score, best_score, (size_t)G, Q, sdc_cem_group_sample_launch,
+                          "sdc_cem_group_sample_kernel", T, sdc_cem_group_refit_launch, "sdc_cem_group_refit_kernel");
+  };
+}
 }  // extern "C++"
 
 int sdc_plan_cem(sdc_handle* h, int n_steps, const sdc_cem_params* cem, const sdc_plan_objective* objective, double* probs,
@@ -2148,24 +2188,13 @@ int sdc_plan_cem(sdc_handle* h, int n_steps, const sdc_cem_params* cem, const sd
   if (!h) return fail_msg(w + "null handle");
   if (!cem) return fail_msg(w + "null cem");
   const sdc_cem_params c = *cem;
-  if (cem_iters_refused(w, c.n_iters, c.iter0)) return -2;
-  if (c.n_cand < 2 || c.n_cand > SDC_CEM_MAX_CAND)
-    return fail_msg(w + "n_cand = " + std::to_string(c.n_cand) + " outside [2, " + std::to_string(SDC_CEM_MAX_CAND) + "]");
-  if (cem_elite_refused(w, c.n_elite, "n_cand", c.n_cand) || cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min)) return -2;
+  if (cem_params_refused(w, c)) return -2;
   sdc_plan_objective obj;
   if (plan_refused("sdc_plan_cem", h, n_steps, probs && best_seq && best_score && best_action && cand && cand_score, obs, share_obs,
                    objective, obj))
     return -2;
-  const int N = h->cfg.n_envs;
-  SdcCemSample Q = cem_sample_plan<SdcCemSample>(N, n_steps, c, probs, best_seq, cand);
-  Q.n_cand = c.n_cand;
-  Q.env_base = h->cfg.env_index_base;
-  SdcCemRefit F = cem_refit_plan<SdcCemRefit>(N, n_steps, c, cand_score, cand, probs, best_seq, best_action);
-  F.n_cand = c.n_cand;
-  return plan_session(h, n_steps, obj, obs, share_obs, stream, [&](PlanSession& P) {
-    return cem_iterations(P, c.n_iters, c.iter0, c.n_cand, cand, cand_score, best_score, (size_t)N, Q, sdc_cem_sample_launch,
-                          "sdc_cem_sample_kernel", F, sdc_cem_refit_launch, "sdc_cem_refit_kernel");
-  });
+  return plan_session(h, n_steps, obj, obs, share_obs, stream,
+                      cem_body(h, c, n_steps, probs, best_seq, best_score, best_action, cand, cand_score));
 }
 
 // What sdc_plan_cem_groups and sdc_rollout_cem_groups_stats refuse alike about the groups of a batch of N envs, in the former's order
@@ -2197,8 +2226,7 @@ static int groups_out_of_step_refused(const std::string& w, const sdc_handle* h,
   return 0;
 }
 
-// sdc_plan_cem with the candidates in env slots: per iteration ONE rollout of the whole batch (plan_candidates with the single
-// "candidate" cand) between the group sample and the group refit kernel.
+// sdc_plan_cem with the candidates in env slots (cem_groups_body)
 int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* cem, const sdc_plan_objective* objective, double* probs,
                         int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* step_actions, int32_t* cand,
                         double* cand_score, float* obs, float* share_obs, void* stream) {
@@ -2214,17 +2242,8 @@ int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* 
                    obs, share_obs, objective, obj))
     return -2;
   if (groups_out_of_step_refused(w, h, c.group_size)) return -2;
-  const int R = c.group_size, G = N / R;
-  SdcCemGroupSample Q = cem_sample_plan<SdcCemGroupSample>(N, n_steps, c, probs, best_seq, cand);
-  SdcCemGroupRefit F = cem_refit_plan<SdcCemGroupRefit>(N, n_steps, c, cand_score, cand, probs, best_seq, best_action);
-  Q.group_size = F.group_size = R;
-  Q.n_groups = F.n_groups = G;
-  Q.group_base = c.group_base;
-  F.step_actions = step_actions;
-  return plan_session(h, n_steps, obj, obs, share_obs, stream, [&](PlanSession& P) {
-    return cem_iterations(P, c.n_iters, c.iter0, 1, cand, cand_score, best_score, (size_t)G, Q, sdc_cem_group_sample_launch,
-                          "sdc_cem_group_sample_kernel", F, sdc_cem_group_refit_launch, "sdc_cem_group_refit_kernel");
-  });
+  return plan_session(h, n_steps, obj, obs, share_obs, stream,
+                      cem_groups_body(h, c, n_steps, probs, best_seq, best_score, best_action, step_actions, cand, cand_score));
 }
 
 // ---- episode statistics (sdc_stats.hip, sdc_policy_stats.hip) ---------------------------------------------------------------------
@@ -2255,11 +2274,11 @@ static int stats_refused(const std::string& w, const sdc_handle* h, const int n_
   if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) return fail_msg(w + "verify mode checks single steps (sdc_rollout refuses it as well)");
   return 0;
 }
-// ... and about the episode's end
-static int stats_past_end_refused(const std::string& w, const sdc_handle* h, const int n_steps) {
-  if (n_steps > h->mirror.steps_to_terminal())
-    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" +
-                    std::to_string(h->mirror.steps_to_terminal()) + " steps left)");
+// ... and about the episode's end, `left` steps away (the mirror's steps_to_terminal, or what a sync will make of it)
+static int stats_past_end_refused(const std::string& w, const int n_steps, const int left) {
+  if (n_steps > left)
+    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" + std::to_string(left) +
+                    " steps left)");
   return 0;
 }
 
@@ -2326,7 +2345,7 @@ int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int ac
   const StatsArrays a = {stats, returns, counts, obs, share_obs, rew, done, info, final_obs};
   if (stats_refused(w, h, n_steps, accumulate, a)) return -2;
   if (!actions && !sdc_all_policies(h->d.policy)) return fail_msg(w + "actions may only be NULL when every agent slot has a policy");
-  if (stats_past_end_refused(w, h, n_steps)) return -2;
+  if (stats_past_end_refused(w, n_steps, h->mirror.steps_to_terminal())) return -2;
   HIP_TRY(hipSetDevice(h->device));
   int chunk;
   SdcPlanBlock B;
@@ -2363,7 +2382,7 @@ int sdc_rollout_actor_stats(sdc_handle* h, int n_steps, int sample, int accumula
   if ((reinterpret_cast<uintptr_t>(policy_sums) & 15u) != 0) return fail_msg(w + "policy_sums not 16-byte aligned");
   if ((reinterpret_cast<uintptr_t>(policy_counts) & 3u) != 0) return fail_msg(w + "policy_counts not dword-aligned");
   if (actor_refused(w, h)) return -2;
-  if (stats_past_end_refused(w, h, n_steps)) return -2;
+  if (stats_past_end_refused(w, n_steps, h->mirror.steps_to_terminal())) return -2;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t N = (size_t)h->cfg.n_envs;
@@ -2397,9 +2416,10 @@ int sdc_rollout_actor_stats(sdc_handle* h, int n_steps, int sample, int accumula
 
 // ---- planner evaluation (sdc_mpc.hip) -----------------------------------------------------------------------------------------------
 // The contract: include/sustaindc_hip.h; the decision schedule: sdc_mpc_schedule.hpp; the two kernels' plans: sdc_mpc.hpp.  A planned
-// decision is sdc_plan_cem's own body (plan_marked around cem_iterations), the step sdc_rollout_stats' with a one-step chunk; the
+// decision is sdc_plan_cem's own body (plan_marked around cem_body), the step sdc_rollout_stats' with a one-step chunk; the
 // discount table of the longest horizon is staged once, and every decision reads its prefix.  sdc_rollout_cem_groups_stats
-// (sdc_mpc_groups.hip) is the same loop (mpc_steps) with sdc_plan_cem_groups' body, a sync in front and the agreement check behind the step.
+// (sdc_mpc_groups.hip) is the same loop (mpc_steps) with sdc_plan_cem_groups' body (cem_groups_body) and its own fold kernel, a sync in
+// front and the agreement check behind the step.
 
 // What both calls refuse about the loop's own parameters (the leading fields of sdc_mpc_params and sdc_mpc_group_params)
 static int mpc_loop_refused(const std::string& w, const int H, const int warm_start, const int resume, const int resume_steps,
@@ -2416,6 +2436,40 @@ static int mpc_loop_refused(const std::string& w, const int H, const int warm_st
   return 0;
 }
 
+// A caller's array under the name the messages give it, and the alignment in bytes the kernels need of it
+struct NamedArray {
+  const char* name;
+  const void* p;
+  unsigned align;
+};
+// the names of v's arrays of that alignment (0: of all of them), `sep` between them and `last` in front of the last one
+static std::string array_names(const std::vector<NamedArray>& v, const unsigned align, const char* sep, const char* last) {
+  std::string s, tail;
+  for (const NamedArray& x : v)
+    if (!align || x.align == align) {
+      if (!tail.empty()) s += (s.empty() ? "" : sep) + tail;
+      tail = x.name;
+    }
+  return s.empty() ? tail : s + last + tail;
+}
+// What both calls refuse about their own arrays, each list in its signature's order: `plan`, the planner's (all required, 8-byte or
+// dword aligned), and `opt`, the statistics' (given together or not at all, 16-byte or dword aligned)
+static int mpc_arrays_refused(const std::string& w, const std::vector<NamedArray>& plan, const std::vector<NamedArray>& opt) {
+  uintptr_t bits[2][17] = {};      // the addresses OR-ed together, by list and alignment
+  for (const NamedArray& x : plan) bits[0][x.align] |= reinterpret_cast<uintptr_t>(x.p);
+  for (const NamedArray& x : opt) bits[1][x.align] |= reinterpret_cast<uintptr_t>(x.p);
+  for (const NamedArray& x : plan)
+    if (!x.p) return fail_msg(w + "null array (" + array_names(plan, 0, ", ", " and ") + " are required)");
+  if (bits[0][8] & 7u) return fail_msg(w + array_names(plan, 8, " / ", " / ") + " not 8-byte aligned");
+  if (bits[0][4] & 3u) return fail_msg(w + array_names(plan, 4, " / ", " / ") + " not dword-aligned");
+  for (const NamedArray& x : opt)
+    if ((x.p == nullptr) != (opt[0].p == nullptr))
+      return fail_msg(w + array_names(opt, 0, ", ", " and ") + " are given together or not at all");
+  if (bits[1][16] & 15u) return fail_msg(w + array_names(opt, 16, " / ", " / ") + " not 16-byte aligned");
+  if (bits[1][4] & 3u) return fail_msg(w + array_names(opt, 4, " / ", " / ") + " not dword-aligned");
+  return 0;
+}
+
 // the longest planned decision of a call of n_steps that starts `left` steps before the episode's end: the first one (the horizon only
 // shrinks towards the episode's end); 0: every decision idles
 static int mpc_longest(const int H, const int warm_start, const int auto_reset, const int resume_steps, const int left, const int n_steps) {
@@ -2426,18 +2480,40 @@ static int mpc_longest(const int H, const int warm_start, const int auto_reset, 
 }
 
 extern "C++" {
-// The steps of a planner evaluation once its arguments have passed.  Every buffer at its largest before anything is enqueued: the step's
-// one-step block, the longest decision's (k_max steps) rows, block and forecast; then first() -> rc (the groups' sync); the discount table
-// of H steps staged once; then per step the schedule's decision d -- planned: start(d) -> rc and plan_marked around body(session, d)
-// -> rc, which enqueues the planner's iterations --, fold(d, init) -> rc, and the step: sdc_rollout_stats' path with a one-step chunk and
-// `actions` [N][3], behind its reduce kernel behind(B1, init) -> rc.  Behind the last step sdc_stats_last_kernel.
-template <class First, class Start, class Body, class Fold, class Behind>
-static int mpc_steps(sdc_handle* h, const int n_steps, const int H, const int warm_start, const int resume_steps, const int k_max,
-                     const int accumulate, const sdc_plan_objective& obj, const StatsArrays& a, const int32_t* actions, void* stream,
-                     First&& first, Start&& start, Body&& body, Fold&& fold, Behind&& behind) {
+// what the two fold kernels' plans share but for the decision's own fields and the idle actions (mpc_steps); best_score's rows are `row`
+// entries long (N, or G)
+template <class Fold>
+static Fold mpc_fold_plan(const int n_envs, const size_t row, const int n_iters, const double* best_score, int32_t* best_action,
+                          int32_t* plan_counts, double* plan_sums) {
+  Fold F;
+  std::memset(&F, 0, sizeof(F));
+  F.n_envs = n_envs;
+  F.best_action = best_action;
+  F.counts = plan_counts;
+  F.sums = plan_sums;
+  F.score_first = best_score;
+  F.score_last = best_score + (size_t)(n_iters - 1) * row;
+  return F;
+}
+
+// The steps of a planner evaluation once its arguments have passed, but for the forecast's reach, which is refused here, before the
+// device is touched.  m: the loop's fields (sdc_mpc_params or sdc_mpc_group_params); left: the steps the episode has left at the first
+// decision.  Every buffer at its largest before anything is enqueued: the step's one-step block, the longest decision's (k_max steps)
+// rows, block and forecast; then first() -> rc (the groups' sync); the discount table of H steps staged once; then per step the
+// schedule's decision d -- planned: sdc_mpc_start_kernel (plan A, of which the caller fills n_envs, probs and best_seq) and plan_marked
+// around body(d), the planner's body for that decision (cem_body, cem_groups_body) --, the fold kernel (plan F through `fold`; a planned
+// decision without statistics has nothing to fold), and the step: sdc_rollout_stats' path with a one-step chunk and `actions` [N][3],
+// behind its reduce kernel behind(B1, init) -> rc.  Behind the last step sdc_stats_last_kernel.  The idle actions go into A and F here.
+template <class Params, class Fold, class First, class Body, class Behind>
+static int mpc_steps(const std::string& w, sdc_handle* h, const int n_steps, const Params& m, const int left, const int accumulate,
+                     const sdc_plan_objective& obj, const StatsArrays& a, SdcMpcStart A, Fold F, hipError_t (*fold)(const Fold&, hipStream_t),
+                     const char* fold_kernel, const int32_t* actions, void* stream, First&& first, Body&& body, Behind&& behind) {
+  const int H = m.horizon, warm_start = m.warm_start, resume_steps = m.resume ? m.resume_steps : 0, auto_reset = h->cfg.auto_reset ? 1 : 0;
+  const int k_max = mpc_longest(H, warm_start, auto_reset, resume_steps, left, n_steps);
+  if (k_max > 0 && forecast_refused(w, h, k_max)) return -2;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int auto_reset = h->cfg.auto_reset ? 1 : 0;
+  for (int k = 0; k < 3; k++) A.idle[k] = F.idle[k] = m.idle_action[k];
   int chunk1;
   SdcPlanBlock B1;
   if (plan_out_block(h, 1, chunk1, B1)) return -1;
@@ -2464,12 +2540,18 @@ static int mpc_steps(sdc_handle* h, const int n_steps, const int H, const int wa
       const int init = (t == 0 && accumulate == 0) ? 1 : 0;
       if (d.planned) {
         const int K = d.steps;
-        rc = start(d);
+        A.steps = K;
+        A.fresh = d.fresh;
+        rc = launched("sdc_mpc_start_kernel", sdc_mpc_start_launch(A, st));
         PlanSession P{h, {}, g_dev, g[K - 1] * obj.gamma, a.obs, a.share_obs, stream};
         if (rc == 0 && (plan_prepare(h, K, obj, P.R) || plan_forecast_swap(h, K, W))) rc = -1;
-        if (rc == 0) rc = plan_marked(P, W, [&](PlanSession& P_) { return body(P_, d); });
+        if (rc == 0) rc = plan_marked(P, W, body(d));
       }
-      if (rc == 0) rc = fold(d, init);
+      if (rc == 0 && (!d.planned || F.counts)) {
+        F.planned = d.planned;
+        F.init = init;
+        rc = launched(fold_kernel, fold(F, st));
+      }
       if (rc == 0)
         rc = rollout_chunks(h, B1, 1, 1, rollout_of(h, actions, stream), [&](int, int) {
           R1.init = init;
@@ -2494,68 +2576,24 @@ int sdc_rollout_cem_stats(sdc_handle* h, int n_steps, const sdc_mpc_params* mpc,
   if (!mpc) return fail_msg(w + "null mpc");
   const sdc_mpc_params m = *mpc;
   const sdc_cem_params c = m.cem;
-  const int H = m.horizon;
-  if (mpc_loop_refused(w, H, m.warm_start, m.resume, m.resume_steps, m.idle_action)) return -2;
-  if (cem_iters_refused(w, c.n_iters, c.iter0)) return -2;
-  if (c.n_cand < 2 || c.n_cand > SDC_CEM_MAX_CAND)
-    return fail_msg(w + "n_cand = " + std::to_string(c.n_cand) + " outside [2, " + std::to_string(SDC_CEM_MAX_CAND) + "]");
-  if (cem_elite_refused(w, c.n_elite, "n_cand", c.n_cand) || cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min)) return -2;
-  if (!probs || !best_seq || !best_score || !best_action || !cand || !cand_score)
-    return fail_msg(w + "null array (probs, best_seq, best_score, best_action, cand and cand_score are required)");
-  const auto addr = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
-  if (((addr(probs) | addr(best_score) | addr(cand_score)) & 7u) != 0) return fail_msg(w + "probs / best_score / cand_score not 8-byte aligned");
-  if (((addr(best_seq) | addr(best_action) | addr(cand)) & 3u) != 0) return fail_msg(w + "best_seq / best_action / cand not dword-aligned");
-  if ((plan_counts == nullptr) != (plan_sums == nullptr)) return fail_msg(w + "plan_counts and plan_sums are given together or not at all");
-  if ((addr(plan_sums) & 15u) != 0) return fail_msg(w + "plan_sums not 16-byte aligned");
-  if ((addr(plan_counts) & 3u) != 0) return fail_msg(w + "plan_counts not dword-aligned");
+  const int H = m.horizon, N = h->cfg.n_envs;
+  if (mpc_loop_refused(w, H, m.warm_start, m.resume, m.resume_steps, m.idle_action) || cem_params_refused(w, c)) return -2;
+  if (mpc_arrays_refused(w,
+                         {{"probs", probs, 8}, {"best_seq", best_seq, 4}, {"best_score", best_score, 8}, {"best_action", best_action, 4},
+                          {"cand", cand, 4}, {"cand_score", cand_score, 8}},
+                         {{"plan_counts", plan_counts, 4}, {"plan_sums", plan_sums, 16}}))
+    return -2;
   sdc_plan_objective obj;
-  if (plan_objective_refused(w, objective, obj)) return -2;
-  if (stats_past_end_refused(w, h, n_steps)) return -2;
-  const int resume_steps = m.resume ? m.resume_steps : 0;
-  const int k_max = mpc_longest(H, m.warm_start, h->cfg.auto_reset ? 1 : 0, resume_steps, h->mirror.steps_to_terminal(), n_steps);
-  if (k_max > 0 && forecast_refused(w, h, k_max)) return -2;
-
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int N = h->cfg.n_envs;
-  SdcMpcStart A;
-  std::memset(&A, 0, sizeof(A));
-  A.n_envs = N;
-  A.probs = probs;
-  A.best_seq = best_seq;
-  SdcMpcFold F;
-  std::memset(&F, 0, sizeof(F));
-  F.n_envs = N;
-  F.best_action = best_action;
-  F.counts = plan_counts;
-  F.sums = plan_sums;
-  F.score_first = best_score;
-  F.score_last = best_score + (size_t)(c.n_iters - 1) * (size_t)N;
-  for (int k = 0; k < 3; k++) A.idle[k] = F.idle[k] = m.idle_action[k];
-
+  const int left = h->mirror.steps_to_terminal();
+  if (plan_objective_refused(w, objective, obj) || stats_past_end_refused(w, n_steps, left)) return -2;
   return mpc_steps(
-      h, n_steps, H, m.warm_start, resume_steps, k_max, accumulate, obj, a, best_action, stream, [] { return 0; },
+      w, h, n_steps, m, left, accumulate, obj, a, SdcMpcStart{N, 0, 0, {}, probs, best_seq},
+      mpc_fold_plan<SdcMpcFold>(N, (size_t)N, c.n_iters, best_score, best_action, plan_counts, plan_sums), sdc_mpc_fold_launch,
+      "sdc_mpc_fold_kernel", best_action, stream, [] { return 0; },
       [&](const SdcMpcDecision& d) {
-        A.steps = d.steps;
-        A.fresh = d.fresh;
-        return launched("sdc_mpc_start_kernel", sdc_mpc_start_launch(A, st));
-      },
-      [&](PlanSession& P, const SdcMpcDecision& d) {
-        const int K = d.steps;
         sdc_cem_params ck = c;
         ck.draw = c.draw + d.draw_index;
-        SdcCemSample Q = cem_sample_plan<SdcCemSample>(N, K, ck, probs, best_seq, cand);
-        Q.n_cand = c.n_cand;
-        Q.env_base = h->cfg.env_index_base;
-        SdcCemRefit T = cem_refit_plan<SdcCemRefit>(N, K, ck, cand_score, cand, probs, best_seq, best_action);
-        T.n_cand = c.n_cand;
-        return cem_iterations(P, c.n_iters, c.iter0, c.n_cand, cand, cand_score, best_score, (size_t)N, Q, sdc_cem_sample_launch,
-                              "sdc_cem_sample_kernel", T, sdc_cem_refit_launch, "sdc_cem_refit_kernel");
-      },
-      [&](const SdcMpcDecision& d, const int init) {
-        if (d.planned && !plan_counts) return 0;
-        F.planned = d.planned;
-        F.init = init;
-        return launched("sdc_mpc_fold_kernel", sdc_mpc_fold_launch(F, st));
+        return cem_body(h, ck, d.steps, probs, best_seq, best_score, best_action, cand, cand_score);
       },
       [](const SdcPlanBlock&, int) { return 0; });
 }
@@ -2582,16 +2620,11 @@ int sdc_rollout_cem_groups_stats(sdc_handle* h, int n_steps, const sdc_mpc_group
     return fail_msg(w + "sync_first with resume (behind the sync the first planned decision starts fresh: nothing can be resumed)");
   if (cem_iters_refused(w, c.n_iters, c.iter0) || cem_groups_refused(w, N, c) || cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min))
     return -2;
-  if (!probs || !best_seq || !best_score || !best_action || !step_actions || !cand || !cand_score)
-    return fail_msg(w + "null array (probs, best_seq, best_score, best_action, step_actions, cand and cand_score are required)");
-  const auto addr = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
-  if (((addr(probs) | addr(best_score) | addr(cand_score)) & 7u) != 0) return fail_msg(w + "probs / best_score / cand_score not 8-byte aligned");
-  if (((addr(best_seq) | addr(best_action) | addr(step_actions) | addr(cand)) & 3u) != 0)
-    return fail_msg(w + "best_seq / best_action / step_actions / cand not dword-aligned");
-  if ((plan_counts == nullptr) != (plan_sums == nullptr) || (plan_counts == nullptr) != (diverged == nullptr))
-    return fail_msg(w + "plan_counts, plan_sums and diverged are given together or not at all");
-  if ((addr(plan_sums) & 15u) != 0) return fail_msg(w + "plan_sums not 16-byte aligned");
-  if (((addr(plan_counts) | addr(diverged)) & 3u) != 0) return fail_msg(w + "plan_counts / diverged not dword-aligned");
+  if (mpc_arrays_refused(w,
+                         {{"probs", probs, 8}, {"best_seq", best_seq, 4}, {"best_score", best_score, 8}, {"best_action", best_action, 4},
+                          {"step_actions", step_actions, 4}, {"cand", cand, 4}, {"cand_score", cand_score, 8}},
+                         {{"plan_counts", plan_counts, 4}, {"plan_sums", plan_sums, 16}, {"diverged", diverged, 4}}))
+    return -2;
   sdc_plan_objective obj;
   if (plan_objective_refused(w, objective, obj)) return -2;
   // the steps the episode has left: behind a sync every replica stands where its group's first env stands
@@ -2602,32 +2635,14 @@ int sdc_rollout_cem_groups_stats(sdc_handle* h, int n_steps, const sdc_mpc_group
     for (int e = 0; e < N; e += R) most = std::max(most, h->mirror.t_rel(e));
     left0 = h->d.episode_steps - most;
   }
-  if (n_steps > left0)
-    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" + std::to_string(left0) +
-                    " steps left)");
+  if (stats_past_end_refused(w, n_steps, left0)) return -2;
   if (!m.sync_first && groups_out_of_step_refused(w, h, R)) return -2;
-  const int resume_steps = m.resume ? m.resume_steps : 0;
-  const int k_max = mpc_longest(H, m.warm_start, h->cfg.auto_reset ? 1 : 0, resume_steps, left0, n_steps);
-  if (k_max > 0 && forecast_refused(w, h, k_max)) return -2;
 
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  SdcMpcStart A;
-  std::memset(&A, 0, sizeof(A));
-  A.n_envs = G;
-  A.probs = probs;
-  A.best_seq = best_seq;
-  SdcMpcGroupFold F;
-  std::memset(&F, 0, sizeof(F));
-  F.n_envs = N;
+  SdcMpcGroupFold F = mpc_fold_plan<SdcMpcGroupFold>(N, (size_t)G, c.n_iters, best_score, best_action, plan_counts, plan_sums);
   F.n_groups = G;
-  F.best_action = best_action;
   F.step_actions = step_actions;
-  F.counts = plan_counts;
-  F.sums = plan_sums;
   F.diverged = diverged;
-  F.score_first = best_score;
-  F.score_last = best_score + (size_t)(c.n_iters - 1) * (size_t)G;
-  for (int k = 0; k < 3; k++) A.idle[k] = F.idle[k] = m.idle_action[k];
   SdcGroupAgree Y;
   std::memset(&Y, 0, sizeof(Y));
   Y.n_envs = N;
@@ -2635,7 +2650,8 @@ int sdc_rollout_cem_groups_stats(sdc_handle* h, int n_steps, const sdc_mpc_group
   Y.diverged = diverged;
 
   return mpc_steps(
-      h, n_steps, H, m.warm_start, resume_steps, k_max, accumulate, obj, a, step_actions, stream,
+      w, h, n_steps, m, left0, accumulate, obj, a, SdcMpcStart{G, 0, 0, {}, probs, best_seq}, F,
+      sdc_mpc_group_fold_launch, "sdc_mpc_group_fold_kernel", step_actions, stream,
       [&] {
         if (!m.sync_first) return 0;
         std::vector<int32_t> src((size_t)(N - G)), dst((size_t)(N - G));
@@ -2648,28 +2664,9 @@ int sdc_rollout_cem_groups_stats(sdc_handle* h, int n_steps, const sdc_mpc_group
         return sdc_clone_envs(h, src.data(), dst.data(), N - G, obs, share_obs, stream);
       },
       [&](const SdcMpcDecision& d) {
-        A.steps = d.steps;
-        A.fresh = d.fresh;
-        return launched("sdc_mpc_start_kernel", sdc_mpc_start_launch(A, st));
-      },
-      [&](PlanSession& P, const SdcMpcDecision& d) {
-        const int K = d.steps;
         sdc_cem_group_params ck = c;
         ck.draw = c.draw + d.draw_index;
-        SdcCemGroupSample Q = cem_sample_plan<SdcCemGroupSample>(N, K, ck, probs, best_seq, cand);
-        SdcCemGroupRefit T = cem_refit_plan<SdcCemGroupRefit>(N, K, ck, cand_score, cand, probs, best_seq, best_action);
-        Q.group_size = T.group_size = R;
-        Q.n_groups = T.n_groups = G;
-        Q.group_base = c.group_base;
-        T.step_actions = step_actions;
-        return cem_iterations(P, c.n_iters, c.iter0, 1, cand, cand_score, best_score, (size_t)G, Q, sdc_cem_group_sample_launch,
-                              "sdc_cem_group_sample_kernel", T, sdc_cem_group_refit_launch, "sdc_cem_group_refit_kernel");
-      },
-      [&](const SdcMpcDecision& d, const int init) {
-        if (d.planned && !plan_counts) return 0;
-        F.planned = d.planned;
-        F.init = init;
-        return launched("sdc_mpc_group_fold_kernel", sdc_mpc_group_fold_launch(F, st));
+        return cem_groups_body(h, ck, d.steps, probs, best_seq, best_score, best_action, step_actions, cand, cand_score);
       },
       [&](const SdcPlanBlock& B1, int) {
         if (!diverged) return 0;

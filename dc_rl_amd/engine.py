@@ -1133,14 +1133,38 @@ class SdcEngine:
         where every channel is "perfect".  A plan call of K steps plans against forecast_traces(K + 2)."""
         return self._traces("forecast_traces", n, False)
 
+    @staticmethod
+    def _three(who, name, values):
+        """`values` as three ints (ls, dc, bat)"""
+        three = [int(x) for x in values]
+        if len(three) != 3:
+            raise ValueError(f"{who}: {name} must be three integers (ls, dc, bat), got {len(three)}")
+        return three
+
     def _cem_fixed(self, who, fixed_action, seed, draw):
-        """fixed_action as three ints; the ValueErrors both CEM calls raise first"""
-        fixed = [int(x) for x in fixed_action]
-        if len(fixed) != 3:
-            raise ValueError(f"{who}: fixed_action must be three integers (ls, dc, bat), got {len(fixed)}")
+        """fixed_action as three ints; the ValueErrors every CEM call raises first"""
+        fixed = self._three(who, "fixed_action", fixed_action)
         if not 0 <= int(seed) < 1 << 64 or not 0 <= int(draw) < 1 << 32:
             raise ValueError(f"{who}: seed must fit 64 bits and draw 32, both unsigned")
         return fixed
+
+    @staticmethod
+    def _cem_shared(cem, n_iters, iter0, n_elite, fixed, seed, draw, alpha, p_min):
+        """the fields sdc_cem_params and sdc_cem_group_params share"""
+        cem.n_iters, cem.iter0, cem.n_elite = int(n_iters), int(iter0), int(n_elite)
+        cem.fixed_action[:] = fixed
+        cem.draw, cem.seed, cem.alpha, cem.p_min = int(draw), int(seed), float(alpha), float(p_min)
+
+    def _group_base(self, who, R, grouped, group_base):
+        """a groups call's `group_base` (None: env_index_base // R, refused where R does not divide it) as an int that fits 32 bits"""
+        if group_base is None:
+            base = int(self.config["env_index_base"])
+            if grouped and base % R:
+                raise ValueError(f"{who}: group_size = {R} does not divide env_index_base = {base} (pass group_base)")
+            group_base = base // R if grouped else 0
+        if not -(1 << 31) <= int(group_base) < 1 << 31:
+            raise ValueError(f"{who}: group_base must fit 32 bits")
+        return int(group_base)
 
     def _cem(self, who, fn, cem, fixed, K, lead, outputs, result, sized, check, sizes, n_iters, n_elite, probs, best_seq, seed, draw, iter0,
              alpha, p_min, reward_weights, gamma, info_weights):
@@ -1155,9 +1179,7 @@ class SdcEngine:
         if check and best_seq is not None:
             A.device_tensor(best_seq, who, "best_seq", t.int32, (K, lead, 3), device=self.device)
         obj = plan_objective(reward_weights, gamma, info_weights)
-        cem.n_iters, cem.iter0, cem.n_elite = int(n_iters), int(iter0), int(n_elite)
-        cem.fixed_action[:] = fixed
-        cem.draw, cem.seed, cem.alpha, cem.p_min = int(draw), int(seed), float(alpha), float(p_min)
+        self._cem_shared(cem, n_iters, iter0, n_elite, fixed, seed, draw, alpha, p_min)
         arrays = []
         if sized:
             # (probs and best_seq -- the defaults below, a caller's, CEMMPCAgent's shifted ones -- are read by the sample kernel)
@@ -1235,16 +1257,9 @@ class SdcEngine:
         K, N, R, n_it = int(horizon), self.n_envs, int(group_size), int(n_iters)
         fixed = self._cem_fixed("plan_cem_groups", fixed_action, seed, draw)
         grouped = 2 <= R <= L.CEM_MAX_GROUP and N % R == 0
-        if group_base is None:
-            base = int(self.config["env_index_base"])
-            if grouped and base % R:
-                raise ValueError(f"plan_cem_groups: group_size = {R} does not divide env_index_base = {base} (pass group_base)")
-            group_base = base // R if grouped else 0
-        if not -(1 << 31) <= int(group_base) < 1 << 31:
-            raise ValueError("plan_cem_groups: group_base must fit 32 bits")
         G = N // R if grouped else 0
         cem = L.SdcCemGroupParams()
-        cem.group_size, cem.group_base = R, int(group_base)
+        cem.group_size, cem.group_base = R, self._group_base("plan_cem_groups", R, grouped, group_base)
         sized = grouped and 1 <= K <= L.MARK_MAX_STEPS and n_it >= 1 and 0 <= int(iter0) <= L.CEM_MAX_ITERS - n_it
         outputs = [((n_it, G), t.float64), ((G, 3), t.int32), ((N, 3), t.int32), ((K, N, 3), t.int32), ((N,), t.float64)]
         return self._cem("plan_cem_groups", self.lib.sdc_plan_cem_groups, cem, fixed, K, G, outputs,
@@ -1330,6 +1345,50 @@ class SdcEngine:
                    _p(self.final_obs), self._stream(), refuses=True, wrote=(res.stats, res.returns, res.counts, pc, ps))
         return res
 
+    def _mpc_stats(self, who, fn, mpc, own, sized, sizes, grouped, n_steps, H, lead, outputs, left, n_iters, n_elite, probs, best_seq,
+                   resume_steps, warm_start, seed, draw, alpha, p_min, fixed_action, idle_action, reward_weights, gamma, info_weights, into,
+                   plan_stats):
+        """The closed-loop call of rollout_cem_stats and rollout_cem_groups_stats: library function `fn` with `mpc`, its params struct --
+        the loop's fields and the shared ones of its `cem` are filled here, the caller's own by own(), which raises the caller's own
+        ValueErrors at their place among the others --, probs [H, lead, 3, 3] / best_seq [H, lead, 3] (a caller's are validated, None:
+        new ones) and, behind them, new tensors of `outputs`' (shape, dtype), best_score and best_action first; `grouped`: the PlanStats
+        is per group with `diverged`, and the third output is step_actions.  left() behind the call: the steps the episode had left at
+        the first decision.  -> the EpisodeStats with its `mpc`.  Not `sized`: as in _cem."""
+        t = self.torch
+        fixed = self._cem_fixed(who, fixed_action, seed, draw)
+        idle = self._three(who, "idle_action", idle_action)
+        k_res = int(resume_steps)
+        if k_res < 0 or (k_res > 0 and (probs is None or best_seq is None)):
+            raise ValueError(f"{who}: resume_steps = {k_res} must not be negative, and resuming needs probs and best_seq")
+        own()
+        obj = plan_objective(reward_weights, gamma, info_weights)
+        if sized and probs is not None:
+            A.device_tensor(probs, who, "probs", t.float64, (H, lead, 3, 3), device=self.device)
+        if sized and best_seq is not None:
+            A.device_tensor(best_seq, who, "best_seq", t.int32, (H, lead, 3), device=self.device)
+        pl = bool(plan_stats)
+        res = self._stats_into(who, into, None, pl, lead if grouped and sized else None)
+        mpc.horizon, mpc.warm_start, mpc.resume, mpc.resume_steps = H, 1 if warm_start else 0, 1 if k_res > 0 else 0, k_res
+        mpc.idle_action[:] = idle
+        self._cem_shared(mpc.cem, n_iters, 0, n_elite, fixed, seed, draw, alpha, p_min)
+        arrays = [None] * (2 + len(outputs))
+        if sized:
+            self._behind_torch_stream()      # (a caller's probs / best_seq may have been filled by torch ops)
+            new = lambda shape, dtype: t.empty(shape, dtype=dtype, device=self.device)
+            arrays = [new((H, lead, 3, 3), t.float64) if probs is None else probs, new((H, lead, 3), t.int32) if best_seq is None else best_seq]
+            arrays += [new(shape, dtype) for shape, dtype in outputs]
+        n_plan = 3 if grouped else 2
+        plan_arrays = [res.plan.counts, res.plan.sums, res.plan.diverged][:n_plan] if pl else [None] * n_plan
+        self._call(fn, int(n_steps), C.byref(mpc), C.byref(obj), 0 if into is None else 1, _p(res.stats), _p(res.returns), _p(res.counts),
+                   *[_p(x) for x in plan_arrays + arrays], *self._obs_ptrs, _p(self.rew), _p(self.done), _p(self.info), _p(self.final_obs),
+                   self._stream(), refuses=True, wrote=[res.stats, res.returns, res.counts] + plan_arrays + arrays)
+        if not sized:
+            raise L.SdcError(f"{who}: {fn.__name__} accepted {sizes} and no arrays")
+        plan = mpc_schedule(left(), int(n_steps), H, self.config["auto_reset"], bool(warm_start), k_res)
+        res.mpc = MPCCarry(arrays[0], arrays[1], plan[-1][0], sum(1 for d in plan if d[1]), arrays[3], arrays[2],
+                           arrays[4] if grouped else None)
+        return res
+
     def rollout_cem_stats(self, n_steps: int, horizon: int, n_iters: int, n_candidates: int, n_elite: int, *, probs=None, best_seq=None,
                           resume_steps: int = 0, warm_start: bool = True, seed: int = 0, draw: int = 0, alpha: float = 0.0,
                           p_min: float = 0.0, fixed_action=(-1, -1, -1), idle_action=(1, 1, 2), reward_weights=(1.0, 1.0, 1.0),
@@ -1353,47 +1412,18 @@ class SdcEngine:
         (the latter's horizon rules replaced by the schedule), horizon outside [1, MARK_MAX_STEPS], resume_steps outside [0, horizon]
         or without the arrays, an idle_action outside 0..2."""
         t = self.torch
-        who = "rollout_cem_stats"
         H, N, M, n_it = int(horizon), self.n_envs, int(n_candidates), int(n_iters)
-        fixed = self._cem_fixed(who, fixed_action, seed, draw)
-        idle = [int(x) for x in idle_action]
-        if len(idle) != 3:
-            raise ValueError(f"{who}: idle_action must be three integers (ls, dc, bat), got {len(idle)}")
-        k_res = int(resume_steps)
-        if k_res < 0 or (k_res > 0 and (probs is None or best_seq is None)):
-            raise ValueError(f"{who}: resume_steps = {k_res} must not be negative, and resuming needs probs and best_seq")
-        obj = plan_objective(reward_weights, gamma, info_weights)
-        sized = 1 <= H <= L.MARK_MAX_STEPS and 2 <= M <= L.CEM_MAX_CAND and 1 <= n_it <= L.CEM_MAX_ITERS
-        if sized and probs is not None:
-            A.device_tensor(probs, who, "probs", t.float64, (H, N, 3, 3), device=self.device)
-        if sized and best_seq is not None:
-            A.device_tensor(best_seq, who, "best_seq", t.int32, (H, N, 3), device=self.device)
-        pl = bool(plan_stats)
-        res = self._stats_into(who, into, None, pl)
         mpc = L.SdcMpcParams()
-        mpc.horizon, mpc.warm_start, mpc.resume, mpc.resume_steps = H, 1 if warm_start else 0, 1 if k_res > 0 else 0, k_res
-        mpc.idle_action[:] = idle
-        cem = mpc.cem
-        cem.n_iters, cem.iter0, cem.n_cand, cem.n_elite = n_it, 0, M, int(n_elite)
-        cem.fixed_action[:] = fixed
-        cem.draw, cem.seed, cem.alpha, cem.p_min = int(draw), int(seed), float(alpha), float(p_min)
-        arrays = [None] * 6
-        if sized:
-            self._behind_torch_stream()      # (a caller's probs / best_seq may have been filled by torch ops)
-            new = lambda shape, dtype: t.empty(shape, dtype=dtype, device=self.device)
-            arrays = [new((H, N, 3, 3), t.float64) if probs is None else probs, new((H, N, 3), t.int32) if best_seq is None else best_seq,
-                      new((n_it, N), t.float64), new((N, 3), t.int32), new((M, H, N, 3), t.int32), new((M, N), t.float64)]
-        pc, ps = (res.plan.counts, res.plan.sums) if pl else (None, None)
+
+        def own():
+            mpc.cem.n_cand = M
+
+        sized = 1 <= H <= L.MARK_MAX_STEPS and 2 <= M <= L.CEM_MAX_CAND and 1 <= n_it <= L.CEM_MAX_ITERS
+        outputs = [((n_it, N), t.float64), ((N, 3), t.int32), ((M, H, N, 3), t.int32), ((M, N), t.float64)]
         left = self.steps_to_episode_end()
-        self._call(self.lib.sdc_rollout_cem_stats, int(n_steps), C.byref(mpc), C.byref(obj), 0 if into is None else 1, _p(res.stats),
-                   _p(res.returns), _p(res.counts), _p(pc), _p(ps), *[_p(x) for x in arrays], *self._obs_ptrs, _p(self.rew),
-                   _p(self.done), _p(self.info), _p(self.final_obs), self._stream(), refuses=True,
-                   wrote=[res.stats, res.returns, res.counts, pc, ps] + arrays)
-        if not sized:
-            raise L.SdcError(f"{who}: sdc_rollout_cem_stats accepted H = {H}, M = {M}, I = {n_it} and no arrays")
-        plan = mpc_schedule(left, int(n_steps), H, self.config["auto_reset"], bool(warm_start), k_res)
-        res.mpc = MPCCarry(arrays[0], arrays[1], plan[-1][0], sum(1 for d in plan if d[1]), arrays[3], arrays[2])
-        return res
+        return self._mpc_stats("rollout_cem_stats", self.lib.sdc_rollout_cem_stats, mpc, own, sized, f"H = {H}, M = {M}, I = {n_it}", False,
+                               n_steps, H, N, outputs, lambda: left, n_it, n_elite, probs, best_seq, resume_steps, warm_start, seed, draw,
+                               alpha, p_min, fixed_action, idle_action, reward_weights, gamma, info_weights, into, plan_stats)
 
     def rollout_cem_groups_stats(self, n_steps: int, group_size: int, horizon: int, n_iters: int, n_elite: int, *, sync: bool = False,
                                  probs=None, best_seq=None, resume_steps: int = 0, warm_start: bool = True, seed: int = 0, draw: int = 0,
@@ -1418,56 +1448,23 @@ class SdcEngine:
         t = self.torch
         who = "rollout_cem_groups_stats"
         H, N, R, n_it = int(horizon), self.n_envs, int(group_size), int(n_iters)
-        fixed = self._cem_fixed(who, fixed_action, seed, draw)
-        idle = [int(x) for x in idle_action]
-        if len(idle) != 3:
-            raise ValueError(f"{who}: idle_action must be three integers (ls, dc, bat), got {len(idle)}")
-        k_res = int(resume_steps)
-        if k_res < 0 or (k_res > 0 and (probs is None or best_seq is None)):
-            raise ValueError(f"{who}: resume_steps = {k_res} must not be negative, and resuming needs probs and best_seq")
         grouped = 2 <= R <= L.CEM_MAX_GROUP and N % R == 0
-        if group_base is None:
-            base = int(self.config["env_index_base"])
-            if grouped and base % R:
-                raise ValueError(f"{who}: group_size = {R} does not divide env_index_base = {base} (pass group_base)")
-            group_base = base // R if grouped else 0
-        if not -(1 << 31) <= int(group_base) < 1 << 31:
-            raise ValueError(f"{who}: group_base must fit 32 bits")
         G = N // R if grouped else 0
-        obj = plan_objective(reward_weights, gamma, info_weights)
-        sized = grouped and 1 <= H <= L.MARK_MAX_STEPS and 1 <= n_it <= L.CEM_MAX_ITERS
-        if sized and probs is not None:
-            A.device_tensor(probs, who, "probs", t.float64, (H, G, 3, 3), device=self.device)
-        if sized and best_seq is not None:
-            A.device_tensor(best_seq, who, "best_seq", t.int32, (H, G, 3), device=self.device)
-        pl = bool(plan_stats)
-        res = self._stats_into(who, into, None, pl, G if sized else None)
         mpc = L.SdcMpcGroupParams()
-        mpc.horizon, mpc.warm_start, mpc.resume, mpc.resume_steps = H, 1 if warm_start else 0, 1 if k_res > 0 else 0, k_res
-        mpc.idle_action[:] = idle
-        mpc.sync_first = 1 if sync else 0
-        cem = mpc.cem
-        cem.group_size, cem.group_base, cem.n_iters, cem.iter0, cem.n_elite = R, int(group_base), n_it, 0, int(n_elite)
-        cem.fixed_action[:] = fixed
-        cem.draw, cem.seed, cem.alpha, cem.p_min = int(draw), int(seed), float(alpha), float(p_min)
-        arrays = [None] * 7
-        if sized:
-            self._behind_torch_stream()      # (a caller's probs / best_seq may have been filled by torch ops)
-            new = lambda shape, dtype: t.empty(shape, dtype=dtype, device=self.device)
-            arrays = [new((H, G, 3, 3), t.float64) if probs is None else probs, new((H, G, 3), t.int32) if best_seq is None else best_seq,
-                      new((n_it, G), t.float64), new((G, 3), t.int32), new((N, 3), t.int32), new((H, N, 3), t.int32), new((N,), t.float64)]
-        pc, ps, pd = (res.plan.counts, res.plan.sums, res.plan.diverged) if pl else (None, None, None)
-        self._call(self.lib.sdc_rollout_cem_groups_stats, int(n_steps), C.byref(mpc), C.byref(obj), 0 if into is None else 1, _p(res.stats),
-                   _p(res.returns), _p(res.counts), _p(pc), _p(ps), _p(pd), *[_p(x) for x in arrays], *self._obs_ptrs, _p(self.rew),
-                   _p(self.done), _p(self.info), _p(self.final_obs), self._stream(), refuses=True,
-                   wrote=[res.stats, res.returns, res.counts, pc, ps, pd] + arrays)
-        if not sized:
-            raise L.SdcError(f"{who}: sdc_rollout_cem_groups_stats accepted R = {R}, H = {H}, I = {n_it} and no arrays")
-        # the steps the episode had left behind the sync, from where the call has left the batch (no env finished: it moved n_steps)
-        left = int(n_steps) if self.last_done() is not None else self.steps_to_episode_end() + int(n_steps)
-        plan = mpc_schedule(left, int(n_steps), H, self.config["auto_reset"], bool(warm_start), k_res)
-        res.mpc = MPCCarry(arrays[0], arrays[1], plan[-1][0], sum(1 for d in plan if d[1]), arrays[3], arrays[2], arrays[4])
-        return res
+
+        def own():
+            mpc.sync_first = 1 if sync else 0
+            mpc.cem.group_size, mpc.cem.group_base = R, self._group_base(who, R, grouped, group_base)
+
+        def left():
+            # behind the sync, from where the call has left the batch (no env finished: it moved n_steps)
+            return int(n_steps) if self.last_done() is not None else self.steps_to_episode_end() + int(n_steps)
+
+        sized = grouped and 1 <= H <= L.MARK_MAX_STEPS and 1 <= n_it <= L.CEM_MAX_ITERS
+        outputs = [((n_it, G), t.float64), ((G, 3), t.int32), ((N, 3), t.int32), ((H, N, 3), t.int32), ((N,), t.float64)]
+        return self._mpc_stats(who, self.lib.sdc_rollout_cem_groups_stats, mpc, own, sized, f"R = {R}, H = {H}, I = {n_it}", True, n_steps, H,
+                               G, outputs, left, n_it, n_elite, probs, best_seq, resume_steps, warm_start, seed, draw, alpha, p_min,
+                               fixed_action, idle_action, reward_weights, gamma, info_weights, into, plan_stats)
 
     def evaluate(self, n_episodes: int, actions=None, *, actors: bool = False, sample: bool = False, mpc=None) -> EpisodeStats:
         """`n_episodes` whole episodes of the batch, one `rollout_stats` of episode_steps steps each -> an EpisodeStats whose tensors

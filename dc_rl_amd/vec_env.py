@@ -695,6 +695,20 @@ class SustainDCVecEnv(ShareVecEnv):
         self._gen += 1      # (the engine's info buffer now holds another step: `infos` objects that view it say so)
         return res
 
+    def _planned_stats(self, who, synced, *args, **kw):
+        """the engine's closed-loop planner call `who`, refused under an agent subset; `synced`: the group size it syncs with first, or None"""
+        if self.n_agents != 3:
+            raise ValueError(f"{who}: this env trains {self.agents}; the library steps with the planner's best_action for all "
+                             "three agents, which is not what step() plays in the other slots' columns")
+        self._ready(who)
+        res = getattr(self.engine, who)(*args, **kw)
+        if synced is not None:
+            self._groups_synced(synced)
+        return self._stats_done(res)
+
+    def _groups_synced(self, group_size):      # (inside a library call: the host's per-env entries follow as after sync_groups)
+        self._host_entries_follow(*group_sync_pairs(group_size, self.num_envs, "num_envs"), self._const, self._cfg_id, self.months)
+
     def rollout_actor_stats(self, n_steps, sample=False, into=None, policy_stats=True):
         """K env-steps played by the three actors (set_actor) inside the kernel, reduced on the device to an EpisodeStats with a
         PolicyStats (SdcEngine.rollout_actor_stats, which documents the arguments and the result).  The envs move as under K calls of
@@ -710,11 +724,7 @@ class SustainDCVecEnv(ShareVecEnv):
         stepped are dropped; the logger accumulator (accumulate_logger_sums) is left alone, as by rollout_stats.  ValueError when
         this env trains an agent subset -- plan_cem + step() would play 1 in the other slots' columns, the library steps with the
         planner's best_action of all three: the two would differ --, and for what the engine refuses."""
-        if self.n_agents != 3:
-            raise ValueError(f"rollout_cem_stats: this env trains {self.agents}; the library steps with the planner's best_action for all "
-                             "three agents, which is not what step() plays in the other slots' columns")
-        self._ready("rollout_cem_stats")
-        return self._stats_done(self.engine.rollout_cem_stats(n_steps, horizon, n_iters, n_candidates, n_elite, **kw))
+        return self._planned_stats("rollout_cem_stats", None, n_steps, horizon, n_iters, n_candidates, n_elite, **kw)
 
     def rollout_cem_groups_stats(self, n_steps, group_size, horizon, n_iters, n_elite, *, sync=False, **kw):
         """n_steps env-steps planned by the cross-entropy method over replica groups inside the library, reduced on the device to an
@@ -723,14 +733,8 @@ class SustainDCVecEnv(ShareVecEnv):
         step(); with `sync` the call begins as sync_groups(group_size) does, and the host's per-env entries follow as after it.  Actions
         handed to step_async and not yet stepped are dropped; the logger accumulator (accumulate_logger_sums) is left alone, as by
         rollout_stats.  ValueError when this env trains an agent subset, as for rollout_cem_stats, and for what the engine refuses."""
-        if self.n_agents != 3:
-            raise ValueError(f"rollout_cem_groups_stats: this env trains {self.agents}; the library steps with the planner's best_action "
-                             "for all three agents, which is not what step() plays in the other slots' columns")
-        self._ready("rollout_cem_groups_stats")
-        res = self.engine.rollout_cem_groups_stats(n_steps, group_size, horizon, n_iters, n_elite, sync=sync, **kw)
-        if sync:
-            self._host_entries_follow(*group_sync_pairs(group_size, self.num_envs, "num_envs"), self._const, self._cfg_id, self.months)
-        return self._stats_done(res)
+        return self._planned_stats("rollout_cem_groups_stats", group_size if sync else None, n_steps, group_size, horizon, n_iters, n_elite,
+                                   sync=sync, **kw)
 
     def evaluate(self, n_episodes, actions=None, *, actors=False, sample=False, mpc=None):
         """`n_episodes` whole episodes of the batch from a reset (SdcEngine.evaluate) -> an EpisodeStats with a leading [E] dimension.
@@ -752,8 +756,7 @@ class SustainDCVecEnv(ShareVecEnv):
             synced = getattr(mpc, "syncs", 0)
             res = self.engine.evaluate(n_episodes, mpc=mpc)
             if getattr(mpc, "syncs", 0) != synced:      # a GroupCEMMPCAgent's calls synced the groups: the host's entries follow once
-                self._host_entries_follow(*group_sync_pairs(mpc.group_size, self.num_envs, "num_envs"), self._const, self._cfg_id,
-                                          self.months)
+                self._groups_synced(mpc.group_size)
         elif actors:
             if actions is not None:
                 raise ValueError("evaluate: actors=True plays the actors' own actions: give no actions")

@@ -82,15 +82,16 @@ def assert_no_scratch_or_spills(per, kernels):
 
 
 class AgentStub:
-    """What the CEM agents' `act` asks of an engine, on the CPU: sync_groups, plan_cem and plan_cem_groups record their arguments; the
-    plans answer with tensors that tell the step and the decision apart (best_seq[k] = 100 d + 10 k + agent, probs[k] = d + k / 16 +
-    (agent, action) / 256, step_actions = best_seq[0] of the env's group)."""
+    """What the CEM agents' `act` and `rollout_stats` ask of an engine, on the CPU: sync_groups, plan_cem and plan_cem_groups record
+    their arguments; the plans answer with tensors that tell the step and the decision apart (best_seq[k] = 100 d + 10 k + agent,
+    probs[k] = d + k / 16 + (agent, action) / 256, step_actions = best_seq[0] of the env's group); rollout_cem_stats and
+    rollout_cem_groups_stats: below."""
 
     def __init__(self, n_envs=2, episode_steps=12):
         import torch
         self.n_envs, self.device = n_envs, torch.device("cpu")
         self.config = dict(auto_reset=True, episode_steps=episode_steps)
-        self.t, self.calls, self.syncs = 0, [], []
+        self.t, self.calls, self.syncs, self.loops = 0, [], [], []
 
     def steps_to_episode_end(self):
         return self.config["episode_steps"] - self.t
@@ -120,6 +121,27 @@ class AgentStub:
         from dc_rl_amd.engine import GroupCEMResult
         seq, score, p = self._answer(K, self.n_envs // R, n_iters, probs, best_seq, R=R, draw=draw, E=E, **kw)
         return GroupCEMResult(seq[0].clone(), seq[0].repeat_interleave(R, dim=0), seq, score, p, None, None)
+
+    # The closed-loop calls of the agents' `rollout_stats`: recorded in `loops` with every keyword they were given (probs and best_seq as
+    # copies); `refuse`: raise as the engine refuses, nothing moved; else the batch moves n_steps, the caller's probs / best_seq are
+    # filled with the call's number and go back in an MPCCarry of `carry` = (steps, planned)
+    refuse, carry = False, (0, 0)
+
+    def _loop(self, n_steps, H, probs, best_seq, **rec):
+        from dc_rl_amd.engine import MPCCarry
+        self.loops.append(dict(n_steps=n_steps, H=H, probs=probs.clone(), best_seq=best_seq.clone(), **rec))
+        if self.refuse:
+            raise ValueError("refused")
+        self.t = (self.t + n_steps) % self.config["episode_steps"]
+        res = type("Res", (), {})()
+        res.mpc = MPCCarry(probs.fill_(len(self.loops)), best_seq.fill_(len(self.loops)), *self.carry, None, None)
+        return res
+
+    def rollout_cem_stats(self, n_steps, H, n_iters, M, E, *, probs, best_seq, **kw):
+        return self._loop(n_steps, H, probs, best_seq, n_iters=n_iters, M=M, E=E, **kw)
+
+    def rollout_cem_groups_stats(self, n_steps, R, H, n_iters, E, *, probs, best_seq, **kw):
+        return self._loop(n_steps, H, probs, best_seq, n_iters=n_iters, R=R, E=E, **kw)
 
 
 # ---- GPU side ---------------------------------------------------------------------------------------------------------------------

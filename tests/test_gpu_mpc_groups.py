@@ -477,6 +477,18 @@ def test_refusals_leave_the_engine_the_launch_counter_and_the_arrays_untouched()
     a.set_plan_forecast(carbon="values", values=torch.zeros((H + 1, N, 4), dtype=torch.float64, device=a.device))
     raw("entries")
     a.set_plan_forecast()
+    # the order of the refusals: of two faults at once the earlier one is named
+    raw("n_steps = 0 must be positive", n_steps=0, null_mpc=True)
+    raw("horizon = 0 outside", mpc=dict(horizon=0), cem=dict(n_iters=0))
+    raw("n_iters = 0", cem=dict(n_iters=0), null=("probs",))
+    raw("null array", null=("probs",), offset={"plan_sums": 8})
+    raw("plan_sums not 16-byte aligned", offset={"plan_sums": 8}, objective=C.byref(_objective(gamma=0.0)))
+    raw("gamma", objective=C.byref(_objective(gamma=0.0)), n_steps=39)
+    raw("sync_first = 2 outside", mpc=dict(sync_first=2), cem=dict(n_iters=0))
+    raw("not a multiple", cem=dict(group_size=3, alpha=1.0))
+    split.set_plan_forecast(carbon="values", values=torch.zeros((H + 1, N, 4), dtype=torch.float64, device=split.device))
+    raw("out of step", eng=split)
+    split.set_plan_forecast()
     # through the binding: ValueError before the library is asked, or from it
     call = lambda **kw: (lambda: _call(a, kw.pop("n", 2), kw.pop("R", R), **kw))
     G = N // R
