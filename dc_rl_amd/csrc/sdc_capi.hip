@@ -4,6 +4,12 @@
 // sdc_dynamics_kernel (one launch = one env-step of all N envs, rewards included), sdc_reset_kernel at episode
 // boundaries, sdc_reward_verify_kernel only in verify mode.  No CPU fallback: every entry point fails with an
 // error code when HIP reports one.
+//
+// WHAT A CALL REFUSES before it touches the device is not decided here: sdc_refusals.hpp holds one pure rule per entry point, call_facts
+// below tells it what it may know of the handle, and refused() turns its message into -2 with sdc_last_error set.  The fail_msg calls
+// left in this file need a HIP call's result (a device that is not there, an allocation or copy that failed) or come up while a kernel
+// plan is built from a HIP header (a segment table that is full, a layout a plan does not know); the null checks of the small setters
+// and getters and the parameter checks of sdc_setup.hpp / sdc_critic_pack.hpp are reported where they always were.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +42,7 @@
 #include "sdc_mpc.hpp"
 #include "sdc_mpc_groups.hpp"
 #include "sdc_mpc_schedule.hpp"
+#include "sdc_refusals.hpp"
 
 namespace {
 
@@ -49,6 +56,10 @@ int fail_msg(const std::string& m) {
   g_err = m;
   return -2;
 }
+
+// a rule's answer (sdc_refusals.hpp) -> 0 if it accepts, else -2 with the message set
+int refused(const char* m) { return m ? fail_msg(m) : 0; }
+int refused(const SdcMsg& m) { return m ? fail_msg(*m) : 0; }
 
 #define HIP_TRY(expr)                          \
   do {                                         \
@@ -401,31 +412,6 @@ void stage_destroy(IdxStage& S) {
   if (S.pin) (void)hipHostFree(S.pin);
 }
 
-// The inverse map of n entries (envs[k], vals ? vals[k] : k) -- map[env] = its value, -1 for the other envs -- or why the entries have
-// none ("" if they have), without the caller's prefix: an env outside [0, N); a value outside [0, n_vals) (n_vals > 0, `val_noun`:
-// checked entry by entry with the env); an env that appears twice (`twice`: the caller's noun for it).  map == nullptr: the ranges only
-std::string unique_index_map(const int32_t* envs, const int32_t* vals, const int n, const int N, const int n_vals, const char* val_noun,
-                             const char* twice, std::vector<int>* map) {
-  const auto outside = [](const char* noun, const int v, const int k, const int bound) {
-    return std::string(noun) + " " + std::to_string(v) + " (entry " + std::to_string(k) + ") outside [0, " + std::to_string(bound) + ")";
-  };
-  for (int k = 0; k < n; k++) {
-    if (envs[k] < 0 || envs[k] >= N) return outside("env", envs[k], k, N);
-    if (n_vals > 0 && (vals[k] < 0 || vals[k] >= n_vals)) return outside(val_noun, vals[k], k, n_vals);
-  }
-  if (!map) return "";
-  map->assign((size_t)N, -1);
-  for (int k = 0; k < n; k++) {
-    if ((*map)[(size_t)envs[k]] >= 0) return std::string(twice) + " " + std::to_string(envs[k]) + " appears twice";
-    (*map)[(size_t)envs[k]] = vals ? vals[k] : k;
-  }
-  return "";
-}
-// the caller's row buffer (snapshot rows, mark rows): nullptr if it may be used, else why not
-const char* rows_error(const void* rows) {
-  return (reinterpret_cast<uintptr_t>(rows) & 255u) != 0 ? "rows must be 256-byte aligned" : nullptr;
-}
-
 // One env-major array joins the segment table of a copy plan (SdcClonePlan, SdcSnapPlan: the same fields) as a wide segment (16-byte
 // units) or a narrow one (dwords).  Which, is the caller's rule:
 //   SEG_DEMOTE (the clone): wide if pitch AND base are 16-byte aligned, else narrow -- any array can be copied;
@@ -475,6 +461,51 @@ static constexpr uint32_t state_layout_hash() {
   return x;
 }
 uint32_t sdc_state_layout(void) { return state_layout_hash(); }
+
+// WHAT A REFUSAL MAY KNOW OF THE HANDLE (sdc_refusals.hpp): host fields and the mirror's summaries, nothing per env.  stepping_facts:
+// the few scalars sdc_step, sdc_rollout and sdc_rollout_actor read, and nothing else -- a step pays for no more; call_facts: all of it
+// (the closed-loop rule's step facts are the caller's to add)
+static void fill_stepping_facts(const sdc_handle* h, SdcSteppingFacts& f) {
+  f.handle = true;
+  f.started = h->started;
+  f.left = h->mirror.steps_to_terminal();
+  f.debug_flags = h->cfg.debug_flags;
+  f.all_policies = sdc_all_policies(h->d.policy);
+  for (int a = 0; a < 3; a++) {
+    f.actor_set[a] = h->actor_set[a];
+    f.actor_activation[a] = h->actor_activation[a];
+  }
+  f.latch_valid = h->latch_valid;
+  f.critic_set = h->critic_set;
+}
+static SdcSteppingFacts stepping_facts(const sdc_handle* h) {
+  SdcSteppingFacts f;
+  if (h) fill_stepping_facts(h, f);
+  return f;
+}
+static SdcCallFacts call_facts(const sdc_handle* h) {
+  SdcCallFacts f;
+  if (!h) return f;
+  fill_stepping_facts(h, f);
+  f.n_envs = h->cfg.n_envs;
+  f.episode_steps = h->cfg.episode_steps;
+  f.hist_cap = h->cfg.hist_cap;
+  f.n_locations = h->cfg.n_locations;
+  f.n_dc_configs = h->cfg.n_dc_configs;
+  f.auto_reset = h->cfg.auto_reset;
+  f.tables_set = h->tables_set;
+  f.assigned = h->assigned;
+  f.has_feat = h->d.feat != nullptr;
+  f.state_layout = state_layout_hash();
+  f.qstride = h->d.qstride;
+  f.lw = h->d.lw;
+  f.rec_dwords = SDC_REC_DWORDS;
+  f.rec_cfg = R_CFG;
+  f.mark_engine_id = h->mark_engine_id;
+  f.forecast = h->plan_forecast;
+  f.mirror = &h->mirror;
+  return f;
+}
 
 int sdc_create(const sdc_config* cfg, sdc_handle** out) {
   if (!cfg || !out) return fail_msg("sdc_create: null argument");
@@ -662,9 +693,7 @@ int sdc_queue_stride(const sdc_handle* h) { return h ? h->d.qstride : -1; }
 
 int sdc_set_tables(sdc_handle* h, int loc_id, const double* W, const double* C, const double* T, const double* WB,
                    int n) {
-  if (!h || !W || !C || !T || !WB) return fail_msg("sdc_set_tables: null argument");
-  if (loc_id < 0 || loc_id >= h->cfg.n_locations) return fail_msg("sdc_set_tables: loc_id out of range");
-  if (n != SDC_TABLE_LEN) return fail_msg("sdc_set_tables: tables must hold 35040 samples");
+  if (refused(sdc_set_tables_refused(call_facts(h), loc_id, W, C, T, WB, n))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   const size_t off = (size_t)loc_id * SDC_TABLE_LEN, bytes = sizeof(double) * SDC_TABLE_LEN;
   HIP_TRY(hipMemcpy(const_cast<double*>(h->d.tabW) + off, W, bytes, hipMemcpyHostToDevice));
@@ -677,8 +706,7 @@ int sdc_set_tables(sdc_handle* h, int loc_id, const double* W, const double* C, 
 }
 
 int sdc_set_dc_params(sdc_handle* h, int cfg_id, const sdc_dc_params* p) {
-  if (!h || !p) return fail_msg("sdc_set_dc_params: null argument");
-  if (cfg_id < 0 || cfg_id >= h->cfg.n_dc_configs) return fail_msg("sdc_set_dc_params: cfg_id out of range");
+  if (refused(sdc_set_dc_params_refused(call_facts(h), cfg_id, p))) return -2;
   SdcDcDev e;
   if (const char* refused = sdc_derive_dc(*p, e)) return fail_msg(refused);      // (sdc_setup.hpp: reciprocals, rack classes)
   HIP_TRY(hipSetDevice(h->device));
@@ -691,13 +719,8 @@ int sdc_set_dc_params(sdc_handle* h, int cfg_id, const sdc_dc_params* p) {
 
 int sdc_assign_envs(sdc_handle* h, const int32_t* loc_id, const int32_t* cfg_id, const int32_t* day_lo,
                     const int32_t* day_hi) {
-  if (!h || !loc_id || !cfg_id || !day_lo || !day_hi) return fail_msg("sdc_assign_envs: null argument");
+  if (refused(sdc_assign_envs_refused(call_facts(h), loc_id, cfg_id, day_lo, day_hi))) return -2;
   const int N = h->cfg.n_envs;
-  for (int e = 0; e < N; e++) {
-    if (loc_id[e] < 0 || loc_id[e] >= h->cfg.n_locations) return fail_msg("sdc_assign_envs: loc_id out of range");
-    if (cfg_id[e] < 0 || cfg_id[e] >= h->cfg.n_dc_configs) return fail_msg("sdc_assign_envs: cfg_id out of range");
-    if (day_lo[e] < 0 || day_hi[e] > 364 || day_lo[e] > day_hi[e]) return fail_msg("sdc_assign_envs: bad day range");
-  }
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());
   if (rec_put(h, R_LOC, 1, loc_id) || rec_put(h, R_CFG, 1, cfg_id) || rec_put(h, R_DAY_LO, 1, day_lo) ||
@@ -717,8 +740,7 @@ int sdc_assign_envs(sdc_handle* h, const int32_t* loc_id, const int32_t* cfg_id,
 
 int sdc_reset(sdc_handle* h, const uint8_t* mask_host, const sdc_reset_override* ovr, float* obs, float* share_obs,
               void* stream) {
-  if (!h) return fail_msg("sdc_reset: null handle");
-  if (!h->tables_set || !h->assigned) return fail_msg("sdc_reset: call sdc_set_tables / sdc_set_dc_params / sdc_assign_envs first");
+  if (refused(sdc_reset_refused(call_facts(h), mask_host, ovr))) return -2;      // (the overrides' ranges included)
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N = h->cfg.n_envs;
@@ -733,13 +755,6 @@ int sdc_reset(sdc_handle* h, const uint8_t* mask_host, const sdc_reset_override*
   const bool inject_noise = ovr && ovr->noise;
   if (inject_noise) {
     // the reference's own draws, the arithmetic on the device: day / hour / roll + the year's noise array per env
-    if (!ovr->day || !ovr->hour || !ovr->roll_days) return fail_msg("sdc_reset: noise injection needs day, hour and roll_days");
-    for (int e = 0; e < N; e++) {
-      if (mask_host && !mask_host[e]) continue;
-      if (ovr->day[e] < 0 || ovr->day[e] > 364 || ovr->hour[e] < 0 || ovr->hour[e] > 23 || ovr->roll_days[e] < 0 ||
-          ovr->roll_days[e] > 364)
-        return fail_msg("sdc_reset: injected day / hour / roll_days out of range");
-    }
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&inj_noise), sizeof(double) * (size_t)N * SDC_TABLE_LEN));
     if (hipMalloc(reinterpret_cast<void**>(&inj_roll), sizeof(int) * (size_t)N) != hipSuccess) {
       (void)hipFree(inj_noise);
@@ -755,14 +770,6 @@ int sdc_reset(sdc_handle* h, const uint8_t* mask_host, const sdc_reset_override*
       return fail_msg("sdc_reset: upload of the injected noise failed");
     }
   } else if (ovr) {
-    if (!ovr->day || !ovr->hour || !ovr->ci_min || !ovr->ci_max || !ovr->t_min || !ovr->t_max || !ovr->t_win ||
-        !ovr->wb_win)
-      return fail_msg("sdc_reset: incomplete override");
-    for (int e = 0; e < N; e++) {
-      if (mask_host && !mask_host[e]) continue;
-      if (ovr->day[e] < 0 || ovr->day[e] > 364 || ovr->hour[e] < 0 || ovr->hour[e] > 23)
-        return fail_msg("sdc_reset: override day/hour out of range");
-    }
     HIP_TRY(hipMemcpyAsync(h->ovr_day, ovr->day, sizeof(int) * (size_t)N, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->ovr_hour, ovr->hour, sizeof(int) * (size_t)N, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(h->ovr_ci_min, ovr->ci_min, sizeof(double) * (size_t)N, hipMemcpyHostToDevice, st));
@@ -819,11 +826,7 @@ int sdc_reset(sdc_handle* h, const uint8_t* mask_host, const sdc_reset_override*
 
 int sdc_step(sdc_handle* h, const int32_t* actions, float* obs, float* share_obs, float* rew, uint8_t* done,
              float* info, float* final_obs, void* stream) {
-  if (!h || !obs || !rew || !done) return fail_msg("sdc_step: null argument");
-  if (!actions && !sdc_all_policies(h->d.policy)) return fail_msg("sdc_step: actions may only be NULL when every agent slot has a policy");
-  if (!h->started) return fail_msg("sdc_step: sdc_reset must be called first");
-  if (h->mirror.steps_to_terminal() <= 0)
-    return fail_msg("sdc_step: an environment has finished its episode; call sdc_reset (auto_reset is off)");
+  if (refused(sdc_step_refused(stepping_facts(h), actions, obs, rew, done))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N = h->cfg.n_envs;
@@ -843,14 +846,7 @@ int sdc_step(sdc_handle* h, const int32_t* actions, float* obs, float* share_obs
 
 int sdc_rollout(sdc_handle* h, int n_steps, const int32_t* actions, float* obs, float* share_obs, float* rew,
                 uint8_t* done, float* info, float* final_obs, int32_t* actions_out, void* stream) {
-  if (!h || !obs || !rew || !done) return fail_msg("sdc_rollout: null argument");
-  if (!actions && !sdc_all_policies(h->d.policy)) return fail_msg("sdc_rollout: actions may only be NULL when every agent slot has a policy");
-  if (!h->started) return fail_msg("sdc_rollout: sdc_reset must be called first");
-  if (n_steps <= 0) return fail_msg("sdc_rollout: n_steps must be positive");
-  if (n_steps > h->mirror.steps_to_terminal())
-    return fail_msg("sdc_rollout: the rollout would run past the end of an episode (" +
-                    std::to_string(h->mirror.steps_to_terminal()) + " steps left); split it there");
-  if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) return fail_msg("sdc_rollout: verify mode checks single steps; use sdc_step");
+  if (refused(sdc_rollout_refused(stepping_facts(h), n_steps, actions, obs, rew, done))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N = h->cfg.n_envs;
@@ -885,9 +881,7 @@ int sdc_rollout(sdc_handle* h, int n_steps, const int32_t* actions, float* obs, 
 }
 
 int sdc_set_actor(sdc_handle* h, int slot, const sdc_actor_params* p) {
-  if (!h || !p) return fail_msg("sdc_set_actor: null argument");
-  if (slot < 0 || slot > 2) return fail_msg("sdc_set_actor: agent_slot must be 0 (ls), 1 (dc) or 2 (bat)");
-  if (p->activation < 0 || p->activation > 1) return fail_msg("sdc_set_actor: activation must be 0 (tanh) or 1 (relu)");
+  if (refused(sdc_set_actor_refused(call_facts(h), slot, p))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   if (!h->actor_dev) {
     if (dev_alloc(h, &h->actor_dev, 3) != 0) return -1;
@@ -922,22 +916,10 @@ int sdc_set_actor(sdc_handle* h, int slot, const sdc_actor_params* p) {
 
 int sdc_rollout_actor(sdc_handle* h, int n_steps, int sample, float* obs, float* share_obs, float* rew, uint8_t* done,
                       float* info, float* final_obs, int32_t* actions_out, float* logits_out, void* stream) {
-  if (!h || !obs || !share_obs || !rew || !done || !info || !actions_out) return fail_msg("sdc_rollout_actor: null argument");
-  if (!h->actor_set[0] || !h->actor_set[1] || !h->actor_set[2]) return fail_msg("sdc_rollout_actor: sdc_set_actor all three agents first");
-  if (h->actor_activation[0] != h->actor_activation[1] || h->actor_activation[0] != h->actor_activation[2])
-    return fail_msg("sdc_rollout_actor: the three actors must share one activation (the reference builds them from one "
-                    "model config: happo.yaml activation_func)");
-  if (!h->started) return fail_msg("sdc_rollout_actor: sdc_reset must be called first");
-  if (!h->latch_valid) return fail_msg("sdc_rollout_actor: no observations yet (the actors were set after the last reset / step: reset or step once)");
-  if (n_steps <= 0) return fail_msg("sdc_rollout_actor: n_steps must be positive");
-  if (n_steps > h->mirror.steps_to_terminal())
-    return fail_msg("sdc_rollout_actor: the rollout would run past the end of an episode (" + std::to_string(h->mirror.steps_to_terminal()) +
-                    " steps left); split it there");
   // the common case only, with the actions coming from the actors instead of the caller
-  const SdcActorPath ap = sdc_actor_path(step_facts(h, true, obs, share_obs, info, final_obs, actions_out, false));
-  if (ap.refused)
-    return fail_msg("sdc_rollout_actor: needs the common case (lock-step batch with feature rows, one data-centre config of <= 32 "
-                    "racks, external-action slots, default rewards, an even number of envs, no debug flags)");
+  const SdcStepFacts step = h ? step_facts(h, true, obs, share_obs, info, final_obs, actions_out, false) : SdcStepFacts{};
+  if (refused(sdc_rollout_actor_refused(stepping_facts(h), step, n_steps, obs, share_obs, rew, done, info, actions_out))) return -2;
+  const SdcActorPath ap = sdc_actor_path(step);
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N = h->cfg.n_envs;
@@ -977,7 +959,7 @@ int sdc_last_done(const sdc_handle* h, uint8_t* done_host) {
 }
 
 int sdc_profile_enable(sdc_handle* h, int enable) {
-  if (!h) return fail_msg("sdc_profile_enable: null handle");
+  if (refused(sdc_profile_enable_refused(stepping_facts(h)))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   if (enable > 0 && !h->prof_buf) {
     if (dev_alloc(h, &h->prof_buf, (size_t)PROF_SLOTS * 3 * h->cfg.n_envs * 2) != 0) return -1;
@@ -993,7 +975,7 @@ int sdc_profile_enable(sdc_handle* h, int enable) {
 }
 
 int sdc_profile_read(sdc_handle* h, double* out5, int reset) {
-  if (!h || !out5) return fail_msg("sdc_profile_read: null argument");
+  if (refused(sdc_profile_read_refused(stepping_facts(h), out5))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());
   const size_t N = (size_t)h->cfg.n_envs;
@@ -1025,21 +1007,22 @@ int sdc_profile_read(sdc_handle* h, double* out5, int reset) {
 }
 
 static const Field* find_field(sdc_handle* h, const char* name) {
+  if (!h || !name) return nullptr;
   for (const Field& f : h->fields)
     if (std::strcmp(f.name, name) == 0) return &f;
   return nullptr;
 }
+// ... as the rules of sdc_get_state / sdc_set_state see it (sdc_refusals.hpp)
+static SdcFieldFacts field_facts(const Field* f) { return {f ? f->elem : 0, f && (!f->ptr || *f->ptr)}; }
 
 int sdc_get_state(sdc_handle* h, const char* field, void* host_buf, size_t bytes) {
-  if (!h || !field || !host_buf) return fail_msg("sdc_get_state: null argument");
   const Field* f = find_field(h, field);
-  if (!f) return fail_msg(std::string("sdc_get_state: unknown field ") + field);
+  const SdcFieldFacts ff = field_facts(f);
+  if (refused(sdc_get_state_refused(call_facts(h), field, host_buf, bytes, f ? &ff : nullptr))) return -2;
   const size_t need = f->elem * (size_t)h->cfg.n_envs;
-  if (bytes != need) return fail_msg(std::string("sdc_get_state: size mismatch for ") + field);
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());
   if (!f->ptr) return rec_get(h, f->rec_idx, f->rec_dwords, host_buf, f->in_hdr);
-  if (!*f->ptr) return fail_msg(std::string("sdc_get_state: this batch has no ") + field);
   HIP_TRY(hipMemcpy(host_buf, *f->ptr, need, hipMemcpyDeviceToHost));
   if (std::strcmp(field, "hist") == 0) {  // device keys -> fp32 offsets (empty slot -> NaN)
     unsigned* u = static_cast<unsigned*>(host_buf);
@@ -1061,24 +1044,11 @@ __global__ void sdc_hist_mirror_kernel(SdcDev S) {
 }
 
 int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t bytes) {
-  if (!h || !field || !host_buf) return fail_msg("sdc_set_state: null argument");
   const Field* f = find_field(h, field);
-  if (!f) return fail_msg(std::string("sdc_set_state: unknown field ") + field);
-  if (std::strcmp(field, "qcum_t") == 0 || std::strcmp(field, "hist_t") == 0)
-    return fail_msg(std::string("sdc_set_state: ") + field + " is derived from " + (field[0] == 'q' ? "qtab" : "hist") + ": write that");
+  const SdcFieldFacts ff = field_facts(f);
+  if (refused(sdc_set_state_refused(call_facts(h), field, host_buf, bytes, f ? &ff : nullptr))) return -2;
   const size_t need = f->elem * (size_t)h->cfg.n_envs;
-  if (bytes != need) return fail_msg(std::string("sdc_set_state: size mismatch for ") + field);
-  // what the kernels index with is validated BEFORE anything reaches the device: a config id out of range would index
-  // S.dc[] / the per-env config scalars out of bounds on the next step (with one config the kernels never read the id)
   const bool is_cfg = std::strcmp(field, "cfg_id") == 0, is_record = std::strcmp(field, "record") == 0;
-  if (is_cfg || is_record) {
-    const int* c = static_cast<const int*>(host_buf);
-    for (int e = 0; e < h->cfg.n_envs; e++) {
-      const int id = is_cfg ? c[e] : (int)static_cast<const unsigned*>(host_buf)[(size_t)e * SDC_REC_DWORDS + R_CFG];
-      if (id < 0 || id >= h->cfg.n_dc_configs)
-        return fail_msg(is_cfg ? "sdc_set_state: cfg_id out of range" : "sdc_set_state: record with a cfg_id out of range");
-    }
-  }
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());
   if (!f->ptr) {
@@ -1137,21 +1107,9 @@ int sdc_set_state(sdc_handle* h, const char* field, const void* host_buf, size_t
 // Env dst[k] becomes a copy of env src[k], on the device and ordered on `stream` like a step (sdc_clone.hip).  What is copied and
 // what is not, and why the deferred re-centring stamps are cleared rather than the launch counter moved: include/sustaindc_hip.h.
 int sdc_clone_envs(sdc_handle* h, const int32_t* src, const int32_t* dst, int n, float* obs, float* share_obs, void* stream) {
-  if (!h) return fail_msg("sdc_clone_envs: null handle");
-  if (n <= 0) return fail_msg("sdc_clone_envs: n must be positive");
-  if (!src || !dst) return fail_msg("sdc_clone_envs: null index array");
-  if (!h->started) return fail_msg("sdc_clone_envs: sdc_reset must be called first");
-  const int N = h->cfg.n_envs;
-  // every refusal before anything reaches the device
-  for (int k = 0; k < n; k++)
-    if (src[k] < 0 || src[k] >= N || dst[k] < 0 || dst[k] >= N)
-      return fail_msg("sdc_clone_envs: pair " + std::to_string(k) + " (" + std::to_string(src[k]) + " -> " + std::to_string(dst[k]) +
-                      ") has an env index outside [0, " + std::to_string(N) + ")");
   std::vector<int> src_of;      // dst -> its src
-  const std::string why = unique_index_map(dst, src, n, N, 0, nullptr, "dst", &src_of);
-  if (!why.empty()) return fail_msg("sdc_clone_envs: " + why);
-  for (int k = 0; k < n; k++)
-    if (src_of[(size_t)src[k]] >= 0) return fail_msg("sdc_clone_envs: env " + std::to_string(src[k]) + " is both a src and a dst");
+  if (refused(sdc_clone_envs_refused(call_facts(h), src, dst, n, src_of))) return -2;      // (every refusal before anything reaches the device)
+  const int N = h->cfg.n_envs;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const SdcDev& d = h->d;
@@ -1264,25 +1222,6 @@ static int snap_launch(sdc_handle* h, SdcSnapPlan& P, const bool save, const std
   });
 }
 
-// why a manifest row cannot be restored into this engine ("" if it can)
-static std::string snap_manifest_error(const sdc_handle* h, const int32_t* m) {
-  const int32_t want[5] = {(int32_t)state_layout_hash(), h->cfg.episode_steps, h->cfg.hist_cap, h->d.qstride, h->d.lw};
-  static const char* what[5] = {"state layout", "episode_steps", "hist_cap", "queue stride", "weather window length"};
-  static_assert(SDC_SNAP_LAYOUT == 0 && SDC_SNAP_EPISODE_STEPS == 1 && SDC_SNAP_HIST_CAP == 2 && SDC_SNAP_QUEUE_STRIDE == 3 &&
-                SDC_SNAP_WINDOW_LEN == 4, "the manifest's shape entries come first");
-  for (int i = 0; i < 5; i++)
-    if (m[i] != want[i])
-      return std::string(what[i]) + " " + std::to_string(m[i]) + ", this engine's is " + std::to_string(want[i]);
-  if (m[SDC_SNAP_T_REL] < 0 || m[SDC_SNAP_T_REL] > h->cfg.episode_steps)
-    return "episode step " + std::to_string(m[SDC_SNAP_T_REL]) + " outside [0, episode_steps]";
-  if (m[SDC_SNAP_FEAT_OK] != 0 && m[SDC_SNAP_FEAT_OK] != 1) return "feature-rows flag " + std::to_string(m[SDC_SNAP_FEAT_OK]);
-  if (m[SDC_SNAP_CFG_ID] < 0 || m[SDC_SNAP_CFG_ID] >= h->cfg.n_dc_configs)
-    return "cfg_id " + std::to_string(m[SDC_SNAP_CFG_ID]) + ", this engine has " + std::to_string(h->cfg.n_dc_configs) + " dc configs";
-  if (m[SDC_SNAP_LOC_ID] < 0 || m[SDC_SNAP_LOC_ID] >= h->cfg.n_locations)
-    return "loc_id " + std::to_string(m[SDC_SNAP_LOC_ID]) + ", this engine has " + std::to_string(h->cfg.n_locations) + " locations";
-  return "";
-}
-
 size_t sdc_snapshot_row_bytes(const sdc_handle* h) {
   if (!h) return 0;
   SdcSnapPlan P;
@@ -1295,15 +1234,7 @@ size_t sdc_snapshot_row_bytes(const sdc_handle* h) {
 // what the manifest records: include/sustaindc_hip.h.
 int sdc_snapshot_envs(sdc_handle* h, const int32_t* envs, int n, void* rows, int32_t* manifest, const float* obs,
                       const float* share_obs, void* stream) {
-  if (!h) return fail_msg("sdc_snapshot_envs: null handle");
-  if (n <= 0) return fail_msg("sdc_snapshot_envs: n must be positive");
-  if (!envs || !rows || !manifest || !obs || !share_obs) return fail_msg("sdc_snapshot_envs: null array");
-  if (!h->started) return fail_msg("sdc_snapshot_envs: sdc_reset must be called first");
-  const int N = h->cfg.n_envs;
-  if (n > N) return fail_msg("sdc_snapshot_envs: n = " + std::to_string(n) + " is more than the batch's " + std::to_string(N) + " envs");
-  const std::string why = unique_index_map(envs, nullptr, n, N, 0, nullptr, nullptr, nullptr);      // (an env may appear twice)
-  if (!why.empty()) return fail_msg("sdc_snapshot_envs: " + why);
-  if (const char* w = rows_error(rows)) return fail_msg(std::string("sdc_snapshot_envs: ") + w);
+  if (refused(sdc_snapshot_envs_refused(call_facts(h), envs, n, rows, manifest, obs, share_obs))) return -2;
   SdcSnapPlan P;
   size_t row_bytes = 0;
   if (!snap_plan(h, P, row_bytes, const_cast<float*>(obs), const_cast<float*>(share_obs)))
@@ -1336,21 +1267,9 @@ int sdc_snapshot_envs(sdc_handle* h, const int32_t* envs, int n, void* rows, int
 // manifest, so a restore that leaves the batch in lock-step keeps rel_hint and the specialised kernels
 int sdc_restore_envs(sdc_handle* h, const int32_t* rows_idx, const int32_t* envs, int n, const void* rows, int n_rows,
                      const int32_t* manifest, float* obs, float* share_obs, void* stream) {
-  if (!h) return fail_msg("sdc_restore_envs: null handle");
-  if (n <= 0) return fail_msg("sdc_restore_envs: n must be positive");
-  if (n_rows <= 0) return fail_msg("sdc_restore_envs: n_rows must be positive");
-  if (!rows_idx || !envs || !rows || !manifest || !obs || !share_obs) return fail_msg("sdc_restore_envs: null array");
-  if (!h->started) return fail_msg("sdc_restore_envs: sdc_reset must be called first");
-  const int N = h->cfg.n_envs;
-  // every refusal before anything reaches the device
   std::vector<int> row_of;      // dst -> its row
-  const std::string bad = unique_index_map(envs, rows_idx, n, N, n_rows, "row", "dst", &row_of);
-  if (!bad.empty()) return fail_msg("sdc_restore_envs: " + bad);
-  for (int k = 0; k < n; k++) {
-    const std::string why = snap_manifest_error(h, manifest + (size_t)rows_idx[k] * SDC_SNAPSHOT_MANIFEST);
-    if (!why.empty()) return fail_msg("sdc_restore_envs: row " + std::to_string(rows_idx[k]) + ": " + why);
-  }
-  if (const char* w = rows_error(rows)) return fail_msg(std::string("sdc_restore_envs: ") + w);
+  if (refused(sdc_restore_envs_refused(call_facts(h), rows_idx, envs, n, rows, n_rows, manifest, obs, share_obs, row_of))) return -2;
+  const int N = h->cfg.n_envs;
   SdcSnapPlan P;
   size_t row_bytes = 0;
   if (!snap_plan(h, P, row_bytes, obs, share_obs))
@@ -1431,23 +1350,6 @@ static bool mark_plan(const sdc_handle* h, SdcMarkPlan& P, const int n, const in
          d.hist_cap <= SDC_HIST_STRIDE && d.qstride >= 1;
 }
 
-// the arguments both calls refuse alike ("" if they pass)
-static std::string mark_args_error(const sdc_handle* h, const int32_t* envs, const int n, const void* rows, const void* manifest,
-                                   const void* obs, const void* share_obs) {
-  if (n <= 0) return "n must be positive";
-  if (!rows || !manifest || !obs || !share_obs) return "null array";
-  if (!h->started) return "sdc_reset must be called first";
-  const int N = h->cfg.n_envs;
-  if (n > N) return "n = " + std::to_string(n) + " is more than the batch's " + std::to_string(N) + " envs";
-  if (!envs && n != N) return "envs == NULL means the whole batch: n must be " + std::to_string(N) + ", not " + std::to_string(n);
-  if (envs) {
-    const std::string why = unique_index_map(envs, nullptr, n, N, 0, nullptr, nullptr, nullptr);
-    if (!why.empty()) return why;
-  }
-  if (const char* w = rows_error(rows)) return w;
-  return "";
-}
-
 // the launch's {env, row} pairs (sorted by env: range M's lanes are then consecutive envs) through the handle's idx_stage, and the
 // launch; `whole` (envs == NULL): nothing to stage.  row_of: env -> its row, -1 for the others
 static int mark_launch(sdc_handle* h, SdcMarkPlan& P, const bool save, const std::vector<int>& row_of, const bool whole,
@@ -1470,17 +1372,8 @@ static int mark_launch(sdc_handle* h, SdcMarkPlan& P, const bool save, const std
 // env's earlier mark is dead from here on.
 int sdc_mark_envs(sdc_handle* h, const int32_t* envs, int n, int max_steps, void* rows, int32_t* manifest, const float* obs,
                   const float* share_obs, void* stream) {
-  if (!h) return fail_msg("sdc_mark_envs: null handle");
-  if (max_steps < 1 || max_steps > SDC_MARK_MAX_STEPS)
-    return fail_msg("sdc_mark_envs: max_steps = " + std::to_string(max_steps) + " outside [1, " + std::to_string(SDC_MARK_MAX_STEPS) + "]");
-  const std::string why = mark_args_error(h, envs, n, rows, manifest, obs, share_obs);
-  if (!why.empty()) return fail_msg("sdc_mark_envs: " + why);
-  const int N = h->cfg.n_envs;
   std::vector<int> row_of;
-  if (envs) {
-    const std::string twice = unique_index_map(envs, nullptr, n, N, 0, nullptr, "env", &row_of);
-    if (!twice.empty()) return fail_msg("sdc_mark_envs: " + twice);
-  }
+  if (refused(sdc_mark_envs_refused(call_facts(h), envs, n, max_steps, rows, manifest, obs, share_obs, row_of))) return -2;
   SdcMarkPlan P;
   if (!mark_plan(h, P, n, max_steps, rows, obs, share_obs)) return fail_msg("sdc_mark_envs: obs / share_obs rows not dword-aligned");
   HIP_TRY(hipSetDevice(h->device));
@@ -1511,58 +1404,13 @@ int sdc_mark_envs(sdc_handle* h, const int32_t* envs, int n, int max_steps, void
 // batch keeps rel_hint and the specialised kernels.  The mark stays alive: a rewind may be repeated.
 int sdc_rewind_envs(sdc_handle* h, const int32_t* envs, int n, const void* rows, const int32_t* manifest, float* obs, float* share_obs,
                     void* stream) {
-  if (!h) return fail_msg("sdc_rewind_envs: null handle");
-  std::string why = mark_args_error(h, envs, n, rows, manifest, obs, share_obs);
-  if (!why.empty()) return fail_msg("sdc_rewind_envs: " + why);
-  const int N = h->cfg.n_envs;
-  // every refusal before anything reaches the device, from the host's mirror
+  // every refusal before anything reaches the device, from the host's mirror; a mark that has been overrun dies whatever the call answers
+  std::vector<int> row_of, overrun;
+  const int rc = refused(sdc_rewind_envs_refused(call_facts(h), envs, n, rows, manifest, obs, share_obs, row_of, overrun));
+  for (const int e : overrun) h->mirror.mark_kill(e);
+  if (rc) return rc;
   SdcHostMirror& mir = h->mirror;
-  const int32_t layout = (int32_t)state_layout_hash();
   const int max_steps = manifest[SDC_MARK_M_STEPS];
-  if (max_steps < 1 || max_steps > SDC_MARK_MAX_STEPS)
-    return fail_msg("sdc_rewind_envs: manifest with max_steps = " + std::to_string(max_steps) + " outside [1, " +
-                    std::to_string(SDC_MARK_MAX_STEPS) + "]");
-  std::vector<int> row_of;
-  if (envs) row_of.assign((size_t)N, -1);
-  // (the scan goes on behind the first refusal: every mark of the call that has been overrun dies; a message is built for the first only)
-  int bad_k = -1, bad_why = 0;
-  for (int k = 0; k < n; k++) {
-    const int e = envs ? envs[k] : k;
-    const int32_t* m = manifest + (size_t)k * SDC_MARK_MANIFEST;
-    int w = 0;
-    if (m[SDC_MARK_M_LAYOUT] != layout) w = 1;
-    else if (h->mark_engine_id == 0 || m[SDC_MARK_M_ENGINE] != h->mark_engine_id) w = 2;
-    else if (m[SDC_MARK_M_ENV] != e) w = 3;
-    else if (m[SDC_MARK_M_STEPS] != max_steps || m[SDC_MARK_M_HIST_CAP] != h->cfg.hist_cap) w = 4;
-    else if (envs && row_of[(size_t)e] >= 0) w = 5;
-    else if (!mir.mark_alive(e, m[SDC_MARK_M_SERIAL])) w = 6;
-    else if (mir.steps_since(e, m[SDC_MARK_M_T_REL]) < 0) w = 7;
-    else if (mir.steps_since(e, m[SDC_MARK_M_T_REL]) > max_steps) {
-      w = 8;
-      mir.mark_kill(e);     // slots beyond the row's reach have been overwritten: nothing can bring this mark back
-    }
-    if (envs) row_of[(size_t)e] = k;
-    if (w && bad_k < 0) { bad_k = k; bad_why = w; }
-  }
-  if (bad_k >= 0) {
-    const int e = envs ? envs[bad_k] : bad_k;
-    const int32_t* m = manifest + (size_t)bad_k * SDC_MARK_MANIFEST;
-    const int taken = mir.steps_since(e, m[SDC_MARK_M_T_REL]);
-    switch (bad_why) {
-      case 1: why = "state layout " + std::to_string(m[SDC_MARK_M_LAYOUT]) + ", this library's is " + std::to_string(layout); break;
-      case 2: why = "the mark was taken from another engine (a mark goes back into the engine and the env it came from)"; break;
-      case 3: why = "the mark was taken from env " + std::to_string(m[SDC_MARK_M_ENV]); break;
-      case 4: why = "max_steps / hist_cap differ from the first row's / this engine's (the rows of a call come from one sdc_mark_envs call)"; break;
-      case 5: why = "the env appears twice"; break;
-      case 6: why = "the mark is dead (a later mark of the env, a reset, sdc_set_state, a clone or restore into the env, or an earlier "
-                    "rewind refused beyond its max_steps)"; break;
-      case 7: why = "the env is at episode step " + std::to_string(mir.t_rel(e)) + ", before the mark's " +
-                    std::to_string(m[SDC_MARK_M_T_REL]); break;
-      default: why = std::to_string(taken) + " steps taken since the mark, more than its max_steps = " + std::to_string(max_steps) +
-                     " (the mark is dead for good: slots beyond its reach have been overwritten)";
-    }
-    return fail_msg("sdc_rewind_envs: row " + std::to_string(bad_k) + " (env " + std::to_string(e) + "): " + why);
-  }
   SdcMarkPlan P;
   if (!mark_plan(h, P, n, max_steps, rows, obs, share_obs)) return fail_msg("sdc_rewind_envs: obs / share_obs rows not dword-aligned");
   const SdcDev& d = h->d;
@@ -1612,28 +1460,6 @@ static unsigned forecast_channels(const sdc_handle* h) {
     if (h->plan_forecast.mode[c] != SDC_FORECAST_PERFECT) m |= 1u << c;
   return m;
 }
-// a VALUES channel of the handle's forecast without n_entries entries to read -> -2 with the message set
-static int forecast_values_refused(const std::string& w, const sdc_handle* h, const int n_entries) {
-  const sdc_plan_forecast& f = h->plan_forecast;
-  for (int c = 0; c < SDC_FC_CHANNELS; c++) {
-    if (f.mode[c] != SDC_FORECAST_VALUES) continue;
-    if (!f.values) return fail_msg(w + "forecast channel " + std::to_string(c) + " is SDC_FORECAST_VALUES and values is null");
-    if (f.values_entries < n_entries)
-      return fail_msg(w + "the forecast's values hold " + std::to_string(f.values_entries) + " entries, " + std::to_string(n_entries) +
-                      " are needed (n_steps + 2 at a plan call)");
-  }
-  return 0;
-}
-// what a plan call of n_steps refuses while a forecast is set
-static int forecast_refused(const std::string& w, const sdc_handle* h, const int n_steps) {
-  if (forecast_channels(h) == 0) return 0;
-  if (!h->d.feat) return fail_msg(w + "this engine has no feature rows (episodes too long for them): the forecast lives in the feature rows");
-  for (int e = 0; e < h->cfg.n_envs && h->mirror.n_feat() != h->cfg.n_envs; e++)      // (the count: no walk while every env's rows are valid)
-    if (!h->mirror.feat(e))
-      return fail_msg(w + "env " + std::to_string(e) +
-                      "'s feature rows are not valid (a host write to its state since its reset): the forecast lives in the feature rows");
-  return forecast_values_refused(w, h, n_steps + 2);
-}
 // the fill kernel's plan for n_entries entries into fc, with the handle's modes or -- truth -- every channel PERFECT
 static SdcForecastFill forecast_fill_plan(const sdc_handle* h, const int n_entries, const bool truth, double* fc) {
   const sdc_plan_forecast& f = h->plan_forecast;
@@ -1660,20 +1486,8 @@ static SdcForecastFill forecast_fill_plan(const sdc_handle* h, const int n_entri
 }
 
 int sdc_set_plan_forecast(sdc_handle* h, const sdc_plan_forecast* fc) {
-  static const std::string w = "sdc_set_plan_forecast: ";
-  if (!h) return fail_msg(w + "null handle");
   sdc_plan_forecast f;
-  std::memset(&f, 0, sizeof(f));
-  if (fc) {
-    for (int c = 0; c < SDC_FC_CHANNELS; c++) {
-      if (fc->mode[c] < SDC_FORECAST_PERFECT || fc->mode[c] > SDC_FORECAST_VALUES)
-        return fail_msg(w + "mode[" + std::to_string(c) + "] = " + std::to_string(fc->mode[c]) + " outside [0, 3]");
-      f.mode[c] = fc->mode[c];
-    }
-    if (fc->values_entries < 0) return fail_msg(w + "values_entries = " + std::to_string(fc->values_entries) + " is negative");
-    f.values_entries = fc->values_entries;
-    f.values = fc->values;
-  }
+  if (refused(sdc_set_plan_forecast_refused(call_facts(h), fc, f))) return -2;
   h->plan_forecast = f;
   return 0;
 }
@@ -1685,58 +1499,10 @@ int sdc_get_plan_forecast(const sdc_handle* h, sdc_plan_forecast* out) {
 }
 
 int sdc_forecast_traces(sdc_handle* h, int n_entries, int truth, double* out, void* stream) {
-  static const std::string w = "sdc_forecast_traces: ";
-  if (!h) return fail_msg(w + "null handle");
-  if (n_entries < 1 || n_entries > SDC_MARK_MAX_STEPS + 2)
-    return fail_msg(w + "n_entries = " + std::to_string(n_entries) + " outside [1, " + std::to_string(SDC_MARK_MAX_STEPS + 2) + "]");
-  if (!out) return fail_msg(w + "null out");
-  if ((reinterpret_cast<uintptr_t>(out) & 7u) != 0) return fail_msg(w + "out not 8-byte aligned");
-  if (!h->started) return fail_msg(w + "sdc_reset must be called first");
-  if (n_entries > h->mirror.steps_to_terminal() + 2)
-    return fail_msg(w + "n_entries = " + std::to_string(n_entries) + " reaches past the end of an episode (" +
-                    std::to_string(h->mirror.steps_to_terminal()) + " steps left: at most that + 2 entries)");
-  if (!truth && forecast_values_refused(w, h, n_entries)) return -2;
+  if (refused(sdc_forecast_traces_refused(call_facts(h), n_entries, truth, out))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   return launched("sdc_forecast_fill_kernel",
                   sdc_forecast_fill_launch(forecast_fill_plan(h, n_entries, truth != 0, out), reinterpret_cast<hipStream_t>(stream)));
-}
-
-// What every plan call refuses about its objective; obj: the objective with the defaults filled in.  -> 0, or -2 with the message set
-static int plan_objective_refused(const std::string& w, const sdc_plan_objective* objective, sdc_plan_objective& obj) {
-  std::memset(&obj, 0, sizeof(obj));
-  obj.reward_weight[0] = obj.reward_weight[1] = obj.reward_weight[2] = 1.0;
-  obj.gamma = 1.0;
-  if (objective) obj = *objective;
-  if (!(obj.gamma > 0.0 && obj.gamma <= 1.0)) return fail_msg(w + "gamma = " + std::to_string(obj.gamma) + " outside (0, 1]");
-  if (obj.n_cols < 0 || obj.n_cols > SDC_PLAN_MAX_COLS)
-    return fail_msg(w + "n_cols = " + std::to_string(obj.n_cols) + " outside [0, " + std::to_string(SDC_PLAN_MAX_COLS) + "]");
-  for (int j = 0; j < obj.n_cols; j++)
-    if (obj.col[j] < 0 || obj.col[j] >= SDC_INFO_DIM)
-      return fail_msg(w + "info column " + std::to_string(obj.col[j]) + " (entry " + std::to_string(j) + ") outside [0, " +
-                      std::to_string(SDC_INFO_DIM) + ")");
-  return 0;
-}
-
-// What every plan call refuses about the horizon, the engine and the objective, in sdc_plan's order (`arrays`: the caller's own null
-// check, reported at its place in that order); obj: the objective with the defaults filled in.  -> 0, or -2 with the message set
-static int plan_refused(const char* who, const sdc_handle* h, const int n_steps, const bool arrays, const float* obs, const float* share_obs,
-                        const sdc_plan_objective* objective, sdc_plan_objective& obj) {
-  const std::string w = std::string(who) + ": ";
-  if (n_steps < 1 || n_steps > SDC_MARK_MAX_STEPS)
-    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " outside [1, " + std::to_string(SDC_MARK_MAX_STEPS) + "]");
-  if (!arrays || !obs || !share_obs) return fail_msg(w + "null array");
-  if (((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(share_obs)) & 3u) != 0)
-    return fail_msg(w + "obs / share_obs rows not dword-aligned");
-  if (!h->started) return fail_msg(w + "sdc_reset must be called first");
-  if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) return fail_msg(w + "verify mode checks single steps (sdc_rollout refuses it as well)");
-  if (h->cfg.auto_reset && n_steps >= h->mirror.steps_to_terminal())
-    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would finish an episode (" + std::to_string(h->mirror.steps_to_terminal()) +
-                    " steps left): the auto-reset kills the mark");
-  if (n_steps > h->mirror.steps_to_terminal())
-    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" +
-                    std::to_string(h->mirror.steps_to_terminal()) + " steps left)");
-  if (plan_objective_refused(w, objective, obj)) return -2;
-  return forecast_refused(w, h, n_steps);
 }
 
 // A plan call's horizon, the layout of the handle's output block for it, and the score kernel's plan but for the candidate's own arrays
@@ -1950,10 +1716,8 @@ static int plan_session(sdc_handle* h, const int n_steps, const sdc_plan_objecti
 // Mark, the candidates (plan_candidates), select.  Whatever the entry points underneath would refuse is refused here first.
 int sdc_plan(sdc_handle* h, int n_cand, int n_steps, const int32_t* actions, const sdc_plan_objective* objective, double* returns,
              double* score, int32_t* best, int32_t* best_action, float* obs, float* share_obs, void* stream) {
-  if (!h) return fail_msg("sdc_plan: null handle");
-  if (n_cand < 1) return fail_msg("sdc_plan: n_cand = " + std::to_string(n_cand) + " must be positive");
   sdc_plan_objective obj;
-  if (plan_refused("sdc_plan", h, n_steps, actions && score && best && best_action, obs, share_obs, objective, obj)) return -2;
+  if (refused(sdc_plan_refused(call_facts(h), n_cand, n_steps, actions, objective, score, best, best_action, obs, share_obs, obj))) return -2;
   const SdcPlanSelect Q{h->cfg.n_envs, n_cand, n_steps, score, actions, best, best_action};
   return plan_session(h, n_steps, obj, obs, share_obs, stream, [&](PlanSession& P) {
     const int rc = plan_candidates(P, n_cand, actions, returns, score);
@@ -1964,44 +1728,8 @@ int sdc_plan(sdc_handle* h, int n_cand, int n_steps, const int32_t* actions, con
 // ---- plan terms (sdc_plan_terms.hip) ---------------------------------------------------------------------------------------------------
 // Host state of the handle; plan_candidates reads it.  The contract: include/sustaindc_hip.h.
 int sdc_set_plan_terms(sdc_handle* h, const sdc_plan_terms* terms) {
-  static const std::string w = "sdc_set_plan_terms: ";
-  if (!h) return fail_msg(w + "null handle");
   sdc_plan_terms t;
-  std::memset(&t, 0, sizeof(t));
-  if (!terms || (terms->n_limits == 0 && terms->n_terminal == 0)) {
-    h->plan_terms = t;
-    return 0;
-  }
-  if (terms->n_limits < 0 || terms->n_limits > SDC_PLAN_MAX_LIMITS)
-    return fail_msg(w + "n_limits = " + std::to_string(terms->n_limits) + " outside [0, " + std::to_string(SDC_PLAN_MAX_LIMITS) + "]");
-  if (terms->n_terminal < 0 || terms->n_terminal > SDC_PLAN_MAX_TERMINAL)
-    return fail_msg(w + "n_terminal = " + std::to_string(terms->n_terminal) + " outside [0, " + std::to_string(SDC_PLAN_MAX_TERMINAL) + "]");
-  const auto entry = [](const char* field, const int j) { return std::string(field) + "[" + std::to_string(j) + "] = "; };
-  t.n_limits = terms->n_limits;
-  t.n_terminal = terms->n_terminal;
-  for (int j = 0; j < t.n_limits; j++) {
-    const int col = terms->limit_col[j], side = terms->limit_side[j];
-    const double bound = terms->limit_bound[j], weight = terms->limit_weight[j];
-    if (col < 0 || col >= SDC_INFO_DIM)
-      return fail_msg(w + entry("limit_col", j) + std::to_string(col) + " outside [0, " + std::to_string(SDC_INFO_DIM) + ")");
-    if (side != 1 && side != -1) return fail_msg(w + entry("limit_side", j) + std::to_string(side) + " is neither +1 (upper) nor -1 (lower)");
-    if (!std::isfinite(bound)) return fail_msg(w + entry("limit_bound", j) + std::to_string(bound) + " is not finite");
-    if (!std::isfinite(weight)) return fail_msg(w + entry("limit_weight", j) + std::to_string(weight) + " is not finite");
-    if (weight < 0.0) return fail_msg(w + entry("limit_weight", j) + std::to_string(weight) + " is negative");
-    t.limit_col[j] = col;
-    t.limit_side[j] = side;
-    t.limit_bound[j] = bound;
-    t.limit_weight[j] = weight;
-  }
-  for (int j = 0; j < t.n_terminal; j++) {
-    const int col = terms->terminal_col[j];
-    const double weight = terms->terminal_weight[j];
-    if (col < 0 || col >= SDC_INFO_DIM)
-      return fail_msg(w + entry("terminal_col", j) + std::to_string(col) + " outside [0, " + std::to_string(SDC_INFO_DIM) + ")");
-    if (!std::isfinite(weight)) return fail_msg(w + entry("terminal_weight", j) + std::to_string(weight) + " is not finite");
-    t.terminal_col[j] = col;
-    t.terminal_weight[j] = weight;
-  }
+  if (refused(sdc_set_plan_terms_refused(call_facts(h), terms, t))) return -2;
   h->plan_terms = t;
   return 0;
 }
@@ -2029,13 +1757,7 @@ int sdc_set_critic(sdc_handle* h, const sdc_critic_params* p) {
 }
 
 int sdc_critic_values(sdc_handle* h, const float* share_obs, long long n_rows, float* values, void* stream) {
-  static const std::string w = "sdc_critic_values: ";
-  if (!h) return fail_msg(w + "null handle");
-  if (!h->critic_set) return fail_msg(w + "sdc_set_critic first");
-  if (n_rows < 1) return fail_msg(w + "n_rows = " + std::to_string(n_rows) + " must be positive");
-  if (!share_obs || !values) return fail_msg(w + "null array");
-  if (((reinterpret_cast<uintptr_t>(share_obs) | reinterpret_cast<uintptr_t>(values)) & 3u) != 0)
-    return fail_msg(w + "share_obs / values not dword-aligned");
+  if (refused(sdc_critic_values_refused(call_facts(h), share_obs, n_rows, values))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   h->last_step_kernel = "sdc_critic_values_kernel";
   return launched("sdc_critic_values_kernel",
@@ -2043,10 +1765,7 @@ int sdc_critic_values(sdc_handle* h, const float* share_obs, long long n_rows, f
 }
 
 int sdc_set_plan_critic(sdc_handle* h, double weight) {
-  static const std::string w = "sdc_set_plan_critic: ";
-  if (!h) return fail_msg(w + "null handle");
-  if (!std::isfinite(weight)) return fail_msg(w + "weight = " + std::to_string(weight) + " is not finite");
-  if (weight != 0.0 && !h->critic_set) return fail_msg(w + "weight = " + std::to_string(weight) + " while no critic is set (sdc_set_critic first)");
+  if (refused(sdc_set_plan_critic_refused(call_facts(h), weight))) return -2;
   h->plan_critic_weight = weight;
   return 0;
 }
@@ -2059,36 +1778,6 @@ int sdc_get_plan_critic(const sdc_handle* h, double* weight) {
 
 // ---- plan with the cross-entropy method (sdc_cem.hip, sdc_cem_groups.hip) -----------------------------------------------------------
 // The contract and the arithmetic: include/sustaindc_hip.h; the kernels' plans: sdc_cem.hpp, sdc_cem_groups.hpp.
-
-// The parameter ranges sdc_plan_cem and sdc_plan_cem_groups refuse alike (w: the caller's "who: "), each -> 0, or -2 with the message
-// set.  The callers run them in their own order, with their own checks in between.
-static int cem_iters_refused(const std::string& w, const int n_iters, const int iter0) {
-  if (n_iters < 1) return fail_msg(w + "n_iters = " + std::to_string(n_iters) + " must be positive");
-  if (iter0 < 0 || (long long)iter0 + n_iters > 65536)
-    return fail_msg(w + "iter0 = " + std::to_string(iter0) + " with n_iters = " + std::to_string(n_iters) + " outside [0, 65536]");
-  return 0;
-}
-// (the population the elites are taken from: its name and size)
-static int cem_elite_refused(const std::string& w, const int n_elite, const char* pop, const int size) {
-  if (n_elite < 1 || n_elite > size)
-    return fail_msg(w + "n_elite = " + std::to_string(n_elite) + " outside [1, " + pop + " = " + std::to_string(size) + "]");
-  return 0;
-}
-static int cem_refit_refused(const std::string& w, const int32_t* fixed_action, const double alpha, const double p_min) {
-  for (int a = 0; a < 3; a++)
-    if (fixed_action[a] < -1 || fixed_action[a] > 2)
-      return fail_msg(w + "fixed_action[" + std::to_string(a) + "] = " + std::to_string(fixed_action[a]) + " outside [-1, 2]");
-  if (!(alpha >= 0.0 && alpha < 1.0)) return fail_msg(w + "alpha = " + std::to_string(alpha) + " outside [0, 1)");
-  if (!(p_min >= 0.0 && p_min <= 1.0 / 3.0)) return fail_msg(w + "p_min = " + std::to_string(p_min) + " outside [0, 1/3]");
-  return 0;
-}
-// What sdc_plan_cem and sdc_rollout_cem_stats refuse alike about the per-env planner's parameters, in the former's order
-static int cem_params_refused(const std::string& w, const sdc_cem_params& c) {
-  if (cem_iters_refused(w, c.n_iters, c.iter0)) return -2;
-  if (c.n_cand < 2 || c.n_cand > SDC_CEM_MAX_CAND)
-    return fail_msg(w + "n_cand = " + std::to_string(c.n_cand) + " outside [2, " + std::to_string(SDC_CEM_MAX_CAND) + "]");
-  return cem_elite_refused(w, c.n_elite, "n_cand", c.n_cand) || cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min) ? -2 : 0;
-}
 
 extern "C++" {
 // the fields the per-env and the group kernels' plans share, from the fields the two parameter structs share
@@ -2184,64 +1873,24 @@ static auto cem_groups_body(const sdc_handle* h, const sdc_cem_group_params& c, 
 int sdc_plan_cem(sdc_handle* h, int n_steps, const sdc_cem_params* cem, const sdc_plan_objective* objective, double* probs,
                  int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* cand, double* cand_score, float* obs,
                  float* share_obs, void* stream) {
-  static const std::string w = "sdc_plan_cem: ";
-  if (!h) return fail_msg(w + "null handle");
-  if (!cem) return fail_msg(w + "null cem");
-  const sdc_cem_params c = *cem;
-  if (cem_params_refused(w, c)) return -2;
   sdc_plan_objective obj;
-  if (plan_refused("sdc_plan_cem", h, n_steps, probs && best_seq && best_score && best_action && cand && cand_score, obs, share_obs,
-                   objective, obj))
+  if (refused(sdc_plan_cem_refused(call_facts(h), n_steps, cem, objective, probs, best_seq, best_score, best_action, cand, cand_score, obs,
+                                   share_obs, obj)))
     return -2;
+  const sdc_cem_params c = *cem;
   return plan_session(h, n_steps, obj, obs, share_obs, stream,
                       cem_body(h, c, n_steps, probs, best_seq, best_score, best_action, cand, cand_score));
-}
-
-// What sdc_plan_cem_groups and sdc_rollout_cem_groups_stats refuse alike about the groups of a batch of N envs, in the former's order
-static int cem_groups_refused(const std::string& w, const int N, const sdc_cem_group_params& c) {
-  if (c.group_size < 2 || c.group_size > SDC_CEM_MAX_GROUP)
-    return fail_msg(w + "group_size = " + std::to_string(c.group_size) + " outside [2, " + std::to_string(SDC_CEM_MAX_GROUP) + "]");
-  if (N % c.group_size != 0)
-    return fail_msg(w + "n_envs = " + std::to_string(N) + " is not a multiple of group_size = " + std::to_string(c.group_size));
-  if (cem_elite_refused(w, c.n_elite, "group_size", c.group_size)) return -2;
-  if (c.group_base < 0) return fail_msg(w + "group_base = " + std::to_string(c.group_base) + " is negative");
-  return 0;
-}
-// ... and, from what the host's mirror (sdc_mirror.hpp) knows of a group's replicas in O(N): the episode step, the config, the trace
-// set, the feature-row flag
-static int groups_out_of_step_refused(const std::string& w, const sdc_handle* h, const int R) {
-  const SdcHostMirror& mir = h->mirror;
-  for (int e = 0; e < h->cfg.n_envs; e++) {
-    const int l = e - e % R;      // the group's first env
-    if (e == l) continue;
-    const char* what = mir.t_rel(e) != mir.t_rel(l)   ? "episode step"
-                       : mir.cfg(e) != mir.cfg(l)     ? "data-centre config"
-                       : mir.loc(e) != mir.loc(l)     ? "location"
-                       : mir.feat(e) != mir.feat(l)   ? "feature-row flag"
-                                                      : nullptr;
-    if (what)
-      return fail_msg(w + "group " + std::to_string(e / R) + " is out of step: env " + std::to_string(e) + " and its group's first env " +
-                      std::to_string(l) + " differ in " + what + " (the replicas of a group hold one state: sdc_clone_envs)");
-  }
-  return 0;
 }
 
 // sdc_plan_cem with the candidates in env slots (cem_groups_body)
 int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* cem, const sdc_plan_objective* objective, double* probs,
                         int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* step_actions, int32_t* cand,
                         double* cand_score, float* obs, float* share_obs, void* stream) {
-  static const std::string w = "sdc_plan_cem_groups: ";
-  if (!h) return fail_msg(w + "null handle");
-  if (!cem) return fail_msg(w + "null cem");
-  const sdc_cem_group_params c = *cem;
-  const int N = h->cfg.n_envs;
-  if (cem_iters_refused(w, c.n_iters, c.iter0) || cem_groups_refused(w, N, c) || cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min))
-    return -2;
   sdc_plan_objective obj;
-  if (plan_refused("sdc_plan_cem_groups", h, n_steps, probs && best_seq && best_score && best_action && step_actions && cand && cand_score,
-                   obs, share_obs, objective, obj))
+  if (refused(sdc_plan_cem_groups_refused(call_facts(h), n_steps, cem, objective, probs, best_seq, best_score, best_action, step_actions, cand,
+                                          cand_score, obs, share_obs, obj)))
     return -2;
-  if (groups_out_of_step_refused(w, h, c.group_size)) return -2;
+  const sdc_cem_group_params c = *cem;
   return plan_session(h, n_steps, obj, obs, share_obs, stream,
                       cem_groups_body(h, c, n_steps, probs, best_seq, best_score, best_action, step_actions, cand, cand_score));
 }
@@ -2250,37 +1899,7 @@ int sdc_plan_cem_groups(sdc_handle* h, int n_steps, const sdc_cem_group_params* 
 // The contracts and the arithmetic: include/sustaindc_hip.h; the kernels' plans and the lane mappings: sdc_stats.hpp,
 // sdc_policy_stats.hpp.  The rollouts go into the plan calls' output block (plan_out_block, rollout_chunks); nothing is marked or rewound.
 
-// the caller's arrays of sdc_rollout_stats and sdc_rollout_actor_stats
-struct StatsArrays {
-  double *stats, *returns;
-  int32_t* counts;
-  float *obs, *share_obs, *rew;
-  uint8_t* done;
-  float *info, *final_obs;
-};
-
-// What both calls refuse about their arrays and the engine, in sdc_rollout_stats' order, up to verify mode.  -> 0, or -2 with the message set
-static int stats_refused(const std::string& w, const sdc_handle* h, const int n_steps, const int accumulate, const StatsArrays& a) {
-  if (!h) return fail_msg(w + "null handle");
-  if (n_steps < 1) return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " must be positive");
-  if (!a.stats || !a.returns || !a.counts || !a.obs || !a.share_obs)
-    return fail_msg(w + "null array (stats, returns, counts, obs and share_obs are required)");
-  const auto addr = [](const void* q) { return reinterpret_cast<uintptr_t>(q); };
-  if (((addr(a.stats) | addr(a.returns)) & 15u) != 0) return fail_msg(w + "stats / returns not 16-byte aligned");
-  if (((addr(a.counts) | addr(a.obs) | addr(a.share_obs) | addr(a.rew) | addr(a.info) | addr(a.final_obs)) & 3u) != 0)
-    return fail_msg(w + "counts / obs / share_obs / rew / info / final_obs rows not dword-aligned");
-  if (accumulate != 0 && accumulate != 1) return fail_msg(w + "accumulate = " + std::to_string(accumulate) + " outside {0, 1}");
-  if (!h->started) return fail_msg(w + "sdc_reset must be called first");
-  if (h->cfg.debug_flags & SDC_DEBUG_VERIFY) return fail_msg(w + "verify mode checks single steps (sdc_rollout refuses it as well)");
-  return 0;
-}
-// ... and about the episode's end, `left` steps away (the mirror's steps_to_terminal, or what a sync will make of it)
-static int stats_past_end_refused(const std::string& w, const int n_steps, const int left) {
-  if (n_steps > left)
-    return fail_msg(w + "n_steps = " + std::to_string(n_steps) + " would run past the end of an episode (" + std::to_string(left) +
-                    " steps left)");
-  return 0;
-}
+using StatsArrays = SdcStatsArrays;      // (the caller's arrays of the statistics calls: sdc_refusals.hpp)
 
 // sdc_stats_reduce_kernel's plan over the block (layout B) into the caller's arrays, but for the chunk's steps and init
 static SdcStatsReduce stats_reduce_plan(const sdc_handle* h, const SdcPlanBlock& B, const StatsArrays& a) {
@@ -2341,11 +1960,8 @@ static int stats_chunks(sdc_handle* h, const SdcPlanBlock& B, const int n_steps,
 int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int accumulate, double* stats, double* returns,
                       int32_t* counts, float* obs, float* share_obs, float* rew, uint8_t* done, float* info, float* final_obs,
                       void* stream) {
-  static const std::string w = "sdc_rollout_stats: ";
   const StatsArrays a = {stats, returns, counts, obs, share_obs, rew, done, info, final_obs};
-  if (stats_refused(w, h, n_steps, accumulate, a)) return -2;
-  if (!actions && !sdc_all_policies(h->d.policy)) return fail_msg(w + "actions may only be NULL when every agent slot has a policy");
-  if (stats_past_end_refused(w, n_steps, h->mirror.steps_to_terminal())) return -2;
+  if (refused(sdc_rollout_stats_refused(call_facts(h), n_steps, actions, accumulate, a))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   int chunk;
   SdcPlanBlock B;
@@ -2354,35 +1970,18 @@ int sdc_rollout_stats(sdc_handle* h, int n_steps, const int32_t* actions, int ac
                       [](int, int, int) { return 0; });
 }
 
-// What sdc_rollout_actor would refuse about the actors and the batch, asked before anything is enqueued (its own checks stay where they
-// are: every chunk passes them again).  The output arrays are the handle's block's: all there, 256-byte aligned
-static int actor_refused(const std::string& w, const sdc_handle* h) {
-  if (!h->actor_set[0] || !h->actor_set[1] || !h->actor_set[2]) return fail_msg(w + "sdc_set_actor all three agents first");
-  if (h->actor_activation[0] != h->actor_activation[1] || h->actor_activation[0] != h->actor_activation[2])
-    return fail_msg(w + "the three actors must share one activation (the reference builds them from one model config: happo.yaml "
-                        "activation_func)");
-  if (!h->latch_valid)
-    return fail_msg(w + "no observations yet (the actors were set after the last reset / step: reset or step once)");
-  SdcStepFacts f = step_facts(h, true, nullptr, nullptr, nullptr, nullptr, nullptr, false);
-  f.share_obs = f.info = f.actions_out = true;
-  if (sdc_actor_path(f).refused)
-    return fail_msg(w + "needs the common case (lock-step batch with feature rows, one data-centre config of <= 32 racks, "
-                        "external-action slots, default rewards, an even number of envs, no debug flags)");
-  return 0;
-}
-
 int sdc_rollout_actor_stats(sdc_handle* h, int n_steps, int sample, int accumulate, double* stats, double* returns, int32_t* counts,
                             int32_t* policy_counts, double* policy_sums, float* obs, float* share_obs, float* rew, uint8_t* done,
                             float* info, float* final_obs, void* stream) {
-  static const std::string w = "sdc_rollout_actor_stats: ";
   const StatsArrays a = {stats, returns, counts, obs, share_obs, rew, done, info, final_obs};
-  if (stats_refused(w, h, n_steps, accumulate, a)) return -2;
-  if (sample != 0 && sample != 1) return fail_msg(w + "sample = " + std::to_string(sample) + " outside {0, 1}");
-  if ((policy_counts == nullptr) != (policy_sums == nullptr)) return fail_msg(w + "policy_counts and policy_sums are given together or not at all");
-  if ((reinterpret_cast<uintptr_t>(policy_sums) & 15u) != 0) return fail_msg(w + "policy_sums not 16-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(policy_counts) & 3u) != 0) return fail_msg(w + "policy_counts not dword-aligned");
-  if (actor_refused(w, h)) return -2;
-  if (stats_past_end_refused(w, n_steps, h->mirror.steps_to_terminal())) return -2;
+  // (what sdc_rollout_actor would refuse about the actors and the batch is asked before anything is enqueued; its own checks stay where
+  // they are: every chunk passes them again.  The output arrays are the handle's block's: all there, 256-byte aligned)
+  SdcCallFacts facts = call_facts(h);
+  if (h) {
+    facts.step = step_facts(h, true, nullptr, nullptr, nullptr, nullptr, nullptr, false);
+    facts.step.share_obs = facts.step.info = facts.step.actions_out = true;
+  }
+  if (refused(sdc_rollout_actor_stats_refused(facts, n_steps, sample, accumulate, a, policy_counts, policy_sums))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t N = (size_t)h->cfg.n_envs;
@@ -2421,64 +2020,6 @@ int sdc_rollout_actor_stats(sdc_handle* h, int n_steps, int sample, int accumula
 // (sdc_mpc_groups.hip) is the same loop (mpc_steps) with sdc_plan_cem_groups' body (cem_groups_body) and its own fold kernel, a sync in
 // front and the agreement check behind the step.
 
-// What both calls refuse about the loop's own parameters (the leading fields of sdc_mpc_params and sdc_mpc_group_params)
-static int mpc_loop_refused(const std::string& w, const int H, const int warm_start, const int resume, const int resume_steps,
-                            const int32_t* idle_action) {
-  if (H < 1 || H > SDC_MARK_MAX_STEPS)
-    return fail_msg(w + "horizon = " + std::to_string(H) + " outside [1, " + std::to_string(SDC_MARK_MAX_STEPS) + "]");
-  if (warm_start != 0 && warm_start != 1) return fail_msg(w + "warm_start = " + std::to_string(warm_start) + " outside {0, 1}");
-  if (resume != 0 && resume != 1) return fail_msg(w + "resume = " + std::to_string(resume) + " outside {0, 1}");
-  if (resume && (resume_steps < 1 || resume_steps > H))
-    return fail_msg(w + "resume_steps = " + std::to_string(resume_steps) + " outside [1, horizon = " + std::to_string(H) + "]");
-  for (int k = 0; k < 3; k++)
-    if (idle_action[k] < 0 || idle_action[k] > 2)
-      return fail_msg(w + "idle_action[" + std::to_string(k) + "] = " + std::to_string(idle_action[k]) + " outside [0, 2]");
-  return 0;
-}
-
-// A caller's array under the name the messages give it, and the alignment in bytes the kernels need of it
-struct NamedArray {
-  const char* name;
-  const void* p;
-  unsigned align;
-};
-// the names of v's arrays of that alignment (0: of all of them), `sep` between them and `last` in front of the last one
-static std::string array_names(const std::vector<NamedArray>& v, const unsigned align, const char* sep, const char* last) {
-  std::string s, tail;
-  for (const NamedArray& x : v)
-    if (!align || x.align == align) {
-      if (!tail.empty()) s += (s.empty() ? "" : sep) + tail;
-      tail = x.name;
-    }
-  return s.empty() ? tail : s + last + tail;
-}
-// What both calls refuse about their own arrays, each list in its signature's order: `plan`, the planner's (all required, 8-byte or
-// dword aligned), and `opt`, the statistics' (given together or not at all, 16-byte or dword aligned)
-static int mpc_arrays_refused(const std::string& w, const std::vector<NamedArray>& plan, const std::vector<NamedArray>& opt) {
-  uintptr_t bits[2][17] = {};      // the addresses OR-ed together, by list and alignment
-  for (const NamedArray& x : plan) bits[0][x.align] |= reinterpret_cast<uintptr_t>(x.p);
-  for (const NamedArray& x : opt) bits[1][x.align] |= reinterpret_cast<uintptr_t>(x.p);
-  for (const NamedArray& x : plan)
-    if (!x.p) return fail_msg(w + "null array (" + array_names(plan, 0, ", ", " and ") + " are required)");
-  if (bits[0][8] & 7u) return fail_msg(w + array_names(plan, 8, " / ", " / ") + " not 8-byte aligned");
-  if (bits[0][4] & 3u) return fail_msg(w + array_names(plan, 4, " / ", " / ") + " not dword-aligned");
-  for (const NamedArray& x : opt)
-    if ((x.p == nullptr) != (opt[0].p == nullptr))
-      return fail_msg(w + array_names(opt, 0, ", ", " and ") + " are given together or not at all");
-  if (bits[1][16] & 15u) return fail_msg(w + array_names(opt, 16, " / ", " / ") + " not 16-byte aligned");
-  if (bits[1][4] & 3u) return fail_msg(w + array_names(opt, 4, " / ", " / ") + " not dword-aligned");
-  return 0;
-}
-
-// the longest planned decision of a call of n_steps that starts `left` steps before the episode's end: the first one (the horizon only
-// shrinks towards the episode's end); 0: every decision idles
-static int mpc_longest(const int H, const int warm_start, const int auto_reset, const int resume_steps, const int left, const int n_steps) {
-  int k_max = 0;
-  SdcMpcSchedule S(H, warm_start, auto_reset, resume_steps);
-  for (int t = 0; t < n_steps; t++) k_max = std::max(k_max, S.next(left - t).steps);
-  return k_max;
-}
-
 extern "C++" {
 // what the two fold kernels' plans share but for the decision's own fields and the idle actions (mpc_steps); best_score's rows are `row`
 // entries long (N, or G)
@@ -2496,21 +2037,18 @@ static Fold mpc_fold_plan(const int n_envs, const size_t row, const int n_iters,
   return F;
 }
 
-// The steps of a planner evaluation once its arguments have passed, but for the forecast's reach, which is refused here, before the
-// device is touched.  m: the loop's fields (sdc_mpc_params or sdc_mpc_group_params); left: the steps the episode has left at the first
-// decision.  Every buffer at its largest before anything is enqueued: the step's one-step block, the longest decision's (k_max steps)
-// rows, block and forecast; then first() -> rc (the groups' sync); the discount table of H steps staged once; then per step the
-// schedule's decision d -- planned: sdc_mpc_start_kernel (plan A, of which the caller fills n_envs, probs and best_seq) and plan_marked
+// The steps of a planner evaluation once its arguments have passed.  m: the loop's fields (sdc_mpc_params or sdc_mpc_group_params);
+// k_max: the longest planned decision (sdc_refusals.hpp sdc_mpc_longest).  Every buffer at its largest before anything is enqueued: the
+// step's one-step block, the longest decision's (k_max steps) rows, block and forecast; then first() -> rc (the groups' sync); the
+// discount table of H steps staged once; then per step the schedule's decision d -- planned: sdc_mpc_start_kernel (plan A, of which the caller fills n_envs, probs and best_seq) and plan_marked
 // around body(d), the planner's body for that decision (cem_body, cem_groups_body) --, the fold kernel (plan F through `fold`; a planned
 // decision without statistics has nothing to fold), and the step: sdc_rollout_stats' path with a one-step chunk and `actions` [N][3],
 // behind its reduce kernel behind(B1, init) -> rc.  Behind the last step sdc_stats_last_kernel.  The idle actions go into A and F here.
 template <class Params, class Fold, class First, class Body, class Behind>
-static int mpc_steps(const std::string& w, sdc_handle* h, const int n_steps, const Params& m, const int left, const int accumulate,
+static int mpc_steps(sdc_handle* h, const int n_steps, const Params& m, const int k_max, const int accumulate,
                      const sdc_plan_objective& obj, const StatsArrays& a, SdcMpcStart A, Fold F, hipError_t (*fold)(const Fold&, hipStream_t),
                      const char* fold_kernel, const int32_t* actions, void* stream, First&& first, Body&& body, Behind&& behind) {
   const int H = m.horizon, warm_start = m.warm_start, resume_steps = m.resume ? m.resume_steps : 0, auto_reset = h->cfg.auto_reset ? 1 : 0;
-  const int k_max = mpc_longest(H, warm_start, auto_reset, resume_steps, left, n_steps);
-  if (k_max > 0 && forecast_refused(w, h, k_max)) return -2;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   for (int k = 0; k < 3; k++) A.idle[k] = F.idle[k] = m.idle_action[k];
@@ -2570,24 +2108,17 @@ int sdc_rollout_cem_stats(sdc_handle* h, int n_steps, const sdc_mpc_params* mpc,
                           double* stats, double* returns, int32_t* counts, int32_t* plan_counts, double* plan_sums, double* probs,
                           int32_t* best_seq, double* best_score, int32_t* best_action, int32_t* cand, double* cand_score, float* obs,
                           float* share_obs, float* rew, uint8_t* done, float* info, float* final_obs, void* stream) {
-  static const std::string w = "sdc_rollout_cem_stats: ";
   const StatsArrays a = {stats, returns, counts, obs, share_obs, rew, done, info, final_obs};
-  if (stats_refused(w, h, n_steps, accumulate, a)) return -2;
-  if (!mpc) return fail_msg(w + "null mpc");
+  sdc_plan_objective obj;
+  int k_max = 0;
+  if (refused(sdc_rollout_cem_stats_refused(call_facts(h), n_steps, mpc, objective, accumulate, a, plan_counts, plan_sums, probs, best_seq,
+                                            best_score, best_action, cand, cand_score, obj, k_max)))
+    return -2;
   const sdc_mpc_params m = *mpc;
   const sdc_cem_params c = m.cem;
-  const int H = m.horizon, N = h->cfg.n_envs;
-  if (mpc_loop_refused(w, H, m.warm_start, m.resume, m.resume_steps, m.idle_action) || cem_params_refused(w, c)) return -2;
-  if (mpc_arrays_refused(w,
-                         {{"probs", probs, 8}, {"best_seq", best_seq, 4}, {"best_score", best_score, 8}, {"best_action", best_action, 4},
-                          {"cand", cand, 4}, {"cand_score", cand_score, 8}},
-                         {{"plan_counts", plan_counts, 4}, {"plan_sums", plan_sums, 16}}))
-    return -2;
-  sdc_plan_objective obj;
-  const int left = h->mirror.steps_to_terminal();
-  if (plan_objective_refused(w, objective, obj) || stats_past_end_refused(w, n_steps, left)) return -2;
+  const int N = h->cfg.n_envs;
   return mpc_steps(
-      w, h, n_steps, m, left, accumulate, obj, a, SdcMpcStart{N, 0, 0, {}, probs, best_seq},
+      h, n_steps, m, k_max, accumulate, obj, a, SdcMpcStart{N, 0, 0, {}, probs, best_seq},
       mpc_fold_plan<SdcMpcFold>(N, (size_t)N, c.n_iters, best_score, best_action, plan_counts, plan_sums), sdc_mpc_fold_launch,
       "sdc_mpc_fold_kernel", best_action, stream, [] { return 0; },
       [&](const SdcMpcDecision& d) {
@@ -2607,36 +2138,15 @@ int sdc_rollout_cem_groups_stats(sdc_handle* h, int n_steps, const sdc_mpc_group
                                  int32_t* diverged, double* probs, int32_t* best_seq, double* best_score, int32_t* best_action,
                                  int32_t* step_actions, int32_t* cand, double* cand_score, float* obs, float* share_obs, float* rew,
                                  uint8_t* done, float* info, float* final_obs, void* stream) {
-  static const std::string w = "sdc_rollout_cem_groups_stats: ";
   const StatsArrays a = {stats, returns, counts, obs, share_obs, rew, done, info, final_obs};
-  if (stats_refused(w, h, n_steps, accumulate, a)) return -2;
-  if (!mpc) return fail_msg(w + "null mpc");
+  sdc_plan_objective obj;
+  int k_max = 0;
+  if (refused(sdc_rollout_cem_groups_stats_refused(call_facts(h), n_steps, mpc, objective, accumulate, a, plan_counts, plan_sums, diverged,
+                                                   probs, best_seq, best_score, best_action, step_actions, cand, cand_score, obj, k_max)))
+    return -2;
   const sdc_mpc_group_params m = *mpc;
   const sdc_cem_group_params c = m.cem;
-  const int H = m.horizon, N = h->cfg.n_envs;
-  if (mpc_loop_refused(w, H, m.warm_start, m.resume, m.resume_steps, m.idle_action)) return -2;
-  if (m.sync_first != 0 && m.sync_first != 1) return fail_msg(w + "sync_first = " + std::to_string(m.sync_first) + " outside {0, 1}");
-  if (m.sync_first && m.resume)
-    return fail_msg(w + "sync_first with resume (behind the sync the first planned decision starts fresh: nothing can be resumed)");
-  if (cem_iters_refused(w, c.n_iters, c.iter0) || cem_groups_refused(w, N, c) || cem_refit_refused(w, c.fixed_action, c.alpha, c.p_min))
-    return -2;
-  if (mpc_arrays_refused(w,
-                         {{"probs", probs, 8}, {"best_seq", best_seq, 4}, {"best_score", best_score, 8}, {"best_action", best_action, 4},
-                          {"step_actions", step_actions, 4}, {"cand", cand, 4}, {"cand_score", cand_score, 8}},
-                         {{"plan_counts", plan_counts, 4}, {"plan_sums", plan_sums, 16}, {"diverged", diverged, 4}}))
-    return -2;
-  sdc_plan_objective obj;
-  if (plan_objective_refused(w, objective, obj)) return -2;
-  // the steps the episode has left: behind a sync every replica stands where its group's first env stands
-  const int R = c.group_size, G = N / R;
-  int left0 = h->mirror.steps_to_terminal();
-  if (m.sync_first) {
-    int most = 0;
-    for (int e = 0; e < N; e += R) most = std::max(most, h->mirror.t_rel(e));
-    left0 = h->d.episode_steps - most;
-  }
-  if (stats_past_end_refused(w, n_steps, left0)) return -2;
-  if (!m.sync_first && groups_out_of_step_refused(w, h, R)) return -2;
+  const int N = h->cfg.n_envs, R = c.group_size, G = N / R;
 
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   SdcMpcGroupFold F = mpc_fold_plan<SdcMpcGroupFold>(N, (size_t)G, c.n_iters, best_score, best_action, plan_counts, plan_sums);
@@ -2650,7 +2160,7 @@ int sdc_rollout_cem_groups_stats(sdc_handle* h, int n_steps, const sdc_mpc_group
   Y.diverged = diverged;
 
   return mpc_steps(
-      w, h, n_steps, m, left0, accumulate, obj, a, SdcMpcStart{G, 0, 0, {}, probs, best_seq}, F,
+      h, n_steps, m, k_max, accumulate, obj, a, SdcMpcStart{G, 0, 0, {}, probs, best_seq}, F,
       sdc_mpc_group_fold_launch, "sdc_mpc_group_fold_kernel", step_actions, stream,
       [&] {
         if (!m.sync_first) return 0;

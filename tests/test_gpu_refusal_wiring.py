@@ -1,0 +1,220 @@
+"""sdc_capi.hip hands the right facts to the right rule in the right order: the refusals of tests/refusal_cases.py that a fresh engine
+can show (`wire`: no fact changed -- 8 envs, 96-step episodes, no auto-reset, reset once), made through the raw library calls, past the
+Python validators, and held to the same literals: return code -2, sdc_last_error() the full text, the engine's `record` state unchanged
+afterwards.  A refusal returns before any device work; every address is nevertheless a real one -- the table's made-up GOOD becomes the
+start of a device (or host) pool, its low bits kept -- so that a call that did get through would stay inside memory it may use."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from dc_rl_amd import _lib as L
+from tests import refusal_cases as RC
+
+pytestmark = pytest.mark.gpu
+POOL = 4 << 20
+OPTIONAL = ("policy_counts", "policy_sums", "plan_counts", "plan_sums", "diverged", "noise")      # (NULL unless a case gives them)
+
+
+class Rig:
+    """the engine's handle, the two pools, and the table's arguments as the raw calls take them"""
+
+    def __init__(self, eng):
+        import torch
+        self.eng, self.lib = eng, eng.lib
+        self.dev_pool = torch.zeros(POOL + 4096, dtype=torch.uint8, device="cuda")
+        self.host_pool = np.zeros(POOL + 4096, dtype=np.uint8)
+        self.dev = -(-self.dev_pool.data_ptr() // 4096) * 4096
+        self.host = -(-self.host_pool.ctypes.data // 4096) * 4096
+        self.keep = []
+
+    def _at(self, base, a, key):
+        v = a.get(key, 0 if key in OPTIONAL else RC.GOOD)
+        return None if v == 0 else base + (v - RC.GOOD)
+
+    def d(self, a, *keys):      # device arrays
+        return [self._at(self.dev, a, k) for k in keys]
+
+    def h(self, a, key, ctype=None):      # a host array the call would read or write
+        p = self._at(self.host, a, key)
+        return p if ctype is None or p is None else C.cast(C.c_void_p(p), C.POINTER(ctype))
+
+    def ints(self, a, key, default, ctype=C.c_int32, dtype=np.int32):      # a host list the rule reads
+        v = a.get(key, default)
+        if v is None:
+            return None
+        arr = np.ascontiguousarray(v, dtype=dtype)
+        self.keep.append(arr)
+        return arr.ctypes.data_as(C.POINTER(ctype))
+
+    def objective(self, a):
+        if not a.get("obj"):
+            return None
+        o = L.SdcPlanObjective()
+        o.reward_weight[:] = [1.0, 1.0, 1.0]
+        o.gamma, o.n_cols = a.get("gamma", 1.0), a.get("n_cols", 0)
+        for j, c in enumerate(a.get("col", [])[:8]):
+            o.col[j] = c
+        return C.byref(o)
+
+    def cem(self, a, c):
+        c.n_iters, c.iter0, c.n_elite = a.get("n_iters", 1), a.get("iter0", 0), a.get("n_elite", 1)
+        c.fixed_action[:] = a.get("fixed", [-1, -1, -1])
+        c.alpha, c.p_min = a.get("alpha", 0.0), a.get("p_min", 0.0)
+        if isinstance(c, L.SdcCemParams):
+            c.n_cand = a.get("n_cand", 2)
+        else:
+            c.group_size, c.group_base = a.get("group_size", 2), a.get("group_base", 0)
+        return c
+
+    def mpc(self, a, m):
+        if not a.get("mpc", 1):
+            return None
+        m.horizon, m.warm_start, m.resume, m.resume_steps = a.get("horizon", 1), a.get("warm_start", 0), a.get("resume", 0), a.get("resume_steps", 0)
+        m.idle_action[:] = a.get("idle", [0, 0, 0])
+        if isinstance(m, L.SdcMpcGroupParams):
+            m.sync_first = a.get("sync_first", 0)
+        self.cem(a, m.cem)
+        return C.byref(m)
+
+    def call(self, c):
+        """the case's raw call -> (return code, sdc_last_error())"""
+        a, lib, N = c.args, self.lib, RC.N
+        H = self.eng._h if c.facts.get("handle", 1) else None
+        e = c.entry
+        n_steps, acc = a.get("n_steps", 1), a.get("accumulate", 0)
+        step_out = self.d(a, "obs", "share_obs", "rew", "done", "info", "final_obs")
+        stats = self.d(a, "stats", "returns", "counts")
+        Z = [0] * N
+        if e == "sdc_set_tables":
+            rc = lib.sdc_set_tables(H, a.get("loc_id", 0), *[self.h(a, k, C.c_double) for k in ("W", "C", "T_", "WB")], a.get("n", 35040))
+        elif e == "sdc_set_dc_params":
+            rc = lib.sdc_set_dc_params(H, a.get("cfg_id", 0), C.byref(L.SdcDcParams()) if a.get("p", 1) else None)
+        elif e == "sdc_assign_envs":
+            rc = lib.sdc_assign_envs(H, self.ints(a, "loc_id", Z), self.ints(a, "cfg_id", Z), self.ints(a, "day_lo", Z), self.ints(a, "day_hi", [364] * N))
+        elif e == "sdc_reset":
+            o = L.SdcResetOverride()
+            o.day, o.hour, o.roll_days = self.ints(a, "day", Z), self.ints(a, "hour", Z), self.ints(a, "roll", Z)
+            for k in ("ci_min", "ci_max", "t_min", "t_max", "t_win", "wb_win", "noise"):
+                setattr(o, k, self.h(a, k, C.c_double))
+            mask = self.ints(a, "mask", None, C.c_uint8, np.uint8)
+            rc = lib.sdc_reset(H, mask, C.byref(o) if a.get("ovr") else None, *self.d(a, "obs", "share_obs"), None)
+        elif e == "sdc_step":
+            rc = lib.sdc_step(H, *self.d(a, "actions"), *step_out[:4], *step_out[4:], None)
+        elif e == "sdc_rollout":
+            rc = lib.sdc_rollout(H, n_steps, *self.d(a, "actions"), *step_out, *self.d(a, "actions_out"), None)
+        elif e == "sdc_set_actor":
+            p = L.SdcActorParams()
+            p.activation = a.get("activation", 0)
+            rc = lib.sdc_set_actor(H, a.get("slot", 0), C.byref(p) if a.get("p", 1) else None)
+        elif e == "sdc_rollout_actor":
+            rc = lib.sdc_rollout_actor(H, n_steps, 0, *step_out, *self.d(a, "actions_out", "logits_out"), None)
+        elif e == "sdc_profile_enable":
+            rc = lib.sdc_profile_enable(H, 0)
+        elif e == "sdc_profile_read":
+            rc = lib.sdc_profile_read(H, self.h(a, "out5", C.c_double), 0)
+        elif e in ("sdc_get_state", "sdc_set_state"):
+            field = a.get("field", "day")
+            ids = np.ascontiguousarray(a.get("ids", Z), dtype=np.int32)
+            if field == "record":
+                rec = np.zeros((N, 64), dtype=np.int32)
+                rec[:, 24] = ids
+                ids = rec
+            self.keep.append(ids)
+            buf = None if not a.get("buf", 1) else ids.ctypes.data if "ids" in a else self.host
+            rc = getattr(lib, e)(H, None if field is None else field.encode(), buf, a.get("bytes", 4 * N))
+        elif e == "sdc_clone_envs":
+            src, dst = a.get("src", [0]), a.get("dst", [1])
+            rc = lib.sdc_clone_envs(H, self.ints(a, "src", [0]), self.ints(a, "dst", [1]), a.get("n", len(src) if src is not None else 1), None, None, None)
+        elif e == "sdc_snapshot_envs":
+            envs = a.get("envs", [0])
+            rc = lib.sdc_snapshot_envs(H, self.ints(a, "envs", [0]), a.get("n", len(envs) if envs is not None else 1), *self.d(a, "rows"),
+                                       self.h(a, "manifest", C.c_int32), *self.d(a, "obs", "share_obs"), None)
+        elif e == "sdc_restore_envs":
+            envs = a.get("envs", [0])
+            rc = lib.sdc_restore_envs(H, self.ints(a, "rows_idx", [0]), self.ints(a, "envs", [0]), a.get("n", len(envs) if envs is not None else 1),
+                                      *self.d(a, "rows"), a.get("n_rows", 1), self.ints(a, "manifest", None), *self.d(a, "obs", "share_obs"), None)
+        elif e == "sdc_mark_envs":
+            envs = a.get("envs")
+            rc = lib.sdc_mark_envs(H, self.ints(a, "envs", None), a.get("n", len(envs) if envs is not None else N), a.get("max_steps", 1),
+                                   *self.d(a, "rows"), self.h(a, "manifest", C.c_int32), *self.d(a, "obs", "share_obs"), None)
+        elif e == "sdc_rewind_envs":
+            envs = a.get("envs")
+            rc = lib.sdc_rewind_envs(H, self.ints(a, "envs", None), a.get("n", len(envs) if envs is not None else N), *self.d(a, "rows"),
+                                     self.ints(a, "manifest", None), *self.d(a, "obs", "share_obs"), None)
+        elif e == "sdc_set_plan_forecast":
+            fc = L.SdcPlanForecast()
+            fc.mode[:] = a.get("mode", [0, 0, 0, 0])
+            fc.values_entries, fc.values = a.get("entries", 0), self.d(a, "values")[0]
+            rc = lib.sdc_set_plan_forecast(H, C.byref(fc) if a.get("fc", 1) else None)
+        elif e == "sdc_forecast_traces":
+            rc = lib.sdc_forecast_traces(H, a.get("n_entries", 1), a.get("truth", 0), *self.d(a, "out"), None)
+        elif e == "sdc_plan":
+            rc = lib.sdc_plan(H, a.get("n_cand", 1), n_steps, *self.d(a, "actions"), self.objective(a), None,
+                              *self.d(a, "score", "best", "best_action", "obs", "share_obs"), None)
+        elif e == "sdc_set_plan_terms":
+            t = L.SdcPlanTerms()
+            t.n_limits, t.n_terminal = a.get("n_limits", 0), a.get("n_terminal", 0)
+            for k in ("limit_col", "limit_side", "limit_bound", "limit_weight", "terminal_col", "terminal_weight"):
+                for j, v in enumerate(a.get(k, [])[:8]):
+                    getattr(t, k)[j] = v
+            rc = lib.sdc_set_plan_terms(H, C.byref(t) if a.get("terms", 1) else None)
+        elif e == "sdc_critic_values":
+            rc = lib.sdc_critic_values(H, *self.d(a, "share_obs"), a.get("n_rows", 1), *self.d(a, "values"), None)
+        elif e == "sdc_set_plan_critic":
+            rc = lib.sdc_set_plan_critic(H, a.get("weight", 0.0))
+        elif e == "sdc_plan_cem":
+            rc = lib.sdc_plan_cem(H, n_steps, C.byref(self.cem(a, L.SdcCemParams())) if a.get("cem", 1) else None, self.objective(a),
+                                  *self.d(a, "probs", "best_seq", "best_score", "best_action", "cand", "cand_score", "obs", "share_obs"), None)
+        elif e == "sdc_plan_cem_groups":
+            rc = lib.sdc_plan_cem_groups(H, n_steps, C.byref(self.cem(a, L.SdcCemGroupParams())) if a.get("cem", 1) else None, self.objective(a),
+                                         *self.d(a, "probs", "best_seq", "best_score", "best_action", "step_actions", "cand", "cand_score", "obs",
+                                                 "share_obs"), None)
+        elif e == "sdc_rollout_stats":
+            rc = lib.sdc_rollout_stats(H, n_steps, *self.d(a, "actions"), acc, *stats, *step_out, None)
+        elif e == "sdc_rollout_actor_stats":
+            rc = lib.sdc_rollout_actor_stats(H, n_steps, a.get("sample", 0), acc, *stats, *self.d(a, "policy_counts", "policy_sums"), *step_out, None)
+        elif e == "sdc_rollout_cem_stats":
+            rc = lib.sdc_rollout_cem_stats(H, n_steps, self.mpc(a, L.SdcMpcParams()), self.objective(a), acc, *stats,
+                                           *self.d(a, "plan_counts", "plan_sums", "probs", "best_seq", "best_score", "best_action", "cand", "cand_score"),
+                                           *step_out, None)
+        elif e == "sdc_rollout_cem_groups_stats":
+            rc = lib.sdc_rollout_cem_groups_stats(H, n_steps, self.mpc(a, L.SdcMpcGroupParams()), self.objective(a), acc, *stats,
+                                                  *self.d(a, "plan_counts", "plan_sums", "diverged", "probs", "best_seq", "best_score", "best_action",
+                                                          "step_actions", "cand", "cand_score"), *step_out, None)
+        else:
+            raise AssertionError(e)
+        return rc, self.lib.sdc_last_error().decode()
+
+
+def wired_cases():
+    return [c for c in RC.CASES if c.wire and c.text is not None]
+
+
+def make_engine():
+    """the table's default handle: 8 envs, 96-step episodes, no auto-reset, one location, one config, reset once"""
+    from tests.test_gpu_mark import _mk
+    eng = _mk(RC.N, cap=RC.HIST_CAP, ep=RC.T, auto_reset=False)
+    assert eng.config["n_locations"] == 1 and eng.config["n_dc_configs"] == 1 and eng.queue_stride == RC.QSTRIDE and eng.lw == RC.LW
+    return eng
+
+
+def test_every_reachable_refusal_of_the_table_with_its_code_and_text():
+    eng = make_engine()
+    try:
+        rig = Rig(eng)
+        before = eng.get_state("record")
+        cases = wired_cases()
+        assert {c.entry for c in cases} == set(RC.ENTRY_POINTS) and len(cases) >= 300
+        wrong = []
+        for c in cases:
+            rc, text = rig.call(c)
+            if (rc, text) != (-2, c.text):
+                wrong.append((RC.request_line(c), c.text, rc, text))
+        assert not wrong, wrong[:5]
+        assert np.array_equal(before, eng.get_state("record")) and eng.steps_to_episode_end() == RC.T
+        import torch
+        eng.step(torch.ones((RC.N, 3), dtype=torch.int32, device="cuda"))      # ... and the engine goes on as if nothing had been asked of it
+        assert eng.steps_to_episode_end() == RC.T - 1
+    finally:
+        eng.close()
