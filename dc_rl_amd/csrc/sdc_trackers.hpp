@@ -16,6 +16,8 @@
 //     moves across from one step to the next (the bounds move with the quartiles, a fraction of a key per step out
 //     in the tails).  However heavy a tail is, it is only ever a count and two sums.
 // Everything here is wave-uniform scalar work or one-wavefront vector work.
+// Held function by function on the device (tests/test_gpu_reward_functions.py): the three window forms, the refills, the rebuild,
+// clip_bounds and clipped_moments against a sorted-list NumPy model (tests/reward_model.py) on the branches episodes rarely reach.
 #pragma once
 #include "sdc_device.hpp"
 
@@ -172,7 +174,9 @@ __device__ __forceinline__ Bounds clip_bounds(const int n, unsigned a1, unsigned
   b.lb = qv1 - 1.5 * iqr;
   b.ub = qv3 + 1.5 * iqr;
   b.ctr = 0.5 * (qv1 + qv3);
-  const float lbf = (float)b.lb, ubf = (float)b.ub;
+  // (+-0 are two keys of one value: the lower bound's key starts from -0 and the upper bound's from +0, so that with a bound at zero
+  // klb is still the SMALLEST key whose value is >= lb and kub the smallest whose value is > ub; neither form folds without nsz)
+  const float lbf = -(0.0f - (float)b.lb), ubf = (float)b.ub + 0.0f;
   unsigned klb = f32_key(lbf) + (((double)lbf < b.lb) ? 1u : 0u);
   unsigned kub = f32_key(ubf) + (((double)ubf <= b.ub) ? 1u : 0u);
   klb = min(max(klb, 2u), KEY_NONE - 2u);

@@ -7,17 +7,8 @@ scheduling options included), so it holds the bits the library ships; __graft_en
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
-from dc_rl_amd import _lib as L
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "aux", "physics_probe.hip")
-OUT_DIR = os.path.join(HERE, "aux", "build")          # (git-ignored: build/)
-LIB_PATH = os.path.join(OUT_DIR, "libphysics_probe.so")
-BUILD_HINT = "python -c 'import __graft_entry__ as g; g.build()'   (or: python -c 'from tests import physics_probe as p; p.build()')"
+from tests.probe_build import OUT_DIR, ROOT, Probe                                 # (the build / staleness / load logic both probes share)
 
 # launcher -> (input rows, output rows); tests/aux/physics_probe.hip lists what each row is
 KERNELS = {
@@ -28,53 +19,21 @@ KERNELS = {
 KLIT, KLDS = 0, 1
 SOURCES = (("KLit", KLIT), ("KLds", KLDS))
 
-
-def build_command(out_path: str = LIB_PATH, flags=None):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = list(L.HIPCC_FLAGS if flags is None else flags)
-    return [hipcc] + flags + ["-I", L.CSRC, SRC, "-o", out_path]
+_PROBE = Probe("physics_probe", "physics probe")
+SRC, LIB_PATH, BUILD_HINT = _PROBE.src, _PROBE.lib_path, _PROBE.build_hint
+build_command, build = _PROBE.build_command, _PROBE.build
 
 
-def _deps():
-    return [SRC, os.path.abspath(L.__file__), os.path.join(ROOT, "include", "sustaindc_hip.h")] + \
-           [os.path.join(L.CSRC, f) for f in os.listdir(L.CSRC) if f.endswith(".hpp")]
-
-
-def build(force: bool = False, verbose: bool = False) -> str:
-    """hipcc (cross-compiles gfx950 without a GPU) -> tests/aux/build/libphysics_probe.so; a few seconds."""
-    if not force and os.path.exists(LIB_PATH) and os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in _deps()):
-        return LIB_PATH
-    os.makedirs(OUT_DIR, exist_ok=True)
-    tmp = LIB_PATH + f".{os.getpid()}.tmp"             # (several test workers may build at once: the rename is atomic)
-    cmd = build_command(tmp)
-    if verbose:
-        print(" ".join(cmd))
-    try:
-        subprocess.check_call(cmd, cwd=ROOT)
-        os.replace(tmp, LIB_PATH)
-    finally:
-        if os.path.exists(tmp):
-            os.remove(tmp)
-    return LIB_PATH
-
-
-_lib = None
+def _declare(lib):
+    for name in KERNELS:
+        fn = getattr(lib, "probe_" + name)
+        fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        fn.restype = C.c_int
 
 
 def load():
     """The loaded probe.  A missing probe is an error that names the build command: the GPU machine runs what build() made."""
-    global _lib
-    if _lib is None:
-        import torch  # noqa: F401  (maps PyTorch-ROCm's HIP runtime first, as dc_rl_amd._lib.load does)
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"the physics probe is not built: {LIB_PATH} is missing.  Run {BUILD_HINT}")
-        lib = C.CDLL(LIB_PATH)
-        for name in KERNELS:
-            fn = getattr(lib, "probe_" + name)
-            fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-            fn.restype = C.c_int
-        _lib = lib
-    return _lib
+    return _PROBE.load(_declare)
 
 
 def run(name: str, source: int, *rows):
