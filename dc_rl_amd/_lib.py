@@ -24,7 +24,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
            "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip", "sdc_plan_terms.hip",
-           "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip", "sdc_mpc_groups.hip", "sdc_critic.hip"]
+           "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip", "sdc_mpc_groups.hip", "sdc_critic.hip", "sdc_onpolicy.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
@@ -242,6 +242,7 @@ EXPORTS = [
     "sdc_set_plan_forecast", "sdc_get_plan_forecast", "sdc_forecast_traces", "sdc_rollout_actor_stats",
     "sdc_rollout_cem_stats", "sdc_rollout_cem_groups_stats",
     "sdc_set_critic", "sdc_critic_values", "sdc_set_plan_critic", "sdc_get_plan_critic",
+    "sdc_gae", "sdc_action_log_probs",
 ]
 
 
@@ -417,6 +418,8 @@ def load():
     L.sdc_critic_values.argtypes = [vp, fp, C.c_longlong, fp, vp]
     L.sdc_set_plan_critic.argtypes = [vp, C.c_double]
     L.sdc_get_plan_critic.argtypes = [vp, dp]
+    L.sdc_gae.argtypes = [vp, C.c_int, fp, C.c_int, vp, vp, fp, C.c_double, C.c_double, C.c_int, fp, fp, fp, fp, vp, vp]
+    L.sdc_action_log_probs.argtypes = [vp, C.c_int, vp, fp, fp, fp, vp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

@@ -39,6 +39,7 @@
 #include "sdc_forecast.hpp"
 #include "sdc_stats.hpp"
 #include "sdc_policy_stats.hpp"
+#include "sdc_onpolicy.hpp"
 #include "sdc_mpc.hpp"
 #include "sdc_mpc_groups.hpp"
 #include "sdc_mpc_schedule.hpp"
@@ -165,6 +166,8 @@ struct sdc_handle {
   // sdc_rollout_actor_stats: a chunk's actions and logits (sdc_policy_stats.hpp), grown on demand and freed with the handle
   unsigned char* policy_out = nullptr;
   size_t policy_out_bytes = 0;
+  // sdc_gae: every env's sum and sum of squares of its advantages [N][2] (sdc_onpolicy.hpp), allocated on first use
+  double* adv_part = nullptr;
 };
 
 namespace {
@@ -1762,6 +1765,51 @@ int sdc_critic_values(sdc_handle* h, const float* share_obs, long long n_rows, f
   h->last_step_kernel = "sdc_critic_values_kernel";
   return launched("sdc_critic_values_kernel",
                   sdc_critic_values_launch(SdcCriticValues{h->critic_dev, share_obs, n_rows, values}, reinterpret_cast<hipStream_t>(stream)));
+}
+
+// ---- the on-policy batch (sdc_onpolicy.hip) ------------------------------------------------------------------------------------------------
+// The contract and the arithmetic: include/sustaindc_hip.h THE ON-POLICY BATCH; the kernels' plans: sdc_onpolicy.hpp.
+int sdc_gae(sdc_handle* h, int n_steps, const float* rew, int reward_agent, const uint8_t* done, const uint8_t* first_done,
+            const float* values, double gamma, double gae_lambda, int use_gae, float* returns, float* advantages, float* masks,
+            float* value_preds, double* moments, void* stream) {
+  if (refused(sdc_gae_refused(call_facts(h), n_steps, rew, reward_agent, done, values, gamma, gae_lambda, use_gae, returns, advantages,
+                              masks, value_preds, moments)))
+    return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int N = h->cfg.n_envs;
+  if (!h->adv_part && dev_alloc(h, &h->adv_part, (size_t)N * 2, false) != 0) return -1;
+  SdcGae P;
+  std::memset(&P, 0, sizeof(P));
+  P.n_envs = N;
+  P.steps = n_steps;
+  P.reward_agent = reward_agent;
+  P.use_gae = use_gae;
+  P.g = (float)gamma;
+  P.c = (float)(gamma * gae_lambda);
+  P.rew = rew;
+  P.done = done;
+  P.first_done = first_done;
+  P.values = values;
+  P.returns = returns;
+  P.advantages = advantages;
+  P.masks = masks;
+  P.value_preds = value_preds;
+  P.critic = h->critic_dev;
+  P.adv_part = h->adv_part;
+  if (const int rc = launched("sdc_gae_kernel", sdc_gae_launch(P, st))) return rc;
+  if (!moments) return 0;
+  return launched("sdc_adv_moments_kernel",
+                  sdc_adv_moments_launch(SdcAdvMoments{N, (double)n_steps * (double)N, h->adv_part, moments}, st));
+}
+
+int sdc_action_log_probs(sdc_handle* h, int n_steps, const int32_t* actions, const float* logits, float* log_probs, float* entropy,
+                         void* stream) {
+  if (refused(sdc_action_log_probs_refused(call_facts(h), n_steps, actions, logits, log_probs, entropy))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  const long long n = (long long)n_steps * h->cfg.n_envs * SDC_N_AGENTS;
+  return launched("sdc_action_logp_kernel",
+                  sdc_action_logp_launch(SdcActionLogp{n, actions, logits, log_probs, entropy}, reinterpret_cast<hipStream_t>(stream)));
 }
 
 int sdc_set_plan_critic(sdc_handle* h, double weight) {

@@ -554,6 +554,36 @@ static inline SdcMsg sdc_set_plan_critic_refused(const SdcCallFacts& f, const do
   return std::nullopt;
 }
 
+// ---- the on-policy batch ------------------------------------------------------------------------------------------------------------------
+// (pure functions of their arrays: nothing about the engine's episode is asked; their texts are held by tests/test_onpolicy_abi.py)
+static inline SdcMsg sdc_gae_refused(const SdcCallFacts& f, const int n_steps, const float* rew, const int reward_agent, const uint8_t* done,
+                                     const float* values, const double gamma, const double gae_lambda, const int use_gae, const float* returns,
+                                     const float* advantages, const float* masks, const float* value_preds, const double* moments) {
+  static const std::string w = "sdc_gae: ";
+  if (!f.handle) return w + "null handle";
+  if (n_steps < 1) return w + "n_steps = " + std::to_string(n_steps) + " must be positive";
+  if (!rew || !done || !values || !returns || !advantages || !masks)
+    return w + "null array (rew, done, values, returns, advantages and masks are required)";
+  if ((sdc_addr_bits(rew, values, returns, advantages, masks, value_preds) & 3u) != 0)
+    return w + "rew / values / returns / advantages / masks / value_preds not dword-aligned";
+  if ((sdc_addr_bits(moments) & 15u) != 0) return w + "moments not 16-byte aligned";
+  if (reward_agent < 0 || reward_agent > 2) return w + "reward_agent = " + std::to_string(reward_agent) + " outside [0, 2]";
+  if (use_gae != 0 && use_gae != 1) return w + "use_gae = " + std::to_string(use_gae) + " outside {0, 1}";
+  if (!(gamma >= 0.0 && gamma <= 1.0)) return w + "gamma = " + std::to_string(gamma) + " outside [0, 1]";
+  if (!(gae_lambda >= 0.0 && gae_lambda <= 1.0)) return w + "gae_lambda = " + std::to_string(gae_lambda) + " outside [0, 1]";
+  if (value_preds && !f.critic_set) return w + "value_preds asked for while no critic is set (sdc_set_critic first: its scale and shift)";
+  return std::nullopt;
+}
+static inline SdcMsg sdc_action_log_probs_refused(const SdcCallFacts& f, const int n_steps, const int32_t* actions, const float* logits,
+                                                  const float* log_probs, const float* entropy) {
+  static const std::string w = "sdc_action_log_probs: ";
+  if (!f.handle) return w + "null handle";
+  if (n_steps < 1) return w + "n_steps = " + std::to_string(n_steps) + " must be positive";
+  if (!actions || !logits || !log_probs) return w + "null array (actions, logits and log_probs are required)";
+  if ((sdc_addr_bits(actions, logits, log_probs, entropy) & 3u) != 0) return w + "actions / logits / log_probs / entropy not dword-aligned";
+  return std::nullopt;
+}
+
 // ---- the cross-entropy planners -------------------------------------------------------------------------------------------------------------
 // The parameter ranges sdc_plan_cem and sdc_plan_cem_groups refuse alike.  The callers run them in their own order.
 static inline SdcMsg sdc_cem_iters_refused(const std::string& w, const int n_iters, const int iter0) {

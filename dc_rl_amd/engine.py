@@ -277,6 +277,49 @@ class PlanStats:
         return out
 
 
+class GAEResult:
+    """What SdcEngine.gae hands back: `returns`, `advantages` fp32 [T, N]; `masks` fp32 [T+1, N]; `value_preds` fp32 [T+1, N] or None;
+    `moments` fp64 [2] (the advantages' mean and population standard deviation) or None"""
+    __slots__ = ("returns", "advantages", "masks", "value_preds", "moments")
+
+    def __init__(self, returns, advantages, masks, value_preds, moments):
+        self.returns, self.advantages, self.masks, self.value_preds, self.moments = returns, advantages, masks, value_preds, moments
+
+
+class OnPolicyBatch:
+    """One collected on-policy training batch on the device (SdcEngine.collect), T steps of N envs -- the reference's actor and
+    critic buffers after `compute`:
+      obs [T+1,N,3,26], share_obs [T+1,N,29]      row 0: what the engine held before the call, row t+1: after step t
+      actions [T,N,3] int32, logits [T,N,3,3], action_log_probs [T,N,3], entropy [T,N,3]
+      rewards [T,N,3], dones [T,N] uint8, masks [T+1,N] (masks[t+1] = 1 - dones[t]; masks[0] from the call's first_done)
+      values [T+1,N] (the critic's, denormalised), value_preds [T+1,N] (normalised with the critic's ValueNorm: what the clipped
+      value loss keeps), returns [T,N], advantages [T,N], adv_mean, adv_std (0-dim fp64), last_done [N] uint8 (the next call's
+      first_done)."""
+    FIELDS = ("obs", "share_obs", "actions", "logits", "action_log_probs", "entropy", "rewards", "dones", "masks", "values", "value_preds",
+              "returns", "advantages", "adv_mean", "adv_std", "last_done")
+    __slots__ = FIELDS
+
+    def __init__(self, **fields):
+        for k in self.FIELDS:
+            setattr(self, k, fields[k])
+
+    @property
+    def n_steps(self) -> int:
+        return int(self.actions.shape[0])
+
+    def normalized_advantages(self):
+        """(advantages - adv_mean) / (adv_std + 1e-5), fp32 [T, N]: the reference's normalisation (happo.py) in one torch op"""
+        t = self.advantages
+        return ((t - self.adv_mean) / (self.adv_std + 1e-5)).to(t.dtype)
+
+    def flat(self) -> dict:
+        """{name: a [T*N, ...] view} of every per-step field, rows t < T of the [T+1] ones -- what a minibatch sampler indexes"""
+        T = self.n_steps
+        per_step = ("obs", "share_obs", "actions", "logits", "action_log_probs", "entropy", "rewards", "dones", "masks", "values",
+                    "value_preds", "returns", "advantages")
+        return {k: getattr(self, k)[:T].flatten(0, 1) for k in per_step}
+
+
 class MPCCarry:
     """What `rollout_cem_stats` leaves of the planner's state, on the engine's device: `probs` float64 [H, N, 3, 3] and `best_seq` int32
     [H, N, 3], the arrays of the call (a caller's own are the same tensors), whose first `steps` steps hold the last planned decision's
@@ -726,12 +769,16 @@ class SdcEngine:
         out = self._rollout_outputs(K)
         acts = t.empty((K, N, 3), dtype=t.int32, device=self.device)
         logits = t.empty((K, N, 3, 3), dtype=t.float32, device=self.device) if want_logits else None
-        self._call(self.lib.sdc_rollout_actor, K, 1 if sample else 0, *[_p(x) for x in out], _p(self.final_obs), _p(acts), _p(logits),
-                   self._stream(), wrote=out + (acts, logits))
-        self._views_follow(*out)
+        self._rollout_actor_into(K, sample, out, acts, logits)
         if want_values:
             return out + (acts, logits, self.critic_values(out[1]))
         return out + (acts, logits)
+
+    def _rollout_actor_into(self, K, sample, out, acts, logits):
+        """sdc_rollout_actor of K steps into `out` (_rollout_outputs' order), `acts` and `logits` (or None): tensors or slices of [K, ...]"""
+        self._call(self.lib.sdc_rollout_actor, K, 1 if sample else 0, *[_p(x) for x in out], _p(self.final_obs), _p(acts), _p(logits),
+                   self._stream(), wrote=out + (acts, logits))
+        self._views_follow(*out)
 
     # ------------------------------------------------------------------ the critic: values, and the planners' terminal value
     def set_critic(self, params, value_norm=None, activation="tanh"):
@@ -778,6 +825,92 @@ class SdcEngine:
         w = C.c_double()
         self._call(self.lib.sdc_get_plan_critic, C.byref(w), refuses=True)
         return w.value
+
+    # ------------------------------------------------------------------ the on-policy batch: log-probs, GAE, collect
+    def action_log_probs(self, actions, logits, want_entropy: bool = True):
+        """The log-probability of every action played and the entropy of its distribution (sdc_action_log_probs: one launch,
+        stream-ordered; fp64 arithmetic rounded once to fp32, as rollout_actor_stats' sums): `actions` int32 [T, N, 3] and `logits`
+        fp32 [T, N, 3, 3], contiguous on this engine's device -> (log_probs [T, N, 3], entropy [T, N, 3] or None)."""
+        t, who, N = self.torch, "action_log_probs", self.n_envs
+        A.device_tensor(actions, who, "actions", t.int32, (A.SOME, N, 3), "(T, n_envs, 3)", self.device)
+        T = int(actions.shape[0])
+        A.device_tensor(logits, who, "logits", t.float32, (T, N, 3, 3), "(T, n_envs, 3, 3)", self.device)
+        logp = t.empty((T, N, 3), dtype=t.float32, device=self.device)
+        ent = t.empty((T, N, 3), dtype=t.float32, device=self.device) if want_entropy else None
+        self._behind_torch_stream()
+        self._call(self.lib.sdc_action_log_probs, T, _p(actions), _p(logits), _p(logp), _p(ent), self._stream(), refuses=True,
+                   wrote=(actions, logits, logp, ent))
+        return logp, ent
+
+    def gae(self, rew, done, values, gamma: float = 0.99, gae_lambda: float = 0.95, use_gae: bool = True, reward_agent: int = 0,
+            first_done=None, want_value_preds: bool = False, want_moments: bool = True) -> GAEResult:
+        """Returns, advantages and masks of a collected rollout (sdc_gae: the reference's compute_returns in its own fp32 order, one
+        lane per env, stream-ordered): `rew` fp32 [T, N, 3] (column `reward_agent` is read), `done` uint8 [T, N], `values` fp32
+        [T+1, N] (denormalised; row T the bootstrap), `first_done` uint8 [N] or None, all contiguous on this engine's device.
+        `want_value_preds`: also (values - shift) / scale with the critic's (set_critic) ValueNorm; `want_moments`: also the advantages'
+        mean and population standard deviation in fp64.  ValueError for another tensor and for what the library refuses (gamma or
+        gae_lambda outside [0, 1], reward_agent outside 0..2, value_preds before set_critic)."""
+        t, who, N = self.torch, "gae", self.n_envs
+        A.device_tensor(rew, who, "rew", t.float32, (A.SOME, N, 3), "(T, n_envs, 3)", self.device)
+        T = int(rew.shape[0])
+        A.device_tensor(done, who, "done", t.uint8, (T, N), "(T, n_envs)", self.device)
+        A.device_tensor(values, who, "values", t.float32, (T + 1, N), "(T + 1, n_envs)", self.device)
+        if first_done is not None:
+            A.device_tensor(first_done, who, "first_done", t.uint8, (N,), "(n_envs,)", self.device)
+        new = lambda rows, dtype=t.float32: t.empty((rows, N), dtype=dtype, device=self.device)
+        res = GAEResult(new(T), new(T), new(T + 1), new(T + 1) if want_value_preds else None,
+                        t.empty(2, dtype=t.float64, device=self.device) if want_moments else None)
+        self._behind_torch_stream()
+        self._call(self.lib.sdc_gae, T, _p(rew), int(reward_agent), _p(done), _p(first_done), _p(values), float(gamma), float(gae_lambda),
+                   int(use_gae), _p(res.returns), _p(res.advantages), _p(res.masks), _p(res.value_preds), _p(res.moments), self._stream(),
+                   refuses=True, wrote=(rew, done, first_done, values, res.returns, res.advantages, res.masks, res.value_preds, res.moments))
+        return res
+
+    def collect(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, sample: bool = True, use_gae: bool = True,
+                reward_agent: int = 0, first_done=None) -> OnPolicyBatch:
+        """The collection phase of the reference's on-policy runner, on the device: `n_steps` env-steps played by the three actors
+        (set_actor; `sample` as rollout_actor's) -> an OnPolicyBatch.  The batch's tensors are allocated once; the steps run as
+        `rollout_actor` launches of steps_to_episode_end() steps at most, each into its slice of them, so n_steps may cross episode
+        ends under auto-reset (the row after a done step is then the new episode's observation); then one `critic_values` launch over
+        all (T+1) N share_obs rows, `action_log_probs`, and `gae` with the critic's value predictions and the moments.  Row 0 of obs /
+        share_obs is what the engine held before the call; `first_done`: the last_done of the batch before (None: masks[0] = 1).
+        ValueError before anything is launched: an actor or the critic missing, no episode running (no reset yet, or auto_reset off and
+        the episode over), n_steps < 1, auto_reset off and n_steps past the episode's end."""
+        t, N, T = self.torch, self.n_envs, int(n_steps)
+        if T < 1:
+            raise ValueError(f"collect: n_steps = {n_steps} must be positive")
+        if len(self._actors) < 3:
+            raise ValueError("collect: set_actor all three agents first")
+        if self._critic is None:
+            raise ValueError("collect: set_critic first")
+        left = self.steps_to_episode_end()
+        if left <= 0:
+            raise ValueError("collect: no episode is running: call reset() first")
+        if not self.config["auto_reset"] and T > left:
+            raise ValueError(f"collect: n_steps = {T} would run past the end of an episode ({left} steps left; auto_reset is off)")
+        if first_done is not None:
+            A.device_tensor(first_done, "collect", "first_done", t.uint8, (N,), "(n_envs,)", self.device)
+        new = lambda rows, shape=(), dtype=t.float32: t.empty((rows, N) + shape, dtype=dtype, device=self.device)
+        obs, share = new(T + 1, (L.N_AGENTS, L.OBS_PAD)), new(T + 1, (L.SHARE_OBS_DIM,))
+        rew, done = new(T, (L.N_AGENTS,)), new(T, (), t.uint8)
+        acts, logits = new(T, (3,), t.int32), new(T, (3, 3))
+        info = new(min(T, self.episode_steps), (L.INFO_DIM,))      # (the rollouts' info rows, one launch's at a time: not part of the batch)
+        obs[0].copy_(self.obs)
+        share[0].copy_(self.share_obs)
+        self._behind_torch_stream()
+        k = 0
+        while k < T:
+            K = min(T - k, self.steps_to_episode_end())
+            cut = lambda x: x[k:k + K]
+            self._rollout_actor_into(K, sample, (obs[1 + k:1 + k + K], share[1 + k:1 + k + K], cut(rew), cut(done), info[:K]),
+                                     cut(acts), cut(logits))
+            k += K
+        values = self.critic_values(share)
+        logp, ent = self.action_log_probs(acts, logits)
+        g = self.gae(rew, done, values, gamma, gae_lambda, use_gae, reward_agent, first_done, want_value_preds=True)
+        return OnPolicyBatch(obs=obs, share_obs=share, actions=acts, logits=logits, action_log_probs=logp, entropy=ent, rewards=rew,
+                             dones=done, masks=g.masks, values=values, value_preds=g.value_preds, returns=g.returns,
+                             advantages=g.advantages, adv_mean=g.moments[0], adv_std=g.moments[1], last_done=done[T - 1])
 
     # ------------------------------------------------------------------ state access (parity injection / checkpoint)
     def _state_array(self, name):

@@ -717,6 +717,23 @@ class SustainDCVecEnv(ShareVecEnv):
         self._ready("rollout_actor_stats")
         return self._stats_done(self.engine.rollout_actor_stats(n_steps, sample=sample, into=into, policy_stats=policy_stats))
 
+    def action_log_probs(self, actions, logits, want_entropy=True):
+        """Log-probabilities and entropies of played actions from their logits, engine layout [T, num_envs, 3] / [T, num_envs, 3, 3]
+        (SdcEngine.action_log_probs)"""
+        return self.engine.action_log_probs(actions, logits, want_entropy)
+
+    def gae(self, rew, done, values, *args, **kw):
+        """Returns, advantages and masks of a collected rollout (SdcEngine.gae, which documents the arguments and the result)"""
+        return self.engine.gae(rew, done, values, *args, **kw)
+
+    def collect(self, n_steps, *args, **kw):
+        """An on-policy training batch of n_steps env-steps played by the three actors (SdcEngine.collect, which documents the arguments
+        and the OnPolicyBatch), in the engine's layout: all three agents.  The envs move as under n_steps calls of step(); actions
+        handed to step_async and not yet stepped are dropped; the logger accumulator (accumulate_logger_sums) is left alone, as by
+        rollout_stats.  ValueError for what the engine refuses."""
+        self._ready("collect")
+        return self._stats_done(self.engine.collect(n_steps, *args, **kw))
+
     def rollout_cem_stats(self, n_steps, horizon, n_iters, n_candidates, n_elite, **kw):
         """n_steps env-steps planned by the cross-entropy method inside the library, reduced on the device to an EpisodeStats with a
         PlanStats (SdcEngine.rollout_cem_stats, which documents the arguments and the result; `probs` / `best_seq` are the engine's,

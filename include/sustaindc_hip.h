@@ -606,6 +606,53 @@ int sdc_critic_values(sdc_handle* h, const float* share_obs, long long n_rows, f
 int sdc_set_plan_critic(sdc_handle* h, double weight);
 int sdc_get_plan_critic(const sdc_handle* h, double* weight);
 
+/* THE ON-POLICY BATCH.  replaces: what the reference's on-policy runners build on the host, in NumPy, from a collected rollout
+ * (harl/runners/on_policy_base_runner.py insert / compute, harl/common/buffers/on_policy_critic_buffer_ep.py compute_returns -- a Python
+ * loop of episode_length iterations --, harl/runners/on_policy_ha_runner.py and harl/algorithms/actors/happo.py for the advantages and
+ * their normalisation, the actors' evaluate_actions for the log-probabilities).  Both calls are pure functions of their arrays, all
+ * device memory, N = the handle's n_envs, T = n_steps: they read no env state and move nothing in the engine; each is ordered on
+ * `stream` with no synchronisation (sdc_gae's [N][2] fp64 partial sums are a buffer of the handle's, allocated on first use).
+ * sdc_gae: the backward pass of compute_returns for the EP state type, one launch of sdc_gae_kernel (one lane per env) and, when
+ * `moments` is given, one single-workgroup launch of sdc_adv_moments_kernel behind it (csrc/sdc_onpolicy.hip).
+ *   rew [T][N][3] fp32, of which column reward_agent is read (the reference feeds rewards[:, 0]);  done [T][N] uint8;
+ *   first_done [N] uint8 or NULL: the done flags of the step before the batch's first (NULL: none was done);
+ *   values [T+1][N] fp32: the critic's DENORMALISED values of the T+1 share_obs rows, as sdc_critic_values gives them with a ValueNorm
+ *   folded in; row T is the bootstrap.
+ * Everything is fp32, no fused multiply-add, in the reference's order of operations:
+ *     g = (float)gamma;  c = (float)(gamma * gae_lambda)        // the product in double, rounded once: NumPy's weak Python scalars
+ *   for t = T-1 .. 0, per env n:
+ *     m = done[t][n] ? 0.0f : 1.0f                              // the reference's masks[t + 1]
+ *     use_gae:   delta = (r + (g * V[t+1]) * m) - V[t];   gae = delta + (c * m) * gae;   returns[t] = gae + V[t]        (gae starts at 0)
+ *     otherwise: ret = (ret * g) * m + r   (ret starts at V[T]);   returns[t] = ret
+ *     advantages[t] = returns[t] - V[t]
+ * (use_proper_time_limits makes no difference: the reference sets bad_masks nowhere, they are all ones.)
+ *   returns [T][N], advantages [T][N]: written once per env and step;
+ *   masks [T+1][N] fp32: masks[0][n] = first_done && first_done[n] ? 0 : 1, masks[t+1][n] = m;
+ *   value_preds [T+1][N] fp32 or NULL: (V - shift) / scale in fp32 with the scale and shift of the critic set on the handle (the
+ *     ValueNorm folded into it): the normalised predictions the reference's clipped value loss keeps in its buffer, RECOMPUTED from the
+ *     denormalised values -- within a few ulp of, not the bits of, the network's raw output;
+ *   moments [2] fp64, 16-byte aligned, or NULL (no second launch): the mean of the T N advantages and their population standard
+ *     deviation sqrt(max(E[x^2] - mean^2, 0)), E[x^2] = (sum of squares) / (T N), mean = sum / (T N) -- the reference's nanmean / nanstd
+ *     where all agents finish together and active_masks is all ones.  Per env the sum of (double)a and of (double)a * (double)a over
+ *     its advantages in the walk's order t = T-1 .. 0; then with B = 256 partial pair l the sum over envs l, l + B, l + 2 B, ... in that
+ *     order, then partial i += partial i + half for half = B/2 .. 1: a fixed order, no atomics, the same bits on every run.
+ * Refused (-2 and a message, nothing enqueued): a null handle; n_steps < 1; a null rew, done, values, returns, advantages or masks; rew,
+ * values, returns, advantages, masks or value_preds not dword-aligned; moments not 16-byte aligned; reward_agent outside 0 .. 2; use_gae
+ * outside {0, 1}; gamma or gae_lambda not finite or outside [0, 1]; value_preds given while no critic is set.
+ * sdc_action_log_probs: one launch of sdc_action_logp_kernel, one lane per (step, env, agent).  With j = actions[t][n][a] (an action
+ * outside 0 .. 2 is read as 2) and l0, l1, l2 = logits[t][n][a][0..2], in sdc_rollout_actor_stats' arithmetic, word for word:
+ *     m = max(l0, l1, l2) in fp32;   z_i = (double)l_i - (double)m;   e_i = exp(z_i);   s = (e0 + e1) + e2;   lse = log(s)
+ *     lp_i = z_i - lse;   p_i = e_i / s
+ *     log_probs[t][n][a] = (float)lp_j;   entropy[t][n][a] = (float)(-((p0 * lp0 + p1 * lp1) + p2 * lp2))
+ * fp64 without fused multiply-adds, each result rounded once to fp32.  actions [T][N][3] int32, logits [T][N][3][3] fp32, log_probs and
+ * entropy [T][N][3] fp32; entropy may be NULL.  Refused: a null handle; n_steps < 1; a null actions, logits or log_probs; an array that
+ * is not dword-aligned. */
+int sdc_gae(sdc_handle* h, int n_steps, const float* rew, int reward_agent, const uint8_t* done, const uint8_t* first_done,
+            const float* values, double gamma, double gae_lambda, int use_gae, float* returns, float* advantages, float* masks,
+            float* value_preds, double* moments, void* stream);
+int sdc_action_log_probs(sdc_handle* h, int n_steps, const int32_t* actions, const float* logits, float* log_probs, float* entropy,
+                         void* stream);
+
 /* PLAN FORECAST: what the plan calls' rollouts believe the traces of the next n_steps steps are.  Without one a plan call's rollouts
  * read the episode's own feature rows -- the real workload, carbon intensity, dry bulb (with the weather noise the episode drew) and wet
  * bulb of the steps ahead: perfect foresight, an oracle bound.  A forecast is host state of the handle: sdc_set_plan_forecast copies the
