@@ -143,7 +143,9 @@ class ProductionRig:
 
     def __init__(self, N, mapping, debug_flags=0, mixed=False, episode_steps=120, seed=77, n_random=56,
                  reward_method=(0, 0, 0), policy=(0, 0, 0), trim_and_respond_limit=27.0, env_index_base=0, dc_files=None,
-                 oracles=True, hist_cap=CAP):
+                 oracles=True, hist_cap=CAP, sample=None, queue_max_len=None, day_range=None):
+        """sample: the envs to hold to the oracle, instead of the geometry's (`sample_envs`); queue_max_len: the engine's and the
+        oracles' (None: their default, 1000); day_range: (first, last) start day of every env (None: the fortnight around 1 July)."""
         self.N, self.steps, self.seed, self.env_index_base = N, episode_steps, seed, env_index_base
         self.geom = GEOMETRY[mapping]
         self.cap = hist_cap
@@ -159,14 +161,16 @@ class ProductionRig:
         self.engine_kw = dict(episode_steps=episode_steps, auto_reset=True, seed=seed, debug_flags=debug_flags,
                               n_locations=len(locs), n_dc_configs=len(combos), reward_method=reward_method, policy=policy,
                               trim_and_respond_limit=trim_and_respond_limit, env_index_base=env_index_base, hist_cap=hist_cap)
+        if queue_max_len is not None:
+            self.engine_kw["queue_max_len"] = queue_max_len
         e = np.arange(N)
         # BASELINE configs[3]: the rack count follows env_id % 3; the location changes every three envs
         self.loc_id = ((e // len(files)) % len(locs)).astype(np.int32)
         self.cfg_id = (self.loc_id * len(files) + e % len(files)).astype(np.int32)
         init_day = traces.get_init_day(6)
-        self.day_lo, self.day_hi = init_day - 7, init_day + 7
+        self.day_lo, self.day_hi = (init_day - 7, init_day + 7) if day_range is None else day_range
         eng = self.eng = self.make_engine()
-        self.sample = sample_envs(N, self.geom, rng, n_random)
+        self.sample = sample_envs(N, self.geom, rng, n_random) if sample is None else sorted(int(i) for i in sample)
         # steady-state history: every ring full, write positions spread, duplicates included -- generated in place in the buffer
         # set_state hands to the library (no second host copy); only the sampled envs' rings are kept, for their oracles
         hist = np.empty((N, eng.hist_stride), np.float32)
@@ -180,6 +184,8 @@ class ProductionRig:
         self.orcs = {}
         for i in vals:
             p = dict(self.params[self.cfg_id[i]], reward_method=tuple(int(m) for m in reward_method))
+            if queue_max_len is not None:
+                p["queue_max_len"] = queue_max_len
             o = po.OracleEnv(G.oracle_params_from_dict(p))
             o.e.stpt = float(p["init_setpoint"])
             o.e.hist_len = CAP

@@ -87,17 +87,27 @@ def device_normals(seed, env_global, episode, n=TL):
     return out.reshape(-1)[:n]
 
 
-def device_reset_expected(tables, seed, env_global, episode, day_lo, day_hi, episode_steps, noise_std=0.75,
-                          noise_weight=0.02, max_roll_days=14):
-    """Everything sdc_reset_kernel derives for one env: day, hour, roll, cursor, t_win / wb_win [episode_steps + 18],
-    t_min / t_den, ci_min / ci_den."""
+def device_start(seed, env_global, episode, day_lo, day_hi, episode_steps, max_roll_days=14):
+    """-> (day, hour, roll, cursor) of one env's reset: the draws, then the year-end fence"""
     day, hour, roll = (int(v) for v in device_draws(seed, env_global, episode, day_lo, day_hi, max_roll_days))
     last_ok = TL - 1 - (episode_steps + 17)            # year-end fence (csrc/sdc_reset.hip)
     if day * 96 + hour * 4 > last_ok:
         c = max(last_ok, 0)
         day, hour = c // 96, (c % 96) // 4
-    c0 = day * 96 + hour * 4
-    nz = device_normals(seed, env_global, episode).astype(np.float64)
+    return day, hour, roll, day * 96 + hour * 4
+
+
+def device_cursor(seed, env_global, episode, day_lo, day_hi, episode_steps):
+    """The trace-table index the env's episode starts at (no weather: cheap enough for every env of a batch)"""
+    return device_start(seed, env_global, episode, day_lo, day_hi, episode_steps)[3]
+
+
+def device_reset_expected(tables, seed, env_global, episode, day_lo, day_hi, episode_steps, noise_std=0.75,
+                          noise_weight=0.02, max_roll_days=14):
+    """Everything sdc_reset_kernel derives for one env: day, hour, roll, cursor, t_win / wb_win [episode_steps + 18],
+    t_min / t_den, ci_min / ci_den."""
+    day, hour, roll, c0 = device_start(seed, env_global, episode, day_lo, day_hi, episode_steps, max_roll_days)
+    nz =device_normals(seed, env_global, episode).astype(np.float64)
     walk = np.cumsum(noise_weight * nz)
     # the device scales by noise_std / std (one division per reset) and accumulates the walk with fused multiply-adds:
     # the same values to within fp64 rounding (~1e-15), far inside the 2e-6 C of its fp32 transcendentals

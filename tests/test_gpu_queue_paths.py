@@ -2,19 +2,27 @@
 the new oldest task among the 32 queue-table entries from the old one on (requested with the step's inputs when the
 action can pop tasks) and falls back to a 32-ary search over the table when it moved further -- long idle gaps between
 bursts of deferred tasks, overdue tasks popped under an action that is not "process", queues that run empty and refill.
-Step by step against the fp64 CPU oracle (1e-5, verify mode on); the info block carries the queue statistics."""
+Step by step against the fp64 CPU oracle (1e-5, verify mode on); the info block carries the queue statistics.  Which steps moved the
+oldest task by more than the 32 prefetched entries with the queue NON-EMPTY afterwards is counted by tests/queue_model.py (a deque
+on the test's own windows and actions): 12 such moves, all from the last two envs (the first fourteen give none: their far jumps of
+the oldest age are queues that ran empty).  tests/test_gpu_queue_mappings.py has the same paths on every step mapping."""
 import numpy as np
 import pytest
 
 from tests import gpu_helpers as G
 from tests import parity_util as P
+from tests import queue_cases as QC
+from tests import queue_model as QM
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
 
 
 def _ls_script(env, t):
-    """defer bursts separated by idle gaps of different lengths per env, then long processing runs"""
+    """defer bursts separated by idle gaps of different lengths per env, then long processing runs; the last two envs sparse
+    bursts and 20-step blocks (tests/queue_cases.py patterns 2 and 9): "process" reaches the next burst across an idle gap"""
+    if env >= 14:
+        return QC.pattern(2 if env == 14 else 9, t)
     period = 40 + 23 * env                # 40 .. 339 steps
     burst = 4 + (env % 5)                 # steps of deferring at the start of each period
     gap = min(period - burst - 8, 12 + 9 * env)   # idle steps after the burst (up to > 97: tasks become overdue)
@@ -27,7 +35,7 @@ def _ls_script(env, t):
 
 
 def test_oldest_task_search_gaps_overdue_and_empty_queue_vs_oracle():
-    N, steps = 14, 672
+    N, steps = 16, 672
     rig = P.ParityRig(N, episode_steps=steps, seed=97)
     arng = np.random.default_rng(98)
     worst = dict(obs=0.0, rew=0.0, info=0.0)
@@ -36,11 +44,14 @@ def test_oldest_task_search_gaps_overdue_and_empty_queue_vs_oracle():
         worst["obs"] = max(worst["obs"], float(G.rel_err(eobs[i], o).max()))
     seen_overdue = seen_empty = seen_far = 0
     prev_oldest = np.zeros(N)
+    cursor0 = rig.eng.get_state("cursor")
+    a_ls = np.zeros((steps, N), np.int32)
     for t in range(steps):
         acts = arng.integers(0, 3, size=(N, 3)).astype(np.int32)
         acts[:, 0] = [_ls_script(i, t) for i in range(N)]
         if t % 7 == 3:
-            acts[N - 1, 0] = 2            # one env mixes in extra processing steps
+            acts[13, 0] = 2               # one env mixes in extra processing steps
+        a_ls[t] = acts[:, 0]
         P.compare_step(rig, acts, worst)
         info = rig.eng.info.cpu().numpy()
         from dc_rl_amd import _lib as L
@@ -51,8 +62,10 @@ def test_oldest_task_search_gaps_overdue_and_empty_queue_vs_oracle():
         seen_empty += int((q == 0).sum())
         seen_far += int(((prev_oldest - oldest) > 32).sum())      # the oldest task moved by more than the 32 prefetched entries
         prev_oldest = oldest
-    print("queue paths:", worst, "overdue env-steps", seen_overdue, "empty", seen_empty, "jumps > 32 steps", seen_far)
-    assert seen_overdue > 20 and seen_empty > 20 and seen_far > 5
+    far_non_empty = int(QM.far_moves(QM.run_batch(rig.tables[0]["W"], cursor0, a_ls, 1000)["head"]).sum())
+    print("queue paths:", worst, "overdue env-steps", seen_overdue, "empty", seen_empty, "jumps > 32 steps", seen_far,
+          "of the oldest task itself, queue non-empty afterwards", far_non_empty)
+    assert seen_overdue > 20 and seen_empty > 20 and seen_far > 5 and far_non_empty > 5
     assert worst["obs"] <= TOL and worst["rew"] <= TOL and worst["info"] <= 2e-6
     assert (rig.eng.get_state("order_stat_sticky") == 0).all()
     rig.eng.close()
