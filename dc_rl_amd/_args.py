@@ -89,6 +89,48 @@ def device_tensor(x, who, name, dtype, shape, text=None, device=None, plural=Fal
         raise ValueError(f"{pre}{name} {'are' if plural else 'is'} on {x.device}, this engine runs on {device}")
 
 
+# ---------------------------------------------------------------------- the actors on stored rows, the PPO terms
+def agent_slot(who, agent, name="agent"):
+    """an agent slot 0 (ls), 1 (dc) or 2 (bat) as an int; ValueError in the caller's name for anything else"""
+    if isinstance(agent, bool) or not isinstance(agent, (int, np.integer)) or not 0 <= int(agent) < L.N_AGENTS:
+        raise ValueError(f"{who}: {name} = {agent!r} must be 0 (ls), 1 (dc) or 2 (bat)")
+    return int(agent)
+
+
+def agent_slots(who, agents):
+    """`agents` as a tuple of distinct slots, at least one; ValueError in the caller's name"""
+    try:
+        out = tuple(agent_slot(who, a, "an entry of agents") for a in agents)
+    except TypeError:
+        raise ValueError(f"{who}: agents must be a sequence of agent slots") from None
+    if not out or len(set(out)) != len(out):
+        raise ValueError(f"{who}: agents = {tuple(agents)!r} must name at least one slot and none twice")
+    return out
+
+
+def actor_rows(who, obs, agent, per_agent=None, device=None):
+    """actor_logits' `obs` -> (offset in floats, row stride in floats, rows, the logits' shape): a contiguous float32 CUDA tensor
+    (..., 26) of dense rows -- offset 0, stride 26 --, or (..., 3, 26) of which agent `agent`'s rows are taken -- offset 26 * agent,
+    stride 78.  `per_agent`: which of the two (None: the second where the last but one dimension is 3).  ValueError in the caller's name."""
+    import torch
+    D = L.OBS_PAD
+    if not (isinstance(obs, torch.Tensor) and obs.dtype == torch.float32 and obs.is_cuda and obs.is_contiguous() and obs.dim() >= 1 and
+            obs.shape[-1] == D and obs.numel() > 0):
+        raise ValueError(f"{who}: obs must be a contiguous float32 CUDA tensor of shape (..., {D}) or (..., {L.N_AGENTS}, {D}), not empty")
+    if device is not None and obs.device != device:
+        raise ValueError(f"{who}: obs is on {obs.device}, this engine runs on {device}")
+    three = obs.dim() >= 2 and obs.shape[-2] == L.N_AGENTS
+    if per_agent is None:
+        per_agent = three
+    if per_agent and not three:
+        raise ValueError(f"{who}: per_agent asks for obs of shape (..., {L.N_AGENTS}, {D}), got {tuple(obs.shape)}")
+    if per_agent:
+        lead = tuple(obs.shape[:-2])
+        return D * agent, L.N_AGENTS * D, int(np.prod(lead, dtype=np.int64)), lead + (3,)
+    lead = tuple(obs.shape[:-1])
+    return 0, D, int(np.prod(lead, dtype=np.int64)), lead + (3,)
+
+
 # ---------------------------------------------------------------------- the horizon of lookahead and plan
 def check_horizon(who, K, left=None, auto_reset=False):
     """ValueError for a horizon a mark cannot hold and -- `left` = steps_to_episode_end() given -- one that would finish an episode"""

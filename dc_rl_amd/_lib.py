@@ -24,7 +24,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
            "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip", "sdc_plan_terms.hip",
-           "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip", "sdc_mpc_groups.hip", "sdc_critic.hip", "sdc_onpolicy.hip"]
+           "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip", "sdc_mpc_groups.hip", "sdc_critic.hip", "sdc_onpolicy.hip", "sdc_actor_eval.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
@@ -60,6 +60,10 @@ PLAN_SCORE, PLAN_GAIN, PLAN_PLANNED, PLAN_IDLE = range(PLAN_SUMS)
 CEM_MAX_CAND = 64       # include/sustaindc_hip.h SDC_CEM_MAX_CAND: candidates per iteration of sdc_plan_cem
 CEM_MAX_GROUP = 1024    # include/sustaindc_hip.h SDC_CEM_MAX_GROUP: replicas per group of sdc_plan_cem_groups
 CEM_MAX_ITERS = 65536   # ... and its iteration indices: iter0 + n_iters <= this (the index is 16 bits of the generator's counter)
+ACTOR_EVAL_MAX_BLOCKS = 1024    # csrc/sdc_actor_eval.hpp SDC_ACTOR_EVAL_MAX_BLOCKS: workgroups (64 rows per pass each) of sdc_actor_evaluate
+PPO_BLOCK = 256         # csrc/sdc_actor_eval.hpp SDC_PPO_BLOCK: lanes per workgroup of sdc_ppo_terms' two stages
+PPO_MAX_BLOCKS = 1024   # csrc/sdc_actor_eval.hpp SDC_PPO_MAX_BLOCKS: stage 1's workgroups at most (include/sustaindc_hip.h states the order)
+PPO_STATS = 8           # include/sustaindc_hip.h: entries of sdc_ppo_terms' stats
 SNAPSHOT_MANIFEST = 9   # include/sustaindc_hip.h SDC_SNAPSHOT_MANIFEST: int32 entries per snapshot row's manifest (enum sdc_snapshot_manifest)
 # (-amdgpu-sched-strategy=max-ilp: the machine scheduler orders for instruction-level parallelism instead of minimal register
 #  pressure -- the step kernels' occupancy is pinned by amdgpu_waves_per_eu anyway, and their time is dependent-issue latency:
@@ -242,7 +246,7 @@ EXPORTS = [
     "sdc_set_plan_forecast", "sdc_get_plan_forecast", "sdc_forecast_traces", "sdc_rollout_actor_stats",
     "sdc_rollout_cem_stats", "sdc_rollout_cem_groups_stats",
     "sdc_set_critic", "sdc_critic_values", "sdc_set_plan_critic", "sdc_get_plan_critic",
-    "sdc_gae", "sdc_action_log_probs",
+    "sdc_gae", "sdc_action_log_probs", "sdc_actor_evaluate", "sdc_ppo_terms",
 ]
 
 
@@ -420,6 +424,8 @@ def load():
     L.sdc_get_plan_critic.argtypes = [vp, dp]
     L.sdc_gae.argtypes = [vp, C.c_int, fp, C.c_int, vp, vp, fp, C.c_double, C.c_double, C.c_int, fp, fp, fp, fp, vp, vp]
     L.sdc_action_log_probs.argtypes = [vp, C.c_int, vp, fp, fp, fp, vp]
+    L.sdc_actor_evaluate.argtypes = [vp, C.c_int, fp, C.c_longlong, C.c_longlong, fp, C.c_longlong, vp]
+    L.sdc_ppo_terms.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp, C.c_double, fp, fp, fp, vp, vp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

@@ -40,6 +40,7 @@
 #include "sdc_stats.hpp"
 #include "sdc_policy_stats.hpp"
 #include "sdc_onpolicy.hpp"
+#include "sdc_actor_eval.hpp"
 #include "sdc_mpc.hpp"
 #include "sdc_mpc_groups.hpp"
 #include "sdc_mpc_schedule.hpp"
@@ -168,6 +169,10 @@ struct sdc_handle {
   size_t policy_out_bytes = 0;
   // sdc_gae: every env's sum and sum of squares of its advantages [N][2] (sdc_onpolicy.hpp), allocated on first use
   double* adv_part = nullptr;
+  // sdc_actor_evaluate: the three actors once more, in the layout of the 16-rows-per-wavefront kernel (sdc_actor_eval_pack.hpp), allocated
+  // and filled with actor_dev; sdc_ppo_terms: stage 1's partial statistics [SDC_PPO_MAX_BLOCKS][8], allocated on first use
+  SdcActorEvalDev* actor_eval_dev = nullptr;
+  double* ppo_part = nullptr;
 };
 
 namespace {
@@ -888,6 +893,7 @@ int sdc_set_actor(sdc_handle* h, int slot, const sdc_actor_params* p) {
   HIP_TRY(hipSetDevice(h->device));
   if (!h->actor_dev) {
     if (dev_alloc(h, &h->actor_dev, 3) != 0) return -1;
+    if (dev_alloc(h, &h->actor_eval_dev, 3) != 0) return -1;
     if (dev_alloc(h, &h->obs_latch, (size_t)h->cfg.n_envs * SDC_OBS_OUT) != 0) return -1;
     h->latch_valid = false;      // (filled by the next reset / step / rollout)
   }
@@ -910,8 +916,12 @@ int sdc_set_actor(sdc_handle* h, int slot, const sdc_actor_params* p) {
   }
   for (int c = 0; c < SDC_ACT_OUT; c++) a.b3[c] = p->b3[c];
   a.flags = (p->use_feature_normalization ? 1 : 0) | (p->activation << 1);
+  // ... and the same parameters as sdc_actor_evaluate's kernel reads them (sdc_actor_eval_pack.hpp)
+  std::unique_ptr<SdcActorEvalDev> packed(new SdcActorEvalDev);
+  sdc_actor_eval_pack(p, packed.get());
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(h->actor_dev + slot, &a, sizeof(a), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->actor_eval_dev + slot, packed.get(), sizeof(SdcActorEvalDev), hipMemcpyHostToDevice));
   h->actor_set[slot] = true;
   h->actor_activation[slot] = p->activation;
   return 0;
@@ -1810,6 +1820,46 @@ int sdc_action_log_probs(sdc_handle* h, int n_steps, const int32_t* actions, con
   const long long n = (long long)n_steps * h->cfg.n_envs * SDC_N_AGENTS;
   return launched("sdc_action_logp_kernel",
                   sdc_action_logp_launch(SdcActionLogp{n, actions, logits, log_probs, entropy}, reinterpret_cast<hipStream_t>(stream)));
+}
+
+// ---- the actors on stored rows, and the PPO terms (sdc_actor_eval.hip) -----------------------------------------------------------------
+// The contract and the arithmetic: include/sustaindc_hip.h EVALUATE THE ACTORS ON STORED ROWS; the kernels' plans: sdc_actor_eval.hpp.
+int sdc_actor_evaluate(sdc_handle* h, int agent_slot, const float* obs, long long row_stride, long long n_rows, float* logits,
+                       long long logits_stride, void* stream) {
+  if (refused(sdc_actor_evaluate_refused(call_facts(h), agent_slot, obs, row_stride, n_rows, logits, logits_stride))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  return launched("sdc_actor_eval_kernel",
+                  sdc_actor_eval_launch(SdcActorEval{h->actor_eval_dev + agent_slot, obs, row_stride, n_rows, logits, logits_stride},
+                                        reinterpret_cast<hipStream_t>(stream)));
+}
+
+int sdc_ppo_terms(sdc_handle* h, int n_steps, int agent, const float* new_log_probs, const float* old_log_probs, const float* entropy,
+                  const float* advantages, const float* factor, double clip_param, float* ratio, float* surr, float* factor_out,
+                  double* stats, void* stream) {
+  if (refused(sdc_ppo_terms_refused(call_facts(h), n_steps, agent, new_log_probs, old_log_probs, entropy, advantages, factor, clip_param,
+                                    ratio, surr, factor_out, stats)))
+    return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (stats && !h->ppo_part && dev_alloc(h, &h->ppo_part, (size_t)SDC_PPO_MAX_BLOCKS * SDC_PPO_STATS, false) != 0) return -1;
+  SdcPpoTerms P;
+  std::memset(&P, 0, sizeof(P));
+  P.n = (long long)n_steps * h->cfg.n_envs;
+  P.agent = agent;
+  P.new_lp = new_log_probs;
+  P.old_lp = old_log_probs;
+  P.entropy = entropy;
+  P.adv = advantages;
+  P.factor = factor;
+  P.lo = 1.0 - clip_param;
+  P.hi = 1.0 + clip_param;
+  P.ratio = ratio;
+  P.surr = surr;
+  P.factor_out = factor_out;
+  P.part = stats ? h->ppo_part : nullptr;
+  if (const int rc = launched("sdc_ppo_terms_kernel", sdc_ppo_terms_launch(P, st))) return rc;
+  if (!stats) return 0;
+  return launched("sdc_ppo_stats_kernel", sdc_ppo_stats_launch(SdcPpoStats{sdc_ppo_blocks(P.n), (double)P.n, h->ppo_part, stats}, st));
 }
 
 int sdc_set_plan_critic(sdc_handle* h, double weight) {

@@ -584,6 +584,38 @@ static inline SdcMsg sdc_action_log_probs_refused(const SdcCallFacts& f, const i
   return std::nullopt;
 }
 
+// ---- the actors on stored rows, and the PPO terms --------------------------------------------------------------------------------------------
+// (pure functions of their arrays, as the on-policy batch's; their texts are held by tests/test_actor_eval_abi.py)
+static inline SdcMsg sdc_actor_evaluate_refused(const SdcCallFacts& f, const int agent_slot, const float* obs, const long long row_stride,
+                                                const long long n_rows, const float* logits, const long long logits_stride) {
+  static const std::string w = "sdc_actor_evaluate: ";
+  if (!f.handle) return w + "null handle";
+  if (agent_slot < 0 || agent_slot > 2) return w + "agent_slot = " + std::to_string(agent_slot) + " outside [0, 2]";
+  if (!f.actor_set[agent_slot]) return w + "no actor is set for agent_slot " + std::to_string(agent_slot) + " (sdc_set_actor first)";
+  if (n_rows < 1) return w + "n_rows = " + std::to_string(n_rows) + " must be positive";
+  if (!obs || !logits) return w + "null array (obs and logits are required)";
+  if ((sdc_addr_bits(obs, logits) & 3u) != 0) return w + "obs / logits not dword-aligned";
+  if (row_stride < 26) return w + "row_stride = " + std::to_string(row_stride) + " below a row's 26 floats";
+  if (logits_stride < 3) return w + "logits_stride = " + std::to_string(logits_stride) + " below a row's 3 floats";
+  return std::nullopt;
+}
+static inline SdcMsg sdc_ppo_terms_refused(const SdcCallFacts& f, const int n_steps, const int agent, const float* new_log_probs,
+                                           const float* old_log_probs, const float* entropy, const float* advantages, const float* factor,
+                                           const double clip_param, const float* ratio, const float* surr, const float* factor_out,
+                                           const double* stats) {
+  static const std::string w = "sdc_ppo_terms: ";
+  if (!f.handle) return w + "null handle";
+  if (n_steps < 1) return w + "n_steps = " + std::to_string(n_steps) + " must be positive";
+  if (agent < 0 || agent > 2) return w + "agent = " + std::to_string(agent) + " outside [0, 2]";
+  if (!new_log_probs || !old_log_probs || !advantages || !ratio)
+    return w + "null array (new_log_probs, old_log_probs, advantages and ratio are required)";
+  if ((sdc_addr_bits(new_log_probs, old_log_probs, entropy, advantages, factor, ratio, surr, factor_out) & 3u) != 0)
+    return w + "new_log_probs / old_log_probs / entropy / advantages / factor / ratio / surr / factor_out not dword-aligned";
+  if ((sdc_addr_bits(stats) & 7u) != 0) return w + "stats not 8-byte aligned";
+  if (!(clip_param >= 0.0 && clip_param < 1.0)) return w + "clip_param = " + std::to_string(clip_param) + " outside [0, 1)";
+  return std::nullopt;
+}
+
 // ---- the cross-entropy planners -------------------------------------------------------------------------------------------------------------
 // The parameter ranges sdc_plan_cem and sdc_plan_cem_groups refuse alike.  The callers run them in their own order.
 static inline SdcMsg sdc_cem_iters_refused(const std::string& w, const int n_iters, const int iter0) {

@@ -320,6 +320,26 @@ class OnPolicyBatch:
         return {k: getattr(self, k)[:T].flatten(0, 1) for k in per_step}
 
 
+class PPOTerms:
+    """What SdcEngine.ppo_terms hands back for one agent, on the engine's device: `ratio` fp32 [T, N] (the reference's imp_weights),
+    `surr` fp32 [T, N] = factor * min(ratio * A, clamp(ratio, 1 - clip, 1 + clip) * A) or None, `factor` fp32 [T, N] the UPDATED HAPPO
+    factor (the one given, or ones, times ratio), `stats` fp64 [8]: the sums of surr, ratio, new - old and the entropy column, the
+    number of clipped elements, the ratio's minimum and maximum, T N (include/sustaindc_hip.h states their fixed order)."""
+    __slots__ = ("ratio", "surr", "factor", "stats")
+
+    def __init__(self, ratio, surr, factor, stats):
+        self.ratio, self.surr, self.factor, self.stats = ratio, surr, factor, stats
+
+    def summary(self) -> dict:
+        """The update's logged scalars, from one device -> host copy of `stats`: policy_loss = -mean(surr) (happo.py's
+        policy_action_loss), ratio_mean / ratio_min / ratio_max, approx_kl = -mean(new - old), entropy (the mean of the entropy column;
+        0 where none was given), clip_frac"""
+        s = self.stats.cpu().numpy()
+        n = float(s[7])
+        return dict(policy_loss=-float(s[0]) / n, ratio_mean=float(s[1]) / n, ratio_min=float(s[5]), ratio_max=float(s[6]),
+                    approx_kl=-float(s[2]) / n, entropy=float(s[3]) / n, clip_frac=float(s[4]) / n)
+
+
 class MPCCarry:
     """What `rollout_cem_stats` leaves of the planner's state, on the engine's device: `probs` float64 [H, N, 3, 3] and `best_seq` int32
     [H, N, 3], the arrays of the call (a caller's own are the same tensors), whose first `steps` steps hold the last planned decision's
@@ -911,6 +931,85 @@ class SdcEngine:
         return OnPolicyBatch(obs=obs, share_obs=share, actions=acts, logits=logits, action_log_probs=logp, entropy=ent, rewards=rew,
                              dones=done, masks=g.masks, values=values, value_preds=g.value_preds, returns=g.returns,
                              advantages=g.advantages, adv_mean=g.moments[0], adv_std=g.moments[1], last_done=done[T - 1])
+
+    # ------------------------------------------------------------------ the actors on stored rows, the PPO terms
+    def _actor_evaluate(self, agent, obs, offset, row_stride, n_rows, logits, logits_offset, logits_stride):
+        """sdc_actor_evaluate of `n_rows` rows of `obs` from float `offset`, `row_stride` floats apart, into `logits` likewise"""
+        self._call(self.lib.sdc_actor_evaluate, agent, C.c_void_p(obs.data_ptr() + 4 * offset), row_stride, n_rows,
+                   C.c_void_p(logits.data_ptr() + 4 * logits_offset), logits_stride, self._stream(), refuses=True, wrote=(obs, logits))
+
+    def actor_logits(self, agent: int, obs, per_agent=None):
+        """The logits of agent `agent`'s actor (the one last given to set_actor) for stored observation rows -- the forward pass of the
+        reference's evaluate_actions, with no gradient (sdc_actor_evaluate: one launch, stream-ordered, 16 rows per wavefront on the
+        matrix cores; a row's logits depend on that row alone, to the bit).  `obs`: a contiguous fp32 tensor on this engine's device,
+        either (..., 26), dense rows of that agent, or (..., 3, 26), e.g. OnPolicyBatch.obs, of which the agent's rows are read in place
+        (78 floats apart) -> fp32 (..., 3).  A tensor whose last but one dimension is 3 is taken as the second form; `per_agent` says
+        it outright.  The envs are not touched.  ValueError for another tensor, another agent, and before set_actor(agent)."""
+        t, who = self.torch, "actor_logits"
+        a = A.agent_slot(who, agent)
+        offset, stride, rows, shape = A.actor_rows(who, obs, a, per_agent, self.device)
+        logits = t.empty(shape, dtype=t.float32, device=self.device)
+        self._behind_torch_stream()
+        self._actor_evaluate(a, obs, offset, stride, rows, logits, 0, 3)
+        return logits
+
+    def evaluate_actions(self, obs, actions, agents=(0, 1, 2), want_entropy: bool = True):
+        """The reference's evaluate_actions over a stored batch, for the agents asked for: `obs` fp32 [T, N, 3, 26] (e.g. batch.obs[:T])
+        and `actions` int32 [T, N, 3], contiguous on this engine's device -> (logits [T, N, 3, 3], log_probs [T, N, 3], entropy
+        [T, N, 3] or None).  One sdc_actor_evaluate launch per agent into its column of `logits`, then one action_log_probs over all of
+        it.  The columns of agents NOT asked for are zero in `logits`, and not meaningful in log_probs and entropy (they are those of
+        three equal logits).  Evaluated twice with the same actors, the same rows give the same bits."""
+        t, who, N = self.torch, "evaluate_actions", self.n_envs
+        agents = A.agent_slots(who, agents)
+        A.device_tensor(actions, who, "actions", t.int32, (A.SOME, N, 3), "(T, n_envs, 3)", self.device)
+        T = int(actions.shape[0])
+        A.device_tensor(obs, who, "obs", t.float32, (T, N, L.N_AGENTS, L.OBS_PAD), "(T, n_envs, 3, 26)", self.device)
+        all_three = len(agents) == L.N_AGENTS
+        logits = (t.empty if all_three else t.zeros)((T, N, 3, 3), dtype=t.float32, device=self.device)
+        self._behind_torch_stream()
+        for a in agents:
+            self._actor_evaluate(a, obs, L.OBS_PAD * a, L.N_AGENTS * L.OBS_PAD, T * N, logits, 3 * a, 9)
+        logp, ent = self.action_log_probs(actions, logits, want_entropy)
+        return logits, logp, ent
+
+    def ppo_terms(self, agent: int, new_log_probs, old_log_probs, advantages, clip_param: float = 0.2, factor=None, entropy=None,
+                  want_surr: bool = True) -> PPOTerms:
+        """What an actor update and the HAPPO factor need of one agent's log-probabilities (sdc_ppo_terms: elementwise in fp64, each
+        result rounded once; fixed-order fp64 statistics; stream-ordered): `new_log_probs`, `old_log_probs` and `entropy` (or None)
+        fp32 [T, N, 3], of which column `agent` is read; `advantages` and `factor` (None: ones, MAPPO) fp32 [T, N]; all contiguous on
+        this engine's device -> PPOTerms: ratio = exp(new - old), surr = factor * min(ratio * A, clamp(ratio, 1 - clip, 1 + clip) * A)
+        (None without `want_surr`), factor = the given factor * ratio in a new tensor, stats.  ValueError for another tensor or agent
+        and for what the library refuses (clip_param outside [0, 1))."""
+        t, who, N = self.torch, "ppo_terms", self.n_envs
+        a = A.agent_slot(who, agent)
+        A.device_tensor(new_log_probs, who, "new_log_probs", t.float32, (A.SOME, N, 3), "(T, n_envs, 3)", self.device)
+        T = int(new_log_probs.shape[0])
+        A.device_tensor(old_log_probs, who, "old_log_probs", t.float32, (T, N, 3), "(T, n_envs, 3)", self.device)
+        A.device_tensor(advantages, who, "advantages", t.float32, (T, N), "(T, n_envs)", self.device)
+        if factor is not None:
+            A.device_tensor(factor, who, "factor", t.float32, (T, N), "(T, n_envs)", self.device)
+        if entropy is not None:
+            A.device_tensor(entropy, who, "entropy", t.float32, (T, N, 3), "(T, n_envs, 3)", self.device)
+        new = lambda: t.empty((T, N), dtype=t.float32, device=self.device)
+        res = PPOTerms(new(), new() if want_surr else None, new(), t.empty(L.PPO_STATS, dtype=t.float64, device=self.device))
+        self._behind_torch_stream()
+        self._call(self.lib.sdc_ppo_terms, T, a, _p(new_log_probs), _p(old_log_probs), _p(entropy), _p(advantages), _p(factor),
+                   float(clip_param), _p(res.ratio), _p(res.surr), _p(res.factor), _p(res.stats), self._stream(), refuses=True,
+                   wrote=(new_log_probs, old_log_probs, entropy, advantages, factor, res.ratio, res.surr, res.factor, res.stats))
+        return res
+
+    def actor_update_terms(self, batch, agent: int, clip_param: float = 0.2, factor=None, old_log_probs=None) -> PPOTerms:
+        """The HAPPO loop's use of the two calls above for one agent of an OnPolicyBatch: `agent` is evaluated with the actor NOW set
+        over batch.obs[:T] and batch.actions (evaluate_actions), and ppo_terms runs on its log-probabilities and entropies against
+        `old_log_probs` (default: batch.action_log_probs, the closed loop's) and batch.normalized_advantages(), with the factor carried
+        from the agents updated before (None: ones).  The runner's order -- evaluate, update the actor (set_actor), evaluate again,
+        factor *= exp(new - old) -- is evaluate_actions before the update, whose log-probabilities are this call's `old_log_probs`
+        after it; PPOTerms.factor is then the next agent's factor.  With the actor unchanged between the two the ratio is exactly 1."""
+        a = A.agent_slot("actor_update_terms", agent)
+        T = batch.n_steps
+        _, logp, ent = self.evaluate_actions(batch.obs[:T], batch.actions, agents=(a,))
+        old = batch.action_log_probs if old_log_probs is None else old_log_probs
+        return self.ppo_terms(a, logp, old, batch.normalized_advantages(), clip_param, factor=factor, entropy=ent)
 
     # ------------------------------------------------------------------ state access (parity injection / checkpoint)
     def _state_array(self, name):

@@ -722,6 +722,25 @@ class SustainDCVecEnv(ShareVecEnv):
         (SdcEngine.action_log_probs)"""
         return self.engine.action_log_probs(actions, logits, want_entropy)
 
+    def actor_logits(self, agent, obs, per_agent=None):
+        """One actor's logits for stored observation rows, (..., 26) or (..., 3, 26) -> (..., 3) (SdcEngine.actor_logits); the envs are
+        not touched"""
+        return self.engine.actor_logits(agent, obs, per_agent)
+
+    def evaluate_actions(self, obs, actions, *args, **kw):
+        """The actors over a stored batch, engine layout [T, num_envs, 3, 26] / [T, num_envs, 3] -> (logits, log_probs, entropy)
+        (SdcEngine.evaluate_actions, which documents the arguments and the result)"""
+        return self.engine.evaluate_actions(obs, actions, *args, **kw)
+
+    def ppo_terms(self, agent, new_log_probs, old_log_probs, advantages, *args, **kw):
+        """Importance ratio, clipped surrogate, HAPPO factor and their statistics for one agent (SdcEngine.ppo_terms, which documents
+        the arguments and the PPOTerms)"""
+        return self.engine.ppo_terms(agent, new_log_probs, old_log_probs, advantages, *args, **kw)
+
+    def actor_update_terms(self, batch, agent, *args, **kw):
+        """One agent's PPO terms over an OnPolicyBatch with the actor now set (SdcEngine.actor_update_terms)"""
+        return self.engine.actor_update_terms(batch, agent, *args, **kw)
+
     def gae(self, rew, done, values, *args, **kw):
         """Returns, advantages and masks of a collected rollout (SdcEngine.gae, which documents the arguments and the result)"""
         return self.engine.gae(rew, done, values, *args, **kw)

@@ -242,7 +242,7 @@ const char* sdc_last_error(void);
  *        sdc_rollout_stats and sdc_plan_cem_groups likewise; sdc_set_plan_terms and sdc_get_plan_terms likewise;
  *        sdc_set_plan_forecast, sdc_get_plan_forecast and sdc_forecast_traces likewise; sdc_rollout_actor_stats, sdc_rollout_cem_stats
  *        and sdc_rollout_cem_groups_stats likewise; sdc_set_critic, sdc_critic_values, sdc_set_plan_critic and sdc_get_plan_critic
- *        likewise) */
+ *        likewise; sdc_gae and sdc_action_log_probs likewise; sdc_actor_evaluate and sdc_ppo_terms likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -652,6 +652,54 @@ int sdc_gae(sdc_handle* h, int n_steps, const float* rew, int reward_agent, cons
             float* value_preds, double* moments, void* stream);
 int sdc_action_log_probs(sdc_handle* h, int n_steps, const int32_t* actions, const float* logits, float* log_probs, float* entropy,
                          void* stream);
+
+/* EVALUATE THE ACTORS ON STORED ROWS.  replaces: the forward pass of the reference's evaluate_actions over a stored buffer
+ * (harl/algorithms/actors/on_policy_base.py evaluate_actions -> StochasticPolicy.evaluate_actions), which harl/runners/on_policy_ha_runner.py
+ * runs over the whole buffer before and after every agent's update for the HAPPO factor, and the terms harl/algorithms/actors/happo.py and
+ * mappo.py build from its log-probabilities (imp_weights, the clipped surrogate, the entropy).  No gradient: the backward pass, the
+ * optimiser and the critic's value loss are not here.  Both calls are pure functions of their arrays, all device memory: they read no env
+ * state and move nothing in the engine; each is ordered on `stream` with no synchronisation.
+ * sdc_actor_evaluate: the logits of agent_slot's network -- the one last given to sdc_set_actor for that slot, the network stated at
+ * sdc_set_actor, fp32, the hidden layers on fp32-input matrix instructions, 16 rows per wavefront (csrc/sdc_actor_eval.hpp) -- for n_rows
+ * rows of observations, ONE launch of sdc_actor_eval_kernel.  Row r is the 26 floats at obs + r * row_stride (floats; row_stride 26: a
+ * dense per-agent buffer; 78 with obs advanced by 26 * agent: the agent's rows of an [..][3][26] array as sdc_rollout_actor fills it); its
+ * three logits go to logits + r * logits_stride (logits_stride 3: dense; 9 with logits advanced by 3 * agent: the agent's column of a
+ * [T][N][3][3] array, on which sdc_action_log_probs runs unchanged).  Nothing else is written: the floats between two rows' logits keep
+ * their values.  A row's logits depend on that row and the parameters alone -- not on its position, the strides, n_rows or the rows next
+ * to it -- to the bit; against the closed loop's logits of the same row (sdc_rollout_actor sums in another order) they agree to fp32
+ * rounding, not to the bit.
+ * Refused (-2 and a message, nothing enqueued): a null handle; agent_slot outside 0 .. 2; no actor set for that slot; n_rows < 1; a null
+ * obs or logits; obs or logits not dword-aligned; row_stride < 26; logits_stride < 3.
+ * sdc_ppo_terms: per element i = t N + n < T N (N = the handle's n_envs, T = n_steps), with j = 3 i + agent, in fp64 with no fused
+ * multiply-add, each stored value rounded once to fp32:
+ *     lr = (double)new_log_probs[j] - (double)old_log_probs[j]           // exact
+ *     r  = exp(lr);                        ratio[i] = (float)r           // the reference's imp_weights
+ *     A  = (double)advantages[i];          F = factor ? (double)factor[i] : 1.0
+ *     s1 = r * A;    rc = r < lo ? lo : r;   rc = rc > hi ? hi : rc;    s2 = rc * A      // lo = 1 - clip_param, hi = 1 + clip_param, in double
+ *     surr[i] = (float)(F * (s2 < s1 ? s2 : s1))
+ *     factor_out[i] = (factor ? factor[i] : 1.0f) * ratio[i]             // ONE fp32 product of the stored values: the runner's
+ *                                                                        // factor * exp(new - old); factor_out may be the array `factor`
+ *     clipped_i = r < lo || r > hi
+ * new_log_probs, old_log_probs, entropy [T][N][3] fp32, of which column `agent` alone is read (the other columns may hold anything);
+ * advantages, factor, ratio, surr, factor_out [T][N] fp32; entropy, factor, surr, factor_out and stats may be NULL (factor NULL: 1, MAPPO).
+ * stats [8] fp64 or NULL: fp64 statistics of the STORED fp32 values, so that a host redoes them bit for bit from the call's outputs:
+ *     0 sum of (double)surr[i] (whether or not surr is stored)    1 sum of (double)ratio[i]    2 sum of lr    3 sum of (double)entropy[j]
+ *     (0 without entropy)    4 number of clipped elements    5 min of (double)ratio[i]    6 max of (double)ratio[i]    7 (double)(T N)
+ * in a fixed order, no atomics, the same bits on every run -- two launches, sdc_ppo_terms_kernel and sdc_ppo_stats_kernel:
+ *   stage 1: B = min(ceil(T N / 256), 1024) workgroups of 256 lanes.  Lane l of workgroup b starts from (0, 0, 0, 0, 0, +inf, -inf) and
+ *     folds the elements i = b * 256 + l + k * 256 * B, k = 0, 1, ... (i < T N) in that order: sums s = s + x, minimum m = x < m ? x : m,
+ *     maximum m = x > m ? x : m.  Then for half = 128, 64, .. 1: lane l < half takes lane l + half (sums a + b, minimum b < a ? b : a,
+ *     maximum b > a ? b : a); lane 0's is partial b.
+ *   stage 2: one workgroup of 256 lanes.  Lane l starts as above and takes partials l, l + 256, ... (< B) in that order, then the same
+ *     halving; lane 0's values are stats[0..6], and stats[7] = (double)(T N).
+ * With stats NULL neither reduction runs (one launch).  The partials are a buffer of the handle's, allocated on first use.
+ * Refused: a null handle; n_steps < 1; agent outside 0 .. 2; a null new_log_probs, old_log_probs, advantages or ratio; a float array not
+ * dword-aligned; stats not 8-byte aligned; clip_param not finite or outside [0, 1). */
+int sdc_actor_evaluate(sdc_handle* h, int agent_slot, const float* obs, long long row_stride, long long n_rows, float* logits,
+                       long long logits_stride, void* stream);
+int sdc_ppo_terms(sdc_handle* h, int n_steps, int agent, const float* new_log_probs, const float* old_log_probs, const float* entropy,
+                  const float* advantages, const float* factor, double clip_param, float* ratio, float* surr, float* factor_out,
+                  double* stats, void* stream);
 
 /* PLAN FORECAST: what the plan calls' rollouts believe the traces of the next n_steps steps are.  Without one a plan call's rollouts
  * read the episode's own feature rows -- the real workload, carbon intensity, dry bulb (with the weather noise the episode drew) and wet
