@@ -131,6 +131,29 @@ def actor_rows(who, obs, agent, per_agent=None, device=None):
     return 0, D, int(np.prod(lead, dtype=np.int64)), lead + (3,)
 
 
+def actor_row_values(who, x, name, dtype, lead, agent, device=None):
+    """actor_backward's per-row `actions` -> (offset, stride in elements): a contiguous `dtype` CUDA tensor of shape `lead` (dense:
+    offset 0, stride 1) or `lead` + (3,), of which agent `agent`'s column is taken (offset agent, stride 3).  ValueError in the caller's
+    name."""
+    import torch
+    kind = str(dtype).split(".")[-1]
+    if not (isinstance(x, torch.Tensor) and x.dtype == dtype and x.is_cuda and x.is_contiguous() and
+            tuple(x.shape) in (tuple(lead), tuple(lead) + (L.N_AGENTS,))):
+        raise ValueError(f"{who}: {name} must be a contiguous {kind} CUDA tensor of shape {tuple(lead)} or {tuple(lead) + (L.N_AGENTS,)}")
+    if device is not None and x.device != device:
+        raise ValueError(f"{who}: {name} is on {x.device}, this engine runs on {device}")
+    if tuple(x.shape) == tuple(lead):        # (lead = (..., 3) with a dense tensor of that shape: dense wins, as the shapes say)
+        return 0, 1
+    return agent, L.N_AGENTS
+
+
+def finite_float(who, name, value):
+    """`value` as a float; ValueError in the caller's name for what is no real number (the library refuses what is not finite)"""
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{who}: {name} = {value!r} must be a number")
+    return float(value)
+
+
 # ---------------------------------------------------------------------- the horizon of lookahead and plan
 def check_horizon(who, K, left=None, auto_reset=False):
     """ValueError for a horizon a mark cannot hold and -- `left` = steps_to_episode_end() given -- one that would finish an episode"""

@@ -24,7 +24,8 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
            "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip", "sdc_plan_terms.hip",
-           "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip", "sdc_mpc_groups.hip", "sdc_critic.hip", "sdc_onpolicy.hip", "sdc_actor_eval.hip"]
+           "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip", "sdc_mpc_groups.hip", "sdc_critic.hip", "sdc_onpolicy.hip", "sdc_actor_eval.hip",
+           "sdc_actor_grad.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
@@ -64,6 +65,8 @@ ACTOR_EVAL_MAX_BLOCKS = 1024    # csrc/sdc_actor_eval.hpp SDC_ACTOR_EVAL_MAX_BLO
 PPO_BLOCK = 256         # csrc/sdc_actor_eval.hpp SDC_PPO_BLOCK: lanes per workgroup of sdc_ppo_terms' two stages
 PPO_MAX_BLOCKS = 1024   # csrc/sdc_actor_eval.hpp SDC_PPO_MAX_BLOCKS: stage 1's workgroups at most (include/sustaindc_hip.h states the order)
 PPO_STATS = 8           # include/sustaindc_hip.h: entries of sdc_ppo_terms' stats
+ACTOR_N_PARAMS = 6391           # include/sustaindc_hip.h SDC_ACTOR_N_PARAMS: the float members of sdc_actor_params, sdc_actor_backward's grads
+ACTOR_GRAD_MAX_BLOCKS = 256     # include/sustaindc_hip.h SDC_ACTOR_GRAD_MAX_BLOCKS: workgroups (partial gradients) of sdc_actor_backward at most
 SNAPSHOT_MANIFEST = 9   # include/sustaindc_hip.h SDC_SNAPSHOT_MANIFEST: int32 entries per snapshot row's manifest (enum sdc_snapshot_manifest)
 # (-amdgpu-sched-strategy=max-ilp: the machine scheduler orders for instruction-level parallelism instead of minimal register
 #  pressure -- the step kernels' occupancy is pinned by amdgpu_waves_per_eu anyway, and their time is dependent-issue latency:
@@ -246,7 +249,7 @@ EXPORTS = [
     "sdc_set_plan_forecast", "sdc_get_plan_forecast", "sdc_forecast_traces", "sdc_rollout_actor_stats",
     "sdc_rollout_cem_stats", "sdc_rollout_cem_groups_stats",
     "sdc_set_critic", "sdc_critic_values", "sdc_set_plan_critic", "sdc_get_plan_critic",
-    "sdc_gae", "sdc_action_log_probs", "sdc_actor_evaluate", "sdc_ppo_terms",
+    "sdc_gae", "sdc_action_log_probs", "sdc_actor_evaluate", "sdc_ppo_terms", "sdc_ppo_dlogp", "sdc_actor_backward",
 ]
 
 
@@ -426,6 +429,8 @@ def load():
     L.sdc_action_log_probs.argtypes = [vp, C.c_int, vp, fp, fp, fp, vp]
     L.sdc_actor_evaluate.argtypes = [vp, C.c_int, fp, C.c_longlong, C.c_longlong, fp, C.c_longlong, vp]
     L.sdc_ppo_terms.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp, C.c_double, fp, fp, fp, vp, vp]
+    L.sdc_ppo_dlogp.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp, C.c_double, C.c_double, fp, vp]
+    L.sdc_actor_backward.argtypes = [vp, C.c_int, fp, C.c_longlong, C.c_longlong, vp, C.c_longlong, fp, C.c_double, fp, vp, vp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sdc_actor_eval.hpp"
+#include "sdc_actor_forward.hpp"
 #include "sdc_critic.hpp"
 
 #pragma clang fp contract(off)
@@ -52,70 +53,12 @@ __device__ __forceinline__ void fetch(float (&v)[TILE_LOADS], const float* obs, 
   }
 }
 
-// W: the actor in LDS.  x[s]: lane (g, e) holds entry 4 s + g of row e's observation (0 beyond entry 25, and for a row past the last).
-// -> the row's three logits, in every lane of column e.
-template <int KIND>
-__device__ __forceinline__ void forward_kind(const SdcActorEvalDev* W, float (&x)[SDC_AEV_S1], const int lane, float (&lg)[SDC_AEV_OUT]) {
-  const int g = lane >> 4;
-  // feature LayerNorm (observation entries are of order one: one unshifted pass, as sdc_actor.hpp's)
-  if (W->flags & 1) {
-    float s1 = 0.0f, s2 = 0.0f;
-#pragma unroll
-    for (int s = 0; s < SDC_AEV_S1; s++) {
-      s1 += x[s];
-      s2 += x[s] * x[s];
-    }
-    float sum, sq;
-    sdc_critic::all_sum2(s1, s2, sum, sq);
-    const float mean = sum * (1.0f / SDC_AEV_IN);
-    const float var = fmaxf(sq * (1.0f / SDC_AEV_IN) - mean * mean, 0.0f);
-    const float rs = __builtin_amdgcn_rsqf(var + 1e-5f);
-#pragma unroll
-    for (int s = 0; s < SDC_AEV_S1; s++) x[s] = (x[s] - mean) * rs * W->ln0_g[g][s] + W->ln0_b[g][s];      // (gain and bias 0 beyond entry 25)
-  }
-  // ---- layer 1: 26 (28) -> 64 ------------------------------------------------------------------------------------------------------
-  f4 h[4];
-  sdc_critic::unit_vector(h, W->b1, g);
-#pragma unroll
-  for (int s = 0; s < SDC_AEV_S1; s++) {
-    const f4 a = *reinterpret_cast<const f4*>(W->a1[s][lane]);
-#pragma unroll
-    for (int t = 0; t < 4; t++) h[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], x[s], h[t], 0, 0, 0);
-  }
-  sdc_critic::epilogue<KIND>(h, W->ln1_g, W->ln1_b, g);
-  // ---- layer 2: 64 -> 64; k-step s = 4 t + i reads register (t, i) of layer 1 ------------------------------------------------------
-  f4 acc[4];
-  sdc_critic::unit_vector(acc, W->b2, g);
-#pragma unroll
-  for (int s = 0; s < SDC_AEV_S2; s++) {
-    const f4 a = *reinterpret_cast<const f4*>(W->a2[s][lane]);
-#pragma unroll
-    for (int t = 0; t < 4; t++) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], h[s >> 2][s & 3], acc[t], 0, 0, 0);
-  }
-  sdc_critic::epilogue<KIND>(acc, W->ln2_g, W->ln2_b, g);
-  // ---- the logits: 64 -> 3 ---------------------------------------------------------------------------------------------------------
-  float v[SDC_AEV_OUT];
-#pragma unroll
-  for (int c = 0; c < SDC_AEV_OUT; c++) {
-    f4 w3[4];
-    sdc_critic::unit_vector(w3, W->w3[c], g);
-    v[c] = 0.0f;
-#pragma unroll
-    for (int t = 0; t < 4; t++)
-#pragma unroll
-      for (int i = 0; i < 4; i++) v[c] = fmaf(w3[t][i], acc[t][i], v[c]);
-  }
-  float t0, t1;
-  sdc_critic::all_sum2(v[0], v[1], t0, t1);
-  const float t2 = sdc_critic::all_sum(v[2]);
-  lg[0] = t0 + W->b3[0];
-  lg[1] = t1 + W->b3[1];
-  lg[2] = t2 + W->b3[2];
-}
+// The forward itself: sdc_actor_forward.hpp (shared with sdc_actor_grad.hip), here with nothing kept.
 // (the activation is a template parameter, as the closed loop's: chosen per element it is a branch around every exp -> rcp chain)
 __device__ __forceinline__ void forward(const SdcActorEvalDev* W, float (&x)[SDC_AEV_S1], const int lane, float (&lg)[SDC_AEV_OUT]) {
-  if (__builtin_amdgcn_readfirstlane((W->flags >> 1) & 3) == 1) forward_kind<1>(W, x, lane, lg);
-  else forward_kind<0>(W, x, lane, lg);
+  sdc_aev::NoTape none;
+  if (__builtin_amdgcn_readfirstlane((W->flags >> 1) & 3) == 1) sdc_aev::forward_kind<1>(W, x, lane, lg, none);
+  else sdc_aev::forward_kind<0>(W, x, lane, lg, none);
 }
 
 // One pass of a wavefront: the fetched dwords through the wavefront's tile -> the logits of row (lane & 15), in every lane of that

@@ -41,6 +41,7 @@
 #include "sdc_policy_stats.hpp"
 #include "sdc_onpolicy.hpp"
 #include "sdc_actor_eval.hpp"
+#include "sdc_actor_grad.hpp"
 #include "sdc_mpc.hpp"
 #include "sdc_mpc_groups.hpp"
 #include "sdc_mpc_schedule.hpp"
@@ -173,6 +174,10 @@ struct sdc_handle {
   // and filled with actor_dev; sdc_ppo_terms: stage 1's partial statistics [SDC_PPO_MAX_BLOCKS][8], allocated on first use
   SdcActorEvalDev* actor_eval_dev = nullptr;
   double* ppo_part = nullptr;
+  // sdc_actor_backward: the three actors' transposed weights (sdc_actor_grad_pack.hpp), allocated and filled with actor_dev; the
+  // workgroups' partial gradients [SDC_ACTOR_GRAD_MAX_BLOCKS][SDC_ACTOR_N_PARAMS], allocated on first use
+  SdcActorGradDev* actor_grad_dev = nullptr;
+  float* actor_grad_part = nullptr;
 };
 
 namespace {
@@ -894,6 +899,7 @@ int sdc_set_actor(sdc_handle* h, int slot, const sdc_actor_params* p) {
   if (!h->actor_dev) {
     if (dev_alloc(h, &h->actor_dev, 3) != 0) return -1;
     if (dev_alloc(h, &h->actor_eval_dev, 3) != 0) return -1;
+    if (dev_alloc(h, &h->actor_grad_dev, 3) != 0) return -1;
     if (dev_alloc(h, &h->obs_latch, (size_t)h->cfg.n_envs * SDC_OBS_OUT) != 0) return -1;
     h->latch_valid = false;      // (filled by the next reset / step / rollout)
   }
@@ -919,9 +925,13 @@ int sdc_set_actor(sdc_handle* h, int slot, const sdc_actor_params* p) {
   // ... and the same parameters as sdc_actor_evaluate's kernel reads them (sdc_actor_eval_pack.hpp)
   std::unique_ptr<SdcActorEvalDev> packed(new SdcActorEvalDev);
   sdc_actor_eval_pack(p, packed.get());
+  // ... and their transposes as sdc_actor_backward's kernel reads them (sdc_actor_grad_pack.hpp)
+  std::unique_ptr<SdcActorGradDev> packed_t(new SdcActorGradDev);
+  sdc_actor_grad_pack(p, packed_t.get());
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(h->actor_dev + slot, &a, sizeof(a), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->actor_eval_dev + slot, packed.get(), sizeof(SdcActorEvalDev), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->actor_grad_dev + slot, packed_t.get(), sizeof(SdcActorGradDev), hipMemcpyHostToDevice));
   h->actor_set[slot] = true;
   h->actor_activation[slot] = p->activation;
   return 0;
@@ -1860,6 +1870,55 @@ int sdc_ppo_terms(sdc_handle* h, int n_steps, int agent, const float* new_log_pr
   if (const int rc = launched("sdc_ppo_terms_kernel", sdc_ppo_terms_launch(P, st))) return rc;
   if (!stats) return 0;
   return launched("sdc_ppo_stats_kernel", sdc_ppo_stats_launch(SdcPpoStats{sdc_ppo_blocks(P.n), (double)P.n, h->ppo_part, stats}, st));
+}
+
+// ---- the actors' gradient (sdc_actor_grad.hip) ---------------------------------------------------------------------------------------
+// The contract and the arithmetic: include/sustaindc_hip.h THE ACTORS' GRADIENT; the kernels' plans: sdc_actor_grad.hpp.
+int sdc_ppo_dlogp(sdc_handle* h, int n_steps, int agent, const float* new_log_probs, const float* old_log_probs, const float* advantages,
+                  const float* factor, double clip_param, double scale, float* dlogp, void* stream) {
+  if (refused(sdc_ppo_dlogp_refused(call_facts(h), n_steps, agent, new_log_probs, old_log_probs, advantages, factor, clip_param, scale, dlogp)))
+    return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  SdcPpoDlogp P;
+  std::memset(&P, 0, sizeof(P));
+  P.n = (long long)n_steps * h->cfg.n_envs;
+  P.agent = agent;
+  P.new_lp = new_log_probs;
+  P.old_lp = old_log_probs;
+  P.adv = advantages;
+  P.factor = factor;
+  P.lo = 1.0 - clip_param;
+  P.hi = 1.0 + clip_param;
+  P.scale = scale;
+  P.dlogp = dlogp;
+  return launched("sdc_ppo_dlogp_kernel", sdc_ppo_dlogp_launch(P, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int sdc_actor_backward(sdc_handle* h, int agent_slot, const float* obs, long long row_stride, long long n_rows, const int32_t* actions,
+                       long long action_stride, const float* dlogp, double dent, float* grads, double* grad_sq, void* stream) {
+  if (refused(sdc_actor_backward_refused(call_facts(h), agent_slot, obs, row_stride, n_rows, actions, action_stride, dlogp, dent, grads, grad_sq)))
+    return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!h->actor_grad_part && dev_alloc(h, &h->actor_grad_part, (size_t)SDC_ACTOR_GRAD_MAX_BLOCKS * SDC_ACTOR_N_PARAMS, false) != 0) return -1;
+  SdcActorGrad P;
+  std::memset(&P, 0, sizeof(P));
+  P.actor = h->actor_eval_dev + agent_slot;
+  P.actor_t = h->actor_grad_dev + agent_slot;
+  P.obs = obs;
+  P.row_stride = row_stride;
+  P.n_rows = n_rows;
+  P.actions = actions;
+  P.action_stride = action_stride;
+  P.dlogp = dlogp;
+  P.dent = dent;
+  P.part = h->actor_grad_part;
+  if (const int rc = launched("sdc_actor_grad_kernel", sdc_actor_grad_launch(P, h->actor_activation[agent_slot], st))) return rc;
+  if (const int rc = launched("sdc_actor_grad_reduce_kernel",
+                              sdc_actor_grad_reduce_launch(SdcActorGradReduce{sdc_actor_grad_blocks(n_rows), h->actor_grad_part, grads}, st)))
+    return rc;
+  if (!grad_sq) return 0;
+  return launched("sdc_actor_grad_sq_kernel", sdc_actor_grad_sq_launch(SdcActorGradSq{grads, grad_sq}, st));
 }
 
 int sdc_set_plan_critic(sdc_handle* h, double weight) {

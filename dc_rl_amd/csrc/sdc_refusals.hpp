@@ -616,6 +616,40 @@ static inline SdcMsg sdc_ppo_terms_refused(const SdcCallFacts& f, const int n_st
   return std::nullopt;
 }
 
+// ---- the actors' gradient --------------------------------------------------------------------------------------------------------------------
+// (pure functions of their arrays, as the calls above; their texts are held by tests/test_actor_grad_abi.py)
+static inline SdcMsg sdc_ppo_dlogp_refused(const SdcCallFacts& f, const int n_steps, const int agent, const float* new_log_probs,
+                                           const float* old_log_probs, const float* advantages, const float* factor, const double clip_param,
+                                           const double scale, const float* dlogp) {
+  static const std::string w = "sdc_ppo_dlogp: ";
+  if (!f.handle) return w + "null handle";
+  if (n_steps < 1) return w + "n_steps = " + std::to_string(n_steps) + " must be positive";
+  if (agent < 0 || agent > 2) return w + "agent = " + std::to_string(agent) + " outside [0, 2]";
+  if (!new_log_probs || !old_log_probs || !advantages || !dlogp)
+    return w + "null array (new_log_probs, old_log_probs, advantages and dlogp are required)";
+  if ((sdc_addr_bits(new_log_probs, old_log_probs, advantages, factor, dlogp) & 3u) != 0)
+    return w + "new_log_probs / old_log_probs / advantages / factor / dlogp not dword-aligned";
+  if (!(clip_param >= 0.0 && clip_param < 1.0)) return w + "clip_param = " + std::to_string(clip_param) + " outside [0, 1)";
+  if (!std::isfinite(scale)) return w + "scale = " + std::to_string(scale) + " is not finite";
+  return std::nullopt;
+}
+static inline SdcMsg sdc_actor_backward_refused(const SdcCallFacts& f, const int agent_slot, const float* obs, const long long row_stride,
+                                                const long long n_rows, const int32_t* actions, const long long action_stride,
+                                                const float* dlogp, const double dent, const float* grads, const double* grad_sq) {
+  static const std::string w = "sdc_actor_backward: ";
+  if (!f.handle) return w + "null handle";
+  if (agent_slot < 0 || agent_slot > 2) return w + "agent_slot = " + std::to_string(agent_slot) + " outside [0, 2]";
+  if (!f.actor_set[agent_slot]) return w + "no actor is set for agent_slot " + std::to_string(agent_slot) + " (sdc_set_actor first)";
+  if (n_rows < 1) return w + "n_rows = " + std::to_string(n_rows) + " must be positive";
+  if (!obs || !actions || !dlogp || !grads) return w + "null array (obs, actions, dlogp and grads are required)";
+  if ((sdc_addr_bits(obs, actions, dlogp, grads) & 3u) != 0) return w + "obs / actions / dlogp / grads not dword-aligned";
+  if ((sdc_addr_bits(grad_sq) & 7u) != 0) return w + "grad_sq not 8-byte aligned";
+  if (row_stride < 26) return w + "row_stride = " + std::to_string(row_stride) + " below a row's 26 floats";
+  if (action_stride < 1) return w + "action_stride = " + std::to_string(action_stride) + " must be positive";
+  if (!std::isfinite(dent)) return w + "dent = " + std::to_string(dent) + " is not finite";
+  return std::nullopt;
+}
+
 // ---- the cross-entropy planners -------------------------------------------------------------------------------------------------------------
 // The parameter ranges sdc_plan_cem and sdc_plan_cem_groups refuse alike.  The callers run them in their own order.
 static inline SdcMsg sdc_cem_iters_refused(const std::string& w, const int n_iters, const int iter0) {

@@ -340,6 +340,48 @@ class PPOTerms:
                     approx_kl=-float(s[2]) / n, entropy=float(s[3]) / n, clip_frac=float(s[4]) / n)
 
 
+class ActorGrads:
+    """What SdcEngine.actor_backward hands back for one agent, on the engine's device: `flat` fp32 [6391], the gradient with respect to
+    the float members of sdc_actor_params in declaration order (ln0_gamma .. b3, torch's [out][in] layout), and `sq_norm` fp64 0-dim,
+    the sum of its squares in the fixed order include/sustaindc_hip.h states."""
+    __slots__ = ("flat", "sq_norm")
+
+    def __init__(self, flat, sq_norm):
+        self.flat, self.sq_norm = flat, sq_norm
+
+    def named(self) -> dict:
+        """{sdc_actor_params field: a shaped view of `flat`}"""
+        out, at = {}, 0
+        for field, shape in _ACTOR_SHAPES.items():
+            n = int(np.prod(shape))
+            out[field] = self.flat[at:at + n].view(shape)
+            at += n
+        return out
+
+    def state_dict(self) -> dict:
+        """the same views under the reference's StochasticPolicy state_dict keys"""
+        return {_ACTOR_SD_KEYS[k]: v for k, v in self.named().items()}
+
+    def norm(self):
+        """the gradient's 2-norm, fp64 0-dim on the device"""
+        return self.sq_norm.sqrt()
+
+    def clip_(self, max_norm: float):
+        """torch's clip_grad_norm_ rule on `flat`, in place: flat *= min(1, max_norm / (norm + 1e-6)); -> the norm before clipping.
+        (sq_norm is left as the call computed it.)"""
+        total = self.norm()
+        self.flat.mul_((float(max_norm) / (total + 1e-6)).clamp(max=1.0).to(self.flat.dtype))
+        return total
+
+    def assign_to(self, module):
+        """.grad of every parameter of `module` that has the reference's keys (a module without a feature_norm takes the rest)"""
+        sd = self.state_dict()
+        for name, p in module.named_parameters():
+            if name not in sd:
+                raise KeyError(f"assign_to: the module's parameter {name!r} is none of the actor's {sorted(sd)}")
+            p.grad = sd[name].detach().to(device=p.device, dtype=p.dtype).clone()
+
+
 class MPCCarry:
     """What `rollout_cem_stats` leaves of the planner's state, on the engine's device: `probs` float64 [H, N, 3, 3] and `best_seq` int32
     [H, N, 3], the arrays of the call (a caller's own are the same tensors), whose first `steps` steps hold the last planned decision's
@@ -1010,6 +1052,65 @@ class SdcEngine:
         _, logp, ent = self.evaluate_actions(batch.obs[:T], batch.actions, agents=(a,))
         old = batch.action_log_probs if old_log_probs is None else old_log_probs
         return self.ppo_terms(a, logp, old, batch.normalized_advantages(), clip_param, factor=factor, entropy=ent)
+
+    # ------------------------------------------------------------------ the actors' gradient
+    def ppo_dlogp(self, agent: int, new_log_probs, old_log_probs, advantages, clip_param: float = 0.2, factor=None, scale=None):
+        """The derivative of the reference's policy loss -scale * sum(factor * min(ratio * A, clamp(ratio) * A)) with respect to each
+        stored log-probability of agent `agent` (sdc_ppo_dlogp: elementwise in fp64 as ppo_terms, rounded once; stream-ordered):
+        tensors as ppo_terms' -> fp32 [T, N]; zero where the clipped branch is the minimum, as torch differentiates min and clamp.
+        `scale`: default 1 / (T N), the reference's mean.  ValueError for another tensor or agent and for what the library refuses."""
+        t, who, N = self.torch, "ppo_dlogp", self.n_envs
+        a = A.agent_slot(who, agent)
+        A.device_tensor(new_log_probs, who, "new_log_probs", t.float32, (A.SOME, N, 3), "(T, n_envs, 3)", self.device)
+        T = int(new_log_probs.shape[0])
+        A.device_tensor(old_log_probs, who, "old_log_probs", t.float32, (T, N, 3), "(T, n_envs, 3)", self.device)
+        A.device_tensor(advantages, who, "advantages", t.float32, (T, N), "(T, n_envs)", self.device)
+        if factor is not None:
+            A.device_tensor(factor, who, "factor", t.float32, (T, N), "(T, n_envs)", self.device)
+        scale = 1.0 / (T * N) if scale is None else A.finite_float(who, "scale", scale)
+        out = t.empty((T, N), dtype=t.float32, device=self.device)
+        self._behind_torch_stream()
+        self._call(self.lib.sdc_ppo_dlogp, T, a, _p(new_log_probs), _p(old_log_probs), _p(advantages), _p(factor), float(clip_param), scale,
+                   _p(out), self._stream(), refuses=True, wrote=(new_log_probs, old_log_probs, advantages, factor, out))
+        return out
+
+    def actor_backward(self, agent: int, obs, actions, dlogp, dent: float = 0.0, per_agent=None) -> ActorGrads:
+        """The gradient of L = sum_r dlogp[r] * logp_r(actions[r]) + dent * sum_r entropy_r with respect to every parameter of agent
+        `agent`'s actor (the one last given to set_actor), over stored rows (sdc_actor_backward: the forward recomputed per 16-row
+        tile, the backward on the matrix cores, fixed summation order: the same call gives the same bits; stream-ordered).  `obs` as
+        actor_logits' (dense (..., 26) or (..., 3, 26) read in place; `per_agent` says which); `actions` int32 of the rows' shape (...)
+        or (..., 3), of which the agent's column is read; `dlogp` fp32 (...), contiguous on this engine's device.  -> ActorGrads.
+        ValueError for another tensor or agent, before set_actor(agent), and for a dent that is not finite."""
+        t, who = self.torch, "actor_backward"
+        a = A.agent_slot(who, agent)
+        offset, stride, rows, shape = A.actor_rows(who, obs, a, per_agent, self.device)
+        lead = shape[:-1]
+        act_offset, act_stride = A.actor_row_values(who, actions, "actions", t.int32, lead, a, self.device)
+        A.device_tensor(dlogp, who, "dlogp", t.float32, lead, None, self.device)
+        dent = A.finite_float(who, "dent", dent)
+        res = ActorGrads(t.empty(L.ACTOR_N_PARAMS, dtype=t.float32, device=self.device), t.empty((), dtype=t.float64, device=self.device))
+        self._behind_torch_stream()
+        self._call(self.lib.sdc_actor_backward, a, C.c_void_p(obs.data_ptr() + 4 * offset), stride, rows,
+                   C.c_void_p(actions.data_ptr() + 4 * act_offset), act_stride, _p(dlogp), dent, _p(res.flat), _p(res.sq_norm),
+                   self._stream(), refuses=True, wrote=(obs, actions, dlogp, res.flat, res.sq_norm))
+        return res
+
+    def actor_grads(self, batch, agent: int, clip_param: float = 0.2, entropy_coef: float = 0.01, factor=None, old_log_probs=None):
+        """The gradient of the reference's actor loss (happo.py update: policy_loss - entropy_coef * dist_entropy, every active mask
+        one) for one agent of an OnPolicyBatch with the actor NOW set: evaluate_actions -> ppo_terms -> ppo_dlogp -> actor_backward
+        with batch.normalized_advantages(), scale = 1 / (T N) and dent = -entropy_coef / (T N); `factor` and `old_log_probs` as
+        actor_update_terms'.  -> (ActorGrads, PPOTerms).  The optimiser step is the caller's: step it over the 6391 values (assign_to)
+        and call set_actor."""
+        a = A.agent_slot("actor_grads", agent)
+        T = batch.n_steps
+        n = T * self.n_envs
+        obs = batch.obs[:T]
+        _, logp, ent = self.evaluate_actions(obs, batch.actions, agents=(a,))
+        old = batch.action_log_probs if old_log_probs is None else old_log_probs
+        adv = batch.normalized_advantages()
+        terms = self.ppo_terms(a, logp, old, adv, clip_param, factor=factor, entropy=ent)
+        dlogp = self.ppo_dlogp(a, logp, old, adv, clip_param, factor=factor, scale=1.0 / n)
+        return self.actor_backward(a, obs, batch.actions, dlogp, dent=-float(entropy_coef) / n, per_agent=True), terms
 
     # ------------------------------------------------------------------ state access (parity injection / checkpoint)
     def _state_array(self, name):

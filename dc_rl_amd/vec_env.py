@@ -741,6 +741,18 @@ class SustainDCVecEnv(ShareVecEnv):
         """One agent's PPO terms over an OnPolicyBatch with the actor now set (SdcEngine.actor_update_terms)"""
         return self.engine.actor_update_terms(batch, agent, *args, **kw)
 
+    def ppo_dlogp(self, agent, new_log_probs, old_log_probs, advantages, *args, **kw):
+        """The PPO loss's derivative per stored log-probability for one agent (SdcEngine.ppo_dlogp, which documents the arguments)"""
+        return self.engine.ppo_dlogp(agent, new_log_probs, old_log_probs, advantages, *args, **kw)
+
+    def actor_backward(self, agent, obs, actions, dlogp, *args, **kw):
+        """The gradient of one actor's loss with respect to its parameters over stored rows (SdcEngine.actor_backward) -> ActorGrads"""
+        return self.engine.actor_backward(agent, obs, actions, dlogp, *args, **kw)
+
+    def actor_grads(self, batch, agent, *args, **kw):
+        """The gradient of the reference's actor loss for one agent of an OnPolicyBatch (SdcEngine.actor_grads) -> (ActorGrads, PPOTerms)"""
+        return self.engine.actor_grads(batch, agent, *args, **kw)
+
     def gae(self, rew, done, values, *args, **kw):
         """Returns, advantages and masks of a collected rollout (SdcEngine.gae, which documents the arguments and the result)"""
         return self.engine.gae(rew, done, values, *args, **kw)

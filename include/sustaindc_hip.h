@@ -656,8 +656,8 @@ int sdc_action_log_probs(sdc_handle* h, int n_steps, const int32_t* actions, con
 /* EVALUATE THE ACTORS ON STORED ROWS.  replaces: the forward pass of the reference's evaluate_actions over a stored buffer
  * (harl/algorithms/actors/on_policy_base.py evaluate_actions -> StochasticPolicy.evaluate_actions), which harl/runners/on_policy_ha_runner.py
  * runs over the whole buffer before and after every agent's update for the HAPPO factor, and the terms harl/algorithms/actors/happo.py and
- * mappo.py build from its log-probabilities (imp_weights, the clipped surrogate, the entropy).  No gradient: the backward pass, the
- * optimiser and the critic's value loss are not here.  Both calls are pure functions of their arrays, all device memory: they read no env
+ * mappo.py build from its log-probabilities (imp_weights, the clipped surrogate, the entropy).  No gradient: the backward pass is
+ * sdc_actor_backward (THE ACTORS' GRADIENT below); the optimiser and the critic's value loss are not here.  Both calls are pure functions of their arrays, all device memory: they read no env
  * state and move nothing in the engine; each is ordered on `stream` with no synchronisation.
  * sdc_actor_evaluate: the logits of agent_slot's network -- the one last given to sdc_set_actor for that slot, the network stated at
  * sdc_set_actor, fp32, the hidden layers on fp32-input matrix instructions, 16 rows per wavefront (csrc/sdc_actor_eval.hpp) -- for n_rows
@@ -700,6 +700,54 @@ int sdc_actor_evaluate(sdc_handle* h, int agent_slot, const float* obs, long lon
 int sdc_ppo_terms(sdc_handle* h, int n_steps, int agent, const float* new_log_probs, const float* old_log_probs, const float* entropy,
                   const float* advantages, const float* factor, double clip_param, float* ratio, float* surr, float* factor_out,
                   double* stats, void* stream);
+
+/* THE ACTORS' GRADIENT.  replaces: loss.backward() of the reference's actor update (harl/algorithms/actors/happo.py update:
+ * policy_loss - entropy_coef * dist_entropy, differentiated by autograd through StochasticPolicy.evaluate_actions) -- the gradient with
+ * respect to every parameter of one agent's network, on fp32-input matrix instructions, in a fixed summation order.  NOT here: the
+ * optimiser step, the critic's value loss and its gradient, minibatch shuffling (a caller steps an optimiser over the
+ * SDC_ACTOR_N_PARAMS values and calls sdc_set_actor).  Both calls are pure functions of their arrays, all device memory: they read no
+ * env state and move nothing in the engine; each is ordered on `stream` with no synchronisation.
+ * sdc_ppo_dlogp: the loss's derivative per stored log-probability, ONE launch of sdc_ppo_dlogp_kernel.  Per element i = t N + n < T N
+ * with j = 3 i + agent, in fp64 with no fused multiply-add, in sdc_ppo_terms' words (lo = 1 - clip_param, hi = 1 + clip_param):
+ *     lr = (double)new_log_probs[j] - (double)old_log_probs[j];   r = exp(lr);   A = (double)advantages[i];   F = factor ? (double)factor[i] : 1.0
+ *     s1 = r * A;   rc = r < lo ? lo : r;   rc = rc > hi ? hi : rc;   s2 = rc * A;   clipped = r < lo || r > hi
+ *     open = !clipped || s1 < s2
+ *     dlogp[i] = (float)(open ? -(((scale * F) * A) * r) : 0.0)
+ * which is d(-scale * sum_i F min(s1, s2)) / d new_log_probs[j] as torch differentiates it (torch.min halves a tie, clamp passes the
+ * gradient on its closed interval: together the rule `open`).  scale: a finite double; 1 / (T N) is the reference's mean with every
+ * active mask one.  Refused: what sdc_ppo_terms refuses about the arguments they share, a null or misaligned dlogp, a scale not finite.
+ * sdc_actor_backward: with logp_r(a) and H_r the log-probability and the entropy of row r's categorical distribution under the network
+ * last given to sdc_set_actor for agent_slot, the gradient of
+ *     L = sum_r dlogp[r] * logp_r(actions_r) + dent * sum_r H_r
+ * with respect to the float members of sdc_actor_params in declaration order (ln0_gamma .. b3, torch's [out][in] layout), fp32
+ * [SDC_ACTOR_N_PARAMS] in `grads`.  Row r is the 26 floats at obs + r * row_stride (as sdc_actor_evaluate's), its action
+ * actions[r * action_stride] (1: dense; 3 with actions advanced by agent: the agent's column of [T][N][3]) -- a value outside 0 .. 2 is
+ * an all-zero one-hot: it enters arithmetic only, never an address --, its coefficient dlogp[r], dense; dent = dL/dH_r is the same for
+ * every row (the reference: -entropy_coef / n_rows).  The backward is the textbook one over the call's own forward
+ * (csrc/sdc_actor_grad.hpp, fp32): with p = softmax(logits)
+ *     dlogit_c = dlogp[r] * (1[c == a_r] - p_c) - dent * (p_c * (log p_c + H_r))
+ *     Linear:     dW += dz x^T, db += dz, dx = W^T dz
+ *     LayerNorm:  dgain += dy * n, dbias += dy, dn = dy * gain, dx = rs * (dn - mean(dn) - n * mean(dn * n)), n and rs the forward's
+ *                 (the forward's clamp of the variance at 0 is not differentiated)
+ *     tanh' = 1 - h * h from the forward's own h;  relu' = [z > 0]
+ * The feature LayerNorm's gain and bias receive gradients when use_feature_normalization is on and exact zeros when it is off; nothing
+ * is propagated to obs.  Doubling dlogp and dent doubles every gradient exactly; all-zero coefficients give all-zero gradients.
+ * THE ORDER OF EVERY SUM IS FIXED -- no atomics, the same call gives the same bits on every run: B = min(ceil(n_rows / 64),
+ * SDC_ACTOR_GRAD_MAX_BLOCKS) workgroups (a function of n_rows alone) each write one fp32 partial [SDC_ACTOR_N_PARAMS] into a buffer
+ * of the handle's, allocated on first use (sdc_actor_grad_kernel; within it: csrc/sdc_actor_grad.hpp); sdc_actor_grad_reduce_kernel
+ * adds a parameter's B partials in workgroup order in fp64 and rounds once to fp32.
+ * grad_sq [1] fp64 or NULL: the sum of squares of the STORED fp32 grads, so that a host redoes it bit for bit
+ * (sdc_actor_grad_sq_kernel, one workgroup of 256 lanes): lane l starts from 0 and adds (double)grads[j] * (double)grads[j] for
+ * j = l, l + 256, ... < SDC_ACTOR_N_PARAMS in that order; then for half = 128, 64, .. 1 lane l < half adds lane l + half; lane 0's sum.
+ * Refused (-2 and a message, nothing enqueued): a null handle; agent_slot outside 0 .. 2; no actor set for that slot; n_rows < 1; a
+ * null obs, actions, dlogp or grads; one of them not dword-aligned; grad_sq not 8-byte aligned; row_stride < 26; action_stride < 1;
+ * dent not finite. */
+#define SDC_ACTOR_N_PARAMS 6391
+#define SDC_ACTOR_GRAD_MAX_BLOCKS 256
+int sdc_ppo_dlogp(sdc_handle* h, int n_steps, int agent, const float* new_log_probs, const float* old_log_probs, const float* advantages,
+                  const float* factor, double clip_param, double scale, float* dlogp, void* stream);
+int sdc_actor_backward(sdc_handle* h, int agent_slot, const float* obs, long long row_stride, long long n_rows, const int32_t* actions,
+                       long long action_stride, const float* dlogp, double dent, float* grads, double* grad_sq, void* stream);
 
 /* PLAN FORECAST: what the plan calls' rollouts believe the traces of the next n_steps steps are.  Without one a plan call's rollouts
  * read the episode's own feature rows -- the real workload, carbon intensity, dry bulb (with the weather noise the episode drew) and wet
