@@ -839,7 +839,7 @@ int sdc_reset(sdc_handle* h, const uint8_t* mask_host, const sdc_reset_override*
 
 int sdc_step(sdc_handle* h, const int32_t* actions, float* obs, float* share_obs, float* rew, uint8_t* done,
              float* info, float* final_obs, void* stream) {
-  if (refused(sdc_step_refused(stepping_facts(h), actions, obs, rew, done))) return -2;
+  if (refused(sdc_step_refused(stepping_facts(h), actions, obs, rew, done, info))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int N = h->cfg.n_envs;

@@ -114,11 +114,15 @@ static inline const char* sdc_reset_refused(const SdcCallFacts& f, const uint8_t
   return nullptr;
 }
 
-static inline const char* sdc_step_refused(const SdcSteppingFacts& f, const int32_t* actions, const float* obs, const float* rew, const uint8_t* done) {
+// info: optional (NULL: not wanted) -- but for verify mode, whose kernel reads info[energy_z] and raises its fault bit there.  (A caller of
+// this rule that does not say has said NULL: the refusing side.)
+static inline const char* sdc_step_refused(const SdcSteppingFacts& f, const int32_t* actions, const float* obs, const float* rew, const uint8_t* done,
+                                           const float* info = nullptr) {
   if (!f.handle || !obs || !rew || !done) return "sdc_step: null argument";
   if (!actions && !f.all_policies) return "sdc_step: actions may only be NULL when every agent slot has a policy";
   if (!f.started) return "sdc_step: sdc_reset must be called first";
   if (f.left <= 0) return "sdc_step: an environment has finished its episode; call sdc_reset (auto_reset is off)";
+  if ((f.debug_flags & SDC_DEBUG_VERIFY) && !info) return "sdc_step: verify mode reports through info; info may not be NULL";
   return nullptr;
 }
 

@@ -107,8 +107,8 @@ typedef struct sdc_handle sdc_handle;
  * A bit without a name sends the call to the general kernel as well. */
 #define SDC_DEBUG_VERIFY 1           /* bit 0, PUBLIC MODE: after every sdc_step check the incremental reward state (the four rank
                                         windows, running sums) and the reported z-score against an exact bisection and a direct fp64
-                                        pass over each env's history (slow; a mismatch sets SDC_FAULT_ORDER_STAT).  The multi-step
-                                        entry points refuse it */
+                                        pass over each env's history (slow; a mismatch sets SDC_FAULT_ORDER_STAT in info[fault],
+                                        so sdc_step refuses a NULL info in this mode).  The multi-step entry points refuse it */
 #define SDC_DEBUG_WHY_REBUILD 2      /* bit 1, MEASUREMENT MODE: info[reserved]'s path codes 3 / 5 carry why a rebuild happened */
 #define SDC_DEBUG_PHASES 8           /* bit 3, MEASUREMENT MODE: per-wavefront phase durations in info[40..43], the rare paths the
                                         wavefront's step took in info[reserved] above bit 3 */
@@ -282,7 +282,9 @@ int sdc_reset(sdc_handle* h, const uint8_t* mask_host, const sdc_reset_override*
  * (harlsustaindc_env.py:106-131, env_wrappers.py:168-192) for all N envs.
  * actions [N][3] int32 (ls, dc, bat) in {0,1,2}; obs [N][3][26]; share_obs [N][29]; rew [N][3];
  * done [N] u8; info [N][SDC_INFO_DIM] f32; final_obs [N][3][26] receives the pre-reset observation of
- * envs that finished ("original_obs"); info / final_obs / share_obs may be NULL. */
+ * envs that finished ("original_obs"); info / final_obs / share_obs may be NULL -- but in verify mode
+ * (debug_flags SDC_DEBUG_VERIFY), whose check reads info[energy_z] and reports through info[fault]: there a NULL info
+ * is refused. */
 int sdc_step(sdc_handle* h, const int32_t* actions, float* obs, float* share_obs, float* rew, uint8_t* done,
              float* info, float* final_obs, void* stream);
 

@@ -137,6 +137,11 @@ ok(E, facts=dict(all_policies=1), actions=0)
 no(E, "sdc_reset must be called first", facts=dict(started=0))
 no(E, "an environment has finished its episode; call sdc_reset (auto_reset is off)", facts=dict(t_rel=where(Z, _4=T)))
 ok(E, facts=dict(t_rel=where(Z, _4=T - 1)))
+ok(E, share_obs=0, info=0, final_obs=0)      # (the optional outputs)
+no(E, "verify mode reports through info; info may not be NULL", facts=dict(debug_flags=1), info=0)
+ok(E, facts=dict(debug_flags=1))
+ok(E, facts=dict(debug_flags=2), info=0)      # (another bit: info stays optional)
+no(E, "an environment has finished its episode; call sdc_reset (auto_reset is off)", facts=dict(debug_flags=1, t_rel=where(Z, _4=T)), two=True, info=0)
 no(E, "null argument", two=True, done=0, actions=0)
 no(E, "actions may only be NULL when every agent slot has a policy", facts=dict(started=0), two=True, actions=0)
 no(E, "sdc_reset must be called first", facts=dict(started=0, t_rel=ALL(T)), two=True)

@@ -199,6 +199,59 @@ def make_engine():
     return eng
 
 
+def test_verify_mode_refuses_a_null_info_and_launches_nothing():
+    """sdc_step's `info` is optional -- but sdc_reward_verify_kernel reads info[energy_z] and writes info[fault] of every env: in verify mode a
+    NULL info is refused (the table's row with the fact debug_flags = 1) before anything is launched, from the raw call and from
+    SdcEngine.step(want_info=False) alike, and the engine goes on."""
+    import torch
+    from tests.test_gpu_mark import _mk
+    eng = _mk(RC.N, cap=RC.HIST_CAP, ep=RC.T, auto_reset=False, debug_flags=L.DEBUG_VERIFY)
+    try:
+        rig = Rig(eng)
+        cases = [c for c in RC.CASES if c.entry == "sdc_step" and c.text is not None and c.facts == dict(debug_flags=1)]
+        assert [c.text for c in cases] == ["sdc_step: verify mode reports through info; info may not be NULL"] and cases[0].args == dict(info=0)
+        before = [eng.get_state(name) for name in ("record", "header", "hist")]
+        assert eng.last_step_kernel() == ""
+        assert rig.call(cases[0]) == (-2, cases[0].text)
+        acts = torch.ones((RC.N, 3), dtype=torch.int32, device="cuda")
+        with pytest.raises(L.SdcError, match="verify mode reports through info"):
+            eng.step(acts, want_info=False)
+        assert eng.last_step_kernel() == "" and eng.steps_to_episode_end() == RC.T      # no step kernel, no step counted
+        for x, name in zip(before, ("record", "header", "hist")):
+            y = eng.get_state(name)
+            assert np.array_equal(x, y, equal_nan=name == "hist"), name
+        eng.step(acts)
+        assert eng.last_step_kernel() != "" and eng.steps_to_episode_end() == RC.T - 1
+        assert (eng.info[:, L.INFO_IDX["fault"]] == 0).all() and (eng.get_state("order_stat_sticky") == 0).all()
+    finally:
+        eng.close()
+
+
+def test_the_optional_outputs_may_all_be_null_without_verify_mode():
+    """share_obs, info and final_obs all NULL through the raw call (debug_flags 0), two steps: obs, rew and done are the same bits as a
+    twin's that passes every array."""
+    import torch
+    from tests.test_gpu_mark import _mk
+    a, b = (_mk(RC.N, cap=RC.HIST_CAP, ep=RC.T, auto_reset=False) for _ in range(2))
+    try:
+        g = torch.Generator(device="cpu").manual_seed(3)
+        acts = torch.randint(0, 3, (2, RC.N, 3), dtype=torch.int32, generator=g).cuda()
+        p = lambda t: C.c_void_p(t.data_ptr())
+        share0 = a.share_obs.clone()
+        for t in range(2):
+            rc = a.lib.sdc_step(a._h, p(acts[t]), p(a.obs), None, p(a.rew), p(a.done), None, None, None)
+            assert rc == 0, a.lib.sdc_last_error().decode()
+            b.step(acts[t])
+            torch.cuda.synchronize()
+            for name in ("obs", "rew", "done"):
+                assert torch.equal(getattr(a, name), getattr(b, name)), (t, name)
+        assert torch.equal(a.share_obs, share0)      # (not given: not written)
+        assert a.steps_to_episode_end() == b.steps_to_episode_end() == RC.T - 2
+    finally:
+        a.close()
+        b.close()
+
+
 def test_every_reachable_refusal_of_the_table_with_its_code_and_text():
     eng = make_engine()
     try:

@@ -190,7 +190,7 @@ static bool answer(const std::string& e) {
     if (get("mask") && mask) m8.assign(mask->begin(), mask->end());
     out(sdc_reset_refused(f, get("mask") && mask ? m8.data() : nullptr, I("ovr", 0) ? &o : nullptr));
   } else if (e == "sdc_step") {
-    out(sdc_step_refused(f, P<int32_t>("actions"), P<float>("obs"), P<float>("rew"), P<uint8_t>("done")));
+    out(sdc_step_refused(f, P<int32_t>("actions"), P<float>("obs"), P<float>("rew"), P<uint8_t>("done"), P<float>("info")));
   } else if (e == "sdc_rollout") {
     out(sdc_rollout_refused(f, n_steps, P<int32_t>("actions"), P<float>("obs"), P<float>("rew"), P<uint8_t>("done")));
   } else if (e == "sdc_set_actor") {
