@@ -3,68 +3,35 @@
 // log-probabilities that come of it, for sdc_actor_evaluate and sdc_ppo_terms (sdc_capi.hip; the plans, the lane mappings and the
 // address bounds: sdc_actor_eval.hpp; the arithmetic: include/sustaindc_hip.h EVALUATE THE ACTORS ON STORED ROWS).
 //
-// The network's shape is sdc_critic.hip's, and its arithmetic is taken from the functions that file's forward is made of
-// (sdc_critic::epilogue, all_sum2, all_sum, unit_vector over sdc_act::activate): 26 inputs in 7 k-steps, and three outputs.  The PPO
-// terms are fp64 with nothing fused (the library is built with -ffp-contract=off; the pragma below says it for this file whatever the
-// flags; the network's last layer names its fmaf itself, as the critic's does).
+// The network is sdc_rowmlp.hpp's, as the critic's (26 inputs in 7 k-steps, three outputs: sdc_actor_forward.hpp), and so is the
+// kernel's plumbing.  The PPO terms are fp64 with nothing fused (the library is built with -ffp-contract=off; the pragma below says it
+// for this file whatever the flags; the network's last layer names its fmaf itself).
 #include <hip/hip_runtime.h>
 
 #include "sdc_actor_eval.hpp"
 #include "sdc_actor_forward.hpp"
-#include "sdc_critic.hpp"
+#include "sdc_rowmlp.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-using sdc_act::f4;
-
-constexpr int WAVES = SDC_ACTOR_EVAL_BLOCK / 64;
-constexpr int TILE_DW = SDC_AEV_ROWS * SDC_AEV_IN;            // 416
-constexpr int TILE_LOADS = (TILE_DW + 63) / 64;               // 7
-static_assert(sizeof(SdcActorEvalDev) + WAVES * TILE_DW * sizeof(float) <= 40 * 1024, "four workgroups' LDS fit a CU");
-static_assert(sizeof(SdcActorEvalDev) % sizeof(uint4) == 0, "copied as 16-byte units");
-static_assert(SDC_AEV_H == SDC_CRITIC_H && SDC_AEV_ROWS == SDC_CRITIC_ROWS, "the critic's epilogue: 64 units, 16 rows per wavefront");
+constexpr int TILE_DW = sdc_rowmlp::TILE_DW<SDC_AEV_IN>;              // 416
+constexpr int TILE_LOADS = sdc_rowmlp::TILE_LOADS<SDC_AEV_IN>;        // 7
 static_assert((SDC_PPO_BLOCK & (SDC_PPO_BLOCK - 1)) == 0 && SDC_PPO_BLOCK % 64 == 0, "the tree halves whole wavefronts");
 
-struct alignas(16) Lds {      // (16-byte aligned: the A operands and the per-unit vectors are read as 16-byte units)
-  SdcActorEvalDev actor;
-  float tile[WAVES][TILE_DW];
-};
-
-__device__ __forceinline__ void actor_to_lds(SdcActorEvalDev* dst, const SdcActorEvalDev* src) {
-  const uint4* const s = reinterpret_cast<const uint4*>(src);
-  uint4* const d = reinterpret_cast<uint4*>(dst);
-  for (int u = (int)threadIdx.x; u < (int)(sizeof(SdcActorEvalDev) / sizeof(uint4)); u += SDC_ACTOR_EVAL_BLOCK) d[u] = s[u];
-}
-
-// A wavefront's rows row0 .. row0 + 15 (n_rows in all, `stride` floats apart): lane l takes tile dwords u = l, l + 64, ... of the 416,
-// dword u = entry u % 26 of tile row u / 26; a dword of a row at or past n_rows is not loaded (0)
-__device__ __forceinline__ void fetch(float (&v)[TILE_LOADS], const float* obs, const long long stride, const long long row0,
-                                      const long long n_rows, const int lane) {
-  const long long left = n_rows - row0;
-  const int valid = left >= SDC_AEV_ROWS ? SDC_AEV_ROWS : (left > 0 ? (int)left : 0);      // rows that exist
-#pragma unroll
-  for (int j = 0; j < TILE_LOADS; j++) {
-    const int u = lane + 64 * j;
-    const int r = u / SDC_AEV_IN, k = u - r * SDC_AEV_IN;
-    v[j] = 0.0f;
-    if (r < valid) v[j] = obs[(row0 + r) * stride + k];      // (r < valid <= 16 implies u < 416)
-  }
-}
+using Lds = sdc_rowmlp::Lds<SdcActorEvalDev, SDC_AEV_IN>;
+static_assert(sizeof(Lds) <= 40 * 1024, "four workgroups' LDS fit a CU");
 
 // The forward itself: sdc_actor_forward.hpp (shared with sdc_actor_grad.hip), here with nothing kept.
-// (the activation is a template parameter, as the closed loop's: chosen per element it is a branch around every exp -> rcp chain)
 __device__ __forceinline__ void forward(const SdcActorEvalDev* W, float (&x)[SDC_AEV_S1], const int lane, float (&lg)[SDC_AEV_OUT]) {
-  sdc_aev::NoTape none;
+  sdc_rowmlp::NoTape none;
   if (__builtin_amdgcn_readfirstlane((W->flags >> 1) & 3) == 1) sdc_aev::forward_kind<1>(W, x, lane, lg, none);
   else sdc_aev::forward_kind<0>(W, x, lane, lg, none);
 }
 
 // One pass of a wavefront: the fetched dwords through the wavefront's tile -> the logits of row (lane & 15), in every lane of that
-// column.  The barrier orders the tile's stores (and, in the first pass, the actor's copy) before the reads; the tile is the wavefront's
-// own, and LDS operations of one wavefront complete in order, so the next pass's stores need no second barrier.  Behind the tile's
-// reads the NEXT pass's rows are fetched (next0; past the grid's last pass: nothing is loaded), under this pass's arithmetic.
+// column; behind the tile's reads the NEXT pass's rows are fetched (the barrier and the order: sdc_critic.hip's pass).
 __device__ __forceinline__ void pass(Lds& L, float (&v)[TILE_LOADS], const SdcActorEval& P, const long long next0, const int wave,
                                      const int lane, float (&lg)[SDC_AEV_OUT]) {
 #pragma unroll
@@ -81,8 +48,8 @@ __device__ __forceinline__ void pass(Lds& L, float (&v)[TILE_LOADS], const SdcAc
     x[s] = 0.0f;
     if (k < SDC_AEV_IN) x[s] = L.tile[wave][e * SDC_AEV_IN + k];
   }
-  fetch(v, P.obs, P.row_stride, next0, P.n_rows, lane);
-  forward(&L.actor, x, lane, lg);
+  sdc_rowmlp::fetch<SDC_AEV_IN>(v, P.obs, P.row_stride, next0, P.n_rows, lane);
+  forward(&L.net, x, lane, lg);
 }
 
 }  // namespace
@@ -90,19 +57,19 @@ __device__ __forceinline__ void pass(Lds& L, float (&v)[TILE_LOADS], const SdcAc
 extern "C" __global__ void __launch_bounds__(SDC_ACTOR_EVAL_BLOCK, SDC_ACTOR_EVAL_WAVES_PER_SIMD) sdc_actor_eval_kernel(SdcActorEval P) {
   __shared__ Lds L;
   const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
-  actor_to_lds(&L.actor, P.actor);
+  sdc_rowmlp::to_lds(&L.net, P.actor);
   const long long n_pass = (P.n_rows + SDC_ACTOR_EVAL_BLOCK_ROWS - 1) / SDC_ACTOR_EVAL_BLOCK_ROWS;
   const long long stride = (long long)gridDim.x * SDC_ACTOR_EVAL_BLOCK_ROWS;
-  long long row0 = (long long)blockIdx.x * SDC_ACTOR_EVAL_BLOCK_ROWS + wave * SDC_AEV_ROWS;
+  long long row0 = (long long)blockIdx.x * SDC_ACTOR_EVAL_BLOCK_ROWS + wave * SDC_ROWMLP_ROWS;
   float v[TILE_LOADS];
-  fetch(v, P.obs, P.row_stride, row0, P.n_rows, lane);
+  sdc_rowmlp::fetch<SDC_AEV_IN>(v, P.obs, P.row_stride, row0, P.n_rows, lane);
 #pragma unroll 1
   for (long long p = blockIdx.x; p < n_pass; p += gridDim.x, row0 += stride) {
     // (a next pass that does not exist starts at or past n_rows -- the grid's stride is whole workgroups --: fetch loads nothing)
     float lg[SDC_AEV_OUT];
     pass(L, v, P, row0 + stride, wave, lane, lg);
     const long long row = row0 + lane;
-    if (lane < SDC_AEV_ROWS && row < P.n_rows) {
+    if (lane < SDC_ROWMLP_ROWS && row < P.n_rows) {
       float* const out = P.logits + row * P.logits_stride;
       out[0] = lg[0];
       out[1] = lg[1];

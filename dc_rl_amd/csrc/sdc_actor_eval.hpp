@@ -4,22 +4,13 @@
 //
 // sdc_actor_eval_kernel: one agent's network (sdc_actor.hpp's header comment: LayerNorm(26) under flag bit 0 -> Linear(26, 64) -> act ->
 // LayerNorm(64) -> Linear(64, 64) -> act -> LayerNorm(64) -> Linear(64, 3), tanh or relu) over R rows that lie `row_stride` floats apart,
-// the three logits of a row `logits_stride` floats apart.  THE MAPPING IS THE CRITIC'S (sdc_critic.hpp), not the rollout's: the rows are
-// independent and there are millions, so a wavefront takes SIXTEEN rows and a hidden layer is H^T = W X^T on v_mfma_f32_16x16x4_f32,
-//     lane l = (g = l >> 4, e = l & 15) supplies A[unit e of tile t][k = g] and B[k = g][row e], and holds D[unit 4 g + i][row e] in
-//     accumulator register i of tile t -- four tiles, four independent accumulators;
-// register (t, i) of layer 1 IS the B operand of layer 2's k-step s = 4 t + i (the host numbers W2's columns so: sdc_actor_eval_pack.hpp),
-// the hand-over moves no data.  A row's three logits are three fmaf chains over the lane's 16 registers in the order (t, i), then the
-// sums across the four lane groups (sdc_critic::all_sum2 / all_sum: v_permlane16_swap, v_permlane32_swap).  The numerics are
-// sdc_actor.hpp's, through the functions the critic's forward uses: sdc_act::activate, sdc_critic::epilogue (the hidden LayerNorms'
-// one-pass moments of values shifted by unit 0's, rsq(max(var, 0) + 1e-5)), the unshifted one-pass feature LayerNorm.  EVERY SUM'S ORDER IS
-// FIXED BY THE UNIT'S PLACE (t, i, g) ALONE: a row's logits do not depend on its lane column, its wavefront, the rows next to it, the
-// strides or n_rows.
+// the three logits of a row `logits_stride` floats apart.  THE MAPPING IS sdc_rowmlp.hpp's, the critic's, not the rollout's: sixteen rows
+// per wavefront on the matrix cores, every sum's order fixed by the unit's place alone -- a row's logits do not depend on its lane
+// column, its wavefront, the rows next to it, the strides or n_rows.  The forward: sdc_actor_forward.hpp.
 // Workgroups of four wavefronts copy the agent's SdcActorEvalDev (26 KB) to LDS once, then take 64 rows per pass and as many passes as
-// the grid (at most SDC_ACTOR_EVAL_MAX_BLOCKS workgroups) leaves them; the next pass's rows are fetched under the current pass's
-// arithmetic.  A wavefront's 16 rows are 416 dwords, NOT contiguous under a stride: lane l takes tile dwords u = l, l + 64, ... (7 loads,
-// u < 416), dword u being entry k = u % 26 of tile row r = u / 26 at address obs + (row0 + r) * row_stride + k, into the wavefront's own
-// LDS tile, and picks its B operands (entries 4 s + g of row e) from there.
+// the grid (at most SDC_ACTOR_EVAL_MAX_BLOCKS workgroups) leaves them (sdc_rowmlp.hpp's plumbing).  A wavefront's 16 rows are 416
+// dwords, NOT contiguous under a stride: lane l takes tile dwords u = l, l + 64, ... (7 loads, u < 416), dword u being entry k = u % 26
+// of tile row r = u / 26 at address obs + (row0 + r) * row_stride + k.
 //
 // EVERY ADDRESS A LANE FORMS IS BELOW ITS ARRAY'S END.  With row = row0 + r a dword is loaded only when row < n_rows (a row at or past
 // n_rows is not loaded: its tile entries are 0, it computes on zeros and stores nothing), and then
@@ -44,9 +35,10 @@
 
 #include "../../include/sustaindc_hip.h"
 #include "sdc_actor_eval_pack.hpp"
+#include "sdc_rowmlp.hpp"
 
-#define SDC_ACTOR_EVAL_BLOCK 256                                              // four wavefronts: 64 rows per workgroup and pass
-#define SDC_ACTOR_EVAL_BLOCK_ROWS (SDC_ACTOR_EVAL_BLOCK / 64 * SDC_AEV_ROWS)
+#define SDC_ACTOR_EVAL_BLOCK SDC_ROWMLP_BLOCK                                 // four wavefronts: 64 rows per workgroup and pass
+#define SDC_ACTOR_EVAL_BLOCK_ROWS SDC_ROWMLP_BLOCK_ROWS
 #define SDC_ACTOR_EVAL_WAVES_PER_SIMD 4                                       // the register budget: four workgroups per CU, as their LDS allows
 #define SDC_ACTOR_EVAL_MAX_BLOCKS 1024                                        // ... of 256 CUs, all resident at once; more rows: more passes
 #define SDC_PPO_BLOCK 256                                                     // lanes per workgroup of both kernels (a power of two)

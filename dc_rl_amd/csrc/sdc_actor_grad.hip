@@ -9,6 +9,7 @@
 
 #include "sdc_actor_forward.hpp"
 #include "sdc_actor_grad.hpp"
+#include "sdc_rowmlp.hpp"
 
 #pragma clang fp contract(off)
 
@@ -18,10 +19,9 @@ using sdc_act::f4;
 typedef float f2 __attribute__((ext_vector_type(2)));
 
 constexpr int WAVES = SDC_ACTOR_GRAD_BLOCK / 64;
-constexpr int TILE_DW = SDC_AEV_ROWS * SDC_AEV_IN;            // 416
-constexpr int TILE_LOADS = (TILE_DW + 63) / 64;               // 7
+constexpr int TILE_LOADS = sdc_rowmlp::TILE_LOADS<SDC_AEV_IN>;        // 7
 constexpr int TILE_PAD = TILE_LOADS * 64;                     // 448: every lane stores all its seven dwords, the last 32 are never read
-constexpr int TT_DW = SDC_AEV_H * SDC_AGR_S;                  // a transposed tile: 64 units of 16 rows, 20 dwords apart
+constexpr int TT_DW = SDC_ROWMLP_H * SDC_AGR_S;               // a transposed tile: 64 units of 16 rows, 20 dwords apart
 constexpr int N = SDC_ACTOR_N_PARAMS;
 
 struct Tiles {
@@ -41,18 +41,10 @@ struct alignas(16) Lds {      // (16-byte aligned: the A operands, the per-unit 
 };
 static_assert(sizeof(Lds) <= 160 * 1024, "one workgroup per CU");
 static_assert(sizeof(Tiles) >= N * sizeof(float), "the stage lies inside the tiles");
-static_assert(sizeof(SdcActorEvalDev) % sizeof(uint4) == 0 && sizeof(SdcActorGradDev) % sizeof(uint4) == 0, "copied as 16-byte units");
 static_assert(offsetof(Tiles, ta) % 16 == 0 && (TT_DW * sizeof(float)) % 16 == 0 && SDC_AGR_S % 4 == 0, "a tile's 16-byte reads are aligned");
 static_assert((SDC_ACTOR_GRAD_SQ_BLOCK & (SDC_ACTOR_GRAD_SQ_BLOCK - 1)) == 0, "the tree halves");
 
-template <class T>
-__device__ __forceinline__ void to_lds(T* dst, const T* src) {
-  const uint4* const s = reinterpret_cast<const uint4*>(src);
-  uint4* const d = reinterpret_cast<uint4*>(dst);
-  for (int u = (int)threadIdx.x; u < (int)(sizeof(T) / sizeof(uint4)); u += SDC_ACTOR_GRAD_BLOCK) d[u] = s[u];
-}
-
-// what a lane fetches ahead for a pass: its seven dwords of the wavefront's observation tile (sdc_actor_eval.hip's fetch) and, for
+// what a lane fetches ahead for a pass: its seven dwords of the wavefront's observation tile (sdc_rowmlp::fetch) and, for
 // row e = lane & 15, the action and the log-probability's coefficient.  A row at or past n_rows is not loaded: zeros, action -1.
 struct Fetched {
   float v[TILE_LOADS];
@@ -60,15 +52,8 @@ struct Fetched {
   float dlogp;
 };
 __device__ __forceinline__ void fetch(Fetched& F, const SdcActorGrad& P, const long long row0, const int lane) {
-  const long long left = P.n_rows - row0;
-  const int valid = left >= SDC_AEV_ROWS ? SDC_AEV_ROWS : (left > 0 ? (int)left : 0);      // rows that exist
-#pragma unroll
-  for (int j = 0; j < TILE_LOADS; j++) {
-    const int u = lane + 64 * j;
-    const int r = u / SDC_AEV_IN, k = u - r * SDC_AEV_IN;
-    F.v[j] = 0.0f;
-    if (r < valid) F.v[j] = P.obs[(row0 + r) * P.row_stride + k];      // (r < valid <= 16 implies u < 416)
-  }
+  const int valid = sdc_rowmlp::rows_that_exist(row0, P.n_rows);
+  sdc_rowmlp::fetch<SDC_AEV_IN>(F.v, P.obs, P.row_stride, row0, P.n_rows, lane);
   const int e = lane & 15;
   F.action = -1;
   F.dlogp = 0.0f;
@@ -93,7 +78,7 @@ struct Acc {
 __device__ __forceinline__ void ln_back(f4 (&d)[4], const f4 (&n)[4], const float rs, const float (&gain)[4][4][4], const int g,
                                         f4 (&dgain)[4], f4* const dbias) {
   f4 gn[4];
-  sdc_critic::unit_vector(gn, gain, g);
+  sdc_rowmlp::unit_vector(gn, gain, g);
   float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
   for (int t = 0; t < 4; t++)
@@ -108,8 +93,8 @@ __device__ __forceinline__ void ln_back(f4 (&d)[4], const f4 (&n)[4], const floa
       s2 += dn * n[t][i];
     }
   float sum, sq;
-  sdc_critic::all_sum2(s1, s2, sum, sq);
-  const float m1 = sum * (1.0f / SDC_AEV_H), m2 = sq * (1.0f / SDC_AEV_H);
+  sdc_rowmlp::all_sum2(s1, s2, sum, sq);
+  const float m1 = sum * (1.0f / SDC_ROWMLP_H), m2 = sq * (1.0f / SDC_ROWMLP_H);
 #pragma unroll
   for (int t = 0; t < 4; t++)
 #pragma unroll
@@ -127,14 +112,7 @@ __device__ __forceinline__ void act_back(f4 (&d)[4], const f4 (&dact)[4], f4 (&d
     }
 }
 
-// a lane's sixteen registers (unit 16 t + 4 g + i of row e) into the wavefront's transposed tile: [unit][row]
-__device__ __forceinline__ void transpose_out(float* tile, const f4 (&v)[4], const int g, const int e) {
-#pragma unroll
-  for (int t = 0; t < 4; t++)
-#pragma unroll
-    for (int i = 0; i < 4; i++) tile[(16 * t + 4 * g + i) * SDC_AGR_S + e] = v[t][i];
-}
-// ... and back as an MFMA operand: rows 4 g .. 4 g + 3 of unit 16 t + e
+// a transposed tile (sdc_rowmlp::transpose_out stores it) back as an MFMA operand: rows 4 g .. 4 g + 3 of unit 16 t + e
 __device__ __forceinline__ f4 transposed(const float* tile, const int t, const int g, const int e) {
   return *reinterpret_cast<const f4*>(tile + (16 * t + e) * SDC_AGR_S + 4 * g);
 }
@@ -149,8 +127,10 @@ __device__ __forceinline__ void pass(Lds& L, Acc& A, Fetched& F, const SdcActorG
   float* const tb = L.u.tile.tb[wave];
   float* const tc = L.u.tile.tc[wave];
   float* const tl = L.u.tile.tl[wave];
+  // (not the critic's and evaluate's store and pick with their bound tests: a lane predicate costs an SGPR pair this kernel does not
+  // have -- the tile is padded instead, every lane stores all its seven dwords, dwords 416 .. 447 fetch's zeros)
 #pragma unroll
-  for (int j = 0; j < TILE_LOADS; j++) L.u.tile.obs[wave][lane + 64 * j] = F.v[j];      // (dwords 416 .. 447: fetch's zeros)
+  for (int j = 0; j < TILE_LOADS; j++) L.u.tile.obs[wave][lane + 64 * j] = F.v[j];
   __syncthreads();
   // entry 4 s + g of row e; entries 26, 27 (s = 6, g >= 2) are padding: what is read there (< 448) is dropped
   float x[SDC_AEV_S1];
@@ -201,19 +181,19 @@ __device__ __forceinline__ void pass(Lds& L, Acc& A, Fetched& F, const SdcActorG
   for (int c = 0; c < SDC_AEV_OUT; c++) {
     A.b3[c] = A.b3[c] + dl[c];
     f4 w3[4];
-    sdc_critic::unit_vector(w3, W->w3[c], g);
+    sdc_rowmlp::unit_vector(w3, W->w3[c], g);
 #pragma unroll
     for (int t = 0; t < 4; t++)
 #pragma unroll
       for (int i = 0; i < 4; i++) d[t][i] = d[t][i] + dl[c] * w3[t][i];
   }
-  transpose_out(tc, T.y2, g, e);
+  sdc_rowmlp::transpose_out(tc, T.y2, g, e);
   tl[g * SDC_AGR_S + e] = g == 0 ? dl[0] : (g == 1 ? dl[1] : (g == 2 ? dl[2] : 0.0f));      // (row 3: zeros)
   // ---- LayerNorm 2, activation 2: d = dZ2 ---------------------------------------------------------------------------------------------
-  ln_back(d, T.n2, T.rs2, W->ln2_g, g, A.g2, nullptr);
-  act_back(d, T.da2, A.b2);
+  ln_back(d, T.l2.n, T.l2.rs, W->ln2_g, g, A.g2, nullptr);
+  act_back(d, T.l2.dact, A.b2);
   // ---- dW2 += dZ2 Y1^T (Y1^T: the forward left it in tb), dW3 += Y2 dl^T: through the wavefront's tiles, rows on the k side ------------
-  transpose_out(ta, d, g, e);
+  sdc_rowmlp::transpose_out(ta, d, g, e);
   __syncthreads();
   {
     f4 a[4], b[4], y[4];
@@ -238,17 +218,17 @@ __device__ __forceinline__ void pass(Lds& L, Acc& A, Fetched& F, const SdcActorG
 #pragma unroll
   for (int t = 0; t < 4; t++) d1[t] = f4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-  for (int s = 0; s < SDC_AEV_S2; s++) {
+  for (int s = 0; s < SDC_ROWMLP_S2; s++) {
     const f4 a = *reinterpret_cast<const f4*>(L.actor_t.a2t[s][lane]);
 #pragma unroll
     for (int t = 0; t < 4; t++) d1[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], d[s >> 2][s & 3], d1[t], 0, 0, 0);
   }
   // ---- LayerNorm 1, activation 1: d1 = dZ1 --------------------------------------------------------------------------------------------
-  ln_back(d1, T.n1, T.rs1, W->ln1_g, g, A.g1, A.be1);
+  ln_back(d1, T.l1.n, T.l1.rs, W->ln1_g, g, A.g1, A.be1);
 #pragma unroll
-  for (int t = 0; t < 4; t++) d1[t] = d1[t] * T.da1[t];
+  for (int t = 0; t < 4; t++) d1[t] = d1[t] * T.l1.dact[t];
   // ---- dW1 += dZ1 X^T (X: layer 1's input, 26 entries, then a ONE -- its column of dW1 is db1 -- and zeros to 32) -----------------------
-  transpose_out(ta, d1, g, e);
+  sdc_rowmlp::transpose_out(ta, d1, g, e);
 #pragma unroll
   for (int s = 0; s < SDC_AEV_S1 - 1; s++) tb[(4 * s + g) * SDC_AGR_S + e] = x[s];
   tb[(4 * (SDC_AEV_S1 - 1) + g) * SDC_AGR_S + e] = g == 2 ? 1.0f : x[SDC_AEV_S1 - 1];      // (entry 26: the one; 27: x's zero)
@@ -272,7 +252,7 @@ __device__ __forceinline__ void pass(Lds& L, Acc& A, Fetched& F, const SdcActorG
     f4 dx[2];
     dx[0] = dx[1] = f4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-    for (int s = 0; s < SDC_AEV_S2; s++) {
+    for (int s = 0; s < SDC_ROWMLP_S2; s++) {
       const f2 a = *reinterpret_cast<const f2*>(L.actor_t.a1t[s][lane]);
 #pragma unroll
       for (int tp = 0; tp < 2; tp++) dx[tp] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[tp], d1[s >> 2][s & 3], dx[tp], 0, 0, 0);
@@ -280,7 +260,7 @@ __device__ __forceinline__ void pass(Lds& L, Acc& A, Fetched& F, const SdcActorG
 #pragma unroll
     for (int s = 0; s < SDC_AEV_S1; s++) {
       const float v = dx[s >> 2][s & 3];
-      A.g0[s] = A.g0[s] + v * T.n0[s];
+      A.g0[s] = A.g0[s] + v * T.l0.n[s];
       A.be0[s] = A.be0[s] + v;
     }
   }
@@ -317,7 +297,7 @@ __device__ __forceinline__ void emit(float* stage, const Acc& A, const float (&w
     for (int r = 0; r < 4; r++) {
       const int unit = 16 * t + 4 * g + r;
 #pragma unroll
-      for (int tp = 0; tp < 4; tp++) put<FIRST>(stage, SDC_AGR_W2 + unit * SDC_AEV_H + 16 * tp + e, A.w2[t][tp][r]);
+      for (int tp = 0; tp < 4; tp++) put<FIRST>(stage, SDC_AGR_W2 + unit * SDC_ROWMLP_H + 16 * tp + e, A.w2[t][tp][r]);
       put<FIRST>(stage, SDC_AGR_W1 + unit * SDC_AEV_IN + e, A.w1[t][0][r]);
     }
   if (e < SDC_AEV_IN - 16) {
@@ -336,7 +316,7 @@ __device__ __forceinline__ void emit(float* stage, const Acc& A, const float (&w
 #pragma unroll
     for (int t = 0; t < 4; t++)
 #pragma unroll
-      for (int r = 0; r < 4; r++) put<FIRST>(stage, SDC_AGR_W3 + e * SDC_AEV_H + 16 * t + 4 * g + r, A.w3[t][r]);
+      for (int r = 0; r < 4; r++) put<FIRST>(stage, SDC_AGR_W3 + e * SDC_ROWMLP_H + 16 * t + 4 * g + r, A.w3[t][r]);
   }
   if (e == 0) {
 #pragma unroll
@@ -388,10 +368,10 @@ __device__ __forceinline__ void grad_body(Lds& L, const SdcActorGrad& P) {
   const long long stride = (long long)gridDim.x * SDC_ACTOR_GRAD_BLOCK_ROWS;
   const float dent = (float)P.dent;
   Fetched F;
-  fetch(F, P, (long long)blockIdx.x * SDC_ACTOR_GRAD_BLOCK_ROWS + wave * SDC_AEV_ROWS, lane);
+  fetch(F, P, (long long)blockIdx.x * SDC_ACTOR_GRAD_BLOCK_ROWS + wave * SDC_ROWMLP_ROWS, lane);
 #pragma unroll 1
   for (long long p = blockIdx.x; p < n_pass; p += gridDim.x) {
-    const long long row0 = p * SDC_ACTOR_GRAD_BLOCK_ROWS + wave * SDC_AEV_ROWS;
+    const long long row0 = p * SDC_ACTOR_GRAD_BLOCK_ROWS + wave * SDC_ROWMLP_ROWS;
     pass<KIND>(L, A, F, P, dent, row0, row0 + stride, wave, lane);
   }
 
@@ -421,14 +401,14 @@ __device__ __forceinline__ void grad_body(Lds& L, const SdcActorGrad& P) {
 // (the activation is a template parameter, as the forward's, and here a kernel each: one body's registers are all a launch pays for)
 extern "C" __global__ void __launch_bounds__(SDC_ACTOR_GRAD_BLOCK, 1) sdc_actor_grad_tanh_kernel(SdcActorGrad P) {
   __shared__ Lds L;
-  to_lds(&L.actor, P.actor);
-  to_lds(&L.actor_t, P.actor_t);
+  sdc_rowmlp::to_lds(&L.actor, P.actor);
+  sdc_rowmlp::to_lds(&L.actor_t, P.actor_t);
   grad_body<0>(L, P);      // (the first pass's barrier orders the copies before the reads)
 }
 extern "C" __global__ void __launch_bounds__(SDC_ACTOR_GRAD_BLOCK, 1) sdc_actor_grad_relu_kernel(SdcActorGrad P) {
   __shared__ Lds L;
-  to_lds(&L.actor, P.actor);
-  to_lds(&L.actor_t, P.actor_t);
+  sdc_rowmlp::to_lds(&L.actor, P.actor);
+  sdc_rowmlp::to_lds(&L.actor_t, P.actor_t);
   grad_body<1>(L, P);
 }
 

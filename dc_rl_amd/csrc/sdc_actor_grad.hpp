@@ -54,9 +54,9 @@
 #include "sdc_actor_forward.hpp"
 #include "sdc_actor_grad_pack.hpp"
 
-#define SDC_ACTOR_GRAD_BLOCK 256                                              // four wavefronts: 64 rows per workgroup and pass
-#define SDC_ACTOR_GRAD_BLOCK_ROWS (SDC_ACTOR_GRAD_BLOCK / 64 * SDC_AEV_ROWS)
-#define SDC_AGR_S SDC_AEV_TS                                                  // 20 dwords between two units' rows in a transposed tile
+#define SDC_ACTOR_GRAD_BLOCK SDC_ROWMLP_BLOCK                                 // four wavefronts: 64 rows per workgroup and pass
+#define SDC_ACTOR_GRAD_BLOCK_ROWS SDC_ROWMLP_BLOCK_ROWS
+#define SDC_AGR_S SDC_ROWMLP_TS                                               // 20 dwords between two units' rows in a transposed tile
 #define SDC_ACTOR_GRAD_SQ_BLOCK 256                                           // lanes of sdc_actor_grad_sq_kernel (a power of two)
 
 // where each member of sdc_actor_params starts in `grads`

@@ -8,7 +8,7 @@
 // THE LAYOUT follows the backward's two products that move no data (sdc_actor_grad.hpp).  The forward leaves a layer's pre-activation
 // gradient dZ in the accumulators' layout -- register (t, i) of lane l = (g = l >> 4, e = l & 15) is unit 16 t + 4 g + i of row e --, and
 // that register IS the B operand of k-step s = 4 t + i of the transposed product dY^T = W^T dZ^T, its k index 4 s + g standing for unit
-// sdc_critic_unit_of_k(4 s + g) (sdc_critic_pack.hpp).  The A operand holds W^T with its columns numbered so:
+// sdc_rowmlp_unit_of_k(4 s + g) (sdc_rowmlp_pack.hpp).  The A operand holds W^T with its columns numbered so:
 //   a2t[s][l][t'] = W2[unit_of_k(4 s + (l >> 4))][16 t' + (l & 15)]          dY1: register (t', r) = unit 16 t' + 4 g + r, layer 1's own layout
 //   a1t[s][l][t'] = W1[unit_of_k(4 s + (l >> 4))][entry(t', l & 15)]         t' = 0, 1; entry(t', i) = 16 t' + 4 (i & 3) + (i >> 2), 0 for
 //                                                                            entries >= 26
@@ -23,8 +23,8 @@
 #include "sdc_actor_eval_pack.hpp"
 
 struct SdcActorGradDev {
-  float a2t[SDC_AEV_S2][64][4];
-  float a1t[SDC_AEV_S2][64][2];
+  float a2t[SDC_ROWMLP_S2][64][4];
+  float a1t[SDC_ROWMLP_S2][64][2];
 };
 static_assert(sizeof(SdcActorGradDev) % 16 == 0, "copied to LDS as 16-byte units");
 
@@ -38,11 +38,11 @@ inline int sdc_actor_grad_entry(const int tp, const int i) { return 16 * tp + 4 
 // torch's layout ([out][in] rows) -> the backward's
 inline void sdc_actor_grad_pack(const sdc_actor_params* p, SdcActorGradDev* d) {
   std::memset(d, 0, sizeof(*d));
-  for (int s = 0; s < SDC_AEV_S2; s++)
+  for (int s = 0; s < SDC_ROWMLP_S2; s++)
     for (int l = 0; l < 64; l++) {
       const int g = l >> 4, e = l & 15;
-      const int unit = sdc_critic_unit_of_k(4 * s + g);
-      for (int t = 0; t < 4; t++) d->a2t[s][l][t] = p->w2[unit * SDC_AEV_H + 16 * t + e];
+      const int unit = sdc_rowmlp_unit_of_k(4 * s + g);
+      for (int t = 0; t < 4; t++) d->a2t[s][l][t] = p->w2[unit * SDC_ROWMLP_H + 16 * t + e];
       for (int t = 0; t < 2; t++) {
         const int k = sdc_actor_grad_entry(t, e);
         d->a1t[s][l][t] = k < SDC_AEV_IN ? p->w1[unit * SDC_AEV_IN + k] : 0.0f;

@@ -1,4 +1,4 @@
-// sdc_critic.hip -- the two kernels over sdc_critic::forward (sdc_critic.hpp: the network, the mapping, the numerics):
+// sdc_critic.hip -- the two kernels over sdc_critic::forward (sdc_critic.hpp; the network, the mapping, the numerics: sdc_rowmlp.hpp):
 //   sdc_critic_values_kernel     rows [R][29] in, values [R] out                                     (sdc_critic_values)
 //   sdc_critic_terminal_kernel   the N share_obs rows of a plan horizon's last step -> score[n] += factor * (done[n] ? 0 : V[n])
 //                                in fp64, no fused multiply-add (the library is built with -ffp-contract=off; the contract:
@@ -14,31 +14,20 @@
 #include <hip/hip_runtime.h>
 
 #include "sdc_critic.hpp"
+#include "sdc_rowmlp.hpp"
 
 namespace {
 
-constexpr int WAVES = SDC_CRITIC_BLOCK / 64;
-constexpr int TILE_DW = SDC_CRITIC_ROWS * SDC_CRITIC_IN;      // 464
-constexpr int TILE_LOADS = (TILE_DW + 63) / 64;               // 8
-static_assert(sizeof(SdcCriticDev) + WAVES * TILE_DW * sizeof(float) <= 40 * 1024, "four workgroups' LDS fit a CU");
-static_assert(sizeof(SdcCriticDev) % sizeof(uint4) == 0, "copied as 16-byte units");
+constexpr int TILE_DW = sdc_rowmlp::TILE_DW<SDC_CRITIC_IN>;           // 464
+constexpr int TILE_LOADS = sdc_rowmlp::TILE_LOADS<SDC_CRITIC_IN>;     // 8
 
-struct alignas(16) Lds {      // (16-byte aligned: the A operands and the per-unit vectors are read as 16-byte units)
-  SdcCriticDev critic;
-  float tile[WAVES][TILE_DW];
-};
-
-__device__ __forceinline__ void critic_to_lds(SdcCriticDev* dst, const SdcCriticDev* src) {
-  const uint4* const s = reinterpret_cast<const uint4*>(src);
-  uint4* const d = reinterpret_cast<uint4*>(dst);
-  for (int u = (int)threadIdx.x; u < (int)(sizeof(SdcCriticDev) / sizeof(uint4)); u += SDC_CRITIC_BLOCK) d[u] = s[u];
-}
+using Lds = sdc_rowmlp::Lds<SdcCriticDev, SDC_CRITIC_IN>;
+static_assert(sizeof(Lds) <= 40 * 1024, "four workgroups' LDS fit a CU");
 
 // A wavefront's rows row0 .. row0 + 15 of `rows` (n_rows in all), densely: lane l takes dwords l, l + 64, ... of the 464; a dword of
-// a row at or past n_rows is not loaded (0)
+// a row at or past n_rows is not loaded (0).  (Not sdc_rowmlp::fetch: contiguous rows need no division.)
 __device__ __forceinline__ void fetch(float (&v)[TILE_LOADS], const float* rows, const long long row0, const long long n_rows, const int lane) {
-  const long long left = n_rows - row0;
-  const int valid = (left >= SDC_CRITIC_ROWS ? SDC_CRITIC_ROWS : (left > 0 ? (int)left : 0)) * SDC_CRITIC_IN;      // dwords that exist
+  const int valid = sdc_rowmlp::rows_that_exist(row0, n_rows) * SDC_CRITIC_IN;      // dwords that exist
   const float* const src = rows + row0 * SDC_CRITIC_IN;
 #pragma unroll
   for (int j = 0; j < TILE_LOADS; j++) {
@@ -69,17 +58,17 @@ __device__ __forceinline__ float pass(Lds& L, float (&v)[TILE_LOADS], const floa
     if (k < SDC_CRITIC_IN) x[s] = L.tile[wave][e * SDC_CRITIC_IN + k];
   }
   fetch(v, rows, next0, n_rows, lane);
-  return sdc_critic::forward(&L.critic, x, lane);
+  return sdc_critic::forward(&L.net, x, lane);
 }
 
 // the passes of a workgroup over n_rows rows: store(row, value) for every row that exists, by the lane (< 16) that owns it
 template <class Store>
 __device__ __forceinline__ void passes(Lds& L, const SdcCriticDev* critic, const float* rows, const long long n_rows, Store&& store) {
   const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
-  critic_to_lds(&L.critic, critic);
+  sdc_rowmlp::to_lds(&L.net, critic);
   const long long n_pass = (n_rows + SDC_CRITIC_BLOCK_ROWS - 1) / SDC_CRITIC_BLOCK_ROWS;
   const long long stride = (long long)gridDim.x * SDC_CRITIC_BLOCK_ROWS;
-  long long row0 = (long long)blockIdx.x * SDC_CRITIC_BLOCK_ROWS + wave * SDC_CRITIC_ROWS;
+  long long row0 = (long long)blockIdx.x * SDC_CRITIC_BLOCK_ROWS + wave * SDC_ROWMLP_ROWS;
   float v[TILE_LOADS];
   fetch(v, rows, row0, n_rows, lane);
 #pragma unroll 1
@@ -87,7 +76,7 @@ __device__ __forceinline__ void passes(Lds& L, const SdcCriticDev* critic, const
     // (a next pass that does not exist starts at or past n_rows -- the grid's stride is whole workgroups --: fetch loads nothing)
     const float value = pass(L, v, rows, row0 + stride, n_rows, wave, lane);
     const long long row = row0 + lane;
-    if (lane < SDC_CRITIC_ROWS && row < n_rows) store(row, value);
+    if (lane < SDC_ROWMLP_ROWS && row < n_rows) store(row, value);
   }
 }
 

@@ -571,7 +571,7 @@ int sdc_get_plan_terms(const sdc_handle* h, sdc_plan_terms* out);
  * MLPBase, hidden_sizes [64, 64], no recurrence) and harl/common/valuenorm.py ValueNorm.denormalize, over rows of share_obs:
  *     LayerNorm(29) -> Linear(29, 64) -> act -> LayerNorm(64) -> Linear(64, 64) -> act -> LayerNorm(64) -> Linear(64, 1);  v * scale + shift
  * fp32 throughout (LayerNorm: biased variance, eps 1e-5), the two hidden layers on fp32-input matrix instructions, 16 rows per wavefront
- * (csrc/sdc_critic.hpp).  sdc_critic_params is torch's layout ([out][in], row-major), as sdc_actor_params is; flags bit 0: the feature
+ * (csrc/sdc_rowmlp.hpp).  sdc_critic_params is torch's layout ([out][in], row-major), as sdc_actor_params is; flags bit 0: the feature
  * LayerNorm is on (off: ln0_g / ln0_b are not used, but must be finite), bits 1-2: the activation, 0 tanh, 1 relu.  scale and shift fold a
  * ValueNorm (sqrt of its debiased variance, its debiased mean); 1 and 0 without one.
  * sdc_set_critic packs the parameters into the kernels' layout and copies them to the handle's device (host pointer; it waits for the
@@ -662,7 +662,7 @@ int sdc_action_log_probs(sdc_handle* h, int n_steps, const int32_t* actions, con
  * sdc_actor_backward (THE ACTORS' GRADIENT below); the optimiser and the critic's value loss are not here.  Both calls are pure functions of their arrays, all device memory: they read no env
  * state and move nothing in the engine; each is ordered on `stream` with no synchronisation.
  * sdc_actor_evaluate: the logits of agent_slot's network -- the one last given to sdc_set_actor for that slot, the network stated at
- * sdc_set_actor, fp32, the hidden layers on fp32-input matrix instructions, 16 rows per wavefront (csrc/sdc_actor_eval.hpp) -- for n_rows
+ * sdc_set_actor, fp32, the hidden layers on fp32-input matrix instructions, 16 rows per wavefront (csrc/sdc_rowmlp.hpp) -- for n_rows
  * rows of observations, ONE launch of sdc_actor_eval_kernel.  Row r is the 26 floats at obs + r * row_stride (floats; row_stride 26: a
  * dense per-agent buffer; 78 with obs advanced by 26 * agent: the agent's rows of an [..][3][26] array as sdc_rollout_actor fills it); its
  * three logits go to logits + r * logits_stride (logits_stride 3: dense; 9 with logits advanced by 3 * agent: the agent's column of a

@@ -60,11 +60,21 @@ def test_kernels_compile_for_gfx950_without_scratch_or_spills():
 
 
 def test_the_shared_forward_left_the_evaluate_kernels_as_they_were():
-    """sdc_actor_eval.hip still holds exactly its three kernels with their resources (the forward moved to a shared header)"""
+    """sdc_actor_eval.hip still holds exactly its three kernels with their resources, and the network they, the critic and the gradient
+    kernels run stands ONCE, in csrc/sdc_rowmlp.hpp: the three .hip files include it, and neither they nor the two forward headers hold
+    a matrix-instruction layer loop, an epilogue or a LayerNorm's rsq of their own (sdc_actor_grad.hip: its backward's five products)"""
     per = kernel_resources("sdc_actor_eval.hip")
     assert_no_scratch_or_spills(per, {"sdc_actor_eval_kernel", "sdc_ppo_terms_kernel", "sdc_ppo_stats_kernel"})
-    src = open(os.path.join(L.CSRC, "sdc_actor_eval.hip")).read()
-    assert '#include "sdc_actor_forward.hpp"' in src and "sdc_aev::NoTape" in src
+    read = lambda name: open(os.path.join(L.CSRC, name)).read()
+    mfma, shared = "__builtin_amdgcn_mfma_f32_16x16x4f32", read("sdc_rowmlp.hpp")
+    assert shared.count(mfma) == 2 and len(re.findall(r"\bvoid epilogue\(", shared)) == 1 and shared.count("__builtin_amdgcn_rsqf") == 2
+    for name in ("sdc_critic.hip", "sdc_actor_eval.hip", "sdc_actor_grad.hip", "sdc_critic.hpp", "sdc_actor_forward.hpp"):
+        src = read(name)
+        assert '#include "sdc_rowmlp.hpp"' in src, name
+        assert src.count(mfma) == (5 if name == "sdc_actor_grad.hip" else 0), name
+        assert "epilogue" not in src and "__builtin_amdgcn_rsqf" not in src, name
+    grad = read("sdc_actor_grad.hip")
+    assert grad.index("sdc_aev::forward_kind<KIND>") < grad.index(mfma)      # (the five stand behind the forward's call: the backward)
 
 
 # ---- the transposed pack ------------------------------------------------------------------------------------------------------------
