@@ -154,6 +154,29 @@ def finite_float(who, name, value):
     return float(value)
 
 
+# ---------------------------------------------------------------------- the critic's gradient
+def share_rows(who, share_obs, device):
+    """rows of share_obs: a contiguous float32 CUDA tensor (..., 29) on the engine's `device` -> the rows' shape (...); ValueError in the
+    caller's name for anything else"""
+    import torch
+    if not (isinstance(share_obs, torch.Tensor) and share_obs.dtype == torch.float32 and share_obs.is_cuda and share_obs.is_contiguous() and
+            share_obs.dim() >= 1 and share_obs.shape[-1] == L.SHARE_OBS_DIM):
+        raise ValueError(f"{who}: share_obs must be a contiguous float32 CUDA tensor of shape (..., {L.SHARE_OBS_DIM})")
+    if share_obs.device != device:
+        raise ValueError(f"{who}: share_obs is on {share_obs.device}, this engine runs on {device}")
+    return tuple(share_obs.shape[:-1])
+
+
+def any_shape(who, x, name, dtype, device):
+    """a contiguous CUDA tensor of `dtype` on the engine's `device`, of whatever shape -> that shape; ValueError in the caller's name"""
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.dtype == dtype and x.is_cuda and x.is_contiguous()):
+        raise ValueError(f"{who}: {name} must be a contiguous {str(dtype).split('.')[-1]} CUDA tensor")
+    if x.device != device:
+        raise ValueError(f"{who}: {name} is on {x.device}, this engine runs on {device}")
+    return tuple(x.shape)
+
+
 # ---------------------------------------------------------------------- the horizon of lookahead and plan
 def check_horizon(who, K, left=None, auto_reset=False):
     """ValueError for a horizon a mark cannot hold and -- `left` = steps_to_episode_end() given -- one that would finish an episode"""

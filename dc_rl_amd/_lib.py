@@ -25,7 +25,7 @@ LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
            "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip", "sdc_plan_terms.hip",
            "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip", "sdc_mpc_groups.hip", "sdc_critic.hip", "sdc_onpolicy.hip", "sdc_actor_eval.hip",
-           "sdc_actor_grad.hip"]
+           "sdc_actor_grad.hip", "sdc_critic_grad.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
@@ -67,6 +67,9 @@ PPO_MAX_BLOCKS = 1024   # csrc/sdc_actor_eval.hpp SDC_PPO_MAX_BLOCKS: stage 1's 
 PPO_STATS = 8           # include/sustaindc_hip.h: entries of sdc_ppo_terms' stats
 ACTOR_N_PARAMS = 6391           # include/sustaindc_hip.h SDC_ACTOR_N_PARAMS: the float members of sdc_actor_params, sdc_actor_backward's grads
 ACTOR_GRAD_MAX_BLOCKS = 256     # include/sustaindc_hip.h SDC_ACTOR_GRAD_MAX_BLOCKS: workgroups (partial gradients) of sdc_actor_backward at most
+CRITIC_N_PARAMS = 6459          # include/sustaindc_hip.h SDC_CRITIC_N_PARAMS: sdc_critic_params' float members ln0_g .. b3, sdc_critic_backward's grads
+CRITIC_GRAD_MAX_BLOCKS = 256    # include/sustaindc_hip.h SDC_CRITIC_GRAD_MAX_BLOCKS: workgroups (partial gradients) of sdc_critic_backward at most
+VALUE_LOSS_HUBER, VALUE_LOSS_CLIPPED = 1, 2     # include/sustaindc_hip.h: sdc_value_loss' flags (bit 0: Huber loss, bit 1: clipped value loss)
 SNAPSHOT_MANIFEST = 9   # include/sustaindc_hip.h SDC_SNAPSHOT_MANIFEST: int32 entries per snapshot row's manifest (enum sdc_snapshot_manifest)
 # (-amdgpu-sched-strategy=max-ilp: the machine scheduler orders for instruction-level parallelism instead of minimal register
 #  pressure -- the step kernels' occupancy is pinned by amdgpu_waves_per_eu anyway, and their time is dependent-issue latency:
@@ -250,6 +253,7 @@ EXPORTS = [
     "sdc_rollout_cem_stats", "sdc_rollout_cem_groups_stats",
     "sdc_set_critic", "sdc_critic_values", "sdc_set_plan_critic", "sdc_get_plan_critic",
     "sdc_gae", "sdc_action_log_probs", "sdc_actor_evaluate", "sdc_ppo_terms", "sdc_ppo_dlogp", "sdc_actor_backward",
+    "sdc_critic_evaluate", "sdc_value_loss", "sdc_critic_backward",
 ]
 
 
@@ -431,6 +435,9 @@ def load():
     L.sdc_ppo_terms.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp, fp, C.c_double, fp, fp, fp, vp, vp]
     L.sdc_ppo_dlogp.argtypes = [vp, C.c_int, C.c_int, fp, fp, fp, fp, C.c_double, C.c_double, fp, vp]
     L.sdc_actor_backward.argtypes = [vp, C.c_int, fp, C.c_longlong, C.c_longlong, vp, C.c_longlong, fp, C.c_double, fp, vp, vp]
+    L.sdc_critic_evaluate.argtypes = [vp, fp, C.c_longlong, fp, vp]
+    L.sdc_value_loss.argtypes = [vp, C.c_longlong, fp, fp, fp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, fp, fp, vp, vp]
+    L.sdc_critic_backward.argtypes = [vp, fp, C.c_longlong, fp, fp, vp, vp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

@@ -42,6 +42,7 @@
 #include "sdc_onpolicy.hpp"
 #include "sdc_actor_eval.hpp"
 #include "sdc_actor_grad.hpp"
+#include "sdc_critic_grad.hpp"
 #include "sdc_mpc.hpp"
 #include "sdc_mpc_groups.hpp"
 #include "sdc_mpc_schedule.hpp"
@@ -178,6 +179,13 @@ struct sdc_handle {
   // workgroups' partial gradients [SDC_ACTOR_GRAD_MAX_BLOCKS][SDC_ACTOR_N_PARAMS], allocated on first use
   SdcActorGradDev* actor_grad_dev = nullptr;
   float* actor_grad_part = nullptr;
+  // sdc_critic_backward: the critic's transposed weights (sdc_critic_grad_pack.hpp), allocated and filled with critic_dev, and its
+  // activation; the workgroups' partial gradients [SDC_CRITIC_GRAD_MAX_BLOCKS][SDC_CRITIC_N_PARAMS] and sdc_value_loss' stage 1
+  // statistics [SDC_PPO_MAX_BLOCKS][8] (its own: not sdc_ppo_terms' -- the two may run on different streams), allocated on first use
+  SdcCriticGradDev* critic_grad_dev = nullptr;
+  int critic_activation = 0;
+  float* critic_grad_part = nullptr;
+  double* value_loss_part = nullptr;
 };
 
 namespace {
@@ -1771,11 +1779,17 @@ int sdc_set_critic(sdc_handle* h, const sdc_critic_params* p) {
   if (const char* why = sdc_critic_params_error(p)) return fail_msg(w + why);
   HIP_TRY(hipSetDevice(h->device));
   if (!h->critic_dev && dev_alloc(h, &h->critic_dev, 1) != 0) return -1;
+  if (!h->critic_grad_dev && dev_alloc(h, &h->critic_grad_dev, 1) != 0) return -1;
   std::unique_ptr<SdcCriticDev> packed(new SdcCriticDev);      // (26 KB: on the heap, per call -- see sdc_set_actor)
   sdc_critic_pack(p, packed.get());
+  // ... and the transposed weights as sdc_critic_backward's kernel reads them (sdc_critic_grad_pack.hpp)
+  std::unique_ptr<SdcCriticGradDev> packed_t(new SdcCriticGradDev);
+  sdc_critic_grad_pack(p, packed_t.get());
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(h->critic_dev, packed.get(), sizeof(SdcCriticDev), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(h->critic_grad_dev, packed_t.get(), sizeof(SdcCriticGradDev), hipMemcpyHostToDevice));
   h->critic_set = true;
+  h->critic_activation = (p->flags >> 1) & 3;
   return 0;
 }
 
@@ -1919,6 +1933,67 @@ int sdc_actor_backward(sdc_handle* h, int agent_slot, const float* obs, long lon
     return rc;
   if (!grad_sq) return 0;
   return launched("sdc_actor_grad_sq_kernel", sdc_actor_grad_sq_launch(SdcActorGradSq{grads, grad_sq}, st));
+}
+
+// ---- the critic's gradient (sdc_critic_grad.hip) -------------------------------------------------------------------------------------
+// The contract and the arithmetic: include/sustaindc_hip.h THE CRITIC'S GRADIENT; the kernels' plans: sdc_critic_grad.hpp.
+int sdc_critic_evaluate(sdc_handle* h, const float* share_obs, long long n_rows, float* raw_values, void* stream) {
+  if (refused(sdc_critic_evaluate_refused(call_facts(h), share_obs, n_rows, raw_values))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  return launched("sdc_critic_raw_kernel",
+                  sdc_critic_raw_launch(SdcCriticRaw{h->critic_dev, share_obs, n_rows, raw_values}, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int sdc_value_loss(sdc_handle* h, long long n, const float* raw_values, const float* value_preds, const float* returns, double target_scale,
+                   double target_shift, double clip_param, double huber_delta, int flags, double coef, float* loss, float* dvalue,
+                   double* stats, void* stream) {
+  if (refused(sdc_value_loss_refused(call_facts(h), n, raw_values, value_preds, returns, target_scale, target_shift, clip_param, huber_delta,
+                                     flags, coef, loss, dvalue, stats)))
+    return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (stats && !h->value_loss_part && dev_alloc(h, &h->value_loss_part, (size_t)SDC_PPO_MAX_BLOCKS * SDC_PPO_STATS, false) != 0) return -1;
+  SdcValueLoss P;
+  std::memset(&P, 0, sizeof(P));
+  P.n = n;
+  P.raw = raw_values;
+  P.vp = value_preds;
+  P.ret = returns;
+  P.scale = target_scale;
+  P.shift = target_shift;
+  P.clip = clip_param;
+  P.delta = (flags & SDC_VALUE_LOSS_HUBER) ? huber_delta : 0.0;
+  P.coef = coef;
+  P.flags = flags;
+  P.loss = loss;
+  P.dvalue = dvalue;
+  P.part = stats ? h->value_loss_part : nullptr;
+  if (const int rc = launched("sdc_value_loss_kernel", sdc_value_loss_launch(P, st))) return rc;
+  if (!stats) return 0;
+  // (stage 2 is sdc_ppo_terms' own: the same seven folds over the partials)
+  return launched("sdc_ppo_stats_kernel", sdc_ppo_stats_launch(SdcPpoStats{sdc_ppo_blocks(n), (double)n, h->value_loss_part, stats}, st));
+}
+
+int sdc_critic_backward(sdc_handle* h, const float* share_obs, long long n_rows, const float* dvalue, float* grads, double* grad_sq,
+                        void* stream) {
+  if (refused(sdc_critic_backward_refused(call_facts(h), share_obs, n_rows, dvalue, grads, grad_sq))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (!h->critic_grad_part && dev_alloc(h, &h->critic_grad_part, (size_t)SDC_CRITIC_GRAD_MAX_BLOCKS * SDC_CRITIC_N_PARAMS, false) != 0) return -1;
+  SdcCriticGrad P;
+  std::memset(&P, 0, sizeof(P));
+  P.critic = h->critic_dev;
+  P.critic_t = h->critic_grad_dev;
+  P.rows = share_obs;
+  P.n_rows = n_rows;
+  P.dvalue = dvalue;
+  P.part = h->critic_grad_part;
+  if (const int rc = launched("sdc_critic_grad_kernel", sdc_critic_grad_launch(P, h->critic_activation, st))) return rc;
+  if (const int rc = launched("sdc_critic_grad_reduce_kernel",
+                              sdc_critic_grad_reduce_launch(SdcCriticGradReduce{sdc_critic_grad_blocks(n_rows), h->critic_grad_part, grads}, st)))
+    return rc;
+  if (!grad_sq) return 0;
+  return launched("sdc_critic_grad_sq_kernel", sdc_critic_grad_sq_launch(SdcCriticGradSq{grads, grad_sq}, st));
 }
 
 int sdc_set_plan_critic(sdc_handle* h, double weight) {

@@ -654,6 +654,49 @@ static inline SdcMsg sdc_actor_backward_refused(const SdcCallFacts& f, const int
   return std::nullopt;
 }
 
+// ---- the critic's gradient -------------------------------------------------------------------------------------------------------------------
+// (pure functions of their arrays, as the calls above; their texts are held by tests/test_critic_grad_abi.py)
+static inline SdcMsg sdc_critic_evaluate_refused(const SdcCallFacts& f, const float* share_obs, const long long n_rows, const float* raw_values) {
+  static const std::string w = "sdc_critic_evaluate: ";
+  if (!f.handle) return w + "null handle";
+  if (!f.critic_set) return w + "sdc_set_critic first";
+  if (n_rows < 1) return w + "n_rows = " + std::to_string(n_rows) + " must be positive";
+  if (!share_obs || !raw_values) return w + "null array";
+  if ((sdc_addr_bits(share_obs, raw_values) & 3u) != 0) return w + "share_obs / raw_values not dword-aligned";
+  return std::nullopt;
+}
+static inline SdcMsg sdc_value_loss_refused(const SdcCallFacts& f, const long long n, const float* raw_values, const float* value_preds,
+                                            const float* returns, const double target_scale, const double target_shift, const double clip_param,
+                                            const double huber_delta, const int flags, const double coef, const float* loss, const float* dvalue,
+                                            const double* stats) {
+  static const std::string w = "sdc_value_loss: ";
+  if (!f.handle) return w + "null handle";
+  if (n < 1) return w + "n = " + std::to_string(n) + " must be positive";
+  if (!raw_values || !value_preds || !returns || !dvalue) return w + "null array (raw_values, value_preds, returns and dvalue are required)";
+  if ((sdc_addr_bits(raw_values, value_preds, returns, loss, dvalue) & 3u) != 0)
+    return w + "raw_values / value_preds / returns / loss / dvalue not dword-aligned";
+  if ((sdc_addr_bits(stats) & 7u) != 0) return w + "stats not 8-byte aligned";
+  if (!(std::isfinite(target_scale) && target_scale > 0.0)) return w + "target_scale = " + std::to_string(target_scale) + " must be finite and positive";
+  if (!std::isfinite(target_shift)) return w + "target_shift = " + std::to_string(target_shift) + " is not finite";
+  if (!(std::isfinite(clip_param) && clip_param >= 0.0)) return w + "clip_param = " + std::to_string(clip_param) + " must be finite and not negative";
+  if (flags < 0 || (flags >> 2) != 0) return w + "flags = " + std::to_string(flags) + ": unknown bits (bit 0: Huber loss, bit 1: clipped value loss)";
+  if ((flags & 1) != 0 && !(std::isfinite(huber_delta) && huber_delta > 0.0))
+    return w + "huber_delta = " + std::to_string(huber_delta) + " must be finite and positive";
+  if (!std::isfinite(coef)) return w + "coef = " + std::to_string(coef) + " is not finite";
+  return std::nullopt;
+}
+static inline SdcMsg sdc_critic_backward_refused(const SdcCallFacts& f, const float* share_obs, const long long n_rows, const float* dvalue,
+                                                 const float* grads, const double* grad_sq) {
+  static const std::string w = "sdc_critic_backward: ";
+  if (!f.handle) return w + "null handle";
+  if (!f.critic_set) return w + "sdc_set_critic first";
+  if (n_rows < 1) return w + "n_rows = " + std::to_string(n_rows) + " must be positive";
+  if (!share_obs || !dvalue || !grads) return w + "null array (share_obs, dvalue and grads are required)";
+  if ((sdc_addr_bits(share_obs, dvalue, grads) & 3u) != 0) return w + "share_obs / dvalue / grads not dword-aligned";
+  if ((sdc_addr_bits(grad_sq) & 7u) != 0) return w + "grad_sq not 8-byte aligned";
+  return std::nullopt;
+}
+
 // ---- the cross-entropy planners -------------------------------------------------------------------------------------------------------------
 // The parameter ranges sdc_plan_cem and sdc_plan_cem_groups refuse alike.  The callers run them in their own order.
 static inline SdcMsg sdc_cem_iters_refused(const std::string& w, const int n_iters, const int iter0) {

@@ -340,27 +340,34 @@ class PPOTerms:
                     approx_kl=-float(s[2]) / n, entropy=float(s[3]) / n, clip_frac=float(s[4]) / n)
 
 
-class ActorGrads:
-    """What SdcEngine.actor_backward hands back for one agent, on the engine's device: `flat` fp32 [6391], the gradient with respect to
-    the float members of sdc_actor_params in declaration order (ln0_gamma .. b3, torch's [out][in] layout), and `sq_norm` fp64 0-dim,
-    the sum of its squares in the fixed order include/sustaindc_hip.h states."""
+class _ParamGrads:
+    """What ActorGrads and CriticGrads share: `flat`, the fp32 gradient with respect to a params struct's float members in
+    declaration order (torch's [out][in] layout), and `sq_norm` fp64 0-dim, the sum of its squares in the fixed order
+    include/sustaindc_hip.h states.  A subclass names its network (`_WHAT`) and gives `_layout()`: (the struct's {field: shape}, the
+    reference's {field: state_dict key}, {field: the shape under that key, where it differs})."""
     __slots__ = ("flat", "sq_norm")
+    _WHAT = ""
 
     def __init__(self, flat, sq_norm):
         self.flat, self.sq_norm = flat, sq_norm
 
+    @staticmethod
+    def _layout():
+        raise NotImplementedError
+
     def named(self) -> dict:
-        """{sdc_actor_params field: a shaped view of `flat`}"""
+        """{params struct field: a shaped view of `flat`}"""
         out, at = {}, 0
-        for field, shape in _ACTOR_SHAPES.items():
+        for field, shape in self._layout()[0].items():
             n = int(np.prod(shape))
             out[field] = self.flat[at:at + n].view(shape)
             at += n
         return out
 
     def state_dict(self) -> dict:
-        """the same views under the reference's StochasticPolicy state_dict keys"""
-        return {_ACTOR_SD_KEYS[k]: v for k, v in self.named().items()}
+        """the same views under the reference's state_dict keys, in its shapes"""
+        _, keys, shapes = self._layout()
+        return {keys[k]: (v.view(shapes[k]) if k in shapes else v) for k, v in self.named().items()}
 
     def norm(self):
         """the gradient's 2-norm, fp64 0-dim on the device"""
@@ -378,8 +385,51 @@ class ActorGrads:
         sd = self.state_dict()
         for name, p in module.named_parameters():
             if name not in sd:
-                raise KeyError(f"assign_to: the module's parameter {name!r} is none of the actor's {sorted(sd)}")
+                raise KeyError(f"assign_to: the module's parameter {name!r} is none of the {self._WHAT}'s {sorted(sd)}")
             p.grad = sd[name].detach().to(device=p.device, dtype=p.dtype).clone()
+
+
+class ActorGrads(_ParamGrads):
+    """What SdcEngine.actor_backward hands back for one agent, on the engine's device: `flat` fp32 [6391], the gradient with respect to
+    the float members of sdc_actor_params in declaration order (ln0_gamma .. b3, torch's [out][in] layout), and `sq_norm` fp64 0-dim,
+    the sum of its squares in the fixed order include/sustaindc_hip.h states.  state_dict(): the reference's StochasticPolicy keys."""
+    __slots__ = ()
+    _WHAT = "actor"
+
+    @staticmethod
+    def _layout():
+        return _ACTOR_SHAPES, _ACTOR_SD_KEYS, {}
+
+
+class CriticGrads(_ParamGrads):
+    """What SdcEngine.critic_backward hands back, on the engine's device: `flat` fp32 [6459], the gradient with respect to the float
+    members of sdc_critic_params from ln0_g to b3 in declaration order (scale and shift are no parameters), and `sq_norm` fp64 0-dim.
+    state_dict(): the reference's VNet keys, v_out.weight as [1, 64] and v_out.bias as [1]."""
+    __slots__ = ()
+    _WHAT = "critic"
+
+    @staticmethod
+    def _layout():
+        return _CRITIC_SHAPES, _CRITIC_SD_KEYS, {"w3": (1, 64), "b3": (1,)}
+
+
+class ValueLossTerms:
+    """What SdcEngine.value_loss hands back, on the engine's device: `loss` fp32 (the inputs' shape; None without want_loss) the value
+    loss per element, `dvalue` fp32 the derivative of coef * sum(loss) per raw value -- critic_backward's coefficients --, `stats` fp64
+    [8]: the sums of loss, the raw values, the error target - raw and its square, the number of elements whose clipped loss is the
+    larger, the error's minimum and maximum, n (include/sustaindc_hip.h states their fixed order)."""
+    __slots__ = ("loss", "dvalue", "stats")
+
+    def __init__(self, loss, dvalue, stats):
+        self.loss, self.dvalue, self.stats = loss, dvalue, stats
+
+    def summary(self) -> dict:
+        """The update's logged scalars, from one device -> host copy of `stats`: value_loss = mean(loss) (v_critic.py's value_loss),
+        value_mean (of the raw values), error_mean, error_rms, clipped_frac, error_min, error_max"""
+        s = self.stats.cpu().numpy()
+        n = float(s[7])
+        return dict(value_loss=float(s[0]) / n, value_mean=float(s[1]) / n, error_mean=float(s[2]) / n,
+                    error_rms=float(np.sqrt(float(s[3]) / n)), clipped_frac=float(s[4]) / n, error_min=float(s[5]), error_max=float(s[6]))
 
 
 class MPCCarry:
@@ -1111,6 +1161,78 @@ class SdcEngine:
         terms = self.ppo_terms(a, logp, old, adv, clip_param, factor=factor, entropy=ent)
         dlogp = self.ppo_dlogp(a, logp, old, adv, clip_param, factor=factor, scale=1.0 / n)
         return self.actor_backward(a, obs, batch.actions, dlogp, dent=-float(entropy_coef) / n, per_agent=True), terms
+
+    # ------------------------------------------------------------------ the critic's gradient
+    def critic_raw_values(self, share_obs):
+        """The critic's OWN output for every row of `share_obs` (as critic_values takes it), before `* scale + shift` -- what the
+        reference's critic(cent_obs) returns under a ValueNorm (sdc_critic_evaluate: one launch, stream-ordered).  critic_values of
+        the same rows is raw * scale + shift in fp32, to the bit.  -> fp32 [...].  ValueError as critic_values'."""
+        t = self.torch
+        lead = A.share_rows("critic_raw_values", share_obs, self.device)
+        raw = t.empty(lead, dtype=t.float32, device=self.device)
+        self._behind_torch_stream()
+        self._call(self.lib.sdc_critic_evaluate, _p(share_obs), raw.numel(), _p(raw), self._stream(), refuses=True, wrote=(share_obs, raw))
+        return raw
+
+    def value_loss(self, raw_values, value_preds, returns, clip_param: float = 0.2, huber_delta: float = 10.0, use_huber_loss: bool = True,
+                   use_clipped_value_loss: bool = True, value_norm=None, coef=None, want_loss: bool = True) -> ValueLossTerms:
+        """The reference's value loss (v_critic.py cal_value_loss) per element and its derivative per raw value (sdc_value_loss:
+        elementwise in fp64, each result rounded once; fixed-order fp64 statistics; stream-ordered): `raw_values` (critic_raw_values'),
+        `value_preds` (the stored normalised predictions, OnPolicyBatch.value_preds[:T]) and `returns`, contiguous fp32 tensors of one
+        shape on this engine's device.  The target is (returns - shift) / scale: `value_norm` None -- the scale and shift of the critic
+        in force (1 and 0 before set_critic) --, a (mean, var) pair, or a ValueNorm, as `critic_params` takes it.  `coef`: dvalue =
+        coef * d loss / d raw; None: 1 / n, the reference's mean at value_loss_coef 1.  -> ValueLossTerms.  ValueError for another
+        tensor and for what the library refuses (clip_param < 0, huber_delta <= 0 under use_huber_loss, a coef that is not finite)."""
+        t, who = self.torch, "value_loss"
+        shape = A.any_shape(who, raw_values, "raw_values", t.float32, self.device)
+        A.device_tensor(value_preds, who, "value_preds", t.float32, shape, None, self.device)
+        A.device_tensor(returns, who, "returns", t.float32, shape, None, self.device)
+        n = raw_values.numel()
+        if value_norm is None:
+            scale, shift = (1.0, 0.0) if self._critic is None else (float(self._critic.scale), float(self._critic.shift))
+        else:
+            scale, shift = value_norm_scale_shift(value_norm)
+        coef = 1.0 / max(n, 1) if coef is None else A.finite_float(who, "coef", coef)
+        flags = (L.VALUE_LOSS_HUBER if use_huber_loss else 0) | (L.VALUE_LOSS_CLIPPED if use_clipped_value_loss else 0)
+        new = lambda: t.empty(shape, dtype=t.float32, device=self.device)
+        res = ValueLossTerms(new() if want_loss else None, new(), t.empty(L.PPO_STATS, dtype=t.float64, device=self.device))
+        self._behind_torch_stream()
+        self._call(self.lib.sdc_value_loss, n, _p(raw_values), _p(value_preds), _p(returns), scale, shift,
+                   A.finite_float(who, "clip_param", clip_param), A.finite_float(who, "huber_delta", huber_delta), flags, coef, _p(res.loss),
+                   _p(res.dvalue), _p(res.stats), self._stream(), refuses=True,
+                   wrote=(raw_values, value_preds, returns, res.loss, res.dvalue, res.stats))
+        return res
+
+    def critic_backward(self, share_obs, dvalue) -> CriticGrads:
+        """The gradient of L = sum_r dvalue[r] * raw_r with respect to every parameter of the critic last given to set_critic, over
+        stored rows (sdc_critic_backward: the forward recomputed per 16-row tile, the backward on the matrix cores, fixed summation
+        order: the same call gives the same bits; stream-ordered).  `share_obs` as critic_values takes it, `dvalue` fp32 of the rows'
+        shape (...), contiguous on this engine's device (ValueLossTerms.dvalue).  -> CriticGrads.  ValueError for another tensor and
+        before set_critic."""
+        t, who = self.torch, "critic_backward"
+        lead = A.share_rows(who, share_obs, self.device)
+        A.device_tensor(dvalue, who, "dvalue", t.float32, lead, None, self.device)
+        res = CriticGrads(t.empty(L.CRITIC_N_PARAMS, dtype=t.float32, device=self.device), t.empty((), dtype=t.float64, device=self.device))
+        self._behind_torch_stream()
+        self._call(self.lib.sdc_critic_backward, _p(share_obs), dvalue.numel(), _p(dvalue), _p(res.flat), _p(res.sq_norm), self._stream(),
+                   refuses=True, wrote=(share_obs, dvalue, res.flat, res.sq_norm))
+        return res
+
+    def critic_grads(self, batch, clip_param: float = 0.2, huber_delta: float = 10.0, use_huber_loss: bool = True,
+                     use_clipped_value_loss: bool = True, value_loss_coef: float = 1.0, value_norm=None):
+        """The gradient of the reference's critic loss (v_critic.py update: value_loss * value_loss_coef, the mean over the batch) for
+        an OnPolicyBatch with the critic NOW set: critic_raw_values over batch.share_obs[:T] -> value_loss against
+        batch.value_preds[:T] and batch.returns with coef = value_loss_coef / (T N) -> critic_backward.  `value_norm` as value_loss'
+        (a caller that keeps a ValueNorm updates it with the returns first, as the reference does, and passes it here).
+        -> (CriticGrads, ValueLossTerms).  The optimiser step is the caller's: step it over the 6459 values (assign_to) and call
+        set_critic."""
+        T = batch.n_steps
+        share = batch.share_obs[:T]
+        raw = self.critic_raw_values(share)
+        coef = A.finite_float("critic_grads", "value_loss_coef", value_loss_coef) / raw.numel()
+        terms = self.value_loss(raw, batch.value_preds[:T], batch.returns, clip_param, huber_delta, use_huber_loss, use_clipped_value_loss,
+                                value_norm=value_norm, coef=coef)
+        return self.critic_backward(share, terms.dvalue), terms
 
     # ------------------------------------------------------------------ state access (parity injection / checkpoint)
     def _state_array(self, name):

@@ -753,6 +753,24 @@ class SustainDCVecEnv(ShareVecEnv):
         """The gradient of the reference's actor loss for one agent of an OnPolicyBatch (SdcEngine.actor_grads) -> (ActorGrads, PPOTerms)"""
         return self.engine.actor_grads(batch, agent, *args, **kw)
 
+    def critic_raw_values(self, share_obs):
+        """The critic's own output for rows of share_obs, before its ValueNorm's scale and shift (SdcEngine.critic_raw_values)"""
+        return self.engine.critic_raw_values(share_obs)
+
+    def value_loss(self, raw_values, value_preds, returns, *args, **kw):
+        """The reference's value loss per element and its derivative per raw value (SdcEngine.value_loss, which documents the
+        arguments) -> ValueLossTerms"""
+        return self.engine.value_loss(raw_values, value_preds, returns, *args, **kw)
+
+    def critic_backward(self, share_obs, dvalue):
+        """The gradient of sum(dvalue * raw) with respect to the critic's parameters over stored rows (SdcEngine.critic_backward)
+        -> CriticGrads"""
+        return self.engine.critic_backward(share_obs, dvalue)
+
+    def critic_grads(self, batch, *args, **kw):
+        """The gradient of the reference's critic loss for an OnPolicyBatch (SdcEngine.critic_grads) -> (CriticGrads, ValueLossTerms)"""
+        return self.engine.critic_grads(batch, *args, **kw)
+
     def gae(self, rew, done, values, *args, **kw):
         """Returns, advantages and masks of a collected rollout (SdcEngine.gae, which documents the arguments and the result)"""
         return self.engine.gae(rew, done, values, *args, **kw)

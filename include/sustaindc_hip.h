@@ -242,7 +242,8 @@ const char* sdc_last_error(void);
  *        sdc_rollout_stats and sdc_plan_cem_groups likewise; sdc_set_plan_terms and sdc_get_plan_terms likewise;
  *        sdc_set_plan_forecast, sdc_get_plan_forecast and sdc_forecast_traces likewise; sdc_rollout_actor_stats, sdc_rollout_cem_stats
  *        and sdc_rollout_cem_groups_stats likewise; sdc_set_critic, sdc_critic_values, sdc_set_plan_critic and sdc_get_plan_critic
- *        likewise; sdc_gae and sdc_action_log_probs likewise; sdc_actor_evaluate and sdc_ppo_terms likewise) */
+ *        likewise; sdc_gae and sdc_action_log_probs likewise; sdc_actor_evaluate and sdc_ppo_terms likewise; sdc_critic_evaluate,
+ *        sdc_value_loss and sdc_critic_backward likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -659,7 +660,7 @@ int sdc_action_log_probs(sdc_handle* h, int n_steps, const int32_t* actions, con
  * (harl/algorithms/actors/on_policy_base.py evaluate_actions -> StochasticPolicy.evaluate_actions), which harl/runners/on_policy_ha_runner.py
  * runs over the whole buffer before and after every agent's update for the HAPPO factor, and the terms harl/algorithms/actors/happo.py and
  * mappo.py build from its log-probabilities (imp_weights, the clipped surrogate, the entropy).  No gradient: the backward pass is
- * sdc_actor_backward (THE ACTORS' GRADIENT below); the optimiser and the critic's value loss are not here.  Both calls are pure functions of their arrays, all device memory: they read no env
+ * sdc_actor_backward (THE ACTORS' GRADIENT below), the critic's value loss is THE CRITIC'S GRADIENT's; the optimiser is not here.  Both calls are pure functions of their arrays, all device memory: they read no env
  * state and move nothing in the engine; each is ordered on `stream` with no synchronisation.
  * sdc_actor_evaluate: the logits of agent_slot's network -- the one last given to sdc_set_actor for that slot, the network stated at
  * sdc_set_actor, fp32, the hidden layers on fp32-input matrix instructions, 16 rows per wavefront (csrc/sdc_rowmlp.hpp) -- for n_rows
@@ -706,8 +707,8 @@ int sdc_ppo_terms(sdc_handle* h, int n_steps, int agent, const float* new_log_pr
 /* THE ACTORS' GRADIENT.  replaces: loss.backward() of the reference's actor update (harl/algorithms/actors/happo.py update:
  * policy_loss - entropy_coef * dist_entropy, differentiated by autograd through StochasticPolicy.evaluate_actions) -- the gradient with
  * respect to every parameter of one agent's network, on fp32-input matrix instructions, in a fixed summation order.  NOT here: the
- * optimiser step, the critic's value loss and its gradient, minibatch shuffling (a caller steps an optimiser over the
- * SDC_ACTOR_N_PARAMS values and calls sdc_set_actor).  Both calls are pure functions of their arrays, all device memory: they read no
+ * optimiser step and minibatch shuffling (a caller steps an optimiser over the SDC_ACTOR_N_PARAMS values and calls sdc_set_actor);
+ * the critic's value loss and its gradient are THE CRITIC'S GRADIENT below.  Both calls are pure functions of their arrays, all device memory: they read no
  * env state and move nothing in the engine; each is ordered on `stream` with no synchronisation.
  * sdc_ppo_dlogp: the loss's derivative per stored log-probability, ONE launch of sdc_ppo_dlogp_kernel.  Per element i = t N + n < T N
  * with j = 3 i + agent, in fp64 with no fused multiply-add, in sdc_ppo_terms' words (lo = 1 - clip_param, hi = 1 + clip_param):
@@ -750,6 +751,65 @@ int sdc_ppo_dlogp(sdc_handle* h, int n_steps, int agent, const float* new_log_pr
                   const float* factor, double clip_param, double scale, float* dlogp, void* stream);
 int sdc_actor_backward(sdc_handle* h, int agent_slot, const float* obs, long long row_stride, long long n_rows, const int32_t* actions,
                        long long action_stride, const float* dlogp, double dent, float* grads, double* grad_sq, void* stream);
+
+/* THE CRITIC'S GRADIENT.  replaces: the critic's half of an on-policy update (harl/algorithms/critics/v_critic.py cal_value_loss and
+ * update's loss.backward(), harl/utils/models_tools.py huber_loss / mse_loss, harl/common/valuenorm.py normalize) -- the network's own
+ * output over stored share_obs rows, the clipped Huber / MSE value loss with its derivative per row, and the gradient with respect to
+ * every parameter of the critic.  NOT here: the optimiser step, ValueNorm's running update, minibatch shuffling (a caller updates its
+ * normaliser first, as the reference does, steps an optimiser over the SDC_CRITIC_N_PARAMS values and calls sdc_set_critic).  All three
+ * calls are pure functions of their arrays, all device memory: they read no env state and move nothing in the engine; each is ordered
+ * on `stream` with no synchronisation; no atomics: the same call gives the same bits on every run.
+ * sdc_critic_evaluate: raw_values[r] = u_r, the network's own output for share_obs row r BEFORE `* scale + shift` -- what the
+ * reference's critic(cent_obs) returns under a ValueNorm --, rows [n_rows][29] dense as sdc_critic_values'; ONE launch of
+ * sdc_critic_raw_kernel.  sdc_critic_values of the same row is (u_r * scale) + shift in fp32 with no fused multiply-add, bit for bit.
+ * Refused: what sdc_critic_values refuses.
+ * sdc_value_loss: per element i < n, with u, vp, ret = raw_values[i], value_preds[i], returns[i] widened to fp64, clip = clip_param,
+ * delta = huber_delta, in fp64 with no fused multiply-add, each stored result rounded once to fp32:
+ *     t   = (ret - target_shift) / target_scale            // ValueNorm.normalize; 1 and 0 without one
+ *     d   = u - vp;  dc = d < -clip ? -clip : (d > clip ? clip : d);  uc = vp + dc
+ *     eo  = t - u;   ec = t - uc
+ *     l(e)  = huber ? (|e| <= delta ? (e * e) / 2 : delta * (|e| - delta / 2)) : (e * e) / 2
+ *     l'(e) = huber ? (|e| <= delta ? e : (e > 0 ? delta : -delta)) : e
+ *     go  = -l'(eo);   gc = (-clip <= d && d <= clip) ? -l'(ec) : 0
+ *     clipped loss on:   L = l(eo) > l(ec) ? l(eo) : l(ec);
+ *                        g = l(eo) > l(ec) ? go : (l(eo) < l(ec) ? gc : 0.5 * go + 0.5 * gc)
+ *     clipped loss off:  L = l(eo);  g = go
+ *     loss[i] = (float)L;   dvalue[i] = (float)(coef * g)
+ * which is d(coef * sum_i L_i) / d u_i as torch differentiates the reference (clamp passes the gradient on its closed interval, the
+ * binary torch.max halves a tie, the Huber masks are constants).  flags bit 0: Huber loss (off: (e * e) / 2), bit 1: clipped value
+ * loss.  coef: a finite double; the reference's is value_loss_coef / n.  loss and stats may be NULL.
+ * stats [8] fp64 or NULL: 0 sum of (double)loss[i] (whether or not loss is stored)   1 sum of u   2 sum of eo   3 sum of eo * eo
+ *     4 number of elements with l(ec) > l(eo)   5 min of eo   6 max of eo   7 (double)n
+ * in sdc_ppo_terms' fixed two-stage order, word for word (B = min(ceil(n / 256), 1024) workgroups of 256 lanes, the same folding and
+ * halving; stage 2 IS sdc_ppo_stats_kernel): two launches, sdc_value_loss_kernel and sdc_ppo_stats_kernel; with stats NULL one.  The
+ * partials are a buffer of the handle's, allocated on first use.  It reads nothing from the handle but its device.
+ * Refused (-2 and a message, nothing enqueued): a null handle; n < 1; a null raw_values, value_preds, returns or dvalue; a float array
+ * not dword-aligned; stats not 8-byte aligned; target_scale not finite or <= 0; target_shift not finite; clip_param not finite or < 0;
+ * flag bits above bit 1; huber_delta not finite or <= 0 while bit 0 is set; coef not finite.
+ * sdc_critic_backward: with u_r the raw output of the critic last given to sdc_set_critic for share_obs row r, the gradient of
+ *     L = sum_r dvalue[r] * u_r
+ * with respect to the float members of sdc_critic_params from ln0_g to b3 in declaration order (torch's [out][in] layout), fp32
+ * [SDC_CRITIC_N_PARAMS] in `grads`; scale and shift are no parameters and get no gradient; nothing is propagated to share_obs.  The
+ * backward is THE ACTORS' GRADIENT's (Linear, LayerNorm, tanh' / relu' as stated there) over the call's own forward
+ * (csrc/sdc_critic_grad.hpp, fp32); the head has one output: dy2 = w3 * dvalue[r], db3 = sum_r dvalue[r], and with S = sum_r dvalue[r]
+ * * n2_r (n2: the second hidden LayerNorm's normalised values) dgain2 = w3 * S, dbeta2 = w3 * db3, dW3 = gain2 * S + beta2 * db3 -- per
+ * wavefront of a workgroup, then summed as everything else.  The feature LayerNorm's gain and bias receive gradients when flags bit 0
+ * is on and exact zeros when it is off.  Doubling dvalue doubles every gradient exactly; all-zero coefficients give all-zero gradients.
+ * THE ORDER OF EVERY SUM IS FIXED as sdc_actor_backward's: B = min(ceil(n_rows / 64), SDC_CRITIC_GRAD_MAX_BLOCKS) workgroups (a
+ * function of n_rows alone) each write one fp32 partial [SDC_CRITIC_N_PARAMS] into a buffer of the handle's, allocated on first use
+ * (sdc_critic_grad_tanh_kernel / sdc_critic_grad_relu_kernel); sdc_critic_grad_reduce_kernel adds a parameter's B partials in
+ * workgroup order in fp64 and rounds once to fp32.  grad_sq [1] fp64 or NULL: the sum of squares of the STORED fp32 grads in the order
+ * sdc_actor_backward documents, over SDC_CRITIC_N_PARAMS values (sdc_critic_grad_sq_kernel).
+ * Refused (-2 and a message, nothing enqueued): a null handle; no critic set; n_rows < 1; a null share_obs, dvalue or grads; one of
+ * them not dword-aligned; grad_sq not 8-byte aligned. */
+#define SDC_CRITIC_N_PARAMS 6459
+#define SDC_CRITIC_GRAD_MAX_BLOCKS 256
+int sdc_critic_evaluate(sdc_handle* h, const float* share_obs, long long n_rows, float* raw_values, void* stream);
+int sdc_value_loss(sdc_handle* h, long long n, const float* raw_values, const float* value_preds, const float* returns, double target_scale,
+                   double target_shift, double clip_param, double huber_delta, int flags, double coef, float* loss, float* dvalue,
+                   double* stats, void* stream);
+int sdc_critic_backward(sdc_handle* h, const float* share_obs, long long n_rows, const float* dvalue, float* grads, double* grad_sq,
+                        void* stream);
 
 /* PLAN FORECAST: what the plan calls' rollouts believe the traces of the next n_steps steps are.  Without one a plan call's rollouts
  * read the episode's own feature rows -- the real workload, carbon intensity, dry bulb (with the weather noise the episode drew) and wet
