@@ -177,6 +177,52 @@ def any_shape(who, x, name, dtype, device):
     return tuple(x.shape)
 
 
+# ---------------------------------------------------------------------- the optimiser step
+def adam_struct(who, lr, betas, eps, weight_decay, max_grad_norm) -> L.SdcAdam:
+    """the step's hyper-parameters as the library's struct (max_grad_norm None: +inf, no clipping); ValueError in the caller's name for
+    what is no number or no pair of betas -- the ranges are the library's to refuse"""
+    try:
+        b1, b2 = betas
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: betas = {betas!r} must be a pair (beta1, beta2)") from None
+    num = lambda name, v: finite_float(who, name, v)
+    return L.SdcAdam(lr=num("lr", lr), beta1=num("beta1", b1), beta2=num("beta2", b2), eps=num("eps", eps),
+                     weight_decay=num("weight_decay", weight_decay),
+                     max_grad_norm=float("inf") if max_grad_norm is None else num("max_grad_norm", max_grad_norm))
+
+
+def flat_grads(who, grads, n, device):
+    """an ActorGrads / CriticGrads (anything with .flat) or a flat tensor -> the contiguous float32 CUDA tensor [n] on `device`"""
+    import torch
+    flat = getattr(grads, "flat", grads)
+    device_tensor(flat, who, "grads", torch.float32, (n,), f"({n},)", device)
+    return flat
+
+
+def optim_which(who, which):
+    """`which` network an optimiser state belongs to: an agent slot 0 .. 2 -> that int, "critic" -> None; ValueError for anything else"""
+    if isinstance(which, str):
+        if which != "critic":
+            raise ValueError(f"{who}: which = {which!r} must be an agent slot 0 (ls), 1 (dc), 2 (bat) or 'critic'")
+        return None
+    return agent_slot(who, which, "which")
+
+
+def optim_arrays(who, state, n):
+    """load_optim_state's `state` -> (m, v as contiguous float32 arrays [n], L.SdcOptimState); ValueError / KeyError in the caller's name"""
+    arrays = []
+    for name in ("m", "v"):
+        if name not in state:
+            raise KeyError(f"{who}: the state holds no {name!r}")
+        a = np.ascontiguousarray(state[name].detach().cpu().numpy() if hasattr(state[name], "detach") else state[name], dtype=np.float32)
+        if a.shape != (n,):
+            raise ValueError(f"{who}: {name} has shape {a.shape}, expected ({n},)")
+        arrays.append(a)
+    st = L.SdcOptimState(step=int(state.get("step", 0)), beta1_pow=float(state.get("beta1_pow", 1.0)),
+                         beta2_pow=float(state.get("beta2_pow", 1.0)), skipped=int(state.get("skipped", 0)))
+    return arrays[0], arrays[1], st
+
+
 # ---------------------------------------------------------------------- the horizon of lookahead and plan
 def check_horizon(who, K, left=None, auto_reset=False):
     """ValueError for a horizon a mark cannot hold and -- `left` = steps_to_episode_end() given -- one that would finish an episode"""

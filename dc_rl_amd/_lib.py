@@ -25,7 +25,7 @@ LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
            "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip", "sdc_plan_terms.hip",
            "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip", "sdc_mpc_groups.hip", "sdc_critic.hip", "sdc_onpolicy.hip", "sdc_actor_eval.hip",
-           "sdc_actor_grad.hip", "sdc_critic_grad.hip"]
+           "sdc_actor_grad.hip", "sdc_critic_grad.hip", "sdc_optim.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
@@ -185,6 +185,17 @@ class SdcCriticParams(C.Structure):
     ]
 
 
+class SdcAdam(C.Structure):
+    """One Adam step's hyper-parameters (include/sustaindc_hip.h sdc_adam; max_grad_norm +inf: no clipping)."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("max_grad_norm", C.c_double)]
+
+
+class SdcOptimState(C.Structure):
+    """A network's optimiser state block (include/sustaindc_hip.h sdc_optim_state)."""
+    _fields_ = [("step", C.c_int64), ("beta1_pow", C.c_double), ("beta2_pow", C.c_double), ("skipped", C.c_int64)]
+
+
 class SdcPlanObjective(C.Structure):
     """What sdc_plan scores a candidate by (include/sustaindc_hip.h sdc_plan_objective)."""
     _fields_ = [
@@ -254,6 +265,8 @@ EXPORTS = [
     "sdc_set_critic", "sdc_critic_values", "sdc_set_plan_critic", "sdc_get_plan_critic",
     "sdc_gae", "sdc_action_log_probs", "sdc_actor_evaluate", "sdc_ppo_terms", "sdc_ppo_dlogp", "sdc_actor_backward",
     "sdc_critic_evaluate", "sdc_value_loss", "sdc_critic_backward",
+    "sdc_actor_adam_step", "sdc_critic_adam_step", "sdc_get_actor", "sdc_get_critic", "sdc_get_actor_optim", "sdc_set_actor_optim",
+    "sdc_get_critic_optim", "sdc_set_critic_optim", "sdc_set_critic_norm",
 ]
 
 
@@ -438,6 +451,15 @@ def load():
     L.sdc_critic_evaluate.argtypes = [vp, fp, C.c_longlong, fp, vp]
     L.sdc_value_loss.argtypes = [vp, C.c_longlong, fp, fp, fp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, fp, fp, vp, vp]
     L.sdc_critic_backward.argtypes = [vp, fp, C.c_longlong, fp, fp, vp, vp]
+    L.sdc_actor_adam_step.argtypes = [vp, C.c_int, fp, C.POINTER(SdcAdam), vp, vp]
+    L.sdc_critic_adam_step.argtypes = [vp, fp, C.POINTER(SdcAdam), vp, vp]
+    L.sdc_get_actor.argtypes = [vp, C.c_int, C.POINTER(SdcActorParams)]
+    L.sdc_get_critic.argtypes = [vp, C.POINTER(SdcCriticParams)]
+    L.sdc_get_actor_optim.argtypes = [vp, C.c_int, fp, fp, C.POINTER(SdcOptimState)]
+    L.sdc_set_actor_optim.argtypes = [vp, C.c_int, fp, fp, C.POINTER(SdcOptimState)]
+    L.sdc_get_critic_optim.argtypes = [vp, fp, fp, C.POINTER(SdcOptimState)]
+    L.sdc_set_critic_optim.argtypes = [vp, fp, fp, C.POINTER(SdcOptimState)]
+    L.sdc_set_critic_norm.argtypes = [vp, C.c_double, C.c_double, vp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

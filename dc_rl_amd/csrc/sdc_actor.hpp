@@ -27,25 +27,8 @@
 #pragma once
 #include "sdc_device.hpp"
 
-#define SDC_ACT_IN SDC_OBS_PAD     // 26
-#define SDC_ACT_M1 7               // K-quads of layer 1 (26 inputs padded to 28)
-#define SDC_ACT_H 64
-#define SDC_ACT_M2 (SDC_ACT_H / 4)
-#define SDC_ACT_OUT 3
-
-// one agent's actor as the kernel reads it (device memory, then LDS); filled by sdc_set_actor (sdc_capi.hip)
-struct SdcActorDev {
-  float ln0_g[32], ln0_b[32];                 // feature LayerNorm over the 26 inputs (entries 26.. unused)
-  float w1[SDC_ACT_M1][SDC_ACT_H][4];         // w1[m][j][v] = W1[j][4 m + v]   (W as torch stores it: [out][in]; 0 beyond k = 25)
-  float w2[SDC_ACT_M2][SDC_ACT_H][4];         // w2[m][j][v] = W2[j][4 m + v]: one ds_read_b128 per lane = four B operands
-  float w3[4][SDC_ACT_H];                     // w3[c][j] = W3[c][j], c < 3
-  float b1[SDC_ACT_H], ln1_g[SDC_ACT_H], ln1_b[SDC_ACT_H];
-  float b2[SDC_ACT_H], ln2_g[SDC_ACT_H], ln2_b[SDC_ACT_H];
-  float b3[4];
-  int flags;                                  // bit 0: feature LayerNorm on; bits 1-2: activation (0 tanh, 1 relu)
-  int pad[3];
-};
-static_assert(sizeof(SdcActorDev) % 16 == 0, "copied to LDS as uint4");
+// (the sizes SDC_ACT_*, SdcActorDev -- one agent's actor as the kernel reads it -- and the pack into it: HIP-free, next door)
+#include "sdc_actor_pack.hpp"
 
 namespace sdc_act {
 

@@ -43,6 +43,8 @@
 #include "sdc_actor_eval.hpp"
 #include "sdc_actor_grad.hpp"
 #include "sdc_critic_grad.hpp"
+#include "sdc_optim_dev.hpp"
+#include "sdc_pack_tables.hpp"
 #include "sdc_mpc.hpp"
 #include "sdc_mpc_groups.hpp"
 #include "sdc_mpc_schedule.hpp"
@@ -186,6 +188,25 @@ struct sdc_handle {
   int critic_activation = 0;
   float* critic_grad_part = nullptr;
   double* value_loss_part = nullptr;
+  // the optimiser step (sdc_optim.hip): per actor slot and for the critic the master parameters, Adam's moments (each [3][SDC_ACTOR_N_PARAMS]
+  // / [SDC_CRITIC_N_PARAMS] fp32) and the state block, allocated and filled with the packed copies by sdc_set_actor / sdc_set_critic; the
+  // gather tables of the packed copies (sdc_pack_tables.hpp), uploaded once per handle; and what a get hands back that is no parameter:
+  // the host record of the actors' flags and of the critic's scale, shift and flags
+  float* actor_params = nullptr;
+  float* actor_m = nullptr;
+  float* actor_v = nullptr;
+  sdc_optim_state* actor_optim = nullptr;
+  int32_t* actor_table = nullptr;
+  int actor_table_offset[4] = {0, 0, 0, 0};
+  int actor_feature_norm[3] = {0, 0, 0};
+  float* critic_params = nullptr;
+  float* critic_m = nullptr;
+  float* critic_v = nullptr;
+  sdc_optim_state* critic_optim = nullptr;
+  int32_t* critic_table = nullptr;
+  int critic_table_offset[3] = {0, 0, 0};
+  float critic_scale = 1.0f, critic_shift = 0.0f;
+  int critic_flags = 0;
 };
 
 namespace {
@@ -208,6 +229,25 @@ int dev_alloc(sdc_handle* h, T** p, size_t count, bool zero = true) {
   if (zero) HIP_TRY(hipMemset(q, 0, count * sizeof(T)));
   h->allocs.push_back(q);
   *p = reinterpret_cast<T*>(q);
+  return 0;
+}
+
+// a network's optimiser from new (sdc_set_actor / sdc_set_critic; the device is idle): the master copy filled from the params struct's
+// leading floats, the moments zeroed, the state block reset
+int optim_reset(const void* host_params, const size_t n, float* params, float* m, float* v, sdc_optim_state* state) {
+  const sdc_optim_state fresh{0, 1.0, 1.0, 0};
+  HIP_TRY(hipMemcpy(params, host_params, n * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(m, 0, n * sizeof(float)));
+  HIP_TRY(hipMemset(v, 0, n * sizeof(float)));
+  HIP_TRY(hipMemcpy(state, &fresh, sizeof(fresh), hipMemcpyHostToDevice));
+  return 0;
+}
+// a gather table (sdc_pack_tables.hpp) on the device
+template <int PACKS>
+int upload_table(sdc_handle* h, const SdcPackTables<PACKS>& t, int32_t** dev, int (&offset)[PACKS + 1]) {
+  if (dev_alloc(h, dev, t.table.size(), false) != 0) return -1;
+  HIP_TRY(hipMemcpy(*dev, t.table.data(), t.table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  for (int i = 0; i <= PACKS; i++) offset[i] = t.offset[i];
   return 0;
 }
 
@@ -908,6 +948,11 @@ int sdc_set_actor(sdc_handle* h, int slot, const sdc_actor_params* p) {
     if (dev_alloc(h, &h->actor_dev, 3) != 0) return -1;
     if (dev_alloc(h, &h->actor_eval_dev, 3) != 0) return -1;
     if (dev_alloc(h, &h->actor_grad_dev, 3) != 0) return -1;
+    if (dev_alloc(h, &h->actor_params, (size_t)3 * SDC_ACTOR_N_PARAMS) != 0) return -1;
+    if (dev_alloc(h, &h->actor_m, (size_t)3 * SDC_ACTOR_N_PARAMS) != 0) return -1;
+    if (dev_alloc(h, &h->actor_v, (size_t)3 * SDC_ACTOR_N_PARAMS) != 0) return -1;
+    if (dev_alloc(h, &h->actor_optim, 3) != 0) return -1;
+    if (upload_table(h, sdc_actor_pack_tables(), &h->actor_table, h->actor_table_offset) != 0) return -1;
     if (dev_alloc(h, &h->obs_latch, (size_t)h->cfg.n_envs * SDC_OBS_OUT) != 0) return -1;
     h->latch_valid = false;      // (filled by the next reset / step / rollout)
   }
@@ -916,20 +961,7 @@ int sdc_set_actor(sdc_handle* h, int slot, const sdc_actor_params* p) {
   // other host threads -- ctypes releases the GIL during this call)
   std::unique_ptr<SdcActorDev> ap(new SdcActorDev);
   SdcActorDev& a = *ap;
-  std::memset(&a, 0, sizeof(a));
-  for (int k = 0; k < SDC_ACT_IN; k++) {
-    a.ln0_g[k] = p->ln0_gamma[k];
-    a.ln0_b[k] = p->ln0_beta[k];
-  }
-  for (int j = 0; j < SDC_ACT_H; j++) {
-    for (int k = 0; k < SDC_ACT_IN; k++) a.w1[k / 4][j][k & 3] = p->w1[j * SDC_ACT_IN + k];
-    for (int k = 0; k < SDC_ACT_H; k++) a.w2[k / 4][j][k & 3] = p->w2[j * SDC_ACT_H + k];
-    a.b1[j] = p->b1[j]; a.ln1_g[j] = p->ln1_gamma[j]; a.ln1_b[j] = p->ln1_beta[j];
-    a.b2[j] = p->b2[j]; a.ln2_g[j] = p->ln2_gamma[j]; a.ln2_b[j] = p->ln2_beta[j];
-    for (int c = 0; c < SDC_ACT_OUT; c++) a.w3[c][j] = p->w3[c * SDC_ACT_H + j];
-  }
-  for (int c = 0; c < SDC_ACT_OUT; c++) a.b3[c] = p->b3[c];
-  a.flags = (p->use_feature_normalization ? 1 : 0) | (p->activation << 1);
+  sdc_actor_pack(p, &a);
   // ... and the same parameters as sdc_actor_evaluate's kernel reads them (sdc_actor_eval_pack.hpp)
   std::unique_ptr<SdcActorEvalDev> packed(new SdcActorEvalDev);
   sdc_actor_eval_pack(p, packed.get());
@@ -940,8 +972,12 @@ int sdc_set_actor(sdc_handle* h, int slot, const sdc_actor_params* p) {
   HIP_TRY(hipMemcpy(h->actor_dev + slot, &a, sizeof(a), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->actor_eval_dev + slot, packed.get(), sizeof(SdcActorEvalDev), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->actor_grad_dev + slot, packed_t.get(), sizeof(SdcActorGradDev), hipMemcpyHostToDevice));
+  // ... and the optimiser's master copy, with a new optimiser (sdc_optim.hip)
+  const size_t at = (size_t)slot * SDC_ACTOR_N_PARAMS;
+  if (optim_reset(p, SDC_ACTOR_N_PARAMS, h->actor_params + at, h->actor_m + at, h->actor_v + at, h->actor_optim + slot) != 0) return -1;
   h->actor_set[slot] = true;
   h->actor_activation[slot] = p->activation;
+  h->actor_feature_norm[slot] = p->use_feature_normalization ? 1 : 0;
   return 0;
 }
 
@@ -1780,6 +1816,13 @@ int sdc_set_critic(sdc_handle* h, const sdc_critic_params* p) {
   HIP_TRY(hipSetDevice(h->device));
   if (!h->critic_dev && dev_alloc(h, &h->critic_dev, 1) != 0) return -1;
   if (!h->critic_grad_dev && dev_alloc(h, &h->critic_grad_dev, 1) != 0) return -1;
+  if (!h->critic_params) {
+    if (dev_alloc(h, &h->critic_params, (size_t)SDC_CRITIC_N_PARAMS) != 0) return -1;
+    if (dev_alloc(h, &h->critic_m, (size_t)SDC_CRITIC_N_PARAMS) != 0) return -1;
+    if (dev_alloc(h, &h->critic_v, (size_t)SDC_CRITIC_N_PARAMS) != 0) return -1;
+    if (dev_alloc(h, &h->critic_optim, 1) != 0) return -1;
+    if (upload_table(h, sdc_critic_pack_tables(), &h->critic_table, h->critic_table_offset) != 0) return -1;
+  }
   std::unique_ptr<SdcCriticDev> packed(new SdcCriticDev);      // (26 KB: on the heap, per call -- see sdc_set_actor)
   sdc_critic_pack(p, packed.get());
   // ... and the transposed weights as sdc_critic_backward's kernel reads them (sdc_critic_grad_pack.hpp)
@@ -1788,8 +1831,13 @@ int sdc_set_critic(sdc_handle* h, const sdc_critic_params* p) {
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(h->critic_dev, packed.get(), sizeof(SdcCriticDev), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->critic_grad_dev, packed_t.get(), sizeof(SdcCriticGradDev), hipMemcpyHostToDevice));
+  // ... and the optimiser's master copy, with a new optimiser (sdc_optim.hip)
+  if (optim_reset(p, SDC_CRITIC_N_PARAMS, h->critic_params, h->critic_m, h->critic_v, h->critic_optim) != 0) return -1;
   h->critic_set = true;
   h->critic_activation = (p->flags >> 1) & 3;
+  h->critic_scale = p->scale;
+  h->critic_shift = p->shift;
+  h->critic_flags = p->flags;
   return 0;
 }
 
@@ -2006,6 +2054,123 @@ int sdc_get_plan_critic(const sdc_handle* h, double* weight) {
   if (!h || !weight) return fail_msg("sdc_get_plan_critic: null handle or out");
   *weight = h->plan_critic_weight;
   return 0;
+}
+
+// ---- the optimiser step (sdc_optim.hip) ------------------------------------------------------------------------------------------------
+// The contract and the arithmetic: include/sustaindc_hip.h THE OPTIMISER STEP; the kernel's plan: sdc_optim_dev.hpp.
+int sdc_actor_adam_step(sdc_handle* h, int agent_slot, const float* grads, const sdc_adam* adam, double* grad_norm, void* stream) {
+  if (refused(sdc_adam_step_refused("sdc_actor_adam_step", call_facts(h), true, agent_slot, grads, adam, grad_norm))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t at = (size_t)agent_slot * SDC_ACTOR_N_PARAMS;
+  SdcAdamStep P{};
+  P.grads = grads;
+  P.params = h->actor_params + at;
+  P.m = h->actor_m + at;
+  P.v = h->actor_v + at;
+  P.state = h->actor_optim + agent_slot;
+  P.grad_norm = grad_norm;
+  P.adam = *adam;
+  P.n = SDC_ACTOR_N_PARAMS;
+  P.first = h->actor_feature_norm[agent_slot] ? 0 : 2 * SDC_ACT_IN;
+  P.n_packs = 3;
+  P.table = h->actor_table;
+  P.pack[0] = reinterpret_cast<uint32_t*>(h->actor_dev + agent_slot);
+  P.pack[1] = reinterpret_cast<uint32_t*>(h->actor_eval_dev + agent_slot);
+  P.pack[2] = reinterpret_cast<uint32_t*>(h->actor_grad_dev + agent_slot);
+  for (int i = 0; i < 3; i++) P.pack_dwords[i] = h->actor_table_offset[i + 1] - h->actor_table_offset[i];
+  h->last_step_kernel = "sdc_adam_gather_kernel";
+  return launched("sdc_adam_update_kernel / sdc_adam_gather_kernel", sdc_adam_step_launch(P, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int sdc_critic_adam_step(sdc_handle* h, const float* grads, const sdc_adam* adam, double* grad_norm, void* stream) {
+  if (refused(sdc_adam_step_refused("sdc_critic_adam_step", call_facts(h), false, -1, grads, adam, grad_norm))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  SdcAdamStep P{};
+  P.grads = grads;
+  P.params = h->critic_params;
+  P.m = h->critic_m;
+  P.v = h->critic_v;
+  P.state = h->critic_optim;
+  P.grad_norm = grad_norm;
+  P.adam = *adam;
+  P.n = SDC_CRITIC_N_PARAMS;
+  P.first = (h->critic_flags & 1) ? 0 : 2 * SDC_CRITIC_IN;
+  P.n_packs = 2;
+  P.table = h->critic_table;
+  P.pack[0] = reinterpret_cast<uint32_t*>(h->critic_dev);
+  P.pack[1] = reinterpret_cast<uint32_t*>(h->critic_grad_dev);
+  for (int i = 0; i < 2; i++) P.pack_dwords[i] = h->critic_table_offset[i + 1] - h->critic_table_offset[i];
+  h->last_step_kernel = "sdc_adam_gather_kernel";
+  return launched("sdc_adam_update_kernel / sdc_adam_gather_kernel", sdc_adam_step_launch(P, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int sdc_get_actor(sdc_handle* h, int agent_slot, sdc_actor_params* out) {
+  if (refused(sdc_optim_get_refused("sdc_get_actor", call_facts(h), true, agent_slot, out != nullptr))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, h->actor_params + (size_t)agent_slot * SDC_ACTOR_N_PARAMS, sizeof(float) * SDC_ACTOR_N_PARAMS, hipMemcpyDeviceToHost));
+  out->use_feature_normalization = h->actor_feature_norm[agent_slot];
+  out->activation = h->actor_activation[agent_slot];
+  return 0;
+}
+
+int sdc_get_critic(sdc_handle* h, sdc_critic_params* out) {
+  if (refused(sdc_optim_get_refused("sdc_get_critic", call_facts(h), false, -1, out != nullptr))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, h->critic_params, sizeof(float) * SDC_CRITIC_N_PARAMS, hipMemcpyDeviceToHost));
+  out->scale = h->critic_scale;
+  out->shift = h->critic_shift;
+  out->flags = h->critic_flags;
+  return 0;
+}
+
+// the moments and the state block of one network <-> host memory (the device is waited for)
+static int optim_get(sdc_handle* h, const size_t n, const float* dm, const float* dv, const sdc_optim_state* ds, float* m, float* v,
+                     sdc_optim_state* st) {
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(m, dm, n * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(v, dv, n * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(st, ds, sizeof(*st), hipMemcpyDeviceToHost));
+  return 0;
+}
+static int optim_put(sdc_handle* h, const size_t n, float* dm, float* dv, sdc_optim_state* ds, const float* m, const float* v,
+                     const sdc_optim_state* st) {
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(dm, m, n * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dv, v, n * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ds, st, sizeof(*st), hipMemcpyHostToDevice));
+  return 0;
+}
+
+int sdc_get_actor_optim(sdc_handle* h, int agent_slot, float* m, float* v, sdc_optim_state* st) {
+  if (refused(sdc_optim_get_refused("sdc_get_actor_optim", call_facts(h), true, agent_slot, m && v && st))) return -2;
+  const size_t at = (size_t)agent_slot * SDC_ACTOR_N_PARAMS;
+  return optim_get(h, SDC_ACTOR_N_PARAMS, h->actor_m + at, h->actor_v + at, h->actor_optim + agent_slot, m, v, st);
+}
+int sdc_set_actor_optim(sdc_handle* h, int agent_slot, const float* m, const float* v, const sdc_optim_state* st) {
+  if (refused(sdc_set_optim_refused("sdc_set_actor_optim", call_facts(h), true, agent_slot, m, v, st))) return -2;
+  const size_t at = (size_t)agent_slot * SDC_ACTOR_N_PARAMS;
+  return optim_put(h, SDC_ACTOR_N_PARAMS, h->actor_m + at, h->actor_v + at, h->actor_optim + agent_slot, m, v, st);
+}
+int sdc_get_critic_optim(sdc_handle* h, float* m, float* v, sdc_optim_state* st) {
+  if (refused(sdc_optim_get_refused("sdc_get_critic_optim", call_facts(h), false, -1, m && v && st))) return -2;
+  return optim_get(h, SDC_CRITIC_N_PARAMS, h->critic_m, h->critic_v, h->critic_optim, m, v, st);
+}
+int sdc_set_critic_optim(sdc_handle* h, const float* m, const float* v, const sdc_optim_state* st) {
+  if (refused(sdc_set_optim_refused("sdc_set_critic_optim", call_facts(h), false, -1, m, v, st))) return -2;
+  return optim_put(h, SDC_CRITIC_N_PARAMS, h->critic_m, h->critic_v, h->critic_optim, m, v, st);
+}
+
+int sdc_set_critic_norm(sdc_handle* h, double scale, double shift, void* stream) {
+  if (refused(sdc_set_critic_norm_refused(call_facts(h), scale, shift))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  h->critic_scale = (float)scale;
+  h->critic_shift = (float)shift;
+  return launched("sdc_critic_norm_kernel",
+                  sdc_critic_norm_launch(SdcCriticNorm{h->critic_dev, h->critic_scale, h->critic_shift}, reinterpret_cast<hipStream_t>(stream)));
 }
 
 // ---- plan with the cross-entropy method (sdc_cem.hip, sdc_cem_groups.hip) -----------------------------------------------------------

@@ -27,6 +27,7 @@
 #include "sdc_dispatch.hpp"
 #include "sdc_mirror.hpp"
 #include "sdc_mpc_schedule.hpp"
+#include "sdc_optim.hpp"
 
 using SdcMsg = std::optional<std::string>;
 
@@ -694,6 +695,51 @@ static inline SdcMsg sdc_critic_backward_refused(const SdcCallFacts& f, const fl
   if (!share_obs || !dvalue || !grads) return w + "null array (share_obs, dvalue and grads are required)";
   if ((sdc_addr_bits(share_obs, dvalue, grads) & 3u) != 0) return w + "share_obs / dvalue / grads not dword-aligned";
   if ((sdc_addr_bits(grad_sq) & 7u) != 0) return w + "grad_sq not 8-byte aligned";
+  return std::nullopt;
+}
+
+// ---- the optimiser step ------------------------------------------------------------------------------------------------------------------------
+// (what is refused about an sdc_adam and an sdc_optim_state: sdc_optim.hpp; the texts are held by tests/test_optim_abi.py.  `who`: the
+// entry point; agent_slot < 0 where `who` is one of the critic's: its rule about the network is "sdc_set_critic first")
+static inline SdcMsg sdc_optim_network_refused(const std::string& w, const SdcCallFacts& f, const bool actor, const int agent_slot) {
+  if (!f.handle) return w + "null handle";
+  if (actor) {
+    if (agent_slot < 0 || agent_slot > 2) return w + "agent_slot = " + std::to_string(agent_slot) + " outside [0, 2]";
+    if (!f.actor_set[agent_slot]) return w + "no actor is set for agent_slot " + std::to_string(agent_slot) + " (sdc_set_actor first)";
+  } else if (!f.critic_set) {
+    return w + "sdc_set_critic first";
+  }
+  return std::nullopt;
+}
+static inline SdcMsg sdc_adam_step_refused(const char* who, const SdcCallFacts& f, const bool actor, const int agent_slot, const float* grads,
+                                           const sdc_adam* adam, const double* grad_norm) {
+  const std::string w = std::string(who) + ": ";
+  if (SdcMsg m = sdc_optim_network_refused(w, f, actor, agent_slot)) return m;
+  if (!grads) return w + "null grads";
+  if ((sdc_addr_bits(grads) & 3u) != 0) return w + "grads not dword-aligned";
+  if ((sdc_addr_bits(grad_norm) & 7u) != 0) return w + "grad_norm not 8-byte aligned";
+  if (const char* why = sdc_adam_error(adam)) return w + why;
+  return std::nullopt;
+}
+// sdc_get_actor / sdc_get_critic / sdc_get_*_optim: `out_ok`: every output pointer is there
+static inline SdcMsg sdc_optim_get_refused(const char* who, const SdcCallFacts& f, const bool actor, const int agent_slot, const bool out_ok) {
+  const std::string w = std::string(who) + ": ";
+  if (SdcMsg m = sdc_optim_network_refused(w, f, actor, agent_slot)) return m;
+  if (!out_ok) return w + "null output";
+  return std::nullopt;
+}
+static inline SdcMsg sdc_set_optim_refused(const char* who, const SdcCallFacts& f, const bool actor, const int agent_slot, const float* m,
+                                           const float* v, const sdc_optim_state* st) {
+  const std::string w = std::string(who) + ": ";
+  if (SdcMsg msg = sdc_optim_network_refused(w, f, actor, agent_slot)) return msg;
+  if (const char* why = sdc_optim_state_error(m, v, st, actor ? SDC_ACTOR_N_PARAMS : SDC_CRITIC_N_PARAMS)) return w + why;
+  return std::nullopt;
+}
+static inline SdcMsg sdc_set_critic_norm_refused(const SdcCallFacts& f, const double scale, const double shift) {
+  static const std::string w = "sdc_set_critic_norm: ";
+  if (SdcMsg m = sdc_optim_network_refused(w, f, false, -1)) return m;
+  if (!std::isfinite((float)scale) || !std::isfinite((float)shift)) return w + "an entry that is not finite";
+  if (!((float)scale > 0.0f)) return w + "scale must be positive";
   return std::nullopt;
 }
 

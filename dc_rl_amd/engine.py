@@ -559,6 +559,20 @@ _CRITIC_SHAPES = {"ln0_g": (29,), "ln0_b": (29,), "w1": (64, 29), "b1": (64,), "
                   "w2": (64, 64), "b2": (64,), "ln2_g": (64,), "ln2_b": (64,), "w3": (64,), "b3": ()}
 
 
+def _struct_state_dict(p, shapes, keys, sd_shapes, feature_norm):
+    """a params struct's float members under the reference's state_dict keys, as torch tensors on the host (copies); without the
+    feature LayerNorm's two when it is off, as the reference's module has none then"""
+    import torch
+    out = {}
+    for field, shape in shapes.items():
+        if not feature_norm and field.startswith("ln0_"):
+            continue
+        v = getattr(p, field)
+        a = np.array(v, dtype=np.float32) if isinstance(v, float) else np.ctypeslib.as_array(v).astype(np.float32, copy=True)
+        out[keys[field]] = torch.from_numpy(a.reshape(sd_shapes.get(field, shape)).copy())
+    return out
+
+
 def value_norm_scale_shift(value_norm):
     """A ValueNorm folded into (scale, shift) of `value * scale + shift`, in fp32 as harl/common/valuenorm.py running_mean_var and
     denormalize do it: None -> (1, 0); a (mean, var) pair -> (sqrt(var), mean); an object or dict with running_mean, running_mean_sq
@@ -658,8 +672,10 @@ class SdcEngine:
         self._out_ptrs = None
         self._done_buf = None
         self._forecast_values = None      # set_plan_forecast's `values`, kept alive while the library holds its address
-        self._actors = {}                 # set_actor's structs by slot
-        self._critic = None               # set_critic's struct
+        self._actors = {}                 # set_actor's structs by slot; the slots of _stale_actors have been stepped on the device since
+        self._critic = None               # set_critic's struct (_stale_critic likewise): _host_actors() / _host_critic() refresh them
+        self._stale_actors = set()
+        self._stale_critic = False
         with torch.cuda.device(self.device):
             torch.cuda.init()
             L.check(self.lib.sdc_create(C.byref(cfg), C.byref(self._h)))
@@ -867,6 +883,7 @@ class SdcEngine:
     def _set_actor_struct(self, slot: int, p: L.SdcActorParams):
         self._call(self.lib.sdc_set_actor, slot, C.byref(p))
         self._actors[slot] = p      # (the host copy: what a copy of this engine is given, SustainDCVecEnv._take_state)
+        self._stale_actors.discard(slot)
 
     def rollout_actor(self, n_steps: int, sample: bool = False, want_logits: bool = False, want_values: bool = False):
         """K env-steps in ONE launch with the three actors (set_actor) choosing every action inside the kernel from the
@@ -904,6 +921,7 @@ class SdcEngine:
     def _set_critic_struct(self, p: L.SdcCriticParams):
         self._call(self.lib.sdc_set_critic, C.byref(p), refuses=True)
         self._critic = p      # (the host copy: what a copy of this engine is given, SustainDCVecEnv._take_state)
+        self._stale_critic = False
 
     def critic_values(self, share_obs):
         """The critic's value of every row of `share_obs`, a contiguous fp32 tensor [..., 29] on this engine's device -> fp32 [...]
@@ -1149,8 +1167,8 @@ class SdcEngine:
         """The gradient of the reference's actor loss (happo.py update: policy_loss - entropy_coef * dist_entropy, every active mask
         one) for one agent of an OnPolicyBatch with the actor NOW set: evaluate_actions -> ppo_terms -> ppo_dlogp -> actor_backward
         with batch.normalized_advantages(), scale = 1 / (T N) and dent = -entropy_coef / (T N); `factor` and `old_log_probs` as
-        actor_update_terms'.  -> (ActorGrads, PPOTerms).  The optimiser step is the caller's: step it over the 6391 values (assign_to)
-        and call set_actor."""
+        actor_update_terms'.  -> (ActorGrads, PPOTerms).  The optimiser step: actor_adam_step on the device (actor_update chains
+        the two), or a caller's own over the 6391 values (assign_to) and set_actor."""
         a = A.agent_slot("actor_grads", agent)
         T = batch.n_steps
         n = T * self.n_envs
@@ -1224,8 +1242,8 @@ class SdcEngine:
         an OnPolicyBatch with the critic NOW set: critic_raw_values over batch.share_obs[:T] -> value_loss against
         batch.value_preds[:T] and batch.returns with coef = value_loss_coef / (T N) -> critic_backward.  `value_norm` as value_loss'
         (a caller that keeps a ValueNorm updates it with the returns first, as the reference does, and passes it here).
-        -> (CriticGrads, ValueLossTerms).  The optimiser step is the caller's: step it over the 6459 values (assign_to) and call
-        set_critic."""
+        -> (CriticGrads, ValueLossTerms).  The optimiser step: critic_adam_step on the device (critic_update chains the two), or a
+        caller's own over the 6459 values (assign_to) and set_critic."""
         T = batch.n_steps
         share = batch.share_obs[:T]
         raw = self.critic_raw_values(share)
@@ -1233,6 +1251,120 @@ class SdcEngine:
         terms = self.value_loss(raw, batch.value_preds[:T], batch.returns, clip_param, huber_delta, use_huber_loss, use_clipped_value_loss,
                                 value_norm=value_norm, coef=coef)
         return self.critic_backward(share, terms.dvalue), terms
+
+    # ------------------------------------------------------------------ the optimiser step: Adam with clipping, on the device
+    def _host_actors(self) -> dict:
+        """{slot: SdcActorParams} as the device holds them NOW: the slots stepped since they were set are read back (sdc_get_actor,
+        which waits for the device)"""
+        for slot in sorted(self._stale_actors):
+            p = L.SdcActorParams()
+            self._call(self.lib.sdc_get_actor, slot, C.byref(p), refuses=True)
+            self._actors[slot] = p
+        self._stale_actors.clear()
+        return self._actors
+
+    def _host_critic(self):
+        """the critic's SdcCriticParams as the device holds it NOW (None before set_critic): read back after a step (sdc_get_critic)"""
+        if self._stale_critic:
+            p = L.SdcCriticParams()
+            self._call(self.lib.sdc_get_critic, C.byref(p), refuses=True)
+            self._critic = p
+            self._stale_critic = False
+        return self._critic
+
+    def _adam_step(self, who, fn, lead, grads, n, lr, betas, eps, weight_decay, max_grad_norm):
+        adam = A.adam_struct(who, lr, betas, eps, weight_decay, max_grad_norm)
+        flat = A.flat_grads(who, grads, n, self.device)
+        norm = self.torch.empty((), dtype=self.torch.float64, device=self.device)
+        self._behind_torch_stream()
+        self._call(fn, *lead, _p(flat), C.byref(adam), _p(norm), self._stream(), refuses=True, wrote=(flat, norm))
+        return norm
+
+    def actor_adam_step(self, agent: int, grads, lr, betas=(0.9, 0.999), eps: float = 1e-5, weight_decay: float = 0.0, max_grad_norm=None):
+        """One Adam step with gradient-norm clipping over agent `agent`'s actor ON THE DEVICE (sdc_actor_adam_step: two launches,
+        stream-ordered, no synchronisation; include/sustaindc_hip.h THE OPTIMISER STEP states the arithmetic): the parameters the
+        engine keeps since set_actor move, and every packed copy the kernels read is rewritten -- launches behind this call on the
+        stream see the new actor.  `grads`: an ActorGrads or a flat fp32 tensor [6391] on this engine's device, UNCLIPPED; `eps`
+        defaults to the reference's opti_eps; `max_grad_norm` None: no clipping.  A gradient that is not finite changes nothing but
+        the state's `skipped` (optim_state).  -> the norm before clipping, fp64 0-dim on the device.  ValueError for another tensor
+        or agent, before set_actor(agent), and for what the library refuses about the hyper-parameters."""
+        a = A.agent_slot("actor_adam_step", agent)
+        norm = self._adam_step("actor_adam_step", self.lib.sdc_actor_adam_step, (a,), grads, L.ACTOR_N_PARAMS, lr, betas, eps, weight_decay,
+                               max_grad_norm)
+        self._stale_actors.add(a)
+        return norm
+
+    def critic_adam_step(self, grads, lr, betas=(0.9, 0.999), eps: float = 1e-5, weight_decay: float = 0.0, max_grad_norm=None):
+        """actor_adam_step for the critic (sdc_critic_adam_step): `grads` a CriticGrads or a flat fp32 tensor [6459]; scale and shift
+        are no parameters and stay.  -> the norm before clipping, fp64 0-dim on the device."""
+        norm = self._adam_step("critic_adam_step", self.lib.sdc_critic_adam_step, (), grads, L.CRITIC_N_PARAMS, lr, betas, eps, weight_decay,
+                               max_grad_norm)
+        self._stale_critic = True
+        return norm
+
+    def actor_update(self, batch, agent: int, clip_param: float = 0.2, entropy_coef: float = 0.01, factor=None, old_log_probs=None, *,
+                     lr, betas=(0.9, 0.999), eps: float = 1e-5, weight_decay: float = 0.0, max_grad_norm=None):
+        """One whole update of an agent's actor on the device: actor_grads (evaluate, terms, derivative, backward) and actor_adam_step
+        behind it, nothing synchronised in between.  -> (PPOTerms, the gradient's norm before clipping)."""
+        grads, terms = self.actor_grads(batch, agent, clip_param, entropy_coef, factor=factor, old_log_probs=old_log_probs)
+        return terms, self.actor_adam_step(agent, grads, lr, betas, eps, weight_decay, max_grad_norm)
+
+    def critic_update(self, batch, clip_param: float = 0.2, huber_delta: float = 10.0, use_huber_loss: bool = True,
+                      use_clipped_value_loss: bool = True, value_loss_coef: float = 1.0, value_norm=None, *, lr, betas=(0.9, 0.999),
+                      eps: float = 1e-5, weight_decay: float = 0.0, max_grad_norm=None):
+        """One whole update of the critic on the device: critic_grads and critic_adam_step behind it, nothing synchronised in between.
+        -> (ValueLossTerms, the gradient's norm before clipping)."""
+        grads, terms = self.critic_grads(batch, clip_param, huber_delta, use_huber_loss, use_clipped_value_loss, value_loss_coef, value_norm)
+        return terms, self.critic_adam_step(grads, lr, betas, eps, weight_decay, max_grad_norm)
+
+    def actor_state_dict(self, agent: int) -> dict:
+        """Agent `agent`'s actor as the device holds it now, under the reference's StochasticPolicy state_dict keys (host tensors;
+        without base.feature_norm.* when the feature LayerNorm is off).  It waits for the device.  ValueError before set_actor."""
+        a = A.agent_slot("actor_state_dict", agent)
+        if a not in self._actors:
+            raise ValueError(f"actor_state_dict: no actor is set for agent {a} (set_actor first)")
+        p = self._host_actors()[a]
+        return _struct_state_dict(p, _ACTOR_SHAPES, _ACTOR_SD_KEYS, {}, bool(p.use_feature_normalization))
+
+    def critic_state_dict(self) -> dict:
+        """The critic as the device holds it now, under the reference's VNet state_dict keys (v_out.weight [1, 64], v_out.bias [1]).
+        It waits for the device.  ValueError before set_critic."""
+        if self._critic is None:
+            raise ValueError("critic_state_dict: set_critic first")
+        p = self._host_critic()
+        return _struct_state_dict(p, _CRITIC_SHAPES, _CRITIC_SD_KEYS, {"w3": (1, 64), "b3": (1,)}, bool(p.flags & 1))
+
+    def optim_state(self, which) -> dict:
+        """The optimiser state of agent slot `which` (0 .. 2) or of "critic", for a checkpoint: {m, v: fp32 host arrays in the
+        gradient's order, step, beta1_pow, beta2_pow, skipped}.  It waits for the device.  ValueError before the network is set."""
+        slot = A.optim_which("optim_state", which)
+        n = L.CRITIC_N_PARAMS if slot is None else L.ACTOR_N_PARAMS
+        m, v, st = np.empty(n, np.float32), np.empty(n, np.float32), L.SdcOptimState()
+        ptrs = (C.c_void_p(m.ctypes.data), C.c_void_p(v.ctypes.data), C.byref(st))
+        if slot is None:
+            self._call(self.lib.sdc_get_critic_optim, *ptrs, refuses=True)
+        else:
+            self._call(self.lib.sdc_get_actor_optim, slot, *ptrs, refuses=True)
+        return dict(m=m, v=v, step=int(st.step), beta1_pow=float(st.beta1_pow), beta2_pow=float(st.beta2_pow), skipped=int(st.skipped))
+
+    def load_optim_state(self, which, state: dict):
+        """optim_state's dict back into the network `which` (its parameters are set_actor's / set_critic's to give, before this).
+        ValueError for a wrong shape and for what the library refuses (step < 0, a power outside (0, 1], a moment not finite)."""
+        slot = A.optim_which("load_optim_state", which)
+        m, v, st = A.optim_arrays("load_optim_state", state, L.CRITIC_N_PARAMS if slot is None else L.ACTOR_N_PARAMS)
+        ptrs = (C.c_void_p(m.ctypes.data), C.c_void_p(v.ctypes.data), C.byref(st))
+        if slot is None:
+            self._call(self.lib.sdc_set_critic_optim, *ptrs, refuses=True)
+        else:
+            self._call(self.lib.sdc_set_actor_optim, slot, *ptrs, refuses=True)
+
+    def set_critic_value_norm(self, value_norm):
+        """The critic's ValueNorm alone (sdc_set_critic_norm: stream-ordered, the parameters stay on the device): `value_norm` as
+        critic_params takes it -- None, a (mean, var) pair or a ValueNorm.  critic_values, collect's value_preds and value_loss'
+        default target follow from the next launch on.  ValueError before set_critic and for a scale that is not positive."""
+        scale, shift = value_norm_scale_shift(value_norm)
+        self._call(self.lib.sdc_set_critic_norm, float(scale), float(shift), self._stream(), refuses=True)
+        self._critic.scale, self._critic.shift = float(scale), float(shift)      # (no parameters: the host copy follows at once)
 
     # ------------------------------------------------------------------ state access (parity injection / checkpoint)
     def _state_array(self, name):

@@ -771,6 +771,43 @@ class SustainDCVecEnv(ShareVecEnv):
         """The gradient of the reference's critic loss for an OnPolicyBatch (SdcEngine.critic_grads) -> (CriticGrads, ValueLossTerms)"""
         return self.engine.critic_grads(batch, *args, **kw)
 
+    def actor_adam_step(self, agent, grads, lr, **kw):
+        """One Adam step with gradient-norm clipping over one agent's actor on the device (SdcEngine.actor_adam_step, which documents
+        the arguments) -> the norm before clipping"""
+        return self.engine.actor_adam_step(agent, grads, lr, **kw)
+
+    def critic_adam_step(self, grads, lr, **kw):
+        """One Adam step with gradient-norm clipping over the critic on the device (SdcEngine.critic_adam_step) -> the norm before clipping"""
+        return self.engine.critic_adam_step(grads, lr, **kw)
+
+    def actor_update(self, batch, agent, *args, **kw):
+        """One whole update of an agent's actor over an OnPolicyBatch on the device (SdcEngine.actor_update) -> (PPOTerms, grad norm)"""
+        return self.engine.actor_update(batch, agent, *args, **kw)
+
+    def critic_update(self, batch, *args, **kw):
+        """One whole update of the critic over an OnPolicyBatch on the device (SdcEngine.critic_update) -> (ValueLossTerms, grad norm)"""
+        return self.engine.critic_update(batch, *args, **kw)
+
+    def actor_state_dict(self, agent):
+        """One agent's actor as the device holds it now, under the reference's keys (SdcEngine.actor_state_dict)"""
+        return self.engine.actor_state_dict(agent)
+
+    def critic_state_dict(self):
+        """The critic as the device holds it now, under the reference's keys (SdcEngine.critic_state_dict)"""
+        return self.engine.critic_state_dict()
+
+    def optim_state(self, which):
+        """The optimiser state of an agent slot or of "critic" (SdcEngine.optim_state)"""
+        return self.engine.optim_state(which)
+
+    def load_optim_state(self, which, state):
+        """optim_state's dict back into a network's optimiser (SdcEngine.load_optim_state)"""
+        self.engine.load_optim_state(which, state)
+
+    def set_critic_value_norm(self, value_norm):
+        """The critic's ValueNorm alone, stream-ordered (SdcEngine.set_critic_value_norm)"""
+        self.engine.set_critic_value_norm(value_norm)
+
     def gae(self, rew, done, values, *args, **kw):
         """Returns, advantages and masks of a collected rollout (SdcEngine.gae, which documents the arguments and the result)"""
         return self.engine.gae(rew, done, values, *args, **kw)
@@ -842,10 +879,13 @@ class SustainDCVecEnv(ShareVecEnv):
         self.engine._set_plan_terms_struct(src.engine._plan_terms_struct())
         modes, values = src.engine._plan_forecast_state()
         self.engine._set_plan_forecast_state(modes, None if values is None else values.to(self.engine.device, copy=True))
-        for slot, p in sorted(src.engine._actors.items()):      # (before the reset below: it fills the closed loop's observation copy)
+        # (the networks as src's device holds them now -- stepped ones are read back -- and their optimisers' state with them)
+        for slot, p in sorted(src.engine._host_actors().items()):      # (before the reset below: it fills the closed loop's observation copy)
             self.engine._set_actor_struct(slot, p)
-        if src.engine._critic is not None:
+            self.engine.load_optim_state(slot, src.engine.optim_state(slot))
+        if src.engine._host_critic() is not None:
             self.engine._set_critic_struct(src.engine._critic)
+            self.engine.load_optim_state("critic", src.engine.optim_state("critic"))
             self.engine.set_plan_critic(src.engine.plan_critic)
         self.months, self._cfg_id, self._const = list(src.months), list(src._cfg_id), list(src._const)
         if not src._need_reset:

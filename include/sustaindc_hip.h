@@ -243,7 +243,8 @@ const char* sdc_last_error(void);
  *        sdc_set_plan_forecast, sdc_get_plan_forecast and sdc_forecast_traces likewise; sdc_rollout_actor_stats, sdc_rollout_cem_stats
  *        and sdc_rollout_cem_groups_stats likewise; sdc_set_critic, sdc_critic_values, sdc_set_plan_critic and sdc_get_plan_critic
  *        likewise; sdc_gae and sdc_action_log_probs likewise; sdc_actor_evaluate and sdc_ppo_terms likewise; sdc_critic_evaluate,
- *        sdc_value_loss and sdc_critic_backward likewise) */
+ *        sdc_value_loss and sdc_critic_backward likewise; sdc_actor_adam_step, sdc_critic_adam_step, sdc_get_actor, sdc_get_critic,
+ *        sdc_get_actor_optim, sdc_set_actor_optim, sdc_get_critic_optim, sdc_set_critic_optim and sdc_set_critic_norm likewise) */
 #define SDC_ABI_VERSION 313
 int sdc_version(void);
 
@@ -707,7 +708,7 @@ int sdc_ppo_terms(sdc_handle* h, int n_steps, int agent, const float* new_log_pr
 /* THE ACTORS' GRADIENT.  replaces: loss.backward() of the reference's actor update (harl/algorithms/actors/happo.py update:
  * policy_loss - entropy_coef * dist_entropy, differentiated by autograd through StochasticPolicy.evaluate_actions) -- the gradient with
  * respect to every parameter of one agent's network, on fp32-input matrix instructions, in a fixed summation order.  NOT here: the
- * optimiser step and minibatch shuffling (a caller steps an optimiser over the SDC_ACTOR_N_PARAMS values and calls sdc_set_actor);
+ * optimiser step and minibatch shuffling (sdc_actor_adam_step, THE OPTIMISER STEP below; or a caller steps an optimiser over the SDC_ACTOR_N_PARAMS values and calls sdc_set_actor);
  * the critic's value loss and its gradient are THE CRITIC'S GRADIENT below.  Both calls are pure functions of their arrays, all device memory: they read no
  * env state and move nothing in the engine; each is ordered on `stream` with no synchronisation.
  * sdc_ppo_dlogp: the loss's derivative per stored log-probability, ONE launch of sdc_ppo_dlogp_kernel.  Per element i = t N + n < T N
@@ -756,7 +757,7 @@ int sdc_actor_backward(sdc_handle* h, int agent_slot, const float* obs, long lon
  * update's loss.backward(), harl/utils/models_tools.py huber_loss / mse_loss, harl/common/valuenorm.py normalize) -- the network's own
  * output over stored share_obs rows, the clipped Huber / MSE value loss with its derivative per row, and the gradient with respect to
  * every parameter of the critic.  NOT here: the optimiser step, ValueNorm's running update, minibatch shuffling (a caller updates its
- * normaliser first, as the reference does, steps an optimiser over the SDC_CRITIC_N_PARAMS values and calls sdc_set_critic).  All three
+ * normaliser first, as the reference does, and steps with sdc_critic_adam_step, THE OPTIMISER STEP below, or its own optimiser and sdc_set_critic).  All three
  * calls are pure functions of their arrays, all device memory: they read no env state and move nothing in the engine; each is ordered
  * on `stream` with no synchronisation; no atomics: the same call gives the same bits on every run.
  * sdc_critic_evaluate: raw_values[r] = u_r, the network's own output for share_obs row r BEFORE `* scale + shift` -- what the
@@ -810,6 +811,64 @@ int sdc_value_loss(sdc_handle* h, long long n, const float* raw_values, const fl
                    double* stats, void* stream);
 int sdc_critic_backward(sdc_handle* h, const float* share_obs, long long n_rows, const float* dvalue, float* grads, double* grad_sq,
                         void* stream);
+
+/* THE OPTIMISER STEP.  replaces: the last link of an on-policy update (torch.optim.Adam.step() behind nn.utils.clip_grad_norm_ in
+ * harl/algorithms/actors/happo.py and critics/v_critic.py update) and the round trip through the host that followed it.  From the
+ * first sdc_set_actor / sdc_set_critic on the handle keeps, per actor slot and for the critic, on the device: a master copy
+ * params[SDC_*_N_PARAMS] fp32 in the order of `grads`, Adam's moments m[] and v[] fp32 of that length, and a state block
+ * (sdc_optim_state).  sdc_set_actor / sdc_set_critic do what they always did and also fill the master copy, zero the moments and
+ * reset the state block to {0, 1.0, 1.0, 0}: a new network gets a new optimiser.
+ * sdc_actor_adam_step / sdc_critic_adam_step: one Adam step with gradient-norm clipping over `grads` ([SDC_*_N_PARAMS] fp32 device
+ * memory, as sdc_*_backward wrote it, UNCLIPPED), then every packed copy the kernels read (an actor's three, the critic's two) is
+ * rewritten from the master copy.  Ordered on `stream`: no synchronisation, no device memory read by the host, no atomics, TWO
+ * launches (sdc_adam_update_kernel on one workgroup, sdc_adam_gather_kernel on twenty; csrc/sdc_optim.hip).  Launches in front of it on the same stream see
+ * the old weights, launches behind it the new ones; ORDERING AGAINST OTHER STREAMS IS THE CALLER'S (a rollout on another stream may
+ * read a packed copy while it is rewritten).  The arithmetic (csrc/sdc_optim.hpp holds it once, for the device and for a host
+ * compiler), g = grads as given:
+ *   1. S = the fp64 sum of squares of g in exactly sdc_actor_backward's grad_sq order (256 lanes, strided, tree from 128 down);
+ *      sqrt(S) is the norm of that call's grad_sq bit for bit.  grad_norm [1] fp64 device memory or NULL receives sqrt(S).
+ *   2. S not finite (a NaN or infinity somewhere in g): skipped += 1 and NOTHING else changes -- parameters, moments, step, the
+ *      powers and every packed copy keep their bits.
+ *   3. c = min(1.0, max_grad_norm / (sqrt(S) + 1e-6)) in fp64, rounded once to fp32 (torch's clip_grad_norm_ rule).
+ *   4. step += 1; beta1_pow *= beta1; beta2_pow *= beta2 in fp64; step_size = (float)(lr / (1 - beta1_pow));
+ *      rsq = (float)sqrt(1 - beta2_pow); beta2, 1 - beta1, 1 - beta2 (formed in fp64), eps and weight_decay each rounded once to fp32.
+ *   5. per element, fp32, correctly rounded division and square root, no fused multiply-add, one rounding per operation, in the form
+ *      of torch/optim/adam.py _single_tensor_adam:
+ *          g = g * c;   if (weight_decay != 0) g = g + weight_decay * p
+ *          m = m + (1 - beta1) * (g - m)                       (lerp_, the form of weights below 0.5, unfused)
+ *          v = v * beta2;   v = v + ((1 - beta2) * g) * g      (mul_ / addcmul_)
+ *          denom = sqrt(v) / rsq + eps;   p = p - step_size * (m / denom)
+ *      Where torch's kernels differ among themselves this is the CPU kernels' order of operations without their fused multiply-adds:
+ *      a division by rsq (not a multiplication by its reciprocal), value * t1 * t2 left to right in addcmul, value * (t1 / t2) in
+ *      addcdiv.
+ *   6. with the network's feature LayerNorm off its ln0 entries (the first 52 / 58 values) are not touched, not even by weight decay.
+ * Refused (-2 and a message, nothing enqueued): a null handle; agent_slot outside 0 .. 2; no actor / critic set; null or not
+ * dword-aligned grads; grad_norm not 8-byte aligned; a null sdc_adam; lr, eps or weight_decay not finite or negative; a beta outside
+ * [0, 1); max_grad_norm NaN or not above 0 (+INFINITY: no clipping).
+ * sdc_get_actor / sdc_get_critic: the master copy in a host struct, with the flags (and the critic's scale and shift) as last set;
+ * they wait for the device.  sdc_get_*_optim / sdc_set_*_optim: the moments and the state block to / from host memory (they wait for
+ * the device); set refuses a step < 0, a power outside (0, 1], skipped < 0 and a moment that is not finite or a negative v.
+ * sdc_set_critic_norm: the critic's scale and shift alone, ordered on `stream` (one small launch into SdcCriticDev) and into the
+ * handle's host record; refused: scale not finite or <= 0, shift not finite (what sdc_set_critic refuses about them), no critic set. */
+typedef struct {
+  double lr, beta1, beta2, eps, weight_decay;
+  double max_grad_norm;      /* > 0; +INFINITY means no clipping */
+} sdc_adam;
+typedef struct {
+  int64_t step;              /* steps taken (skipped ones not counted) */
+  double beta1_pow;          /* beta1 ** step and beta2 ** step as running fp64 products; both start at 1.0 */
+  double beta2_pow;
+  int64_t skipped;           /* steps refused on the device for a gradient that was not finite */
+} sdc_optim_state;
+int sdc_actor_adam_step(sdc_handle* h, int agent_slot, const float* grads, const sdc_adam* adam, double* grad_norm, void* stream);
+int sdc_critic_adam_step(sdc_handle* h, const float* grads, const sdc_adam* adam, double* grad_norm, void* stream);
+int sdc_get_actor(sdc_handle* h, int agent_slot, sdc_actor_params* out);
+int sdc_get_critic(sdc_handle* h, sdc_critic_params* out);
+int sdc_get_actor_optim(sdc_handle* h, int agent_slot, float* m, float* v, sdc_optim_state* st);
+int sdc_set_actor_optim(sdc_handle* h, int agent_slot, const float* m, const float* v, const sdc_optim_state* st);
+int sdc_get_critic_optim(sdc_handle* h, float* m, float* v, sdc_optim_state* st);
+int sdc_set_critic_optim(sdc_handle* h, const float* m, const float* v, const sdc_optim_state* st);
+int sdc_set_critic_norm(sdc_handle* h, double scale, double shift, void* stream);
 
 /* PLAN FORECAST: what the plan calls' rollouts believe the traces of the next n_steps steps are.  Without one a plan call's rollouts
  * read the episode's own feature rows -- the real workload, carbon intensity, dry bulb (with the weather noise the episode drew) and wet
