@@ -223,6 +223,66 @@ def optim_arrays(who, state, n):
     return arrays[0], arrays[1], st
 
 
+# ---------------------------------------------------------------------- train on the device: ValueNorm, mini-batches, the schedule
+def value_norm_struct(who, value_norm):
+    """set_value_norm's argument as the library's struct: None -> None (uninstall); a (mean, var) pair -> running_mean = mean,
+    running_mean_sq = var + mean^2, debiasing_term = 1; an object or dict with running_mean, running_mean_sq and debiasing_term -> those
+    three in fp32.  ValueError / KeyError in the caller's name."""
+    if value_norm is None:
+        return None
+    f = np.float32
+    num = lambda v: f(np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32).reshape(-1)[0])
+    if isinstance(value_norm, (tuple, list)):
+        if len(value_norm) != 2:
+            raise ValueError(f"{who}: value_norm must be None, a (mean, var) pair, or hold running_mean, running_mean_sq and debiasing_term")
+        mean, var = num(value_norm[0]), num(value_norm[1])
+        return L.SdcValueNorm(float(mean), float(f(var + f(mean * mean))), 1.0)
+    get = (lambda k: value_norm[k]) if isinstance(value_norm, dict) else (lambda k: getattr(value_norm, k))
+    try:
+        return L.SdcValueNorm(*(float(num(get(k))) for k in ("running_mean", "running_mean_sq", "debiasing_term")))
+    except (KeyError, AttributeError):
+        raise KeyError(f"{who}: value_norm holds no running_mean / running_mean_sq / debiasing_term") from None
+
+
+# OnPolicyBatch's per-step fields as dword rows: name -> (dwords per row, dwords per agent column or 0, who reads it: "actor", "critic"
+# or "book" -- the bookkeeping no update reads).  dones is uint8: no dword array, gathered by torch (SdcEngine.minibatch).
+MINIBATCH_FIELDS = {
+    "obs": (L.N_AGENTS * L.OBS_PAD, L.OBS_PAD, "actor"), "actions": (3, 1, "actor"), "logits": (9, 3, "actor"),
+    "action_log_probs": (3, 1, "actor"), "entropy": (3, 1, "actor"), "advantages": (1, 0, "actor"),
+    "share_obs": (L.SHARE_OBS_DIM, 0, "critic"), "values": (1, 0, "critic"), "value_preds": (1, 0, "critic"), "returns": (1, 0, "critic"),
+    "rewards": (3, 0, "book"), "masks": (1, 0, "book"),
+}
+
+
+def minibatch_segments(agent=None, actors=True, critic=True):
+    """the dword segments of one minibatch gather: [(field, offset in a row, dwords copied, dwords per row)] -- with `agent` only that
+    column of the per-agent fields; without `actors` / `critic` not their fields; the bookkeeping fields only with both"""
+    out = []
+    for name, (row, col, group) in MINIBATCH_FIELDS.items():
+        if (group == "actor" and not actors) or (group == "critic" and not critic) or (group == "book" and not (actors and critic)):
+            continue
+        if col and agent is not None:
+            out.append((name, col * agent, col, row))
+        else:
+            out.append((name, 0, row, row))
+    return out
+
+
+def minibatch_rows(who, T, N, num_mini_batch):
+    """rows per mini-batch when T steps of N envs are cut into `num_mini_batch` pieces: (T / num_mini_batch) N; ValueError when it does
+    not divide T (the reference drops the remainder's rows; we refuse)"""
+    if isinstance(num_mini_batch, bool) or not isinstance(num_mini_batch, (int, np.integer)) or num_mini_batch < 1:
+        raise ValueError(f"{who}: num_mini_batch = {num_mini_batch!r} must be a positive integer")
+    if T % int(num_mini_batch):
+        raise ValueError(f"{who}: num_mini_batch = {num_mini_batch} does not divide the batch's {T} steps")
+    return T // int(num_mini_batch) * N
+
+
+def perm_stream_id(who: int, epoch: int) -> int:
+    """happo_train's stream_id of one epoch's permutation: (who << 32) | epoch, who = the agent slot, 3 for the critic"""
+    return (int(who) << 32) | int(epoch)
+
+
 # ---------------------------------------------------------------------- the horizon of lookahead and plan
 def check_horizon(who, K, left=None, auto_reset=False):
     """ValueError for a horizon a mark cannot hold and -- `left` = steps_to_episode_end() given -- one that would finish an episode"""

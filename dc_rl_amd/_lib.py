@@ -25,7 +25,7 @@ LIB_PATH = os.path.join(CSRC, "libsustaindc_hip.so")
 SOURCES = ["sdc_capi.hip", "sdc_step.hip", "sdc_rollout.hip", "sdc_wide.hip", "sdc_features.hip", "sdc_verify.hip", "sdc_reset.hip", "sdc_clone.hip",
            "sdc_snapshot.hip", "sdc_mark.hip", "sdc_plan.hip", "sdc_cem.hip", "sdc_cem_groups.hip", "sdc_stats.hip", "sdc_plan_terms.hip",
            "sdc_forecast.hip", "sdc_policy_stats.hip", "sdc_mpc.hip", "sdc_mpc_groups.hip", "sdc_critic.hip", "sdc_onpolicy.hip", "sdc_actor_eval.hip",
-           "sdc_actor_grad.hip", "sdc_critic_grad.hip", "sdc_optim.hip"]
+           "sdc_actor_grad.hip", "sdc_critic_grad.hip", "sdc_optim.hip", "sdc_minibatch.hip"]
 MARK_MANIFEST = 7       # include/sustaindc_hip.h SDC_MARK_MANIFEST: int32 entries per mark row's manifest (enum sdc_mark_manifest)
 MARK_MAX_STEPS = 256    # include/sustaindc_hip.h SDC_MARK_MAX_STEPS
 PLAN_MAX_COLS = 8       # include/sustaindc_hip.h SDC_PLAN_MAX_COLS: info columns an sdc_plan objective may weigh
@@ -69,6 +69,8 @@ ACTOR_N_PARAMS = 6391           # include/sustaindc_hip.h SDC_ACTOR_N_PARAMS: th
 ACTOR_GRAD_MAX_BLOCKS = 256     # include/sustaindc_hip.h SDC_ACTOR_GRAD_MAX_BLOCKS: workgroups (partial gradients) of sdc_actor_backward at most
 CRITIC_N_PARAMS = 6459          # include/sustaindc_hip.h SDC_CRITIC_N_PARAMS: sdc_critic_params' float members ln0_g .. b3, sdc_critic_backward's grads
 CRITIC_GRAD_MAX_BLOCKS = 256    # include/sustaindc_hip.h SDC_CRITIC_GRAD_MAX_BLOCKS: workgroups (partial gradients) of sdc_critic_backward at most
+GATHER_MAX_SEGMENTS = 16        # include/sustaindc_hip.h SDC_GATHER_MAX_SEGMENTS: segments of one sdc_gather_rows call
+PERM_MAX_N = 2 ** 31 - 1        # sdc_permutation's largest n (the outputs are int32)
 VALUE_LOSS_HUBER, VALUE_LOSS_CLIPPED = 1, 2     # include/sustaindc_hip.h: sdc_value_loss' flags (bit 0: Huber loss, bit 1: clipped value loss)
 SNAPSHOT_MANIFEST = 9   # include/sustaindc_hip.h SDC_SNAPSHOT_MANIFEST: int32 entries per snapshot row's manifest (enum sdc_snapshot_manifest)
 # (-amdgpu-sched-strategy=max-ilp: the machine scheduler orders for instruction-level parallelism instead of minimal register
@@ -196,6 +198,16 @@ class SdcOptimState(C.Structure):
     _fields_ = [("step", C.c_int64), ("beta1_pow", C.c_double), ("beta2_pow", C.c_double), ("skipped", C.c_int64)]
 
 
+class SdcValueNorm(C.Structure):
+    """A ValueNorm's three running values (include/sustaindc_hip.h sdc_value_norm)."""
+    _fields_ = [("running_mean", C.c_float), ("running_mean_sq", C.c_float), ("debiasing_term", C.c_float)]
+
+
+class SdcGatherSegment(C.Structure):
+    """One array of an sdc_gather_rows call (include/sustaindc_hip.h sdc_gather_segment; strides and n_dwords in dwords)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride", C.c_longlong), ("dst_stride", C.c_longlong), ("n_dwords", C.c_int)]
+
+
 class SdcPlanObjective(C.Structure):
     """What sdc_plan scores a candidate by (include/sustaindc_hip.h sdc_plan_objective)."""
     _fields_ = [
@@ -267,6 +279,7 @@ EXPORTS = [
     "sdc_critic_evaluate", "sdc_value_loss", "sdc_critic_backward",
     "sdc_actor_adam_step", "sdc_critic_adam_step", "sdc_get_actor", "sdc_get_critic", "sdc_get_actor_optim", "sdc_set_actor_optim",
     "sdc_get_critic_optim", "sdc_set_critic_optim", "sdc_set_critic_norm",
+    "sdc_permutation", "sdc_gather_rows", "sdc_set_value_norm", "sdc_get_value_norm", "sdc_value_norm_update", "sdc_value_loss_normed",
 ]
 
 
@@ -460,6 +473,12 @@ def load():
     L.sdc_get_critic_optim.argtypes = [vp, fp, fp, C.POINTER(SdcOptimState)]
     L.sdc_set_critic_optim.argtypes = [vp, fp, fp, C.POINTER(SdcOptimState)]
     L.sdc_set_critic_norm.argtypes = [vp, C.c_double, C.c_double, vp]
+    L.sdc_permutation.argtypes = [vp, C.c_longlong, C.c_uint64, C.c_uint64, vp, vp]
+    L.sdc_gather_rows.argtypes = [vp, vp, C.c_longlong, C.c_longlong, C.POINTER(SdcGatherSegment), C.c_int, vp, vp]
+    L.sdc_set_value_norm.argtypes = [vp, C.POINTER(SdcValueNorm)]
+    L.sdc_get_value_norm.argtypes = [vp, C.POINTER(SdcValueNorm)]
+    L.sdc_value_norm_update.argtypes = [vp, fp, C.c_longlong, C.c_double, vp]
+    L.sdc_value_loss_normed.argtypes = [vp, C.c_longlong, fp, fp, fp, C.c_double, C.c_double, C.c_int, C.c_double, fp, fp, vp, vp]
     for name in EXPORTS:
         getattr(L, name)
     built = L.sdc_version()

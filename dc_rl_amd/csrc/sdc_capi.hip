@@ -44,6 +44,7 @@
 #include "sdc_actor_grad.hpp"
 #include "sdc_critic_grad.hpp"
 #include "sdc_optim_dev.hpp"
+#include "sdc_minibatch_dev.hpp"
 #include "sdc_pack_tables.hpp"
 #include "sdc_mpc.hpp"
 #include "sdc_mpc_groups.hpp"
@@ -207,6 +208,13 @@ struct sdc_handle {
   int critic_table_offset[3] = {0, 0, 0};
   float critic_scale = 1.0f, critic_shift = 0.0f;
   int critic_flags = 0;
+  // train on the device (sdc_minibatch.hip): the ValueNorm block, allocated with the critic; "installed": sdc_set_value_norm has filled
+  // it and neither sdc_set_critic nor sdc_set_critic_norm has been called since -- while it is, the device's scale and shift are the
+  // block's, not critic_scale / critic_shift; stage 1's partial sums [SDC_VN_MAX_BLOCKS][2] of sdc_value_norm_update and
+  // sdc_value_loss_normed's partial statistics are allocated on first use
+  SdcValueNormDev* value_norm = nullptr;
+  bool value_norm_installed = false;
+  double* value_norm_part = nullptr;
 };
 
 namespace {
@@ -1822,6 +1830,7 @@ int sdc_set_critic(sdc_handle* h, const sdc_critic_params* p) {
     if (dev_alloc(h, &h->critic_v, (size_t)SDC_CRITIC_N_PARAMS) != 0) return -1;
     if (dev_alloc(h, &h->critic_optim, 1) != 0) return -1;
     if (upload_table(h, sdc_critic_pack_tables(), &h->critic_table, h->critic_table_offset) != 0) return -1;
+    if (dev_alloc(h, &h->value_norm, 1) != 0) return -1;
   }
   std::unique_ptr<SdcCriticDev> packed(new SdcCriticDev);      // (26 KB: on the heap, per call -- see sdc_set_actor)
   sdc_critic_pack(p, packed.get());
@@ -1838,6 +1847,7 @@ int sdc_set_critic(sdc_handle* h, const sdc_critic_params* p) {
   h->critic_scale = p->scale;
   h->critic_shift = p->shift;
   h->critic_flags = p->flags;
+  h->value_norm_installed = false;      // (scale and shift set by hand: no running state)
   return 0;
 }
 
@@ -2122,6 +2132,12 @@ int sdc_get_critic(sdc_handle* h, sdc_critic_params* out) {
   out->scale = h->critic_scale;
   out->shift = h->critic_shift;
   out->flags = h->critic_flags;
+  if (h->value_norm_installed) {      // (the device's: sdc_value_norm_update moves them without the host)
+    SdcValueNormDev vn;
+    HIP_TRY(hipMemcpy(&vn, h->value_norm, sizeof(vn), hipMemcpyDeviceToHost));
+    out->scale = vn.scale;
+    out->shift = vn.shift;
+  }
   return 0;
 }
 
@@ -2169,8 +2185,115 @@ int sdc_set_critic_norm(sdc_handle* h, double scale, double shift, void* stream)
   HIP_TRY(hipSetDevice(h->device));
   h->critic_scale = (float)scale;
   h->critic_shift = (float)shift;
+  h->value_norm_installed = false;      // (scale and shift set by hand: no running state)
   return launched("sdc_critic_norm_kernel",
                   sdc_critic_norm_launch(SdcCriticNorm{h->critic_dev, h->critic_scale, h->critic_shift}, reinterpret_cast<hipStream_t>(stream)));
+}
+
+// ---- train on the device (sdc_minibatch.hip) ---------------------------------------------------------------------------------------------
+// The contract: include/sustaindc_hip.h TRAIN ON THE DEVICE; the arithmetic: sdc_minibatch.hpp; the kernels' plans: sdc_minibatch_dev.hpp.
+int sdc_permutation(sdc_handle* h, long long n, uint64_t seed, uint64_t stream_id, int32_t* perm, void* stream) {
+  if (refused(sdc_permutation_refused(call_facts(h), n, perm))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  return launched("sdc_permutation_kernel",
+                  sdc_permutation_launch(SdcPermutation{sdc_perm_key(n, seed, stream_id), perm}, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int sdc_gather_rows(sdc_handle* h, const int32_t* idx, long long n_rows, long long n_src_rows, const sdc_gather_segment* segs, int n_segs,
+                    int32_t* bad, void* stream) {
+  if (refused(sdc_gather_rows_refused(call_facts(h), idx, n_rows, n_src_rows, segs, n_segs, bad))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  SdcGatherRows P;
+  std::memset(&P, 0, sizeof(P));
+  P.idx = idx;
+  P.n_rows = n_rows;
+  P.n_src_rows = (unsigned)n_src_rows;
+  P.n_segs = n_segs;
+  P.bad = bad;
+  long long first = 0;
+  for (int g = 0; g < n_segs; g++) {
+    P.seg[g] = SdcGatherSeg{static_cast<const uint32_t*>(segs[g].src), static_cast<uint32_t*>(segs[g].dst), segs[g].src_stride,
+                            segs[g].dst_stride, (int)first, segs[g].n_dwords};
+    first += segs[g].n_dwords;
+  }
+  if (first > 0x7fffffffll) return fail_msg("sdc_gather_rows: the segments' n_dwords add up to more than 2147483647");
+  P.row_dwords = (int)first;
+  return launched("sdc_gather_rows_kernel", sdc_gather_rows_launch(P, reinterpret_cast<hipStream_t>(stream)));
+}
+
+int sdc_set_value_norm(sdc_handle* h, const sdc_value_norm* st) {
+  if (refused(sdc_set_value_norm_refused(call_facts(h), st))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  SdcValueNormDev vn{};
+  if (!st) {      // uninstall: the critic keeps the scale and shift it has, and the host record follows them
+    if (h->value_norm_installed) {
+      HIP_TRY(hipMemcpy(&vn, h->value_norm, sizeof(vn), hipMemcpyDeviceToHost));
+      h->critic_scale = vn.scale;
+      h->critic_shift = vn.shift;
+    }
+    h->value_norm_installed = false;
+    return 0;
+  }
+  vn.running_mean = st->running_mean;
+  vn.running_mean_sq = st->running_mean_sq;
+  vn.debiasing_term = st->debiasing_term;
+  sdc_value_norm_derive(vn);
+  HIP_TRY(hipMemcpy(h->value_norm, &vn, sizeof(vn), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(&h->critic_dev->scale, &vn.scale, sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(&h->critic_dev->shift, &vn.shift, sizeof(float), hipMemcpyHostToDevice));
+  h->critic_scale = vn.scale;
+  h->critic_shift = vn.shift;
+  h->value_norm_installed = true;
+  return 0;
+}
+
+int sdc_get_value_norm(sdc_handle* h, sdc_value_norm* out) {
+  if (refused(sdc_get_value_norm_refused(call_facts(h), h && h->value_norm_installed, out))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipDeviceSynchronize());
+  SdcValueNormDev vn;
+  HIP_TRY(hipMemcpy(&vn, h->value_norm, sizeof(vn), hipMemcpyDeviceToHost));
+  *out = sdc_value_norm{vn.running_mean, vn.running_mean_sq, vn.debiasing_term};
+  return 0;
+}
+
+int sdc_value_norm_update(sdc_handle* h, const float* returns, long long n, double beta, void* stream) {
+  if (refused(sdc_value_norm_update_refused(call_facts(h), h && h->value_norm_installed, returns, n, beta))) return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  if (!h->value_norm_part && dev_alloc(h, &h->value_norm_part, (size_t)SDC_VN_MAX_BLOCKS * 2, false) != 0) return -1;
+  const int B = sdc_value_norm_blocks(n);
+  return launched("sdc_value_norm_sums_kernel / sdc_value_norm_update_kernel",
+                  sdc_value_norm_update_launch(SdcValueNormSums{returns, n, h->value_norm_part},
+                                               SdcValueNormUpdate{B, n, beta, h->value_norm_part, h->value_norm, h->critic_dev},
+                                               reinterpret_cast<hipStream_t>(stream)));
+}
+
+int sdc_value_loss_normed(sdc_handle* h, long long n, const float* raw_values, const float* value_preds, const float* returns,
+                          double clip_param, double huber_delta, int flags, double coef, float* loss, float* dvalue, double* stats,
+                          void* stream) {
+  if (refused(sdc_value_loss_normed_refused(call_facts(h), h && h->value_norm_installed, n, raw_values, value_preds, returns, clip_param,
+                                            huber_delta, flags, coef, loss, dvalue, stats)))
+    return -2;
+  HIP_TRY(hipSetDevice(h->device));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (stats && !h->value_loss_part && dev_alloc(h, &h->value_loss_part, (size_t)SDC_PPO_MAX_BLOCKS * SDC_PPO_STATS, false) != 0) return -1;
+  SdcValueLoss P;
+  std::memset(&P, 0, sizeof(P));
+  P.n = n;
+  P.raw = raw_values;
+  P.vp = value_preds;
+  P.ret = returns;
+  P.clip = clip_param;
+  P.delta = (flags & SDC_VALUE_LOSS_HUBER) ? huber_delta : 0.0;
+  P.coef = coef;
+  P.flags = flags;
+  P.loss = loss;
+  P.dvalue = dvalue;
+  P.part = stats ? h->value_loss_part : nullptr;
+  if (const int rc = launched("sdc_value_loss_normed_kernel", sdc_value_loss_normed_launch(P, h->value_norm, st))) return rc;
+  if (!stats) return 0;
+  return launched("sdc_ppo_stats_kernel", sdc_ppo_stats_launch(SdcPpoStats{sdc_ppo_blocks(n), (double)n, h->value_loss_part, stats}, st));
 }
 
 // ---- plan with the cross-entropy method (sdc_cem.hip, sdc_cem_groups.hip) -----------------------------------------------------------

@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "../../include/sustaindc_hip.h"
+#include "sdc_philox.hpp"
 #include "sdc_setup.hpp"   // SdcDcDev, SdcRackClasses, SdcWideCfg and the sizes the host derives: defined HIP-free, next to their derivation
 
 #define SDC_NORM_WINDOW 2880    // 30 days x 96 (utils/managers.py:435, :606)
@@ -516,35 +517,8 @@ __device__ __forceinline__ void stage_windows(const SdcDev& S, int loc, int ip, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// counter-based RNG for device-side resets: Philox4x32-R (Salmon et al., SC'11; Random123's known-answer vectors for
-// R = 7 and R = 10 pin the NumPy restatement, tests/test_reset_ref.py, and the restatement pins this code,
-// tests/test_gpu_reset_pin.py).  R = 10 for the per-episode draws and the actor's sampler; R = 7 -- the paper's
-// Crush-resistant minimum with a safety margin -- for the 35 040 normals of a reset's weather walk, whose cost is the
-// 2 R quarter-rate 32 x 32 -> 64-bit products per block.
+// counter-based RNG for device-side resets: Philox4x32-R, in a header of its own that a host compiler builds as well (sdc_philox.hpp)
 
-struct Philox4 {
-  unsigned x, y, z, w;
-};
-template <int R>
-__device__ __forceinline__ Philox4 philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-  for (int r = 0; r < R; r++) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-    const unsigned n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-    const unsigned n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return Philox4{c0, c1, c2, c3};
-}
-__device__ __forceinline__ Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                                 unsigned k1) {
-  return philox4x32<10>(c0, c1, c2, c3, k0, k1);
-}
 // uniform in (0, 1) from 2 x 32 bits (53-bit mantissa)
 __device__ __forceinline__ double u01(unsigned hi, unsigned lo) {
   const unsigned long long b = (((unsigned long long)hi << 32) | lo) >> 11;

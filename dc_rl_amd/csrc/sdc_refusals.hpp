@@ -28,6 +28,7 @@
 #include "sdc_mirror.hpp"
 #include "sdc_mpc_schedule.hpp"
 #include "sdc_optim.hpp"
+#include "sdc_minibatch.hpp"
 
 using SdcMsg = std::optional<std::string>;
 
@@ -740,6 +741,72 @@ static inline SdcMsg sdc_set_critic_norm_refused(const SdcCallFacts& f, const do
   if (SdcMsg m = sdc_optim_network_refused(w, f, false, -1)) return m;
   if (!std::isfinite((float)scale) || !std::isfinite((float)shift)) return w + "an entry that is not finite";
   if (!((float)scale > 0.0f)) return w + "scale must be positive";
+  return std::nullopt;
+}
+
+// ---- train on the device: permutation, gather, ValueNorm ------------------------------------------------------------------------------------
+// (what is refused about an sdc_value_norm and a gather segment: sdc_minibatch.hpp; the texts are held by tests/test_train_abi.py.
+// `installed`: the handle holds a ValueNorm)
+static inline SdcMsg sdc_permutation_refused(const SdcCallFacts& f, const long long n, const int32_t* perm) {
+  static const std::string w = "sdc_permutation: ";
+  if (!f.handle) return w + "null handle";
+  if (n < 1 || n > SDC_PERM_MAX_N) return w + "n = " + std::to_string(n) + " outside [1, 2147483647]";
+  if (!perm) return w + "null perm";
+  if ((sdc_addr_bits(perm) & 3u) != 0) return w + "perm not dword-aligned";
+  return std::nullopt;
+}
+static inline SdcMsg sdc_gather_rows_refused(const SdcCallFacts& f, const int32_t* idx, const long long n_rows, const long long n_src_rows,
+                                             const sdc_gather_segment* segs, const int n_segs, const int32_t* bad) {
+  static const std::string w = "sdc_gather_rows: ";
+  if (!f.handle) return w + "null handle";
+  if (n_rows < 1) return w + "n_rows = " + std::to_string(n_rows) + " must be positive";
+  if (n_src_rows < 1 || n_src_rows > SDC_PERM_MAX_N) return w + "n_src_rows = " + std::to_string(n_src_rows) + " outside [1, 2147483647]";
+  if (!idx || !segs) return w + "null idx or segs";
+  if ((sdc_addr_bits(idx, bad) & 3u) != 0) return w + "idx / bad not dword-aligned";
+  if (n_segs < 1 || n_segs > SDC_GATHER_MAX_SEGMENTS)
+    return w + "n_segs = " + std::to_string(n_segs) + " outside [1, " + std::to_string(SDC_GATHER_MAX_SEGMENTS) + "]";
+  static const char* const why[4] = {"a null src or dst", "src / dst not dword-aligned", "n_dwords must be positive",
+                                     "a stride below n_dwords"};
+  for (int g = 0; g < n_segs; g++) {
+    const int e = sdc_gather_segment_error(segs[g]);
+    if (e >= 0) return w + "segment " + std::to_string(g) + ": " + why[e];
+  }
+  return std::nullopt;
+}
+static inline SdcMsg sdc_set_value_norm_refused(const SdcCallFacts& f, const sdc_value_norm* st) {
+  static const std::string w = "sdc_set_value_norm: ";
+  if (SdcMsg m = sdc_optim_network_refused(w, f, false, -1)) return m;
+  if (st)
+    if (const char* e = sdc_value_norm_error(st)) return w + e;
+  return std::nullopt;
+}
+static inline SdcMsg sdc_get_value_norm_refused(const SdcCallFacts& f, const bool installed, const sdc_value_norm* out) {
+  static const std::string w = "sdc_get_value_norm: ";
+  if (SdcMsg m = sdc_optim_network_refused(w, f, false, -1)) return m;
+  if (!installed) return w + "no ValueNorm is installed (sdc_set_value_norm first)";
+  if (!out) return w + "null output";
+  return std::nullopt;
+}
+static inline SdcMsg sdc_value_norm_update_refused(const SdcCallFacts& f, const bool installed, const float* returns, const long long n,
+                                                   const double beta) {
+  static const std::string w = "sdc_value_norm_update: ";
+  if (SdcMsg m = sdc_optim_network_refused(w, f, false, -1)) return m;
+  if (!installed) return w + "no ValueNorm is installed (sdc_set_value_norm first)";
+  if (n < 1) return w + "n = " + std::to_string(n) + " must be positive";
+  if (!returns) return w + "null returns";
+  if ((sdc_addr_bits(returns) & 3u) != 0) return w + "returns not dword-aligned";
+  if (!(beta >= 0.0 && beta < 1.0)) return w + "beta = " + std::to_string(beta) + " outside [0, 1)";
+  return std::nullopt;
+}
+// (sdc_value_loss' rule under this call's name, with the block's scale and shift standing in as 1 and 0)
+static inline SdcMsg sdc_value_loss_normed_refused(const SdcCallFacts& f, const bool installed, const long long n, const float* raw_values,
+                                                   const float* value_preds, const float* returns, const double clip_param,
+                                                   const double huber_delta, const int flags, const double coef, const float* loss,
+                                                   const float* dvalue, const double* stats) {
+  static const std::string w = "sdc_value_loss_normed: ";
+  if (SdcMsg m = sdc_value_loss_refused(f, n, raw_values, value_preds, returns, 1.0, 0.0, clip_param, huber_delta, flags, coef, loss, dvalue, stats))
+    return w + m->substr(std::strlen("sdc_value_loss: "));
+  if (!installed) return w + "no ValueNorm is installed (sdc_set_value_norm first)";
   return std::nullopt;
 }
 

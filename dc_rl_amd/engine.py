@@ -432,6 +432,55 @@ class ValueLossTerms:
                     error_rms=float(np.sqrt(float(s[3]) / n)), clipped_frac=float(s[4]) / n, error_min=float(s[5]), error_max=float(s[6]))
 
 
+class MiniBatch(OnPolicyBatch):
+    """What SdcEngine.minibatch hands back: an OnPolicyBatch of T' = len(indices) / N steps whose per-step fields are the parent's rows
+    `indices`, every field [T', N, ...] (there is no row T').  A field the call was told not to gather is None; with `agent` given the
+    other agents' columns of the per-agent fields hold anything.  adv_mean, adv_std and last_done are the parent's.  `factor`: the
+    gathered HAPPO factor [T', N] or None; `bad`: int32 [1], 1 when an index lay outside the parent's rows (that row is zeros)."""
+    __slots__ = ("factor", "bad", "_steps")
+
+    def __init__(self, steps, factor=None, bad=None, **fields):
+        super().__init__(**fields)
+        self.factor, self.bad, self._steps = factor, bad, int(steps)
+
+    @property
+    def n_steps(self) -> int:
+        return self._steps
+
+
+class TrainInfo:
+    """What SdcEngine.happo_train hands back, everything on the device: `actor[a]`, the (PPOTerms.stats fp64 [8], gradient norm fp64
+    0-dim) of every update of agent a in the order they ran; `critic`, the (ValueLossTerms.stats, gradient norm) of every critic
+    update; `factor` fp32 [T, N], the HAPPO factor behind the last agent (None without use_factor)."""
+    __slots__ = ("actor", "critic", "factor")
+
+    def __init__(self):
+        self.actor, self.critic, self.factor = {}, [], None
+
+    def summary(self) -> dict:
+        """The reference's train_info, the means over a network's updates, from ONE device -> host copy: {"actor": {agent:
+        {policy_loss, dist_entropy, actor_grad_norm, ratio}}, "critic": {value_loss, critic_grad_norm}}"""
+        import torch
+        groups = [(a, self.actor[a]) for a in sorted(self.actor)] + [("critic", self.critic)]
+        rows = [torch.cat((stats, norm.reshape(1))) for _, ups in groups for stats, norm in ups]
+        if not rows:
+            return {"actor": {}, "critic": {}}
+        host = torch.stack(rows).cpu().numpy()
+        out, at = {"actor": {}, "critic": {}}, 0
+        for who, ups in groups:
+            s = host[at:at + len(ups)]
+            at += len(ups)
+            if not len(ups):
+                continue
+            n = s[:, 7]
+            if who == "critic":
+                out["critic"] = dict(value_loss=float(np.mean(s[:, 0] / n)), critic_grad_norm=float(np.mean(s[:, 8])))
+            else:
+                out["actor"][who] = dict(policy_loss=float(np.mean(-s[:, 0] / n)), dist_entropy=float(np.mean(s[:, 3] / n)),
+                                         actor_grad_norm=float(np.mean(s[:, 8])), ratio=float(np.mean(s[:, 1] / n)))
+        return out
+
+
 class MPCCarry:
     """What `rollout_cem_stats` leaves of the planner's state, on the engine's device: `probs` float64 [H, N, 3, 3] and `best_seq` int32
     [H, N, 3], the arrays of the call (a caller's own are the same tensors), whose first `steps` steps hold the last planned decision's
@@ -676,6 +725,7 @@ class SdcEngine:
         self._critic = None               # set_critic's struct (_stale_critic likewise): _host_actors() / _host_critic() refresh them
         self._stale_actors = set()
         self._stale_critic = False
+        self._value_norm_installed = False      # set_value_norm: the critic's scale and shift follow a ValueNorm kept on the device
         with torch.cuda.device(self.device):
             torch.cuda.init()
             L.check(self.lib.sdc_create(C.byref(cfg), C.byref(self._h)))
@@ -922,6 +972,7 @@ class SdcEngine:
         self._call(self.lib.sdc_set_critic, C.byref(p), refuses=True)
         self._critic = p      # (the host copy: what a copy of this engine is given, SustainDCVecEnv._take_state)
         self._stale_critic = False
+        self._value_norm_installed = False      # (the library uninstalls: scale and shift were set by hand)
 
     def critic_values(self, share_obs):
         """The critic's value of every row of `share_obs`, a contiguous fp32 tensor [..., 29] on this engine's device -> fp32 [...]
@@ -1198,7 +1249,8 @@ class SdcEngine:
         elementwise in fp64, each result rounded once; fixed-order fp64 statistics; stream-ordered): `raw_values` (critic_raw_values'),
         `value_preds` (the stored normalised predictions, OnPolicyBatch.value_preds[:T]) and `returns`, contiguous fp32 tensors of one
         shape on this engine's device.  The target is (returns - shift) / scale: `value_norm` None -- the scale and shift of the critic
-        in force (1 and 0 before set_critic) --, a (mean, var) pair, or a ValueNorm, as `critic_params` takes it.  `coef`: dvalue =
+        in force (1 and 0 before set_critic; with a ValueNorm installed by set_value_norm the kernel reads them on the device,
+        sdc_value_loss_normed, and the host never does) --, a (mean, var) pair, or a ValueNorm, as `critic_params` takes it.  `coef`: dvalue =
         coef * d loss / d raw; None: 1 / n, the reference's mean at value_loss_coef 1.  -> ValueLossTerms.  ValueError for another
         tensor and for what the library refuses (clip_param < 0, huber_delta <= 0 under use_huber_loss, a coef that is not finite)."""
         t, who = self.torch, "value_loss"
@@ -1206,19 +1258,23 @@ class SdcEngine:
         A.device_tensor(value_preds, who, "value_preds", t.float32, shape, None, self.device)
         A.device_tensor(returns, who, "returns", t.float32, shape, None, self.device)
         n = raw_values.numel()
-        if value_norm is None:
-            scale, shift = (1.0, 0.0) if self._critic is None else (float(self._critic.scale), float(self._critic.shift))
-        else:
-            scale, shift = value_norm_scale_shift(value_norm)
         coef = 1.0 / max(n, 1) if coef is None else A.finite_float(who, "coef", coef)
         flags = (L.VALUE_LOSS_HUBER if use_huber_loss else 0) | (L.VALUE_LOSS_CLIPPED if use_clipped_value_loss else 0)
         new = lambda: t.empty(shape, dtype=t.float32, device=self.device)
         res = ValueLossTerms(new() if want_loss else None, new(), t.empty(L.PPO_STATS, dtype=t.float64, device=self.device))
+        tail = (A.finite_float(who, "clip_param", clip_param), A.finite_float(who, "huber_delta", huber_delta), flags, coef, _p(res.loss),
+                _p(res.dvalue), _p(res.stats), self._stream())
+        wrote = (raw_values, value_preds, returns, res.loss, res.dvalue, res.stats)
         self._behind_torch_stream()
-        self._call(self.lib.sdc_value_loss, n, _p(raw_values), _p(value_preds), _p(returns), scale, shift,
-                   A.finite_float(who, "clip_param", clip_param), A.finite_float(who, "huber_delta", huber_delta), flags, coef, _p(res.loss),
-                   _p(res.dvalue), _p(res.stats), self._stream(), refuses=True,
-                   wrote=(raw_values, value_preds, returns, res.loss, res.dvalue, res.stats))
+        if value_norm is None and self._value_norm_installed:
+            # (the installed ValueNorm's scale and shift are the device's: the kernel reads them, the host never does)
+            self._call(self.lib.sdc_value_loss_normed, n, _p(raw_values), _p(value_preds), _p(returns), *tail, refuses=True, wrote=wrote)
+            return res
+        if value_norm is None:
+            scale, shift = (1.0, 0.0) if self._critic is None else (float(self._critic.scale), float(self._critic.shift))
+        else:
+            scale, shift = value_norm_scale_shift(value_norm)
+        self._call(self.lib.sdc_value_loss, n, _p(raw_values), _p(value_preds), _p(returns), scale, shift, *tail, refuses=True, wrote=wrote)
         return res
 
     def critic_backward(self, share_obs, dvalue) -> CriticGrads:
@@ -1336,7 +1392,9 @@ class SdcEngine:
 
     def optim_state(self, which) -> dict:
         """The optimiser state of agent slot `which` (0 .. 2) or of "critic", for a checkpoint: {m, v: fp32 host arrays in the
-        gradient's order, step, beta1_pow, beta2_pow, skipped}.  It waits for the device.  ValueError before the network is set."""
+        gradient's order, step, beta1_pow, beta2_pow, skipped} -- and for "critic" with a ValueNorm installed (set_value_norm) also
+        value_norm: its three running values, training state as the moments are.  It waits for the device.  ValueError before the
+        network is set."""
         slot = A.optim_which("optim_state", which)
         n = L.CRITIC_N_PARAMS if slot is None else L.ACTOR_N_PARAMS
         m, v, st = np.empty(n, np.float32), np.empty(n, np.float32), L.SdcOptimState()
@@ -1345,16 +1403,23 @@ class SdcEngine:
             self._call(self.lib.sdc_get_critic_optim, *ptrs, refuses=True)
         else:
             self._call(self.lib.sdc_get_actor_optim, slot, *ptrs, refuses=True)
-        return dict(m=m, v=v, step=int(st.step), beta1_pow=float(st.beta1_pow), beta2_pow=float(st.beta2_pow), skipped=int(st.skipped))
+        out = dict(m=m, v=v, step=int(st.step), beta1_pow=float(st.beta1_pow), beta2_pow=float(st.beta2_pow), skipped=int(st.skipped))
+        if slot is None and self._value_norm_installed:      # (the critic's running ValueNorm is training state as the moments are)
+            vn = self.value_norm_state()
+            out["value_norm"] = {k: vn[k] for k in ("running_mean", "running_mean_sq", "debiasing_term")}
+        return out
 
     def load_optim_state(self, which, state: dict):
-        """optim_state's dict back into the network `which` (its parameters are set_actor's / set_critic's to give, before this).
+        """optim_state's dict back into the network `which` (its parameters are set_actor's / set_critic's to give, before this); a
+        "value_norm" entry of the critic's is installed with set_value_norm.
         ValueError for a wrong shape and for what the library refuses (step < 0, a power outside (0, 1], a moment not finite)."""
         slot = A.optim_which("load_optim_state", which)
         m, v, st = A.optim_arrays("load_optim_state", state, L.CRITIC_N_PARAMS if slot is None else L.ACTOR_N_PARAMS)
         ptrs = (C.c_void_p(m.ctypes.data), C.c_void_p(v.ctypes.data), C.byref(st))
         if slot is None:
             self._call(self.lib.sdc_set_critic_optim, *ptrs, refuses=True)
+            if state.get("value_norm") is not None:      # (optim_state's, of an engine with a ValueNorm installed)
+                self.set_value_norm(state["value_norm"])
         else:
             self._call(self.lib.sdc_set_actor_optim, slot, *ptrs, refuses=True)
 
@@ -1365,6 +1430,183 @@ class SdcEngine:
         scale, shift = value_norm_scale_shift(value_norm)
         self._call(self.lib.sdc_set_critic_norm, float(scale), float(shift), self._stream(), refuses=True)
         self._critic.scale, self._critic.shift = float(scale), float(shift)      # (no parameters: the host copy follows at once)
+        self._value_norm_installed = False      # (the library uninstalls: scale and shift were set by hand)
+
+    # ------------------------------------------------------------------ train on the device: ValueNorm, shuffled mini-batches, happo_train
+    def set_value_norm(self, value_norm):
+        """A ValueNorm KEPT ON THE DEVICE (sdc_set_value_norm): `value_norm` as `critic_params` takes it -- a ValueNorm object or dict
+        with running_mean, running_mean_sq and debiasing_term; a (mean, var) pair becomes (mean, var + mean^2, 1) -- or None, which
+        uninstalls (the critic keeps the scale and shift it has).  While one is installed the critic's scale and shift follow it:
+        value_norm_update moves them on the device, and value_loss / critic_grads / critic_update called with value_norm=None read them
+        there.  set_critic and set_critic_value_norm uninstall.  The call waits for the device.  ValueError before set_critic and for
+        values that are not finite."""
+        st = A.value_norm_struct("set_value_norm", value_norm)
+        self._call(self.lib.sdc_set_value_norm, None if st is None else C.byref(st), refuses=True)
+        self._value_norm_installed = st is not None
+        self._stale_critic = True      # (scale and shift of the host copy)
+        if st is None:
+            self._host_critic()
+
+    def value_norm_state(self) -> dict:
+        """The installed ValueNorm as the device holds it now: {running_mean, running_mean_sq, debiasing_term, scale, shift} as Python
+        floats of the fp32 values (the first three are what set_value_norm takes).  It waits for the device.  ValueError while none is
+        installed."""
+        st = L.SdcValueNorm()
+        self._call(self.lib.sdc_get_value_norm, C.byref(st), refuses=True)
+        self._stale_critic = True
+        p = self._host_critic()
+        return dict(running_mean=float(st.running_mean), running_mean_sq=float(st.running_mean_sq), debiasing_term=float(st.debiasing_term),
+                    scale=float(p.scale), shift=float(p.shift))
+
+    def value_norm_update(self, returns, beta: float = 0.99999):
+        """ValueNorm.update(returns) for the installed ValueNorm, on the device (sdc_value_norm_update: two launches, stream-ordered,
+        fixed-order fp64 sums, the reference's fp32 recurrence; include/sustaindc_hip.h states it): `returns` a contiguous fp32 tensor
+        of any shape on this engine's device.  The critic's scale and shift follow: launches behind this call see the new statistics.
+        ValueError while no ValueNorm is installed, for an empty tensor and for beta outside [0, 1)."""
+        t, who = self.torch, "value_norm_update"
+        A.any_shape(who, returns, "returns", t.float32, self.device)
+        self._behind_torch_stream()
+        self._call(self.lib.sdc_value_norm_update, _p(returns), returns.numel(), A.finite_float(who, "beta", beta), self._stream(),
+                   refuses=True, wrote=(returns,))
+        self._stale_critic = True      # (scale and shift of the host copy)
+
+    def permutation(self, n: int, seed: int, stream_id: int = 0):
+        """A keyed pseudo-random bijection of 0 .. n-1 as an int32 tensor [n] on this engine's device (sdc_permutation: one launch, one
+        lane per output, no sort; stream-ordered).  The same (n, seed, stream_id) give the same bits on every run; it shuffles rows, it
+        is no uniform draw from all n! permutations (include/sustaindc_hip.h).  ValueError for n outside 1 .. 2^31 - 1."""
+        t = self.torch
+        n = int(n)
+        if not 1 <= n <= L.PERM_MAX_N:
+            raise ValueError(f"permutation: n = {n} outside [1, {L.PERM_MAX_N}]")
+        perm = t.empty(n, dtype=t.int32, device=self.device)
+        self._call(self.lib.sdc_permutation, n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFFFFFFFFFF, _p(perm), self._stream(),
+                   refuses=True, wrote=(perm,))
+        return perm
+
+    def minibatch(self, batch, indices, agent=None, critic: bool = True, into=None, *, actors: bool = True, factor=None) -> MiniBatch:
+        """The rows `indices` of an OnPolicyBatch as a dense mini-batch (sdc_gather_rows: ONE launch for all fields, stream-ordered):
+        `indices` int32 [T' N] on this engine's device, indices into the T N rows of batch.flat() -- a permutation(), a slice of one,
+        a torch.randperm cast to int32 -- -> a MiniBatch whose per-step fields are [T', N, ...]; actor_update, actor_update_terms and
+        critic_update run on it unchanged.  `agent`: only that agent's column of obs, actions, action_log_probs, logits and entropy is
+        written (a third of the bytes); `critic` False: share_obs, values, value_preds and returns are not gathered; `actors` False:
+        the per-agent fields and the advantages are not; rewards, masks and dones (uint8: gathered by torch ops) only with both.
+        adv_mean / adv_std are the parent's, so normalized_advantages() gives the parent's normalisation.  `factor` fp32 [T, N]: gathered
+        alongside into MiniBatch.factor.  `into`: a MiniBatch of an earlier call with the same arguments, whose tensors are written
+        again.  An index outside [0, T N) is never an address: that row comes back as zeros and MiniBatch.bad is 1.  ValueError when
+        len(indices) is not a positive multiple of N, and for tensors of another kind."""
+        t, who, N = self.torch, "minibatch", self.n_envs
+        a = None if agent is None else A.agent_slot(who, agent)
+        if not isinstance(batch, OnPolicyBatch):
+            raise ValueError(f"{who}: batch must be an OnPolicyBatch")
+        if not (actors or critic):
+            raise ValueError(f"{who}: neither the actors' nor the critic's fields are asked for")
+        T = batch.n_steps
+        A.device_tensor(indices, who, "indices", t.int32, (A.SOME,), "(rows,)", self.device)
+        rows = indices.numel()
+        if rows % N:
+            raise ValueError(f"{who}: len(indices) = {rows} is not a positive multiple of n_envs = {N}")
+        Tm = rows // N
+        plan = A.minibatch_segments(a, actors, critic)
+        if len(plan) + (factor is not None) > L.GATHER_MAX_SEGMENTS:
+            raise ValueError(f"{who}: more than {L.GATHER_MAX_SEGMENTS} arrays in one gather")
+        book = actors and critic
+        names = [name for name, _, _, _ in plan] + (["dones"] if book else [])
+        if into is None:
+            fields = dict.fromkeys(OnPolicyBatch.FIELDS)
+            for name in names:
+                src = getattr(batch, name)
+                fields[name] = t.empty((Tm, N) + tuple(src.shape[2:]), dtype=src.dtype, device=self.device)
+            into = MiniBatch(Tm, None if factor is None else t.empty((Tm, N), dtype=t.float32, device=self.device),
+                             t.zeros(1, dtype=t.int32, device=self.device), **fields)
+        else:
+            if not isinstance(into, MiniBatch) or into.n_steps != Tm or (factor is None) != (into.factor is None):
+                raise ValueError(f"{who}: into must be a MiniBatch of {Tm} steps from a call with the same arguments")
+            into.bad.zero_()
+        into.adv_mean, into.adv_std, into.last_done = batch.adv_mean, batch.adv_std, batch.last_done
+        segs = (L.SdcGatherSegment * (len(plan) + (factor is not None)))()
+        used = [indices, into.bad]
+        pairs = [(getattr(batch, name), getattr(into, name), off, n, row, name) for name, off, n, row in plan]
+        if factor is not None:
+            A.device_tensor(factor, who, "factor", t.float32, (T, N), "(T, n_envs)", self.device)
+            pairs.append((factor, into.factor, 0, 1, 1, "factor"))
+        for g, (src, dst, off, n, row, name) in zip(segs, pairs):
+            if src is None or dst is None:
+                raise ValueError(f"{who}: the batch or `into` holds no {name}")
+            want = (Tm, N) + tuple(src.shape[2:])
+            if not (src.is_contiguous() and dst.is_contiguous() and src.shape[0] >= T and tuple(dst.shape) == want and dst.dtype == src.dtype
+                    and src.element_size() == 4 and src.device == self.device and dst.device == self.device):
+                raise ValueError(f"{who}: {name} must be contiguous 4-byte tensors on {self.device}, `into`'s of shape {want}")
+            g.src, g.dst = src.data_ptr() + 4 * off, dst.data_ptr() + 4 * off
+            g.src_stride = g.dst_stride = row
+            g.n_dwords = n
+            used += [src, dst]
+        self._behind_torch_stream()
+        self._call(self.lib.sdc_gather_rows, _p(indices), rows, T * N, segs, len(segs), _p(into.bad), self._stream(), refuses=True, wrote=used)
+        if book:      # (uint8 rows are no dword rows: torch gathers them, an index outside the rows giving 0 as above)
+            ok = (indices >= 0) & (indices < T * N)
+            picked = batch.dones[:T].reshape(-1).index_select(0, indices.clamp(0, T * N - 1).long())
+            into.dones.copy_((picked * ok).view(Tm, N))
+        return into
+
+    def happo_train(self, batch, *, seed=None, ppo_epoch: int = 5, critic_epoch: int = 5, actor_num_mini_batch: int = 1,
+                    critic_num_mini_batch: int = 1, agent_order=(0, 1, 2), use_factor: bool = True, indices=None, clip_param: float = 0.2,
+                    entropy_coef: float = 0.01, huber_delta: float = 10.0, use_huber_loss: bool = True, use_clipped_value_loss: bool = True,
+                    value_loss_coef: float = 1.0, lr, critic_lr=None, betas=(0.9, 0.999), eps: float = 1e-5, weight_decay: float = 0.0,
+                    max_grad_norm=None, update_value_norm: bool = True, beta: float = 0.99999) -> TrainInfo:
+        """The reference's OnPolicyHARunner.train() over one OnPolicyBatch, on the device, nothing read by the host.  For every agent
+        of `agent_order`: its log-probabilities over the whole batch before the update (evaluate_actions); `ppo_epoch` epochs, each
+        over one permutation of the T N rows -- permutation(T N, seed, (agent << 32) | epoch) -- cut into `actor_num_mini_batch` pieces
+        of (T / num) N rows, each piece gathered (minibatch, the agent's columns and the factor) and given to actor_update; then the
+        HAPPO factor is multiplied by exp(new - old) over the whole batch (actor_update_terms).  The critic follows: `critic_epoch`
+        epochs over permutation(T N, seed, (3 << 32) | epoch) cut into `critic_num_mini_batch` pieces; per piece value_norm_update on
+        the piece's returns first -- while a ValueNorm is installed (set_value_norm) and `update_value_norm` is on -- then
+        critic_update.  `indices`: {(who, epoch): int32 [T N] on the device}, who an agent slot or "critic": these replace the draws
+        (a test replays the reference's own permutations); `seed` may be None when it names every epoch.  The loss arguments are
+        actor_update's and critic_update's, `lr` the actors' and `critic_lr` the critic's (None: lr), the Adam arguments both's.
+        -> TrainInfo.  ValueError when a num_mini_batch does not divide T (the reference drops the remainder; we refuse)."""
+        who, N, T = "happo_train", self.n_envs, batch.n_steps
+        order = A.agent_slots(who, agent_order)
+        a_rows = A.minibatch_rows(who, T, N, actor_num_mini_batch)
+        c_rows = A.minibatch_rows(who, T, N, critic_num_mini_batch)
+        indices = {} if indices is None else indices
+
+        def draw(key, stream_who, epoch):
+            if key in indices:
+                A.device_tensor(indices[key], who, f"indices[{key!r}]", self.torch.int32, (T * N,), f"({T * N},)", self.device)
+                return indices[key]
+            if seed is None:
+                raise ValueError(f"{who}: no seed and no indices for {key!r}")
+            return self.permutation(T * N, seed, A.perm_stream_id(stream_who, epoch))
+
+        adam = dict(betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        info, factor, mb = TrainInfo(), None, None
+        for a in order:
+            _, old_lp, _ = self.evaluate_actions(batch.obs[:T], batch.actions, agents=(a,), want_entropy=False)
+            ups = info.actor[a] = []
+            for e in range(int(ppo_epoch)):
+                perm = draw((a, e), a, e)
+                for k in range(0, T * N, a_rows):
+                    mb = self.minibatch(batch, perm[k:k + a_rows], agent=a, critic=False, into=mb, factor=factor)
+                    terms, norm = self.actor_update(mb, a, clip_param, entropy_coef, factor=mb.factor, lr=lr, **adam)
+                    ups.append((terms.stats, norm))
+            if use_factor:
+                new_factor = self.actor_update_terms(batch, a, clip_param, factor=factor, old_log_probs=old_lp).factor
+                if factor is None:
+                    mb = None      # (the next agent's pieces carry a factor: other tensors)
+                factor = new_factor
+        info.factor = factor
+        mb = None
+        vn = update_value_norm and self._value_norm_installed
+        for e in range(int(critic_epoch)):
+            perm = draw(("critic", e), 3, e)
+            for k in range(0, T * N, c_rows):
+                mb = self.minibatch(batch, perm[k:k + c_rows], actors=False, into=mb)
+                if vn:
+                    self.value_norm_update(mb.returns, beta)
+                terms, norm = self.critic_update(mb, clip_param, huber_delta, use_huber_loss, use_clipped_value_loss, value_loss_coef,
+                                                 lr=lr if critic_lr is None else critic_lr, **adam)
+                info.critic.append((terms.stats, norm))
+        return info
 
     # ------------------------------------------------------------------ state access (parity injection / checkpoint)
     def _state_array(self, name):

@@ -808,6 +808,32 @@ class SustainDCVecEnv(ShareVecEnv):
         """The critic's ValueNorm alone, stream-ordered (SdcEngine.set_critic_value_norm)"""
         self.engine.set_critic_value_norm(value_norm)
 
+    def set_value_norm(self, value_norm):
+        """A ValueNorm kept on the device, which the critic's scale and shift then follow; None uninstalls (SdcEngine.set_value_norm)"""
+        self.engine.set_value_norm(value_norm)
+
+    def value_norm_state(self):
+        """The installed ValueNorm as the device holds it now (SdcEngine.value_norm_state)"""
+        return self.engine.value_norm_state()
+
+    def value_norm_update(self, returns, beta=0.99999):
+        """ValueNorm.update(returns) on the device, stream-ordered (SdcEngine.value_norm_update)"""
+        self.engine.value_norm_update(returns, beta)
+
+    def permutation(self, n, seed, stream_id=0):
+        """A keyed pseudo-random bijection of 0 .. n-1 as an int32 device tensor (SdcEngine.permutation)"""
+        return self.engine.permutation(n, seed, stream_id)
+
+    def minibatch(self, batch, indices, *args, **kw):
+        """The rows `indices` of an OnPolicyBatch as a dense MiniBatch, one gather launch (SdcEngine.minibatch, which documents the
+        arguments)"""
+        return self.engine.minibatch(batch, indices, *args, **kw)
+
+    def happo_train(self, batch, **kw):
+        """The reference's OnPolicyHARunner.train() over one OnPolicyBatch on the device: shuffled mini-batches, the HAPPO factor,
+        ValueNorm's running update (SdcEngine.happo_train, which documents the arguments) -> TrainInfo"""
+        return self.engine.happo_train(batch, **kw)
+
     def gae(self, rew, done, values, *args, **kw):
         """Returns, advantages and masks of a collected rollout (SdcEngine.gae, which documents the arguments and the result)"""
         return self.engine.gae(rew, done, values, *args, **kw)
@@ -885,7 +911,7 @@ class SustainDCVecEnv(ShareVecEnv):
             self.engine.load_optim_state(slot, src.engine.optim_state(slot))
         if src.engine._host_critic() is not None:
             self.engine._set_critic_struct(src.engine._critic)
-            self.engine.load_optim_state("critic", src.engine.optim_state("critic"))
+            self.engine.load_optim_state("critic", src.engine.optim_state("critic"))      # (an installed ValueNorm travels with it)
             self.engine.set_plan_critic(src.engine.plan_critic)
         self.months, self._cfg_id, self._const = list(src.months), list(src._cfg_id), list(src._const)
         if not src._need_reset:

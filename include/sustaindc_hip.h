@@ -661,7 +661,7 @@ int sdc_action_log_probs(sdc_handle* h, int n_steps, const int32_t* actions, con
  * (harl/algorithms/actors/on_policy_base.py evaluate_actions -> StochasticPolicy.evaluate_actions), which harl/runners/on_policy_ha_runner.py
  * runs over the whole buffer before and after every agent's update for the HAPPO factor, and the terms harl/algorithms/actors/happo.py and
  * mappo.py build from its log-probabilities (imp_weights, the clipped surrogate, the entropy).  No gradient: the backward pass is
- * sdc_actor_backward (THE ACTORS' GRADIENT below), the critic's value loss is THE CRITIC'S GRADIENT's; the optimiser is not here.  Both calls are pure functions of their arrays, all device memory: they read no env
+ * sdc_actor_backward (THE ACTORS' GRADIENT below), the critic's value loss is THE CRITIC'S GRADIENT's; the optimiser is THE OPTIMISER STEP, shuffled mini-batches are TRAIN ON THE DEVICE.  Both calls are pure functions of their arrays, all device memory: they read no env
  * state and move nothing in the engine; each is ordered on `stream` with no synchronisation.
  * sdc_actor_evaluate: the logits of agent_slot's network -- the one last given to sdc_set_actor for that slot, the network stated at
  * sdc_set_actor, fp32, the hidden layers on fp32-input matrix instructions, 16 rows per wavefront (csrc/sdc_rowmlp.hpp) -- for n_rows
@@ -708,7 +708,8 @@ int sdc_ppo_terms(sdc_handle* h, int n_steps, int agent, const float* new_log_pr
 /* THE ACTORS' GRADIENT.  replaces: loss.backward() of the reference's actor update (harl/algorithms/actors/happo.py update:
  * policy_loss - entropy_coef * dist_entropy, differentiated by autograd through StochasticPolicy.evaluate_actions) -- the gradient with
  * respect to every parameter of one agent's network, on fp32-input matrix instructions, in a fixed summation order.  NOT here: the
- * optimiser step and minibatch shuffling (sdc_actor_adam_step, THE OPTIMISER STEP below; or a caller steps an optimiser over the SDC_ACTOR_N_PARAMS values and calls sdc_set_actor);
+ * optimiser step (sdc_actor_adam_step, THE OPTIMISER STEP below; or a caller steps an optimiser over the SDC_ACTOR_N_PARAMS values and calls sdc_set_actor)
+ * and minibatch shuffling (sdc_permutation and sdc_gather_rows, TRAIN ON THE DEVICE below: the rows are made dense, then these calls run on them);
  * the critic's value loss and its gradient are THE CRITIC'S GRADIENT below.  Both calls are pure functions of their arrays, all device memory: they read no
  * env state and move nothing in the engine; each is ordered on `stream` with no synchronisation.
  * sdc_ppo_dlogp: the loss's derivative per stored log-probability, ONE launch of sdc_ppo_dlogp_kernel.  Per element i = t N + n < T N
@@ -756,8 +757,9 @@ int sdc_actor_backward(sdc_handle* h, int agent_slot, const float* obs, long lon
 /* THE CRITIC'S GRADIENT.  replaces: the critic's half of an on-policy update (harl/algorithms/critics/v_critic.py cal_value_loss and
  * update's loss.backward(), harl/utils/models_tools.py huber_loss / mse_loss, harl/common/valuenorm.py normalize) -- the network's own
  * output over stored share_obs rows, the clipped Huber / MSE value loss with its derivative per row, and the gradient with respect to
- * every parameter of the critic.  NOT here: the optimiser step, ValueNorm's running update, minibatch shuffling (a caller updates its
- * normaliser first, as the reference does, and steps with sdc_critic_adam_step, THE OPTIMISER STEP below, or its own optimiser and sdc_set_critic).  All three
+ * every parameter of the critic.  NOT here: the optimiser step (sdc_critic_adam_step, THE OPTIMISER STEP below, or a caller's own optimiser and sdc_set_critic),
+ * ValueNorm's running update and minibatch shuffling (sdc_value_norm_update, sdc_permutation and sdc_gather_rows, TRAIN ON THE DEVICE
+ * below: the normaliser is updated first, as the reference does it, and sdc_value_loss_normed reads the new statistics).  All three
  * calls are pure functions of their arrays, all device memory: they read no env state and move nothing in the engine; each is ordered
  * on `stream` with no synchronisation; no atomics: the same call gives the same bits on every run.
  * sdc_critic_evaluate: raw_values[r] = u_r, the network's own output for share_obs row r BEFORE `* scale + shift` -- what the
@@ -869,6 +871,79 @@ int sdc_set_actor_optim(sdc_handle* h, int agent_slot, const float* m, const flo
 int sdc_get_critic_optim(sdc_handle* h, float* m, float* v, sdc_optim_state* st);
 int sdc_set_critic_optim(sdc_handle* h, const float* m, const float* v, const sdc_optim_state* st);
 int sdc_set_critic_norm(sdc_handle* h, double scale, double shift, void* stream);
+
+/* TRAIN ON THE DEVICE.  replaces: what a trainer does between two collections around the calls above -- the shuffled mini-batches of
+ * harl/common/buffers (feed_forward_generator_actor / _critic: torch.randperm(T N) per epoch, index sets of (T / num_mini_batch) N
+ * rows) and harl/common/valuenorm.py ValueNorm.update, which v_critic.py cal_value_loss runs inside every critic mini-batch before it
+ * normalises the returns with the new statistics.  Every call but the set / get pair is ordered on `stream` with no synchronisation
+ * and no atomics: the same call gives the same bits on every run.  The arithmetic stands once, for the device and for a host
+ * compiler, in csrc/sdc_minibatch.hpp; the kernels' plans: csrc/sdc_minibatch_dev.hpp.  The loop itself (agent order, epochs, the
+ * HAPPO factor) is the binding's: dc_rl_amd.SdcEngine.happo_train.
+ * sdc_permutation: perm[i], i < n, a keyed bijection of 0 .. n-1 (1 <= n <= 2^31 - 1) in int32 device memory, ONE launch of
+ * sdc_permutation_kernel with one lane per output and no sort -- a six-round Feistel network over 4^b >= n values with cycle walking,
+ * its round function one philox4x32_10 block (csrc/sdc_philox.hpp):
+ *     bits = bit length of (n - 1)   (0 for n = 1);   b = max(1, (bits + 1) / 2);   mask = 2^b - 1
+ *     x = i
+ *     do {  L = x >> b;  R = x & mask
+ *           for r = 0 .. 5:  F = philox4x32_10(counter (R, r, stream_lo, stream_hi), key (seed_lo, seed_hi)).x & mask;   (L, R) = (R, L ^ F)
+ *           x = (L << b) | R
+ *     } while (x >= n)
+ *     perm[i] = x
+ * (lo, hi: the low and high 32 bits of stream_id and seed).  For n >= 2, 4^b < 4 n: a lane walks fewer than four times on average.
+ * IT IS A PSEUDO-RANDOM BIJECTION FOR SHUFFLING ROWS, NOT A UNIFORM DRAW FROM ALL n! PERMUTATIONS.  Four rounds are not enough: over
+ * 4096 streams at n = 12 the position-by-value table has chi-square 234 on 121 degrees of freedom with four rounds and 129 with six.
+ * Refused (-2 and a message, nothing enqueued): a null handle; n outside 1 .. 2^31 - 1; a null perm or one not dword-aligned.
+ * sdc_gather_rows: for every k < n_rows and every segment g < n_segs (1 .. SDC_GATHER_MAX_SEGMENTS, a HOST array) the g.n_dwords
+ * dwords at g.src + idx[k] * g.src_stride are copied to g.dst + k * g.dst_stride -- all arrays are dword arrays in device memory, the
+ * strides are in dwords; ONE launch of sdc_gather_rows_kernel for all segments.  idx [n_rows] int32 device memory: a permutation,
+ * a slice of one, or any index array.  The dwords between two destination rows keep their values.  AN INDEX OUTSIDE
+ * [0, n_src_rows) IS NEVER AN ADDRESS: that destination row is written as zero dwords in every segment, and bad[0] (int32 device
+ * memory, or NULL) receives a plain store of 1; bad is not cleared by the call.  Source and destination arrays must not overlap.
+ * Refused: a null handle; n_rows < 1; n_src_rows outside 1 .. 2^31 - 1; a null idx or segs; idx or bad not dword-aligned; n_segs
+ * outside 1 .. 16; a segment with a null src or dst, one not dword-aligned, n_dwords < 1 or a stride below n_dwords.
+ * VALUENORM ON THE DEVICE: the handle keeps a device block {running_mean, running_mean_sq, debiasing_term, scale, shift} fp32 and a
+ * host flag "installed".  sdc_set_value_norm installs the three values of `st` (NULL: uninstalls; the critic keeps the scale and shift
+ * it has), derives, in fp32 with one rounding per operation,
+ *     deb = max(debiasing_term, 1e-5);  mean = running_mean / deb;  mean_sq = running_mean_sq / deb
+ *     var = max(mean_sq - mean * mean, 1e-2);  scale = sqrt(var);  shift = mean
+ * and writes scale and shift into the critic's packed copy as sdc_set_critic_norm does; it waits for the device, as sdc_set_critic
+ * does.  sdc_get_value_norm: the three values as the device holds them now (it waits for the device).  sdc_set_critic and
+ * sdc_set_critic_norm do exactly what they did, and they UNINSTALL: a caller who sets scale and shift by hand has no running state.
+ * While a ValueNorm is installed sdc_get_critic returns the device's scale and shift.
+ * sdc_value_norm_update: ValueNorm.update for per_element_update = False over returns [n] fp32 device memory, TWO launches
+ * (sdc_value_norm_sums_kernel, sdc_value_norm_update_kernel):
+ *     S1 = sum of (double)x,  S2 = sum of (double)(float)(x * x)      // the square rounded to fp32 first, as the reference squares
+ * both in sdc_ppo_terms' fixed two-stage order, word for word (B = min(ceil(n / 256), 1024) workgroups of 256 lanes, lane l of workgroup
+ * b folds i = b * 256 + l + k * 256 * B from 0.0, the tree from 128 down; then one workgroup whose lane l takes partials l, l + 256,
+ * ... and the same tree).  One lane then computes, each operation rounded once to fp32, nothing contracted:
+ *     bm = (float)(S1 / n);  bsq = (float)(S2 / n);  w = (float)beta;  omw = (float)(1.0 - beta)      // the subtraction in double
+ *     running_mean = running_mean * w + bm * omw;   running_mean_sq = running_mean_sq * w + bsq * omw
+ *     debiasing_term = debiasing_term * w + omw
+ * derives scale and shift as above, and stores the five values in the block and scale and shift in the critic's packed copy:
+ * launches behind it on the stream -- sdc_critic_values, sdc_gae's value_preds, sdc_value_loss_normed -- see the new statistics.
+ * Refused: a null handle; no critic set; no ValueNorm installed; n < 1; a null returns or one not dword-aligned; beta outside [0, 1).
+ * sdc_value_loss_normed: sdc_value_loss with target_scale and target_shift read by the kernel from the block
+ * (sdc_value_loss_normed_kernel: the same arithmetic, the same statistics, the same two launches); sdc_value_loss and its kernel are
+ * unchanged.  Refused: what sdc_value_loss refuses about the arguments they share, and while no ValueNorm is installed. */
+#define SDC_GATHER_MAX_SEGMENTS 16
+typedef struct {
+  float running_mean, running_mean_sq, debiasing_term;
+} sdc_value_norm;
+typedef struct {
+  const void* src;           /* device memory, dword-aligned: row r starts at src + r * src_stride dwords */
+  void* dst;                 /* device memory, dword-aligned: row k starts at dst + k * dst_stride dwords */
+  long long src_stride, dst_stride;
+  int n_dwords;              /* 1 .. min(src_stride, dst_stride) */
+} sdc_gather_segment;
+int sdc_permutation(sdc_handle* h, long long n, uint64_t seed, uint64_t stream_id, int32_t* perm, void* stream);
+int sdc_gather_rows(sdc_handle* h, const int32_t* idx, long long n_rows, long long n_src_rows, const sdc_gather_segment* segs, int n_segs,
+                    int32_t* bad, void* stream);
+int sdc_set_value_norm(sdc_handle* h, const sdc_value_norm* st);
+int sdc_get_value_norm(sdc_handle* h, sdc_value_norm* out);
+int sdc_value_norm_update(sdc_handle* h, const float* returns, long long n, double beta, void* stream);
+int sdc_value_loss_normed(sdc_handle* h, long long n, const float* raw_values, const float* value_preds, const float* returns,
+                          double clip_param, double huber_delta, int flags, double coef, float* loss, float* dvalue, double* stats,
+                          void* stream);
 
 /* PLAN FORECAST: what the plan calls' rollouts believe the traces of the next n_steps steps are.  Without one a plan call's rollouts
  * read the episode's own feature rows -- the real workload, carbon intensity, dry bulb (with the weather noise the episode drew) and wet
