@@ -1,51 +1,20 @@
 // sdc_actor_grad_pack.hpp -- the TRANSPOSED weights of one agent's actor as sdc_actor_grad_kernel's backward reads them
-// (SdcActorGradDev: device memory, then LDS), and the pack from torch's layout (sdc_actor_params) into it.  sdc_set_actor
-// (sdc_capi.hip) builds it next to SdcActorEvalDev (sdc_actor_eval_pack.hpp) and uploads both.
+// (SdcActorGradDev: the row networks' SdcRowMlpGradDev with 26 inputs; the layout and the pack: sdc_rowmlp_grad_pack.hpp).
+// sdc_set_actor (sdc_capi.hip) builds it next to SdcActorEvalDev (sdc_actor_eval_pack.hpp) and uploads both.
 //
-// Plain C++17: no HIP, no sdc_handle, no device calls -- a host compiler alone builds it (tests/test_actor_grad_abi.py builds it into a
-// small program, un-permutes what it packed and holds it to the input bit for bit).
-//
-// THE LAYOUT follows the backward's two products that move no data (sdc_actor_grad.hpp).  The forward leaves a layer's pre-activation
-// gradient dZ in the accumulators' layout -- register (t, i) of lane l = (g = l >> 4, e = l & 15) is unit 16 t + 4 g + i of row e --, and
-// that register IS the B operand of k-step s = 4 t + i of the transposed product dY^T = W^T dZ^T, its k index 4 s + g standing for unit
-// sdc_rowmlp_unit_of_k(4 s + g) (sdc_rowmlp_pack.hpp).  The A operand holds W^T with its columns numbered so:
-//   a2t[s][l][t'] = W2[unit_of_k(4 s + (l >> 4))][16 t' + (l & 15)]          dY1: register (t', r) = unit 16 t' + 4 g + r, layer 1's own layout
-//   a1t[s][l][t'] = W1[unit_of_k(4 s + (l >> 4))][entry(t', l & 15)]         t' = 0, 1; entry(t', i) = 16 t' + 4 (i & 3) + (i >> 2), 0 for
-//                                                                            entries >= 26
-// The rows of a1t are numbered so that register (t', r) of lane (g, e) is entry 16 t' + 4 r + g = 4 (4 t' + r) + g of row e: the
-// observation's own layout (x[s] = entry 4 s + g, s = 4 t' + r), where the feature LayerNorm's normalised entries wait.
+// Plain C++17: no HIP, no sdc_handle, no device calls -- a host compiler alone builds it (tests/test_actor_grad_abi.py).
 #pragma once
 
 #include <cstddef>
-#include <cstring>
 
 #include "../../include/sustaindc_hip.h"
 #include "sdc_actor_eval_pack.hpp"
+#include "sdc_rowmlp_grad_pack.hpp"
 
-struct SdcActorGradDev {
-  float a2t[SDC_ROWMLP_S2][64][4];
-  float a1t[SDC_ROWMLP_S2][64][2];
-};
-static_assert(sizeof(SdcActorGradDev) % 16 == 0, "copied to LDS as 16-byte units");
+using SdcActorGradDev = SdcRowMlpGradDev;
 
 // the float members of sdc_actor_params, in declaration order: what sdc_actor_backward's `grads` holds
 static_assert(SDC_ACTOR_N_PARAMS * sizeof(float) == offsetof(sdc_actor_params, use_feature_normalization), "every float member, no padding");
 static_assert(SDC_ACTOR_N_PARAMS == 2 * 26 + 64 * 26 + 3 * 64 + 64 * 64 + 3 * 64 + 3 * 64 + 3, "ln0, w1, b1 ln1, w2, b2 ln2, w3, b3");
 
-// the observation entry that row i of tile t' of a1t stands for
-inline int sdc_actor_grad_entry(const int tp, const int i) { return 16 * tp + 4 * (i & 3) + (i >> 2); }
-
-// torch's layout ([out][in] rows) -> the backward's
-inline void sdc_actor_grad_pack(const sdc_actor_params* p, SdcActorGradDev* d) {
-  std::memset(d, 0, sizeof(*d));
-  for (int s = 0; s < SDC_ROWMLP_S2; s++)
-    for (int l = 0; l < 64; l++) {
-      const int g = l >> 4, e = l & 15;
-      const int unit = sdc_rowmlp_unit_of_k(4 * s + g);
-      for (int t = 0; t < 4; t++) d->a2t[s][l][t] = p->w2[unit * SDC_ROWMLP_H + 16 * t + e];
-      for (int t = 0; t < 2; t++) {
-        const int k = sdc_actor_grad_entry(t, e);
-        d->a1t[s][l][t] = k < SDC_AEV_IN ? p->w1[unit * SDC_AEV_IN + k] : 0.0f;
-      }
-    }
-}
+inline void sdc_actor_grad_pack(const sdc_actor_params* p, SdcActorGradDev* d) { sdc_rowmlp_grad_pack<SDC_AEV_IN>(p->w1, p->w2, d); }

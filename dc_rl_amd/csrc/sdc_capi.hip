@@ -1966,6 +1966,15 @@ int sdc_ppo_dlogp(sdc_handle* h, int n_steps, int agent, const float* new_log_pr
   return launched("sdc_ppo_dlogp_kernel", sdc_ppo_dlogp_launch(P, reinterpret_cast<hipStream_t>(stream)));
 }
 
+// the tail of both backward calls (sdc_rowmlp_grad.hpp): the B partials' fp64 sum into `grads`, then, where grad_sq is given, its squares
+static int grads_from_partials(const char* reduce_kernel, hipError_t (*reduce)(const SdcRowMlpGradReduce&, hipStream_t), const char* sq_kernel,
+                               hipError_t (*sq)(const SdcRowMlpGradSq&, hipStream_t), const int n_part, const float* part, float* grads,
+                               double* grad_sq, hipStream_t st) {
+  if (const int rc = launched(reduce_kernel, reduce(SdcRowMlpGradReduce{n_part, part, grads}, st))) return rc;
+  if (!grad_sq) return 0;
+  return launched(sq_kernel, sq(SdcRowMlpGradSq{grads, grad_sq}, st));
+}
+
 int sdc_actor_backward(sdc_handle* h, int agent_slot, const float* obs, long long row_stride, long long n_rows, const int32_t* actions,
                        long long action_stride, const float* dlogp, double dent, float* grads, double* grad_sq, void* stream) {
   if (refused(sdc_actor_backward_refused(call_facts(h), agent_slot, obs, row_stride, n_rows, actions, action_stride, dlogp, dent, grads, grad_sq)))
@@ -1986,11 +1995,8 @@ int sdc_actor_backward(sdc_handle* h, int agent_slot, const float* obs, long lon
   P.dent = dent;
   P.part = h->actor_grad_part;
   if (const int rc = launched("sdc_actor_grad_kernel", sdc_actor_grad_launch(P, h->actor_activation[agent_slot], st))) return rc;
-  if (const int rc = launched("sdc_actor_grad_reduce_kernel",
-                              sdc_actor_grad_reduce_launch(SdcActorGradReduce{sdc_actor_grad_blocks(n_rows), h->actor_grad_part, grads}, st)))
-    return rc;
-  if (!grad_sq) return 0;
-  return launched("sdc_actor_grad_sq_kernel", sdc_actor_grad_sq_launch(SdcActorGradSq{grads, grad_sq}, st));
+  return grads_from_partials("sdc_actor_grad_reduce_kernel", sdc_actor_grad_reduce_launch, "sdc_actor_grad_sq_kernel", sdc_actor_grad_sq_launch,
+                             sdc_rowmlp_grad_blocks(n_rows, SDC_ACTOR_GRAD_MAX_BLOCKS), h->actor_grad_part, grads, grad_sq, st);
 }
 
 // ---- the critic's gradient (sdc_critic_grad.hip) -------------------------------------------------------------------------------------
@@ -2047,11 +2053,8 @@ int sdc_critic_backward(sdc_handle* h, const float* share_obs, long long n_rows,
   P.dvalue = dvalue;
   P.part = h->critic_grad_part;
   if (const int rc = launched("sdc_critic_grad_kernel", sdc_critic_grad_launch(P, h->critic_activation, st))) return rc;
-  if (const int rc = launched("sdc_critic_grad_reduce_kernel",
-                              sdc_critic_grad_reduce_launch(SdcCriticGradReduce{sdc_critic_grad_blocks(n_rows), h->critic_grad_part, grads}, st)))
-    return rc;
-  if (!grad_sq) return 0;
-  return launched("sdc_critic_grad_sq_kernel", sdc_critic_grad_sq_launch(SdcCriticGradSq{grads, grad_sq}, st));
+  return grads_from_partials("sdc_critic_grad_reduce_kernel", sdc_critic_grad_reduce_launch, "sdc_critic_grad_sq_kernel", sdc_critic_grad_sq_launch,
+                             sdc_rowmlp_grad_blocks(n_rows, SDC_CRITIC_GRAD_MAX_BLOCKS), h->critic_grad_part, grads, grad_sq, st);
 }
 
 int sdc_set_plan_critic(sdc_handle* h, double weight) {

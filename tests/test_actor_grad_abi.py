@@ -62,19 +62,27 @@ def test_kernels_compile_for_gfx950_without_scratch_or_spills():
 def test_the_shared_forward_left_the_evaluate_kernels_as_they_were():
     """sdc_actor_eval.hip still holds exactly its three kernels with their resources, and the network they, the critic and the gradient
     kernels run stands ONCE, in csrc/sdc_rowmlp.hpp: the three .hip files include it, and neither they nor the two forward headers hold
-    a matrix-instruction layer loop, an epilogue or a LayerNorm's rsq of their own (sdc_actor_grad.hip: its backward's five products)"""
+    a matrix-instruction layer loop, an epilogue or a LayerNorm's rsq of their own.  The backward stands ONCE as well, in
+    csrc/sdc_rowmlp_grad.hpp: its four products (dW2, dY1, dW1, dX) behind the head's forward call; sdc_actor_grad.hip holds its head's
+    one (dW3), sdc_critic_grad.hip none"""
     per = kernel_resources("sdc_actor_eval.hip")
     assert_no_scratch_or_spills(per, {"sdc_actor_eval_kernel", "sdc_ppo_terms_kernel", "sdc_ppo_stats_kernel"})
     read = lambda name: open(os.path.join(L.CSRC, name)).read()
     mfma, shared = "__builtin_amdgcn_mfma_f32_16x16x4f32", read("sdc_rowmlp.hpp")
     assert shared.count(mfma) == 2 and len(re.findall(r"\bvoid epilogue\(", shared)) == 1 and shared.count("__builtin_amdgcn_rsqf") == 2
-    for name in ("sdc_critic.hip", "sdc_actor_eval.hip", "sdc_actor_grad.hip", "sdc_critic.hpp", "sdc_actor_forward.hpp"):
+    counts = {"sdc_rowmlp_grad.hpp": 4, "sdc_actor_grad.hip": 1, "sdc_critic_grad.hip": 0}
+    for name in ("sdc_critic.hip", "sdc_actor_eval.hip", "sdc_actor_grad.hip", "sdc_critic_grad.hip", "sdc_rowmlp_grad.hpp", "sdc_critic.hpp",
+                 "sdc_actor_forward.hpp"):
         src = read(name)
         assert '#include "sdc_rowmlp.hpp"' in src, name
-        assert src.count(mfma) == (5 if name == "sdc_actor_grad.hip" else 0), name
+        assert src.count(mfma) == counts.get(name, 0), name
         assert "epilogue" not in src and "__builtin_amdgcn_rsqf" not in src, name
+        assert name not in counts or "rsq" not in src, name
+    body = read("sdc_rowmlp_grad.hpp")
+    assert body.index("HEAD::template forward<KIND>(W, x, lane, out, T)") < body.index(mfma)      # (the four stand behind the forward's call)
     grad = read("sdc_actor_grad.hip")
-    assert grad.index("sdc_aev::forward_kind<KIND>") < grad.index(mfma)      # (the five stand behind the forward's call: the backward)
+    assert grad.index("sdc_aev::forward_kind<KIND>(W, x, lane, out.lg, T)") < grad.index(mfma)     # (and dW3 behind the head's forward)
+    assert '#include "sdc_rowmlp_grad.hpp"' in grad and grad.index("struct Head {") < grad.index(mfma)
 
 
 # ---- the transposed pack ------------------------------------------------------------------------------------------------------------

@@ -69,18 +69,22 @@ def test_kernels_compile_for_gfx950_without_scratch_or_spills():
 
 
 def test_the_critic_backward_stands_next_to_the_actors_over_the_shared_trunk():
-    """the trunk stands ONCE, in csrc/sdc_rowmlp.hpp, with the two matrix-instruction loops it had; sdc_critic_grad.hip holds its
-    backward's four products (dW2, dY1, dW1, dX) behind the trunk's call and no epilogue or LayerNorm rsq of its own; no atomics anywhere in it"""
+    """the trunk stands ONCE, in csrc/sdc_rowmlp.hpp, with the two matrix-instruction loops it had; the backward's four products (dW2,
+    dY1, dW1, dX) stand ONCE, in csrc/sdc_rowmlp_grad.hpp, behind the head's forward call; sdc_critic_grad.hip holds its head (the
+    trunk's call) and no product, epilogue or LayerNorm rsq of its own; no atomics anywhere in it or in the shared backward"""
     read = lambda name: open(os.path.join(L.CSRC, name)).read()
     mfma, shared = "__builtin_amdgcn_mfma_f32_16x16x4f32", read("sdc_rowmlp.hpp")
     assert shared.count(mfma) == 2 and shared.count("__builtin_amdgcn_rsqf") == 2
-    src = read("sdc_critic_grad.hip")
-    assert '#include "sdc_rowmlp.hpp"' in src and src.count(mfma) == 4
-    assert "epilogue" not in src and "__builtin_amdgcn_rsqf" not in src and "atomic" not in src.lower()
-    assert src.index("sdc_rowmlp::trunk<KIND, SDC_CRITIC_IN>(W, x, lane, y2, T)") < src.index(mfma)
-    for name in ("sdc_critic_grad.hpp", "sdc_critic_grad_pack.hpp"):
+    src, body = read("sdc_critic_grad.hip"), read("sdc_rowmlp_grad.hpp")
+    assert '#include "sdc_rowmlp.hpp"' in src and '#include "sdc_rowmlp_grad.hpp"' in src and src.count(mfma) == 0 and body.count(mfma) == 4
+    for text in (src, body):
+        assert "epilogue" not in text and "rsq" not in text and "atomic" not in text.lower()
+    assert "sdc_rowmlp::trunk<KIND, SDC_CRITIC_IN>(W, x, lane, out.y2, T)" in src[src.index("struct Head {"):]
+    assert body.index("HEAD::template forward<KIND>(W, x, lane, out, T)") < body.index(mfma)
+    for name in ("sdc_critic_grad.hpp", "sdc_critic_grad_pack.hpp", "sdc_rowmlp_grad_pack.hpp"):
         assert mfma not in read(name), name
-    assert "hip" not in re.sub(r"//.*", "", read("sdc_critic_grad_pack.hpp")).replace("sustaindc_hip.h", "")      # (HIP-free)
+    for name in ("sdc_critic_grad_pack.hpp", "sdc_rowmlp_grad_pack.hpp"):
+        assert "hip" not in re.sub(r"//.*", "", read(name)).replace("sustaindc_hip.h", ""), name      # (HIP-free)
 
 
 # ---- the transposed pack ------------------------------------------------------------------------------------------------------------
