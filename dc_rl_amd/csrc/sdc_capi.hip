@@ -9,7 +9,7 @@
 // below tells it what it may know of the handle, and refused() turns its message into -2 with sdc_last_error set.  The fail_msg calls
 // left in this file need a HIP call's result (a device that is not there, an allocation or copy that failed) or come up while a kernel
 // plan is built from a HIP header (a segment table that is full, a layout a plan does not know); the null checks of the small setters
-// and getters and the parameter checks of sdc_setup.hpp / sdc_critic_pack.hpp are reported where they always were.
+// and getters and the parameter checks of sdc_setup.hpp are reported where they always were.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,6 +46,7 @@
 #include "sdc_optim_dev.hpp"
 #include "sdc_minibatch_dev.hpp"
 #include "sdc_pack_tables.hpp"
+#include "sdc_nets.hpp"
 #include "sdc_mpc.hpp"
 #include "sdc_mpc_groups.hpp"
 #include "sdc_mpc_schedule.hpp"
@@ -114,11 +115,11 @@ struct sdc_handle {
   double* ovr_ci_max = nullptr;
   double* ovr_t_min = nullptr;
   double* ovr_t_max = nullptr;
-  // closed loop (sdc_set_actor / sdc_rollout_actor): the three actor networks and the library's copy of the latest
-  // observations (what the first actions of a launch are chosen from); allocated when the first actor is set
-  SdcActorDev* actor_dev = nullptr;
-  bool actor_set[3] = {false, false, false};
-  int actor_activation[3] = {0, 0, 0};
+  // the three actor slots and the critic as the library holds a trainable network (sdc_nets.hpp SdcNet), filled when the first actor /
+  // the first critic is set (nets_alloc); the closed loop's SdcActorDev [3] is actor[0]'s first pack
+  SdcNet actor[3], critic;
+  // closed loop (sdc_rollout_actor): the library's copy of the latest observations (what the first actions of a launch are chosen
+  // from), allocated with the actors
   bool actor_lds_set = false;   // the closed-loop kernels' dynamic-LDS limit has been raised on this handle's device
   float* obs_latch = nullptr;
   bool latch_valid = false;
@@ -157,10 +158,7 @@ struct sdc_handle {
   IdxStage plan_stage{sizeof(double), SDC_MARK_MAX_STEPS};
   // sdc_set_plan_terms: what the plan calls score with next to their objective (both counts 0: nothing set, every field 0)
   sdc_plan_terms plan_terms{};
-  // sdc_set_critic: the critic in the kernels' layout (sdc_critic_pack.hpp), allocated when the first one is set; sdc_set_plan_critic:
-  // the weight the plan calls give its value of the horizon's last share_obs rows (0: off, nothing launched)
-  SdcCriticDev* critic_dev = nullptr;
-  bool critic_set = false;
+  // sdc_set_plan_critic: the weight the plan calls give the critic's value of the horizon's last share_obs rows (0: off, nothing launched)
   double plan_critic_weight = 0.0;
   // sdc_set_plan_forecast: what the plan calls' rollouts believe the traces ahead are (every field 0: nothing set); the forecast
   // [n_steps + 2][N][4] of a plan call and the row bits its overlay replaces (sdc_forecast.hpp), grown on demand and freed with the handle
@@ -174,46 +172,19 @@ struct sdc_handle {
   size_t policy_out_bytes = 0;
   // sdc_gae: every env's sum and sum of squares of its advantages [N][2] (sdc_onpolicy.hpp), allocated on first use
   double* adv_part = nullptr;
-  // sdc_actor_evaluate: the three actors once more, in the layout of the 16-rows-per-wavefront kernel (sdc_actor_eval_pack.hpp), allocated
-  // and filled with actor_dev; sdc_ppo_terms: stage 1's partial statistics [SDC_PPO_MAX_BLOCKS][8], allocated on first use
-  SdcActorEvalDev* actor_eval_dev = nullptr;
+  // sdc_ppo_terms: stage 1's partial statistics [SDC_PPO_MAX_BLOCKS][8], allocated on first use
   double* ppo_part = nullptr;
-  // sdc_actor_backward: the three actors' transposed weights (sdc_actor_grad_pack.hpp), allocated and filled with actor_dev; the
-  // workgroups' partial gradients [SDC_ACTOR_GRAD_MAX_BLOCKS][SDC_ACTOR_N_PARAMS], allocated on first use
-  SdcActorGradDev* actor_grad_dev = nullptr;
-  float* actor_grad_part = nullptr;
-  // sdc_critic_backward: the critic's transposed weights (sdc_critic_grad_pack.hpp), allocated and filled with critic_dev, and its
-  // activation; the workgroups' partial gradients [SDC_CRITIC_GRAD_MAX_BLOCKS][SDC_CRITIC_N_PARAMS] and sdc_value_loss' stage 1
-  // statistics [SDC_PPO_MAX_BLOCKS][8] (its own: not sdc_ppo_terms' -- the two may run on different streams), allocated on first use
-  SdcCriticGradDev* critic_grad_dev = nullptr;
-  int critic_activation = 0;
-  float* critic_grad_part = nullptr;
-  double* value_loss_part = nullptr;
-  // the optimiser step (sdc_optim.hip): per actor slot and for the critic the master parameters, Adam's moments (each [3][SDC_ACTOR_N_PARAMS]
-  // / [SDC_CRITIC_N_PARAMS] fp32) and the state block, allocated and filled with the packed copies by sdc_set_actor / sdc_set_critic; the
-  // gather tables of the packed copies (sdc_pack_tables.hpp), uploaded once per handle; and what a get hands back that is no parameter:
-  // the host record of the actors' flags and of the critic's scale, shift and flags
-  float* actor_params = nullptr;
-  float* actor_m = nullptr;
-  float* actor_v = nullptr;
-  sdc_optim_state* actor_optim = nullptr;
-  int32_t* actor_table = nullptr;
-  int actor_table_offset[4] = {0, 0, 0, 0};
-  int actor_feature_norm[3] = {0, 0, 0};
-  float* critic_params = nullptr;
-  float* critic_m = nullptr;
-  float* critic_v = nullptr;
-  sdc_optim_state* critic_optim = nullptr;
-  int32_t* critic_table = nullptr;
-  int critic_table_offset[3] = {0, 0, 0};
+  // what only the critic has: the host record of its scale, shift and flags (what a get hands back that is no parameter); the ValueNorm
+  // block (sdc_minibatch.hip), allocated with the critic -- "installed": sdc_set_value_norm has filled it and neither sdc_set_critic nor
+  // sdc_set_critic_norm has been called since; while it is, the device's scale and shift are the block's, not critic_scale /
+  // critic_shift (critic_norm_now answers).  Allocated on first use: the stage 1 statistics [SDC_PPO_MAX_BLOCKS][8] of sdc_value_loss /
+  // sdc_value_loss_normed (their own, not sdc_ppo_terms' -- the two may run on different streams) and sdc_value_norm_update's partial
+  // sums [SDC_VN_MAX_BLOCKS][2]
   float critic_scale = 1.0f, critic_shift = 0.0f;
   int critic_flags = 0;
-  // train on the device (sdc_minibatch.hip): the ValueNorm block, allocated with the critic; "installed": sdc_set_value_norm has filled
-  // it and neither sdc_set_critic nor sdc_set_critic_norm has been called since -- while it is, the device's scale and shift are the
-  // block's, not critic_scale / critic_shift; stage 1's partial sums [SDC_VN_MAX_BLOCKS][2] of sdc_value_norm_update and
-  // sdc_value_loss_normed's partial statistics are allocated on first use
   SdcValueNormDev* value_norm = nullptr;
   bool value_norm_installed = false;
+  double* value_loss_part = nullptr;
   double* value_norm_part = nullptr;
 };
 
@@ -240,22 +211,37 @@ int dev_alloc(sdc_handle* h, T** p, size_t count, bool zero = true) {
   return 0;
 }
 
-// a network's optimiser from new (sdc_set_actor / sdc_set_critic; the device is idle): the master copy filled from the params struct's
-// leading floats, the moments zeroed, the state block reset
-int optim_reset(const void* host_params, const size_t n, float* params, float* m, float* v, sdc_optim_state* state) {
-  const sdc_optim_state fresh{0, 1.0, 1.0, 0};
-  HIP_TRY(hipMemcpy(params, host_params, n * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemset(m, 0, n * sizeof(float)));
-  HIP_TRY(hipMemset(v, 0, n * sizeof(float)));
-  HIP_TRY(hipMemcpy(state, &fresh, sizeof(fresh), hipMemcpyHostToDevice));
+// ---- the networks (sdc_nets.hpp): every host path once, over an SdcNet; an entry point keeps its rule, its packs, what else it allocates
+SdcCriticDev* critic_dev(const sdc_handle* h) { return h->critic.pack_as<SdcCriticDev>(SDC_CRITIC_PACK_VALUES); }      // (null before sdc_set_critic)
+// first use of the `count` networks of one kind: their packed structs, master parameters, moments and state blocks (zeroed) and the
+// kind's gather table `t` (sdc_pack_tables.hpp), then the records -- filled only once everything is there
+template <int PACKS>
+int nets_alloc(sdc_handle* h, SdcNet* nets, const int count, const int n_params, const int n_in, const int grad_max_blocks, const SdcPackTables<PACKS>& t) {
+  SdcNet kind = sdc_net_kind(n_params, n_in, grad_max_blocks, PACKS, t.offset);
+  for (int i = 0; i < PACKS; i++)
+    if (dev_alloc(h, &kind.pack[i], (size_t)count * kind.pack_dwords[i]) != 0) return -1;
+  for (float** p : {&kind.params, &kind.m, &kind.v})
+    if (dev_alloc(h, p, (size_t)count * n_params) != 0) return -1;
+  if (dev_alloc(h, &kind.state, count) != 0) return -1;
+  int32_t* table = nullptr;
+  if (dev_alloc(h, &table, t.table.size(), false) != 0) return -1;
+  HIP_TRY(hipMemcpy(table, t.table.data(), t.table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  kind.table = table;
+  sdc_nets_fill(nets, count, kind);
   return 0;
 }
-// a gather table (sdc_pack_tables.hpp) on the device
-template <int PACKS>
-int upload_table(sdc_handle* h, const SdcPackTables<PACKS>& t, int32_t** dev, int (&offset)[PACKS + 1]) {
-  if (dev_alloc(h, dev, t.table.size(), false) != 0) return -1;
-  HIP_TRY(hipMemcpy(*dev, t.table.data(), t.table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  for (int i = 0; i <= PACKS; i++) offset[i] = t.offset[i];
+// a freshly set network: with the device idle, the host packs `packed` [n_packs] over its packed structs, a new optimiser (the master
+// copy from the params struct's leading floats, the moments zeroed, the state block reset), and the host facts recorded
+int net_install(SdcNet& n, const void* host_params, const void* const* packed, const int activation, const bool feature_norm) {
+  const sdc_optim_state fresh{0, 1.0, 1.0, 0};
+  const size_t bytes = (size_t)n.n_params * sizeof(float);
+  HIP_TRY(hipDeviceSynchronize());
+  for (int i = 0; i < n.n_packs; i++) HIP_TRY(hipMemcpy(n.pack[i], packed[i], (size_t)n.pack_dwords[i] * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(n.params, host_params, bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(n.m, 0, bytes));
+  HIP_TRY(hipMemset(n.v, 0, bytes));
+  HIP_TRY(hipMemcpy(n.state, &fresh, sizeof(fresh), hipMemcpyHostToDevice));
+  n.set = true, n.activation = activation, n.feature_norm = feature_norm;
   return 0;
 }
 
@@ -541,11 +527,11 @@ static void fill_stepping_facts(const sdc_handle* h, SdcSteppingFacts& f) {
   f.debug_flags = h->cfg.debug_flags;
   f.all_policies = sdc_all_policies(h->d.policy);
   for (int a = 0; a < 3; a++) {
-    f.actor_set[a] = h->actor_set[a];
-    f.actor_activation[a] = h->actor_activation[a];
+    f.actor_set[a] = h->actor[a].set;
+    f.actor_activation[a] = h->actor[a].activation;
   }
   f.latch_valid = h->latch_valid;
-  f.critic_set = h->critic_set;
+  f.critic_set = h->critic.set;
 }
 static SdcSteppingFacts stepping_facts(const sdc_handle* h) {
   SdcSteppingFacts f;
@@ -952,41 +938,24 @@ int sdc_rollout(sdc_handle* h, int n_steps, const int32_t* actions, float* obs, 
 int sdc_set_actor(sdc_handle* h, int slot, const sdc_actor_params* p) {
   if (refused(sdc_set_actor_refused(call_facts(h), slot, p))) return -2;
   HIP_TRY(hipSetDevice(h->device));
-  if (!h->actor_dev) {
-    if (dev_alloc(h, &h->actor_dev, 3) != 0) return -1;
-    if (dev_alloc(h, &h->actor_eval_dev, 3) != 0) return -1;
-    if (dev_alloc(h, &h->actor_grad_dev, 3) != 0) return -1;
-    if (dev_alloc(h, &h->actor_params, (size_t)3 * SDC_ACTOR_N_PARAMS) != 0) return -1;
-    if (dev_alloc(h, &h->actor_m, (size_t)3 * SDC_ACTOR_N_PARAMS) != 0) return -1;
-    if (dev_alloc(h, &h->actor_v, (size_t)3 * SDC_ACTOR_N_PARAMS) != 0) return -1;
-    if (dev_alloc(h, &h->actor_optim, 3) != 0) return -1;
-    if (upload_table(h, sdc_actor_pack_tables(), &h->actor_table, h->actor_table_offset) != 0) return -1;
+  if (!h->actor[0].params) {
+    if (nets_alloc(h, h->actor, 3, SDC_ACTOR_N_PARAMS, SDC_ACT_IN, SDC_ACTOR_GRAD_MAX_BLOCKS, sdc_actor_pack_tables()) != 0) return -1;
     if (dev_alloc(h, &h->obs_latch, (size_t)h->cfg.n_envs * SDC_OBS_OUT) != 0) return -1;
     h->latch_valid = false;      // (filled by the next reset / step / rollout)
   }
   // torch's [out][in] rows -> the kernel's k-major layout, four consecutive k per lane (sdc_actor.hpp)
   // (per call, on the heap: 26 KB is too large for the stack, and a function-static buffer would be shared by engines on
   // other host threads -- ctypes releases the GIL during this call)
-  std::unique_ptr<SdcActorDev> ap(new SdcActorDev);
-  SdcActorDev& a = *ap;
-  sdc_actor_pack(p, &a);
+  std::unique_ptr<SdcActorDev> loop(new SdcActorDev);
+  sdc_actor_pack(p, loop.get());
   // ... and the same parameters as sdc_actor_evaluate's kernel reads them (sdc_actor_eval_pack.hpp)
   std::unique_ptr<SdcActorEvalDev> packed(new SdcActorEvalDev);
   sdc_actor_eval_pack(p, packed.get());
   // ... and their transposes as sdc_actor_backward's kernel reads them (sdc_actor_grad_pack.hpp)
   std::unique_ptr<SdcActorGradDev> packed_t(new SdcActorGradDev);
   sdc_actor_grad_pack(p, packed_t.get());
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->actor_dev + slot, &a, sizeof(a), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->actor_eval_dev + slot, packed.get(), sizeof(SdcActorEvalDev), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->actor_grad_dev + slot, packed_t.get(), sizeof(SdcActorGradDev), hipMemcpyHostToDevice));
-  // ... and the optimiser's master copy, with a new optimiser (sdc_optim.hip)
-  const size_t at = (size_t)slot * SDC_ACTOR_N_PARAMS;
-  if (optim_reset(p, SDC_ACTOR_N_PARAMS, h->actor_params + at, h->actor_m + at, h->actor_v + at, h->actor_optim + slot) != 0) return -1;
-  h->actor_set[slot] = true;
-  h->actor_activation[slot] = p->activation;
-  h->actor_feature_norm[slot] = p->use_feature_normalization ? 1 : 0;
-  return 0;
+  const void* const packs[SDC_ACTOR_N_PACKS] = {loop.get(), packed.get(), packed_t.get()};
+  return net_install(h->actor[slot], p, packs, p->activation, p->use_feature_normalization != 0);
 }
 
 int sdc_rollout_actor(sdc_handle* h, int n_steps, int sample, float* obs, float* share_obs, float* rew, uint8_t* done,
@@ -1016,7 +985,7 @@ int sdc_rollout_actor(sdc_handle* h, int n_steps, int sample, float* obs, float*
   h->last_step_kernel = k.name;
   hipLaunchKernelGGL(quad ? sdc_rollout_actor_quad_kernel : sdc_rollout_actor_kernel, dim3(sdc_env_blocks(k, N)),
                      dim3(SDC_WAVE * k.waves_per_block), quad ? sdc_rollout_actor_quad_lds_bytes() : sdc_rollout_actor_lds_bytes(), st, d,
-                     n_steps, h->mirror.rel_hint(), h->actor_dev, h->obs_latch, sample ? 1 : 0, obs, share_obs, done, info, final_obs, rew,
+                     n_steps, h->mirror.rel_hint(), h->actor[0].pack_as<SdcActorDev>(SDC_ACTOR_PACK_LOOP), h->obs_latch, sample ? 1 : 0, obs, share_obs, done, info, final_obs, rew,
                      actions_out, logits_out, h->obs_latch);
   // (after an auto-reset alone: the next launch starts from the reset observations)
   const size_t last = (size_t)(n_steps - 1) * N;
@@ -1690,7 +1659,7 @@ static int plan_candidates(PlanSession& P, const int n_cand, const int32_t* acti
   // the plan critic (sdc_set_plan_critic): behind the score launch of the chunk that holds the horizon's last step, the critic's value
   // of that step's share_obs rows in the block, added into the candidate's score (sdc_critic.hip)
   const double critic_weight = h->plan_critic_weight;
-  SdcCriticTerminal V{h->critic_dev, nullptr, nullptr, (int)N, P.g_terminal * critic_weight, nullptr};
+  SdcCriticTerminal V{critic_dev(h), nullptr, nullptr, (int)N, P.g_terminal * critic_weight, nullptr};
   int rc = 0;
   for (int c = 0; c < n_cand && rc == 0; c++) {
     S.returns = returns ? returns + (size_t)c * N * 3 : nullptr;
@@ -1818,18 +1787,10 @@ int sdc_get_plan_terms(const sdc_handle* h, sdc_plan_terms* out) {
 // ---- the critic (sdc_critic.hip) -------------------------------------------------------------------------------------------------------
 // The contract: include/sustaindc_hip.h THE CRITIC; the pack and what is refused about the parameters: sdc_critic_pack.hpp.
 int sdc_set_critic(sdc_handle* h, const sdc_critic_params* p) {
-  static const std::string w = "sdc_set_critic: ";
-  if (!h || !p) return fail_msg(w + "null handle or params");
-  if (const char* why = sdc_critic_params_error(p)) return fail_msg(w + why);
+  if (refused(sdc_set_critic_refused(call_facts(h), p))) return -2;
   HIP_TRY(hipSetDevice(h->device));
-  if (!h->critic_dev && dev_alloc(h, &h->critic_dev, 1) != 0) return -1;
-  if (!h->critic_grad_dev && dev_alloc(h, &h->critic_grad_dev, 1) != 0) return -1;
-  if (!h->critic_params) {
-    if (dev_alloc(h, &h->critic_params, (size_t)SDC_CRITIC_N_PARAMS) != 0) return -1;
-    if (dev_alloc(h, &h->critic_m, (size_t)SDC_CRITIC_N_PARAMS) != 0) return -1;
-    if (dev_alloc(h, &h->critic_v, (size_t)SDC_CRITIC_N_PARAMS) != 0) return -1;
-    if (dev_alloc(h, &h->critic_optim, 1) != 0) return -1;
-    if (upload_table(h, sdc_critic_pack_tables(), &h->critic_table, h->critic_table_offset) != 0) return -1;
+  if (!h->critic.params) {
+    if (nets_alloc(h, &h->critic, 1, SDC_CRITIC_N_PARAMS, SDC_CRITIC_IN, SDC_CRITIC_GRAD_MAX_BLOCKS, sdc_critic_pack_tables()) != 0) return -1;
     if (dev_alloc(h, &h->value_norm, 1) != 0) return -1;
   }
   std::unique_ptr<SdcCriticDev> packed(new SdcCriticDev);      // (26 KB: on the heap, per call -- see sdc_set_actor)
@@ -1837,13 +1798,8 @@ int sdc_set_critic(sdc_handle* h, const sdc_critic_params* p) {
   // ... and the transposed weights as sdc_critic_backward's kernel reads them (sdc_critic_grad_pack.hpp)
   std::unique_ptr<SdcCriticGradDev> packed_t(new SdcCriticGradDev);
   sdc_critic_grad_pack(p, packed_t.get());
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(h->critic_dev, packed.get(), sizeof(SdcCriticDev), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->critic_grad_dev, packed_t.get(), sizeof(SdcCriticGradDev), hipMemcpyHostToDevice));
-  // ... and the optimiser's master copy, with a new optimiser (sdc_optim.hip)
-  if (optim_reset(p, SDC_CRITIC_N_PARAMS, h->critic_params, h->critic_m, h->critic_v, h->critic_optim) != 0) return -1;
-  h->critic_set = true;
-  h->critic_activation = (p->flags >> 1) & 3;
+  const void* const packs[SDC_CRITIC_N_PACKS] = {packed.get(), packed_t.get()};
+  if (net_install(h->critic, p, packs, (p->flags >> 1) & 3, (p->flags & 1) != 0) != 0) return -1;
   h->critic_scale = p->scale;
   h->critic_shift = p->shift;
   h->critic_flags = p->flags;
@@ -1856,7 +1812,7 @@ int sdc_critic_values(sdc_handle* h, const float* share_obs, long long n_rows, f
   HIP_TRY(hipSetDevice(h->device));
   h->last_step_kernel = "sdc_critic_values_kernel";
   return launched("sdc_critic_values_kernel",
-                  sdc_critic_values_launch(SdcCriticValues{h->critic_dev, share_obs, n_rows, values}, reinterpret_cast<hipStream_t>(stream)));
+                  sdc_critic_values_launch(SdcCriticValues{critic_dev(h), share_obs, n_rows, values}, reinterpret_cast<hipStream_t>(stream)));
 }
 
 // ---- the on-policy batch (sdc_onpolicy.hip) ------------------------------------------------------------------------------------------------
@@ -1887,7 +1843,7 @@ int sdc_gae(sdc_handle* h, int n_steps, const float* rew, int reward_agent, cons
   P.advantages = advantages;
   P.masks = masks;
   P.value_preds = value_preds;
-  P.critic = h->critic_dev;
+  P.critic = critic_dev(h);
   P.adv_part = h->adv_part;
   if (const int rc = launched("sdc_gae_kernel", sdc_gae_launch(P, st))) return rc;
   if (!moments) return 0;
@@ -1911,9 +1867,47 @@ int sdc_actor_evaluate(sdc_handle* h, int agent_slot, const float* obs, long lon
   if (refused(sdc_actor_evaluate_refused(call_facts(h), agent_slot, obs, row_stride, n_rows, logits, logits_stride))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   return launched("sdc_actor_eval_kernel",
-                  sdc_actor_eval_launch(SdcActorEval{h->actor_eval_dev + agent_slot, obs, row_stride, n_rows, logits, logits_stride},
+                  sdc_actor_eval_launch(SdcActorEval{h->actor[agent_slot].pack_as<SdcActorEvalDev>(SDC_ACTOR_PACK_EVAL), obs, row_stride, n_rows, logits, logits_stride},
                                         reinterpret_cast<hipStream_t>(stream)));
 }
+
+extern "C++" {
+// what sdc_ppo_terms' and sdc_ppo_dlogp's plans share: zeroed, then the elements, the agent, the four inputs and the clip range
+template <class Plan>
+static Plan ppo_plan(const sdc_handle* h, const int n_steps, const int agent, const float* new_log_probs, const float* old_log_probs,
+                     const float* advantages, const float* factor, const double clip_param) {
+  Plan P;
+  std::memset(&P, 0, sizeof(P));
+  P.n = (long long)n_steps * h->cfg.n_envs;
+  P.agent = agent;
+  P.new_lp = new_log_probs;
+  P.old_lp = old_log_probs;
+  P.adv = advantages;
+  P.factor = factor;
+  P.lo = 1.0 - clip_param;
+  P.hi = 1.0 + clip_param;
+  return P;
+}
+// both backward calls (sdc_rowmlp_grad.hpp) behind their plan `P`: the partials of the network's kind allocated on first use (`kind`: its
+// `count` records), the gradient kernel, then the B partials' fp64 sum into `grads` and, where grad_sq is given, its squares
+template <class Plan>
+static int net_backward(sdc_handle* h, SdcNet* kind, const int count, const SdcNet& n, Plan& P, const char* grad_kernel,
+                        hipError_t (*grad)(const Plan&, int, hipStream_t), const char* reduce_kernel,
+                        hipError_t (*reduce)(const SdcRowMlpGradReduce&, hipStream_t), const char* sq_kernel,
+                        hipError_t (*sq)(const SdcRowMlpGradSq&, hipStream_t), const long long n_rows, float* grads, double* grad_sq, hipStream_t st) {
+  if (!n.grad_part) {
+    float* part = nullptr;
+    if (dev_alloc(h, &part, (size_t)n.grad_max_blocks * n.n_params, false) != 0) return -1;
+    for (int i = 0; i < count; i++) kind[i].grad_part = part;
+  }
+  P.part = n.grad_part;
+  if (const int rc = launched(grad_kernel, grad(P, n.activation, st))) return rc;
+  const int n_part = sdc_rowmlp_grad_blocks(n_rows, n.grad_max_blocks);
+  if (const int rc = launched(reduce_kernel, reduce(SdcRowMlpGradReduce{n_part, n.grad_part, grads}, st))) return rc;
+  if (!grad_sq) return 0;
+  return launched(sq_kernel, sq(SdcRowMlpGradSq{grads, grad_sq}, st));
+}
+}  // extern "C++"
 
 int sdc_ppo_terms(sdc_handle* h, int n_steps, int agent, const float* new_log_probs, const float* old_log_probs, const float* entropy,
                   const float* advantages, const float* factor, double clip_param, float* ratio, float* surr, float* factor_out,
@@ -1924,17 +1918,8 @@ int sdc_ppo_terms(sdc_handle* h, int n_steps, int agent, const float* new_log_pr
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (stats && !h->ppo_part && dev_alloc(h, &h->ppo_part, (size_t)SDC_PPO_MAX_BLOCKS * SDC_PPO_STATS, false) != 0) return -1;
-  SdcPpoTerms P;
-  std::memset(&P, 0, sizeof(P));
-  P.n = (long long)n_steps * h->cfg.n_envs;
-  P.agent = agent;
-  P.new_lp = new_log_probs;
-  P.old_lp = old_log_probs;
+  SdcPpoTerms P = ppo_plan<SdcPpoTerms>(h, n_steps, agent, new_log_probs, old_log_probs, advantages, factor, clip_param);
   P.entropy = entropy;
-  P.adv = advantages;
-  P.factor = factor;
-  P.lo = 1.0 - clip_param;
-  P.hi = 1.0 + clip_param;
   P.ratio = ratio;
   P.surr = surr;
   P.factor_out = factor_out;
@@ -1951,28 +1936,10 @@ int sdc_ppo_dlogp(sdc_handle* h, int n_steps, int agent, const float* new_log_pr
   if (refused(sdc_ppo_dlogp_refused(call_facts(h), n_steps, agent, new_log_probs, old_log_probs, advantages, factor, clip_param, scale, dlogp)))
     return -2;
   HIP_TRY(hipSetDevice(h->device));
-  SdcPpoDlogp P;
-  std::memset(&P, 0, sizeof(P));
-  P.n = (long long)n_steps * h->cfg.n_envs;
-  P.agent = agent;
-  P.new_lp = new_log_probs;
-  P.old_lp = old_log_probs;
-  P.adv = advantages;
-  P.factor = factor;
-  P.lo = 1.0 - clip_param;
-  P.hi = 1.0 + clip_param;
+  SdcPpoDlogp P = ppo_plan<SdcPpoDlogp>(h, n_steps, agent, new_log_probs, old_log_probs, advantages, factor, clip_param);
   P.scale = scale;
   P.dlogp = dlogp;
   return launched("sdc_ppo_dlogp_kernel", sdc_ppo_dlogp_launch(P, reinterpret_cast<hipStream_t>(stream)));
-}
-
-// the tail of both backward calls (sdc_rowmlp_grad.hpp): the B partials' fp64 sum into `grads`, then, where grad_sq is given, its squares
-static int grads_from_partials(const char* reduce_kernel, hipError_t (*reduce)(const SdcRowMlpGradReduce&, hipStream_t), const char* sq_kernel,
-                               hipError_t (*sq)(const SdcRowMlpGradSq&, hipStream_t), const int n_part, const float* part, float* grads,
-                               double* grad_sq, hipStream_t st) {
-  if (const int rc = launched(reduce_kernel, reduce(SdcRowMlpGradReduce{n_part, part, grads}, st))) return rc;
-  if (!grad_sq) return 0;
-  return launched(sq_kernel, sq(SdcRowMlpGradSq{grads, grad_sq}, st));
 }
 
 int sdc_actor_backward(sdc_handle* h, int agent_slot, const float* obs, long long row_stride, long long n_rows, const int32_t* actions,
@@ -1981,11 +1948,11 @@ int sdc_actor_backward(sdc_handle* h, int agent_slot, const float* obs, long lon
     return -2;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (!h->actor_grad_part && dev_alloc(h, &h->actor_grad_part, (size_t)SDC_ACTOR_GRAD_MAX_BLOCKS * SDC_ACTOR_N_PARAMS, false) != 0) return -1;
+  const SdcNet& n = h->actor[agent_slot];
   SdcActorGrad P;
   std::memset(&P, 0, sizeof(P));
-  P.actor = h->actor_eval_dev + agent_slot;
-  P.actor_t = h->actor_grad_dev + agent_slot;
+  P.actor = n.pack_as<SdcActorEvalDev>(SDC_ACTOR_PACK_EVAL);
+  P.actor_t = n.pack_as<SdcActorGradDev>(SDC_ACTOR_PACK_GRAD);
   P.obs = obs;
   P.row_stride = row_stride;
   P.n_rows = n_rows;
@@ -1993,10 +1960,8 @@ int sdc_actor_backward(sdc_handle* h, int agent_slot, const float* obs, long lon
   P.action_stride = action_stride;
   P.dlogp = dlogp;
   P.dent = dent;
-  P.part = h->actor_grad_part;
-  if (const int rc = launched("sdc_actor_grad_kernel", sdc_actor_grad_launch(P, h->actor_activation[agent_slot], st))) return rc;
-  return grads_from_partials("sdc_actor_grad_reduce_kernel", sdc_actor_grad_reduce_launch, "sdc_actor_grad_sq_kernel", sdc_actor_grad_sq_launch,
-                             sdc_rowmlp_grad_blocks(n_rows, SDC_ACTOR_GRAD_MAX_BLOCKS), h->actor_grad_part, grads, grad_sq, st);
+  return net_backward(h, h->actor, 3, n, P, "sdc_actor_grad_kernel", sdc_actor_grad_launch, "sdc_actor_grad_reduce_kernel",
+                      sdc_actor_grad_reduce_launch, "sdc_actor_grad_sq_kernel", sdc_actor_grad_sq_launch, n_rows, grads, grad_sq, st);
 }
 
 // ---- the critic's gradient (sdc_critic_grad.hip) -------------------------------------------------------------------------------------
@@ -2005,15 +1970,14 @@ int sdc_critic_evaluate(sdc_handle* h, const float* share_obs, long long n_rows,
   if (refused(sdc_critic_evaluate_refused(call_facts(h), share_obs, n_rows, raw_values))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   return launched("sdc_critic_raw_kernel",
-                  sdc_critic_raw_launch(SdcCriticRaw{h->critic_dev, share_obs, n_rows, raw_values}, reinterpret_cast<hipStream_t>(stream)));
+                  sdc_critic_raw_launch(SdcCriticRaw{critic_dev(h), share_obs, n_rows, raw_values}, reinterpret_cast<hipStream_t>(stream)));
 }
 
-int sdc_value_loss(sdc_handle* h, long long n, const float* raw_values, const float* value_preds, const float* returns, double target_scale,
-                   double target_shift, double clip_param, double huber_delta, int flags, double coef, float* loss, float* dvalue,
-                   double* stats, void* stream) {
-  if (refused(sdc_value_loss_refused(call_facts(h), n, raw_values, value_preds, returns, target_scale, target_shift, clip_param, huber_delta,
-                                     flags, coef, loss, dvalue, stats)))
-    return -2;
+// sdc_value_loss and sdc_value_loss_normed behind their rule: the plan but for the targets' scale and shift (the caller's, or read from
+// the ValueNorm `block` on the device), stage 1's partial statistics allocated on first use, and stage 2
+static int value_loss(sdc_handle* h, const long long n, const float* raw_values, const float* value_preds, const float* returns,
+                      const double target_scale, const double target_shift, const SdcValueNormDev* block, const double clip_param,
+                      const double huber_delta, const int flags, const double coef, float* loss, float* dvalue, double* stats, void* stream) {
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (stats && !h->value_loss_part && dev_alloc(h, &h->value_loss_part, (size_t)SDC_PPO_MAX_BLOCKS * SDC_PPO_STATS, false) != 0) return -1;
@@ -2032,10 +1996,22 @@ int sdc_value_loss(sdc_handle* h, long long n, const float* raw_values, const fl
   P.loss = loss;
   P.dvalue = dvalue;
   P.part = stats ? h->value_loss_part : nullptr;
-  if (const int rc = launched("sdc_value_loss_kernel", sdc_value_loss_launch(P, st))) return rc;
+  if (const int rc = block ? launched("sdc_value_loss_normed_kernel", sdc_value_loss_normed_launch(P, block, st))
+                           : launched("sdc_value_loss_kernel", sdc_value_loss_launch(P, st)))
+    return rc;
   if (!stats) return 0;
   // (stage 2 is sdc_ppo_terms' own: the same seven folds over the partials)
   return launched("sdc_ppo_stats_kernel", sdc_ppo_stats_launch(SdcPpoStats{sdc_ppo_blocks(n), (double)n, h->value_loss_part, stats}, st));
+}
+
+int sdc_value_loss(sdc_handle* h, long long n, const float* raw_values, const float* value_preds, const float* returns, double target_scale,
+                   double target_shift, double clip_param, double huber_delta, int flags, double coef, float* loss, float* dvalue,
+                   double* stats, void* stream) {
+  if (refused(sdc_value_loss_refused(call_facts(h), n, raw_values, value_preds, returns, target_scale, target_shift, clip_param, huber_delta,
+                                     flags, coef, loss, dvalue, stats)))
+    return -2;
+  return value_loss(h, n, raw_values, value_preds, returns, target_scale, target_shift, nullptr, clip_param, huber_delta, flags, coef, loss,
+                    dvalue, stats, stream);
 }
 
 int sdc_critic_backward(sdc_handle* h, const float* share_obs, long long n_rows, const float* dvalue, float* grads, double* grad_sq,
@@ -2043,18 +2019,15 @@ int sdc_critic_backward(sdc_handle* h, const float* share_obs, long long n_rows,
   if (refused(sdc_critic_backward_refused(call_facts(h), share_obs, n_rows, dvalue, grads, grad_sq))) return -2;
   HIP_TRY(hipSetDevice(h->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (!h->critic_grad_part && dev_alloc(h, &h->critic_grad_part, (size_t)SDC_CRITIC_GRAD_MAX_BLOCKS * SDC_CRITIC_N_PARAMS, false) != 0) return -1;
   SdcCriticGrad P;
   std::memset(&P, 0, sizeof(P));
-  P.critic = h->critic_dev;
-  P.critic_t = h->critic_grad_dev;
+  P.critic = critic_dev(h);
+  P.critic_t = h->critic.pack_as<SdcCriticGradDev>(SDC_CRITIC_PACK_GRAD);
   P.rows = share_obs;
   P.n_rows = n_rows;
   P.dvalue = dvalue;
-  P.part = h->critic_grad_part;
-  if (const int rc = launched("sdc_critic_grad_kernel", sdc_critic_grad_launch(P, h->critic_activation, st))) return rc;
-  return grads_from_partials("sdc_critic_grad_reduce_kernel", sdc_critic_grad_reduce_launch, "sdc_critic_grad_sq_kernel", sdc_critic_grad_sq_launch,
-                             sdc_rowmlp_grad_blocks(n_rows, SDC_CRITIC_GRAD_MAX_BLOCKS), h->critic_grad_part, grads, grad_sq, st);
+  return net_backward(h, &h->critic, 1, h->critic, P, "sdc_critic_grad_kernel", sdc_critic_grad_launch, "sdc_critic_grad_reduce_kernel",
+                      sdc_critic_grad_reduce_launch, "sdc_critic_grad_sq_kernel", sdc_critic_grad_sq_launch, n_rows, grads, grad_sq, st);
 }
 
 int sdc_set_plan_critic(sdc_handle* h, double weight) {
@@ -2071,116 +2044,87 @@ int sdc_get_plan_critic(const sdc_handle* h, double* weight) {
 
 // ---- the optimiser step (sdc_optim.hip) ------------------------------------------------------------------------------------------------
 // The contract and the arithmetic: include/sustaindc_hip.h THE OPTIMISER STEP; the kernel's plan: sdc_optim_dev.hpp.
+static int net_adam_step(sdc_handle* h, const SdcNet& n, const float* grads, const sdc_adam* adam, double* grad_norm, void* stream) {
+  HIP_TRY(hipSetDevice(h->device));
+  h->last_step_kernel = "sdc_adam_gather_kernel";
+  return launched("sdc_adam_update_kernel / sdc_adam_gather_kernel",
+                  sdc_adam_step_launch(sdc_net_adam_plan(n, grads, *adam, grad_norm), reinterpret_cast<hipStream_t>(stream)));
+}
 int sdc_actor_adam_step(sdc_handle* h, int agent_slot, const float* grads, const sdc_adam* adam, double* grad_norm, void* stream) {
   if (refused(sdc_adam_step_refused("sdc_actor_adam_step", call_facts(h), true, agent_slot, grads, adam, grad_norm))) return -2;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t at = (size_t)agent_slot * SDC_ACTOR_N_PARAMS;
-  SdcAdamStep P{};
-  P.grads = grads;
-  P.params = h->actor_params + at;
-  P.m = h->actor_m + at;
-  P.v = h->actor_v + at;
-  P.state = h->actor_optim + agent_slot;
-  P.grad_norm = grad_norm;
-  P.adam = *adam;
-  P.n = SDC_ACTOR_N_PARAMS;
-  P.first = h->actor_feature_norm[agent_slot] ? 0 : 2 * SDC_ACT_IN;
-  P.n_packs = 3;
-  P.table = h->actor_table;
-  P.pack[0] = reinterpret_cast<uint32_t*>(h->actor_dev + agent_slot);
-  P.pack[1] = reinterpret_cast<uint32_t*>(h->actor_eval_dev + agent_slot);
-  P.pack[2] = reinterpret_cast<uint32_t*>(h->actor_grad_dev + agent_slot);
-  for (int i = 0; i < 3; i++) P.pack_dwords[i] = h->actor_table_offset[i + 1] - h->actor_table_offset[i];
-  h->last_step_kernel = "sdc_adam_gather_kernel";
-  return launched("sdc_adam_update_kernel / sdc_adam_gather_kernel", sdc_adam_step_launch(P, reinterpret_cast<hipStream_t>(stream)));
+  return net_adam_step(h, h->actor[agent_slot], grads, adam, grad_norm, stream);
 }
-
 int sdc_critic_adam_step(sdc_handle* h, const float* grads, const sdc_adam* adam, double* grad_norm, void* stream) {
   if (refused(sdc_adam_step_refused("sdc_critic_adam_step", call_facts(h), false, -1, grads, adam, grad_norm))) return -2;
+  return net_adam_step(h, h->critic, grads, adam, grad_norm, stream);
+}
+
+// the master parameters of a network -> the leading floats of its params struct (the device is waited for)
+static int net_params_get(sdc_handle* h, const SdcNet& n, void* out) {
   HIP_TRY(hipSetDevice(h->device));
-  SdcAdamStep P{};
-  P.grads = grads;
-  P.params = h->critic_params;
-  P.m = h->critic_m;
-  P.v = h->critic_v;
-  P.state = h->critic_optim;
-  P.grad_norm = grad_norm;
-  P.adam = *adam;
-  P.n = SDC_CRITIC_N_PARAMS;
-  P.first = (h->critic_flags & 1) ? 0 : 2 * SDC_CRITIC_IN;
-  P.n_packs = 2;
-  P.table = h->critic_table;
-  P.pack[0] = reinterpret_cast<uint32_t*>(h->critic_dev);
-  P.pack[1] = reinterpret_cast<uint32_t*>(h->critic_grad_dev);
-  for (int i = 0; i < 2; i++) P.pack_dwords[i] = h->critic_table_offset[i + 1] - h->critic_table_offset[i];
-  h->last_step_kernel = "sdc_adam_gather_kernel";
-  return launched("sdc_adam_update_kernel / sdc_adam_gather_kernel", sdc_adam_step_launch(P, reinterpret_cast<hipStream_t>(stream)));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, n.params, sizeof(float) * n.n_params, hipMemcpyDeviceToHost));
+  return 0;
+}
+// the critic's scale and shift now: the ValueNorm block's while one is installed (one device read: sdc_value_norm_update moves them
+// without the host), else the host record
+static int critic_norm_now(sdc_handle* h, float* scale, float* shift) {
+  SdcValueNormDev vn{};
+  vn.scale = h->critic_scale, vn.shift = h->critic_shift;
+  if (h->value_norm_installed) HIP_TRY(hipMemcpy(&vn, h->value_norm, sizeof(vn), hipMemcpyDeviceToHost));
+  *scale = vn.scale, *shift = vn.shift;
+  return 0;
 }
 
 int sdc_get_actor(sdc_handle* h, int agent_slot, sdc_actor_params* out) {
   if (refused(sdc_optim_get_refused("sdc_get_actor", call_facts(h), true, agent_slot, out != nullptr))) return -2;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, h->actor_params + (size_t)agent_slot * SDC_ACTOR_N_PARAMS, sizeof(float) * SDC_ACTOR_N_PARAMS, hipMemcpyDeviceToHost));
-  out->use_feature_normalization = h->actor_feature_norm[agent_slot];
-  out->activation = h->actor_activation[agent_slot];
+  const SdcNet& n = h->actor[agent_slot];
+  if (net_params_get(h, n, out) != 0) return -1;
+  out->use_feature_normalization = n.feature_norm ? 1 : 0;
+  out->activation = n.activation;
   return 0;
 }
 
 int sdc_get_critic(sdc_handle* h, sdc_critic_params* out) {
   if (refused(sdc_optim_get_refused("sdc_get_critic", call_facts(h), false, -1, out != nullptr))) return -2;
-  HIP_TRY(hipSetDevice(h->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out, h->critic_params, sizeof(float) * SDC_CRITIC_N_PARAMS, hipMemcpyDeviceToHost));
-  out->scale = h->critic_scale;
-  out->shift = h->critic_shift;
+  if (net_params_get(h, h->critic, out) != 0) return -1;
   out->flags = h->critic_flags;
-  if (h->value_norm_installed) {      // (the device's: sdc_value_norm_update moves them without the host)
-    SdcValueNormDev vn;
-    HIP_TRY(hipMemcpy(&vn, h->value_norm, sizeof(vn), hipMemcpyDeviceToHost));
-    out->scale = vn.scale;
-    out->shift = vn.shift;
-  }
-  return 0;
+  return critic_norm_now(h, &out->scale, &out->shift);
 }
 
 // the moments and the state block of one network <-> host memory (the device is waited for)
-static int optim_get(sdc_handle* h, const size_t n, const float* dm, const float* dv, const sdc_optim_state* ds, float* m, float* v,
-                     sdc_optim_state* st) {
+static int net_optim_get(sdc_handle* h, const SdcNet& n, float* m, float* v, sdc_optim_state* st) {
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(m, dm, n * sizeof(float), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(v, dv, n * sizeof(float), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(st, ds, sizeof(*st), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(m, n.m, n.n_params * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(v, n.v, n.n_params * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(st, n.state, sizeof(*st), hipMemcpyDeviceToHost));
   return 0;
 }
-static int optim_put(sdc_handle* h, const size_t n, float* dm, float* dv, sdc_optim_state* ds, const float* m, const float* v,
-                     const sdc_optim_state* st) {
+static int net_optim_put(sdc_handle* h, const SdcNet& n, const float* m, const float* v, const sdc_optim_state* st) {
   HIP_TRY(hipSetDevice(h->device));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(dm, m, n * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(dv, v, n * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ds, st, sizeof(*st), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(n.m, m, n.n_params * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(n.v, v, n.n_params * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(n.state, st, sizeof(*st), hipMemcpyHostToDevice));
   return 0;
 }
 
 int sdc_get_actor_optim(sdc_handle* h, int agent_slot, float* m, float* v, sdc_optim_state* st) {
   if (refused(sdc_optim_get_refused("sdc_get_actor_optim", call_facts(h), true, agent_slot, m && v && st))) return -2;
-  const size_t at = (size_t)agent_slot * SDC_ACTOR_N_PARAMS;
-  return optim_get(h, SDC_ACTOR_N_PARAMS, h->actor_m + at, h->actor_v + at, h->actor_optim + agent_slot, m, v, st);
+  return net_optim_get(h, h->actor[agent_slot], m, v, st);
 }
 int sdc_set_actor_optim(sdc_handle* h, int agent_slot, const float* m, const float* v, const sdc_optim_state* st) {
   if (refused(sdc_set_optim_refused("sdc_set_actor_optim", call_facts(h), true, agent_slot, m, v, st))) return -2;
-  const size_t at = (size_t)agent_slot * SDC_ACTOR_N_PARAMS;
-  return optim_put(h, SDC_ACTOR_N_PARAMS, h->actor_m + at, h->actor_v + at, h->actor_optim + agent_slot, m, v, st);
+  return net_optim_put(h, h->actor[agent_slot], m, v, st);
 }
 int sdc_get_critic_optim(sdc_handle* h, float* m, float* v, sdc_optim_state* st) {
   if (refused(sdc_optim_get_refused("sdc_get_critic_optim", call_facts(h), false, -1, m && v && st))) return -2;
-  return optim_get(h, SDC_CRITIC_N_PARAMS, h->critic_m, h->critic_v, h->critic_optim, m, v, st);
+  return net_optim_get(h, h->critic, m, v, st);
 }
 int sdc_set_critic_optim(sdc_handle* h, const float* m, const float* v, const sdc_optim_state* st) {
   if (refused(sdc_set_optim_refused("sdc_set_critic_optim", call_facts(h), false, -1, m, v, st))) return -2;
-  return optim_put(h, SDC_CRITIC_N_PARAMS, h->critic_m, h->critic_v, h->critic_optim, m, v, st);
+  return net_optim_put(h, h->critic, m, v, st);
 }
 
 int sdc_set_critic_norm(sdc_handle* h, double scale, double shift, void* stream) {
@@ -2190,7 +2134,7 @@ int sdc_set_critic_norm(sdc_handle* h, double scale, double shift, void* stream)
   h->critic_shift = (float)shift;
   h->value_norm_installed = false;      // (scale and shift set by hand: no running state)
   return launched("sdc_critic_norm_kernel",
-                  sdc_critic_norm_launch(SdcCriticNorm{h->critic_dev, h->critic_scale, h->critic_shift}, reinterpret_cast<hipStream_t>(stream)));
+                  sdc_critic_norm_launch(SdcCriticNorm{critic_dev(h), h->critic_scale, h->critic_shift}, reinterpret_cast<hipStream_t>(stream)));
 }
 
 // ---- train on the device (sdc_minibatch.hip) ---------------------------------------------------------------------------------------------
@@ -2230,11 +2174,7 @@ int sdc_set_value_norm(sdc_handle* h, const sdc_value_norm* st) {
   HIP_TRY(hipDeviceSynchronize());
   SdcValueNormDev vn{};
   if (!st) {      // uninstall: the critic keeps the scale and shift it has, and the host record follows them
-    if (h->value_norm_installed) {
-      HIP_TRY(hipMemcpy(&vn, h->value_norm, sizeof(vn), hipMemcpyDeviceToHost));
-      h->critic_scale = vn.scale;
-      h->critic_shift = vn.shift;
-    }
+    if (critic_norm_now(h, &h->critic_scale, &h->critic_shift) != 0) return -1;
     h->value_norm_installed = false;
     return 0;
   }
@@ -2243,8 +2183,8 @@ int sdc_set_value_norm(sdc_handle* h, const sdc_value_norm* st) {
   vn.debiasing_term = st->debiasing_term;
   sdc_value_norm_derive(vn);
   HIP_TRY(hipMemcpy(h->value_norm, &vn, sizeof(vn), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(&h->critic_dev->scale, &vn.scale, sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(&h->critic_dev->shift, &vn.shift, sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(&critic_dev(h)->scale, &vn.scale, sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(&critic_dev(h)->shift, &vn.shift, sizeof(float), hipMemcpyHostToDevice));
   h->critic_scale = vn.scale;
   h->critic_shift = vn.shift;
   h->value_norm_installed = true;
@@ -2268,7 +2208,7 @@ int sdc_value_norm_update(sdc_handle* h, const float* returns, long long n, doub
   const int B = sdc_value_norm_blocks(n);
   return launched("sdc_value_norm_sums_kernel / sdc_value_norm_update_kernel",
                   sdc_value_norm_update_launch(SdcValueNormSums{returns, n, h->value_norm_part},
-                                               SdcValueNormUpdate{B, n, beta, h->value_norm_part, h->value_norm, h->critic_dev},
+                                               SdcValueNormUpdate{B, n, beta, h->value_norm_part, h->value_norm, critic_dev(h)},
                                                reinterpret_cast<hipStream_t>(stream)));
 }
 
@@ -2278,25 +2218,8 @@ int sdc_value_loss_normed(sdc_handle* h, long long n, const float* raw_values, c
   if (refused(sdc_value_loss_normed_refused(call_facts(h), h && h->value_norm_installed, n, raw_values, value_preds, returns, clip_param,
                                             huber_delta, flags, coef, loss, dvalue, stats)))
     return -2;
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (stats && !h->value_loss_part && dev_alloc(h, &h->value_loss_part, (size_t)SDC_PPO_MAX_BLOCKS * SDC_PPO_STATS, false) != 0) return -1;
-  SdcValueLoss P;
-  std::memset(&P, 0, sizeof(P));
-  P.n = n;
-  P.raw = raw_values;
-  P.vp = value_preds;
-  P.ret = returns;
-  P.clip = clip_param;
-  P.delta = (flags & SDC_VALUE_LOSS_HUBER) ? huber_delta : 0.0;
-  P.coef = coef;
-  P.flags = flags;
-  P.loss = loss;
-  P.dvalue = dvalue;
-  P.part = stats ? h->value_loss_part : nullptr;
-  if (const int rc = launched("sdc_value_loss_normed_kernel", sdc_value_loss_normed_launch(P, h->value_norm, st))) return rc;
-  if (!stats) return 0;
-  return launched("sdc_ppo_stats_kernel", sdc_ppo_stats_launch(SdcPpoStats{sdc_ppo_blocks(n), (double)n, h->value_loss_part, stats}, st));
+  return value_loss(h, n, raw_values, value_preds, returns, 0.0, 0.0, h->value_norm, clip_param, huber_delta, flags, coef, loss, dvalue, stats,
+                    stream);
 }
 
 // ---- plan with the cross-entropy method (sdc_cem.hip, sdc_cem_groups.hip) -----------------------------------------------------------

@@ -16,9 +16,10 @@
 // Built with -DSDC_OPTIM_ONE_LAUNCH the same body runs as ONE launch of one workgroup with a barrier between update and gather
 // (sdc_adam_step_kernel): the form this one was measured against with tools/update_rate.py and found 0.010 ms slower per step
 // (DESIGN.md section 4.31).
+//
+// THE PLANS ARE PLAIN TYPES: up to the launchers this header holds no HIP, and a host compiler alone builds it (sdc_nets.hpp derives
+// SdcAdamStep from a network's record; tests/test_host_nets.py holds that without a GPU).
 #pragma once
-
-#include <hip/hip_runtime.h>
 
 #include <cstdint>
 
@@ -50,5 +51,9 @@ struct SdcCriticNorm {
   float scale, shift;
 };
 
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+
 hipError_t sdc_adam_step_launch(const SdcAdamStep& P, hipStream_t st);
 hipError_t sdc_critic_norm_launch(const SdcCriticNorm& P, hipStream_t st);
+#endif

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/sustaindc_hip.h"
+#include "sdc_critic_pack.hpp"
 #include "sdc_dispatch.hpp"
 #include "sdc_mirror.hpp"
 #include "sdc_mpc_schedule.hpp"
@@ -543,6 +544,14 @@ static inline SdcMsg sdc_set_plan_terms_refused(const SdcCallFacts& f, const sdc
 }
 
 // ---- the critic ---------------------------------------------------------------------------------------------------------------------------
+// (what is refused about the parameters themselves: sdc_critic_pack.hpp sdc_critic_params_error, which reads every float of the struct)
+static inline SdcMsg sdc_set_critic_refused(const SdcCallFacts& f, const sdc_critic_params* p) {
+  static const std::string w = "sdc_set_critic: ";
+  if (!f.handle || !p) return w + "null handle or params";
+  if (const char* why = sdc_critic_params_error(p)) return w + why;
+  return std::nullopt;
+}
+
 static inline SdcMsg sdc_critic_values_refused(const SdcCallFacts& f, const float* share_obs, const long long n_rows, const float* values) {
   static const std::string w = "sdc_critic_values: ";
   if (!f.handle) return w + "null handle";

@@ -19,7 +19,7 @@ ENTRY_POINTS = (
     "sdc_profile_enable", "sdc_profile_read", "sdc_get_state", "sdc_set_state", "sdc_clone_envs", "sdc_snapshot_envs", "sdc_restore_envs",
     "sdc_mark_envs", "sdc_rewind_envs", "sdc_set_plan_forecast", "sdc_forecast_traces", "sdc_plan", "sdc_set_plan_terms", "sdc_critic_values",
     "sdc_set_plan_critic", "sdc_plan_cem", "sdc_plan_cem_groups", "sdc_rollout_stats", "sdc_rollout_actor_stats", "sdc_rollout_cem_stats",
-    "sdc_rollout_cem_groups_stats")
+    "sdc_rollout_cem_groups_stats", "sdc_set_critic")
 ONE_RULE = ("sdc_profile_enable", "sdc_profile_read")      # (a single rule each: no pair to order)
 
 
@@ -508,7 +508,27 @@ no(E, "n_limits = 9 outside [0, 8]", two=True, n_limits=9, n_terminal=9)
 no(E, "limit_side[0] = 2 is neither +1 (upper) nor -1 (lower)", two=True, **dict(LIMIT, limit_side=[2], limit_bound=[INF]))
 no(E, "limit_weight[0] = -1.000000 is negative", two=True, n_terminal=1, terminal_col=[44], terminal_weight=[1.0], **dict(LIMIT, limit_weight=[-1.0]))
 
-# ---- sdc_critic_values, sdc_set_plan_critic --------------------------------------------------------------------------------------------------
+# ---- sdc_set_critic, sdc_critic_values, sdc_set_plan_critic ------------------------------------------------------------------------------------
+# (the parameters: zeros but scale 1, shift 0, flags 0 and what a case plants -- b3 stands for any of the 6459)
+E = "sdc_set_critic"
+FLAG_BITS = "unknown flag bits (bit 0: feature LayerNorm, bits 1-2: activation)"
+ok(E)
+ok(E, flags=3)      # (the feature LayerNorm on, relu)
+ok(E, flags=2, scale=1e-30, shift=-1e30, b3=-7.5)
+no(E, "null handle or params", facts=dict(handle=0), wire=True)
+no(E, "null handle or params", p=0)
+no(E, "an entry that is not finite", b3=float("nan"))
+no(E, "an entry that is not finite", shift=-INF)
+no(E, "an entry that is not finite", scale=INF)
+no(E, "scale must be positive", scale=0.0)
+no(E, "scale must be positive", scale=-2.5)
+no(E, FLAG_BITS, flags=8)
+no(E, FLAG_BITS, flags=-1)
+no(E, "unknown activation code (0 tanh, 1 relu)", flags=4)
+no(E, "unknown activation code (0 tanh, 1 relu)", flags=7)
+no(E, "an entry that is not finite", two=True, b3=INF, scale=0.0)
+no(E, "scale must be positive", two=True, scale=0.0, flags=8)
+no(E, FLAG_BITS, two=True, flags=12)      # (and bits 1-2 say 2)
 E = "sdc_critic_values"
 ok(E, facts=dict(critic=1))
 no(E, "null handle", facts=dict(handle=0), wire=True)

@@ -159,6 +159,10 @@ class Rig:
                 for j, v in enumerate(a.get(k, [])[:8]):
                     getattr(t, k)[j] = v
             rc = lib.sdc_set_plan_terms(H, C.byref(t) if a.get("terms", 1) else None)
+        elif e == "sdc_set_critic":
+            p = L.SdcCriticParams()
+            p.b3, p.scale, p.shift, p.flags = a.get("b3", 0.0), a.get("scale", 1.0), a.get("shift", 0.0), a.get("flags", 0)
+            rc = lib.sdc_set_critic(H, C.byref(p) if a.get("p", 1) else None)
         elif e == "sdc_critic_values":
             rc = lib.sdc_critic_values(H, *self.d(a, "share_obs"), a.get("n_rows", 1), *self.d(a, "values"), None)
         elif e == "sdc_set_plan_critic":

@@ -275,6 +275,10 @@ static bool answer(const std::string& e) {
       if (j < tw.size()) t.terminal_weight[j] = tw[j];
     }
     out(sdc_set_plan_terms_refused(f, I("terms", 1) ? &t : nullptr, kept));
+  } else if (e == "sdc_set_critic") {
+    static sdc_critic_params p;
+    p.b3 = (float)D("b3", 0.0), p.scale = (float)D("scale", 1.0), p.shift = (float)D("shift", 0.0), p.flags = (int)I("flags", 0);
+    out(sdc_set_critic_refused(f, I("p", 1) ? &p : nullptr));
   } else if (e == "sdc_critic_values") {
     out(sdc_critic_values_refused(f, P<float>("share_obs"), I("n_rows", 1), P<float>("values")));
   } else if (e == "sdc_set_plan_critic") {
@@ -393,7 +397,7 @@ def test_every_case_under_the_address_and_undefined_behaviour_sanitizers(plain, 
 def test_the_table_covers_what_it_says():
     """every entry point of the header has an acceptance with no key changed but the facts it needs, a refusal, and a case of two faults"""
     entries = {c.entry for c in RC.CASES}
-    assert entries == set(RC.ENTRY_POINTS) and len(entries) == 29
+    assert entries == set(RC.ENTRY_POINTS) and len(entries) == 30
     for e in RC.ENTRY_POINTS:
         mine = [c for c in RC.CASES if c.entry == e]
         assert any(c.text is None for c in mine), e
